@@ -7,8 +7,10 @@ Contract: python bench.py --gpus N --steps K --warmup W  prints ONE JSON line on
               10 % outliers): flatten + alpha / alpha_k, RANSAC (50 trials, tol 0.05: 9-point minimal solver, hypothesis-batched
               Ceres-LM depth solves of ALL pixels, scoring, best trial, compaction), joint nonlinear refinement, sign fix + depth
               map, per-scanline pose table (reference main.cc:398-522), ONE C-ABI call per pair (rsdsfm_solve_frame_dev), one
-              pair at a time.  `value` = pixels of the K timed pairs / the time of the K steps; `median_ms_per_solve` beside it.
-              Sub-records of the line:
+              pair at a time.  `value` = pixels of the K timed pairs / the time of the K steps; `median_ms_per_solve` beside it;
+              `ms_per_step` = the time of the K steps / K.  A plain run stops there (set-up, W warm-up steps, K timed steps, the line);
+              --dump-outputs DIR writes what the last timed solve returned (depth map, pose table, poses, counts) as DIR/<name>.npy.
+              Sub-records of the line, measured only with --full:
                 roofline            the dominant kernel ransac_lma_kernel<2, true> (fp64 VALU bound: counted fp64 lane-instructions / its
                                     launch duration, measured here with HIP events, / 39.3e12; counts from profiles/counters.json, which
                                     is stamped with the kernel source hashes -- `counters_stale` when they do not match) and, under
@@ -242,7 +244,7 @@ def parse_args(argv=None):
     ap.add_argument("--workload", default="full", choices=["depth", "depth_closed_form", "full", "tiled", "tiled_full", "rectify", "true_flow", "metrics", "launch_check"])
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--sequence-only", action="store_true", help="full workload: only the sequence solve (rsdsfm_solve_frames_dev), --steps passes of 32 pairs (profiling runs)")
-    ap.add_argument("--no-side-records", action="store_true", help="full workload: skip depth_only / full_solve_batched / full_solve_fused (profiling runs)")
+    ap.add_argument("--no-side-records", action="store_true", help="full workload with --full: skip depth_only / full_solve_batched / full_solve_fused / ... / tiled_full (profiling runs)")
     ap.add_argument("--tiled-driver", default="native", choices=["native", "python"], help="tiled / tiled_full: the C++ driver inside the library (default) or the Python driver")
     ap.add_argument("--arith", default="reference", choices=["reference", "fused"], help="library: 'reference' = the default librsdsfm_hip.so (see --help's header), 'fused' = the opt-in fused-fma build")
     ap.add_argument("--nbuf", type=int, default=7, help="rotating HBM buffer sets (7 x 59 MB > 256 MiB L3)")
@@ -257,12 +259,17 @@ def parse_args(argv=None):
     ap.add_argument("--launch-grace", type=float, default=10.0, help="launcher: seconds the other ranks get after one rank failed")
     ap.add_argument("--hang-dump", type=float, default=0.0, help="seconds after which every thread's Python stack is written to stderr (diagnosing a bench that does not come back); 0 = off")
     ap.add_argument("--tiled-timeout", type=float, default=240.0, help="full workload: watchdog of the tiled_full (strong scaling) sub-record; on expiry the line is printed without it")
+    ap.add_argument("--full", action="store_true", help="full workload: also measure the sub-records (roofline, refine_pass, cpu_baseline, side records, tiled_full); "
+                                                         "without it the run times the headline steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="full workload: write what the last timed solve returned as DIR/<name>.npy (float64)")
     args = ap.parse_args(argv)
     dsteps = {"depth": 160, "depth_closed_form": 160, "full": 100, "tiled": 2000, "tiled_full": 100, "rectify": 2000, "true_flow": 500, "metrics": 2000, "launch_check": 3}
     if args.steps is None:
         args.steps = dsteps[args.workload]
     if args.warmup is None:
         args.warmup = max(3, args.steps // 25)
+    if args.dump_outputs and (args.workload != "full" or args.sequence_only):
+        ap.error("--dump-outputs: only the full workload's one-call solve")
     return args
 
 
@@ -681,9 +688,12 @@ def run(args):
                          "full_solve_batched": rec, "roofline": None, "cpu_baseline": None})
 
     elif args.workload == "full":
-        full = _full_solve(rsdsfm, solver, torch, dev, np, rank, args, steps=args.steps, warmup=args.warmup, timed=timed)
-        roof = _full_roofline(rsdsfm, solver, torch, dev, np, stream, args, full) if rank == 0 else None
-        side = not args.no_side_records
+        full = _full_solve(rsdsfm, solver, torch, dev, np, rank, args, steps=args.steps, warmup=args.warmup, timed=timed, outputs=bool(args.dump_outputs))
+        if rank == 0 and args.dump_outputs:
+            _dump_outputs(args.dump_outputs, full.pop("_outputs"))
+        # a plain run stops at the headline; --full adds the sub-records below
+        roof = _full_roofline(rsdsfm, solver, torch, dev, np, stream, args, full) if rank == 0 and args.full else None
+        side = args.full and not args.no_side_records
         # sequence-throughput mode (BASELINE configs[4]): 32 pairs with 32 data seeds through ONE context of each GPU
         batched = _full_solve_sequence(rsdsfm, solver, torch, dev, np, rank, args) if side else None
         fused = depth_only = regimes = threads8 = exact_kernel = host_boundary = None
@@ -714,8 +724,10 @@ def run(args):
                                     "pairs": "the timed steps rotate over %d different pairs (data seeds) and a new sampler seed per step" % full["data_seeds"],
                                     **{k2: full[k2] for k2 in ("rows", "cols", "trials", "tol", "n", "num_inliers", "data_seeds", "num_inliers_min_max",
                                                                "refine_iterations_min_max", "distinct_winners", "refine_summary", "w_err", "v_angle_deg")}},
-                         "roofline": roof, "refine_pass": _refine_pass_record(full), "refine_restarts": full.get("refine_restarts"), "full_solve_batched": batched, "full_solve_8_threads": threads8, "full_solve_fused": fused, "full_solve_exact_kernel": exact_kernel, "host_boundary": host_boundary, "regimes": regimes, "depth_only": depth_only,
-                         "cpu_baseline": None if (args.no_cpu_baseline or world > 1) else cpu_baseline_full(rsdsfm, np, rank, args.trials, args.tol)})
+                         "refine_restarts": full.get("refine_restarts")})
+            if args.full:
+                line.update({"roofline": roof, "refine_pass": _refine_pass_record(full), "full_solve_batched": batched, "full_solve_8_threads": threads8, "full_solve_fused": fused, "full_solve_exact_kernel": exact_kernel, "host_boundary": host_boundary, "regimes": regimes, "depth_only": depth_only,
+                             "cpu_baseline": None if (args.no_cpu_baseline or world > 1) else cpu_baseline_full(rsdsfm, np, rank, args.trials, args.tol)})
             # the regimes the headline does not exercise, lifted to the top level of the line: `value_selective` = the same one-call solve
             # at the selective tolerance 0.002 (M < N: compaction and the rank-indexed flow are NOT the identity), `value_sequence` =
             # BASELINE configs[4] (32 pairs / 32 data seeds through rsdsfm_solve_frames_dev), both in the line's unit
@@ -727,11 +739,12 @@ def run(args):
             # count and error sum -- the noise-free regime; the headline's DeepFlow-like pairs trip none)
             lr, lg = solver.lma_restarts()
             line["lma_restarts"] = {"count": lr, "last_guards": lg, "per_solve_headline": 0.0 if full.get("lma_restarts") is None else full["lma_restarts"] / max(1, args.steps + args.warmup)}
-            line["value_selective"] = regimes["selective_tol_0.002"]["value"] if regimes else None
-            line["value_sequence"] = batched["value"] * world if batched else None
-            if line["cpu_baseline"] and side:  # the single-thread figure "plus an all-cores variant"
+            if args.full:
+                line["value_selective"] = regimes["selective_tol_0.002"]["value"] if regimes else None
+                line["value_sequence"] = batched["value"] * world if batched else None
+            if line.get("cpu_baseline") and side:  # the single-thread figure "plus an all-cores variant"
                 line["cpu_baseline"]["all_cores"] = cpu_baseline_full_all_cores(rsdsfm, np, rank, args.trials, args.tol, line["cpu_baseline"])
-            if line["cpu_baseline"] and side:  # the reference-STRUCTURED single-thread variant
+            if line.get("cpu_baseline") and side:  # the reference-STRUCTURED single-thread variant
                 line["cpu_baseline"]["reference_structured"] = cpu_baseline_reference_structured(rsdsfm, np, rank, args.trials, args.tol)
         # LAST: the strong-scaling sub-record (north_star: one 3840x2160 frame in N column slabs over the native RCCL driver).  Multi-rank
         # RCCL inside the library cannot be exercised on the 1-GPU development boxes, so the section runs under a watchdog: if it
@@ -1193,17 +1206,18 @@ def _plain_timed(torch, step, steps, warmup):
     return time.perf_counter() - t0
 
 
-def _full_solve(rsdsfm, solver, torch, dev, np, rank, args, steps, warmup, timed, data_seeds=4):
+def _full_solve(rsdsfm, solver, torch, dev, np, rank, args, steps, warmup, timed, data_seeds=4, outputs=False):
     """whole solve on 1280x720 DeepFlow-like pairs (0.3 px noise, 10 % outliers), flow images resident in HBM.  The timed steps rotate
     over `data_seeds` DIFFERENT pairs (one noise / outlier realisation each: other hypotheses, another winner, another refinement
-    length per step) and the sampler seed changes every step as well; the per-pair results of the timed steps are kept for the record."""
+    length per step) and the sampler seed changes every step as well; the per-pair results of the timed steps are kept for the record.
+    outputs: the record's "_outputs" = what the LAST timed solve returned (host copies, float64), for --dump-outputs."""
     seeds = [0x5EED0005 + rank + 7919 * j for j in range(data_seeds)]
     flows, meta = rsdsfm.synth.make_flow_sequence(5, seeds)
     rows, cols, K, gamma = meta["rows"], meta["cols"], meta["K"], meta["gamma"]
     imgs = [torch.from_numpy(f).to(dev) for f in flows]
     depth_map = torch.empty((cols, rows), dtype=torch.float64, device=dev)  # column-major rows x cols
     R, tt = torch.empty((rows, 9), dtype=torch.float64, device=dev), torch.empty((rows, 3), dtype=torch.float64, device=dev)
-    per_step, seen = [], []
+    per_step, seen, last = [], [], [None]
 
     # ONE C-ABI call per frame pair (rsdsfm_solve_frame_dev) with pre-marshalled arguments; it returns after its last result has
     # reached the host
@@ -1217,10 +1231,18 @@ def _full_solve(rsdsfm, solver, torch, dev, np, rank, args, steps, warmup, timed
         r_ = calls[i % nd](1 + i)
         per_step.append(clock() - t0)
         seen.append((int(r_.num_inliers), int(r_.refine_summary.num_iterations), int(r_.best_trial)))  # (after the clock: not in the step's own time)
+        last[0] = r_
 
     lma0 = solver.lma_restarts()[0]
     rf0 = solver.refine_restarts()
     el = timed(step, steps, warmup)
+    dumped = None
+    if outputs:  # before the next call on the context: the result struct and the three maps are still the last timed solve's
+        r_, sm = last[0], last[0].refine_summary
+        dumped = {"depth_map": depth_map.cpu().numpy(), "pose_table_R": R.cpu().numpy(), "pose_table_t": tt.cpu().numpy(),
+                  "pose": np.array(r_.v[:] + r_.w[:] + [r_.k]), "ransac_pose": np.array(r_.ransac_v[:] + r_.ransac_w[:] + [r_.ransac_k]),
+                  "counts": np.array([r_.n_points, r_.num_inliers, r_.best_trial, r_.flipped], dtype=np.float64),
+                  "refine_summary": np.array([getattr(sm, k2) for k2, _ in sm._fields_], dtype=np.float64)}
     lma_restarts = solver.lma_restarts()[0] - lma0  # guard restarts of the analytic pass during the warm-up + timed steps
     rf1 = solver.refine_restarts()
     # the joint refinement's default path (radius-factorised Schur sums): solves that ran on it, those a guard sent back to the iterate-by-iterate
@@ -1242,7 +1264,19 @@ def _full_solve(rsdsfm, solver, torch, dev, np, rank, args, steps, warmup, timed
             "refine_iterations_min_max": [min(x[1] for x in seen), max(x[1] for x in seen)], "distinct_winners": len({x[2] for x in seen}),
             "refine_summary": r["refine_summary"], "K": K, "gamma": gamma, "_img": imgs[0],
             "w_err": float(np.linalg.norm(r["w"] - t["w"])), "v_angle_deg": float(np.degrees(np.arccos(min(1.0, abs(float(vv @ vt)))))),
-            "stages": "flatten+alpha, minimal9 x %d, RANSAC LM sums/decide/score/pick/compaction, refinement, depth map, pose table" % args.trials}
+            "stages": "flatten+alpha, minimal9 x %d, RANSAC LM sums/decide/score/pick/compaction, refinement, depth map, pose table" % args.trials,
+            "_outputs": dumped}
+
+
+def _dump_outputs(out_dir, arrays):
+    """--dump-outputs: one DIR/<name>.npy per array of the last timed solve (float64, 7.5 MB in all at 1280x720).  depth_map is the
+    column-major rows x cols map as the call writes it (cols x rows); pose / ransac_pose = v, w, k; counts = n_points, num_inliers,
+    best_trial, flipped; refine_summary = the LmSummary fields in their C order"""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
 
 
 def _host_boundary(rsdsfm, solver, np, rank, args, reps=3):

@@ -11,7 +11,7 @@ b depth
 b depth_1stream --streams 1 --no-cpu-baseline
 b depth_1pair --batch 1 --streams 1 --no-cpu-baseline
 b cf --workload depth_closed_form
-b full --workload full
+b full --workload full --full
 b tiled --workload tiled
 b tiled_full --workload tiled_full
 b rectify --workload rectify

@@ -29,9 +29,9 @@ if [ "${1:-}" != "quick" ]; then
 fi
 cp $OUT/counters.json profiles/counters.json
 t full --steps 100 $PROF
-b full
+b full --full
 if [ "${1:-}" != "quick" ]; then
-  b full_fused --arith fused --no-side-records
+  b full_fused --arith fused --no-side-records --full
   b depth --workload depth
   b tiled_full --workload tiled_full
   b tiled_full_python --workload tiled_full --tiled-driver python

@@ -30,11 +30,11 @@ if [ "${1:-}" != "quick" ]; then
 fi
 cp $OUT/counters.json profiles/counters.json
 t full --steps 100 $PROF
-b full
+b full --full
 if [ "${1:-}" != "quick" ]; then
   # the sequence solve (32 pairs pipelined over 3 lanes): per-kernel durations WHILE kernels of several pairs share the GPU
   t sequence --steps 3 --warmup 1 --no-cpu-baseline --sequence-only
-  b full_fused --arith fused --no-side-records
+  b full_fused --arith fused --no-side-records --full
   b depth --workload depth
   b tiled_full --workload tiled_full
   b tiled --workload tiled

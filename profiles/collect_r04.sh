@@ -33,11 +33,11 @@ fi
 cp $OUT/counters.json profiles/counters.json
 t full --steps 100 $PROF
 python3 tools/timeline.py /tmp/tr_full 40 > $OUT/timeline_full.txt
-b full
+b full --full
 if [ "${1:-}" != "quick" ]; then
   # the sequence solve (32 pairs pipelined over 3 lanes): per-kernel durations WHILE kernels of several pairs share the GPU
   t sequence --steps 3 --warmup 1 --no-cpu-baseline --sequence-only
-  b full_fused --arith fused --no-side-records
+  b full_fused --arith fused --no-side-records --full
   b depth --workload depth
   b tiled_full --workload tiled_full
   b tiled --workload tiled
@@ -49,7 +49,7 @@ if [ "${1:-}" != "quick" ]; then
   t metrics --workload metrics --no-cpu-baseline
   t tiled_full --workload tiled_full --steps 20
   # N ranks over real RCCL communicators, all sharing this box's ONE GPU (socket transport via NCCL_HOSTID: functional evidence, the rates mean nothing)
-  for n in 2 4 8; do RSDSFM_SHARE_GPU=1 python3 bench.py --gpus $n --steps 10 --warmup 3 --no-cpu-baseline 2>$OUT/bench_shared_gpu_rccl$n.err | tail -1 > $OUT/bench_shared_gpu_rccl$n.json; echo "shared $n: $(cut -c1-160 $OUT/bench_shared_gpu_rccl$n.json)"; done
+  for n in 2 4 8; do RSDSFM_SHARE_GPU=1 python3 bench.py --gpus $n --steps 10 --warmup 3 --no-cpu-baseline --full 2>$OUT/bench_shared_gpu_rccl$n.err | tail -1 > $OUT/bench_shared_gpu_rccl$n.json; echo "shared $n: $(cut -c1-160 $OUT/bench_shared_gpu_rccl$n.json)"; done
   ./tools/depth_clock_probe 60 > $OUT/depth_clock_probe.txt 2>&1
   python3 tools/svd_spread.py 1000 > $OUT/svd_spread.txt 2>/dev/null
   python3 tools/refine_slots.py > $OUT/refine_slots.txt 2>/dev/null

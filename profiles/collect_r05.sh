@@ -34,11 +34,11 @@ fi
 cp $OUT/counters.json profiles/counters.json
 t full --steps 100 $PROF
 python3 tools/timeline.py /tmp/tr_full 40 > $OUT/timeline_full.txt
-b full
+b full --full
 python3 tools/lma_time.py 60 > $OUT/lma_time.txt 2>/dev/null
 if [ "${1:-}" != "quick" ]; then
   t sequence --steps 3 --warmup 1 --no-cpu-baseline --sequence-only
-  b full_fused --arith fused --no-side-records
+  b full_fused --arith fused --no-side-records --full
   b depth --workload depth
   b depth_batch4 --workload depth --batch 4
   b tiled_full --workload tiled_full
@@ -48,7 +48,7 @@ if [ "${1:-}" != "quick" ]; then
   b true_flow --workload true_flow
   t depth --workload depth --streams 1 --steps 60 --no-cpu-baseline
   t tiled_full --workload tiled_full --steps 20
-  for n in 2 4 8; do RSDSFM_SHARE_GPU=1 python3 bench.py --gpus $n --steps 10 --warmup 3 --no-cpu-baseline 2>$OUT/bench_shared_gpu_rccl$n.err | tail -1 > $OUT/bench_shared_gpu_rccl$n.json; echo "shared $n: $(cut -c1-160 $OUT/bench_shared_gpu_rccl$n.json)"; done
+  for n in 2 4 8; do RSDSFM_SHARE_GPU=1 python3 bench.py --gpus $n --steps 10 --warmup 3 --no-cpu-baseline --full 2>$OUT/bench_shared_gpu_rccl$n.err | tail -1 > $OUT/bench_shared_gpu_rccl$n.json; echo "shared $n: $(cut -c1-160 $OUT/bench_shared_gpu_rccl$n.json)"; done
   python3 tools/seq_sweep.py > $OUT/seq_sweep.txt 2>/dev/null
   python3 tools/solve_times.py > $OUT/solve_times.txt 2>/dev/null
 fi

@@ -27,7 +27,7 @@ python3 tools/timeline.py /tmp/tr_full 40 > $OUT/timeline_full.txt
 # the launch durations of the refinement's pass (the launches that ran their loop: > 12 us) into counters.json beside its counters
 python3 profiles/trace_avg_into_counters.py $OUT/counters.json /tmp/tr_full "refine_rf_pass_kernel<6, false, false>" 12.0
 cp $OUT/counters.json profiles/counters.json
-b full
+b full --full
 timeout 300 python3 tools/lma_time.py 60 > $OUT/lma_time.txt 2>/dev/null
 timeout 400 python3 tools/lma_time.py sweep 30 > $OUT/lma_T_sweep.txt 2>/dev/null
 RSDSFM_RF_STAMPS=1 timeout 200 python3 tools/refine_rf_phases.py > $OUT/refine_phases.txt 2>/dev/null
@@ -45,7 +45,7 @@ t accel tools/accel_solves.py 30
 timeout 120 python3 tools/accel_solves.py 60 > $OUT/accel_solves.txt 2>/dev/null
 if [ "${1:-}" != "quick" ]; then
   t sequence bench.py --steps 3 --warmup 1 --no-cpu-baseline --sequence-only
-  b full_fused --arith fused --no-side-records
+  b full_fused --arith fused --no-side-records --full
   b depth --workload depth
   b depth_batch4 --workload depth --batch 4
   b tiled_full --workload tiled_full
@@ -55,7 +55,7 @@ if [ "${1:-}" != "quick" ]; then
   b true_flow --workload true_flow
   t depth bench.py --workload depth --streams 1 --steps 60 --no-cpu-baseline
   t tiled_full bench.py --workload tiled_full --steps 20
-  for n in 2 4 8; do RSDSFM_SHARE_GPU=1 timeout 600 python3 bench.py --gpus $n --steps 10 --warmup 3 --no-cpu-baseline 2>$OUT/bench_shared_gpu_rccl$n.err | tail -1 > $OUT/bench_shared_gpu_rccl$n.json; echo "shared $n: $(cut -c1-160 $OUT/bench_shared_gpu_rccl$n.json)"; done
+  for n in 2 4 8; do RSDSFM_SHARE_GPU=1 timeout 600 python3 bench.py --gpus $n --steps 10 --warmup 3 --no-cpu-baseline --full 2>$OUT/bench_shared_gpu_rccl$n.err | tail -1 > $OUT/bench_shared_gpu_rccl$n.json; echo "shared $n: $(cut -c1-160 $OUT/bench_shared_gpu_rccl$n.json)"; done
   timeout 400 python3 tools/seq_sweep.py > $OUT/seq_sweep.txt 2>/dev/null
   timeout 400 python3 tools/solve_times.py > $OUT/solve_times.txt 2>/dev/null
   for i in 1 2 3; do timeout 120 python3 tools/seq_determinism_probe.py 0 3 10 2>/dev/null | tail -2; done > $OUT/seq_determinism.txt

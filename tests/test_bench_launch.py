@@ -2,10 +2,13 @@
 GPU, starts N rank processes with the torch.distributed.run environment, relays rank 0's single JSON line and returns the worst
 exit code.  Runs on the CPU: --dry-launch prints what would be started, --workload launch_check is the rendezvous + the
 barrier-bracketed timing protocol over gloo with world_size 2."""
+import importlib.util
 import json
 import os
 import subprocess
 import sys
+
+import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BENCH = os.path.join(ROOT, "bench.py")
@@ -85,3 +88,16 @@ def test_watchdog_prints_the_line_when_a_section_hangs():
     assert len(lines) == 1
     d = json.loads(lines[0])
     assert d["n_gpus"] == 2 and "watchdog" in d["guarded"]["error"]
+
+
+def test_full_is_off_by_default_and_dump_outputs_belongs_to_the_full_workload():
+    spec = importlib.util.spec_from_file_location("bench_args", BENCH)
+    b = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(b)
+    a = b.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert a.workload == "full" and a.steps == 7 and a.warmup == 2 and not a.full and a.dump_outputs is None
+    a = b.parse_args(["--full", "--dump-outputs", "out"])
+    assert a.full and a.dump_outputs == "out"
+    for argv in (["--workload", "depth", "--dump-outputs", "out"], ["--sequence-only", "--dump-outputs", "out"]):
+        with pytest.raises(SystemExit):
+            b.parse_args(argv)
