@@ -850,6 +850,91 @@ for _name, _fn in list(vars(_TrueFlowMixin).items()):
 
 
 # ---------------------------------------------------------------------------------------------------
+# DeepFlow front end: two 8-bit frames -> dense flow (include/rsdsfm_flow.h; camera.cc:253-277)
+# ---------------------------------------------------------------------------------------------------
+FLOW_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "rsdsfm_flow.h")
+
+
+class FlowParams(C.Structure):
+    _fields_ = [("sigma", C.c_double), ("min_size", C.c_int32), ("downscale", C.c_double), ("fixed_point_iterations", C.c_int32),
+                ("sor_iterations", C.c_int32), ("alpha", C.c_double), ("delta", C.c_double), ("gamma", C.c_double), ("omega", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+def flow_declared_symbols():
+    """Names of every function include/rsdsfm_flow.h declares"""
+    import re
+
+    txt = open(FLOW_HEADER_PATH).read()
+    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
+    return sorted(set(re.findall(r"\b(rsdsfm_[a-z0-9_]+)\s*\(", txt)))
+
+
+def flow_default_params():
+    """createOptFlow_DeepFlow()'s defaults as a dict (rsdsfm_flow_default_params)"""
+    p = FlowParams()
+    if load_library().rsdsfm_flow_default_params(C.byref(p)) != OK:
+        raise RsdsfmError("rsdsfm_flow_default_params failed")
+    return p.as_dict()
+
+
+def _flow_params(params):
+    """None -> NULL (defaults); a dict (or FlowParams) -> a FlowParams with the given keys over the defaults"""
+    if params is None:
+        return None
+    if isinstance(params, FlowParams):
+        return params
+    d = flow_default_params()
+    unknown = set(params) - set(d)
+    if unknown:
+        raise ValueError("unknown flow parameters %s" % sorted(unknown))
+    d.update(params)
+    return FlowParams(**d)
+
+
+def flow_levels(rows, cols, params=None):
+    """the pyramid DeepFlow builds for a rows x cols pair: list of (rows, cols), level 0 first (host only)"""
+    lib = load_library()
+    p = _flow_params(params)
+    n = C.c_int32(0)
+    pp = C.byref(p) if p is not None else None
+    if lib.rsdsfm_flow_levels(C.c_int32(rows), C.c_int32(cols), pp, C.byref(n), None, None) != OK:
+        raise RsdsfmError("rsdsfm_flow_levels: bad arguments")
+    lr, lc = (C.c_int32 * n.value)(), (C.c_int32 * n.value)()
+    if lib.rsdsfm_flow_levels(C.c_int32(rows), C.c_int32(cols), pp, C.byref(n), lr, lc) != OK:
+        raise RsdsfmError("rsdsfm_flow_levels failed")
+    return [(lr[i], lc[i]) for i in range(n.value)]
+
+
+class _DeepFlowMixin:
+    def deep_flow(self, img1, img2, params=None):
+        """Camera::calculateDeepFlow: two uint8 images (rows, cols, 3) BGR or (rows, cols[, 1]) gray -> flow (rows, cols, 2) float64"""
+        a, b = np.ascontiguousarray(img1, dtype=np.uint8), np.ascontiguousarray(img2, dtype=np.uint8)
+        if a.shape != b.shape or a.ndim not in (2, 3):
+            raise ValueError("the two images must have the same (rows, cols[, channels]) shape")
+        rows, cols = a.shape[:2]
+        ch = 1 if a.ndim == 2 else a.shape[2]
+        p = _flow_params(params)
+        flow = np.empty((rows, cols, 2))
+        self._check(self.lib.rsdsfm_deep_flow(self._ctx, _p(a), _p(b), C.c_int32(rows), C.c_int32(cols), C.c_int32(ch),
+                                              C.byref(p) if p is not None else None, _p(flow)), "rsdsfm_deep_flow")
+        return flow
+
+    def deep_flow_dev(self, d_img1, d_img2, rows, cols, channels, d_flow, params=None):
+        """the same on device buffers, enqueued on the context's stream (no host wait)"""
+        p = _flow_params(params)
+        self._check(self.lib.rsdsfm_deep_flow_dev(self._ctx, _dp(d_img1), _dp(d_img2), C.c_int32(rows), C.c_int32(cols), C.c_int32(channels),
+                                                  C.byref(p) if p is not None else None, _dp(d_flow)), "rsdsfm_deep_flow_dev")
+
+
+for _name, _fn in list(vars(_DeepFlowMixin).items()):
+    if not _name.startswith("__"):
+        setattr(Solver, _name, _fn)
+
+
+# ---------------------------------------------------------------------------------------------------
 # accuracy metrics (SURVEY 8 f-4)
 # ---------------------------------------------------------------------------------------------------
 class ReprojectionStats(C.Structure):

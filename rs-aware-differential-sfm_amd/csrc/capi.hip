@@ -12,6 +12,8 @@
 
 namespace rsdsfm {
 
+void flow_release(Ctx* c);  // flow_host.hip: the DeepFlow front end's pyramid workspace of the context
+
 int fail(Ctx* c, int code, const char* msg) {
     if (c) c->err = msg;
     return code;
@@ -180,6 +182,7 @@ void rsdsfm_destroy(rsdsfm_ctx* ctx) {
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     frame_release(c);  // (the sequence lanes, the second stream and its events)
+    flow_release(c);
     if (c->d_partials) (void)hipFree(c->d_partials);
     if (c->d_tickets) (void)hipFree(c->d_tickets);
     if (c->d_lm) (void)hipFree(c->d_lm);

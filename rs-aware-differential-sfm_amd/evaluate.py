@@ -88,29 +88,46 @@ def evaluate_single_run(solver, task_dir, out_dir, trials=50, tol=0.05, seed=1, 
     return out
 
 
-def evaluate_real_run(solver, data_prefix, flow, camera="galaxy", gamma=0.95, out_dir=None, trials=5, tol=0.05, seed=1,
+def evaluate_real_run(solver, data_prefix, flow=None, camera="galaxy", gamma=0.95, out_dir=None, trials=5, tol=0.05, seed=1,
                       use_acceleration_mode=False, use_refinement=True, use_global_shutter_mode=False, flow_threshold=1e-10,
-                      flow_index_mode=0, device=0):
+                      flow_index_mode=0, device=0, frame2=None, flow_params=None):
     """The real-world branch of evaluateSingleRun (main.cc:341-361, 364-531; setupCameraReal main.cc:675-690): <data_prefix>frame1.png,
     one of the hard-coded phone calibrations (or a (f_x, f_y, c_x, c_y) tuple), gamma 0.95 -- and the optical flow from frame 1 to
-    frame 2, which the reference computes with OpenCV's DeepFlow in-process (out of scope) and which is passed in here: an array, a
-    .npy or a Middlebury .flo file (formats.load_flow).  Runs the whole solve in ONE device-resident call, then the consumers
-    (8-bit depth image, back projection, crack interpolation, point cloud) and writes what the reference writes.  Defaults as in
-    main.cc:304-311 (5 trials, tolerance 0.05, refinement on)."""
+    frame 2: passed in (an array, a .npy or a Middlebury .flo file, formats.load_flow), or, with flow=None, computed on the device
+    by the DeepFlow front end (Solver.deep_flow_dev; camera.cc:253-277, main.cc:380-384) from <data_prefix>frame2.png or the
+    `frame2` array (flow_params: its parameters, None = OpenCV's defaults); that flow goes into the solve without leaving the device
+    and is returned as out["flow"].  Runs the whole solve in ONE device-resident call, then the consumers (8-bit depth image, back
+    projection, crack interpolation, point cloud) and writes what the reference writes (optical_flow.png too when the flow was
+    computed here, main.cc:386-392).  Defaults as in main.cc:304-311 (5 trials, tolerance 0.05, refinement on)."""
     import torch
 
     from . import BACKPROJECT_GS, BACKPROJECT_RS
 
     image = formats.read_png(data_prefix + "frame1.png") if isinstance(data_prefix, str) else np.ascontiguousarray(data_prefix, dtype=np.uint8)
     K = formats.CAMERA_INTRINSICS[camera] if isinstance(camera, str) else tuple(float(x) for x in camera)
-    flow = formats.load_flow(flow)
     rows, cols = image.shape[:2]
-    if flow.shape[:2] != (rows, cols):
-        raise ValueError("flow is %dx%d, frame1 is %dx%d" % (flow.shape[0], flow.shape[1], rows, cols))
+    image2 = None
+    if flow is None:
+        if frame2 is None:
+            if not isinstance(data_prefix, str):
+                raise ValueError("flow=None needs frame 2: a data prefix with frame2.png or the frame2 array")
+            frame2 = formats.read_png(data_prefix + "frame2.png")
+        image2 = np.ascontiguousarray(frame2, dtype=np.uint8)
+        if image2.shape != image.shape:
+            raise ValueError("frame2 is %s, frame1 is %s" % (image2.shape, image.shape))
+    else:
+        flow = formats.load_flow(flow)
+        if flow.shape[:2] != (rows, cols):
+            raise ValueError("flow is %dx%d, frame1 is %dx%d" % (flow.shape[0], flow.shape[1], rows, cols))
     dev = torch.device("cuda", device)
     mode = BACKPROJECT_GS if use_global_shutter_mode else BACKPROJECT_RS
     with torch.cuda.device(dev):  # everything stays on the device until the products are copied out
-        d_flow, d_img = torch.from_numpy(flow).to(dev), torch.from_numpy(image).to(dev)
+        d_img = torch.from_numpy(image).to(dev)
+        if image2 is None:
+            d_flow = torch.from_numpy(flow).to(dev)
+        else:
+            d_img2 = torch.from_numpy(image2).to(dev)
+            d_flow = torch.empty((rows, cols, 2), dtype=torch.float64, device=dev)
         d_map = torch.empty(rows * cols, dtype=torch.float64, device=dev)
         d_R = torch.empty(rows * 9, dtype=torch.float64, device=dev)
         d_t = torch.empty(rows * 3, dtype=torch.float64, device=dev)
@@ -118,6 +135,9 @@ def evaluate_real_run(solver, data_prefix, flow, camera="galaxy", gamma=0.95, ou
         d_gs, d_back = torch.empty_like(d_img), torch.empty_like(d_img)
         d_coords = torch.empty((rows, cols, 3), dtype=torch.float32, device=dev)
         torch.cuda.synchronize()
+        if image2 is not None:  # the flow is computed on the solver's stream, ahead of the solve that reads it
+            solver.deep_flow_dev(d_img.data_ptr(), d_img2.data_ptr(), rows, cols, 1 if image.ndim == 2 else image.shape[2], d_flow.data_ptr(),
+                                 params=flow_params)
         r = solver.solve_frame_dev(d_flow.data_ptr(), rows, cols, K, gamma, d_map.data_ptr(), d_R.data_ptr(), d_t.data_ptr(), trials=trials, tol=tol,
                                    seed=seed, use_acceleration_mode=use_acceleration_mode, use_refinement=use_refinement,
                                    flow_threshold=flow_threshold, flow_index_mode=flow_index_mode, use_global_shutter_mode=use_global_shutter_mode)
@@ -129,10 +149,16 @@ def evaluate_real_run(solver, data_prefix, flow, camera="galaxy", gamma=0.95, ou
         depth_map = d_map.cpu().numpy().reshape(cols, rows).T.copy()  # the device map is column-major (Eigen MatrixXd)
         R_rel, t_rel = d_R.cpu().numpy().reshape(rows, 3, 3), d_t.cpu().numpy().reshape(rows, 3)
         depth_est, gs, backprojection, coords = d_depth_est.cpu().numpy(), d_gs.cpu().numpy(), d_back.cpu().numpy(), d_coords.cpu().numpy()
+        if image2 is not None:
+            flow = d_flow.cpu().numpy()
     out = dict(n=r["n"], num_inliers=m, v=r["v"], w=r["w"], k=r["k"], flipped=r["flipped"], refine_summary=r["refine_summary"],
                depth_map=depth_map, depth_est=depth_est, gs_image=gs, backprojection=backprojection, coords=coords, R=R_rel, t=t_rel)
+    if image2 is not None:
+        out["flow"] = flow
     if out_dir:
         os.makedirs(out_dir, exist_ok=True)
+        if image2 is not None:
+            formats.write_png(out_dir + "/optical_flow.png", formats.flow_to_bgr(flow))  # main.cc:386-392
         formats.write_png(out_dir + "/MinimalDepth.png", depth_est)
         formats.write_png(out_dir + "/rs_image.png", image)
         formats.write_png(out_dir + "/backprojection.png", backprojection)

@@ -1,16 +1,19 @@
 // camera.h -- the facade of the reference's Camera (src/camera.h) over the frames: intrinsics (incl. the five
 // hard-coded phone calibrations, camera.cc:179-206), gamma, pose and depth map forwarding (camera.cc:335-371).
 // plus the rectifier entry points backProject / backProjectGs (camera.cc:353-361) and interpolateCrackyImage
-// (camera.cc:753-774).  Flow, CSV and visualisation members are out of scope.
+// (camera.cc:753-774), the ground-truth flow (camera.cc:209-249) and DeepFlow (camera.cc:253-277).  CSV and visualisation members are
+// out of scope.
 #ifndef RSDSFM_HOST_CAMERA_H
 #define RSDSFM_HOST_CAMERA_H
 
 #include <cmath>
 #include <cstdlib>
 #include <iostream>
+#include <stdexcept>
 #include <string>
 #include <vector>
 
+#include "../../include/rsdsfm_flow.h"
 #include "rsframe.h"
 
 class Camera {
@@ -195,6 +198,16 @@ public:
      *  relative scanline poses of frame 2) */
     rsdsfm::FlowImage calculateTrueFlow(const int frameNr1, const int frameNr2) {
         return frames_[(size_t)frameNr2 - 1].trueFlowFrom(frames_[(size_t)frameNr1 - 1]);
+    }
+    /** reference camera.cc:253-277: DeepFlow (default parameters) from the image of frame frameNr1 to that of frame frameNr2, both given
+     *  to addFrameReal; on the GPU (include/rsdsfm_flow.h).  The reference ignores its two arguments and always uses frames 1 and 2
+     *  (camera.cc:265-266); this mirror honours them, which is the same for (1, 2). */
+    rsdsfm::FlowImage calculateDeepFlow(const int frameNr1, const int frameNr2) {
+        rsdsfm::ImageBGR a = frames_[(size_t)frameNr1 - 1].getRsImage(), b = frames_[(size_t)frameNr2 - 1].getRsImage();
+        if (a.rows() != b.rows() || a.cols() != b.cols()) throw std::runtime_error("calculateDeepFlow: the two frames differ in size");
+        rsdsfm::FlowImage flow(a.rows(), a.cols());
+        rsdsfm::check(rsdsfm_deep_flow(rsdsfm::default_context(), a.data(), b.data(), a.rows(), a.cols(), 3, nullptr, flow.data()), "rsdsfm_deep_flow");
+        return flow;
     }
     /** reference camera.cc:594-691 */
     double meanReprojectionError(const int frameNr) { return frames_[(size_t)frameNr - 1].reprojectionError(10.0, nullptr).mean_error; }

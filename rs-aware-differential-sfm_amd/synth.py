@@ -150,6 +150,54 @@ def flatten_numpy(flow_img, K, gamma, thr=1e-10):
             np.ascontiguousarray(alpha_k), pix)
 
 
+def _texture(x, y, seed):
+    """procedural BGR texture at real coordinates: six octaves of seeded sinusoids (periods 256 .. 8 px, four directions each) --
+    gradients at every pyramid scale -- plus a per-channel offset; float64 (rows, cols, 3) in [0, 255]"""
+    u = uniform01(seed, 6 * 4 * 2)
+    t = np.zeros(np.broadcast(x, y).shape)
+    for o in range(6):
+        freq = 2.0 * np.pi / (256.0 / 2 ** o)
+        for j in range(4):
+            th, ph = np.pi * u[8 * o + 2 * j], 2.0 * np.pi * u[8 * o + 2 * j + 1]
+            t = t + (22.0 / (1.0 + 0.5 * o)) * np.sin(freq * (np.cos(th) * x + np.sin(th) * y) + ph)
+    t = 128.0 + 0.55 * t
+    return np.clip(np.stack([t, 0.9 * t + 12.0, 1.1 * t - 12.0], axis=-1), 0.0, 255.0)
+
+
+def _bilinear(f, x, y):
+    """f (rows, cols, ...) sampled at real (x, y), replicate border"""
+    rows, cols = f.shape[:2]
+    x = np.clip(x, 0.0, cols - 1.0)
+    y = np.clip(y, 0.0, rows - 1.0)
+    x0 = np.minimum(np.floor(x).astype(np.int64), cols - 2)
+    y0 = np.minimum(np.floor(y).astype(np.int64), rows - 2)
+    ax, ay = (x - x0)[..., None], (y - y0)[..., None]
+    return ((1 - ay) * ((1 - ax) * f[y0, x0] + ax * f[y0, x0 + 1]) + ay * ((1 - ax) * f[y0 + 1, x0] + ax * f[y0 + 1, x0 + 1]))
+
+
+def render_pair(rows, cols, K, v, w, k=0.0, gamma=0.8, seed=0x5EED0000):
+    """Two 8-bit BGR frames of a procedural texture moved by make_flow's model flow F, for testing a flow estimator (the DeepFlow
+    front end): frame 1 is the texture T, frame 2 at pixel q shows T(p) with p + F(p) = q (solved by p <- q - F(p), F bilinear).
+    Returns (img1, img2, flow F (rows, cols, 2), valid mask): the mask leaves out a border band of max|F| + 5 pixels, where frame 2
+    shows texture that frame 1 does not."""
+    flow, _ = make_flow(rows, cols, K, v, w, k, gamma, _model_only=True)
+    yy, xx = np.mgrid[0:rows, 0:cols].astype(np.float64)
+    img1 = np.rint(_texture(xx, yy, seed)).astype(np.uint8)
+    px, py = xx.copy(), yy.copy()
+    for _ in range(50):
+        F = _bilinear(flow, px, py)
+        nx, ny = xx - F[..., 0], yy - F[..., 1]
+        done = max(np.abs(nx - px).max(), np.abs(ny - py).max()) < 1e-9
+        px, py = nx, ny
+        if done:
+            break
+    img2 = np.rint(_texture(px, py, seed)).astype(np.uint8)
+    band = int(np.ceil(np.abs(flow).max())) + 5
+    mask = np.zeros((rows, cols), dtype=bool)
+    mask[band:rows - band, band:cols - band] = True
+    return img1, img2, np.ascontiguousarray(flow), mask
+
+
 def default_motion():
     """examples/README.md:20 first synthetic example: v = (0.03, 0.03, 0) * mean depth, w = (0, 0, 0.5 deg), k = 0."""
     return np.array([0.03, 0.03, 0.0]), np.array([0.0, 0.0, np.deg2rad(0.5)]), 0.0
