@@ -935,6 +935,87 @@ for _name, _fn in list(vars(_DeepFlowMixin).items()):
 
 
 # ---------------------------------------------------------------------------------------------------
+# whole clips: frames in, the flow of every consecutive pair and its solve out (include/rsdsfm_video.h)
+# ---------------------------------------------------------------------------------------------------
+VIDEO_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "rsdsfm_video.h")
+
+
+def video_declared_symbols():
+    """Names of every function include/rsdsfm_video.h declares"""
+    import re
+
+    txt = open(VIDEO_HEADER_PATH).read()
+    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
+    return sorted(set(re.findall(r"\b(rsdsfm_[a-z0-9_]+)\s*\(", txt)))
+
+
+def _ptr_array(ptrs):
+    """a list of device pointers (ints / data_ptr(); 0 = NULL) -> a C array of void*"""
+    return (C.c_void_p * len(ptrs))(*[int(p) or None for p in ptrs])
+
+
+def _frame_result_dict(r):
+    return dict(n=int(r.n_points), num_inliers=int(r.num_inliers), best_trial=int(r.best_trial), flipped=bool(r.flipped),
+                ransac_w=np.array(r.ransac_w[:]), ransac_v=np.array(r.ransac_v[:]), ransac_k=float(r.ransac_k),
+                w=np.array(r.w[:]), v=np.array(r.v[:]), k=float(r.k), refine_summary=r.refine_summary.as_dict(),
+                d_inliers=r.d_inliers, d_inlier_idx=r.d_inlier_idx, d_scanline=r.d_scanline)
+
+
+class _VideoMixin:
+    def set_flow_batch(self, pairs):
+        """pairs per batch of the clip calls (rsdsfm_set_flow_batch): 1..32, 0 = the default (8); scheduling only (it sizes the
+        context's sequence workspace, about (120 B + 41 (B + 1)) bytes per pixel)"""
+        self._check(self.lib.rsdsfm_set_flow_batch(self._ctx, C.c_int32(int(pairs))), "rsdsfm_set_flow_batch")
+
+    def deep_flow_seq(self, frames, params=None):
+        """DeepFlow of every consecutive pair of a clip: uint8 (F, rows, cols, 3) BGR or (F, rows, cols) gray -> (F - 1, rows, cols, 2)
+        float64; flows[p] is deep_flow(frames[p], frames[p + 1]) bit for bit"""
+        f = np.ascontiguousarray(frames, dtype=np.uint8)
+        if f.ndim not in (3, 4) or f.shape[0] < 2:
+            raise ValueError("frames must be (F >= 2, rows, cols[, channels])")
+        nf, rows, cols = f.shape[:3]
+        ch = 1 if f.ndim == 3 else f.shape[3]
+        p = _flow_params(params)
+        flows = np.empty((nf - 1, rows, cols, 2))
+        self._check(self.lib.rsdsfm_deep_flow_seq(self._ctx, _ptr_array([f[i].ctypes.data for i in range(nf)]), C.c_int32(nf), C.c_int32(rows),
+                                                  C.c_int32(cols), C.c_int32(ch), C.byref(p) if p is not None else None,
+                                                  _ptr_array([flows[i].ctypes.data for i in range(nf - 1)])), "rsdsfm_deep_flow_seq")
+        return flows
+
+    def deep_flow_seq_dev(self, d_frames, rows, cols, channels, d_flows, params=None):
+        """the same on device buffers (lists of F frame and F - 1 field pointers), enqueued on the context's stream (no host wait)"""
+        p = _flow_params(params)
+        self._check(self.lib.rsdsfm_deep_flow_seq_dev(self._ctx, _ptr_array(d_frames), C.c_int32(len(d_frames)), C.c_int32(rows), C.c_int32(cols),
+                                                      C.c_int32(channels), C.byref(p) if p is not None else None, _ptr_array(d_flows)),
+                    "rsdsfm_deep_flow_seq_dev")
+
+    def solve_video_dev(self, d_frames, rows, cols, channels, K, gamma, d_depth_maps, seeds=None, d_flows=None, d_R=None, d_t=None, flow_params=None,
+                        trials=50, tol=0.05, use_acceleration_mode=False, use_refinement=True, depth_mode=DEPTH_CERES_LM, k_sign_mode=K_COMPAT,
+                        flow_threshold=1e-10, flow_index_mode=FLOW_COMPAT_RANK, use_global_shutter_mode=False):
+        """a whole clip in ONE call (rsdsfm_solve_video_dev): the flow of each batch of pairs, then solve_frames_dev over that batch.
+        d_frames: F device frames; d_depth_maps (and optionally d_flows, d_R, d_t): F - 1 device buffers each (d_flows=None: a ring
+        owned by the library); seeds: one per pair (None: 1).  Returns one dict per pair, as solve_frames_dev."""
+        n = len(d_frames) - 1
+        prm = FrameParams(int(trials), int(use_acceleration_mode), int(use_refinement), int(depth_mode), int(k_sign_mode),
+                          int(flow_index_mode), int(use_global_shutter_mode), 0, float(tol), float(flow_threshold), 1)
+        res = (FrameResult * max(n, 1))()
+        sd = (C.c_uint64 * n)(*[int(s) for s in seeds]) if seeds is not None else None
+        arr = lambda a: _ptr_array(a) if a is not None else None
+        p = _flow_params(flow_params)
+        d = C.c_double
+        self._check(self.lib.rsdsfm_solve_video_dev(self._ctx, _ptr_array(d_frames), C.c_int32(len(d_frames)), C.c_int32(rows), C.c_int32(cols),
+                                                    C.c_int32(channels), d(K[0]), d(K[1]), d(K[2]), d(K[3]), d(gamma), C.byref(p) if p is not None else None,
+                                                    C.byref(prm), sd, arr(d_flows), _ptr_array(d_depth_maps), arr(d_R), arr(d_t), res),
+                    "rsdsfm_solve_video_dev")
+        return [_frame_result_dict(r) for r in res[:n]]
+
+
+for _name, _fn in list(vars(_VideoMixin).items()):
+    if not _name.startswith("__"):
+        setattr(Solver, _name, _fn)
+
+
+# ---------------------------------------------------------------------------------------------------
 # accuracy metrics (SURVEY 8 f-4)
 # ---------------------------------------------------------------------------------------------------
 class ReprojectionStats(C.Structure):

@@ -7,13 +7,12 @@
 #include <vector>
 
 #include "../../include/rsdsfm_flow.h"
+#include "flow_host.hpp"
 #include "flow_kernels.hpp"
 #include "rsdsfm_internal.hpp"
 
 namespace rsdsfm {
-namespace {
-
-constexpr int kFlowMaxSide = 16384;
+namespace flowhost {
 
 bool params_ok(const rsdsfm_flow_params& p) {
     const double d[] = {p.sigma, p.downscale, p.alpha, p.delta, p.gamma, p.omega};
@@ -63,10 +62,6 @@ std::vector<float> gauss_taps(double sigma) {
     return t;
 }
 
-// resize tables of one axis (tests/flow_spec_numpy.py resize_table): offsets into the workspace's int / float tables
-struct AxisTab {
-    size_t i0, i1, w0, w1;
-};
 AxisTab axis_table(int src, int dst, std::vector<int32_t>& ti, std::vector<float>& tf) {
     AxisTab a{ti.size(), ti.size() + (size_t)dst, tf.size(), tf.size() + (size_t)dst};
     std::vector<int32_t> i0(dst), i1(dst);
@@ -87,6 +82,20 @@ AxisTab axis_table(int src, int dst, std::vector<int32_t>& ti, std::vector<float
     tf.insert(tf.end(), w1.begin(), w1.end());
     return a;
 }
+
+int check_args(Ctx* c, int rows, int cols, int channels, const rsdsfm_flow_params* pp, rsdsfm_flow_params* p) {
+    if (rows < 2 || cols < 2 || rows > kFlowMaxSide || cols > kFlowMaxSide) return fail(c, RSDSFM_ERR_INVALID, "deep flow: sides must be in [2, 16384]");
+    if (channels != 1 && channels != 3) return fail(c, RSDSFM_ERR_INVALID, "deep flow: channels must be 1 or 3");
+    *p = pp ? *pp : defaults();
+    if (!params_ok(*p)) return fail(c, RSDSFM_ERR_INVALID, "deep flow: bad parameters");
+    return RSDSFM_OK;
+}
+
+}  // namespace flowhost
+
+using namespace flowhost;
+
+namespace {
 
 // the context's pyramid workspace: one device allocation, rebuilt when the size or the pyramid changes
 struct FlowWs {
@@ -170,14 +179,6 @@ int ensure_flow_ws(Ctx* c, int rows, int cols, const rsdsfm_flow_params& p, Flow
     RSDSFM_HIP_CHECK(c, hipMemcpyAsync(w->d_tf, w->tf.data(), 4 * w->tf.size(), hipMemcpyHostToDevice, c->stream));
     RSDSFM_HIP_CHECK(c, hipStreamSynchronize(c->stream));  // the host tables are pageable
     w->rows = rows, w->cols = cols, w->min_size = p.min_size, w->downscale = p.downscale, w->sigma = p.sigma;
-    return RSDSFM_OK;
-}
-
-int check_args(Ctx* c, int rows, int cols, int channels, const rsdsfm_flow_params* pp, rsdsfm_flow_params* p) {
-    if (rows < 2 || cols < 2 || rows > kFlowMaxSide || cols > kFlowMaxSide) return fail(c, RSDSFM_ERR_INVALID, "deep flow: sides must be in [2, 16384]");
-    if (channels != 1 && channels != 3) return fail(c, RSDSFM_ERR_INVALID, "deep flow: channels must be 1 or 3");
-    *p = pp ? *pp : defaults();
-    if (!params_ok(*p)) return fail(c, RSDSFM_ERR_INVALID, "deep flow: bad parameters");
     return RSDSFM_OK;
 }
 

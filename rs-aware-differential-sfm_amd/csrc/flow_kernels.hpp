@@ -59,4 +59,25 @@ hipError_t flow_coef(hipStream_t s, const FlowLevelBufs& L, int rows, int cols, 
 hipError_t flow_sor(hipStream_t s, const FlowSorArgs& a, int tiles);
 hipError_t flow_output(hipStream_t s, const FlowLevelBufs& L, int rows, int cols, double* flow);
 
+// ---- batches of consecutive pairs (flow_seq_kernels.hip; DESIGN section 12, "Sequences") ------------------------------------------
+// A batch of n <= kFlowSeqMaxPairs pairs reads n + 1 frames; per-frame planes at base + frame * pstride (pyramids) or * stride (the
+// blur's temporary), per-pair planes at base + pair * stride.  The frames and the output fields are kernel-argument tables.
+constexpr int kFlowSeqMaxPairs = 32;
+struct FlowFramePtrs {
+    const uint8_t* p[kFlowSeqMaxPairs + 1];
+};
+struct FlowOutPtrs {
+    double* p[kFlowSeqMaxPairs];
+};
+
+hipError_t flow_seq_presmooth(hipStream_t s, const FlowFramePtrs& img, int nframes, int rows, int cols, int channels, const float* taps, int radius,
+                              float* tmp, size_t stride, float* pyr, size_t pstride);
+hipError_t flow_seq_pyr_down(hipStream_t s, const float* src, int scols, const FlowResizeTab& tab, int rows, int cols, float* dst, size_t pstride,
+                             int nframes);
+hipError_t flow_seq_level_entry(hipStream_t s, const FlowLevelBufs& L, size_t stride, const float* pyr_l, size_t pstride, int rows, int cols,
+                                const FlowCoarse& C, float scale, int npairs);
+hipError_t flow_seq_coef(hipStream_t s, const FlowLevelBufs& L, size_t stride, int rows, int cols, const FlowConsts& k, int npairs);
+hipError_t flow_seq_sor(hipStream_t s, const FlowSorArgs& a, size_t stride, int tiles, int npairs);
+hipError_t flow_seq_output(hipStream_t s, const FlowLevelBufs& L, size_t stride, int rows, int cols, const FlowOutPtrs& out, int npairs);
+
 }  // namespace rsdsfm

@@ -156,14 +156,87 @@ def evaluate_real_run(solver, data_prefix, flow=None, camera="galaxy", gamma=0.9
     if image2 is not None:
         out["flow"] = flow
     if out_dir:
-        os.makedirs(out_dir, exist_ok=True)
-        if image2 is not None:
-            formats.write_png(out_dir + "/optical_flow.png", formats.flow_to_bgr(flow))  # main.cc:386-392
-        formats.write_png(out_dir + "/MinimalDepth.png", depth_est)
-        formats.write_png(out_dir + "/rs_image.png", image)
-        formats.write_png(out_dir + "/backprojection.png", backprojection)
-        formats.write_ply(out_dir + "/point_cloud.ply", coords, image)
+        _write_real_outputs(out_dir, image, flow if image2 is not None else None, depth_est, backprojection, coords)
     return out
+
+
+def _write_real_outputs(out_dir, image, flow, depth_est, backprojection, coords):
+    """what the real-world branch writes (main.cc:386-392 and :480-523); optical_flow.png only for a flow computed here"""
+    os.makedirs(out_dir, exist_ok=True)
+    if flow is not None:
+        formats.write_png(out_dir + "/optical_flow.png", formats.flow_to_bgr(flow))  # main.cc:386-392
+    formats.write_png(out_dir + "/MinimalDepth.png", depth_est)
+    formats.write_png(out_dir + "/rs_image.png", image)
+    formats.write_png(out_dir + "/backprojection.png", backprojection)
+    formats.write_ply(out_dir + "/point_cloud.ply", coords, image)
+
+
+def evaluate_real_sequence(solver, frames, camera="galaxy", gamma=0.95, out_dir=None, trials=5, seeds=None, tol=0.05, use_acceleration_mode=False,
+                           use_refinement=True, use_global_shutter_mode=False, flow_threshold=1e-10, flow_index_mode=0, device=0, flow_params=None):
+    """evaluate_real_run's real-world branch (main.cc:341-361, 364-531) for a clip: `frames` is <prefix>frame1.png ... frameN.png (the
+    prefix, or a list of paths), or the frames themselves (an (N, rows, cols[, 3]) uint8 array or a list of arrays).  The DeepFlow of
+    every consecutive pair runs once for the clip (Solver.deep_flow_seq_dev, batched); then, per pair p (frames p, p + 1), the solve
+    (seed seeds[p], default 1 as in evaluate_real_run) and the rectification on that pair's device flow -- solve_frame_dev and
+    rectify_frame_dev, since the rectifier reads the pair's device inlier list.  Returns one dict per pair with evaluate_real_run's keys
+    and "flow"; each is bit for bit evaluate_real_run(frames[p], None, frame2=frames[p + 1]).  With out_dir: evaluate_real_run's files
+    (optical_flow.png included) under out_dir/<pair>/, and out_dir/poses.csv (pair, v, w, k, inliers)."""
+    import torch
+
+    from . import BACKPROJECT_GS, BACKPROJECT_RS
+
+    if isinstance(frames, str):
+        paths, i = [], 1
+        while os.path.exists(frames + "frame%d.png" % i):
+            paths.append(frames + "frame%d.png" % i)
+            i += 1
+        frames = paths
+    images = [formats.read_png(f) if isinstance(f, str) else np.ascontiguousarray(f, dtype=np.uint8) for f in frames]
+    if len(images) < 2 or any(im.shape != images[0].shape for im in images):
+        raise ValueError("a clip needs at least two frames of one shape")
+    npairs = len(images) - 1
+    seeds = [1] * npairs if seeds is None else [int(s) for s in seeds]
+    if len(seeds) != npairs:
+        raise ValueError("one seed per pair")
+    K = formats.CAMERA_INTRINSICS[camera] if isinstance(camera, str) else tuple(float(x) for x in camera)
+    rows, cols = images[0].shape[:2]
+    channels = 1 if images[0].ndim == 2 else images[0].shape[2]
+    dev = torch.device("cuda", device)
+    mode = BACKPROJECT_GS if use_global_shutter_mode else BACKPROJECT_RS
+    outs = []
+    with torch.cuda.device(dev):
+        d_imgs = [torch.from_numpy(im).to(dev) for im in images]
+        d_flows = [torch.empty((rows, cols, 2), dtype=torch.float64, device=dev) for _ in range(npairs)]
+        torch.cuda.synchronize()
+        solver.deep_flow_seq_dev([d.data_ptr() for d in d_imgs], rows, cols, channels, [f.data_ptr() for f in d_flows], params=flow_params)
+        for p in range(npairs):
+            d_img, d_flow = d_imgs[p], d_flows[p]
+            d_map = torch.empty(rows * cols, dtype=torch.float64, device=dev)
+            d_R = torch.empty(rows * 9, dtype=torch.float64, device=dev)
+            d_t = torch.empty(rows * 3, dtype=torch.float64, device=dev)
+            d_depth_est = torch.empty((rows, cols), dtype=torch.uint8, device=dev)
+            d_gs, d_back = torch.empty_like(d_img), torch.empty_like(d_img)
+            d_coords = torch.empty((rows, cols, 3), dtype=torch.float32, device=dev)
+            torch.cuda.synchronize()
+            r = solver.solve_frame_dev(d_flow.data_ptr(), rows, cols, K, gamma, d_map.data_ptr(), d_R.data_ptr(), d_t.data_ptr(), trials=trials, tol=tol,
+                                       seed=seeds[p], use_acceleration_mode=use_acceleration_mode, use_refinement=use_refinement,
+                                       flow_threshold=flow_threshold, flow_index_mode=flow_index_mode, use_global_shutter_mode=use_global_shutter_mode)
+            m = r["num_inliers"]
+            solver.rectify_frame_dev(r["d_inliers"], m, d_img.data_ptr(), d_map.data_ptr(), d_R.data_ptr(), d_t.data_ptr(), K, rows, cols, d_depth_est.data_ptr(),
+                                     d_gs.data_ptr(), d_back.data_ptr(), d_coords=d_coords.data_ptr(), mode=mode, offset=1)
+            solver.synchronize()
+            outs.append(dict(n=r["n"], num_inliers=m, v=r["v"], w=r["w"], k=r["k"], flipped=r["flipped"], refine_summary=r["refine_summary"],
+                             depth_map=d_map.cpu().numpy().reshape(cols, rows).T.copy(), depth_est=d_depth_est.cpu().numpy(), gs_image=d_gs.cpu().numpy(),
+                             backprojection=d_back.cpu().numpy(), coords=d_coords.cpu().numpy(), R=d_R.cpu().numpy().reshape(rows, 3, 3),
+                             t=d_t.cpu().numpy().reshape(rows, 3), flow=d_flow.cpu().numpy()))
+    if out_dir:
+        os.makedirs(out_dir, exist_ok=True)
+        lines = ["pair,v_x,v_y,v_z,w_x,w_y,w_z,k,inliers"]
+        for p, o in enumerate(outs):
+            _write_real_outputs(os.path.join(out_dir, str(p)), images[p], o["flow"], o["depth_est"], o["backprojection"], o["coords"])
+            lines.append(",".join([str(p)] + ["%.17g" % x for x in list(o["v"]) + list(o["w"]) + [o["k"]]] + [str(o["num_inliers"])]))
+        with open(os.path.join(out_dir, "poses.csv"), "w") as fh:
+            fh.write("\n".join(lines) + "\n")
+    return outs
 
 
 # ---------------------------------------------------------------------------------------------------

@@ -198,6 +198,34 @@ def render_pair(rows, cols, K, v, w, k=0.0, gamma=0.8, seed=0x5EED0000):
     return img1, img2, np.ascontiguousarray(flow), mask
 
 
+def render_sequence(nframes, rows, cols, K, v, w, k=0.0, gamma=0.8, seed=0x5EED0000):
+    """nframes 8-bit BGR frames of render_pair's texture under a constant motion: frame j at pixel q shows T(inv^j(q)), where inv is
+    render_pair's fixed-point inverse of the model flow F (p + F(p) = q), applied j times from the pixel grid.  Every consecutive pair
+    (j, j + 1) therefore has the true flow F and the true (v, w, k); render_pair's border mask.  nframes = 2 gives render_pair's two
+    frames bit for bit.  Returns (frames (nframes, rows, cols, 3) uint8, F (rows, cols, 2), mask)."""
+    if nframes < 2:
+        raise ValueError("a sequence has at least two frames")
+    flow, _ = make_flow(rows, cols, K, v, w, k, gamma, _model_only=True)
+    yy, xx = np.mgrid[0:rows, 0:cols].astype(np.float64)
+    frames = [np.rint(_texture(xx, yy, seed)).astype(np.uint8)]
+    qx, qy = xx, yy
+    for _ in range(1, nframes):
+        px, py = qx.copy(), qy.copy()
+        for _ in range(50):  # render_pair's iteration, from the previous frame's positions
+            F = _bilinear(flow, px, py)
+            nx, ny = qx - F[..., 0], qy - F[..., 1]
+            done = max(np.abs(nx - px).max(), np.abs(ny - py).max()) < 1e-9
+            px, py = nx, ny
+            if done:
+                break
+        qx, qy = px, py
+        frames.append(np.rint(_texture(qx, qy, seed)).astype(np.uint8))
+    band = int(np.ceil(np.abs(flow).max())) + 5
+    mask = np.zeros((rows, cols), dtype=bool)
+    mask[band:rows - band, band:cols - band] = True
+    return np.stack(frames), np.ascontiguousarray(flow), mask
+
+
 def default_motion():
     """examples/README.md:20 first synthetic example: v = (0.03, 0.03, 0) * mean depth, w = (0, 0, 0.5 deg), k = 0."""
     return np.array([0.03, 0.03, 0.0]), np.array([0.0, 0.0, np.deg2rad(0.5)]), 0.0
