@@ -368,6 +368,13 @@ int rsdsfm_set_sequence_lanes(rsdsfm_ctx* ctx, int32_t lanes);
  * Measured on MI355X (1280x720, T = 50, medians of 60 solves): 0.963 / 0.986 / 0.995 / 0.977 ms for 3 / 2 / 1 / 0 -- the
  * cross-stream join of mode 1 costs more than the 21 us of flatten kernels it hides.  Scheduling only: identical results. */
 int rsdsfm_set_frame_side_flatten(rsdsfm_ctx* ctx, int mode);
+/* The launches at the end of a frame solve with refinement:
+ *   0 (default) = the refinement's output pass also claims the depth-map pixel of every inlier it copies, and ONE kernel behind it
+ *       decides the sign of z, writes the header, the pose table and the depth map and -- only if the sign flips -- negates z of the
+ *       inliers in place (two launches);
+ *   1 = the stage-by-stage form: output pass, sign decision, claim, depth-map write (four launches).
+ * Copied to the lanes of rsdsfm_solve_frames_dev.  Which launches run, never a result: both modes return the same bytes. */
+int rsdsfm_set_frame_tail(rsdsfm_ctx* ctx, int mode);
 /* minimal::ransac on device-resident inputs.  The arrays of `out` (inlier_idx, inliers, alpha, alpha_k, mask,
  * inv_depth) are DEVICE pointers with capacity n (each may be NULL); its trial_* arrays are HOST pointers.
  * samples_9xT_or_null is a HOST pointer.  Synchronises once at the end to return the scalars of `out`. */

@@ -597,6 +597,11 @@ class Solver:
         workgroups flatten while T waves solve), 2 behind the solver, 1 beside it on a second stream, 0 in front of it; scheduling only"""
         self._check(self.lib.rsdsfm_set_frame_side_flatten(self._ctx, int(on)), "rsdsfm_set_frame_side_flatten")
 
+    def set_frame_tail(self, mode):
+        """the launches at the end of a frame solve (rsdsfm_set_frame_tail): 0 (default) the output pass claims the depth-map pixels and one
+        kernel decides the sign and writes the map, 1 the stage-by-stage launches; identical results"""
+        self._check(self.lib.rsdsfm_set_frame_tail(self._ctx, int(mode)), "rsdsfm_set_frame_tail")
+
     def prepared_frames_solve(self, jobs, trials=50, tol=0.05, use_acceleration_mode=False, use_refinement=True, depth_mode=DEPTH_CERES_LM,
                               k_sign_mode=K_COMPAT, flow_threshold=1e-10, flow_index_mode=FLOW_COMPAT_RANK, use_global_shutter_mode=False):
         """A SEQUENCE of frame pairs in ONE C-ABI call (rsdsfm_solve_frames_dev), pipelined inside the library.  jobs: list of dicts with

@@ -55,6 +55,7 @@ struct FrameRun {
     int rc_begin = RSDSFM_OK;
     int64_t m_known = -1;  // the inlier count once the host has it; until then the kernels read it from the refinement's state
     RefineTail tail;
+    FinishClaim claim;  // short launch tail (Ctx::frame_tail == 0): what the refinement's output pass needs to claim the depth-map pixels
     RansacSpecTail spec_tail;
     std::function<int()> join;
 };
@@ -251,12 +252,23 @@ int frame_begin(Ctx* c, FrameRun* F) {
         if (J2.d_R_rows9_or_null && J2.d_t_rows3_or_null)
             pt.R = J2.d_R_rows9_or_null, pt.t = J2.d_t_rows3_or_null, pt.rows = J2.rows, pt.gamma = J2.gamma, pt.wk_dev = st->p + 3;
         // (the sums of z come from the refinement's output pass: one entry per workgroup of that launch)
+        if (B.claim.on)  // short tail: the output pass has claimed the pixels and written the scanlines, one launch does the rest
+            return depth_map_decided_launch(c, F->d_inl_ref, m_arg, F->d_zpartials, refine_finish_grid(c, B), B, J2.d_depth_map_colmajor, F->d_zheader,
+                                            header_host(c), st->p, m_dev, &pt);
         return depth_map_slab_launch(c, F->d_inl_ref, m_arg, F->d_zpartials, refine_finish_grid(c, B), m_arg, nullptr, J2.fx, J2.fy, J2.cx, J2.cy, J2.rows,
                                      0, J2.cols, J2.d_depth_map_colmajor, nullptr, F->d_ys, F->d_zheader, header_host(c), st->p, m_dev, &pt);
     };
+    F->claim = FinishClaim();
+    if (c->frame_tail == 0) {
+        F->claim.on = true;
+        F->claim.fx = J.fx, F->claim.fy = J.fy, F->claim.cx = J.cx, F->claim.cy = J.cy;
+        F->claim.rows = rows, F->claim.cols = cols;
+        F->claim.ys = F->d_ys;
+    }
     F->spec_tail = [c, F](const RansacBest* d_best) -> int {
         return refine_begin(c, F->d_u, F->n, F->n, F->d_inl, F->d_in_a, F->d_in_ak, F->d_idx, nullptr, nullptr, 0.0, F->prm.use_acceleration_mode,
-                            F->prm.flow_index_mode, F->d_inl_ref, &F->tail, d_best, F->d_refine_ws, &F->refine, state_host(c), F->d_zpartials);
+                            F->prm.flow_index_mode, F->d_inl_ref, &F->tail, d_best, F->d_refine_ws, &F->refine, state_host(c), F->d_zpartials, false,
+                            &F->claim);
     };
     F->refinement_enqueued = false;
     // (the refinement goes behind the SPECULATED final stage unless that stage did not count in the last two RANSACs: data whose
@@ -270,7 +282,8 @@ int frame_begin(Ctx* c, FrameRun* F) {
     F->rc_begin = ransac_begin(c, F->d_q, F->d_u, F->d_a, F->d_ak, n, prm->use_acceleration_mode, prm->ransac_trials, prm->ransac_tol, nullptr, J.seed,
                                prm->depth_mode, prm->k_sign_mode, &F->ro, prm->use_refinement ? &F->spec_tail : nullptr, &F->refinement_enqueued, &F->ransac,
                                F->side_flatten ? &F->direct : nullptr, F->side_flatten && !F->dense_in_launch ? &F->join : nullptr,
-                               F->dense_in_launch ? &F->dense : nullptr, F->ahead, true);
+                               F->dense_in_launch ? &F->dense : nullptr, F->ahead, true,
+                               F->claim.on && prm->use_refinement ? refine_flag_words(F->d_refine_ws) : nullptr);
     return RSDSFM_OK;  // (an error of the speculated run may only mean that n was wrong: frame_finish sorts that out)
 }
 
@@ -307,7 +320,8 @@ int frame_finish(Ctx* c, FrameRun* F, rsdsfm_frame_result* res) {
         counted = false;
         rc = ransac_begin(c, F->d_q, F->d_u, F->d_a, F->d_ak, n, prm->use_acceleration_mode, prm->ransac_trials, prm->ransac_tol, nullptr, J.seed,
                           prm->depth_mode, prm->k_sign_mode, &F->ro, prm->use_refinement ? &F->spec_tail : nullptr, &F->refinement_enqueued, &F->ransac, nullptr, nullptr,
-                          nullptr, F->ahead, true);
+                          nullptr, F->ahead, true,
+                               F->claim.on && prm->use_refinement ? refine_flag_words(F->d_refine_ws) : nullptr);
         if (rc == RSDSFM_OK) rc = ransac_finish(c, &F->ransac);
         counted = rc == RSDSFM_OK;
     }
@@ -334,7 +348,7 @@ int frame_finish(Ctx* c, FrameRun* F, rsdsfm_frame_result* res) {
         }
         if (!F->refinement_enqueued || exact)
             rc = refine_device(c, F->d_u, n, ro.num_inliers, F->d_inl, F->d_in_a, F->d_in_ak, F->d_idx, v, w, k, prm->use_acceleration_mode,
-                               prm->flow_index_mode, F->d_inl_ref, v, w, &k, &res->refine_summary, &F->tail, F->d_zpartials, exact);
+                               prm->flow_index_mode, F->d_inl_ref, v, w, &k, &res->refine_summary, &F->tail, F->d_zpartials, exact, &F->claim);
         if (rc != RSDSFM_OK) return rc;
         d_final = F->d_inl_ref;
         const double* h_header = header_host(c);
@@ -426,6 +440,13 @@ int rsdsfm_set_sequence_lanes(rsdsfm_ctx* ctx, int32_t lanes) {
     return RSDSFM_OK;
 }
 
+int rsdsfm_set_frame_tail(rsdsfm_ctx* ctx, int mode) {
+    if (!ctx) return RSDSFM_ERR_INVALID;
+    if (mode < 0 || mode > 1) return fail(&ctx->c, RSDSFM_ERR_INVALID, "mode must be 0 (short launch tail) or 1 (stage-by-stage launches)");
+    ctx->c.frame_tail = mode;
+    return RSDSFM_OK;
+}
+
 int rsdsfm_set_frame_side_flatten(rsdsfm_ctx* ctx, int mode) {
     if (!ctx) return RSDSFM_ERR_INVALID;
     if (mode < 0 || mode > 3) return fail(&ctx->c, RSDSFM_ERR_INVALID, "mode must be 0 (flatten first), 1 (flatten on a second stream), 2 (flatten behind the minimal solver) or 3 (flatten inside the solver's launch)");
@@ -466,6 +487,7 @@ int rsdsfm_solve_frames_dev(rsdsfm_ctx* ctx, const rsdsfm_frame_job* jobs, int32
         lc->refine_arithmetic = c->refine_arithmetic;
         lc->lma_count_only_force = c->lma_count_only_force;
         lc->frame_side_flatten = c->frame_side_flatten;
+        lc->frame_tail = c->frame_tail;
         lc->refine_stage_mode = c->refine_stage_mode;
     }
     // several pairs in flight share the GPU: the refinement's single-workgroup stage gets launches of its own (Ctx::refine_stage_mode)

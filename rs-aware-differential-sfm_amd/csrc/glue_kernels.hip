@@ -276,6 +276,61 @@ __global__ __launch_bounds__(kGB) void depth_write_kernel(const double* __restri
     }
 }
 
+// zsum_decide_kernel + depth_write_kernel in one launch, behind an output pass that has claimed the pixels (refine_finish_claim_kernel).
+// Every workgroup adds the per-workgroup sums of z itself, in zsum_decide_kernel's order (lane b-strided over 256 lanes, wave_sum,
+// ((s0 + s1) + s2) + s3: the same bits in every workgroup), so every workgroup knows the sign; workgroup 0 writes the header and its host-mapped
+// copy, the scanlines of the pose table are spread over the grid.  A claimed pixel gets z of its owner as the output pass formed it, 1 / rho
+// of the state's current rho buffer -- nobody writes that buffer here --, times -1.0 if the sign flips; the in-place flip of the inliers' z
+// (main.cc:475-478) then only touches `inl`, which this launch does not read otherwise.
+__global__ __launch_bounds__(kGB) void depth_decide_write_kernel(const double* __restrict__ partials, int nblocks, int64_t m, double* __restrict__ header,
+                                                                double* __restrict__ header_host, const double* __restrict__ v_dev,
+                                                                const int64_t* __restrict__ m_dev, PoseTableOut pt, double* __restrict__ inl,
+                                                                const double* __restrict__ rho_a, const double* __restrict__ rho_b,
+                                                                const RefineState* __restrict__ st, const unsigned* __restrict__ owner, unsigned tag,
+                                                                unsigned mask, int64_t npix, double* __restrict__ depth_map) {
+    static_assert(kGB == 256, "zsum_decide_kernel's reduction shape");
+    __shared__ double s_red[4];
+    if (m_dev) m = *m_dev;
+    double acc = 0.0;
+    for (int b = threadIdx.x; b < nblocks; b += 256) acc += partials[b];
+    const double r = wave_sum(acc);
+    if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = r;
+    __syncthreads();
+    const double count_z = ((s_red[0] + s_red[1]) + s_red[2]) + s_red[3];
+    const double z_mean = count_z * 1.0 / (double)m;  // main.cc:472 (NaN for m == 0: no flip)
+    const bool flip = z_mean < 0;
+    Pose pose;
+    pose.v[0] = flip ? v_dev[0] * -1.0 : v_dev[0];
+    pose.v[1] = flip ? v_dev[1] * -1.0 : v_dev[1];
+    pose.v[2] = flip ? v_dev[2] * -1.0 : v_dev[2];
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        header[0] = flip ? 1.0 : 0.0;
+        header[1] = pose.v[0], header[2] = pose.v[1], header[3] = pose.v[2];
+        if (header_host) {
+            header_host[0] = flip ? 1.0 : 0.0;
+            header_host[1] = pose.v[0], header_host[2] = pose.v[1], header_host[3] = pose.v[2];
+        }
+    }
+    const int64_t stride = (int64_t)gridDim.x * kGB;
+    const int64_t g0 = (int64_t)blockIdx.x * kGB + threadIdx.x;
+    if (pt.R) {
+        pose.w[0] = pt.wk_dev[0], pose.w[1] = pt.wk_dev[1], pose.w[2] = pt.wk_dev[2], pose.k = pt.wk_dev[3];
+        for (int64_t i = g0; i < pt.rows; i += stride) pose_table_row(pose, pt.gamma, pt.rows, (int)i, pt.R, pt.t);
+    }
+    const double* __restrict__ rho = st->cur ? rho_b : rho_a;
+    for (int64_t p = g0; p < npix; p += stride) {
+        const unsigned w = owner[p];
+        double d = 0.0;
+        if ((w & ~mask) == tag) {
+            const double z = 1.0 / rho[(int64_t)(w & mask)];
+            d = flip ? z * -1.0 : z;
+        }
+        depth_map[p] = d;
+    }
+    if (flip)
+        for (int64_t i = g0; i < m; i += stride) inl[3 * i + 2] = inl[3 * i + 2] * -1.0;
+}
+
 // exclusive scan of the cell counts in two levels (a single workgroup walking 15 000 ... 130 000 counts serialises on load
 // latency: 31 us at 1280x720).  Level 1: every workgroup scans kScanSeg consecutive counts (coalesced staging through LDS)
 // and writes local exclusive offsets + its segment total; level 2: one workgroup scans the segment totals in place and
@@ -442,6 +497,17 @@ int depth_map_slab_launch(Ctx* c, double* d_inl, int64_t m, const double* d_zsum
         RSDSFM_HIP_CHECK(c, hipGetLastError());
     }
     hipLaunchKernelGGL(depth_write_kernel, dim3(stream_grid(npix)), dim3(kGB), 0, c->stream, d_inl, d_owner, tag, mask, npix, d_depth_map);
+    RSDSFM_HIP_CHECK(c, hipGetLastError());
+    return RSDSFM_OK;
+}
+
+int depth_map_decided_launch(Ctx* c, double* d_inl, int64_t m, const double* d_zsums, int nz, const RefineBuffers& B, double* d_depth_map,
+                             double* d_header, double* h_header, const double* v_dev, const int64_t* m_dev, const PoseTableOut* pt) {
+    const FinishClaim& C = B.claim;
+    if (!C.on || !C.owner || !v_dev) return fail(c, RSDSFM_ERR_INVALID, "depth map: no output pass has claimed the pixels");
+    const int64_t npix = (int64_t)C.rows * C.cols;
+    hipLaunchKernelGGL(depth_decide_write_kernel, dim3(stream_grid(npix)), dim3(kGB), 0, c->stream, d_zsums, nz, m, d_header, h_header, v_dev, m_dev,
+                       pt ? *pt : PoseTableOut(), d_inl, B.rho_a, B.rho_b, B.state, C.owner, C.tag, C.mask, npix, d_depth_map);
     RSDSFM_HIP_CHECK(c, hipGetLastError());
     return RSDSFM_OK;
 }

@@ -224,7 +224,7 @@ int ransac_advance(Ctx* c, RansacRun& R, bool yield_at_wait) {
                     if (rc != RSDSFM_OK) return rc;
                     flags_via_pick = true;
                     rc = ransac_final_launch(c, R.d_q, R.d_u, R.d_a, R.d_ak, n, R.d_best, R.d_states, depth_mode, tol, R.d_rho, R.d_mask, R.d_bcounts,
-                                             R.d_boffs, out->inlier_idx, out->inliers, out->alpha, out->alpha_k, R.h_best);
+                                             R.d_boffs, out->inlier_idx, out->inliers, out->alpha, out->alpha_k, R.h_best, R.refine_flag_words);
                     if (rc != RSDSFM_OK) return rc;
                     R.final_done = true;
                     R.spec_final = true;
@@ -321,7 +321,7 @@ int ransac_advance(Ctx* c, RansacRun& R, bool yield_at_wait) {
                                             R.count_only ? PickLazy{R.d_scored, R.d_unscored, R.d_flags + 1} : PickLazy());
                     if (rc != RSDSFM_OK) return rc;
                     rc = ransac_final_launch(c, R.d_q, R.d_u, R.d_a, R.d_ak, n, R.d_best, R.d_states, depth_mode, tol, R.d_rho, R.d_mask, R.d_bcounts,
-                                             R.d_boffs, out->inlier_idx, out->inliers, out->alpha, out->alpha_k, R.h_best);
+                                             R.d_boffs, out->inlier_idx, out->inliers, out->alpha, out->alpha_k, R.h_best, R.refine_flag_words);
                     if (rc != RSDSFM_OK) return rc;
                 }
                 // the caller's tail behind the DEFINITIVE final stage, where it is not already behind a speculated one that held: it
@@ -436,7 +436,7 @@ void ransac_commit_hints(Ctx* c, const RansacRun& R) {
 int ransac_begin(Ctx* c, const double* d_q, const double* d_u, const double* d_a, const double* d_ak, int64_t n, int use_alpha_k, int T,
                  double tol, const int32_t* h_samples, uint64_t seed, int depth_mode, int k_sign_mode, rsdsfm_ransac_out* out,
                  const RansacSpecTail* spec_tail, bool* spec_tail_held, RansacRun* run, const Minimal9Direct* direct,
-                 const std::function<int()>* after_minimal9, const DenseFlatten* dense, bool tail_ahead, bool count_only) {
+                 const std::function<int()>* after_minimal9, const DenseFlatten* dense, bool tail_ahead, bool count_only, int* refine_flag_words) {
     RansacRun& R = *run;
     R = RansacRun();
     R.tail_ahead = tail_ahead;
@@ -452,6 +452,7 @@ int ransac_begin(Ctx* c, const double* d_q, const double* d_u, const double* d_a
     // pixel under any good hypothesis -- the error sums decide every solve and the fused ones are far cheaper than the scoring pass.
     R.count_only = count_only && R.analytic && T <= kRansacBatch && (c->lma_unique_run >= 2 || c->lma_count_only_force);
     if (R.count_only) R.tie_margin = 0.0;
+    R.refine_flag_words = refine_flag_words;
     if (spec_tail_held) *spec_tail_held = false;
     if (!out) return fail(c, RSDSFM_ERR_INVALID, "null out");
     if (n < 9) return fail(c, RSDSFM_ERR_INVALID, "ransac needs at least 9 points (the reference would compute rand() % 0)");

@@ -948,9 +948,13 @@ __global__ __launch_bounds__(kRB) void ransac_scatter_kernel(const double2* __re
                                                             const double* __restrict__ rho, const uint8_t* __restrict__ mask,
                                                             const int64_t* __restrict__ block_counts, RansacBest* best,
                                                             RansacBest* best_host, int64_t* __restrict__ inlier_idx, double* __restrict__ inliers,
-                                                            double* __restrict__ out_alpha, double* __restrict__ out_alpha_k) {
+                                                            double* __restrict__ out_alpha, double* __restrict__ out_alpha_k,
+                                                            int* __restrict__ zero_words = nullptr) {
     __shared__ int s_wave[kRB / 64];
     __shared__ int64_t s_base;
+    // frame solve: the flag + list-counter words of the refinement that is enqueued behind this stage (kRefineStateBlockTail bytes), cleared here,
+    // a launch in front of their first atomic -- its first pass builds its start state itself and no launch of its own clears them
+    if (zero_words && blockIdx.x == 0 && threadIdx.x < (int)(kRefineStateBlockTail / sizeof(int))) zero_words[threadIdx.x] = 0;
     __shared__ int64_t s_pre[kRB / 64], s_all[kRB / 64];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     // behind a final stage that left at once (RansacBest::undecided, see ransac_pick_kernel) the counts and the mask are stale, possibly
@@ -1198,7 +1202,7 @@ int ransac_pick_launch(Ctx* c, const double* trial_count, const double* trial_er
 int ransac_final_launch(Ctx* c, const double* q, const double* u, const double* a, const double* ak, int64_t n,
                         RansacBest* best, const LmState* states, int depth_mode, double tol, double* rho, uint8_t* mask,
                         int64_t* block_counts, int64_t* block_offsets, int64_t* inlier_idx, double* inliers,
-                        double* out_alpha, double* out_alpha_k, RansacBest* best_host) {
+                        double* out_alpha, double* out_alpha_k, RansacBest* best_host, int* zero_words) {
     int64_t blocks = (n + kRB - 1) / kRB;
     if (blocks < 1) blocks = 1;
     const int64_t cap = 2048;
@@ -1213,8 +1217,9 @@ int ransac_final_launch(Ctx* c, const double* q, const double* u, const double* 
     RSDSFM_HIP_CHECK(c, hipGetLastError());
     if (inlier_idx || inliers || out_alpha || out_alpha_k) {  // the compaction scans the workgroup counts itself
         hipLaunchKernelGGL(ransac_scatter_kernel, dim3((int)blocks), dim3(kRB), 0, c->stream, reinterpret_cast<const double2*>(q),
-                           a, ak, n, chunk, rho, mask, block_counts, best, best_host, inlier_idx, inliers, out_alpha, out_alpha_k);
+                           a, ak, n, chunk, rho, mask, block_counts, best, best_host, inlier_idx, inliers, out_alpha, out_alpha_k, zero_words);
     } else {  // no compacted outputs requested: only the total is needed
+        if (zero_words) RSDSFM_HIP_CHECK(c, hipMemsetAsync(zero_words, 0, kRefineStateBlockTail, c->stream));
         hipLaunchKernelGGL(ransac_scan_kernel, dim3(1), dim3(256), 0, c->stream, block_counts, (int)blocks, block_offsets, best, best_host);
     }
     RSDSFM_HIP_CHECK(c, hipGetLastError());

@@ -23,7 +23,7 @@ namespace rsdsfm {
 int refine_begin(Ctx* c, const double* d_flow, int64_t n_flow, int64_t m, const double* d_inl, const double* d_alpha,
                  const double* d_alpha_k, const int64_t* d_inlier_idx, const double v_in[3], const double w_in[3], double k_in,
                  int const_acceleration, int flow_index_mode, double* d_inl_out, const RefineTail* tail, const RansacBest* d_best,
-                 void* ws_base, RefineRun* run, RefineState* hs_prefetch, double* d_zpartials, bool exact) {
+                 void* ws_base, RefineRun* run, RefineState* hs_prefetch, double* d_zpartials, bool exact, const FinishClaim* claim) {
     if (m < 0 || n_flow < 0 || (!d_best && (!v_in || !w_in))) return fail(c, RSDSFM_ERR_INVALID, "bad arguments");
     if (flow_index_mode != RSDSFM_FLOW_COMPAT_RANK && flow_index_mode != RSDSFM_FLOW_GATHERED) return fail(c, RSDSFM_ERR_INVALID, "unknown flow_index_mode");
     if (flow_index_mode == RSDSFM_FLOW_GATHERED && m > 0 && !d_inlier_idx) return fail(c, RSDSFM_ERR_INVALID, "gathered mode needs inlier_idx");
@@ -63,6 +63,7 @@ int refine_begin(Ctx* c, const double* d_flow, int64_t n_flow, int64_t m, const 
     B.partials = ws.take<double>(npart);
     B.bad_index = reinterpret_cast<int*>(state_block + sizeof(RefineState));
     B.zpartials = d_zpartials;
+    if (claim && claim->on && d_zpartials) B.claim = *claim;
     run->np = np;
     // the radius-factorised path (refine_rf_kernels.hip) unless the context asks for the reference's arithmetic or this solve is run again
     // behind a tripped guard
@@ -76,7 +77,11 @@ int refine_begin(Ctx* c, const double* d_flow, int64_t n_flow, int64_t m, const 
     run->prefetch = hs_prefetch != nullptr;
     run->prefetched = false;
     B.state_host = hs_prefetch;  // prefetch: the output pass writes the state there itself
-    if (d_best) {
+    if (d_best && claim && claim->on && run->rf && !c->refine_stage_separate) {
+        // short launch tail: the first pass builds the start state itself (refine_rf_pass_kernel FIRST), and the flag + list-counter words were
+        // cleared by the RANSAC's compaction, the launch in front of it (RansacRun::refine_flag_words)
+        B.best_dev = d_best;
+    } else if (d_best) {
         rc = refine_state_from_best_launch(c, d_best, B, np);
         if (rc != RSDSFM_OK) return rc;
     } else {
@@ -111,6 +116,9 @@ int refine_begin(Ctx* c, const double* d_flow, int64_t n_flow, int64_t m, const 
     // slots (noise-free data, e.g. ground-truth flow, ends after ONE iteration), where the first chunk is that count + 1, and behind one
     // that took more than 8 (acceleration mode: 7 .. 38, two per iteration that did not speculate or whose speculation did not apply), where it
     // is that count + 1 as well, at most 28.  The chunking changes when the host looks at the state, never what the kernels compute.
+    // (A first chunk that follows the context's recent solves -- the maximum of the last 1 / 2 / 4, with or without + 1 -- was replayed on the
+    // recorded counts of the bench's pairs and of 32 data seeds, tools/frame_tail_iters.py: the counts follow the sampler seed, not the pair, and
+    // every such rule either buys second chunks or enqueues as many finished passes as the fixed 7.  DESIGN section 8b.)
     const int hp = run->hint_prev;
     run->chunk = (hp >= 0 && hp <= 3) ? hp + 1 : (hp > 8 ? std::min(hp + 1, 28) : 7);
     // (radius-factorised path: a solve of `it` candidate evaluations consumes exactly it + 1 slots -- 4 .. 7 on DeepFlow-like pairs, 14 .. 16 in
@@ -152,7 +160,17 @@ int refine_enqueue_chunk(Ctx* c, RefineRun* run) {
     run->launched += run->chunk;
     // the output pass is enqueued before the host knows whether the solve has finished (the common case: <= 5 iterations),
     // which saves a host round trip with an idle GPU; if iterations remain it simply runs again after the next chunk
-    int rc = refine_finish_launch(c, run->B, run->d_inl_out);
+    int rc = RSDSFM_OK;
+    if (run->B.claim.on) {
+        // the claim word holds the inlier index: the map's index field is sized by the larger of the two counts (depth_map_slab_launch).  A new tag
+        // per output pass: what an earlier pass of this solve claimed loses against it like the words of earlier solves do
+        FinishClaim& C = run->B.claim;
+        const int64_t npix = (int64_t)C.rows * C.cols;
+        if (run->B.m >= ((int64_t)1 << 31)) return fail(c, RSDSFM_ERR_INVALID, "depth map: more than 2^31 inliers");
+        rc = claim_map_acquire(c, 2, (size_t)std::max<int64_t>(std::max<int64_t>(npix, run->B.m), 1), &C.owner, &C.tag, &C.mask);
+        if (rc != RSDSFM_OK) return rc;
+    }
+    rc = refine_finish_launch(c, run->B, run->d_inl_out);
     if (rc != RSDSFM_OK) return rc;
     // the tail only pays behind a chunk that can be the last one: where the previous solve needed clearly more slots than are enqueued so
     // far (acceleration mode: ~14) it is left out, and refine_poll enqueues it should the solve end early after all.  (One more than
@@ -218,6 +236,11 @@ int refine_poll(Ctx* c, RefineRun* run, double v_out[3], double w_out[3], double
     return RSDSFM_OK;
 }
 
+int* refine_flag_words(void* ws_base) {
+    Arena ws(ws_base);
+    return reinterpret_cast<int*>(ws.take<char>(sizeof(RefineState) + 64) + sizeof(RefineState));  // (refine_begin: the state block comes first)
+}
+
 size_t refine_workspace_bytes(const Ctx* c, int64_t m, bool m_on_device) {
     const size_t M = (size_t)std::max<int64_t>(m, 1);
     const size_t npart = (size_t)(m_on_device ? refine_partials_doubles_cap(c) : refine_partials_doubles(c, m));
@@ -227,13 +250,13 @@ size_t refine_workspace_bytes(const Ctx* c, int64_t m, bool m_on_device) {
 int refine_device(Ctx* c, const double* d_flow, int64_t n_flow, int64_t m, const double* d_inl, const double* d_alpha,
                   const double* d_alpha_k, const int64_t* d_inlier_idx, const double v_in[3], const double w_in[3], double k_in,
                   int const_acceleration, int flow_index_mode, double* d_inl_out, double v_out[3], double w_out[3], double* k_out,
-                  rsdsfm_lm_summary* summary, const RefineTail* tail, double* d_zpartials, bool exact) {
+                  rsdsfm_lm_summary* summary, const RefineTail* tail, double* d_zpartials, bool exact, const FinishClaim* claim) {
     if (!v_out || !w_out || !k_out) return fail(c, RSDSFM_ERR_INVALID, "bad arguments");
     const double v0[3] = {v_in[0], v_in[1], v_in[2]}, w0[3] = {w_in[0], w_in[1], w_in[2]};  // (v_in may alias v_out)
     for (int attempt = 0;; ++attempt) {
         RefineRun run;
         int rc = refine_begin(c, d_flow, n_flow, m, d_inl, d_alpha, d_alpha_k, d_inlier_idx, v0, w0, k_in, const_acceleration, flow_index_mode,
-                              d_inl_out, tail, nullptr, nullptr, &run, nullptr, d_zpartials, exact || attempt > 0);
+                              d_inl_out, tail, nullptr, nullptr, &run, nullptr, d_zpartials, exact || attempt > 0, claim);
         if (rc != RSDSFM_OK) return rc;
         rc = refine_poll(c, &run, v_out, w_out, k_out, summary);
         if (rc != kRcRefineRestartExact || attempt > 0) return rc == kRcRefineRestartExact ? fail(c, RSDSFM_ERR_NUMERIC, "refinement: restart loop") : rc;

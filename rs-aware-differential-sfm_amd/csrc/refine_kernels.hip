@@ -501,6 +501,47 @@ __global__ __launch_bounds__(kFB) void refine_finish_kernel(int64_t m, const dou
     }
 }
 
+// The output pass of the frame solve's short tail: refine_finish_kernel, and for the inlier it is copying depth_claim_kernel's claim as well
+// (glue_kernels.hip: pixel of (x, y), scanline, atomicMax of `tag | i`).  The claim does not depend on the sign decision that follows -- only
+// the sign of z does -- and an output pass that runs again behind a further chunk claims the same pixels for the same inliers.
+__global__ __launch_bounds__(kFB) void refine_finish_claim_kernel(int64_t m, const double* __restrict__ inl, const double* __restrict__ rho_a,
+                                                                 const double* __restrict__ rho_b, const RefineState* __restrict__ st,
+                                                                 double* __restrict__ inl_out, double* __restrict__ zpartials,
+                                                                 RefineState* __restrict__ state_host, const int* __restrict__ bad_index,
+                                                                 double fx, double fy, double cx, double cy, int rows, int ncols,
+                                                                 unsigned* __restrict__ owner, unsigned tag, int32_t* __restrict__ ys) {
+    __shared__ double s_red[kFB / 64];
+    if (state_host && blockIdx.x == 0) {
+        for (int i = threadIdx.x; i < (int)(sizeof(RefineState) / 8); i += kFB)
+            reinterpret_cast<double*>(state_host)[i] = reinterpret_cast<const double*>(st)[i];
+        if (threadIdx.x == 0) *reinterpret_cast<int*>(reinterpret_cast<char*>(state_host) + sizeof(RefineState)) = *bad_index;
+    }
+    const double* __restrict__ rho = st->cur ? rho_b : rho_a;
+    if (m < 0) m = st->m;
+    const int64_t stride = (int64_t)gridDim.x * kFB;
+    double acc = 0.0;
+    for (int64_t i = (int64_t)blockIdx.x * kFB + threadIdx.x; i < m; i += stride) {
+        const double xn = inl[3 * i], yn = inl[3 * i + 1];
+        inl_out[3 * i] = xn;
+        inl_out[3 * i + 1] = yn;
+        const double z = 1.0 / rho[i];
+        inl_out[3 * i + 2] = z;
+        acc += z;
+        const int x = (int)(fx * xn + cx + 0.5);
+        const int y = (int)(fy * yn + cy + 0.5);
+        ys[i] = y;
+        if (x >= 0 && x < ncols && y >= 0 && y < rows) atomicMax(&owner[(int64_t)x * rows + y], tag | (unsigned)i);
+    }
+    const double r = wave_sum(acc);
+    if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = r;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double t = s_red[0];
+        for (int w2 = 1; w2 < kFB / 64; ++w2) t += s_red[w2];
+        zpartials[blockIdx.x] = t;
+    }
+}
+
 // Start state of a refinement that is enqueued before the host has read the RANSAC result (frame solve): pose of the best trial and
 // the inlier count from the device-resident RansacBest, logical grid by the launchers' rule (refine_grid below).
 __global__ void refine_state_from_best_kernel(const RansacBest* __restrict__ best, RefineState* __restrict__ st, int np, int cap,
@@ -952,6 +993,13 @@ int refine_finish_grid(const Ctx* c, const RefineBuffers& B) { return B.m_on_dev
 
 int refine_finish_launch(Ctx* c, const RefineBuffers& B, double* inl_out) {
     if (!B.m_on_device && B.m == 0 && !B.zpartials && !B.state_host) return RSDSFM_OK;
+    if (B.claim.on) {  // frame solve, short tail (refine_enqueue_chunk has taken the claim map)
+        hipLaunchKernelGGL(refine_finish_claim_kernel, dim3(refine_finish_grid(c, B)), dim3(kFB), 0, c->stream, B.m_on_device ? (int64_t)-1 : B.m, B.inl,
+                           B.rho_a, B.rho_b, B.state, inl_out, B.zpartials, B.state_host, B.bad_index, B.claim.fx, B.claim.fy, B.claim.cx, B.claim.cy,
+                           B.claim.rows, B.claim.cols, B.claim.owner, B.claim.tag, B.claim.ys);
+        RSDSFM_HIP_CHECK(c, hipGetLastError());
+        return RSDSFM_OK;
+    }
     hipLaunchKernelGGL(refine_finish_kernel, dim3(refine_finish_grid(c, B)), dim3(kFB), 0, c->stream,
                        B.m_on_device ? (int64_t)-1 : B.m, B.inl, B.rho_a, B.rho_b, B.state, inl_out, B.zpartials, B.state_host, B.bad_index);
     RSDSFM_HIP_CHECK(c, hipGetLastError());

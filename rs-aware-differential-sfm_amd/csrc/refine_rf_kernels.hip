@@ -687,6 +687,8 @@ struct RfPassArgs {
     int* bad_index;
     unsigned long long* beat;    // opt-in (RSDSFM_SYNC_WATCHDOG_S): host-mapped heartbeat words of this context, see rf_beat
     int slot;
+    const RansacBest* best;      // first pass, frame solve: the start state is built from it here (refine_state_from_best_kernel's rule); null: st_in holds it
+    int grid_cap;                // ... with this cap on the logical grid
     unsigned long long* stamps;  // opt-in (RSDSFM_RF_STAMPS=1): workgroup 0 adds the 100 MHz ticks of its phases here (tools/refine_rf_probe.py)
 };
 
@@ -732,7 +734,36 @@ __global__ __launch_bounds__(kFB) void refine_rf_pass_kernel(const RfPassArgs A)
         for (int i = 0; i < 8; ++i) tk[i] = 0;
     }
     if (stamp) tk[0] = wall_clock64();
-    state_to_lds(&s_state, A.st_in);
+    if (FIRST && A.best) {
+        // the start state of a refinement enqueued before the host has read the RANSAC result, by refine_state_from_best_kernel's rule: every
+        // workgroup builds it for itself (workgroup 0 writes it out below), instead of a one-lane launch in front of this one
+        if (threadIdx.x < sizeof(RefineState) / 8) reinterpret_cast<unsigned long long*>(&s_state)[threadIdx.x] = 0ull;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            RefineState& z = s_state;
+            z.np = NP;
+            for (int i = 0; i < 3; ++i) {
+                z.p[i] = A.best->hyp[3 + i];  // v
+                z.p[3 + i] = A.best->hyp[i];  // w
+            }
+            z.p[6] = A.best->hyp[6];
+            z.termination = -1;
+            z.radius = kInitialRadius;
+            z.need_schur = 1;
+            const int64_t mb = A.best->undecided ? 0 : A.best->num_inliers_scan;  // (a RANSAC that is not over: no inliers, every kernel leaves at once)
+            z.m = mb;
+            int64_t b = (mb + kFB - 1) / kFB;
+            if (b < 1) b = 1;
+            if (b > A.grid_cap) {
+                const int64_t iters = (b + A.grid_cap - 1) / A.grid_cap;
+                b = (b + iters - 1) / iters;
+            }
+            z.grid = (int)b;
+        }
+        __syncthreads();
+    } else {
+        state_to_lds(&s_state, A.st_in);
+    }
     RefineState* st = &s_state;
     if (stamp) tk[1] = wall_clock64();
     if (FIRST) {
@@ -999,6 +1030,9 @@ int refine_rf_extra_doubles() { return 3 * kRfListCap * kRfEntry + 2 * kRfExtDou
 int refine_rf_row_doubles(int np) { return (np == 7 ? RfRow<7>::NW : RfRow<6>::NW) + kRfListDoubles; }
 
 namespace {
+// (with the inlier count on the device the pass is launched with this many workgroups and takes RefineState::grid -- capped by
+// num_cus * kWorkgroupsPerCu where the start state is built -- as its stride and row count: the two caps must be one)
+static_assert(kWorkgroupsPerCu == 1, "rf_grid_cap and the cap of RefineState::grid (refine_state_from_best_kernel) agree only at one workgroup per CU");
 inline int rf_grid_cap(const Ctx* c) { return c->num_cus; }
 inline int rf_grid(const Ctx* c, int64_t m) {
     int64_t b = (m + kFB - 1) / kFB;
@@ -1016,6 +1050,7 @@ struct RfLayout {
     double* list[3];
     RfExt* ext[2];
 };
+static_assert(RfRow<7>::NW <= SlotRow<7>::NW && RfRow<6>::NW <= SlotRow<7>::NW, "the rows buffer is sized by SlotRow<7>::NW doubles per workgroup");
 inline RfLayout rf_layout(const Ctx* c, const RefineBuffers& B) {
     RfLayout Lo;
     double* base = B.partials;
@@ -1127,6 +1162,8 @@ int refine_rf_pass_launch(Ctx* c, const RefineBuffers& B, int np, int g, int g_f
     A.inlier_idx = B.inlier_idx;
     A.flow_index_mode = B.flow_index_mode;
     A.bad_index = B.bad_index;
+    A.best = g == 0 ? B.best_dev : nullptr;
+    A.grid_cap = rf_grid_cap(c);
     A.stamps = rf_stamps(c);
     A.beat = rf_beat(c);
     A.slot = g;

@@ -78,6 +78,7 @@ struct LmState : LmScal {
 };
 
 // device-resident result header of a RANSAC run
+constexpr size_t kRefineStateBlockTail = 32;  // bytes behind RefineState that travel with it: bad-index flag (+0), list counters (+16, +20, +24)
 struct RansacBest {
     int32_t best_trial;
     int32_t undecided;         // 1: written by a pick that ran BEHIND round 0 on flags that say the RANSAC is not over (hypotheses still running or unscored): everything enqueued behind it on speculation leaves at once
@@ -186,6 +187,9 @@ struct Ctx {
     hipStream_t aux_stream = nullptr;
     hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_seq = nullptr;
     int frame_side_flatten = 3;  // rsdsfm_set_frame_side_flatten: where a dense frame's flatten runs -- 0 first, 1 on aux_stream beside the minimal solver, 2 behind it, 3 INSIDE the solver's launch
+    // rsdsfm_set_frame_tail: 0 = the frame solve's short launch tail (the output pass claims the depth-map pixels, one kernel decides the sign and
+    // writes the map), 1 = the stage-by-stage launches (refine_finish, zsum_decide, depth_claim, depth_write).  Which launches run, never a result.
+    int frame_tail = 0;
     unsigned long long* d_flat_counters = nullptr;  // the two counters of minimal9_flatten_kernel (zero between launches)
     int seq_lanes = 0;               // rsdsfm_set_sequence_lanes (0 = kSequenceLanesDefault)
     // where the refinement's single-workgroup stage runs (rsdsfm_set_refine_stage): 0 = automatic -- in the prologue of the next slot's pass
@@ -410,7 +414,7 @@ int ransac_pick_launch(Ctx* c, const double* trial_count, const double* trial_er
 int ransac_final_launch(Ctx* c, const double* q, const double* u, const double* a, const double* ak, int64_t n,
                         RansacBest* best, const LmState* states, int depth_mode, double tol, double* rho, uint8_t* mask,
                         int64_t* block_counts, int64_t* block_offsets, int64_t* inlier_idx, double* inliers,
-                        double* out_alpha, double* out_alpha_k, RansacBest* best_host = nullptr);
+                        double* out_alpha, double* out_alpha_k, RansacBest* best_host = nullptr, int* zero_words = nullptr);
 // row-tiled stages
 int ransac_rows_doubles();
 int ransac_lm_rows_launch(Ctx* c, const double* q, const double* u, const double* a, const double* ak, int64_t n,
@@ -476,6 +480,16 @@ struct RefineState {
 };
 // RefineState::termination of a radius-factorised refinement one of whose guards tripped: the host runs the solve again on the iterate-by-iterate kernels
 constexpr int kTermRestartExact = 64;
+// frame solve, short launch tail (Ctx::frame_tail == 0): the refinement's output pass also claims the depth-map pixel of every inlier it copies
+// (depth_claim_kernel's rule) and writes its scanline; owner / tag / mask are the claim map's, taken in front of every output pass
+struct FinishClaim {
+    bool on = false;
+    double fx = 0.0, fy = 0.0, cx = 0.0, cy = 0.0;
+    int rows = 0, cols = 0;
+    int32_t* ys = nullptr;
+    unsigned* owner = nullptr;
+    unsigned tag = 0, mask = 0;
+};
 struct RefineBuffers {
     const double* flow;  // 2 x n_flow
     int64_t n_flow, m;
@@ -495,6 +509,8 @@ struct RefineBuffers {
     int* bad_index;
     RefineState* state_host = nullptr;  // frame solve: host-mapped copy of the state (+ flag) written by refine_finish_kernel
     double* zpartials = nullptr;  // frame solve: refine_finish_kernel also leaves its per-workgroup sums of z here (refine_finish_grid entries)
+    const RansacBest* best_dev = nullptr;  // frame solve, short launch tail: the first pass builds the start state from it (no refine_state_from_best launch)
+    FinishClaim claim;            // frame solve: the output pass claims the depth-map pixels as well (refine_finish_claim_kernel)
     bool want_zsum = false;       // the streaming passes also sum 1 / rho (one division per inlier and pass) into the last slot of their rows -> RefineState::zsum
 };
 size_t ransac_pinned_bytes(int T);
@@ -516,6 +532,7 @@ struct RansacRun {
     bool core_math = true;   // round 0 through the in-range function cores (ransac_lm_kernel CORE); false after a restart
     bool analytic = false;   // the depth solves on the analytic LM trajectory (ransac_lma_kernels.hip); false after a guard tripped
     bool lma_restarted = false;
+    int* refine_flag_words = nullptr;  // frame solve: words of the refinement behind the final stage that the compaction clears (ransac_scatter_kernel)
     bool count_only = false;  // analytic pass without error sums; ransac_pick_kernel asks for the exact sums of the trials that share the best count
     int lazy_rounds = 0;
     int shared_best = 0;      // RansacBest::shared_best of the definitive pick
@@ -554,7 +571,8 @@ struct RansacRun {
 int ransac_begin(Ctx* c, const double* d_q, const double* d_u, const double* d_a, const double* d_ak, int64_t n, int use_alpha_k, int T,
                  double tol, const int32_t* h_samples, uint64_t seed, int depth_mode, int k_sign_mode, rsdsfm_ransac_out* out,
                  const RansacSpecTail* spec_tail, bool* spec_tail_held, RansacRun* run, const Minimal9Direct* direct,
-                 const std::function<int()>* after_minimal9, const DenseFlatten* dense = nullptr, bool tail_ahead = true, bool count_only = false);
+                 const std::function<int()>* after_minimal9, const DenseFlatten* dense = nullptr, bool tail_ahead = true, bool count_only = false,
+                 int* refine_flag_words = nullptr);
 int ransac_finish(Ctx* c, RansacRun* run);
 void ransac_commit_hints(Ctx* c, const RansacRun& run);
 int flatten_enqueue(Ctx* c, const double* d_img, int32_t rows, int32_t cols, double fx, double fy, double cx, double cy, double gamma,
@@ -562,6 +580,10 @@ int flatten_enqueue(Ctx* c, const double* d_img, int32_t rows, int32_t cols, dou
 // see refine_device (refine_host.hip): caller's work enqueued behind the refinement's output pass, given the device-resident state
 typedef std::function<int(const RefineBuffers&)> RefineTail;
 int refine_finish_grid(const Ctx* c, const RefineBuffers& B);
+// the frame solve's short tail behind an output pass that has claimed the pixels (RefineBuffers::claim): sign decision, header, pose table,
+// depth map and -- only if the sign flips -- z of the inliers in place, in ONE launch; z of a pixel's owner is 1 / rho, the output pass's division
+int depth_map_decided_launch(Ctx* c, double* d_inl, int64_t m, const double* d_zsums, int nz, const RefineBuffers& B, double* d_depth_map,
+                             double* d_header, double* h_header, const double* v_dev, const int64_t* m_dev, const PoseTableOut* pt);
 // one refinement in flight (refine_host.hip: refine_begin / refine_poll)
 struct RefineRun {
     RefineBuffers B;
@@ -582,19 +604,22 @@ size_t refine_workspace_bytes(const Ctx* c, int64_t m, bool m_on_device);
 int refine_begin(Ctx* c, const double* d_flow, int64_t n_flow, int64_t m, const double* d_inl, const double* d_alpha,
                  const double* d_alpha_k, const int64_t* d_inlier_idx, const double v_in[3], const double w_in[3], double k_in,
                  int const_acceleration, int flow_index_mode, double* d_inl_out, const RefineTail* tail, const RansacBest* d_best,
-                 void* ws_base, RefineRun* run, RefineState* hs_prefetch, double* d_zpartials, bool exact = false);
+                 void* ws_base, RefineRun* run, RefineState* hs_prefetch, double* d_zpartials, bool exact = false,
+                 const FinishClaim* claim = nullptr);
 // refine_poll's return value when a guard of the radius-factorised path tripped: nothing was written to the outputs; run the solve again with exact = true
 constexpr int kRcRefineRestartExact = 1;
 int refine_device(Ctx* c, const double* d_flow, int64_t n_flow, int64_t m, const double* d_inl, const double* d_alpha,
                   const double* d_alpha_k, const int64_t* d_inlier_idx, const double v_in[3], const double w_in[3], double k_in,
                   int const_acceleration, int flow_index_mode, double* d_inl_out, double v_out[3], double w_out[3], double* k_out,
-                  rsdsfm_lm_summary* summary, const RefineTail* tail, double* d_zpartials, bool exact = false);
+                  rsdsfm_lm_summary* summary, const RefineTail* tail, double* d_zpartials, bool exact = false, const FinishClaim* claim = nullptr);
 int refine_enqueue_chunk(Ctx* c, RefineRun* run);
 int frames_in_flight(const Ctx* c);  // frame solves between begin and the end of finish on the context's device, all contexts of the process (frame_host.hip)
 int refine_poll(Ctx* c, RefineRun* run, double v_out[3], double w_out[3], double* k_out, rsdsfm_lm_summary* summary);
 int refine_partials_doubles(const Ctx* c, int64_t m);
 int refine_partials_doubles_cap(const Ctx* c);
 int refine_state_from_best_launch(Ctx* c, const RansacBest* d_best, const RefineBuffers& B, int np);
+// the flag + list-counter words (kRefineStateBlockTail bytes) of a refinement whose buffers are laid out at ws_base (refine_begin)
+int* refine_flag_words(void* ws_base);
 // start of a refinement: NaN-fill the opt-in iteration trace (rsdsfm_set_refine_trace), enqueued on the context's stream
 inline int refine_trace_reset(Ctx* c) {
     if (!c->d_refine_trace) return RSDSFM_OK;
@@ -616,7 +641,6 @@ int refine_partials_half_doubles(const Ctx* c);
 int refine_state_doubles();
 // the three list counters of the radius-factorised path live behind the state and its bad-index flag (zeroed with them)
 inline int* refine_rf_counters(const RefineBuffers& B) { return B.bad_index + 4; }
-constexpr size_t kRefineStateBlockTail = 32;  // bytes behind RefineState that travel with it: bad-index flag (+0), list counters (+16, +20, +24)
 // slot `j` of a chunk of `chunk` slots (refine_kernels.hip): its pass carries the single-workgroup stage of slot j - 1 in its prologue; the
 // last one is followed by that stage on its own, which leaves the state in B.state for the output pass, the caller's tail and the host
 int refine_iter_launch(Ctx* c, const RefineBuffers& B, int np, int j, int chunk);
