@@ -23,7 +23,7 @@ extern "C" {
  * omega in (0, 2); every value finite. */
 typedef struct rsdsfm_flow_params {
     double sigma;                    /* pre-smoothing Gaussian (0.6) */
-    int32_t min_size;                /* the pyramid stops before a level with a side <= min_size (25) */
+    int32_t min_size;                /* the pyramid stops before a level with a side <= min_size (25) or < 2 */
     double downscale;                /* pyramid factor per level (0.95) */
     int32_t fixed_point_iterations;  /* outer iterations per level (5) */
     int32_t sor_iterations;          /* red-black SOR iterations per outer iteration (25) */
@@ -37,7 +37,8 @@ typedef struct rsdsfm_flow_params {
 int rsdsfm_flow_default_params(rsdsfm_flow_params* out);
 
 /* camera.cc:253-277, the pyramid DeepFlow builds: level 0 = rows x cols, next side = (int)(side * downscale + 0.5), stop before a level
- * with a side <= min_size (or one that would not shrink).  Host only, no GPU needed.  *n: on entry the capacity of level_rows /
+ * with a side <= min_size or below 2 (the floor of the frame itself, whatever min_size: a 1 x 1 level has no neighbour to smooth
+ * against), or one that would not shrink.  Host only, no GPU needed.  *n: on entry the capacity of level_rows /
  * level_cols (which may be NULL to ask for the count), on return the number of levels; RSDSFM_ERR_INVALID when the capacity is
  * too small (*n then holds the count needed) or the arguments are bad. */
 int rsdsfm_flow_levels(int32_t rows, int32_t cols, const rsdsfm_flow_params* params_or_null, int32_t* n, int32_t* level_rows,

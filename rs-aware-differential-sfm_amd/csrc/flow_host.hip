@@ -42,7 +42,8 @@ void levels_of(int rows, int cols, const rsdsfm_flow_params& p, std::vector<int>
     for (;;) {
         const int r = lr.back(), c = lc.back();
         const int nr = (int)(r * p.downscale + 0.5), nc = (int)(c * p.downscale + 0.5);
-        if (nr <= p.min_size || nc <= p.min_size || (nr == r && nc == c)) return;
+        // no level with a side below 2: a 1x1 level has no neighbour and no derivative, its system is 0 * du = 0 (R1 = 1 / 0)
+        if (nr <= p.min_size || nc <= p.min_size || nr < 2 || nc < 2 || (nr == r && nc == c)) return;
         lr.push_back(nr);
         lc.push_back(nc);
     }

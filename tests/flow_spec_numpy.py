@@ -4,6 +4,7 @@ Two 8-bit images -> a dense flow field (rows x cols x 2, f64).  Every per-pixel 
 operation, in the order written here; the HIP kernels evaluate the same expressions in the same order (-ffp-contract=off,
 correctly rounded / and sqrt), so the device result is this function's result bit for bit.  Gaussian taps and resize
 weights are computed in double and rounded to float once, as the host code does.
+deep_flow(..., dtype=np.float64) is the same algorithm in double: the yardstick for what float32 costs (tests/test_flow_cpu.py).
 
 The structure follows cv::optflow::createOptFlow_DeepFlow() of OpenCV 3.4 (recalled, not verified against its source):
 one pre-smoothing, a bilinear pyramid with factor `downscale`, per level (coarse to fine) a variational refinement with
@@ -29,13 +30,14 @@ def params(**kw):
 
 
 def flow_levels(rows, cols, downscale=0.95, min_size=25):
-    """level 0 = full size; next = (int)(prev * downscale + 0.5) per axis; stop before a level with a side <= min_size (or one that
-    would not shrink at all)"""
+    """level 0 = full size; next = (int)(prev * downscale + 0.5) per axis; stop before a level with a side <= min_size or below 2 (a
+    1x1 level has no neighbour and no derivative: its system is 0 * du = 0; 2 is also the smallest frame), or one that would not
+    shrink at all"""
     levels = [(rows, cols)]
     while True:
         r, c = levels[-1]
         nr, nc = int(r * downscale + 0.5), int(c * downscale + 0.5)
-        if nr <= min_size or nc <= min_size or (nr == r and nc == c):
+        if nr <= min_size or nc <= min_size or nr < 2 or nc < 2 or (nr == r and nc == c):
             return levels
         levels.append((nr, nc))
 
@@ -222,12 +224,15 @@ def constants(p):
                 scale=F(1.0 / p["downscale"]))
 
 
-def deep_flow(img1, img2, **kw):
-    """(rows, cols[, channels]) uint8 x 2 -> (rows, cols, 2) float64"""
+def deep_flow(img1, img2, dtype=F, **kw):
+    """(rows, cols[, channels]) uint8 x 2 -> (rows, cols, 2) float64.  dtype=np.float64 runs the same algorithm with every per-pixel
+    operation in double (the gray images and the zero fields start as float64 and every expression below follows its operands); the
+    taps, the resize weights and the constants stay the float32 values the kernels receive, so the difference to the float32 run is
+    the rounding of the per-pixel arithmetic alone"""
     p = params(**kw)
     k = constants(p)
     taps = gauss_taps(p["sigma"])
-    a, b = smooth(gray(img1), taps), smooth(gray(img2), taps)
+    a, b = smooth(gray(img1).astype(dtype), taps), smooth(gray(img2).astype(dtype), taps)
     rows, cols = a.shape
     levels = flow_levels(rows, cols, p["downscale"], p["min_size"])
     pyr = [(a, b)]
@@ -239,11 +244,11 @@ def deep_flow(img1, img2, **kw):
         r, c = levels[li]
         i1, i2 = pyr[li]
         if u is None:
-            u, v = np.zeros((r, c), F), np.zeros((r, c), F)
+            u, v = np.zeros((r, c), dtype), np.zeros((r, c), dtype)
         else:
             u, v = resize(u, r, c) * k["scale"], resize(v, r, c) * k["scale"]
         d = derivatives(i1, warp(i2, u, v))
-        du, dv = np.zeros((r, c), F), np.zeros((r, c), F)
+        du, dv = np.zeros((r, c), dtype), np.zeros((r, c), dtype)
         red = ((np.arange(r)[:, None] + np.arange(c)[None, :]) % 2) == 0
         for _ in range(p["fixed_point_iterations"]):
             co = coefficients(d, u, v, du, dv, k)
