@@ -12,9 +12,6 @@
 
 namespace rsdsfm {
 
-void flow_release(Ctx* c);  // flow_host.hip: the DeepFlow front end's pyramid workspace of the context
-void flow_seq_release(Ctx* c);  // flow_seq_host.hip: the sequence workspace of the context (rsdsfm_video.h)
-
 int fail(Ctx* c, int code, const char* msg) {
     if (c) c->err = msg;
     return code;
@@ -184,7 +181,6 @@ void rsdsfm_destroy(rsdsfm_ctx* ctx) {
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     frame_release(c);  // (the sequence lanes, the second stream and its events)
     flow_release(c);
-    flow_seq_release(c);
     if (c->d_partials) (void)hipFree(c->d_partials);
     if (c->d_tickets) (void)hipFree(c->d_tickets);
     if (c->d_lm) (void)hipFree(c->d_lm);

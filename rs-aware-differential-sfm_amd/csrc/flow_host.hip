@@ -1,9 +1,13 @@
-// flow_host.hip -- C ABI of the DeepFlow front end (include/rsdsfm_flow.h; Camera::calculateDeepFlow, camera.cc:253-277; DESIGN
-// section 12).  Drives flow_kernels.hip: pre-smoothing, pyramid, then per level (coarse to fine) one entry launch (upsample + warp +
-// averaged image), one derivative launch, and per fixed-point iteration one coefficient launch + the SOR launches.
+// flow_host.hip -- host driver of the DeepFlow front end and its single-pair C ABI (include/rsdsfm_flow.h; Camera::calculateDeepFlow,
+// camera.cc:253-277).  One workspace type and one level loop serve single pairs (flow_kernels.hip) and batches of a
+// clip (flow_seq_kernels.hip; the clip ABI is flow_seq_host.hip): pre-smoothing, pyramid, then per level (coarse to fine) one entry
+// launch (upsample + warp + averaged image), one derivative launch, and per fixed-point iteration one coefficient launch + the SOR
+// launches.  A batch of n pairs reads n + 1 frames and makes exactly the launches of one pair, each serving every pair of the batch
+// (the boundary frame's pyramid is recomputed by the next batch: no extra launch).  All launches run on the context's stream.
+#include <algorithm>
+#include <cassert>
 #include <cmath>
-#include <map>
-#include <mutex>
+#include <string>
 #include <vector>
 
 #include "../../include/rsdsfm_flow.h"
@@ -13,6 +17,9 @@
 
 namespace rsdsfm {
 namespace flowhost {
+namespace {
+
+constexpr int kFlowMaxSide = 16384;
 
 bool params_ok(const rsdsfm_flow_params& p) {
     const double d[] = {p.sigma, p.downscale, p.alpha, p.delta, p.gamma, p.omega};
@@ -21,6 +28,8 @@ bool params_ok(const rsdsfm_flow_params& p) {
     return p.sigma >= 0.0 && p.sigma <= 16.0 && p.min_size >= 0 && p.downscale > 0.0 && p.downscale < 1.0 && p.fixed_point_iterations > 0 &&
            p.sor_iterations > 0 && p.alpha > 0.0 && p.delta >= 0.0 && p.gamma >= 0.0 && p.omega > 0.0 && p.omega < 2.0;
 }
+
+bool sides_ok(int rows, int cols) { return rows >= 2 && cols >= 2 && rows <= kFlowMaxSide && cols <= kFlowMaxSide; }
 
 rsdsfm_flow_params defaults() {
     rsdsfm_flow_params p;
@@ -84,65 +93,46 @@ AxisTab axis_table(int src, int dst, std::vector<int32_t>& ti, std::vector<float
     return a;
 }
 
+FlowResizeTab make_tab(const FlowWs& w, const AxisTab& x, const AxisTab& y) {
+    return FlowResizeTab{w.d_ti + x.i0, w.d_ti + x.i1, w.d_ti + y.i0, w.d_ti + y.i1, w.d_tf + x.w0, w.d_tf + x.w1, w.d_tf + y.w0, w.d_tf + y.w1};
+}
+
+#define FLOW_LAUNCH(expr)                                                                                                  \
+    do {                                                                                                                   \
+        hipError_t _e = (expr);                                                                                            \
+        if (_e != hipSuccess) {                                                                                            \
+            c->err = std::string(w->pair ? "deep flow: " : "deep flow sequence: ") + #expr + ": " + hipGetErrorString(_e); \
+            return RSDSFM_ERR_HIP;                                                                                         \
+        }                                                                                                                  \
+    } while (0)
+
+}  // namespace
+
 int check_args(Ctx* c, int rows, int cols, int channels, const rsdsfm_flow_params* pp, rsdsfm_flow_params* p) {
-    if (rows < 2 || cols < 2 || rows > kFlowMaxSide || cols > kFlowMaxSide) return fail(c, RSDSFM_ERR_INVALID, "deep flow: sides must be in [2, 16384]");
+    if (!sides_ok(rows, cols)) return fail(c, RSDSFM_ERR_INVALID, "deep flow: sides must be in [2, 16384]");
     if (channels != 1 && channels != 3) return fail(c, RSDSFM_ERR_INVALID, "deep flow: channels must be 1 or 3");
     *p = pp ? *pp : defaults();
     if (!params_ok(*p)) return fail(c, RSDSFM_ERR_INVALID, "deep flow: bad parameters");
     return RSDSFM_OK;
 }
 
-}  // namespace flowhost
-
-using namespace flowhost;
-
-namespace {
-
-// the context's pyramid workspace: one device allocation, rebuilt when the size or the pyramid changes
-struct FlowWs {
-    int rows = 0, cols = 0, min_size = -1;
-    double downscale = 0.0, sigma = -1.0;
-    void* d_buf = nullptr;
-    size_t bytes = 0;
-    std::vector<int> lr, lc;
-    std::vector<size_t> lvl_off;  // pyramid level offsets (floats) into each image's pyramid
-    std::vector<AxisTab> down_x, down_y, up_x, up_y;  // [l]: level l -> l + 1 / level l + 1 -> l
-    int radius = 0;
-    std::vector<int32_t> ti;
-    std::vector<float> tf;  // taps first, then the resize weights
-    // device pointers
-    int32_t* d_ti = nullptr;
-    float* d_tf = nullptr;
-    float *pyr1 = nullptr, *pyr2 = nullptr;
-    float* set[2][6] = {};  // per level parity: u, v, du0, dv0, du1, dv1
-    float* avg = nullptr;
-    float* d[FLOW_NDERIV] = {};
-    float* c[FLOW_NCOEF] = {};
-};
-
-std::mutex g_ws_mutex;
-std::map<const Ctx*, FlowWs*> g_ws;
-
-FlowResizeTab make_tab(const FlowWs& w, const AxisTab& x, const AxisTab& y) {
-    return FlowResizeTab{w.d_ti + x.i0, w.d_ti + x.i1, w.d_ti + y.i0, w.d_ti + y.i1, w.d_tf + x.w0, w.d_tf + x.w1, w.d_tf + y.w0, w.d_tf + y.w1};
+FlowWs* flow_ws(Ctx* c, bool pair) {
+    void*& slot = pair ? c->flow_pair : c->flow_clip;
+    if (!slot) slot = new FlowWs(pair);
+    return static_cast<FlowWs*>(slot);
 }
 
-int ensure_flow_ws(Ctx* c, int rows, int cols, const rsdsfm_flow_params& p, FlowWs** out) {
-    FlowWs* w;
-    {
-        std::lock_guard<std::mutex> lk(g_ws_mutex);
-        FlowWs*& slot = g_ws[c];
-        if (!slot) slot = new FlowWs();
-        w = slot;
+int ensure_flow_ws(Ctx* c, FlowWs* w, int B, int rows, int cols, const rsdsfm_flow_params& p) {
+    assert(B >= 1 && B <= kFlowSeqMaxPairs && (!w->pair || B == 1));
+    if (w->d_buf && w->B == B && w->rows == rows && w->cols == cols && w->min_size == p.min_size && w->downscale == p.downscale && w->sigma == p.sigma)
+        return RSDSFM_OK;
+    if (w->d_buf || w->d_ring) {
+        RSDSFM_HIP_CHECK(c, hipStreamSynchronize(c->stream));  // the previous batch may still read them
+        if (w->d_buf) RSDSFM_HIP_CHECK(c, hipFree(w->d_buf));
+        if (w->d_ring) RSDSFM_HIP_CHECK(c, hipFree(w->d_ring));
+        w->d_buf = w->d_ring = nullptr;
     }
-    *out = w;
-    if (w->d_buf && w->rows == rows && w->cols == cols && w->min_size == p.min_size && w->downscale == p.downscale && w->sigma == p.sigma) return RSDSFM_OK;
-    if (w->d_buf) {
-        RSDSFM_HIP_CHECK(c, hipStreamSynchronize(c->stream));  // the previous pair may still read it
-        RSDSFM_HIP_CHECK(c, hipFree(w->d_buf));
-        w->d_buf = nullptr;
-    }
-    w->rows = w->cols = 0;
+    w->B = w->rows = w->cols = 0;
     levels_of(rows, cols, p, w->lr, w->lc);
     const int nl = (int)w->lr.size();
     w->ti.clear();
@@ -161,54 +151,65 @@ int ensure_flow_ws(Ctx* c, int rows, int cols, const rsdsfm_flow_params& p, Flow
             w->up_y.push_back(axis_table(w->lr[l + 1], w->lr[l], w->ti, w->tf));
         }
     }
-    const size_t n = (size_t)rows * cols;
-    const size_t planes = 12 + 1 + FLOW_NDERIV + FLOW_NCOEF;  // two sets of six, avg, derivatives, coefficients
-    size_t bytes = Arena::need(4 * w->ti.size()) + Arena::need(4 * w->tf.size()) + 2 * Arena::need(4 * total) + planes * Arena::need(4 * n);
+    const size_t npix = (size_t)rows * cols;
+    w->stride = Arena::need(4 * npix) / 4;  // (256-byte aligned planes)
+    w->pstride = Arena::need(4 * total) / 4;
+    const size_t pair_planes = 12 + 1 + FLOW_NDERIV + FLOW_NCOEF;  // two sets of six, avg, derivatives, coefficients
+    static_assert(FLOW_NCOEF >= 2, "the coefficient block holds the B + 1 frames of the horizontal pass");
+    // At B = 1 this is a single pair's 2 pyramids + 30 planes to the byte: 4 * pstride = Arena::need(4 * total) and 4 * stride =
+    // Arena::need(4 * npix) are what Arena::take advances by for one pyramid / one plane, so a block of k of them is k separate slices.
+    const size_t bytes = Arena::need(4 * w->ti.size()) + Arena::need(4 * w->tf.size()) + 4 * (size_t)(B + 1) * w->pstride +
+                         4 * pair_planes * (size_t)B * w->stride;
+    assert(B != 1 || bytes == Arena::need(4 * w->ti.size()) + Arena::need(4 * w->tf.size()) + 2 * Arena::need(4 * total) + pair_planes * Arena::need(4 * npix));
     RSDSFM_HIP_CHECK(c, hipMalloc(&w->d_buf, bytes));
-    w->bytes = bytes;
     Arena a(w->d_buf);
     w->d_ti = a.take<int32_t>(w->ti.size());
     w->d_tf = a.take<float>(w->tf.size());
-    w->pyr1 = a.take<float>(total);
-    w->pyr2 = a.take<float>(total);
+    w->pyr = a.take<float>((size_t)(B + 1) * w->pstride);
     for (int s = 0; s < 2; ++s)
-        for (int k = 0; k < 6; ++k) w->set[s][k] = a.take<float>(n);
-    w->avg = a.take<float>(n);
-    for (int k = 0; k < FLOW_NDERIV; ++k) w->d[k] = a.take<float>(n);
-    for (int k = 0; k < FLOW_NCOEF; ++k) w->c[k] = a.take<float>(n);
+        for (int k = 0; k < 6; ++k) w->set[s][k] = a.take<float>((size_t)B * w->stride);
+    w->avg = a.take<float>((size_t)B * w->stride);
+    for (int k = 0; k < FLOW_NDERIV; ++k) w->d[k] = a.take<float>((size_t)B * w->stride);
+    float* cb = a.take<float>((size_t)FLOW_NCOEF * B * w->stride);
+    for (int k = 0; k < FLOW_NCOEF; ++k) w->c[k] = cb + (size_t)k * B * w->stride;
+    assert(a.off == bytes);
     if (!w->ti.empty()) RSDSFM_HIP_CHECK(c, hipMemcpyAsync(w->d_ti, w->ti.data(), 4 * w->ti.size(), hipMemcpyHostToDevice, c->stream));
     RSDSFM_HIP_CHECK(c, hipMemcpyAsync(w->d_tf, w->tf.data(), 4 * w->tf.size(), hipMemcpyHostToDevice, c->stream));
     RSDSFM_HIP_CHECK(c, hipStreamSynchronize(c->stream));  // the host tables are pageable
-    w->rows = rows, w->cols = cols, w->min_size = p.min_size, w->downscale = p.downscale, w->sigma = p.sigma;
+    w->B = B, w->rows = rows, w->cols = cols, w->min_size = p.min_size, w->downscale = p.downscale, w->sigma = p.sigma;
     return RSDSFM_OK;
 }
 
-#define FLOW_LAUNCH(expr)                                                                          \
-    do {                                                                                           \
-        hipError_t _e = (expr);                                                                    \
-        if (_e != hipSuccess) {                                                                    \
-            c->err = std::string("deep flow: ") + #expr + ": " + hipGetErrorString(_e);          \
-            return RSDSFM_ERR_HIP;                                                                 \
-        }                                                                                          \
-    } while (0)
-
-int deep_flow_enqueue(Ctx* c, const uint8_t* img1, const uint8_t* img2, int rows, int cols, int channels, const rsdsfm_flow_params& p, double* flow) {
-    FlowWs* w = nullptr;
-    int rc = ensure_flow_ws(c, rows, cols, p, &w);
-    if (rc != RSDSFM_OK) return rc;
+int flow_enqueue(Ctx* c, const FlowWs* w, const uint8_t* const* frames, int n, int channels, const rsdsfm_flow_params& p, double* const* flows) {
+    assert(n >= 1 && n <= w->B);
     hipStream_t s = c->stream;
     const int nl = (int)w->lr.size();
-    // pre-smoothing (the coefficient planes serve as the horizontal pass's output) and the pyramid
-    FLOW_LAUNCH(flow_presmooth(s, img1, img2, rows, cols, channels, w->d_tf, w->radius, w->c[0], w->c[1], w->pyr1, w->pyr2));
-    for (int l = 0; l + 1 < nl; ++l)
-        FLOW_LAUNCH(flow_pyr_down(s, w->pyr1 + w->lvl_off[l], w->pyr2 + w->lvl_off[l], w->lc[l], make_tab(*w, w->down_x[l], w->down_y[l]), w->lr[l + 1],
-                                  w->lc[l + 1], w->pyr1 + w->lvl_off[l + 1], w->pyr2 + w->lvl_off[l + 1]));
+    const size_t stride = w->stride, pstride = w->pstride;
+    FlowFramePtrs fp{};
+    for (int f = 0; f <= n; ++f) fp.p[f] = frames[f];
+    FlowOutPtrs op{};
+    for (int q = 0; q < n; ++q) op.p[q] = flows[q];
+    // pre-smoothing (the coefficient block serves as the horizontal pass's output) and the pyramid
+    if (w->pair)
+        FLOW_LAUNCH(flow_presmooth(s, frames[0], frames[1], w->rows, w->cols, channels, w->d_tf, w->radius, w->c[0], w->c[0] + stride, w->pyr, w->pyr + pstride));
+    else
+        FLOW_LAUNCH(flow_seq_presmooth(s, fp, n + 1, w->rows, w->cols, channels, w->d_tf, w->radius, w->c[0], stride, w->pyr, pstride));
+    for (int l = 0; l + 1 < nl; ++l) {
+        const float* src = w->pyr + w->lvl_off[l];
+        float* dst = w->pyr + w->lvl_off[l + 1];
+        const FlowResizeTab tab = make_tab(*w, w->down_x[l], w->down_y[l]);
+        if (w->pair)
+            FLOW_LAUNCH(flow_pyr_down(s, src, src + pstride, w->lc[l], tab, w->lr[l + 1], w->lc[l + 1], dst, dst + pstride));
+        else
+            FLOW_LAUNCH(flow_seq_pyr_down(s, src, w->lc[l], tab, w->lr[l + 1], w->lc[l + 1], dst, pstride, n + 1));
+    }
     const FlowConsts k{(float)(4.0 * p.alpha), (float)(p.delta / 3.0), (float)(p.gamma / 3.0)};
     const float scale = (float)(1.0 / p.downscale), om = (float)p.omega, om1 = (float)(1.0 - p.omega);
     int cur_prev = 0;  // which du / dv pair of the coarser level holds its increment
     for (int l = nl - 1; l >= 0; --l) {
         const int r = w->lr[l], cc = w->lc[l];
         float* const* S = w->set[l & 1];
+        const float* pyr_l = w->pyr + w->lvl_off[l];
         FlowLevelBufs L;
         L.u = S[0], L.v = S[1], L.du = S[2], L.dv = S[3], L.avg = w->avg;
         for (int q = 0; q < FLOW_NDERIV; ++q) L.d[q] = w->d[q];
@@ -220,8 +221,12 @@ int deep_flow_enqueue(Ctx* c, const uint8_t* img1, const uint8_t* img2, int rows
             C.rows = w->lr[l + 1], C.cols = w->lc[l + 1];
             C.tab = make_tab(*w, w->up_x[l], w->up_y[l]);
         }
-        FLOW_LAUNCH(flow_level_entry(s, L, w->pyr1 + w->lvl_off[l], w->pyr2 + w->lvl_off[l], r, cc, C, scale));
-        // SOR geometry: one region without halo when the level fits, else regions of interior kFlowRegion - 2 halo
+        if (w->pair)
+            FLOW_LAUNCH(flow_level_entry(s, L, pyr_l, pyr_l + pstride, r, cc, C, scale));
+        else
+            FLOW_LAUNCH(flow_seq_level_entry(s, L, stride, pyr_l, pstride, r, cc, C, scale, n));
+        // SOR geometry: one region without halo when the level fits, else regions of interior kFlowRegion - 2 halo (red-black order:
+        // the tiling decides no value)
         const bool single = r <= kFlowRegion && cc <= kFlowRegion;
         const int halo = single ? 0 : 2 * kFlowSorBlock, inner = kFlowRegion - 2 * halo;
         const int tiles_x = (cc + inner - 1) / inner, tiles_y = (r + inner - 1) / inner;
@@ -229,7 +234,10 @@ int deep_flow_enqueue(Ctx* c, const uint8_t* img1, const uint8_t* img2, int rows
         int cur = 0;
         for (int f = 0; f < p.fixed_point_iterations; ++f) {
             L.du = S[2 + 2 * cur], L.dv = S[3 + 2 * cur];
-            FLOW_LAUNCH(flow_coef(s, L, r, cc, k));
+            if (w->pair)
+                FLOW_LAUNCH(flow_coef(s, L, r, cc, k));
+            else
+                FLOW_LAUNCH(flow_seq_coef(s, L, stride, r, cc, k, n));
             for (int done = 0; done < p.sor_iterations; done += per_launch) {
                 FlowSorArgs a;
                 for (int q = 0; q < FLOW_NCOEF; ++q) a.c[q] = w->c[q];
@@ -238,37 +246,64 @@ int deep_flow_enqueue(Ctx* c, const uint8_t* img1, const uint8_t* img2, int rows
                 a.rows = r, a.cols = cc, a.halo = halo, a.tiles_x = tiles_x;
                 a.nit = std::min(per_launch, p.sor_iterations - done);
                 a.om = om, a.om1 = om1;
-                FLOW_LAUNCH(flow_sor(s, a, tiles_x * tiles_y));
+                if (w->pair)
+                    FLOW_LAUNCH(flow_sor(s, a, tiles_x * tiles_y));
+                else
+                    FLOW_LAUNCH(flow_seq_sor(s, a, stride, tiles_x * tiles_y, n));
                 cur = 1 - cur;
             }
         }
         cur_prev = cur;
         if (l == 0) {
             L.du = S[2 + 2 * cur], L.dv = S[3 + 2 * cur];
-            FLOW_LAUNCH(flow_output(s, L, r, cc, flow));
+            if (w->pair)
+                FLOW_LAUNCH(flow_output(s, L, r, cc, flows[0]));
+            else
+                FLOW_LAUNCH(flow_seq_output(s, L, stride, r, cc, op, n));
         }
     }
     return RSDSFM_OK;
 }
 
-}  // namespace
+int flow_staged(Ctx* c, const FlowWs* w, const uint8_t* const* frames, int nframes, int channels, const rsdsfm_flow_params& p, double* const* flows) {
+    const int B = w->B;
+    const size_t npix = (size_t)w->rows * (size_t)w->cols, img_bytes = npix * (size_t)channels;
+    int rc = ensure_stage(c, (size_t)(B + 1) * Arena::need(img_bytes) + (size_t)B * Arena::need(16 * npix));
+    if (rc != RSDSFM_OK) return rc;
+    Arena sa(c->d_stage);
+    const uint8_t* d_img[kFlowSeqMaxPairs + 1];
+    double* d_flow[kFlowSeqMaxPairs];
+    for (int f = 0; f <= B; ++f) d_img[f] = sa.take<uint8_t>(img_bytes);
+    for (int q = 0; q < B; ++q) d_flow[q] = sa.take<double>(2 * npix);
+    for (int g0 = 0; g0 < nframes - 1; g0 += B) {
+        const int n = std::min(B, nframes - 1 - g0);
+        for (int f = 0; f <= n; ++f)
+            RSDSFM_HIP_CHECK(c, hipMemcpyAsync(const_cast<uint8_t*>(d_img[f]), frames[g0 + f], img_bytes, hipMemcpyHostToDevice, c->stream));
+        rc = flow_enqueue(c, w, d_img, n, channels, p, d_flow);
+        if (rc != RSDSFM_OK) return rc;
+        for (int q = 0; q < n; ++q) RSDSFM_HIP_CHECK(c, hipMemcpyAsync(flows[g0 + q], d_flow[q], 16 * npix, hipMemcpyDeviceToHost, c->stream));
+        RSDSFM_HIP_CHECK(c, hipStreamSynchronize(c->stream));  // the next batch overwrites the staging buffer
+    }
+    return RSDSFM_OK;
+}
+
+}  // namespace flowhost
 
 void flow_release(Ctx* c) {
-    FlowWs* w = nullptr;
-    {
-        std::lock_guard<std::mutex> lk(g_ws_mutex);
-        auto it = g_ws.find(c);
-        if (it == g_ws.end()) return;
-        w = it->second;
-        g_ws.erase(it);
+    for (void** slot : {&c->flow_pair, &c->flow_clip}) {
+        flowhost::FlowWs* w = static_cast<flowhost::FlowWs*>(*slot);
+        if (!w) continue;
+        if (w->d_buf) (void)hipFree(w->d_buf);
+        if (w->d_ring) (void)hipFree(w->d_ring);
+        delete w;
+        *slot = nullptr;
     }
-    if (w->d_buf) (void)hipFree(w->d_buf);
-    delete w;
 }
 
 }  // namespace rsdsfm
 
 using namespace rsdsfm;
+using namespace rsdsfm::flowhost;
 
 extern "C" {
 
@@ -281,7 +316,7 @@ int rsdsfm_flow_default_params(rsdsfm_flow_params* out) {
 int rsdsfm_flow_levels(int32_t rows, int32_t cols, const rsdsfm_flow_params* params_or_null, int32_t* n, int32_t* level_rows, int32_t* level_cols) {
     if (!n) return RSDSFM_ERR_INVALID;
     const rsdsfm_flow_params p = params_or_null ? *params_or_null : defaults();
-    if (rows < 2 || cols < 2 || rows > kFlowMaxSide || cols > kFlowMaxSide || !params_ok(p)) return RSDSFM_ERR_INVALID;
+    if (!sides_ok(rows, cols) || !params_ok(p)) return RSDSFM_ERR_INVALID;
     std::vector<int> lr, lc;
     levels_of(rows, cols, p, lr, lc);
     const int cap = *n;
@@ -301,7 +336,11 @@ int rsdsfm_deep_flow_dev(rsdsfm_ctx* ctx, const uint8_t* d_img1, const uint8_t* 
     int rc = check_args(c, rows, cols, channels, params_or_null, &p);
     if (rc != RSDSFM_OK) return rc;
     if (!d_img1 || !d_img2 || !d_flow) return fail(c, RSDSFM_ERR_INVALID, "deep flow: null device pointer");
-    return deep_flow_enqueue(c, d_img1, d_img2, rows, cols, channels, p, d_flow);
+    FlowWs* w = flow_ws(c, true);
+    rc = ensure_flow_ws(c, w, 1, rows, cols, p);
+    if (rc != RSDSFM_OK) return rc;
+    const uint8_t* const frames[2] = {d_img1, d_img2};
+    return flow_enqueue(c, w, frames, 1, channels, p, &d_flow);
 }
 
 int rsdsfm_deep_flow(rsdsfm_ctx* ctx, const uint8_t* img1, const uint8_t* img2, int32_t rows, int32_t cols, int32_t channels,
@@ -313,20 +352,11 @@ int rsdsfm_deep_flow(rsdsfm_ctx* ctx, const uint8_t* img1, const uint8_t* img2, 
     int rc = check_args(c, rows, cols, channels, params_or_null, &p);
     if (rc != RSDSFM_OK) return rc;
     if (!img1 || !img2 || !flow) return fail(c, RSDSFM_ERR_INVALID, "deep flow: null pointer");
-    const size_t npix = (size_t)rows * (size_t)cols, img_bytes = npix * (size_t)channels;
-    rc = ensure_stage(c, 2 * Arena::need(img_bytes) + Arena::need(16 * npix));
+    FlowWs* w = flow_ws(c, true);
+    rc = ensure_flow_ws(c, w, 1, rows, cols, p);
     if (rc != RSDSFM_OK) return rc;
-    Arena sa(c->d_stage);
-    uint8_t* d_a = sa.take<uint8_t>(img_bytes);
-    uint8_t* d_b = sa.take<uint8_t>(img_bytes);
-    double* d_flow = sa.take<double>(2 * npix);
-    RSDSFM_HIP_CHECK(c, hipMemcpyAsync(d_a, img1, img_bytes, hipMemcpyHostToDevice, c->stream));
-    RSDSFM_HIP_CHECK(c, hipMemcpyAsync(d_b, img2, img_bytes, hipMemcpyHostToDevice, c->stream));
-    rc = deep_flow_enqueue(c, d_a, d_b, rows, cols, channels, p, d_flow);
-    if (rc != RSDSFM_OK) return rc;
-    RSDSFM_HIP_CHECK(c, hipMemcpyAsync(flow, d_flow, 16 * npix, hipMemcpyDeviceToHost, c->stream));
-    RSDSFM_HIP_CHECK(c, hipStreamSynchronize(c->stream));
-    return RSDSFM_OK;
+    const uint8_t* const frames[2] = {img1, img2};
+    return flow_staged(c, w, frames, 2, channels, p, &flow);
 }
 
 }  // extern "C"

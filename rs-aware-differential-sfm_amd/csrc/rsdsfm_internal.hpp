@@ -176,6 +176,11 @@ struct Ctx {
     size_t tile_bytes = 0;
     void* tile_session = nullptr;  // heap RefineBuffers of the open session
     int tile_np = 0;
+    // DeepFlow front end (flow_host.hip): heap FlowWs of single pairs and of clips, made on first use, and rsdsfm_set_flow_batch's
+    // pairs per batch of a clip (0 = the default)
+    void* flow_pair = nullptr;
+    void* flow_clip = nullptr;
+    int flow_batch = 0;
     // persistent claim maps of the forward-splat kernels (rectify_kernels.hip: claim_map_acquire): 0 = back projection, 1 = depth image
     unsigned* d_claim[3] = {nullptr, nullptr, nullptr};  // 2 = the depth map of the solve (glue_kernels.hip: depth_claim_kernel)
     size_t claim_words[3] = {0, 0, 0};
@@ -225,6 +230,7 @@ constexpr int kSequenceLanesDefault = 3;  // measured: 1 / 2 / 3 / 4 / 6 / 8 lan
 void dist_release(Ctx* c);
 void dist_reset_hold(Ctx* c);
 void frame_release(Ctx* c);
+void flow_release(Ctx* c);  // flow_host.hip: both DeepFlow workspaces of the context
 
 constexpr int kDepthBlock = 256;
 constexpr int kDepthMaxBlocks = 512;
