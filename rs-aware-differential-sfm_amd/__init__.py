@@ -1021,6 +1021,61 @@ for _name, _fn in list(vars(_VideoMixin).items()):
 
 
 # ---------------------------------------------------------------------------------------------------
+# rectified products of whole clips, gray frames included (include/rsdsfm_rectify_video.h)
+# ---------------------------------------------------------------------------------------------------
+RECTIFY_VIDEO_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "rsdsfm_rectify_video.h")
+
+
+def rectify_video_declared_symbols():
+    """Names of every function include/rsdsfm_rectify_video.h declares"""
+    import re
+
+    txt = open(RECTIFY_VIDEO_HEADER_PATH).read()
+    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
+    return sorted(set(re.findall(r"\b(rsdsfm_[a-z0-9_]+)\s*\(", txt)))
+
+
+class _RectifyVideoMixin:
+    def rectify_gray_frame_dev(self, d_inl, m, d_img, d_depth_map, d_R, d_t, K, rows, cols, d_preview, d_gs, d_fixed, d_coords=None, mode=BACKPROJECT_RS,
+                               q5_mode=Q5_COMPAT, offset=1):
+        """rectify_frame_dev on a one-channel image (rsdsfm_rectify_gray_frame_dev): d_img, d_gs, d_fixed are rows x cols bytes; the outputs are
+        channel 0 of rectify_frame_dev's for the image (g, g, g), the depth image and the world points are its bit for bit"""
+        d = C.c_double
+        self._check(self.lib.rsdsfm_rectify_gray_frame_dev(self._ctx, _np0(d_inl), C.c_int64(m), _dp(d_img), _dp(d_depth_map), _dp(d_R), _dp(d_t), d(K[0]),
+                                                           d(K[1]), d(K[2]), d(K[3]), C.c_int32(rows), C.c_int32(cols), int(mode), int(q5_mode),
+                                                           C.c_int32(offset), _dp(d_preview), _dp(d_gs), _np0(d_coords), _dp(d_fixed)),
+                    "rsdsfm_rectify_gray_frame_dev")
+
+    def rectify_video_dev(self, d_frames, rows, cols, channels, K, gamma, d_depth_maps, d_depth_est, d_gs, d_fixed, d_coords=None, seeds=None,
+                          d_flows=None, d_R=None, d_t=None, flow_params=None, mode=BACKPROJECT_RS, q5_mode=Q5_COMPAT, offset=1, trials=50, tol=0.05,
+                          use_acceleration_mode=False, use_refinement=True, depth_mode=DEPTH_CERES_LM, k_sign_mode=K_COMPAT, flow_threshold=1e-10,
+                          flow_index_mode=FLOW_COMPAT_RANK, use_global_shutter_mode=False):
+        """solve_video_dev plus, per pair p, the rectification of frame p with pair p's solve, in ONE call (rsdsfm_rectify_video_dev).
+        d_depth_est, d_gs, d_fixed (and optionally d_coords): F - 1 device buffers each -- rows x cols bytes, rows x cols x channels bytes
+        (twice), rows x cols x 3 floats; channels 1 = gray frames and gray images.  All outputs are complete on return.  Returns one dict
+        per pair, as solve_video_dev."""
+        n = len(d_frames) - 1
+        prm = FrameParams(int(trials), int(use_acceleration_mode), int(use_refinement), int(depth_mode), int(k_sign_mode),
+                          int(flow_index_mode), int(use_global_shutter_mode), 0, float(tol), float(flow_threshold), 1)
+        res = (FrameResult * max(n, 1))()
+        sd = (C.c_uint64 * n)(*[int(s) for s in seeds]) if seeds is not None else None
+        arr = lambda a: _ptr_array(a) if a is not None else None
+        p = _flow_params(flow_params)
+        d = C.c_double
+        self._check(self.lib.rsdsfm_rectify_video_dev(self._ctx, _ptr_array(d_frames), C.c_int32(len(d_frames)), C.c_int32(rows), C.c_int32(cols),
+                                                      C.c_int32(channels), d(K[0]), d(K[1]), d(K[2]), d(K[3]), d(gamma),
+                                                      C.byref(p) if p is not None else None, C.byref(prm), sd, arr(d_flows), _ptr_array(d_depth_maps),
+                                                      arr(d_R), arr(d_t), res, int(mode), int(q5_mode), C.c_int32(offset), _ptr_array(d_depth_est),
+                                                      _ptr_array(d_gs), _ptr_array(d_fixed), arr(d_coords)), "rsdsfm_rectify_video_dev")
+        return [_frame_result_dict(r) for r in res[:n]]
+
+
+for _name, _fn in list(vars(_RectifyVideoMixin).items()):
+    if not _name.startswith("__"):
+        setattr(Solver, _name, _fn)
+
+
+# ---------------------------------------------------------------------------------------------------
 # accuracy metrics (SURVEY 8 f-4)
 # ---------------------------------------------------------------------------------------------------
 class ReprojectionStats(C.Structure):

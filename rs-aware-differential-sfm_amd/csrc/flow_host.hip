@@ -126,11 +126,13 @@ int ensure_flow_ws(Ctx* c, FlowWs* w, int B, int rows, int cols, const rsdsfm_fl
     assert(B >= 1 && B <= kFlowSeqMaxPairs && (!w->pair || B == 1));
     if (w->d_buf && w->B == B && w->rows == rows && w->cols == cols && w->min_size == p.min_size && w->downscale == p.downscale && w->sigma == p.sigma)
         return RSDSFM_OK;
-    if (w->d_buf || w->d_ring) {
+    if (w->d_buf || w->d_ring || w->d_tables) {
         RSDSFM_HIP_CHECK(c, hipStreamSynchronize(c->stream));  // the previous batch may still read them
         if (w->d_buf) RSDSFM_HIP_CHECK(c, hipFree(w->d_buf));
         if (w->d_ring) RSDSFM_HIP_CHECK(c, hipFree(w->d_ring));
+        if (w->d_tables) RSDSFM_HIP_CHECK(c, hipFree(w->d_tables));  // (rsdsfm_rectify_video_dev waits for every lane before it returns)
         w->d_buf = w->d_ring = nullptr;
+        w->d_tables = nullptr;
     }
     w->B = w->rows = w->cols = 0;
     levels_of(rows, cols, p, w->lr, w->lc);
@@ -295,6 +297,7 @@ void flow_release(Ctx* c) {
         if (!w) continue;
         if (w->d_buf) (void)hipFree(w->d_buf);
         if (w->d_ring) (void)hipFree(w->d_ring);
+        if (w->d_tables) (void)hipFree(w->d_tables);
         delete w;
         *slot = nullptr;
     }

@@ -13,6 +13,8 @@
 namespace rsdsfm {
 namespace flowhost {
 
+constexpr int kLaneTables = 16;  // the most lanes rsdsfm_set_sequence_lanes admits
+
 // resize tables of one axis (tests/flow_spec_numpy.py resize_table): offsets into the workspace's int / float tables
 struct AxisTab {
     size_t i0, i1, w0, w1;
@@ -22,7 +24,7 @@ struct AxisTab {
 // working planes, rebuilt when the size, the pyramid or B changes.  A context owns two (flow_ws; alternating calls rebuild neither):
 // the pair one (B = 1, the single-pair kernels of flow_kernels.hip) and the clip one (B from rsdsfm_set_flow_batch, the batched
 // kernels of flow_seq_kernels.hip at every B).  The ring of B fields of rsdsfm_solve_video_dev is a second allocation of the clip
-// one, made on first use.
+// one, made on first use; so are the lanes' scratch pose tables of rsdsfm_rectify_video_dev.
 struct FlowWs {
     const bool pair;  // which kernel set and error prefix: never n == 1 (a clip at B = 1 runs the batched kernels)
     int B = 0, rows = 0, cols = 0, min_size = -1;
@@ -30,6 +32,7 @@ struct FlowWs {
     void* d_buf = nullptr;
     void* d_ring = nullptr;
     size_t ring_stride = 0;  // bytes between the ring's fields
+    double* d_tables = nullptr;  // kLaneTables x rows x 12 doubles: per lane R (rows x 9) then t (rows x 3)
     std::vector<int> lr, lc;
     std::vector<size_t> lvl_off;  // pyramid level offsets (floats) into each frame's pyramid
     std::vector<AxisTab> down_x, down_y, up_x, up_y;  // [l]: level l -> l + 1 / level l + 1 -> l

@@ -9,6 +9,7 @@
 #include "flow_host.hpp"
 #include "flow_kernels.hpp"
 #include "rsdsfm_internal.hpp"
+#include "sequence_host.hpp"
 
 namespace rsdsfm {
 namespace {
@@ -31,12 +32,11 @@ int ensure_ring(Ctx* c, FlowWs* w) {
     return RSDSFM_OK;
 }
 
-template <class T>
-bool all_set(const T* const* a, int n) {
-    if (!a) return false;
-    for (int i = 0; i < n; ++i)
-        if (!a[i]) return false;
-    return true;
+// the lanes' scratch pose tables behind rsdsfm_rectify_video_dev's d_R_or_null / d_t_or_null = NULL (freed with the workspace)
+int ensure_tables(Ctx* c, FlowWs* w) {
+    if (w->d_tables) return RSDSFM_OK;
+    RSDSFM_HIP_CHECK(c, hipMalloc(reinterpret_cast<void**>(&w->d_tables), sizeof(double) * 12 * (size_t)w->rows * kLaneTables));
+    return RSDSFM_OK;
 }
 
 int check_clip(Ctx* c, int nframes, int rows, int cols, int channels, const rsdsfm_flow_params* pp, rsdsfm_flow_params* p) {
@@ -47,6 +47,57 @@ int check_clip(Ctx* c, int nframes, int rows, int cols, int channels, const rsds
 }
 
 }  // namespace
+
+int solve_video_run(rsdsfm_ctx* ctx, const uint8_t* const* d_frames, int32_t nframes, int32_t rows, int32_t cols, int32_t channels, double fx, double fy,
+                    double cx, double cy, double gamma, const rsdsfm_flow_params* flow_params_or_null, const rsdsfm_frame_params* params,
+                    const uint64_t* seeds, double* const* d_flows_or_null, double* const* d_depth_maps, double* const* d_R_or_null,
+                    double* const* d_t_or_null, rsdsfm_frame_result* results, const PairHook* hook, bool lane_tables) {
+    Ctx* c = &ctx->c;
+    rsdsfm_flow_params p;
+    int rc = check_clip(c, nframes, rows, cols, channels, flow_params_or_null, &p);
+    if (rc != RSDSFM_OK) return rc;
+    const int np = nframes - 1;
+    if (!params || !results) return fail(c, RSDSFM_ERR_INVALID, "solve video: bad arguments");
+    if (!all_set(d_frames, nframes) || !all_set(d_depth_maps, np) || (d_flows_or_null && !all_set(d_flows_or_null, np)) ||
+        (d_R_or_null && !all_set(d_R_or_null, np)) || (d_t_or_null && !all_set(d_t_or_null, np)))
+        return fail(c, RSDSFM_ERR_INVALID, "solve video: null device pointer");
+    FlowWs* w = nullptr;
+    rc = clip_ws(c, rows, cols, p, &w);
+    if (rc == RSDSFM_OK && !d_flows_or_null) rc = ensure_ring(c, w);
+    const bool tables = hook && lane_tables && (!d_R_or_null || !d_t_or_null);
+    if (rc == RSDSFM_OK && tables) rc = ensure_tables(c, w);
+    if (rc != RSDSFM_OK) return rc;
+    const int B = w->B;
+    double* fl[kFlowSeqMaxPairs];
+    rsdsfm_frame_job jobs[kFlowSeqMaxPairs];
+    for (int g0 = 0; g0 < np; g0 += B) {
+        const int n = std::min(B, np - g0);
+        for (int q = 0; q < n; ++q)
+            fl[q] = d_flows_or_null ? d_flows_or_null[g0 + q] : reinterpret_cast<double*>(static_cast<char*>(w->d_ring) + (size_t)q * w->ring_stride);
+        rc = flow_enqueue(c, w, d_frames + g0, n, channels, p, fl);
+        if (rc != RSDSFM_OK) return rc;
+        const int L = sequence_lane_count(c, n);
+        for (int q = 0; q < n; ++q) {
+            // (a lane's table is read by the hook's work on that lane's stream and written by the lane's next solve behind it)
+            double* lane_R = tables ? w->d_tables + (size_t)(q % L) * 12 * (size_t)rows : nullptr;
+            jobs[q] = rsdsfm_frame_job{fl[q], rows, cols, fx, fy, cx, cy, gamma, d_depth_maps[g0 + q], d_R_or_null ? d_R_or_null[g0 + q] : lane_R,
+                                       d_t_or_null ? d_t_or_null[g0 + q] : (lane_R ? lane_R + 9 * (size_t)rows : nullptr),
+                                       seeds ? seeds[g0 + q] : params->seed};
+        }
+        const PairHook in_clip = [&](Ctx* lane, int pair, const rsdsfm_frame_job& job, const rsdsfm_frame_result& r) { return (*hook)(lane, g0 + pair, job, r); };
+        rc = solve_frames_run(c, jobs, n, params, results + g0, hook ? &in_clip : nullptr);
+        if (rc != RSDSFM_OK) {
+            // the pairs of the batch are numbered from 0: number them within the clip
+            const size_t colon = c->err.find(':');
+            if (g0 > 0 && c->err.compare(0, 5, "pair ") == 0 && colon != std::string::npos)
+                c->err = "pair " + std::to_string(g0 + std::stoi(c->err.substr(5, colon - 5))) + c->err.substr(colon);
+            return rc;
+        }
+        for (int i = 0; i < g0; ++i) results[i].d_inliers = nullptr, results[i].d_inlier_idx = nullptr, results[i].d_scanline = nullptr;
+    }
+    return RSDSFM_OK;
+}
+
 }  // namespace rsdsfm
 
 using namespace rsdsfm;
@@ -97,43 +148,9 @@ int rsdsfm_solve_video_dev(rsdsfm_ctx* ctx, const uint8_t* const* d_frames, int3
                            const rsdsfm_frame_params* params, const uint64_t* seeds, double* const* d_flows_or_null, double* const* d_depth_maps,
                            double* const* d_R_or_null, double* const* d_t_or_null, rsdsfm_frame_result* results) {
     if (!ctx) return RSDSFM_ERR_INVALID;
-    Ctx* c = &ctx->c;
-    DeviceGuard device_guard_(c);
-    rsdsfm_flow_params p;
-    int rc = check_clip(c, nframes, rows, cols, channels, flow_params_or_null, &p);
-    if (rc != RSDSFM_OK) return rc;
-    const int np = nframes - 1;
-    if (!params || !results) return fail(c, RSDSFM_ERR_INVALID, "solve video: bad arguments");
-    if (!all_set(d_frames, nframes) || !all_set(d_depth_maps, np) || (d_flows_or_null && !all_set(d_flows_or_null, np)) ||
-        (d_R_or_null && !all_set(d_R_or_null, np)) || (d_t_or_null && !all_set(d_t_or_null, np)))
-        return fail(c, RSDSFM_ERR_INVALID, "solve video: null device pointer");
-    FlowWs* w = nullptr;
-    rc = clip_ws(c, rows, cols, p, &w);
-    if (rc == RSDSFM_OK && !d_flows_or_null) rc = ensure_ring(c, w);
-    if (rc != RSDSFM_OK) return rc;
-    const int B = w->B;
-    double* fl[kFlowSeqMaxPairs];
-    rsdsfm_frame_job jobs[kFlowSeqMaxPairs];
-    for (int g0 = 0; g0 < np; g0 += B) {
-        const int n = std::min(B, np - g0);
-        for (int q = 0; q < n; ++q)
-            fl[q] = d_flows_or_null ? d_flows_or_null[g0 + q] : reinterpret_cast<double*>(static_cast<char*>(w->d_ring) + (size_t)q * w->ring_stride);
-        rc = flow_enqueue(c, w, d_frames + g0, n, channels, p, fl);
-        if (rc != RSDSFM_OK) return rc;
-        for (int q = 0; q < n; ++q)
-            jobs[q] = rsdsfm_frame_job{fl[q], rows, cols, fx, fy, cx, cy, gamma, d_depth_maps[g0 + q], d_R_or_null ? d_R_or_null[g0 + q] : nullptr,
-                                       d_t_or_null ? d_t_or_null[g0 + q] : nullptr, seeds ? seeds[g0 + q] : params->seed};
-        rc = rsdsfm_solve_frames_dev(ctx, jobs, n, params, results + g0);
-        if (rc != RSDSFM_OK) {
-            // rsdsfm_solve_frames_dev numbers the pairs of the batch from 0: number them within the clip
-            const size_t colon = c->err.find(':');
-            if (g0 > 0 && c->err.compare(0, 5, "pair ") == 0 && colon != std::string::npos)
-                c->err = "pair " + std::to_string(g0 + std::stoi(c->err.substr(5, colon - 5))) + c->err.substr(colon);
-            return rc;
-        }
-        for (int i = 0; i < g0; ++i) results[i].d_inliers = nullptr, results[i].d_inlier_idx = nullptr, results[i].d_scanline = nullptr;
-    }
-    return RSDSFM_OK;
+    DeviceGuard device_guard_(&ctx->c);
+    return solve_video_run(ctx, d_frames, nframes, rows, cols, channels, fx, fy, cx, cy, gamma, flow_params_or_null, params, seeds, d_flows_or_null,
+                           d_depth_maps, d_R_or_null, d_t_or_null, results, nullptr, false);
 }
 
 }  // extern "C"

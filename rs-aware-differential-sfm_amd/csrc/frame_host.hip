@@ -20,6 +20,7 @@
 #include <new>
 
 #include "rsdsfm_internal.hpp"
+#include "sequence_host.hpp"
 
 namespace rsdsfm {
 
@@ -454,18 +455,20 @@ int rsdsfm_set_frame_side_flatten(rsdsfm_ctx* ctx, int mode) {
     return RSDSFM_OK;
 }
 
+}  // extern "C"
+
+namespace rsdsfm {
+
+int sequence_lane_count(const Ctx* c, int count) { return std::max(1, std::min<int>(count, c->seq_lanes > 0 ? c->seq_lanes : kSequenceLanesDefault)); }
+
 // A sequence of frame pairs through ONE context, one host thread (BASELINE configs[4], "sequence throughput mode").  Pair i runs on
 // lane i % L: lane 0 is the context itself, the others are contexts of their own (stream, workspace, scheduling hints) owned by it.
 // Up to L pairs are in flight: the host begins pair i (frame_begin: enqueues its whole speculated chain, no wait) and only then
 // finishes pair i - L + 1 (frame_finish: waits for it).  Every pair's results are those of rsdsfm_solve_frame_dev (which lane, which
 // neighbours and which hints a pair meets decides when its kernels run, never what they compute).
-int rsdsfm_solve_frames_dev(rsdsfm_ctx* ctx, const rsdsfm_frame_job* jobs, int32_t count, const rsdsfm_frame_params* prm, rsdsfm_frame_result* results) {
-    if (!ctx) return RSDSFM_ERR_INVALID;
-    Ctx* c = &ctx->c;
-    DeviceGuard device_guard_(c);
-    if (count < 0 || !prm || (count > 0 && (!jobs || !results))) return fail(c, RSDSFM_ERR_INVALID, "bad arguments");
-    if (count == 0) return RSDSFM_OK;
-    const int L = std::max(1, std::min<int>(count, c->seq_lanes > 0 ? c->seq_lanes : kSequenceLanesDefault));
+// The hook (sequence_host.hpp), if any, runs right after frame_finish of pair i on its lane, before that lane begins pair i + L.
+int solve_frames_run(Ctx* c, const rsdsfm_frame_job* jobs, int32_t count, const rsdsfm_frame_params* prm, rsdsfm_frame_result* results, const PairHook* hook) {
+    const int L = sequence_lane_count(c, count);
     while ((int)c->lanes.size() < L - 1) {
         rsdsfm_ctx* lane = nullptr;
         int rc = rsdsfm_create(&lane, c->device, nullptr);
@@ -505,6 +508,13 @@ int rsdsfm_solve_frames_dev(rsdsfm_ctx* ctx, const rsdsfm_frame_job* jobs, int32
             first_error = rc;
             if (lc != c) c->err = "pair " + std::to_string(i) + ": " + lc->err;
         }
+        if (rc == RSDSFM_OK && hook && first_error == RSDSFM_OK) {
+            rc = (*hook)(lc, i, static_cast<FrameRun*>(lc->frame_run)->job, results[i]);
+            if (rc != RSDSFM_OK) {
+                first_error = rc;
+                c->err = "pair " + std::to_string(i) + ": " + std::string(lc->err);
+            }
+        }
     };
     for (int i = 0; i < count && first_error == RSDSFM_OK; ++i) {
         const int l = i % L;
@@ -536,6 +546,19 @@ int rsdsfm_solve_frames_dev(rsdsfm_ctx* ctx, const rsdsfm_frame_job* jobs, int32
     }
     for (int l = 0; l < L; ++l) lane_ctx(l)->refine_stage_separate = false;  // (single solves on this context: the stage back in the prologue)
     return first_error;
+}
+
+}  // namespace rsdsfm
+
+extern "C" {
+
+int rsdsfm_solve_frames_dev(rsdsfm_ctx* ctx, const rsdsfm_frame_job* jobs, int32_t count, const rsdsfm_frame_params* prm, rsdsfm_frame_result* results) {
+    if (!ctx) return RSDSFM_ERR_INVALID;
+    Ctx* c = &ctx->c;
+    DeviceGuard device_guard_(c);
+    if (count < 0 || !prm || (count > 0 && (!jobs || !results))) return fail(c, RSDSFM_ERR_INVALID, "bad arguments");
+    if (count == 0) return RSDSFM_OK;
+    return solve_frames_run(c, jobs, count, prm, results, nullptr);
 }
 
 int rsdsfm_set_refine_stage(rsdsfm_ctx* ctx, int mode) {

@@ -17,6 +17,12 @@
 //       Camera::interpolateCrackyImage (camera.cc:694-774): 4-neighbour fill of black pixels.
 //   preview_claim_minmax_kernel / preview_write_kernel
 //       the 8-bit depth image of evaluateSingleRun (main.cc:480-509).
+//   *_gray_kernel
+//       the same stages on a ONE-channel image (rsdsfm_rectify_gray_frame_dev).  A gray value g stands for the BGR pixel (g, g, g) and
+//       the outputs are channel 0 of the BGR result: the three rules are symmetric in the channels (marker g == 1; black 3 g^2 <= 225;
+//       fill value the mean of the non-black neighbours), so one byte per pixel is loaded, kept (LDS word, registers) and stored --
+//       1 B + 8 B read, 1 B + 1 B + 12 B written per pixel.  The bodies take the channel count CH as a template parameter; the BGR
+//       kernels instantiate CH = 3, the gray ones CH = 1.
 //
 // Arithmetic mirrors oracle/rsdsfm_oracle.c (rso_back_project, rso_interpolate_cracky, rso_depth_preview) operation
 // for operation; all outputs are integers / bytes (bit-exact) except the float3 world points (bit-exact as well: the
@@ -26,6 +32,7 @@
 #include <algorithm>
 
 #include "device_math.hpp"
+#include "rectify_gray.hpp"
 #include "rsdsfm_internal.hpp"
 
 namespace rsdsfm {
@@ -48,6 +55,8 @@ __device__ __forceinline__ int trunc_int(double x) {
 // decided exactly by the integers.
 __device__ __forceinline__ bool is_black(unsigned b, unsigned g, unsigned r) { return b * b + g * g + r * r <= 225u; }
 
+__device__ __forceinline__ bool is_black(unsigned g) { return 3u * g * g <= 225u; }  // the pixel (g, g, g): g <= 8
+
 __device__ __forceinline__ unsigned char saturate_u8(double v) {  // cvRound (nearest even) + clamp
     const long long r = __double2ll_rn(v);
     return (unsigned char)(r < 0 ? 0 : (r > 255 ? 255 : r));
@@ -59,6 +68,7 @@ __device__ __forceinline__ unsigned char saturate_u8(double v) {  // cvRound (ne
 // A wave walks one scanline segment of 64 pixels at a time, so the scanline index is wave-uniform and its pose (12
 // doubles) comes through the scalar data path; every pixel of the image is visited exactly once, so the world point of
 // skipped (marker) pixels is zeroed here instead of by a separate memset.
+template <int CH>
 __device__ __forceinline__ void back_project_claim_body(int bx, int by, const unsigned char* __restrict__ img,
                                                         const double* __restrict__ depth_cm, const double* __restrict__ R,
                                                         const double* __restrict__ t, double fx, double fy, double cx, double cy, double fyp,
@@ -90,7 +100,10 @@ __device__ __forceinline__ void back_project_claim_body(int bx, int by, const un
         const int y = y0 + wv + j * (kCB / kTX);
         const bool live = y < rows && x < cols;
         const int64_t s = live ? (int64_t)y * cols + x : 0;
-        pb[j] = img[3 * s], pg_[j] = img[3 * s + 1], pr[j] = img[3 * s + 2];
+        if constexpr (CH == 3)
+            pb[j] = img[3 * s], pg_[j] = img[3 * s + 1], pr[j] = img[3 * s + 2];
+        else
+            pb[j] = pg_[j] = pr[j] = img[s];  // one byte load; the marker test below then reads g == 1
         const int ys = (mode == 0 && y < rows) ? y : 0;
 #pragma unroll
         for (int i = 0; i < 9; ++i) Rr[j][i] = R[(int64_t)ys * 9 + i];
@@ -151,11 +164,12 @@ __global__ __launch_bounds__(kCB) void back_project_claim_kernel(const unsigned 
                                                                 double fx, double fy, double cx, double cy, double fyp, int rows,
                                                                 int cols, int mode, unsigned* __restrict__ owner, unsigned tag,
                                                                 float* __restrict__ c3d) {
-    back_project_claim_body(blockIdx.x, blockIdx.y, img, depth_cm, R, t, fx, fy, cx, cy, fyp, rows, cols, mode, owner, tag, c3d);
+    back_project_claim_body<3>(blockIdx.x, blockIdx.y, img, depth_cm, R, t, fx, fy, cx, cy, fyp, rows, cols, mode, owner, tag, c3d);
 }
 
-// 4 target pixels (12 bytes) per thread
+// 4 target pixels (12 bytes; one channel: 4 bytes = one dword) per thread
 // a claim word is valid for this frame iff its bits above `mask` equal `tag`; its low bits are the winner's scan index
+template <int CH>
 __device__ __forceinline__ void back_project_write_body(int block, int nblocks, const unsigned char* __restrict__ img,
                                                         const unsigned* __restrict__ owner, unsigned tag, unsigned mask, int64_t npix,
                                                         unsigned char* __restrict__ gs) {
@@ -164,28 +178,38 @@ __device__ __forceinline__ void back_project_write_body(int block, int nblocks, 
         if (p0 + 4 <= npix) {
             const uint4 o = *reinterpret_cast<const uint4*>(owner + p0);  // p0 multiple of 4: 16-byte aligned
             const unsigned oo[4] = {o.x, o.y, o.z, o.w};
-            unsigned v[12];
+            if constexpr (CH == 1) {
+                unsigned v[4];
 #pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const bool hit = (oo[j] & ~mask) == tag;
-                const int64_t src = 3 * (int64_t)(hit ? (oo[j] & mask) : 0u);
-                const unsigned b = img[src], g = img[src + 1], r = img[src + 2];
-                v[3 * j] = hit ? b : 0u;
-                v[3 * j + 1] = hit ? g : 0u;
-                v[3 * j + 2] = hit ? r : 0u;
+                for (int j = 0; j < 4; ++j) {
+                    const bool hit = (oo[j] & ~mask) == tag;
+                    const unsigned g = img[hit ? (oo[j] & mask) : 0u];
+                    v[j] = hit ? g : 0u;
+                }
+                *reinterpret_cast<unsigned*>(gs + p0) = v[0] | (v[1] << 8) | (v[2] << 16) | (v[3] << 24);  // p0 % 4 == 0: 4-byte aligned
+            } else {
+                unsigned v[12];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const bool hit = (oo[j] & ~mask) == tag;
+                    const int64_t src = 3 * (int64_t)(hit ? (oo[j] & mask) : 0u);
+                    const unsigned b = img[src], g = img[src + 1], r = img[src + 2];
+                    v[3 * j] = hit ? b : 0u;
+                    v[3 * j + 1] = hit ? g : 0u;
+                    v[3 * j + 2] = hit ? r : 0u;
+                }
+                unsigned* dst = reinterpret_cast<unsigned*>(gs + 3 * p0);  // 12 p0 bytes: 4-byte aligned
+                dst[0] = v[0] | (v[1] << 8) | (v[2] << 16) | (v[3] << 24);
+                dst[1] = v[4] | (v[5] << 8) | (v[6] << 16) | (v[7] << 24);
+                dst[2] = v[8] | (v[9] << 8) | (v[10] << 16) | (v[11] << 24);
             }
-            unsigned* dst = reinterpret_cast<unsigned*>(gs + 3 * p0);  // 12 p0 bytes: 4-byte aligned
-            dst[0] = v[0] | (v[1] << 8) | (v[2] << 16) | (v[3] << 24);
-            dst[1] = v[4] | (v[5] << 8) | (v[6] << 16) | (v[7] << 24);
-            dst[2] = v[8] | (v[9] << 8) | (v[10] << 16) | (v[11] << 24);
         } else {
             for (int64_t p = p0; p < npix; ++p) {
                 const unsigned w = owner[p];
                 const bool hit = (w & ~mask) == tag;
                 const int64_t o = (int64_t)(w & mask);
-                gs[3 * p] = hit ? img[3 * o] : 0;
-                gs[3 * p + 1] = hit ? img[3 * o + 1] : 0;
-                gs[3 * p + 2] = hit ? img[3 * o + 2] : 0;
+#pragma unroll
+                for (int c2 = 0; c2 < CH; ++c2) gs[CH * p + c2] = hit ? img[CH * o + c2] : 0;
             }
         }
     }
@@ -194,7 +218,7 @@ __device__ __forceinline__ void back_project_write_body(int block, int nblocks, 
 __global__ __launch_bounds__(kBP) void back_project_write_kernel(const unsigned char* __restrict__ img,
                                                                 const unsigned* __restrict__ owner, unsigned tag, unsigned mask,
                                                                 int64_t npix, unsigned char* __restrict__ gs) {
-    back_project_write_body(blockIdx.x, gridDim.x, img, owner, tag, mask, npix, gs);
+    back_project_write_body<3>(blockIdx.x, gridDim.x, img, owner, tag, mask, npix, gs);
 }
 
 // one pixel of the stencil; (b, g, r) hold the pixel's own colour on entry and the result on exit
@@ -223,13 +247,49 @@ __device__ __forceinline__ void interpolate_pixel(const unsigned char* __restric
     }
 }
 
-// 4 pixels (12 bytes = 3 dwords) per thread: most pixels are not black and are simply copied
-__global__ __launch_bounds__(kBP) void interpolate_cracky_kernel(const unsigned char* __restrict__ in, int rows, int cols,
-                                                                int offset, unsigned char* __restrict__ out) {
+// the same on one channel: the mean of the non-black neighbours in double, as every channel of the BGR pixel (g, g, g) gets it
+__device__ __forceinline__ void interpolate_pixel(const unsigned char* __restrict__ in, int rows, int cols, int offset, int64_t p, unsigned& g) {
+    const int row = (int)(p / cols), col = (int)(p - (int64_t)row * cols);
+    if (!(row >= offset && row < rows - offset && col >= offset && col < cols - offset && is_black(g))) return;
+    const int64_t nb[4] = {p - (int64_t)offset * cols, p + (int64_t)offset * cols, p - offset, p + offset};
+    double s0 = 0;
+    unsigned count = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const unsigned n0 = in[nb[j]];
+        if (!is_black(n0)) {
+            s0 += (double)n0;
+            count++;
+        }
+    }
+    if (count > 0) g = saturate_u8(1 / (double)count * s0);
+}
+
+// 4 pixels (12 bytes = 3 dwords; one channel: one dword) per thread: most pixels are not black and are simply copied
+template <int CH>
+__device__ __forceinline__ void interpolate_cracky_body(const unsigned char* __restrict__ in, int rows, int cols, int offset,
+                                                        unsigned char* __restrict__ out) {
     const int64_t npix = (int64_t)rows * cols;
     const int64_t stride = (int64_t)gridDim.x * kBP * 4;
     for (int64_t p0 = ((int64_t)blockIdx.x * kBP + threadIdx.x) * 4; p0 < npix; p0 += stride) {
-        if (p0 + 4 <= npix) {
+        if constexpr (CH == 1) {
+            if (p0 + 4 <= npix) {
+                const unsigned w = *reinterpret_cast<const unsigned*>(in + p0);  // p0 % 4 == 0: 4-byte aligned
+                unsigned v[4];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    v[j] = (w >> (8 * j)) & 0xffu;
+                    interpolate_pixel(in, rows, cols, offset, p0 + j, v[j]);
+                }
+                *reinterpret_cast<unsigned*>(out + p0) = v[0] | (v[1] << 8) | (v[2] << 16) | (v[3] << 24);
+            } else {
+                for (int64_t p = p0; p < npix; ++p) {
+                    unsigned g = in[p];
+                    interpolate_pixel(in, rows, cols, offset, p, g);
+                    out[p] = (unsigned char)g;
+                }
+            }
+        } else if (p0 + 4 <= npix) {
             const unsigned* src = reinterpret_cast<const unsigned*>(in + 3 * p0);  // 12 p0 bytes: 4-byte aligned
             unsigned w[3] = {src[0], src[1], src[2]};
             unsigned v[12];
@@ -251,6 +311,16 @@ __global__ __launch_bounds__(kBP) void interpolate_cracky_kernel(const unsigned 
             }
         }
     }
+}
+
+__global__ __launch_bounds__(kBP) void interpolate_cracky_kernel(const unsigned char* __restrict__ in, int rows, int cols,
+                                                                int offset, unsigned char* __restrict__ out) {
+    interpolate_cracky_body<3>(in, rows, cols, offset, out);
+}
+
+__global__ __launch_bounds__(kBP) void interpolate_cracky_gray_kernel(const unsigned char* __restrict__ in, int rows, int cols,
+                                                                     int offset, unsigned char* __restrict__ out) {
+    interpolate_cracky_body<1>(in, rows, cols, offset, out);
 }
 
 // ---- 8-bit depth preview (main.cc:480-509) ----
@@ -382,9 +452,11 @@ __global__ __launch_bounds__(kBP) void preview_write_kernel(const double* __rest
 
 // ---- back-projection write pass + crack interpolation on one tile (rsdsfm_rectify_frame_dev with offset <= kMaxHalo) ------------------
 // The interpolation (camera.cc:694-774) only reads the global-shutter image at the pixel and its four neighbours `offset` away, so a
-// workgroup that forms a kWT x kHT tile of that image plus a halo of `offset` pixels from the claim map (LDS: one packed BGR word per pixel)
-// can write the tile of BOTH images: no launch of its own for the interpolation, and the global-shutter image is not read back.
+// workgroup that forms a kWT x kHT tile of that image plus a halo of `offset` pixels from the claim map (LDS: one packed BGR word per pixel;
+// one channel: the word holds g) can write the tile of BOTH images: no launch of its own for the interpolation, and the global-shutter image
+// is not read back.
 constexpr int kWT = 64, kHT = 16, kMaxHalo = 2;
+template <int CH>
 __device__ __forceinline__ void write_interpolate_body(int bx, int by, const unsigned char* __restrict__ img, const unsigned* __restrict__ owner,
                                                        unsigned tag, unsigned mask, int rows, int cols, int offset, unsigned char* __restrict__ gs,
                                                        unsigned char* __restrict__ fixed) {
@@ -399,8 +471,12 @@ __device__ __forceinline__ void write_interpolate_body(int bx, int by, const uns
         if (x >= 0 && x < cols && y >= 0 && y < rows) {
             const unsigned w = owner[(int64_t)y * cols + x];
             if ((w & ~mask) == tag) {
-                const int64_t src = 3 * (int64_t)(w & mask);
-                v = (unsigned)img[src] | ((unsigned)img[src + 1] << 8) | ((unsigned)img[src + 2] << 16);
+                if constexpr (CH == 3) {
+                    const int64_t src = 3 * (int64_t)(w & mask);
+                    v = (unsigned)img[src] | ((unsigned)img[src + 1] << 8) | ((unsigned)img[src + 2] << 16);
+                } else {
+                    v = img[w & mask];
+                }
             }
         }
         s_px[i] = v;
@@ -410,56 +486,90 @@ __device__ __forceinline__ void write_interpolate_body(int bx, int by, const uns
     const int ly = tid / (kWT / 4), lx4 = (tid - ly * (kWT / 4)) * 4;
     const int y = by * kHT + ly, xb = bx * kWT + lx4;
     if (y >= rows || xb >= cols) return;
-    unsigned g[12], f[12];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int x = xb + j;
-        const unsigned c0 = s_px[(ly + h) * W + (lx4 + j + h)];
-        unsigned b = c0 & 0xffu, gg = (c0 >> 8) & 0xffu, r = c0 >> 16;
-        g[3 * j] = b, g[3 * j + 1] = gg, g[3 * j + 2] = r;
-        if (x < cols && y >= offset && y < rows - offset && x >= offset && x < cols - offset && is_black(b, gg, r)) {  // interpolate_pixel on the tile
-            const unsigned nb[4] = {s_px[(ly + h - offset) * W + (lx4 + j + h)], s_px[(ly + h + offset) * W + (lx4 + j + h)],
-                                    s_px[(ly + h) * W + (lx4 + j + h - offset)], s_px[(ly + h) * W + (lx4 + j + h + offset)]};
-            double s0 = 0, s1 = 0, s2 = 0;
-            unsigned count = 0;
-#pragma unroll
-            for (int k2 = 0; k2 < 4; ++k2) {
-                const unsigned n0 = nb[k2] & 0xffu, n1 = (nb[k2] >> 8) & 0xffu, n2 = nb[k2] >> 16;
-                if (!is_black(n0, n1, n2)) {
-                    s0 += (double)n0;
-                    s1 += (double)n1;
-                    s2 += (double)n2;
-                    count++;
-                }
-            }
-            if (count > 0) {
-                const double inv = 1 / (double)count;
-                b = saturate_u8(inv * s0);
-                gg = saturate_u8(inv * s1);
-                r = saturate_u8(inv * s2);
-            }
-        }
-        f[3 * j] = b, f[3 * j + 1] = gg, f[3 * j + 2] = r;
-    }
     const int64_t p0 = (int64_t)y * cols + xb;
-    if (xb + 4 <= cols && ((3 * p0) & 3) == 0) {
-        unsigned* dg = reinterpret_cast<unsigned*>(gs + 3 * p0);
-        unsigned* df = reinterpret_cast<unsigned*>(fixed + 3 * p0);
+    if constexpr (CH == 1) {  // 4 bytes = one dword of each image
+        unsigned g[4], f[4];
 #pragma unroll
-        for (int d = 0; d < 3; ++d) {
-            dg[d] = g[4 * d] | (g[4 * d + 1] << 8) | (g[4 * d + 2] << 16) | (g[4 * d + 3] << 24);
-            df[d] = f[4 * d] | (f[4 * d + 1] << 8) | (f[4 * d + 2] << 16) | (f[4 * d + 3] << 24);
+        for (int j = 0; j < 4; ++j) {
+            const int x = xb + j;
+            unsigned v = s_px[(ly + h) * W + (lx4 + j + h)];
+            g[j] = v;
+            if (x < cols && y >= offset && y < rows - offset && x >= offset && x < cols - offset && is_black(v)) {  // interpolate_pixel on the tile
+                const unsigned nb[4] = {s_px[(ly + h - offset) * W + (lx4 + j + h)], s_px[(ly + h + offset) * W + (lx4 + j + h)],
+                                        s_px[(ly + h) * W + (lx4 + j + h - offset)], s_px[(ly + h) * W + (lx4 + j + h + offset)]};
+                double s0 = 0;
+                unsigned count = 0;
+#pragma unroll
+                for (int k2 = 0; k2 < 4; ++k2)
+                    if (!is_black(nb[k2])) {
+                        s0 += (double)nb[k2];
+                        count++;
+                    }
+                if (count > 0) v = saturate_u8(1 / (double)count * s0);
+            }
+            f[j] = v;
+        }
+        if (xb + 4 <= cols && (p0 & 3) == 0) {
+            *reinterpret_cast<unsigned*>(gs + p0) = g[0] | (g[1] << 8) | (g[2] << 16) | (g[3] << 24);
+            *reinterpret_cast<unsigned*>(fixed + p0) = f[0] | (f[1] << 8) | (f[2] << 16) | (f[3] << 24);
+        } else {
+            for (int j = 0; j < 4 && xb + j < cols; ++j) {
+                gs[p0 + j] = (unsigned char)g[j];
+                fixed[p0 + j] = (unsigned char)f[j];
+            }
         }
     } else {
-        for (int j = 0; j < 4 && xb + j < cols; ++j)
-            for (int c2 = 0; c2 < 3; ++c2) {
-                gs[3 * (p0 + j) + c2] = (unsigned char)g[3 * j + c2];
-                fixed[3 * (p0 + j) + c2] = (unsigned char)f[3 * j + c2];
+        unsigned g[12], f[12];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int x = xb + j;
+            const unsigned c0 = s_px[(ly + h) * W + (lx4 + j + h)];
+            unsigned b = c0 & 0xffu, gg = (c0 >> 8) & 0xffu, r = c0 >> 16;
+            g[3 * j] = b, g[3 * j + 1] = gg, g[3 * j + 2] = r;
+            if (x < cols && y >= offset && y < rows - offset && x >= offset && x < cols - offset && is_black(b, gg, r)) {  // interpolate_pixel on the tile
+                const unsigned nb[4] = {s_px[(ly + h - offset) * W + (lx4 + j + h)], s_px[(ly + h + offset) * W + (lx4 + j + h)],
+                                        s_px[(ly + h) * W + (lx4 + j + h - offset)], s_px[(ly + h) * W + (lx4 + j + h + offset)]};
+                double s0 = 0, s1 = 0, s2 = 0;
+                unsigned count = 0;
+#pragma unroll
+                for (int k2 = 0; k2 < 4; ++k2) {
+                    const unsigned n0 = nb[k2] & 0xffu, n1 = (nb[k2] >> 8) & 0xffu, n2 = nb[k2] >> 16;
+                    if (!is_black(n0, n1, n2)) {
+                        s0 += (double)n0;
+                        s1 += (double)n1;
+                        s2 += (double)n2;
+                        count++;
+                    }
+                }
+                if (count > 0) {
+                    const double inv = 1 / (double)count;
+                    b = saturate_u8(inv * s0);
+                    gg = saturate_u8(inv * s1);
+                    r = saturate_u8(inv * s2);
+                }
             }
+            f[3 * j] = b, f[3 * j + 1] = gg, f[3 * j + 2] = r;
+        }
+        if (xb + 4 <= cols && ((3 * p0) & 3) == 0) {
+            unsigned* dg = reinterpret_cast<unsigned*>(gs + 3 * p0);
+            unsigned* df = reinterpret_cast<unsigned*>(fixed + 3 * p0);
+#pragma unroll
+            for (int d = 0; d < 3; ++d) {
+                dg[d] = g[4 * d] | (g[4 * d + 1] << 8) | (g[4 * d + 2] << 16) | (g[4 * d + 3] << 24);
+                df[d] = f[4 * d] | (f[4 * d + 1] << 8) | (f[4 * d + 2] << 16) | (f[4 * d + 3] << 24);
+            }
+        } else {
+            for (int j = 0; j < 4 && xb + j < cols; ++j)
+                for (int c2 = 0; c2 < 3; ++c2) {
+                    gs[3 * (p0 + j) + c2] = (unsigned char)g[3 * j + c2];
+                    fixed[3 * (p0 + j) + c2] = (unsigned char)f[3 * j + c2];
+                }
+        }
     }
 }
 
-__global__ __launch_bounds__(kBP) void rectify_write_interpolate_kernel(const unsigned char* __restrict__ img, const unsigned* __restrict__ owner_bp,
+template <int CH>
+__device__ __forceinline__ void rectify_write_interpolate_body(const unsigned char* __restrict__ img, const unsigned* __restrict__ owner_bp,
                                                                        unsigned tag_bp, unsigned mask_bp, int rows, int cols, int offset,
                                                                        unsigned char* __restrict__ gs, unsigned char* __restrict__ fixed, int tiles_x,
                                                                        int nb_t, const double* __restrict__ inl, const unsigned* __restrict__ owner_pv,
@@ -467,9 +577,23 @@ __global__ __launch_bounds__(kBP) void rectify_write_interpolate_kernel(const un
                                                                        int nrows_pv, int tiles_x_pv, unsigned char* __restrict__ preview) {
     const int b = blockIdx.x;
     if (b < nb_t)
-        write_interpolate_body(b % tiles_x, b / tiles_x, img, owner_bp, tag_bp, mask_bp, rows, cols, offset, gs, fixed);
+        write_interpolate_body<CH>(b % tiles_x, b / tiles_x, img, owner_bp, tag_bp, mask_bp, rows, cols, offset, gs, fixed);
     else
         preview_write_body((b - nb_t) % tiles_x_pv, (b - nb_t) / tiles_x_pv, inl, owner_pv, tag_pv, mask_pv, partials, nrows_pv, rows, cols, preview);
+}
+
+__global__ __launch_bounds__(kBP) void rectify_write_interpolate_kernel(const unsigned char* __restrict__ img, const unsigned* __restrict__ owner_bp,
+        unsigned tag_bp, unsigned mask_bp, int rows, int cols, int offset, unsigned char* __restrict__ gs, unsigned char* __restrict__ fixed, int tiles_x, int nb_t,
+        const double* __restrict__ inl, const unsigned* __restrict__ owner_pv, unsigned tag_pv, unsigned mask_pv, const double* __restrict__ partials,
+        int nrows_pv, int tiles_x_pv, unsigned char* __restrict__ preview) {
+    rectify_write_interpolate_body<3>(img, owner_bp, tag_bp, mask_bp, rows, cols, offset, gs, fixed, tiles_x, nb_t, inl, owner_pv, tag_pv, mask_pv, partials, nrows_pv, tiles_x_pv, preview);
+}
+
+__global__ __launch_bounds__(kBP) void rectify_write_interpolate_gray_kernel(const unsigned char* __restrict__ img, const unsigned* __restrict__ owner_bp,
+        unsigned tag_bp, unsigned mask_bp, int rows, int cols, int offset, unsigned char* __restrict__ gs, unsigned char* __restrict__ fixed, int tiles_x, int nb_t,
+        const double* __restrict__ inl, const unsigned* __restrict__ owner_pv, unsigned tag_pv, unsigned mask_pv, const double* __restrict__ partials,
+        int nrows_pv, int tiles_x_pv, unsigned char* __restrict__ preview) {
+    rectify_write_interpolate_body<1>(img, owner_bp, tag_bp, mask_bp, rows, cols, offset, gs, fixed, tiles_x, nb_t, inl, owner_pv, tag_pv, mask_pv, partials, nrows_pv, tiles_x_pv, preview);
 }
 
 // ---- main.cc:480-523 in three launches instead of five (rsdsfm_rectify_frame_dev) ----------------------------------------------------
@@ -477,7 +601,8 @@ __global__ __launch_bounds__(kBP) void rectify_write_interpolate_kernel(const un
 // -> global-shutter image) of two launches each, every one of them short enough for the launch floor to show: the two claim passes share
 // ONE launch (its first workgroups walk the back projection's tiles, the rest the inlier list) and so do the two write passes.  Same bodies,
 // same results; which workgroup does what depends on the block index alone.
-__global__ __launch_bounds__(kCB) void rectify_claim_kernel(const unsigned char* __restrict__ img, const double* __restrict__ depth_cm,
+template <int CH>
+__device__ __forceinline__ void rectify_claim_body(const unsigned char* __restrict__ img, const double* __restrict__ depth_cm,
                                                            const double* __restrict__ R, const double* __restrict__ t, double fx, double fy,
                                                            double cx, double cy, double fyp, int rows, int cols, int mode,
                                                            unsigned* __restrict__ owner_bp, unsigned tag_bp, float* __restrict__ c3d, int tiles_x,
@@ -485,21 +610,50 @@ __global__ __launch_bounds__(kCB) void rectify_claim_kernel(const unsigned char*
                                                            unsigned tag_pv, double* __restrict__ partials) {
     const int b = blockIdx.x;
     if (b < nb_bp)
-        back_project_claim_body(b % tiles_x, b / tiles_x, img, depth_cm, R, t, fx, fy, cx, cy, fyp, rows, cols, mode, owner_bp, tag_bp, c3d);
+        back_project_claim_body<CH>(b % tiles_x, b / tiles_x, img, depth_cm, R, t, fx, fy, cx, cy, fyp, rows, cols, mode, owner_bp, tag_bp, c3d);
     else
         preview_claim_minmax_body<kCB>(b - nb_bp, (int)gridDim.x - nb_bp, inl, m, fx, fy, cx, cy, rows, cols, owner_pv, tag_pv, partials);
 }
 
-__global__ __launch_bounds__(kBP) void rectify_write_kernel(const unsigned char* __restrict__ img, const unsigned* __restrict__ owner_bp, unsigned tag_bp,
+__global__ __launch_bounds__(kCB) void rectify_claim_kernel(const unsigned char* __restrict__ img, const double* __restrict__ depth_cm,
+        const double* __restrict__ R, const double* __restrict__ t, double fx, double fy, double cx, double cy, double fyp, int rows, int cols, int mode,
+        unsigned* __restrict__ owner_bp, unsigned tag_bp, float* __restrict__ c3d, int tiles_x, int nb_bp, const double* __restrict__ inl, int64_t m,
+        unsigned* __restrict__ owner_pv, unsigned tag_pv, double* __restrict__ partials) {
+    rectify_claim_body<3>(img, depth_cm, R, t, fx, fy, cx, cy, fyp, rows, cols, mode, owner_bp, tag_bp, c3d, tiles_x, nb_bp, inl, m, owner_pv, tag_pv, partials);
+}
+
+__global__ __launch_bounds__(kCB) void rectify_claim_gray_kernel(const unsigned char* __restrict__ img, const double* __restrict__ depth_cm,
+        const double* __restrict__ R, const double* __restrict__ t, double fx, double fy, double cx, double cy, double fyp, int rows, int cols, int mode,
+        unsigned* __restrict__ owner_bp, unsigned tag_bp, float* __restrict__ c3d, int tiles_x, int nb_bp, const double* __restrict__ inl, int64_t m,
+        unsigned* __restrict__ owner_pv, unsigned tag_pv, double* __restrict__ partials) {
+    rectify_claim_body<1>(img, depth_cm, R, t, fx, fy, cx, cy, fyp, rows, cols, mode, owner_bp, tag_bp, c3d, tiles_x, nb_bp, inl, m, owner_pv, tag_pv, partials);
+}
+
+template <int CH>
+__device__ __forceinline__ void rectify_write_body(const unsigned char* __restrict__ img, const unsigned* __restrict__ owner_bp, unsigned tag_bp,
                                                            unsigned mask_bp, int64_t npix, unsigned char* __restrict__ gs, int nb_w,
                                                            const double* __restrict__ inl, const unsigned* __restrict__ owner_pv, unsigned tag_pv,
                                                            unsigned mask_pv, const double* __restrict__ partials, int nrows_pv, int rows, int cols,
                                                            int tiles_x_pv, unsigned char* __restrict__ preview) {
     const int b = blockIdx.x;
     if (b < nb_w)
-        back_project_write_body(b, nb_w, img, owner_bp, tag_bp, mask_bp, npix, gs);
+        back_project_write_body<CH>(b, nb_w, img, owner_bp, tag_bp, mask_bp, npix, gs);
     else
         preview_write_body((b - nb_w) % tiles_x_pv, (b - nb_w) / tiles_x_pv, inl, owner_pv, tag_pv, mask_pv, partials, nrows_pv, rows, cols, preview);
+}
+
+__global__ __launch_bounds__(kBP) void rectify_write_kernel(const unsigned char* __restrict__ img, const unsigned* __restrict__ owner_bp, unsigned tag_bp,
+        unsigned mask_bp, int64_t npix, unsigned char* __restrict__ gs, int nb_w, const double* __restrict__ inl, const unsigned* __restrict__ owner_pv,
+        unsigned tag_pv, unsigned mask_pv, const double* __restrict__ partials, int nrows_pv, int rows, int cols, int tiles_x_pv,
+        unsigned char* __restrict__ preview) {
+    rectify_write_body<3>(img, owner_bp, tag_bp, mask_bp, npix, gs, nb_w, inl, owner_pv, tag_pv, mask_pv, partials, nrows_pv, rows, cols, tiles_x_pv, preview);
+}
+
+__global__ __launch_bounds__(kBP) void rectify_write_gray_kernel(const unsigned char* __restrict__ img, const unsigned* __restrict__ owner_bp, unsigned tag_bp,
+        unsigned mask_bp, int64_t npix, unsigned char* __restrict__ gs, int nb_w, const double* __restrict__ inl, const unsigned* __restrict__ owner_pv,
+        unsigned tag_pv, unsigned mask_pv, const double* __restrict__ partials, int nrows_pv, int rows, int cols, int tiles_x_pv,
+        unsigned char* __restrict__ preview) {
+    rectify_write_body<1>(img, owner_bp, tag_bp, mask_bp, npix, gs, nb_w, inl, owner_pv, tag_pv, mask_pv, partials, nrows_pv, rows, cols, tiles_x_pv, preview);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -577,11 +731,16 @@ int back_project_launch(Ctx* c, const unsigned char* d_img, const double* d_dept
     return RSDSFM_OK;
 }
 
-int interpolate_cracky_launch(Ctx* c, const unsigned char* d_in, int rows, int cols, int offset, unsigned char* d_out) {
-    hipLaunchKernelGGL(interpolate_cracky_kernel, dim3(stream_grid((int64_t)rows * cols, 4)), dim3(kBP), 0, c->stream, d_in, rows, cols,
-                       offset, d_out);
+template <int CH>
+static int interpolate_cracky_launch_ch(Ctx* c, const unsigned char* d_in, int rows, int cols, int offset, unsigned char* d_out) {
+    hipLaunchKernelGGL(CH == 3 ? interpolate_cracky_kernel : interpolate_cracky_gray_kernel, dim3(stream_grid((int64_t)rows * cols, 4)), dim3(kBP), 0,
+                       c->stream, d_in, rows, cols, offset, d_out);
     RSDSFM_HIP_CHECK(c, hipGetLastError());
     return RSDSFM_OK;
+}
+
+int interpolate_cracky_launch(Ctx* c, const unsigned char* d_in, int rows, int cols, int offset, unsigned char* d_out) {
+    return interpolate_cracky_launch_ch<3>(c, d_in, rows, cols, offset, d_out);
 }
 
 // d_partials: >= 2 * 1024 doubles
@@ -603,8 +762,10 @@ int depth_preview_launch(Ctx* c, const double* d_inl, int64_t m, double fx, doub
     return RSDSFM_OK;
 }
 
-// main.cc:480-523: 8-bit depth image + back projection + crack interpolation; d_partials: >= 2 * 1024 doubles
-int rectify_frame_launch(Ctx* c, const double* d_inl, int64_t m, const unsigned char* d_img, const double* d_depth_cm, const double* d_R,
+// main.cc:480-523: 8-bit depth image + back projection + crack interpolation; d_partials: >= 2 * 1024 doubles.  CH = 3: BGR images; CH = 1: gray
+// ones (d_img, d_gs, d_fixed rows x cols bytes) through the *_gray_kernel set -- same grids, same claim maps, same depth image and world points.
+template <int CH>
+static int rectify_frame_launch_ch(Ctx* c, const double* d_inl, int64_t m, const unsigned char* d_img, const double* d_depth_cm, const double* d_R,
                          const double* d_t, double fx, double fy, double cx, double cy, int rows, int cols, int mode, int q5_mode, int offset,
                          unsigned char* d_preview, unsigned char* d_gs, float* d_c3d, unsigned char* d_fixed, double* d_partials) {
     const int64_t npix = (int64_t)rows * cols;
@@ -617,22 +778,36 @@ int rectify_frame_launch(Ctx* c, const double* d_inl, int64_t m, const unsigned 
     const int tiles_x = (cols + kTX - 1) / kTX, tiles_y = (rows + kTY - 1) / kTY;
     const int nb_bp = tiles_x * tiles_y;
     const int zb = (int)std::min<int64_t>(1024, std::max<int64_t>(1, (m + kCB - 1) / kCB));
-    hipLaunchKernelGGL(rectify_claim_kernel, dim3(nb_bp + zb), dim3(kCB), 0, c->stream, d_img, d_depth_cm, d_R, d_t, fx, fy, cx, cy,
+    hipLaunchKernelGGL(CH == 3 ? rectify_claim_kernel : rectify_claim_gray_kernel, dim3(nb_bp + zb), dim3(kCB), 0, c->stream, d_img, d_depth_cm, d_R, d_t, fx, fy, cx, cy,
                        q5_mode == 0 ? fx : fy, rows, cols, mode, d_owner_bp, tag_bp, d_c3d, tiles_x, nb_bp, d_inl, m, d_owner_pv, tag_pv, d_partials);
     RSDSFM_HIP_CHECK(c, hipGetLastError());
     const int ptx = (cols + 31) / 32, pty = (rows + 31) / 32;
     if (offset <= kMaxHalo && (cols % 4) == 0) {  // two launches: the write pass forms the interpolated image from its own tile (+ halo)
         const int ttx = (cols + kWT - 1) / kWT, tty = (rows + kHT - 1) / kHT;
-        hipLaunchKernelGGL(rectify_write_interpolate_kernel, dim3(ttx * tty + ptx * pty), dim3(kBP), 0, c->stream, d_img, d_owner_bp, tag_bp, mask_bp, rows,
+        hipLaunchKernelGGL(CH == 3 ? rectify_write_interpolate_kernel : rectify_write_interpolate_gray_kernel, dim3(ttx * tty + ptx * pty), dim3(kBP), 0, c->stream, d_img, d_owner_bp, tag_bp, mask_bp, rows,
                            cols, offset, d_gs, d_fixed, ttx, ttx * tty, d_inl, d_owner_pv, tag_pv, mask_pv, d_partials, zb, ptx, d_preview);
         RSDSFM_HIP_CHECK(c, hipGetLastError());
         return RSDSFM_OK;
     }
     const int nb_w = stream_grid(npix, 4);
-    hipLaunchKernelGGL(rectify_write_kernel, dim3(nb_w + ptx * pty), dim3(kBP), 0, c->stream, d_img, d_owner_bp, tag_bp, mask_bp, npix, d_gs, nb_w,
+    hipLaunchKernelGGL(CH == 3 ? rectify_write_kernel : rectify_write_gray_kernel, dim3(nb_w + ptx * pty), dim3(kBP), 0, c->stream, d_img, d_owner_bp, tag_bp, mask_bp, npix, d_gs, nb_w,
                        d_inl, d_owner_pv, tag_pv, mask_pv, d_partials, zb, rows, cols, ptx, d_preview);
     RSDSFM_HIP_CHECK(c, hipGetLastError());
-    return interpolate_cracky_launch(c, d_gs, rows, cols, offset, d_fixed);
+    return interpolate_cracky_launch_ch<CH>(c, d_gs, rows, cols, offset, d_fixed);
+}
+
+int rectify_frame_launch(Ctx* c, const double* d_inl, int64_t m, const unsigned char* d_img, const double* d_depth_cm, const double* d_R,
+                         const double* d_t, double fx, double fy, double cx, double cy, int rows, int cols, int mode, int q5_mode, int offset,
+                         unsigned char* d_preview, unsigned char* d_gs, float* d_c3d, unsigned char* d_fixed, double* d_partials) {
+    return rectify_frame_launch_ch<3>(c, d_inl, m, d_img, d_depth_cm, d_R, d_t, fx, fy, cx, cy, rows, cols, mode, q5_mode, offset, d_preview, d_gs, d_c3d,
+                                      d_fixed, d_partials);
+}
+
+int rectify_gray_frame_launch(Ctx* c, const double* d_inl, int64_t m, const unsigned char* d_img, const double* d_depth_cm, const double* d_R,
+                              const double* d_t, double fx, double fy, double cx, double cy, int rows, int cols, int mode, int q5_mode, int offset,
+                              unsigned char* d_preview, unsigned char* d_gs, float* d_c3d, unsigned char* d_fixed, double* d_partials) {
+    return rectify_frame_launch_ch<1>(c, d_inl, m, d_img, d_depth_cm, d_R, d_t, fx, fy, cx, cy, rows, cols, mode, q5_mode, offset, d_preview, d_gs, d_c3d,
+                                      d_fixed, d_partials);
 }
 
 }  // namespace rsdsfm

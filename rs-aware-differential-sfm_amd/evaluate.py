@@ -98,7 +98,9 @@ def evaluate_real_run(solver, data_prefix, flow=None, camera="galaxy", gamma=0.9
     `frame2` array (flow_params: its parameters, None = OpenCV's defaults); that flow goes into the solve without leaving the device
     and is returned as out["flow"].  Runs the whole solve in ONE device-resident call, then the consumers (8-bit depth image, back
     projection, crack interpolation, point cloud) and writes what the reference writes (optical_flow.png too when the flow was
-    computed here, main.cc:386-392).  Defaults as in main.cc:304-311 (5 trials, tolerance 0.05, refinement on)."""
+    computed here, main.cc:386-392).  Defaults as in main.cc:304-311 (5 trials, tolerance 0.05, refinement on).  A 2-D (gray) frame 1 goes
+    through the one-channel rectifier (Solver.rectify_gray_frame_dev): gs_image / backprojection come back (rows, cols), equal to channel 0
+    of the run on the replicated BGR frame, and the point cloud takes the replicated gray as its colour."""
     import torch
 
     from . import BACKPROJECT_GS, BACKPROJECT_RS
@@ -143,8 +145,9 @@ def evaluate_real_run(solver, data_prefix, flow=None, camera="galaxy", gamma=0.9
                                    flow_threshold=flow_threshold, flow_index_mode=flow_index_mode, use_global_shutter_mode=use_global_shutter_mode)
         m = r["num_inliers"]
         # main.cc:480-523 -- 8-bit depth image, back projection, crack interpolation -- in ONE call of two launches
-        solver.rectify_frame_dev(r["d_inliers"], m, d_img.data_ptr(), d_map.data_ptr(), d_R.data_ptr(), d_t.data_ptr(), K, rows, cols, d_depth_est.data_ptr(),
-                                 d_gs.data_ptr(), d_back.data_ptr(), d_coords=d_coords.data_ptr(), mode=mode, offset=1)
+        rectify = solver.rectify_gray_frame_dev if image.ndim == 2 else solver.rectify_frame_dev
+        rectify(r["d_inliers"], m, d_img.data_ptr(), d_map.data_ptr(), d_R.data_ptr(), d_t.data_ptr(), K, rows, cols, d_depth_est.data_ptr(),
+                d_gs.data_ptr(), d_back.data_ptr(), d_coords=d_coords.data_ptr(), mode=mode, offset=1)
         solver.synchronize()
         depth_map = d_map.cpu().numpy().reshape(cols, rows).T.copy()  # the device map is column-major (Eigen MatrixXd)
         R_rel, t_rel = d_R.cpu().numpy().reshape(rows, 3, 3), d_t.cpu().numpy().reshape(rows, 3)
@@ -168,18 +171,18 @@ def _write_real_outputs(out_dir, image, flow, depth_est, backprojection, coords)
     formats.write_png(out_dir + "/MinimalDepth.png", depth_est)
     formats.write_png(out_dir + "/rs_image.png", image)
     formats.write_png(out_dir + "/backprojection.png", backprojection)
-    formats.write_ply(out_dir + "/point_cloud.ply", coords, image)
+    formats.write_ply(out_dir + "/point_cloud.ply", coords, image if image.ndim == 3 else np.repeat(image[:, :, None], 3, axis=2))
 
 
 def evaluate_real_sequence(solver, frames, camera="galaxy", gamma=0.95, out_dir=None, trials=5, seeds=None, tol=0.05, use_acceleration_mode=False,
                            use_refinement=True, use_global_shutter_mode=False, flow_threshold=1e-10, flow_index_mode=0, device=0, flow_params=None):
     """evaluate_real_run's real-world branch (main.cc:341-361, 364-531) for a clip: `frames` is <prefix>frame1.png ... frameN.png (the
-    prefix, or a list of paths), or the frames themselves (an (N, rows, cols[, 3]) uint8 array or a list of arrays).  The DeepFlow of
-    every consecutive pair runs once for the clip (Solver.deep_flow_seq_dev, batched); then, per pair p (frames p, p + 1), the solve
-    (seed seeds[p], default 1 as in evaluate_real_run) and the rectification on that pair's device flow -- solve_frame_dev and
-    rectify_frame_dev, since the rectifier reads the pair's device inlier list.  Returns one dict per pair with evaluate_real_run's keys
-    and "flow"; each is bit for bit evaluate_real_run(frames[p], None, frame2=frames[p + 1]).  With out_dir: evaluate_real_run's files
-    (optical_flow.png included) under out_dir/<pair>/, and out_dir/poses.csv (pair, v, w, k, inliers)."""
+    prefix, or a list of paths), or the frames themselves (an (N, rows, cols[, 3]) uint8 array or a list of arrays; 2-D frames are gray).
+    ONE call does the clip (Solver.rectify_video_dev): the batched DeepFlow of every consecutive pair, the pipelined solve of every pair p
+    (frames p, p + 1; seed seeds[p], default 1 as in evaluate_real_run) and, behind it on the pair's lane, the rectification of frame p.
+    Returns one dict per pair with evaluate_real_run's keys and "flow"; each is bit for bit evaluate_real_run(frames[p], None,
+    frame2=frames[p + 1]).  With out_dir: evaluate_real_run's files (optical_flow.png included) under out_dir/<pair>/, and
+    out_dir/poses.csv (pair, v, w, k, inliers)."""
     import torch
 
     from . import BACKPROJECT_GS, BACKPROJECT_RS
@@ -206,28 +209,25 @@ def evaluate_real_sequence(solver, frames, camera="galaxy", gamma=0.95, out_dir=
     with torch.cuda.device(dev):
         d_imgs = [torch.from_numpy(im).to(dev) for im in images]
         d_flows = [torch.empty((rows, cols, 2), dtype=torch.float64, device=dev) for _ in range(npairs)]
+        d_maps = [torch.empty(rows * cols, dtype=torch.float64, device=dev) for _ in range(npairs)]
+        d_Rs = [torch.empty(rows * 9, dtype=torch.float64, device=dev) for _ in range(npairs)]
+        d_ts = [torch.empty(rows * 3, dtype=torch.float64, device=dev) for _ in range(npairs)]
+        d_depth_ests = [torch.empty((rows, cols), dtype=torch.uint8, device=dev) for _ in range(npairs)]
+        d_gss = [torch.empty_like(d_imgs[0]) for _ in range(npairs)]
+        d_backs = [torch.empty_like(d_imgs[0]) for _ in range(npairs)]
+        d_coordss = [torch.empty((rows, cols, 3), dtype=torch.float32, device=dev) for _ in range(npairs)]
         torch.cuda.synchronize()
-        solver.deep_flow_seq_dev([d.data_ptr() for d in d_imgs], rows, cols, channels, [f.data_ptr() for f in d_flows], params=flow_params)
-        for p in range(npairs):
-            d_img, d_flow = d_imgs[p], d_flows[p]
-            d_map = torch.empty(rows * cols, dtype=torch.float64, device=dev)
-            d_R = torch.empty(rows * 9, dtype=torch.float64, device=dev)
-            d_t = torch.empty(rows * 3, dtype=torch.float64, device=dev)
-            d_depth_est = torch.empty((rows, cols), dtype=torch.uint8, device=dev)
-            d_gs, d_back = torch.empty_like(d_img), torch.empty_like(d_img)
-            d_coords = torch.empty((rows, cols, 3), dtype=torch.float32, device=dev)
-            torch.cuda.synchronize()
-            r = solver.solve_frame_dev(d_flow.data_ptr(), rows, cols, K, gamma, d_map.data_ptr(), d_R.data_ptr(), d_t.data_ptr(), trials=trials, tol=tol,
-                                       seed=seeds[p], use_acceleration_mode=use_acceleration_mode, use_refinement=use_refinement,
-                                       flow_threshold=flow_threshold, flow_index_mode=flow_index_mode, use_global_shutter_mode=use_global_shutter_mode)
-            m = r["num_inliers"]
-            solver.rectify_frame_dev(r["d_inliers"], m, d_img.data_ptr(), d_map.data_ptr(), d_R.data_ptr(), d_t.data_ptr(), K, rows, cols, d_depth_est.data_ptr(),
-                                     d_gs.data_ptr(), d_back.data_ptr(), d_coords=d_coords.data_ptr(), mode=mode, offset=1)
-            solver.synchronize()
-            outs.append(dict(n=r["n"], num_inliers=m, v=r["v"], w=r["w"], k=r["k"], flipped=r["flipped"], refine_summary=r["refine_summary"],
-                             depth_map=d_map.cpu().numpy().reshape(cols, rows).T.copy(), depth_est=d_depth_est.cpu().numpy(), gs_image=d_gs.cpu().numpy(),
-                             backprojection=d_back.cpu().numpy(), coords=d_coords.cpu().numpy(), R=d_R.cpu().numpy().reshape(rows, 3, 3),
-                             t=d_t.cpu().numpy().reshape(rows, 3), flow=d_flow.cpu().numpy()))
+        ptrs = lambda ts: [t.data_ptr() for t in ts]
+        res = solver.rectify_video_dev(ptrs(d_imgs), rows, cols, channels, K, gamma, ptrs(d_maps), ptrs(d_depth_ests), ptrs(d_gss), ptrs(d_backs),
+                                       d_coords=ptrs(d_coordss), seeds=seeds, d_flows=ptrs(d_flows), d_R=ptrs(d_Rs), d_t=ptrs(d_ts), flow_params=flow_params,
+                                       mode=mode, offset=1, trials=trials, tol=tol, use_acceleration_mode=use_acceleration_mode,
+                                       use_refinement=use_refinement, flow_threshold=flow_threshold, flow_index_mode=flow_index_mode,
+                                       use_global_shutter_mode=use_global_shutter_mode)  # (every output is complete when it returns)
+        for p, r in enumerate(res):
+            outs.append(dict(n=r["n"], num_inliers=r["num_inliers"], v=r["v"], w=r["w"], k=r["k"], flipped=r["flipped"], refine_summary=r["refine_summary"],
+                             depth_map=d_maps[p].cpu().numpy().reshape(cols, rows).T.copy(), depth_est=d_depth_ests[p].cpu().numpy(),
+                             gs_image=d_gss[p].cpu().numpy(), backprojection=d_backs[p].cpu().numpy(), coords=d_coordss[p].cpu().numpy(),
+                             R=d_Rs[p].cpu().numpy().reshape(rows, 3, 3), t=d_ts[p].cpu().numpy().reshape(rows, 3), flow=d_flows[p].cpu().numpy()))
     if out_dir:
         os.makedirs(out_dir, exist_ok=True)
         lines = ["pair,v_x,v_y,v_z,w_x,w_y,w_z,k,inliers"]
