@@ -1076,6 +1076,88 @@ for _name, _fn in list(vars(_RectifyVideoMixin).items()):
 
 
 # ---------------------------------------------------------------------------------------------------
+# the dense global-shutter frame: depth fill + backward warp (include/rsdsfm_rectify_dense.h)
+# ---------------------------------------------------------------------------------------------------
+RECTIFY_DENSE_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "rsdsfm_rectify_dense.h")
+
+
+def rectify_dense_declared_symbols():
+    """Names of every function include/rsdsfm_rectify_dense.h declares"""
+    import re
+
+    txt = open(RECTIFY_DENSE_HEADER_PATH).read()
+    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
+    return sorted(set(re.findall(r"\b(rsdsfm_[a-z0-9_]+)\s*\(", txt)))
+
+
+def rectify_dense_launches(rows, cols):
+    """kernel launches of one rectify_dense_frame_dev call at this size (rsdsfm_rectify_dense_launches; host only)"""
+    n = load_library().rsdsfm_rectify_dense_launches(C.c_int32(rows), C.c_int32(cols))
+    if n < 0:
+        raise RsdsfmError("rsdsfm_rectify_dense_launches failed (%d): rows and cols must be in [2, 16384]" % n)
+    return n
+
+
+class _RectifyDenseMixin:
+    def rectify_dense_frame_dev(self, d_img, channels, d_depth_map, d_R, d_t, K, rows, cols, d_dense, d_mask=None, d_filled=None, d_disp=None,
+                                mode=BACKPROJECT_RS, q5_mode=Q5_COMPAT, iterations=0):
+        """the hole-free, sub-pixel global-shutter frame (rsdsfm_rectify_dense_frame_dev): push-pull fill of the inverse depth, the splat's
+        chain per pixel as a displacement plane, and its fixed-point inverse sampled bilinearly.  d_img / d_dense rows x cols x channels
+        bytes; optional d_mask rows x cols bytes, d_filled rows x cols doubles (column-major, like d_depth_map), d_disp rows x cols x 2
+        floats; iterations 1..16, 0 = the default (3).  Enqueued on the context's stream."""
+        d = C.c_double
+        self._check(self.lib.rsdsfm_rectify_dense_frame_dev(self._ctx, _dp(d_img), C.c_int32(channels), _dp(d_depth_map), _dp(d_R), _dp(d_t), d(K[0]), d(K[1]),
+                                                            d(K[2]), d(K[3]), C.c_int32(rows), C.c_int32(cols), int(mode), int(q5_mode), C.c_int32(iterations),
+                                                            _dp(d_dense), _np0(d_mask), _np0(d_filled), _np0(d_disp)), "rsdsfm_rectify_dense_frame_dev")
+
+    def rectify_dense(self, image, depth_map, R, t, K, mode=BACKPROJECT_RS, q5_mode=Q5_COMPAT, iterations=0, device=0):
+        """host convenience around rectify_dense_frame_dev: image (rows, cols) or (rows, cols, 3) uint8, depth_map (rows, cols) (0 where
+        unknown), R (rows, 3, 3) / (rows, 9), t (rows, 3).  Returns (dense image, mask)."""
+        import torch
+
+        img = np.ascontiguousarray(image, dtype=np.uint8)
+        rows, cols = img.shape[:2]
+        dev = torch.device("cuda", device)
+        with torch.cuda.device(dev):
+            up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+            d_img, d_dm = up(img), up(np.asarray(depth_map, dtype=np.float64).T)  # column-major rows x cols
+            d_R, d_t = up(_f64(np.asarray(R).reshape(rows, 9))), up(_f64(t))
+            d_out, d_mask = torch.empty_like(d_img), torch.empty((rows, cols), dtype=torch.uint8, device=dev)
+            torch.cuda.synchronize()
+            self.rectify_dense_frame_dev(d_img.data_ptr(), 1 if img.ndim == 2 else img.shape[2], d_dm.data_ptr(), d_R.data_ptr(), d_t.data_ptr(), K, rows, cols,
+                                         d_out.data_ptr(), d_mask.data_ptr(), mode=mode, q5_mode=q5_mode, iterations=iterations)
+            self.synchronize()
+            return d_out.cpu().numpy(), d_mask.cpu().numpy()
+
+    def rectify_dense_video_dev(self, d_frames, rows, cols, channels, K, gamma, d_depth_maps, d_dense, d_masks=None, d_filled=None, seeds=None,
+                                d_flows=None, d_R=None, d_t=None, flow_params=None, mode=BACKPROJECT_RS, q5_mode=Q5_COMPAT, iterations=0, trials=50,
+                                tol=0.05, use_acceleration_mode=False, use_refinement=True, depth_mode=DEPTH_CERES_LM, k_sign_mode=K_COMPAT,
+                                flow_threshold=1e-10, flow_index_mode=FLOW_COMPAT_RANK, use_global_shutter_mode=False):
+        """solve_video_dev plus, per pair p and on that pair's lane, rectify_dense_frame_dev of frame p with pair p's depth map and pose
+        table, in ONE call (rsdsfm_rectify_dense_video_dev).  d_dense (and optionally d_masks, d_filled): F - 1 device buffers each.  All
+        outputs are complete on return.  Returns one dict per pair, as solve_video_dev."""
+        n = len(d_frames) - 1
+        prm = FrameParams(int(trials), int(use_acceleration_mode), int(use_refinement), int(depth_mode), int(k_sign_mode),
+                          int(flow_index_mode), int(use_global_shutter_mode), 0, float(tol), float(flow_threshold), 1)
+        res = (FrameResult * max(n, 1))()
+        sd = (C.c_uint64 * n)(*[int(s) for s in seeds]) if seeds is not None else None
+        arr = lambda a: _ptr_array(a) if a is not None else None
+        p = _flow_params(flow_params)
+        d = C.c_double
+        self._check(self.lib.rsdsfm_rectify_dense_video_dev(self._ctx, _ptr_array(d_frames), C.c_int32(len(d_frames)), C.c_int32(rows), C.c_int32(cols),
+                                                            C.c_int32(channels), d(K[0]), d(K[1]), d(K[2]), d(K[3]), d(gamma),
+                                                            C.byref(p) if p is not None else None, C.byref(prm), sd, arr(d_flows), _ptr_array(d_depth_maps),
+                                                            arr(d_R), arr(d_t), res, int(mode), int(q5_mode), C.c_int32(iterations), _ptr_array(d_dense),
+                                                            arr(d_masks), arr(d_filled)), "rsdsfm_rectify_dense_video_dev")
+        return [_frame_result_dict(r) for r in res[:n]]
+
+
+for _name, _fn in list(vars(_RectifyDenseMixin).items()):
+    if not _name.startswith("__"):
+        setattr(Solver, _name, _fn)
+
+
+# ---------------------------------------------------------------------------------------------------
 # accuracy metrics (SURVEY 8 f-4)
 # ---------------------------------------------------------------------------------------------------
 class ReprojectionStats(C.Structure):

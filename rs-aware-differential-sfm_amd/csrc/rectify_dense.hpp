@@ -1,0 +1,40 @@
+// rectify_dense.hpp -- the dense global-shutter rectifier (include/rsdsfm_rectify_dense.h): what rectify_dense_kernels.hip,
+// rectify_dense_host.hip and rectify_dense_video_host.hip share.
+#pragma once
+
+#include <stddef.h>
+#include <stdint.h>
+
+#include "rsdsfm_internal.hpp"
+
+namespace rsdsfm {
+
+// The context's (and so every lane's) workspace, Ctx::rectify_dense: the pull-push pyramid from level 1 up (level 0 is the depth map itself,
+// read in place) and the displacement plane of stage B.  Made on first use and again when the image size changes (rectify_dense_ws).
+struct DenseWs {
+    double* d_pyr = nullptr;  // levels 1 .. top, level after level, row-major
+    float2* d_disp = nullptr; // rows x cols
+    int rows = 0, cols = 0;
+};
+
+// geometry of the pyramid of a rows x cols map: level l (1 .. nl) has h[l - 1] x w[l - 1] cells at off[l - 1] doubles
+constexpr int kDenseMaxLevels = 16;  // 16384 -> 8192 = 2^13 -> ... -> 1: 14 levels
+struct DensePlan {
+    int nl = 0, small = 0;  // small: index of the first level of the single-workgroup launch (everything from it up fits its LDS)
+    int h[kDenseMaxLevels], w[kDenseMaxLevels];
+    size_t off[kDenseMaxLevels], total = 0;
+};
+DensePlan rectify_dense_plan(int rows, int cols);
+int rectify_dense_launch_count(int rows, int cols);  // kernel launches of one frame
+
+int rectify_dense_ws(Ctx* c, int rows, int cols, DenseWs** ws);  // rectify_dense_host.hip
+void rectify_dense_release(Ctx* c);
+
+// the launches of one frame on c->stream (arguments checked by the caller; iterations 1 .. 16)
+int rectify_dense_launch(Ctx* c, const DenseWs& ws, const unsigned char* d_img, int channels, const double* d_depth_cm, const double* d_R, const double* d_t,
+                         double fx, double fy, double cx, double cy, int rows, int cols, int mode, int q5_mode, int iterations, unsigned char* d_out,
+                         unsigned char* d_mask, double* d_filled_cm);
+// the argument checks both entry points share (everything but the context and the sizes of the clip)
+int rectify_dense_check(Ctx* c, int channels, int rows, int cols, int mode, int q5_mode, int iterations);
+
+}  // namespace rsdsfm

@@ -90,7 +90,7 @@ def evaluate_single_run(solver, task_dir, out_dir, trials=50, tol=0.05, seed=1, 
 
 def evaluate_real_run(solver, data_prefix, flow=None, camera="galaxy", gamma=0.95, out_dir=None, trials=5, tol=0.05, seed=1,
                       use_acceleration_mode=False, use_refinement=True, use_global_shutter_mode=False, flow_threshold=1e-10,
-                      flow_index_mode=0, device=0, frame2=None, flow_params=None):
+                      flow_index_mode=0, device=0, frame2=None, flow_params=None, dense=False):
     """The real-world branch of evaluateSingleRun (main.cc:341-361, 364-531; setupCameraReal main.cc:675-690): <data_prefix>frame1.png,
     one of the hard-coded phone calibrations (or a (f_x, f_y, c_x, c_y) tuple), gamma 0.95 -- and the optical flow from frame 1 to
     frame 2: passed in (an array, a .npy or a Middlebury .flo file, formats.load_flow), or, with flow=None, computed on the device
@@ -100,7 +100,9 @@ def evaluate_real_run(solver, data_prefix, flow=None, camera="galaxy", gamma=0.9
     projection, crack interpolation, point cloud) and writes what the reference writes (optical_flow.png too when the flow was
     computed here, main.cc:386-392).  Defaults as in main.cc:304-311 (5 trials, tolerance 0.05, refinement on).  A 2-D (gray) frame 1 goes
     through the one-channel rectifier (Solver.rectify_gray_frame_dev): gs_image / backprojection come back (rows, cols), equal to channel 0
-    of the run on the replicated BGR frame, and the point cloud takes the replicated gray as its colour."""
+    of the run on the replicated BGR frame, and the point cloud takes the replicated gray as its colour.  dense=True additionally
+    returns the hole-free global-shutter frame and its mask (Solver.rectify_dense_frame_dev: out["dense_image"], out["dense_mask"]) and, with
+    out_dir, writes rectified_dense.png and rectified_dense_mask.png (mask x 255); the default returns and writes exactly what it did."""
     import torch
 
     from . import BACKPROJECT_GS, BACKPROJECT_RS
@@ -148,6 +150,10 @@ def evaluate_real_run(solver, data_prefix, flow=None, camera="galaxy", gamma=0.9
         rectify = solver.rectify_gray_frame_dev if image.ndim == 2 else solver.rectify_frame_dev
         rectify(r["d_inliers"], m, d_img.data_ptr(), d_map.data_ptr(), d_R.data_ptr(), d_t.data_ptr(), K, rows, cols, d_depth_est.data_ptr(),
                 d_gs.data_ptr(), d_back.data_ptr(), d_coords=d_coords.data_ptr(), mode=mode, offset=1)
+        if dense:
+            d_dense, d_dmask = torch.empty_like(d_img), torch.empty((rows, cols), dtype=torch.uint8, device=dev)
+            solver.rectify_dense_frame_dev(d_img.data_ptr(), 1 if image.ndim == 2 else image.shape[2], d_map.data_ptr(), d_R.data_ptr(), d_t.data_ptr(), K,
+                                           rows, cols, d_dense.data_ptr(), d_dmask.data_ptr(), mode=mode)
         solver.synchronize()
         depth_map = d_map.cpu().numpy().reshape(cols, rows).T.copy()  # the device map is column-major (Eigen MatrixXd)
         R_rel, t_rel = d_R.cpu().numpy().reshape(rows, 3, 3), d_t.cpu().numpy().reshape(rows, 3)
@@ -158,9 +164,19 @@ def evaluate_real_run(solver, data_prefix, flow=None, camera="galaxy", gamma=0.9
                depth_map=depth_map, depth_est=depth_est, gs_image=gs, backprojection=backprojection, coords=coords, R=R_rel, t=t_rel)
     if image2 is not None:
         out["flow"] = flow
+    if dense:
+        out["dense_image"], out["dense_mask"] = d_dense.cpu().numpy(), d_dmask.cpu().numpy()
     if out_dir:
         _write_real_outputs(out_dir, image, flow if image2 is not None else None, depth_est, backprojection, coords)
+        if dense:
+            _write_dense_outputs(out_dir, out["dense_image"], out["dense_mask"])
     return out
+
+
+def _write_dense_outputs(out_dir, dense_image, dense_mask):
+    """the dense rectifier's two files beside _write_real_outputs'"""
+    formats.write_png(out_dir + "/rectified_dense.png", dense_image)
+    formats.write_png(out_dir + "/rectified_dense_mask.png", (dense_mask * 255).astype(np.uint8))
 
 
 def _write_real_outputs(out_dir, image, flow, depth_est, backprojection, coords):
@@ -175,14 +191,16 @@ def _write_real_outputs(out_dir, image, flow, depth_est, backprojection, coords)
 
 
 def evaluate_real_sequence(solver, frames, camera="galaxy", gamma=0.95, out_dir=None, trials=5, seeds=None, tol=0.05, use_acceleration_mode=False,
-                           use_refinement=True, use_global_shutter_mode=False, flow_threshold=1e-10, flow_index_mode=0, device=0, flow_params=None):
+                           use_refinement=True, use_global_shutter_mode=False, flow_threshold=1e-10, flow_index_mode=0, device=0, flow_params=None, dense=False):
     """evaluate_real_run's real-world branch (main.cc:341-361, 364-531) for a clip: `frames` is <prefix>frame1.png ... frameN.png (the
     prefix, or a list of paths), or the frames themselves (an (N, rows, cols[, 3]) uint8 array or a list of arrays; 2-D frames are gray).
     ONE call does the clip (Solver.rectify_video_dev): the batched DeepFlow of every consecutive pair, the pipelined solve of every pair p
     (frames p, p + 1; seed seeds[p], default 1 as in evaluate_real_run) and, behind it on the pair's lane, the rectification of frame p.
     Returns one dict per pair with evaluate_real_run's keys and "flow"; each is bit for bit evaluate_real_run(frames[p], None,
     frame2=frames[p + 1]).  With out_dir: evaluate_real_run's files (optical_flow.png included) under out_dir/<pair>/, and
-    out_dir/poses.csv (pair, v, w, k, inliers)."""
+    out_dir/poses.csv (pair, v, w, k, inliers).  dense=True: per pair also evaluate_real_run's dense_image / dense_mask (behind the clip call,
+    from the pair's depth map and pose table) and its two files rectified_dense.png / rectified_dense_mask.png; the default writes exactly
+    what it did."""
     import torch
 
     from . import BACKPROJECT_GS, BACKPROJECT_RS
@@ -228,11 +246,23 @@ def evaluate_real_sequence(solver, frames, camera="galaxy", gamma=0.95, out_dir=
                              depth_map=d_maps[p].cpu().numpy().reshape(cols, rows).T.copy(), depth_est=d_depth_ests[p].cpu().numpy(),
                              gs_image=d_gss[p].cpu().numpy(), backprojection=d_backs[p].cpu().numpy(), coords=d_coordss[p].cpu().numpy(),
                              R=d_Rs[p].cpu().numpy().reshape(rows, 3, 3), t=d_ts[p].cpu().numpy().reshape(rows, 3), flow=d_flows[p].cpu().numpy()))
+        if dense:  # every pair enqueued behind the clip call, one wait for all of them
+            d_denses = [torch.empty_like(d_imgs[0]) for _ in range(npairs)]
+            d_dmasks = [torch.empty((rows, cols), dtype=torch.uint8, device=dev) for _ in range(npairs)]
+            torch.cuda.synchronize()
+            for p in range(npairs):
+                solver.rectify_dense_frame_dev(d_imgs[p].data_ptr(), channels, d_maps[p].data_ptr(), d_Rs[p].data_ptr(), d_ts[p].data_ptr(), K, rows, cols,
+                                               d_denses[p].data_ptr(), d_dmasks[p].data_ptr(), mode=mode)
+            solver.synchronize()
+            for p in range(npairs):
+                outs[p]["dense_image"], outs[p]["dense_mask"] = d_denses[p].cpu().numpy(), d_dmasks[p].cpu().numpy()
     if out_dir:
         os.makedirs(out_dir, exist_ok=True)
         lines = ["pair,v_x,v_y,v_z,w_x,w_y,w_z,k,inliers"]
         for p, o in enumerate(outs):
             _write_real_outputs(os.path.join(out_dir, str(p)), images[p], o["flow"], o["depth_est"], o["backprojection"], o["coords"])
+            if dense:
+                _write_dense_outputs(os.path.join(out_dir, str(p)), o["dense_image"], o["dense_mask"])
             lines.append(",".join([str(p)] + ["%.17g" % x for x in list(o["v"]) + list(o["w"]) + [o["k"]]] + [str(o["num_inliers"])]))
         with open(os.path.join(out_dir, "poses.csv"), "w") as fh:
             fh.write("\n".join(lines) + "\n")
