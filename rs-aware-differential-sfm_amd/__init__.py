@@ -1158,6 +1158,130 @@ for _name, _fn in list(vars(_RectifyDenseMixin).items()):
 
 
 # ---------------------------------------------------------------------------------------------------
+# the forward-backward flow check: an occlusion mask that gates the solve (include/rsdsfm_flow_check.h)
+# ---------------------------------------------------------------------------------------------------
+FLOW_CHECK_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "rsdsfm_flow_check.h")
+
+
+class FlowCheckParams(C.Structure):
+    _fields_ = [("a1", C.c_double), ("a2", C.c_double)]
+
+
+def flow_check_declared_symbols():
+    """Names of every function include/rsdsfm_flow_check.h declares"""
+    import re
+
+    txt = open(FLOW_CHECK_HEADER_PATH).read()
+    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
+    return sorted(set(re.findall(r"\b(rsdsfm_[a-z0-9_]+)\s*\(", txt)))
+
+
+def flow_check_default_params():
+    """the check's defaults as a dict: a1 = 0.01, a2 = 0.5 (rsdsfm_flow_check_default_params)"""
+    p = FlowCheckParams()
+    if load_library().rsdsfm_flow_check_default_params(C.byref(p)) != OK:
+        raise RsdsfmError("rsdsfm_flow_check_default_params failed")
+    return dict(a1=p.a1, a2=p.a2)
+
+
+def _flow_check_params(a1, a2):
+    """(None, None) -> NULL (the defaults); otherwise a FlowCheckParams with the given values over the defaults"""
+    if a1 is None and a2 is None:
+        return None
+    d = flow_check_default_params()
+    return FlowCheckParams(float(d["a1"] if a1 is None else a1), float(d["a2"] if a2 is None else a2))
+
+
+class _FlowCheckMixin:
+    def flow_consistency_dev(self, d_fwd, d_bwd, rows, cols, d_mask, d_masked=None, d_resid=None, d_count=None, a1=None, a2=None):
+        """the forward-backward check on device fields (rsdsfm_flow_consistency_dev; tests/flow_check_spec_numpy.py): d_fwd / d_bwd
+        rows x cols x 2 doubles, d_mask rows x cols bytes (4-byte aligned); optional d_masked rows x cols x 2 doubles (may be d_fwd),
+        d_resid rows x cols doubles, d_count one int64.  One launch, enqueued on the context's stream."""
+        k = _flow_check_params(a1, a2)
+        self._check(self.lib.rsdsfm_flow_consistency_dev(self._ctx, _dp(d_fwd), _dp(d_bwd), C.c_int32(rows), C.c_int32(cols),
+                                                         C.byref(k) if k is not None else None, _dp(d_mask), _np0(d_masked), _np0(d_resid), _np0(d_count)),
+                    "rsdsfm_flow_consistency_dev")
+
+    def flow_consistency(self, fwd, bwd, a1=None, a2=None, device=0):
+        """host convenience around flow_consistency_dev: two (rows, cols, 2) float64 fields in, dict(mask (rows, cols) uint8, masked
+        (rows, cols, 2), resid (rows, cols), count) out"""
+        import torch
+
+        f, b = _f64(fwd), _f64(bwd)
+        if f.ndim != 3 or f.shape[2] != 2 or b.shape != f.shape:
+            raise ValueError("the two fields must have the same (rows, cols, 2) shape")
+        rows, cols = f.shape[:2]
+        dev = torch.device("cuda", device)
+        with torch.cuda.device(dev):
+            d_f, d_b = torch.from_numpy(f).to(dev), torch.from_numpy(b).to(dev)
+            d_mask = torch.empty((rows, cols), dtype=torch.uint8, device=dev)
+            d_masked, d_resid = torch.empty_like(d_f), torch.empty((rows, cols), dtype=torch.float64, device=dev)
+            d_count = torch.empty(1, dtype=torch.int64, device=dev)
+            torch.cuda.synchronize()
+            self.flow_consistency_dev(d_f.data_ptr(), d_b.data_ptr(), rows, cols, d_mask.data_ptr(), d_masked.data_ptr(), d_resid.data_ptr(),
+                                      d_count.data_ptr(), a1=a1, a2=a2)
+            self.synchronize()
+            return dict(mask=d_mask.cpu().numpy(), masked=d_masked.cpu().numpy(), resid=d_resid.cpu().numpy(), count=int(d_count.cpu()[0]))
+
+    def deep_flow_checked_dev(self, d_img1, d_img2, rows, cols, channels, d_flow, d_mask, d_bwd=None, d_count=None, params=None, a1=None, a2=None):
+        """DeepFlow both ways and the check (rsdsfm_deep_flow_checked_dev): d_flow receives the MASKED forward field (solve_frame_dev can
+        follow on the same stream), d_mask the mask, optionally d_bwd the backward field and d_count the number of consistent pixels"""
+        p, k = _flow_params(params), _flow_check_params(a1, a2)
+        self._check(self.lib.rsdsfm_deep_flow_checked_dev(self._ctx, _dp(d_img1), _dp(d_img2), C.c_int32(rows), C.c_int32(cols), C.c_int32(channels),
+                                                          C.byref(p) if p is not None else None, C.byref(k) if k is not None else None, _dp(d_flow),
+                                                          _np0(d_bwd), _dp(d_mask), _np0(d_count)), "rsdsfm_deep_flow_checked_dev")
+
+    def deep_flow_checked(self, img1, img2, params=None, a1=None, a2=None, device=0):
+        """host convenience around deep_flow_checked_dev: two uint8 images as deep_flow takes them -> dict(flow (rows, cols, 2): the
+        masked forward field, bwd (rows, cols, 2), mask (rows, cols) uint8, count)"""
+        import torch
+
+        a, b = np.ascontiguousarray(img1, dtype=np.uint8), np.ascontiguousarray(img2, dtype=np.uint8)
+        if a.shape != b.shape or a.ndim not in (2, 3):
+            raise ValueError("the two images must have the same (rows, cols[, channels]) shape")
+        rows, cols = a.shape[:2]
+        dev = torch.device("cuda", device)
+        with torch.cuda.device(dev):
+            d_a, d_b = torch.from_numpy(a).to(dev), torch.from_numpy(b).to(dev)
+            d_flow, d_bwd = (torch.empty((rows, cols, 2), dtype=torch.float64, device=dev) for _ in range(2))
+            d_mask, d_count = torch.empty((rows, cols), dtype=torch.uint8, device=dev), torch.empty(1, dtype=torch.int64, device=dev)
+            torch.cuda.synchronize()
+            self.deep_flow_checked_dev(d_a.data_ptr(), d_b.data_ptr(), rows, cols, 1 if a.ndim == 2 else a.shape[2], d_flow.data_ptr(), d_mask.data_ptr(),
+                                       d_bwd=d_bwd.data_ptr(), d_count=d_count.data_ptr(), params=params, a1=a1, a2=a2)
+            self.synchronize()
+            return dict(flow=d_flow.cpu().numpy(), bwd=d_bwd.cpu().numpy(), mask=d_mask.cpu().numpy(), count=int(d_count.cpu()[0]))
+
+    def solve_video_checked_dev(self, d_frames, rows, cols, channels, K, gamma, d_depth_maps, d_masks, seeds=None, d_flows=None, d_bwd_flows=None,
+                                d_R=None, d_t=None, flow_params=None, a1=None, a2=None, trials=50, tol=0.05, use_acceleration_mode=False,
+                                use_refinement=True, depth_mode=DEPTH_CERES_LM, k_sign_mode=K_COMPAT, flow_threshold=1e-10,
+                                flow_index_mode=FLOW_COMPAT_RANK, use_global_shutter_mode=False):
+        """solve_video_dev with the forward-backward check between every batch's flow and its solve (rsdsfm_solve_video_checked_dev):
+        d_masks: F - 1 device masks; d_flows (or the library's ring) hold the MASKED fields; d_bwd_flows: F - 1 buffers for the backward
+        fields (None: a ring owned by the library).  Returns one dict per pair, as solve_video_dev, each with "consistent" (the pair's
+        count of consistent pixels)."""
+        n = len(d_frames) - 1
+        prm = FrameParams(int(trials), int(use_acceleration_mode), int(use_refinement), int(depth_mode), int(k_sign_mode),
+                          int(flow_index_mode), int(use_global_shutter_mode), 0, float(tol), float(flow_threshold), 1)
+        res = (FrameResult * max(n, 1))()
+        cnt = (C.c_int64 * max(n, 1))()
+        sd = (C.c_uint64 * n)(*[int(s) for s in seeds]) if seeds is not None else None
+        arr = lambda a: _ptr_array(a) if a is not None else None
+        p, k = _flow_params(flow_params), _flow_check_params(a1, a2)
+        d = C.c_double
+        self._check(self.lib.rsdsfm_solve_video_checked_dev(self._ctx, _ptr_array(d_frames), C.c_int32(len(d_frames)), C.c_int32(rows), C.c_int32(cols),
+                                                            C.c_int32(channels), d(K[0]), d(K[1]), d(K[2]), d(K[3]), d(gamma),
+                                                            C.byref(p) if p is not None else None, C.byref(prm), sd, arr(d_flows), _ptr_array(d_depth_maps),
+                                                            arr(d_R), arr(d_t), res, C.byref(k) if k is not None else None, _ptr_array(d_masks),
+                                                            arr(d_bwd_flows), cnt), "rsdsfm_solve_video_checked_dev")
+        return [dict(_frame_result_dict(r), consistent=int(cnt[i])) for i, r in enumerate(res[:n])]
+
+
+for _name, _fn in list(vars(_FlowCheckMixin).items()):
+    if not _name.startswith("__"):
+        setattr(Solver, _name, _fn)
+
+
+# ---------------------------------------------------------------------------------------------------
 # accuracy metrics (SURVEY 8 f-4)
 # ---------------------------------------------------------------------------------------------------
 class ReprojectionStats(C.Structure):

@@ -181,6 +181,7 @@ void rsdsfm_destroy(rsdsfm_ctx* ctx) {
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     frame_release(c);  // (the sequence lanes, the second stream and its events)
     flow_release(c);
+    flow_check_release(c);
     rectify_dense_release(c);
     if (c->d_partials) (void)hipFree(c->d_partials);
     if (c->d_tickets) (void)hipFree(c->d_tickets);

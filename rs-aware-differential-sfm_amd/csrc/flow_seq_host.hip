@@ -21,7 +21,7 @@ constexpr int kFlowBatchDefault = 8;  // profiles/flow_seq_time.txt
 // the context's clip workspace, ready for this size and pyramid at the batch size of rsdsfm_set_flow_batch
 int clip_ws(Ctx* c, int rows, int cols, const rsdsfm_flow_params& p, FlowWs** w) {
     *w = flow_ws(c, false);
-    return ensure_flow_ws(c, *w, c->flow_batch > 0 ? c->flow_batch : kFlowBatchDefault, rows, cols, p);
+    return ensure_flow_ws(c, *w, video_batch_size(c), rows, cols, p);
 }
 
 // the ring of B fields behind rsdsfm_solve_video_dev's d_flows_or_null = NULL (freed with the workspace)
@@ -48,10 +48,12 @@ int check_clip(Ctx* c, int nframes, int rows, int cols, int channels, const rsds
 
 }  // namespace
 
+int video_batch_size(const Ctx* c) { return c->flow_batch > 0 ? c->flow_batch : kFlowBatchDefault; }
+
 int solve_video_run(rsdsfm_ctx* ctx, const uint8_t* const* d_frames, int32_t nframes, int32_t rows, int32_t cols, int32_t channels, double fx, double fy,
                     double cx, double cy, double gamma, const rsdsfm_flow_params* flow_params_or_null, const rsdsfm_frame_params* params,
                     const uint64_t* seeds, double* const* d_flows_or_null, double* const* d_depth_maps, double* const* d_R_or_null,
-                    double* const* d_t_or_null, rsdsfm_frame_result* results, const PairHook* hook, bool lane_tables) {
+                    double* const* d_t_or_null, rsdsfm_frame_result* results, const PairHook* hook, bool lane_tables, const BatchHook* pre_solve) {
     Ctx* c = &ctx->c;
     rsdsfm_flow_params p;
     int rc = check_clip(c, nframes, rows, cols, channels, flow_params_or_null, &p);
@@ -75,6 +77,7 @@ int solve_video_run(rsdsfm_ctx* ctx, const uint8_t* const* d_frames, int32_t nfr
         for (int q = 0; q < n; ++q)
             fl[q] = d_flows_or_null ? d_flows_or_null[g0 + q] : reinterpret_cast<double*>(static_cast<char*>(w->d_ring) + (size_t)q * w->ring_stride);
         rc = flow_enqueue(c, w, d_frames + g0, n, channels, p, fl);
+        if (rc == RSDSFM_OK && pre_solve) rc = (*pre_solve)(w, p, g0, n, fl);
         if (rc != RSDSFM_OK) return rc;
         const int L = sequence_lane_count(c, n);
         for (int q = 0; q < n; ++q) {

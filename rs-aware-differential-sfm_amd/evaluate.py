@@ -90,7 +90,7 @@ def evaluate_single_run(solver, task_dir, out_dir, trials=50, tol=0.05, seed=1, 
 
 def evaluate_real_run(solver, data_prefix, flow=None, camera="galaxy", gamma=0.95, out_dir=None, trials=5, tol=0.05, seed=1,
                       use_acceleration_mode=False, use_refinement=True, use_global_shutter_mode=False, flow_threshold=1e-10,
-                      flow_index_mode=0, device=0, frame2=None, flow_params=None, dense=False):
+                      flow_index_mode=0, device=0, frame2=None, flow_params=None, dense=False, check_flow=False):
     """The real-world branch of evaluateSingleRun (main.cc:341-361, 364-531; setupCameraReal main.cc:675-690): <data_prefix>frame1.png,
     one of the hard-coded phone calibrations (or a (f_x, f_y, c_x, c_y) tuple), gamma 0.95 -- and the optical flow from frame 1 to
     frame 2: passed in (an array, a .npy or a Middlebury .flo file, formats.load_flow), or, with flow=None, computed on the device
@@ -102,11 +102,16 @@ def evaluate_real_run(solver, data_prefix, flow=None, camera="galaxy", gamma=0.9
     through the one-channel rectifier (Solver.rectify_gray_frame_dev): gs_image / backprojection come back (rows, cols), equal to channel 0
     of the run on the replicated BGR frame, and the point cloud takes the replicated gray as its colour.  dense=True additionally
     returns the hole-free global-shutter frame and its mask (Solver.rectify_dense_frame_dev: out["dense_image"], out["dense_mask"]) and, with
-    out_dir, writes rectified_dense.png and rectified_dense_mask.png (mask x 255); the default returns and writes exactly what it did."""
+    out_dir, writes rectified_dense.png and rectified_dense_mask.png (mask x 255); the default returns and writes exactly what it did.
+    check_flow=True (only with a flow computed here: ValueError with a passed-in flow) puts the forward-backward check between the flow and
+    the solve (Solver.deep_flow_checked_dev, include/rsdsfm_flow_check.h): the solve sees the MASKED field, which is also out["flow"];
+    out["flow_mask"] is the mask (rows, cols) uint8, out["flow_consistent"] its count, and with out_dir flow_mask.png (mask x 255) is written."""
     import torch
 
     from . import BACKPROJECT_GS, BACKPROJECT_RS
 
+    if check_flow and flow is not None:
+        raise ValueError("check_flow=True needs the flow to be computed here (flow=None): the check reads the backward field too")
     image = formats.read_png(data_prefix + "frame1.png") if isinstance(data_prefix, str) else np.ascontiguousarray(data_prefix, dtype=np.uint8)
     K = formats.CAMERA_INTRINSICS[camera] if isinstance(camera, str) else tuple(float(x) for x in camera)
     rows, cols = image.shape[:2]
@@ -139,7 +144,12 @@ def evaluate_real_run(solver, data_prefix, flow=None, camera="galaxy", gamma=0.9
         d_gs, d_back = torch.empty_like(d_img), torch.empty_like(d_img)
         d_coords = torch.empty((rows, cols, 3), dtype=torch.float32, device=dev)
         torch.cuda.synchronize()
-        if image2 is not None:  # the flow is computed on the solver's stream, ahead of the solve that reads it
+        if check_flow:  # both fields and the check on the solver's stream, ahead of the solve that reads the masked field
+            d_fmask, d_fcount = torch.empty((rows, cols), dtype=torch.uint8, device=dev), torch.empty(1, dtype=torch.int64, device=dev)
+            torch.cuda.synchronize()
+            solver.deep_flow_checked_dev(d_img.data_ptr(), d_img2.data_ptr(), rows, cols, 1 if image.ndim == 2 else image.shape[2], d_flow.data_ptr(),
+                                         d_fmask.data_ptr(), d_count=d_fcount.data_ptr(), params=flow_params)
+        elif image2 is not None:  # the flow is computed on the solver's stream, ahead of the solve that reads it
             solver.deep_flow_dev(d_img.data_ptr(), d_img2.data_ptr(), rows, cols, 1 if image.ndim == 2 else image.shape[2], d_flow.data_ptr(),
                                  params=flow_params)
         r = solver.solve_frame_dev(d_flow.data_ptr(), rows, cols, K, gamma, d_map.data_ptr(), d_R.data_ptr(), d_t.data_ptr(), trials=trials, tol=tol,
@@ -166,10 +176,14 @@ def evaluate_real_run(solver, data_prefix, flow=None, camera="galaxy", gamma=0.9
         out["flow"] = flow
     if dense:
         out["dense_image"], out["dense_mask"] = d_dense.cpu().numpy(), d_dmask.cpu().numpy()
+    if check_flow:
+        out["flow_mask"], out["flow_consistent"] = d_fmask.cpu().numpy(), int(d_fcount.cpu()[0])
     if out_dir:
         _write_real_outputs(out_dir, image, flow if image2 is not None else None, depth_est, backprojection, coords)
         if dense:
             _write_dense_outputs(out_dir, out["dense_image"], out["dense_mask"])
+        if check_flow:
+            formats.write_png(out_dir + "/flow_mask.png", (out["flow_mask"] * 255).astype(np.uint8))
     return out
 
 
@@ -191,16 +205,19 @@ def _write_real_outputs(out_dir, image, flow, depth_est, backprojection, coords)
 
 
 def evaluate_real_sequence(solver, frames, camera="galaxy", gamma=0.95, out_dir=None, trials=5, seeds=None, tol=0.05, use_acceleration_mode=False,
-                           use_refinement=True, use_global_shutter_mode=False, flow_threshold=1e-10, flow_index_mode=0, device=0, flow_params=None, dense=False):
+                           use_refinement=True, use_global_shutter_mode=False, flow_threshold=1e-10, flow_index_mode=0, device=0, flow_params=None, dense=False,
+                           check_flow=False):
     """evaluate_real_run's real-world branch (main.cc:341-361, 364-531) for a clip: `frames` is <prefix>frame1.png ... frameN.png (the
     prefix, or a list of paths), or the frames themselves (an (N, rows, cols[, 3]) uint8 array or a list of arrays; 2-D frames are gray).
-    ONE call does the clip (Solver.rectify_video_dev): the batched DeepFlow of every consecutive pair, the pipelined solve of every pair p
+    By default ONE call does the clip (Solver.rectify_video_dev): the batched DeepFlow of every consecutive pair, the pipelined solve of every pair p
     (frames p, p + 1; seed seeds[p], default 1 as in evaluate_real_run) and, behind it on the pair's lane, the rectification of frame p.
     Returns one dict per pair with evaluate_real_run's keys and "flow"; each is bit for bit evaluate_real_run(frames[p], None,
     frame2=frames[p + 1]).  With out_dir: evaluate_real_run's files (optical_flow.png included) under out_dir/<pair>/, and
     out_dir/poses.csv (pair, v, w, k, inliers).  dense=True: per pair also evaluate_real_run's dense_image / dense_mask (behind the clip call,
     from the pair's depth map and pose table) and its two files rectified_dense.png / rectified_dense_mask.png; the default writes exactly
-    what it did."""
+    what it did.  check_flow=True: every pair goes through evaluate_real_run's checked chain instead (Solver.deep_flow_checked_dev, the solve on
+    the masked field, the rectifier; pair after pair on the solver's stream, one wait at the end) -- per pair evaluate_real_run(...,
+    check_flow=True) bit for bit, with its flow_mask / flow_consistent and flow_mask.png."""
     import torch
 
     from . import BACKPROJECT_GS, BACKPROJECT_RS
@@ -236,16 +253,35 @@ def evaluate_real_sequence(solver, frames, camera="galaxy", gamma=0.95, out_dir=
         d_coordss = [torch.empty((rows, cols, 3), dtype=torch.float32, device=dev) for _ in range(npairs)]
         torch.cuda.synchronize()
         ptrs = lambda ts: [t.data_ptr() for t in ts]
-        res = solver.rectify_video_dev(ptrs(d_imgs), rows, cols, channels, K, gamma, ptrs(d_maps), ptrs(d_depth_ests), ptrs(d_gss), ptrs(d_backs),
-                                       d_coords=ptrs(d_coordss), seeds=seeds, d_flows=ptrs(d_flows), d_R=ptrs(d_Rs), d_t=ptrs(d_ts), flow_params=flow_params,
-                                       mode=mode, offset=1, trials=trials, tol=tol, use_acceleration_mode=use_acceleration_mode,
-                                       use_refinement=use_refinement, flow_threshold=flow_threshold, flow_index_mode=flow_index_mode,
-                                       use_global_shutter_mode=use_global_shutter_mode)  # (every output is complete when it returns)
+        if check_flow:
+            d_fmasks = [torch.empty((rows, cols), dtype=torch.uint8, device=dev) for _ in range(npairs)]
+            d_fcounts = torch.empty(npairs, dtype=torch.int64, device=dev)
+            torch.cuda.synchronize()
+            rectify = solver.rectify_gray_frame_dev if channels == 1 else solver.rectify_frame_dev
+            res = []
+            for p in range(npairs):  # (a pair's rectifier is enqueued in front of the next pair's solve, which overwrites the inlier list)
+                solver.deep_flow_checked_dev(d_imgs[p].data_ptr(), d_imgs[p + 1].data_ptr(), rows, cols, channels, d_flows[p].data_ptr(),
+                                             d_fmasks[p].data_ptr(), d_count=d_fcounts[p:].data_ptr(), params=flow_params)
+                r = solver.solve_frame_dev(d_flows[p].data_ptr(), rows, cols, K, gamma, d_maps[p].data_ptr(), d_Rs[p].data_ptr(), d_ts[p].data_ptr(),
+                                           trials=trials, tol=tol, seed=seeds[p], use_acceleration_mode=use_acceleration_mode, use_refinement=use_refinement,
+                                           flow_threshold=flow_threshold, flow_index_mode=flow_index_mode, use_global_shutter_mode=use_global_shutter_mode)
+                rectify(r["d_inliers"], r["num_inliers"], d_imgs[p].data_ptr(), d_maps[p].data_ptr(), d_Rs[p].data_ptr(), d_ts[p].data_ptr(), K, rows, cols,
+                        d_depth_ests[p].data_ptr(), d_gss[p].data_ptr(), d_backs[p].data_ptr(), d_coords=d_coordss[p].data_ptr(), mode=mode, offset=1)
+                res.append(r)
+            solver.synchronize()
+        else:
+            res = solver.rectify_video_dev(ptrs(d_imgs), rows, cols, channels, K, gamma, ptrs(d_maps), ptrs(d_depth_ests), ptrs(d_gss), ptrs(d_backs),
+                                           d_coords=ptrs(d_coordss), seeds=seeds, d_flows=ptrs(d_flows), d_R=ptrs(d_Rs), d_t=ptrs(d_ts), flow_params=flow_params,
+                                           mode=mode, offset=1, trials=trials, tol=tol, use_acceleration_mode=use_acceleration_mode,
+                                           use_refinement=use_refinement, flow_threshold=flow_threshold, flow_index_mode=flow_index_mode,
+                                           use_global_shutter_mode=use_global_shutter_mode)  # (every output is complete when it returns)
         for p, r in enumerate(res):
             outs.append(dict(n=r["n"], num_inliers=r["num_inliers"], v=r["v"], w=r["w"], k=r["k"], flipped=r["flipped"], refine_summary=r["refine_summary"],
                              depth_map=d_maps[p].cpu().numpy().reshape(cols, rows).T.copy(), depth_est=d_depth_ests[p].cpu().numpy(),
                              gs_image=d_gss[p].cpu().numpy(), backprojection=d_backs[p].cpu().numpy(), coords=d_coordss[p].cpu().numpy(),
                              R=d_Rs[p].cpu().numpy().reshape(rows, 3, 3), t=d_ts[p].cpu().numpy().reshape(rows, 3), flow=d_flows[p].cpu().numpy()))
+            if check_flow:
+                outs[p]["flow_mask"], outs[p]["flow_consistent"] = d_fmasks[p].cpu().numpy(), int(d_fcounts[p].cpu())
         if dense:  # every pair enqueued behind the clip call, one wait for all of them
             d_denses = [torch.empty_like(d_imgs[0]) for _ in range(npairs)]
             d_dmasks = [torch.empty((rows, cols), dtype=torch.uint8, device=dev) for _ in range(npairs)]
@@ -263,6 +299,8 @@ def evaluate_real_sequence(solver, frames, camera="galaxy", gamma=0.95, out_dir=
             _write_real_outputs(os.path.join(out_dir, str(p)), images[p], o["flow"], o["depth_est"], o["backprojection"], o["coords"])
             if dense:
                 _write_dense_outputs(os.path.join(out_dir, str(p)), o["dense_image"], o["dense_mask"])
+            if check_flow:
+                formats.write_png(os.path.join(out_dir, str(p), "flow_mask.png"), (o["flow_mask"] * 255).astype(np.uint8))
             lines.append(",".join([str(p)] + ["%.17g" % x for x in list(o["v"]) + list(o["w"]) + [o["k"]]] + [str(o["num_inliers"])]))
         with open(os.path.join(out_dir, "poses.csv"), "w") as fh:
             fh.write("\n".join(lines) + "\n")

@@ -198,6 +198,31 @@ def render_pair(rows, cols, K, v, w, k=0.0, gamma=0.8, seed=0x5EED0000):
     return img1, img2, np.ascontiguousarray(flow), mask
 
 
+def render_occluded_pair(rows, cols, K, v, w, k=0.0, gamma=0.8, seed=0x5EED0000, block=None, block_motion=(6, 0)):
+    """render_pair's two frames with a textured rectangle pasted over both, moved by its own integer translation between them: a pair
+    with a real occlusion, for testing the forward-backward flow check.  block = (y0, x0, h, w) is the rectangle in frame 1 (None: a
+    quarter of each side, starting at a third), block_motion = (dx, dy) its translation; it must lie inside both frames.  Its texture is
+    _texture in the block's own coordinates under another seed.  Returns (img1, img2, occluded, block_plane): occluded marks the
+    frame-1 BACKGROUND pixels p whose landing point p + F(p) (F = render_pair's model flow), rounded to the nearest pixel, the block
+    covers in frame 2 -- no flow can match them; block_plane marks the block's pixels in frame 1."""
+    img1, img2, flow, _ = render_pair(rows, cols, K, v, w, k, gamma, seed)
+    y0, x0, h, bw = (rows // 3, cols // 3, rows // 4, cols // 4) if block is None else (int(b) for b in block)
+    dx, dy = (int(m) for m in block_motion)
+    if min(y0, x0, y0 + dy, x0 + dx) < 0 or h < 1 or bw < 1 or max(y0, y0 + dy) + h > rows or max(x0, x0 + dx) + bw > cols:
+        raise ValueError("the block must lie inside both frames")
+    by, bx = np.mgrid[0:h, 0:bw].astype(np.float64)
+    tex = np.rint(_texture(3.0 * bx, 3.0 * by, (seed ^ 0xB10C) & 0xFFFFFFFF)[..., ::-1]).astype(np.uint8)
+    img1, img2 = img1.copy(), img2.copy()
+    img1[y0:y0 + h, x0:x0 + bw] = tex
+    img2[y0 + dy:y0 + dy + h, x0 + dx:x0 + dx + bw] = tex
+    block_plane = np.zeros((rows, cols), dtype=bool)
+    block_plane[y0:y0 + h, x0:x0 + bw] = True
+    yy, xx = np.mgrid[0:rows, 0:cols]
+    lx, ly = np.rint(xx + flow[..., 0]), np.rint(yy + flow[..., 1])
+    covered = (lx >= x0 + dx) & (lx < x0 + dx + bw) & (ly >= y0 + dy) & (ly < y0 + dy + h)
+    return img1, img2, covered & ~block_plane, block_plane
+
+
 def render_sequence(nframes, rows, cols, K, v, w, k=0.0, gamma=0.8, seed=0x5EED0000):
     """nframes 8-bit BGR frames of render_pair's texture under a constant motion: frame j at pixel q shows T(inv^j(q)), where inv is
     render_pair's fixed-point inverse of the model flow F (p + F(p) = q), applied j times from the pixel grid.  Every consecutive pair
