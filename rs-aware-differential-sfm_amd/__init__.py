@@ -1282,6 +1282,166 @@ for _name, _fn in list(vars(_FlowCheckMixin).items()):
 
 
 # ---------------------------------------------------------------------------------------------------
+# a clip's trajectory: the links between consecutive pairs, the chain of scales and poses, the clip's points (include/rsdsfm_trajectory.h)
+# ---------------------------------------------------------------------------------------------------
+TRAJECTORY_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "rsdsfm_trajectory.h")
+
+
+class LinkParams(C.Structure):
+    _fields_ = [("tol", C.c_double), ("min_links", C.c_int32), ("radix_bits", C.c_int32), ("struct_bytes", C.c_int32), ("reserved", C.c_int32)]
+
+
+class LinkRecord(C.Structure):
+    _fields_ = [("n", C.c_int64), ("ratio", C.c_double), ("agree", C.c_int64), ("valid", C.c_int32), ("reserved", C.c_int32)]
+
+    def as_dict(self):
+        return dict(n=int(self.n), ratio=float(self.ratio), agree=int(self.agree), valid=bool(self.valid))
+
+
+def trajectory_declared_symbols():
+    """Names of every function include/rsdsfm_trajectory.h declares"""
+    import re
+
+    txt = open(TRAJECTORY_HEADER_PATH).read()
+    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
+    return sorted(set(re.findall(r"\b(rsdsfm_[a-z0-9_]+)\s*\(", txt)))
+
+
+def link_default_params():
+    """the link's defaults as a dict: tol = 0.1, min_links = 16, radix_bits = 0 (rsdsfm_link_params_init)"""
+    p = LinkParams()
+    if load_library().rsdsfm_link_params_init(C.byref(p)) != OK:
+        raise RsdsfmError("rsdsfm_link_params_init failed")
+    return dict(tol=p.tol, min_links=p.min_links, radix_bits=p.radix_bits)
+
+
+def _link_params(tol, min_links, radix_bits):
+    """(None, None, None) -> NULL (the defaults); otherwise a LinkParams with the given values over the defaults"""
+    if tol is None and min_links is None and radix_bits is None:
+        return None
+    p = LinkParams()
+    if load_library().rsdsfm_link_params_init(C.byref(p)) != OK:
+        raise RsdsfmError("rsdsfm_link_params_init failed")
+    if tol is not None:
+        p.tol = float(tol)
+    if min_links is not None:
+        p.min_links = int(min_links)
+    if radix_bits is not None:
+        p.radix_bits = int(radix_bits)
+    return p
+
+
+def _records_in(records):
+    rec = (LinkRecord * max(len(records), 1))()
+    for i, r in enumerate(records):
+        rec[i].n, rec[i].ratio, rec[i].agree, rec[i].valid = int(r["n"]), float(r["ratio"]), int(r["agree"]), int(bool(r["valid"]))
+    return rec
+
+
+def chain_clip(records, vs, ws, gamma):
+    """the clip's scales and poses from its links and motions (rsdsfm_chain_clip; host arithmetic, no GPU).  records: the F - 2 link records
+    (dicts with n, ratio, agree, valid); vs / ws: (F - 1, 3).  -> dict(scales (F - 1), A (F, 3, 3), c (F, 3), broken (F - 2) uint8):
+    S_0 = 1, S_{q+1} = S_q / ratio_q (carried over a link that is not valid: broken[q] = 1); frame q's first scanline in frame 0's
+    coordinates is X_0 = A_q X_q + c_q."""
+    v, w = _f64(vs).reshape(-1, 3), _f64(ws).reshape(-1, 3)
+    n = v.shape[0]
+    if w.shape[0] != n or len(records) != max(n - 1, 0):
+        raise ValueError("F - 1 motions need F - 2 link records")
+    scales, A, c = np.empty(max(n, 1)), np.empty((n + 1, 3, 3)), np.empty((n + 1, 3))
+    broken = np.zeros(max(n - 1, 1), dtype=np.uint8)
+    rc = load_library().rsdsfm_chain_clip(_records_in(records), _p(v), _p(w), C.c_int32(n), C.c_double(gamma), _p(scales), _p(A), _p(c), _p(broken))
+    if rc != OK:
+        raise RsdsfmError("rsdsfm_chain_clip failed (%d): at least one pair, gamma finite and > 0" % rc)
+    return dict(scales=scales[:n], A=A, c=c, broken=broken[:max(n - 1, 0)])
+
+
+class _TrajectoryMixin:
+    def link_pairs_dev(self, d_fields, d_depth_maps, vs, ws, ks, rows, cols, K, gamma, global_shutter=False, d_planes=None, tol=None, min_links=None,
+                       radix_bits=None):
+        """the links of n solved pairs on the device (rsdsfm_link_pairs_dev; tests/link_spec_numpy.py): d_fields / d_depth_maps: n device
+        pointers each (the last field is not read: 0 will do), vs / ws (n, 3) and ks (n): the pairs' final motions; d_planes: n - 1
+        buffers of rows x cols uint64 for the ratio planes (None: the context's workspace).  Returns the n - 1 records as dicts
+        (n, ratio, agree, valid).  Waits for the one copy of the scalars."""
+        n = len(d_depth_maps)
+        v, w, k = _f64(vs).reshape(-1, 3), _f64(ws).reshape(-1, 3), _f64(ks).reshape(-1)
+        if not (v.shape[0] == w.shape[0] == k.shape[0] == n) or len(d_fields) not in (n - 1, n):
+            raise ValueError("n depth maps need n motions and n (or n - 1) fields")
+        p = _link_params(tol, min_links, radix_bits)
+        rec = (LinkRecord * max(n - 1, 1))()
+        d = C.c_double
+        self._check(self.lib.rsdsfm_link_pairs_dev(self._ctx, _ptr_array(list(d_fields) + [0] * (n - len(d_fields))), _ptr_array(d_depth_maps), _p(v), _p(w),
+                                                   _p(k), C.c_int32(n), C.c_int32(rows), C.c_int32(cols), d(K[0]), d(K[1]), d(K[2]), d(K[3]), d(gamma),
+                                                   C.c_int32(int(bool(global_shutter))), C.byref(p) if p is not None else None,
+                                                   _ptr_array(d_planes) if d_planes is not None else None, rec), "rsdsfm_link_pairs_dev")
+        return [r.as_dict() for r in rec[:max(n - 1, 0)]]
+
+    def link_pairs(self, fields, depth_maps, vs, ws, ks, K, gamma, global_shutter=False, tol=None, min_links=None, radix_bits=None, want_planes=False,
+                   device=0):
+        """host convenience around link_pairs_dev: fields (n or n - 1, rows, cols, 2) float64, depth_maps (n, rows, cols) float64 (row-major
+        here; uploaded column-major, as the solve writes them) -> the n - 1 records, each with "plane" ((rows, cols) uint64) when
+        want_planes"""
+        import torch
+
+        maps = [_f64(m) for m in depth_maps]
+        rows, cols = maps[0].shape
+        dev = torch.device("cuda", device)
+        with torch.cuda.device(dev):
+            d_f = [torch.from_numpy(_f64(f)).to(dev) for f in fields]
+            d_z = [torch.from_numpy(np.ascontiguousarray(m.T)).to(dev) for m in maps]
+            d_pl = [torch.zeros((rows, cols), dtype=torch.int64, device=dev) for _ in range(len(maps) - 1)] if want_planes else None
+            torch.cuda.synchronize()
+            rec = self.link_pairs_dev([t.data_ptr() for t in d_f], [t.data_ptr() for t in d_z], vs, ws, ks, rows, cols, K, gamma, global_shutter,
+                                      [t.data_ptr() for t in d_pl] if want_planes else None, tol, min_links, radix_bits)
+            if want_planes:
+                for r, t in zip(rec, d_pl):
+                    r["plane"] = t.cpu().numpy().view(np.uint64)
+        return rec
+
+    def clip_points_dev(self, d_points_in, d_points_out, rows, cols, scales, A, c):
+        """the clip's points (rsdsfm_clip_points_dev): pair q's world points (rows x cols x 3 floats, in frame q's coordinates) ->
+        A_q (S_q X) + c_q, float64 rounded once to float; d_points_out[q] may be d_points_in[q]; (0, 0, 0) stays (0, 0, 0).  Enqueued on
+        the context's stream."""
+        n = len(d_points_in)
+        s, a, cc = _f64(scales).reshape(-1), _f64(A).reshape(-1, 9), _f64(c).reshape(-1, 3)
+        if len(d_points_out) != n or s.shape[0] < n or a.shape[0] < n or cc.shape[0] < n:
+            raise ValueError("every pair needs an output, a scale and a pose")
+        self._check(self.lib.rsdsfm_clip_points_dev(self._ctx, _ptr_array(d_points_in), _ptr_array(d_points_out), C.c_int32(n), C.c_int32(rows),
+                                                    C.c_int32(cols), _p(s), _p(a), _p(cc)), "rsdsfm_clip_points_dev")
+
+    def solve_video_linked_dev(self, d_frames, rows, cols, channels, K, gamma, d_depth_maps, d_flows, d_masks=None, seeds=None, d_R=None, d_t=None,
+                               d_points=None, flow_params=None, a1=None, a2=None, link_tol=None, min_links=None, radix_bits=None, trials=50, tol=0.05,
+                               use_acceleration_mode=False, use_refinement=True, depth_mode=DEPTH_CERES_LM, k_sign_mode=K_COMPAT, flow_threshold=1e-10,
+                               flow_index_mode=FLOW_COMPAT_RANK, use_global_shutter_mode=False):
+        """solve_video_dev (solve_video_checked_dev when d_masks is passed), then the links, the chain and -- when d_points is passed (F - 1
+        buffers holding each pair's world points) -- the clip's points in place (rsdsfm_solve_video_linked_dev).  d_flows is required.
+        Returns dict(pairs: one dict per pair as solve_video_dev, links: the F - 2 records, scales, A, c, broken)."""
+        n = len(d_frames) - 1
+        prm = FrameParams(int(trials), int(use_acceleration_mode), int(use_refinement), int(depth_mode), int(k_sign_mode),
+                          int(flow_index_mode), int(use_global_shutter_mode), 0, float(tol), float(flow_threshold), 1)
+        res = (FrameResult * max(n, 1))()
+        rec = (LinkRecord * max(n - 1, 1))()
+        scales, A, c = np.empty(max(n, 1)), np.empty((max(n, 1) + 1, 3, 3)), np.empty((max(n, 1) + 1, 3))
+        broken = np.zeros(max(n - 1, 1), dtype=np.uint8)
+        sd = (C.c_uint64 * n)(*[int(s) for s in seeds]) if seeds is not None else None
+        arr = lambda a: _ptr_array(a) if a is not None else None
+        p, k, lp = _flow_params(flow_params), _flow_check_params(a1, a2), _link_params(link_tol, min_links, radix_bits)
+        d = C.c_double
+        self._check(self.lib.rsdsfm_solve_video_linked_dev(self._ctx, _ptr_array(d_frames), C.c_int32(len(d_frames)), C.c_int32(rows), C.c_int32(cols),
+                                                           C.c_int32(channels), d(K[0]), d(K[1]), d(K[2]), d(K[3]), d(gamma),
+                                                           C.byref(p) if p is not None else None, C.byref(prm), sd, arr(d_flows), _ptr_array(d_depth_maps),
+                                                           arr(d_R), arr(d_t), res, C.byref(k) if k is not None else None, arr(d_masks),
+                                                           C.byref(lp) if lp is not None else None, rec, _p(scales), _p(A), _p(c), _p(broken), arr(d_points)),
+                    "rsdsfm_solve_video_linked_dev")
+        return dict(pairs=[_frame_result_dict(r) for r in res[:n]], links=[r.as_dict() for r in rec[:max(n - 1, 0)]], scales=scales[:n], A=A[:n + 1],
+                    c=c[:n + 1], broken=broken[:max(n - 1, 0)])
+
+
+for _name, _fn in list(vars(_TrajectoryMixin).items()):
+    if not _name.startswith("__"):
+        setattr(Solver, _name, _fn)
+
+
+# ---------------------------------------------------------------------------------------------------
 # accuracy metrics (SURVEY 8 f-4)
 # ---------------------------------------------------------------------------------------------------
 class ReprojectionStats(C.Structure):

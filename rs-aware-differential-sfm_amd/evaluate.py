@@ -206,7 +206,7 @@ def _write_real_outputs(out_dir, image, flow, depth_est, backprojection, coords)
 
 def evaluate_real_sequence(solver, frames, camera="galaxy", gamma=0.95, out_dir=None, trials=5, seeds=None, tol=0.05, use_acceleration_mode=False,
                            use_refinement=True, use_global_shutter_mode=False, flow_threshold=1e-10, flow_index_mode=0, device=0, flow_params=None, dense=False,
-                           check_flow=False):
+                           check_flow=False, trajectory=False, link_tol=None, min_links=None):
     """evaluate_real_run's real-world branch (main.cc:341-361, 364-531) for a clip: `frames` is <prefix>frame1.png ... frameN.png (the
     prefix, or a list of paths), or the frames themselves (an (N, rows, cols[, 3]) uint8 array or a list of arrays; 2-D frames are gray).
     By default ONE call does the clip (Solver.rectify_video_dev): the batched DeepFlow of every consecutive pair, the pipelined solve of every pair p
@@ -217,7 +217,12 @@ def evaluate_real_sequence(solver, frames, camera="galaxy", gamma=0.95, out_dir=
     from the pair's depth map and pose table) and its two files rectified_dense.png / rectified_dense_mask.png; the default writes exactly
     what it did.  check_flow=True: every pair goes through evaluate_real_run's checked chain instead (Solver.deep_flow_checked_dev, the solve on
     the masked field, the rectifier; pair after pair on the solver's stream, one wait at the end) -- per pair evaluate_real_run(...,
-    check_flow=True) bit for bit, with its flow_mask / flow_consistent and flow_mask.png."""
+    check_flow=True) bit for bit, with its flow_mask / flow_consistent and flow_mask.png.
+    trajectory=True: behind the clip, the links between consecutive pairs (Solver.link_pairs_dev on the pairs' fields, depth maps and motions), the
+    chain (chain_clip) and the clip's points (Solver.clip_points_dev on the pairs' world points); the return value is then
+    dict(pairs: the list above, links, scales, A, c, broken, points: per pair (rows, cols, 3) float32 in frame 0's coordinates and unit), and
+    out_dir receives trajectory.csv (frame, position, rotation row by row, the scale of the pair that starts there) and clip.ply: the points
+    of every pair's pixels that carry a depth, with frame p's colours, written by formats.write_ply."""
     import torch
 
     from . import BACKPROJECT_GS, BACKPROJECT_RS
@@ -292,6 +297,18 @@ def evaluate_real_sequence(solver, frames, camera="galaxy", gamma=0.95, out_dir=
             solver.synchronize()
             for p in range(npairs):
                 outs[p]["dense_image"], outs[p]["dense_mask"] = d_denses[p].cpu().numpy(), d_dmasks[p].cpu().numpy()
+        if trajectory:
+            from . import chain_clip
+
+            d_clip = [torch.empty_like(t) for t in d_coordss]
+            torch.cuda.synchronize()
+            vs, ws, ks = [o["v"] for o in outs], [o["w"] for o in outs], [o["k"] for o in outs]
+            links = solver.link_pairs_dev(ptrs(d_flows), ptrs(d_maps), vs, ws, ks, rows, cols, K, gamma, use_global_shutter_mode, tol=link_tol,
+                                          min_links=min_links) if npairs >= 2 else []
+            traj = chain_clip(links, vs, ws, gamma)
+            solver.clip_points_dev(ptrs(d_coordss), ptrs(d_clip), rows, cols, traj["scales"], traj["A"], traj["c"])
+            solver.synchronize()
+            traj.update(links=links, points=[t.cpu().numpy() for t in d_clip])
     if out_dir:
         os.makedirs(out_dir, exist_ok=True)
         lines = ["pair,v_x,v_y,v_z,w_x,w_y,w_z,k,inliers"]
@@ -304,6 +321,19 @@ def evaluate_real_sequence(solver, frames, camera="galaxy", gamma=0.95, out_dir=
             lines.append(",".join([str(p)] + ["%.17g" % x for x in list(o["v"]) + list(o["w"]) + [o["k"]]] + [str(o["num_inliers"])]))
         with open(os.path.join(out_dir, "poses.csv"), "w") as fh:
             fh.write("\n".join(lines) + "\n")
+        if trajectory:
+            rows_ = ["frame,c_x,c_y,c_z," + ",".join("a_%d%d" % (i, j) for i in range(3) for j in range(3)) + ",scale"]
+            for f in range(npairs + 1):
+                rows_.append(",".join([str(f)] + ["%.17g" % x for x in list(traj["c"][f]) + list(traj["A"][f].reshape(-1))] +
+                                      ["%.17g" % traj["scales"][f] if f < npairs else ""]))
+            with open(os.path.join(out_dir, "trajectory.csv"), "w") as fh:
+                fh.write("\n".join(rows_) + "\n")
+            keep = [o["depth_map"] > 0 for o in outs]
+            colour = [im if im.ndim == 3 else np.repeat(im[..., None], 3, axis=2) for im in images[:npairs]]
+            formats.write_ply(os.path.join(out_dir, "clip.ply"), np.concatenate([traj["points"][p][keep[p]] for p in range(npairs)]),
+                              np.concatenate([colour[p][keep[p]] for p in range(npairs)]))
+    if trajectory:
+        return dict(traj, pairs=outs)
     return outs
 
 
