@@ -1411,10 +1411,15 @@ class _TrajectoryMixin:
     def solve_video_linked_dev(self, d_frames, rows, cols, channels, K, gamma, d_depth_maps, d_flows, d_masks=None, seeds=None, d_R=None, d_t=None,
                                d_points=None, flow_params=None, a1=None, a2=None, link_tol=None, min_links=None, radix_bits=None, trials=50, tol=0.05,
                                use_acceleration_mode=False, use_refinement=True, depth_mode=DEPTH_CERES_LM, k_sign_mode=K_COMPAT, flow_threshold=1e-10,
-                               flow_index_mode=FLOW_COMPAT_RANK, use_global_shutter_mode=False):
+                               flow_index_mode=FLOW_COMPAT_RANK, use_global_shutter_mode=False, d_fused=None, d_flags=None, fuse_tol=None):
         """solve_video_dev (solve_video_checked_dev when d_masks is passed), then the links, the chain and -- when d_points is passed (F - 1
         buffers holding each pair's world points) -- the clip's points in place (rsdsfm_solve_video_linked_dev).  d_flows is required.
-        Returns dict(pairs: one dict per pair as solve_video_dev, links: the F - 2 records, scales, A, c, broken)."""
+        Returns dict(pairs: one dict per pair as solve_video_dev, links: the F - 2 records, scales, A, c, broken).
+        d_fused (F - 1 buffers of rows x cols doubles; d_flags: as many of rows x cols bytes, optional): behind the links, the fusion of
+        the pairs' depth maps (fuse_depths_dev on the call's own fields, maps, motions and records); the result then carries "fuse", the
+        F - 1 fusion records.  Without d_fused the call is unchanged."""
+        if d_fused is None and d_flags is not None:
+            raise ValueError("d_flags needs d_fused")
         n = len(d_frames) - 1
         prm = FrameParams(int(trials), int(use_acceleration_mode), int(use_refinement), int(depth_mode), int(k_sign_mode),
                           int(flow_index_mode), int(use_global_shutter_mode), 0, float(tol), float(flow_threshold), 1)
@@ -1432,11 +1437,121 @@ class _TrajectoryMixin:
                                                            arr(d_R), arr(d_t), res, C.byref(k) if k is not None else None, arr(d_masks),
                                                            C.byref(lp) if lp is not None else None, rec, _p(scales), _p(A), _p(c), _p(broken), arr(d_points)),
                     "rsdsfm_solve_video_linked_dev")
-        return dict(pairs=[_frame_result_dict(r) for r in res[:n]], links=[r.as_dict() for r in rec[:max(n - 1, 0)]], scales=scales[:n], A=A[:n + 1],
-                    c=c[:n + 1], broken=broken[:max(n - 1, 0)])
+        out = dict(pairs=[_frame_result_dict(r) for r in res[:n]], links=[r.as_dict() for r in rec[:max(n - 1, 0)]], scales=scales[:n], A=A[:n + 1],
+                   c=c[:n + 1], broken=broken[:max(n - 1, 0)])
+        if d_fused is not None:
+            out["fuse"] = self.fuse_depths_dev(d_flows, d_depth_maps, [r["v"] for r in out["pairs"]], [r["w"] for r in out["pairs"]],
+                                               [r["k"] for r in out["pairs"]], rows, cols, K, gamma, out["links"], d_fused, use_global_shutter_mode,
+                                               d_flags, None, fuse_tol)
+        return out
 
 
 for _name, _fn in list(vars(_TrajectoryMixin).items()):
+    if not _name.startswith("__"):
+        setattr(Solver, _name, _fn)
+
+
+# ---------------------------------------------------------------------------------------------------
+# the fusion of a clip's depth maps: every pair's holes filled from what its neighbours measured there (include/rsdsfm_fuse.h)
+# ---------------------------------------------------------------------------------------------------
+FUSE_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "rsdsfm_fuse.h")
+FUSE_OWN, FUSE_PREV, FUSE_NEXT, FUSE_PREV_AGREES, FUSE_NEXT_AGREES = 1, 2, 4, 8, 16
+
+
+class FuseParams(C.Structure):
+    _fields_ = [("tol", C.c_double), ("struct_bytes", C.c_int32), ("reserved", C.c_int32)]
+
+
+class FuseRecord(C.Structure):
+    _fields_ = [("own", C.c_int64), ("filled_prev", C.c_int64), ("filled_next", C.c_int64), ("confirmed", C.c_int64), ("contradicted", C.c_int64),
+                ("left", C.c_int64)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+def fuse_declared_symbols():
+    """Names of every function include/rsdsfm_fuse.h declares"""
+    import re
+
+    txt = open(FUSE_HEADER_PATH).read()
+    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
+    return sorted(set(re.findall(r"\b(rsdsfm_[a-z0-9_]+)\s*\(", txt)))
+
+
+def fuse_default_params():
+    """the fusion's defaults as a dict: tol = 0.1 (rsdsfm_fuse_params_init)"""
+    p = FuseParams()
+    if load_library().rsdsfm_fuse_params_init(C.byref(p)) != OK:
+        raise RsdsfmError("rsdsfm_fuse_params_init failed")
+    return dict(tol=p.tol)
+
+
+def _fuse_records_in(records):
+    """link records as the fusion reads them: ratio and valid (n and agree are carried along where present)"""
+    rec = (LinkRecord * max(len(records), 1))()
+    for i, r in enumerate(records):
+        rec[i].n, rec[i].ratio, rec[i].agree, rec[i].valid = int(r.get("n", 0)), float(r["ratio"]), int(r.get("agree", 0)), int(bool(r["valid"]))
+    return rec
+
+
+class _FuseMixin:
+    def fuse_depths_dev(self, d_fields, d_depth_maps, vs, ws, ks, rows, cols, K, gamma, records, d_fused, global_shutter=False, d_flags=None, d_planes=None,
+                        tol=None, want_records=True):
+        """the fused depth maps of n solved pairs on the device (rsdsfm_fuse_depths_dev; tests/fuse_spec_numpy.py): d_fields / d_depth_maps
+        / vs / ws / ks as link_pairs_dev's, records: its n - 1 link records (dicts); d_fused: n buffers of rows x cols doubles
+        (column-major, none of them an input); d_flags: n buffers of rows x cols bytes (None: no flags); d_planes: n - 1 buffers of
+        rows x cols uint64 for the splat planes (None: the context's workspace).  Returns the n records as dicts (own, filled_prev,
+        filled_next, confirmed, contradicted, left) and waits for their one copy; want_records=False only enqueues and returns None."""
+        n = len(d_depth_maps)
+        v, w, k = _f64(vs).reshape(-1, 3), _f64(ws).reshape(-1, 3), _f64(ks).reshape(-1)
+        if not (v.shape[0] == w.shape[0] == k.shape[0] == n) or len(d_fields) not in (n - 1, n) or len(records) != max(n - 1, 0) or len(d_fused) != n:
+            raise ValueError("n depth maps need n motions, n (or n - 1) fields, n - 1 link records and n outputs")
+        p = None
+        if tol is not None:
+            p = FuseParams()
+            if self.lib.rsdsfm_fuse_params_init(C.byref(p)) != OK:
+                raise RsdsfmError("rsdsfm_fuse_params_init failed")
+            p.tol = float(tol)
+        rec = (FuseRecord * max(n, 1))() if want_records else None
+        d = C.c_double
+        self._check(self.lib.rsdsfm_fuse_depths_dev(self._ctx, _ptr_array(list(d_fields) + [0] * (n - len(d_fields))), _ptr_array(d_depth_maps), _p(v), _p(w),
+                                                    _p(k), C.c_int32(n), C.c_int32(rows), C.c_int32(cols), d(K[0]), d(K[1]), d(K[2]), d(K[3]), d(gamma),
+                                                    C.c_int32(int(bool(global_shutter))), _fuse_records_in(records) if n > 1 else None,
+                                                    C.byref(p) if p is not None else None, _ptr_array(d_fused),
+                                                    _ptr_array(d_flags) if d_flags is not None else None,
+                                                    _ptr_array(d_planes) if d_planes is not None else None, rec), "rsdsfm_fuse_depths_dev")
+        return [r.as_dict() for r in rec[:n]] if want_records else None
+
+    def fuse_depths(self, fields, depth_maps, vs, ws, ks, records, K, gamma, global_shutter=False, tol=None, want_flags=False, want_planes=False, device=0):
+        """host convenience around fuse_depths_dev: fields (n or n - 1, rows, cols, 2) float64, depth_maps (n, rows, cols) float64
+        (row-major here; uploaded column-major, as the solve writes them), records: the n - 1 link records -> dict(fused: n (rows, cols)
+        float64, records: n dicts, flags: n (rows, cols) uint8 when want_flags, planes: n - 1 (rows, cols) uint64 when want_planes)"""
+        import torch
+
+        maps = [_f64(m) for m in depth_maps]
+        n = len(maps)
+        rows, cols = maps[0].shape
+        dev = torch.device("cuda", device)
+        ptrs = lambda ts: [t.data_ptr() for t in ts]
+        with torch.cuda.device(dev):
+            d_f = [torch.from_numpy(_f64(f)).to(dev) for f in fields]
+            d_z = [torch.from_numpy(np.ascontiguousarray(m.T)).to(dev) for m in maps]
+            d_out = [torch.empty((cols, rows), dtype=torch.float64, device=dev) for _ in range(n)]
+            d_fl = [torch.empty((rows, cols), dtype=torch.uint8, device=dev) for _ in range(n)] if want_flags else None
+            d_pl = [torch.empty((rows, cols), dtype=torch.int64, device=dev) for _ in range(n - 1)] if want_planes else None
+            torch.cuda.synchronize()
+            rec = self.fuse_depths_dev(ptrs(d_f), ptrs(d_z), vs, ws, ks, rows, cols, K, gamma, records, ptrs(d_out), global_shutter,
+                                       ptrs(d_fl) if want_flags else None, ptrs(d_pl) if want_planes else None, tol)
+            out = dict(fused=[t.cpu().numpy().T.copy() for t in d_out], records=rec)
+            if want_flags:
+                out["flags"] = [t.cpu().numpy() for t in d_fl]
+            if want_planes:
+                out["planes"] = [t.cpu().numpy().view(np.uint64) for t in d_pl]
+        return out
+
+
+for _name, _fn in list(vars(_FuseMixin).items()):
     if not _name.startswith("__"):
         setattr(Solver, _name, _fn)
 

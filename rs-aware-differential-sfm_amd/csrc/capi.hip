@@ -184,6 +184,7 @@ void rsdsfm_destroy(rsdsfm_ctx* ctx) {
     flow_check_release(c);
     rectify_dense_release(c);
     link_release(c);
+    fuse_release(c);
     if (c->d_partials) (void)hipFree(c->d_partials);
     if (c->d_tickets) (void)hipFree(c->d_tickets);
     if (c->d_lm) (void)hipFree(c->d_lm);

@@ -206,7 +206,7 @@ def _write_real_outputs(out_dir, image, flow, depth_est, backprojection, coords)
 
 def evaluate_real_sequence(solver, frames, camera="galaxy", gamma=0.95, out_dir=None, trials=5, seeds=None, tol=0.05, use_acceleration_mode=False,
                            use_refinement=True, use_global_shutter_mode=False, flow_threshold=1e-10, flow_index_mode=0, device=0, flow_params=None, dense=False,
-                           check_flow=False, trajectory=False, link_tol=None, min_links=None):
+                           check_flow=False, trajectory=False, link_tol=None, min_links=None, fuse=False, fuse_tol=None):
     """evaluate_real_run's real-world branch (main.cc:341-361, 364-531) for a clip: `frames` is <prefix>frame1.png ... frameN.png (the
     prefix, or a list of paths), or the frames themselves (an (N, rows, cols[, 3]) uint8 array or a list of arrays; 2-D frames are gray).
     By default ONE call does the clip (Solver.rectify_video_dev): the batched DeepFlow of every consecutive pair, the pipelined solve of every pair p
@@ -222,7 +222,14 @@ def evaluate_real_sequence(solver, frames, camera="galaxy", gamma=0.95, out_dir=
     chain (chain_clip) and the clip's points (Solver.clip_points_dev on the pairs' world points); the return value is then
     dict(pairs: the list above, links, scales, A, c, broken, points: per pair (rows, cols, 3) float32 in frame 0's coordinates and unit), and
     out_dir receives trajectory.csv (frame, position, rotation row by row, the scale of the pair that starts there) and clip.ply: the points
-    of every pair's pixels that carry a depth, with frame p's colours, written by formats.write_ply."""
+    of every pair's pixels that carry a depth, with frame p's colours, written by formats.write_ply.
+    fuse=True (needs trajectory=True: ValueError otherwise): behind the links, the fusion of the pairs' depth maps (Solver.fuse_depths_dev:
+    every pair's holes filled from what its neighbours measured there); each pair's dict gets fused_depth ((rows, cols) float64, 0 = no value),
+    fuse_flags ((rows, cols) uint8: FUSE_OWN ...) and fuse_record; with dense=True the dense rectifier reads the FUSED map; out_dir receives
+    depth_fused.png per pair (Solver.depth_preview's 8-bit depth image of the fused map) and fusion.csv (pair and the six counts).  The clip's
+    points and clip.ply keep selecting by the solve's map.  The default writes exactly what it did."""
+    if fuse and not trajectory:
+        raise ValueError("fuse=True needs trajectory=True: the fusion converts between the pairs' units with the links' ratios")
     import torch
 
     from . import BACKPROJECT_GS, BACKPROJECT_RS
@@ -287,16 +294,19 @@ def evaluate_real_sequence(solver, frames, camera="galaxy", gamma=0.95, out_dir=
                              R=d_Rs[p].cpu().numpy().reshape(rows, 3, 3), t=d_ts[p].cpu().numpy().reshape(rows, 3), flow=d_flows[p].cpu().numpy()))
             if check_flow:
                 outs[p]["flow_mask"], outs[p]["flow_consistent"] = d_fmasks[p].cpu().numpy(), int(d_fcounts[p].cpu())
-        if dense:  # every pair enqueued behind the clip call, one wait for all of them
+        def run_dense(d_depths):  # every pair enqueued behind the clip call, one wait for all of them
             d_denses = [torch.empty_like(d_imgs[0]) for _ in range(npairs)]
             d_dmasks = [torch.empty((rows, cols), dtype=torch.uint8, device=dev) for _ in range(npairs)]
             torch.cuda.synchronize()
             for p in range(npairs):
-                solver.rectify_dense_frame_dev(d_imgs[p].data_ptr(), channels, d_maps[p].data_ptr(), d_Rs[p].data_ptr(), d_ts[p].data_ptr(), K, rows, cols,
+                solver.rectify_dense_frame_dev(d_imgs[p].data_ptr(), channels, d_depths[p].data_ptr(), d_Rs[p].data_ptr(), d_ts[p].data_ptr(), K, rows, cols,
                                                d_denses[p].data_ptr(), d_dmasks[p].data_ptr(), mode=mode)
             solver.synchronize()
             for p in range(npairs):
                 outs[p]["dense_image"], outs[p]["dense_mask"] = d_denses[p].cpu().numpy(), d_dmasks[p].cpu().numpy()
+
+        if dense and not fuse:
+            run_dense(d_maps)
         if trajectory:
             from . import chain_clip
 
@@ -309,6 +319,17 @@ def evaluate_real_sequence(solver, frames, camera="galaxy", gamma=0.95, out_dir=
             solver.clip_points_dev(ptrs(d_coordss), ptrs(d_clip), rows, cols, traj["scales"], traj["A"], traj["c"])
             solver.synchronize()
             traj.update(links=links, points=[t.cpu().numpy() for t in d_clip])
+            if fuse:
+                d_fused = [torch.empty(rows * cols, dtype=torch.float64, device=dev) for _ in range(npairs)]
+                d_fflags = [torch.empty((rows, cols), dtype=torch.uint8, device=dev) for _ in range(npairs)]
+                torch.cuda.synchronize()
+                frecs = solver.fuse_depths_dev(ptrs(d_flows), ptrs(d_maps), vs, ws, ks, rows, cols, K, gamma, links, ptrs(d_fused), use_global_shutter_mode,
+                                               ptrs(d_fflags), tol=fuse_tol)
+                for p in range(npairs):
+                    outs[p]["fused_depth"], outs[p]["fuse_flags"] = d_fused[p].cpu().numpy().reshape(cols, rows).T.copy(), d_fflags[p].cpu().numpy()
+                    outs[p]["fuse_record"] = frecs[p]
+                if dense:
+                    run_dense(d_fused)
     if out_dir:
         os.makedirs(out_dir, exist_ok=True)
         lines = ["pair,v_x,v_y,v_z,w_x,w_y,w_z,k,inliers"]
@@ -321,6 +342,18 @@ def evaluate_real_sequence(solver, frames, camera="galaxy", gamma=0.95, out_dir=
             lines.append(",".join([str(p)] + ["%.17g" % x for x in list(o["v"]) + list(o["w"]) + [o["k"]]] + [str(o["num_inliers"])]))
         with open(os.path.join(out_dir, "poses.csv"), "w") as fh:
             fh.write("\n".join(lines) + "\n")
+        if fuse:
+            names = ["own", "filled_prev", "filled_next", "confirmed", "contradicted", "left"]
+            flines = ["pair," + ",".join(names)]
+            ii, jj = np.mgrid[0:rows, 0:cols].astype(np.float64)
+            for p, o in enumerate(outs):
+                z = o["fused_depth"]
+                has = z > 0
+                pts = np.stack([(jj[has] - K[2]) / K[0], (ii[has] - K[3]) / K[1], z[has]], axis=-1)  # the depth image's input: (x, y, z) per pixel with a value
+                formats.write_png(os.path.join(out_dir, str(p), "depth_fused.png"), solver.depth_preview(pts, K, rows, cols))
+                flines.append(",".join([str(p)] + [str(o["fuse_record"][k_]) for k_ in names]))
+            with open(os.path.join(out_dir, "fusion.csv"), "w") as fh:
+                fh.write("\n".join(flines) + "\n")
         if trajectory:
             rows_ = ["frame,c_x,c_y,c_z," + ",".join("a_%d%d" % (i, j) for i in range(3) for j in range(3)) + ",scale"]
             for f in range(npairs + 1):
