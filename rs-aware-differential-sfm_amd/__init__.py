@@ -1557,6 +1557,170 @@ for _name, _fn in list(vars(_FuseMixin).items()):
 
 
 # ---------------------------------------------------------------------------------------------------
+# the stabiliser: a smoothed camera path and every frame rendered from its virtual camera on it (include/rsdsfm_stabilize.h)
+# ---------------------------------------------------------------------------------------------------
+STABILIZE_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "rsdsfm_stabilize.h")
+
+
+class StabilizeParams(C.Structure):
+    _fields_ = [("sigma", C.c_double), ("radius", C.c_int32), ("translation", C.c_int32), ("struct_bytes", C.c_int32), ("reserved", C.c_int32)]
+
+
+def stabilize_declared_symbols():
+    """Names of every function include/rsdsfm_stabilize.h declares"""
+    import re
+
+    txt = open(STABILIZE_HEADER_PATH).read()
+    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
+    return sorted(set(re.findall(r"\b(rsdsfm_[a-z0-9_]+)\s*\(", txt)))
+
+
+def stabilize_default_params():
+    """the stabiliser's defaults as a dict: sigma = 4.0 frames, radius = 0 (ceil(3 sigma)), translation = 1 (rsdsfm_stabilize_params_init)"""
+    p = StabilizeParams()
+    if load_library().rsdsfm_stabilize_params_init(C.byref(p)) != OK:
+        raise RsdsfmError("rsdsfm_stabilize_params_init failed")
+    return dict(sigma=p.sigma, radius=p.radius, translation=p.translation)
+
+
+def _stabilize_params(sigma, radius, translation):
+    """a StabilizeParams with the given values over the defaults (sigma None: the default)"""
+    p = StabilizeParams()
+    if load_library().rsdsfm_stabilize_params_init(C.byref(p)) != OK:
+        raise RsdsfmError("rsdsfm_stabilize_params_init failed")
+    if sigma is not None:
+        p.sigma = float(sigma)
+    p.radius, p.translation = int(radius), int(bool(translation))
+    return p
+
+
+def smooth_path(A, c, sigma=None, radius=0, translation=True):
+    """the smoothed camera path (rsdsfm_smooth_path; host arithmetic, no GPU; tests/stabilize_spec_numpy.py): A (F, 3, 3), c (F, 3) from
+    chain_clip -> (A_s, c_s), one tangent-space mean step about every frame's pose with Gaussian weights of width sigma frames (None: the
+    default, 4) over |j| <= radius (0: ceil(3 sigma)); translation=False smooths the rotation only (c_s = c)."""
+    a, cc = _f64(A).reshape(-1, 9), _f64(c).reshape(-1, 3)
+    n = a.shape[0]
+    if cc.shape[0] != n:
+        raise ValueError("every frame needs a rotation and a centre")
+    p = _stabilize_params(sigma, radius, translation)
+    A_s, c_s = np.empty((max(n, 1), 9)), np.empty((max(n, 1), 3))
+    rc = load_library().rsdsfm_smooth_path(_p(a), _p(cc), C.c_int32(n), C.byref(p), _p(A_s), _p(c_s))
+    if rc != OK:
+        raise RsdsfmError("rsdsfm_smooth_path failed (%d): at least one frame, sigma finite and > 0, radius in [0, 1024]" % rc)
+    return A_s[:n].reshape(n, 3, 3), c_s[:n]
+
+
+def virtual_poses(A, c, A_s, c_s, scales, translation=True):
+    """every pair's virtual pose (rsdsfm_virtual_poses; host): M_q = A_s_q^T A_q, m_q = A_s_q^T (c_q - c_s_q) / S_q for q < F - 1 -- a point X in
+    frame q's first-scanline coordinates is M_q X + m_q in the virtual camera's.  translation=False: m = 0 and scales (may be None) is not read.
+    -> (M (F - 1, 3, 3), m (F - 1, 3))"""
+    a, cc, a_s, cc_s = _f64(A).reshape(-1, 9), _f64(c).reshape(-1, 3), _f64(A_s).reshape(-1, 9), _f64(c_s).reshape(-1, 3)
+    n = a.shape[0] - 1
+    if not (cc.shape[0] == a_s.shape[0] == cc_s.shape[0] == n + 1):
+        raise ValueError("the path and the smoothed path need the same number of frames")
+    sc = None
+    if translation:
+        sc = _f64(scales).reshape(-1)
+        if sc.shape[0] < n:
+            raise ValueError("every pair needs a scale")
+    M, m = np.empty((max(n, 1), 9)), np.empty((max(n, 1), 3))
+    rc = load_library().rsdsfm_virtual_poses(_p(a), _p(cc), _p(a_s), _p(cc_s), _p(sc), C.c_int32(n), C.c_int32(int(bool(translation))), _p(M), _p(m))
+    if rc != OK:
+        raise RsdsfmError("rsdsfm_virtual_poses failed (%d): at least one pair, every scale finite and positive" % rc)
+    return M[:n].reshape(n, 3, 3), m[:n]
+
+
+def stabilize_launches(rows, cols, count=False):
+    """kernel launches of one stabilize_frame_dev call at this size: rectify_dense_launches, plus one with a valid count
+    (rsdsfm_stabilize_launches; host only)"""
+    n = load_library().rsdsfm_stabilize_launches(C.c_int32(rows), C.c_int32(cols), C.c_int32(int(bool(count))))
+    if n < 0:
+        raise RsdsfmError("rsdsfm_stabilize_launches failed (%d): rows and cols must be in [2, 16384]" % n)
+    return n
+
+
+class _StabilizeMixin:
+    def stabilize_frame_dev(self, d_img, channels, d_depth_map, d_R, d_t, K, rows, cols, M, m, d_out, d_mask=None, d_filled=None, d_disp=None, d_valid=None,
+                            mode=BACKPROJECT_RS, q5_mode=Q5_COMPAT, iterations=0):
+        """rectify_dense_frame_dev seen from the virtual camera (M (3, 3), m (3): host arrays; rsdsfm_stabilize_frame_dev): one more rigid
+        transform inside the dense rectifier's stage B.  d_valid: a device int64 that receives the number of mask pixels that are 1.
+        Enqueued on the context's stream."""
+        d = C.c_double
+        Mh = None if M is None else _f64(M).reshape(9)
+        mh = None if m is None else _f64(m).reshape(3)
+        self._check(self.lib.rsdsfm_stabilize_frame_dev(self._ctx, _dp(d_img), C.c_int32(channels), _dp(d_depth_map), _dp(d_R), _dp(d_t), d(K[0]), d(K[1]), d(K[2]),
+                                                        d(K[3]), C.c_int32(rows), C.c_int32(cols), int(mode), int(q5_mode), C.c_int32(iterations), _p(Mh), _p(mh),
+                                                        _dp(d_out), _np0(d_mask), _np0(d_filled), _np0(d_disp), _np0(d_valid)), "rsdsfm_stabilize_frame_dev")
+
+    def stabilize(self, image, depth_map, R, t, K, M, m, mode=BACKPROJECT_RS, q5_mode=Q5_COMPAT, iterations=0, device=0):
+        """host convenience around stabilize_frame_dev: image (rows, cols) or (rows, cols, 3) uint8, depth_map (rows, cols) (0 where unknown),
+        R (rows, 3, 3) / (rows, 9), t (rows, 3), M (3, 3), m (3).  Returns (stabilised image, mask, valid)."""
+        import torch
+
+        img = np.ascontiguousarray(image, dtype=np.uint8)
+        rows, cols = img.shape[:2]
+        dev = torch.device("cuda", device)
+        with torch.cuda.device(dev):
+            up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+            d_img, d_dm = up(img), up(np.asarray(depth_map, dtype=np.float64).T)  # column-major rows x cols
+            d_R, d_t = up(_f64(np.asarray(R).reshape(rows, 9))), up(_f64(t))
+            d_out, d_mask = torch.empty_like(d_img), torch.empty((rows, cols), dtype=torch.uint8, device=dev)
+            d_valid = torch.zeros(1, dtype=torch.int64, device=dev)
+            torch.cuda.synchronize()
+            self.stabilize_frame_dev(d_img.data_ptr(), 1 if img.ndim == 2 else img.shape[2], d_dm.data_ptr(), d_R.data_ptr(), d_t.data_ptr(), K, rows, cols, M, m,
+                                     d_out.data_ptr(), d_mask.data_ptr(), d_valid=d_valid.data_ptr(), mode=mode, q5_mode=q5_mode, iterations=iterations)
+            self.synchronize()
+            return d_out.cpu().numpy(), d_mask.cpu().numpy(), int(d_valid.cpu().numpy()[0])
+
+    def stabilize_video_dev(self, d_frames, rows, cols, channels, K, gamma, d_depth_maps, d_flows, d_R, d_t, d_stab, d_masks_out=None, d_fused=None,
+                            want_valid=True, sigma=None, radius=0, translation=True, fuse_tol=None, d_masks=None, seeds=None, flow_params=None, a1=None,
+                            a2=None, link_tol=None, min_links=None, radix_bits=None, mode=BACKPROJECT_RS, q5_mode=Q5_COMPAT, iterations=0, trials=50, tol=0.05,
+                            use_acceleration_mode=False, use_refinement=True, depth_mode=DEPTH_CERES_LM, k_sign_mode=K_COMPAT, flow_threshold=1e-10,
+                            flow_index_mode=FLOW_COMPAT_RANK, use_global_shutter_mode=False):
+        """the stabilised clip in ONE call (rsdsfm_stabilize_video_dev): solve_video_linked_dev (d_flows, d_depth_maps, d_R, d_t all required), the
+        fusion of the maps when d_fused (F - 1 buffers) is passed, smooth_path, virtual_poses and stabilize_frame_dev of frames 0 .. F - 2 into
+        d_stab (and d_masks_out).  Returns solve_video_linked_dev's dict plus A_s, c_s, M, m and, with want_valid, valid (F - 1 counts; the
+        call then waits for the frames)."""
+        n = len(d_frames) - 1
+        prm = FrameParams(int(trials), int(use_acceleration_mode), int(use_refinement), int(depth_mode), int(k_sign_mode),
+                          int(flow_index_mode), int(use_global_shutter_mode), 0, float(tol), float(flow_threshold), 1)
+        res = (FrameResult * max(n, 1))()
+        rec = (LinkRecord * max(n - 1, 1))()
+        nn = max(n, 1)
+        scales, A, c = np.empty(nn), np.empty((nn + 1, 3, 3)), np.empty((nn + 1, 3))
+        A_s, c_s, M, m = np.empty((nn + 1, 3, 3)), np.empty((nn + 1, 3)), np.empty((nn, 3, 3)), np.empty((nn, 3))
+        valid = np.zeros(nn, dtype=np.int64) if want_valid else None
+        broken = np.zeros(max(n - 1, 1), dtype=np.uint8)
+        sd = (C.c_uint64 * n)(*[int(s) for s in seeds]) if seeds is not None else None
+        arr = lambda a: _ptr_array(a) if a is not None else None
+        p, k, lp = _flow_params(flow_params), _flow_check_params(a1, a2), _link_params(link_tol, min_links, radix_bits)
+        sp = _stabilize_params(sigma, radius, translation)
+        fp = None
+        if fuse_tol is not None:
+            fp = FuseParams()
+            if self.lib.rsdsfm_fuse_params_init(C.byref(fp)) != OK:
+                raise RsdsfmError("rsdsfm_fuse_params_init failed")
+            fp.tol = float(fuse_tol)
+        d = C.c_double
+        ref = lambda x: C.byref(x) if x is not None else None
+        self._check(self.lib.rsdsfm_stabilize_video_dev(self._ctx, _ptr_array(d_frames), C.c_int32(len(d_frames)), C.c_int32(rows), C.c_int32(cols),
+                                                        C.c_int32(channels), d(K[0]), d(K[1]), d(K[2]), d(K[3]), d(gamma), ref(p), C.byref(prm), sd, arr(d_flows),
+                                                        arr(d_depth_maps), arr(d_R), arr(d_t), res, ref(k), arr(d_masks), ref(lp), rec, _p(scales), _p(A), _p(c),
+                                                        _p(broken), ref(fp), arr(d_fused), C.byref(sp), int(mode), int(q5_mode), C.c_int32(iterations), _p(A_s),
+                                                        _p(c_s), _p(M), _p(m), arr(d_stab), arr(d_masks_out), _p(valid)), "rsdsfm_stabilize_video_dev")
+        out = dict(pairs=[_frame_result_dict(r) for r in res[:n]], links=[r.as_dict() for r in rec[:max(n - 1, 0)]], scales=scales[:n], A=A[:n + 1], c=c[:n + 1],
+                   broken=broken[:max(n - 1, 0)], A_s=A_s[:n + 1], c_s=c_s[:n + 1], M=M[:n], m=m[:n])
+        if want_valid:
+            out["valid"] = valid[:n]
+        return out
+
+
+for _name, _fn in list(vars(_StabilizeMixin).items()):
+    if not _name.startswith("__"):
+        setattr(Solver, _name, _fn)
+
+
+# ---------------------------------------------------------------------------------------------------
 # accuracy metrics (SURVEY 8 f-4)
 # ---------------------------------------------------------------------------------------------------
 class ReprojectionStats(C.Structure):

@@ -53,6 +53,7 @@ int link_launch_count(int bits);
 // npairs <= kPointsMax pairs in one launch
 hipError_t clip_points_launch(hipStream_t s, const PointsArgs& a, int npairs, int64_t npix);
 
+void link_rodrigues(const double a[3], double R[9]);  // link_host.hip: the chain's exp([a]x), row-major (host); the stabiliser's too
 void link_release(Ctx* c);  // link_host.hip: the context's link workspace (Ctx::link)
 
 }  // namespace rsdsfm

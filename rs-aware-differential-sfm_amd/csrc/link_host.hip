@@ -146,6 +146,8 @@ int check_points_args(Ctx* c, const float* const* in, float* const* out, int npa
 
 }  // namespace
 
+void link_rodrigues(const double a[3], double R[9]) { rodrigues(a, R); }
+
 void link_release(Ctx* c) {
     LinkWs* w = static_cast<LinkWs*>(c->link);
     if (!w) return;

@@ -14,6 +14,7 @@ namespace rsdsfm {
 struct DenseWs {
     double* d_pyr = nullptr;  // levels 1 .. top, level after level, row-major
     float2* d_disp = nullptr; // rows x cols
+    unsigned char* d_mask = nullptr;  // rows x cols: the stabiliser's mask when it counts without a caller's mask (made when first asked for)
     int rows = 0, cols = 0;
 };
 
@@ -34,6 +35,11 @@ void rectify_dense_release(Ctx* c);
 int rectify_dense_launch(Ctx* c, const DenseWs& ws, const unsigned char* d_img, int channels, const double* d_depth_cm, const double* d_R, const double* d_t,
                          double fx, double fy, double cx, double cy, int rows, int cols, int mode, int q5_mode, int iterations, unsigned char* d_out,
                          unsigned char* d_mask, double* d_filled_cm);
+// its parts, for the stabiliser (stabilize_kernels.hip), which puts a map kernel of its own between them: stage A (*top: the 1 x 1 level,
+// in the workspace) and stage C
+int rectify_dense_launch_fill(Ctx* c, const DenseWs& ws, const double* d_depth_cm, int rows, int cols, const double** top);
+int rectify_dense_launch_warp(Ctx* c, const DenseWs& ws, const unsigned char* d_img, int channels, const double* top, int rows, int cols, int iterations,
+                              unsigned char* d_out, unsigned char* d_mask);
 // the argument checks both entry points share (everything but the context and the sizes of the clip)
 int rectify_dense_check(Ctx* c, int channels, int rows, int cols, int mode, int q5_mode, int iterations);
 

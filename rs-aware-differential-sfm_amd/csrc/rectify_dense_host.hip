@@ -10,8 +10,10 @@ namespace rsdsfm {
 static void dense_ws_free(DenseWs* w) {
     if (w->d_pyr) (void)hipFree(w->d_pyr);
     if (w->d_disp) (void)hipFree(w->d_disp);
+    if (w->d_mask) (void)hipFree(w->d_mask);
     w->d_pyr = nullptr;
     w->d_disp = nullptr;
+    w->d_mask = nullptr;
     w->rows = w->cols = 0;
 }
 

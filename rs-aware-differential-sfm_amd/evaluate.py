@@ -206,7 +206,8 @@ def _write_real_outputs(out_dir, image, flow, depth_est, backprojection, coords)
 
 def evaluate_real_sequence(solver, frames, camera="galaxy", gamma=0.95, out_dir=None, trials=5, seeds=None, tol=0.05, use_acceleration_mode=False,
                            use_refinement=True, use_global_shutter_mode=False, flow_threshold=1e-10, flow_index_mode=0, device=0, flow_params=None, dense=False,
-                           check_flow=False, trajectory=False, link_tol=None, min_links=None, fuse=False, fuse_tol=None):
+                           check_flow=False, trajectory=False, link_tol=None, min_links=None, fuse=False, fuse_tol=None, stabilize=False, smooth_sigma=None,
+                           smooth_translation=True):
     """evaluate_real_run's real-world branch (main.cc:341-361, 364-531) for a clip: `frames` is <prefix>frame1.png ... frameN.png (the
     prefix, or a list of paths), or the frames themselves (an (N, rows, cols[, 3]) uint8 array or a list of arrays; 2-D frames are gray).
     By default ONE call does the clip (Solver.rectify_video_dev): the batched DeepFlow of every consecutive pair, the pipelined solve of every pair p
@@ -227,7 +228,15 @@ def evaluate_real_sequence(solver, frames, camera="galaxy", gamma=0.95, out_dir=
     every pair's holes filled from what its neighbours measured there); each pair's dict gets fused_depth ((rows, cols) float64, 0 = no value),
     fuse_flags ((rows, cols) uint8: FUSE_OWN ...) and fuse_record; with dense=True the dense rectifier reads the FUSED map; out_dir receives
     depth_fused.png per pair (Solver.depth_preview's 8-bit depth image of the fused map) and fusion.csv (pair and the six counts).  The clip's
-    points and clip.ply keep selecting by the solve's map.  The default writes exactly what it did."""
+    points and clip.ply keep selecting by the solve's map.  The default writes exactly what it did.
+    stabilize=True (implies trajectory=True): behind the chain (and the fusion), the smoothed camera path (smooth_path with smooth_sigma frames,
+    None = the default; smooth_translation=False smooths the rotation only), every pair's virtual pose (virtual_poses) and frame p rendered from
+    its virtual camera (Solver.stabilize_frame_dev on the pair's map -- the FUSED one with fuse=True -- and pose table).  The returned dict then
+    also has stabilized and stab_masks (per pair, the frame's shape / (rows, cols) uint8), stab_valid (per pair, the mask's count) and
+    path_smoothed = dict(A_s, c_s, M, m); out_dir receives stabilized_<p>.png per pair and path_smoothed.csv (frame, smoothed position, smoothed
+    rotation row by row).  The last frame has no pair and is not rendered.  With stabilize=False every output is unchanged."""
+    if stabilize:
+        trajectory = True
     if fuse and not trajectory:
         raise ValueError("fuse=True needs trajectory=True: the fusion converts between the pairs' units with the links' ratios")
     import torch
@@ -330,6 +339,22 @@ def evaluate_real_sequence(solver, frames, camera="galaxy", gamma=0.95, out_dir=
                     outs[p]["fuse_record"] = frecs[p]
                 if dense:
                     run_dense(d_fused)
+            if stabilize:
+                from . import smooth_path, virtual_poses
+
+                A_s, c_s = smooth_path(traj["A"], traj["c"], smooth_sigma, 0, smooth_translation)
+                vM, vm = virtual_poses(traj["A"], traj["c"], A_s, c_s, traj["scales"], smooth_translation)
+                d_stabs = [torch.empty_like(d_imgs[0]) for _ in range(npairs)]
+                d_smasks = [torch.empty((rows, cols), dtype=torch.uint8, device=dev) for _ in range(npairs)]
+                d_svalid = torch.zeros(npairs, dtype=torch.int64, device=dev)
+                torch.cuda.synchronize()
+                d_src = d_fused if fuse else d_maps
+                for p in range(npairs):  # every frame enqueued behind the clip, one wait for all of them
+                    solver.stabilize_frame_dev(d_imgs[p].data_ptr(), channels, d_src[p].data_ptr(), d_Rs[p].data_ptr(), d_ts[p].data_ptr(), K, rows, cols, vM[p],
+                                               vm[p], d_stabs[p].data_ptr(), d_smasks[p].data_ptr(), d_valid=d_svalid[p:].data_ptr(), mode=mode)
+                solver.synchronize()
+                traj.update(stabilized=[t.cpu().numpy() for t in d_stabs], stab_masks=[t.cpu().numpy() for t in d_smasks],
+                            stab_valid=[int(x) for x in d_svalid.cpu().numpy()], path_smoothed=dict(A_s=A_s, c_s=c_s, M=vM, m=vm))
     if out_dir:
         os.makedirs(out_dir, exist_ok=True)
         lines = ["pair,v_x,v_y,v_z,w_x,w_y,w_z,k,inliers"]
@@ -365,6 +390,15 @@ def evaluate_real_sequence(solver, frames, camera="galaxy", gamma=0.95, out_dir=
             colour = [im if im.ndim == 3 else np.repeat(im[..., None], 3, axis=2) for im in images[:npairs]]
             formats.write_ply(os.path.join(out_dir, "clip.ply"), np.concatenate([traj["points"][p][keep[p]] for p in range(npairs)]),
                               np.concatenate([colour[p][keep[p]] for p in range(npairs)]))
+        if stabilize:
+            for p in range(npairs):
+                formats.write_png(os.path.join(out_dir, "stabilized_%d.png" % p), traj["stabilized"][p])
+            ps = traj["path_smoothed"]
+            rows_ = ["frame,c_x,c_y,c_z," + ",".join("a_%d%d" % (i, j) for i in range(3) for j in range(3))]
+            for f in range(npairs + 1):
+                rows_.append(",".join([str(f)] + ["%.17g" % x for x in list(ps["c_s"][f]) + list(ps["A_s"][f].reshape(-1))]))
+            with open(os.path.join(out_dir, "path_smoothed.csv"), "w") as fh:
+                fh.write("\n".join(rows_) + "\n")
     if trajectory:
         return dict(traj, pairs=outs)
     return outs
