@@ -1681,6 +1681,14 @@ class _StabilizeMixin:
         fusion of the maps when d_fused (F - 1 buffers) is passed, smooth_path, virtual_poses and stabilize_frame_dev of frames 0 .. F - 2 into
         d_stab (and d_masks_out).  Returns solve_video_linked_dev's dict plus A_s, c_s, M, m and, with want_valid, valid (F - 1 counts; the
         call then waits for the frames)."""
+        args = {k_: v_ for k_, v_ in locals().items() if k_ != "self"}
+        return self._stabilize_video("rsdsfm_stabilize_video_dev", (), **args)
+
+    def _stabilize_video(self, entry, tail, d_frames, rows, cols, channels, K, gamma, d_depth_maps, d_flows, d_R, d_t, d_stab, d_masks_out, d_fused, want_valid,
+                         sigma, radius, translation, fuse_tol, d_masks, seeds, flow_params, a1, a2, link_tol, min_links, radix_bits, mode, q5_mode, iterations,
+                         trials, tol, use_acceleration_mode, use_refinement, depth_mode, k_sign_mode, flow_threshold, flow_index_mode, use_global_shutter_mode):
+        """stabilize_video_dev's marshalling, for it and for the entry points that take its arguments and then a `tail` of their own
+        (stabilize_video_filled_dev)"""
         n = len(d_frames) - 1
         prm = FrameParams(int(trials), int(use_acceleration_mode), int(use_refinement), int(depth_mode), int(k_sign_mode),
                           int(flow_index_mode), int(use_global_shutter_mode), 0, float(tol), float(flow_threshold), 1)
@@ -1703,11 +1711,11 @@ class _StabilizeMixin:
             fp.tol = float(fuse_tol)
         d = C.c_double
         ref = lambda x: C.byref(x) if x is not None else None
-        self._check(self.lib.rsdsfm_stabilize_video_dev(self._ctx, _ptr_array(d_frames), C.c_int32(len(d_frames)), C.c_int32(rows), C.c_int32(cols),
-                                                        C.c_int32(channels), d(K[0]), d(K[1]), d(K[2]), d(K[3]), d(gamma), ref(p), C.byref(prm), sd, arr(d_flows),
-                                                        arr(d_depth_maps), arr(d_R), arr(d_t), res, ref(k), arr(d_masks), ref(lp), rec, _p(scales), _p(A), _p(c),
-                                                        _p(broken), ref(fp), arr(d_fused), C.byref(sp), int(mode), int(q5_mode), C.c_int32(iterations), _p(A_s),
-                                                        _p(c_s), _p(M), _p(m), arr(d_stab), arr(d_masks_out), _p(valid)), "rsdsfm_stabilize_video_dev")
+        self._check(getattr(self.lib, entry)(self._ctx, _ptr_array(d_frames), C.c_int32(len(d_frames)), C.c_int32(rows), C.c_int32(cols),
+                                             C.c_int32(channels), d(K[0]), d(K[1]), d(K[2]), d(K[3]), d(gamma), ref(p), C.byref(prm), sd, arr(d_flows),
+                                             arr(d_depth_maps), arr(d_R), arr(d_t), res, ref(k), arr(d_masks), ref(lp), rec, _p(scales), _p(A), _p(c),
+                                             _p(broken), ref(fp), arr(d_fused), C.byref(sp), int(mode), int(q5_mode), C.c_int32(iterations), _p(A_s),
+                                             _p(c_s), _p(M), _p(m), arr(d_stab), arr(d_masks_out), _p(valid), *tail), entry)
         out = dict(pairs=[_frame_result_dict(r) for r in res[:n]], links=[r.as_dict() for r in rec[:max(n - 1, 0)]], scales=scales[:n], A=A[:n + 1], c=c[:n + 1],
                    broken=broken[:max(n - 1, 0)], A_s=A_s[:n + 1], c_s=c_s[:n + 1], M=M[:n], m=m[:n])
         if want_valid:
@@ -1716,6 +1724,152 @@ class _StabilizeMixin:
 
 
 for _name, _fn in list(vars(_StabilizeMixin).items()):
+    if not _name.startswith("__"):
+        setattr(Solver, _name, _fn)
+
+
+# ---------------------------------------------------------------------------------------------------
+# the stabiliser's border fill: the band its own frame leaves empty, from the neighbouring frames (include/rsdsfm_stabilize_fill.h)
+# ---------------------------------------------------------------------------------------------------
+STABILIZE_FILL_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "rsdsfm_stabilize_fill.h")
+
+
+class StabilizeFillParams(C.Structure):
+    _fields_ = [("radius", C.c_int32), ("struct_bytes", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
+def stabilize_fill_declared_symbols():
+    """Names of every function include/rsdsfm_stabilize_fill.h declares"""
+    import re
+
+    txt = open(STABILIZE_FILL_HEADER_PATH).read()
+    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
+    return sorted(set(re.findall(r"\b(rsdsfm_[a-z0-9_]+)\s*\(", txt)))
+
+
+def stabilize_fill_default_params():
+    """the border fill's defaults as a dict: radius = 2 neighbours on each side (rsdsfm_stabilize_fill_params_init)"""
+    p = StabilizeFillParams()
+    if load_library().rsdsfm_stabilize_fill_params_init(C.byref(p)) != OK:
+        raise RsdsfmError("rsdsfm_stabilize_fill_params_init failed")
+    return dict(radius=p.radius)
+
+
+def _stabilize_fill_params(radius):
+    """a StabilizeFillParams with the given radius (0: the default)"""
+    p = StabilizeFillParams()
+    if load_library().rsdsfm_stabilize_fill_params_init(C.byref(p)) != OK:
+        raise RsdsfmError("rsdsfm_stabilize_fill_params_init failed")
+    if radius:
+        p.radius = int(radius)
+    return p
+
+
+def neighbour_poses(A, c, A_s, c_s, scales, q, radius=2):
+    """the candidates of frame q and their poses (rsdsfm_neighbour_poses; host arithmetic, no GPU; tests/stabilize_fill_spec_numpy.py): the
+    frames n = q - 1, q + 1, ..., q - radius, q + radius that have a pair, their source ids (2 |j| for a previous, 2 |j| + 1 for a next frame)
+    and M = A_s_q^T A_n, m = A_s_q^T (c_n - c_s_q) / S_n -- a point X in frame n's first-scanline coordinates is M X + m in virtual camera q's.
+    scales: one per pair (their number is the number of pairs), always read.  -> (frames (k,), source_ids (k,), M (k, 3, 3), m (k, 3)),
+    k <= 2 radius"""
+    a, cc, a_s, cc_s, sc = _f64(A).reshape(-1, 9), _f64(c).reshape(-1, 3), _f64(A_s).reshape(-1, 9), _f64(c_s).reshape(-1, 3), _f64(scales).reshape(-1)
+    n = sc.shape[0]
+    if not (a.shape[0] == cc.shape[0] and a_s.shape[0] == cc_s.shape[0] and a.shape[0] >= n and a_s.shape[0] >= n):
+        raise ValueError("the path and the smoothed path need an entry for every pair")
+    room = 2 * max(int(radius), 1)
+    frames, ids = np.zeros(room, dtype=np.int32), np.zeros(room, dtype=np.int32)
+    M, m = np.empty((room, 9)), np.empty((room, 3))
+    k = C.c_int32(0)
+    rc = load_library().rsdsfm_neighbour_poses(_p(a), _p(cc), _p(a_s), _p(cc_s), _p(sc), C.c_int32(n), C.c_int32(q), C.c_int32(radius), _p(frames), _p(ids), _p(M),
+                                               _p(m), C.byref(k))
+    if rc != OK:
+        raise RsdsfmError("rsdsfm_neighbour_poses failed (%d): q in [0, pairs - 1], radius in [1, 16], every listed neighbour's scale finite and positive" % rc)
+    return frames[:k.value], ids[:k.value], M[:k.value].reshape(-1, 3, 3), m[:k.value]
+
+
+def stabilize_fill_launches(rows, cols):
+    """kernel launches of one stabilize_fill_frame_dev call at this size: rectify_dense_launches -- the fill-warp kernel counts by itself
+    (rsdsfm_stabilize_fill_launches; host only)"""
+    n = load_library().rsdsfm_stabilize_fill_launches(C.c_int32(rows), C.c_int32(cols))
+    if n < 0:
+        raise RsdsfmError("rsdsfm_stabilize_fill_launches failed (%d): rows and cols must be in [2, 16384]" % n)
+    return n
+
+
+class _StabilizeFillMixin:
+    def stabilize_fill_frame_dev(self, d_img_n, channels, d_depth_map_n, d_R_n, d_t_n, K, rows, cols, M, m, source_id, d_image, d_mask, d_source=None,
+                                 d_filled=None, mode=BACKPROJECT_RS, q5_mode=Q5_COMPAT, iterations=0):
+        """one candidate of the border fill (rsdsfm_stabilize_fill_frame_dev): the neighbour's frame, depth map and pose table seen from the
+        virtual camera (M (3, 3), m (3): host arrays, neighbour_poses') and taken where d_mask is 0 and the candidate is valid: d_image gets the
+        pixel, d_mask 1, d_source (a device plane of bytes) source_id.  d_filled: a device int64 that receives the number of pixels taken.
+        Enqueued on the context's stream."""
+        d = C.c_double
+        Mh = None if M is None else _f64(M).reshape(9)
+        mh = None if m is None else _f64(m).reshape(3)
+        self._check(self.lib.rsdsfm_stabilize_fill_frame_dev(self._ctx, _dp(d_img_n), C.c_int32(channels), _dp(d_depth_map_n), _dp(d_R_n), _dp(d_t_n), d(K[0]),
+                                                             d(K[1]), d(K[2]), d(K[3]), C.c_int32(rows), C.c_int32(cols), int(mode), int(q5_mode),
+                                                             C.c_int32(iterations), _p(Mh), _p(mh), C.c_int32(source_id), _dp(d_image), _dp(d_mask), _np0(d_source),
+                                                             _np0(d_filled)), "rsdsfm_stabilize_fill_frame_dev")
+
+    def stabilize_filled(self, images, depth_maps, Rs, ts, K, A, c, A_s, c_s, scales, q, M, m, radius=2, mode=BACKPROJECT_RS, q5_mode=Q5_COMPAT, iterations=0,
+                         device=0):
+        """host convenience: frame q of a clip rendered from its virtual camera (M, m: virtual_poses' entry q) and its empty band filled from
+        its neighbours (neighbour_poses, then one stabilize_fill_frame_dev each).  images / depth_maps / Rs / ts are indexed by frame and entry
+        q and its candidates' are read: images (rows, cols[, 3]) uint8, depth maps (rows, cols) (0 where unknown), R (rows, 3, 3) / (rows, 9),
+        t (rows, 3).  Returns (image, mask, source (rows, cols) uint8, counts (2 + 2 radius,) int64: [none, own, -1, +1, -2, +2, ...])."""
+        import torch
+
+        frames, ids, nM, nm = neighbour_poses(A, c, A_s, c_s, scales, q, radius)
+        rows, cols = np.asarray(images[q]).shape[:2]
+        dev = torch.device("cuda", device)
+        with torch.cuda.device(dev):
+            up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+
+            def frame(n):  # image, column-major depth map, pose table
+                img = np.ascontiguousarray(images[n], dtype=np.uint8)
+                return up(img), up(np.asarray(depth_maps[n], dtype=np.float64).T), up(_f64(np.asarray(Rs[n]).reshape(rows, 9))), up(_f64(ts[n]))
+
+            d_img, d_dm, d_R, d_t = frame(q)
+            channels = 1 if d_img.ndim == 2 else d_img.shape[2]
+            d_out, d_mask = torch.empty_like(d_img), torch.empty((rows, cols), dtype=torch.uint8, device=dev)
+            d_cnt = torch.zeros(2 + 2 * radius, dtype=torch.int64, device=dev)
+            cand = [frame(int(n)) for n in frames]
+            torch.cuda.synchronize()
+            self.stabilize_frame_dev(d_img.data_ptr(), channels, d_dm.data_ptr(), d_R.data_ptr(), d_t.data_ptr(), K, rows, cols, M, m, d_out.data_ptr(),
+                                     d_mask.data_ptr(), d_valid=d_cnt[1:].data_ptr(), mode=mode, q5_mode=q5_mode, iterations=iterations)
+            self.synchronize()
+            d_source = d_mask.clone()
+            torch.cuda.synchronize()
+            for (n_img, n_dm, n_R, n_t), sid, Mn, mn in zip(cand, ids, nM, nm):
+                self.stabilize_fill_frame_dev(n_img.data_ptr(), channels, n_dm.data_ptr(), n_R.data_ptr(), n_t.data_ptr(), K, rows, cols, Mn, mn, int(sid),
+                                              d_out.data_ptr(), d_mask.data_ptr(), d_source.data_ptr(), d_cnt[int(sid):].data_ptr(), mode=mode, q5_mode=q5_mode,
+                                              iterations=iterations)
+            self.synchronize()
+            counts = d_cnt.cpu().numpy()
+            counts[0] = rows * cols - int(counts[1:].sum())
+            return d_out.cpu().numpy(), d_mask.cpu().numpy(), d_source.cpu().numpy(), counts
+
+    def stabilize_video_filled_dev(self, d_frames, rows, cols, channels, K, gamma, d_depth_maps, d_flows, d_R, d_t, d_stab, d_masks_out, d_sources=None,
+                                   fill_radius=0, want_counts=True, d_fused=None, want_valid=True, sigma=None, radius=0, translation=True, fuse_tol=None,
+                                   d_masks=None, seeds=None, flow_params=None, a1=None, a2=None, link_tol=None, min_links=None, radix_bits=None,
+                                   mode=BACKPROJECT_RS, q5_mode=Q5_COMPAT, iterations=0, trials=50, tol=0.05, use_acceleration_mode=False, use_refinement=True,
+                                   depth_mode=DEPTH_CERES_LM, k_sign_mode=K_COMPAT, flow_threshold=1e-10, flow_index_mode=FLOW_COMPAT_RANK,
+                                   use_global_shutter_mode=False):
+        """the stabilised clip with its borders filled in ONE call (rsdsfm_stabilize_video_filled_dev): stabilize_video_dev with these arguments
+        (d_masks_out required), then for every frame its mask copied to d_sources (F - 1 device planes of bytes, optional), neighbour_poses with
+        fill_radius neighbours on each side (0: the default, 2) and one stabilize_fill_frame_dev per candidate -- on the fused maps when d_fused
+        is passed.  Returns stabilize_video_dev's dict plus, with want_counts, counts ((F - 1, 2 + 2 fill_radius) int64: [none, own, -1, +1,
+        ...] per frame; the call then waits for the passes)."""
+        n = len(d_frames) - 1
+        fp = _stabilize_fill_params(fill_radius)
+        counts = np.zeros((max(n, 1), 2 + 2 * fp.radius), dtype=np.int64) if want_counts else None
+        args = {k_: v_ for k_, v_ in locals().items() if k_ not in ("self", "n", "fp", "counts", "d_sources", "fill_radius", "want_counts")}
+        out = self._stabilize_video("rsdsfm_stabilize_video_filled_dev", (C.byref(fp), _ptr_array(d_sources) if d_sources is not None else None, _p(counts)), **args)
+        if want_counts:
+            out["counts"] = counts[:n]
+        return out
+
+
+for _name, _fn in list(vars(_StabilizeFillMixin).items()):
     if not _name.startswith("__"):
         setattr(Solver, _name, _fn)
 

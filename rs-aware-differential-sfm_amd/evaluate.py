@@ -207,7 +207,7 @@ def _write_real_outputs(out_dir, image, flow, depth_est, backprojection, coords)
 def evaluate_real_sequence(solver, frames, camera="galaxy", gamma=0.95, out_dir=None, trials=5, seeds=None, tol=0.05, use_acceleration_mode=False,
                            use_refinement=True, use_global_shutter_mode=False, flow_threshold=1e-10, flow_index_mode=0, device=0, flow_params=None, dense=False,
                            check_flow=False, trajectory=False, link_tol=None, min_links=None, fuse=False, fuse_tol=None, stabilize=False, smooth_sigma=None,
-                           smooth_translation=True):
+                           smooth_translation=True, fill=0):
     """evaluate_real_run's real-world branch (main.cc:341-361, 364-531) for a clip: `frames` is <prefix>frame1.png ... frameN.png (the
     prefix, or a list of paths), or the frames themselves (an (N, rows, cols[, 3]) uint8 array or a list of arrays; 2-D frames are gray).
     By default ONE call does the clip (Solver.rectify_video_dev): the batched DeepFlow of every consecutive pair, the pipelined solve of every pair p
@@ -234,7 +234,15 @@ def evaluate_real_sequence(solver, frames, camera="galaxy", gamma=0.95, out_dir=
     its virtual camera (Solver.stabilize_frame_dev on the pair's map -- the FUSED one with fuse=True -- and pose table).  The returned dict then
     also has stabilized and stab_masks (per pair, the frame's shape / (rows, cols) uint8), stab_valid (per pair, the mask's count) and
     path_smoothed = dict(A_s, c_s, M, m); out_dir receives stabilized_<p>.png per pair and path_smoothed.csv (frame, smoothed position, smoothed
-    rotation row by row).  The last frame has no pair and is not rendered.  With stabilize=False every output is unchanged."""
+    rotation row by row).  The last frame has no pair and is not rendered.  With stabilize=False every output is unchanged.
+    fill=K (needs stabilize=True: ValueError otherwise; K = 1 .. 16 neighbours on each side): behind the stabilised frames, the band each leaves
+    empty filled from its neighbours (neighbour_poses, then one Solver.stabilize_fill_frame_dev per candidate on COPIES of the frame and its
+    mask, on the neighbour's map -- the FUSED one with fuse=True).  The returned dict then also has stab_filled (per pair, the frame's shape),
+    stab_sources (per pair, (rows, cols) uint8: 0 nobody, 1 the own frame, 2 |j| / 2 |j| + 1 the frame j before / after) and fill_counts
+    ((pairs, 2 + 2 K) int64: [none, own, -1, +1, -2, +2, ...]); out_dir receives stabilized_filled_<p>.png per pair and fill.csv (pair and the
+    counts).  Without fill every output is what it was."""
+    if fill and not stabilize:
+        raise ValueError("fill needs stabilize=True: it fills the stabilised frames' borders")
     if stabilize:
         trajectory = True
     if fuse and not trajectory:
@@ -355,6 +363,22 @@ def evaluate_real_sequence(solver, frames, camera="galaxy", gamma=0.95, out_dir=
                 solver.synchronize()
                 traj.update(stabilized=[t.cpu().numpy() for t in d_stabs], stab_masks=[t.cpu().numpy() for t in d_smasks],
                             stab_valid=[int(x) for x in d_svalid.cpu().numpy()], path_smoothed=dict(A_s=A_s, c_s=c_s, M=vM, m=vm))
+                if fill:
+                    from . import neighbour_poses
+
+                    d_fills, d_fmasks2, d_sources = [t.clone() for t in d_stabs], [t.clone() for t in d_smasks], [t.clone() for t in d_smasks]
+                    d_fcnt = torch.zeros((npairs, 2 + 2 * fill), dtype=torch.int64, device=dev)
+                    d_fcnt[:, 1] = d_svalid
+                    torch.cuda.synchronize()
+                    for p in range(npairs):  # every pass enqueued, one wait for all of them
+                        for n, sid, nM, nm in zip(*neighbour_poses(traj["A"], traj["c"], A_s, c_s, traj["scales"], p, fill)):
+                            solver.stabilize_fill_frame_dev(d_imgs[n].data_ptr(), channels, d_src[n].data_ptr(), d_Rs[n].data_ptr(), d_ts[n].data_ptr(), K, rows,
+                                                            cols, nM, nm, int(sid), d_fills[p].data_ptr(), d_fmasks2[p].data_ptr(), d_sources[p].data_ptr(),
+                                                            d_fcnt[p, int(sid):].data_ptr(), mode=mode)
+                    solver.synchronize()
+                    counts = d_fcnt.cpu().numpy()
+                    counts[:, 0] = rows * cols - counts[:, 1:].sum(axis=1)
+                    traj.update(stab_filled=[t.cpu().numpy() for t in d_fills], stab_sources=[t.cpu().numpy() for t in d_sources], fill_counts=counts)
     if out_dir:
         os.makedirs(out_dir, exist_ok=True)
         lines = ["pair,v_x,v_y,v_z,w_x,w_y,w_z,k,inliers"]
@@ -398,6 +422,14 @@ def evaluate_real_sequence(solver, frames, camera="galaxy", gamma=0.95, out_dir=
             for f in range(npairs + 1):
                 rows_.append(",".join([str(f)] + ["%.17g" % x for x in list(ps["c_s"][f]) + list(ps["A_s"][f].reshape(-1))]))
             with open(os.path.join(out_dir, "path_smoothed.csv"), "w") as fh:
+                fh.write("\n".join(rows_) + "\n")
+        if fill:
+            names = ["none", "own"] + ["%s%d" % (sg, j) for j in range(1, fill + 1) for sg in ("prev", "next")]
+            rows_ = ["pair," + ",".join(names)]
+            for p in range(npairs):
+                formats.write_png(os.path.join(out_dir, "stabilized_filled_%d.png" % p), traj["stab_filled"][p])
+                rows_.append(",".join([str(p)] + [str(int(x)) for x in traj["fill_counts"][p]]))
+            with open(os.path.join(out_dir, "fill.csv"), "w") as fh:
                 fh.write("\n".join(rows_) + "\n")
     if trajectory:
         return dict(traj, pairs=outs)
