@@ -17,8 +17,8 @@
  * tests/stabilize_spec_numpy.py is the executable definition; the frame call reproduces it bit for bit, the host functions to rounding
  * (they call exp, sin, cos, atan2).  DESIGN.md section 12 ("Stabilisation") has the launches, the bytes and what has been measured.
  *
- * There is NO zoom or crop parameter: with a zoom folded into the displacement plane the fixed point p <- g - D(p) of stage C contracts by
- * |zoom - 1| per step and does not converge at zoom 2.  Cropping is the caller's, guided by the mask and the valid count.
+ * There is NO zoom or crop parameter HERE: with a zoom folded into the displacement plane the fixed point p <- g - D(p) of stage C contracts
+ * by |zoom - 1| per step and does not converge at zoom 2.  rsdsfm_stabilize_crop.h crops and zooms with D as it is and the target moved.
  */
 #ifndef RSDSFM_STABILIZE_H
 #define RSDSFM_STABILIZE_H

@@ -3,7 +3,7 @@
  * cover, filled from the neighbouring frames of the clip.
  *
  * The reference solves one pair per process run (evaluateSingleRun's per-pair loop, main.cc:380-523) and has no counterpart to this.  The
- * stabiliser (rsdsfm_stabilize.h) has no zoom or crop, so a stabilised frame has an empty band where the virtual camera sees what its own
+ * stabiliser (rsdsfm_stabilize.h) neither zooms nor crops, so a stabilised frame has an empty band where the virtual camera sees what its own
  * frame does not, and the band moves from frame to frame.  Every frame's pose is in one coordinate system (rsdsfm_chain_clip), every pair
  * has a scale and a hole-free depth, and the stabiliser's map pass takes any rigid transform: frame n rendered into the virtual camera of
  * frame q is the stabiliser's stages A and B with

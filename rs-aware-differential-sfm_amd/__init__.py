@@ -1875,6 +1875,176 @@ for _name, _fn in list(vars(_StabilizeFillMixin).items()):
 
 
 # ---------------------------------------------------------------------------------------------------
+# the stabiliser's crop and zoom: one window for the clip, every frame rendered through it (include/rsdsfm_stabilize_crop.h)
+# ---------------------------------------------------------------------------------------------------
+STABILIZE_CROP_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "rsdsfm_stabilize_crop.h")
+
+
+class StabilizeCropParams(C.Structure):
+    _fields_ = [("max_empty", C.c_int64), ("margin", C.c_int32), ("struct_bytes", C.c_int32), ("reserved", C.c_int32 * 4)]
+
+
+def stabilize_crop_declared_symbols():
+    """Names of every function include/rsdsfm_stabilize_crop.h declares"""
+    import re
+
+    txt = open(STABILIZE_CROP_HEADER_PATH).read()
+    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
+    return sorted(set(re.findall(r"\b(rsdsfm_[a-z0-9_]+)\s*\(", txt)))
+
+
+def stabilize_crop_default_params():
+    """the crop's defaults as a dict: max_empty = 0, margin = 1 (rsdsfm_stabilize_crop_params_init)"""
+    p = StabilizeCropParams()
+    if load_library().rsdsfm_stabilize_crop_params_init(C.byref(p)) != OK:
+        raise RsdsfmError("rsdsfm_stabilize_crop_params_init failed")
+    return dict(max_empty=p.max_empty, margin=p.margin)
+
+
+def _stabilize_crop_params(max_empty, margin):
+    """a StabilizeCropParams with the given values over the defaults (margin None: the default)"""
+    p = StabilizeCropParams()
+    if load_library().rsdsfm_stabilize_crop_params_init(C.byref(p)) != OK:
+        raise RsdsfmError("rsdsfm_stabilize_crop_params_init failed")
+    p.max_empty = int(max_empty)
+    if margin is not None:
+        p.margin = int(margin)
+    return p
+
+
+def crop_window_launches(rows, cols):
+    """kernel launches of one crop_window_dev call: 3 (rsdsfm_crop_window_launches; host only)"""
+    n = load_library().rsdsfm_crop_window_launches(C.c_int32(rows), C.c_int32(cols))
+    if n < 0:
+        raise RsdsfmError("rsdsfm_crop_window_launches failed (%d): rows and cols must be in [2, 16384]" % n)
+    return n
+
+
+def stabilize_window_launches(rows, cols):
+    """kernel launches of one stabilize_window_frame_dev call at this size: stabilize_fill_launches (rsdsfm_stabilize_window_launches; host
+    only)"""
+    n = load_library().rsdsfm_stabilize_window_launches(C.c_int32(rows), C.c_int32(cols))
+    if n < 0:
+        raise RsdsfmError("rsdsfm_stabilize_window_launches failed (%d): rows and cols must be in [2, 16384]" % n)
+    return n
+
+
+def _window4(window):
+    return None if window is None else (C.c_int32 * 4)(*[int(x) for x in window])
+
+
+class _StabilizeCropMixin:
+    def crop_window_dev(self, d_masks, rows, cols, max_empty=0, margin=None):
+        """the clip's window (rsdsfm_crop_window_dev; tests/stabilize_crop_spec_numpy.py): d_masks, a list of device planes of rows x cols bytes
+        (0 = empty) -> (r0, c0, h, w): the largest rectangle of the frame's aspect ratio whose surroundings within `margin` pixels (None: the
+        default, 1) hold at most max_empty pixels empty in any plane, nearest the centre; (0, 0, 0, 0) when nothing fits.  Waits for the result."""
+        p = _stabilize_crop_params(max_empty, margin)
+        w = (C.c_int32 * 4)()
+        self._check(self.lib.rsdsfm_crop_window_dev(self._ctx, _ptr_array(d_masks), C.c_int32(len(d_masks)), C.c_int32(rows), C.c_int32(cols), C.byref(p), w),
+                    "rsdsfm_crop_window_dev")
+        return tuple(int(x) for x in w)
+
+    def crop_window(self, masks, max_empty=0, margin=None, device=0):
+        """host convenience around crop_window_dev: masks (planes, rows, cols) or a list of (rows, cols) uint8 arrays"""
+        import torch
+
+        m = np.ascontiguousarray(masks, dtype=np.uint8)
+        if m.ndim == 2:
+            m = m[None]
+        dev = torch.device("cuda", device)
+        with torch.cuda.device(dev):
+            planes = [torch.from_numpy(np.ascontiguousarray(x)).to(dev) for x in m]
+            torch.cuda.synchronize()
+            return self.crop_window_dev([t.data_ptr() for t in planes], m.shape[1], m.shape[2], max_empty, margin)
+
+    def stabilize_window_frame_dev(self, d_img_n, channels, d_depth_map_n, d_R_n, d_t_n, K, rows, cols, M, m, source_id, window, d_image, d_mask, d_source=None,
+                                   d_filled=None, mode=BACKPROJECT_RS, q5_mode=Q5_COMPAT, iterations=0):
+        """one frame through a window (rsdsfm_stabilize_window_frame_dev): stabilize_fill_frame_dev with output pixel g mapped into
+        window = (r0, c0, h, w) before stage C's fixed point, so that the full-size output shows the window, zoomed.  source_id 1 .. 255 (1: the
+        own frame, onto a zeroed mask).  Enqueued on the context's stream."""
+        d = C.c_double
+        Mh = None if M is None else _f64(M).reshape(9)
+        mh = None if m is None else _f64(m).reshape(3)
+        self._check(self.lib.rsdsfm_stabilize_window_frame_dev(self._ctx, _dp(d_img_n), C.c_int32(channels), _dp(d_depth_map_n), _dp(d_R_n), _dp(d_t_n), d(K[0]),
+                                                               d(K[1]), d(K[2]), d(K[3]), C.c_int32(rows), C.c_int32(cols), int(mode), int(q5_mode),
+                                                               C.c_int32(iterations), _p(Mh), _p(mh), C.c_int32(source_id), _window4(window), _dp(d_image),
+                                                               _dp(d_mask), _np0(d_source), _np0(d_filled)), "rsdsfm_stabilize_window_frame_dev")
+
+    def stabilize_cropped(self, images, depth_maps, Rs, ts, K, A, c, A_s, c_s, scales, q, M, m, window, radius=2, mode=BACKPROJECT_RS, q5_mode=Q5_COMPAT,
+                          iterations=0, device=0):
+        """host convenience: frame q of a clip rendered through `window` from its virtual camera (M, m: virtual_poses' entry q) onto zeroed
+        planes, then its neighbours (neighbour_poses with `radius`; 0: none), one stabilize_window_frame_dev each.  Arguments as
+        stabilize_filled.  Returns (image, mask, source (rows, cols) uint8, counts (2 + 2 radius,) int64: [none, own, -1, +1, -2, +2, ...])."""
+        import torch
+
+        frames, ids, nM, nm = neighbour_poses(A, c, A_s, c_s, scales, q, radius) if radius else ((), (), (), ())
+        rows, cols = np.asarray(images[q]).shape[:2]
+        dev = torch.device("cuda", device)
+        with torch.cuda.device(dev):
+            up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+
+            def frame(n):  # image, column-major depth map, pose table
+                img = np.ascontiguousarray(images[n], dtype=np.uint8)
+                return up(img), up(np.asarray(depth_maps[n], dtype=np.float64).T), up(_f64(np.asarray(Rs[n]).reshape(rows, 9))), up(_f64(ts[n]))
+
+            own = frame(q)
+            channels = 1 if own[0].ndim == 2 else own[0].shape[2]
+            d_out = torch.zeros_like(own[0])
+            d_mask, d_source = (torch.zeros((rows, cols), dtype=torch.uint8, device=dev) for _ in range(2))
+            d_cnt = torch.zeros(2 + 2 * radius, dtype=torch.int64, device=dev)
+            cand = [frame(int(n)) for n in frames]
+            torch.cuda.synchronize()
+            for (n_img, n_dm, n_R, n_t), sid, Mn, mn in zip([own] + cand, [1] + list(ids), [M] + list(nM), [m] + list(nm)):
+                self.stabilize_window_frame_dev(n_img.data_ptr(), channels, n_dm.data_ptr(), n_R.data_ptr(), n_t.data_ptr(), K, rows, cols, Mn, mn, int(sid), window,
+                                                d_out.data_ptr(), d_mask.data_ptr(), d_source.data_ptr(), d_cnt[int(sid):].data_ptr(), mode=mode, q5_mode=q5_mode,
+                                                iterations=iterations)
+            self.synchronize()
+            counts = d_cnt.cpu().numpy()
+            counts[0] = rows * cols - int(counts[1:].sum())
+            return d_out.cpu().numpy(), d_mask.cpu().numpy(), d_source.cpu().numpy(), counts
+
+    def stabilize_video_cropped_dev(self, d_frames, rows, cols, channels, K, gamma, d_depth_maps, d_flows, d_R, d_t, d_stab, d_masks_out, d_crop, d_crop_masks,
+                                    d_crop_sources=None, window_in=None, max_empty=0, margin=None, want_crop_counts=True, d_sources=None, fill_radius=2,
+                                    want_counts=True, d_fused=None, want_valid=True, sigma=None, radius=0, translation=True, fuse_tol=None, d_masks=None,
+                                    seeds=None, flow_params=None, a1=None, a2=None, link_tol=None, min_links=None, radix_bits=None, mode=BACKPROJECT_RS,
+                                    q5_mode=Q5_COMPAT, iterations=0, trials=50, tol=0.05, use_acceleration_mode=False, use_refinement=True,
+                                    depth_mode=DEPTH_CERES_LM, k_sign_mode=K_COMPAT, flow_threshold=1e-10, flow_index_mode=FLOW_COMPAT_RANK,
+                                    use_global_shutter_mode=False):
+        """the stabilised clip, cropped and zoomed, in ONE call (rsdsfm_stabilize_video_cropped_dev): stabilize_video_filled_dev with these
+        arguments (fill_radius 0 .. 16 HERE: 0 means no fill, the inner call is then stabilize_video_dev), the window of its output masks
+        (crop_window_dev with max_empty / margin; window_in = (r0, c0, h, w) skips the search) and, for every frame, the own frame and its
+        neighbours through that window (stabilize_window_frame_dev) into d_crop, d_crop_masks and d_crop_sources (F - 1 device buffers each,
+        zeroed first).  Returns the inner call's dict plus window and, with want_crop_counts, crop_counts ((F - 1, 2 + 2 fill_radius) int64:
+        [none, own, -1, +1, ...] per frame; the call then waits for the passes)."""
+        n = len(d_frames) - 1
+        fp = _stabilize_fill_params(fill_radius)
+        fp.radius = int(fill_radius)  # 0 stays 0 here
+        cp = _stabilize_crop_params(max_empty, margin)
+        width = 2 + 2 * int(fill_radius)
+        counts = np.zeros((max(n, 1), width), dtype=np.int64) if want_counts else None
+        crop_counts = np.zeros((max(n, 1), width), dtype=np.int64) if want_crop_counts else None
+        window = (C.c_int32 * 4)()
+        own = ("self", "n", "fp", "cp", "width", "counts", "crop_counts", "window", "d_sources", "fill_radius", "want_counts", "d_crop", "d_crop_masks",
+               "d_crop_sources", "window_in", "max_empty", "margin", "want_crop_counts")
+        args = {k_: v_ for k_, v_ in locals().items() if k_ not in own and k_ != "own"}
+        arr = lambda a: _ptr_array(a) if a is not None else None
+        out = self._stabilize_video("rsdsfm_stabilize_video_cropped_dev",
+                                    (C.byref(fp), arr(d_sources), _p(counts), C.byref(cp), _window4(window_in), arr(d_crop), arr(d_crop_masks), arr(d_crop_sources),
+                                     window, _p(crop_counts)), **args)
+        out["window"] = tuple(int(x) for x in window)
+        if want_counts:
+            out["counts"] = counts[:n]
+        if want_crop_counts:
+            out["crop_counts"] = crop_counts[:n]
+        return out
+
+
+for _name, _fn in list(vars(_StabilizeCropMixin).items()):
+    if not _name.startswith("__"):
+        setattr(Solver, _name, _fn)
+
+
+# ---------------------------------------------------------------------------------------------------
 # accuracy metrics (SURVEY 8 f-4)
 # ---------------------------------------------------------------------------------------------------
 class ReprojectionStats(C.Structure):

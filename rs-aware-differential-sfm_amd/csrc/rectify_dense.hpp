@@ -15,6 +15,7 @@ struct DenseWs {
     double* d_pyr = nullptr;  // levels 1 .. top, level after level, row-major
     float2* d_disp = nullptr; // rows x cols
     unsigned char* d_mask = nullptr;  // rows x cols: the stabiliser's mask when it counts without a caller's mask (made when first asked for)
+    void* d_crop = nullptr;           // the crop window's key, plane pointers and summed-area table (stabilize_crop.hpp; made when first asked for)
     int rows = 0, cols = 0;
 };
 

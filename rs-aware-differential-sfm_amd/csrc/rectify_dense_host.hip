@@ -11,9 +11,11 @@ static void dense_ws_free(DenseWs* w) {
     if (w->d_pyr) (void)hipFree(w->d_pyr);
     if (w->d_disp) (void)hipFree(w->d_disp);
     if (w->d_mask) (void)hipFree(w->d_mask);
+    if (w->d_crop) (void)hipFree(w->d_crop);
     w->d_pyr = nullptr;
     w->d_disp = nullptr;
     w->d_mask = nullptr;
+    w->d_crop = nullptr;
     w->rows = w->cols = 0;
 }
 

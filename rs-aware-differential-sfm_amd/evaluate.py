@@ -207,7 +207,7 @@ def _write_real_outputs(out_dir, image, flow, depth_est, backprojection, coords)
 def evaluate_real_sequence(solver, frames, camera="galaxy", gamma=0.95, out_dir=None, trials=5, seeds=None, tol=0.05, use_acceleration_mode=False,
                            use_refinement=True, use_global_shutter_mode=False, flow_threshold=1e-10, flow_index_mode=0, device=0, flow_params=None, dense=False,
                            check_flow=False, trajectory=False, link_tol=None, min_links=None, fuse=False, fuse_tol=None, stabilize=False, smooth_sigma=None,
-                           smooth_translation=True, fill=0):
+                           smooth_translation=True, fill=0, crop=False, crop_margin=None, crop_max_empty=0):
     """evaluate_real_run's real-world branch (main.cc:341-361, 364-531) for a clip: `frames` is <prefix>frame1.png ... frameN.png (the
     prefix, or a list of paths), or the frames themselves (an (N, rows, cols[, 3]) uint8 array or a list of arrays; 2-D frames are gray).
     By default ONE call does the clip (Solver.rectify_video_dev): the batched DeepFlow of every consecutive pair, the pipelined solve of every pair p
@@ -240,9 +240,17 @@ def evaluate_real_sequence(solver, frames, camera="galaxy", gamma=0.95, out_dir=
     mask, on the neighbour's map -- the FUSED one with fuse=True).  The returned dict then also has stab_filled (per pair, the frame's shape),
     stab_sources (per pair, (rows, cols) uint8: 0 nobody, 1 the own frame, 2 |j| / 2 |j| + 1 the frame j before / after) and fill_counts
     ((pairs, 2 + 2 K) int64: [none, own, -1, +1, -2, +2, ...]); out_dir receives stabilized_filled_<p>.png per pair and fill.csv (pair and the
-    counts).  Without fill every output is what it was."""
+    counts).  Without fill every output is what it was.
+    crop=True (needs stabilize=True: ValueError otherwise; with or without fill=K): ONE window for the clip (Solver.crop_window_dev with
+    crop_margin -- None: the default, 1 -- and crop_max_empty on the filled masks, or the stabilised ones without fill) and every frame rendered
+    through it at full size (Solver.stabilize_window_frame_dev: the own frame onto zeroed planes, then the K neighbours on each side).  The
+    returned dict then also has stab_cropped (per pair, the frame's shape), crop_window ((r0, c0, h, w); all 0: nothing fits, the frames are
+    then black) and crop_counts ((pairs, 2 + 2 K) int64, fill_counts' layout); out_dir receives stabilized_cropped_<p>.png per pair and crop.csv
+    (the window, then pair and the counts).  Without crop every output is what it was."""
     if fill and not stabilize:
         raise ValueError("fill needs stabilize=True: it fills the stabilised frames' borders")
+    if crop and not stabilize:
+        raise ValueError("crop needs stabilize=True: it crops the stabilised frames")
     if stabilize:
         trajectory = True
     if fuse and not trajectory:
@@ -379,6 +387,24 @@ def evaluate_real_sequence(solver, frames, camera="galaxy", gamma=0.95, out_dir=
                     counts = d_fcnt.cpu().numpy()
                     counts[:, 0] = rows * cols - counts[:, 1:].sum(axis=1)
                     traj.update(stab_filled=[t.cpu().numpy() for t in d_fills], stab_sources=[t.cpu().numpy() for t in d_sources], fill_counts=counts)
+                if crop:
+                    from . import neighbour_poses
+
+                    window = solver.crop_window_dev(ptrs(d_fmasks2 if fill else d_smasks), rows, cols, crop_max_empty, crop_margin)
+                    d_crops = [torch.zeros_like(t) for t in d_stabs]
+                    d_cmasks = [torch.zeros((rows, cols), dtype=torch.uint8, device=dev) for _ in range(npairs)]
+                    d_ccnt = torch.zeros((npairs, 2 + 2 * fill), dtype=torch.int64, device=dev)
+                    torch.cuda.synchronize()
+                    for p in range(npairs if window[2] else 0):  # every pass enqueued, one wait for all of them
+                        cand = [(p, 1, vM[p], vm[p])] + (list(zip(*neighbour_poses(traj["A"], traj["c"], A_s, c_s, traj["scales"], p, fill))) if fill else [])
+                        for n, sid, nM, nm in cand:
+                            solver.stabilize_window_frame_dev(d_imgs[n].data_ptr(), channels, d_src[n].data_ptr(), d_Rs[n].data_ptr(), d_ts[n].data_ptr(), K, rows,
+                                                              cols, nM, nm, int(sid), window, d_crops[p].data_ptr(), d_cmasks[p].data_ptr(), None,
+                                                              d_ccnt[p, int(sid):].data_ptr(), mode=mode)
+                    solver.synchronize()
+                    counts = d_ccnt.cpu().numpy()
+                    counts[:, 0] = rows * cols - counts[:, 1:].sum(axis=1)
+                    traj.update(stab_cropped=[t.cpu().numpy() for t in d_crops], crop_window=window, crop_counts=counts)
     if out_dir:
         os.makedirs(out_dir, exist_ok=True)
         lines = ["pair,v_x,v_y,v_z,w_x,w_y,w_z,k,inliers"]
@@ -430,6 +456,14 @@ def evaluate_real_sequence(solver, frames, camera="galaxy", gamma=0.95, out_dir=
                 formats.write_png(os.path.join(out_dir, "stabilized_filled_%d.png" % p), traj["stab_filled"][p])
                 rows_.append(",".join([str(p)] + [str(int(x)) for x in traj["fill_counts"][p]]))
             with open(os.path.join(out_dir, "fill.csv"), "w") as fh:
+                fh.write("\n".join(rows_) + "\n")
+        if crop:
+            names = ["none", "own"] + ["%s%d" % (sg, j) for j in range(1, fill + 1) for sg in ("prev", "next")]
+            rows_ = ["window," + ",".join(str(x) for x in traj["crop_window"]), "pair," + ",".join(names)]
+            for p in range(npairs):
+                formats.write_png(os.path.join(out_dir, "stabilized_cropped_%d.png" % p), traj["stab_cropped"][p])
+                rows_.append(",".join([str(p)] + [str(int(x)) for x in traj["crop_counts"][p]]))
+            with open(os.path.join(out_dir, "crop.csv"), "w") as fh:
                 fh.write("\n".join(rows_) + "\n")
     if trajectory:
         return dict(traj, pairs=outs)
