@@ -2045,6 +2045,161 @@ for _name, _fn in list(vars(_StabilizeCropMixin).items()):
 
 
 # ---------------------------------------------------------------------------------------------------
+# the stabiliser's seam blend: a gain per candidate and a feather next to the own frame's empty band (include/rsdsfm_stabilize_blend.h)
+# ---------------------------------------------------------------------------------------------------
+STABILIZE_BLEND_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "rsdsfm_stabilize_blend.h")
+GAIN_ONE = 65536
+
+
+class StabilizeBlendParams(C.Structure):
+    _fields_ = [("min_overlap", C.c_int64), ("feather", C.c_int32), ("gain_mode", C.c_int32), ("struct_bytes", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
+def stabilize_blend_declared_symbols():
+    """Names of every function include/rsdsfm_stabilize_blend.h declares"""
+    import re
+
+    txt = open(STABILIZE_BLEND_HEADER_PATH).read()
+    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
+    return sorted(set(re.findall(r"\b(rsdsfm_[a-z0-9_]+)\s*\(", txt)))
+
+
+def stabilize_blend_default_params():
+    """the blend's defaults as a dict: feather = 16, gain_mode = 0, min_overlap = 1024 (rsdsfm_stabilize_blend_params_init)"""
+    p = StabilizeBlendParams()
+    if load_library().rsdsfm_stabilize_blend_params_init(C.byref(p)) != OK:
+        raise RsdsfmError("rsdsfm_stabilize_blend_params_init failed")
+    return dict(feather=p.feather, gain_mode=p.gain_mode, min_overlap=p.min_overlap)
+
+
+def _stabilize_blend_params(feather, gain, min_overlap):
+    """a StabilizeBlendParams with the given values over the defaults (feather / min_overlap None or 0: the default; gain False: off)"""
+    p = StabilizeBlendParams()
+    if load_library().rsdsfm_stabilize_blend_params_init(C.byref(p)) != OK:
+        raise RsdsfmError("rsdsfm_stabilize_blend_params_init failed")
+    if feather:
+        p.feather = int(feather)
+    if min_overlap:
+        p.min_overlap = int(min_overlap)
+    p.gain_mode = 0 if gain else 1
+    return p
+
+
+def seam_gains(sums, channels, min_overlap=0, gain_mode=0):
+    """the gains of one 8-word record of seam_blend_layer_dev, with the kernel's integer arithmetic (rsdsfm_seam_gains; host only): (3,)
+    uint32 in 1 / 65536, 65536 for a channel >= channels.  min_overlap 0: the default, 1024."""
+    s = np.ascontiguousarray(sums, dtype=np.uint64).reshape(-1)
+    if s.shape[0] != 8:
+        raise ValueError("a record has 8 values")
+    g = np.zeros(3, dtype=np.uint32)
+    rc = load_library().rsdsfm_seam_gains(_p(s), C.c_int32(channels), C.c_int64(min_overlap), C.c_int32(gain_mode), _p(g))
+    if rc != OK:
+        raise RsdsfmError("rsdsfm_seam_gains failed (%d): channels 1 or 3, min_overlap >= 0, gain_mode 0 or 1" % rc)
+    return g
+
+
+def seam_distance_launches(rows, cols):
+    """kernel launches of one seam_distance_dev call: 2 (rsdsfm_seam_distance_launches; host only)"""
+    n = load_library().rsdsfm_seam_distance_launches(C.c_int32(rows), C.c_int32(cols))
+    if n < 0:
+        raise RsdsfmError("rsdsfm_seam_distance_launches failed (%d): rows and cols must be in [2, 16384]" % n)
+    return n
+
+
+def seam_blend_layer_launches(rows, cols):
+    """kernel launches of one seam_blend_layer_dev call: 2 (rsdsfm_seam_blend_layer_launches; host only)"""
+    n = load_library().rsdsfm_seam_blend_layer_launches(C.c_int32(rows), C.c_int32(cols))
+    if n < 0:
+        raise RsdsfmError("rsdsfm_seam_blend_layer_launches failed (%d): rows and cols must be in [2, 16384]" % n)
+    return n
+
+
+class _StabilizeBlendMixin:
+    def seam_distance_dev(self, d_mask, rows, cols, feather, d_dist):
+        """the seam distance of a device mask into a device plane of bytes (rsdsfm_seam_distance_dev; tests/stabilize_blend_spec_numpy.py): 0 on
+        an empty pixel, else min(feather, chessboard distance to the nearest empty pixel of the frame); feather 1 .. 64 (0: 16).  Enqueued on
+        the context's stream."""
+        self._check(self.lib.rsdsfm_seam_distance_dev(self._ctx, _dp(d_mask), C.c_int32(rows), C.c_int32(cols), C.c_int32(feather), _dp(d_dist)),
+                    "rsdsfm_seam_distance_dev")
+
+    def seam_distance(self, mask, feather=0, device=0):
+        """host convenience around seam_distance_dev: mask (rows, cols) uint8 -> the distance plane (rows, cols) uint8"""
+        import torch
+
+        m = np.ascontiguousarray(mask, dtype=np.uint8)
+        dev = torch.device("cuda", device)
+        with torch.cuda.device(dev):
+            d_m = torch.from_numpy(m).to(dev)
+            d_d = torch.empty_like(d_m)
+            torch.cuda.synchronize()
+            self.seam_distance_dev(d_m.data_ptr(), m.shape[0], m.shape[1], feather, d_d.data_ptr())
+            self.synchronize()
+            return d_d.cpu().numpy()
+
+    def seam_blend_layer_dev(self, d_layer_image, d_layer_mask, channels, rows, cols, d_dist, source_id, d_image, d_mask, d_source, d_sums, d_counts=None, feather=None,
+                             gain=True, min_overlap=None):
+        """one candidate's layer onto the in-out planes (rsdsfm_seam_blend_layer_dev): the sums over the pixels the layer shares with the own
+        frame (source 1) into d_sums (8 device uint64), one gain per channel from them (gain=False: none), then every pixel of the layer
+        copied where source is 0 and mixed where source is 1 and d_dist (seam_distance_dev's plane for the same feather) is below feather.
+        d_counts: 2 device int64 that receive [filled, blended].  source_id 2 .. 255.  Enqueued on the context's stream."""
+        p = _stabilize_blend_params(feather, gain, min_overlap)
+        self._check(self.lib.rsdsfm_seam_blend_layer_dev(self._ctx, _dp(d_layer_image), _dp(d_layer_mask), C.c_int32(channels), C.c_int32(rows), C.c_int32(cols),
+                                                         _dp(d_dist), C.byref(p), C.c_int32(source_id), _dp(d_image), _dp(d_mask), _dp(d_source), _dp(d_sums),
+                                                         _np0(d_counts)), "rsdsfm_seam_blend_layer_dev")
+
+    def stabilize_video_blended_dev(self, d_frames, rows, cols, channels, K, gamma, d_depth_maps, d_flows, d_R, d_t, d_stab, d_masks_out, d_crop, d_crop_masks,
+                                    d_blend, d_blend_masks, d_blend_sources, blend_feather=None, blend_gain=True, blend_min_overlap=None, want_gains=True,
+                                    want_blend_counts=True, d_crop_sources=None, window_in=None, max_empty=0, margin=None, want_crop_counts=True, d_sources=None,
+                                    fill_radius=2, want_counts=True, d_fused=None, want_valid=True, sigma=None, radius=0, translation=True, fuse_tol=None,
+                                    d_masks=None, seeds=None, flow_params=None, a1=None, a2=None, link_tol=None, min_links=None, radix_bits=None,
+                                    mode=BACKPROJECT_RS, q5_mode=Q5_COMPAT, iterations=0, trials=50, tol=0.05, use_acceleration_mode=False, use_refinement=True,
+                                    depth_mode=DEPTH_CERES_LM, k_sign_mode=K_COMPAT, flow_threshold=1e-10, flow_index_mode=FLOW_COMPAT_RANK,
+                                    use_global_shutter_mode=False):
+        """the stabilised clip, cropped, zoomed and blended, in ONE call (rsdsfm_stabilize_video_blended_dev): stabilize_video_cropped_dev with
+        these arguments, then for every frame the own frame through the window into d_blend, d_blend_masks and d_blend_sources (F - 1 device
+        buffers each, zeroed first), seam_distance_dev of its mask and, per neighbour, the neighbour alone on the context's layer and
+        seam_blend_layer_dev (blend_feather None: 16; blend_gain False: no gain; blend_min_overlap None: 1024).  To blend without cropping pass
+        window_in = (0, 0, rows, cols).  Returns stabilize_video_cropped_dev's dict plus, with want_gains, gains ((F - 1, 2 fill_radius, 3)
+        uint32 in 1 / 65536, per offset -1, +1, -2, +2, ...) and, with want_blend_counts, blend_counts ((F - 1, 2 + 4 fill_radius) int64:
+        [none, own_untouched, (filled, blended) per offset]); with either the call waits for the passes."""
+        n = len(d_frames) - 1
+        fp = _stabilize_fill_params(fill_radius)
+        fp.radius = int(fill_radius)  # 0 stays 0 here
+        cp = _stabilize_crop_params(max_empty, margin)
+        bp = _stabilize_blend_params(blend_feather, blend_gain, blend_min_overlap)
+        width = 2 + 2 * int(fill_radius)
+        counts = np.zeros((max(n, 1), width), dtype=np.int64) if want_counts else None
+        crop_counts = np.zeros((max(n, 1), width), dtype=np.int64) if want_crop_counts else None
+        gains = np.zeros((max(n, 1), max(2 * int(fill_radius), 1), 3), dtype=np.uint32) if want_gains else None
+        blend_counts = np.zeros((max(n, 1), 2 + 4 * int(fill_radius)), dtype=np.int64) if want_blend_counts else None
+        window = (C.c_int32 * 4)()
+        own = ("self", "n", "fp", "cp", "bp", "width", "counts", "crop_counts", "gains", "blend_counts", "window", "d_sources", "fill_radius", "want_counts", "d_crop",
+               "d_crop_masks", "d_crop_sources", "window_in", "max_empty", "margin", "want_crop_counts", "d_blend", "d_blend_masks", "d_blend_sources",
+               "blend_feather", "blend_gain", "blend_min_overlap", "want_gains", "want_blend_counts")
+        args = {k_: v_ for k_, v_ in locals().items() if k_ not in own and k_ != "own"}
+        arr = lambda a: _ptr_array(a) if a is not None else None
+        out = self._stabilize_video("rsdsfm_stabilize_video_blended_dev",
+                                    (C.byref(fp), arr(d_sources), _p(counts), C.byref(cp), _window4(window_in), arr(d_crop), arr(d_crop_masks), arr(d_crop_sources),
+                                     window, _p(crop_counts), C.byref(bp), arr(d_blend), arr(d_blend_masks), arr(d_blend_sources), _p(gains), _p(blend_counts)),
+                                    **args)
+        out["window"] = tuple(int(x) for x in window)
+        if want_counts:
+            out["counts"] = counts[:n]
+        if want_crop_counts:
+            out["crop_counts"] = crop_counts[:n]
+        if want_gains:
+            out["gains"] = gains[:n, :2 * int(fill_radius)]
+        if want_blend_counts:
+            out["blend_counts"] = blend_counts[:n]
+        return out
+
+
+for _name, _fn in list(vars(_StabilizeBlendMixin).items()):
+    if not _name.startswith("__"):
+        setattr(Solver, _name, _fn)
+
+
+# ---------------------------------------------------------------------------------------------------
 # accuracy metrics (SURVEY 8 f-4)
 # ---------------------------------------------------------------------------------------------------
 class ReprojectionStats(C.Structure):

@@ -16,6 +16,8 @@ struct DenseWs {
     float2* d_disp = nullptr; // rows x cols
     unsigned char* d_mask = nullptr;  // rows x cols: the stabiliser's mask when it counts without a caller's mask (made when first asked for)
     void* d_crop = nullptr;           // the crop window's key, plane pointers and summed-area table (stabilize_crop.hpp; made when first asked for)
+    unsigned char* d_seam = nullptr;  // rows x cols: the seam distance's row pass (stabilize_blend.hpp; made when first asked for)
+    unsigned char* d_layer = nullptr; // the blended clip's distance plane, layer mask and layer image, 5 planes (stabilize_blend.hpp; made when first asked for)
     int rows = 0, cols = 0;
 };
 

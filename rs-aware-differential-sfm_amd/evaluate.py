@@ -207,7 +207,8 @@ def _write_real_outputs(out_dir, image, flow, depth_est, backprojection, coords)
 def evaluate_real_sequence(solver, frames, camera="galaxy", gamma=0.95, out_dir=None, trials=5, seeds=None, tol=0.05, use_acceleration_mode=False,
                            use_refinement=True, use_global_shutter_mode=False, flow_threshold=1e-10, flow_index_mode=0, device=0, flow_params=None, dense=False,
                            check_flow=False, trajectory=False, link_tol=None, min_links=None, fuse=False, fuse_tol=None, stabilize=False, smooth_sigma=None,
-                           smooth_translation=True, fill=0, crop=False, crop_margin=None, crop_max_empty=0):
+                           smooth_translation=True, fill=0, crop=False, crop_margin=None, crop_max_empty=0, blend=False, blend_feather=None,
+                           blend_gain=True):
     """evaluate_real_run's real-world branch (main.cc:341-361, 364-531) for a clip: `frames` is <prefix>frame1.png ... frameN.png (the
     prefix, or a list of paths), or the frames themselves (an (N, rows, cols[, 3]) uint8 array or a list of arrays; 2-D frames are gray).
     By default ONE call does the clip (Solver.rectify_video_dev): the batched DeepFlow of every consecutive pair, the pipelined solve of every pair p
@@ -246,7 +247,17 @@ def evaluate_real_sequence(solver, frames, camera="galaxy", gamma=0.95, out_dir=
     through it at full size (Solver.stabilize_window_frame_dev: the own frame onto zeroed planes, then the K neighbours on each side).  The
     returned dict then also has stab_cropped (per pair, the frame's shape), crop_window ((r0, c0, h, w); all 0: nothing fits, the frames are
     then black) and crop_counts ((pairs, 2 + 2 K) int64, fill_counts' layout); out_dir receives stabilized_cropped_<p>.png per pair and crop.csv
-    (the window, then pair and the counts).  Without crop every output is what it was."""
+    (the window, then pair and the counts).  Without crop every output is what it was.
+    blend=True (needs stabilize=True and fill >= 1: ValueError otherwise): every frame once more through the crop's window (crop=True) or the
+    full frame, with its seams blended (tests/stabilize_blend_spec_numpy.py): the own frame onto zeroed planes, Solver.seam_distance_dev of its
+    mask with blend_feather pixels (None: the default, 16), then every neighbour rendered alone onto a layer and Solver.seam_blend_layer_dev
+    (a gain per channel from the overlap unless blend_gain=False, the layer copied where nobody is and mixed over the feather).  The returned
+    dict then also has stab_blended (per pair, the frame's shape), blend_gains ((pairs, 2 K, 3) uint32 in 1 / 65536, per offset -1, +1, -2,
+    +2, ...; 65536 for a skipped offset or an unused channel) and blend_counts ((pairs, 2 + 4 K) int64: [none, own_untouched, (filled,
+    blended) per offset]); out_dir receives stabilized_blended_<p>.png per pair and blend.csv (pair, the counts, the gains).  Without blend
+    every output is what it was."""
+    if blend and not (stabilize and fill >= 1):
+        raise ValueError("blend needs stabilize=True and fill >= 1: it blends the seams between a stabilised frame and its neighbours")
     if fill and not stabilize:
         raise ValueError("fill needs stabilize=True: it fills the stabilised frames' borders")
     if crop and not stabilize:
@@ -405,6 +416,45 @@ def evaluate_real_sequence(solver, frames, camera="galaxy", gamma=0.95, out_dir=
                     counts = d_ccnt.cpu().numpy()
                     counts[:, 0] = rows * cols - counts[:, 1:].sum(axis=1)
                     traj.update(stab_cropped=[t.cpu().numpy() for t in d_crops], crop_window=window, crop_counts=counts)
+                if blend:
+                    from . import GAIN_ONE, neighbour_poses, seam_gains
+
+                    bwindow = traj["crop_window"] if crop else (0, 0, rows, cols)
+                    d_blends = [torch.zeros_like(t) for t in d_stabs]
+                    d_bmasks = [torch.zeros((rows, cols), dtype=torch.uint8, device=dev) for _ in range(npairs)]
+                    d_bsources = [torch.zeros((rows, cols), dtype=torch.uint8, device=dev) for _ in range(npairs)]
+                    d_dist = torch.zeros((rows, cols), dtype=torch.uint8, device=dev)
+                    d_layers = [torch.zeros_like(d_stabs[0]) for _ in range(2 * fill)]  # one per candidate of a frame, zeroed again per frame
+                    d_lmasks = [torch.zeros((rows, cols), dtype=torch.uint8, device=dev) for _ in range(2 * fill)]
+                    d_sums = torch.zeros((npairs, 2 * fill, 8), dtype=torch.int64, device=dev)  # (the records' 64-bit words)
+                    d_bcnt = torch.zeros((npairs, 2 * fill, 2), dtype=torch.int64, device=dev)
+                    d_own = torch.zeros(npairs, dtype=torch.int64, device=dev)
+                    torch.cuda.synchronize()
+                    for p in range(npairs if bwindow[2] else 0):  # a frame's passes enqueued on the solver's stream, one wait per frame
+                        if p:
+                            for t in d_layers + d_lmasks:
+                                t.zero_()
+                            torch.cuda.synchronize()
+                        solver.stabilize_window_frame_dev(d_imgs[p].data_ptr(), channels, d_src[p].data_ptr(), d_Rs[p].data_ptr(), d_ts[p].data_ptr(), K, rows, cols,
+                                                          vM[p], vm[p], 1, bwindow, d_blends[p].data_ptr(), d_bmasks[p].data_ptr(), d_bsources[p].data_ptr(),
+                                                          d_own[p:].data_ptr(), mode=mode)
+                        solver.seam_distance_dev(d_bmasks[p].data_ptr(), rows, cols, blend_feather or 0, d_dist.data_ptr())
+                        for n, sid, nM, nm in zip(*neighbour_poses(traj["A"], traj["c"], A_s, c_s, traj["scales"], p, fill)):
+                            d_layer, d_lmask = d_layers[int(sid) - 2], d_lmasks[int(sid) - 2]
+                            solver.stabilize_window_frame_dev(d_imgs[n].data_ptr(), channels, d_src[n].data_ptr(), d_Rs[n].data_ptr(), d_ts[n].data_ptr(), K, rows,
+                                                              cols, nM, nm, int(sid), bwindow, d_layer.data_ptr(), d_lmask.data_ptr(), None, None, mode=mode)
+                            solver.seam_blend_layer_dev(d_layer.data_ptr(), d_lmask.data_ptr(), channels, rows, cols, d_dist.data_ptr(), int(sid),
+                                                        d_blends[p].data_ptr(), d_bmasks[p].data_ptr(), d_bsources[p].data_ptr(), d_sums[p, int(sid) - 2].data_ptr(),
+                                                        d_bcnt[p, int(sid) - 2].data_ptr(), feather=blend_feather, gain=blend_gain)
+                        solver.synchronize()
+                    sums, per, own = d_sums.cpu().numpy().view(np.uint64), d_bcnt.cpu().numpy(), d_own.cpu().numpy()
+                    gains = np.full((npairs, 2 * fill, 3), GAIN_ONE, dtype=np.uint32)
+                    for p in range(npairs):
+                        for k_ in range(2 * fill):
+                            gains[p, k_] = seam_gains(sums[p, k_], channels, 0, 0 if blend_gain else 1)
+                    counts = np.concatenate([(rows * cols - own - per[:, :, 0].sum(axis=1))[:, None], (own - per[:, :, 1].sum(axis=1))[:, None],
+                                             per.reshape(npairs, -1)], axis=1)
+                    traj.update(stab_blended=[t.cpu().numpy() for t in d_blends], blend_gains=gains, blend_counts=counts)
     if out_dir:
         os.makedirs(out_dir, exist_ok=True)
         lines = ["pair,v_x,v_y,v_z,w_x,w_y,w_z,k,inliers"]
@@ -464,6 +514,15 @@ def evaluate_real_sequence(solver, frames, camera="galaxy", gamma=0.95, out_dir=
                 formats.write_png(os.path.join(out_dir, "stabilized_cropped_%d.png" % p), traj["stab_cropped"][p])
                 rows_.append(",".join([str(p)] + [str(int(x)) for x in traj["crop_counts"][p]]))
             with open(os.path.join(out_dir, "crop.csv"), "w") as fh:
+                fh.write("\n".join(rows_) + "\n")
+        if blend:
+            offs = ["%s%d" % (sg, j) for j in range(1, fill + 1) for sg in ("prev", "next")]
+            names = ["none", "own_untouched"] + [o + "_" + w for o in offs for w in ("filled", "blended")] + ["gain_%s_%d" % (o, c_) for o in offs for c_ in range(3)]
+            rows_ = ["pair," + ",".join(names)]
+            for p in range(npairs):
+                formats.write_png(os.path.join(out_dir, "stabilized_blended_%d.png" % p), traj["stab_blended"][p])
+                rows_.append(",".join([str(p)] + [str(int(x)) for x in traj["blend_counts"][p]] + [str(int(x)) for x in traj["blend_gains"][p].reshape(-1)]))
+            with open(os.path.join(out_dir, "blend.csv"), "w") as fh:
                 fh.write("\n".join(rows_) + "\n")
     if trajectory:
         return dict(traj, pairs=outs)

@@ -223,23 +223,34 @@ def render_occluded_pair(rows, cols, K, v, w, k=0.0, gamma=0.8, seed=0x5EED0000,
     return img1, img2, covered & ~block_plane, block_plane
 
 
-def render_sequence(nframes, rows, cols, K, v, w, k=0.0, gamma=0.8, seed=0x5EED0000, speeds=None):
+def _exposed(texture, gain):
+    """one frame's bytes: the texture rounded, or with an exposure factor clip(rint(gain texture))"""
+    if gain is None:
+        return np.rint(texture).astype(np.uint8)
+    return np.clip(np.rint(float(gain) * texture), 0, 255).astype(np.uint8)
+
+
+def render_sequence(nframes, rows, cols, K, v, w, k=0.0, gamma=0.8, seed=0x5EED0000, speeds=None, gains=None):
     """nframes 8-bit BGR frames of render_pair's texture under a constant motion: frame j at pixel q shows T(inv^j(q)), where inv is
     render_pair's fixed-point inverse of the model flow F (p + F(p) = q), applied j times from the pixel grid.  Every consecutive pair
     (j, j + 1) therefore has the true flow F and the true (v, w, k); render_pair's border mask.  nframes = 2 gives render_pair's two
     frames bit for bit.  Returns (frames (nframes, rows, cols, 3) uint8, F (rows, cols, 2), mask).
     speeds: one factor per pair on v (nframes - 1 of them): pair j moves with (speeds[j] v, w, k) and has the model flow F_j of that
     motion; F is then (nframes - 1, rows, cols, 2) and the band of the mask is the widest pair's.  None: the frames of a constant motion,
-    byte for byte what this function returned before it had the argument."""
+    byte for byte what this function returned before it had the argument.
+    gains: one exposure factor per frame (nframes of them): frame j = clip(rint(gains[j] texture)); the geometry is unchanged.  None: byte
+    for byte what this function returns without the argument."""
     if nframes < 2:
         raise ValueError("a sequence has at least two frames")
+    if gains is not None and len(gains) != nframes:
+        raise ValueError("gains needs one factor per frame (nframes)")
     if speeds is not None:
-        return _render_sequence_speeds(nframes, rows, cols, K, v, w, k, gamma, seed, speeds)
+        return _render_sequence_speeds(nframes, rows, cols, K, v, w, k, gamma, seed, speeds, gains)
     flow, _ = make_flow(rows, cols, K, v, w, k, gamma, _model_only=True)
     yy, xx = np.mgrid[0:rows, 0:cols].astype(np.float64)
-    frames = [np.rint(_texture(xx, yy, seed)).astype(np.uint8)]
+    frames = [_exposed(_texture(xx, yy, seed), None if gains is None else gains[0])]
     qx, qy = xx, yy
-    for _ in range(1, nframes):
+    for j in range(1, nframes):
         px, py = qx.copy(), qy.copy()
         for _ in range(50):  # render_pair's iteration, from the previous frame's positions
             F = _bilinear(flow, px, py)
@@ -249,21 +260,21 @@ def render_sequence(nframes, rows, cols, K, v, w, k=0.0, gamma=0.8, seed=0x5EED0
             if done:
                 break
         qx, qy = px, py
-        frames.append(np.rint(_texture(qx, qy, seed)).astype(np.uint8))
+        frames.append(_exposed(_texture(qx, qy, seed), None if gains is None else gains[j]))
     band = int(np.ceil(np.abs(flow).max())) + 5
     mask = np.zeros((rows, cols), dtype=bool)
     mask[band:rows - band, band:cols - band] = True
     return np.stack(frames), np.ascontiguousarray(flow), mask
 
 
-def _render_sequence_speeds(nframes, rows, cols, K, v, w, k, gamma, seed, speeds):
+def _render_sequence_speeds(nframes, rows, cols, K, v, w, k, gamma, seed, speeds, gains=None):
     """render_sequence with one speed factor per pair: its loop, with the model flow of pair j - 1 in step j"""
     speeds = [float(s_) for s_ in speeds]
     if len(speeds) != nframes - 1:
         raise ValueError("speeds needs one factor per pair (nframes - 1)")
     flows = [make_flow(rows, cols, K, s_ * np.asarray(v, dtype=np.float64), w, k, gamma, _model_only=True)[0] for s_ in speeds]
     yy, xx = np.mgrid[0:rows, 0:cols].astype(np.float64)
-    frames = [np.rint(_texture(xx, yy, seed)).astype(np.uint8)]
+    frames = [_exposed(_texture(xx, yy, seed), None if gains is None else gains[0])]
     qx, qy = xx, yy
     for j in range(1, nframes):
         flow = flows[j - 1]
@@ -276,7 +287,7 @@ def _render_sequence_speeds(nframes, rows, cols, K, v, w, k, gamma, seed, speeds
             if done:
                 break
         qx, qy = px, py
-        frames.append(np.rint(_texture(qx, qy, seed)).astype(np.uint8))
+        frames.append(_exposed(_texture(qx, qy, seed), None if gains is None else gains[j]))
     band = int(np.ceil(max(np.abs(f).max() for f in flows))) + 5
     mask = np.zeros((rows, cols), dtype=bool)
     mask[band:rows - band, band:cols - band] = True
