@@ -23,7 +23,8 @@
  * and what has been measured.
  *
  * NOT here: feathering between two neighbours' regions, multi-band blending, gains smoothed over time or solved jointly over the clip,
- * vignetting, occlusion tests between candidates, the clip's last frame.
+ * vignetting, occlusion tests between candidates, the clip's last frame, inpainting of pixels nobody saw (built since:
+ * rsdsfm_stabilize_inpaint.h).
  */
 #ifndef RSDSFM_STABILIZE_BLEND_H
 #define RSDSFM_STABILIZE_BLEND_H

@@ -17,7 +17,8 @@
  * DESIGN.md section 12 ("Border fill") has the launches, the bytes and what has been measured.
  *
  * NOT here: blending or feathering at the seams, exposure compensation between frames, occlusion tests between candidates (a fold of a
- * neighbour's map fills like any pixel), moving objects, the clip's last frame, inpainting of pixels nobody saw.
+ * neighbour's map fills like any pixel), moving objects, the clip's last frame, inpainting of pixels nobody saw (built since:
+ * rsdsfm_stabilize_inpaint.h).
  */
 #ifndef RSDSFM_STABILIZE_FILL_H
 #define RSDSFM_STABILIZE_FILL_H

@@ -2200,6 +2200,110 @@ for _name, _fn in list(vars(_StabilizeBlendMixin).items()):
 
 
 # ---------------------------------------------------------------------------------------------------
+# the stabiliser's inpainting: the pixels no frame saw, from an integer pull-push pyramid (include/rsdsfm_stabilize_inpaint.h)
+# ---------------------------------------------------------------------------------------------------
+STABILIZE_INPAINT_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "rsdsfm_stabilize_inpaint.h")
+INPAINT_SOURCE = 255  # RSDSFM_SOURCE_INPAINTED
+
+
+def stabilize_inpaint_declared_symbols():
+    """Names of every function include/rsdsfm_stabilize_inpaint.h declares"""
+    import re
+
+    txt = open(STABILIZE_INPAINT_HEADER_PATH).read()
+    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
+    return sorted(set(re.findall(r"\b(rsdsfm_[a-z0-9_]+)\s*\(", txt)))
+
+
+def inpaint_launches(rows, cols):
+    """kernel launches of one inpaint_frame_dev call: 3 for a small frame, 8 at 1280 x 720 (rsdsfm_inpaint_launches; host only)"""
+    n = load_library().rsdsfm_inpaint_launches(C.c_int32(rows), C.c_int32(cols))
+    if n < 0:
+        raise RsdsfmError("rsdsfm_inpaint_launches failed (%d): rows and cols must be in [2, 16384]" % n)
+    return n
+
+
+class _StabilizeInpaintMixin:
+    def inpaint_frame_dev(self, d_image, d_mask, channels, rows, cols, d_source=None, d_count=None):
+        """the empty pixels (d_mask byte 0; only read) of the device image filled from an integer pull-push pyramid of the set ones
+        (rsdsfm_inpaint_frame_dev; tests/stabilize_inpaint_spec_numpy.py).  d_source: a device plane of rows x cols bytes that receives
+        INPAINT_SOURCE where a pixel was written; d_count: one device int64 that receives their number.  Enqueued on the context's stream."""
+        self._check(self.lib.rsdsfm_inpaint_frame_dev(self._ctx, _dp(d_image), _dp(d_mask), C.c_int32(channels), C.c_int32(rows), C.c_int32(cols), _np0(d_source),
+                                                      _np0(d_count)), "rsdsfm_inpaint_frame_dev")
+
+    def inpaint(self, image, mask, device=0):
+        """host convenience around inpaint_frame_dev: image (rows, cols) or (rows, cols, 3) uint8 and mask (rows, cols) uint8 (0 = empty) ->
+        (image, source (rows, cols) uint8: INPAINT_SOURCE where a pixel was written and 0 elsewhere, count)"""
+        import torch
+
+        img = np.ascontiguousarray(image, dtype=np.uint8)
+        m = np.ascontiguousarray(mask, dtype=np.uint8)
+        if img.shape[:2] != m.shape or m.ndim != 2:
+            raise ValueError("image (rows, cols[, channels]) and mask (rows, cols)")
+        dev = torch.device("cuda", device)
+        with torch.cuda.device(dev):
+            d_img, d_m = torch.from_numpy(img).to(dev), torch.from_numpy(m).to(dev)
+            d_src, d_cnt = torch.zeros_like(d_m), torch.zeros(1, dtype=torch.int64, device=dev)
+            torch.cuda.synchronize()
+            self.inpaint_frame_dev(d_img.data_ptr(), d_m.data_ptr(), 1 if img.ndim == 2 else img.shape[2], m.shape[0], m.shape[1], d_src.data_ptr(), d_cnt.data_ptr())
+            self.synchronize()
+            return d_img.cpu().numpy(), d_src.cpu().numpy(), int(d_cnt.cpu()[0])
+
+    def stabilize_video_inpainted_dev(self, d_frames, rows, cols, channels, K, gamma, d_depth_maps, d_flows, d_R, d_t, d_stab, d_masks_out, d_crop, d_crop_masks,
+                                      d_blend, d_blend_masks, d_blend_sources, d_inpaint, d_inpaint_sources=None, want_inpaint_counts=True, blend_feather=None,
+                                      blend_gain=True, blend_min_overlap=None, want_gains=True, want_blend_counts=True, d_crop_sources=None, window_in=None,
+                                      max_empty=0, margin=None, want_crop_counts=True, d_sources=None, fill_radius=2, want_counts=True, d_fused=None,
+                                      want_valid=True, sigma=None, radius=0, translation=True, fuse_tol=None, d_masks=None, seeds=None, flow_params=None, a1=None,
+                                      a2=None, link_tol=None, min_links=None, radix_bits=None, mode=BACKPROJECT_RS, q5_mode=Q5_COMPAT, iterations=0, trials=50,
+                                      tol=0.05, use_acceleration_mode=False, use_refinement=True, depth_mode=DEPTH_CERES_LM, k_sign_mode=K_COMPAT,
+                                      flow_threshold=1e-10, flow_index_mode=FLOW_COMPAT_RANK, use_global_shutter_mode=False):
+        """the stabilised clip, cropped, zoomed, blended and inpainted, in ONE call (rsdsfm_stabilize_video_inpainted_dev):
+        stabilize_video_blended_dev with these arguments, then for every frame d_blend copied to d_inpaint (and d_blend_sources to
+        d_inpaint_sources when passed; F - 1 device buffers each) and inpaint_frame_dev on the copy with the frame's blend mask.  Returns
+        stabilize_video_blended_dev's dict plus, with want_inpaint_counts, inpaint_counts ((F - 1,) int64: the pixels written per frame; the
+        call then waits for the passes)."""
+        n = len(d_frames) - 1
+        fp = _stabilize_fill_params(fill_radius)
+        fp.radius = int(fill_radius)  # 0 stays 0 here
+        cp = _stabilize_crop_params(max_empty, margin)
+        bp = _stabilize_blend_params(blend_feather, blend_gain, blend_min_overlap)
+        width = 2 + 2 * int(fill_radius)
+        counts = np.zeros((max(n, 1), width), dtype=np.int64) if want_counts else None
+        crop_counts = np.zeros((max(n, 1), width), dtype=np.int64) if want_crop_counts else None
+        gains = np.zeros((max(n, 1), max(2 * int(fill_radius), 1), 3), dtype=np.uint32) if want_gains else None
+        blend_counts = np.zeros((max(n, 1), 2 + 4 * int(fill_radius)), dtype=np.int64) if want_blend_counts else None
+        inpaint_counts = np.zeros(max(n, 1), dtype=np.int64) if want_inpaint_counts else None
+        window = (C.c_int32 * 4)()
+        own = ("self", "n", "fp", "cp", "bp", "width", "counts", "crop_counts", "gains", "blend_counts", "inpaint_counts", "window", "d_sources", "fill_radius",
+               "want_counts", "d_crop", "d_crop_masks", "d_crop_sources", "window_in", "max_empty", "margin", "want_crop_counts", "d_blend", "d_blend_masks",
+               "d_blend_sources", "blend_feather", "blend_gain", "blend_min_overlap", "want_gains", "want_blend_counts", "d_inpaint", "d_inpaint_sources",
+               "want_inpaint_counts")
+        args = {k_: v_ for k_, v_ in locals().items() if k_ not in own and k_ != "own"}
+        arr = lambda a: _ptr_array(a) if a is not None else None
+        out = self._stabilize_video("rsdsfm_stabilize_video_inpainted_dev",
+                                    (C.byref(fp), arr(d_sources), _p(counts), C.byref(cp), _window4(window_in), arr(d_crop), arr(d_crop_masks), arr(d_crop_sources),
+                                     window, _p(crop_counts), C.byref(bp), arr(d_blend), arr(d_blend_masks), arr(d_blend_sources), _p(gains), _p(blend_counts),
+                                     arr(d_inpaint), arr(d_inpaint_sources), _p(inpaint_counts)), **args)
+        out["window"] = tuple(int(x) for x in window)
+        if want_counts:
+            out["counts"] = counts[:n]
+        if want_crop_counts:
+            out["crop_counts"] = crop_counts[:n]
+        if want_gains:
+            out["gains"] = gains[:n, :2 * int(fill_radius)]
+        if want_blend_counts:
+            out["blend_counts"] = blend_counts[:n]
+        if want_inpaint_counts:
+            out["inpaint_counts"] = inpaint_counts[:n]
+        return out
+
+
+for _name, _fn in list(vars(_StabilizeInpaintMixin).items()):
+    if not _name.startswith("__"):
+        setattr(Solver, _name, _fn)
+
+
+# ---------------------------------------------------------------------------------------------------
 # accuracy metrics (SURVEY 8 f-4)
 # ---------------------------------------------------------------------------------------------------
 class ReprojectionStats(C.Structure):

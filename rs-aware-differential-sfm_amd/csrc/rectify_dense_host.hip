@@ -14,12 +14,14 @@ static void dense_ws_free(DenseWs* w) {
     if (w->d_crop) (void)hipFree(w->d_crop);
     if (w->d_seam) (void)hipFree(w->d_seam);
     if (w->d_layer) (void)hipFree(w->d_layer);
+    if (w->d_inpaint) (void)hipFree(w->d_inpaint);
     w->d_pyr = nullptr;
     w->d_disp = nullptr;
     w->d_mask = nullptr;
     w->d_crop = nullptr;
     w->d_seam = nullptr;
     w->d_layer = nullptr;
+    w->d_inpaint = nullptr;
     w->rows = w->cols = 0;
 }
 

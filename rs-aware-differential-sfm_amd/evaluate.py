@@ -208,7 +208,7 @@ def evaluate_real_sequence(solver, frames, camera="galaxy", gamma=0.95, out_dir=
                            use_refinement=True, use_global_shutter_mode=False, flow_threshold=1e-10, flow_index_mode=0, device=0, flow_params=None, dense=False,
                            check_flow=False, trajectory=False, link_tol=None, min_links=None, fuse=False, fuse_tol=None, stabilize=False, smooth_sigma=None,
                            smooth_translation=True, fill=0, crop=False, crop_margin=None, crop_max_empty=0, blend=False, blend_feather=None,
-                           blend_gain=True):
+                           blend_gain=True, inpaint=False):
     """evaluate_real_run's real-world branch (main.cc:341-361, 364-531) for a clip: `frames` is <prefix>frame1.png ... frameN.png (the
     prefix, or a list of paths), or the frames themselves (an (N, rows, cols[, 3]) uint8 array or a list of arrays; 2-D frames are gray).
     By default ONE call does the clip (Solver.rectify_video_dev): the batched DeepFlow of every consecutive pair, the pipelined solve of every pair p
@@ -255,7 +255,15 @@ def evaluate_real_sequence(solver, frames, camera="galaxy", gamma=0.95, out_dir=
     dict then also has stab_blended (per pair, the frame's shape), blend_gains ((pairs, 2 K, 3) uint32 in 1 / 65536, per offset -1, +1, -2,
     +2, ...; 65536 for a skipped offset or an unused channel) and blend_counts ((pairs, 2 + 4 K) int64: [none, own_untouched, (filled,
     blended) per offset]); out_dir receives stabilized_blended_<p>.png per pair and blend.csv (pair, the counts, the gains).  Without blend
-    every output is what it was."""
+    every output is what it was.
+    inpaint=True (needs stabilize=True: ValueError otherwise): the pixels the last stage produced -- blended, else cropped, else filled, else
+    stabilised -- leaves empty, invented from what surrounds them (Solver.inpaint_frame_dev on a COPY of the stage's frames, with its masks;
+    tests/stabilize_inpaint_spec_numpy.py).  The returned dict then also has stab_inpainted (per pair, the frame's shape), inpaint_sources (per
+    pair, (rows, cols) uint8: INPAINT_SOURCE = 255 where a pixel was invented, elsewhere the stage's source plane -- the blend's and the fill's
+    -- or its mask) and inpaint_counts ((pairs,) int64); out_dir receives stabilized_inpainted_<p>.png per pair and inpaint.csv (pair, stage,
+    the count).  Without inpaint every output is what it was."""
+    if inpaint and not stabilize:
+        raise ValueError("inpaint needs stabilize=True: it inpaints what the stabilised frames leave empty")
     if blend and not (stabilize and fill >= 1):
         raise ValueError("blend needs stabilize=True and fill >= 1: it blends the seams between a stabilised frame and its neighbours")
     if fill and not stabilize:
@@ -455,6 +463,23 @@ def evaluate_real_sequence(solver, frames, camera="galaxy", gamma=0.95, out_dir=
                     counts = np.concatenate([(rows * cols - own - per[:, :, 0].sum(axis=1))[:, None], (own - per[:, :, 1].sum(axis=1))[:, None],
                                              per.reshape(npairs, -1)], axis=1)
                     traj.update(stab_blended=[t.cpu().numpy() for t in d_blends], blend_gains=gains, blend_counts=counts)
+                if inpaint:
+                    if blend:
+                        stage, d_last, d_lmask, d_lsrc = "blended", d_blends, d_bmasks, d_bsources
+                    elif crop:
+                        stage, d_last, d_lmask, d_lsrc = "cropped", d_crops, d_cmasks, d_cmasks
+                    elif fill:
+                        stage, d_last, d_lmask, d_lsrc = "filled", d_fills, d_fmasks2, d_sources
+                    else:
+                        stage, d_last, d_lmask, d_lsrc = "stabilized", d_stabs, d_smasks, d_smasks
+                    d_inps, d_isrcs = [t.clone() for t in d_last], [t.clone() for t in d_lsrc]
+                    d_icnt = torch.zeros(npairs, dtype=torch.int64, device=dev)
+                    torch.cuda.synchronize()
+                    for p in range(npairs):  # every frame enqueued, one wait for all of them
+                        solver.inpaint_frame_dev(d_inps[p].data_ptr(), d_lmask[p].data_ptr(), channels, rows, cols, d_isrcs[p].data_ptr(), d_icnt[p:].data_ptr())
+                    solver.synchronize()
+                    traj.update(stab_inpainted=[t.cpu().numpy() for t in d_inps], inpaint_sources=[t.cpu().numpy() for t in d_isrcs],
+                                inpaint_counts=d_icnt.cpu().numpy())
     if out_dir:
         os.makedirs(out_dir, exist_ok=True)
         lines = ["pair,v_x,v_y,v_z,w_x,w_y,w_z,k,inliers"]
@@ -523,6 +548,13 @@ def evaluate_real_sequence(solver, frames, camera="galaxy", gamma=0.95, out_dir=
                 formats.write_png(os.path.join(out_dir, "stabilized_blended_%d.png" % p), traj["stab_blended"][p])
                 rows_.append(",".join([str(p)] + [str(int(x)) for x in traj["blend_counts"][p]] + [str(int(x)) for x in traj["blend_gains"][p].reshape(-1)]))
             with open(os.path.join(out_dir, "blend.csv"), "w") as fh:
+                fh.write("\n".join(rows_) + "\n")
+        if inpaint:
+            rows_ = ["pair,stage,inpainted"]
+            for p in range(npairs):
+                formats.write_png(os.path.join(out_dir, "stabilized_inpainted_%d.png" % p), traj["stab_inpainted"][p])
+                rows_.append("%d,%s,%d" % (p, stage, int(traj["inpaint_counts"][p])))
+            with open(os.path.join(out_dir, "inpaint.csv"), "w") as fh:
                 fh.write("\n".join(rows_) + "\n")
     if trajectory:
         return dict(traj, pairs=outs)
