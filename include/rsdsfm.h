@@ -375,6 +375,14 @@ int rsdsfm_set_frame_side_flatten(rsdsfm_ctx* ctx, int mode);
  *   1 = the stage-by-stage form: output pass, sign decision, claim, depth-map write (four launches).
  * Copied to the lanes of rsdsfm_solve_frames_dev.  Which launches run, never a result: both modes return the same bytes. */
 int rsdsfm_set_frame_tail(rsdsfm_ctx* ctx, int mode);
+/* The hand-off from the RANSAC's winner to the refinement in a frame solve:
+ *   0 (default) = where the refinement is enqueued behind the speculated final stage, that stage leaves block-local lists of its inliers'
+ *       pixel indices and the refinement's first pass finds the pixel of every rank in them itself (no compaction launch in between);
+ *   1 = the compaction launch (inliers, alpha, alpha_k and index list written by rank, read again by the first pass).
+ * Every other caller of the final stage (rsdsfm_ransac*, the tiled driver, use_refinement = 0, a refinement started from the host-side
+ * result) compacts in both modes.  Copied to the lanes of rsdsfm_solve_frames_dev.  Which launches run, never a result: both modes
+ * return the same bytes. */
+int rsdsfm_set_frame_handoff(rsdsfm_ctx* ctx, int mode);
 /* minimal::ransac on device-resident inputs.  The arrays of `out` (inlier_idx, inliers, alpha, alpha_k, mask,
  * inv_depth) are DEVICE pointers with capacity n (each may be NULL); its trial_* arrays are HOST pointers.
  * samples_9xT_or_null is a HOST pointer.  Synchronises once at the end to return the scalars of `out`. */

@@ -602,6 +602,11 @@ class Solver:
         kernel decides the sign and writes the map, 1 the stage-by-stage launches; identical results"""
         self._check(self.lib.rsdsfm_set_frame_tail(self._ctx, int(mode)), "rsdsfm_set_frame_tail")
 
+    def set_frame_handoff(self, mode):
+        """how a frame solve's refinement gets its inliers (rsdsfm_set_frame_handoff): 0 (default) the first refinement pass gathers them from
+        the final stage's block-local lists, 1 the compaction launch; identical results"""
+        self._check(self.lib.rsdsfm_set_frame_handoff(self._ctx, int(mode)), "rsdsfm_set_frame_handoff")
+
     def prepared_frames_solve(self, jobs, trials=50, tol=0.05, use_acceleration_mode=False, use_refinement=True, depth_mode=DEPTH_CERES_LM,
                               k_sign_mode=K_COMPAT, flow_threshold=1e-10, flow_index_mode=FLOW_COMPAT_RANK, use_global_shutter_mode=False):
         """A SEQUENCE of frame pairs in ONE C-ABI call (rsdsfm_solve_frames_dev), pipelined inside the library.  jobs: list of dicts with

@@ -44,6 +44,7 @@ struct FrameRun {
     int64_t* d_idx = nullptr;
     uint8_t* d_mask = nullptr;
     int32_t* d_ys = nullptr;
+    uint32_t* d_local_idx = nullptr;  // direct hand-off (Ctx::frame_handoff == 0): the final stage's block-local inlier lists; null: the compaction launch
     double *d_zpartials = nullptr, *d_zheader = nullptr;
     char* d_refine_ws = nullptr;
     rsdsfm_ransac_out ro;
@@ -117,7 +118,7 @@ int frame_begin(Ctx* c, FrameRun* F) {
     // frame buffers live in the context's frame arena (separate from the per-stage workspace)
     const size_t ncells = (size_t)flatten_cells(rows, cols);
     const size_t need = 2 * Arena::need(16 * N) + 4 * Arena::need(8 * N) + 2 * Arena::need(24 * N) + Arena::need(8 * N) + Arena::need(N) +
-                        Arena::need(4 * N) + Arena::need(8 * 1024) + Arena::need(64) + Arena::need(refine_workspace_bytes(c, (int64_t)N, true)) +
+                        2 * Arena::need(4 * N) + Arena::need(8 * 1024) + Arena::need(64) + Arena::need(refine_workspace_bytes(c, (int64_t)N, true)) +
                         2 * Arena::need(sizeof(int64_t) * (ncells + 2048)) + Arena::need(64) + 4096;
     if (need > c->frame_bytes) {
         RSDSFM_HIP_CHECK(c, hipStreamSynchronize(c->stream));
@@ -139,6 +140,7 @@ int frame_begin(Ctx* c, FrameRun* F) {
     F->d_idx = fa.take<int64_t>(N);
     F->d_mask = fa.take<uint8_t>(N);
     F->d_ys = fa.take<int32_t>(N);
+    uint32_t* d_local_idx = fa.take<uint32_t>(N);  // (workgroup b's list starts at its first pixel: n entries hold every list)
     F->d_zpartials = fa.take<double>(1024);  // scratch of the depth-map stage when it is enqueued behind the refinement
     F->d_zheader = fa.take<double>(8);
     // buffers of a refinement that is enqueued while the RANSAC still owns the stage workspace (see below)
@@ -269,7 +271,7 @@ int frame_begin(Ctx* c, FrameRun* F) {
     F->spec_tail = [c, F](const RansacBest* d_best) -> int {
         return refine_begin(c, F->d_u, F->n, F->n, F->d_inl, F->d_in_a, F->d_in_ak, F->d_idx, nullptr, nullptr, 0.0, F->prm.use_acceleration_mode,
                             F->prm.flow_index_mode, F->d_inl_ref, &F->tail, d_best, F->d_refine_ws, &F->refine, state_host(c), F->d_zpartials, false,
-                            &F->claim);
+                            &F->claim, F->ransac.direct_final ? &F->ransac.handoff : nullptr);
     };
     F->refinement_enqueued = false;
     // (the refinement goes behind the SPECULATED final stage unless that stage did not count in the last two RANSACs: data whose
@@ -277,6 +279,11 @@ int frame_begin(Ctx* c, FrameRun* F) {
     // miss -- one DeepFlow-like pair in ten has a hypothesis with three accepted steps -- does not switch it off.  Either way the
     // refinement is enqueued behind the definitive final stage from the device-resident result, without a host round trip.)
     F->ahead = prm->use_refinement && c->ransac_spec_miss < 2;
+    // Direct hand-off: where the refinement goes behind the speculated final stage and its first pass builds the start state (refine_begin: short
+    // tail, radius-factorised path, alone on the GPU), that pass also finds its inliers itself and the compaction launch between the two is left
+    // out.  Everyone else -- a definitive final stage, no refinement, a refinement from the host-side result -- gets the compaction as ever.
+    F->d_local_idx = (c->frame_handoff == 0 && F->ahead && F->claim.on && c->lm_arithmetic == 0 && c->refine_arithmetic == 0 && !c->refine_stage_separate)
+                         ? d_local_idx : nullptr;
     F->open = true;
     g_frames_in_flight[c->device & 63].fetch_add(1, std::memory_order_relaxed);
     F->counted = true;
@@ -284,7 +291,7 @@ int frame_begin(Ctx* c, FrameRun* F) {
                                prm->depth_mode, prm->k_sign_mode, &F->ro, prm->use_refinement ? &F->spec_tail : nullptr, &F->refinement_enqueued, &F->ransac,
                                F->side_flatten ? &F->direct : nullptr, F->side_flatten && !F->dense_in_launch ? &F->join : nullptr,
                                F->dense_in_launch ? &F->dense : nullptr, F->ahead, true,
-                               F->claim.on && prm->use_refinement ? refine_flag_words(F->d_refine_ws) : nullptr);
+                               F->claim.on && prm->use_refinement ? refine_flag_words(F->d_refine_ws) : nullptr, F->d_local_idx);
     return RSDSFM_OK;  // (an error of the speculated run may only mean that n was wrong: frame_finish sorts that out)
 }
 
@@ -322,7 +329,7 @@ int frame_finish(Ctx* c, FrameRun* F, rsdsfm_frame_result* res) {
         rc = ransac_begin(c, F->d_q, F->d_u, F->d_a, F->d_ak, n, prm->use_acceleration_mode, prm->ransac_trials, prm->ransac_tol, nullptr, J.seed,
                           prm->depth_mode, prm->k_sign_mode, &F->ro, prm->use_refinement ? &F->spec_tail : nullptr, &F->refinement_enqueued, &F->ransac, nullptr, nullptr,
                           nullptr, F->ahead, true,
-                               F->claim.on && prm->use_refinement ? refine_flag_words(F->d_refine_ws) : nullptr);
+                               F->claim.on && prm->use_refinement ? refine_flag_words(F->d_refine_ws) : nullptr, F->d_local_idx);
         if (rc == RSDSFM_OK) rc = ransac_finish(c, &F->ransac);
         counted = rc == RSDSFM_OK;
     }
@@ -346,6 +353,13 @@ int frame_finish(Ctx* c, FrameRun* F, rsdsfm_frame_result* res) {
         if (F->refinement_enqueued) {
             rc = refine_poll(c, &F->refine, v, w, &k, &res->refine_summary);
             exact = rc == kRcRefineRestartExact;  // (a guard of the radius-factorised path: again from the host-side RANSAC result, iterate by iterate)
+        }
+        if ((!F->refinement_enqueued || exact) && F->ransac.direct_final) {
+            // this refinement reads the RANSAC's compacted outputs, which the direct hand-off left out: the compaction after the fact, from the
+            // final stage's mask, rho and counts -- still in the stage workspace, which nothing has touched since (refine_device takes it below)
+            rc = ransac_scatter_launch(c, F->ransac.handoff);
+            if (rc != RSDSFM_OK) return rc;
+            F->ransac.direct_final = false;
         }
         if (!F->refinement_enqueued || exact)
             rc = refine_device(c, F->d_u, n, ro.num_inliers, F->d_inl, F->d_in_a, F->d_in_ak, F->d_idx, v, w, k, prm->use_acceleration_mode,
@@ -448,6 +462,13 @@ int rsdsfm_set_frame_tail(rsdsfm_ctx* ctx, int mode) {
     return RSDSFM_OK;
 }
 
+int rsdsfm_set_frame_handoff(rsdsfm_ctx* ctx, int mode) {
+    if (!ctx) return RSDSFM_ERR_INVALID;
+    if (mode < 0 || mode > 1) return fail(&ctx->c, RSDSFM_ERR_INVALID, "mode must be 0 (the first refinement pass gathers its inliers) or 1 (the compaction launch)");
+    ctx->c.frame_handoff = mode;
+    return RSDSFM_OK;
+}
+
 int rsdsfm_set_frame_side_flatten(rsdsfm_ctx* ctx, int mode) {
     if (!ctx) return RSDSFM_ERR_INVALID;
     if (mode < 0 || mode > 3) return fail(&ctx->c, RSDSFM_ERR_INVALID, "mode must be 0 (flatten first), 1 (flatten on a second stream), 2 (flatten behind the minimal solver) or 3 (flatten inside the solver's launch)");
@@ -491,6 +512,7 @@ int solve_frames_run(Ctx* c, const rsdsfm_frame_job* jobs, int32_t count, const 
         lc->lma_count_only_force = c->lma_count_only_force;
         lc->frame_side_flatten = c->frame_side_flatten;
         lc->frame_tail = c->frame_tail;
+        lc->frame_handoff = c->frame_handoff;
         lc->refine_stage_mode = c->refine_stage_mode;
     }
     // several pairs in flight share the GPU: the refinement's single-workgroup stage gets launches of its own (Ctx::refine_stage_mode)

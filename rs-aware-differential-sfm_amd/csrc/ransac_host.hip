@@ -223,9 +223,14 @@ int ransac_advance(Ctx* c, RansacRun& R, bool yield_at_wait) {
                                             nullptr, 0, 0, nullptr, R.tie_margin, lazy);
                     if (rc != RSDSFM_OK) return rc;
                     flags_via_pick = true;
+                    // (the caller's refinement right behind it, from the device-resident winner: its first pass gathers the inliers itself and the
+                    // compaction launch is left out -- RansacRun::d_local_idx, FrameHandoff)
+                    const bool direct = R.d_local_idx && R.spec_tail && R.tail_ahead;
                     rc = ransac_final_launch(c, R.d_q, R.d_u, R.d_a, R.d_ak, n, R.d_best, R.d_states, depth_mode, tol, R.d_rho, R.d_mask, R.d_bcounts,
-                                             R.d_boffs, out->inlier_idx, out->inliers, out->alpha, out->alpha_k, R.h_best, R.refine_flag_words);
+                                             R.d_boffs, out->inlier_idx, out->inliers, out->alpha, out->alpha_k, R.h_best, R.refine_flag_words,
+                                             direct ? R.d_local_idx : nullptr, direct ? &R.handoff : nullptr);
                     if (rc != RSDSFM_OK) return rc;
+                    R.direct_final = direct && R.handoff.local_idx;
                     R.final_done = true;
                     R.spec_final = true;
                     if (R.spec_tail && R.tail_ahead) {
@@ -323,6 +328,8 @@ int ransac_advance(Ctx* c, RansacRun& R, bool yield_at_wait) {
                     rc = ransac_final_launch(c, R.d_q, R.d_u, R.d_a, R.d_ak, n, R.d_best, R.d_states, depth_mode, tol, R.d_rho, R.d_mask, R.d_bcounts,
                                              R.d_boffs, out->inlier_idx, out->inliers, out->alpha, out->alpha_k, R.h_best, R.refine_flag_words);
                     if (rc != RSDSFM_OK) return rc;
+                    R.direct_final = false;  // (the definitive final stage compacts: what is enqueued behind it reads the compacted arrays)
+                    R.handoff = FrameHandoff();
                 }
                 // the caller's tail behind the DEFINITIVE final stage, where it is not already behind a speculated one that held: it
                 // starts from the device-resident result without a host round trip in between
@@ -436,9 +443,11 @@ void ransac_commit_hints(Ctx* c, const RansacRun& R) {
 int ransac_begin(Ctx* c, const double* d_q, const double* d_u, const double* d_a, const double* d_ak, int64_t n, int use_alpha_k, int T,
                  double tol, const int32_t* h_samples, uint64_t seed, int depth_mode, int k_sign_mode, rsdsfm_ransac_out* out,
                  const RansacSpecTail* spec_tail, bool* spec_tail_held, RansacRun* run, const Minimal9Direct* direct,
-                 const std::function<int()>* after_minimal9, const DenseFlatten* dense, bool tail_ahead, bool count_only, int* refine_flag_words) {
+                 const std::function<int()>* after_minimal9, const DenseFlatten* dense, bool tail_ahead, bool count_only, int* refine_flag_words,
+                 uint32_t* local_idx) {
     RansacRun& R = *run;
     R = RansacRun();
+    R.d_local_idx = local_idx;
     R.tail_ahead = tail_ahead;
     R.core_math = c->ransac_math_mode == 0 && c->ransac_standard_math == 0;
     R.analytic = depth_mode == RSDSFM_DEPTH_CERES_LM && T > 0 && c->lm_arithmetic == 0 && c->lma_hold == 0;

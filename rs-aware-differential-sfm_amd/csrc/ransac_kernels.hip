@@ -862,10 +862,15 @@ __global__ __launch_bounds__(kRB) void ransac_final_kernel(const double2* __rest
                                                           const RansacBest* __restrict__ best,
                                                           const LmState* __restrict__ states, int depth_mode, double tol,
                                                           double* __restrict__ rho_out, uint8_t* __restrict__ mask_out,
-                                                          int64_t* __restrict__ block_counts) {
+                                                          int64_t* __restrict__ block_counts, uint32_t* __restrict__ local_idx = nullptr,
+                                                          int* __restrict__ zero_words = nullptr) {
     __shared__ LmPlanLds plan;
     __shared__ int s_cnt[kRB / 64];
+    __shared__ int s_win[2][kRB / 64];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    // frame solve, direct hand-off (no compaction launch behind this one): the flag + list-counter words of the refinement whose first pass is
+    // the next launch are cleared here, as ransac_scatter_kernel clears them where it runs -- a launch in front of their first atomic
+    if (zero_words && blockIdx.x == 0 && tid < (int)(kRefineStateBlockTail / sizeof(int))) zero_words[tid] = 0;
     if (best->undecided) return;  // (see ransac_pick_kernel)
     const int bt = best->best_trial;
     Pose pose;
@@ -885,18 +890,53 @@ __global__ __launch_bounds__(kRB) void ransac_final_kernel(const double2* __rest
     const int64_t i0 = (int64_t)blockIdx.x * chunk;
     const int64_t i1 = (i0 + chunk < n) ? i0 + chunk : n;
     int count = 0;
-    for (int64_t i = i0 + tid; i < i1; i += kRB) {
-        double2 qq = q[i], uu = u[i];
-        const double al = alpha[i], ak = alpha_k[i];
-        bool in = false;
-        double rho = 0.0;
-        if (bt >= 0) {
-            rho = hyp_rho(qq.x, qq.y, uu.x, uu.y, al, ak, pose, two_over, depth_mode, plan);
-            in = point_error(qq.x, qq.y, uu.x, uu.y, al, ak, pose, two_over, rho) < tol;
+    if (local_idx) {
+        // ... and its inliers' pixel indices, in pixel order, at local_idx[blockIdx.x * chunk ...]: the list the refinement's first pass finds its
+        // ranks in (FrameHandoff) -- positions inside this workgroup's own range, no other workgroup's count is needed.  Every lane takes part in
+        // every window's ballot; the waves' counts of a window take turns in two LDS rows, so that one barrier per window is enough.
+        int base = 0, par = 0;
+        for (int64_t start = i0; start < i1; start += kRB, par ^= 1) {
+            const int64_t i = start + tid;
+            bool in = false;
+            if (i < i1) {
+                double2 qq = q[i], uu = u[i];
+                const double al = alpha[i], ak = alpha_k[i];
+                double rho = 0.0;
+                if (bt >= 0) {
+                    rho = hyp_rho(qq.x, qq.y, uu.x, uu.y, al, ak, pose, two_over, depth_mode, plan);
+                    in = point_error(qq.x, qq.y, uu.x, uu.y, al, ak, pose, two_over, rho) < tol;
+                }
+                rho_out[i] = rho;
+                mask_out[i] = in ? 1 : 0;
+                count += in ? 1 : 0;
+            }
+            const unsigned long long bal = __ballot(in);
+            if (lane == 0) s_win[par][wv] = __popcll(bal);
+            __syncthreads();
+            int woff = 0, total = 0;
+#pragma unroll
+            for (int w2 = 0; w2 < kRB / 64; ++w2) {
+                const int c = s_win[par][w2];
+                if (w2 < wv) woff += c;
+                total += c;
+            }
+            if (in) local_idx[i0 + base + woff + __popcll(bal & ((1ull << lane) - 1ull))] = (uint32_t)i;
+            base += total;
         }
-        rho_out[i] = rho;
-        mask_out[i] = in ? 1 : 0;
-        count += in ? 1 : 0;
+    } else {
+        for (int64_t i = i0 + tid; i < i1; i += kRB) {
+            double2 qq = q[i], uu = u[i];
+            const double al = alpha[i], ak = alpha_k[i];
+            bool in = false;
+            double rho = 0.0;
+            if (bt >= 0) {
+                rho = hyp_rho(qq.x, qq.y, uu.x, uu.y, al, ak, pose, two_over, depth_mode, plan);
+                in = point_error(qq.x, qq.y, uu.x, uu.y, al, ak, pose, two_over, rho) < tol;
+            }
+            rho_out[i] = rho;
+            mask_out[i] = in ? 1 : 0;
+            count += in ? 1 : 0;
+        }
     }
     // block count (integers: order irrelevant)
     for (int off = 32; off >= 1; off >>= 1) count += __shfl_xor(count, off, 64);
@@ -1202,19 +1242,32 @@ int ransac_pick_launch(Ctx* c, const double* trial_count, const double* trial_er
 int ransac_final_launch(Ctx* c, const double* q, const double* u, const double* a, const double* ak, int64_t n,
                         RansacBest* best, const LmState* states, int depth_mode, double tol, double* rho, uint8_t* mask,
                         int64_t* block_counts, int64_t* block_offsets, int64_t* inlier_idx, double* inliers,
-                        double* out_alpha, double* out_alpha_k, RansacBest* best_host, int* zero_words) {
+                        double* out_alpha, double* out_alpha_k, RansacBest* best_host, int* zero_words, uint32_t* local_idx,
+                        FrameHandoff* handoff) {
     int64_t blocks = (n + kRB - 1) / kRB;
     if (blocks < 1) blocks = 1;
-    const int64_t cap = 2048;
+    const int64_t cap = kRfHandoffBlocks;
     int64_t chunk = kRB;
     if (blocks > cap) {
         chunk = ((blocks + cap - 1) / cap) * kRB;
         blocks = (n + chunk - 1) / chunk;
     }
+    // direct hand-off: block-local inlier lists instead of the compaction; the caller's first refinement pass resolves the ranks (FrameHandoff).
+    // (32-bit pixel indices; where n does not fit them the launches below run as ever)
+    const bool direct = local_idx && handoff && n <= (int64_t)INT32_MAX;
+    if (handoff) *handoff = FrameHandoff();
     hipLaunchKernelGGL(ransac_final_kernel, dim3((int)blocks), dim3(kRB), 0, c->stream, reinterpret_cast<const double2*>(q),
                        reinterpret_cast<const double2*>(u), a, ak, n, chunk, best, states, depth_mode, tol, rho, mask,
-                       block_counts);
+                       block_counts, direct ? local_idx : nullptr, direct ? zero_words : nullptr);
     RSDSFM_HIP_CHECK(c, hipGetLastError());
+    if (direct) {
+        FrameHandoff& H = *handoff;
+        H.local_idx = local_idx, H.block_counts = block_counts, H.nblocks = (int)blocks, H.chunk = chunk, H.n = n;
+        H.q = q, H.alpha = a, H.alpha_k = ak, H.rho = rho, H.mask = mask;
+        H.best = best, H.best_host = best_host;
+        H.inlier_idx = inlier_idx, H.inliers = inliers, H.out_alpha = out_alpha, H.out_alpha_k = out_alpha_k;
+        return RSDSFM_OK;
+    }
     if (inlier_idx || inliers || out_alpha || out_alpha_k) {  // the compaction scans the workgroup counts itself
         hipLaunchKernelGGL(ransac_scatter_kernel, dim3((int)blocks), dim3(kRB), 0, c->stream, reinterpret_cast<const double2*>(q),
                            a, ak, n, chunk, rho, mask, block_counts, best, best_host, inlier_idx, inliers, out_alpha, out_alpha_k, zero_words);
@@ -1222,6 +1275,13 @@ int ransac_final_launch(Ctx* c, const double* q, const double* u, const double* 
         if (zero_words) RSDSFM_HIP_CHECK(c, hipMemsetAsync(zero_words, 0, kRefineStateBlockTail, c->stream));
         hipLaunchKernelGGL(ransac_scan_kernel, dim3(1), dim3(256), 0, c->stream, block_counts, (int)blocks, block_offsets, best, best_host);
     }
+    RSDSFM_HIP_CHECK(c, hipGetLastError());
+    return RSDSFM_OK;
+}
+
+int ransac_scatter_launch(Ctx* c, const FrameHandoff& H) {
+    hipLaunchKernelGGL(ransac_scatter_kernel, dim3(H.nblocks), dim3(kRB), 0, c->stream, reinterpret_cast<const double2*>(H.q), H.alpha, H.alpha_k, H.n,
+                       H.chunk, H.rho, H.mask, H.block_counts, H.best, H.best_host, H.inlier_idx, H.inliers, H.out_alpha, H.out_alpha_k, nullptr);
     RSDSFM_HIP_CHECK(c, hipGetLastError());
     return RSDSFM_OK;
 }

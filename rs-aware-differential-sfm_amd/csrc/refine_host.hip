@@ -23,7 +23,9 @@ namespace rsdsfm {
 int refine_begin(Ctx* c, const double* d_flow, int64_t n_flow, int64_t m, const double* d_inl, const double* d_alpha,
                  const double* d_alpha_k, const int64_t* d_inlier_idx, const double v_in[3], const double w_in[3], double k_in,
                  int const_acceleration, int flow_index_mode, double* d_inl_out, const RefineTail* tail, const RansacBest* d_best,
-                 void* ws_base, RefineRun* run, RefineState* hs_prefetch, double* d_zpartials, bool exact, const FinishClaim* claim) {
+                 void* ws_base, RefineRun* run, RefineState* hs_prefetch, double* d_zpartials, bool exact, const FinishClaim* claim,
+                 const FrameHandoff* handoff) {
+    const bool direct = handoff && handoff->local_idx;  // (d_inl, d_alpha, d_alpha_k, d_inlier_idx: where the compaction WOULD have written)
     if (m < 0 || n_flow < 0 || (!d_best && (!v_in || !w_in))) return fail(c, RSDSFM_ERR_INVALID, "bad arguments");
     if (flow_index_mode != RSDSFM_FLOW_COMPAT_RANK && flow_index_mode != RSDSFM_FLOW_GATHERED) return fail(c, RSDSFM_ERR_INVALID, "unknown flow_index_mode");
     if (flow_index_mode == RSDSFM_FLOW_GATHERED && m > 0 && !d_inlier_idx) return fail(c, RSDSFM_ERR_INVALID, "gathered mode needs inlier_idx");
@@ -81,6 +83,14 @@ int refine_begin(Ctx* c, const double* d_flow, int64_t n_flow, int64_t m, const 
         // short launch tail: the first pass builds the start state itself (refine_rf_pass_kernel FIRST), and the flag + list-counter words were
         // cleared by the RANSAC's compaction, the launch in front of it (RansacRun::refine_flag_words)
         B.best_dev = d_best;
+        if (direct) {
+            // direct hand-off: no compacted arrays -- the first pass finds its inliers in the final stage's block-local lists and writes the
+            // index list (k refined: alpha and alpha_k too, for the later passes); the output pass takes (x, y) from the first pass's records
+            B.handoff = *handoff;
+            B.fin_xy = B.uu, B.fin_stride = 4;
+        }
+    } else if (direct) {
+        return fail(c, RSDSFM_ERR_INVALID, "refinement: direct hand-off without the start state in the first pass");
     } else if (d_best) {
         rc = refine_state_from_best_launch(c, d_best, B, np);
         if (rc != RSDSFM_OK) return rc;

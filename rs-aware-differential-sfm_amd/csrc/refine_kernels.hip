@@ -509,7 +509,10 @@ __global__ __launch_bounds__(kFB) void refine_finish_claim_kernel(int64_t m, con
                                                                  double* __restrict__ inl_out, double* __restrict__ zpartials,
                                                                  RefineState* __restrict__ state_host, const int* __restrict__ bad_index,
                                                                  double fx, double fy, double cx, double cy, int rows, int ncols,
-                                                                 unsigned* __restrict__ owner, unsigned tag, int32_t* __restrict__ ys) {
+                                                                 unsigned* __restrict__ owner, unsigned tag, int32_t* __restrict__ ys,
+                                                                 int xy_stride) {
+    // (inl, xy_stride: where (x, y) of inlier i is -- the RANSAC's compacted inliers, 3 doubles each, or, behind a first pass that gathered its
+    // inliers itself, that pass's records, 4 doubles each: the same values)
     __shared__ double s_red[kFB / 64];
     if (state_host && blockIdx.x == 0) {
         for (int i = threadIdx.x; i < (int)(sizeof(RefineState) / 8); i += kFB)
@@ -521,7 +524,7 @@ __global__ __launch_bounds__(kFB) void refine_finish_claim_kernel(int64_t m, con
     const int64_t stride = (int64_t)gridDim.x * kFB;
     double acc = 0.0;
     for (int64_t i = (int64_t)blockIdx.x * kFB + threadIdx.x; i < m; i += stride) {
-        const double xn = inl[3 * i], yn = inl[3 * i + 1];
+        const double xn = inl[xy_stride * i], yn = inl[xy_stride * i + 1];
         inl_out[3 * i] = xn;
         inl_out[3 * i + 1] = yn;
         const double z = 1.0 / rho[i];
@@ -994,12 +997,13 @@ int refine_finish_grid(const Ctx* c, const RefineBuffers& B) { return B.m_on_dev
 int refine_finish_launch(Ctx* c, const RefineBuffers& B, double* inl_out) {
     if (!B.m_on_device && B.m == 0 && !B.zpartials && !B.state_host) return RSDSFM_OK;
     if (B.claim.on) {  // frame solve, short tail (refine_enqueue_chunk has taken the claim map)
-        hipLaunchKernelGGL(refine_finish_claim_kernel, dim3(refine_finish_grid(c, B)), dim3(kFB), 0, c->stream, B.m_on_device ? (int64_t)-1 : B.m, B.inl,
-                           B.rho_a, B.rho_b, B.state, inl_out, B.zpartials, B.state_host, B.bad_index, B.claim.fx, B.claim.fy, B.claim.cx, B.claim.cy,
-                           B.claim.rows, B.claim.cols, B.claim.owner, B.claim.tag, B.claim.ys);
+        hipLaunchKernelGGL(refine_finish_claim_kernel, dim3(refine_finish_grid(c, B)), dim3(kFB), 0, c->stream, B.m_on_device ? (int64_t)-1 : B.m,
+                           B.fin_xy ? B.fin_xy : B.inl, B.rho_a, B.rho_b, B.state, inl_out, B.zpartials, B.state_host, B.bad_index, B.claim.fx, B.claim.fy,
+                           B.claim.cx, B.claim.cy, B.claim.rows, B.claim.cols, B.claim.owner, B.claim.tag, B.claim.ys, B.fin_xy ? B.fin_stride : 3);
         RSDSFM_HIP_CHECK(c, hipGetLastError());
         return RSDSFM_OK;
     }
+    if (B.fin_xy) return fail(c, RSDSFM_ERR_INVALID, "refinement: the direct hand-off needs the claiming output pass");
     hipLaunchKernelGGL(refine_finish_kernel, dim3(refine_finish_grid(c, B)), dim3(kFB), 0, c->stream,
                        B.m_on_device ? (int64_t)-1 : B.m, B.inl, B.rho_a, B.rho_b, B.state, inl_out, B.zpartials, B.state_host, B.bad_index);
     RSDSFM_HIP_CHECK(c, hipGetLastError());

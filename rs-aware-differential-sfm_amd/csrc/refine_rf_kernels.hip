@@ -690,6 +690,20 @@ struct RfPassArgs {
     const RansacBest* best;      // first pass, frame solve: the start state is built from it here (refine_state_from_best_kernel's rule); null: st_in holds it
     int grid_cap;                // ... with this cap on the logical grid
     unsigned long long* stamps;  // opt-in (RSDSFM_RF_STAMPS=1): workgroup 0 adds the 100 MHz ticks of its phases here (tools/refine_rf_probe.py)
+    // first pass, frame solve, direct hand-off (DIRECT; FrameHandoff): no compacted arrays -- rank i's pixel is found in the final stage's block-local lists
+    const uint32_t* local_idx;
+    const int64_t* block_counts;
+    int nblocks;
+    int64_t chunk;
+    const double2* q_px;         // per PIXEL: what ransac_scatter_kernel would have compacted
+    const double* alpha_px;
+    const double* alpha_k_px;
+    const double* rho_px;
+    int64_t* inlier_idx_out;     // the pixel of every rank (rsdsfm_frame_result::d_inlier_idx)
+    double* alpha_out;           // NP == 7: the later passes read alpha / alpha_k by rank
+    double* alpha_k_out;
+    RansacBest* best_pub;        // workgroup 0 records the total of the counts ...
+    RansacBest* best_host;       // ... also in host-mapped memory
 };
 
 // per-inlier inputs of a later pass, as loaded
@@ -716,9 +730,15 @@ __device__ __forceinline__ RfLoad rf_load(const RfPassArgs& A, const double* __r
 }  // namespace
 
 // (the kernels themselves have external names: rocprofv3 and the profile summaries list them by name)
-template <int NP, bool FIRST, bool ZSUM>
+template <int NP, bool FIRST, bool ZSUM, bool DIRECT = false>
 __global__ __launch_bounds__(kFB) void refine_rf_pass_kernel(const RfPassArgs A) {
+    static_assert(FIRST || !DIRECT, "only the first pass gathers");
     using RR = RfRow<NP>;
+    // DIRECT: exclusive scan of the final stage's workgroup counts (block b's inliers are the ranks [s_off[b], s_off[b + 1]))
+    __shared__ uint32_t s_off[DIRECT ? kRfHandoffBlocks + 1 : 1];
+    __shared__ uint32_t s_coarse[64];  // ... every 32nd of them (0xFFFFFFFF past the end): the first round of the search
+    static_assert(kRfHandoffBlocks == 64 * 32, "rounds of the search");
+    __shared__ uint32_t s_wtot[kFB / 64];
     __shared__ RfStageLds<NP> s_stage;
     __shared__ double s_red[kFB / 64][RR::NW];
     __shared__ RefineState s_state;
@@ -734,6 +754,57 @@ __global__ __launch_bounds__(kFB) void refine_rf_pass_kernel(const RfPassArgs A)
         for (int i = 0; i < 8; ++i) tk[i] = 0;
     }
     if (stamp) tk[0] = wall_clock64();
+    int64_t m_direct = 0;
+    if (DIRECT) {
+        // Every workgroup sums the final stage's <= kRfHandoffBlocks counts for itself (integers: exact in any order), as ransac_scatter_kernel
+        // does where it runs: the offsets go to LDS, the total is the inlier count, workgroup 0 records it.  Behind a final stage that left at
+        // once (RansacBest::undecided) the counts are stale, possibly of another size: not read.
+        const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+        const int nb = A.nblocks;
+        if (!A.best->undecided) {  // (uniform)
+            constexpr int kPer = (kRfHandoffBlocks + kFB - 1) / kFB;
+            const int per = (nb + kFB - 1) / kFB;
+            uint32_t cnt[kPer], sum = 0;
+#pragma unroll
+            for (int j = 0; j < kPer; ++j) {
+                const int b = tid * per + j;
+                cnt[j] = (j < per && b < nb) ? (uint32_t)A.block_counts[b] : 0u;
+                sum += cnt[j];
+            }
+            uint32_t inc = sum;
+#pragma unroll
+            for (int off = 1; off < 64; off <<= 1) {
+                const uint32_t t = __shfl_up(inc, off, 64);
+                if (lane >= off) inc += t;
+            }
+            if (lane == 63) s_wtot[wv] = inc;
+            __syncthreads();
+            uint32_t wbase = 0, total = 0;
+#pragma unroll
+            for (int w2 = 0; w2 < kFB / 64; ++w2) {
+                const uint32_t v = s_wtot[w2];
+                if (w2 < wv) wbase += v;
+                total += v;
+            }
+            uint32_t run = wbase + inc - sum;
+#pragma unroll
+            for (int j = 0; j < kPer; ++j) {
+                const int b = tid * per + j;
+                if (j < per && b < nb) {
+                    s_off[b] = run;
+                    run += cnt[j];
+                }
+            }
+            if (tid == 0) s_off[nb] = total;
+            m_direct = (int64_t)total;
+            __syncthreads();
+            if (tid < 64) s_coarse[tid] = tid * 32 < nb ? s_off[tid * 32] : 0xFFFFFFFFu;
+            if (blockIdx.x == 0 && tid == 0) {
+                A.best_pub->num_inliers_scan = m_direct;
+                if (A.best_host) A.best_host->num_inliers_scan = m_direct;
+            }
+        }
+    }
     if (FIRST && A.best) {
         // the start state of a refinement enqueued before the host has read the RANSAC result, by refine_state_from_best_kernel's rule: every
         // workgroup builds it for itself (workgroup 0 writes it out below), instead of a one-lane launch in front of this one
@@ -750,7 +821,7 @@ __global__ __launch_bounds__(kFB) void refine_rf_pass_kernel(const RfPassArgs A)
             z.termination = -1;
             z.radius = kInitialRadius;
             z.need_schur = 1;
-            const int64_t mb = A.best->undecided ? 0 : A.best->num_inliers_scan;  // (a RANSAC that is not over: no inliers, every kernel leaves at once)
+            const int64_t mb = A.best->undecided ? 0 : (DIRECT ? m_direct : A.best->num_inliers_scan);  // (a RANSAC that is not over: no inliers, every kernel leaves at once)
             z.m = mb;
             int64_t b = (mb + kFB - 1) / kFB;
             if (b < 1) b = 1;
@@ -809,16 +880,8 @@ __global__ __launch_bounds__(kFB) void refine_rf_pass_kernel(const RfPassArgs A)
     if (FIRST) {
         RfPoint Pq = rf_point(st->p);
         const RfPoint P = rf_point_uniform(Pq);
-        for (int64_t i = i0; i < m; i += stride) {
-            int64_t fi = (A.flow_index_mode == RSDSFM_FLOW_GATHERED) ? A.inlier_idx[i] : i;
-            if (fi < 0 || fi >= A.n_flow) {
-                *A.bad_index = 1;
-                fi = 0;
-            }
-            const double2 f = A.flow[fi];
-            const double x = A.inl[3 * i], y = A.inl[3 * i + 1];
-            const double rho = 1.0 / A.inl[3 * i + 2];  // nonlinearRefinement.cc:213
-            const double al = A.alpha[i], ak = A.alpha_k[i];
+        // one inlier from its start values: the records of the later passes, residual and Jacobian at the start point, the Schur sums of iteration 1
+        auto body = [&](int64_t i, double x, double y, double rho, double al, double ak, const double2 f) {
             A.xyuv_out[i] = make_double4(x, y, f.x, f.y);
             const double ab = NP == 6 ? P.c1 * __builtin_fma(P.k, ak, al) : al;
             if (NP == 6) A.beta[i] = ab;
@@ -837,6 +900,96 @@ __global__ __launch_bounds__(kFB) void refine_rf_pass_kernel(const RfPassArgs A)
             const double ihm = flagged ? 0.0 : rcp_core(flagged ? 1.0 : o.h);
             rf_schur_accumulate<NP>(o, ihm, acc);
             if (flagged) rf_list_append(A.list_count, A.list_entries, x, y, f.x, f.y, ab, ak, rho, i);
+        };
+        if (DIRECT) {
+            // The pixel of rank iw + lane, iw the rank of the wave's lane 0 (a wave's ranks of one turn are consecutive): the block of rank iw by
+            // two 64-way rounds over the sorted offsets -- every 32nd, then the 32 in between: the last one that is <= iw -- and from there each
+            // lane walks to its own block (a dense frame: at most one step; empty blocks share their successor's offset and are walked over;
+            // s_off[nblocks] = m stops every walk).  Then the block's list.  Every lane of the wave takes part: callers keep the turns wave-uniform.
+            // (Measured and dropped: a binary search per lane, eleven dependent LDS reads, 25.2 us; three bits per round with seven reads each,
+            // 27.4 us -- the search costs its instructions, not its latency.)
+            const int lane = threadIdx.x & 63;
+            auto rank_pixel = [&](int64_t iw) -> int64_t {
+                if (iw >= m) return 0;  // (uniform)
+                const uint32_t r0 = (uint32_t)iw, r = r0 + (uint32_t)lane;
+                const int c = __popcll(__ballot(s_coarse[lane] <= r0)) - 1;
+                const int t = c * 32 + lane;
+                const int b_lo = c * 32 + __popcll(__ballot(lane < 32 && t <= A.nblocks && s_off[t] <= r0)) - 1;
+                if (r >= (uint32_t)m) return 0;
+                int b = b_lo;
+                while (s_off[b + 1] <= r) ++b;
+                return (int64_t)A.local_idx[(int64_t)b * A.chunk + (r - s_off[b])];
+            };
+            // what the compaction would have written for rank i, read at its pixel p (flow: by rank, or at the pixel in gathered mode)
+            struct Rec {
+                double2 q, f;
+                double rho, al, ak;
+                int64_t p;
+            };
+            auto load = [&](int64_t i, int64_t p) {
+                Rec r;
+                r.q = r.f = make_double2(0.0, 0.0), r.rho = r.al = r.ak = 0.0, r.p = p;
+                if (i < m) {
+                    int64_t fi = (A.flow_index_mode == RSDSFM_FLOW_GATHERED) ? p : i;
+                    if (fi < 0 || fi >= A.n_flow) {
+                        *A.bad_index = 1;
+                        fi = 0;
+                    }
+                    r.f = A.flow[fi];
+                    r.q = A.q_px[p];
+                    r.rho = A.rho_px[p];
+                    r.al = A.alpha_px[p], r.ak = A.alpha_k_px[p];
+                }
+                return r;
+            };
+            auto turn = [&](const Rec& r, int64_t i) {
+                // exactly what the compaction and this pass did to the same values: z = 1 / rho of the pixel (minimal.cc:299), rho = 1 / z
+                const double z = 1.0 / r.rho;
+                const double rho = 1.0 / z;  // nonlinearRefinement.cc:213
+                A.inlier_idx_out[i] = r.p;
+                if (NP == 7) A.alpha_out[i] = r.al, A.alpha_k_out[i] = r.ak;
+                body(i, r.q.x, r.q.y, rho, r.al, r.ak, r.f);
+            };
+            // A rank's loads hang on a chain (LDS search, index, the pixel's values), so they are requested turns ahead of their arithmetic: the
+            // index three turns, the values two (NP == 6; k refined: 75 accumulators leave no registers for values in flight -- the index two
+            // turns ahead, the values in their own turn; see the later passes below).
+            // (The turns are counted by the wave: iw is the same in every lane, a lane whose rank is past the end sits its last turn out.)
+            const int64_t iw0 = i0 - lane;
+            if (NP == 6) {
+                Rec r0 = load(i0, rank_pixel(iw0));
+                Rec r1 = load(i0 + stride, rank_pixel(iw0 + stride));
+                int64_t p2 = rank_pixel(iw0 + 2 * stride);
+                for (int64_t iw = iw0; iw < m; iw += stride) {
+                    const int64_t i = iw + lane;
+                    const Rec r2 = load(i + 2 * stride, p2);
+                    p2 = rank_pixel(iw + 3 * stride);
+                    if (i < m) turn(r0, i);
+                    r0 = r1;
+                    r1 = r2;
+                }
+            } else {
+                int64_t p0 = rank_pixel(iw0), p1 = rank_pixel(iw0 + stride);
+                for (int64_t iw = iw0; iw < m; iw += stride) {
+                    const int64_t i = iw + lane;
+                    const Rec r = load(i, p0);
+                    p0 = p1;
+                    p1 = rank_pixel(iw + 2 * stride);
+                    if (i < m) turn(r, i);
+                }
+            }
+        } else {
+            for (int64_t i = i0; i < m; i += stride) {
+                int64_t fi = (A.flow_index_mode == RSDSFM_FLOW_GATHERED) ? A.inlier_idx[i] : i;
+                if (fi < 0 || fi >= A.n_flow) {
+                    *A.bad_index = 1;
+                    fi = 0;
+                }
+                const double2 f = A.flow[fi];
+                const double x = A.inl[3 * i], y = A.inl[3 * i + 1];
+                const double rho = 1.0 / A.inl[3 * i + 2];  // nonlinearRefinement.cc:213
+                const double al = A.alpha[i], ak = A.alpha_k[i];
+                body(i, x, y, rho, al, ak, f);
+            }
         }
     } else {
         RfPoint Pq = rf_point(st->p), Pcq = rf_point(st->pc);
@@ -1115,7 +1268,9 @@ unsigned long long* rf_stamps(Ctx* c) {
 }
 template <int NP, bool ZSUM>
 void rf_pass_launch_t(Ctx* c, const RfPassArgs& A, bool first, int grid) {
-    if (first)
+    if (first && A.local_idx)
+        hipLaunchKernelGGL((refine_rf_pass_kernel<NP, true, ZSUM, true>), dim3(grid), dim3(kFB), 0, c->stream, A);
+    else if (first)
         hipLaunchKernelGGL((refine_rf_pass_kernel<NP, true, ZSUM>), dim3(grid), dim3(kFB), 0, c->stream, A);
     else
         hipLaunchKernelGGL((refine_rf_pass_kernel<NP, false, ZSUM>), dim3(grid), dim3(kFB), 0, c->stream, A);
@@ -1168,6 +1323,14 @@ int refine_rf_pass_launch(Ctx* c, const RefineBuffers& B, int np, int g, int g_f
     A.beat = rf_beat(c);
     A.slot = g;
     const bool first = g == 0;
+    if (first && B.handoff.local_idx) {  // (refine_begin: only with best_dev, the start state built here)
+        const FrameHandoff& H = B.handoff;
+        if (!A.best || H.nblocks > kRfHandoffBlocks || H.n > (int64_t)INT32_MAX) return fail(c, RSDSFM_ERR_INVALID, "refinement: direct hand-off without its preconditions");
+        A.local_idx = H.local_idx, A.block_counts = H.block_counts, A.nblocks = H.nblocks, A.chunk = H.chunk;
+        A.q_px = reinterpret_cast<const double2*>(H.q), A.alpha_px = H.alpha, A.alpha_k_px = H.alpha_k, A.rho_px = H.rho;
+        A.inlier_idx_out = H.inlier_idx, A.alpha_out = H.out_alpha, A.alpha_k_out = H.out_alpha_k;
+        A.best_pub = H.best, A.best_host = H.best_host;
+    }
     if (np == 7) {
         if (B.want_zsum) rf_pass_launch_t<7, true>(c, A, first, grid); else rf_pass_launch_t<7, false>(c, A, first, grid);
     } else {

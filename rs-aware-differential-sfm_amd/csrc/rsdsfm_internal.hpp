@@ -91,6 +91,23 @@ struct RansacBest {
     int32_t _pad_shared;
     int32_t lazy_pending;  // count-only analytic pass: several trials share the best inlier count and some of them have no error sum yet (ransac_pick_kernel put them on the scoring pass's list; such a result is also `undecided`)
 };
+// Frame solve, direct hand-off (Ctx::frame_handoff == 0): what a final stage that left the compaction out hands to the refinement's first pass.
+// Workgroup b of the final stage wrote the pixel indices of its inliers, in pixel order, at local_idx[b * chunk ...] and their number at
+// block_counts[b]; the first pass scans the counts itself, finds the pixel of every rank and reads q / alpha / alpha_k / rho there.
+constexpr int kRfHandoffBlocks = 2048;  // workgroups of the final stage at most (ransac_final_launch): the first pass keeps their offsets in LDS
+struct FrameHandoff {
+    const uint32_t* local_idx = nullptr;  // null: off (the compacted arrays are the RANSAC's outputs)
+    const int64_t* block_counts = nullptr;
+    int nblocks = 0;
+    int64_t chunk = 0, n = 0;
+    const double *q = nullptr, *alpha = nullptr, *alpha_k = nullptr, *rho = nullptr;
+    const uint8_t* mask = nullptr;
+    RansacBest *best = nullptr, *best_host = nullptr;  // the first pass's workgroup 0 records the total like the compaction's does
+    // the RANSAC's compacted outputs: inlier_idx (and, k refined, alpha / alpha_k, which the later passes read) written by the first pass;
+    // all of them by ransac_scatter_launch where a consumer wants them after the fact
+    int64_t* inlier_idx = nullptr;
+    double *inliers = nullptr, *out_alpha = nullptr, *out_alpha_k = nullptr;
+};
 // ransac_pick_kernel, lazy error sums: scored[T] (2 = the trial has a count only), the scoring pass's list and its counter; scored == null: off
 struct PickLazy {
     int* scored = nullptr;
@@ -199,6 +216,9 @@ struct Ctx {
     // rsdsfm_set_frame_tail: 0 = the frame solve's short launch tail (the output pass claims the depth-map pixels, one kernel decides the sign and
     // writes the map), 1 = the stage-by-stage launches (refine_finish, zsum_decide, depth_claim, depth_write).  Which launches run, never a result.
     int frame_tail = 0;
+    // rsdsfm_set_frame_handoff: 0 = the refinement's first pass gathers its inliers itself from the final stage's block-local lists (no compaction
+    // launch between them), 1 = the compaction launch (ransac_scatter_kernel).  Which launches run, never a result.
+    int frame_handoff = 0;
     unsigned long long* d_flat_counters = nullptr;  // the two counters of minimal9_flatten_kernel (zero between launches)
     int seq_lanes = 0;               // rsdsfm_set_sequence_lanes (0 = kSequenceLanesDefault)
     // where the refinement's single-workgroup stage runs (rsdsfm_set_refine_stage): 0 = automatic -- in the prologue of the next slot's pass
@@ -428,7 +448,10 @@ int ransac_pick_launch(Ctx* c, const double* trial_count, const double* trial_er
 int ransac_final_launch(Ctx* c, const double* q, const double* u, const double* a, const double* ak, int64_t n,
                         RansacBest* best, const LmState* states, int depth_mode, double tol, double* rho, uint8_t* mask,
                         int64_t* block_counts, int64_t* block_offsets, int64_t* inlier_idx, double* inliers,
-                        double* out_alpha, double* out_alpha_k, RansacBest* best_host = nullptr, int* zero_words = nullptr);
+                        double* out_alpha, double* out_alpha_k, RansacBest* best_host = nullptr, int* zero_words = nullptr,
+                        uint32_t* local_idx = nullptr, FrameHandoff* handoff = nullptr);
+// the compaction of a final stage that left it out (FrameHandoff), from that stage's mask, rho and counts
+int ransac_scatter_launch(Ctx* c, const FrameHandoff& H);
 // row-tiled stages
 int ransac_rows_doubles();
 int ransac_lm_rows_launch(Ctx* c, const double* q, const double* u, const double* a, const double* ak, int64_t n,
@@ -525,6 +548,9 @@ struct RefineBuffers {
     double* zpartials = nullptr;  // frame solve: refine_finish_kernel also leaves its per-workgroup sums of z here (refine_finish_grid entries)
     const RansacBest* best_dev = nullptr;  // frame solve, short launch tail: the first pass builds the start state from it (no refine_state_from_best launch)
     FinishClaim claim;            // frame solve: the output pass claims the depth-map pixels as well (refine_finish_claim_kernel)
+    FrameHandoff handoff;         // frame solve, direct hand-off: the first pass gathers its inliers itself (local_idx != null)
+    const double* fin_xy = nullptr;  // the output pass's source of (x, y), fin_stride doubles per inlier; null: inl (stride 3)
+    int fin_stride = 3;
     bool want_zsum = false;       // the streaming passes also sum 1 / rho (one division per inlier and pass) into the last slot of their rows -> RefineState::zsum
 };
 size_t ransac_pinned_bytes(int T);
@@ -547,6 +573,9 @@ struct RansacRun {
     bool analytic = false;   // the depth solves on the analytic LM trajectory (ransac_lma_kernels.hip); false after a guard tripped
     bool lma_restarted = false;
     int* refine_flag_words = nullptr;  // frame solve: words of the refinement behind the final stage that the compaction clears (ransac_scatter_kernel)
+    uint32_t* d_local_idx = nullptr;  // frame solve, direct hand-off: the speculated final stage writes block-local inlier lists here and leaves the compaction out
+    FrameHandoff handoff;             // ... what it hands to the caller's tail
+    bool direct_final = false;        // the final stage that counts left the compaction out (the compacted outputs do not exist yet: ransac_scatter_launch)
     bool count_only = false;  // analytic pass without error sums; ransac_pick_kernel asks for the exact sums of the trials that share the best count
     int lazy_rounds = 0;
     int shared_best = 0;      // RansacBest::shared_best of the definitive pick
@@ -586,7 +615,7 @@ int ransac_begin(Ctx* c, const double* d_q, const double* d_u, const double* d_a
                  double tol, const int32_t* h_samples, uint64_t seed, int depth_mode, int k_sign_mode, rsdsfm_ransac_out* out,
                  const RansacSpecTail* spec_tail, bool* spec_tail_held, RansacRun* run, const Minimal9Direct* direct,
                  const std::function<int()>* after_minimal9, const DenseFlatten* dense = nullptr, bool tail_ahead = true, bool count_only = false,
-                 int* refine_flag_words = nullptr);
+                 int* refine_flag_words = nullptr, uint32_t* local_idx = nullptr);
 int ransac_finish(Ctx* c, RansacRun* run);
 void ransac_commit_hints(Ctx* c, const RansacRun& run);
 int flatten_enqueue(Ctx* c, const double* d_img, int32_t rows, int32_t cols, double fx, double fy, double cx, double cy, double gamma,
@@ -619,7 +648,7 @@ int refine_begin(Ctx* c, const double* d_flow, int64_t n_flow, int64_t m, const 
                  const double* d_alpha_k, const int64_t* d_inlier_idx, const double v_in[3], const double w_in[3], double k_in,
                  int const_acceleration, int flow_index_mode, double* d_inl_out, const RefineTail* tail, const RansacBest* d_best,
                  void* ws_base, RefineRun* run, RefineState* hs_prefetch, double* d_zpartials, bool exact = false,
-                 const FinishClaim* claim = nullptr);
+                 const FinishClaim* claim = nullptr, const FrameHandoff* handoff = nullptr);
 // refine_poll's return value when a guard of the radius-factorised path tripped: nothing was written to the outputs; run the solve again with exact = true
 constexpr int kRcRefineRestartExact = 1;
 int refine_device(Ctx* c, const double* d_flow, int64_t n_flow, int64_t m, const double* d_inl, const double* d_alpha,
