@@ -383,6 +383,20 @@ int rsdsfm_set_frame_tail(rsdsfm_ctx* ctx, int mode);
  * result) compacts in both modes.  Copied to the lanes of rsdsfm_solve_frames_dev.  Which launches run, never a result: both modes
  * return the same bytes. */
 int rsdsfm_set_frame_handoff(rsdsfm_ctx* ctx, int mode);
+/* The pixel pass of a frame solve's RANSAC (analytic LM trajectory), where a dense frame is solved in the minimal solver's launch:
+ *   0 (default) = the solver workgroups predict, from a fixed lattice of at most 768 pixels of the flow image, after how many accepted LM
+ *       steps (1 or 2) each hypothesis' depth solve ends, and the pass fuses the score of that iterate alone; a hypothesis that ends
+ *       elsewhere gets its score from the scoring pass, as one that ends after 0 or 3 steps always has;
+ *   1 = the pass fuses the scores of both iterates for every hypothesis;
+ *   2 = mode 0 with the prediction inverted and none of the pass's scores taken (tests: every hypothesis is scored by the scoring pass).
+ * Every other caller of the pass (rsdsfm_ransac*, the tiled driver, a frame with dropped pixels, rsdsfm_set_lm_arithmetic(1)) runs the
+ * two-iterate pass in every mode.  The prediction is a function of the flow image and the samples alone.  Copied to the lanes of
+ * rsdsfm_solve_frames_dev.  A mispredicted hypothesis' error sum comes from the scoring pass instead of the closed form (last bits of a
+ * trial's error sum, which decide a pick only inside the tie guard's margin); the frame solve's outputs are the same in every mode. */
+int rsdsfm_set_frame_predict(rsdsfm_ctx* ctx, int mode);
+/* hypotheses whose pixel pass fused their predicted iterate alone (rsdsfm_set_frame_predict 0 / 2) on this context and its sequence lanes,
+ * discarded speculative runs included, and how many of them ended at that iterate.  Waits for the contexts' streams. */
+int rsdsfm_lma_predict_stats(rsdsfm_ctx* ctx, int64_t* hypotheses, int64_t* ended_where_predicted);
 /* minimal::ransac on device-resident inputs.  The arrays of `out` (inlier_idx, inliers, alpha, alpha_k, mask,
  * inv_depth) are DEVICE pointers with capacity n (each may be NULL); its trial_* arrays are HOST pointers.
  * samples_9xT_or_null is a HOST pointer.  Synchronises once at the end to return the scalars of `out`. */

@@ -287,6 +287,12 @@ class Solver:
         self._check(self.lib.rsdsfm_lma_count_only(self._ctx, C.byref(a), C.byref(b)), "rsdsfm_lma_count_only")
         return int(a.value), int(b.value)
 
+    def lma_predict_stats(self):
+        """(hypotheses whose pixel pass fused their predicted iterate alone, those of them that ended there) -- rsdsfm_lma_predict_stats"""
+        a, b = C.c_int64(0), C.c_int64(0)
+        self._check(self.lib.rsdsfm_lma_predict_stats(self._ctx, C.byref(a), C.byref(b)), "rsdsfm_lma_predict_stats")
+        return int(a.value), int(b.value)
+
     def ransac_restarts(self):
         """RANSAC runs of this context that started over with the standard functions (rsdsfm_ransac_restarts)"""
         n = C.c_int64()
@@ -606,6 +612,11 @@ class Solver:
         """how a frame solve's refinement gets its inliers (rsdsfm_set_frame_handoff): 0 (default) the first refinement pass gathers them from
         the final stage's block-local lists, 1 the compaction launch; identical results"""
         self._check(self.lib.rsdsfm_set_frame_handoff(self._ctx, int(mode)), "rsdsfm_set_frame_handoff")
+
+    def set_frame_predict(self, mode):
+        """the pixel pass of a dense frame's RANSAC (rsdsfm_set_frame_predict): 0 (default) each hypothesis fuses the iterate the solver's launch
+        predicted for it, 1 both iterates for every hypothesis, 2 the prediction inverted and the pass's scores discarded (tests); identical outputs of the frame solve"""
+        self._check(self.lib.rsdsfm_set_frame_predict(self._ctx, int(mode)), "rsdsfm_set_frame_predict")
 
     def prepared_frames_solve(self, jobs, trials=50, tol=0.05, use_acceleration_mode=False, use_refinement=True, depth_mode=DEPTH_CERES_LM,
                               k_sign_mode=K_COMPAT, flow_threshold=1e-10, flow_index_mode=FLOW_COMPAT_RANK, use_global_shutter_mode=False):

@@ -349,6 +349,29 @@ int rsdsfm_lma_count_only(rsdsfm_ctx* ctx, int64_t* runs, int64_t* lazy_runs) {
     return RSDSFM_OK;
 }
 
+int rsdsfm_lma_predict_stats(rsdsfm_ctx* ctx, int64_t* hypotheses, int64_t* ended_where_predicted) {
+    CTX_OR_FAIL(ctx);
+    if (!hypotheses || !ended_where_predicted) return fail(c, RSDSFM_ERR_INVALID, "lma predict stats: null output");
+    // (the counters live on the device, behind the minimal solver's range-flag word: the decide stage adds to them, no solve reads them back)
+    int64_t h = 0, e = 0;
+    auto add = [&](Ctx* x) -> int {
+        if (!x->d_core_flag) return RSDSFM_OK;
+        DeviceGuard guard(x);
+        unsigned long long w[2] = {0, 0};
+        RSDSFM_HIP_CHECK(c, hipStreamSynchronize(x->stream));
+        RSDSFM_HIP_CHECK(c, hipMemcpy(w, x->d_core_flag + 4, sizeof(w), hipMemcpyDeviceToHost));
+        h += (int64_t)w[0], e += (int64_t)w[1];
+        return RSDSFM_OK;
+    };
+    int rc = add(c);
+    for (rsdsfm_ctx* lane : c->lanes)
+        if (rc == RSDSFM_OK) rc = add(&lane->c);
+    if (rc != RSDSFM_OK) return rc;
+    *hypotheses = h;
+    *ended_where_predicted = e;
+    return RSDSFM_OK;
+}
+
 int rsdsfm_lma_restarts(rsdsfm_ctx* ctx, int64_t* count, int32_t* last_guards) {
     CTX_OR_FAIL(ctx);
     if (!count) return fail(c, RSDSFM_ERR_INVALID, "lma restarts: null output");

@@ -294,8 +294,9 @@ __device__ __forceinline__ int lma_decide(const double* row, int64_t n, const Lm
         return 0;
     }
     const double phi2 = phi * phi;
-    for (int c = 0; c < cd.nc; ++c)
-        if (cd.steps[c] == st.n_hist && cd.phi2[c] == phi2) {
+#pragma unroll  // (compile-time indices: a caller's own LmaCand -- ransac_lma_rows_decide_kernel's view -- stays out of scratch)
+    for (int c = 0; c < kLmaNC; ++c)
+        if (c < cd.nc && cd.steps[c] == st.n_hist && cd.phi2[c] == phi2) {
             count = row[kLmaRowScore + 2 * c];
             err = row[kLmaRowScore + 2 * c + 1];
             scored = true;

@@ -10,6 +10,8 @@
 #include <float.h>
 
 #include "device_math.hpp"
+#include "lma_common.hpp"
+#include "lma_stages.hpp"
 #include "rsdsfm_internal.hpp"
 
 namespace rsdsfm {
@@ -784,13 +786,14 @@ __device__ __forceinline__ void minimal9_body(double* lds, int block, int nblock
                                               const double* __restrict__ u, const double* __restrict__ alpha,
                                               const double* __restrict__ alpha_k, const int32_t* __restrict__ samples, int T,
                                               int use_alpha_k, int k_sign_mode, double* __restrict__ hyp_out,
-                                              uint64_t* __restrict__ zero_words, int64_t n_zero_words, const Minimal9Direct& direct) {
+                                              uint64_t* __restrict__ zero_words, int64_t n_zero_words, const Minimal9Direct& direct,
+                                              double* pose_lds = nullptr) {
     // RANSAC: the per-hypothesis LM states, score marks and flag words must be zero before the depth solves start; the workgroups of
     // this launch clear them on the way (8-byte words, grid-strided) instead of a fill launch in front of it
     if (zero_words)
         for (int64_t i = (int64_t)block * 64 + lane; i < n_zero_words; i += (int64_t)nblocks * 64) zero_words[i] = 0ull;
     const int t = COOP ? block : block * 64 + lane;
-    if (t >= T) return;  // per-lane independent work, no workgroup barriers below
+    if (t >= T) return;  // per-lane independent work, no workgroup barriers below (the caller's barrier, if any, is behind this function)
     const unsigned long long body_clk0 = (COOP && direct.probe) ? __builtin_amdgcn_s_memtime() : 0ull;
     LVec base{lds + lane};
     LVec Z = base.at(0), V = base.at(81), sv = base.at(162), col = base.at(171);
@@ -1047,6 +1050,12 @@ __device__ __forceinline__ void minimal9_body(double* lds, int block, int nblock
     o[5] = e[2];
     o[6] = k;
     o[7] = (double)rc;
+    if (pose_lds) {  // (minimal9_flatten_kernel: the workgroup's other waves take the pose from here behind its barrier)
+        pose_lds[0] = w_hat[7], pose_lds[1] = w_hat[2], pose_lds[2] = w_hat[3];
+        pose_lds[3] = e[0], pose_lds[4] = e[1], pose_lds[5] = e[2];
+        pose_lds[6] = k;
+        pose_lds[7] = (double)rc;
+    }
 }
 
 template <bool COOP>
@@ -1075,19 +1084,108 @@ __global__ __launch_bounds__(64) void minimal9_kernel(const double* __restrict__
 // ---------------------------------------------------------------------------------------------------
 constexpr int kDF_W = 8, kDF_H = 64;  // tile columns (one 128-byte line per image row) x tile rows (one wave per column)
 
+// The predictor's lattice: gx x gy points, a function of (rows, cols) only, spread over the whole frame -- point (ix, iy) is pixel
+// (column (2 ix + 1) cols / (2 gx), row (2 iy + 1) rows / (2 gy)), integer division.  32 x 24 = kPredS points for every frame of at least
+// 32 columns and 24 rows; a frame with fewer than kPredS pixels uses all of them (gx = cols, gy = rows).  tests/test_lma_predict_cpu.py
+// restates the rule.
+constexpr int kPredS = 768, kPredLanes = 192, kPredPer = kPredS / kPredLanes;  // lattice points at most; lanes of waves 1 - 3; points per lane
+__device__ __forceinline__ void pred_lattice(int rows, int cols, int& gx, int& gy) {
+    gx = min(cols, 32);
+    gy = min(rows, kPredS / gx);
+    gx = min(cols, kPredS / gy);
+}
+
 __global__ __launch_bounds__(256) void minimal9_flatten_kernel(const int32_t* __restrict__ samples, int T, int use_alpha_k, int k_sign_mode,
                                                               double* __restrict__ hyp_out, uint64_t* __restrict__ zero_words,
                                                               int64_t n_zero_words, Minimal9Direct direct, double thr,
                                                               double2* __restrict__ q, double2* __restrict__ u,
                                                               double* __restrict__ alpha, double* __restrict__ alpha_k,
                                                               unsigned long long* __restrict__ counters, int64_t* __restrict__ total_out,
-                                                              int tiles_x, int nflat) {
+                                                              int tiles_x, int nflat, int* __restrict__ pred_steps, int pred_invert, const LmaPlan plan) {
     extern __shared__ double lds[];
     const int tid = threadIdx.x;
     if ((int)blockIdx.x < T) {
-        if (tid >= 64) return;
-        minimal9_body<true>(lds, (int)blockIdx.x, T, tid, nullptr, nullptr, nullptr, nullptr, samples, T, use_alpha_k, k_sign_mode, hyp_out, zero_words,
-                            n_zero_words, direct);
+        const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);  // (wave-uniform by construction: the roles below are scalar branches)
+        if (!pred_steps) {
+            if (wv != 0) return;
+            minimal9_body<true>(lds, (int)blockIdx.x, T, tid, nullptr, nullptr, nullptr, nullptr, samples, T, use_alpha_k, k_sign_mode, hyp_out, zero_words,
+                                n_zero_words, direct);
+            return;
+        }
+        // ---- with the prediction of the iterate the hypothesis' depth solve ends at.  lma_decide settles that from the sums A .. E, G of ALL
+        // pixels; its thresholds are far apart in B / A (phi shrinks by ~1e-4 per accepted step), so the sums of a lattice of <= kPredS pixels
+        // decide the same.  Waves 1 - 3 form their lattice points during the SVD (statically allocated LDS and registers only: the dynamic
+        // block is wave 0's), everybody meets at the barrier -- minimal9_body returns on every path --, then the lattice is evaluated under the
+        // pose, reduced in a fixed order, and one lane runs the trust-region loop.  A function of the flow image and the samples alone.
+        __shared__ double s_pose[8], s_wsum[3][8], s_prow[kLmaRow], s_phist[kMaxIter];
+        PixIn px[kPredPer];
+        bool ok[kPredPer];
+        if (wv == 0) {
+            minimal9_body<true>(lds, (int)blockIdx.x, T, tid, nullptr, nullptr, nullptr, nullptr, samples, T, use_alpha_k, k_sign_mode, hyp_out, zero_words,
+                                n_zero_words, direct, s_pose);
+        } else {
+            int gx, gy;
+            pred_lattice(direct.rows, direct.cols, gx, gy);
+            const double2* img = reinterpret_cast<const double2*>(direct.img);
+#pragma unroll
+            for (int m = 0; m < kPredPer; ++m) {
+                const int j = (tid - 64) + m * kPredLanes;  // lattice point j: column ix = j % gx, row iy = j / gx of the gx x gy lattice
+                const bool in = j < gx * gy;
+                const int ix = in ? j % gx : 0, iy = in ? j / gx : 0;
+                const int pc = (int)(((int64_t)(2 * ix + 1) * direct.cols) / (2 * gx)), pr = (int)(((int64_t)(2 * iy + 1) * direct.rows) / (2 * gy));
+                const double2 f = img[(int64_t)pr * direct.cols + pc];
+                const FlatPoint fp = flatten_point(f, pc, pr, direct.fx, direct.fy, direct.cx, direct.cy, direct.gamma, (double)direct.rows);
+                px[m].x = fp.qx, px[m].y = fp.qy, px[m].ux = fp.ux, px[m].uy = fp.uy;
+                px[m].al = direct.alpha_ones ? fp.alpha * 0.0 + 1.0 : fp.alpha;
+                px[m].ak = fp.alpha_k;
+                ok[m] = in && f.x * f.x + f.y * f.y > thr;  // (the flatten's drop rule)
+            }
+        }
+        __syncthreads();
+        if (wv != 0) {
+            Pose pose;
+            pose.w[0] = s_pose[0], pose.w[1] = s_pose[1], pose.w[2] = s_pose[2];
+            pose.v[0] = s_pose[3], pose.v[1] = s_pose[4], pose.v[2] = s_pose[5];
+            pose.k = s_pose[6];
+            const double two_over = 2.0 / (2.0 + pose.k);
+            double A = 0.0, B = 0.0, C = 0.0, D = 0.0, E = 0.0, G = 0.0, cnt = 0.0;
+#pragma unroll
+            for (int m = 0; m < kPredPer; ++m) {
+                if (ok[m]) {
+                    const LmaPx v = lma_pixel(px[m].x, px[m].y, px[m].ux, px[m].uy, px[m].al, px[m].ak, pose, two_over);
+                    A += v.a;
+                    B += v.ge;
+                    C = __builtin_fma(v.e0, v.e0, C);
+                    D = __builtin_fma(v.rhos, v.rhos, D);
+                    E = __builtin_fma(v.rhos, v.e0, E);
+                    G = lma_max_abs(G, v.g);
+                    cnt += 1.0;
+                }
+            }
+            A = wave_sum(A), B = wave_sum(B), C = wave_sum(C), D = wave_sum(D), E = wave_sum(E), cnt = wave_sum(cnt);
+            G = wave_max(G);  // (never a NaN: lma_max_abs drops one, the sums carry it)
+            if ((tid & 63) == 0) {
+                double* w = s_wsum[wv - 1];
+                w[0] = A, w[1] = B, w[2] = C, w[3] = D, w[4] = E, w[5] = G, w[6] = cnt;
+            }
+        }
+        __syncthreads();
+        if (tid == 64) {
+            for (int j = 0; j < kLmaRow; ++j) s_prow[j] = 0.0;  // (no clamped pixels' walk, no list: the closed form alone)
+            for (int j = 0; j < 5; ++j) s_prow[j] = (s_wsum[0][j] + s_wsum[1][j]) + s_wsum[2][j];
+            s_prow[kLmaG] = fmax(fmax(s_wsum[0][5], s_wsum[1][5]), s_wsum[2][5]);
+            const int64_t used = (int64_t)((s_wsum[0][6] + s_wsum[1][6]) + s_wsum[2][6]);
+            LmaCand none;  // (no fused scores to look up)
+            none.nc = 0;
+            LmScal st;
+            bool scored;
+            double count, err;
+            const int fb = lma_decide(s_prow, used, none, plan, false, st, s_phist, scored, count, err);
+            // the rule: the accepted-step count where it is 1 or 2, else 2 (0 or 3 steps, a guard, a non-finite sum, a failed or NaN pose)
+            int p = (s_pose[7] == 0.0 && !fb && (st.n_hist == 1 || st.n_hist == 2)) ? st.n_hist : 2;
+            if (pred_invert) p = 3 - p;
+            pred_steps[blockIdx.x] = p;
+        }
         return;
     }
     // ---- dense flatten of one 8 x 64 tile (the tile lives at the start of the dynamic LDS block) ----
@@ -1144,7 +1242,7 @@ __global__ __launch_bounds__(256) void minimal9_flatten_kernel(const int32_t* __
 
 int minimal9_flatten_launch(Ctx* c, const int32_t* samples, int T, int use_alpha_k, int k_sign_mode, double* hyp_out, void* zero_begin, size_t zero_bytes,
                             const Minimal9Direct& direct, double thr, double* d_q, double* d_u, double* d_alpha, double* d_alpha_k,
-                            unsigned long long* d_counters, int64_t* total_out) {
+                            unsigned long long* d_counters, int64_t* total_out, int* pred_steps, int pred_invert) {
     const size_t lds_bytes = (size_t)((use_alpha_k ? kSlotsK : kSlotsNoK) + kCoopSlots) * 64 * sizeof(double);
     static_assert(sizeof(double2) * kDF_H * (kDF_W + 1) <= (size_t)kSlotsNoK * 64 * sizeof(double), "the flatten tile fits the solver's LDS block");
     static bool attr_set_dev[64] = {false};
@@ -1158,7 +1256,7 @@ int minimal9_flatten_launch(Ctx* c, const int32_t* samples, int T, int use_alpha
     const int nflat = tiles_x * tiles_y;
     hipLaunchKernelGGL(minimal9_flatten_kernel, dim3(T + nflat), dim3(256), lds_bytes, c->stream, samples, T, use_alpha_k, k_sign_mode, hyp_out,
                        reinterpret_cast<uint64_t*>(zero_begin), (int64_t)(zero_bytes / 8), direct, thr, reinterpret_cast<double2*>(d_q),
-                       reinterpret_cast<double2*>(d_u), d_alpha, d_alpha_k, d_counters, total_out, tiles_x, nflat);
+                       reinterpret_cast<double2*>(d_u), d_alpha, d_alpha_k, d_counters, total_out, tiles_x, nflat, pred_steps, pred_invert, lma_plan());
     RSDSFM_HIP_CHECK(c, hipGetLastError());
     return RSDSFM_OK;
 }

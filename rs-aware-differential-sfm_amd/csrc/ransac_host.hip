@@ -146,11 +146,15 @@ int ransac_advance(Ctx* c, RansacRun& R, bool yield_at_wait) {
                         dir.core_flag = c->d_core_flag;
                         dir.core_epoch = R.core_epoch = c->core_epoch;
                     }
-                    if (R.direct && R.dense && T <= c->num_cus * 2)  // one launch: T solver workgroups + the dense flatten's
+                    R.own_pass = false;
+                    if (R.direct && R.dense && T <= c->num_cus * 2) {  // one launch: T solver workgroups + the dense flatten's
+                        // (... and, for the analytic pass, the prediction of the iterate each hypothesis ends at: Ctx::frame_predict)
+                        R.own_pass = R.analytic && c->frame_predict != 1;
                         rc = minimal9_flatten_launch(c, R.h_samples_pinned, T, R.use_alpha_k, R.k_sign_mode, R.d_hyp, zero_in_minimal9 ? R.zero_begin : nullptr,
                                                      zero_in_minimal9 ? R.zero_bytes : 0, dir, R.dense->thr, R.dense->d_q, R.dense->d_u, R.dense->d_alpha,
-                                                     R.dense->d_alpha_k, R.dense->d_counters, R.dense->total_out);
-                    else
+                                                     R.dense->d_alpha_k, R.dense->d_counters, R.dense->total_out, R.own_pass ? R.d_pred_steps : nullptr,
+                                                     c->frame_predict == 2 ? 1 : 0);
+                    } else
                         rc = minimal9_launch(c, R.d_q, R.d_u, R.d_a, R.d_ak, R.h_samples_pinned, T, R.use_alpha_k, R.k_sign_mode, R.d_hyp,
                                              zero_in_minimal9 ? R.zero_begin : nullptr, zero_in_minimal9 ? R.zero_bytes : 0, &dir);
                     if (rc != RSDSFM_OK) return rc;
@@ -190,7 +194,8 @@ int ransac_advance(Ctx* c, RansacRun& R, bool yield_at_wait) {
                     // back as "still running": rounds 1, 2, ... below are the iterate-by-iterate kernels', where only such hypotheses take part
                     rc = ransac_lma_launch(c, R.d_q, R.d_u, R.d_a, R.d_ak, n, R.d_hyp + (size_t)b0 * 8, B, R.d_states + b0, R.d_partials, R.d_flags,
                                            R.d_scored + b0, R.d_tcount + b0, R.d_terr + b0, tol, R.lma_cand, 2, R.d_irr_count, R.d_irr_list, R.d_unscored,
-                                           nullptr, R.core_epoch ? c->d_core_flag : nullptr, R.core_epoch, R.count_only);
+                                           nullptr, R.core_epoch ? c->d_core_flag : nullptr, R.core_epoch, R.count_only,
+                                           R.own_pass ? R.d_pred_steps + b0 : nullptr, reinterpret_cast<unsigned long long*>(c->d_core_flag + 4), c->frame_predict == 2);
                 } else {
                     rc = ransac_lm_round_launch(c, R.d_q, R.d_u, R.d_a, R.d_ak, n, R.d_hyp + (size_t)b0 * 8, B, R.d_states + b0, R.d_partials, R.d_flags,
                                                 R.d_scored + b0, R.d_tcount + b0, R.d_terr + b0, round, tol, R.k0, R.fused_base, R.core_math,
@@ -480,7 +485,7 @@ int ransac_begin(Ctx* c, const double* d_q, const double* d_u, const double* d_a
     const int Tn = std::max(T, 1);
     const int batch = std::min(Tn, kRansacBatch);
     const size_t partials_doubles = std::max<size_t>((size_t)ransac_lm_partials_doubles(c, n, batch), (size_t)ransac_lma_partials_doubles(c, n, batch));
-    size_t need = Arena::need(sizeof(double) * Tn * 8) + Arena::need(sizeof(int) * batch) + Arena::need(sizeof(int) * ransac_lma_list_ints(batch)) +
+    size_t need = Arena::need(sizeof(double) * Tn * 8) + Arena::need(sizeof(int) * batch) + Arena::need(sizeof(int) * Tn) + Arena::need(sizeof(int) * ransac_lma_list_ints(batch)) +
                   Arena::need(sizeof(LmState) * Tn) + Arena::need(sizeof(double) * partials_doubles) +
                   Arena::need(sizeof(int) * 8) + 2 * Arena::need(sizeof(int) * Tn) + 2 * Arena::need(sizeof(double) * Tn) + Arena::need(sizeof(RansacBest)) +
                   2 * Arena::need(sizeof(int64_t) * 2048) + Arena::need(sizeof(double) * (size_t)n) + Arena::need((size_t)n) + 4096;
@@ -497,6 +502,7 @@ int ransac_begin(Ctx* c, const double* d_q, const double* d_u, const double* d_a
     R.zero_bytes = (size_t)((ws.base + ws.off) - R.zero_begin);
     R.d_irr_list = ws.take<int>(ransac_lma_list_ints(batch));
     R.d_unscored = ws.take<int>(batch);
+    R.d_pred_steps = ws.take<int>(Tn);
     R.d_partials = ws.take<double>(partials_doubles);
     R.d_tcount = ws.take<double>(Tn);
     R.d_terr = ws.take<double>(Tn);

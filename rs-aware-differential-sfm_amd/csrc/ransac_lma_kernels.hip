@@ -7,6 +7,9 @@
 //                             pixel range -- no cross-lane reduction, no LDS, no barrier inside the pixel loop (the iterate-by-iterate
 //                             kernel reduces 22 sums across the workgroup per hypothesis and tile).  The pixels of guards (a) / (b) go
 //                             to the hypothesis' list.
+//   ransac_lma_own_kernel     the same pass with ONE fused iterate per hypothesis, the hypothesis' OWN: the one the solver's launch predicted it
+//                             ends at (minimal9_flatten_kernel: pred_steps).  A hypothesis ends at exactly one iterate, so the score at the other
+//                             is work the result does not need; a hypothesis that ends elsewhere is "not scored" and takes the scoring pass.
 //   ransac_lma_rows_kernel    one workgroup per hypothesis: fixed-order reduction of the workgroups' partial rows, the listed pixels on the
 //                             reference's exact recurrence (sorted by pixel index: deterministic sums) -> the row the decide stage consumes
 //                             (the all-gather payload of the column-tiled solve)
@@ -53,12 +56,18 @@ __device__ __forceinline__ bool pose_nan(const Pose& p) {
 // ERR = false (the frame solve's RANSAC: `LmaCand::count_only`): inlier COUNTS only.  minimal.cc:278-285 looks at a trial's error sum only to
 // break a tie in the count, so the pass leaves the two square roots per pixel-hypothesis out and ransac_pick_kernel asks for the exact error
 // sums (ransac_score_kernel: the reference's arithmetic) of the trials that share the best count, when there is more than one.
-template <int NC, bool ERR>
-__global__ __launch_bounds__(kLB) __attribute__((amdgpu_waves_per_eu(4, 5))) void ransac_lma_kernel(const double2* __restrict__ q, const double2* __restrict__ u, const double* __restrict__ alpha,
-                                                        const double* __restrict__ alpha_k, int64_t n, const double* __restrict__ hyp, int T,
-                                                        const LmaCand cd, double* __restrict__ partials, int* __restrict__ irr_count,
-                                                        int* __restrict__ irr_list, int64_t chunk, unsigned long long* __restrict__ clk_probe, int clk_bid,
-                                                        int Tg, int nwg) {
+// which of the pass's two candidate iterates a predicted step count selects (the pixel pass and the rows / decide stage must agree)
+__device__ __forceinline__ int lma_own_index(const LmaCand& cd, int pred) { return pred == cd.steps[1] ? 1 : 0; }
+
+// The body of both forms.  OWN (NC = 1): phi^2 of the lane's hypothesis is cd.phi2[lma_own_index(pred_steps[t])] -- a per-lane value at no cost,
+// the lane owns the hypothesis -- and score slot 0 of the partial row carries that iterate: the same per-pixel values added in the same order
+// as the slot of that iterate in the two-iterate pass.
+template <int NC, bool ERR, bool OWN>
+__device__ __forceinline__ void lma_pass_body(const double2* __restrict__ q, const double2* __restrict__ u, const double* __restrict__ alpha,
+                                              const double* __restrict__ alpha_k, int64_t n, const double* __restrict__ hyp, int T, const LmaCand& cd,
+                                              double* __restrict__ partials, int* __restrict__ irr_count, int* __restrict__ irr_list, int64_t chunk,
+                                              unsigned long long* __restrict__ clk_probe, int clk_bid, int Tg, int nwg, const int* __restrict__ pred_steps) {
+    static_assert(!OWN || NC == 1, "the own-iterate form fuses one iterate");
     __shared__ double s_part[kLB][kLmaSlots + 1];
     const int g = threadIdx.x;
     // rsdsfm_set_profiling: one lane of one workgroup in the middle of the launch (clk_bid; -1 = off) stamps the shader clock counter and the
@@ -89,6 +98,7 @@ __global__ __launch_bounds__(kLB) __attribute__((amdgpu_waves_per_eu(4, 5))) voi
     if (active) {
         const Pose pose = load_pose(hyp, t);
         const double two_over = 2.0 / (2.0 + pose.k);
+        const double phi2_own = OWN ? (lma_own_index(cd, pred_steps[t]) ? cd.phi2[1] : cd.phi2[0]) : 0.0;
         // one pixel under this lane's hypothesis; returns whether it goes to the list.  Straight-line on purpose (no branch around the square
         // roots: the error of a pixel that is not an inlier is multiplied by a 0.0 mask instead of being skipped -- the argument is floored into
         // the core's range first, so the product is exact and the sum has the same bits), so that the two pixels of an iteration form ONE basic
@@ -105,7 +115,7 @@ __global__ __launch_bounds__(kLB) __attribute__((amdgpu_waves_per_eu(4, 5))) voi
             bool listed = v.clamped;
 #pragma unroll
             for (int c = 0; c < NC; ++c) {
-                const double e2 = __builtin_fma(v.ge, cd.phi2[c], v.a);
+                const double e2 = __builtin_fma(v.ge, OWN ? phi2_own : cd.phi2[c], v.a);
                 const bool in = e2 < cd.tol2;
                 listed = listed || (fabs(e2 - cd.tol2) <= m);
                 cnt[c] += in ? 1 : 0;
@@ -165,6 +175,24 @@ __global__ __launch_bounds__(kLB) __attribute__((amdgpu_waves_per_eu(4, 5))) voi
     }
 }
 
+template <int NC, bool ERR>
+__global__ __launch_bounds__(kLB) __attribute__((amdgpu_waves_per_eu(4, 5))) void ransac_lma_kernel(const double2* __restrict__ q, const double2* __restrict__ u, const double* __restrict__ alpha,
+                                                        const double* __restrict__ alpha_k, int64_t n, const double* __restrict__ hyp, int T,
+                                                        const LmaCand cd, double* __restrict__ partials, int* __restrict__ irr_count,
+                                                        int* __restrict__ irr_list, int64_t chunk, unsigned long long* __restrict__ clk_probe, int clk_bid,
+                                                        int Tg, int nwg) {
+    lma_pass_body<NC, ERR, false>(q, u, alpha, alpha_k, n, hyp, T, cd, partials, irr_count, irr_list, chunk, clk_probe, clk_bid, Tg, nwg, nullptr);
+}
+// cd: the TWO candidate iterates (nc = 2), of which every hypothesis fuses its own
+template <bool ERR>
+__global__ __launch_bounds__(kLB) __attribute__((amdgpu_waves_per_eu(4, 5))) void ransac_lma_own_kernel(const double2* __restrict__ q, const double2* __restrict__ u, const double* __restrict__ alpha,
+                                                        const double* __restrict__ alpha_k, int64_t n, const double* __restrict__ hyp, int T,
+                                                        const LmaCand cd, double* __restrict__ partials, int* __restrict__ irr_count,
+                                                        int* __restrict__ irr_list, int64_t chunk, unsigned long long* __restrict__ clk_probe, int clk_bid,
+                                                        int Tg, int nwg, const int* __restrict__ pred_steps) {
+    lma_pass_body<1, ERR, true>(q, u, alpha, alpha_k, n, hyp, T, cd, partials, irr_count, irr_list, chunk, clk_probe, clk_bid, Tg, nwg, pred_steps);
+}
+
 // flags: the RANSAC's flag words (ransac_host.hip): [1] += hypotheses that ended where no score was fused (+ their list), [3] |= 2 a guard
 // tripped (the run starts over on the iterate-by-iterate kernels), [4 + min(steps, 3)] histogram of the accepted steps
 __device__ __forceinline__ void lma_publish(int t, const LmScal& st, const double* hist_l, int fallback, bool scored, double count, double err,
@@ -217,13 +245,24 @@ __global__ __launch_bounds__(kLB) void ransac_lma_rows_decide_kernel(const doubl
                                                                     const LmaCand cd, const int* __restrict__ irr_count, const int* __restrict__ irr_list,
                                                                     LmState* states, int* flags, int* __restrict__ scored_out, double* __restrict__ trial_count,
                                                                     double* __restrict__ trial_err, int* __restrict__ unscored_list, int* guard_word,
-                                                                    const int* __restrict__ m9_core_flag, int m9_core_epoch) {
+                                                                    const int* __restrict__ m9_core_flag, int m9_core_epoch,
+                                                                    const int* __restrict__ pred_steps, unsigned long long* pred_stats, int pred_discard) {
     __shared__ double s_row[kLmaRow];
     const int t = blockIdx.x;
     // the minimal solver of this run met an SVD operand outside the range of its function cores (minimal9_kernels.hip): reported through the
     // run's flag word like ransac_lm_kernel does -- the host starts the run over with the standard functions
     if (t == 0 && threadIdx.x == 0 && m9_core_flag && *m9_core_flag == m9_core_epoch) atomicOr(&flags[3], 1);
-    lma_rows_stage(partials, nblocks, T, t, q, u, alpha, alpha_k, load_pose(hyp, t), cd, irr_count, irr_list, s_row);
+    // behind the own-iterate pass (pred_steps != null): this hypothesis' view of the candidates is the ONE iterate its lanes fused
+    LmaCand view = cd;
+    if (pred_steps) {
+        const int ci = lma_own_index(cd, pred_steps[t]);
+        // (pred_discard, rsdsfm_set_frame_predict 2: the pass fused the OTHER iterate and no score of it is taken -- every hypothesis is "not
+        // scored" and goes to the scoring pass, also one whose prediction was wrong, for which the other iterate is the right one)
+        view.nc = pred_discard ? 0 : 1;
+        view.steps[0] = ci ? cd.steps[1] : cd.steps[0];
+        view.phi2[0] = ci ? cd.phi2[1] : cd.phi2[0];
+    }
+    lma_rows_stage(partials, nblocks, T, t, q, u, alpha, alpha_k, load_pose(hyp, t), view, irr_count, irr_list, s_row);
     __syncthreads();
     if (threadIdx.x == 0) {
         LmScal st;
@@ -231,8 +270,12 @@ __global__ __launch_bounds__(kLB) void ransac_lma_rows_decide_kernel(const doubl
         bool scored;
         double count, err;
         const Pose pose = load_pose(hyp, t);
-        const int fb = lma_decide(s_row, n, cd, cd.plan, pose_nan(pose), st, hist_l, scored, count, err);
+        const int fb = lma_decide(s_row, n, view, cd.plan, pose_nan(pose), st, hist_l, scored, count, err);
         lma_publish(t, st, hist_l, fb, scored, count, err, states, flags, scored_out, trial_count, trial_err, flags + 4, unscored_list, guard_word, cd.count_only != 0);
+        if (pred_steps && pred_stats) {  // rsdsfm_lma_predict_stats: {hypotheses, those that ended where predicted}
+            atomicAdd(&pred_stats[0], 1ull);
+            if (!fb && scored && view.nc == 1 && st.n_hist == view.steps[0]) atomicAdd(&pred_stats[1], 1ull);
+        }
     }
 }
 
@@ -351,14 +394,16 @@ int64_t ransac_lma_partials_doubles(const Ctx* c, int64_t n, int batch) {
 size_t ransac_lma_list_ints(int batch) { return (size_t)batch * kLmaListCap; }
 
 static int lma_pass_launch(Ctx* c, const double* q, const double* u, const double* a, const double* ak, int64_t n, const double* hyp, int T,
-                           const LmaCand& cd, double* partials, int* irr_count, int* irr_list, int* grid_out, unsigned long long* clk = nullptr) {
-    // resident workgroups per CU of the kernel that is about to run (registers set it: 5 at 94 VGPRs)
+                           const LmaCand& cd, double* partials, int* irr_count, int* irr_list, int* grid_out, unsigned long long* clk = nullptr,
+                           const int* pred_steps = nullptr) {
+    // resident workgroups per CU of the kernel that is about to run (registers set it: 5 at 94 VGPRs); slot 0: the own-iterate form
     static int occ_tab[2][kLmaNC + 1] = {{0, 0, 0, 0}, {0, 0, 0, 0}};
-    const int nc = std::min(std::max(cd.nc, 1), (int)kLmaNC);
+    const int nc = pred_steps ? 0 : std::min(std::max(cd.nc, 1), (int)kLmaNC);
     int* occ = occ_tab[cd.count_only ? 1 : 0];
     if (occ[nc] == 0) {
         int nb = 0;
-        const void* fn = cd.count_only ? (nc == 1 ? reinterpret_cast<const void*>(&ransac_lma_kernel<1, false>) : nc == 2 ? reinterpret_cast<const void*>(&ransac_lma_kernel<2, false>) : reinterpret_cast<const void*>(&ransac_lma_kernel<3, false>))
+        const void* fn = pred_steps ? (cd.count_only ? reinterpret_cast<const void*>(&ransac_lma_own_kernel<false>) : reinterpret_cast<const void*>(&ransac_lma_own_kernel<true>))
+                         : cd.count_only ? (nc == 1 ? reinterpret_cast<const void*>(&ransac_lma_kernel<1, false>) : nc == 2 ? reinterpret_cast<const void*>(&ransac_lma_kernel<2, false>) : reinterpret_cast<const void*>(&ransac_lma_kernel<3, false>))
                                        : (nc == 1 ? reinterpret_cast<const void*>(&ransac_lma_kernel<1, true>) : nc == 2 ? reinterpret_cast<const void*>(&ransac_lma_kernel<2, true>) : reinterpret_cast<const void*>(&ransac_lma_kernel<3, true>));
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, kLB, 0) != hipSuccess || nb < 1) nb = 4;
         occ[nc] = nb;
@@ -386,7 +431,12 @@ static int lma_pass_launch(Ctx* c, const double* q, const double* u, const doubl
     const int clk_bid = clk ? grid / 2 : -1;
 #define RSDSFM_LMA_LAUNCH(NC, ERR) \
     hipLaunchKernelGGL((ransac_lma_kernel<NC, ERR>), dim3(grid), dim3(kLB), 0, c->stream, q2, u2, a, ak, n, hyp, T, cd, partials, irr_count, irr_list, chunk, clk, clk_bid, Tg, nwg)
-    if (cd.count_only) {
+    if (pred_steps) {
+        if (cd.count_only)
+            hipLaunchKernelGGL((ransac_lma_own_kernel<false>), dim3(grid), dim3(kLB), 0, c->stream, q2, u2, a, ak, n, hyp, T, cd, partials, irr_count, irr_list, chunk, clk, clk_bid, Tg, nwg, pred_steps);
+        else
+            hipLaunchKernelGGL((ransac_lma_own_kernel<true>), dim3(grid), dim3(kLB), 0, c->stream, q2, u2, a, ak, n, hyp, T, cd, partials, irr_count, irr_list, chunk, clk, clk_bid, Tg, nwg, pred_steps);
+    } else if (cd.count_only) {
         if (cd.nc == 1) RSDSFM_LMA_LAUNCH(1, false);
         else if (cd.nc == 2) RSDSFM_LMA_LAUNCH(2, false);
         else RSDSFM_LMA_LAUNCH(3, false);
@@ -402,13 +452,14 @@ static int lma_pass_launch(Ctx* c, const double* q, const double* u, const doubl
 int ransac_lma_launch(Ctx* c, const double* q, const double* u, const double* a, const double* ak, int64_t n, const double* hyp, int T,
                       LmState* states, double* partials, int* flags, int* scored, double* trial_count, double* trial_err, double tol,
                       const int* cand_steps, int ncand, int* irr_count, int* irr_list, int* unscored_list, int* guard_word, const int* m9_core_flag,
-                      int m9_core_epoch, bool count_only) {
+                      int m9_core_epoch, bool count_only, const int* pred_steps, unsigned long long* pred_stats, bool pred_discard) {
     if (T < 1 || T > kLB) return fail(c, RSDSFM_ERR_INVALID, "hypothesis batch of the analytic pass exceeds 256");
+    if (pred_steps && ncand != 2) return fail(c, RSDSFM_ERR_INVALID, "the own-iterate pass chooses between two candidate iterates");
     const LmaCand cd = lma_candidates(cand_steps, ncand, tol, count_only);
     int grid = 0;
     const bool prof = c->profile && c->ev_prof[0] && c->ev_prof[1];
     if (prof) RSDSFM_HIP_CHECK(c, hipEventRecord(c->ev_prof[0], c->stream));
-    int rc = lma_pass_launch(c, q, u, a, ak, n, hyp, T, cd, partials, irr_count, irr_list, &grid, prof ? c->d_clk_probe : nullptr);
+    int rc = lma_pass_launch(c, q, u, a, ak, n, hyp, T, cd, partials, irr_count, irr_list, &grid, prof ? c->d_clk_probe : nullptr, pred_steps);
     if (rc != RSDSFM_OK) return rc;
     if (prof) {
         RSDSFM_HIP_CHECK(c, hipEventRecord(c->ev_prof[1], c->stream));
@@ -417,7 +468,7 @@ int ransac_lma_launch(Ctx* c, const double* q, const double* u, const double* a,
     }
     hipLaunchKernelGGL(ransac_lma_rows_decide_kernel, dim3(T), dim3(kLB), 0, c->stream, partials, grid, T, reinterpret_cast<const double2*>(q),
                        reinterpret_cast<const double2*>(u), a, ak, n, hyp, cd, irr_count, irr_list, states, flags, scored, trial_count, trial_err,
-                       unscored_list, guard_word, m9_core_flag, m9_core_epoch);
+                       unscored_list, guard_word, m9_core_flag, m9_core_epoch, pred_steps, pred_stats, pred_discard ? 1 : 0);
     RSDSFM_HIP_CHECK(c, hipGetLastError());
     return RSDSFM_OK;
 }

@@ -138,7 +138,7 @@ struct Ctx {
     int ransac_score_idle = kScoreIdleLimit;  // consecutive solves (saturating) that did NOT need the separate scoring pass behind round 0; below the limit the pass is enqueued ahead of the host's flag read
     int refine_iters_hint = -1;    // slots (refine_kernels.hip; LM iterations + 1 as a rule) the context's previous refinement consumed (-1: none yet): length of the first chunk the host enqueues
     int ransac_standard_math = 0;  // > 0: that many of the context's next RANSACs run round 0 with the standard sqrt / reciprocal (set to 16 by a run that met an argument outside the range of the in-range cores and had to start over; ransac_lm_kernel CORE)
-    int* d_core_flag = nullptr;    // device word the minimal solver stores its launch epoch in when an SVD operand left the range of the function cores (persistent: never a stale value)
+    int* d_core_flag = nullptr;    // device word the minimal solver stores its launch epoch in when an SVD operand left the range of the function cores (persistent: never a stale value); 16 bytes behind it: the two counters of rsdsfm_lma_predict_stats
     int core_epoch = 0;
     int ransac_math_mode = 0;      // rsdsfm_set_ransac_math: 0 = in-range cores with restart (default), 1 = always the standard functions
     int64_t ransac_restarts = 0;   // RANSAC runs of this context that started over for that reason (rsdsfm_ransac_restarts)
@@ -219,6 +219,10 @@ struct Ctx {
     // rsdsfm_set_frame_handoff: 0 = the refinement's first pass gathers its inliers itself from the final stage's block-local lists (no compaction
     // launch between them), 1 = the compaction launch (ransac_scatter_kernel).  Which launches run, never a result.
     int frame_handoff = 0;
+    // rsdsfm_set_frame_predict: 0 = a dense frame solved in the solver's launch (minimal9_flatten_kernel) predicts there at which iterate each
+    // hypothesis ends and its pixel pass fuses that iterate alone (ransac_lma_own_kernel), 1 = the two-iterate pass, 2 = mode 0 with the
+    // prediction inverted and the pass's scores discarded (tests: every hypothesis takes the scoring pass).  Same outputs of the frame solve in every mode.
+    int frame_predict = 0;
     unsigned long long* d_flat_counters = nullptr;  // the two counters of minimal9_flatten_kernel (zero between launches)
     int seq_lanes = 0;               // rsdsfm_set_sequence_lanes (0 = kSequenceLanesDefault)
     // where the refinement's single-workgroup stage runs (rsdsfm_set_refine_stage): 0 = automatic -- in the prologue of the next slot's pass
@@ -425,9 +429,11 @@ struct DenseFlatten {
     unsigned long long* d_counters = nullptr;
     int64_t* total_out = nullptr;
 };
+// pred_steps (optional, [T], outside the zeroed region): the solver workgroups also predict, from a fixed lattice of pixels, after how many
+// accepted LM steps (1 or 2) each hypothesis' depth solve ends -- the iterate the own-iterate pixel pass fuses; pred_invert: 1 <-> 2 (tests)
 int minimal9_flatten_launch(Ctx* c, const int32_t* samples, int T, int use_alpha_k, int k_sign_mode, double* hyp_out, void* zero_begin, size_t zero_bytes,
                             const Minimal9Direct& direct, double thr, double* d_q, double* d_u, double* d_alpha, double* d_alpha_k,
-                            unsigned long long* d_counters, int64_t* total_out);
+                            unsigned long long* d_counters, int64_t* total_out, int* pred_steps = nullptr, int pred_invert = 0);
 }  // namespace rsdsfm
 
 namespace rsdsfm {
@@ -473,7 +479,8 @@ size_t ransac_lma_list_ints(int batch);
 int ransac_lma_launch(Ctx* c, const double* q, const double* u, const double* a, const double* ak, int64_t n, const double* hyp, int T,
                       LmState* states, double* partials, int* flags, int* scored, double* trial_count, double* trial_err, double tol,
                       const int* cand_steps, int ncand, int* irr_count, int* irr_list, int* unscored_list, int* guard_word,
-                      const int* m9_core_flag = nullptr, int m9_core_epoch = 0, bool count_only = false);
+                      const int* m9_core_flag = nullptr, int m9_core_epoch = 0, bool count_only = false, const int* pred_steps = nullptr,
+                      unsigned long long* pred_stats = nullptr, bool pred_discard = false);  // pred_steps != null: the own-iterate pass (cand_steps: the two candidates); pred_discard: none of its scores is taken
 int ransac_lma_rows_doubles();
 int ransac_lma_rows_launch(Ctx* c, const double* q, const double* u, const double* a, const double* ak, int64_t n, const double* hyp, int T,
                            double* partials, double tol, const int* cand_steps, int ncand, int* irr_count, int* irr_list, double* rows);
@@ -584,6 +591,8 @@ struct RansacRun {
     bool lma_tie_seen = false;  // the final pick of an iterate-by-iterate run saw a tie the analytic arithmetic could not have broken
     int lma_cand[2] = {2, 1}, lma_cand_next[2] = {0, 0};
     int *d_irr_count = nullptr, *d_irr_list = nullptr;
+    int* d_pred_steps = nullptr;  // [Tn] the solver launch's prediction of each hypothesis' accepted steps (1 or 2); outside the zeroed region
+    bool own_pass = false;        // this run's solver launch wrote d_pred_steps: the pixel pass fuses each hypothesis' own iterate
     bool restarted = false;
     bool tail_ahead = true;  // enqueue the caller's tail behind the SPECULATED final stage (otherwise only behind the definitive one)
     const Minimal9Direct* direct = nullptr;
