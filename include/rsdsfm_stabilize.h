@@ -36,7 +36,9 @@ typedef struct rsdsfm_stabilize_params {
     int32_t translation;  /* 0: only the rotation is smoothed (c~ = c, m = 0; scales are not read) */
     int32_t struct_bytes; /* 0 (zero-initialised struct) or sizeof(rsdsfm_stabilize_params), as rsdsfm_stabilize_params_init sets it; anything
                              else is refused: the caller was built against another layout */
-    int32_t reserved;     /* 0 */
+    int32_t last_frame;   /* 0: a clip call renders frames 0 .. nframes - 2, one per pair; 1: it also renders the clip's last frame from the last
+                             pair's depth map moved onto that frame (rsdsfm_last_frame.h).  Anything else is refused.  (The word was
+                             `reserved`, 0, before: same offset, same struct_bytes) */
 } rsdsfm_stabilize_params;
 
 /* sigma = 4.0, radius = 0, translation = 1, struct_bytes = sizeof */
@@ -79,9 +81,19 @@ int rsdsfm_stabilize_launches(int32_t rows, int32_t cols, int32_t count);
  *   - for p = 0 .. nframes - 2 in order, rsdsfm_stabilize_frame_dev of d_frames[p] with pair p's map and pose table and (M_p, m_p) into
  *     d_stab_images[p] (rows x cols x channels bytes) and d_masks_out_or_null[p] (rows x cols bytes), mode / q5_mode / iterations as there.
  * The smoothing is not causal, so nothing hooks into the solve.  Every output is, byte for byte, what those public calls give when made one
- * after another.  The last frame has no pair and is not rendered.  A broken link carries its scale over, as in the chain; with
- * translation == 0 the scales are not read at all.  valid_or_null: nframes - 1 HOST counts, fetched in one copy behind the last frame,
- * which the call then waits for; without it the frames are only enqueued on the context's stream. */
+ * after another.  The last frame has no pair and is not rendered unless `last_frame` is set.  A broken link carries its scale over, as in the
+ * chain; with translation == 0 the scales are not read at all.  valid_or_null: nframes - 1 HOST counts, fetched in one copy behind the last
+ * frame, which the call then waits for; without it the frames are only enqueued on the context's stream.
+ *
+ * With stabilize_params_or_null->last_frame == 1 (np = nframes - 1), behind the solve, the wait for its lanes and the fusion:
+ *   - rsdsfm_last_frame_dev (rsdsfm_last_frame.h) on pair np - 1's field, solved map and final motion into d_depth_maps[np], d_R[np], d_t[np];
+ *   - when fused maps are requested, rsdsfm_advance_depth_dev of d_fused_maps[np - 1] with the same field and motion into d_fused_maps[np];
+ *   - scales[np] = scales[np - 1];
+ *   - rsdsfm_virtual_poses with np + 1, and the frame loop runs p = 0 .. np.
+ * Then d_depth_maps, d_R, d_t, d_fused_maps_or_null, scales, M, m, d_stab_images, d_masks_out_or_null and valid_or_null have nframes
+ * entries; results, d_flows, seeds, d_masks_or_null, records and broken keep nframes - 1 (nframes - 2 for the links).  Every output is still,
+ * byte for byte, what those public calls give when made one after another, and everything the solve writes is what it writes without the
+ * flag. */
 int rsdsfm_stabilize_video_dev(rsdsfm_ctx* ctx, const uint8_t* const* d_frames, int32_t nframes, int32_t rows, int32_t cols, int32_t channels,
                                double fx, double fy, double cx, double cy, double gamma, const rsdsfm_flow_params* flow_params_or_null,
                                const rsdsfm_frame_params* params, const uint64_t* seeds, double* const* d_flows, double* const* d_depth_maps,

@@ -23,7 +23,7 @@
  * and what has been measured.
  *
  * NOT here: feathering between two neighbours' regions, multi-band blending, gains smoothed over time or solved jointly over the clip,
- * vignetting, occlusion tests between candidates, the clip's last frame, inpainting of pixels nobody saw (built since:
+ * vignetting, occlusion tests between candidates, the clip's last frame (built since: rsdsfm_last_frame.h), inpainting of pixels nobody saw (built since:
  * rsdsfm_stabilize_inpaint.h).
  */
 #ifndef RSDSFM_STABILIZE_BLEND_H
@@ -94,7 +94,11 @@ int rsdsfm_seam_gains(const uint64_t* sums8, int32_t channels, int64_t min_overl
  * blend_counts_or_null: HOST, (nframes - 1) x (2 + 4 radius) int64, per frame [none, own_untouched, (filled, blended) per offset -1, +1, -2,
  * +2, ...]; none and own_untouched are computed on the host from the own render's count.
  * With neither host array the passes are only enqueued; with either the call ends with one copy and one wait.
- * RSDSFM_ERR_INVALID in addition: a NULL or misaligned blend plane, a source plane that is the mask, bad blend params. */
+ * RSDSFM_ERR_INVALID in addition: a NULL or misaligned blend plane, a source plane that is the mask, bad blend params.
+ * With stabilize_params_or_null->last_frame == 1 the inner call renders the last frame too (rsdsfm_stabilize.h), the crop search takes nframes
+ * masks, rsdsfm_neighbour_poses is asked with nframes "pairs" and every per-frame loop runs p = 0 .. nframes - 1.  d_blend_images, d_blend_masks, d_blend_sources, gains_or_null and blend_counts_or_null
+ * then have nframes entries (rows), like the inner call's per-frame arrays; results, d_flows, seeds, the check masks, records and broken keep
+ * nframes - 1 (nframes - 2 for the links).  The rule "byte for byte those public calls one after another" holds as it stands. */
 int rsdsfm_stabilize_video_blended_dev(rsdsfm_ctx* ctx, const uint8_t* const* d_frames, int32_t nframes, int32_t rows, int32_t cols, int32_t channels,
                                        double fx, double fy, double cx, double cy, double gamma, const rsdsfm_flow_params* flow_params_or_null,
                                        const rsdsfm_frame_params* params, const uint64_t* seeds, double* const* d_flows, double* const* d_depth_maps,

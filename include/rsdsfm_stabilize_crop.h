@@ -22,7 +22,7 @@
  * and zoom") has the kernels, the launches, the bytes and what has been measured.
  *
  * NOT here: windows that vary over time, path optimisers that trade smoothness against crop, a search that re-renders until the mask is
- * full, blending at the seams, the clip's last frame.
+ * full, blending at the seams.  The clip's last frame is built since: rsdsfm_last_frame.h.
  */
 #ifndef RSDSFM_STABILIZE_CROP_H
 #define RSDSFM_STABILIZE_CROP_H
@@ -85,7 +85,11 @@ int rsdsfm_stabilize_window_launches(int32_t rows, int32_t cols);
  * Every output is byte for byte what those public calls give when made one after another; everything the inner call writes is what it
  * writes alone.  window_out: HOST, the window used.  No window (h = 0): crop images and masks are zeroed and none = rows cols.
  * crop_counts_or_null: HOST, (nframes - 1) x (2 + 2 radius) int64 with the fill's layout [none, own, -1, +1, ...]; with it the call waits
- * for the passes, without it they are only enqueued (the search's wait stays). */
+ * for the passes, without it they are only enqueued (the search's wait stays).
+ * With stabilize_params_or_null->last_frame == 1 the inner call renders the last frame too (rsdsfm_stabilize.h), the crop search takes nframes
+ * masks, rsdsfm_neighbour_poses is asked with nframes "pairs" and every per-frame loop runs p = 0 .. nframes - 1.  d_crop_images, d_crop_masks, d_crop_sources_or_null and crop_counts_or_null
+ * then have nframes entries (rows), like the inner call's per-frame arrays; results, d_flows, seeds, the check masks, records and broken keep
+ * nframes - 1 (nframes - 2 for the links).  The rule "byte for byte those public calls one after another" holds as it stands. */
 int rsdsfm_stabilize_video_cropped_dev(rsdsfm_ctx* ctx, const uint8_t* const* d_frames, int32_t nframes, int32_t rows, int32_t cols, int32_t channels,
                                        double fx, double fy, double cx, double cy, double gamma, const rsdsfm_flow_params* flow_params_or_null,
                                        const rsdsfm_frame_params* params, const uint64_t* seeds, double* const* d_flows, double* const* d_depth_maps,

@@ -10,15 +10,16 @@
  *   M_{q,n} = A~_q^T A_n,   m_{q,n} = (A~_q^T (c_n - c~_q)) / S_n          (pair n's own unit)
  * -- a point X in the coordinates of frame n's first scanline is M X + m in virtual camera q's -- and a stage C that writes only where
  * the output is still empty.  The candidates of frame q are asked in the order n = q - 1, q + 1, q - 2, q + 2, ..., q - radius,
- * q + radius (nearer first, previous before next; only 0 <= n <= npairs - 1: the clip's last frame has no pair, hence no depth); the first
+ * q + radius (nearer first, previous before next; only 0 <= n <= npairs - 1: the clip's last frame has no pair, hence no depth, unless
+ * `last_frame` of rsdsfm_stabilize_params is set: rsdsfm_last_frame.h gives it the last pair's, and npairs then counts it); the first
  * that offers a pixel keeps it.  The SOURCE ID of the neighbour at offset j is 2 |j| for j < 0 and 2 |j| + 1 for j > 0; 1 is the own frame,
  * 0 nobody.
  * tests/stabilize_fill_spec_numpy.py is the executable definition; the frame call reproduces it bit for bit, the host function to rounding.
  * DESIGN.md section 12 ("Border fill") has the launches, the bytes and what has been measured.
  *
  * NOT here: blending or feathering at the seams, exposure compensation between frames, occlusion tests between candidates (a fold of a
- * neighbour's map fills like any pixel), moving objects, the clip's last frame, inpainting of pixels nobody saw (built since:
- * rsdsfm_stabilize_inpaint.h).
+ * neighbour's map fills like any pixel), moving objects, inpainting of pixels nobody saw (built since: rsdsfm_stabilize_inpaint.h).  The
+ * clip's last frame is built since: rsdsfm_last_frame.h.
  */
 #ifndef RSDSFM_STABILIZE_FILL_H
 #define RSDSFM_STABILIZE_FILL_H
@@ -80,7 +81,11 @@ int rsdsfm_stabilize_fill_launches(int32_t rows, int32_t cols);
  * counts_or_null: HOST, (nframes - 1) x (2 + 2 radius) int64, per frame [none, own, offset -1, +1, -2, +2, ...] -- the index is the source
  * id; a skipped offset counts 0, none = rows cols - the rest, computed on the host.  With it the inner call is asked for its valid counts
  * (the `own` column; into valid_or_null or a buffer of this call's own) and waits as it does; the fill counts take one copy behind the last
- * launch and one wait.  Without it the fill passes are only enqueued on the context's stream. */
+ * launch and one wait.  Without it the fill passes are only enqueued on the context's stream.
+ * With stabilize_params_or_null->last_frame == 1 the inner call renders the last frame too (see there), rsdsfm_neighbour_poses is asked with
+ * nframes "pairs" and the loop runs p = 0 .. nframes - 1: the last frame has only previous candidates and is a candidate of the frames
+ * before it, under the offsets' existing source ids.  d_masks_out, d_sources_or_null and counts_or_null then have nframes entries (rows),
+ * like the inner call's per-frame arrays; the rule "byte for byte those public calls one after another" holds as it stands. */
 int rsdsfm_stabilize_video_filled_dev(rsdsfm_ctx* ctx, const uint8_t* const* d_frames, int32_t nframes, int32_t rows, int32_t cols, int32_t channels,
                                       double fx, double fy, double cx, double cy, double gamma, const rsdsfm_flow_params* flow_params_or_null,
                                       const rsdsfm_frame_params* params, const uint64_t* seeds, double* const* d_flows, double* const* d_depth_maps,

@@ -24,7 +24,7 @@
  * bytes and what has been measured.
  *
  * NOT here: exemplar, patch or diffusion inpainting (the values are a smooth interpolation: no texture is invented), temporal consistency of
- * the invented pixels (every frame is inpainted alone), the clip's last frame, the C++ mirror.
+ * the invented pixels (every frame is inpainted alone), the C++ mirror.  The clip's last frame is built since: rsdsfm_last_frame.h.
  */
 #ifndef RSDSFM_STABILIZE_INPAINT_H
 #define RSDSFM_STABILIZE_INPAINT_H
@@ -63,7 +63,11 @@ int rsdsfm_inpaint_launches(int32_t rows, int32_t cols);
  * inpaint_counts_or_null: HOST, nframes - 1 int64, the pixels written per frame; with it the call ends with one copy and one wait, without
  * it the passes are only enqueued.
  * RSDSFM_ERR_INVALID in addition: a NULL or misaligned inpaint plane, an inpaint plane that is one of the frame's blend planes or its other
- * inpaint plane. */
+ * inpaint plane.
+ * With stabilize_params_or_null->last_frame == 1 the inner call renders the last frame too (rsdsfm_stabilize.h), the crop search takes nframes
+ * masks, rsdsfm_neighbour_poses is asked with nframes "pairs" and every per-frame loop runs p = 0 .. nframes - 1.  d_inpaint_images, d_inpaint_sources_or_null and inpaint_counts_or_null
+ * then have nframes entries (rows), like the inner call's per-frame arrays; results, d_flows, seeds, the check masks, records and broken keep
+ * nframes - 1 (nframes - 2 for the links).  The rule "byte for byte those public calls one after another" holds as it stands. */
 int rsdsfm_stabilize_video_inpainted_dev(rsdsfm_ctx* ctx, const uint8_t* const* d_frames, int32_t nframes, int32_t rows, int32_t cols, int32_t channels,
                                          double fx, double fy, double cx, double cy, double gamma, const rsdsfm_flow_params* flow_params_or_null,
                                          const rsdsfm_frame_params* params, const uint64_t* seeds, double* const* d_flows, double* const* d_depth_maps,

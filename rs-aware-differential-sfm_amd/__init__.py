@@ -1579,7 +1579,8 @@ STABILIZE_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "rsdsfm_
 
 
 class StabilizeParams(C.Structure):
-    _fields_ = [("sigma", C.c_double), ("radius", C.c_int32), ("translation", C.c_int32), ("struct_bytes", C.c_int32), ("reserved", C.c_int32)]
+    _fields_ = [("sigma", C.c_double), ("radius", C.c_int32), ("translation", C.c_int32), ("struct_bytes", C.c_int32), ("last_frame", C.c_int32)]
+    reserved = property(lambda self: self.last_frame)  # the word's name before it meant anything
 
 
 def stabilize_declared_symbols():
@@ -1599,15 +1600,26 @@ def stabilize_default_params():
     return dict(sigma=p.sigma, radius=p.radius, translation=p.translation)
 
 
-def _stabilize_params(sigma, radius, translation):
+def _stabilize_params(sigma, radius, translation, last_frame=False):
     """a StabilizeParams with the given values over the defaults (sigma None: the default)"""
     p = StabilizeParams()
     if load_library().rsdsfm_stabilize_params_init(C.byref(p)) != OK:
         raise RsdsfmError("rsdsfm_stabilize_params_init failed")
     if sigma is not None:
         p.sigma = float(sigma)
-    p.radius, p.translation = int(radius), int(bool(translation))
+    p.radius, p.translation, p.last_frame = int(radius), int(bool(translation)), int(last_frame)
     return p
+
+
+def _need_all(n, **lists):
+    for what, lst in lists.items():
+        _need_entries(what, lst, n)
+
+
+def _need_entries(what, lst, n):
+    """a clip wrapper's list must have an entry for every frame the call writes: the library reads exactly n pointers"""
+    if lst is not None and len(lst) < n:
+        raise RsdsfmError("%s has %d entries, the call needs %d (one per rendered frame; last_frame=True renders every frame of the clip)" % (what, len(lst), n))
 
 
 def smooth_path(A, c, sigma=None, radius=0, translation=True):
@@ -1626,13 +1638,14 @@ def smooth_path(A, c, sigma=None, radius=0, translation=True):
     return A_s[:n].reshape(n, 3, 3), c_s[:n]
 
 
-def virtual_poses(A, c, A_s, c_s, scales, translation=True):
+def virtual_poses(A, c, A_s, c_s, scales, translation=True, last_frame=False):
     """every pair's virtual pose (rsdsfm_virtual_poses; host): M_q = A_s_q^T A_q, m_q = A_s_q^T (c_q - c_s_q) / S_q for q < F - 1 -- a point X in
     frame q's first-scanline coordinates is M_q X + m_q in the virtual camera's.  translation=False: m = 0 and scales (may be None) is not read.
-    -> (M (F - 1, 3, 3), m (F - 1, 3))"""
+    -> (M (F - 1, 3, 3), m (F - 1, 3)).  last_frame=True: the clip's last frame has a pose too (its scale is scales[F - 1], the last pair's
+    carried over): F entries."""
     a, cc, a_s, cc_s = _f64(A).reshape(-1, 9), _f64(c).reshape(-1, 3), _f64(A_s).reshape(-1, 9), _f64(c_s).reshape(-1, 3)
-    n = a.shape[0] - 1
-    if not (cc.shape[0] == a_s.shape[0] == cc_s.shape[0] == n + 1):
+    n = a.shape[0] - (0 if last_frame else 1)
+    if not (cc.shape[0] == a_s.shape[0] == cc_s.shape[0] == a.shape[0]):
         raise ValueError("the path and the smoothed path need the same number of frames")
     sc = None
     if translation:
@@ -1692,33 +1705,39 @@ class _StabilizeMixin:
                             want_valid=True, sigma=None, radius=0, translation=True, fuse_tol=None, d_masks=None, seeds=None, flow_params=None, a1=None,
                             a2=None, link_tol=None, min_links=None, radix_bits=None, mode=BACKPROJECT_RS, q5_mode=Q5_COMPAT, iterations=0, trials=50, tol=0.05,
                             use_acceleration_mode=False, use_refinement=True, depth_mode=DEPTH_CERES_LM, k_sign_mode=K_COMPAT, flow_threshold=1e-10,
-                            flow_index_mode=FLOW_COMPAT_RANK, use_global_shutter_mode=False):
+                            flow_index_mode=FLOW_COMPAT_RANK, use_global_shutter_mode=False, last_frame=False):
         """the stabilised clip in ONE call (rsdsfm_stabilize_video_dev): solve_video_linked_dev (d_flows, d_depth_maps, d_R, d_t all required), the
         fusion of the maps when d_fused (F - 1 buffers) is passed, smooth_path, virtual_poses and stabilize_frame_dev of frames 0 .. F - 2 into
         d_stab (and d_masks_out).  Returns solve_video_linked_dev's dict plus A_s, c_s, M, m and, with want_valid, valid (F - 1 counts; the
-        call then waits for the frames)."""
+        call then waits for the frames).  last_frame=True also renders frame F - 1, from the last pair's map moved onto it (last_frame_dev):
+        d_depth_maps, d_R, d_t, d_stab, d_masks_out and d_fused then need F entries, and scales, M, m and valid have F."""
         args = {k_: v_ for k_, v_ in locals().items() if k_ != "self"}
         return self._stabilize_video("rsdsfm_stabilize_video_dev", (), **args)
 
     def _stabilize_video(self, entry, tail, d_frames, rows, cols, channels, K, gamma, d_depth_maps, d_flows, d_R, d_t, d_stab, d_masks_out, d_fused, want_valid,
                          sigma, radius, translation, fuse_tol, d_masks, seeds, flow_params, a1, a2, link_tol, min_links, radix_bits, mode, q5_mode, iterations,
-                         trials, tol, use_acceleration_mode, use_refinement, depth_mode, k_sign_mode, flow_threshold, flow_index_mode, use_global_shutter_mode):
+                         trials, tol, use_acceleration_mode, use_refinement, depth_mode, k_sign_mode, flow_threshold, flow_index_mode, use_global_shutter_mode,
+                         last_frame=False):
         """stabilize_video_dev's marshalling, for it and for the entry points that take its arguments and then a `tail` of their own
         (stabilize_video_filled_dev)"""
         n = len(d_frames) - 1
+        nr = n + (1 if last_frame else 0)  # rendered frames
+        for what, lst, need in (("d_depth_maps", d_depth_maps, nr), ("d_R", d_R, nr), ("d_t", d_t, nr), ("d_stab", d_stab, nr), ("d_masks_out", d_masks_out, nr),
+                                ("d_fused", d_fused, nr), ("d_flows", d_flows, n), ("d_masks", d_masks, n), ("seeds", seeds, n)):
+            _need_entries(what, lst, need)
         prm = FrameParams(int(trials), int(use_acceleration_mode), int(use_refinement), int(depth_mode), int(k_sign_mode),
                           int(flow_index_mode), int(use_global_shutter_mode), 0, float(tol), float(flow_threshold), 1)
         res = (FrameResult * max(n, 1))()
         rec = (LinkRecord * max(n - 1, 1))()
         nn = max(n, 1)
-        scales, A, c = np.empty(nn), np.empty((nn + 1, 3, 3)), np.empty((nn + 1, 3))
-        A_s, c_s, M, m = np.empty((nn + 1, 3, 3)), np.empty((nn + 1, 3)), np.empty((nn, 3, 3)), np.empty((nn, 3))
-        valid = np.zeros(nn, dtype=np.int64) if want_valid else None
+        scales, A, c = np.empty(nn + 1), np.empty((nn + 1, 3, 3)), np.empty((nn + 1, 3))
+        A_s, c_s, M, m = np.empty((nn + 1, 3, 3)), np.empty((nn + 1, 3)), np.empty((nn + 1, 3, 3)), np.empty((nn + 1, 3))
+        valid = np.zeros(nn + 1, dtype=np.int64) if want_valid else None
         broken = np.zeros(max(n - 1, 1), dtype=np.uint8)
         sd = (C.c_uint64 * n)(*[int(s) for s in seeds]) if seeds is not None else None
         arr = lambda a: _ptr_array(a) if a is not None else None
         p, k, lp = _flow_params(flow_params), _flow_check_params(a1, a2), _link_params(link_tol, min_links, radix_bits)
-        sp = _stabilize_params(sigma, radius, translation)
+        sp = _stabilize_params(sigma, radius, translation, last_frame)
         fp = None
         if fuse_tol is not None:
             fp = FuseParams()
@@ -1732,10 +1751,10 @@ class _StabilizeMixin:
                                              arr(d_depth_maps), arr(d_R), arr(d_t), res, ref(k), arr(d_masks), ref(lp), rec, _p(scales), _p(A), _p(c),
                                              _p(broken), ref(fp), arr(d_fused), C.byref(sp), int(mode), int(q5_mode), C.c_int32(iterations), _p(A_s),
                                              _p(c_s), _p(M), _p(m), arr(d_stab), arr(d_masks_out), _p(valid), *tail), entry)
-        out = dict(pairs=[_frame_result_dict(r) for r in res[:n]], links=[r.as_dict() for r in rec[:max(n - 1, 0)]], scales=scales[:n], A=A[:n + 1], c=c[:n + 1],
-                   broken=broken[:max(n - 1, 0)], A_s=A_s[:n + 1], c_s=c_s[:n + 1], M=M[:n], m=m[:n])
+        out = dict(pairs=[_frame_result_dict(r) for r in res[:n]], links=[r.as_dict() for r in rec[:max(n - 1, 0)]], scales=scales[:nr], A=A[:n + 1], c=c[:n + 1],
+                   broken=broken[:max(n - 1, 0)], A_s=A_s[:n + 1], c_s=c_s[:n + 1], M=M[:nr], m=m[:nr])
         if want_valid:
-            out["valid"] = valid[:n]
+            out["valid"] = valid[:nr]
         return out
 
 
@@ -1869,13 +1888,15 @@ class _StabilizeFillMixin:
                                    d_masks=None, seeds=None, flow_params=None, a1=None, a2=None, link_tol=None, min_links=None, radix_bits=None,
                                    mode=BACKPROJECT_RS, q5_mode=Q5_COMPAT, iterations=0, trials=50, tol=0.05, use_acceleration_mode=False, use_refinement=True,
                                    depth_mode=DEPTH_CERES_LM, k_sign_mode=K_COMPAT, flow_threshold=1e-10, flow_index_mode=FLOW_COMPAT_RANK,
-                                   use_global_shutter_mode=False):
+                                   use_global_shutter_mode=False, last_frame=False):
         """the stabilised clip with its borders filled in ONE call (rsdsfm_stabilize_video_filled_dev): stabilize_video_dev with these arguments
         (d_masks_out required), then for every frame its mask copied to d_sources (F - 1 device planes of bytes, optional), neighbour_poses with
         fill_radius neighbours on each side (0: the default, 2) and one stabilize_fill_frame_dev per candidate -- on the fused maps when d_fused
         is passed.  Returns stabilize_video_dev's dict plus, with want_counts, counts ((F - 1, 2 + 2 fill_radius) int64: [none, own, -1, +1,
-        ...] per frame; the call then waits for the passes)."""
-        n = len(d_frames) - 1
+        ...] per frame; the call then waits for the passes).
+        last_frame=True (see stabilize_video_dev): the clip's last frame too; every per-frame list and array then has F entries."""
+        n = len(d_frames) - 1 + (1 if last_frame else 0)  # rendered frames
+        _need_all(n, d_sources=d_sources)
         fp = _stabilize_fill_params(fill_radius)
         counts = np.zeros((max(n, 1), 2 + 2 * fp.radius), dtype=np.int64) if want_counts else None
         args = {k_: v_ for k_, v_ in locals().items() if k_ not in ("self", "n", "fp", "counts", "d_sources", "fill_radius", "want_counts")}
@@ -2025,14 +2046,16 @@ class _StabilizeCropMixin:
                                     seeds=None, flow_params=None, a1=None, a2=None, link_tol=None, min_links=None, radix_bits=None, mode=BACKPROJECT_RS,
                                     q5_mode=Q5_COMPAT, iterations=0, trials=50, tol=0.05, use_acceleration_mode=False, use_refinement=True,
                                     depth_mode=DEPTH_CERES_LM, k_sign_mode=K_COMPAT, flow_threshold=1e-10, flow_index_mode=FLOW_COMPAT_RANK,
-                                    use_global_shutter_mode=False):
+                                    use_global_shutter_mode=False, last_frame=False):
         """the stabilised clip, cropped and zoomed, in ONE call (rsdsfm_stabilize_video_cropped_dev): stabilize_video_filled_dev with these
         arguments (fill_radius 0 .. 16 HERE: 0 means no fill, the inner call is then stabilize_video_dev), the window of its output masks
         (crop_window_dev with max_empty / margin; window_in = (r0, c0, h, w) skips the search) and, for every frame, the own frame and its
         neighbours through that window (stabilize_window_frame_dev) into d_crop, d_crop_masks and d_crop_sources (F - 1 device buffers each,
         zeroed first).  Returns the inner call's dict plus window and, with want_crop_counts, crop_counts ((F - 1, 2 + 2 fill_radius) int64:
-        [none, own, -1, +1, ...] per frame; the call then waits for the passes)."""
-        n = len(d_frames) - 1
+        [none, own, -1, +1, ...] per frame; the call then waits for the passes).
+        last_frame=True (see stabilize_video_dev): the clip's last frame too; every per-frame list and array then has F entries."""
+        n = len(d_frames) - 1 + (1 if last_frame else 0)  # rendered frames
+        _need_all(n, d_sources=d_sources, d_crop=d_crop, d_crop_masks=d_crop_masks, d_crop_sources=d_crop_sources)
         fp = _stabilize_fill_params(fill_radius)
         fp.radius = int(fill_radius)  # 0 stays 0 here
         cp = _stabilize_crop_params(max_empty, margin)
@@ -2170,15 +2193,17 @@ class _StabilizeBlendMixin:
                                     d_masks=None, seeds=None, flow_params=None, a1=None, a2=None, link_tol=None, min_links=None, radix_bits=None,
                                     mode=BACKPROJECT_RS, q5_mode=Q5_COMPAT, iterations=0, trials=50, tol=0.05, use_acceleration_mode=False, use_refinement=True,
                                     depth_mode=DEPTH_CERES_LM, k_sign_mode=K_COMPAT, flow_threshold=1e-10, flow_index_mode=FLOW_COMPAT_RANK,
-                                    use_global_shutter_mode=False):
+                                    use_global_shutter_mode=False, last_frame=False):
         """the stabilised clip, cropped, zoomed and blended, in ONE call (rsdsfm_stabilize_video_blended_dev): stabilize_video_cropped_dev with
         these arguments, then for every frame the own frame through the window into d_blend, d_blend_masks and d_blend_sources (F - 1 device
         buffers each, zeroed first), seam_distance_dev of its mask and, per neighbour, the neighbour alone on the context's layer and
         seam_blend_layer_dev (blend_feather None: 16; blend_gain False: no gain; blend_min_overlap None: 1024).  To blend without cropping pass
         window_in = (0, 0, rows, cols).  Returns stabilize_video_cropped_dev's dict plus, with want_gains, gains ((F - 1, 2 fill_radius, 3)
         uint32 in 1 / 65536, per offset -1, +1, -2, +2, ...) and, with want_blend_counts, blend_counts ((F - 1, 2 + 4 fill_radius) int64:
-        [none, own_untouched, (filled, blended) per offset]); with either the call waits for the passes."""
-        n = len(d_frames) - 1
+        [none, own_untouched, (filled, blended) per offset]); with either the call waits for the passes.
+        last_frame=True (see stabilize_video_dev): the clip's last frame too; every per-frame list and array then has F entries."""
+        n = len(d_frames) - 1 + (1 if last_frame else 0)  # rendered frames
+        _need_all(n, d_sources=d_sources, d_crop=d_crop, d_crop_masks=d_crop_masks, d_crop_sources=d_crop_sources, d_blend=d_blend, d_blend_masks=d_blend_masks, d_blend_sources=d_blend_sources)
         fp = _stabilize_fill_params(fill_radius)
         fp.radius = int(fill_radius)  # 0 stays 0 here
         cp = _stabilize_crop_params(max_empty, margin)
@@ -2272,13 +2297,15 @@ class _StabilizeInpaintMixin:
                                       want_valid=True, sigma=None, radius=0, translation=True, fuse_tol=None, d_masks=None, seeds=None, flow_params=None, a1=None,
                                       a2=None, link_tol=None, min_links=None, radix_bits=None, mode=BACKPROJECT_RS, q5_mode=Q5_COMPAT, iterations=0, trials=50,
                                       tol=0.05, use_acceleration_mode=False, use_refinement=True, depth_mode=DEPTH_CERES_LM, k_sign_mode=K_COMPAT,
-                                      flow_threshold=1e-10, flow_index_mode=FLOW_COMPAT_RANK, use_global_shutter_mode=False):
+                                      flow_threshold=1e-10, flow_index_mode=FLOW_COMPAT_RANK, use_global_shutter_mode=False, last_frame=False):
         """the stabilised clip, cropped, zoomed, blended and inpainted, in ONE call (rsdsfm_stabilize_video_inpainted_dev):
         stabilize_video_blended_dev with these arguments, then for every frame d_blend copied to d_inpaint (and d_blend_sources to
         d_inpaint_sources when passed; F - 1 device buffers each) and inpaint_frame_dev on the copy with the frame's blend mask.  Returns
         stabilize_video_blended_dev's dict plus, with want_inpaint_counts, inpaint_counts ((F - 1,) int64: the pixels written per frame; the
-        call then waits for the passes)."""
-        n = len(d_frames) - 1
+        call then waits for the passes).
+        last_frame=True (see stabilize_video_dev): the clip's last frame too; every per-frame list and array then has F entries."""
+        n = len(d_frames) - 1 + (1 if last_frame else 0)  # rendered frames
+        _need_all(n, d_sources=d_sources, d_crop=d_crop, d_crop_masks=d_crop_masks, d_crop_sources=d_crop_sources, d_blend=d_blend, d_blend_masks=d_blend_masks, d_blend_sources=d_blend_sources, d_inpaint=d_inpaint, d_inpaint_sources=d_inpaint_sources)
         fp = _stabilize_fill_params(fill_radius)
         fp.radius = int(fill_radius)  # 0 stays 0 here
         cp = _stabilize_crop_params(max_empty, margin)
@@ -2315,6 +2342,87 @@ class _StabilizeInpaintMixin:
 
 
 for _name, _fn in list(vars(_StabilizeInpaintMixin).items()):
+    if not _name.startswith("__"):
+        setattr(Solver, _name, _fn)
+
+
+# ---------------------------------------------------------------------------------------------------
+# the clip's last frame: the last pair's depth map moved onto it, and its pose table (include/rsdsfm_last_frame.h)
+# ---------------------------------------------------------------------------------------------------
+LAST_FRAME_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "rsdsfm_last_frame.h")
+
+
+def last_frame_declared_symbols():
+    """Names of every function include/rsdsfm_last_frame.h declares"""
+    import re
+
+    txt = open(LAST_FRAME_HEADER_PATH).read()
+    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
+    return sorted(set(re.findall(r"\b(rsdsfm_[a-z0-9_]+)\s*\(", txt)))
+
+
+def last_frame_motion(v, w, k):
+    """the motion that puts a pair's SECOND frame into pose_table's form (rsdsfm_last_frame_motion; host arithmetic, no GPU;
+    tests/last_frame_spec_numpy.py): v' = v (2 + 3 k) / (2 + k), w' likewise, k' = k / (1 + k); the identity bit for bit at k = 0.
+    -> (v' (3,), w' (3,), k')"""
+    vo, wo, ko = (C.c_double * 3)(), (C.c_double * 3)(), C.c_double()
+    rc = load_library().rsdsfm_last_frame_motion(_v3(v), _v3(w), C.c_double(k), vo, wo, C.byref(ko))
+    if rc != OK:
+        raise RsdsfmError("rsdsfm_last_frame_motion failed (%d): the motion must be finite with 1 + k > 0" % rc)
+    return np.array(vo[:]), np.array(wo[:]), ko.value
+
+
+def advance_depth_launches(rows, cols):
+    """kernel launches of one advance_depth_dev call: 3 (rsdsfm_advance_depth_launches; host only)"""
+    n = load_library().rsdsfm_advance_depth_launches(C.c_int32(rows), C.c_int32(cols))
+    if n < 0:
+        raise RsdsfmError("rsdsfm_advance_depth_launches failed (%d): rows and cols must be in [2, 16384]" % n)
+    return n
+
+
+class _LastFrameMixin:
+    def advance_depth_dev(self, d_field, d_depth_map, v, w, k, rows, cols, K, gamma, d_out, global_shutter=False, d_plane=None, d_count=None):
+        """a pair's depth map moved to its second capture, as a depth map of the second frame (rsdsfm_advance_depth_dev;
+        tests/last_frame_spec_numpy.py): d_field the pair's field (rows x cols x 2, row-major), d_depth_map / d_out column-major maps, (v, w, k)
+        the pair's final motion (host).  d_plane: a device plane of rows x cols uint64 that receives the winners' bit patterns; d_count: one
+        device int64 that receives the number of pixels with a value.  Enqueued on the context's stream."""
+        d = C.c_double
+        self._check(self.lib.rsdsfm_advance_depth_dev(self._ctx, _dp(d_field), _dp(d_depth_map), _v3(v), _v3(w), d(k), C.c_int32(rows), C.c_int32(cols), d(K[0]),
+                                                      d(K[1]), d(K[2]), d(K[3]), d(gamma), C.c_int32(int(bool(global_shutter))), _dp(d_out), _np0(d_plane),
+                                                      _np0(d_count)), "rsdsfm_advance_depth_dev")
+
+    def advance_depth(self, field, depth_map, v, w, k, K, gamma, global_shutter=False, want_plane=False, device=0):
+        """host convenience around advance_depth_dev: field (rows, cols, 2), depth_map (rows, cols) (0 where unknown) -> (map (rows, cols),
+        count[, plane (rows, cols) uint64])"""
+        import torch
+
+        F, Z = _f64(field), _f64(depth_map)
+        rows, cols = Z.shape
+        if F.shape != (rows, cols, 2):
+            raise ValueError("field (rows, cols, 2) and depth_map (rows, cols)")
+        dev = torch.device("cuda", device)
+        with torch.cuda.device(dev):
+            d_F, d_Z = torch.from_numpy(F).to(dev), torch.from_numpy(np.ascontiguousarray(Z.T)).to(dev)  # column-major rows x cols
+            d_out = torch.empty((cols, rows), dtype=torch.float64, device=dev)
+            d_plane = torch.empty((rows, cols), dtype=torch.int64, device=dev) if want_plane else None
+            d_cnt = torch.zeros(1, dtype=torch.int64, device=dev)
+            torch.cuda.synchronize()
+            self.advance_depth_dev(d_F.data_ptr(), d_Z.data_ptr(), v, w, k, rows, cols, K, gamma, d_out.data_ptr(), global_shutter,
+                                   d_plane.data_ptr() if want_plane else None, d_cnt.data_ptr())
+            self.synchronize()
+            out = (np.ascontiguousarray(d_out.cpu().numpy().T), int(d_cnt.cpu()[0]))
+            return out + (d_plane.cpu().numpy().view(np.uint64),) if want_plane else out
+
+    def last_frame_dev(self, d_field, d_depth_map, v, w, k, rows, cols, K, gamma, d_out, d_R, d_t, global_shutter=False, d_plane=None, d_count=None):
+        """the last frame's depth map and pose table from the last pair (rsdsfm_last_frame_dev): advance_depth_dev, last_frame_motion and
+        pose_table_dev of the moved motion into d_R (rows x 9) / d_t (rows x 3), one after another.  Enqueued on the context's stream."""
+        d = C.c_double
+        self._check(self.lib.rsdsfm_last_frame_dev(self._ctx, _dp(d_field), _dp(d_depth_map), _v3(v), _v3(w), d(k), C.c_int32(rows), C.c_int32(cols), d(K[0]),
+                                                   d(K[1]), d(K[2]), d(K[3]), d(gamma), C.c_int32(int(bool(global_shutter))), _dp(d_out), _dp(d_R), _dp(d_t),
+                                                   _np0(d_plane), _np0(d_count)), "rsdsfm_last_frame_dev")
+
+
+for _name, _fn in list(vars(_LastFrameMixin).items()):
     if not _name.startswith("__"):
         setattr(Solver, _name, _fn)
 

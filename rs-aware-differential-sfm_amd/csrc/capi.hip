@@ -185,6 +185,7 @@ void rsdsfm_destroy(rsdsfm_ctx* ctx) {
     rectify_dense_release(c);
     link_release(c);
     fuse_release(c);
+    last_frame_release(c);
     if (c->d_partials) (void)hipFree(c->d_partials);
     if (c->d_tickets) (void)hipFree(c->d_tickets);
     if (c->d_lm) (void)hipFree(c->d_lm);

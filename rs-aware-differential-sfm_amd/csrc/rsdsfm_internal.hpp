@@ -201,6 +201,7 @@ struct Ctx {
     void* flow_check = nullptr;  // flow_check_host.hip: heap FlowCheckWs of the checked-flow calls, made on first use
     void* link = nullptr;  // link_host.hip: heap LinkWs (ratio planes, histograms, per-link state) of the trajectory calls, made on first use
     void* fuse = nullptr;  // fuse_host.hip: heap FuseWs (splat planes, per-pair counters) of the depth fusion, made on first use
+    void* last_frame = nullptr;  // last_frame_host.hip: heap LastFrameWs (the advance's plane), made on first use
     void* rectify_dense = nullptr;  // rectify_dense_host.hip: heap DenseWs (pyramid + displacement plane) of the dense rectifier, made on first use
     // persistent claim maps of the forward-splat kernels (rectify_kernels.hip: claim_map_acquire): 0 = back projection, 1 = depth image
     unsigned* d_claim[3] = {nullptr, nullptr, nullptr};  // 2 = the depth map of the solve (glue_kernels.hip: depth_claim_kernel)
@@ -263,6 +264,7 @@ void flow_check_release(Ctx* c);  // flow_check_host.hip: the checked-flow calls
 void rectify_dense_release(Ctx* c);  // rectify_dense_host.hip: the dense rectifier's workspace
 void link_release(Ctx* c);  // link_host.hip: the trajectory calls' workspace
 void fuse_release(Ctx* c);  // fuse_host.hip: the depth fusion's workspace
+void last_frame_release(Ctx* c);  // last_frame_host.hip: the advance's plane
 
 constexpr int kDepthBlock = 256;
 constexpr int kDepthMaxBlocks = 512;

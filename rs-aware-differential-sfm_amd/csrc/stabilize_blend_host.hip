@@ -6,6 +6,7 @@
 #include "../../include/rsdsfm_stabilize_blend.h"
 #include "rectify_dense.hpp"
 #include "rsdsfm_internal.hpp"
+#include "last_frame.hpp"
 #include "sequence_host.hpp"
 #include "stabilize_blend.hpp"
 
@@ -122,7 +123,7 @@ int rsdsfm_stabilize_video_blended_dev(rsdsfm_ctx* ctx, const uint8_t* const* d_
     Ctx* c = &ctx->c;
     DeviceGuard device_guard_(c);
     if (nframes < 2) return fail(c, RSDSFM_ERR_INVALID, "stabilise video: nframes must be >= 2");
-    const int np = nframes - 1;
+    const int np = stabilize_rendered_frames(stabilize_params_or_null, nframes);  // rendered frames: the pairs' first frames, and the last frame when asked for
     if (!blend_size_ok(rows, cols)) return fail(c, RSDSFM_ERR_INVALID, "blend: rows and cols must be in [2, 16384]");
     if (channels != 1 && channels != 3) return fail(c, RSDSFM_ERR_INVALID, "blend: channels must be 1 or 3");
     rsdsfm_stabilize_blend_params bp;

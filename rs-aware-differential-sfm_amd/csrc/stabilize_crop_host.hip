@@ -7,6 +7,7 @@
 #include "../../include/rsdsfm_stabilize_crop.h"
 #include "rectify_dense.hpp"
 #include "rsdsfm_internal.hpp"
+#include "last_frame.hpp"
 #include "sequence_host.hpp"
 #include "stabilize_crop.hpp"
 
@@ -159,7 +160,7 @@ int rsdsfm_stabilize_video_cropped_dev(rsdsfm_ctx* ctx, const uint8_t* const* d_
     Ctx* c = &ctx->c;
     DeviceGuard device_guard_(c);
     if (nframes < 2) return fail(c, RSDSFM_ERR_INVALID, "stabilise video: nframes must be >= 2");
-    const int np = nframes - 1;
+    const int np = stabilize_rendered_frames(stabilize_params_or_null, nframes);  // rendered frames: the pairs' first frames, and the last frame when asked for
     if (!crop_size_ok(rows, cols)) return fail(c, RSDSFM_ERR_INVALID, "crop: rows and cols must be in [2, 16384]");
     if (fill_params_or_null && ((fill_params_or_null->struct_bytes != 0 && fill_params_or_null->struct_bytes != (int32_t)sizeof(rsdsfm_stabilize_fill_params)) ||
                                 fill_params_or_null->radius < 0 || fill_params_or_null->radius > kCropFillRadiusMax))

@@ -8,6 +8,7 @@
 #include "../../include/rsdsfm_stabilize_fill.h"
 #include "rectify_dense.hpp"
 #include "rsdsfm_internal.hpp"
+#include "last_frame.hpp"
 #include "sequence_host.hpp"
 #include "stabilize_fill.hpp"
 
@@ -121,7 +122,7 @@ int rsdsfm_stabilize_video_filled_dev(rsdsfm_ctx* ctx, const uint8_t* const* d_f
     Ctx* c = &ctx->c;
     DeviceGuard device_guard_(c);
     if (nframes < 2) return fail(c, RSDSFM_ERR_INVALID, "stabilise video: nframes must be >= 2");
-    const int np = nframes - 1;
+    const int np = stabilize_rendered_frames(stabilize_params_or_null, nframes);  // rendered frames: the pairs' first frames, and the last frame when asked for
     const rsdsfm_stabilize_fill_params fp = fill_params_or_null ? *fill_params_or_null : fill_defaults();
     if (!fill_params_ok(fp))
         return fail(c, RSDSFM_ERR_INVALID, "rsdsfm_stabilize_fill_params: radius in [0, 16], struct_bytes 0 or sizeof (use rsdsfm_stabilize_fill_params_init)");

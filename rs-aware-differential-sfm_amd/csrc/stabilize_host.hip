@@ -5,6 +5,7 @@
 #include <vector>
 
 #include "../../include/rsdsfm_stabilize.h"
+#include "last_frame.hpp"
 #include "link.hpp"
 #include "rectify_dense.hpp"
 #include "rsdsfm_internal.hpp"
@@ -18,7 +19,7 @@ rsdsfm_stabilize_params stabilize_defaults() { return rsdsfm_stabilize_params{4.
 
 bool stabilize_params_ok(const rsdsfm_stabilize_params& p) {
     if (p.struct_bytes != 0 && p.struct_bytes != (int32_t)sizeof(rsdsfm_stabilize_params)) return false;
-    return std::isfinite(p.sigma) && p.sigma > 0.0 && p.radius >= 0 && p.radius <= 1024;
+    return std::isfinite(p.sigma) && p.sigma > 0.0 && p.radius >= 0 && p.radius <= 1024 && (p.last_frame == 0 || p.last_frame == 1);
 }
 
 // a b for row-major 3 x 3, every entry (a_i0 b_0j + a_i1 b_1j) + a_i2 b_2j; ta: a transposed
@@ -164,16 +165,19 @@ int rsdsfm_stabilize_video_dev(rsdsfm_ctx* ctx, const uint8_t* const* d_frames, 
     if (!d_frames || !d_flows || !d_depth_maps || !d_R || !d_t || !results || !params)
         return fail(c, RSDSFM_ERR_INVALID,
                     "stabilise video: d_flows, d_depth_maps, d_R and d_t are required -- every pair's field, map and pose table is read after the whole clip is solved");
-    if (!all_set(d_R, np) || !all_set(d_t, np)) return fail(c, RSDSFM_ERR_INVALID, "stabilise video: every pair needs a pose table of its own (d_R, d_t)");
+    const int nr = stabilize_rendered_frames(stabilize_params_or_null, nframes);  // rendered frames: np, and the last frame when asked for
+    if (!all_set(d_R, nr) || !all_set(d_t, nr)) return fail(c, RSDSFM_ERR_INVALID, "stabilise video: every pair needs a pose table of its own (d_R, d_t)");
+    if (nr > np && (!all_set(d_depth_maps, nr) || !all_set(d_flows, np) || !scales))
+        return fail(c, RSDSFM_ERR_INVALID, "stabilise video: the last frame needs a depth map of its own (d_depth_maps[nframes - 1]), the last pair's field and scales");
     if (!A_s || !c_s || !M || !m || !d_stab_images) return fail(c, RSDSFM_ERR_INVALID, "stabilise video: null pointer");
     int rc = rectify_dense_check(c, channels, rows, cols, mode, q5_mode, iterations);
     if (rc != RSDSFM_OK) return rc;
     const rsdsfm_stabilize_params sp = stabilize_params_or_null ? *stabilize_params_or_null : stabilize_defaults();
     if (!stabilize_params_ok(sp))
-        return fail(c, RSDSFM_ERR_INVALID, "rsdsfm_stabilize_params: sigma must be finite and > 0, radius in [0, 1024], struct_bytes 0 or sizeof (use rsdsfm_stabilize_params_init)");
-    if (!all_set(d_stab_images, np) || (d_masks_out_or_null && !all_set(d_masks_out_or_null, np)) || (d_fused_maps_or_null && !all_set(d_fused_maps_or_null, np)))
+        return fail(c, RSDSFM_ERR_INVALID, "rsdsfm_stabilize_params: sigma must be finite and > 0, radius in [0, 1024], last_frame 0 or 1, struct_bytes 0 or sizeof (use rsdsfm_stabilize_params_init)");
+    if (!all_set(d_stab_images, nr) || (d_masks_out_or_null && !all_set(d_masks_out_or_null, nr)) || (d_fused_maps_or_null && !all_set(d_fused_maps_or_null, nr)))
         return fail(c, RSDSFM_ERR_INVALID, "stabilise video: null device pointer");
-    for (int p = 0; p < np; ++p) {
+    for (int p = 0; p < nr; ++p) {
         if (d_stab_images[p] == d_frames[p]) return fail(c, RSDSFM_ERR_INVALID, "stabilise video: a pair's output image is its frame");
         if (((uintptr_t)d_stab_images[p] | (uintptr_t)d_frames[p] | (uintptr_t)(d_masks_out_or_null ? d_masks_out_or_null[p] : nullptr)) & 3u)
             return fail(c, RSDSFM_ERR_INVALID, "dense rectifier: images and mask must be 4-byte aligned");
@@ -195,17 +199,28 @@ int rsdsfm_stabilize_video_dev(rsdsfm_ctx* ctx, const uint8_t* const* d_frames, 
                                     params->use_global_shutter_mode ? 1 : 0, records, fuse_params_or_null, d_fused_maps_or_null, nullptr, nullptr, nullptr);
         if (rc != RSDSFM_OK) return rc;
     }
+    if (nr > np) {  // the last frame: its pair's map moved onto it, its pose table from its pair's motion, its pair's unit
+        const rsdsfm_frame_result& last = results[np - 1];
+        const int gs = params->use_global_shutter_mode ? 1 : 0;
+        rc = rsdsfm_last_frame_dev(ctx, d_flows[np - 1], d_depth_maps[np - 1], last.v, last.w, last.k, rows, cols, fx, fy, cx, cy, gamma, gs, d_depth_maps[np], d_R[np],
+                                   d_t[np], nullptr, nullptr);
+        if (rc == RSDSFM_OK && d_fused_maps_or_null)
+            rc = rsdsfm_advance_depth_dev(ctx, d_flows[np - 1], d_fused_maps_or_null[np - 1], last.v, last.w, last.k, rows, cols, fx, fy, cx, cy, gamma, gs,
+                                          d_fused_maps_or_null[np], nullptr, nullptr);
+        if (rc != RSDSFM_OK) return rc;
+        scales[np] = scales[np - 1];
+    }
     if (rsdsfm_smooth_path(A, c_, nframes, &sp, A_s, c_s) != RSDSFM_OK) return fail(c, RSDSFM_ERR_INVALID, "stabilise video: the path smoother refused its arguments");
-    if (rsdsfm_virtual_poses(A, c_, A_s, c_s, scales, np, sp.translation, M, m) != RSDSFM_OK)
+    if (rsdsfm_virtual_poses(A, c_, A_s, c_s, scales, nr, sp.translation, M, m) != RSDSFM_OK)
         return fail(c, RSDSFM_ERR_INVALID, "stabilise video: a pair's scale is not finite and positive");
     int64_t* d_valid = nullptr;
-    if (valid_or_null) RSDSFM_HIP_CHECK(c, hipMalloc(reinterpret_cast<void**>(&d_valid), sizeof(int64_t) * (size_t)np));
-    for (int p = 0; p < np && rc == RSDSFM_OK; ++p)
+    if (valid_or_null) RSDSFM_HIP_CHECK(c, hipMalloc(reinterpret_cast<void**>(&d_valid), sizeof(int64_t) * (size_t)nr));
+    for (int p = 0; p < nr && rc == RSDSFM_OK; ++p)
         rc = rsdsfm_stabilize_frame_dev(ctx, d_frames[p], channels, d_fused_maps_or_null ? d_fused_maps_or_null[p] : d_depth_maps[p], d_R[p], d_t[p], fx, fy, cx, cy,
                                         rows, cols, mode, q5_mode, iterations, M + 9 * (size_t)p, m + 3 * (size_t)p, d_stab_images[p],
                                         d_masks_out_or_null ? d_masks_out_or_null[p] : nullptr, nullptr, nullptr, d_valid ? d_valid + p : nullptr);
     if (d_valid) {
-        hipError_t e = rc == RSDSFM_OK ? hipMemcpyAsync(valid_or_null, d_valid, sizeof(int64_t) * (size_t)np, hipMemcpyDeviceToHost, c->stream) : hipSuccess;
+        hipError_t e = rc == RSDSFM_OK ? hipMemcpyAsync(valid_or_null, d_valid, sizeof(int64_t) * (size_t)nr, hipMemcpyDeviceToHost, c->stream) : hipSuccess;
         if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
         (void)hipFree(d_valid);
         if (rc == RSDSFM_OK) RSDSFM_HIP_CHECK(c, e);

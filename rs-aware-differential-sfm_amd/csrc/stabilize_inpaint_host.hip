@@ -4,6 +4,7 @@
 #include "../../include/rsdsfm_stabilize_inpaint.h"
 #include "rectify_dense.hpp"
 #include "rsdsfm_internal.hpp"
+#include "last_frame.hpp"
 #include "sequence_host.hpp"
 #include "stabilize_inpaint.hpp"
 
@@ -66,7 +67,7 @@ int rsdsfm_stabilize_video_inpainted_dev(rsdsfm_ctx* ctx, const uint8_t* const* 
     Ctx* c = &ctx->c;
     DeviceGuard device_guard_(c);
     if (nframes < 2) return fail(c, RSDSFM_ERR_INVALID, "stabilise video: nframes must be >= 2");
-    const int np = nframes - 1;
+    const int np = stabilize_rendered_frames(stabilize_params_or_null, nframes);  // rendered frames: the pairs' first frames, and the last frame when asked for
     if (!all_set(d_inpaint_images, np) || (d_inpaint_sources_or_null && !all_set(d_inpaint_sources_or_null, np)))
         return fail(c, RSDSFM_ERR_INVALID, "inpaint: d_inpaint_images is required, and every plane of d_inpaint_sources when it is passed");
     for (int p = 0; p < np; ++p) {

@@ -208,7 +208,7 @@ def evaluate_real_sequence(solver, frames, camera="galaxy", gamma=0.95, out_dir=
                            use_refinement=True, use_global_shutter_mode=False, flow_threshold=1e-10, flow_index_mode=0, device=0, flow_params=None, dense=False,
                            check_flow=False, trajectory=False, link_tol=None, min_links=None, fuse=False, fuse_tol=None, stabilize=False, smooth_sigma=None,
                            smooth_translation=True, fill=0, crop=False, crop_margin=None, crop_max_empty=0, blend=False, blend_feather=None,
-                           blend_gain=True, inpaint=False):
+                           blend_gain=True, inpaint=False, last_frame=False):
     """evaluate_real_run's real-world branch (main.cc:341-361, 364-531) for a clip: `frames` is <prefix>frame1.png ... frameN.png (the
     prefix, or a list of paths), or the frames themselves (an (N, rows, cols[, 3]) uint8 array or a list of arrays; 2-D frames are gray).
     By default ONE call does the clip (Solver.rectify_video_dev): the batched DeepFlow of every consecutive pair, the pipelined solve of every pair p
@@ -235,7 +235,7 @@ def evaluate_real_sequence(solver, frames, camera="galaxy", gamma=0.95, out_dir=
     its virtual camera (Solver.stabilize_frame_dev on the pair's map -- the FUSED one with fuse=True -- and pose table).  The returned dict then
     also has stabilized and stab_masks (per pair, the frame's shape / (rows, cols) uint8), stab_valid (per pair, the mask's count) and
     path_smoothed = dict(A_s, c_s, M, m); out_dir receives stabilized_<p>.png per pair and path_smoothed.csv (frame, smoothed position, smoothed
-    rotation row by row).  The last frame has no pair and is not rendered.  With stabilize=False every output is unchanged.
+    rotation row by row).  The last frame has no pair and is not rendered unless last_frame=True.  With stabilize=False every output is unchanged.
     fill=K (needs stabilize=True: ValueError otherwise; K = 1 .. 16 neighbours on each side): behind the stabilised frames, the band each leaves
     empty filled from its neighbours (neighbour_poses, then one Solver.stabilize_fill_frame_dev per candidate on COPIES of the frame and its
     mask, on the neighbour's map -- the FUSED one with fuse=True).  The returned dict then also has stab_filled (per pair, the frame's shape),
@@ -261,7 +261,14 @@ def evaluate_real_sequence(solver, frames, camera="galaxy", gamma=0.95, out_dir=
     tests/stabilize_inpaint_spec_numpy.py).  The returned dict then also has stab_inpainted (per pair, the frame's shape), inpaint_sources (per
     pair, (rows, cols) uint8: INPAINT_SOURCE = 255 where a pixel was invented, elsewhere the stage's source plane -- the blend's and the fill's
     -- or its mask) and inpaint_counts ((pairs,) int64); out_dir receives stabilized_inpainted_<p>.png per pair and inpaint.csv (pair, stage,
-    the count).  Without inpaint every output is what it was."""
+    the count).  Without inpaint every output is what it was.
+    last_frame=True (needs stabilize=True: ValueError otherwise): the clip's last frame is rendered too, from the last pair's depth map moved onto
+    it and that pair's motion (Solver.last_frame_dev; the fused map by Solver.advance_depth_dev with fuse=True; the last pair's scale): every
+    stage above then has one more frame -- one more entry in its lists and arrays, the N-th stabilized*_<p>.png and one more row in fill.csv,
+    crop.csv, blend.csv and inpaint.csv -- and the last frame is a candidate for the frames before it.  The solve's outputs, the trajectory and
+    path_smoothed's A_s and c_s are unchanged (M and m gain the last frame's entry).  Without last_frame every output is what it was."""
+    if last_frame and not stabilize:
+        raise ValueError("last_frame needs stabilize=True: it renders the clip's last frame")
     if inpaint and not stabilize:
         raise ValueError("inpaint needs stabilize=True: it inpaints what the stabilised frames leave empty")
     if blend and not (stabilize and fill >= 1):
@@ -376,15 +383,30 @@ def evaluate_real_sequence(solver, frames, camera="galaxy", gamma=0.95, out_dir=
                     run_dense(d_fused)
             if stabilize:
                 from . import smooth_path, virtual_poses
+                nst, st_scales = npairs, traj["scales"]  # rendered frames and their units
+                if last_frame:  # the last frame: its pair's map moved onto it, its table from its pair's motion, its pair's unit
+                    d_maps.append(torch.empty(rows * cols, dtype=torch.float64, device=dev))
+                    d_Rs.append(torch.empty(rows * 9, dtype=torch.float64, device=dev))
+                    d_ts.append(torch.empty(rows * 3, dtype=torch.float64, device=dev))
+                    torch.cuda.synchronize()
+                    lo = outs[npairs - 1]
+                    solver.last_frame_dev(d_flows[npairs - 1].data_ptr(), d_maps[npairs - 1].data_ptr(), lo["v"], lo["w"], lo["k"], rows, cols, K, gamma,
+                                          d_maps[npairs].data_ptr(), d_Rs[npairs].data_ptr(), d_ts[npairs].data_ptr(), use_global_shutter_mode)
+                    if fuse:
+                        d_fused.append(torch.empty(rows * cols, dtype=torch.float64, device=dev))
+                        torch.cuda.synchronize()
+                        solver.advance_depth_dev(d_flows[npairs - 1].data_ptr(), d_fused[npairs - 1].data_ptr(), lo["v"], lo["w"], lo["k"], rows, cols, K, gamma,
+                                                 d_fused[npairs].data_ptr(), use_global_shutter_mode)
+                    nst, st_scales = npairs + 1, np.append(traj["scales"], traj["scales"][npairs - 1])
 
                 A_s, c_s = smooth_path(traj["A"], traj["c"], smooth_sigma, 0, smooth_translation)
-                vM, vm = virtual_poses(traj["A"], traj["c"], A_s, c_s, traj["scales"], smooth_translation)
-                d_stabs = [torch.empty_like(d_imgs[0]) for _ in range(npairs)]
-                d_smasks = [torch.empty((rows, cols), dtype=torch.uint8, device=dev) for _ in range(npairs)]
-                d_svalid = torch.zeros(npairs, dtype=torch.int64, device=dev)
+                vM, vm = virtual_poses(traj["A"], traj["c"], A_s, c_s, st_scales, smooth_translation, last_frame)
+                d_stabs = [torch.empty_like(d_imgs[0]) for _ in range(nst)]
+                d_smasks = [torch.empty((rows, cols), dtype=torch.uint8, device=dev) for _ in range(nst)]
+                d_svalid = torch.zeros(nst, dtype=torch.int64, device=dev)
                 torch.cuda.synchronize()
                 d_src = d_fused if fuse else d_maps
-                for p in range(npairs):  # every frame enqueued behind the clip, one wait for all of them
+                for p in range(nst):  # every frame enqueued behind the clip, one wait for all of them
                     solver.stabilize_frame_dev(d_imgs[p].data_ptr(), channels, d_src[p].data_ptr(), d_Rs[p].data_ptr(), d_ts[p].data_ptr(), K, rows, cols, vM[p],
                                                vm[p], d_stabs[p].data_ptr(), d_smasks[p].data_ptr(), d_valid=d_svalid[p:].data_ptr(), mode=mode)
                 solver.synchronize()
@@ -394,11 +416,11 @@ def evaluate_real_sequence(solver, frames, camera="galaxy", gamma=0.95, out_dir=
                     from . import neighbour_poses
 
                     d_fills, d_fmasks2, d_sources = [t.clone() for t in d_stabs], [t.clone() for t in d_smasks], [t.clone() for t in d_smasks]
-                    d_fcnt = torch.zeros((npairs, 2 + 2 * fill), dtype=torch.int64, device=dev)
+                    d_fcnt = torch.zeros((nst, 2 + 2 * fill), dtype=torch.int64, device=dev)
                     d_fcnt[:, 1] = d_svalid
                     torch.cuda.synchronize()
-                    for p in range(npairs):  # every pass enqueued, one wait for all of them
-                        for n, sid, nM, nm in zip(*neighbour_poses(traj["A"], traj["c"], A_s, c_s, traj["scales"], p, fill)):
+                    for p in range(nst):  # every pass enqueued, one wait for all of them
+                        for n, sid, nM, nm in zip(*neighbour_poses(traj["A"], traj["c"], A_s, c_s, st_scales, p, fill)):
                             solver.stabilize_fill_frame_dev(d_imgs[n].data_ptr(), channels, d_src[n].data_ptr(), d_Rs[n].data_ptr(), d_ts[n].data_ptr(), K, rows,
                                                             cols, nM, nm, int(sid), d_fills[p].data_ptr(), d_fmasks2[p].data_ptr(), d_sources[p].data_ptr(),
                                                             d_fcnt[p, int(sid):].data_ptr(), mode=mode)
@@ -411,11 +433,11 @@ def evaluate_real_sequence(solver, frames, camera="galaxy", gamma=0.95, out_dir=
 
                     window = solver.crop_window_dev(ptrs(d_fmasks2 if fill else d_smasks), rows, cols, crop_max_empty, crop_margin)
                     d_crops = [torch.zeros_like(t) for t in d_stabs]
-                    d_cmasks = [torch.zeros((rows, cols), dtype=torch.uint8, device=dev) for _ in range(npairs)]
-                    d_ccnt = torch.zeros((npairs, 2 + 2 * fill), dtype=torch.int64, device=dev)
+                    d_cmasks = [torch.zeros((rows, cols), dtype=torch.uint8, device=dev) for _ in range(nst)]
+                    d_ccnt = torch.zeros((nst, 2 + 2 * fill), dtype=torch.int64, device=dev)
                     torch.cuda.synchronize()
-                    for p in range(npairs if window[2] else 0):  # every pass enqueued, one wait for all of them
-                        cand = [(p, 1, vM[p], vm[p])] + (list(zip(*neighbour_poses(traj["A"], traj["c"], A_s, c_s, traj["scales"], p, fill))) if fill else [])
+                    for p in range(nst if window[2] else 0):  # every pass enqueued, one wait for all of them
+                        cand = [(p, 1, vM[p], vm[p])] + (list(zip(*neighbour_poses(traj["A"], traj["c"], A_s, c_s, st_scales, p, fill))) if fill else [])
                         for n, sid, nM, nm in cand:
                             solver.stabilize_window_frame_dev(d_imgs[n].data_ptr(), channels, d_src[n].data_ptr(), d_Rs[n].data_ptr(), d_ts[n].data_ptr(), K, rows,
                                                               cols, nM, nm, int(sid), window, d_crops[p].data_ptr(), d_cmasks[p].data_ptr(), None,
@@ -429,16 +451,16 @@ def evaluate_real_sequence(solver, frames, camera="galaxy", gamma=0.95, out_dir=
 
                     bwindow = traj["crop_window"] if crop else (0, 0, rows, cols)
                     d_blends = [torch.zeros_like(t) for t in d_stabs]
-                    d_bmasks = [torch.zeros((rows, cols), dtype=torch.uint8, device=dev) for _ in range(npairs)]
-                    d_bsources = [torch.zeros((rows, cols), dtype=torch.uint8, device=dev) for _ in range(npairs)]
+                    d_bmasks = [torch.zeros((rows, cols), dtype=torch.uint8, device=dev) for _ in range(nst)]
+                    d_bsources = [torch.zeros((rows, cols), dtype=torch.uint8, device=dev) for _ in range(nst)]
                     d_dist = torch.zeros((rows, cols), dtype=torch.uint8, device=dev)
                     d_layers = [torch.zeros_like(d_stabs[0]) for _ in range(2 * fill)]  # one per candidate of a frame, zeroed again per frame
                     d_lmasks = [torch.zeros((rows, cols), dtype=torch.uint8, device=dev) for _ in range(2 * fill)]
-                    d_sums = torch.zeros((npairs, 2 * fill, 8), dtype=torch.int64, device=dev)  # (the records' 64-bit words)
-                    d_bcnt = torch.zeros((npairs, 2 * fill, 2), dtype=torch.int64, device=dev)
-                    d_own = torch.zeros(npairs, dtype=torch.int64, device=dev)
+                    d_sums = torch.zeros((nst, 2 * fill, 8), dtype=torch.int64, device=dev)  # (the records' 64-bit words)
+                    d_bcnt = torch.zeros((nst, 2 * fill, 2), dtype=torch.int64, device=dev)
+                    d_own = torch.zeros(nst, dtype=torch.int64, device=dev)
                     torch.cuda.synchronize()
-                    for p in range(npairs if bwindow[2] else 0):  # a frame's passes enqueued on the solver's stream, one wait per frame
+                    for p in range(nst if bwindow[2] else 0):  # a frame's passes enqueued on the solver's stream, one wait per frame
                         if p:
                             for t in d_layers + d_lmasks:
                                 t.zero_()
@@ -447,7 +469,7 @@ def evaluate_real_sequence(solver, frames, camera="galaxy", gamma=0.95, out_dir=
                                                           vM[p], vm[p], 1, bwindow, d_blends[p].data_ptr(), d_bmasks[p].data_ptr(), d_bsources[p].data_ptr(),
                                                           d_own[p:].data_ptr(), mode=mode)
                         solver.seam_distance_dev(d_bmasks[p].data_ptr(), rows, cols, blend_feather or 0, d_dist.data_ptr())
-                        for n, sid, nM, nm in zip(*neighbour_poses(traj["A"], traj["c"], A_s, c_s, traj["scales"], p, fill)):
+                        for n, sid, nM, nm in zip(*neighbour_poses(traj["A"], traj["c"], A_s, c_s, st_scales, p, fill)):
                             d_layer, d_lmask = d_layers[int(sid) - 2], d_lmasks[int(sid) - 2]
                             solver.stabilize_window_frame_dev(d_imgs[n].data_ptr(), channels, d_src[n].data_ptr(), d_Rs[n].data_ptr(), d_ts[n].data_ptr(), K, rows,
                                                               cols, nM, nm, int(sid), bwindow, d_layer.data_ptr(), d_lmask.data_ptr(), None, None, mode=mode)
@@ -456,12 +478,12 @@ def evaluate_real_sequence(solver, frames, camera="galaxy", gamma=0.95, out_dir=
                                                         d_bcnt[p, int(sid) - 2].data_ptr(), feather=blend_feather, gain=blend_gain)
                         solver.synchronize()
                     sums, per, own = d_sums.cpu().numpy().view(np.uint64), d_bcnt.cpu().numpy(), d_own.cpu().numpy()
-                    gains = np.full((npairs, 2 * fill, 3), GAIN_ONE, dtype=np.uint32)
-                    for p in range(npairs):
+                    gains = np.full((nst, 2 * fill, 3), GAIN_ONE, dtype=np.uint32)
+                    for p in range(nst):
                         for k_ in range(2 * fill):
                             gains[p, k_] = seam_gains(sums[p, k_], channels, 0, 0 if blend_gain else 1)
                     counts = np.concatenate([(rows * cols - own - per[:, :, 0].sum(axis=1))[:, None], (own - per[:, :, 1].sum(axis=1))[:, None],
-                                             per.reshape(npairs, -1)], axis=1)
+                                             per.reshape(nst, -1)], axis=1)
                     traj.update(stab_blended=[t.cpu().numpy() for t in d_blends], blend_gains=gains, blend_counts=counts)
                 if inpaint:
                     if blend:
@@ -473,9 +495,9 @@ def evaluate_real_sequence(solver, frames, camera="galaxy", gamma=0.95, out_dir=
                     else:
                         stage, d_last, d_lmask, d_lsrc = "stabilized", d_stabs, d_smasks, d_smasks
                     d_inps, d_isrcs = [t.clone() for t in d_last], [t.clone() for t in d_lsrc]
-                    d_icnt = torch.zeros(npairs, dtype=torch.int64, device=dev)
+                    d_icnt = torch.zeros(nst, dtype=torch.int64, device=dev)
                     torch.cuda.synchronize()
-                    for p in range(npairs):  # every frame enqueued, one wait for all of them
+                    for p in range(nst):  # every frame enqueued, one wait for all of them
                         solver.inpaint_frame_dev(d_inps[p].data_ptr(), d_lmask[p].data_ptr(), channels, rows, cols, d_isrcs[p].data_ptr(), d_icnt[p:].data_ptr())
                     solver.synchronize()
                     traj.update(stab_inpainted=[t.cpu().numpy() for t in d_inps], inpaint_sources=[t.cpu().numpy() for t in d_isrcs],
@@ -516,7 +538,8 @@ def evaluate_real_sequence(solver, frames, camera="galaxy", gamma=0.95, out_dir=
             formats.write_ply(os.path.join(out_dir, "clip.ply"), np.concatenate([traj["points"][p][keep[p]] for p in range(npairs)]),
                               np.concatenate([colour[p][keep[p]] for p in range(npairs)]))
         if stabilize:
-            for p in range(npairs):
+            nst = npairs + (1 if last_frame else 0)
+            for p in range(nst):
                 formats.write_png(os.path.join(out_dir, "stabilized_%d.png" % p), traj["stabilized"][p])
             ps = traj["path_smoothed"]
             rows_ = ["frame,c_x,c_y,c_z," + ",".join("a_%d%d" % (i, j) for i in range(3) for j in range(3))]
@@ -527,7 +550,7 @@ def evaluate_real_sequence(solver, frames, camera="galaxy", gamma=0.95, out_dir=
         if fill:
             names = ["none", "own"] + ["%s%d" % (sg, j) for j in range(1, fill + 1) for sg in ("prev", "next")]
             rows_ = ["pair," + ",".join(names)]
-            for p in range(npairs):
+            for p in range(nst):
                 formats.write_png(os.path.join(out_dir, "stabilized_filled_%d.png" % p), traj["stab_filled"][p])
                 rows_.append(",".join([str(p)] + [str(int(x)) for x in traj["fill_counts"][p]]))
             with open(os.path.join(out_dir, "fill.csv"), "w") as fh:
@@ -535,7 +558,7 @@ def evaluate_real_sequence(solver, frames, camera="galaxy", gamma=0.95, out_dir=
         if crop:
             names = ["none", "own"] + ["%s%d" % (sg, j) for j in range(1, fill + 1) for sg in ("prev", "next")]
             rows_ = ["window," + ",".join(str(x) for x in traj["crop_window"]), "pair," + ",".join(names)]
-            for p in range(npairs):
+            for p in range(nst):
                 formats.write_png(os.path.join(out_dir, "stabilized_cropped_%d.png" % p), traj["stab_cropped"][p])
                 rows_.append(",".join([str(p)] + [str(int(x)) for x in traj["crop_counts"][p]]))
             with open(os.path.join(out_dir, "crop.csv"), "w") as fh:
@@ -544,14 +567,14 @@ def evaluate_real_sequence(solver, frames, camera="galaxy", gamma=0.95, out_dir=
             offs = ["%s%d" % (sg, j) for j in range(1, fill + 1) for sg in ("prev", "next")]
             names = ["none", "own_untouched"] + [o + "_" + w for o in offs for w in ("filled", "blended")] + ["gain_%s_%d" % (o, c_) for o in offs for c_ in range(3)]
             rows_ = ["pair," + ",".join(names)]
-            for p in range(npairs):
+            for p in range(nst):
                 formats.write_png(os.path.join(out_dir, "stabilized_blended_%d.png" % p), traj["stab_blended"][p])
                 rows_.append(",".join([str(p)] + [str(int(x)) for x in traj["blend_counts"][p]] + [str(int(x)) for x in traj["blend_gains"][p].reshape(-1)]))
             with open(os.path.join(out_dir, "blend.csv"), "w") as fh:
                 fh.write("\n".join(rows_) + "\n")
         if inpaint:
             rows_ = ["pair,stage,inpainted"]
-            for p in range(npairs):
+            for p in range(nst):
                 formats.write_png(os.path.join(out_dir, "stabilized_inpainted_%d.png" % p), traj["stab_inpainted"][p])
                 rows_.append("%d,%s,%d" % (p, stage, int(traj["inpaint_counts"][p])))
             with open(os.path.join(out_dir, "inpaint.csv"), "w") as fh:
