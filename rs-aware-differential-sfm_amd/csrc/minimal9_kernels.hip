@@ -158,27 +158,52 @@ __device__ void jacobi_svd9_nullvec(LVec W, LVec V, LVec sv, LVec col, double e_
     for (int i = 0; i < 9; ++i) e_out[i] = V[i * 9 + c8];
 }
 
+// ---- range test of the rotations that go through the in-range function cores (device_math.hpp) ---------------------------------------
+// A rotation's cores take ten operands; FOUR are tested -- t, d of the 2x2 step and xz, deno of makeJacobi, the numerators and
+// denominators of the two divisions that start from matrix entries -- against the window |x| in [2^-190, 2^190), and the other six are then
+// in range by construction:
+//   uu  = t / d                   : |uu| in (2^-380, 2^380), both operands and the quotient inside div_core's window [2^-383, 2^385)
+//   a1p = 1 + uu * uu             : in [1, 2^761), inside sqrt_core's range [2^-767, DBL_MAX]
+//   tmp = sqrt(a1p)               : in [1, 2^381): a normal reciprocal (rcp_core), and inside the division window for uu / tmp
+//   tau = xz / deno, ww = tau * tau + 1, w = sqrt(ww), den = tau +- w (the signs agree: |den| in [1, 2^382)) : the same argument
+//   t * t + 1 with |t| <= 1       : in [1, 2], its root in [1, 1.42]
+// The window is a test on the high word: exponent field in [0x341, 0x4BD); NaNs, infinities, zeros and denormals all fail it.  The entries
+// of the scaled matrix are at most 1 in magnitude and a pair is rotated only when an off-diagonal entry exceeds 2^-51 max|diagonal|, so real
+// operands sit some hundred binades inside it; a hypothesis that leaves it is computed again with the standard functions (`outside`), which
+// return the same bits -- only which path computes them changes.
+constexpr uint32_t kSvdRangeLo = 0x34100000u;                  // high word of 2^-190
+constexpr uint32_t kSvdRangeKeys = 0x4BD00000u - kSvdRangeLo;  // ... up to 2^190, exclusive: in range iff key < kSvdRangeKeys
+__device__ __forceinline__ void svd_range_track(uint32_t& worst, double x) {
+    worst = max(worst, ((uint32_t)__double2hiint(x) & 0x7FFFFFFFu) - kSvdRangeLo);
+}
+
 // makeJacobi through the in-range cores of division, reciprocal and square root (device_math.hpp): the same bits for operands in
-// range; wd / ws track the range tests of the operands that are not in range by construction
-__device__ __forceinline__ Rot make_jacobi_core(double x, double y, double z, uint32_t& wd, uint32_t& ws) {
+// range; wr tracks the range tests of xz and deno (svd_range_track: the other operands are in range by construction)
+// `identity`: the rotation is (1, 0).  That is the first branch and never the second: there j.s = +-|t| n with t = rcp_core(den), den
+// finite (never 0), and n in [0.7, 1] -- a product of normal numbers far from the underflow threshold
+__device__ __forceinline__ Rot make_jacobi_core(double x, double y, double z, uint32_t& wr, bool& identity) {
     Rot j;
-    double deno = 2.0 * fabs(y);
-    if (deno < DBL_MIN) {
+    double deno;  // 2.0 * fabs(y) = |y| + |y|, exactly
+    asm("v_add_f64 %0, |%1|, |%1|" : "=v"(deno) : "v"(y));
+    identity = fabs(y) < 0.5 * DBL_MIN;  // deno < DBL_MIN (doubling is exact), written on y: a condition the compiler knows to be wave-uniform
+    if (identity) {
         j.c = 1.0;
         j.s = 0.0;
     } else {
         const double xz = x - z;
-        div_range_track(wd, xz);
-        div_range_track(wd, deno);
+        svd_range_track(wr, xz);
+        svd_range_track(wr, deno);
         double tau = div_core(xz, deno);
         const double ww = tau * tau + 1.0;
-        sqrt_range_track(ws, ww);  // (>= 1: only an overflow of tau * tau takes it out of range)
         double w = sqrt_core(ww);
-        const double den = (tau > 0.0) ? tau + w : tau - w;  // |den| >= 1, < 2^513 while ww is in range
+        // The two sign selects of makeJacobi as sign-bit copies.  For operands in range tau is not 0 (|tau| > 2^-380) and t = 1 / den is a
+        // number with den's sign, so  (tau > 0 ? tau + w : tau - w) = tau + copysign(w, tau)  and  -sign_t * sign(y) * |t| = -sign(y) * t;
+        // multiplying by +-1 is exact and rounding is symmetric, so  ((-sign_t * sign(y)) * |t|) * n = -(t * n) * sign(y)  bit for bit.
+        // (A compare, a select and a sign flip less at each place; out of range the hypothesis is computed again.)
+        const double den = tau + copysign(w, tau);  // |den| >= 1, < 2^382 while xz and deno are in range
         double t = rcp_core(den);
-        double sign_t = t > 0.0 ? 1.0 : -1.0;
         double n = rcp_core(sqrt_core(t * t + 1.0));  // |t| <= 1: the argument lies in [1, 2], its root in [1, 1.42]
-        j.s = -sign_t * copysign(1.0, y) * fabs(t) * n;
+        j.s = -(t * n) * copysign(1.0, y);
         j.c = n;
     }
     return j;
@@ -199,13 +224,36 @@ __device__ __forceinline__ double& sh(double* M, int e) { return M[e]; }
 constexpr int kCoopV = 98;      // V behind W, two doubles off a multiple of 32: the row accesses of the two halves (stride 9) then use disjoint banks
 constexpr int kCoopSlots = 3;   // LDS slots (of 64 doubles) behind the per-lane block that hold the compact W and V
 
+// Two idioms on |.| source modifiers (lma_max_abs, lma_common.hpp, is the model): v_max_f64 returns the other operand for a NaN, like
+// fmax, and the modifiers spare the canonicalising copies (v_max_f64 x, x, x) the compiler puts in front of fmax.
+// max(m, max(|a|, |b|)): fmax(m, fmax(fabs(a), fabs(b)))
+__device__ __forceinline__ double max_abs3(double m, double a, double b) {
+    double t;
+    asm("v_max_f64 %1, |%2|, |%3|\n\tv_max_f64 %0, %0, %1" : "+v"(m), "=&v"(t) : "v"(a), "v"(b));
+    return m;
+}
+// fabs(a) > thr || fabs(b) > thr of wave-uniform values (a NaN fails its test in either form) as a SCALAR condition: the compiler takes
+// the result of an instruction it did not choose itself for divergent, and a branch on it for one that needs the exec mask saved and
+// restored; a compare into a scalar register pair is uniform.  Every lane of the wave is active where this is called.
+__device__ __forceinline__ bool any_abs_above(double a, double b, double thr) {
+    uint64_t lanes;
+    double t;
+    asm("v_max_f64 %1, |%2|, |%3|\n\tv_cmp_gt_f64 %0, %1, %4" : "=s"(lanes), "=&v"(t) : "v"(a), "v"(b), "v"(thr));
+    return lanes != 0;
+}
+// the sweep's threshold: precision * max_diag, floored at DBL_MIN
+__device__ __forceinline__ double svd_threshold(double max_diag) {
+    double threshold = (2.0 * DBL_EPSILON) * max_diag;
+    if (threshold < DBL_MIN) threshold = DBL_MIN;
+    return threshold;
+}
+
 // CORE: the rotations through the in-range function cores; *outside is set when an operand was out of range (the caller has the
 // hypotheses computed again with CORE = false)
 template <bool CORE>
-__device__ __forceinline__ void jacobi_svd9_nullvec_coop(double* W, double* V, int lane, LVec sv, LVec col, double (&e_out)[9], bool& outside, int& sweeps_out, int& rotations_out) {
-    uint32_t wd = 0, ws = 0;
+__device__ __forceinline__ void jacobi_svd9_nullvec_coop(double* W, double* V, int lane, double (&e_out)[9], bool& outside, int& sweeps_out, int& rotations_out) {
+    uint32_t wr = 0;
     int rotations = 0;
-    const double precision = 2.0 * DBL_EPSILON;
     // scale = max |W| (exact in any order)
     double m = fabs(sh(W, lane));
     if (lane < 17) m = fmax(m, fabs(sh(W, 64 + lane)));
@@ -223,6 +271,7 @@ __device__ __forceinline__ void jacobi_svd9_nullvec_coop(double* W, double* V, i
     const int li = lane & 15;
     const bool rowlane = li < 9 && lane < 32;
     double* RM = lane < 16 ? W : V;
+    double threshold = svd_threshold(max_diag);  // (a function of max_diag: formed again where that changes, not at every pair)
     bool finished = false;
     int sweeps = 0;
     while (!finished && sweeps < 1000) {
@@ -230,11 +279,9 @@ __device__ __forceinline__ void jacobi_svd9_nullvec_coop(double* W, double* V, i
         ++sweeps;
         for (int p = 1; p < 9; ++p) {
             for (int q = 0; q < p; ++q) {
-                double threshold = precision * max_diag;
-                if (threshold < DBL_MIN) threshold = DBL_MIN;
                 // the 2x2 block, broadcast to every lane
                 double m0 = sh(W, p * 9 + p), m1 = sh(W, p * 9 + q), m2 = sh(W, q * 9 + p), m3 = sh(W, q * 9 + q);
-                if (fabs(m1) > threshold || fabs(m2) > threshold) {
+                if (any_abs_above(m1, m2, threshold)) {  // fabs(m1) > threshold || fabs(m2) > threshold (a NaN entry fails its test either way)
                     finished = false;
                     ++rotations;
                     // real_2x2_jacobi_svd (JacobiSVD.h), identical to the scalar version
@@ -246,15 +293,12 @@ __device__ __forceinline__ void jacobi_svd9_nullvec_coop(double* W, double* V, i
                         rot1.c = 1.0;
                     } else {
                         if (CORE) {
-                            div_range_track(wd, t);
-                            div_range_track(wd, d);
+                            svd_range_track(wr, t);
+                            svd_range_track(wr, d);
                             const double uu = div_core(t, d);
                             const double a1p = 1.0 + uu * uu;
-                            sqrt_range_track(ws, a1p);
-                            const double tmp = sqrt_core(a1p);  // in [1, 2^512) while a1p is in range
+                            const double tmp = sqrt_core(a1p);  // in [1, 2^381) while t and d are in range
                             rot1.s = rcp_core(tmp);
-                            div_range_track(wd, uu);
-                            div_range_track(wd, tmp);
                             rot1.c = div_core(uu, tmp);
                         } else {
                             const double uu = t / d;
@@ -262,13 +306,22 @@ __device__ __forceinline__ void jacobi_svd9_nullvec_coop(double* W, double* V, i
                             rot1.s = 1.0 / tmp;
                             rot1.c = uu / tmp;
                         }
+                        // "is rot1 the identity": with the cores it is one exactly when the branch above ran -- here rot1.s = rcp_core(tmp)
+                        // with tmp finite (in [1, 2^381) for operands in range; a hypothesis out of range is computed again), never 0 -- so the
+                        // branch taken IS the test; the standard functions keep the computed test (1 / tmp is 0 for an infinite tmp)
+                        if (CORE || !(rot1.c == 1.0 && rot1.s == 0.0)) {
+                            const double a0 = rot1.c * m0 + rot1.s * m2, a2 = -rot1.s * m0 + rot1.c * m2;
+                            const double a1 = rot1.c * m1 + rot1.s * m3, a3 = -rot1.s * m1 + rot1.c * m3;
+                            m0 = a0, m1 = a1, m2 = a2, m3 = a3;
+                        }
                     }
-                    if (!(rot1.c == 1.0 && rot1.s == 0.0)) {
-                        const double a0 = rot1.c * m0 + rot1.s * m2, a2 = -rot1.s * m0 + rot1.c * m2;
-                        const double a1 = rot1.c * m1 + rot1.s * m3, a3 = -rot1.s * m1 + rot1.c * m3;
-                        m0 = a0, m1 = a1, m2 = a2, m3 = a3;
+                    bool jr_identity = false;
+                    if (CORE) {
+                        jr = make_jacobi_core(m0, m1, m3, wr, jr_identity);
+                    } else {
+                        jr = make_jacobi(m0, m1, m3);
+                        jr_identity = jr.c == 1.0 && jr.s == 0.0;
                     }
-                    jr = CORE ? make_jacobi_core(m0, m1, m3, wd, ws) : make_jacobi(m0, m1, m3);
                     const Rot jt = {jr.c, -jr.s};
                     jl.c = rot1.c * jt.c - rot1.s * jt.s;
                     jl.s = rot1.c * jt.s + rot1.s * jt.c;
@@ -280,43 +333,56 @@ __device__ __forceinline__ void jacobi_svd9_nullvec_coop(double* W, double* V, i
                     }
                     // applyOnTheRight(p, q, jr) on W and V: columns p, q, one row per lane
                     const Rot jrt = {jr.c, -jr.s};
-                    if (rowlane && !(jrt.c == 1.0 && jrt.s == 0.0)) {
+                    if (rowlane && !jr_identity) {
                         const double x = sh(RM, li * 9 + p), y = sh(RM, li * 9 + q);
                         sh(RM, li * 9 + p) = jrt.c * x + jrt.s * y;
                         sh(RM, li * 9 + q) = -jrt.s * x + jrt.c * y;
                     }
-                    max_diag = fmax(max_diag, fmax(fabs(sh(W, p * 9 + p)), fabs(sh(W, q * 9 + q))));
+                    max_diag = max_abs3(max_diag, sh(W, p * 9 + p), sh(W, q * 9 + q));
+                    threshold = svd_threshold(max_diag);
                 }
             }
         }
     }
-    if (CORE) outside = wd >= kDivRangeKeys || ws >= kSqrtRangeKeys;
+    if (CORE) outside = wr >= kSvdRangeKeys;
     sweeps_out = sweeps, rotations_out = rotations;
+    // selection sort, descending (JacobiSVD step 4): the comparisons of the scalar version in its order, on registers with compile-time
+    // indices (through the stride-64 LDS vectors the 36 comparisons were 36 dependent round trips); `live` is its `break`
+    double s[9];
+    int cl[9];
+#pragma unroll
     for (int i = 0; i < 9; ++i) {
-        sv[i] = fabs(sh(W, i * 9 + i)) * scale;
-        col[i] = (double)i;
+        s[i] = fabs(sh(W, i * 9 + i)) * scale;
+        cl[i] = i;
     }
-    for (int i = 0; i < 9; ++i) {  // selection sort, descending (JacobiSVD step 4), as in the scalar version
+    bool live = true;
+#pragma unroll
+    for (int i = 0; i < 9; ++i) {
         int pos = i;
-        double best = sv[i];
+        double best = s[i];
+#pragma unroll
         for (int j = i + 1; j < 9; ++j) {
-            const double sj = sv[j];
-            if (sj > best) {
-                best = sj;
+            if (s[j] > best) {
+                best = s[j];
                 pos = j;
             }
         }
-        if (best == 0.0) break;
-        if (pos != i) {
-            const double tt = sv[i];
-            sv[i] = sv[pos];
-            sv[pos] = tt;
-            const double tc = col[i];
-            col[i] = col[pos];
-            col[pos] = tc;
+        if (best == 0.0) live = false;
+        // swap slots i and pos (pos == i: both assignments below write what is there)
+        const double si = s[i];
+        const int ci = cl[i];
+        int cbest = ci;
+#pragma unroll
+        for (int j = i + 1; j < 9; ++j) {
+            const bool hit = live && pos == j;
+            cbest = hit ? cl[j] : cbest;
+            s[j] = hit ? si : s[j];
+            cl[j] = hit ? ci : cl[j];
         }
+        s[i] = live ? best : si;
+        cl[i] = cbest;
     }
-    const int c8 = (int)col[8];
+    const int c8 = cl[8];
 #pragma unroll
     for (int i = 0; i < 9; ++i) e_out[i] = sh(V, i * 9 + c8);
 }
@@ -946,10 +1012,10 @@ __device__ __forceinline__ void minimal9_body(double* lds, int block, int nblock
         bool outside = false;
         const unsigned long long svd_clk0 = direct.probe ? __builtin_amdgcn_s_memtime() : 0ull;
         if (direct.core_flag) {
-            jacobi_svd9_nullvec_coop<true>(Wc, Wc + kCoopV, lane, sv, col, e, outside, n_sweeps, n_rotations);
+            jacobi_svd9_nullvec_coop<true>(Wc, Wc + kCoopV, lane, e, outside, n_sweeps, n_rotations);
             if (outside && lane == 0) *direct.core_flag = direct.core_epoch;  // (every writer of this launch stores the same value)
         } else {
-            jacobi_svd9_nullvec_coop<false>(Wc, Wc + kCoopV, lane, sv, col, e, outside, n_sweeps, n_rotations);
+            jacobi_svd9_nullvec_coop<false>(Wc, Wc + kCoopV, lane, e, outside, n_sweeps, n_rotations);
         }
         if (direct.probe && lane == 0) {
             direct.probe[4 * t] = (double)n_sweeps;
