@@ -23,7 +23,7 @@
  * and what has been measured.
  *
  * NOT here: feathering between two neighbours' regions, multi-band blending, gains smoothed over time or solved jointly over the clip,
- * vignetting, occlusion tests between candidates, the clip's last frame (built since: rsdsfm_last_frame.h), inpainting of pixels nobody saw (built since:
+ * vignetting, occlusion tests between candidates (built since: rsdsfm_stabilize_visible.h), the clip's last frame (built since: rsdsfm_last_frame.h), inpainting of pixels nobody saw (built since:
  * rsdsfm_stabilize_inpaint.h).
  */
 #ifndef RSDSFM_STABILIZE_BLEND_H

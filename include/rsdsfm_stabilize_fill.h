@@ -18,8 +18,8 @@
  * DESIGN.md section 12 ("Border fill") has the launches, the bytes and what has been measured.
  *
  * NOT here: blending or feathering at the seams, exposure compensation between frames, occlusion tests between candidates (a fold of a
- * neighbour's map fills like any pixel), moving objects, inpainting of pixels nobody saw (built since: rsdsfm_stabilize_inpaint.h).  The
- * clip's last frame is built since: rsdsfm_last_frame.h.
+ * neighbour's map fills like any pixel; built since: rsdsfm_stabilize_visible.h, asked for with `occlusion` below), moving objects,
+ * inpainting of pixels nobody saw (built since: rsdsfm_stabilize_inpaint.h).  The clip's last frame is built since: rsdsfm_last_frame.h.
  */
 #ifndef RSDSFM_STABILIZE_FILL_H
 #define RSDSFM_STABILIZE_FILL_H
@@ -34,10 +34,15 @@ typedef struct rsdsfm_stabilize_fill_params {
     int32_t radius;       /* neighbours on each side, 1 .. 16; 0 = the default, 2, which is a choice, not a measurement */
     int32_t struct_bytes; /* 0 (zero-initialised struct) or sizeof(rsdsfm_stabilize_fill_params), as rsdsfm_stabilize_fill_params_init sets it;
                              anything else is refused: the caller was built against another layout */
-    int32_t reserved[2];  /* 0 */
+    int32_t occlusion;    /* 0 = off: every byte of every clip call is what it was before the word had a name.  1 = the neighbour candidates
+                             (source ids >= 2) of the clip calls go through rsdsfm_stabilize_visible_frame_dev (rsdsfm_stabilize_visible.h), in
+                             the filled call with the window (0, 0, rows, cols).  Anything else is refused.  (The first of two words that were
+                             `reserved`; the offset stays.) */
+    int32_t occlusion_tol_q16; /* the test's tolerance in 1 / 65536: 0 = the default, 3277 (a choice, not a measurement), 1 .. 65536; anything
+                             else is refused.  Read only when occlusion == 1.  (The second of the two words.) */
 } rsdsfm_stabilize_fill_params;
 
-/* radius = 2, struct_bytes = sizeof */
+/* radius = 2, struct_bytes = sizeof, occlusion = 0, occlusion_tol_q16 = 0 */
 int rsdsfm_stabilize_fill_params_init(rsdsfm_stabilize_fill_params* params);
 
 /* The candidates of frame q and their poses.  HOST arithmetic in double, no GPU, no context.  A / c: rsdsfm_chain_clip's, A_s / c_s:
@@ -85,7 +90,10 @@ int rsdsfm_stabilize_fill_launches(int32_t rows, int32_t cols);
  * With stabilize_params_or_null->last_frame == 1 the inner call renders the last frame too (see there), rsdsfm_neighbour_poses is asked with
  * nframes "pairs" and the loop runs p = 0 .. nframes - 1: the last frame has only previous candidates and is a candidate of the frames
  * before it, under the offsets' existing source ids.  d_masks_out, d_sources_or_null and counts_or_null then have nframes entries (rows),
- * like the inner call's per-frame arrays; the rule "byte for byte those public calls one after another" holds as it stands. */
+ * like the inner call's per-frame arrays; the rule "byte for byte those public calls one after another" holds as it stands.
+ * With fill_params_or_null->occlusion == 1 every candidate is one rsdsfm_stabilize_visible_frame_dev (rsdsfm_stabilize_visible.h) with the
+ * window (0, 0, rows, cols) and occlusion_tol_q16 in the fill call's place, and the rule holds with that call named; the counts keep
+ * their layout (the pixels taken), a rejected pixel shows up under a later offset or under `none`. */
 int rsdsfm_stabilize_video_filled_dev(rsdsfm_ctx* ctx, const uint8_t* const* d_frames, int32_t nframes, int32_t rows, int32_t cols, int32_t channels,
                                       double fx, double fy, double cx, double cy, double gamma, const rsdsfm_flow_params* flow_params_or_null,
                                       const rsdsfm_frame_params* params, const uint64_t* seeds, double* const* d_flows, double* const* d_depth_maps,

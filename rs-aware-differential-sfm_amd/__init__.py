@@ -1770,7 +1770,8 @@ STABILIZE_FILL_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "rs
 
 
 class StabilizeFillParams(C.Structure):
-    _fields_ = [("radius", C.c_int32), ("struct_bytes", C.c_int32), ("reserved", C.c_int32 * 2)]
+    _fields_ = [("radius", C.c_int32), ("struct_bytes", C.c_int32), ("occlusion", C.c_int32), ("occlusion_tol_q16", C.c_int32)]
+    reserved = property(lambda self: [self.occlusion, self.occlusion_tol_q16])  # the two words' name before they meant anything
 
 
 def stabilize_fill_declared_symbols():
@@ -1790,13 +1791,22 @@ def stabilize_fill_default_params():
     return dict(radius=p.radius)
 
 
-def _stabilize_fill_params(radius):
-    """a StabilizeFillParams with the given radius (0: the default)"""
+def _occlusion_tol_q16(tol):
+    """a tolerance as a fraction of the depth -> units of 1 / 65536; outside (0, 1] a value the library refuses"""
+    q = int(round(float(tol) * 65536.0))
+    return q if 1 <= q <= 65536 else -1
+
+
+def _stabilize_fill_params(radius, occlusion=False, occlusion_tol=None):
+    """a StabilizeFillParams with the given radius (0: the default); occlusion: the neighbour candidates go through the occlusion test
+    (stabilize_visible_frame_dev), occlusion_tol its tolerance as a fraction of the depth in (0, 1] (None: the default, about 0.05)"""
     p = StabilizeFillParams()
     if load_library().rsdsfm_stabilize_fill_params_init(C.byref(p)) != OK:
         raise RsdsfmError("rsdsfm_stabilize_fill_params_init failed")
     if radius:
         p.radius = int(radius)
+    p.occlusion = int(occlusion)  # (anything but 0 and 1 is refused by the library)
+    p.occlusion_tol_q16 = 0 if occlusion_tol is None else _occlusion_tol_q16(occlusion_tol)
     return p
 
 
@@ -1888,18 +1898,20 @@ class _StabilizeFillMixin:
                                    d_masks=None, seeds=None, flow_params=None, a1=None, a2=None, link_tol=None, min_links=None, radix_bits=None,
                                    mode=BACKPROJECT_RS, q5_mode=Q5_COMPAT, iterations=0, trials=50, tol=0.05, use_acceleration_mode=False, use_refinement=True,
                                    depth_mode=DEPTH_CERES_LM, k_sign_mode=K_COMPAT, flow_threshold=1e-10, flow_index_mode=FLOW_COMPAT_RANK,
-                                   use_global_shutter_mode=False, last_frame=False):
+                                   use_global_shutter_mode=False, last_frame=False, occlusion=False, occlusion_tol=None):
         """the stabilised clip with its borders filled in ONE call (rsdsfm_stabilize_video_filled_dev): stabilize_video_dev with these arguments
         (d_masks_out required), then for every frame its mask copied to d_sources (F - 1 device planes of bytes, optional), neighbour_poses with
         fill_radius neighbours on each side (0: the default, 2) and one stabilize_fill_frame_dev per candidate -- on the fused maps when d_fused
         is passed.  Returns stabilize_video_dev's dict plus, with want_counts, counts ((F - 1, 2 + 2 fill_radius) int64: [none, own, -1, +1,
         ...] per frame; the call then waits for the passes).
-        last_frame=True (see stabilize_video_dev): the clip's last frame too; every per-frame list and array then has F entries."""
+        last_frame=True (see stabilize_video_dev): the clip's last frame too; every per-frame list and array then has F entries.
+        occlusion=True: the neighbour candidates go through the occlusion test (stabilize_visible_frame_dev; occlusion_tol: its tolerance as a
+        fraction of the depth, None: the default) -- a rejected pixel shows up under a later offset or under none."""
         n = len(d_frames) - 1 + (1 if last_frame else 0)  # rendered frames
         _need_all(n, d_sources=d_sources)
-        fp = _stabilize_fill_params(fill_radius)
+        fp = _stabilize_fill_params(fill_radius, occlusion, occlusion_tol)
         counts = np.zeros((max(n, 1), 2 + 2 * fp.radius), dtype=np.int64) if want_counts else None
-        args = {k_: v_ for k_, v_ in locals().items() if k_ not in ("self", "n", "fp", "counts", "d_sources", "fill_radius", "want_counts")}
+        args = {k_: v_ for k_, v_ in locals().items() if k_ not in ("self", "n", "fp", "counts", "d_sources", "fill_radius", "want_counts", "occlusion", "occlusion_tol")}
         out = self._stabilize_video("rsdsfm_stabilize_video_filled_dev", (C.byref(fp), _ptr_array(d_sources) if d_sources is not None else None, _p(counts)), **args)
         if want_counts:
             out["counts"] = counts[:n]
@@ -2046,17 +2058,19 @@ class _StabilizeCropMixin:
                                     seeds=None, flow_params=None, a1=None, a2=None, link_tol=None, min_links=None, radix_bits=None, mode=BACKPROJECT_RS,
                                     q5_mode=Q5_COMPAT, iterations=0, trials=50, tol=0.05, use_acceleration_mode=False, use_refinement=True,
                                     depth_mode=DEPTH_CERES_LM, k_sign_mode=K_COMPAT, flow_threshold=1e-10, flow_index_mode=FLOW_COMPAT_RANK,
-                                    use_global_shutter_mode=False, last_frame=False):
+                                    use_global_shutter_mode=False, last_frame=False, occlusion=False, occlusion_tol=None):
         """the stabilised clip, cropped and zoomed, in ONE call (rsdsfm_stabilize_video_cropped_dev): stabilize_video_filled_dev with these
         arguments (fill_radius 0 .. 16 HERE: 0 means no fill, the inner call is then stabilize_video_dev), the window of its output masks
         (crop_window_dev with max_empty / margin; window_in = (r0, c0, h, w) skips the search) and, for every frame, the own frame and its
         neighbours through that window (stabilize_window_frame_dev) into d_crop, d_crop_masks and d_crop_sources (F - 1 device buffers each,
         zeroed first).  Returns the inner call's dict plus window and, with want_crop_counts, crop_counts ((F - 1, 2 + 2 fill_radius) int64:
         [none, own, -1, +1, ...] per frame; the call then waits for the passes).
-        last_frame=True (see stabilize_video_dev): the clip's last frame too; every per-frame list and array then has F entries."""
+        last_frame=True (see stabilize_video_dev): the clip's last frame too; every per-frame list and array then has F entries.
+        occlusion=True: the neighbour candidates go through the occlusion test (stabilize_visible_frame_dev; occlusion_tol: its tolerance as a
+        fraction of the depth, None: the default) -- a rejected pixel shows up under a later offset or under none."""
         n = len(d_frames) - 1 + (1 if last_frame else 0)  # rendered frames
         _need_all(n, d_sources=d_sources, d_crop=d_crop, d_crop_masks=d_crop_masks, d_crop_sources=d_crop_sources)
-        fp = _stabilize_fill_params(fill_radius)
+        fp = _stabilize_fill_params(fill_radius, occlusion, occlusion_tol)
         fp.radius = int(fill_radius)  # 0 stays 0 here
         cp = _stabilize_crop_params(max_empty, margin)
         width = 2 + 2 * int(fill_radius)
@@ -2065,7 +2079,7 @@ class _StabilizeCropMixin:
         window = (C.c_int32 * 4)()
         own = ("self", "n", "fp", "cp", "width", "counts", "crop_counts", "window", "d_sources", "fill_radius", "want_counts", "d_crop", "d_crop_masks",
                "d_crop_sources", "window_in", "max_empty", "margin", "want_crop_counts")
-        args = {k_: v_ for k_, v_ in locals().items() if k_ not in own and k_ != "own"}
+        args = {k_: v_ for k_, v_ in locals().items() if k_ not in own and k_ not in ("own", "occlusion", "occlusion_tol")}
         arr = lambda a: _ptr_array(a) if a is not None else None
         out = self._stabilize_video("rsdsfm_stabilize_video_cropped_dev",
                                     (C.byref(fp), arr(d_sources), _p(counts), C.byref(cp), _window4(window_in), arr(d_crop), arr(d_crop_masks), arr(d_crop_sources),
@@ -2079,6 +2093,80 @@ class _StabilizeCropMixin:
 
 
 for _name, _fn in list(vars(_StabilizeCropMixin).items()):
+    if not _name.startswith("__"):
+        setattr(Solver, _name, _fn)
+
+
+# ---------------------------------------------------------------------------------------------------
+# the stabiliser's occlusion test: a neighbour offers a pixel only where it is the nearest surface there (include/rsdsfm_stabilize_visible.h)
+# ---------------------------------------------------------------------------------------------------
+STABILIZE_VISIBLE_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "rsdsfm_stabilize_visible.h")
+OCCLUSION_TOL_Q16_DEFAULT = 3277  # RSDSFM_OCCLUSION_TOL_Q16_DEFAULT: about 0.05, a choice, not a measurement
+
+
+def stabilize_visible_declared_symbols():
+    """Names of every function include/rsdsfm_stabilize_visible.h declares"""
+    import re
+
+    txt = open(STABILIZE_VISIBLE_HEADER_PATH).read()
+    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
+    return sorted(set(re.findall(r"\b(rsdsfm_[a-z0-9_]+)\s*\(", txt)))
+
+
+def stabilize_visible_launches(rows, cols):
+    """kernel launches of one stabilize_visible_frame_dev call at this size: stabilize_window_launches -- the map kernel splats and the warp
+    kernel tests and counts by themselves (rsdsfm_stabilize_visible_launches; host only)"""
+    n = load_library().rsdsfm_stabilize_visible_launches(C.c_int32(rows), C.c_int32(cols))
+    if n < 0:
+        raise RsdsfmError("rsdsfm_stabilize_visible_launches failed (%d): rows and cols must be in [2, 16384]" % n)
+    return n
+
+
+class _StabilizeVisibleMixin:
+    def stabilize_visible_frame_dev(self, d_img_n, channels, d_depth_map_n, d_R_n, d_t_n, K, rows, cols, M, m, source_id, window, d_image, d_mask, d_source=None,
+                                    d_counts2=None, tol_q16=0, mode=BACKPROJECT_RS, q5_mode=Q5_COMPAT, iterations=0):
+        """one frame through a window and the occlusion test (rsdsfm_stabilize_visible_frame_dev; tests/stabilize_visible_spec_numpy.py):
+        stabilize_window_frame_dev, but a valid pixel whose source is not the nearest surface that lands there (within tol_q16 / 65536 of
+        the depth; 0: the default, 3277) is rejected and not taken.  d_counts2: two device int64 that receive [taken, rejected].  Enqueued on
+        the context's stream."""
+        d = C.c_double
+        Mh = None if M is None else _f64(M).reshape(9)
+        mh = None if m is None else _f64(m).reshape(3)
+        self._check(self.lib.rsdsfm_stabilize_visible_frame_dev(self._ctx, _dp(d_img_n), C.c_int32(channels), _dp(d_depth_map_n), _dp(d_R_n), _dp(d_t_n), d(K[0]),
+                                                                d(K[1]), d(K[2]), d(K[3]), C.c_int32(rows), C.c_int32(cols), int(mode), int(q5_mode),
+                                                                C.c_int32(iterations), _p(Mh), _p(mh), C.c_int32(source_id), _window4(window), _dp(d_image),
+                                                                _dp(d_mask), _np0(d_source), C.c_int32(tol_q16), _np0(d_counts2)),
+                    "rsdsfm_stabilize_visible_frame_dev")
+
+    def stabilize_visible(self, image_n, depth_map_n, R_n, t_n, K, M, m, source_id=2, window=None, image=None, mask=None, source=None, tol_q16=0, mode=BACKPROJECT_RS,
+                          q5_mode=Q5_COMPAT, iterations=0, device=0):
+        """host convenience around stabilize_visible_frame_dev: one candidate -- image_n (rows, cols[, 3]) uint8, depth_map_n (rows, cols) (0
+        where unknown), R_n (rows, 3, 3) / (rows, 9), t_n (rows, 3), seen with (M, m) -- onto the planes image / mask / source (None: zeroed;
+        the arrays passed are not changed).  window None: the full frame.  Returns (image, mask, source (rows, cols) uint8, taken, rejected)."""
+        import torch
+
+        img = np.ascontiguousarray(image_n, dtype=np.uint8)
+        rows, cols = img.shape[:2]
+        channels = 1 if img.ndim == 2 else img.shape[2]
+        dev = torch.device("cuda", device)
+        with torch.cuda.device(dev):
+            up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+            plane = lambda a, like: up(np.zeros_like(like) if a is None else np.asarray(a, dtype=np.uint8))
+            zero = np.zeros((rows, cols), dtype=np.uint8)
+            d_n, d_dm = up(img), up(np.asarray(depth_map_n, dtype=np.float64).T)
+            d_R, d_t = up(_f64(np.asarray(R_n).reshape(rows, 9))), up(_f64(t_n))
+            d_out, d_mask, d_source = plane(image, img), plane(mask, zero), plane(source, zero)
+            d_cnt = torch.zeros(2, dtype=torch.int64, device=dev)
+            torch.cuda.synchronize()
+            self.stabilize_visible_frame_dev(d_n.data_ptr(), channels, d_dm.data_ptr(), d_R.data_ptr(), d_t.data_ptr(), K, rows, cols, M, m, int(source_id),
+                                             (0, 0, rows, cols) if window is None else window, d_out.data_ptr(), d_mask.data_ptr(), d_source.data_ptr(),
+                                             d_cnt.data_ptr(), tol_q16=tol_q16, mode=mode, q5_mode=q5_mode, iterations=iterations)
+            self.synchronize()
+            cnt = d_cnt.cpu().numpy()
+            return d_out.cpu().numpy(), d_mask.cpu().numpy(), d_source.cpu().numpy(), int(cnt[0]), int(cnt[1])
+
+
+for _name, _fn in list(vars(_StabilizeVisibleMixin).items()):
     if not _name.startswith("__"):
         setattr(Solver, _name, _fn)
 
@@ -2193,7 +2281,7 @@ class _StabilizeBlendMixin:
                                     d_masks=None, seeds=None, flow_params=None, a1=None, a2=None, link_tol=None, min_links=None, radix_bits=None,
                                     mode=BACKPROJECT_RS, q5_mode=Q5_COMPAT, iterations=0, trials=50, tol=0.05, use_acceleration_mode=False, use_refinement=True,
                                     depth_mode=DEPTH_CERES_LM, k_sign_mode=K_COMPAT, flow_threshold=1e-10, flow_index_mode=FLOW_COMPAT_RANK,
-                                    use_global_shutter_mode=False, last_frame=False):
+                                    use_global_shutter_mode=False, last_frame=False, occlusion=False, occlusion_tol=None):
         """the stabilised clip, cropped, zoomed and blended, in ONE call (rsdsfm_stabilize_video_blended_dev): stabilize_video_cropped_dev with
         these arguments, then for every frame the own frame through the window into d_blend, d_blend_masks and d_blend_sources (F - 1 device
         buffers each, zeroed first), seam_distance_dev of its mask and, per neighbour, the neighbour alone on the context's layer and
@@ -2201,10 +2289,12 @@ class _StabilizeBlendMixin:
         window_in = (0, 0, rows, cols).  Returns stabilize_video_cropped_dev's dict plus, with want_gains, gains ((F - 1, 2 fill_radius, 3)
         uint32 in 1 / 65536, per offset -1, +1, -2, +2, ...) and, with want_blend_counts, blend_counts ((F - 1, 2 + 4 fill_radius) int64:
         [none, own_untouched, (filled, blended) per offset]); with either the call waits for the passes.
-        last_frame=True (see stabilize_video_dev): the clip's last frame too; every per-frame list and array then has F entries."""
+        last_frame=True (see stabilize_video_dev): the clip's last frame too; every per-frame list and array then has F entries.
+        occlusion=True: the neighbour candidates go through the occlusion test (stabilize_visible_frame_dev; occlusion_tol: its tolerance as a
+        fraction of the depth, None: the default) -- a rejected pixel shows up under a later offset or under none."""
         n = len(d_frames) - 1 + (1 if last_frame else 0)  # rendered frames
         _need_all(n, d_sources=d_sources, d_crop=d_crop, d_crop_masks=d_crop_masks, d_crop_sources=d_crop_sources, d_blend=d_blend, d_blend_masks=d_blend_masks, d_blend_sources=d_blend_sources)
-        fp = _stabilize_fill_params(fill_radius)
+        fp = _stabilize_fill_params(fill_radius, occlusion, occlusion_tol)
         fp.radius = int(fill_radius)  # 0 stays 0 here
         cp = _stabilize_crop_params(max_empty, margin)
         bp = _stabilize_blend_params(blend_feather, blend_gain, blend_min_overlap)
@@ -2217,7 +2307,7 @@ class _StabilizeBlendMixin:
         own = ("self", "n", "fp", "cp", "bp", "width", "counts", "crop_counts", "gains", "blend_counts", "window", "d_sources", "fill_radius", "want_counts", "d_crop",
                "d_crop_masks", "d_crop_sources", "window_in", "max_empty", "margin", "want_crop_counts", "d_blend", "d_blend_masks", "d_blend_sources",
                "blend_feather", "blend_gain", "blend_min_overlap", "want_gains", "want_blend_counts")
-        args = {k_: v_ for k_, v_ in locals().items() if k_ not in own and k_ != "own"}
+        args = {k_: v_ for k_, v_ in locals().items() if k_ not in own and k_ not in ("own", "occlusion", "occlusion_tol")}
         arr = lambda a: _ptr_array(a) if a is not None else None
         out = self._stabilize_video("rsdsfm_stabilize_video_blended_dev",
                                     (C.byref(fp), arr(d_sources), _p(counts), C.byref(cp), _window4(window_in), arr(d_crop), arr(d_crop_masks), arr(d_crop_sources),
@@ -2297,16 +2387,18 @@ class _StabilizeInpaintMixin:
                                       want_valid=True, sigma=None, radius=0, translation=True, fuse_tol=None, d_masks=None, seeds=None, flow_params=None, a1=None,
                                       a2=None, link_tol=None, min_links=None, radix_bits=None, mode=BACKPROJECT_RS, q5_mode=Q5_COMPAT, iterations=0, trials=50,
                                       tol=0.05, use_acceleration_mode=False, use_refinement=True, depth_mode=DEPTH_CERES_LM, k_sign_mode=K_COMPAT,
-                                      flow_threshold=1e-10, flow_index_mode=FLOW_COMPAT_RANK, use_global_shutter_mode=False, last_frame=False):
+                                      flow_threshold=1e-10, flow_index_mode=FLOW_COMPAT_RANK, use_global_shutter_mode=False, last_frame=False, occlusion=False, occlusion_tol=None):
         """the stabilised clip, cropped, zoomed, blended and inpainted, in ONE call (rsdsfm_stabilize_video_inpainted_dev):
         stabilize_video_blended_dev with these arguments, then for every frame d_blend copied to d_inpaint (and d_blend_sources to
         d_inpaint_sources when passed; F - 1 device buffers each) and inpaint_frame_dev on the copy with the frame's blend mask.  Returns
         stabilize_video_blended_dev's dict plus, with want_inpaint_counts, inpaint_counts ((F - 1,) int64: the pixels written per frame; the
         call then waits for the passes).
-        last_frame=True (see stabilize_video_dev): the clip's last frame too; every per-frame list and array then has F entries."""
+        last_frame=True (see stabilize_video_dev): the clip's last frame too; every per-frame list and array then has F entries.
+        occlusion=True: the neighbour candidates go through the occlusion test (stabilize_visible_frame_dev; occlusion_tol: its tolerance as a
+        fraction of the depth, None: the default) -- a rejected pixel shows up under a later offset or under none."""
         n = len(d_frames) - 1 + (1 if last_frame else 0)  # rendered frames
         _need_all(n, d_sources=d_sources, d_crop=d_crop, d_crop_masks=d_crop_masks, d_crop_sources=d_crop_sources, d_blend=d_blend, d_blend_masks=d_blend_masks, d_blend_sources=d_blend_sources, d_inpaint=d_inpaint, d_inpaint_sources=d_inpaint_sources)
-        fp = _stabilize_fill_params(fill_radius)
+        fp = _stabilize_fill_params(fill_radius, occlusion, occlusion_tol)
         fp.radius = int(fill_radius)  # 0 stays 0 here
         cp = _stabilize_crop_params(max_empty, margin)
         bp = _stabilize_blend_params(blend_feather, blend_gain, blend_min_overlap)
@@ -2321,7 +2413,7 @@ class _StabilizeInpaintMixin:
                "want_counts", "d_crop", "d_crop_masks", "d_crop_sources", "window_in", "max_empty", "margin", "want_crop_counts", "d_blend", "d_blend_masks",
                "d_blend_sources", "blend_feather", "blend_gain", "blend_min_overlap", "want_gains", "want_blend_counts", "d_inpaint", "d_inpaint_sources",
                "want_inpaint_counts")
-        args = {k_: v_ for k_, v_ in locals().items() if k_ not in own and k_ != "own"}
+        args = {k_: v_ for k_, v_ in locals().items() if k_ not in own and k_ not in ("own", "occlusion", "occlusion_tol")}
         arr = lambda a: _ptr_array(a) if a is not None else None
         out = self._stabilize_video("rsdsfm_stabilize_video_inpainted_dev",
                                     (C.byref(fp), arr(d_sources), _p(counts), C.byref(cp), _window4(window_in), arr(d_crop), arr(d_crop_masks), arr(d_crop_sources),

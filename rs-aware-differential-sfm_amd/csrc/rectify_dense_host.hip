@@ -15,6 +15,8 @@ static void dense_ws_free(DenseWs* w) {
     if (w->d_seam) (void)hipFree(w->d_seam);
     if (w->d_layer) (void)hipFree(w->d_layer);
     if (w->d_inpaint) (void)hipFree(w->d_inpaint);
+    if (w->d_visible) (void)hipFree(w->d_visible);
+    w->d_visible = nullptr;
     w->d_pyr = nullptr;
     w->d_disp = nullptr;
     w->d_mask = nullptr;

@@ -9,6 +9,7 @@
 #include "last_frame.hpp"
 #include "sequence_host.hpp"
 #include "stabilize_blend.hpp"
+#include "stabilize_visible.hpp"
 
 namespace rsdsfm {
 namespace {
@@ -144,6 +145,7 @@ int rsdsfm_stabilize_video_blended_dev(rsdsfm_ctx* ctx, const uint8_t* const* d_
                                                 window_in_or_null, d_crop_images, d_crop_masks, d_crop_sources_or_null, window_out, crop_counts_or_null);
     if (rc != RSDSFM_OK) return rc;
     const int radius = fill_params_or_null ? fill_params_or_null->radius : kBlendFillRadiusDefault;  // 0 .. 16: the inner call checked it
+    const bool occ = visible_asked(fill_params_or_null);  // every layer is rendered through the occlusion test (the inner call checked the words)
     const int offs = 2 * radius;
     const size_t plane = (size_t)rows * (size_t)cols, P = blend_plane_bytes(rows, cols);
     const bool have = window_out[2] >= 1, host = gains_or_null || blend_counts_or_null;
@@ -191,9 +193,12 @@ int rsdsfm_stabilize_video_blended_dev(rsdsfm_ctx* ctx, const uint8_t* const* d_
                 rc = fail(c, RSDSFM_ERR_HIP, "blend: zeroing the layer failed");
                 break;
             }
-            rc = rsdsfm_stabilize_window_frame_dev(ctx, d_frames[n], channels, d_fused_maps_or_null ? d_fused_maps_or_null[n] : d_depth_maps[n], d_R[n], d_t[n], fx, fy,
-                                                   cx, cy, rows, cols, mode, q5_mode, iterations, nM + 9 * (size_t)k, nm + 3 * (size_t)k, ids[k], window_out, d_limage,
-                                                   d_lmask, nullptr, nullptr);
+            const double* nmap = d_fused_maps_or_null ? d_fused_maps_or_null[n] : d_depth_maps[n];
+            rc = occ ? rsdsfm_stabilize_visible_frame_dev(ctx, d_frames[n], channels, nmap, d_R[n], d_t[n], fx, fy, cx, cy, rows, cols, mode, q5_mode, iterations,
+                                                          nM + 9 * (size_t)k, nm + 3 * (size_t)k, ids[k], window_out, d_limage, d_lmask, nullptr,
+                                                          fill_params_or_null->occlusion_tol_q16, nullptr)
+                     : rsdsfm_stabilize_window_frame_dev(ctx, d_frames[n], channels, nmap, d_R[n], d_t[n], fx, fy, cx, cy, rows, cols, mode, q5_mode, iterations,
+                                                         nM + 9 * (size_t)k, nm + 3 * (size_t)k, ids[k], window_out, d_limage, d_lmask, nullptr, nullptr);
             if (rc == RSDSFM_OK)
                 rc = rsdsfm_seam_blend_layer_dev(ctx, d_limage, d_lmask, channels, rows, cols, d_dist, &bp, ids[k], d_blend_images[p], d_blend_masks[p], d_blend_sources[p],
                                                  rec ? rec + (size_t)slot * 8 : d_one,

@@ -10,6 +10,7 @@
 #include "last_frame.hpp"
 #include "sequence_host.hpp"
 #include "stabilize_crop.hpp"
+#include "stabilize_visible.hpp"
 
 namespace rsdsfm {
 namespace {
@@ -163,8 +164,11 @@ int rsdsfm_stabilize_video_cropped_dev(rsdsfm_ctx* ctx, const uint8_t* const* d_
     const int np = stabilize_rendered_frames(stabilize_params_or_null, nframes);  // rendered frames: the pairs' first frames, and the last frame when asked for
     if (!crop_size_ok(rows, cols)) return fail(c, RSDSFM_ERR_INVALID, "crop: rows and cols must be in [2, 16384]");
     if (fill_params_or_null && ((fill_params_or_null->struct_bytes != 0 && fill_params_or_null->struct_bytes != (int32_t)sizeof(rsdsfm_stabilize_fill_params)) ||
-                                fill_params_or_null->radius < 0 || fill_params_or_null->radius > kCropFillRadiusMax))
-        return fail(c, RSDSFM_ERR_INVALID, "rsdsfm_stabilize_fill_params: radius in [0, 16], struct_bytes 0 or sizeof (use rsdsfm_stabilize_fill_params_init)");
+                                fill_params_or_null->radius < 0 || fill_params_or_null->radius > kCropFillRadiusMax || !visible_words_ok(fill_params_or_null)))
+        return fail(c, RSDSFM_ERR_INVALID,
+                    "rsdsfm_stabilize_fill_params: radius in [0, 16], occlusion 0 or 1, occlusion_tol_q16 in [0, 65536], struct_bytes 0 or sizeof (use rsdsfm_stabilize_fill_params_init)");
+    const bool occ = visible_asked(fill_params_or_null);  // the neighbours go through the occlusion test: [taken, rejected] per frame call, the first is the count
+    const int cw = occ ? 2 : 1;
     const int radius = fill_params_or_null ? fill_params_or_null->radius : kCropFillRadiusDefault;  // 0 here: no fill at all
     const rsdsfm_stabilize_crop_params cp = crop_params_or_null ? *crop_params_or_null : crop_defaults();
     if (!crop_params_ok(cp, rows, cols))
@@ -217,8 +221,8 @@ int rsdsfm_stabilize_video_cropped_dev(rsdsfm_ctx* ctx, const uint8_t* const* d_
     const bool have = window_out[2] >= 1;
     int64_t* d_cnt = nullptr;
     if (crop_counts_or_null && have) {
-        RSDSFM_HIP_CHECK(c, hipMalloc(reinterpret_cast<void**>(&d_cnt), sizeof(int64_t) * (size_t)np * slots));
-        const hipError_t e = hipMemsetAsync(d_cnt, 0, sizeof(int64_t) * (size_t)np * slots, c->stream);
+        RSDSFM_HIP_CHECK(c, hipMalloc(reinterpret_cast<void**>(&d_cnt), sizeof(int64_t) * (size_t)np * slots * cw));
+        const hipError_t e = hipMemsetAsync(d_cnt, 0, sizeof(int64_t) * (size_t)np * slots * cw, c->stream);
         if (e != hipSuccess) {
             (void)hipFree(d_cnt);
             RSDSFM_HIP_CHECK(c, e);
@@ -234,15 +238,19 @@ int rsdsfm_stabilize_video_cropped_dev(rsdsfm_ctx* ctx, const uint8_t* const* d_
         if (!have || rc != RSDSFM_OK) continue;
         const double* map = d_fused_maps_or_null ? d_fused_maps_or_null[p] : d_depth_maps[p];
         rc = rsdsfm_stabilize_window_frame_dev(ctx, d_frames[p], channels, map, d_R[p], d_t[p], fx, fy, cx, cy, rows, cols, mode, q5_mode, iterations, M + 9 * (size_t)p,
-                                               m + 3 * (size_t)p, 1, window_out, d_crop_images[p], d_crop_masks[p], src, d_cnt ? d_cnt + (size_t)p * slots : nullptr);
+                                               m + 3 * (size_t)p, 1, window_out, d_crop_images[p], d_crop_masks[p], src, d_cnt ? d_cnt + (size_t)p * slots * cw : nullptr);
         listed = 0;
         if (rc == RSDSFM_OK && radius > 0 && rsdsfm_neighbour_poses(A, c_, A_s, c_s, scales, np, p, radius, frames, ids, nM, nm, &listed) != RSDSFM_OK)
             rc = fail(c, RSDSFM_ERR_INVALID, "crop: a neighbour's scale is not finite and positive");
         for (int k = 0; k < listed && rc == RSDSFM_OK; ++k) {
             const int n = frames[k];
-            rc = rsdsfm_stabilize_window_frame_dev(ctx, d_frames[n], channels, d_fused_maps_or_null ? d_fused_maps_or_null[n] : d_depth_maps[n], d_R[n], d_t[n], fx, fy,
-                                                   cx, cy, rows, cols, mode, q5_mode, iterations, nM + 9 * (size_t)k, nm + 3 * (size_t)k, ids[k], window_out,
-                                                   d_crop_images[p], d_crop_masks[p], src, d_cnt ? d_cnt + (size_t)p * slots + (ids[k] - 1) : nullptr);
+            const double* nmap = d_fused_maps_or_null ? d_fused_maps_or_null[n] : d_depth_maps[n];
+            int64_t* cnt = d_cnt ? d_cnt + ((size_t)p * slots + (ids[k] - 1)) * cw : nullptr;
+            rc = occ ? rsdsfm_stabilize_visible_frame_dev(ctx, d_frames[n], channels, nmap, d_R[n], d_t[n], fx, fy, cx, cy, rows, cols, mode, q5_mode, iterations,
+                                                          nM + 9 * (size_t)k, nm + 3 * (size_t)k, ids[k], window_out, d_crop_images[p], d_crop_masks[p], src,
+                                                          fill_params_or_null->occlusion_tol_q16, cnt)
+                     : rsdsfm_stabilize_window_frame_dev(ctx, d_frames[n], channels, nmap, d_R[n], d_t[n], fx, fy, cx, cy, rows, cols, mode, q5_mode, iterations,
+                                                         nM + 9 * (size_t)k, nm + 3 * (size_t)k, ids[k], window_out, d_crop_images[p], d_crop_masks[p], src, cnt);
         }
     }
     if (crop_counts_or_null && !have && rc == RSDSFM_OK) {
@@ -254,7 +262,7 @@ int rsdsfm_stabilize_video_cropped_dev(rsdsfm_ctx* ctx, const uint8_t* const* d_
         RSDSFM_HIP_CHECK(c, hipStreamSynchronize(c->stream));
     }
     if (d_cnt) {
-        std::vector<int64_t> taken((size_t)np * slots);
+        std::vector<int64_t> taken((size_t)np * slots * cw);
         hipError_t e = rc == RSDSFM_OK ? hipMemcpyAsync(taken.data(), d_cnt, sizeof(int64_t) * taken.size(), hipMemcpyDeviceToHost, c->stream) : hipSuccess;
         if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
         (void)hipFree(d_cnt);
@@ -263,7 +271,7 @@ int rsdsfm_stabilize_video_cropped_dev(rsdsfm_ctx* ctx, const uint8_t* const* d_
             for (int p = 0; p < np; ++p) {
                 int64_t* row = crop_counts_or_null + (size_t)p * (1 + slots);
                 int64_t sum = 0;
-                for (int k = 0; k < slots; ++k) sum += (row[1 + k] = taken[(size_t)p * slots + k]);
+                for (int k = 0; k < slots; ++k) sum += (row[1 + k] = taken[((size_t)p * slots + k) * cw]);
                 row[0] = (int64_t)plane - sum;
             }
     }

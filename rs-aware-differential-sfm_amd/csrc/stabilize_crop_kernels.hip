@@ -21,6 +21,7 @@
 #include "rectify_dense_device.hpp"
 #include "rsdsfm_internal.hpp"
 #include "stabilize_crop.hpp"
+#include "stabilize_window_device.hpp"
 
 namespace rsdsfm {
 
@@ -31,45 +32,12 @@ constexpr int kSegs = 8;  // row segments of the column scan: kCB = 64 columns x
 // 1 in every byte of w that is not 0
 __device__ __forceinline__ unsigned bytes_set(unsigned w) { return ((w | ((w & 0x7f7f7f7fu) + 0x7f7f7f7fu)) >> 7) & 0x01010101u; }
 
-// warp_pixel (rectify_dense_device.hpp) with the target given: the fixed point about (gx, gy), then the sample
-template <int CH>
-__device__ __forceinline__ unsigned warp_pixel_at(const unsigned char* __restrict__ img, const float2* __restrict__ disp, int rows, int cols, int iterations,
-                                                  double gx, double gy, unsigned* v) {
-    double px = gx, py = gy;
-    for (int it = 0; it < iterations; ++it) {
-        const Tap tx = tap(px, cols), ty = tap(py, rows);
-        const float2* r0 = disp + (int64_t)ty.i0 * cols;
-        const float2* r1 = disp + (int64_t)ty.i1 * cols;
-        const float2 d00 = r0[tx.i0], d01 = r0[tx.i1], d10 = r1[tx.i0], d11 = r1[tx.i1];
-        const double dx = lerp(lerp((double)d00.x, (double)d01.x, tx.a), lerp((double)d10.x, (double)d11.x, tx.a), ty.a);
-        const double dy = lerp(lerp((double)d00.y, (double)d01.y, tx.a), lerp((double)d10.y, (double)d11.y, tx.a), ty.a);
-        px = gx - dx;
-        py = gy - dy;
-    }
-    const bool valid = px >= -0.5 && px < (double)cols - 0.5 && py >= -0.5 && py < (double)rows - 0.5;  // false for NaN / inf
-    const Tap tx = tap(px, cols), ty = tap(py, rows);
-    const unsigned char* r0 = img + ((int64_t)ty.i0 * cols) * CH;
-    const unsigned char* r1 = img + ((int64_t)ty.i1 * cols) * CH;
-#pragma unroll
-    for (int c = 0; c < CH; ++c) {
-        const double i00 = (double)r0[tx.i0 * CH + c], i01 = (double)r0[tx.i1 * CH + c], i10 = (double)r1[tx.i0 * CH + c], i11 = (double)r1[tx.i1 * CH + c];
-        const unsigned s = saturate_u8(lerp(lerp(i00, i01, tx.a), lerp(i10, i11, tx.a), ty.a));
-        v[c] = valid ? s : 0u;
-    }
-    return valid ? 1u : 0u;
-}
-
-// the window (r0, c0) and the scales sy = h / rows, sx = w / cols, as doubles: uniform
-struct CropMap {
-    double r0, c0, sy, sx;
-};
-
+// warp_pixel_at, CropMap and window_target: stabilize_window_device.hpp (shared with the occlusion test's warp kernels)
 template <int CH>
 __device__ __forceinline__ unsigned window_pixel(const unsigned char* __restrict__ img, const float2* __restrict__ disp, int rows, int cols, int iterations,
                                                  const CropMap& wm, int p, unsigned* v) {
-    const int iy = p / cols, ix = p - iy * cols;
-    const double tx = (wm.c0 + ((double)ix + 0.5) * wm.sx) - 0.5;
-    const double ty = (wm.r0 + ((double)iy + 0.5) * wm.sy) - 0.5;
+    double tx, ty;
+    window_target(wm, cols, p, tx, ty);
     return warp_pixel_at<CH>(img, disp, rows, cols, iterations, tx, ty, v);
 }
 

@@ -11,17 +11,18 @@
 #include "last_frame.hpp"
 #include "sequence_host.hpp"
 #include "stabilize_fill.hpp"
+#include "stabilize_visible.hpp"
 
 namespace rsdsfm {
 namespace {
 
 constexpr int kFillRadiusDefault = 2, kFillRadiusMax = 16;
 
-rsdsfm_stabilize_fill_params fill_defaults() { return rsdsfm_stabilize_fill_params{kFillRadiusDefault, (int32_t)sizeof(rsdsfm_stabilize_fill_params), {0, 0}}; }
+rsdsfm_stabilize_fill_params fill_defaults() { return rsdsfm_stabilize_fill_params{kFillRadiusDefault, (int32_t)sizeof(rsdsfm_stabilize_fill_params), 0, 0}; }
 
 bool fill_params_ok(const rsdsfm_stabilize_fill_params& p) {
     if (p.struct_bytes != 0 && p.struct_bytes != (int32_t)sizeof(rsdsfm_stabilize_fill_params)) return false;
-    return p.radius >= 0 && p.radius <= kFillRadiusMax;
+    return p.radius >= 0 && p.radius <= kFillRadiusMax && visible_words_ok(&p);
 }
 
 bool fill_finite_all(const double* a, int n) {
@@ -125,8 +126,11 @@ int rsdsfm_stabilize_video_filled_dev(rsdsfm_ctx* ctx, const uint8_t* const* d_f
     const int np = stabilize_rendered_frames(stabilize_params_or_null, nframes);  // rendered frames: the pairs' first frames, and the last frame when asked for
     const rsdsfm_stabilize_fill_params fp = fill_params_or_null ? *fill_params_or_null : fill_defaults();
     if (!fill_params_ok(fp))
-        return fail(c, RSDSFM_ERR_INVALID, "rsdsfm_stabilize_fill_params: radius in [0, 16], struct_bytes 0 or sizeof (use rsdsfm_stabilize_fill_params_init)");
+        return fail(c, RSDSFM_ERR_INVALID, "rsdsfm_stabilize_fill_params: radius in [0, 16], occlusion 0 or 1, occlusion_tol_q16 in [0, 65536], struct_bytes 0 or sizeof (use rsdsfm_stabilize_fill_params_init)");
     const int radius = fp.radius ? fp.radius : kFillRadiusDefault;
+    const bool occ = visible_asked(&fp);  // the candidates go through the occlusion test: [taken, rejected] per candidate, the first is the count
+    const int cw = occ ? 2 : 1;
+    const int32_t full[4] = {0, 0, rows, cols};
     if (!all_set(d_masks_out, np)) return fail(c, RSDSFM_ERR_INVALID, "border fill: d_masks_out is required -- a candidate is taken where the mask is 0");
     if (d_sources_or_null) {
         if (!all_set(d_sources_or_null, np)) return fail(c, RSDSFM_ERR_INVALID, "border fill: null device pointer");
@@ -150,8 +154,8 @@ int rsdsfm_stabilize_video_filled_dev(rsdsfm_ctx* ctx, const uint8_t* const* d_f
     const int slots = 2 * radius;
     int64_t* d_cnt = nullptr;  // a counter per frame and offset, at source id - 2; a skipped offset keeps its 0
     if (counts_or_null) {
-        RSDSFM_HIP_CHECK(c, hipMalloc(reinterpret_cast<void**>(&d_cnt), sizeof(int64_t) * (size_t)np * slots));
-        const hipError_t e = hipMemsetAsync(d_cnt, 0, sizeof(int64_t) * (size_t)np * slots, c->stream);
+        RSDSFM_HIP_CHECK(c, hipMalloc(reinterpret_cast<void**>(&d_cnt), sizeof(int64_t) * (size_t)np * slots * cw));
+        const hipError_t e = hipMemsetAsync(d_cnt, 0, sizeof(int64_t) * (size_t)np * slots * cw, c->stream);
         if (e != hipSuccess) {
             (void)hipFree(d_cnt);
             RSDSFM_HIP_CHECK(c, e);
@@ -166,13 +170,18 @@ int rsdsfm_stabilize_video_filled_dev(rsdsfm_ctx* ctx, const uint8_t* const* d_f
             rc = fail(c, RSDSFM_ERR_INVALID, "border fill: a neighbour's scale is not finite and positive");
         for (int k = 0; k < listed && rc == RSDSFM_OK; ++k) {
             const int n = frames[k];
-            rc = rsdsfm_stabilize_fill_frame_dev(ctx, d_frames[n], channels, d_fused_maps_or_null ? d_fused_maps_or_null[n] : d_depth_maps[n], d_R[n], d_t[n], fx, fy, cx,
-                                                 cy, rows, cols, mode, q5_mode, iterations, nM + 9 * (size_t)k, nm + 3 * (size_t)k, ids[k], d_stab_images[p], d_masks_out[p],
-                                                 d_sources_or_null ? d_sources_or_null[p] : nullptr, d_cnt ? d_cnt + (size_t)p * slots + (ids[k] - 2) : nullptr);
+            const double* map = d_fused_maps_or_null ? d_fused_maps_or_null[n] : d_depth_maps[n];
+            uint8_t* src = d_sources_or_null ? d_sources_or_null[p] : nullptr;
+            int64_t* cnt = d_cnt ? d_cnt + ((size_t)p * slots + (ids[k] - 2)) * cw : nullptr;
+            rc = occ ? rsdsfm_stabilize_visible_frame_dev(ctx, d_frames[n], channels, map, d_R[n], d_t[n], fx, fy, cx, cy, rows, cols, mode, q5_mode, iterations,
+                                                          nM + 9 * (size_t)k, nm + 3 * (size_t)k, ids[k], full, d_stab_images[p], d_masks_out[p], src,
+                                                          fp.occlusion_tol_q16, cnt)
+                     : rsdsfm_stabilize_fill_frame_dev(ctx, d_frames[n], channels, map, d_R[n], d_t[n], fx, fy, cx, cy, rows, cols, mode, q5_mode, iterations,
+                                                       nM + 9 * (size_t)k, nm + 3 * (size_t)k, ids[k], d_stab_images[p], d_masks_out[p], src, cnt);
         }
     }
     if (d_cnt) {
-        std::vector<int64_t> filled((size_t)np * slots);
+        std::vector<int64_t> filled((size_t)np * slots * cw);
         hipError_t e = rc == RSDSFM_OK ? hipMemcpyAsync(filled.data(), d_cnt, sizeof(int64_t) * filled.size(), hipMemcpyDeviceToHost, c->stream) : hipSuccess;
         if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
         (void)hipFree(d_cnt);
@@ -182,7 +191,7 @@ int rsdsfm_stabilize_video_filled_dev(rsdsfm_ctx* ctx, const uint8_t* const* d_f
                 int64_t* row = counts_or_null + (size_t)p * (2 + slots);
                 int64_t rest = valid[p];
                 row[1] = valid[p];
-                for (int k = 0; k < slots; ++k) rest += (row[2 + k] = filled[(size_t)p * slots + k]);
+                for (int k = 0; k < slots; ++k) rest += (row[2 + k] = filled[((size_t)p * slots + k) * cw]);
                 row[0] = (int64_t)plane - rest;
             }
     }

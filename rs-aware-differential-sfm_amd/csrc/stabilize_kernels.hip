@@ -27,62 +27,9 @@ __global__ __launch_bounds__(kCB) void stabilize_map_kernel(const double* __rest
                                                            const double* __restrict__ R, const double* __restrict__ t, double fx, double fy, double cx,
                                                            double cy, double fyp, int rows, int cols, int mode, StabPose vp, float2* __restrict__ disp,
                                                            double* __restrict__ filled_cm) {
-    constexpr int RPW = kTY / (kCB / kTX);  // scanlines per wave
-    __shared__ double s_z[kTX][kTY + 1];
-    const int x0 = blockIdx.x * kTX, y0 = blockIdx.y * kTY;
-    const int tid = threadIdx.x;
-    const int lx = tid & (kTX - 1);
-    const int x = x0 + lx;
-    const int wv = __builtin_amdgcn_readfirstlane(tid / kTX);
-    const int sy = tid & (kTY - 1);  // the staging layout: lanes along y
-    double zst[kTX * kTY / kCB];
-#pragma unroll
-    for (int j = 0; j < kTX * kTY / kCB; ++j) {
-        const int xx = x0 + tid / kTY + j * (kCB / kTY), yy = y0 + sy;
-        zst[j] = (xx < cols && yy < rows) ? depth_cm[(int64_t)xx * rows + yy] : 0.0;
-    }
-    double R0[9], t0[3];
-#pragma unroll
-    for (int i = 0; i < 9; ++i) R0[i] = R[i];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) t0[i] = t[i];
-#pragma unroll
-    for (int j = 0; j < kTX * kTY / kCB; ++j) s_z[tid / kTY + j * (kCB / kTY)][sy] = zst[j];
-    __syncthreads();
-#pragma unroll
-    for (int j = 0; j < RPW; ++j) {
-        const int ly = wv + j * (kCB / kTX);
-        const int y = y0 + ly;  // wave-uniform
-        double Rr[9], tr[3];
-        const int ys = (mode == 0 && y < rows) ? y : 0;
-#pragma unroll
-        for (int i = 0; i < 9; ++i) Rr[i] = R[(int64_t)ys * 9 + i];
-#pragma unroll
-        for (int i = 0; i < 3; ++i) tr[i] = t[(int64_t)ys * 3 + i];
-        if (y < rows && x < cols) {
-            double z = s_z[lx][ly];
-            if (inverse_depth(z) == 0.0) {  // the last push step: level 0 from level 1
-                const double rho = push_from(lv1, h1, w1, x, y);
-                z = rho > 0.0 ? 1.0 / rho : 0.0;
-                s_z[lx][ly] = z;  // (read and written by this thread only)
-            }
-            double pg[3], pv[3], gx, gy;
-            rs_to_gs_point(x, y, z, Rr, tr, R0, t0, fx, fy, cx, cy, pg);
-#pragma unroll
-            for (int i = 0; i < 3; ++i) pv[i] = ((vp.M[3 * i] * pg[0] + vp.M[3 * i + 1] * pg[1]) + vp.M[3 * i + 2] * pg[2]) + vp.m[i];
-            rs_to_gs_project(pv, fx, cx, cy, fyp, gx, gy);
-            disp[(int64_t)y * cols + x] = make_float2((float)(gx - (double)x), (float)(gy - (double)y));
-        }
-    }
-    if (filled_cm) {  // (uniform)
-        __syncthreads();
-#pragma unroll
-        for (int j = 0; j < kTX * kTY / kCB; ++j) {
-            const int sx = tid / kTY + j * (kCB / kTY);
-            const int xx = x0 + sx, yy = y0 + sy;
-            if (xx < cols && yy < rows) filled_cm[(int64_t)xx * rows + yy] = s_z[sx][sy];
-        }
-    }
+#define RSDSFM_STABILIZE_MAP_VISIBLE 0
+#include "stabilize_map_body.hpp"  // the kernel's statements, shared as text with stabilize_visible_map_kernel (see there for why)
+#undef RSDSFM_STABILIZE_MAP_VISIBLE
 }
 
 // mask: npix bytes of 1 / 0, 4-byte aligned; *count += their sum.  grid-stride over the npix / 4 words, the npix % 4 tail bytes by one thread.

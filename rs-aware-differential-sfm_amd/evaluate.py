@@ -208,7 +208,7 @@ def evaluate_real_sequence(solver, frames, camera="galaxy", gamma=0.95, out_dir=
                            use_refinement=True, use_global_shutter_mode=False, flow_threshold=1e-10, flow_index_mode=0, device=0, flow_params=None, dense=False,
                            check_flow=False, trajectory=False, link_tol=None, min_links=None, fuse=False, fuse_tol=None, stabilize=False, smooth_sigma=None,
                            smooth_translation=True, fill=0, crop=False, crop_margin=None, crop_max_empty=0, blend=False, blend_feather=None,
-                           blend_gain=True, inpaint=False, last_frame=False):
+                           blend_gain=True, inpaint=False, last_frame=False, occlusion=False, occlusion_tol=None):
     """evaluate_real_run's real-world branch (main.cc:341-361, 364-531) for a clip: `frames` is <prefix>frame1.png ... frameN.png (the
     prefix, or a list of paths), or the frames themselves (an (N, rows, cols[, 3]) uint8 array or a list of arrays; 2-D frames are gray).
     By default ONE call does the clip (Solver.rectify_video_dev): the batched DeepFlow of every consecutive pair, the pipelined solve of every pair p
@@ -266,7 +266,15 @@ def evaluate_real_sequence(solver, frames, camera="galaxy", gamma=0.95, out_dir=
     it and that pair's motion (Solver.last_frame_dev; the fused map by Solver.advance_depth_dev with fuse=True; the last pair's scale): every
     stage above then has one more frame -- one more entry in its lists and arrays, the N-th stabilized*_<p>.png and one more row in fill.csv,
     crop.csv, blend.csv and inpaint.csv -- and the last frame is a candidate for the frames before it.  The solve's outputs, the trajectory and
-    path_smoothed's A_s and c_s are unchanged (M and m gain the last frame's entry).  Without last_frame every output is what it was."""
+    path_smoothed's A_s and c_s are unchanged (M and m gain the last frame's entry).  Without last_frame every output is what it was.
+    occlusion=True (needs stabilize=True and fill >= 1: ValueError otherwise): every NEIGHBOUR candidate of the fill, the crop and the blend is
+    rendered by Solver.stabilize_visible_frame_dev (tests/stabilize_visible_spec_numpy.py; the fill through the full-frame window): a pixel whose
+    source is not the nearest surface that lands there -- a fold of the neighbour's map, a parallax ghost -- is rejected and left to the next
+    candidate or the inpainter.  occlusion_tol: the test's tolerance as a fraction of the depth in (0, 1] (None: the default, about 0.05).  The
+    outputs keep their keys, shapes and files; a rejected pixel shows up under a later offset or under none.  Without occlusion every output
+    is what it was."""
+    if occlusion and not (stabilize and fill >= 1):
+        raise ValueError("occlusion needs stabilize=True and fill >= 1: it tests the neighbour candidates of the stabilised frames")
     if last_frame and not stabilize:
         raise ValueError("last_frame needs stabilize=True: it renders the clip's last frame")
     if inpaint and not stabilize:
@@ -412,6 +420,25 @@ def evaluate_real_sequence(solver, frames, camera="galaxy", gamma=0.95, out_dir=
                 solver.synchronize()
                 traj.update(stabilized=[t.cpu().numpy() for t in d_stabs], stab_masks=[t.cpu().numpy() for t in d_smasks],
                             stab_valid=[int(x) for x in d_svalid.cpu().numpy()], path_smoothed=dict(A_s=A_s, c_s=c_s, M=vM, m=vm))
+                if occlusion:
+                    from . import _occlusion_tol_q16
+
+                    occ_q16 = 0 if occlusion_tol is None else _occlusion_tol_q16(occlusion_tol)
+                    d_occ = torch.zeros((nst, 2 + 2 * fill, 2), dtype=torch.int64, device=dev)  # [taken, rejected] of the call in flight
+
+                def neighbour_dev(n, sid, nM, nm, window, d_image, d_mask, d_source, d_count, p):
+                    """one neighbour candidate: the window call (the fill call without a window), or with occlusion the visible call, whose first
+                    counter is copied behind it"""
+                    head = (d_imgs[n].data_ptr(), channels, d_src[n].data_ptr(), d_Rs[n].data_ptr(), d_ts[n].data_ptr(), K, rows, cols, nM, nm, int(sid))
+                    tail = (d_image.data_ptr(), d_mask.data_ptr(), None if d_source is None else d_source.data_ptr())
+                    if occlusion:
+                        solver.stabilize_visible_frame_dev(*head, window or (0, 0, rows, cols), *tail, None if d_count is None else d_occ[p, int(sid)].data_ptr(),
+                                                           tol_q16=occ_q16, mode=mode)
+                    elif window is None:
+                        solver.stabilize_fill_frame_dev(*head, *tail, None if d_count is None else d_count.data_ptr(), mode=mode)
+                    else:
+                        solver.stabilize_window_frame_dev(*head, window, *tail, None if d_count is None else d_count.data_ptr(), mode=mode)
+
                 if fill:
                     from . import neighbour_poses
 
@@ -421,11 +448,11 @@ def evaluate_real_sequence(solver, frames, camera="galaxy", gamma=0.95, out_dir=
                     torch.cuda.synchronize()
                     for p in range(nst):  # every pass enqueued, one wait for all of them
                         for n, sid, nM, nm in zip(*neighbour_poses(traj["A"], traj["c"], A_s, c_s, st_scales, p, fill)):
-                            solver.stabilize_fill_frame_dev(d_imgs[n].data_ptr(), channels, d_src[n].data_ptr(), d_Rs[n].data_ptr(), d_ts[n].data_ptr(), K, rows,
-                                                            cols, nM, nm, int(sid), d_fills[p].data_ptr(), d_fmasks2[p].data_ptr(), d_sources[p].data_ptr(),
-                                                            d_fcnt[p, int(sid):].data_ptr(), mode=mode)
+                            neighbour_dev(n, sid, nM, nm, None, d_fills[p], d_fmasks2[p], d_sources[p], d_fcnt[p, int(sid):], p)
                     solver.synchronize()
                     counts = d_fcnt.cpu().numpy()
+                    if occlusion:
+                        counts[:, 2:] = d_occ.cpu().numpy()[:, 2:, 0]
                     counts[:, 0] = rows * cols - counts[:, 1:].sum(axis=1)
                     traj.update(stab_filled=[t.cpu().numpy() for t in d_fills], stab_sources=[t.cpu().numpy() for t in d_sources], fill_counts=counts)
                 if crop:
@@ -439,11 +466,16 @@ def evaluate_real_sequence(solver, frames, camera="galaxy", gamma=0.95, out_dir=
                     for p in range(nst if window[2] else 0):  # every pass enqueued, one wait for all of them
                         cand = [(p, 1, vM[p], vm[p])] + (list(zip(*neighbour_poses(traj["A"], traj["c"], A_s, c_s, st_scales, p, fill))) if fill else [])
                         for n, sid, nM, nm in cand:
-                            solver.stabilize_window_frame_dev(d_imgs[n].data_ptr(), channels, d_src[n].data_ptr(), d_Rs[n].data_ptr(), d_ts[n].data_ptr(), K, rows,
-                                                              cols, nM, nm, int(sid), window, d_crops[p].data_ptr(), d_cmasks[p].data_ptr(), None,
-                                                              d_ccnt[p, int(sid):].data_ptr(), mode=mode)
+                            if int(sid) == 1:  # the own frame keeps its call
+                                solver.stabilize_window_frame_dev(d_imgs[n].data_ptr(), channels, d_src[n].data_ptr(), d_Rs[n].data_ptr(), d_ts[n].data_ptr(), K,
+                                                                  rows, cols, nM, nm, 1, window, d_crops[p].data_ptr(), d_cmasks[p].data_ptr(), None,
+                                                                  d_ccnt[p, 1:].data_ptr(), mode=mode)
+                            else:
+                                neighbour_dev(n, sid, nM, nm, window, d_crops[p], d_cmasks[p], None, d_ccnt[p, int(sid):], p)
                     solver.synchronize()
                     counts = d_ccnt.cpu().numpy()
+                    if occlusion and window[2]:
+                        counts[:, 2:] = d_occ.cpu().numpy()[:, 2:, 0]
                     counts[:, 0] = rows * cols - counts[:, 1:].sum(axis=1)
                     traj.update(stab_cropped=[t.cpu().numpy() for t in d_crops], crop_window=window, crop_counts=counts)
                 if blend:
@@ -471,8 +503,7 @@ def evaluate_real_sequence(solver, frames, camera="galaxy", gamma=0.95, out_dir=
                         solver.seam_distance_dev(d_bmasks[p].data_ptr(), rows, cols, blend_feather or 0, d_dist.data_ptr())
                         for n, sid, nM, nm in zip(*neighbour_poses(traj["A"], traj["c"], A_s, c_s, st_scales, p, fill)):
                             d_layer, d_lmask = d_layers[int(sid) - 2], d_lmasks[int(sid) - 2]
-                            solver.stabilize_window_frame_dev(d_imgs[n].data_ptr(), channels, d_src[n].data_ptr(), d_Rs[n].data_ptr(), d_ts[n].data_ptr(), K, rows,
-                                                              cols, nM, nm, int(sid), bwindow, d_layer.data_ptr(), d_lmask.data_ptr(), None, None, mode=mode)
+                            neighbour_dev(n, sid, nM, nm, bwindow, d_layer, d_lmask, None, None, p)
                             solver.seam_blend_layer_dev(d_layer.data_ptr(), d_lmask.data_ptr(), channels, rows, cols, d_dist.data_ptr(), int(sid),
                                                         d_blends[p].data_ptr(), d_bmasks[p].data_ptr(), d_bsources[p].data_ptr(), d_sums[p, int(sid) - 2].data_ptr(),
                                                         d_bcnt[p, int(sid) - 2].data_ptr(), feather=blend_feather, gain=blend_gain)
