@@ -32,7 +32,7 @@
  * public calls made one after another" holds with this call named in the others' place.  The own frame (id 1) keeps its call.  The count
  * arrays keep their layout: a rejected pixel shows up as fewer pixels for that offset and more for later offsets or `none`.
  *
- * NOT here: searching for the VISIBLE pre-image instead of rejecting, the own frame, the dense rectifier's own folds, per-clip rejected
+ * NOT here: searching for the VISIBLE pre-image instead of rejecting (built since: rsdsfm_stabilize_search.h), the own frame, the dense rectifier's own folds, per-clip rejected
  * counts, the C++ mirror.
  */
 #ifndef RSDSFM_STABILIZE_VISIBLE_H

@@ -10,6 +10,7 @@ Mirrors the reference's function boundary (reference: src/minimal.h:79-161, src/
     Solver.estimate_inverse_depths / non_linear_refinement
     Solver.flatten / depth_map / pose_table            (caller glue, rsframe.cc:771-800)
 """
+import contextlib
 import ctypes as C
 import os
 import sys
@@ -1898,7 +1899,7 @@ class _StabilizeFillMixin:
                                    d_masks=None, seeds=None, flow_params=None, a1=None, a2=None, link_tol=None, min_links=None, radix_bits=None,
                                    mode=BACKPROJECT_RS, q5_mode=Q5_COMPAT, iterations=0, trials=50, tol=0.05, use_acceleration_mode=False, use_refinement=True,
                                    depth_mode=DEPTH_CERES_LM, k_sign_mode=K_COMPAT, flow_threshold=1e-10, flow_index_mode=FLOW_COMPAT_RANK,
-                                   use_global_shutter_mode=False, last_frame=False, occlusion=False, occlusion_tol=None):
+                                   use_global_shutter_mode=False, last_frame=False, occlusion=False, occlusion_tol=None, occlusion_search=False):
         """the stabilised clip with its borders filled in ONE call (rsdsfm_stabilize_video_filled_dev): stabilize_video_dev with these arguments
         (d_masks_out required), then for every frame its mask copied to d_sources (F - 1 device planes of bytes, optional), neighbour_poses with
         fill_radius neighbours on each side (0: the default, 2) and one stabilize_fill_frame_dev per candidate -- on the fused maps when d_fused
@@ -1906,13 +1907,16 @@ class _StabilizeFillMixin:
         ...] per frame; the call then waits for the passes).
         last_frame=True (see stabilize_video_dev): the clip's last frame too; every per-frame list and array then has F entries.
         occlusion=True: the neighbour candidates go through the occlusion test (stabilize_visible_frame_dev; occlusion_tol: its tolerance as a
-        fraction of the depth, None: the default) -- a rejected pixel shows up under a later offset or under none."""
+        fraction of the depth, None: the default) -- a rejected pixel shows up under a later offset or under none.
+        occlusion_search=True (needs occlusion): set_occlusion_search(1) for this call -- a rejected pixel whose visible pre-image is found is
+        recovered (stabilize_search_frame_dev) and counts under its offset; the knob is put back afterwards."""
         n = len(d_frames) - 1 + (1 if last_frame else 0)  # rendered frames
         _need_all(n, d_sources=d_sources)
         fp = _stabilize_fill_params(fill_radius, occlusion, occlusion_tol)
         counts = np.zeros((max(n, 1), 2 + 2 * fp.radius), dtype=np.int64) if want_counts else None
-        args = {k_: v_ for k_, v_ in locals().items() if k_ not in ("self", "n", "fp", "counts", "d_sources", "fill_radius", "want_counts", "occlusion", "occlusion_tol")}
-        out = self._stabilize_video("rsdsfm_stabilize_video_filled_dev", (C.byref(fp), _ptr_array(d_sources) if d_sources is not None else None, _p(counts)), **args)
+        args = {k_: v_ for k_, v_ in locals().items() if k_ not in ("self", "n", "fp", "counts", "d_sources", "fill_radius", "want_counts", "occlusion", "occlusion_tol", "occlusion_search")}
+        with _occlusion_search_for(self, occlusion_search, occlusion):
+            out = self._stabilize_video("rsdsfm_stabilize_video_filled_dev", (C.byref(fp), _ptr_array(d_sources) if d_sources is not None else None, _p(counts)), **args)
         if want_counts:
             out["counts"] = counts[:n]
         return out
@@ -2058,7 +2062,7 @@ class _StabilizeCropMixin:
                                     seeds=None, flow_params=None, a1=None, a2=None, link_tol=None, min_links=None, radix_bits=None, mode=BACKPROJECT_RS,
                                     q5_mode=Q5_COMPAT, iterations=0, trials=50, tol=0.05, use_acceleration_mode=False, use_refinement=True,
                                     depth_mode=DEPTH_CERES_LM, k_sign_mode=K_COMPAT, flow_threshold=1e-10, flow_index_mode=FLOW_COMPAT_RANK,
-                                    use_global_shutter_mode=False, last_frame=False, occlusion=False, occlusion_tol=None):
+                                    use_global_shutter_mode=False, last_frame=False, occlusion=False, occlusion_tol=None, occlusion_search=False):
         """the stabilised clip, cropped and zoomed, in ONE call (rsdsfm_stabilize_video_cropped_dev): stabilize_video_filled_dev with these
         arguments (fill_radius 0 .. 16 HERE: 0 means no fill, the inner call is then stabilize_video_dev), the window of its output masks
         (crop_window_dev with max_empty / margin; window_in = (r0, c0, h, w) skips the search) and, for every frame, the own frame and its
@@ -2067,7 +2071,9 @@ class _StabilizeCropMixin:
         [none, own, -1, +1, ...] per frame; the call then waits for the passes).
         last_frame=True (see stabilize_video_dev): the clip's last frame too; every per-frame list and array then has F entries.
         occlusion=True: the neighbour candidates go through the occlusion test (stabilize_visible_frame_dev; occlusion_tol: its tolerance as a
-        fraction of the depth, None: the default) -- a rejected pixel shows up under a later offset or under none."""
+        fraction of the depth, None: the default) -- a rejected pixel shows up under a later offset or under none.
+        occlusion_search=True (needs occlusion): set_occlusion_search(1) for this call -- a rejected pixel whose visible pre-image is found is
+        recovered (stabilize_search_frame_dev) and counts under its offset; the knob is put back afterwards."""
         n = len(d_frames) - 1 + (1 if last_frame else 0)  # rendered frames
         _need_all(n, d_sources=d_sources, d_crop=d_crop, d_crop_masks=d_crop_masks, d_crop_sources=d_crop_sources)
         fp = _stabilize_fill_params(fill_radius, occlusion, occlusion_tol)
@@ -2079,11 +2085,12 @@ class _StabilizeCropMixin:
         window = (C.c_int32 * 4)()
         own = ("self", "n", "fp", "cp", "width", "counts", "crop_counts", "window", "d_sources", "fill_radius", "want_counts", "d_crop", "d_crop_masks",
                "d_crop_sources", "window_in", "max_empty", "margin", "want_crop_counts")
-        args = {k_: v_ for k_, v_ in locals().items() if k_ not in own and k_ not in ("own", "occlusion", "occlusion_tol")}
+        args = {k_: v_ for k_, v_ in locals().items() if k_ not in own and k_ not in ("own", "occlusion", "occlusion_tol", "occlusion_search")}
         arr = lambda a: _ptr_array(a) if a is not None else None
-        out = self._stabilize_video("rsdsfm_stabilize_video_cropped_dev",
-                                    (C.byref(fp), arr(d_sources), _p(counts), C.byref(cp), _window4(window_in), arr(d_crop), arr(d_crop_masks), arr(d_crop_sources),
-                                     window, _p(crop_counts)), **args)
+        with _occlusion_search_for(self, occlusion_search, occlusion):
+            out = self._stabilize_video("rsdsfm_stabilize_video_cropped_dev",
+                                        (C.byref(fp), arr(d_sources), _p(counts), C.byref(cp), _window4(window_in), arr(d_crop), arr(d_crop_masks), arr(d_crop_sources),
+                                         window, _p(crop_counts)), **args)
         out["window"] = tuple(int(x) for x in window)
         if want_counts:
             out["counts"] = counts[:n]
@@ -2167,6 +2174,103 @@ class _StabilizeVisibleMixin:
 
 
 for _name, _fn in list(vars(_StabilizeVisibleMixin).items()):
+    if not _name.startswith("__"):
+        setattr(Solver, _name, _fn)
+
+
+# ---------------------------------------------------------------------------------------------------
+# the search for the visible pre-image: a pixel the occlusion test rejects is looked for again from the source pixel that landed nearest the
+# camera (include/rsdsfm_stabilize_search.h)
+# ---------------------------------------------------------------------------------------------------
+STABILIZE_SEARCH_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "rsdsfm_stabilize_search.h")
+
+
+def stabilize_search_declared_symbols():
+    """Names of every function include/rsdsfm_stabilize_search.h declares"""
+    import re
+
+    txt = open(STABILIZE_SEARCH_HEADER_PATH).read()
+    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
+    return sorted(set(re.findall(r"\b(rsdsfm_[a-z0-9_]+)\s*\(", txt)))
+
+
+def stabilize_search_launches(rows, cols):
+    """kernel launches of one stabilize_search_frame_dev call at this size: stabilize_window_launches -- the map kernel splats the keys and the
+    warp kernel tests, searches and counts by themselves (rsdsfm_stabilize_search_launches; host only)"""
+    n = load_library().rsdsfm_stabilize_search_launches(C.c_int32(rows), C.c_int32(cols))
+    if n < 0:
+        raise RsdsfmError("rsdsfm_stabilize_search_launches failed (%d): rows and cols must be in [2, 16384]" % n)
+    return n
+
+
+@contextlib.contextmanager
+def _occlusion_search_for(solver, search, occlusion):
+    """a clip call's occlusion_search keyword: True = the context's knob at 1 for the call and put back afterwards (it needs occlusion), False =
+    the knob stays where set_occlusion_search left it"""
+    if not search:
+        yield
+        return
+    if not occlusion:
+        raise RsdsfmError("occlusion_search=True needs occlusion=True: the search runs where the occlusion test rejects")
+    before = getattr(solver, "_occlusion_search", 0)
+    solver.set_occlusion_search(1)
+    try:
+        yield
+    finally:
+        solver.set_occlusion_search(before)
+
+
+class _StabilizeSearchMixin:
+    def set_occlusion_search(self, on):
+        """the clip calls' knob (rsdsfm_set_occlusion_search): 0 (the default) = a neighbour candidate that goes through the occlusion test goes
+        through stabilize_visible_frame_dev, 1 = through stabilize_search_frame_dev; anything else is refused.  It takes effect only in calls
+        with occlusion=True."""
+        self._check(self.lib.rsdsfm_set_occlusion_search(self._ctx, C.c_int32(int(on))), "rsdsfm_set_occlusion_search")
+        self._occlusion_search = int(on)
+
+    def stabilize_search_frame_dev(self, d_img_n, channels, d_depth_map_n, d_R_n, d_t_n, K, rows, cols, M, m, source_id, window, d_image, d_mask, d_source=None,
+                                   d_counts3=None, tol_q16=0, mode=BACKPROJECT_RS, q5_mode=Q5_COMPAT, iterations=0):
+        """one frame through a window, the occlusion test and the search (rsdsfm_stabilize_search_frame_dev; tests/stabilize_search_spec_numpy.py):
+        stabilize_visible_frame_dev, but a pixel the test rejects is looked for again from the source pixel that landed nearest the camera on
+        its cell and, where that ends on the visible surface, recovered.  d_counts3: three device int64 that receive [taken, rejected,
+        recovered].  Enqueued on the context's stream."""
+        d = C.c_double
+        Mh = None if M is None else _f64(M).reshape(9)
+        mh = None if m is None else _f64(m).reshape(3)
+        self._check(self.lib.rsdsfm_stabilize_search_frame_dev(self._ctx, _dp(d_img_n), C.c_int32(channels), _dp(d_depth_map_n), _dp(d_R_n), _dp(d_t_n), d(K[0]),
+                                                               d(K[1]), d(K[2]), d(K[3]), C.c_int32(rows), C.c_int32(cols), int(mode), int(q5_mode),
+                                                               C.c_int32(iterations), _p(Mh), _p(mh), C.c_int32(source_id), _window4(window), _dp(d_image),
+                                                               _dp(d_mask), _np0(d_source), C.c_int32(tol_q16), _np0(d_counts3)),
+                    "rsdsfm_stabilize_search_frame_dev")
+
+    def stabilize_search(self, image_n, depth_map_n, R_n, t_n, K, M, m, source_id=2, window=None, image=None, mask=None, source=None, tol_q16=0, mode=BACKPROJECT_RS,
+                         q5_mode=Q5_COMPAT, iterations=0, device=0):
+        """host convenience around stabilize_search_frame_dev: stabilize_visible's arguments.  Returns (image, mask, source (rows, cols) uint8,
+        taken, rejected, recovered)."""
+        import torch
+
+        img = np.ascontiguousarray(image_n, dtype=np.uint8)
+        rows, cols = img.shape[:2]
+        channels = 1 if img.ndim == 2 else img.shape[2]
+        dev = torch.device("cuda", device)
+        with torch.cuda.device(dev):
+            up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+            plane = lambda a, like: up(np.zeros_like(like) if a is None else np.asarray(a, dtype=np.uint8))
+            zero = np.zeros((rows, cols), dtype=np.uint8)
+            d_n, d_dm = up(img), up(np.asarray(depth_map_n, dtype=np.float64).T)
+            d_R, d_t = up(_f64(np.asarray(R_n).reshape(rows, 9))), up(_f64(t_n))
+            d_out, d_mask, d_source = plane(image, img), plane(mask, zero), plane(source, zero)
+            d_cnt = torch.zeros(3, dtype=torch.int64, device=dev)
+            torch.cuda.synchronize()
+            self.stabilize_search_frame_dev(d_n.data_ptr(), channels, d_dm.data_ptr(), d_R.data_ptr(), d_t.data_ptr(), K, rows, cols, M, m, int(source_id),
+                                            (0, 0, rows, cols) if window is None else window, d_out.data_ptr(), d_mask.data_ptr(), d_source.data_ptr(),
+                                            d_cnt.data_ptr(), tol_q16=tol_q16, mode=mode, q5_mode=q5_mode, iterations=iterations)
+            self.synchronize()
+            cnt = d_cnt.cpu().numpy()
+            return d_out.cpu().numpy(), d_mask.cpu().numpy(), d_source.cpu().numpy(), int(cnt[0]), int(cnt[1]), int(cnt[2])
+
+
+for _name, _fn in list(vars(_StabilizeSearchMixin).items()):
     if not _name.startswith("__"):
         setattr(Solver, _name, _fn)
 
@@ -2281,7 +2385,7 @@ class _StabilizeBlendMixin:
                                     d_masks=None, seeds=None, flow_params=None, a1=None, a2=None, link_tol=None, min_links=None, radix_bits=None,
                                     mode=BACKPROJECT_RS, q5_mode=Q5_COMPAT, iterations=0, trials=50, tol=0.05, use_acceleration_mode=False, use_refinement=True,
                                     depth_mode=DEPTH_CERES_LM, k_sign_mode=K_COMPAT, flow_threshold=1e-10, flow_index_mode=FLOW_COMPAT_RANK,
-                                    use_global_shutter_mode=False, last_frame=False, occlusion=False, occlusion_tol=None):
+                                    use_global_shutter_mode=False, last_frame=False, occlusion=False, occlusion_tol=None, occlusion_search=False):
         """the stabilised clip, cropped, zoomed and blended, in ONE call (rsdsfm_stabilize_video_blended_dev): stabilize_video_cropped_dev with
         these arguments, then for every frame the own frame through the window into d_blend, d_blend_masks and d_blend_sources (F - 1 device
         buffers each, zeroed first), seam_distance_dev of its mask and, per neighbour, the neighbour alone on the context's layer and
@@ -2291,7 +2395,9 @@ class _StabilizeBlendMixin:
         [none, own_untouched, (filled, blended) per offset]); with either the call waits for the passes.
         last_frame=True (see stabilize_video_dev): the clip's last frame too; every per-frame list and array then has F entries.
         occlusion=True: the neighbour candidates go through the occlusion test (stabilize_visible_frame_dev; occlusion_tol: its tolerance as a
-        fraction of the depth, None: the default) -- a rejected pixel shows up under a later offset or under none."""
+        fraction of the depth, None: the default) -- a rejected pixel shows up under a later offset or under none.
+        occlusion_search=True (needs occlusion): set_occlusion_search(1) for this call -- a rejected pixel whose visible pre-image is found is
+        recovered (stabilize_search_frame_dev) and counts under its offset; the knob is put back afterwards."""
         n = len(d_frames) - 1 + (1 if last_frame else 0)  # rendered frames
         _need_all(n, d_sources=d_sources, d_crop=d_crop, d_crop_masks=d_crop_masks, d_crop_sources=d_crop_sources, d_blend=d_blend, d_blend_masks=d_blend_masks, d_blend_sources=d_blend_sources)
         fp = _stabilize_fill_params(fill_radius, occlusion, occlusion_tol)
@@ -2307,12 +2413,13 @@ class _StabilizeBlendMixin:
         own = ("self", "n", "fp", "cp", "bp", "width", "counts", "crop_counts", "gains", "blend_counts", "window", "d_sources", "fill_radius", "want_counts", "d_crop",
                "d_crop_masks", "d_crop_sources", "window_in", "max_empty", "margin", "want_crop_counts", "d_blend", "d_blend_masks", "d_blend_sources",
                "blend_feather", "blend_gain", "blend_min_overlap", "want_gains", "want_blend_counts")
-        args = {k_: v_ for k_, v_ in locals().items() if k_ not in own and k_ not in ("own", "occlusion", "occlusion_tol")}
+        args = {k_: v_ for k_, v_ in locals().items() if k_ not in own and k_ not in ("own", "occlusion", "occlusion_tol", "occlusion_search")}
         arr = lambda a: _ptr_array(a) if a is not None else None
-        out = self._stabilize_video("rsdsfm_stabilize_video_blended_dev",
-                                    (C.byref(fp), arr(d_sources), _p(counts), C.byref(cp), _window4(window_in), arr(d_crop), arr(d_crop_masks), arr(d_crop_sources),
-                                     window, _p(crop_counts), C.byref(bp), arr(d_blend), arr(d_blend_masks), arr(d_blend_sources), _p(gains), _p(blend_counts)),
-                                    **args)
+        with _occlusion_search_for(self, occlusion_search, occlusion):
+            out = self._stabilize_video("rsdsfm_stabilize_video_blended_dev",
+                                        (C.byref(fp), arr(d_sources), _p(counts), C.byref(cp), _window4(window_in), arr(d_crop), arr(d_crop_masks), arr(d_crop_sources),
+                                         window, _p(crop_counts), C.byref(bp), arr(d_blend), arr(d_blend_masks), arr(d_blend_sources), _p(gains), _p(blend_counts)),
+                                        **args)
         out["window"] = tuple(int(x) for x in window)
         if want_counts:
             out["counts"] = counts[:n]
@@ -2387,7 +2494,7 @@ class _StabilizeInpaintMixin:
                                       want_valid=True, sigma=None, radius=0, translation=True, fuse_tol=None, d_masks=None, seeds=None, flow_params=None, a1=None,
                                       a2=None, link_tol=None, min_links=None, radix_bits=None, mode=BACKPROJECT_RS, q5_mode=Q5_COMPAT, iterations=0, trials=50,
                                       tol=0.05, use_acceleration_mode=False, use_refinement=True, depth_mode=DEPTH_CERES_LM, k_sign_mode=K_COMPAT,
-                                      flow_threshold=1e-10, flow_index_mode=FLOW_COMPAT_RANK, use_global_shutter_mode=False, last_frame=False, occlusion=False, occlusion_tol=None):
+                                      flow_threshold=1e-10, flow_index_mode=FLOW_COMPAT_RANK, use_global_shutter_mode=False, last_frame=False, occlusion=False, occlusion_tol=None, occlusion_search=False):
         """the stabilised clip, cropped, zoomed, blended and inpainted, in ONE call (rsdsfm_stabilize_video_inpainted_dev):
         stabilize_video_blended_dev with these arguments, then for every frame d_blend copied to d_inpaint (and d_blend_sources to
         d_inpaint_sources when passed; F - 1 device buffers each) and inpaint_frame_dev on the copy with the frame's blend mask.  Returns
@@ -2395,7 +2502,9 @@ class _StabilizeInpaintMixin:
         call then waits for the passes).
         last_frame=True (see stabilize_video_dev): the clip's last frame too; every per-frame list and array then has F entries.
         occlusion=True: the neighbour candidates go through the occlusion test (stabilize_visible_frame_dev; occlusion_tol: its tolerance as a
-        fraction of the depth, None: the default) -- a rejected pixel shows up under a later offset or under none."""
+        fraction of the depth, None: the default) -- a rejected pixel shows up under a later offset or under none.
+        occlusion_search=True (needs occlusion): set_occlusion_search(1) for this call -- a rejected pixel whose visible pre-image is found is
+        recovered (stabilize_search_frame_dev) and counts under its offset; the knob is put back afterwards."""
         n = len(d_frames) - 1 + (1 if last_frame else 0)  # rendered frames
         _need_all(n, d_sources=d_sources, d_crop=d_crop, d_crop_masks=d_crop_masks, d_crop_sources=d_crop_sources, d_blend=d_blend, d_blend_masks=d_blend_masks, d_blend_sources=d_blend_sources, d_inpaint=d_inpaint, d_inpaint_sources=d_inpaint_sources)
         fp = _stabilize_fill_params(fill_radius, occlusion, occlusion_tol)
@@ -2413,12 +2522,13 @@ class _StabilizeInpaintMixin:
                "want_counts", "d_crop", "d_crop_masks", "d_crop_sources", "window_in", "max_empty", "margin", "want_crop_counts", "d_blend", "d_blend_masks",
                "d_blend_sources", "blend_feather", "blend_gain", "blend_min_overlap", "want_gains", "want_blend_counts", "d_inpaint", "d_inpaint_sources",
                "want_inpaint_counts")
-        args = {k_: v_ for k_, v_ in locals().items() if k_ not in own and k_ not in ("own", "occlusion", "occlusion_tol")}
+        args = {k_: v_ for k_, v_ in locals().items() if k_ not in own and k_ not in ("own", "occlusion", "occlusion_tol", "occlusion_search")}
         arr = lambda a: _ptr_array(a) if a is not None else None
-        out = self._stabilize_video("rsdsfm_stabilize_video_inpainted_dev",
-                                    (C.byref(fp), arr(d_sources), _p(counts), C.byref(cp), _window4(window_in), arr(d_crop), arr(d_crop_masks), arr(d_crop_sources),
-                                     window, _p(crop_counts), C.byref(bp), arr(d_blend), arr(d_blend_masks), arr(d_blend_sources), _p(gains), _p(blend_counts),
-                                     arr(d_inpaint), arr(d_inpaint_sources), _p(inpaint_counts)), **args)
+        with _occlusion_search_for(self, occlusion_search, occlusion):
+            out = self._stabilize_video("rsdsfm_stabilize_video_inpainted_dev",
+                                        (C.byref(fp), arr(d_sources), _p(counts), C.byref(cp), _window4(window_in), arr(d_crop), arr(d_crop_masks), arr(d_crop_sources),
+                                         window, _p(crop_counts), C.byref(bp), arr(d_blend), arr(d_blend_masks), arr(d_blend_sources), _p(gains), _p(blend_counts),
+                                         arr(d_inpaint), arr(d_inpaint_sources), _p(inpaint_counts)), **args)
         out["window"] = tuple(int(x) for x in window)
         if want_counts:
             out["counts"] = counts[:n]

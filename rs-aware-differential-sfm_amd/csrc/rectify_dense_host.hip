@@ -17,6 +17,8 @@ static void dense_ws_free(DenseWs* w) {
     if (w->d_inpaint) (void)hipFree(w->d_inpaint);
     if (w->d_visible) (void)hipFree(w->d_visible);
     w->d_visible = nullptr;
+    if (w->d_search) (void)hipFree(w->d_search);
+    w->d_search = nullptr;
     w->d_pyr = nullptr;
     w->d_disp = nullptr;
     w->d_mask = nullptr;

@@ -9,6 +9,7 @@
 #include "last_frame.hpp"
 #include "sequence_host.hpp"
 #include "stabilize_blend.hpp"
+#include "stabilize_search.hpp"
 #include "stabilize_visible.hpp"
 
 namespace rsdsfm {
@@ -146,6 +147,7 @@ int rsdsfm_stabilize_video_blended_dev(rsdsfm_ctx* ctx, const uint8_t* const* d_
     if (rc != RSDSFM_OK) return rc;
     const int radius = fill_params_or_null ? fill_params_or_null->radius : kBlendFillRadiusDefault;  // 0 .. 16: the inner call checked it
     const bool occ = visible_asked(fill_params_or_null);  // every layer is rendered through the occlusion test (the inner call checked the words)
+    const bool srch = search_asked(c, fill_params_or_null);  // ... and through the search for the visible pre-image
     const int offs = 2 * radius;
     const size_t plane = (size_t)rows * (size_t)cols, P = blend_plane_bytes(rows, cols);
     const bool have = window_out[2] >= 1, host = gains_or_null || blend_counts_or_null;
@@ -194,7 +196,10 @@ int rsdsfm_stabilize_video_blended_dev(rsdsfm_ctx* ctx, const uint8_t* const* d_
                 break;
             }
             const double* nmap = d_fused_maps_or_null ? d_fused_maps_or_null[n] : d_depth_maps[n];
-            rc = occ ? rsdsfm_stabilize_visible_frame_dev(ctx, d_frames[n], channels, nmap, d_R[n], d_t[n], fx, fy, cx, cy, rows, cols, mode, q5_mode, iterations,
+            rc = srch ? rsdsfm_stabilize_search_frame_dev(ctx, d_frames[n], channels, nmap, d_R[n], d_t[n], fx, fy, cx, cy, rows, cols, mode, q5_mode, iterations,
+                                                          nM + 9 * (size_t)k, nm + 3 * (size_t)k, ids[k], window_out, d_limage, d_lmask, nullptr,
+                                                          fill_params_or_null->occlusion_tol_q16, nullptr)
+                 : occ ? rsdsfm_stabilize_visible_frame_dev(ctx, d_frames[n], channels, nmap, d_R[n], d_t[n], fx, fy, cx, cy, rows, cols, mode, q5_mode, iterations,
                                                           nM + 9 * (size_t)k, nm + 3 * (size_t)k, ids[k], window_out, d_limage, d_lmask, nullptr,
                                                           fill_params_or_null->occlusion_tol_q16, nullptr)
                      : rsdsfm_stabilize_window_frame_dev(ctx, d_frames[n], channels, nmap, d_R[n], d_t[n], fx, fy, cx, cy, rows, cols, mode, q5_mode, iterations,

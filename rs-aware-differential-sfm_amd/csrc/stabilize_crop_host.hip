@@ -10,6 +10,7 @@
 #include "last_frame.hpp"
 #include "sequence_host.hpp"
 #include "stabilize_crop.hpp"
+#include "stabilize_search.hpp"
 #include "stabilize_visible.hpp"
 
 namespace rsdsfm {
@@ -168,7 +169,8 @@ int rsdsfm_stabilize_video_cropped_dev(rsdsfm_ctx* ctx, const uint8_t* const* d_
         return fail(c, RSDSFM_ERR_INVALID,
                     "rsdsfm_stabilize_fill_params: radius in [0, 16], occlusion 0 or 1, occlusion_tol_q16 in [0, 65536], struct_bytes 0 or sizeof (use rsdsfm_stabilize_fill_params_init)");
     const bool occ = visible_asked(fill_params_or_null);  // the neighbours go through the occlusion test: [taken, rejected] per frame call, the first is the count
-    const int cw = occ ? 2 : 1;
+    const bool srch = search_asked(c, fill_params_or_null);  // ... and through the search for the visible pre-image: [taken, rejected, recovered]
+    const int cw = candidate_counters(occ, srch);
     const int radius = fill_params_or_null ? fill_params_or_null->radius : kCropFillRadiusDefault;  // 0 here: no fill at all
     const rsdsfm_stabilize_crop_params cp = crop_params_or_null ? *crop_params_or_null : crop_defaults();
     if (!crop_params_ok(cp, rows, cols))
@@ -246,7 +248,10 @@ int rsdsfm_stabilize_video_cropped_dev(rsdsfm_ctx* ctx, const uint8_t* const* d_
             const int n = frames[k];
             const double* nmap = d_fused_maps_or_null ? d_fused_maps_or_null[n] : d_depth_maps[n];
             int64_t* cnt = d_cnt ? d_cnt + ((size_t)p * slots + (ids[k] - 1)) * cw : nullptr;
-            rc = occ ? rsdsfm_stabilize_visible_frame_dev(ctx, d_frames[n], channels, nmap, d_R[n], d_t[n], fx, fy, cx, cy, rows, cols, mode, q5_mode, iterations,
+            rc = srch ? rsdsfm_stabilize_search_frame_dev(ctx, d_frames[n], channels, nmap, d_R[n], d_t[n], fx, fy, cx, cy, rows, cols, mode, q5_mode, iterations,
+                                                          nM + 9 * (size_t)k, nm + 3 * (size_t)k, ids[k], window_out, d_crop_images[p], d_crop_masks[p], src,
+                                                          fill_params_or_null->occlusion_tol_q16, cnt)
+                 : occ ? rsdsfm_stabilize_visible_frame_dev(ctx, d_frames[n], channels, nmap, d_R[n], d_t[n], fx, fy, cx, cy, rows, cols, mode, q5_mode, iterations,
                                                           nM + 9 * (size_t)k, nm + 3 * (size_t)k, ids[k], window_out, d_crop_images[p], d_crop_masks[p], src,
                                                           fill_params_or_null->occlusion_tol_q16, cnt)
                      : rsdsfm_stabilize_window_frame_dev(ctx, d_frames[n], channels, nmap, d_R[n], d_t[n], fx, fy, cx, cy, rows, cols, mode, q5_mode, iterations,
@@ -271,7 +276,7 @@ int rsdsfm_stabilize_video_cropped_dev(rsdsfm_ctx* ctx, const uint8_t* const* d_
             for (int p = 0; p < np; ++p) {
                 int64_t* row = crop_counts_or_null + (size_t)p * (1 + slots);
                 int64_t sum = 0;
-                for (int k = 0; k < slots; ++k) sum += (row[1 + k] = taken[((size_t)p * slots + k) * cw]);
+                for (int k = 0; k < slots; ++k) sum += (row[1 + k] = candidate_count(&taken[((size_t)p * slots + k) * cw], srch));
                 row[0] = (int64_t)plane - sum;
             }
     }

@@ -11,6 +11,7 @@
 #include "last_frame.hpp"
 #include "sequence_host.hpp"
 #include "stabilize_fill.hpp"
+#include "stabilize_search.hpp"
 #include "stabilize_visible.hpp"
 
 namespace rsdsfm {
@@ -129,7 +130,8 @@ int rsdsfm_stabilize_video_filled_dev(rsdsfm_ctx* ctx, const uint8_t* const* d_f
         return fail(c, RSDSFM_ERR_INVALID, "rsdsfm_stabilize_fill_params: radius in [0, 16], occlusion 0 or 1, occlusion_tol_q16 in [0, 65536], struct_bytes 0 or sizeof (use rsdsfm_stabilize_fill_params_init)");
     const int radius = fp.radius ? fp.radius : kFillRadiusDefault;
     const bool occ = visible_asked(&fp);  // the candidates go through the occlusion test: [taken, rejected] per candidate, the first is the count
-    const int cw = occ ? 2 : 1;
+    const bool srch = search_asked(c, &fp);  // ... and through the search for the visible pre-image: [taken, rejected, recovered]
+    const int cw = candidate_counters(occ, srch);
     const int32_t full[4] = {0, 0, rows, cols};
     if (!all_set(d_masks_out, np)) return fail(c, RSDSFM_ERR_INVALID, "border fill: d_masks_out is required -- a candidate is taken where the mask is 0");
     if (d_sources_or_null) {
@@ -173,7 +175,10 @@ int rsdsfm_stabilize_video_filled_dev(rsdsfm_ctx* ctx, const uint8_t* const* d_f
             const double* map = d_fused_maps_or_null ? d_fused_maps_or_null[n] : d_depth_maps[n];
             uint8_t* src = d_sources_or_null ? d_sources_or_null[p] : nullptr;
             int64_t* cnt = d_cnt ? d_cnt + ((size_t)p * slots + (ids[k] - 2)) * cw : nullptr;
-            rc = occ ? rsdsfm_stabilize_visible_frame_dev(ctx, d_frames[n], channels, map, d_R[n], d_t[n], fx, fy, cx, cy, rows, cols, mode, q5_mode, iterations,
+            rc = srch ? rsdsfm_stabilize_search_frame_dev(ctx, d_frames[n], channels, map, d_R[n], d_t[n], fx, fy, cx, cy, rows, cols, mode, q5_mode, iterations,
+                                                          nM + 9 * (size_t)k, nm + 3 * (size_t)k, ids[k], full, d_stab_images[p], d_masks_out[p], src,
+                                                          fp.occlusion_tol_q16, cnt)
+                 : occ ? rsdsfm_stabilize_visible_frame_dev(ctx, d_frames[n], channels, map, d_R[n], d_t[n], fx, fy, cx, cy, rows, cols, mode, q5_mode, iterations,
                                                           nM + 9 * (size_t)k, nm + 3 * (size_t)k, ids[k], full, d_stab_images[p], d_masks_out[p], src,
                                                           fp.occlusion_tol_q16, cnt)
                      : rsdsfm_stabilize_fill_frame_dev(ctx, d_frames[n], channels, map, d_R[n], d_t[n], fx, fy, cx, cy, rows, cols, mode, q5_mode, iterations,
@@ -191,7 +196,7 @@ int rsdsfm_stabilize_video_filled_dev(rsdsfm_ctx* ctx, const uint8_t* const* d_f
                 int64_t* row = counts_or_null + (size_t)p * (2 + slots);
                 int64_t rest = valid[p];
                 row[1] = valid[p];
-                for (int k = 0; k < slots; ++k) rest += (row[2 + k] = filled[((size_t)p * slots + k) * cw]);
+                for (int k = 0; k < slots; ++k) rest += (row[2 + k] = candidate_count(&filled[((size_t)p * slots + k) * cw], srch));
                 row[0] = (int64_t)plane - rest;
             }
     }

@@ -6,6 +6,9 @@
 // at the call, not where they are used, and the existing kernel then spills 10 SGPRs (96 -> 106, measured with hipcc -S) -- its code and its
 // time would not be the parent's.  The including kernel declares, under these names: depth_cm, lv1, h1, w1, R, t, fx, fy, cx, cy, fyp, rows,
 // cols, mode, vp, disp, filled_cm and, VISIBLE, zv (float*) and zbuf (unsigned*).
+// RSDSFM_STABILIZE_MAP_VISIBLE 2 (stabilize_search_map_kernel, stabilize_search_kernels.hip; include/rsdsfm_stabilize_search.h): the splat goes
+// into kbuf (unsigned long long*) instead of zbuf, as the 64-bit key bits(zv) << 32 | (y cols + x) -- the nearest depth and, on equal depth,
+// the smallest source index.  With 0 and 1 the preprocessed text is what it was, token for token.
 //
 // A 64 x 16 tile of the column-major depth map staged through LDS, the last push step fused, a wave per scanline segment with the scanline's
 // pose on the scalar path, the optional filled-depth write-back.  VISIBLE: zv[y cols + x] = (float)pv[2] where that is a positive finite depth,
@@ -64,8 +67,13 @@
                 zv[(int64_t)y * cols + x] = zd;
                 if (zd > 0.0f && gx >= -0.5 && gx < (double)cols - 0.5 && gy >= -0.5 && gy < (double)rows - 0.5) {  // false for NaN
                     const int ix = min((int)(gx + 0.5), cols - 1), iy = min((int)(gy + 0.5), rows - 1);        // gx + 0.5 >= 0: inside the plane
+#if RSDSFM_STABILIZE_MAP_VISIBLE == 2
+                    unsigned long long* cell = kbuf + ((int64_t)iy * cols + ix);
+                    const unsigned long long bits = ((unsigned long long)__float_as_uint(zd) << 32) | (unsigned)(y * cols + x);  // rows cols <= 2^28
+#else
                     unsigned* cell = zbuf + ((int64_t)iy * cols + ix);
                     const unsigned bits = __float_as_uint(zd);
+#endif
                     if (*cell > bits) atomicMin(cell, bits);
                 }
             }

@@ -208,7 +208,7 @@ def evaluate_real_sequence(solver, frames, camera="galaxy", gamma=0.95, out_dir=
                            use_refinement=True, use_global_shutter_mode=False, flow_threshold=1e-10, flow_index_mode=0, device=0, flow_params=None, dense=False,
                            check_flow=False, trajectory=False, link_tol=None, min_links=None, fuse=False, fuse_tol=None, stabilize=False, smooth_sigma=None,
                            smooth_translation=True, fill=0, crop=False, crop_margin=None, crop_max_empty=0, blend=False, blend_feather=None,
-                           blend_gain=True, inpaint=False, last_frame=False, occlusion=False, occlusion_tol=None):
+                           blend_gain=True, inpaint=False, last_frame=False, occlusion=False, occlusion_tol=None, occlusion_search=False):
     """evaluate_real_run's real-world branch (main.cc:341-361, 364-531) for a clip: `frames` is <prefix>frame1.png ... frameN.png (the
     prefix, or a list of paths), or the frames themselves (an (N, rows, cols[, 3]) uint8 array or a list of arrays; 2-D frames are gray).
     By default ONE call does the clip (Solver.rectify_video_dev): the batched DeepFlow of every consecutive pair, the pipelined solve of every pair p
@@ -272,7 +272,14 @@ def evaluate_real_sequence(solver, frames, camera="galaxy", gamma=0.95, out_dir=
     source is not the nearest surface that lands there -- a fold of the neighbour's map, a parallax ghost -- is rejected and left to the next
     candidate or the inpainter.  occlusion_tol: the test's tolerance as a fraction of the depth in (0, 1] (None: the default, about 0.05).  The
     outputs keep their keys, shapes and files; a rejected pixel shows up under a later offset or under none.  Without occlusion every output
-    is what it was."""
+    is what it was.
+    occlusion_search=True (needs occlusion=True: ValueError otherwise): those candidates are rendered by Solver.stabilize_search_frame_dev instead
+    (tests/stabilize_search_spec_numpy.py): a pixel the test rejects is looked for again from the source pixel that landed nearest the camera on
+    its cell and, where that ends on the visible surface, recovered; it counts under its offset.  The returned dict then also has fill_recovered
+    and, with crop=True, crop_recovered ((frames,) int64: the recovered pixels per frame, summed over its candidates, from the calls' own
+    counters); out_dir receives occlusion_search.csv (frame and the sums).  Without occlusion_search every output is what it was."""
+    if occlusion_search and not occlusion:
+        raise ValueError("occlusion_search needs occlusion=True: the search runs where the occlusion test rejects")
     if occlusion and not (stabilize and fill >= 1):
         raise ValueError("occlusion needs stabilize=True and fill >= 1: it tests the neighbour candidates of the stabilised frames")
     if last_frame and not stabilize:
@@ -424,7 +431,13 @@ def evaluate_real_sequence(solver, frames, camera="galaxy", gamma=0.95, out_dir=
                     from . import _occlusion_tol_q16
 
                     occ_q16 = 0 if occlusion_tol is None else _occlusion_tol_q16(occlusion_tol)
-                    d_occ = torch.zeros((nst, 2 + 2 * fill, 2), dtype=torch.int64, device=dev)  # [taken, rejected] of the call in flight
+                    # [taken, rejected] of the call in flight, or with the search [taken, rejected, recovered]
+                    d_occ = torch.zeros((nst, 2 + 2 * fill, 3 if occlusion_search else 2), dtype=torch.int64, device=dev)
+
+                def occ_counts():
+                    """-> (what every neighbour put into its frame (frames, 2 fill), the recovered pixels per frame or None)"""
+                    got = d_occ.cpu().numpy()[:, 2:]
+                    return (got[:, :, 0] + got[:, :, 2], got[:, :, 2].sum(axis=1)) if occlusion_search else (got[:, :, 0], None)
 
                 def neighbour_dev(n, sid, nM, nm, window, d_image, d_mask, d_source, d_count, p):
                     """one neighbour candidate: the window call (the fill call without a window), or with occlusion the visible call, whose first
@@ -432,8 +445,8 @@ def evaluate_real_sequence(solver, frames, camera="galaxy", gamma=0.95, out_dir=
                     head = (d_imgs[n].data_ptr(), channels, d_src[n].data_ptr(), d_Rs[n].data_ptr(), d_ts[n].data_ptr(), K, rows, cols, nM, nm, int(sid))
                     tail = (d_image.data_ptr(), d_mask.data_ptr(), None if d_source is None else d_source.data_ptr())
                     if occlusion:
-                        solver.stabilize_visible_frame_dev(*head, window or (0, 0, rows, cols), *tail, None if d_count is None else d_occ[p, int(sid)].data_ptr(),
-                                                           tol_q16=occ_q16, mode=mode)
+                        call = solver.stabilize_search_frame_dev if occlusion_search else solver.stabilize_visible_frame_dev
+                        call(*head, window or (0, 0, rows, cols), *tail, None if d_count is None else d_occ[p, int(sid)].data_ptr(), tol_q16=occ_q16, mode=mode)
                     elif window is None:
                         solver.stabilize_fill_frame_dev(*head, *tail, None if d_count is None else d_count.data_ptr(), mode=mode)
                     else:
@@ -452,7 +465,9 @@ def evaluate_real_sequence(solver, frames, camera="galaxy", gamma=0.95, out_dir=
                     solver.synchronize()
                     counts = d_fcnt.cpu().numpy()
                     if occlusion:
-                        counts[:, 2:] = d_occ.cpu().numpy()[:, 2:, 0]
+                        counts[:, 2:], recovered = occ_counts()
+                        if occlusion_search:
+                            traj.update(fill_recovered=recovered)
                     counts[:, 0] = rows * cols - counts[:, 1:].sum(axis=1)
                     traj.update(stab_filled=[t.cpu().numpy() for t in d_fills], stab_sources=[t.cpu().numpy() for t in d_sources], fill_counts=counts)
                 if crop:
@@ -475,7 +490,9 @@ def evaluate_real_sequence(solver, frames, camera="galaxy", gamma=0.95, out_dir=
                     solver.synchronize()
                     counts = d_ccnt.cpu().numpy()
                     if occlusion and window[2]:
-                        counts[:, 2:] = d_occ.cpu().numpy()[:, 2:, 0]
+                        counts[:, 2:], recovered = occ_counts()
+                    if occlusion_search:
+                        traj.update(crop_recovered=recovered if window[2] else np.zeros(nst, dtype=np.int64))
                     counts[:, 0] = rows * cols - counts[:, 1:].sum(axis=1)
                     traj.update(stab_cropped=[t.cpu().numpy() for t in d_crops], crop_window=window, crop_counts=counts)
                 if blend:
@@ -593,6 +610,11 @@ def evaluate_real_sequence(solver, frames, camera="galaxy", gamma=0.95, out_dir=
                 formats.write_png(os.path.join(out_dir, "stabilized_cropped_%d.png" % p), traj["stab_cropped"][p])
                 rows_.append(",".join([str(p)] + [str(int(x)) for x in traj["crop_counts"][p]]))
             with open(os.path.join(out_dir, "crop.csv"), "w") as fh:
+                fh.write("\n".join(rows_) + "\n")
+        if occlusion_search:
+            names = ["fill_recovered"] + (["crop_recovered"] if crop else [])
+            rows_ = ["pair," + ",".join(names)] + [",".join([str(p)] + [str(int(traj[k_][p])) for k_ in names]) for p in range(nst)]
+            with open(os.path.join(out_dir, "occlusion_search.csv"), "w") as fh:
                 fh.write("\n".join(rows_) + "\n")
         if blend:
             offs = ["%s%d" % (sg, j) for j in range(1, fill + 1) for sg in ("prev", "next")]
