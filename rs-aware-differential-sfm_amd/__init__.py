@@ -135,10 +135,10 @@ class RansacOut(C.Structure):
 
 
 def declared_symbols():
-    """Names of every function include/rsdsfm.h declares (used by the CPU symbol-export test)."""
+    """Names of every function include/rsdsfm.h and include/rsdsfm_retime.h declare (used by the CPU symbol-export test)."""
     import re
 
-    txt = open(HEADER_PATH).read()
+    txt = open(HEADER_PATH).read() + open(os.path.join(os.path.dirname(HEADER_PATH), "rsdsfm_retime.h")).read()
     txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
     return sorted(set(re.findall(r"\b(rsdsfm_[a-z0-9_]+)\s*\(", txt)))
 
@@ -2625,6 +2625,207 @@ class _LastFrameMixin:
 
 
 for _name, _fn in list(vars(_LastFrameMixin).items()):
+    if not _name.startswith("__"):
+        setattr(Solver, _name, _fn)
+
+
+# ---------------------------------------------------------------------------------------------------
+# the retimer: a frame at any instant along the camera path, from the two input frames next to it in time (include/rsdsfm_retime.h)
+# ---------------------------------------------------------------------------------------------------
+RETIME_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "rsdsfm_retime.h")
+RETIME_NONE, RETIME_FROM_A, RETIME_FROM_B, RETIME_DISSOLVED, RETIME_CONFLICT_A, RETIME_CONFLICT_B = range(6)
+
+
+class RetimeParams(C.Structure):
+    _fields_ = [("threshold", C.c_int32), ("occlusion", C.c_int32), ("occlusion_tol_q16", C.c_int32), ("struct_bytes", C.c_int32), ("reserved", C.c_int32 * 4)]
+
+
+def retime_declared_symbols():
+    """Names of every function include/rsdsfm_retime.h declares"""
+    import re
+
+    txt = open(RETIME_HEADER_PATH).read()
+    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
+    return sorted(set(re.findall(r"\b(rsdsfm_[a-z0-9_]+)\s*\(", txt)))
+
+
+def retime_default_params():
+    """the retimer's defaults as a dict: threshold = 24, occlusion = 0, occlusion_tol_q16 = 0 (rsdsfm_retime_params_init)"""
+    p = RetimeParams()
+    if load_library().rsdsfm_retime_params_init(C.byref(p)) != OK:
+        raise RsdsfmError("rsdsfm_retime_params_init failed")
+    return dict(threshold=p.threshold, occlusion=p.occlusion, occlusion_tol_q16=p.occlusion_tol_q16)
+
+
+def _retime_params(threshold, occlusion, occlusion_tol_q16):
+    """a RetimeParams with the given values over the defaults (threshold None: the default)"""
+    p = RetimeParams()
+    if load_library().rsdsfm_retime_params_init(C.byref(p)) != OK:
+        raise RsdsfmError("rsdsfm_retime_params_init failed")
+    if threshold is not None:
+        p.threshold = int(threshold)
+    p.occlusion, p.occlusion_tol_q16 = int(occlusion), int(occlusion_tol_q16)
+    return p
+
+
+def path_at(A_path, c_path, t):
+    """the pose at time t on a path (rsdsfm_path_at; host arithmetic, no GPU; tests/retime_spec_numpy.py): A_path (F, 3, 3), c_path (F, 3),
+    t in [0, F - 1] -> (A_t (3, 3), c_t (3,)).  An integer t returns the entry's bytes; between two poses the rotation moves along the
+    geodesic and the centre along the segment."""
+    a, cc = _f64(A_path).reshape(-1, 9), _f64(c_path).reshape(-1, 3)
+    if cc.shape[0] != a.shape[0]:
+        raise ValueError("every pose needs a rotation and a centre")
+    A_t, c_t = np.empty(9), np.empty(3)
+    rc = load_library().rsdsfm_path_at(_p(a), _p(cc), C.c_int32(a.shape[0]), C.c_double(t), _p(A_t), _p(c_t))
+    if rc != OK:
+        raise RsdsfmError("rsdsfm_path_at failed (%d): at least one pose, t finite and in [0, nposes - 1]" % rc)
+    return A_t.reshape(3, 3), c_t
+
+
+def retime_poses(A, c, A_path, c_path, scales, t, nsources=None):
+    """the sources of the frame at time t and their poses (rsdsfm_retime_poses; host): A, c the chain's, A_path, c_path the path to ride,
+    nsources the frames that have a depth map (None: len(scales)) -> (sources (n0,) or (n0, n0 + 1), weight_q16, M (nsrc, 3, 3), m (nsrc, 3),
+    A_t (3, 3), c_t (3,))"""
+    a, cc, ap, cp = _f64(A).reshape(-1, 9), _f64(c).reshape(-1, 3), _f64(A_path).reshape(-1, 9), _f64(c_path).reshape(-1, 3)
+    sc = _f64(scales).reshape(-1)
+    ns = sc.shape[0] if nsources is None else int(nsources)
+    if min(a.shape[0], cc.shape[0], ap.shape[0], cp.shape[0], sc.shape[0]) < ns:
+        raise ValueError("every source needs a pose on both paths and a scale")
+    src, nsrc, w = (C.c_int32 * 2)(), C.c_int32(), C.c_int32()
+    M, m, A_t, c_t = np.empty((2, 9)), np.empty((2, 3)), np.empty(9), np.empty(3)
+    rc = load_library().rsdsfm_retime_poses(_p(a), _p(cc), _p(ap), _p(cp), _p(sc), C.c_int32(ns), C.c_double(t), src, C.byref(nsrc), C.byref(w), _p(M), _p(m), _p(A_t),
+                                            _p(c_t))
+    if rc != OK:
+        raise RsdsfmError("rsdsfm_retime_poses failed (%d): t finite and in [0, nsources - 1], the sources' scales finite and positive" % rc)
+    n = nsrc.value
+    return tuple(int(x) for x in src[:n]), int(w.value), M[:n].reshape(n, 3, 3), m[:n], A_t.reshape(3, 3), c_t
+
+
+def retime_times(nsources, factor):
+    """the instants of a clip slowed down by an integer `factor`: i / factor for i = 0 .. (nsources - 1) factor"""
+    nsources, factor = int(nsources), int(factor)
+    if nsources < 1 or factor < 1:
+        raise ValueError("nsources >= 1 and factor >= 1")
+    return np.arange((nsources - 1) * factor + 1, dtype=np.float64) / np.float64(factor)
+
+
+def retime_launches(rows, cols, nsrc=2):
+    """kernel launches of one retime_frame_dev call: nsrc stabilize_window_launches + 1 (rsdsfm_retime_launches; host only)"""
+    n = load_library().rsdsfm_retime_launches(C.c_int32(rows), C.c_int32(cols), C.c_int32(nsrc))
+    if n < 0:
+        raise RsdsfmError("rsdsfm_retime_launches failed (%d): rows and cols must be in [2, 16384], nsrc 1 or 2" % n)
+    return n
+
+
+def retime_merge_launches():
+    """kernel launches of one retime_merge_dev call: 1 (rsdsfm_retime_merge_launches; host only)"""
+    return int(load_library().rsdsfm_retime_merge_launches())
+
+
+class _RetimeMixin:
+    def retime_merge_dev(self, d_image_a, d_mask_a, d_image_b, d_mask_b, channels, rows, cols, weight_q16, d_image, d_mask, d_source=None, d_counts5=None,
+                         threshold=24):
+        """two layers merged by how near each is in time (rsdsfm_retime_merge_dev; tests/retime_spec_numpy.py): where only one layer is set its
+        bytes, where both are a cross-dissolve with weight_q16 / 65536 on b, or the nearer layer's bytes where they differ by more than
+        `threshold`.  d_image_b = d_mask_b = None: b absent (weight 0).  d_source receives the RETIME_* byte per pixel, d_counts5 (five device
+        int64) [none, a only, b only, dissolved, conflict].  Every output byte is written.  Enqueued on the context's stream."""
+        self._check(self.lib.rsdsfm_retime_merge_dev(self._ctx, _dp(d_image_a), _dp(d_mask_a), _np0(d_image_b), _np0(d_mask_b), C.c_int32(channels), C.c_int32(rows),
+                                                     C.c_int32(cols), C.c_int32(weight_q16), C.c_int32(threshold), _dp(d_image), _dp(d_mask), _np0(d_source),
+                                                     _np0(d_counts5)), "rsdsfm_retime_merge_dev")
+
+    def retime_merge(self, image_a, mask_a, image_b=None, mask_b=None, weight_q16=0, threshold=24, device=0):
+        """host convenience around retime_merge_dev -> (image, mask, source (rows, cols) uint8, counts (5,) int64)"""
+        import torch
+
+        ia, ma = np.ascontiguousarray(image_a, dtype=np.uint8), np.ascontiguousarray(mask_a, dtype=np.uint8)
+        rows, cols = ma.shape
+        dev = torch.device("cuda", device)
+        with torch.cuda.device(dev):
+            up = lambda a: None if a is None else torch.from_numpy(np.ascontiguousarray(a, dtype=np.uint8)).to(dev)
+            d_ia, d_ma, d_ib, d_mb = up(ia), up(ma), up(image_b), up(mask_b)
+            d_out, d_mask, d_src = torch.empty_like(d_ia), torch.empty_like(d_ma), torch.empty_like(d_ma)
+            d_cnt = torch.zeros(5, dtype=torch.int64, device=dev)
+            torch.cuda.synchronize()
+            ptr = lambda x: None if x is None else x.data_ptr()
+            self.retime_merge_dev(d_ia.data_ptr(), d_ma.data_ptr(), ptr(d_ib), ptr(d_mb), 1 if ia.ndim == 2 else ia.shape[2], rows, cols, int(weight_q16),
+                                  d_out.data_ptr(), d_mask.data_ptr(), d_src.data_ptr(), d_cnt.data_ptr(), threshold=threshold)
+            self.synchronize()
+            return d_out.cpu().numpy(), d_mask.cpu().numpy(), d_src.cpu().numpy(), d_cnt.cpu().numpy()
+
+    def retime_frame_dev(self, d_images, channels, d_depth_maps, d_Rs, d_ts, K, rows, cols, M, m, weight_q16, d_image, d_mask, d_source=None, d_counts5=None,
+                         window=None, threshold=None, occlusion=False, occlusion_tol_q16=0, mode=BACKPROJECT_RS, q5_mode=Q5_COMPAT, iterations=0, params=None):
+        """one frame at one instant (rsdsfm_retime_frame_dev): d_images, d_depth_maps, d_Rs, d_ts are lists of one or two device pointers (the
+        sources of retime_poses), M (nsrc, 3, 3), m (nsrc, 3) and weight_q16 its results.  Every source is rendered alone onto a layer of the
+        context (stabilize_window_frame_dev; occlusion=True: stabilize_visible_frame_dev, or stabilize_search_frame_dev with
+        set_occlusion_search(1)) and the layers are merged (retime_merge_dev) into d_image, d_mask, d_source, d_counts5.  window None: the full
+        frame.  params: a RetimeParams passed as it is, instead of threshold / occlusion / occlusion_tol_q16.  Enqueued on the context's stream."""
+        d = C.c_double
+        nsrc = len(d_images)
+        Mh = None if M is None else _f64(M).reshape(-1)
+        mh = None if m is None else _f64(m).reshape(-1)
+        if (Mh is not None and Mh.size < 9 * min(nsrc, 2)) or (mh is not None and mh.size < 3 * min(nsrc, 2)) or min(len(d_depth_maps), len(d_Rs), len(d_ts)) < min(nsrc, 2):
+            raise RsdsfmError("retime_frame_dev: every source needs an image, a depth map, a pose table and a pose (M, m)")
+        p = params if params is not None else _retime_params(threshold, occlusion, occlusion_tol_q16)
+        arr = lambda a: _ptr_array(list(a)[:2]) if len(a) else None
+        self._check(self.lib.rsdsfm_retime_frame_dev(self._ctx, arr(d_images), C.c_int32(channels), arr(d_depth_maps), arr(d_Rs), arr(d_ts), d(K[0]), d(K[1]), d(K[2]),
+                                                     d(K[3]), C.c_int32(rows), C.c_int32(cols), int(mode), int(q5_mode), C.c_int32(iterations), C.c_int32(nsrc), _p(Mh),
+                                                     _p(mh), C.c_int32(weight_q16), C.byref(p), _window4(window), _dp(d_image), _dp(d_mask), _np0(d_source),
+                                                     _np0(d_counts5)), "rsdsfm_retime_frame_dev")
+
+    def retime(self, images, depth_maps, Rs, ts, K, M, m, weight_q16, window=None, threshold=None, occlusion=False, occlusion_tol_q16=0, mode=BACKPROJECT_RS,
+               q5_mode=Q5_COMPAT, iterations=0, device=0):
+        """host convenience around retime_frame_dev: images, depth_maps (rows, cols), Rs, ts: lists of one or two sources' host arrays
+        -> (image, mask, source (rows, cols) uint8, counts (5,) int64)"""
+        import torch
+
+        imgs = [np.ascontiguousarray(i, dtype=np.uint8) for i in images]
+        rows, cols = imgs[0].shape[:2]
+        dev = torch.device("cuda", device)
+        with torch.cuda.device(dev):
+            up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+            d_i = [up(i) for i in imgs]
+            d_dm = [up(np.asarray(z, dtype=np.float64).T) for z in depth_maps]
+            d_R, d_t = [up(_f64(np.asarray(R).reshape(rows, 9))) for R in Rs], [up(_f64(t)) for t in ts]
+            d_out, d_mask = torch.empty_like(d_i[0]), torch.empty((rows, cols), dtype=torch.uint8, device=dev)
+            d_src, d_cnt = torch.empty_like(d_mask), torch.zeros(5, dtype=torch.int64, device=dev)
+            torch.cuda.synchronize()
+            ptrs = lambda a: [x.data_ptr() for x in a]
+            self.retime_frame_dev(ptrs(d_i), 1 if imgs[0].ndim == 2 else imgs[0].shape[2], ptrs(d_dm), ptrs(d_R), ptrs(d_t), K, rows, cols, M, m, int(weight_q16),
+                                  d_out.data_ptr(), d_mask.data_ptr(), d_src.data_ptr(), d_cnt.data_ptr(), window=window, threshold=threshold, occlusion=occlusion,
+                                  occlusion_tol_q16=occlusion_tol_q16, mode=mode, q5_mode=q5_mode, iterations=iterations)
+            self.synchronize()
+            return d_out.cpu().numpy(), d_mask.cpu().numpy(), d_src.cpu().numpy(), d_cnt.cpu().numpy()
+
+    def retime_video_dev(self, d_frames, rows, cols, channels, K, d_depth_maps, d_R, d_t, A, c, A_path, c_path, scales, times, d_out, d_out_masks, d_out_sources=None,
+                         want_counts=True, window=None, threshold=None, occlusion=False, occlusion_tol_q16=0, mode=BACKPROJECT_RS, q5_mode=Q5_COMPAT, iterations=0):
+        """a solved clip retimed (rsdsfm_retime_video_dev): d_depth_maps, d_R, d_t (their length is the number of sources; d_frames has at least
+        as many) and the host arrays A, c, scales as a stabilise clip call left them, A_path, c_path the path to ride (its A_s, c_s, or A, c);
+        for every t of `times` retime_poses and retime_frame_dev into d_out[i], d_out_masks[i], d_out_sources[i].  Returns dict(sources
+        (ntimes, 2) int32, -1 for absent; weights (ntimes,) int32; with want_counts counts (ntimes, 5) int64 -- the call then waits)."""
+        ns, tm = len(d_depth_maps), _f64(times).reshape(-1)
+        nt = tm.shape[0]
+        _need_all(ns, d_frames=d_frames, d_R=d_R, d_t=d_t)
+        _need_all(nt, d_out=d_out, d_out_masks=d_out_masks, d_out_sources=d_out_sources)
+        a, cc, ap, cp = _f64(A).reshape(-1, 9), _f64(c).reshape(-1, 3), _f64(A_path).reshape(-1, 9), _f64(c_path).reshape(-1, 3)
+        sc = _f64(scales).reshape(-1)
+        if min(a.shape[0], cc.shape[0], ap.shape[0], cp.shape[0], sc.shape[0]) < ns:
+            raise RsdsfmError("retime_video_dev: every source needs a pose on both paths and a scale")
+        p = _retime_params(threshold, occlusion, occlusion_tol_q16)
+        sources, weights = np.full((max(nt, 1), 2), -1, dtype=np.int32), np.zeros(max(nt, 1), dtype=np.int32)
+        counts = np.zeros((max(nt, 1), 5), dtype=np.int64) if want_counts else None
+        d = C.c_double
+        arr = lambda x, n: _ptr_array(list(x)[:n]) if x is not None and n else None
+        self._check(self.lib.rsdsfm_retime_video_dev(self._ctx, arr(d_frames, ns), C.c_int32(ns), C.c_int32(rows), C.c_int32(cols), C.c_int32(channels), d(K[0]), d(K[1]),
+                                                     d(K[2]), d(K[3]), arr(d_depth_maps, ns), arr(d_R, ns), arr(d_t, ns), _p(a), _p(cc), _p(ap), _p(cp), _p(sc), int(mode),
+                                                     int(q5_mode), C.c_int32(iterations), _p(tm), C.c_int32(nt), C.byref(p), _window4(window), arr(d_out, nt),
+                                                     arr(d_out_masks, nt), arr(d_out_sources, nt), _p(sources), _p(weights), _p(counts)), "rsdsfm_retime_video_dev")
+        out = dict(sources=sources[:nt], weights=weights[:nt])
+        if want_counts:
+            out["counts"] = counts[:nt]
+        return out
+
+
+for _name, _fn in list(vars(_RetimeMixin).items()):
     if not _name.startswith("__"):
         setattr(Solver, _name, _fn)
 

@@ -21,6 +21,7 @@ struct DenseWs {
     void* d_inpaint = nullptr;        // the inpainting's pyramid of 8-byte cells and its validity word (stabilize_inpaint.hpp; made when first asked for)
     void* d_visible = nullptr;        // the occlusion test's planes: zv (rows x cols float) and zbuf (rows x cols uint32) behind it (stabilize_visible.hpp; made when first asked for)
     void* d_search = nullptr;         // the visible pre-image search's planes: kbuf (rows x cols uint64) and a zv behind it (stabilize_search.hpp; made when first asked for)
+    unsigned char* d_layer2 = nullptr; // the retimer's second layer, mask and image, 4 planes (retime.hpp; made when first asked for)
     int rows = 0, cols = 0;
 };
 

@@ -19,6 +19,8 @@ static void dense_ws_free(DenseWs* w) {
     w->d_visible = nullptr;
     if (w->d_search) (void)hipFree(w->d_search);
     w->d_search = nullptr;
+    if (w->d_layer2) (void)hipFree(w->d_layer2);
+    w->d_layer2 = nullptr;
     w->d_pyr = nullptr;
     w->d_disp = nullptr;
     w->d_mask = nullptr;

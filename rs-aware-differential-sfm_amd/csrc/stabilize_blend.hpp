@@ -23,6 +23,11 @@ __host__ __device__ inline unsigned seam_gain(const unsigned long long* sums, in
     return g < kGainMin ? kGainMin : g > kGainMax ? kGainMax : (unsigned)g;
 }
 
+// DenseWs::d_layer: [distance: P][layer mask: P][layer image: 3 P][one record: 8 uint64], P = rows cols rounded up to 8 bytes; the retimer's
+// layer A is this layer (retime_host.hip)
+inline size_t blend_plane_bytes(int rows, int cols) { return ((size_t)rows * (size_t)cols + 7u) & ~(size_t)7u; }
+inline size_t blend_layer_bytes(int rows, int cols) { return 5 * blend_plane_bytes(rows, cols) + 8 * sizeof(uint64_t); }
+
 // the two launches of the seam distance on c->stream (arguments checked by the caller): rows, then columns; d_h is the row pass's plane
 int seam_distance_launch(Ctx* c, const unsigned char* d_mask, int rows, int cols, int feather, unsigned char* d_h, unsigned char* d_dist);
 

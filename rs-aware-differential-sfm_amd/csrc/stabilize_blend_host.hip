@@ -35,9 +35,6 @@ const char* const kBlendParamsMessage =
 
 bool blend_size_ok(int rows, int cols) { return rows >= 2 && cols >= 2 && rows <= 16384 && cols <= 16384; }
 
-// DenseWs::d_layer: [distance: P][layer mask: P][layer image: 3 P][one record: 8 uint64], P = rows cols rounded up to 8 bytes
-size_t blend_plane_bytes(int rows, int cols) { return ((size_t)rows * (size_t)cols + 7u) & ~(size_t)7u; }
-
 }  // namespace
 }  // namespace rsdsfm
 
@@ -154,7 +151,7 @@ int rsdsfm_stabilize_video_blended_dev(rsdsfm_ctx* ctx, const uint8_t* const* d_
     DenseWs* ws = nullptr;
     rc = rectify_dense_ws(c, rows, cols, &ws);
     if (rc != RSDSFM_OK) return rc;
-    if (!ws->d_layer && hipMalloc(reinterpret_cast<void**>(&ws->d_layer), 5 * P + 8 * sizeof(uint64_t)) != hipSuccess) {
+    if (!ws->d_layer && hipMalloc(reinterpret_cast<void**>(&ws->d_layer), blend_layer_bytes(rows, cols)) != hipSuccess) {
         ws->d_layer = nullptr;
         return fail(c, RSDSFM_ERR_HIP, "blend: no memory for the distance plane and the layer");
     }

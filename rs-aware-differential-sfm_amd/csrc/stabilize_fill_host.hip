@@ -61,14 +61,7 @@ int rsdsfm_neighbour_poses(const double* A, const double* c, const double* A_s, 
         for (int s = -1; s <= 1; s += 2) {  // nearer first, previous before next
             const int n = q + s * d;
             if (n < 0 || n > npairs - 1) continue;
-            const double* An = A + 9 * (size_t)n;
-            const double* cn = c + 3 * (size_t)n;
-            const double dc[3] = {cn[0] - cs[0], cn[1] - cs[1], cn[2] - cs[2]};
-            for (int i = 0; i < 3; ++i) {  // row i of A~_q^T: the spec's _mat3 and _matvec
-                const double a0 = As[i], a1 = As[3 + i], a2 = As[6 + i];
-                for (int j = 0; j < 3; ++j) M_out[9 * (size_t)k + 3 * i + j] = (a0 * An[j] + a1 * An[3 + j]) + a2 * An[6 + j];
-                m_out[3 * (size_t)k + i] = ((a0 * dc[0] + a1 * dc[1]) + a2 * dc[2]) / scales[n];
-            }
+            pose_from(As, cs, A + 9 * (size_t)n, c + 3 * (size_t)n, scales[n], M_out + 9 * (size_t)k, m_out + 3 * (size_t)k);  // stabilize.hpp; the retimer's too
             frames_out[k] = n;
             source_ids_out[k] = 2 * d + (s > 0 ? 1 : 0);
             ++k;

@@ -22,24 +22,7 @@ bool stabilize_params_ok(const rsdsfm_stabilize_params& p) {
     return std::isfinite(p.sigma) && p.sigma > 0.0 && p.radius >= 0 && p.radius <= 1024 && (p.last_frame == 0 || p.last_frame == 1);
 }
 
-// a b for row-major 3 x 3, every entry (a_i0 b_0j + a_i1 b_1j) + a_i2 b_2j; ta: a transposed
-void mat3(const double* a, bool ta, const double* b, double* out) {
-    for (int i = 0; i < 3; ++i)
-        for (int j = 0; j < 3; ++j) {
-            const double a0 = ta ? a[i] : a[3 * i], a1 = ta ? a[3 + i] : a[3 * i + 1], a2 = ta ? a[6 + i] : a[3 * i + 2];
-            out[3 * i + j] = (a0 * b[j] + a1 * b[3 + j]) + a2 * b[6 + j];
-        }
-}
-
-// the rotation vector of R (tests/stabilize_spec_numpy.py: so3_log)
-void so3_log(const double* R, double* l) {
-    const double a[3] = {0.5 * (R[7] - R[5]), 0.5 * (R[2] - R[6]), 0.5 * (R[3] - R[1])};
-    const double s = std::sqrt((a[0] * a[0] + a[1] * a[1]) + a[2] * a[2]);
-    const double cc = 0.5 * (((R[0] + R[4]) + R[8]) - 1.0);
-    const double theta = std::atan2(s, cc);
-    const double f = s < 1e-8 ? 1.0 : theta / s;
-    for (int i = 0; i < 3; ++i) l[i] = s < 1e-8 ? a[i] : a[i] * f;
-}
+// mat3 and so3_log: stabilize.hpp (the retimer interpolates the path with them)
 
 bool finite_all(const double* a, int n) {
     for (int i = 0; i < n; ++i)

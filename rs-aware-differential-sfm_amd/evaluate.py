@@ -208,7 +208,7 @@ def evaluate_real_sequence(solver, frames, camera="galaxy", gamma=0.95, out_dir=
                            use_refinement=True, use_global_shutter_mode=False, flow_threshold=1e-10, flow_index_mode=0, device=0, flow_params=None, dense=False,
                            check_flow=False, trajectory=False, link_tol=None, min_links=None, fuse=False, fuse_tol=None, stabilize=False, smooth_sigma=None,
                            smooth_translation=True, fill=0, crop=False, crop_margin=None, crop_max_empty=0, blend=False, blend_feather=None,
-                           blend_gain=True, inpaint=False, last_frame=False, occlusion=False, occlusion_tol=None, occlusion_search=False):
+                           blend_gain=True, inpaint=False, last_frame=False, occlusion=False, occlusion_tol=None, occlusion_search=False, retime=None):
     """evaluate_real_run's real-world branch (main.cc:341-361, 364-531) for a clip: `frames` is <prefix>frame1.png ... frameN.png (the
     prefix, or a list of paths), or the frames themselves (an (N, rows, cols[, 3]) uint8 array or a list of arrays; 2-D frames are gray).
     By default ONE call does the clip (Solver.rectify_video_dev): the batched DeepFlow of every consecutive pair, the pipelined solve of every pair p
@@ -277,7 +277,14 @@ def evaluate_real_sequence(solver, frames, camera="galaxy", gamma=0.95, out_dir=
     (tests/stabilize_search_spec_numpy.py): a pixel the test rejects is looked for again from the source pixel that landed nearest the camera on
     its cell and, where that ends on the visible surface, recovered; it counts under its offset.  The returned dict then also has fill_recovered
     and, with crop=True, crop_recovered ((frames,) int64: the recovered pixels per frame, summed over its candidates, from the calls' own
-    counters); out_dir receives occlusion_search.csv (frame and the sums).  Without occlusion_search every output is what it was."""
+    counters); out_dir receives occlusion_search.csv (frame and the sums).  Without occlusion_search every output is what it was.
+    retime=factor or a list of times (needs stabilize=True: ValueError otherwise): behind everything else, the solved clip rendered once more at
+    the instants retime_times(frames with a depth map, factor), or at the given times, along the SMOOTHED path (Solver.retime_video_dev,
+    tests/retime_spec_numpy.py; the fused maps with fuse=True, the layers through the occlusion test with occlusion=True): the returned dict
+    also has retimed, retime_masks, retime_sources (lists of frames), retime_counts ((times, 5) int64: [none, a only, b only, dissolved,
+    conflict]) and retime_times; out_dir receives retimed_<i>.png and retime.csv.  Without the keyword every key and file is what it was."""
+    if retime is not None and not stabilize:
+        raise ValueError("retime needs stabilize=True: it rides the smoothed path of the stabilised clip")
     if occlusion_search and not occlusion:
         raise ValueError("occlusion_search needs occlusion=True: the search runs where the occlusion test rejects")
     if occlusion and not (stabilize and fill >= 1):
@@ -550,6 +557,19 @@ def evaluate_real_sequence(solver, frames, camera="galaxy", gamma=0.95, out_dir=
                     solver.synchronize()
                     traj.update(stab_inpainted=[t.cpu().numpy() for t in d_inps], inpaint_sources=[t.cpu().numpy() for t in d_isrcs],
                                 inpaint_counts=d_icnt.cpu().numpy())
+                if retime is not None:  # the solved clip once more, at the asked instants along the smoothed path
+                    from . import retime_times
+
+                    times = retime_times(nst, retime) if np.ndim(retime) == 0 else np.asarray(retime, dtype=np.float64).reshape(-1)
+                    d_rts = [torch.empty_like(d_imgs[0]) for _ in times]
+                    d_rmasks = [torch.empty((rows, cols), dtype=torch.uint8, device=dev) for _ in times]
+                    d_rsrcs = [torch.empty((rows, cols), dtype=torch.uint8, device=dev) for _ in times]
+                    torch.cuda.synchronize()
+                    rt = solver.retime_video_dev(ptrs(d_imgs), rows, cols, channels, K, ptrs(d_src[:nst]), ptrs(d_Rs[:nst]), ptrs(d_ts[:nst]), traj["A"], traj["c"], A_s,
+                                                 c_s, st_scales, times, ptrs(d_rts), ptrs(d_rmasks), ptrs(d_rsrcs), occlusion=occlusion,
+                                                 occlusion_tol_q16=occ_q16 if occlusion else 0, mode=mode)
+                    traj.update(retimed=[t.cpu().numpy() for t in d_rts], retime_masks=[t.cpu().numpy() for t in d_rmasks],
+                                retime_sources=[t.cpu().numpy() for t in d_rsrcs], retime_counts=rt["counts"], retime_times=times)
     if out_dir:
         os.makedirs(out_dir, exist_ok=True)
         lines = ["pair,v_x,v_y,v_z,w_x,w_y,w_z,k,inliers"]
@@ -624,6 +644,13 @@ def evaluate_real_sequence(solver, frames, camera="galaxy", gamma=0.95, out_dir=
                 formats.write_png(os.path.join(out_dir, "stabilized_blended_%d.png" % p), traj["stab_blended"][p])
                 rows_.append(",".join([str(p)] + [str(int(x)) for x in traj["blend_counts"][p]] + [str(int(x)) for x in traj["blend_gains"][p].reshape(-1)]))
             with open(os.path.join(out_dir, "blend.csv"), "w") as fh:
+                fh.write("\n".join(rows_) + "\n")
+        if retime is not None:
+            rows_ = ["index,time,source_a,source_b,weight_q16,none,a_only,b_only,dissolved,conflict"]
+            for i, t_ in enumerate(traj["retime_times"]):
+                formats.write_png(os.path.join(out_dir, "retimed_%d.png" % i), traj["retimed"][i])
+                rows_.append(",".join([str(i), "%.17g" % t_] + [str(int(x)) for x in list(rt["sources"][i]) + [rt["weights"][i]] + list(traj["retime_counts"][i])]))
+            with open(os.path.join(out_dir, "retime.csv"), "w") as fh:
                 fh.write("\n".join(rows_) + "\n")
         if inpaint:
             rows_ = ["pair,stage,inpainted"]
