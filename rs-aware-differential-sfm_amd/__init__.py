@@ -135,10 +135,10 @@ class RansacOut(C.Structure):
 
 
 def declared_symbols():
-    """Names of every function include/rsdsfm.h and include/rsdsfm_retime.h declare (used by the CPU symbol-export test)."""
+    """Names of every function include/rsdsfm.h, include/rsdsfm_retime.h and include/rsdsfm_shutter.h declare (used by the CPU symbol-export test)."""
     import re
 
-    txt = open(HEADER_PATH).read() + open(os.path.join(os.path.dirname(HEADER_PATH), "rsdsfm_retime.h")).read()
+    txt = "".join(open(os.path.join(os.path.dirname(HEADER_PATH), name)).read() for name in (os.path.basename(HEADER_PATH), "rsdsfm_retime.h", "rsdsfm_shutter.h"))
     txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
     return sorted(set(re.findall(r"\b(rsdsfm_[a-z0-9_]+)\s*\(", txt)))
 
@@ -2826,6 +2826,169 @@ class _RetimeMixin:
 
 
 for _name, _fn in list(vars(_RetimeMixin).items()):
+    if not _name.startswith("__"):
+        setattr(Solver, _name, _fn)
+
+
+# ---------------------------------------------------------------------------------------------------
+# the synthetic shutter: a frame exposed over a window of time, the mean of sub-instant renders (include/rsdsfm_shutter.h)
+# ---------------------------------------------------------------------------------------------------
+SHUTTER_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "rsdsfm_shutter.h")
+SHUTTER_SAMPLES_MAX = 64
+
+
+class ShutterParams(C.Structure):
+    _fields_ = [("shutter", C.c_double), ("samples", C.c_int32), ("min_samples", C.c_int32), ("struct_bytes", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
+def shutter_declared_symbols():
+    """Names of every function include/rsdsfm_shutter.h declares"""
+    import re
+
+    txt = open(SHUTTER_HEADER_PATH).read()
+    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
+    return sorted(set(re.findall(r"\b(rsdsfm_[a-z0-9_]+)\s*\(", txt)))
+
+
+def _shutter_params(shutter=None, samples=None, min_samples=None):
+    """a ShutterParams with the given values over the defaults (None: the default)"""
+    p = ShutterParams()
+    if load_library().rsdsfm_shutter_params_init(C.byref(p)) != OK:
+        raise RsdsfmError("rsdsfm_shutter_params_init failed")
+    if shutter is not None:
+        p.shutter = float(shutter)
+    if samples is not None:
+        p.samples = int(samples)
+    if min_samples is not None:
+        p.min_samples = int(min_samples)
+    return p
+
+
+def shutter_default_params():
+    """the shutter's defaults as a dict: shutter = 0.5, samples = 8, min_samples = 1 (rsdsfm_shutter_params_init); choices, not measurements"""
+    p = _shutter_params()
+    return dict(shutter=p.shutter, samples=p.samples, min_samples=p.min_samples)
+
+
+def shutter_times(t, shutter, samples, nsources):
+    """the kept sub-instants of the exposure about t (rsdsfm_shutter_times; host arithmetic, no GPU; tests/shutter_spec_numpy.py):
+    t_j = t + shutter ((j + 0.5) / samples - 0.5) for j = 0 .. samples - 1, those inside [0, nsources - 1], in order -> (kept,) float64"""
+    n = int(samples)
+    out, kept = np.zeros(max(min(n, SHUTTER_SAMPLES_MAX), 1)), C.c_int32()
+    rc = load_library().rsdsfm_shutter_times(C.c_double(t), C.c_double(shutter), C.c_int32(n), C.c_int32(nsources), _p(out), C.byref(kept))
+    if rc != OK:
+        raise RsdsfmError("rsdsfm_shutter_times failed (%d): samples in [1, 64], shutter finite and in [0, nsources - 1], t finite and in [0, nsources - 1]" % rc)
+    return out[:kept.value].copy()
+
+
+def shutter_from_angle(angle_deg, factor):
+    """the shutter width, in input-frame intervals, of a shutter angle on a clip retimed by `factor` (output frames per input frame; 1 / 2
+    halves the frame rate): angle / 360 of the output frame's interval 1 / factor"""
+    return float(angle_deg) / 360.0 / float(factor)
+
+
+def shutter_launches(rows, cols, n_one_source, n_two_sources):
+    """kernel launches of one shutter_frame_dev call whose kept sub-instants are n_one_source integer instants and n_two_sources others: their
+    retime_launches plus one accumulate each (rsdsfm_shutter_launches; host only)"""
+    n = load_library().rsdsfm_shutter_launches(C.c_int32(rows), C.c_int32(cols), C.c_int32(n_one_source), C.c_int32(n_two_sources))
+    if n < 0:
+        raise RsdsfmError("rsdsfm_shutter_launches failed (%d): rows and cols in [2, 16384], counts >= 0 with a sum in [1, 64]" % n)
+    return n
+
+
+def shutter_accumulate_launches():
+    """kernel launches of one shutter_accumulate_dev call: 1 (rsdsfm_shutter_accumulate_launches; host only)"""
+    return int(load_library().rsdsfm_shutter_accumulate_launches())
+
+
+class _ShutterMixin:
+    def shutter_accumulate_dev(self, d_image, d_mask, channels, rows, cols, d_cells, first, last, nsamples, min_samples=1, d_image_out=None, d_mask_out=None,
+                               d_coverage=None, d_counts3=None):
+        """one sample accumulated (rsdsfm_shutter_accumulate_dev; tests/shutter_spec_numpy.py): d_cells holds rows x cols cells of channels + 1
+        uint16 [sums, n] (None only with first and last).  first: the cells are set from the sample; otherwise the sample is added where its mask
+        is not 0.  last: the cells are not written; the mean (round half up) goes to d_image_out and 1 to d_mask_out where n >= min_samples, n to
+        d_coverage, [unset, partial, full] to d_counts3 (three device int64).  Enqueued on the context's stream."""
+        self._check(self.lib.rsdsfm_shutter_accumulate_dev(self._ctx, _dp(d_image), _dp(d_mask), C.c_int32(channels), C.c_int32(rows), C.c_int32(cols), _np0(d_cells),
+                                                           C.c_int32(int(first)), C.c_int32(int(last)), C.c_int32(nsamples), C.c_int32(min_samples), _np0(d_image_out),
+                                                           _np0(d_mask_out), _np0(d_coverage), _np0(d_counts3)), "rsdsfm_shutter_accumulate_dev")
+
+    def shutter_accumulate(self, samples, min_samples=1, device=0):
+        """host convenience around shutter_accumulate_dev: samples, a list of 1 .. 64 (image, mask) pairs of host arrays
+        -> (image, mask, coverage (rows, cols) uint8, counts (3,) int64 [unset, partial, full])"""
+        import torch
+
+        S = len(samples)
+        first = np.ascontiguousarray(samples[0][0], dtype=np.uint8)
+        rows, cols = first.shape[:2]
+        ch = 1 if first.ndim == 2 else first.shape[2]
+        dev = torch.device("cuda", device)
+        with torch.cuda.device(dev):
+            up = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.uint8)).to(dev)
+            d_s = [(up(i), up(m)) for i, m in samples]
+            d_cells = torch.empty((rows, cols, ch + 1), dtype=torch.int16, device=dev)
+            d_out, d_mask = torch.empty_like(d_s[0][0]), torch.empty((rows, cols), dtype=torch.uint8, device=dev)
+            d_cov, d_cnt = torch.empty_like(d_mask), torch.zeros(3, dtype=torch.int64, device=dev)
+            torch.cuda.synchronize()
+            for j, (d_i, d_m) in enumerate(d_s):
+                self.shutter_accumulate_dev(d_i.data_ptr(), d_m.data_ptr(), ch, rows, cols, d_cells.data_ptr(), j == 0, j == S - 1, S, min_samples, d_out.data_ptr(),
+                                            d_mask.data_ptr(), d_cov.data_ptr(), d_cnt.data_ptr())
+            self.synchronize()
+            return d_out.cpu().numpy(), d_mask.cpu().numpy(), d_cov.cpu().numpy(), d_cnt.cpu().numpy()
+
+    def _shutter_clip(self, what, d_frames, d_depth_maps, d_R, d_t, A, c, A_path, c_path, scales):
+        ns = len(d_depth_maps)
+        _need_all(ns, d_frames=d_frames, d_R=d_R, d_t=d_t)
+        a, cc, ap, cp = _f64(A).reshape(-1, 9), _f64(c).reshape(-1, 3), _f64(A_path).reshape(-1, 9), _f64(c_path).reshape(-1, 3)
+        sc = _f64(scales).reshape(-1)
+        if min(a.shape[0], cc.shape[0], ap.shape[0], cp.shape[0], sc.shape[0]) < ns:
+            raise RsdsfmError("%s: every source needs a pose on both paths and a scale" % what)
+        return ns, a, cc, ap, cp, sc
+
+    def shutter_frame_dev(self, d_frames, rows, cols, channels, K, d_depth_maps, d_R, d_t, A, c, A_path, c_path, scales, t, d_image, d_mask, d_coverage=None,
+                          d_counts3=None, shutter=None, samples=None, min_samples=None, window=None, threshold=None, occlusion=False, occlusion_tol_q16=0,
+                          mode=BACKPROJECT_RS, q5_mode=Q5_COMPAT, iterations=0, shutter_params=None, retime_params=None):
+        """one exposed frame of a solved clip (rsdsfm_shutter_frame_dev): the clip as retime_video_dev takes it; for every kept sub-instant of
+        shutter_times(t, shutter, samples, len(d_depth_maps)) retime_poses, retime_frame_dev onto the context's sample planes and
+        shutter_accumulate_dev, the mean into d_image, d_mask, d_coverage, d_counts3.  shutter, samples, min_samples None: the defaults (0.5, 8,
+        1); shutter_params / retime_params: structs passed as they are instead.  Returns the kept count.  Enqueued on the context's stream."""
+        ns, a, cc, ap, cp, sc = self._shutter_clip("shutter_frame_dev", d_frames, d_depth_maps, d_R, d_t, A, c, A_path, c_path, scales)
+        sp = shutter_params if shutter_params is not None else _shutter_params(shutter, samples, min_samples)
+        rp = retime_params if retime_params is not None else _retime_params(threshold, occlusion, occlusion_tol_q16)
+        d = C.c_double
+        kept = C.c_int32()
+        arr = lambda x: _ptr_array(list(x)[:ns]) if ns else None
+        self._check(self.lib.rsdsfm_shutter_frame_dev(self._ctx, arr(d_frames), C.c_int32(ns), C.c_int32(rows), C.c_int32(cols), C.c_int32(channels), d(K[0]), d(K[1]),
+                                                      d(K[2]), d(K[3]), arr(d_depth_maps), arr(d_R), arr(d_t), _p(a), _p(cc), _p(ap), _p(cp), _p(sc), int(mode),
+                                                      int(q5_mode), C.c_int32(iterations), d(t), C.byref(sp), C.byref(rp), _window4(window), _dp(d_image), _dp(d_mask),
+                                                      _np0(d_coverage), _np0(d_counts3), C.byref(kept)), "rsdsfm_shutter_frame_dev")
+        return int(kept.value)
+
+    def shutter_video_dev(self, d_frames, rows, cols, channels, K, d_depth_maps, d_R, d_t, A, c, A_path, c_path, scales, times, d_out, d_out_masks, d_out_coverage=None,
+                          want_counts=True, shutter=None, samples=None, min_samples=None, window=None, threshold=None, occlusion=False, occlusion_tol_q16=0,
+                          mode=BACKPROJECT_RS, q5_mode=Q5_COMPAT, iterations=0):
+        """a solved clip exposed at every t of `times` (rsdsfm_shutter_video_dev): one shutter_frame_dev per instant into d_out[i],
+        d_out_masks[i], d_out_coverage[i].  Returns dict(kept (ntimes,) int32; with want_counts counts (ntimes, 3) int64 [unset, partial, full]
+        -- the call then waits)."""
+        ns, a, cc, ap, cp, sc = self._shutter_clip("shutter_video_dev", d_frames, d_depth_maps, d_R, d_t, A, c, A_path, c_path, scales)
+        tm = _f64(times).reshape(-1)
+        nt = tm.shape[0]
+        _need_all(nt, d_out=d_out, d_out_masks=d_out_masks, d_out_coverage=d_out_coverage)
+        sp, rp = _shutter_params(shutter, samples, min_samples), _retime_params(threshold, occlusion, occlusion_tol_q16)
+        kept = np.zeros(max(nt, 1), dtype=np.int32)
+        counts = np.zeros((max(nt, 1), 3), dtype=np.int64) if want_counts else None
+        d = C.c_double
+        arr = lambda x, n: _ptr_array(list(x)[:n]) if x is not None and n else None
+        self._check(self.lib.rsdsfm_shutter_video_dev(self._ctx, arr(d_frames, ns), C.c_int32(ns), C.c_int32(rows), C.c_int32(cols), C.c_int32(channels), d(K[0]), d(K[1]),
+                                                      d(K[2]), d(K[3]), arr(d_depth_maps, ns), arr(d_R, ns), arr(d_t, ns), _p(a), _p(cc), _p(ap), _p(cp), _p(sc), int(mode),
+                                                      int(q5_mode), C.c_int32(iterations), _p(tm), C.c_int32(nt), C.byref(sp), C.byref(rp), _window4(window),
+                                                      arr(d_out, nt), arr(d_out_masks, nt), arr(d_out_coverage, nt), _p(kept), _p(counts)), "rsdsfm_shutter_video_dev")
+        out = dict(kept=kept[:nt])
+        if want_counts:
+            out["counts"] = counts[:nt]
+        return out
+
+
+for _name, _fn in list(vars(_ShutterMixin).items()):
     if not _name.startswith("__"):
         setattr(Solver, _name, _fn)
 

@@ -22,6 +22,7 @@ struct DenseWs {
     void* d_visible = nullptr;        // the occlusion test's planes: zv (rows x cols float) and zbuf (rows x cols uint32) behind it (stabilize_visible.hpp; made when first asked for)
     void* d_search = nullptr;         // the visible pre-image search's planes: kbuf (rows x cols uint64) and a zv behind it (stabilize_search.hpp; made when first asked for)
     unsigned char* d_layer2 = nullptr; // the retimer's second layer, mask and image, 4 planes (retime.hpp; made when first asked for)
+    unsigned char* d_shutter = nullptr; // the synthetic shutter's sample mask and image and its cells, 12 planes (shutter.hpp; made when first asked for)
     int rows = 0, cols = 0;
 };
 

@@ -21,6 +21,8 @@ static void dense_ws_free(DenseWs* w) {
     w->d_search = nullptr;
     if (w->d_layer2) (void)hipFree(w->d_layer2);
     w->d_layer2 = nullptr;
+    if (w->d_shutter) (void)hipFree(w->d_shutter);
+    w->d_shutter = nullptr;
     w->d_pyr = nullptr;
     w->d_disp = nullptr;
     w->d_mask = nullptr;

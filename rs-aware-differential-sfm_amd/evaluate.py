@@ -208,7 +208,8 @@ def evaluate_real_sequence(solver, frames, camera="galaxy", gamma=0.95, out_dir=
                            use_refinement=True, use_global_shutter_mode=False, flow_threshold=1e-10, flow_index_mode=0, device=0, flow_params=None, dense=False,
                            check_flow=False, trajectory=False, link_tol=None, min_links=None, fuse=False, fuse_tol=None, stabilize=False, smooth_sigma=None,
                            smooth_translation=True, fill=0, crop=False, crop_margin=None, crop_max_empty=0, blend=False, blend_feather=None,
-                           blend_gain=True, inpaint=False, last_frame=False, occlusion=False, occlusion_tol=None, occlusion_search=False, retime=None):
+                           blend_gain=True, inpaint=False, last_frame=False, occlusion=False, occlusion_tol=None, occlusion_search=False, retime=None,
+                           shutter=None):
     """evaluate_real_run's real-world branch (main.cc:341-361, 364-531) for a clip: `frames` is <prefix>frame1.png ... frameN.png (the
     prefix, or a list of paths), or the frames themselves (an (N, rows, cols[, 3]) uint8 array or a list of arrays; 2-D frames are gray).
     By default ONE call does the clip (Solver.rectify_video_dev): the batched DeepFlow of every consecutive pair, the pipelined solve of every pair p
@@ -282,7 +283,15 @@ def evaluate_real_sequence(solver, frames, camera="galaxy", gamma=0.95, out_dir=
     the instants retime_times(frames with a depth map, factor), or at the given times, along the SMOOTHED path (Solver.retime_video_dev,
     tests/retime_spec_numpy.py; the fused maps with fuse=True, the layers through the occlusion test with occlusion=True): the returned dict
     also has retimed, retime_masks, retime_sources (lists of frames), retime_counts ((times, 5) int64: [none, a only, b only, dissolved,
-    conflict]) and retime_times; out_dir receives retimed_<i>.png and retime.csv.  Without the keyword every key and file is what it was."""
+    conflict]) and retime_times; out_dir receives retimed_<i>.png and retime.csv.  Without the keyword every key and file is what it was.
+    shutter=width or (width, samples) (needs retime: ValueError otherwise): behind the retimed frames, the same instants once more EXPOSED over a
+    window of `width` input-frame intervals (shutter_from_angle turns a shutter angle into one), the mean of `samples` (default 8) sub-instant
+    renders each (Solver.shutter_video_dev, tests/shutter_spec_numpy.py; the retimed frames' maps, path and occlusion settings): the returned dict
+    also has shuttered, shutter_masks, shutter_coverage (lists of frames; the coverage is the number of sub-instants that saw the pixel),
+    shutter_counts ((times, 3) int64: [unset, partial, full]) and shutter_kept ((times,) int32: the sub-instants inside the clip); out_dir
+    receives shuttered_<i>.png and shutter.csv.  The retimed keys and files stay as they are; without the keyword every key and file is what it was."""
+    if shutter is not None and retime is None:
+        raise ValueError("shutter needs retime=factor or times: it exposes the retimed clip's instants")
     if retime is not None and not stabilize:
         raise ValueError("retime needs stabilize=True: it rides the smoothed path of the stabilised clip")
     if occlusion_search and not occlusion:
@@ -570,6 +579,17 @@ def evaluate_real_sequence(solver, frames, camera="galaxy", gamma=0.95, out_dir=
                                                  occlusion_tol_q16=occ_q16 if occlusion else 0, mode=mode)
                     traj.update(retimed=[t.cpu().numpy() for t in d_rts], retime_masks=[t.cpu().numpy() for t in d_rmasks],
                                 retime_sources=[t.cpu().numpy() for t in d_rsrcs], retime_counts=rt["counts"], retime_times=times)
+                    if shutter is not None:  # the same instants once more, exposed
+                        width, nsamp = (shutter, None) if np.ndim(shutter) == 0 else (shutter[0], int(shutter[1]))
+                        d_sh = [torch.empty_like(d_imgs[0]) for _ in times]
+                        d_shmasks = [torch.empty((rows, cols), dtype=torch.uint8, device=dev) for _ in times]
+                        d_shcov = [torch.empty((rows, cols), dtype=torch.uint8, device=dev) for _ in times]
+                        torch.cuda.synchronize()
+                        sh = solver.shutter_video_dev(ptrs(d_imgs), rows, cols, channels, K, ptrs(d_src[:nst]), ptrs(d_Rs[:nst]), ptrs(d_ts[:nst]), traj["A"], traj["c"],
+                                                      A_s, c_s, st_scales, times, ptrs(d_sh), ptrs(d_shmasks), ptrs(d_shcov), shutter=float(width), samples=nsamp,
+                                                      occlusion=occlusion, occlusion_tol_q16=occ_q16 if occlusion else 0, mode=mode)
+                        traj.update(shuttered=[t.cpu().numpy() for t in d_sh], shutter_masks=[t.cpu().numpy() for t in d_shmasks],
+                                    shutter_coverage=[t.cpu().numpy() for t in d_shcov], shutter_counts=sh["counts"], shutter_kept=sh["kept"])
     if out_dir:
         os.makedirs(out_dir, exist_ok=True)
         lines = ["pair,v_x,v_y,v_z,w_x,w_y,w_z,k,inliers"]
@@ -651,6 +671,13 @@ def evaluate_real_sequence(solver, frames, camera="galaxy", gamma=0.95, out_dir=
                 formats.write_png(os.path.join(out_dir, "retimed_%d.png" % i), traj["retimed"][i])
                 rows_.append(",".join([str(i), "%.17g" % t_] + [str(int(x)) for x in list(rt["sources"][i]) + [rt["weights"][i]] + list(traj["retime_counts"][i])]))
             with open(os.path.join(out_dir, "retime.csv"), "w") as fh:
+                fh.write("\n".join(rows_) + "\n")
+        if shutter is not None:
+            rows_ = ["index,time,kept,unset,partial,full"]
+            for i, t_ in enumerate(traj["retime_times"]):
+                formats.write_png(os.path.join(out_dir, "shuttered_%d.png" % i), traj["shuttered"][i])
+                rows_.append(",".join([str(i), "%.17g" % t_, str(int(traj["shutter_kept"][i]))] + [str(int(x)) for x in traj["shutter_counts"][i]]))
+            with open(os.path.join(out_dir, "shutter.csv"), "w") as fh:
                 fh.write("\n".join(rows_) + "\n")
         if inpaint:
             rows_ = ["pair,stage,inpainted"]
