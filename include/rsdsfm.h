@@ -397,6 +397,16 @@ int rsdsfm_set_frame_predict(rsdsfm_ctx* ctx, int mode);
 /* hypotheses whose pixel pass fused their predicted iterate alone (rsdsfm_set_frame_predict 0 / 2) on this context and its sequence lanes,
  * discarded speculative runs included, and how many of them ended at that iterate.  Waits for the contexts' streams. */
 int rsdsfm_lma_predict_stats(rsdsfm_ctx* ctx, int64_t* hypotheses, int64_t* ended_where_predicted);
+/* Where the lanes of the analytic pixel pass (the T depth solves of a RANSAC: rsdsfm_ransac*, the frame solves, the tiled driver) take their
+ * pixel's operands from.  A lane owns a hypothesis, and the T lanes of a pixel slot all work on the same pixel:
+ *   0 (default) = one thread per pixel loads q, u, alpha and alpha_k, forms what depends on the pixel alone (x y, x x + 1, y y + 1 and -- where
+ *       every hypothesis carries the same k, i.e. without the k estimation -- beta) and leaves a record in LDS that the pixel's lanes read;
+ *       passes of fewer than 16 hypotheses per group (where a record has few readers and a lane meets a barrier every few pixels) run as in 1;
+ *   1 = every lane loads its pixel's operands from global memory and forms those products itself;
+ *   2 = 0 for every hypothesis count (tests, measurements).
+ * Copied to the lanes of rsdsfm_solve_frames_dev.  Every lane sees the same operand bits and does the same operations in the same order:
+ * every mode returns the same bytes. */
+int rsdsfm_set_lma_operands(rsdsfm_ctx* ctx, int mode);
 /* minimal::ransac on device-resident inputs.  The arrays of `out` (inlier_idx, inliers, alpha, alpha_k, mask,
  * inv_depth) are DEVICE pointers with capacity n (each may be NULL); its trial_* arrays are HOST pointers.
  * samples_9xT_or_null is a HOST pointer.  Synchronises once at the end to return the scalars of `out`. */

@@ -619,6 +619,12 @@ class Solver:
         predicted for it, 1 both iterates for every hypothesis, 2 the prediction inverted and the pass's scores discarded (tests); identical outputs of the frame solve"""
         self._check(self.lib.rsdsfm_set_frame_predict(self._ctx, int(mode)), "rsdsfm_set_frame_predict")
 
+    def set_lma_operands(self, mode):
+        """where the lanes of the analytic pixel pass take their pixel's operands from (rsdsfm_set_lma_operands): 0 (default) a record one thread
+        per pixel leaves in LDS (groups of fewer than 16 hypotheses: as 1), 1 every lane's own global loads, 2 the record for every hypothesis count
+        (tests); identical outputs"""
+        self._check(self.lib.rsdsfm_set_lma_operands(self._ctx, int(mode)), "rsdsfm_set_lma_operands")
+
     def prepared_frames_solve(self, jobs, trials=50, tol=0.05, use_acceleration_mode=False, use_refinement=True, depth_mode=DEPTH_CERES_LM,
                               k_sign_mode=K_COMPAT, flow_threshold=1e-10, flow_index_mode=FLOW_COMPAT_RANK, use_global_shutter_mode=False):
         """A SEQUENCE of frame pairs in ONE C-ABI call (rsdsfm_solve_frames_dev), pipelined inside the library.  jobs: list of dicts with

@@ -477,6 +477,14 @@ int rsdsfm_set_frame_predict(rsdsfm_ctx* ctx, int mode) {
     return RSDSFM_OK;
 }
 
+int rsdsfm_set_lma_operands(rsdsfm_ctx* ctx, int mode) {
+    if (!ctx) return RSDSFM_ERR_INVALID;
+    if (mode < 0 || mode > 2) return fail(&ctx->c, RSDSFM_ERR_INVALID, "mode must be 0 (the pixel pass stages each pixel's operands once per workgroup), 1 (every lane loads its pixel's operands) or 2 (0 for every hypothesis count)");
+    ctx->c.lma_operands = mode;
+    for (rsdsfm_ctx* lane : ctx->c.lanes) lane->c.lma_operands = mode;
+    return RSDSFM_OK;
+}
+
 int rsdsfm_set_frame_side_flatten(rsdsfm_ctx* ctx, int mode) {
     if (!ctx) return RSDSFM_ERR_INVALID;
     if (mode < 0 || mode > 3) return fail(&ctx->c, RSDSFM_ERR_INVALID, "mode must be 0 (flatten first), 1 (flatten on a second stream), 2 (flatten behind the minimal solver) or 3 (flatten inside the solver's launch)");
@@ -522,6 +530,7 @@ int solve_frames_run(Ctx* c, const rsdsfm_frame_job* jobs, int32_t count, const 
         lc->frame_tail = c->frame_tail;
         lc->frame_handoff = c->frame_handoff;
         lc->frame_predict = c->frame_predict;
+        lc->lma_operands = c->lma_operands;
         lc->refine_stage_mode = c->refine_stage_mode;
     }
     // several pairs in flight share the GPU: the refinement's single-workgroup stage gets launches of its own (Ctx::refine_stage_mode)

@@ -104,13 +104,13 @@ __device__ __forceinline__ double lma_max_pos(double x, double lo) {
 }
 // oracle/rsdsfm_oracle.c lma_pixel(): the SAME operations in the same order
 // FULL: the standard division (the rows stage, which sees a handful of pixels: same bits in range)
+// The staged form (the pixel pass's operand records, ransac_lma_kernels.hip): beta and the three products of x and y come from the caller, who
+// formed them with the expressions of the overload below; the remaining operations, in the same order.
 template <bool FULL = false>
-__device__ __forceinline__ LmaPx lma_pixel(double x, double y, double ux, double uy, double al, double ak, const Pose& p, double two_over) {
+__device__ __forceinline__ LmaPx lma_pixel(double x, double y, double ux, double uy, double beta, double xy, double xx1, double yy1, const Pose& p) {
     LmaPx o;
-    const double beta = two_over * __builtin_fma(p.k, ak, al);
     const double a0 = __builtin_fma(x, p.v[2], -p.v[0]), a1 = __builtin_fma(y, p.v[2], -p.v[1]);
     const double J0 = beta * a0, J1 = beta * a1;
-    const double xy = x * y, xx1 = __builtin_fma(x, x, 1.0), yy1 = __builtin_fma(y, y, 1.0);
     const double bw0 = __builtin_fma(xx1, p.w[1], __builtin_fma(-xy, p.w[0], -(y * p.w[2])));
     const double bw1 = __builtin_fma(xy, p.w[1], __builtin_fma(-yy1, p.w[0], x * p.w[2]));
     const double c0 = __builtin_fma(-beta, bw0, ux), c1 = __builtin_fma(-beta, bw1, uy);
@@ -134,6 +134,17 @@ __device__ __forceinline__ LmaPx lma_pixel(double x, double y, double ux, double
     o.g = g;
     o.clamped = clamped;
     return o;
+}
+// the pixel's own products (one expression each: a staging thread and a lane form the same bits)
+__device__ __forceinline__ double lma_beta(double al, double ak, double k, double two_over) { return two_over * __builtin_fma(k, ak, al); }
+__device__ __forceinline__ void lma_products(double x, double y, double& xy, double& xx1, double& yy1) {
+    xy = x * y, xx1 = __builtin_fma(x, x, 1.0), yy1 = __builtin_fma(y, y, 1.0);
+}
+template <bool FULL = false>
+__device__ __forceinline__ LmaPx lma_pixel(double x, double y, double ux, double uy, double al, double ak, const Pose& p, double two_over) {
+    double xy, xx1, yy1;
+    lma_products(x, y, xy, xx1, yy1);
+    return lma_pixel<FULL>(x, y, ux, uy, lma_beta(al, ak, p.k, two_over), xy, xx1, yy1, p);
 }
 // max(m, |x|) as the one instruction it is (v_max_f64 returns the other operand for a NaN, like fmax)
 __device__ __forceinline__ double lma_max_abs(double m, double x) {

@@ -195,7 +195,8 @@ int ransac_advance(Ctx* c, RansacRun& R, bool yield_at_wait) {
                     rc = ransac_lma_launch(c, R.d_q, R.d_u, R.d_a, R.d_ak, n, R.d_hyp + (size_t)b0 * 8, B, R.d_states + b0, R.d_partials, R.d_flags,
                                            R.d_scored + b0, R.d_tcount + b0, R.d_terr + b0, tol, R.lma_cand, 2, R.d_irr_count, R.d_irr_list, R.d_unscored,
                                            nullptr, R.core_epoch ? c->d_core_flag : nullptr, R.core_epoch, R.count_only,
-                                           R.own_pass ? R.d_pred_steps + b0 : nullptr, reinterpret_cast<unsigned long long*>(c->d_core_flag + 4), c->frame_predict == 2);
+                                           R.own_pass ? R.d_pred_steps + b0 : nullptr, reinterpret_cast<unsigned long long*>(c->d_core_flag + 4), c->frame_predict == 2,
+                                           !R.use_alpha_k, 0.0);  // (without the k estimation every hypothesis carries k = +0.0: minimal9_body)
                 } else {
                     rc = ransac_lm_round_launch(c, R.d_q, R.d_u, R.d_a, R.d_ak, n, R.d_hyp + (size_t)b0 * 8, B, R.d_states + b0, R.d_partials, R.d_flags,
                                                 R.d_scored + b0, R.d_tcount + b0, R.d_terr + b0, round, tol, R.k0, R.fused_base, R.core_math,

@@ -10,6 +10,10 @@
 //   ransac_lma_own_kernel     the same pass with ONE fused iterate per hypothesis, the hypothesis' OWN: the one the solver's launch predicted it
 //                             ends at (minimal9_flatten_kernel: pred_steps).  A hypothesis ends at exactly one iterate, so the score at the other
 //                             is work the result does not need; a hypothesis that ends elsewhere is "not scored" and takes the scoring pass.
+//   ransac_lma_staged_kernel, ransac_lma_staged_own_kernel
+//                             the two passes with each pixel's operands formed ONCE per workgroup (rsdsfm_set_lma_operands 0, the default): a
+//                             staging thread per pixel leaves a record in LDS that the pixel's T lanes read (tiles of <= 256 pixels, two
+//                             buffers, one barrier per tile); the lanes' arithmetic, sums and visiting order are the per-lane form's
 //   ransac_lma_rows_kernel    one workgroup per hypothesis: fixed-order reduction of the workgroups' partial rows, the listed pixels on the
 //                             reference's exact recurrence (sorted by pixel index: deterministic sums) -> the row the decide stage consumes
 //                             (the all-gather payload of the column-tiled solve)
@@ -62,13 +66,79 @@ __device__ __forceinline__ int lma_own_index(const LmaCand& cd, int pred) { retu
 // The body of both forms.  OWN (NC = 1): phi^2 of the lane's hypothesis is cd.phi2[lma_own_index(pred_steps[t])] -- a per-lane value at no cost,
 // the lane owns the hypothesis -- and score slot 0 of the partial row carries that iterate: the same per-pixel values added in the same order
 // as the slot of that iterate in the two-iterate pass.
-template <int NC, bool ERR, bool OWN>
+//
+// STG, where the lanes' operands come from (rsdsfm_set_lma_operands).  The T lanes of a pixel slot all work on the same pixel:
+//   kLmaPerLane       every lane loads q, u, alpha, alpha_k of its pixel from global memory and forms the pixel's own products
+//   staged            ONE thread per pixel loads them (coalesced), forms what depends on the pixel alone with lma_pixel's own expressions and
+//                     leaves a record in LDS; the lanes of the slot read it with 16-byte reads of one address (a broadcast).  Round r of the P
+//                     slots covers the P contiguous pixels [r P, r P + P) of the workgroup's chunk, so a TILE of R rounds is a contiguous run
+//                     of R P <= 256 pixels; two tile buffers (the next tile's global loads fly under this tile's arithmetic), one barrier per
+//                     tile.  Every lane sees the same operand bits and does the same operations in the same order: the same bytes.
+//     kLmaStageOperands  x y ux uy alpha alpha_k (48 B): the data path alone (measurements; the own-iterate kernels only)
+//     kLmaStageProducts  + xy, x x + 1, y y + 1 (72 B: a 64-byte part and a plane of y y + 1, so that every read is aligned)
+//     kLmaStageBeta      x y ux uy beta xy xx1 yy1 (64 B), where k is the same number for every hypothesis of the launch (`k_uniform`: the
+//                        minimal solver without the k estimation leaves k = +0.0 in every hypothesis, a failed one included --
+//                        minimal9_body: k is only assigned under use_alpha_k)
+enum { kLmaPerLane = 0, kLmaStageOperands = 1, kLmaStageProducts = 2, kLmaStageBeta = 3 };
+constexpr int kLmaTile = kLB;  // pixels of a tile at most (one staging thread each)
+constexpr int kLmaStageMinT = 16;  // hypotheses per group from which rsdsfm_set_lma_operands(0) stages (lma_pass_launch)
+template <int STG>
+struct LmaStageDims {
+    static constexpr int head = STG == kLmaStageOperands ? 6 : 8;          // doubles of a record's 16-byte aligned part
+    static constexpr int rec = STG == kLmaStageProducts ? 9 : head;        // doubles per pixel
+    static constexpr int buf = kLmaTile * rec;                             // doubles per tile buffer
+    static constexpr int part = kLB * (kLmaSlots + 1);                     // the partial sums behind the loop share the storage
+    static constexpr int words = STG == kLmaPerLane ? part : (2 * buf > part ? 2 * buf : part);
+};
+struct LmaRec {
+    double2 a, b, c, d;
+    double e;
+};
+template <int STG>
+__device__ __forceinline__ void lma_stage_store(double* __restrict__ buf, int j, const PixIn& p, double k_uniform, double two_over_uniform) {
+    double2* __restrict__ h = reinterpret_cast<double2*>(buf) + j * (LmaStageDims<STG>::head / 2);
+    h[0] = make_double2(p.x, p.y);
+    h[1] = make_double2(p.ux, p.uy);
+    if (STG == kLmaStageOperands) {
+        h[2] = make_double2(p.al, p.ak);
+        return;
+    }
+    double xy, xx1, yy1;
+    lma_products(p.x, p.y, xy, xx1, yy1);
+    if (STG == kLmaStageProducts) {
+        h[2] = make_double2(p.al, p.ak);
+        h[3] = make_double2(xy, xx1);
+        buf[kLmaTile * 8 + j] = yy1;
+    } else {
+        h[2] = make_double2(lma_beta(p.al, p.ak, k_uniform, two_over_uniform), xy);
+        h[3] = make_double2(xx1, yy1);
+    }
+}
+template <int STG>
+__device__ __forceinline__ LmaRec lma_stage_read(const double* __restrict__ buf, int j) {
+    const double2* __restrict__ h = reinterpret_cast<const double2*>(buf) + j * (LmaStageDims<STG>::head / 2);
+    LmaRec r;
+    r.a = h[0], r.b = h[1], r.c = h[2];
+    r.d = STG == kLmaStageOperands ? make_double2(0.0, 0.0) : h[3];
+    r.e = STG == kLmaStageProducts ? buf[kLmaTile * 8 + j] : 0.0;
+    return r;
+}
+template <int STG>
+__device__ __forceinline__ LmaPx lma_stage_pixel(const LmaRec& r, const Pose& pose, double two_over) {
+    if (STG == kLmaStageOperands) return lma_pixel(r.a.x, r.a.y, r.b.x, r.b.y, r.c.x, r.c.y, pose, two_over);
+    if (STG == kLmaStageProducts) return lma_pixel(r.a.x, r.a.y, r.b.x, r.b.y, lma_beta(r.c.x, r.c.y, pose.k, two_over), r.d.x, r.d.y, r.e, pose);
+    return lma_pixel(r.a.x, r.a.y, r.b.x, r.b.y, r.c.x, r.c.y, r.d.x, r.d.y, pose);
+}
+
+template <int NC, bool ERR, bool OWN, int STG>
 __device__ __forceinline__ void lma_pass_body(const double2* __restrict__ q, const double2* __restrict__ u, const double* __restrict__ alpha,
                                               const double* __restrict__ alpha_k, int64_t n, const double* __restrict__ hyp, int T, const LmaCand& cd,
                                               double* __restrict__ partials, int* __restrict__ irr_count, int* __restrict__ irr_list, int64_t chunk,
-                                              unsigned long long* __restrict__ clk_probe, int clk_bid, int Tg, int nwg, const int* __restrict__ pred_steps) {
+                                              unsigned long long* __restrict__ clk_probe, int clk_bid, int Tg, int nwg, const int* __restrict__ pred_steps,
+                                              double k_uniform) {
     static_assert(!OWN || NC == 1, "the own-iterate form fuses one iterate");
-    __shared__ double s_part[kLB][kLmaSlots + 1];
+    __shared__ __attribute__((aligned(16))) double s_mem[LmaStageDims<STG>::words];
+    double(*s_part)[kLmaSlots + 1] = reinterpret_cast<double(*)[kLmaSlots + 1]>(s_mem);
     const int g = threadIdx.x;
     // rsdsfm_set_profiling: one lane of one workgroup in the middle of the launch (clk_bid; -1 = off) stamps the shader clock counter and the
     // 100 MHz counter at both ends of its life -- the clock this kernel actually runs at
@@ -95,16 +165,17 @@ __device__ __forceinline__ void lma_pass_body(const double2* __restrict__ q, con
     double es[NC];
 #pragma unroll
     for (int c = 0; c < NC; ++c) cnt[c] = 0, es[c] = 0.0;
-    if (active) {
-        const Pose pose = load_pose(hyp, t);
+    // (a lane without a hypothesis takes part in the staged forms' tile loads and barriers only)
+    if (active || STG != kLmaPerLane) {
+        Pose pose = {};
+        if (active) pose = load_pose(hyp, t);
         const double two_over = 2.0 / (2.0 + pose.k);
-        const double phi2_own = OWN ? (lma_own_index(cd, pred_steps[t]) ? cd.phi2[1] : cd.phi2[0]) : 0.0;
+        const double phi2_own = OWN && active ? (lma_own_index(cd, pred_steps[t]) ? cd.phi2[1] : cd.phi2[0]) : 0.0;
         // one pixel under this lane's hypothesis; returns whether it goes to the list.  Straight-line on purpose (no branch around the square
         // roots: the error of a pixel that is not an inlier is multiplied by a 0.0 mask instead of being skipped -- the argument is floored into
         // the core's range first, so the product is exact and the sum has the same bits), so that the two pixels of an iteration form ONE basic
         // block and their chains interleave
-        auto pixel = [&](const PixIn& px) -> bool {
-            const LmaPx v = lma_pixel(px.x, px.y, px.ux, px.uy, px.al, px.ak, pose, two_over);
+        auto sums = [&](const LmaPx& v) -> bool {
             A += v.a;
             B += v.ge;
             C = __builtin_fma(v.e0, v.e0, C);
@@ -132,28 +203,80 @@ __device__ __forceinline__ void lma_pass_body(const double2* __restrict__ q, con
         };
         // whole rounds of the P slots: a uniform trip count (every workgroup but the last owns a multiple of P pixels), the next pixel's
         // loads in flight under this pixel's arithmetic; then the ragged round of the last workgroup
-        const int rounds = len / P;
-        unsigned i = (unsigned)slot;
         const unsigned uP = (unsigned)P;
-        // (two register sets: the loads of one pixel fly under the arithmetic of the other, and no copies between them)
-        PixIn pa, pb;
-        int r = 0;
-        if (rounds > 0) pa = load_pix(qb, ub, ab, akb, i);
-        for (; r + 1 < rounds; r += 2, i += 2 * uP) {
-            pb = load_pix(qb, ub, ab, akb, i + uP);
-            const bool la = pixel(pa);
-            pa = load_pix(qb, ub, ab, akb, r + 2 < rounds ? i + 2 * uP : i);  // (no branch between the two pixels: past the end, a pixel that is not used)
-            const bool lb = pixel(pb);
-            if (la || lb) {
-                if (la) push(i);
-                if (lb) push(i + uP);
+        if constexpr (STG == kLmaPerLane) {
+            auto pixel = [&](const PixIn& px) -> bool { return sums(lma_pixel(px.x, px.y, px.ux, px.uy, px.al, px.ak, pose, two_over)); };
+            const int rounds = len / P;
+            unsigned i = (unsigned)slot;
+            // (two register sets: the loads of one pixel fly under the arithmetic of the other, and no copies between them)
+            PixIn pa, pb;
+            int r = 0;
+            if (rounds > 0) pa = load_pix(qb, ub, ab, akb, i);
+            for (; r + 1 < rounds; r += 2, i += 2 * uP) {
+                pb = load_pix(qb, ub, ab, akb, i + uP);
+                const bool la = pixel(pa);
+                pa = load_pix(qb, ub, ab, akb, r + 2 < rounds ? i + 2 * uP : i);  // (no branch between the two pixels: past the end, a pixel that is not used)
+                const bool lb = pixel(pb);
+                if (la || lb) {
+                    if (la) push(i);
+                    if (lb) push(i + uP);
+                }
             }
+            if (r < rounds) {
+                if (pixel(pa)) push(i);
+                i += uP;
+            }
+            if (i < (unsigned)len && pixel(load_pix(qb, ub, ab, akb, i))) push(i);
+        } else {
+            // tiles of R rounds (an even R where there are two: the pairs of rounds never straddle a tile); the last tile is the ragged one
+            constexpr int BUF = LmaStageDims<STG>::buf;
+            const int R0 = kLmaTile / P, R = R0 > 1 ? (R0 & ~1) : 1;
+            const int tile = R * P;  // (<= 256: thread g stages pixel g of a tile)
+            const int ntiles = (len + tile - 1) / tile;
+            const double two_over_uniform = 2.0 / (2.0 + k_uniform);  // (the lanes' expression on the lanes' operand: the same bits)
+            auto pixel = [&](const LmaRec& rc) -> bool { return sums(lma_stage_pixel<STG>(rc, pose, two_over)); };
+            PixIn sp = {};
+            if (g < min(tile, len)) {
+                sp = load_pix(qb, ub, ab, akb, (unsigned)g);
+                lma_stage_store<STG>(s_mem, g, sp, k_uniform, two_over_uniform);
+            }
+            for (int k = 0; k < ntiles; ++k) {
+                __syncthreads();  // tile k is written; tile k - 1, whose buffer tile k + 1 goes to, is read
+                const int base = k * tile, m = min(tile, len - base);
+                const bool stage = g < min(tile, len - base - tile);  // pixel g of the next tile: its loads fly under this tile's arithmetic
+                if (stage) sp = load_pix(qb, ub, ab, akb, (unsigned)(base + tile + g));
+                if (active) {
+                    const double* __restrict__ cur = s_mem + (k & 1) * BUF;
+                    const int rounds = m / P;
+                    unsigned j = (unsigned)slot;
+                    LmaRec pa, pb;
+                    int r = 0;
+                    // (CARRY: the first record of the next iteration is read under this one's second pixel, as the per-lane form loads it; the
+                    // forms with two or three error sums have no registers left for a record across the back edge and read both at the top)
+                    constexpr bool CARRY = !(ERR && NC >= 2);
+                    if (CARRY && rounds > 0) pa = lma_stage_read<STG>(cur, j);
+                    for (; r + 1 < rounds; r += 2, j += 2 * uP) {
+                        if (!CARRY) pa = lma_stage_read<STG>(cur, j);
+                        pb = lma_stage_read<STG>(cur, j + uP);
+                        const bool la = pixel(pa);
+                        if (CARRY) pa = lma_stage_read<STG>(cur, r + 2 < rounds ? j + 2 * uP : j);
+                        const bool lb = pixel(pb);
+                        if (la || lb) {
+                            if (la) push((unsigned)base + j);
+                            if (lb) push((unsigned)base + j + uP);
+                        }
+                    }
+                    if (r < rounds) {
+                        if (!CARRY) pa = lma_stage_read<STG>(cur, j);
+                        if (pixel(pa)) push((unsigned)base + j);
+                        j += uP;
+                    }
+                    if (j < (unsigned)m && pixel(lma_stage_read<STG>(cur, j))) push((unsigned)base + j);
+                }
+                if (stage) lma_stage_store<STG>(s_mem + ((k + 1) & 1) * BUF, g, sp, k_uniform, two_over_uniform);
+            }
+            __syncthreads();  // (the partial sums below take the tile buffers' storage)
         }
-        if (r < rounds) {
-            if (pixel(pa)) push(i);
-            i += uP;
-        }
-        if (i < (unsigned)len && pixel(load_pix(qb, ub, ab, akb, i))) push(i);
     }
     // the P slots of a hypothesis, in slot order
     s_part[g][0] = A, s_part[g][1] = B, s_part[g][2] = C, s_part[g][3] = D, s_part[g][4] = E, s_part[g][kLmaG] = G;
@@ -175,23 +298,32 @@ __device__ __forceinline__ void lma_pass_body(const double2* __restrict__ q, con
     }
 }
 
+#define RSDSFM_LMA_PASS_PARAMS                                                                                                                        \
+    const double2 *__restrict__ q, const double2 *__restrict__ u, const double *__restrict__ alpha, const double *__restrict__ alpha_k, int64_t n,     \
+        const double *__restrict__ hyp, int T, const LmaCand cd, double *__restrict__ partials, int *__restrict__ irr_count, int *__restrict__ irr_list, \
+        int64_t chunk, unsigned long long *__restrict__ clk_probe, int clk_bid, int Tg, int nwg
+#define RSDSFM_LMA_PASS_ARGS q, u, alpha, alpha_k, n, hyp, T, cd, partials, irr_count, irr_list, chunk, clk_probe, clk_bid, Tg, nwg
 template <int NC, bool ERR>
-__global__ __launch_bounds__(kLB) __attribute__((amdgpu_waves_per_eu(4, 5))) void ransac_lma_kernel(const double2* __restrict__ q, const double2* __restrict__ u, const double* __restrict__ alpha,
-                                                        const double* __restrict__ alpha_k, int64_t n, const double* __restrict__ hyp, int T,
-                                                        const LmaCand cd, double* __restrict__ partials, int* __restrict__ irr_count,
-                                                        int* __restrict__ irr_list, int64_t chunk, unsigned long long* __restrict__ clk_probe, int clk_bid,
-                                                        int Tg, int nwg) {
-    lma_pass_body<NC, ERR, false>(q, u, alpha, alpha_k, n, hyp, T, cd, partials, irr_count, irr_list, chunk, clk_probe, clk_bid, Tg, nwg, nullptr);
+__global__ __launch_bounds__(kLB) __attribute__((amdgpu_waves_per_eu(4, 5))) void ransac_lma_kernel(RSDSFM_LMA_PASS_PARAMS) {
+    lma_pass_body<NC, ERR, false, kLmaPerLane>(RSDSFM_LMA_PASS_ARGS, nullptr, 0.0);
 }
 // cd: the TWO candidate iterates (nc = 2), of which every hypothesis fuses its own
 template <bool ERR>
-__global__ __launch_bounds__(kLB) __attribute__((amdgpu_waves_per_eu(4, 5))) void ransac_lma_own_kernel(const double2* __restrict__ q, const double2* __restrict__ u, const double* __restrict__ alpha,
-                                                        const double* __restrict__ alpha_k, int64_t n, const double* __restrict__ hyp, int T,
-                                                        const LmaCand cd, double* __restrict__ partials, int* __restrict__ irr_count,
-                                                        int* __restrict__ irr_list, int64_t chunk, unsigned long long* __restrict__ clk_probe, int clk_bid,
-                                                        int Tg, int nwg, const int* __restrict__ pred_steps) {
-    lma_pass_body<1, ERR, true>(q, u, alpha, alpha_k, n, hyp, T, cd, partials, irr_count, irr_list, chunk, clk_probe, clk_bid, Tg, nwg, pred_steps);
+__global__ __launch_bounds__(kLB) __attribute__((amdgpu_waves_per_eu(4, 5))) void ransac_lma_own_kernel(RSDSFM_LMA_PASS_PARAMS, const int* __restrict__ pred_steps) {
+    lma_pass_body<1, ERR, true, kLmaPerLane>(RSDSFM_LMA_PASS_ARGS, pred_steps, 0.0);
 }
+// the staged forms of the two (the tile buffers leave room for four workgroups per CU: four waves per SIMD, 128 VGPRs)
+template <int NC, bool ERR, int STG>
+__global__ __launch_bounds__(kLB) __attribute__((amdgpu_waves_per_eu(4, 4))) void ransac_lma_staged_kernel(RSDSFM_LMA_PASS_PARAMS, double k_uniform) {
+    lma_pass_body<NC, ERR, false, STG>(RSDSFM_LMA_PASS_ARGS, nullptr, k_uniform);
+}
+template <bool ERR, int STG>
+__global__ __launch_bounds__(kLB) __attribute__((amdgpu_waves_per_eu(4, 4))) void ransac_lma_staged_own_kernel(RSDSFM_LMA_PASS_PARAMS, const int* __restrict__ pred_steps,
+                                                                                                         double k_uniform) {
+    lma_pass_body<1, ERR, true, STG>(RSDSFM_LMA_PASS_ARGS, pred_steps, k_uniform);
+}
+#undef RSDSFM_LMA_PASS_PARAMS
+#undef RSDSFM_LMA_PASS_ARGS
 
 // flags: the RANSAC's flag words (ransac_host.hip): [1] += hypotheses that ended where no score was fused (+ their list), [3] |= 2 a guard
 // tripped (the run starts over on the iterate-by-iterate kernels), [4 + min(steps, 3)] histogram of the accepted steps
@@ -393,27 +525,60 @@ int64_t ransac_lma_partials_doubles(const Ctx* c, int64_t n, int batch) {
 }
 size_t ransac_lma_list_ints(int batch) { return (size_t)batch * kLmaListCap; }
 
+// the kernel of a pass: own-iterate or nc fused iterates, counts only or with the error sums, and where the operands come from
+template <int STG>
+static const void* lma_pass_kernel(bool own, bool count_only, int nc) {
+#define RSDSFM_FN(...) reinterpret_cast<const void*>(&__VA_ARGS__)
+    if constexpr (STG == kLmaPerLane) {
+        if (own) return count_only ? RSDSFM_FN(ransac_lma_own_kernel<false>) : RSDSFM_FN(ransac_lma_own_kernel<true>);
+        if (count_only) return nc == 1 ? RSDSFM_FN(ransac_lma_kernel<1, false>) : nc == 2 ? RSDSFM_FN(ransac_lma_kernel<2, false>) : RSDSFM_FN(ransac_lma_kernel<3, false>);
+        return nc == 1 ? RSDSFM_FN(ransac_lma_kernel<1, true>) : nc == 2 ? RSDSFM_FN(ransac_lma_kernel<2, true>) : RSDSFM_FN(ransac_lma_kernel<3, true>);
+    } else {
+        if (own) return count_only ? RSDSFM_FN(ransac_lma_staged_own_kernel<false, STG>) : RSDSFM_FN(ransac_lma_staged_own_kernel<true, STG>);
+        if constexpr (STG == kLmaStageOperands) return nullptr;  // (the measurement form: own-iterate kernels only)
+        else {
+            if (count_only)
+                return nc == 1 ? RSDSFM_FN(ransac_lma_staged_kernel<1, false, STG>) : nc == 2 ? RSDSFM_FN(ransac_lma_staged_kernel<2, false, STG>) : RSDSFM_FN(ransac_lma_staged_kernel<3, false, STG>);
+            return nc == 1 ? RSDSFM_FN(ransac_lma_staged_kernel<1, true, STG>) : nc == 2 ? RSDSFM_FN(ransac_lma_staged_kernel<2, true, STG>) : RSDSFM_FN(ransac_lma_staged_kernel<3, true, STG>);
+        }
+    }
+#undef RSDSFM_FN
+}
+
+// k_uniform: every hypothesis of `hyp` carries k = k_value (the callers that ran the minimal solver without the k estimation know it)
 static int lma_pass_launch(Ctx* c, const double* q, const double* u, const double* a, const double* ak, int64_t n, const double* hyp, int T,
                            const LmaCand& cd, double* partials, int* irr_count, int* irr_list, int* grid_out, unsigned long long* clk = nullptr,
-                           const int* pred_steps = nullptr) {
-    // resident workgroups per CU of the kernel that is about to run (registers set it: 5 at 94 VGPRs); slot 0: the own-iterate form
-    static int occ_tab[2][kLmaNC + 1] = {{0, 0, 0, 0}, {0, 0, 0, 0}};
-    const int nc = pred_steps ? 0 : std::min(std::max(cd.nc, 1), (int)kLmaNC);
-    int* occ = occ_tab[cd.count_only ? 1 : 0];
-    if (occ[nc] == 0) {
+                           const int* pred_steps = nullptr, bool k_uniform = false, double k_value = 0.0) {
+    const bool own = pred_steps != nullptr;
+    const int nc = std::min(std::max(cd.nc, 1), (int)kLmaNC);
+    // where the operands come from (Ctx::lma_operands); RSDSFM_LMA_STAGE (experiments, for programs that do not call the switch): 0 = per lane,
+    // 1 = the six operands alone (own-iterate pass), 2 = never beta
+    static const int stage_override = getenv("RSDSFM_LMA_STAGE") ? atoi(getenv("RSDSFM_LMA_STAGE")) : -1;
+    // (mode 0 stages where a slot has enough lanes to share a record: a tile is R = 256 / P ~ Tg rounds, so with few hypotheses per group a lane
+    // meets a barrier and a staging step every few pixels, and there is little to share -- measured, T = 5: 22.7 us per lane, 25.5 us staged)
+    int groups = 1;
+    int Tg = ransac_lma_group_size(T, &groups);
+    const bool staged = stage_override != 0 && (c->lma_operands == 2 || (c->lma_operands == 0 && Tg >= kLmaStageMinT));
+    int stg = !staged ? kLmaPerLane : k_uniform ? kLmaStageBeta : kLmaStageProducts;
+    if (stg != kLmaPerLane && stage_override == 2) stg = kLmaStageProducts;
+    if (stg != kLmaPerLane && stage_override == 1 && own) stg = kLmaStageOperands;
+    const void* fn = stg == kLmaPerLane         ? lma_pass_kernel<kLmaPerLane>(own, cd.count_only != 0, nc)
+                     : stg == kLmaStageOperands ? lma_pass_kernel<kLmaStageOperands>(own, cd.count_only != 0, nc)
+                     : stg == kLmaStageProducts ? lma_pass_kernel<kLmaStageProducts>(own, cd.count_only != 0, nc)
+                                                : lma_pass_kernel<kLmaStageBeta>(own, cd.count_only != 0, nc);
+    // resident workgroups per CU of the kernel that is about to run (registers and, for the staged forms, the tile buffers set it); slot 0: the
+    // own-iterate form
+    static int occ_tab[4][2][kLmaNC + 1] = {};
+    int& occ = occ_tab[stg][cd.count_only ? 1 : 0][own ? 0 : nc];
+    if (occ == 0) {
         int nb = 0;
-        const void* fn = pred_steps ? (cd.count_only ? reinterpret_cast<const void*>(&ransac_lma_own_kernel<false>) : reinterpret_cast<const void*>(&ransac_lma_own_kernel<true>))
-                         : cd.count_only ? (nc == 1 ? reinterpret_cast<const void*>(&ransac_lma_kernel<1, false>) : nc == 2 ? reinterpret_cast<const void*>(&ransac_lma_kernel<2, false>) : reinterpret_cast<const void*>(&ransac_lma_kernel<3, false>))
-                                       : (nc == 1 ? reinterpret_cast<const void*>(&ransac_lma_kernel<1, true>) : nc == 2 ? reinterpret_cast<const void*>(&ransac_lma_kernel<2, true>) : reinterpret_cast<const void*>(&ransac_lma_kernel<3, true>));
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, kLB, 0) != hipSuccess || nb < 1) nb = 4;
-        occ[nc] = nb;
+        occ = nb;
     }
     int64_t chunk;
     static const int grid_override = getenv("RSDSFM_LMA_BLOCKS_PER_CU") ? atoi(getenv("RSDSFM_LMA_BLOCKS_PER_CU")) : 0;  // (experiments)
-    int groups = 1;
-    const int Tg = ransac_lma_group_size(T, &groups);
     // (the resident workgroups are shared by the groups: every group gets 1 / groups of one round of the chip)
-    const int per_cu = std::max(1, (grid_override > 0 ? grid_override : occ[nc]));
+    const int per_cu = std::max(1, (grid_override > 0 ? grid_override : occ));
     int nwg = ransac_lma_grid(c, n, Tg, &chunk, per_cu);
     if (groups > 1) {
         const int64_t cap = std::max<int64_t>(1, (int64_t)c->num_cus * std::min(per_cu, 8) / groups);
@@ -428,22 +593,14 @@ static int lma_pass_launch(Ctx* c, const double* q, const double* u, const doubl
     *grid_out = nwg;  // (workgroups PER HYPOTHESIS: what the rows stages index the partials with)
     const double2* q2 = reinterpret_cast<const double2*>(q);
     const double2* u2 = reinterpret_cast<const double2*>(u);
-    const int clk_bid = clk ? grid / 2 : -1;
-#define RSDSFM_LMA_LAUNCH(NC, ERR) \
-    hipLaunchKernelGGL((ransac_lma_kernel<NC, ERR>), dim3(grid), dim3(kLB), 0, c->stream, q2, u2, a, ak, n, hyp, T, cd, partials, irr_count, irr_list, chunk, clk, clk_bid, Tg, nwg)
-    if (pred_steps) {
-        if (cd.count_only)
-            hipLaunchKernelGGL((ransac_lma_own_kernel<false>), dim3(grid), dim3(kLB), 0, c->stream, q2, u2, a, ak, n, hyp, T, cd, partials, irr_count, irr_list, chunk, clk, clk_bid, Tg, nwg, pred_steps);
-        else
-            hipLaunchKernelGGL((ransac_lma_own_kernel<true>), dim3(grid), dim3(kLB), 0, c->stream, q2, u2, a, ak, n, hyp, T, cd, partials, irr_count, irr_list, chunk, clk, clk_bid, Tg, nwg, pred_steps);
-    } else if (cd.count_only) {
-        if (cd.nc == 1) RSDSFM_LMA_LAUNCH(1, false);
-        else if (cd.nc == 2) RSDSFM_LMA_LAUNCH(2, false);
-        else RSDSFM_LMA_LAUNCH(3, false);
-    } else if (cd.nc == 1) RSDSFM_LMA_LAUNCH(1, true);
-    else if (cd.nc == 2) RSDSFM_LMA_LAUNCH(2, true);
-    else RSDSFM_LMA_LAUNCH(3, true);
-#undef RSDSFM_LMA_LAUNCH
+    int clk_bid = clk ? grid / 2 : -1;
+    LmaCand cdv = cd;
+    // (the kernels' parameter lists: the sixteen they share, then pred_steps for the own-iterate forms, then k_uniform for the staged ones)
+    void* args[18] = {&q2, &u2, &a, &ak, &n, &hyp, &T, &cdv, &partials, &irr_count, &irr_list, &chunk, &clk, &clk_bid, &Tg, &nwg, nullptr, nullptr};
+    int na = 16;
+    if (own) args[na++] = &pred_steps;
+    if (stg != kLmaPerLane) args[na++] = &k_value;
+    RSDSFM_HIP_CHECK(c, hipLaunchKernel(fn, dim3(grid), dim3(kLB), args, 0, c->stream));
     RSDSFM_HIP_CHECK(c, hipGetLastError());
     return RSDSFM_OK;
 }
@@ -452,14 +609,15 @@ static int lma_pass_launch(Ctx* c, const double* q, const double* u, const doubl
 int ransac_lma_launch(Ctx* c, const double* q, const double* u, const double* a, const double* ak, int64_t n, const double* hyp, int T,
                       LmState* states, double* partials, int* flags, int* scored, double* trial_count, double* trial_err, double tol,
                       const int* cand_steps, int ncand, int* irr_count, int* irr_list, int* unscored_list, int* guard_word, const int* m9_core_flag,
-                      int m9_core_epoch, bool count_only, const int* pred_steps, unsigned long long* pred_stats, bool pred_discard) {
+                      int m9_core_epoch, bool count_only, const int* pred_steps, unsigned long long* pred_stats, bool pred_discard, bool k_uniform,
+                      double k_value) {
     if (T < 1 || T > kLB) return fail(c, RSDSFM_ERR_INVALID, "hypothesis batch of the analytic pass exceeds 256");
     if (pred_steps && ncand != 2) return fail(c, RSDSFM_ERR_INVALID, "the own-iterate pass chooses between two candidate iterates");
     const LmaCand cd = lma_candidates(cand_steps, ncand, tol, count_only);
     int grid = 0;
     const bool prof = c->profile && c->ev_prof[0] && c->ev_prof[1];
     if (prof) RSDSFM_HIP_CHECK(c, hipEventRecord(c->ev_prof[0], c->stream));
-    int rc = lma_pass_launch(c, q, u, a, ak, n, hyp, T, cd, partials, irr_count, irr_list, &grid, prof ? c->d_clk_probe : nullptr, pred_steps);
+    int rc = lma_pass_launch(c, q, u, a, ak, n, hyp, T, cd, partials, irr_count, irr_list, &grid, prof ? c->d_clk_probe : nullptr, pred_steps, k_uniform, k_value);
     if (rc != RSDSFM_OK) return rc;
     if (prof) {
         RSDSFM_HIP_CHECK(c, hipEventRecord(c->ev_prof[1], c->stream));

@@ -224,6 +224,10 @@ struct Ctx {
     // hypothesis ends and its pixel pass fuses that iterate alone (ransac_lma_own_kernel), 1 = the two-iterate pass, 2 = mode 0 with the
     // prediction inverted and the pass's scores discarded (tests: every hypothesis takes the scoring pass).  Same outputs of the frame solve in every mode.
     int frame_predict = 0;
+    // rsdsfm_set_lma_operands: 0 = the analytic pixel pass forms each pixel's operands once per workgroup (one staging thread per pixel leaves a
+    // record in LDS, the pixel's lanes read it) where a group has kLmaStageMinT hypotheses or more, 1 = every lane loads its pixel's operands from
+    // global memory, 2 = 0 for every hypothesis count (tests).  Same bytes in every mode.
+    int lma_operands = 0;
     unsigned long long* d_flat_counters = nullptr;  // the two counters of minimal9_flatten_kernel (zero between launches)
     int seq_lanes = 0;               // rsdsfm_set_sequence_lanes (0 = kSequenceLanesDefault)
     // where the refinement's single-workgroup stage runs (rsdsfm_set_refine_stage): 0 = automatic -- in the prologue of the next slot's pass
@@ -483,7 +487,8 @@ int ransac_lma_launch(Ctx* c, const double* q, const double* u, const double* a,
                       LmState* states, double* partials, int* flags, int* scored, double* trial_count, double* trial_err, double tol,
                       const int* cand_steps, int ncand, int* irr_count, int* irr_list, int* unscored_list, int* guard_word,
                       const int* m9_core_flag = nullptr, int m9_core_epoch = 0, bool count_only = false, const int* pred_steps = nullptr,
-                      unsigned long long* pred_stats = nullptr, bool pred_discard = false);  // pred_steps != null: the own-iterate pass (cand_steps: the two candidates); pred_discard: none of its scores is taken
+                      unsigned long long* pred_stats = nullptr, bool pred_discard = false,  // pred_steps != null: the own-iterate pass (cand_steps: the two candidates); pred_discard: none of its scores is taken
+                      bool k_uniform = false, double k_value = 0.0);  // k_uniform: every hypothesis of `hyp` carries k = k_value (the staged pass then stages beta)
 int ransac_lma_rows_doubles();
 int ransac_lma_rows_launch(Ctx* c, const double* q, const double* u, const double* a, const double* ak, int64_t n, const double* hyp, int T,
                            double* partials, double tol, const int* cand_steps, int ncand, int* irr_count, int* irr_list, double* rows);
