@@ -135,10 +135,11 @@ class RansacOut(C.Structure):
 
 
 def declared_symbols():
-    """Names of every function include/rsdsfm.h, include/rsdsfm_retime.h and include/rsdsfm_shutter.h declare (used by the CPU symbol-export test)."""
+    """Names of every function include/rsdsfm.h, include/rsdsfm_retime.h, include/rsdsfm_shutter.h and include/rsdsfm_denoise.h declare (used by
+    the CPU symbol-export test)."""
     import re
 
-    txt = "".join(open(os.path.join(os.path.dirname(HEADER_PATH), name)).read() for name in (os.path.basename(HEADER_PATH), "rsdsfm_retime.h", "rsdsfm_shutter.h"))
+    txt = "".join(open(os.path.join(os.path.dirname(HEADER_PATH), name)).read() for name in (os.path.basename(HEADER_PATH), "rsdsfm_retime.h", "rsdsfm_shutter.h", "rsdsfm_denoise.h"))
     txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
     return sorted(set(re.findall(r"\b(rsdsfm_[a-z0-9_]+)\s*\(", txt)))
 
@@ -2995,6 +2996,160 @@ class _ShutterMixin:
 
 
 for _name, _fn in list(vars(_ShutterMixin).items()):
+    if not _name.startswith("__"):
+        setattr(Solver, _name, _fn)
+
+
+# ---------------------------------------------------------------------------------------------------
+# the temporal denoise: a frame averaged with its registered neighbours, patch-weighted (include/rsdsfm_denoise.h)
+# ---------------------------------------------------------------------------------------------------
+DENOISE_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "rsdsfm_denoise.h")
+DENOISE_RADIUS_MAX = 7
+DENOISE_LAYERS_MAX = 14
+
+
+class DenoiseParams(C.Structure):
+    _fields_ = [("radius", C.c_int32), ("strength", C.c_int32), ("gain_mode", C.c_int32), ("occlusion", C.c_int32), ("occlusion_tol_q16", C.c_int32),
+                ("struct_bytes", C.c_int32), ("min_overlap", C.c_int64), ("reserved", C.c_int32 * 4)]
+
+
+def denoise_declared_symbols():
+    """Names of every function include/rsdsfm_denoise.h declares"""
+    import re
+
+    txt = open(DENOISE_HEADER_PATH).read()
+    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
+    return sorted(set(re.findall(r"\b(rsdsfm_[a-z0-9_]+)\s*\(", txt)))
+
+
+def _denoise_params(radius=None, strength=None, gain=True, occlusion=False, occlusion_tol_q16=0, min_overlap=None):
+    """a DenoiseParams with the given values over the defaults (None: the default)"""
+    p = DenoiseParams()
+    if load_library().rsdsfm_denoise_params_init(C.byref(p)) != OK:
+        raise RsdsfmError("rsdsfm_denoise_params_init failed")
+    if radius is not None:
+        p.radius = int(radius)
+    if strength is not None:
+        p.strength = int(strength)
+    if min_overlap is not None:
+        p.min_overlap = int(min_overlap)
+    p.gain_mode, p.occlusion, p.occlusion_tol_q16 = 0 if gain else 1, int(occlusion), int(occlusion_tol_q16)
+    return p
+
+
+def denoise_default_params():
+    """the denoise's defaults as a dict: radius = 2, strength = 12, min_overlap = 1024 (rsdsfm_denoise_params_init); choices, not measurements"""
+    p = _denoise_params()
+    return dict(radius=p.radius, strength=p.strength, min_overlap=p.min_overlap, gain_mode=p.gain_mode, occlusion=p.occlusion)
+
+
+def denoise_launches(rows, cols, nsrc):
+    """kernel launches of one denoise_frame_dev call on nsrc sources: nsrc stabilize_window_launches + 2 (nsrc - 1), or + 1 with one source
+    (rsdsfm_denoise_launches; host only)"""
+    n = load_library().rsdsfm_denoise_launches(C.c_int32(rows), C.c_int32(cols), C.c_int32(nsrc))
+    if n < 0:
+        raise RsdsfmError("rsdsfm_denoise_launches failed (%d): rows and cols in [2, 16384], nsrc in [1, 15]" % n)
+    return n
+
+
+def denoise_accumulate_launches():
+    """kernel launches of one denoise_accumulate_dev call: 1 (rsdsfm_denoise_accumulate_launches; host only)"""
+    return int(load_library().rsdsfm_denoise_accumulate_launches())
+
+
+class _DenoiseMixin:
+    def seam_overlap_sums_dev(self, d_image, d_source, d_layer, d_layer_mask, channels, rows, cols, d_sums8):
+        """the seam blend's record as a call of its own (rsdsfm_seam_overlap_sums_dev; tests/stabilize_blend_spec_numpy.py's overlap_sums):
+        d_sums8 (8 device uint64) = [count, sum image_c, sum layer_c, 0 ...] over d_source == 1 under a set layer mask.  Enqueued on the context's
+        stream."""
+        self._check(self.lib.rsdsfm_seam_overlap_sums_dev(self._ctx, _dp(d_image), _dp(d_source), _dp(d_layer), _dp(d_layer_mask), C.c_int32(channels), C.c_int32(rows),
+                                                          C.c_int32(cols), _dp(d_sums8)), "rsdsfm_seam_overlap_sums_dev")
+
+    def denoise_accumulate_dev(self, d_ref, d_ref_mask, d_layer, d_layer_mask, channels, rows, cols, d_cells, first, last, d_sums8=None, min_overlap=0, gain_mode=0,
+                               strength=0, d_image_out=None, d_mask_out=None, d_weight=None, d_counts3=None):
+        """one layer accumulated onto the cells (rsdsfm_denoise_accumulate_dev; tests/denoise_spec_numpy.py): the weight of a layer's pixel falls
+        with the mean absolute difference to the reference over its 3 x 3 patch, 16 at none, 0 at `strength` per channel.  d_layer = d_layer_mask
+        = None: no layer (first and last).  d_sums8: the layer's record (seam_overlap_sums_dev), None: no gain.  first: the cells are set from
+        the reference; last: the cells are not written, the mean goes to d_image_out, 1 to d_mask_out where anything counted, the summed weight
+        to d_weight and [unset, own only, averaged] to d_counts3 (three device int64).  At most 14 layers.  Enqueued on the context's stream."""
+        self._check(self.lib.rsdsfm_denoise_accumulate_dev(self._ctx, _dp(d_ref), _dp(d_ref_mask), _np0(d_layer), _np0(d_layer_mask), C.c_int32(channels), C.c_int32(rows),
+                                                           C.c_int32(cols), _np0(d_sums8), C.c_int64(min_overlap), C.c_int32(gain_mode), C.c_int32(strength), _np0(d_cells),
+                                                           C.c_int32(int(first)), C.c_int32(int(last)), _np0(d_image_out), _np0(d_mask_out), _np0(d_weight),
+                                                           _np0(d_counts3)), "rsdsfm_denoise_accumulate_dev")
+
+    def denoise_accumulate(self, ref, ref_mask, layers, records=None, min_overlap=0, gain_mode=0, strength=0, device=0):
+        """host convenience around denoise_accumulate_dev: the reference (image, mask), layers a list of 0 .. 14 (image, mask) pairs of host
+        arrays, records None or one 8-word record (or None) per layer
+        -> (image, mask, weight (rows, cols) uint8, counts (3,) int64 [unset, own only, averaged])"""
+        import torch
+
+        ref = np.ascontiguousarray(ref, dtype=np.uint8)
+        rows, cols = ref.shape[:2]
+        ch = 1 if ref.ndim == 2 else ref.shape[2]
+        dev = torch.device("cuda", device)
+        with torch.cuda.device(dev):
+            up = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.uint8)).to(dev)
+            d_ref, d_rm = up(ref), up(ref_mask)
+            d_l = [(up(i), up(m)) for i, m in layers]
+            d_rec = [None if records is None or records[j] is None else torch.from_numpy(np.ascontiguousarray(records[j], dtype=np.uint64).view(np.int64)).to(dev)
+                     for j in range(len(layers))]
+            d_cells = torch.empty((rows, cols, ch + 1), dtype=torch.int16, device=dev)
+            d_out, d_mask = torch.empty_like(d_ref), torch.empty((rows, cols), dtype=torch.uint8, device=dev)
+            d_w, d_cnt = torch.empty_like(d_mask), torch.zeros(3, dtype=torch.int64, device=dev)
+            torch.cuda.synchronize()
+            outs = dict(d_image_out=d_out.data_ptr(), d_mask_out=d_mask.data_ptr(), d_weight=d_w.data_ptr(), d_counts3=d_cnt.data_ptr())
+            if not d_l:
+                self.denoise_accumulate_dev(d_ref.data_ptr(), d_rm.data_ptr(), None, None, ch, rows, cols, None, True, True, None, min_overlap, gain_mode, strength, **outs)
+            for j, (d_i, d_m) in enumerate(d_l):
+                self.denoise_accumulate_dev(d_ref.data_ptr(), d_rm.data_ptr(), d_i.data_ptr(), d_m.data_ptr(), ch, rows, cols, d_cells.data_ptr(), j == 0, j == len(d_l) - 1,
+                                            d_rec[j].data_ptr() if d_rec[j] is not None else None, min_overlap, gain_mode, strength, **outs)
+            self.synchronize()
+            return d_out.cpu().numpy(), d_mask.cpu().numpy(), d_w.cpu().numpy(), d_cnt.cpu().numpy()
+
+    def denoise_frame_dev(self, d_images, channels, d_depth_maps, d_R, d_t, K, rows, cols, M, m, d_image, d_mask, d_weight=None, d_counts3=None, strength=None, gain=True,
+                          min_overlap=None, window=None, occlusion=False, occlusion_tol_q16=0, mode=BACKPROJECT_RS, q5_mode=Q5_COMPAT, iterations=0, params=None):
+        """one denoised frame (rsdsfm_denoise_frame_dev): d_images, d_depth_maps, d_R, d_t lists of 1 .. 15 device pointers, source 0 the own
+        frame and the others its neighbours; M (nsrc, 3, 3), m (nsrc, 3) every source's pose in the target camera.  The own frame through
+        stabilize_window_frame_dev, every neighbour alone on the context's layer, seam_overlap_sums_dev and denoise_accumulate_dev per neighbour;
+        the mean into d_image, d_mask, d_weight, d_counts3.  params: a DenoiseParams passed as it is instead of the keywords.  Enqueued on the
+        context's stream."""
+        ns = len(d_images)
+        _need_all(ns, d_depth_maps=d_depth_maps, d_R=d_R, d_t=d_t)
+        Mm, mm = _f64(M).reshape(-1, 9), _f64(m).reshape(-1, 3)
+        if Mm.shape[0] < ns or mm.shape[0] < ns:
+            raise RsdsfmError("denoise_frame_dev: every source needs a pose (M, m)")
+        dp = params if params is not None else _denoise_params(None, strength, gain, occlusion, occlusion_tol_q16, min_overlap)
+        d = C.c_double
+        arr = lambda x: _ptr_array(list(x)[:ns]) if ns else None
+        self._check(self.lib.rsdsfm_denoise_frame_dev(self._ctx, arr(d_images), C.c_int32(channels), arr(d_depth_maps), arr(d_R), arr(d_t), d(K[0]), d(K[1]), d(K[2]), d(K[3]),
+                                                      C.c_int32(rows), C.c_int32(cols), int(mode), int(q5_mode), C.c_int32(iterations), C.c_int32(ns), _p(Mm), _p(mm),
+                                                      C.byref(dp), _window4(window), _dp(d_image), _dp(d_mask), _np0(d_weight), _np0(d_counts3)), "rsdsfm_denoise_frame_dev")
+
+    def denoise_video_dev(self, d_frames, rows, cols, channels, K, d_depth_maps, d_R, d_t, A, c, A_path, c_path, scales, d_out, d_out_masks, d_out_weights=None,
+                          want_counts=True, radius=None, strength=None, gain=True, min_overlap=None, window=None, occlusion=False, occlusion_tol_q16=0,
+                          mode=BACKPROJECT_RS, q5_mode=Q5_COMPAT, iterations=0):
+        """a solved clip denoised (rsdsfm_denoise_video_dev): the clip as retime_video_dev takes it; for every frame q the own pose by
+        retime_poses(t = q), the neighbours within `radius` (None: 2) by neighbour_poses on the same path, and denoise_frame_dev into d_out[q],
+        d_out_masks[q], d_out_weights[q].  A_path = A, c_path = c denoises the rectified frames in place.  Returns dict(); with want_counts
+        counts (nsources, 3) int64 [unset, own only, averaged] -- the call then waits."""
+        ns = len(d_depth_maps)
+        _need_all(ns, d_frames=d_frames, d_R=d_R, d_t=d_t, d_out=d_out, d_out_masks=d_out_masks, d_out_weights=d_out_weights)
+        a, cc, ap, cp = _f64(A).reshape(-1, 9), _f64(c).reshape(-1, 3), _f64(A_path).reshape(-1, 9), _f64(c_path).reshape(-1, 3)
+        sc = _f64(scales).reshape(-1)
+        if min(a.shape[0], cc.shape[0], ap.shape[0], cp.shape[0], sc.shape[0]) < ns:
+            raise RsdsfmError("denoise_video_dev: every source needs a pose on both paths and a scale")
+        dp = _denoise_params(radius, strength, gain, occlusion, occlusion_tol_q16, min_overlap)
+        counts = np.zeros((max(ns, 1), 3), dtype=np.int64) if want_counts else None
+        d = C.c_double
+        arr = lambda x: _ptr_array(list(x)[:ns]) if x is not None and ns else None
+        self._check(self.lib.rsdsfm_denoise_video_dev(self._ctx, arr(d_frames), C.c_int32(ns), C.c_int32(rows), C.c_int32(cols), C.c_int32(channels), d(K[0]), d(K[1]),
+                                                      d(K[2]), d(K[3]), arr(d_depth_maps), arr(d_R), arr(d_t), _p(a), _p(cc), _p(ap), _p(cp), _p(sc), int(mode), int(q5_mode),
+                                                      C.c_int32(iterations), C.byref(dp), _window4(window), arr(d_out), arr(d_out_masks), arr(d_out_weights), _p(counts)),
+                    "rsdsfm_denoise_video_dev")
+        return dict(counts=counts[:ns]) if want_counts else dict()
+
+
+for _name, _fn in list(vars(_DenoiseMixin).items()):
     if not _name.startswith("__"):
         setattr(Solver, _name, _fn)
 

@@ -1,0 +1,30 @@
+// denoise.hpp -- the temporal denoise (include/rsdsfm_denoise.h): what denoise_kernels.hip and denoise_host.hip share.
+#pragma once
+
+#include <stddef.h>
+#include <stdint.h>
+
+#include "../../include/rsdsfm_denoise.h"
+#include "rsdsfm_internal.hpp"
+#include "stabilize_blend.hpp"
+
+namespace rsdsfm {
+
+constexpr int kDenoiseRadiusMax = RSDSFM_DENOISE_RADIUS_MAX;
+constexpr int kDenoiseLayersMax = RSDSFM_DENOISE_LAYERS_MAX;  // 16 (1 + 14) = 240 and 240 * 255 = 61 200 < 65 536: a uint16 sum cannot overflow
+constexpr int kDenoiseSourcesMax = 1 + kDenoiseLayersMax;
+constexpr int kDenoiseStrengthDefault = RSDSFM_DENOISE_STRENGTH_DEFAULT, kDenoiseStrengthMax = 255;
+constexpr unsigned kDenoiseW = 16u;                        // the weight's scale: the own frame counts 16
+constexpr int kDenoiseTileRows = 16, kDenoiseTileCols = 64;  // one workgroup's tile: kBP threads of 4 consecutive pixels of a row
+
+// DenseWs::d_denoise: [reference mask: P][reference source: P][reference image: 3 P][cells: 8 P], P = blend_plane_bytes (a multiple of 8, so
+// the cells are 8-byte aligned); apart from the blend's layer, which the neighbours are rendered onto while the cells hold the sums
+inline size_t denoise_ws_bytes(int rows, int cols) { return 13 * blend_plane_bytes(rows, cols); }
+
+// one step on c->stream (arguments checked by the caller; d_layer and d_lmask both NULL: no layer; d_sums NULL: no gain): the counters zeroed
+// by a memset when passed and `last`, then one launch
+int denoise_accumulate_launch(Ctx* c, const unsigned char* d_ref, const unsigned char* d_rmask, const unsigned char* d_layer, const unsigned char* d_lmask, int channels,
+                              int rows, int cols, const unsigned long long* d_sums, int64_t min_overlap, int gain_mode, int strength, uint16_t* d_cells, bool first,
+                              bool last, unsigned char* d_image_out, unsigned char* d_mask_out, unsigned char* d_weight, int64_t* d_counts3);
+
+}  // namespace rsdsfm

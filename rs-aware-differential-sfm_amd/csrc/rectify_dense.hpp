@@ -23,6 +23,7 @@ struct DenseWs {
     void* d_search = nullptr;         // the visible pre-image search's planes: kbuf (rows x cols uint64) and a zv behind it (stabilize_search.hpp; made when first asked for)
     unsigned char* d_layer2 = nullptr; // the retimer's second layer, mask and image, 4 planes (retime.hpp; made when first asked for)
     unsigned char* d_shutter = nullptr; // the synthetic shutter's sample mask and image and its cells, 12 planes (shutter.hpp; made when first asked for)
+    unsigned char* d_denoise = nullptr; // the temporal denoise's reference mask, source plane and image and its cells, 13 planes (denoise.hpp; made when first asked for)
     int rows = 0, cols = 0;
 };
 

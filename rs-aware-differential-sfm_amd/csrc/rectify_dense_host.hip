@@ -23,6 +23,8 @@ static void dense_ws_free(DenseWs* w) {
     w->d_layer2 = nullptr;
     if (w->d_shutter) (void)hipFree(w->d_shutter);
     w->d_shutter = nullptr;
+    if (w->d_denoise) (void)hipFree(w->d_denoise);
+    w->d_denoise = nullptr;
     w->d_pyr = nullptr;
     w->d_disp = nullptr;
     w->d_mask = nullptr;

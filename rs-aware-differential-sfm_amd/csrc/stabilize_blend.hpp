@@ -31,6 +31,11 @@ inline size_t blend_layer_bytes(int rows, int cols) { return 5 * blend_plane_byt
 // the two launches of the seam distance on c->stream (arguments checked by the caller): rows, then columns; d_h is the row pass's plane
 int seam_distance_launch(Ctx* c, const unsigned char* d_mask, int rows, int cols, int feather, unsigned char* d_h, unsigned char* d_dist);
 
+// the record of one layer on c->stream (arguments checked by the caller): d_sums zeroed by a memset, then the sums launch, which also zeroes
+// the blend's two counters when d_counts is passed; the blend launch's front half and rsdsfm_seam_overlap_sums_dev (denoise_host.hip)
+int seam_overlap_sums_launch(Ctx* c, const unsigned char* d_image, const unsigned char* d_source, const unsigned char* d_layer, const unsigned char* d_lmask, int channels,
+                             int rows, int cols, unsigned long long* d_sums, unsigned long long* d_counts);
+
 // one layer onto the in-out planes on c->stream (arguments checked by the caller): the record zeroed, the sums launch (which also zeroes
 // d_counts), the blend launch
 int seam_blend_launch(Ctx* c, const unsigned char* d_layer, const unsigned char* d_lmask, int channels, int rows, int cols, const unsigned char* d_dist, int feather,

@@ -323,16 +323,25 @@ int seam_distance_launch(Ctx* c, const unsigned char* d_mask, int rows, int cols
     return RSDSFM_OK;
 }
 
-int seam_blend_launch(Ctx* c, const unsigned char* d_layer, const unsigned char* d_lmask, int channels, int rows, int cols, const unsigned char* d_dist, int feather,
-                      int64_t min_overlap, int gain_mode, int source_id, unsigned char* d_image, unsigned char* d_mask, unsigned char* d_source,
-                      unsigned long long* d_sums, int64_t* d_counts) {
+int seam_overlap_sums_launch(Ctx* c, const unsigned char* d_image, const unsigned char* d_source, const unsigned char* d_layer, const unsigned char* d_lmask, int channels,
+                             int rows, int cols, unsigned long long* d_sums, unsigned long long* d_counts) {
     RSDSFM_HIP_CHECK(c, hipMemsetAsync(d_sums, 0, 8 * sizeof(unsigned long long), c->stream));
     const int64_t nb = ((int64_t)rows * cols + (int64_t)kBP * 4 - 1) / ((int64_t)kBP * 4);
     const dim3 grid((unsigned)std::min<int64_t>(nb, 65536));
-    unsigned long long* cnt = reinterpret_cast<unsigned long long*>(d_counts);
     hipLaunchKernelGGL(channels == 3 ? seam_overlap_sums_kernel<3> : seam_overlap_sums_kernel<1>, grid, dim3(kBP), 0, c->stream, d_image, d_source, d_layer, d_lmask, rows,
-                       cols, d_sums, cnt);
+                       cols, d_sums, d_counts);
     RSDSFM_HIP_CHECK(c, hipGetLastError());
+    return RSDSFM_OK;
+}
+
+int seam_blend_launch(Ctx* c, const unsigned char* d_layer, const unsigned char* d_lmask, int channels, int rows, int cols, const unsigned char* d_dist, int feather,
+                      int64_t min_overlap, int gain_mode, int source_id, unsigned char* d_image, unsigned char* d_mask, unsigned char* d_source,
+                      unsigned long long* d_sums, int64_t* d_counts) {
+    unsigned long long* cnt = reinterpret_cast<unsigned long long*>(d_counts);
+    const int rc = seam_overlap_sums_launch(c, d_image, d_source, d_layer, d_lmask, channels, rows, cols, d_sums, cnt);
+    if (rc != RSDSFM_OK) return rc;
+    const int64_t nb = ((int64_t)rows * cols + (int64_t)kBP * 4 - 1) / ((int64_t)kBP * 4);
+    const dim3 grid((unsigned)std::min<int64_t>(nb, 65536));
     hipLaunchKernelGGL(channels == 3 ? seam_blend_kernel<3> : seam_blend_kernel<1>, grid, dim3(kBP), 0, c->stream, d_layer, d_lmask, d_dist, (unsigned)feather,
                        (unsigned)source_id, rows, cols, d_sums, (long long)min_overlap, gain_mode, d_image, d_mask, d_source, cnt);
     RSDSFM_HIP_CHECK(c, hipGetLastError());

@@ -209,7 +209,7 @@ def evaluate_real_sequence(solver, frames, camera="galaxy", gamma=0.95, out_dir=
                            check_flow=False, trajectory=False, link_tol=None, min_links=None, fuse=False, fuse_tol=None, stabilize=False, smooth_sigma=None,
                            smooth_translation=True, fill=0, crop=False, crop_margin=None, crop_max_empty=0, blend=False, blend_feather=None,
                            blend_gain=True, inpaint=False, last_frame=False, occlusion=False, occlusion_tol=None, occlusion_search=False, retime=None,
-                           shutter=None):
+                           shutter=None, denoise=None):
     """evaluate_real_run's real-world branch (main.cc:341-361, 364-531) for a clip: `frames` is <prefix>frame1.png ... frameN.png (the
     prefix, or a list of paths), or the frames themselves (an (N, rows, cols[, 3]) uint8 array or a list of arrays; 2-D frames are gray).
     By default ONE call does the clip (Solver.rectify_video_dev): the batched DeepFlow of every consecutive pair, the pipelined solve of every pair p
@@ -289,7 +289,15 @@ def evaluate_real_sequence(solver, frames, camera="galaxy", gamma=0.95, out_dir=
     renders each (Solver.shutter_video_dev, tests/shutter_spec_numpy.py; the retimed frames' maps, path and occlusion settings): the returned dict
     also has shuttered, shutter_masks, shutter_coverage (lists of frames; the coverage is the number of sub-instants that saw the pixel),
     shutter_counts ((times, 3) int64: [unset, partial, full]) and shutter_kept ((times,) int32: the sub-instants inside the clip); out_dir
-    receives shuttered_<i>.png and shutter.csv.  The retimed keys and files stay as they are; without the keyword every key and file is what it was."""
+    receives shuttered_<i>.png and shutter.csv.  The retimed keys and files stay as they are; without the keyword every key and file is what it was.
+    denoise=K or (K, strength) (needs stabilize=True: ValueError otherwise): behind everything else, every stabilised frame once more as the
+    patch-weighted mean of itself and its K neighbours on either side (1 .. 7), each rendered alone into the frame's camera on the SMOOTHED path
+    (Solver.denoise_video_dev, tests/denoise_spec_numpy.py; strength None: the default, 12; the fused maps with fuse=True, the neighbours through
+    the occlusion test with occlusion=True): the returned dict also has stab_denoised, denoise_masks, denoise_weights (lists of frames; the weight
+    is 16 for the own frame plus up to 16 per neighbour) and denoise_counts ((frames, 3) int64: [unset, own only, averaged]); out_dir receives
+    stabilized_denoised_<p>.png and denoise.csv.  Without the keyword every key and file is what it was."""
+    if denoise is not None and not stabilize:
+        raise ValueError("denoise needs stabilize=True: it averages the frames of the stabilised clip")
     if shutter is not None and retime is None:
         raise ValueError("shutter needs retime=factor or times: it exposes the retimed clip's instants")
     if retime is not None and not stabilize:
@@ -590,6 +598,17 @@ def evaluate_real_sequence(solver, frames, camera="galaxy", gamma=0.95, out_dir=
                                                       occlusion=occlusion, occlusion_tol_q16=occ_q16 if occlusion else 0, mode=mode)
                         traj.update(shuttered=[t.cpu().numpy() for t in d_sh], shutter_masks=[t.cpu().numpy() for t in d_shmasks],
                                     shutter_coverage=[t.cpu().numpy() for t in d_shcov], shutter_counts=sh["counts"], shutter_kept=sh["kept"])
+                if denoise is not None:  # every stabilised frame once more, averaged with its neighbours
+                    dn_radius, dn_strength = (int(denoise), None) if np.ndim(denoise) == 0 else (int(denoise[0]), int(denoise[1]))
+                    d_dn = [torch.empty_like(d_imgs[0]) for _ in range(nst)]
+                    d_dnmasks = [torch.empty((rows, cols), dtype=torch.uint8, device=dev) for _ in range(nst)]
+                    d_dnw = [torch.empty((rows, cols), dtype=torch.uint8, device=dev) for _ in range(nst)]
+                    torch.cuda.synchronize()
+                    dn = solver.denoise_video_dev(ptrs(d_imgs), rows, cols, channels, K, ptrs(d_src[:nst]), ptrs(d_Rs[:nst]), ptrs(d_ts[:nst]), traj["A"], traj["c"], A_s,
+                                                  c_s, st_scales, ptrs(d_dn), ptrs(d_dnmasks), ptrs(d_dnw), radius=dn_radius, strength=dn_strength, occlusion=occlusion,
+                                                  occlusion_tol_q16=occ_q16 if occlusion else 0, mode=mode)
+                    traj.update(stab_denoised=[t.cpu().numpy() for t in d_dn], denoise_masks=[t.cpu().numpy() for t in d_dnmasks],
+                                denoise_weights=[t.cpu().numpy() for t in d_dnw], denoise_counts=dn["counts"])
     if out_dir:
         os.makedirs(out_dir, exist_ok=True)
         lines = ["pair,v_x,v_y,v_z,w_x,w_y,w_z,k,inliers"]
@@ -678,6 +697,13 @@ def evaluate_real_sequence(solver, frames, camera="galaxy", gamma=0.95, out_dir=
                 formats.write_png(os.path.join(out_dir, "shuttered_%d.png" % i), traj["shuttered"][i])
                 rows_.append(",".join([str(i), "%.17g" % t_, str(int(traj["shutter_kept"][i]))] + [str(int(x)) for x in traj["shutter_counts"][i]]))
             with open(os.path.join(out_dir, "shutter.csv"), "w") as fh:
+                fh.write("\n".join(rows_) + "\n")
+        if denoise is not None:
+            rows_ = ["pair,unset,own_only,averaged,mean_weight"]
+            for p in range(nst):
+                formats.write_png(os.path.join(out_dir, "stabilized_denoised_%d.png" % p), traj["stab_denoised"][p])
+                rows_.append(",".join([str(p)] + [str(int(x)) for x in traj["denoise_counts"][p]] + ["%.4f" % float(traj["denoise_weights"][p].mean())]))
+            with open(os.path.join(out_dir, "denoise.csv"), "w") as fh:
                 fh.write("\n".join(rows_) + "\n")
         if inpaint:
             rows_ = ["pair,stage,inpainted"]

@@ -230,7 +230,23 @@ def _exposed(texture, gain):
     return np.clip(np.rint(float(gain) * texture), 0, 255).astype(np.uint8)
 
 
-def render_sequence(nframes, rows, cols, K, v, w, k=0.0, gamma=0.8, seed=0x5EED0000, speeds=None, gains=None):
+def _sensor_noise(frames, noise, noise_seed):
+    """seeded integer sensor noise on a stack of frames: every byte + an integer drawn uniformly from [-noise, noise], clipped to 0 .. 255, frame
+    j from the generator seeded (noise_seed, j) -- so a frame's noise does not depend on how many frames follow it.  None or 0: the frames
+    themselves"""
+    if not noise:
+        return frames
+    noise = int(noise)
+    if noise < 0 or noise > 255:
+        raise ValueError("noise is an amplitude in bytes, 0 .. 255")
+    out = np.empty_like(frames)
+    for j in range(frames.shape[0]):
+        rng = np.random.default_rng([int(noise_seed), j])
+        out[j] = np.clip(frames[j].astype(np.int64) + rng.integers(-noise, noise + 1, size=frames[j].shape), 0, 255).astype(np.uint8)
+    return out
+
+
+def render_sequence(nframes, rows, cols, K, v, w, k=0.0, gamma=0.8, seed=0x5EED0000, speeds=None, gains=None, noise=None, noise_seed=0x5EED0001):
     """nframes 8-bit BGR frames of render_pair's texture under a constant motion: frame j at pixel q shows T(inv^j(q)), where inv is
     render_pair's fixed-point inverse of the model flow F (p + F(p) = q), applied j times from the pixel grid.  Every consecutive pair
     (j, j + 1) therefore has the true flow F and the true (v, w, k); render_pair's border mask.  nframes = 2 gives render_pair's two
@@ -239,13 +255,17 @@ def render_sequence(nframes, rows, cols, K, v, w, k=0.0, gamma=0.8, seed=0x5EED0
     motion; F is then (nframes - 1, rows, cols, 2) and the band of the mask is the widest pair's.  None: the frames of a constant motion,
     byte for byte what this function returned before it had the argument.
     gains: one exposure factor per frame (nframes of them): frame j = clip(rint(gains[j] texture)); the geometry is unchanged.  None: byte
+    for byte what this function returns without the argument.
+    noise: an amplitude in bytes: after the exposure gain every byte of frame j gets an integer drawn uniformly from [-noise, noise] by the
+    generator seeded (noise_seed, j), clipped to 0 .. 255 -- seeded integer sensor noise, what the temporal denoise is for.  None (or 0): byte
     for byte what this function returns without the argument."""
     if nframes < 2:
         raise ValueError("a sequence has at least two frames")
     if gains is not None and len(gains) != nframes:
         raise ValueError("gains needs one factor per frame (nframes)")
     if speeds is not None:
-        return _render_sequence_speeds(nframes, rows, cols, K, v, w, k, gamma, seed, speeds, gains)
+        frames, flows, mask = _render_sequence_speeds(nframes, rows, cols, K, v, w, k, gamma, seed, speeds, gains)
+        return _sensor_noise(frames, noise, noise_seed), flows, mask
     flow, _ = make_flow(rows, cols, K, v, w, k, gamma, _model_only=True)
     yy, xx = np.mgrid[0:rows, 0:cols].astype(np.float64)
     frames = [_exposed(_texture(xx, yy, seed), None if gains is None else gains[0])]
@@ -264,7 +284,7 @@ def render_sequence(nframes, rows, cols, K, v, w, k=0.0, gamma=0.8, seed=0x5EED0
     band = int(np.ceil(np.abs(flow).max())) + 5
     mask = np.zeros((rows, cols), dtype=bool)
     mask[band:rows - band, band:cols - band] = True
-    return np.stack(frames), np.ascontiguousarray(flow), mask
+    return _sensor_noise(np.stack(frames), noise, noise_seed), np.ascontiguousarray(flow), mask
 
 
 def _render_sequence_speeds(nframes, rows, cols, K, v, w, k, gamma, seed, speeds, gains=None):
