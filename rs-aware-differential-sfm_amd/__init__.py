@@ -135,11 +135,12 @@ class RansacOut(C.Structure):
 
 
 def declared_symbols():
-    """Names of every function include/rsdsfm.h, include/rsdsfm_retime.h, include/rsdsfm_shutter.h and include/rsdsfm_denoise.h declare (used by
-    the CPU symbol-export test)."""
+    """Names of every function include/rsdsfm.h, include/rsdsfm_retime.h, include/rsdsfm_shutter.h, include/rsdsfm_denoise.h and
+    include/rsdsfm_superres.h declare (used by the CPU symbol-export test)."""
     import re
 
-    txt = "".join(open(os.path.join(os.path.dirname(HEADER_PATH), name)).read() for name in (os.path.basename(HEADER_PATH), "rsdsfm_retime.h", "rsdsfm_shutter.h", "rsdsfm_denoise.h"))
+    txt = "".join(open(os.path.join(os.path.dirname(HEADER_PATH), name)).read()
+                  for name in (os.path.basename(HEADER_PATH), "rsdsfm_retime.h", "rsdsfm_shutter.h", "rsdsfm_denoise.h", "rsdsfm_superres.h"))
     txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
     return sorted(set(re.findall(r"\b(rsdsfm_[a-z0-9_]+)\s*\(", txt)))
 
@@ -3150,6 +3151,202 @@ class _DenoiseMixin:
 
 
 for _name, _fn in list(vars(_DenoiseMixin).items()):
+    if not _name.startswith("__"):
+        setattr(Solver, _name, _fn)
+
+
+# ---------------------------------------------------------------------------------------------------
+# the multi-frame super-resolution: a frame on a grid S times finer, merged from its registered neighbours (include/rsdsfm_superres.h)
+# ---------------------------------------------------------------------------------------------------
+SUPERRES_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "rsdsfm_superres.h")
+SUPERRES_SCALE_MAX = 4
+SUPERRES_RADIUS_MAX = 7
+SUPERRES_LAYERS_MAX = 14
+SUPERRES_PROX_MAX = 16
+
+
+class SuperresParams(C.Structure):
+    _fields_ = [("scale", C.c_int32), ("radius", C.c_int32), ("strength", C.c_int32), ("gain_mode", C.c_int32), ("min_overlap", C.c_int64), ("struct_bytes", C.c_int32),
+                ("reserved", C.c_int32 * 5)]
+
+
+def superres_declared_symbols():
+    """Names of every function include/rsdsfm_superres.h declares"""
+    import re
+
+    txt = open(SUPERRES_HEADER_PATH).read()
+    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
+    return sorted(set(re.findall(r"\b(rsdsfm_[a-z0-9_]+)\s*\(", txt)))
+
+
+def _superres_params(scale=None, radius=None, strength=None, gain=True, min_overlap=None):
+    """a SuperresParams with the given values over the defaults (None: the default)"""
+    p = SuperresParams()
+    if load_library().rsdsfm_superres_params_init(C.byref(p)) != OK:
+        raise RsdsfmError("rsdsfm_superres_params_init failed")
+    if scale is not None:
+        p.scale = int(scale)
+    if radius is not None:
+        p.radius = int(radius)
+    if strength is not None:
+        p.strength = int(strength)
+    if min_overlap is not None:
+        p.min_overlap = int(min_overlap)
+    p.gain_mode = 0 if gain else 1
+    return p
+
+
+def superres_default_params():
+    """the super-resolution's defaults as a dict: scale = 2, radius = 2, strength = 12, min_overlap = 1024 (rsdsfm_superres_params_init); choices,
+    not measurements"""
+    p = _superres_params()
+    return dict(scale=p.scale, radius=p.radius, strength=p.strength, min_overlap=p.min_overlap, gain_mode=p.gain_mode)
+
+
+def superres_render_launches(rows, cols, scale):
+    """kernel launches of one superres_render_dev call: stabilize_window_launches(rows, cols) (rsdsfm_superres_render_launches; host only)"""
+    n = load_library().rsdsfm_superres_render_launches(C.c_int32(rows), C.c_int32(cols), C.c_int32(scale))
+    if n < 0:
+        raise RsdsfmError("rsdsfm_superres_render_launches failed (%d): rows and cols in [2, 16384], scale in [1, 4], scale * size at most 16384" % n)
+    return n
+
+
+def superres_accumulate_launches():
+    """kernel launches of one superres_accumulate_dev call: 1 (rsdsfm_superres_accumulate_launches; host only)"""
+    return int(load_library().rsdsfm_superres_accumulate_launches())
+
+
+def superres_launches(rows, cols, scale, nsrc):
+    """kernel launches of one superres_frame_dev call on nsrc sources of rows x cols: nsrc superres_render_launches + 2 (nsrc - 1), or + 1 with one
+    source (rsdsfm_superres_launches; host only)"""
+    n = load_library().rsdsfm_superres_launches(C.c_int32(rows), C.c_int32(cols), C.c_int32(scale), C.c_int32(nsrc))
+    if n < 0:
+        raise RsdsfmError("rsdsfm_superres_launches failed (%d): rows and cols in [2, 16384], scale in [1, 4], scale * size at most 16384, nsrc in [1, 15]" % n)
+    return n
+
+
+class _SuperresMixin:
+    def superres_render_dev(self, d_image, channels, d_depth_map, d_R, d_t, K, rows, cols, M, m, scale, d_bil, d_near, d_prox, d_valid=None, window=None,
+                            mode=BACKPROJECT_RS, q5_mode=Q5_COMPAT, iterations=0):
+        """one source rendered alone onto a grid `scale` times finer (rsdsfm_superres_render_dev; tests/superres_spec_numpy.py): d_bil and d_near
+        (scale rows x scale cols x channels) the bilinear and the nearest source sample of every fine pixel, d_prox (scale rows x scale cols) how
+        near the nearest fell, 1 .. 16, 0 where the pixel is not valid; d_valid (optional) 1 where d_prox is not 0.  Every byte is written.
+        Enqueued on the context's stream."""
+        d = C.c_double
+        self._check(self.lib.rsdsfm_superres_render_dev(self._ctx, _dp(d_image), C.c_int32(channels), _dp(d_depth_map), _dp(d_R), _dp(d_t), d(K[0]), d(K[1]), d(K[2]),
+                                                        d(K[3]), C.c_int32(rows), C.c_int32(cols), int(mode), int(q5_mode), C.c_int32(iterations), _p(_f64(M).reshape(-1)),
+                                                        _p(_f64(m).reshape(-1)), C.c_int32(scale), _window4(window), _np0(d_bil), _np0(d_near), _np0(d_prox), _np0(d_valid)),
+                    "rsdsfm_superres_render_dev")
+
+    def superres_render(self, image, depth, R, t, K, M, m, scale=2, window=None, mode=BACKPROJECT_RS, q5_mode=Q5_COMPAT, iterations=0, device=0):
+        """host convenience around superres_render_dev: image (rows, cols[, 3]) uint8, depth (rows, cols), R (rows, 9 or 3, 3), t (rows, 3)
+        -> dict(bil, near, prox, valid) of host arrays on the fine grid"""
+        import torch
+
+        image = np.ascontiguousarray(image, dtype=np.uint8)
+        rows, cols = image.shape[:2]
+        ch = 1 if image.ndim == 2 else image.shape[2]
+        dev = torch.device("cuda", device)
+        with torch.cuda.device(dev):
+            tt = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+            d_i, d_z = tt(image), tt(_f64(depth).T)
+            d_R, d_t = tt(_f64(R).reshape(-1, 9)), tt(_f64(t).reshape(-1, 3))
+            fine = (scale * rows, scale * cols)
+            d_b = torch.empty(fine + image.shape[2:], dtype=torch.uint8, device=dev)
+            d_n, d_q, d_v = torch.empty_like(d_b), torch.empty(fine, dtype=torch.uint8, device=dev), torch.empty(fine, dtype=torch.uint8, device=dev)
+            torch.cuda.synchronize()
+            self.superres_render_dev(d_i.data_ptr(), ch, d_z.data_ptr(), d_R.data_ptr(), d_t.data_ptr(), K, rows, cols, M, m, scale, d_b.data_ptr(), d_n.data_ptr(),
+                                     d_q.data_ptr(), d_v.data_ptr(), window, mode, q5_mode, iterations)
+            self.synchronize()
+            return dict(bil=d_b.cpu().numpy(), near=d_n.cpu().numpy(), prox=d_q.cpu().numpy(), valid=d_v.cpu().numpy())
+
+    def superres_accumulate_dev(self, d_ref, d_ref_near, d_ref_prox, d_layer, d_layer_near, d_layer_prox, channels, rows, cols, d_cells, first, last, d_sums8=None,
+                                min_overlap=0, gain_mode=0, strength=0, d_image_out=None, d_mask_out=None, d_weight=None, d_counts3=None):
+        """one layer accumulated onto the cells (rsdsfm_superres_accumulate_dev; tests/superres_spec_numpy.py) on FINE planes of rows x cols: the
+        layer's nearest samples weighted by the denoise's 3 x 3 patch weight (taken on the bilinear planes) times the layer's proximity.  The
+        three layer pointers None: no layer (first and last).  d_sums8: the layer's record (seam_overlap_sums_dev), None: no gain.  first: the
+        cells are set from the reference's nearest samples and proximity; last: the cells are not written, the merged pixel goes to d_image_out
+        (the reference's bilinear sample where no layer contributed), 1 to d_mask_out where anything counted, the summed weight to d_weight and
+        [unset, own only, merged] to d_counts3 (three device int64).  At most 14 layers.  Enqueued on the context's stream."""
+        self._check(self.lib.rsdsfm_superres_accumulate_dev(self._ctx, _dp(d_ref), _dp(d_ref_near), _dp(d_ref_prox), _np0(d_layer), _np0(d_layer_near), _np0(d_layer_prox),
+                                                            C.c_int32(channels), C.c_int32(rows), C.c_int32(cols), _np0(d_sums8), C.c_int64(min_overlap), C.c_int32(gain_mode),
+                                                            C.c_int32(strength), _np0(d_cells), C.c_int32(int(first)), C.c_int32(int(last)), _np0(d_image_out),
+                                                            _np0(d_mask_out), _np0(d_weight), _np0(d_counts3)), "rsdsfm_superres_accumulate_dev")
+
+    def superres_accumulate(self, ref, ref_near, ref_prox, layers, records=None, min_overlap=0, gain_mode=0, strength=0, device=0):
+        """host convenience around superres_accumulate_dev: the reference's (bil, near, prox), layers a list of 0 .. 14 (bil, near, prox) triples of
+        host arrays on the fine grid, records None or one 8-word record (or None) per layer
+        -> (image, mask, weight (rows, cols) uint8, counts (3,) int64 [unset, own only, merged])"""
+        import torch
+
+        ref = np.ascontiguousarray(ref, dtype=np.uint8)
+        rows, cols = ref.shape[:2]
+        ch = 1 if ref.ndim == 2 else ref.shape[2]
+        dev = torch.device("cuda", device)
+        with torch.cuda.device(dev):
+            up = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.uint8)).to(dev)
+            d_ref, d_rn, d_rq = up(ref), up(ref_near), up(ref_prox)
+            d_l = [(up(b), up(n), up(q)) for b, n, q in layers]
+            d_rec = [None if records is None or records[j] is None else torch.from_numpy(np.ascontiguousarray(records[j], dtype=np.uint64).view(np.int64)).to(dev)
+                     for j in range(len(layers))]
+            d_cells = torch.empty((rows, cols, ch + 1), dtype=torch.int16, device=dev)
+            d_out, d_mask = torch.empty_like(d_ref), torch.empty((rows, cols), dtype=torch.uint8, device=dev)
+            d_w, d_cnt = torch.empty_like(d_mask), torch.zeros(3, dtype=torch.int64, device=dev)
+            torch.cuda.synchronize()
+            outs = dict(d_image_out=d_out.data_ptr(), d_mask_out=d_mask.data_ptr(), d_weight=d_w.data_ptr(), d_counts3=d_cnt.data_ptr())
+            ref_ptrs = (d_ref.data_ptr(), d_rn.data_ptr(), d_rq.data_ptr())
+            if not d_l:
+                self.superres_accumulate_dev(*ref_ptrs, None, None, None, ch, rows, cols, None, True, True, None, min_overlap, gain_mode, strength, **outs)
+            for j, (d_b, d_n, d_q) in enumerate(d_l):
+                self.superres_accumulate_dev(*ref_ptrs, d_b.data_ptr(), d_n.data_ptr(), d_q.data_ptr(), ch, rows, cols, d_cells.data_ptr(), j == 0, j == len(d_l) - 1,
+                                             d_rec[j].data_ptr() if d_rec[j] is not None else None, min_overlap, gain_mode, strength, **outs)
+            self.synchronize()
+            return d_out.cpu().numpy(), d_mask.cpu().numpy(), d_w.cpu().numpy(), d_cnt.cpu().numpy()
+
+    def superres_frame_dev(self, d_images, channels, d_depth_maps, d_R, d_t, K, rows, cols, M, m, d_image, d_mask, d_weight=None, d_counts3=None, scale=None, strength=None,
+                           gain=True, min_overlap=None, window=None, mode=BACKPROJECT_RS, q5_mode=Q5_COMPAT, iterations=0, params=None):
+        """one super-resolved frame (rsdsfm_superres_frame_dev): d_images, d_depth_maps, d_R, d_t lists of 1 .. 15 device pointers of rows x cols
+        sources, source 0 the own frame and the others its neighbours; M (nsrc, 3, 3), m (nsrc, 3) every source's pose in the target camera.
+        Every source through superres_render_dev, per neighbour seam_overlap_sums_dev and superres_accumulate_dev; the merged frame into d_image
+        (scale rows x scale cols x channels), d_mask, d_weight (scale rows x scale cols), d_counts3.  params: a SuperresParams passed as it is
+        instead of the keywords.  Enqueued on the context's stream."""
+        ns = len(d_images)
+        _need_all(ns, d_depth_maps=d_depth_maps, d_R=d_R, d_t=d_t)
+        Mm, mm = _f64(M).reshape(-1, 9), _f64(m).reshape(-1, 3)
+        if Mm.shape[0] < ns or mm.shape[0] < ns:
+            raise RsdsfmError("superres_frame_dev: every source needs a pose (M, m)")
+        sp = params if params is not None else _superres_params(scale, None, strength, gain, min_overlap)
+        d = C.c_double
+        arr = lambda x: _ptr_array(list(x)[:ns]) if ns else None
+        self._check(self.lib.rsdsfm_superres_frame_dev(self._ctx, arr(d_images), C.c_int32(channels), arr(d_depth_maps), arr(d_R), arr(d_t), d(K[0]), d(K[1]), d(K[2]),
+                                                       d(K[3]), C.c_int32(rows), C.c_int32(cols), int(mode), int(q5_mode), C.c_int32(iterations), C.c_int32(ns), _p(Mm), _p(mm),
+                                                       C.byref(sp), _window4(window), _dp(d_image), _dp(d_mask), _np0(d_weight), _np0(d_counts3)), "rsdsfm_superres_frame_dev")
+
+    def superres_video_dev(self, d_frames, rows, cols, channels, K, d_depth_maps, d_R, d_t, A, c, A_path, c_path, scales, d_out, d_out_masks, d_out_weights=None,
+                           want_counts=True, scale=None, radius=None, strength=None, gain=True, min_overlap=None, window=None, mode=BACKPROJECT_RS, q5_mode=Q5_COMPAT,
+                           iterations=0):
+        """a solved clip super-resolved (rsdsfm_superres_video_dev): the clip as denoise_video_dev takes it and walks it; for every frame q the
+        own pose by retime_poses(t = q), the neighbours within `radius` (None: 2) by neighbour_poses on the same path, and superres_frame_dev
+        into d_out[q], d_out_masks[q], d_out_weights[q] (planes `scale` (None: 2) times finer than the frames).  Returns dict(); with want_counts
+        counts (nsources, 3) int64 [unset, own only, merged] -- the call then waits."""
+        ns = len(d_depth_maps)
+        _need_all(ns, d_frames=d_frames, d_R=d_R, d_t=d_t, d_out=d_out, d_out_masks=d_out_masks, d_out_weights=d_out_weights)
+        a, cc, ap, cp = _f64(A).reshape(-1, 9), _f64(c).reshape(-1, 3), _f64(A_path).reshape(-1, 9), _f64(c_path).reshape(-1, 3)
+        sc = _f64(scales).reshape(-1)
+        if min(a.shape[0], cc.shape[0], ap.shape[0], cp.shape[0], sc.shape[0]) < ns:
+            raise RsdsfmError("superres_video_dev: every source needs a pose on both paths and a scale")
+        sp = _superres_params(scale, radius, strength, gain, min_overlap)
+        counts = np.zeros((max(ns, 1), 3), dtype=np.int64) if want_counts else None
+        d = C.c_double
+        arr = lambda x: _ptr_array(list(x)[:ns]) if x is not None and ns else None
+        self._check(self.lib.rsdsfm_superres_video_dev(self._ctx, arr(d_frames), C.c_int32(ns), C.c_int32(rows), C.c_int32(cols), C.c_int32(channels), d(K[0]), d(K[1]),
+                                                       d(K[2]), d(K[3]), arr(d_depth_maps), arr(d_R), arr(d_t), _p(a), _p(cc), _p(ap), _p(cp), _p(sc), int(mode), int(q5_mode),
+                                                       C.c_int32(iterations), C.byref(sp), _window4(window), arr(d_out), arr(d_out_masks), arr(d_out_weights), _p(counts)),
+                    "rsdsfm_superres_video_dev")
+        return dict(counts=counts[:ns]) if want_counts else dict()
+
+
+for _name, _fn in list(vars(_SuperresMixin).items()):
     if not _name.startswith("__"):
         setattr(Solver, _name, _fn)
 

@@ -24,6 +24,8 @@ struct DenseWs {
     unsigned char* d_layer2 = nullptr; // the retimer's second layer, mask and image, 4 planes (retime.hpp; made when first asked for)
     unsigned char* d_shutter = nullptr; // the synthetic shutter's sample mask and image and its cells, 12 planes (shutter.hpp; made when first asked for)
     unsigned char* d_denoise = nullptr; // the temporal denoise's reference mask, source plane and image and its cells, 13 planes (denoise.hpp; made when first asked for)
+    unsigned char* d_superres = nullptr; // the super-resolution's own planes, layer planes, cells and record on the FINE grid, 23 planes (superres.hpp; made when first asked for)
+    int superres_scale = 0;              // the scale d_superres was made for
     int rows = 0, cols = 0;
 };
 

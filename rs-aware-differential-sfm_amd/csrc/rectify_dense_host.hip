@@ -25,6 +25,9 @@ static void dense_ws_free(DenseWs* w) {
     w->d_shutter = nullptr;
     if (w->d_denoise) (void)hipFree(w->d_denoise);
     w->d_denoise = nullptr;
+    if (w->d_superres) (void)hipFree(w->d_superres);
+    w->d_superres = nullptr;
+    w->superres_scale = 0;
     w->d_pyr = nullptr;
     w->d_disp = nullptr;
     w->d_mask = nullptr;

@@ -1,0 +1,323 @@
+// superres_host.hip -- C ABI of the multi-frame super-resolution (include/rsdsfm_superres.h; tests/superres_spec_numpy.py is the definition,
+// superres_kernels.hip the kernels): the render call, the accumulate call, the frame call, which CALLS the public render, record and
+// accumulate entry points one after another on planes of the context's dense workspace, and the clip call, which calls the frame call per
+// frame, walking the clip as rsdsfm_denoise_video_dev does.
+#include <cmath>
+#include <vector>
+
+#include "rectify_dense.hpp"
+#include "rsdsfm_internal.hpp"
+#include "sequence_host.hpp"
+#include "stabilize_blend.hpp"
+#include "superres.hpp"
+
+namespace rsdsfm {
+namespace {
+
+rsdsfm_superres_params superres_defaults() {
+    return rsdsfm_superres_params{kSuperresScaleDefault, kSuperresRadiusDefault, kSuperresStrengthDefault, 0, kMinOverlapDefault, (int32_t)sizeof(rsdsfm_superres_params),
+                                  {0, 0, 0, 0, 0}};
+}
+
+// the params with every 0 of scale, radius, strength and min_overlap replaced by its default, or the defaults for NULL; false: refused
+bool superres_params_resolve(const rsdsfm_superres_params* in, rsdsfm_superres_params* out) {
+    *out = in ? *in : superres_defaults();
+    if (out->struct_bytes != 0 && out->struct_bytes != (int32_t)sizeof(rsdsfm_superres_params)) return false;
+    for (int i = 0; i < 5; ++i)
+        if (out->reserved[i] != 0) return false;
+    if (out->scale == 0) out->scale = kSuperresScaleDefault;
+    if (out->radius == 0) out->radius = kSuperresRadiusDefault;
+    if (out->strength == 0) out->strength = kSuperresStrengthDefault;
+    if (out->min_overlap == 0) out->min_overlap = kMinOverlapDefault;
+    return out->scale >= 1 && out->scale <= kSuperresScaleMax && out->radius >= 1 && out->radius <= kSuperresRadiusMax && out->strength >= 1 &&
+           out->strength <= kSuperresStrengthMax && out->min_overlap >= 0 && (out->gain_mode == 0 || out->gain_mode == 1);
+}
+
+const char* const kSuperresParamsMessage =
+    "rsdsfm_superres_params: scale in [1, 4] or 0, radius in [1, 7] or 0, strength in [1, 255] or 0, gain_mode 0 or 1, min_overlap >= 0, reserved 0, struct_bytes 0 or "
+    "sizeof (use rsdsfm_superres_params_init)";
+
+bool superres_size_ok(int rows, int cols) { return rows >= 2 && cols >= 2 && rows <= kSuperresSizeMax && cols <= kSuperresSizeMax; }
+
+// the source size and the scale: the fine size may not pass 16384 either
+bool superres_scale_ok(int rows, int cols, int scale) {
+    return superres_size_ok(rows, cols) && scale >= 1 && scale <= kSuperresScaleMax && (int64_t)scale * rows <= kSuperresSizeMax && (int64_t)scale * cols <= kSuperresSizeMax;
+}
+
+const char* const kSuperresScaleMessage = "superres: scale must be in [1, 4] and scale * rows, scale * cols at most 16384";
+
+bool superres_finite_all(const double* a, int n) {
+    for (int i = 0; i < n; ++i)
+        if (!std::isfinite(a[i])) return false;
+    return true;
+}
+
+bool superres_window_ok(const int32_t* w, int rows, int cols) {
+    return w[2] >= 1 && w[3] >= 1 && w[0] >= 0 && w[1] >= 0 && (int64_t)w[0] + w[2] <= rows && (int64_t)w[1] + w[3] <= cols;
+}
+
+// the argument checks of the final outputs, for the accumulate call and, before anything is enqueued, for the frame call
+int superres_outputs_check(Ctx* c, const uint8_t* d_image_out, const uint8_t* d_mask_out, const uint8_t* d_weight, const int64_t* d_counts3) {
+    if (!d_image_out || !d_mask_out) return fail(c, RSDSFM_ERR_INVALID, "superres: null output plane");
+    if (d_image_out == d_mask_out || (d_weight && (d_weight == d_image_out || d_weight == d_mask_out)))
+        return fail(c, RSDSFM_ERR_INVALID, "superres: the output planes must be distinct");
+    if (((uintptr_t)d_image_out | (uintptr_t)d_mask_out | (uintptr_t)d_weight) & 3u) return fail(c, RSDSFM_ERR_INVALID, "superres: every plane must be 4-byte aligned");
+    if ((uintptr_t)d_counts3 & 7u) return fail(c, RSDSFM_ERR_INVALID, "superres: the counters must be 8-byte aligned");
+    return RSDSFM_OK;
+}
+
+// the workspace's fine planes, cells and record: made when first asked for and again when the scale changes (a size change releases them with the rest)
+int superres_ws(Ctx* c, int rows, int cols, int scale, DenseWs** ws) {
+    const int rc = rectify_dense_ws(c, rows, cols, ws);
+    if (rc != RSDSFM_OK) return rc;
+    DenseWs* w = *ws;
+    if (w->d_superres && w->superres_scale != scale) {
+        RSDSFM_HIP_CHECK(c, hipStreamSynchronize(c->stream));  // behind whatever the stream still runs on the old planes
+        (void)hipFree(w->d_superres);
+        w->d_superres = nullptr;
+        w->superres_scale = 0;
+    }
+    if (!w->d_superres) {
+        if (hipMalloc(reinterpret_cast<void**>(&w->d_superres), superres_ws_bytes(scale * rows, scale * cols)) != hipSuccess) {
+            w->d_superres = nullptr;
+            return fail(c, RSDSFM_ERR_HIP, "superres: no memory for the fine planes and the cells");
+        }
+        w->superres_scale = scale;
+    }
+    return RSDSFM_OK;
+}
+
+// one frame's host part for the clip call: the sources (the own frame first) and their poses, as the denoise's clip call plans them
+struct SuperresPlan {
+    int nsrc = 0;
+    int32_t src[kSuperresSourcesMax];
+    double M[9 * kSuperresSourcesMax], m[3 * kSuperresSourcesMax];
+};
+
+bool superres_plan(const double* A, const double* c_, const double* A_path, const double* c_path, const double* scales, int nsources, int q, int radius, SuperresPlan* plan) {
+    int32_t src2[2], nsrc = 0, wq = 0, ids[kSuperresLayersMax], count = 0;
+    double M18[18], m6[6], At[9], ct[3];
+    if (rsdsfm_retime_poses(A, c_, A_path, c_path, scales, nsources, (double)q, src2, &nsrc, &wq, M18, m6, At, ct) != RSDSFM_OK || nsrc != 1) return false;
+    plan->src[0] = q;
+    for (int k = 0; k < 9; ++k) plan->M[k] = M18[k];
+    for (int k = 0; k < 3; ++k) plan->m[k] = m6[k];
+    if (nsources > 1 && rsdsfm_neighbour_poses(A, c_, A_path, c_path, scales, nsources, q, radius, plan->src + 1, ids, plan->M + 9, plan->m + 3, &count) != RSDSFM_OK)
+        return false;
+    plan->nsrc = 1 + count;
+    return superres_finite_all(plan->M, 9 * plan->nsrc) && superres_finite_all(plan->m, 3 * plan->nsrc);
+}
+
+}  // namespace
+}  // namespace rsdsfm
+
+using namespace rsdsfm;
+
+extern "C" {
+
+int rsdsfm_superres_params_init(rsdsfm_superres_params* params) {
+    if (!params) return RSDSFM_ERR_INVALID;
+    *params = superres_defaults();
+    return RSDSFM_OK;
+}
+
+int rsdsfm_superres_render_launches(int32_t rows, int32_t cols, int32_t scale) {
+    if (!superres_scale_ok(rows, cols, scale)) return RSDSFM_ERR_INVALID;
+    return rsdsfm_stabilize_window_launches(rows, cols);
+}
+
+int rsdsfm_superres_accumulate_launches(void) { return 1; }
+
+int rsdsfm_superres_launches(int32_t rows, int32_t cols, int32_t scale, int32_t nsrc) {
+    if (nsrc < 1 || nsrc > kSuperresSourcesMax) return RSDSFM_ERR_INVALID;
+    const int one = rsdsfm_superres_render_launches(rows, cols, scale);
+    if (one < 0) return one;
+    return nsrc * one + (nsrc == 1 ? 1 : (nsrc - 1) * (1 + rsdsfm_superres_accumulate_launches()));
+}
+
+int rsdsfm_superres_render_dev(rsdsfm_ctx* ctx, const uint8_t* d_image_n, int32_t channels, const double* d_depth_n_colmajor, const double* d_R_n_rows9,
+                               const double* d_t_n_rows3, double fx, double fy, double cx, double cy, int32_t rows, int32_t cols, int mode, int q5_mode,
+                               int32_t iterations, const double* M9, const double* m3, int32_t scale, const int32_t* window_or_null, uint8_t* d_bil_out,
+                               uint8_t* d_near_out, uint8_t* d_prox_out, uint8_t* d_valid_or_null) {
+    if (!ctx) return RSDSFM_ERR_INVALID;
+    Ctx* c = &ctx->c;
+    DeviceGuard device_guard_(c);
+    int rc = rectify_dense_check(c, channels, rows, cols, mode, q5_mode, iterations);
+    if (rc != RSDSFM_OK) return rc;
+    if (!superres_scale_ok(rows, cols, scale)) return fail(c, RSDSFM_ERR_INVALID, kSuperresScaleMessage);
+    if (!d_image_n || !d_depth_n_colmajor || !d_R_n_rows9 || !d_t_n_rows3 || !d_bil_out || !d_near_out || !d_prox_out)
+        return fail(c, RSDSFM_ERR_INVALID, "superres render: null device pointer");
+    const void* io[5] = {d_image_n, d_bil_out, d_near_out, d_prox_out, d_valid_or_null};
+    for (int i = 0; i < 5; ++i)
+        for (int j = i + 1; j < 5; ++j)
+            if (io[j] && io[i] == io[j]) return fail(c, RSDSFM_ERR_INVALID, "superres render: the image and the output planes must be distinct");
+    if (((uintptr_t)d_image_n | (uintptr_t)d_bil_out | (uintptr_t)d_near_out | (uintptr_t)d_prox_out | (uintptr_t)d_valid_or_null) & 3u)
+        return fail(c, RSDSFM_ERR_INVALID, "superres render: the image and every output plane must be 4-byte aligned");
+    if (!M9 || !m3 || !superres_finite_all(M9, 9) || !superres_finite_all(m3, 3))
+        return fail(c, RSDSFM_ERR_INVALID, "superres render: the pose (M, m) must be given and finite");
+    const int32_t full[4] = {0, 0, rows, cols};
+    const int32_t* window = window_or_null ? window_or_null : full;
+    if (!superres_window_ok(window, rows, cols))
+        return fail(c, RSDSFM_ERR_INVALID, "superres render: the window (r0, c0, h, w) needs h >= 1, w >= 1 and must lie inside the frame");
+    DenseWs* ws = nullptr;
+    rc = rectify_dense_ws(c, rows, cols, &ws);
+    if (rc != RSDSFM_OK) return rc;
+    StabPose vp;
+    for (int i = 0; i < 9; ++i) vp.M[i] = M9[i];
+    for (int i = 0; i < 3; ++i) vp.m[i] = m3[i];
+    return superres_render_launch(c, *ws, d_image_n, channels, d_depth_n_colmajor, d_R_n_rows9, d_t_n_rows3, fx, fy, cx, cy, rows, cols, mode, q5_mode,
+                                  iterations ? iterations : 3, vp, scale, window, d_bil_out, d_near_out, d_prox_out, d_valid_or_null);
+}
+
+int rsdsfm_superres_accumulate_dev(rsdsfm_ctx* ctx, const uint8_t* d_ref_bil, const uint8_t* d_ref_near, const uint8_t* d_ref_prox,
+                                   const uint8_t* d_layer_bil_or_null, const uint8_t* d_layer_near_or_null, const uint8_t* d_layer_prox_or_null, int32_t channels,
+                                   int32_t rows, int32_t cols, const uint64_t* d_sums8_or_null, int64_t min_overlap, int32_t gain_mode, int32_t strength,
+                                   uint16_t* d_cells_or_null, int32_t first, int32_t last, uint8_t* d_image_out, uint8_t* d_mask_out, uint8_t* d_weight_or_null,
+                                   int64_t* d_counts3_or_null) {
+    if (!ctx) return RSDSFM_ERR_INVALID;
+    Ctx* c = &ctx->c;
+    DeviceGuard device_guard_(c);
+    if ((first != 0 && first != 1) || (last != 0 && last != 1)) return fail(c, RSDSFM_ERR_INVALID, "superres accumulate: first and last must be 0 or 1");
+    if (!superres_size_ok(rows, cols)) return fail(c, RSDSFM_ERR_INVALID, "superres: rows and cols must be in [2, 16384]");
+    if (channels != 1 && channels != 3) return fail(c, RSDSFM_ERR_INVALID, "superres: channels must be 1 or 3");
+    if (min_overlap < 0 || (gain_mode != 0 && gain_mode != 1) || strength < 0 || strength > kSuperresStrengthMax)
+        return fail(c, RSDSFM_ERR_INVALID, "superres accumulate: min_overlap must be >= 0, gain_mode 0 or 1 and strength in [1, 255] (0: the default, 12)");
+    if (last) {
+        const int rc = superres_outputs_check(c, d_image_out, d_mask_out, d_weight_or_null, d_counts3_or_null);
+        if (rc != RSDSFM_OK) return rc;
+    } else {  // the outputs are not read
+        d_image_out = d_mask_out = d_weight_or_null = nullptr;
+        d_counts3_or_null = nullptr;
+    }
+    if (!d_ref_bil || !d_ref_near || !d_ref_prox) return fail(c, RSDSFM_ERR_INVALID, "superres accumulate: the reference needs its three planes");
+    const int nlayer = (d_layer_bil_or_null != nullptr) + (d_layer_near_or_null != nullptr) + (d_layer_prox_or_null != nullptr);
+    if (nlayer != 0 && nlayer != 3) return fail(c, RSDSFM_ERR_INVALID, "superres accumulate: the layer needs its three planes, or none");
+    if (nlayer == 0 && !(first && last)) return fail(c, RSDSFM_ERR_INVALID, "superres accumulate: without a layer first and last must both be 1");
+    if (!d_cells_or_null && !(first && last)) return fail(c, RSDSFM_ERR_INVALID, "superres accumulate: the cells may be NULL only with first and last");
+    const void* in[8] = {d_ref_bil, d_ref_near, d_ref_prox, d_layer_bil_or_null, d_layer_near_or_null, d_layer_prox_or_null, d_cells_or_null, d_sums8_or_null};
+    for (int i = 0; i < 6; ++i)
+        for (int j = i + 1; j < 6; ++j)
+            if (in[i] && in[i] == in[j]) return fail(c, RSDSFM_ERR_INVALID, "superres accumulate: the reference's and the layer's planes must be distinct");
+    uintptr_t bits = 0;
+    for (int i = 0; i < 6; ++i) bits |= (uintptr_t)in[i];
+    if (bits & 3u) return fail(c, RSDSFM_ERR_INVALID, "superres: every plane must be 4-byte aligned");
+    if (((uintptr_t)d_cells_or_null | (uintptr_t)d_sums8_or_null) & 7u)
+        return fail(c, RSDSFM_ERR_INVALID, "superres accumulate: the cells and the record must be 8-byte aligned");
+    const void* io[4] = {d_image_out, d_mask_out, d_weight_or_null, d_counts3_or_null};
+    for (int i = 0; i < 4; ++i)
+        for (int j = 0; j < 8 && io[i]; ++j)
+            if (in[j] == io[i]) return fail(c, RSDSFM_ERR_INVALID, "superres accumulate: an output may not be an input, the record or the cells");
+    for (int j = 0; j < 6 && d_cells_or_null; ++j)
+        if (in[j] == (const void*)d_cells_or_null) return fail(c, RSDSFM_ERR_INVALID, "superres accumulate: the cells may not be an input plane");
+    return superres_accumulate_launch(c, d_ref_bil, d_ref_near, d_ref_prox, d_layer_bil_or_null, d_layer_near_or_null, d_layer_prox_or_null, channels, rows, cols,
+                                      reinterpret_cast<const unsigned long long*>(d_sums8_or_null), min_overlap ? min_overlap : kMinOverlapDefault, gain_mode,
+                                      strength ? strength : kSuperresStrengthDefault, d_cells_or_null, first == 1, last == 1, d_image_out, d_mask_out, d_weight_or_null,
+                                      d_counts3_or_null);
+}
+
+int rsdsfm_superres_frame_dev(rsdsfm_ctx* ctx, const uint8_t* const* d_images, int32_t channels, const double* const* d_depths_colmajor,
+                              const double* const* d_R_rows9, const double* const* d_t_rows3, double fx, double fy, double cx, double cy, int32_t rows, int32_t cols,
+                              int mode, int q5_mode, int32_t iterations, int32_t nsrc, const double* M, const double* m, const rsdsfm_superres_params* params_or_null,
+                              const int32_t* window_or_null, uint8_t* d_image_out, uint8_t* d_mask_out, uint8_t* d_weight_or_null, int64_t* d_counts3_or_null) {
+    if (!ctx) return RSDSFM_ERR_INVALID;
+    Ctx* c = &ctx->c;
+    DeviceGuard device_guard_(c);
+    int rc = rectify_dense_check(c, channels, rows, cols, mode, q5_mode, iterations);
+    if (rc != RSDSFM_OK) return rc;
+    if (nsrc < 1 || nsrc > kSuperresSourcesMax) return fail(c, RSDSFM_ERR_INVALID, "superres frame: nsrc must be in [1, 15]");
+    rsdsfm_superres_params sp;
+    if (!superres_params_resolve(params_or_null, &sp)) return fail(c, RSDSFM_ERR_INVALID, kSuperresParamsMessage);
+    if (!superres_scale_ok(rows, cols, sp.scale)) return fail(c, RSDSFM_ERR_INVALID, kSuperresScaleMessage);
+    if (!d_images || !d_depths_colmajor || !d_R_rows9 || !d_t_rows3) return fail(c, RSDSFM_ERR_INVALID, "superres frame: null source array");
+    for (int k = 0; k < nsrc; ++k)
+        if (!d_images[k] || !d_depths_colmajor[k] || !d_R_rows9[k] || !d_t_rows3[k] || d_images[k] == d_image_out || d_images[k] == d_mask_out ||
+            (d_weight_or_null && d_images[k] == d_weight_or_null) || ((uintptr_t)d_images[k] & 3u))
+            return fail(c, RSDSFM_ERR_INVALID, "superres frame: null, misaligned or aliased source pointer");
+    if (!M || !m || !superres_finite_all(M, 9 * nsrc) || !superres_finite_all(m, 3 * nsrc))
+        return fail(c, RSDSFM_ERR_INVALID, "superres frame: the poses (M, m) must be given and finite");
+    rc = superres_outputs_check(c, d_image_out, d_mask_out, d_weight_or_null, d_counts3_or_null);
+    if (rc != RSDSFM_OK) return rc;
+    const int32_t full[4] = {0, 0, rows, cols};
+    const int32_t* window = window_or_null ? window_or_null : full;
+    if (!superres_window_ok(window, rows, cols))
+        return fail(c, RSDSFM_ERR_INVALID, "superres frame: the window (r0, c0, h, w) needs h >= 1, w >= 1 and must lie inside the frame");
+    DenseWs* ws = nullptr;
+    rc = superres_ws(c, rows, cols, sp.scale, &ws);
+    if (rc != RSDSFM_OK) return rc;
+    const int orows = sp.scale * rows, ocols = sp.scale * cols;
+    const size_t P = blend_plane_bytes(orows, ocols);
+    uint8_t* b = ws->d_superres;
+    uint8_t *rprox = b, *rvalid = b + P, *rbil = b + 2 * P, *rnear = b + 5 * P, *lprox = b + 8 * P, *lbil = b + 9 * P, *lnear = b + 12 * P;
+    uint16_t* cells = reinterpret_cast<uint16_t*>(b + 15 * P);
+    uint64_t* record = reinterpret_cast<uint64_t*>(b + 23 * P);
+    // the public entry points themselves, so that they run the code they run alone
+    rc = rsdsfm_superres_render_dev(ctx, d_images[0], channels, d_depths_colmajor[0], d_R_rows9[0], d_t_rows3[0], fx, fy, cx, cy, rows, cols, mode, q5_mode, iterations, M, m,
+                                    sp.scale, window, rbil, rnear, rprox, rvalid);
+    if (rc != RSDSFM_OK) return rc;
+    if (nsrc == 1)
+        return rsdsfm_superres_accumulate_dev(ctx, rbil, rnear, rprox, nullptr, nullptr, nullptr, channels, orows, ocols, nullptr, sp.min_overlap, sp.gain_mode, sp.strength,
+                                              nullptr, 1, 1, d_image_out, d_mask_out, d_weight_or_null, d_counts3_or_null);
+    for (int k = 1; k < nsrc; ++k) {
+        rc = rsdsfm_superres_render_dev(ctx, d_images[k], channels, d_depths_colmajor[k], d_R_rows9[k], d_t_rows3[k], fx, fy, cx, cy, rows, cols, mode, q5_mode, iterations,
+                                        M + 9 * k, m + 3 * k, sp.scale, window, lbil, lnear, lprox, nullptr);
+        if (rc != RSDSFM_OK) return rc;
+        rc = rsdsfm_seam_overlap_sums_dev(ctx, rbil, rvalid, lbil, lprox, channels, orows, ocols, record);
+        if (rc != RSDSFM_OK) return rc;
+        rc = rsdsfm_superres_accumulate_dev(ctx, rbil, rnear, rprox, lbil, lnear, lprox, channels, orows, ocols, record, sp.min_overlap, sp.gain_mode, sp.strength, cells,
+                                            k == 1, k == nsrc - 1, d_image_out, d_mask_out, d_weight_or_null, d_counts3_or_null);
+        if (rc != RSDSFM_OK) return rc;
+    }
+    return RSDSFM_OK;
+}
+
+int rsdsfm_superres_video_dev(rsdsfm_ctx* ctx, const uint8_t* const* d_frames, int32_t nsources, int32_t rows, int32_t cols, int32_t channels, double fx, double fy,
+                              double cx, double cy, const double* const* d_depth_maps, const double* const* d_R, const double* const* d_t, const double* A,
+                              const double* c_, const double* A_path, const double* c_path, const double* scales, int mode, int q5_mode, int32_t iterations,
+                              const rsdsfm_superres_params* params_or_null, const int32_t* window_or_null, uint8_t* const* d_out_images, uint8_t* const* d_out_masks,
+                              uint8_t* const* d_out_weights_or_null, int64_t* counts_or_null) {
+    if (!ctx) return RSDSFM_ERR_INVALID;
+    Ctx* c = &ctx->c;
+    DeviceGuard device_guard_(c);
+    if (nsources < 1) return fail(c, RSDSFM_ERR_INVALID, "superres video: nsources must be >= 1");
+    if (!d_frames || !d_depth_maps || !d_R || !d_t || !A || !c_ || !A_path || !c_path || !scales) return fail(c, RSDSFM_ERR_INVALID, "superres video: null array");
+    if (!all_set(d_frames, nsources) || !all_set(d_depth_maps, nsources) || !all_set(d_R, nsources) || !all_set(d_t, nsources))
+        return fail(c, RSDSFM_ERR_INVALID, "superres video: every source needs its frame, depth map and pose table");
+    if (!d_out_images || !d_out_masks || !all_set(d_out_images, nsources) || !all_set(d_out_masks, nsources) ||
+        (d_out_weights_or_null && !all_set(d_out_weights_or_null, nsources)))
+        return fail(c, RSDSFM_ERR_INVALID, "superres video: every frame needs its image and its mask (and its weight plane when the array is passed)");
+    rsdsfm_superres_params sp;
+    if (!superres_params_resolve(params_or_null, &sp)) return fail(c, RSDSFM_ERR_INVALID, kSuperresParamsMessage);
+    for (int q = 0; q < nsources; ++q)  // an output may not be a frame of the clip: a later frame call still reads it
+        for (int n = 0; n < nsources; ++n)
+            if (d_frames[n] == d_out_images[q] || d_frames[n] == d_out_masks[q] || (d_out_weights_or_null && d_frames[n] == d_out_weights_or_null[q]))
+                return fail(c, RSDSFM_ERR_INVALID, "superres video: an output plane may not be a frame of the clip");
+    // every frame's sources and poses first: a refused pose enqueues nothing
+    std::vector<SuperresPlan> plans(nsources);
+    for (int q = 0; q < nsources; ++q)
+        if (!superres_plan(A, c_, A_path, c_path, scales, nsources, q, sp.radius, &plans[q]))
+            return fail(c, RSDSFM_ERR_INVALID, "superres video: the poses must be finite and every listed source's scale finite and positive");
+    int64_t* d_cnt = nullptr;
+    if (counts_or_null) RSDSFM_HIP_CHECK(c, hipMalloc(reinterpret_cast<void**>(&d_cnt), 3 * sizeof(int64_t) * (size_t)nsources));
+    int rc = RSDSFM_OK;
+    for (int q = 0; q < nsources && rc == RSDSFM_OK; ++q) {  // the public entry point itself, so that it runs the code it runs alone
+        const SuperresPlan& p = plans[q];
+        const uint8_t* img[kSuperresSourcesMax];
+        const double *map[kSuperresSourcesMax], *R[kSuperresSourcesMax], *t[kSuperresSourcesMax];
+        for (int k = 0; k < p.nsrc; ++k) {
+            img[k] = d_frames[p.src[k]];
+            map[k] = d_depth_maps[p.src[k]];
+            R[k] = d_R[p.src[k]];
+            t[k] = d_t[p.src[k]];
+        }
+        rc = rsdsfm_superres_frame_dev(ctx, img, channels, map, R, t, fx, fy, cx, cy, rows, cols, mode, q5_mode, iterations, p.nsrc, p.M, p.m, params_or_null, window_or_null,
+                                       d_out_images[q], d_out_masks[q], d_out_weights_or_null ? d_out_weights_or_null[q] : nullptr, d_cnt ? d_cnt + 3 * (size_t)q : nullptr);
+    }
+    if (d_cnt) {
+        hipError_t e = rc == RSDSFM_OK ? hipMemcpyAsync(counts_or_null, d_cnt, 3 * sizeof(int64_t) * (size_t)nsources, hipMemcpyDeviceToHost, c->stream) : hipSuccess;
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        (void)hipFree(d_cnt);
+        if (rc == RSDSFM_OK) RSDSFM_HIP_CHECK(c, e);
+    }
+    return rc;
+}
+
+}  // extern "C"

@@ -209,7 +209,7 @@ def evaluate_real_sequence(solver, frames, camera="galaxy", gamma=0.95, out_dir=
                            check_flow=False, trajectory=False, link_tol=None, min_links=None, fuse=False, fuse_tol=None, stabilize=False, smooth_sigma=None,
                            smooth_translation=True, fill=0, crop=False, crop_margin=None, crop_max_empty=0, blend=False, blend_feather=None,
                            blend_gain=True, inpaint=False, last_frame=False, occlusion=False, occlusion_tol=None, occlusion_search=False, retime=None,
-                           shutter=None, denoise=None):
+                           shutter=None, denoise=None, superres=None):
     """evaluate_real_run's real-world branch (main.cc:341-361, 364-531) for a clip: `frames` is <prefix>frame1.png ... frameN.png (the
     prefix, or a list of paths), or the frames themselves (an (N, rows, cols[, 3]) uint8 array or a list of arrays; 2-D frames are gray).
     By default ONE call does the clip (Solver.rectify_video_dev): the batched DeepFlow of every consecutive pair, the pipelined solve of every pair p
@@ -295,7 +295,14 @@ def evaluate_real_sequence(solver, frames, camera="galaxy", gamma=0.95, out_dir=
     (Solver.denoise_video_dev, tests/denoise_spec_numpy.py; strength None: the default, 12; the fused maps with fuse=True, the neighbours through
     the occlusion test with occlusion=True): the returned dict also has stab_denoised, denoise_masks, denoise_weights (lists of frames; the weight
     is 16 for the own frame plus up to 16 per neighbour) and denoise_counts ((frames, 3) int64: [unset, own only, averaged]); out_dir receives
-    stabilized_denoised_<p>.png and denoise.csv.  Without the keyword every key and file is what it was."""
+    stabilized_denoised_<p>.png and denoise.csv.  Without the keyword every key and file is what it was.
+    superres=scale or (scale, K) (needs stabilize=True: ValueError otherwise): behind everything else, every stabilised frame once more on a grid
+    `scale` times finer (1 .. 4), merged from itself and its K neighbours on either side (1 .. 7, default 2), each rendered alone into the frame's
+    camera on the SMOOTHED path (Solver.superres_video_dev, tests/superres_spec_numpy.py; the fused maps with fuse=True): the returned dict also
+    has superres, superres_masks (lists of scale rows x scale cols frames) and superres_counts ((frames, 3) int64: [unset, own only, merged]);
+    out_dir receives superres_<p>.png and superres.csv.  Without the keyword every key and file is what it was."""
+    if superres is not None and not stabilize:
+        raise ValueError("superres needs stabilize=True: it merges the frames of the stabilised clip")
     if denoise is not None and not stabilize:
         raise ValueError("denoise needs stabilize=True: it averages the frames of the stabilised clip")
     if shutter is not None and retime is None:
@@ -609,6 +616,15 @@ def evaluate_real_sequence(solver, frames, camera="galaxy", gamma=0.95, out_dir=
                                                   occlusion_tol_q16=occ_q16 if occlusion else 0, mode=mode)
                     traj.update(stab_denoised=[t.cpu().numpy() for t in d_dn], denoise_masks=[t.cpu().numpy() for t in d_dnmasks],
                                 denoise_weights=[t.cpu().numpy() for t in d_dnw], denoise_counts=dn["counts"])
+                if superres is not None:  # every stabilised frame once more, on a finer grid, merged with its neighbours
+                    sr_scale, sr_radius = (int(superres), None) if np.ndim(superres) == 0 else (int(superres[0]), int(superres[1]))
+                    fine = (sr_scale * rows, sr_scale * cols)
+                    d_sr = [torch.empty(fine + tuple(d_imgs[0].shape[2:]), dtype=torch.uint8, device=dev) for _ in range(nst)]
+                    d_srmasks = [torch.empty(fine, dtype=torch.uint8, device=dev) for _ in range(nst)]
+                    torch.cuda.synchronize()
+                    sr = solver.superres_video_dev(ptrs(d_imgs), rows, cols, channels, K, ptrs(d_src[:nst]), ptrs(d_Rs[:nst]), ptrs(d_ts[:nst]), traj["A"], traj["c"], A_s,
+                                                   c_s, st_scales, ptrs(d_sr), ptrs(d_srmasks), None, scale=sr_scale, radius=sr_radius, mode=mode)
+                    traj.update(superres=[t.cpu().numpy() for t in d_sr], superres_masks=[t.cpu().numpy() for t in d_srmasks], superres_counts=sr["counts"])
     if out_dir:
         os.makedirs(out_dir, exist_ok=True)
         lines = ["pair,v_x,v_y,v_z,w_x,w_y,w_z,k,inliers"]
@@ -704,6 +720,13 @@ def evaluate_real_sequence(solver, frames, camera="galaxy", gamma=0.95, out_dir=
                 formats.write_png(os.path.join(out_dir, "stabilized_denoised_%d.png" % p), traj["stab_denoised"][p])
                 rows_.append(",".join([str(p)] + [str(int(x)) for x in traj["denoise_counts"][p]] + ["%.4f" % float(traj["denoise_weights"][p].mean())]))
             with open(os.path.join(out_dir, "denoise.csv"), "w") as fh:
+                fh.write("\n".join(rows_) + "\n")
+        if superres is not None:
+            rows_ = ["pair,unset,own_only,merged"]
+            for p in range(nst):
+                formats.write_png(os.path.join(out_dir, "superres_%d.png" % p), traj["superres"][p])
+                rows_.append(",".join([str(p)] + [str(int(x)) for x in traj["superres_counts"][p]]))
+            with open(os.path.join(out_dir, "superres.csv"), "w") as fh:
                 fh.write("\n".join(rows_) + "\n")
         if inpaint:
             rows_ = ["pair,stage,inpainted"]
