@@ -135,12 +135,12 @@ class RansacOut(C.Structure):
 
 
 def declared_symbols():
-    """Names of every function include/rsdsfm.h, include/rsdsfm_retime.h, include/rsdsfm_shutter.h, include/rsdsfm_denoise.h and
-    include/rsdsfm_superres.h declare (used by the CPU symbol-export test)."""
+    """Names of every function include/rsdsfm.h, include/rsdsfm_retime.h, include/rsdsfm_shutter.h, include/rsdsfm_denoise.h,
+    include/rsdsfm_superres.h and include/rsdsfm_plate.h declare (used by the CPU symbol-export test)."""
     import re
 
     txt = "".join(open(os.path.join(os.path.dirname(HEADER_PATH), name)).read()
-                  for name in (os.path.basename(HEADER_PATH), "rsdsfm_retime.h", "rsdsfm_shutter.h", "rsdsfm_denoise.h", "rsdsfm_superres.h"))
+                  for name in (os.path.basename(HEADER_PATH), "rsdsfm_retime.h", "rsdsfm_shutter.h", "rsdsfm_denoise.h", "rsdsfm_superres.h", "rsdsfm_plate.h"))
     txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
     return sorted(set(re.findall(r"\b(rsdsfm_[a-z0-9_]+)\s*\(", txt)))
 
@@ -3347,6 +3347,158 @@ class _SuperresMixin:
 
 
 for _name, _fn in list(vars(_SuperresMixin).items()):
+    if not _name.startswith("__"):
+        setattr(Solver, _name, _fn)
+
+
+# ---------------------------------------------------------------------------------------------------
+# the clean plate: the per-pixel median of a frame and its registered neighbours, and a moving flag (include/rsdsfm_plate.h)
+# ---------------------------------------------------------------------------------------------------
+PLATE_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "rsdsfm_plate.h")
+PLATE_RADIUS_MAX = 7
+PLATE_LAYERS_MAX = 14
+PLATE_UNSET, PLATE_STATIC, PLATE_MOVING, PLATE_UNDECIDED = 0, 1, 2, 3  # the flag plane's bytes and the counters' order
+
+
+class PlateParams(C.Structure):
+    _fields_ = [("radius", C.c_int32), ("threshold", C.c_int32), ("min_votes", C.c_int32), ("gain_mode", C.c_int32), ("occlusion", C.c_int32),
+                ("occlusion_tol_q16", C.c_int32), ("struct_bytes", C.c_int32), ("reserved0", C.c_int32), ("min_overlap", C.c_int64), ("reserved", C.c_int32 * 4)]
+
+
+def plate_declared_symbols():
+    """Names of every function include/rsdsfm_plate.h declares"""
+    import re
+
+    txt = open(PLATE_HEADER_PATH).read()
+    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
+    return sorted(set(re.findall(r"\b(rsdsfm_[a-z0-9_]+)\s*\(", txt)))
+
+
+def _plate_params(radius=None, threshold=None, min_votes=None, gain=True, occlusion=False, occlusion_tol_q16=0, min_overlap=None):
+    """a PlateParams with the given values over the defaults (None: the default)"""
+    p = PlateParams()
+    if load_library().rsdsfm_plate_params_init(C.byref(p)) != OK:
+        raise RsdsfmError("rsdsfm_plate_params_init failed")
+    if radius is not None:
+        p.radius = int(radius)
+    if threshold is not None:
+        p.threshold = int(threshold)
+    if min_votes is not None:
+        p.min_votes = int(min_votes)
+    if min_overlap is not None:
+        p.min_overlap = int(min_overlap)
+    p.gain_mode, p.occlusion, p.occlusion_tol_q16 = 0 if gain else 1, int(occlusion), int(occlusion_tol_q16)
+    return p
+
+
+def plate_default_params():
+    """the plate's defaults as a dict: radius = 2, threshold = 24, min_votes = 3, min_overlap = 1024 (rsdsfm_plate_params_init); choices, not
+    measurements"""
+    p = _plate_params()
+    return dict(radius=p.radius, threshold=p.threshold, min_votes=p.min_votes, min_overlap=p.min_overlap, gain_mode=p.gain_mode, occlusion=p.occlusion)
+
+
+def plate_launches(rows, cols, nsrc):
+    """kernel launches of one plate_frame_dev call on nsrc sources: nsrc stabilize_window_launches + (nsrc - 1) + 1 (rsdsfm_plate_launches; host
+    only)"""
+    n = load_library().rsdsfm_plate_launches(C.c_int32(rows), C.c_int32(cols), C.c_int32(nsrc))
+    if n < 0:
+        raise RsdsfmError("rsdsfm_plate_launches failed (%d): rows and cols in [2, 16384], nsrc in [1, 15]" % n)
+    return n
+
+
+def plate_median_launches():
+    """kernel launches of one plate_median_dev call: 1 (rsdsfm_plate_median_launches; host only)"""
+    return int(load_library().rsdsfm_plate_median_launches())
+
+
+class _PlateMixin:
+    def plate_median_dev(self, d_ref, d_ref_mask, d_layers, d_layer_masks, channels, rows, cols, d_image_out, d_mask_out, d_votes=None, d_moving=None, d_counts4=None,
+                         d_sums8=None, min_overlap=0, gain_mode=0, threshold=0, min_votes=0, nlayers=None):
+        """the per-pixel, per-channel lower median of the reference and 0 .. 14 layers (rsdsfm_plate_median_dev; tests/plate_spec_numpy.py):
+        d_layers, d_layer_masks lists of device pointers (None: no layers), d_sums8 the layers' records, nlayers x 8 device uint64 (None: no
+        gain).  The plate into d_image_out, 1 into d_mask_out where anything voted, the number of candidates into d_votes, the flag 0 unset /
+        1 static / 2 moving / 3 undecided into d_moving and the four counts into d_counts4 (four device int64).  One launch, enqueued on the
+        context's stream."""
+        n = (len(d_layers) if d_layers is not None else 0) if nlayers is None else int(nlayers)
+        arr = lambda x: _ptr_array(list(x)) if x is not None and len(x) else None
+        self._check(self.lib.rsdsfm_plate_median_dev(self._ctx, _dp(d_ref), _dp(d_ref_mask), arr(d_layers), arr(d_layer_masks), C.c_int32(n), C.c_int32(channels),
+                                                     C.c_int32(rows), C.c_int32(cols), _np0(d_sums8), C.c_int64(min_overlap), C.c_int32(gain_mode), C.c_int32(threshold),
+                                                     C.c_int32(min_votes), _np0(d_image_out), _np0(d_mask_out), _np0(d_votes), _np0(d_moving), _np0(d_counts4)),
+                    "rsdsfm_plate_median_dev")
+
+    def plate_median(self, ref, ref_mask, layers, records=None, min_overlap=0, gain_mode=0, threshold=0, min_votes=0, device=0):
+        """host convenience around plate_median_dev: the reference (image, mask), layers a list of 0 .. 14 (image, mask) pairs of host arrays,
+        records None or (nlayers, 8) uint64
+        -> (image, mask, votes, moving (rows, cols) uint8, counts (4,) int64 [unset, static, moving, undecided])"""
+        import torch
+
+        ref = np.ascontiguousarray(ref, dtype=np.uint8)
+        rows, cols = ref.shape[:2]
+        ch = 1 if ref.ndim == 2 else ref.shape[2]
+        dev = torch.device("cuda", device)
+        with torch.cuda.device(dev):
+            up = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.uint8)).to(dev)
+            d_ref, d_rm = up(ref), up(ref_mask)
+            d_l = [(up(i), up(m)) for i, m in layers]
+            d_rec = None
+            if records is not None and len(layers):
+                d_rec = torch.from_numpy(np.ascontiguousarray(records, dtype=np.uint64).reshape(len(layers), 8).view(np.int64)).to(dev)
+            d_out, d_mask = torch.empty_like(d_ref), torch.empty((rows, cols), dtype=torch.uint8, device=dev)
+            d_v, d_f, d_cnt = torch.empty_like(d_mask), torch.empty_like(d_mask), torch.zeros(4, dtype=torch.int64, device=dev)
+            torch.cuda.synchronize()
+            self.plate_median_dev(d_ref.data_ptr(), d_rm.data_ptr(), [i.data_ptr() for i, _ in d_l], [m.data_ptr() for _, m in d_l], ch, rows, cols, d_out.data_ptr(),
+                                  d_mask.data_ptr(), d_v.data_ptr(), d_f.data_ptr(), d_cnt.data_ptr(), d_rec.data_ptr() if d_rec is not None else None, min_overlap,
+                                  gain_mode, threshold, min_votes)
+            self.synchronize()
+            return d_out.cpu().numpy(), d_mask.cpu().numpy(), d_v.cpu().numpy(), d_f.cpu().numpy(), d_cnt.cpu().numpy()
+
+    def plate_frame_dev(self, d_images, channels, d_depth_maps, d_R, d_t, K, rows, cols, M, m, d_image, d_mask, d_votes=None, d_moving=None, d_counts4=None, threshold=None,
+                        min_votes=None, gain=True, min_overlap=None, window=None, occlusion=False, occlusion_tol_q16=0, mode=BACKPROJECT_RS, q5_mode=Q5_COMPAT, iterations=0,
+                        params=None):
+        """one clean plate (rsdsfm_plate_frame_dev): d_images, d_depth_maps, d_R, d_t lists of 1 .. 15 device pointers, source 0 the own frame
+        and the others its neighbours; M (nsrc, 3, 3), m (nsrc, 3) every source's pose in the target camera.  The own frame through
+        stabilize_window_frame_dev, every neighbour alone on its own layer of the context's stack with its record by seam_overlap_sums_dev, one
+        plate_median_dev into d_image, d_mask, d_votes, d_moving, d_counts4.  params: a PlateParams passed as it is instead of the keywords.
+        Enqueued on the context's stream."""
+        ns = len(d_images)
+        _need_all(ns, d_depth_maps=d_depth_maps, d_R=d_R, d_t=d_t)
+        Mm, mm = _f64(M).reshape(-1, 9), _f64(m).reshape(-1, 3)
+        if Mm.shape[0] < ns or mm.shape[0] < ns:
+            raise RsdsfmError("plate_frame_dev: every source needs a pose (M, m)")
+        pp = params if params is not None else _plate_params(None, threshold, min_votes, gain, occlusion, occlusion_tol_q16, min_overlap)
+        d = C.c_double
+        arr = lambda x: _ptr_array(list(x)[:ns]) if ns else None
+        self._check(self.lib.rsdsfm_plate_frame_dev(self._ctx, arr(d_images), C.c_int32(channels), arr(d_depth_maps), arr(d_R), arr(d_t), d(K[0]), d(K[1]), d(K[2]), d(K[3]),
+                                                    C.c_int32(rows), C.c_int32(cols), int(mode), int(q5_mode), C.c_int32(iterations), C.c_int32(ns), _p(Mm), _p(mm),
+                                                    C.byref(pp), _window4(window), _dp(d_image), _dp(d_mask), _np0(d_votes), _np0(d_moving), _np0(d_counts4)),
+                    "rsdsfm_plate_frame_dev")
+
+    def plate_video_dev(self, d_frames, rows, cols, channels, K, d_depth_maps, d_R, d_t, A, c, A_path, c_path, scales, d_out, d_out_masks, d_out_votes=None,
+                        d_out_moving=None, want_counts=True, radius=None, threshold=None, min_votes=None, gain=True, min_overlap=None, window=None, occlusion=False,
+                        occlusion_tol_q16=0, mode=BACKPROJECT_RS, q5_mode=Q5_COMPAT, iterations=0):
+        """a solved clip's plates (rsdsfm_plate_video_dev): the clip as denoise_video_dev takes it and walks it; for every frame q the own pose
+        by retime_poses(t = q), the neighbours within `radius` (None: 2) by neighbour_poses on the same path, and plate_frame_dev into d_out[q],
+        d_out_masks[q], d_out_votes[q], d_out_moving[q].  Returns dict(); with want_counts counts (nsources, 4) int64 [unset, static, moving,
+        undecided] -- the call then waits."""
+        ns = len(d_depth_maps)
+        _need_all(ns, d_frames=d_frames, d_R=d_R, d_t=d_t, d_out=d_out, d_out_masks=d_out_masks, d_out_votes=d_out_votes, d_out_moving=d_out_moving)
+        a, cc, ap, cp = _f64(A).reshape(-1, 9), _f64(c).reshape(-1, 3), _f64(A_path).reshape(-1, 9), _f64(c_path).reshape(-1, 3)
+        sc = _f64(scales).reshape(-1)
+        if min(a.shape[0], cc.shape[0], ap.shape[0], cp.shape[0], sc.shape[0]) < ns:
+            raise RsdsfmError("plate_video_dev: every source needs a pose on both paths and a scale")
+        pp = _plate_params(radius, threshold, min_votes, gain, occlusion, occlusion_tol_q16, min_overlap)
+        counts = np.zeros((max(ns, 1), 4), dtype=np.int64) if want_counts else None
+        d = C.c_double
+        arr = lambda x: _ptr_array(list(x)[:ns]) if x is not None and ns else None
+        self._check(self.lib.rsdsfm_plate_video_dev(self._ctx, arr(d_frames), C.c_int32(ns), C.c_int32(rows), C.c_int32(cols), C.c_int32(channels), d(K[0]), d(K[1]),
+                                                    d(K[2]), d(K[3]), arr(d_depth_maps), arr(d_R), arr(d_t), _p(a), _p(cc), _p(ap), _p(cp), _p(sc), int(mode), int(q5_mode),
+                                                    C.c_int32(iterations), C.byref(pp), _window4(window), arr(d_out), arr(d_out_masks), arr(d_out_votes), arr(d_out_moving),
+                                                    _p(counts)), "rsdsfm_plate_video_dev")
+        return dict(counts=counts[:ns]) if want_counts else dict()
+
+
+for _name, _fn in list(vars(_PlateMixin).items()):
     if not _name.startswith("__"):
         setattr(Solver, _name, _fn)
 

@@ -1,0 +1,50 @@
+// plate.hpp -- the clean plate (include/rsdsfm_plate.h): what plate_kernels.hip and plate_host.hip share.
+#pragma once
+
+#include <stddef.h>
+#include <stdint.h>
+
+#include "../../include/rsdsfm_plate.h"
+#include "denoise.hpp"
+#include "rsdsfm_internal.hpp"
+#include "stabilize_blend.hpp"
+
+namespace rsdsfm {
+
+constexpr int kPlateRadiusMax = RSDSFM_PLATE_RADIUS_MAX;
+constexpr int kPlateLayersMax = RSDSFM_PLATE_LAYERS_MAX;
+constexpr int kPlateSourcesMax = 1 + kPlateLayersMax;  // 15 candidates at most: the own frame and 14 neighbours
+constexpr int kPlateThresholdDefault = RSDSFM_PLATE_THRESHOLD_DEFAULT, kPlateThresholdMax = 255;
+constexpr int kPlateMinVotesDefault = RSDSFM_PLATE_MIN_VOTES_DEFAULT, kPlateMinVotesMax = kPlateSourcesMax;
+static_assert(kPlateLayersMax == kDenoiseLayersMax, "the plate walks a clip as the denoise does");
+
+// the layer counts the kernel is compiled for: a call with L layers runs the smallest of them that holds L, the layers beyond L never read
+constexpr int kPlateSizes[] = {0, 2, 4, 7, 14};
+constexpr int kPlateNumSizes = 5;
+
+// the kernel's argument: the planes travel in the kernel argument itself (15 + 15 pointers, 1 record pointer), no pointer table in global memory
+struct PlateArgs {
+    const unsigned char* ref;
+    const unsigned char* rmask;
+    const unsigned char* layer[kPlateLayersMax];
+    const unsigned char* lmask[kPlateLayersMax];
+    const unsigned long long* sums;  // nlayers x 8, or NULL
+    unsigned char* out;
+    unsigned char* mask_out;
+    unsigned char* votes;   // or NULL
+    unsigned char* moving;  // or NULL
+    unsigned long long* counts;  // [unset, static, moving, undecided], or NULL
+    long long min_overlap;
+    int rows, cols, nlayers, gain_mode;
+    unsigned threshold, min_votes;
+};
+
+// DenseWs::d_plate: [reference mask: P][reference source: P][reference image: 3 P][records: 14 x 8 uint64][layer 0 mask: P][layer 0 image: 3 P]
+// [layer 1 ...], P = blend_plane_bytes (a multiple of 8, so the records are 8-byte aligned and every plane 4)
+inline size_t plate_records_bytes() { return (size_t)kPlateLayersMax * 8 * sizeof(uint64_t); }
+inline size_t plate_ws_bytes(int rows, int cols, int layers) { return (5 + 4 * (size_t)layers) * blend_plane_bytes(rows, cols) + plate_records_bytes(); }
+
+// the median on c->stream (arguments checked by the caller): the counters zeroed by a memset when passed, then one launch
+int plate_median_launch(Ctx* c, const PlateArgs& args, int channels);
+
+}  // namespace rsdsfm

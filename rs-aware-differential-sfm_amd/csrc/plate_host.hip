@@ -1,0 +1,302 @@
+// plate_host.hip -- C ABI of the clean plate (include/rsdsfm_plate.h; tests/plate_spec_numpy.py is the definition, plate_kernels.hip the
+// kernel): the median call, the frame call, which CALLS the public render entry points, the record call and the median one after another on
+// planes of the context's dense workspace, and the clip call, which calls the frame call per frame.
+#include <cmath>
+#include <vector>
+
+#include "plate.hpp"
+#include "rectify_dense.hpp"
+#include "rsdsfm_internal.hpp"
+#include "sequence_host.hpp"
+#include "stabilize_blend.hpp"
+#include "stabilize_visible.hpp"
+
+namespace rsdsfm {
+namespace {
+
+rsdsfm_plate_params plate_defaults() {
+    return rsdsfm_plate_params{RSDSFM_PLATE_RADIUS_DEFAULT, kPlateThresholdDefault, kPlateMinVotesDefault, 0, 0, 0, (int32_t)sizeof(rsdsfm_plate_params), 0, kMinOverlapDefault,
+                               {0, 0, 0, 0}};
+}
+
+// the params with every 0 of radius, threshold, min_votes and min_overlap replaced by its default, or the defaults for NULL; false: refused
+bool plate_params_resolve(const rsdsfm_plate_params* in, rsdsfm_plate_params* out) {
+    *out = in ? *in : plate_defaults();
+    if (out->struct_bytes != 0 && out->struct_bytes != (int32_t)sizeof(rsdsfm_plate_params)) return false;
+    if (out->radius == 0) out->radius = RSDSFM_PLATE_RADIUS_DEFAULT;
+    if (out->threshold == 0) out->threshold = kPlateThresholdDefault;
+    if (out->min_votes == 0) out->min_votes = kPlateMinVotesDefault;
+    if (out->min_overlap == 0) out->min_overlap = kMinOverlapDefault;
+    return out->radius >= 1 && out->radius <= kPlateRadiusMax && out->threshold >= 1 && out->threshold <= kPlateThresholdMax && out->min_votes >= 1 &&
+           out->min_votes <= kPlateMinVotesMax && out->min_overlap >= 0 && (out->gain_mode == 0 || out->gain_mode == 1) && (out->occlusion == 0 || out->occlusion == 1) &&
+           out->occlusion_tol_q16 >= 0 && out->occlusion_tol_q16 <= kVisibleTolQ16Max;
+}
+
+const char* const kPlateParamsMessage =
+    "rsdsfm_plate_params: radius in [1, 7] or 0, threshold in [1, 255] or 0, min_votes in [1, 15] or 0, gain_mode 0 or 1, occlusion 0 or 1, occlusion_tol_q16 in [0, 65536], "
+    "min_overlap >= 0, struct_bytes 0 or sizeof (use rsdsfm_plate_params_init)";
+
+bool plate_size_ok(int rows, int cols) { return rows >= 2 && cols >= 2 && rows <= 16384 && cols <= 16384; }
+
+bool plate_finite_all(const double* a, int n) {
+    for (int i = 0; i < n; ++i)
+        if (!std::isfinite(a[i])) return false;
+    return true;
+}
+
+// the argument checks of the outputs, for the median call and, before anything is enqueued, for the frame call (whose input planes are the context's)
+int plate_outputs_check(Ctx* c, const uint8_t* d_image_out, const uint8_t* d_mask_out, const uint8_t* d_votes, const uint8_t* d_moving, const int64_t* d_counts4) {
+    if (!d_image_out || !d_mask_out) return fail(c, RSDSFM_ERR_INVALID, "plate: null output plane");
+    const void* o[5] = {d_image_out, d_mask_out, d_votes, d_moving, d_counts4};
+    for (int i = 0; i < 5; ++i)
+        for (int j = i + 1; j < 5; ++j)
+            if (o[i] && o[i] == o[j]) return fail(c, RSDSFM_ERR_INVALID, "plate: the output planes must be distinct");
+    if (((uintptr_t)d_image_out | (uintptr_t)d_mask_out | (uintptr_t)d_votes | (uintptr_t)d_moving) & 3u)
+        return fail(c, RSDSFM_ERR_INVALID, "plate: every plane must be 4-byte aligned");
+    if ((uintptr_t)d_counts4 & 7u) return fail(c, RSDSFM_ERR_INVALID, "plate: the counters must be 8-byte aligned");
+    return RSDSFM_OK;
+}
+
+// the workspace's reference planes, records and a stack of at least `layers` layers, made when first asked for and again when more layers are asked for
+int plate_ws(Ctx* c, int rows, int cols, int layers, DenseWs** ws) {
+    const int rc = rectify_dense_ws(c, rows, cols, ws);  // a size change releases them with the rest
+    if (rc != RSDSFM_OK) return rc;
+    DenseWs* w = *ws;
+    if (w->d_plate && w->plate_layers < layers) {  // behind whatever the stream still runs on the smaller stack
+        RSDSFM_HIP_CHECK(c, hipStreamSynchronize(c->stream));
+        (void)hipFree(w->d_plate);
+        w->d_plate = nullptr;
+        w->plate_layers = 0;
+    }
+    if (!w->d_plate) {
+        if (hipMalloc(reinterpret_cast<void**>(&w->d_plate), plate_ws_bytes(rows, cols, layers)) != hipSuccess) {
+            w->d_plate = nullptr;
+            return fail(c, RSDSFM_ERR_HIP, "plate: no memory for the reference planes and the stack of layers");
+        }
+        w->plate_layers = layers;
+    }
+    return RSDSFM_OK;
+}
+
+// one frame's host part for the clip call: the sources (the own frame first) and their poses
+struct PlatePlan {
+    int nsrc = 0;
+    int32_t src[kPlateSourcesMax];
+    double M[9 * kPlateSourcesMax], m[3 * kPlateSourcesMax];
+};
+
+bool plate_plan(const double* A, const double* c_, const double* A_path, const double* c_path, const double* scales, int nsources, int q, int radius, PlatePlan* plan) {
+    int32_t src2[2], nsrc = 0, wq = 0, ids[kPlateLayersMax], count = 0;
+    double M18[18], m6[6], At[9], ct[3];
+    if (rsdsfm_retime_poses(A, c_, A_path, c_path, scales, nsources, (double)q, src2, &nsrc, &wq, M18, m6, At, ct) != RSDSFM_OK || nsrc != 1) return false;
+    plan->src[0] = q;
+    for (int k = 0; k < 9; ++k) plan->M[k] = M18[k];
+    for (int k = 0; k < 3; ++k) plan->m[k] = m6[k];
+    if (nsources > 1 && rsdsfm_neighbour_poses(A, c_, A_path, c_path, scales, nsources, q, radius, plan->src + 1, ids, plan->M + 9, plan->m + 3, &count) != RSDSFM_OK)
+        return false;
+    plan->nsrc = 1 + count;
+    return plate_finite_all(plan->M, 9 * plan->nsrc) && plate_finite_all(plan->m, 3 * plan->nsrc);
+}
+
+const char* const kPlatePlanMessage = "plate video: the poses must be finite and every listed source's scale finite and positive";
+
+}  // namespace
+}  // namespace rsdsfm
+
+using namespace rsdsfm;
+
+extern "C" {
+
+int rsdsfm_plate_params_init(rsdsfm_plate_params* params) {
+    if (!params) return RSDSFM_ERR_INVALID;
+    *params = plate_defaults();
+    return RSDSFM_OK;
+}
+
+int rsdsfm_plate_median_launches(void) { return 1; }
+
+int rsdsfm_plate_launches(int32_t rows, int32_t cols, int32_t nsrc) {
+    if (nsrc < 1 || nsrc > kPlateSourcesMax) return RSDSFM_ERR_INVALID;
+    const int one = rsdsfm_stabilize_window_launches(rows, cols);
+    if (one < 0) return one;
+    return nsrc * one + (nsrc - 1) + rsdsfm_plate_median_launches();
+}
+
+int rsdsfm_plate_median_dev(rsdsfm_ctx* ctx, const uint8_t* d_ref_image, const uint8_t* d_ref_mask, const uint8_t* const* d_layer_images,
+                            const uint8_t* const* d_layer_masks, int32_t nlayers, int32_t channels, int32_t rows, int32_t cols, const uint64_t* d_sums8_or_null,
+                            int64_t min_overlap, int32_t gain_mode, int32_t threshold, int32_t min_votes, uint8_t* d_image_out, uint8_t* d_mask_out,
+                            uint8_t* d_votes_or_null, uint8_t* d_moving_or_null, int64_t* d_counts4_or_null) {
+    if (!ctx) return RSDSFM_ERR_INVALID;
+    Ctx* c = &ctx->c;
+    DeviceGuard device_guard_(c);
+    if (!plate_size_ok(rows, cols)) return fail(c, RSDSFM_ERR_INVALID, "plate: rows and cols must be in [2, 16384]");
+    if (channels != 1 && channels != 3) return fail(c, RSDSFM_ERR_INVALID, "plate: channels must be 1 or 3");
+    if (nlayers < 0 || nlayers > kPlateLayersMax) return fail(c, RSDSFM_ERR_INVALID, "plate median: nlayers must be in [0, 14]");
+    if (min_overlap < 0 || (gain_mode != 0 && gain_mode != 1) || threshold < 0 || threshold > kPlateThresholdMax || min_votes < 0 || min_votes > kPlateMinVotesMax)
+        return fail(c, RSDSFM_ERR_INVALID,
+                    "plate median: min_overlap must be >= 0, gain_mode 0 or 1, threshold in [1, 255] (0: the default, 24) and min_votes in [1, 15] (0: the default, 3)");
+    int rc = plate_outputs_check(c, d_image_out, d_mask_out, d_votes_or_null, d_moving_or_null, d_counts4_or_null);
+    if (rc != RSDSFM_OK) return rc;
+    if (!d_ref_image || !d_ref_mask || d_ref_image == d_ref_mask) return fail(c, RSDSFM_ERR_INVALID, "plate median: the reference needs its image and its mask");
+    if (nlayers > 0 && (!d_layer_images || !d_layer_masks)) return fail(c, RSDSFM_ERR_INVALID, "plate median: the layers need their arrays of images and masks");
+    if (((uintptr_t)d_ref_image | (uintptr_t)d_ref_mask) & 3u) return fail(c, RSDSFM_ERR_INVALID, "plate: every plane must be 4-byte aligned");
+    if ((uintptr_t)d_sums8_or_null & 7u) return fail(c, RSDSFM_ERR_INVALID, "plate median: the records must be 8-byte aligned");
+    const void* in[3 + 2 * kPlateLayersMax] = {d_ref_image, d_ref_mask, d_sums8_or_null};
+    int nin = 3;
+    for (int j = 0; j < nlayers; ++j) {
+        const uint8_t *li = d_layer_images[j], *lm = d_layer_masks[j];
+        if (!li || !lm) return fail(c, RSDSFM_ERR_INVALID, "plate median: every layer needs its image and its mask");
+        if (((uintptr_t)li | (uintptr_t)lm) & 3u) return fail(c, RSDSFM_ERR_INVALID, "plate: every plane must be 4-byte aligned");
+        if (li == lm || li == d_ref_image || li == d_ref_mask || lm == d_ref_image || lm == d_ref_mask)
+            return fail(c, RSDSFM_ERR_INVALID, "plate median: the reference's and a layer's planes must be distinct");
+        in[nin++] = li;
+        in[nin++] = lm;
+    }
+    const void* io[5] = {d_image_out, d_mask_out, d_votes_or_null, d_moving_or_null, d_counts4_or_null};
+    for (int i = 0; i < 5; ++i)
+        for (int j = 0; j < nin && io[i]; ++j)
+            if (in[j] == io[i]) return fail(c, RSDSFM_ERR_INVALID, "plate median: an output may not be an input or the records");
+    PlateArgs args{};
+    args.ref = d_ref_image;
+    args.rmask = d_ref_mask;
+    for (int j = 0; j < nlayers; ++j) {
+        args.layer[j] = d_layer_images[j];
+        args.lmask[j] = d_layer_masks[j];
+    }
+    args.sums = nlayers > 0 ? reinterpret_cast<const unsigned long long*>(d_sums8_or_null) : nullptr;
+    args.out = d_image_out;
+    args.mask_out = d_mask_out;
+    args.votes = d_votes_or_null;
+    args.moving = d_moving_or_null;
+    args.counts = reinterpret_cast<unsigned long long*>(d_counts4_or_null);
+    args.min_overlap = min_overlap ? min_overlap : kMinOverlapDefault;
+    args.rows = rows;
+    args.cols = cols;
+    args.nlayers = nlayers;
+    args.gain_mode = gain_mode;
+    args.threshold = (unsigned)(threshold ? threshold : kPlateThresholdDefault);
+    args.min_votes = (unsigned)(min_votes ? min_votes : kPlateMinVotesDefault);
+    return plate_median_launch(c, args, channels);
+}
+
+int rsdsfm_plate_frame_dev(rsdsfm_ctx* ctx, const uint8_t* const* d_images, int32_t channels, const double* const* d_depths_colmajor,
+                           const double* const* d_R_rows9, const double* const* d_t_rows3, double fx, double fy, double cx, double cy, int32_t rows, int32_t cols,
+                           int mode, int q5_mode, int32_t iterations, int32_t nsrc, const double* M, const double* m, const rsdsfm_plate_params* params_or_null,
+                           const int32_t* window_or_null, uint8_t* d_image_out, uint8_t* d_mask_out, uint8_t* d_votes_or_null, uint8_t* d_moving_or_null,
+                           int64_t* d_counts4_or_null) {
+    if (!ctx) return RSDSFM_ERR_INVALID;
+    Ctx* c = &ctx->c;
+    DeviceGuard device_guard_(c);
+    int rc = rectify_dense_check(c, channels, rows, cols, mode, q5_mode, iterations);
+    if (rc != RSDSFM_OK) return rc;
+    if (nsrc < 1 || nsrc > kPlateSourcesMax) return fail(c, RSDSFM_ERR_INVALID, "plate frame: nsrc must be in [1, 15]");
+    rsdsfm_plate_params pp;
+    if (!plate_params_resolve(params_or_null, &pp)) return fail(c, RSDSFM_ERR_INVALID, kPlateParamsMessage);
+    if (!d_images || !d_depths_colmajor || !d_R_rows9 || !d_t_rows3) return fail(c, RSDSFM_ERR_INVALID, "plate frame: null source array");
+    for (int k = 0; k < nsrc; ++k)
+        if (!d_images[k] || !d_depths_colmajor[k] || !d_R_rows9[k] || !d_t_rows3[k] || d_images[k] == d_image_out || d_images[k] == d_mask_out ||
+            (d_votes_or_null && d_images[k] == d_votes_or_null) || (d_moving_or_null && d_images[k] == d_moving_or_null) || ((uintptr_t)d_images[k] & 3u))
+            return fail(c, RSDSFM_ERR_INVALID, "plate frame: null, misaligned or aliased source pointer");
+    if (!M || !m || !plate_finite_all(M, 9 * nsrc) || !plate_finite_all(m, 3 * nsrc))
+        return fail(c, RSDSFM_ERR_INVALID, "plate frame: the poses (M, m) must be given and finite");
+    rc = plate_outputs_check(c, d_image_out, d_mask_out, d_votes_or_null, d_moving_or_null, d_counts4_or_null);
+    if (rc != RSDSFM_OK) return rc;
+    const int32_t full[4] = {0, 0, rows, cols};
+    const int32_t* window = window_or_null ? window_or_null : full;
+    if (window[2] < 1 || window[3] < 1 || window[0] < 0 || window[1] < 0 || (int64_t)window[0] + window[2] > rows || (int64_t)window[1] + window[3] > cols)
+        return fail(c, RSDSFM_ERR_INVALID, "plate frame: the window (r0, c0, h, w) needs h >= 1, w >= 1 and must lie inside the frame");
+    DenseWs* ws = nullptr;
+    const int nl = nsrc - 1;
+    rc = plate_ws(c, rows, cols, nl, &ws);
+    if (rc != RSDSFM_OK) return rc;
+    const size_t plane = (size_t)rows * (size_t)cols, P = blend_plane_bytes(rows, cols);
+    uint8_t* rmask = ws->d_plate;
+    uint8_t* rsource = ws->d_plate + P;
+    uint8_t* rimage = ws->d_plate + 2 * P;
+    uint64_t* records = reinterpret_cast<uint64_t*>(ws->d_plate + 5 * P);
+    uint8_t* stack = ws->d_plate + 5 * P + plate_records_bytes();
+    if (hipMemsetAsync(rimage, 0, plane * (size_t)channels, c->stream) != hipSuccess || hipMemsetAsync(rmask, 0, plane, c->stream) != hipSuccess ||
+        hipMemsetAsync(rsource, 0, plane, c->stream) != hipSuccess)
+        return fail(c, RSDSFM_ERR_HIP, "plate frame: zeroing the reference failed");
+    // the public entry points themselves, so that they run the code they run alone.  The own frame never goes through the occlusion test
+    rc = rsdsfm_stabilize_window_frame_dev(ctx, d_images[0], channels, d_depths_colmajor[0], d_R_rows9[0], d_t_rows3[0], fx, fy, cx, cy, rows, cols, mode, q5_mode, iterations,
+                                           M, m, 1, window, rimage, rmask, rsource, nullptr);
+    if (rc != RSDSFM_OK) return rc;
+    const bool srch = pp.occlusion == 1 && c->occlusion_search == 1;
+    const uint8_t *limages[kPlateLayersMax], *lmasks[kPlateLayersMax];
+    for (int k = 1; k < nsrc; ++k) {
+        uint8_t* lmask = stack + 4 * P * (size_t)(k - 1);  // every neighbour its own layer: the median sees them all at once
+        uint8_t* limage = lmask + P;
+        limages[k - 1] = limage;
+        lmasks[k - 1] = lmask;
+        if (hipMemsetAsync(limage, 0, plane * (size_t)channels, c->stream) != hipSuccess || hipMemsetAsync(lmask, 0, plane, c->stream) != hipSuccess)
+            return fail(c, RSDSFM_ERR_HIP, "plate frame: zeroing a layer failed");
+        const int id = 2;  // no source plane is passed: the id is not written anywhere
+        rc = srch ? rsdsfm_stabilize_search_frame_dev(ctx, d_images[k], channels, d_depths_colmajor[k], d_R_rows9[k], d_t_rows3[k], fx, fy, cx, cy, rows, cols, mode, q5_mode,
+                                                      iterations, M + 9 * k, m + 3 * k, id, window, limage, lmask, nullptr, pp.occlusion_tol_q16, nullptr)
+             : pp.occlusion == 1
+                 ? rsdsfm_stabilize_visible_frame_dev(ctx, d_images[k], channels, d_depths_colmajor[k], d_R_rows9[k], d_t_rows3[k], fx, fy, cx, cy, rows, cols, mode, q5_mode,
+                                                      iterations, M + 9 * k, m + 3 * k, id, window, limage, lmask, nullptr, pp.occlusion_tol_q16, nullptr)
+                 : rsdsfm_stabilize_window_frame_dev(ctx, d_images[k], channels, d_depths_colmajor[k], d_R_rows9[k], d_t_rows3[k], fx, fy, cx, cy, rows, cols, mode, q5_mode,
+                                                     iterations, M + 9 * k, m + 3 * k, id, window, limage, lmask, nullptr, nullptr);
+        if (rc != RSDSFM_OK) return rc;
+        rc = rsdsfm_seam_overlap_sums_dev(ctx, rimage, rsource, limage, lmask, channels, rows, cols, records + 8 * (size_t)(k - 1));
+        if (rc != RSDSFM_OK) return rc;
+    }
+    return rsdsfm_plate_median_dev(ctx, rimage, rmask, nl ? limages : nullptr, nl ? lmasks : nullptr, nl, channels, rows, cols, nl ? records : nullptr, pp.min_overlap,
+                                   pp.gain_mode, pp.threshold, pp.min_votes, d_image_out, d_mask_out, d_votes_or_null, d_moving_or_null, d_counts4_or_null);
+}
+
+int rsdsfm_plate_video_dev(rsdsfm_ctx* ctx, const uint8_t* const* d_frames, int32_t nsources, int32_t rows, int32_t cols, int32_t channels, double fx, double fy,
+                           double cx, double cy, const double* const* d_depth_maps, const double* const* d_R, const double* const* d_t, const double* A,
+                           const double* c_, const double* A_path, const double* c_path, const double* scales, int mode, int q5_mode, int32_t iterations,
+                           const rsdsfm_plate_params* params_or_null, const int32_t* window_or_null, uint8_t* const* d_out_images, uint8_t* const* d_out_masks,
+                           uint8_t* const* d_out_votes_or_null, uint8_t* const* d_out_moving_or_null, int64_t* counts_or_null) {
+    if (!ctx) return RSDSFM_ERR_INVALID;
+    Ctx* c = &ctx->c;
+    DeviceGuard device_guard_(c);
+    if (nsources < 1) return fail(c, RSDSFM_ERR_INVALID, "plate video: nsources must be >= 1");
+    if (!d_frames || !d_depth_maps || !d_R || !d_t || !A || !c_ || !A_path || !c_path || !scales) return fail(c, RSDSFM_ERR_INVALID, "plate video: null array");
+    if (!all_set(d_frames, nsources) || !all_set(d_depth_maps, nsources) || !all_set(d_R, nsources) || !all_set(d_t, nsources))
+        return fail(c, RSDSFM_ERR_INVALID, "plate video: every source needs its frame, depth map and pose table");
+    if (!d_out_images || !d_out_masks || !all_set(d_out_images, nsources) || !all_set(d_out_masks, nsources) ||
+        (d_out_votes_or_null && !all_set(d_out_votes_or_null, nsources)) || (d_out_moving_or_null && !all_set(d_out_moving_or_null, nsources)))
+        return fail(c, RSDSFM_ERR_INVALID, "plate video: every frame needs its image and its mask (and its votes and flag planes when their arrays are passed)");
+    rsdsfm_plate_params pp;
+    if (!plate_params_resolve(params_or_null, &pp)) return fail(c, RSDSFM_ERR_INVALID, kPlateParamsMessage);
+    for (int q = 0; q < nsources; ++q)  // an output may not be a frame of the clip: a later frame call still reads it
+        for (int n = 0; n < nsources; ++n)
+            if (d_frames[n] == d_out_images[q] || d_frames[n] == d_out_masks[q] || (d_out_votes_or_null && d_frames[n] == d_out_votes_or_null[q]) ||
+                (d_out_moving_or_null && d_frames[n] == d_out_moving_or_null[q]))
+                return fail(c, RSDSFM_ERR_INVALID, "plate video: an output plane may not be a frame of the clip");
+    // every frame's sources and poses first: a refused pose enqueues nothing
+    std::vector<PlatePlan> plans(nsources);
+    for (int q = 0; q < nsources; ++q)
+        if (!plate_plan(A, c_, A_path, c_path, scales, nsources, q, pp.radius, &plans[q])) return fail(c, RSDSFM_ERR_INVALID, kPlatePlanMessage);
+    int64_t* d_cnt = nullptr;
+    if (counts_or_null) RSDSFM_HIP_CHECK(c, hipMalloc(reinterpret_cast<void**>(&d_cnt), 4 * sizeof(int64_t) * (size_t)nsources));
+    int rc = RSDSFM_OK;
+    for (int q = 0; q < nsources && rc == RSDSFM_OK; ++q) {  // the public entry point itself, so that it runs the code it runs alone
+        const PlatePlan& p = plans[q];
+        const uint8_t* img[kPlateSourcesMax];
+        const double *map[kPlateSourcesMax], *R[kPlateSourcesMax], *t[kPlateSourcesMax];
+        for (int k = 0; k < p.nsrc; ++k) {
+            img[k] = d_frames[p.src[k]];
+            map[k] = d_depth_maps[p.src[k]];
+            R[k] = d_R[p.src[k]];
+            t[k] = d_t[p.src[k]];
+        }
+        rc = rsdsfm_plate_frame_dev(ctx, img, channels, map, R, t, fx, fy, cx, cy, rows, cols, mode, q5_mode, iterations, p.nsrc, p.M, p.m, params_or_null, window_or_null,
+                                    d_out_images[q], d_out_masks[q], d_out_votes_or_null ? d_out_votes_or_null[q] : nullptr,
+                                    d_out_moving_or_null ? d_out_moving_or_null[q] : nullptr, d_cnt ? d_cnt + 4 * (size_t)q : nullptr);
+    }
+    if (d_cnt) {
+        hipError_t e = rc == RSDSFM_OK ? hipMemcpyAsync(counts_or_null, d_cnt, 4 * sizeof(int64_t) * (size_t)nsources, hipMemcpyDeviceToHost, c->stream) : hipSuccess;
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        (void)hipFree(d_cnt);
+        if (rc == RSDSFM_OK) RSDSFM_HIP_CHECK(c, e);
+    }
+    return rc;
+}
+
+}  // extern "C"

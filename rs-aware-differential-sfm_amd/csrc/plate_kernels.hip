@@ -1,0 +1,388 @@
+// plate_kernels.hip -- the clean plate's median on MI355X (gfx950, wave64): include/rsdsfm_plate.h, defined by tests/plate_spec_numpy.py and
+// reproduced bit for bit.  Integer arithmetic only; every value goes to memory through ordinary stores and atomicAdd.  The project's first image
+// stage that is not a sum: of the accumulate kernels (denoise_kernels.hip) only the tile is borrowed.
+//   plate_median_kernel<CH, NL, FLAG>  the denoise's 2-D tile: a workgroup of kBP threads owns 16 rows x 64 columns, a thread 4 consecutive pixels
+//                               of one row.  The planes are dense (no pitch): every plane is read as ALIGNED dwords of the flat array about the
+//                               thread's bytes and shifted into place (one path for every cols; a dword that would reach past the plane's end is
+//                               read byte by byte).  NL: the layer count the instance is compiled for, one of kPlateSizes = 0, 2, 4, 7, 14; a call
+//                               with L layers runs the smallest NL >= L and tests j < L (uniform) before it touches layer j.  The reference, the
+//                               layers and the records are pointers in the kernel argument (PlateArgs, 320 B): after unrolling every one is a
+//                               scalar load at a constant offset, there is no pointer table in memory.
+//                               Loads: the NL + 1 mask dwords first; an image's CH dwords only where one of its four mask bytes is set.
+//                               Gains: threads 0 .. NL CH - 1 compute seam_gain(record j, channel c) into LDS, one barrier; no host wait behind
+//                                 the sums kernels.
+//                               Selection, per channel and PAIR of pixels (pixel 0 with 2, 1 with 3): the NL + 1 candidates as packed halfwords,
+//                                 an unset candidate 0xFFFF, sorted by Batcher's odd-even merge network for NL + 1 elements (59 compare-exchanges
+//                                 at 15, 19 at 8, 9 at 5, 3 at 3), fully unrolled, every index a compile-time constant -- the array lives in
+//                                 registers, there is no scratch (tests/test_no_scratch_in_plate.py).  A compare-exchange is one v_pk_min_u16 and
+//                                 one v_pk_max_u16 on both pixels at once; the comparators the median does not depend on are removed by the
+//                                 compiler.  The element at (n - 1) >> 1 is taken per halfword by a chain of selects over indices
+//                                 0 .. NL / 2, not by indexing.
+//                               FLAG (a flag plane or the counters were passed): e = sum_c |R_c - P_c| where mR is set and n >= min_votes, the
+//                                 packed dword (v << 16) | e to LDS, 18 rows x 66 dwords = 4 752 B, the tile's pixel (y, x) at [y + 1][x + 1]
+//                                 (the denoise's layout and bank argument).  The halo of 1 about the tile -- 2 * 66 + 2 * 16 = 164 pixels -- is
+//                                 formed by threads 0 .. 163, each its own median byte by byte (channels 0 and 1 share the packed network),
+//                                 never outside the frame.  The 3 x 3 sums from LDS as nine 8-byte reads; D > threshold * CH * count decides.
+//                                 The four counters: a sum per thread, shuffles, LDS, one 64-bit integer atomicAdd each per workgroup.
+//                               Not FLAG: no LDS tile, no halo, one barrier (the gains; none at NL == 0).
+//                               Stores: whole dwords where the four pixels start on one, else byte by byte: every byte of the outputs given is
+//                                 written, no preset.
+//                               BGR, five sources: 5 (3 + 1) = 20 B read and 3 + 1 (+ 1 + 1) B written per pixel, plus the halo's 164 / 1024 of
+//                                 the reads with FLAG.
+#include <algorithm>
+
+#include "plate.hpp"
+#include "rectify_dense_device.hpp"
+#include "rsdsfm_internal.hpp"
+
+namespace rsdsfm {
+
+namespace {
+
+constexpr int kTR = kDenoiseTileRows, kTC = kDenoiseTileCols;
+constexpr int kLdsStride = kTC + 2;                 // 66 dwords: the denoise's bank argument
+constexpr int kHalo = 2 * (kTC + 2) + 2 * kTR;      // 164
+static_assert(kTR * (kTC / 4) == kBP, "a thread owns 4 consecutive pixels of a row of the tile");
+static_assert(kHalo <= kBP && kLdsStride % 2 == 0, "one halo pixel per thread; 8-byte aligned rows");
+static_assert(kPlateSizes[kPlateNumSizes - 1] == kPlateLayersMax, "the largest instance holds every call");
+
+constexpr unsigned kUnset = 0xFFFFu;  // a candidate that is not there: above every byte, so it sorts last
+
+// 1 in every byte of w that is not 0
+__device__ __forceinline__ unsigned bytes_set(unsigned w) { return ((w | ((w & 0x7f7f7f7fu) + 0x7f7f7f7fu)) >> 7) & 0x01010101u; }
+
+// byte k of an array of dwords (k a compile-time constant after unrolling)
+__device__ __forceinline__ unsigned byte_of(const unsigned* w, int k) { return (w[k >> 2] >> (8 * (k & 3))) & 0xffu; }
+
+typedef unsigned Lds8 __attribute__((ext_vector_type(2), aligned(8)));  // one ds_read_b64
+typedef unsigned short Half2 __attribute__((ext_vector_type(2)));        // two candidates of one compare-exchange
+
+// the aligned dword at byte offset o (a multiple of 4) of a plane of nbytes bytes; bytes past the plane's end read as 0 and are not touched
+__device__ __forceinline__ unsigned aligned_dword(const unsigned char* __restrict__ base, int64_t o, int64_t nbytes) {
+    if (o + 4 <= nbytes) return *reinterpret_cast<const unsigned*>(base + o);
+    unsigned w = 0u;
+    for (int b = 0; b < 4; ++b)
+        if (o + b < nbytes) w |= (unsigned)base[o + b] << (8 * b);
+    return w;
+}
+
+// ND dwords of bytes from byte offset `off` (any alignment) of a plane, as ND + 1 aligned dwords shifted into place
+template <int ND>
+__device__ __forceinline__ void load_bytes(const unsigned char* __restrict__ base, int64_t off, int64_t nbytes, unsigned* out) {
+    const int64_t a = off & ~(int64_t)3;
+    const unsigned sh = 8u * (unsigned)(off & 3);
+    unsigned w[ND + 1];
+#pragma unroll
+    for (int d = 0; d < ND; ++d) w[d] = aligned_dword(base, a + 4 * d, nbytes);
+    w[ND] = sh ? aligned_dword(base, a + 4 * ND, nbytes) : 0u;
+#pragma unroll
+    for (int d = 0; d < ND; ++d) out[d] = sh ? (w[d] >> sh) | (w[d + 1] << (32u - sh)) : w[d];
+}
+
+__device__ __forceinline__ unsigned gained(unsigned G, unsigned l) {  // G <= 2^18, the byte < 2^8
+    const unsigned k = (G * l + 32768u) >> 16;
+    return k > 255u ? 255u : k;
+}
+
+__device__ __forceinline__ unsigned absdiff(unsigned a, unsigned b) { return a > b ? a - b : b - a; }
+
+// Batcher's odd-even merge sort for N elements as a list of compare-exchanges (a[i] < b[i]), made at compile time
+template <int N>
+struct Network {
+    int count = 0;
+    int a[N * 5 + 1] = {}, b[N * 5 + 1] = {};  // 59 at N = 15
+};
+
+template <int N>
+constexpr Network<N> make_network() {
+    Network<N> net;
+    for (int p = 1; p < N; p *= 2)
+        for (int k = p; k >= 1; k /= 2)
+            for (int j = k % p; j <= N - 1 - k; j += 2 * k)
+                for (int i = 0; i <= (k - 1 < N - j - k - 1 ? k - 1 : N - j - k - 1); ++i)
+                    if ((i + j) / (2 * p) == (i + j + k) / (2 * p)) {
+                        net.a[net.count] = i + j;
+                        net.b[net.count] = i + j + k;
+                        ++net.count;
+                    }
+    return net;
+}
+
+// both halfwords of a and b ordered: a the smaller, b the larger of each
+__device__ __forceinline__ void compare_exchange(unsigned& a, unsigned& b) {
+    const Half2 x = __builtin_bit_cast(Half2, a), y = __builtin_bit_cast(Half2, b);
+    a = __builtin_bit_cast(unsigned, __builtin_elementwise_min(x, y));
+    b = __builtin_bit_cast(unsigned, __builtin_elementwise_max(x, y));
+}
+
+template <int N, int I>
+__device__ __forceinline__ void network_from(unsigned (&v)[N]) {
+    constexpr Network<N> net = make_network<N>();
+    if constexpr (I < net.count) {
+        constexpr int ia = net.a[I], ib = net.b[I];
+        compare_exchange(v[ia], v[ib]);
+        network_from<N, I + 1>(v);
+    }
+}
+
+// the packed lower medians of the N candidates of two pixels (low and high halfwords; an unset candidate is kUnset): the elements at med_lo and
+// med_hi (each (n - 1) >> 1 <= (N - 1) / 2) of the ascending orders, as (low | high << 16)
+template <int N>
+__device__ __forceinline__ unsigned median2(unsigned (&v)[N], unsigned med_lo, unsigned med_hi) {
+    network_from<N, 0>(v);
+    unsigned lo = v[0] & 0xffffu, hi = v[0] >> 16;
+#pragma unroll
+    for (int i = 1; i <= (N - 1) / 2; ++i) {
+        lo = med_lo == (unsigned)i ? (v[i] & 0xffffu) : lo;
+        hi = med_hi == (unsigned)i ? (v[i] >> 16) : hi;
+    }
+    return lo | (hi << 16);
+}
+
+template <int CH, int NL, bool FLAG>
+__device__ __forceinline__ void plate_median_body(const PlateArgs& a) {
+    constexpr int N = NL + 1;  // candidates
+    __shared__ __attribute__((aligned(16))) unsigned s_tile[FLAG ? (kTR + 2) * kLdsStride : 2];
+    __shared__ unsigned s_gain[NL * CH + 1];
+    const int rows = a.rows, cols = a.cols, nl = a.nlayers;
+    const int tid = (int)threadIdx.x, ty = tid / (kTC / 4), g = tid % (kTC / 4);
+    const int y0 = (int)blockIdx.y * kTR, x0 = (int)blockIdx.x * kTC;
+    const int y = y0 + ty, x = x0 + 4 * g;
+    const int64_t npix = (int64_t)rows * cols;
+    const int nin = (y < rows && x < cols) ? (cols - x < 4 ? cols - x : 4) : 0;  // the thread's pixels inside the frame: the first nin of its 4
+    const int64_t p0 = (int64_t)y * cols + x;
+    const unsigned inside = nin == 4 ? 0x01010101u : nin == 3 ? 0x00010101u : nin == 2 ? 0x00000101u : nin == 1 ? 0x00000001u : 0u;
+
+    // the mask dwords first, then the images whose mask has a byte set
+    unsigned mr = 0u, nw = 0u, ml[N], rw[CH], lw[N][CH];  // ml[NL], lw[NL] are never used: no array of length 0
+#pragma unroll
+    for (int j = 0; j < NL; ++j) ml[j] = 0u;
+    if (nin) {
+        unsigned w1[1];
+        load_bytes<1>(a.rmask, p0, npix, w1);
+        mr = bytes_set(w1[0]) & inside;
+#pragma unroll
+        for (int j = 0; j < NL; ++j)
+            if (j < nl) {
+                load_bytes<1>(a.lmask[j], p0, npix, w1);
+                ml[j] = bytes_set(w1[0]) & inside;
+            }
+    }
+    nw = mr;
+#pragma unroll
+    for (int j = 0; j < NL; ++j) nw += ml[j];  // the votes, a byte per pixel: at most 15, no carry
+#pragma unroll
+    for (int d = 0; d < CH; ++d) rw[d] = 0u;
+    if (mr) load_bytes<CH>(a.ref, (int64_t)CH * p0, (int64_t)CH * npix, rw);  // image bytes under an empty mask are not read
+#pragma unroll
+    for (int j = 0; j < NL; ++j) {
+#pragma unroll
+        for (int d = 0; d < CH; ++d) lw[j][d] = 0u;
+        if (ml[j]) load_bytes<CH>(a.layer[j], (int64_t)CH * p0, (int64_t)CH * npix, lw[j]);
+    }
+
+    if constexpr (NL > 0) {
+        if (tid < NL * CH) {
+            const int j = tid / CH, c = tid % CH;
+            s_gain[tid] = (a.sums && j < nl) ? seam_gain(a.sums + 8 * j, CH, c, a.min_overlap, a.gain_mode) : kGainOne;
+        }
+        __syncthreads();
+    }
+
+    // the medians of the thread's own four pixels: per channel, pixels 0 and 2, then 1 and 3
+    unsigned ow[CH], med[4];
+#pragma unroll
+    for (int d = 0; d < CH; ++d) ow[d] = 0u;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const unsigned n = (nw >> (8 * j)) & 0xffu;
+        med[j] = n ? (n - 1u) >> 1 : 0u;
+    }
+    if (nw) {
+#pragma unroll
+        for (int c = 0; c < CH; ++c) {
+            unsigned G[N];
+#pragma unroll
+            for (int j = 0; j < NL; ++j) G[j] = s_gain[j * CH + c];
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                unsigned v[N];
+                v[0] = (((mr >> (8 * h)) & 1u) ? byte_of(rw, CH * h + c) : kUnset) | ((((mr >> (8 * (h + 2))) & 1u) ? byte_of(rw, CH * (h + 2) + c) : kUnset) << 16);
+#pragma unroll
+                for (int j = 0; j < NL; ++j)
+                    v[1 + j] = (((ml[j] >> (8 * h)) & 1u) ? gained(G[j], byte_of(lw[j], CH * h + c)) : kUnset) |
+                               ((((ml[j] >> (8 * (h + 2))) & 1u) ? gained(G[j], byte_of(lw[j], CH * (h + 2) + c)) : kUnset) << 16);
+                const unsigned m2 = median2<N>(v, med[h], med[h + 2]);
+                const unsigned lo = ((nw >> (8 * h)) & 0xffu) ? (m2 & 0xffu) : 0u, hi = ((nw >> (8 * (h + 2))) & 0xffu) ? ((m2 >> 16) & 0xffu) : 0u;
+                ow[(CH * h + c) >> 2] |= lo << (8 * ((CH * h + c) & 3));
+                ow[(CH * (h + 2) + c) >> 2] |= hi << (8 * ((CH * (h + 2) + c) & 3));
+            }
+        }
+    }
+    const unsigned mw = bytes_set(nw);
+
+    unsigned fw = 0u, n4[4] = {0u, 0u, 0u, 0u};  // the flags, a byte per pixel; [unset, static, moving, undecided], at most 4 per thread
+    if constexpr (FLAG) {
+        // stage 1: the packed (v, e) of the thread's own four pixels
+        unsigned* row = s_tile + (ty + 1) * kLdsStride + 4 * g + 1;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            unsigned e = 0u;
+#pragma unroll
+            for (int c = 0; c < CH; ++c) e += absdiff(byte_of(rw, CH * j + c), byte_of(ow, CH * j + c));
+            const bool v = ((mr >> (8 * j)) & 1u) && ((nw >> (8 * j)) & 0xffu) >= a.min_votes;
+            row[j] = v ? (0x10000u | e) : 0u;
+        }
+        // the halo: the rows above and below (66 each), the columns left and right (16 each), one pixel per thread, its own median
+        if (tid < kHalo) {
+            int ly, lx;
+            if (tid < 2 * kLdsStride) {
+                ly = tid < kLdsStride ? 0 : kTR + 1;
+                lx = tid < kLdsStride ? tid : tid - kLdsStride;
+            } else {
+                const int r = tid - 2 * kLdsStride;
+                ly = 1 + (r < kTR ? r : r - kTR);
+                lx = r < kTR ? 0 : kTC + 1;
+            }
+            const int hy = y0 + ly - 1, hx = x0 + lx - 1;
+            unsigned ent = 0u;
+            if (hy >= 0 && hy < rows && hx >= 0 && hx < cols) {
+                const int64_t p = (int64_t)hy * cols + hx;
+                if (a.rmask[p] != 0) {
+                    unsigned seen = 0u, n = 1u;  // bit j: layer j saw the pixel
+#pragma unroll
+                    for (int j = 0; j < NL; ++j)
+                        if (j < nl && a.lmask[j][p] != 0) {
+                            seen |= 1u << j;
+                            ++n;
+                        }
+                    if (n >= a.min_votes) {
+                        const unsigned mi = (n - 1u) >> 1;
+                        unsigned R[CH], P[CH], k[N][CH];
+#pragma unroll
+                        for (int c = 0; c < CH; ++c) R[c] = a.ref[CH * p + c];
+#pragma unroll
+                        for (int j = 0; j < NL; ++j)
+#pragma unroll
+                            for (int c = 0; c < CH; ++c) k[j][c] = ((seen >> j) & 1u) ? gained(s_gain[j * CH + c], a.layer[j][CH * p + c]) : kUnset;
+#pragma unroll
+                        for (int c = 0; c < CH; c += 2) {  // channels c and c + 1 share the packed network
+                            const bool two = c + 1 < CH;
+                            unsigned v[N];
+                            v[0] = R[c] | ((two ? R[c + 1 < CH ? c + 1 : c] : kUnset) << 16);
+#pragma unroll
+                            for (int j = 0; j < NL; ++j) v[1 + j] = k[j][c] | ((two ? k[j][c + 1 < CH ? c + 1 : c] : kUnset) << 16);
+                            const unsigned m2 = median2<N>(v, mi, two ? mi : 0u);
+                            P[c] = m2 & 0xffffu;
+                            if (two) P[c + 1 < CH ? c + 1 : c] = m2 >> 16;
+                        }
+                        ent = 0x10000u;
+#pragma unroll
+                        for (int c = 0; c < CH; ++c) ent += absdiff(R[c], P[c]);
+                    }
+                }
+            }
+            s_tile[ly * kLdsStride + lx] = ent;
+        }
+        __syncthreads();
+        // stage 2: the 3 x 3 sums of the packed dwords; three rows of six columns, 8-byte reads
+        if (mr) {
+            unsigned col[6] = {0u, 0u, 0u, 0u, 0u, 0u};
+#pragma unroll
+            for (int r = 0; r < 3; ++r) {
+                const Lds8* q = static_cast<const Lds8*>(__builtin_assume_aligned(s_tile + (ty + r) * kLdsStride + 4 * g, 8));
+#pragma unroll
+                for (int i = 0; i < 3; ++i) {
+                    const Lds8 t = q[i];
+                    col[2 * i] += t[0];  // the high half is a count <= 9, the low half <= 9 * 765 = 6 885: no carry
+                    col[2 * i + 1] += t[1];
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const unsigned s = col[j] + col[j + 1] + col[j + 2];
+                const unsigned D = s & 0xffffu, cnt = s >> 16;
+                const unsigned f = cnt == 0u ? 3u : D > a.threshold * (unsigned)CH * cnt ? 2u : 1u;  // at most 255 * 27: products of integers, no division
+                fw |= (((mr >> (8 * j)) & 1u) ? f : 0u) << (8 * j);
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (j < nin) {
+                const unsigned f = (fw >> (8 * j)) & 0xffu;
+                n4[0] += f == 0u ? 1u : 0u;
+                n4[1] += f == 1u ? 1u : 0u;
+                n4[2] += f == 2u ? 1u : 0u;
+                n4[3] += f == 3u ? 1u : 0u;
+            }
+    }
+
+    if (nin == 4 && (p0 & 3) == 0) {  // p0 and CH * p0 bytes are 4-byte aligned
+#pragma unroll
+        for (int d = 0; d < CH; ++d) reinterpret_cast<unsigned*>(a.out + (int64_t)CH * p0)[d] = ow[d];
+        *reinterpret_cast<unsigned*>(a.mask_out + p0) = mw;
+        if (a.votes) *reinterpret_cast<unsigned*>(a.votes + p0) = nw;
+        if (FLAG && a.moving) *reinterpret_cast<unsigned*>(a.moving + p0) = fw;
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (j < nin) {
+#pragma unroll
+                for (int c = 0; c < CH; ++c) a.out[(int64_t)CH * (p0 + j) + c] = (unsigned char)byte_of(ow, CH * j + c);
+                a.mask_out[p0 + j] = (unsigned char)((mw >> (8 * j)) & 0xffu);
+                if (a.votes) a.votes[p0 + j] = (unsigned char)((nw >> (8 * j)) & 0xffu);
+                if (FLAG && a.moving) a.moving[p0 + j] = (unsigned char)((fw >> (8 * j)) & 0xffu);
+            }
+    }
+
+    if constexpr (FLAG) {
+        __shared__ unsigned s_wave[4][kBP / 64];
+        if (!a.counts) return;  // (uniform)
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) n4[k] += __shfl_down(n4[k], off, 64);
+            if ((threadIdx.x & 63) == 0) s_wave[k][threadIdx.x / 64] = n4[k];
+        }
+        __syncthreads();
+        if (threadIdx.x < 4) {
+            unsigned total = 0;
+#pragma unroll
+            for (int i = 0; i < kBP / 64; ++i) total += s_wave[threadIdx.x][i];
+            if (total) atomicAdd(a.counts + threadIdx.x, (unsigned long long)total);
+        }
+    }
+}
+
+}  // namespace
+
+// grid (ceil(cols / 64), ceil(rows / 16)), block kBP.  out, mask_out and votes (may be NULL) are written whole; FLAG: moving (may be NULL) is
+// written whole and counts[0 .. 3] (may be NULL) += [unset, static, moving, undecided]
+template <int CH, int NL, bool FLAG>
+__global__ __launch_bounds__(kBP) void plate_median_kernel(const PlateArgs a) {
+    plate_median_body<CH, NL, FLAG>(a);
+}
+
+// ---------------------------------------------------------------------------------------------------
+// launcher
+// ---------------------------------------------------------------------------------------------------
+int plate_median_launch(Ctx* c, const PlateArgs& args, int channels) {
+    if (args.counts) RSDSFM_HIP_CHECK(c, hipMemsetAsync(args.counts, 0, 4 * sizeof(int64_t), c->stream));
+    const dim3 grid((unsigned)((args.cols + kTC - 1) / kTC), (unsigned)((args.rows + kTR - 1) / kTR));  // at most 256 x 1024
+    using Kernel = void (*)(const PlateArgs);
+#define RSDSFM_PLATE_ROW(CH) \
+    {{plate_median_kernel<CH, 0, false>, plate_median_kernel<CH, 0, true>}, {plate_median_kernel<CH, 2, false>, plate_median_kernel<CH, 2, true>}, \
+     {plate_median_kernel<CH, 4, false>, plate_median_kernel<CH, 4, true>}, {plate_median_kernel<CH, 7, false>, plate_median_kernel<CH, 7, true>}, \
+     {plate_median_kernel<CH, 14, false>, plate_median_kernel<CH, 14, true>}}
+    static const Kernel kernels[2][kPlateNumSizes][2] = {RSDSFM_PLATE_ROW(1), RSDSFM_PLATE_ROW(3)};
+#undef RSDSFM_PLATE_ROW
+    static_assert(kPlateSizes[0] == 0 && kPlateSizes[1] == 2 && kPlateSizes[2] == 4 && kPlateSizes[3] == 7 && kPlateSizes[4] == 14, "the table above");
+    int size = 0;
+    while (kPlateSizes[size] < args.nlayers) ++size;  // nlayers <= 14: checked by the caller
+    const bool flag = args.moving != nullptr || args.counts != nullptr;
+    hipLaunchKernelGGL(kernels[channels == 3][size][flag], grid, dim3(kBP), 0, c->stream, args);
+    RSDSFM_HIP_CHECK(c, hipGetLastError());
+    return RSDSFM_OK;
+}
+
+}  // namespace rsdsfm

@@ -26,6 +26,8 @@ struct DenseWs {
     unsigned char* d_denoise = nullptr; // the temporal denoise's reference mask, source plane and image and its cells, 13 planes (denoise.hpp; made when first asked for)
     unsigned char* d_superres = nullptr; // the super-resolution's own planes, layer planes, cells and record on the FINE grid, 23 planes (superres.hpp; made when first asked for)
     int superres_scale = 0;              // the scale d_superres was made for
+    unsigned char* d_plate = nullptr;    // the clean plate's reference planes, records and stack of layers (plate.hpp; made when first asked for)
+    int plate_layers = 0;                // the layers d_plate holds
     int rows = 0, cols = 0;
 };
 

@@ -28,6 +28,9 @@ static void dense_ws_free(DenseWs* w) {
     if (w->d_superres) (void)hipFree(w->d_superres);
     w->d_superres = nullptr;
     w->superres_scale = 0;
+    if (w->d_plate) (void)hipFree(w->d_plate);
+    w->d_plate = nullptr;
+    w->plate_layers = 0;
     w->d_pyr = nullptr;
     w->d_disp = nullptr;
     w->d_mask = nullptr;

@@ -209,7 +209,7 @@ def evaluate_real_sequence(solver, frames, camera="galaxy", gamma=0.95, out_dir=
                            check_flow=False, trajectory=False, link_tol=None, min_links=None, fuse=False, fuse_tol=None, stabilize=False, smooth_sigma=None,
                            smooth_translation=True, fill=0, crop=False, crop_margin=None, crop_max_empty=0, blend=False, blend_feather=None,
                            blend_gain=True, inpaint=False, last_frame=False, occlusion=False, occlusion_tol=None, occlusion_search=False, retime=None,
-                           shutter=None, denoise=None, superres=None):
+                           shutter=None, denoise=None, superres=None, plate=None):
     """evaluate_real_run's real-world branch (main.cc:341-361, 364-531) for a clip: `frames` is <prefix>frame1.png ... frameN.png (the
     prefix, or a list of paths), or the frames themselves (an (N, rows, cols[, 3]) uint8 array or a list of arrays; 2-D frames are gray).
     By default ONE call does the clip (Solver.rectify_video_dev): the batched DeepFlow of every consecutive pair, the pipelined solve of every pair p
@@ -300,7 +300,16 @@ def evaluate_real_sequence(solver, frames, camera="galaxy", gamma=0.95, out_dir=
     `scale` times finer (1 .. 4), merged from itself and its K neighbours on either side (1 .. 7, default 2), each rendered alone into the frame's
     camera on the SMOOTHED path (Solver.superres_video_dev, tests/superres_spec_numpy.py; the fused maps with fuse=True): the returned dict also
     has superres, superres_masks (lists of scale rows x scale cols frames) and superres_counts ((frames, 3) int64: [unset, own only, merged]);
-    out_dir receives superres_<p>.png and superres.csv.  Without the keyword every key and file is what it was."""
+    out_dir receives superres_<p>.png and superres.csv.  Without the keyword every key and file is what it was.
+    plate=K or (K, threshold) (needs stabilize=True: ValueError otherwise): behind everything else, every stabilised frame once more as its clean
+    plate -- the per-pixel, per-channel median of the frame and its up to K neighbours on each side, each rendered alone into the frame's camera on
+    the SMOOTHED path -- and where the frame differs from it (Solver.plate_video_dev, tests/plate_spec_numpy.py; threshold None: the default, 24;
+    the fused maps with fuse=True, the neighbours through the occlusion test with occlusion=True): the returned dict also has plate,
+    plate_moving (lists of frames; the flag is 0 unset, 1 static, 2 moving, 3 undecided) and plate_counts ((frames, 4) int64: [unset, static,
+    moving, undecided]); out_dir receives plate_<p>.png, moving_<p>.png (255 where the flag is 2) and plate.csv.  Without the keyword every key
+    and file is what it was."""
+    if plate is not None and not stabilize:
+        raise ValueError("plate needs stabilize=True: it takes the median of the frames of the stabilised clip")
     if superres is not None and not stabilize:
         raise ValueError("superres needs stabilize=True: it merges the frames of the stabilised clip")
     if denoise is not None and not stabilize:
@@ -625,6 +634,16 @@ def evaluate_real_sequence(solver, frames, camera="galaxy", gamma=0.95, out_dir=
                     sr = solver.superres_video_dev(ptrs(d_imgs), rows, cols, channels, K, ptrs(d_src[:nst]), ptrs(d_Rs[:nst]), ptrs(d_ts[:nst]), traj["A"], traj["c"], A_s,
                                                    c_s, st_scales, ptrs(d_sr), ptrs(d_srmasks), None, scale=sr_scale, radius=sr_radius, mode=mode)
                     traj.update(superres=[t.cpu().numpy() for t in d_sr], superres_masks=[t.cpu().numpy() for t in d_srmasks], superres_counts=sr["counts"])
+                if plate is not None:  # every stabilised frame once more, as the median of itself and its neighbours, and where it moved
+                    pl_radius, pl_threshold = (int(plate), None) if np.ndim(plate) == 0 else (int(plate[0]), int(plate[1]))
+                    d_pl = [torch.empty_like(d_imgs[0]) for _ in range(nst)]
+                    d_plmasks = [torch.empty((rows, cols), dtype=torch.uint8, device=dev) for _ in range(nst)]
+                    d_plmov = [torch.empty((rows, cols), dtype=torch.uint8, device=dev) for _ in range(nst)]
+                    torch.cuda.synchronize()
+                    pl = solver.plate_video_dev(ptrs(d_imgs), rows, cols, channels, K, ptrs(d_src[:nst]), ptrs(d_Rs[:nst]), ptrs(d_ts[:nst]), traj["A"], traj["c"], A_s, c_s,
+                                                st_scales, ptrs(d_pl), ptrs(d_plmasks), None, ptrs(d_plmov), radius=pl_radius, threshold=pl_threshold, occlusion=occlusion,
+                                                occlusion_tol_q16=occ_q16 if occlusion else 0, mode=mode)
+                    traj.update(plate=[t.cpu().numpy() for t in d_pl], plate_moving=[t.cpu().numpy() for t in d_plmov], plate_counts=pl["counts"])
     if out_dir:
         os.makedirs(out_dir, exist_ok=True)
         lines = ["pair,v_x,v_y,v_z,w_x,w_y,w_z,k,inliers"]
@@ -727,6 +746,14 @@ def evaluate_real_sequence(solver, frames, camera="galaxy", gamma=0.95, out_dir=
                 formats.write_png(os.path.join(out_dir, "superres_%d.png" % p), traj["superres"][p])
                 rows_.append(",".join([str(p)] + [str(int(x)) for x in traj["superres_counts"][p]]))
             with open(os.path.join(out_dir, "superres.csv"), "w") as fh:
+                fh.write("\n".join(rows_) + "\n")
+        if plate is not None:
+            rows_ = ["pair,unset,static,moving,undecided"]
+            for p in range(nst):
+                formats.write_png(os.path.join(out_dir, "plate_%d.png" % p), traj["plate"][p])
+                formats.write_png(os.path.join(out_dir, "moving_%d.png" % p), np.where(traj["plate_moving"][p] == 2, 255, 0).astype(np.uint8))
+                rows_.append(",".join([str(p)] + [str(int(x)) for x in traj["plate_counts"][p]]))
+            with open(os.path.join(out_dir, "plate.csv"), "w") as fh:
                 fh.write("\n".join(rows_) + "\n")
         if inpaint:
             rows_ = ["pair,stage,inpainted"]

@@ -246,7 +246,39 @@ def _sensor_noise(frames, noise, noise_seed):
     return out
 
 
-def render_sequence(nframes, rows, cols, K, v, w, k=0.0, gamma=0.8, seed=0x5EED0000, speeds=None, gains=None, noise=None, noise_seed=0x5EED0001):
+def _mover_block(mover, seed):
+    """the mover's bytes: render_occluded_pair's block texture ((h, w, 3) uint8), _texture in the block's own coordinates under another seed"""
+    h, bw = int(mover[2]), int(mover[3])
+    by, bx = np.mgrid[0:h, 0:bw].astype(np.float64)
+    return np.rint(_texture(3.0 * bx, 3.0 * by, (seed ^ 0xB10C) & 0xFFFFFFFF)[..., ::-1]).astype(np.uint8)
+
+
+def mover_planes(nframes, rows, cols, mover):
+    """the footprints of render_sequence's mover = (y0, x0, h, w, dx, dy): (nframes, rows, cols) bool, frame j's rectangle of h x w pixels at
+    (y0 + j dy, x0 + j dx).  The rectangle must lie inside every frame"""
+    y0, x0, h, bw, dx, dy = (int(b) for b in mover)
+    ys, xs = [y0, y0 + (nframes - 1) * dy], [x0, x0 + (nframes - 1) * dx]
+    if h < 1 or bw < 1 or min(ys) < 0 or min(xs) < 0 or max(ys) + h > rows or max(xs) + bw > cols:
+        raise ValueError("the mover must lie inside every frame")
+    planes = np.zeros((nframes, rows, cols), dtype=bool)
+    for j in range(nframes):
+        planes[j, y0 + j * dy:y0 + j * dy + h, x0 + j * dx:x0 + j * dx + bw] = True
+    return planes
+
+
+def _with_mover(frames, mover, seed):
+    """the frames with the mover's block pasted onto every one (a new array); None: the frames themselves"""
+    if mover is None:
+        return frames
+    planes = mover_planes(frames.shape[0], frames.shape[1], frames.shape[2], mover)
+    block = _mover_block(mover, seed)
+    out = frames.copy()
+    for j in range(frames.shape[0]):
+        out[j][planes[j]] = block.reshape(-1, 3)
+    return out
+
+
+def render_sequence(nframes, rows, cols, K, v, w, k=0.0, gamma=0.8, seed=0x5EED0000, speeds=None, gains=None, noise=None, noise_seed=0x5EED0001, mover=None):
     """nframes 8-bit BGR frames of render_pair's texture under a constant motion: frame j at pixel q shows T(inv^j(q)), where inv is
     render_pair's fixed-point inverse of the model flow F (p + F(p) = q), applied j times from the pixel grid.  Every consecutive pair
     (j, j + 1) therefore has the true flow F and the true (v, w, k); render_pair's border mask.  nframes = 2 gives render_pair's two
@@ -258,14 +290,18 @@ def render_sequence(nframes, rows, cols, K, v, w, k=0.0, gamma=0.8, seed=0x5EED0
     for byte what this function returns without the argument.
     noise: an amplitude in bytes: after the exposure gain every byte of frame j gets an integer drawn uniformly from [-noise, noise] by the
     generator seeded (noise_seed, j), clipped to 0 .. 255 -- seeded integer sensor noise, what the temporal denoise is for.  None (or 0): byte
-    for byte what this function returns without the argument."""
+    for byte what this function returns without the argument.
+    mover: (y0, x0, h, w, dx, dy): a rectangle of h x w pixels with render_occluded_pair's block texture pasted onto frame j at
+    (y0 + j dy, x0 + j dx), after the exposure gain and before the sensor noise -- something that moves through a static scene, what the clean
+    plate is for; it must lie inside every frame and has no part in F or the mask (mover_planes gives its footprints).  None: byte for byte
+    what this function returns without the argument."""
     if nframes < 2:
         raise ValueError("a sequence has at least two frames")
     if gains is not None and len(gains) != nframes:
         raise ValueError("gains needs one factor per frame (nframes)")
     if speeds is not None:
         frames, flows, mask = _render_sequence_speeds(nframes, rows, cols, K, v, w, k, gamma, seed, speeds, gains)
-        return _sensor_noise(frames, noise, noise_seed), flows, mask
+        return _sensor_noise(_with_mover(frames, mover, seed), noise, noise_seed), flows, mask
     flow, _ = make_flow(rows, cols, K, v, w, k, gamma, _model_only=True)
     yy, xx = np.mgrid[0:rows, 0:cols].astype(np.float64)
     frames = [_exposed(_texture(xx, yy, seed), None if gains is None else gains[0])]
@@ -284,7 +320,7 @@ def render_sequence(nframes, rows, cols, K, v, w, k=0.0, gamma=0.8, seed=0x5EED0
     band = int(np.ceil(np.abs(flow).max())) + 5
     mask = np.zeros((rows, cols), dtype=bool)
     mask[band:rows - band, band:cols - band] = True
-    return _sensor_noise(np.stack(frames), noise, noise_seed), np.ascontiguousarray(flow), mask
+    return _sensor_noise(_with_mover(np.stack(frames), mover, seed), noise, noise_seed), np.ascontiguousarray(flow), mask
 
 
 def _render_sequence_speeds(nframes, rows, cols, K, v, w, k, gamma, seed, speeds, gains=None):
