@@ -1,10 +1,8 @@
 // denoise_host.hip -- C ABI of the temporal denoise (include/rsdsfm_denoise.h; tests/denoise_spec_numpy.py is the definition,
 // denoise_kernels.hip the kernel): the blend's record as a public call, the accumulate call, the frame call, which CALLS the public render
 // entry points, the record call and the accumulate one after another on planes of the context's dense workspace, and the clip call, which
-// calls the frame call per frame.
-#include <cmath>
-#include <vector>
-
+// calls the frame call per frame (walk_clip, clip_stage_host.hpp).
+#include "clip_stage_host.hpp"
 #include "denoise.hpp"
 #include "rectify_dense.hpp"
 #include "rsdsfm_internal.hpp"
@@ -35,14 +33,6 @@ const char* const kDenoiseParamsMessage =
     "rsdsfm_denoise_params: radius in [1, 7] or 0, strength in [1, 255] or 0, gain_mode 0 or 1, occlusion 0 or 1, occlusion_tol_q16 in [0, 65536], min_overlap >= 0, "
     "struct_bytes 0 or sizeof (use rsdsfm_denoise_params_init)";
 
-bool denoise_size_ok(int rows, int cols) { return rows >= 2 && cols >= 2 && rows <= 16384 && cols <= 16384; }
-
-bool denoise_finite_all(const double* a, int n) {
-    for (int i = 0; i < n; ++i)
-        if (!std::isfinite(a[i])) return false;
-    return true;
-}
-
 // the argument checks of the outputs, for the accumulate call and, before anything is enqueued, for the frame call (whose planes and cells are the context's)
 int denoise_outputs_check(Ctx* c, const uint8_t* d_image_out, const uint8_t* d_mask_out, const uint8_t* d_weight, const int64_t* d_counts3) {
     if (!d_image_out || !d_mask_out) return fail(c, RSDSFM_ERR_INVALID, "denoise: null output plane");
@@ -55,40 +45,14 @@ int denoise_outputs_check(Ctx* c, const uint8_t* d_image_out, const uint8_t* d_m
 
 // the workspace's reference planes and cells, made when first asked for, and the blend's layer
 int denoise_ws(Ctx* c, int rows, int cols, DenseWs** ws) {
-    const int rc = rectify_dense_ws(c, rows, cols, ws);  // a size change releases them with the rest
+    int rc = rectify_dense_ws(c, rows, cols, ws);  // a size change releases them with the rest
     if (rc != RSDSFM_OK) return rc;
-    if (!(*ws)->d_layer && hipMalloc(reinterpret_cast<void**>(&(*ws)->d_layer), blend_layer_bytes(rows, cols)) != hipSuccess) {
-        (*ws)->d_layer = nullptr;
-        return fail(c, RSDSFM_ERR_HIP, "denoise: no memory for the layer");
-    }
-    if (!(*ws)->d_denoise && hipMalloc(reinterpret_cast<void**>(&(*ws)->d_denoise), denoise_ws_bytes(rows, cols)) != hipSuccess) {
-        (*ws)->d_denoise = nullptr;
-        return fail(c, RSDSFM_ERR_HIP, "denoise: no memory for the reference planes and the cells");
-    }
-    return RSDSFM_OK;
+    rc = ensure_plane(c, &(*ws)->d_layer, blend_layer_bytes(rows, cols), "denoise: no memory for the layer");
+    if (rc != RSDSFM_OK) return rc;
+    return ensure_plane(c, &(*ws)->d_denoise, denoise_ws_bytes(rows, cols), "denoise: no memory for the reference planes and the cells");
 }
 
-// one frame's host part for the clip call: the sources (the own frame first) and their poses
-struct DenoisePlan {
-    int nsrc = 0;
-    int32_t src[kDenoiseSourcesMax];
-    double M[9 * kDenoiseSourcesMax], m[3 * kDenoiseSourcesMax];
-};
-
-bool denoise_plan(const double* A, const double* c_, const double* A_path, const double* c_path, const double* scales, int nsources, int q, int radius, DenoisePlan* plan) {
-    int32_t src2[2], nsrc = 0, wq = 0, ids[kDenoiseLayersMax], count = 0;
-    double M18[18], m6[6], At[9], ct[3];
-    if (rsdsfm_retime_poses(A, c_, A_path, c_path, scales, nsources, (double)q, src2, &nsrc, &wq, M18, m6, At, ct) != RSDSFM_OK || nsrc != 1) return false;
-    plan->src[0] = q;
-    for (int k = 0; k < 9; ++k) plan->M[k] = M18[k];
-    for (int k = 0; k < 3; ++k) plan->m[k] = m6[k];
-    if (nsources > 1 && rsdsfm_neighbour_poses(A, c_, A_path, c_path, scales, nsources, q, radius, plan->src + 1, ids, plan->M + 9, plan->m + 3, &count) != RSDSFM_OK)
-        return false;
-    plan->nsrc = 1 + count;
-    return denoise_finite_all(plan->M, 9 * plan->nsrc) && denoise_finite_all(plan->m, 3 * plan->nsrc);
-}
-
-const char* const kDenoisePlanMessage = "denoise video: the poses must be finite and every listed source's scale finite and positive";
+static_assert(kDenoiseSourcesMax == kClipSourcesMax, "a frame's sources are a ClipPlan's");
 
 }  // namespace
 }  // namespace rsdsfm
@@ -117,7 +81,7 @@ int rsdsfm_seam_overlap_sums_dev(rsdsfm_ctx* ctx, const uint8_t* d_image, const 
     if (!ctx) return RSDSFM_ERR_INVALID;
     Ctx* c = &ctx->c;
     DeviceGuard device_guard_(c);
-    if (!denoise_size_ok(rows, cols)) return fail(c, RSDSFM_ERR_INVALID, "seam overlap sums: rows and cols must be in [2, 16384]");
+    if (!frame_size_ok(rows, cols)) return fail(c, RSDSFM_ERR_INVALID, "seam overlap sums: rows and cols must be in [2, 16384]");
     if (channels != 1 && channels != 3) return fail(c, RSDSFM_ERR_INVALID, "seam overlap sums: channels must be 1 or 3");
     if (!d_image || !d_source || !d_layer || !d_layer_mask || !d_sums8_out) return fail(c, RSDSFM_ERR_INVALID, "seam overlap sums: null device pointer");
     if (((uintptr_t)d_image | (uintptr_t)d_source | (uintptr_t)d_layer | (uintptr_t)d_layer_mask) & 3u)
@@ -134,7 +98,7 @@ int rsdsfm_denoise_accumulate_dev(rsdsfm_ctx* ctx, const uint8_t* d_ref_image, c
     Ctx* c = &ctx->c;
     DeviceGuard device_guard_(c);
     if ((first != 0 && first != 1) || (last != 0 && last != 1)) return fail(c, RSDSFM_ERR_INVALID, "denoise accumulate: first and last must be 0 or 1");
-    if (!denoise_size_ok(rows, cols)) return fail(c, RSDSFM_ERR_INVALID, "denoise: rows and cols must be in [2, 16384]");
+    if (!frame_size_ok(rows, cols)) return fail(c, RSDSFM_ERR_INVALID, "denoise: rows and cols must be in [2, 16384]");
     if (channels != 1 && channels != 3) return fail(c, RSDSFM_ERR_INVALID, "denoise: channels must be 1 or 3");
     if (min_overlap < 0 || (gain_mode != 0 && gain_mode != 1) || strength < 0 || strength > kDenoiseStrengthMax)
         return fail(c, RSDSFM_ERR_INVALID, "denoise accumulate: min_overlap must be >= 0, gain_mode 0 or 1 and strength in [1, 255] (0: the default, 12)");
@@ -186,14 +150,13 @@ int rsdsfm_denoise_frame_dev(rsdsfm_ctx* ctx, const uint8_t* const* d_images, in
         if (!d_images[k] || !d_depths_colmajor[k] || !d_R_rows9[k] || !d_t_rows3[k] || d_images[k] == d_image_out || d_images[k] == d_mask_out ||
             (d_weight_or_null && d_images[k] == d_weight_or_null) || ((uintptr_t)d_images[k] & 3u))
             return fail(c, RSDSFM_ERR_INVALID, "denoise frame: null, misaligned or aliased source pointer");
-    if (!M || !m || !denoise_finite_all(M, 9 * nsrc) || !denoise_finite_all(m, 3 * nsrc))
+    if (!M || !m || !finite_all(M, 9 * nsrc) || !finite_all(m, 3 * nsrc))
         return fail(c, RSDSFM_ERR_INVALID, "denoise frame: the poses (M, m) must be given and finite");
     rc = denoise_outputs_check(c, d_image_out, d_mask_out, d_weight_or_null, d_counts3_or_null);
     if (rc != RSDSFM_OK) return rc;
-    const int32_t full[4] = {0, 0, rows, cols};
-    const int32_t* window = window_or_null ? window_or_null : full;
-    if (window[2] < 1 || window[3] < 1 || window[0] < 0 || window[1] < 0 || (int64_t)window[0] + window[2] > rows || (int64_t)window[1] + window[3] > cols)
-        return fail(c, RSDSFM_ERR_INVALID, "denoise frame: the window (r0, c0, h, w) needs h >= 1, w >= 1 and must lie inside the frame");
+    int32_t full[4];
+    const int32_t* window = window_or_full(window_or_null, rows, cols, full);
+    if (!window) return fail(c, RSDSFM_ERR_INVALID, "denoise frame: the window (r0, c0, h, w) needs h >= 1, w >= 1 and must lie inside the frame");
     DenseWs* ws = nullptr;
     rc = denoise_ws(c, rows, cols, &ws);
     if (rc != RSDSFM_OK) return rc;
@@ -205,28 +168,18 @@ int rsdsfm_denoise_frame_dev(rsdsfm_ctx* ctx, const uint8_t* const* d_images, in
     uint8_t* lmask = ws->d_layer + P;  // the blend's layer A and its record (stabilize_blend.hpp)
     uint8_t* limage = ws->d_layer + 2 * P;
     uint64_t* record = reinterpret_cast<uint64_t*>(ws->d_layer + 5 * P);
-    if (hipMemsetAsync(rimage, 0, plane * (size_t)channels, c->stream) != hipSuccess || hipMemsetAsync(rmask, 0, plane, c->stream) != hipSuccess ||
-        hipMemsetAsync(rsource, 0, plane, c->stream) != hipSuccess)
-        return fail(c, RSDSFM_ERR_HIP, "denoise frame: zeroing the reference failed");
-    // the public entry points themselves, so that they run the code they run alone.  The own frame never goes through the occlusion test
-    rc = rsdsfm_stabilize_window_frame_dev(ctx, d_images[0], channels, d_depths_colmajor[0], d_R_rows9[0], d_t_rows3[0], fx, fy, cx, cy, rows, cols, mode, q5_mode, iterations,
-                                           M, m, 1, window, rimage, rmask, rsource, nullptr);
+    rc = render_reference(ctx, "denoise frame", d_images[0], channels, d_depths_colmajor[0], d_R_rows9[0], d_t_rows3[0], fx, fy, cx, cy, rows, cols, mode, q5_mode, iterations,
+                          M, m, window, rimage, rmask, rsource);
     if (rc != RSDSFM_OK) return rc;
     if (nsrc == 1)
         return rsdsfm_denoise_accumulate_dev(ctx, rimage, rmask, nullptr, nullptr, channels, rows, cols, nullptr, dp.min_overlap, dp.gain_mode, dp.strength, nullptr, 1, 1,
                                              d_image_out, d_mask_out, d_weight_or_null, d_counts3_or_null);
-    const bool srch = dp.occlusion == 1 && c->occlusion_search == 1;
     for (int k = 1; k < nsrc; ++k) {
         if (hipMemsetAsync(limage, 0, plane * (size_t)channels, c->stream) != hipSuccess || hipMemsetAsync(lmask, 0, plane, c->stream) != hipSuccess)
             return fail(c, RSDSFM_ERR_HIP, "denoise frame: zeroing the layer failed");
         const int id = 2;  // no source plane is passed: the id is not written anywhere
-        rc = srch ? rsdsfm_stabilize_search_frame_dev(ctx, d_images[k], channels, d_depths_colmajor[k], d_R_rows9[k], d_t_rows3[k], fx, fy, cx, cy, rows, cols, mode, q5_mode,
-                                                      iterations, M + 9 * k, m + 3 * k, id, window, limage, lmask, nullptr, dp.occlusion_tol_q16, nullptr)
-             : dp.occlusion == 1
-                 ? rsdsfm_stabilize_visible_frame_dev(ctx, d_images[k], channels, d_depths_colmajor[k], d_R_rows9[k], d_t_rows3[k], fx, fy, cx, cy, rows, cols, mode, q5_mode,
-                                                      iterations, M + 9 * k, m + 3 * k, id, window, limage, lmask, nullptr, dp.occlusion_tol_q16, nullptr)
-                 : rsdsfm_stabilize_window_frame_dev(ctx, d_images[k], channels, d_depths_colmajor[k], d_R_rows9[k], d_t_rows3[k], fx, fy, cx, cy, rows, cols, mode, q5_mode,
-                                                     iterations, M + 9 * k, m + 3 * k, id, window, limage, lmask, nullptr, nullptr);
+        rc = render_candidate(ctx, dp.occlusion == 1, dp.occlusion_tol_q16, d_images[k], channels, d_depths_colmajor[k], d_R_rows9[k], d_t_rows3[k], fx, fy, cx, cy, rows, cols,
+                              mode, q5_mode, iterations, M + 9 * k, m + 3 * k, id, window, limage, lmask, nullptr, nullptr);
         if (rc != RSDSFM_OK) return rc;
         rc = rsdsfm_seam_overlap_sums_dev(ctx, rimage, rsource, limage, lmask, channels, rows, cols, record);
         if (rc != RSDSFM_OK) return rc;
@@ -245,46 +198,20 @@ int rsdsfm_denoise_video_dev(rsdsfm_ctx* ctx, const uint8_t* const* d_frames, in
     if (!ctx) return RSDSFM_ERR_INVALID;
     Ctx* c = &ctx->c;
     DeviceGuard device_guard_(c);
-    if (nsources < 1) return fail(c, RSDSFM_ERR_INVALID, "denoise video: nsources must be >= 1");
-    if (!d_frames || !d_depth_maps || !d_R || !d_t || !A || !c_ || !A_path || !c_path || !scales) return fail(c, RSDSFM_ERR_INVALID, "denoise video: null array");
-    if (!all_set(d_frames, nsources) || !all_set(d_depth_maps, nsources) || !all_set(d_R, nsources) || !all_set(d_t, nsources))
-        return fail(c, RSDSFM_ERR_INVALID, "denoise video: every source needs its frame, depth map and pose table");
-    if (!d_out_images || !d_out_masks || !all_set(d_out_images, nsources) || !all_set(d_out_masks, nsources) ||
-        (d_out_weights_or_null && !all_set(d_out_weights_or_null, nsources)))
-        return fail(c, RSDSFM_ERR_INVALID, "denoise video: every frame needs its image and its mask (and its weight plane when the array is passed)");
+    ClipOutputs outs;
+    outs.planes[0] = d_out_images;
+    outs.planes[1] = d_out_masks;
+    outs.planes[2] = d_out_weights_or_null;
+    const int rc = clip_arrays_check(c, "denoise video", d_frames, nsources, d_depth_maps, d_R, d_t, A, c_, A_path, c_path, scales, outs,
+                                     "its weight plane when the array is passed");
+    if (rc != RSDSFM_OK) return rc;
     rsdsfm_denoise_params dp;
     if (!denoise_params_resolve(params_or_null, &dp)) return fail(c, RSDSFM_ERR_INVALID, kDenoiseParamsMessage);
-    for (int q = 0; q < nsources; ++q)  // an output may not be a frame of the clip: a later frame call still reads it
-        for (int n = 0; n < nsources; ++n)
-            if (d_frames[n] == d_out_images[q] || d_frames[n] == d_out_masks[q] || (d_out_weights_or_null && d_frames[n] == d_out_weights_or_null[q]))
-                return fail(c, RSDSFM_ERR_INVALID, "denoise video: an output plane may not be a frame of the clip");
-    // every frame's sources and poses first: a refused pose enqueues nothing
-    std::vector<DenoisePlan> plans(nsources);
-    for (int q = 0; q < nsources; ++q)
-        if (!denoise_plan(A, c_, A_path, c_path, scales, nsources, q, dp.radius, &plans[q])) return fail(c, RSDSFM_ERR_INVALID, kDenoisePlanMessage);
-    int64_t* d_cnt = nullptr;
-    if (counts_or_null) RSDSFM_HIP_CHECK(c, hipMalloc(reinterpret_cast<void**>(&d_cnt), 3 * sizeof(int64_t) * (size_t)nsources));
-    int rc = RSDSFM_OK;
-    for (int q = 0; q < nsources && rc == RSDSFM_OK; ++q) {  // the public entry point itself, so that it runs the code it runs alone
-        const DenoisePlan& p = plans[q];
-        const uint8_t* img[kDenoiseSourcesMax];
-        const double *map[kDenoiseSourcesMax], *R[kDenoiseSourcesMax], *t[kDenoiseSourcesMax];
-        for (int k = 0; k < p.nsrc; ++k) {
-            img[k] = d_frames[p.src[k]];
-            map[k] = d_depth_maps[p.src[k]];
-            R[k] = d_R[p.src[k]];
-            t[k] = d_t[p.src[k]];
-        }
-        rc = rsdsfm_denoise_frame_dev(ctx, img, channels, map, R, t, fx, fy, cx, cy, rows, cols, mode, q5_mode, iterations, p.nsrc, p.M, p.m, params_or_null, window_or_null,
-                                      d_out_images[q], d_out_masks[q], d_out_weights_or_null ? d_out_weights_or_null[q] : nullptr, d_cnt ? d_cnt + 3 * (size_t)q : nullptr);
-    }
-    if (d_cnt) {
-        hipError_t e = rc == RSDSFM_OK ? hipMemcpyAsync(counts_or_null, d_cnt, 3 * sizeof(int64_t) * (size_t)nsources, hipMemcpyDeviceToHost, c->stream) : hipSuccess;
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        (void)hipFree(d_cnt);
-        if (rc == RSDSFM_OK) RSDSFM_HIP_CHECK(c, e);
-    }
-    return rc;
+    // the public entry point itself, so that it runs the code it runs alone
+    return walk_clip(c, "denoise video", d_frames, nsources, d_depth_maps, d_R, d_t, A, c_, A_path, c_path, scales, dp.radius, outs, 3, counts_or_null, [&](const ClipFrame& f) {
+        return rsdsfm_denoise_frame_dev(ctx, f.img, channels, f.map, f.R, f.t, fx, fy, cx, cy, rows, cols, mode, q5_mode, iterations, f.plan->nsrc, f.plan->M, f.plan->m,
+                                        params_or_null, window_or_null, f.out[0], f.out[1], f.out[2], f.d_counts);
+    });
 }
 
 }  // extern "C"

@@ -1,9 +1,7 @@
 // plate_host.hip -- C ABI of the clean plate (include/rsdsfm_plate.h; tests/plate_spec_numpy.py is the definition, plate_kernels.hip the
 // kernel): the median call, the frame call, which CALLS the public render entry points, the record call and the median one after another on
 // planes of the context's dense workspace, and the clip call, which calls the frame call per frame.
-#include <cmath>
-#include <vector>
-
+#include "clip_stage_host.hpp"
 #include "plate.hpp"
 #include "rectify_dense.hpp"
 #include "rsdsfm_internal.hpp"
@@ -36,14 +34,6 @@ const char* const kPlateParamsMessage =
     "rsdsfm_plate_params: radius in [1, 7] or 0, threshold in [1, 255] or 0, min_votes in [1, 15] or 0, gain_mode 0 or 1, occlusion 0 or 1, occlusion_tol_q16 in [0, 65536], "
     "min_overlap >= 0, struct_bytes 0 or sizeof (use rsdsfm_plate_params_init)";
 
-bool plate_size_ok(int rows, int cols) { return rows >= 2 && cols >= 2 && rows <= 16384 && cols <= 16384; }
-
-bool plate_finite_all(const double* a, int n) {
-    for (int i = 0; i < n; ++i)
-        if (!std::isfinite(a[i])) return false;
-    return true;
-}
-
 // the argument checks of the outputs, for the median call and, before anything is enqueued, for the frame call (whose input planes are the context's)
 int plate_outputs_check(Ctx* c, const uint8_t* d_image_out, const uint8_t* d_mask_out, const uint8_t* d_votes, const uint8_t* d_moving, const int64_t* d_counts4) {
     if (!d_image_out || !d_mask_out) return fail(c, RSDSFM_ERR_INVALID, "plate: null output plane");
@@ -59,7 +49,7 @@ int plate_outputs_check(Ctx* c, const uint8_t* d_image_out, const uint8_t* d_mas
 
 // the workspace's reference planes, records and a stack of at least `layers` layers, made when first asked for and again when more layers are asked for
 int plate_ws(Ctx* c, int rows, int cols, int layers, DenseWs** ws) {
-    const int rc = rectify_dense_ws(c, rows, cols, ws);  // a size change releases them with the rest
+    int rc = rectify_dense_ws(c, rows, cols, ws);  // a size change releases them with the rest
     if (rc != RSDSFM_OK) return rc;
     DenseWs* w = *ws;
     if (w->d_plate && w->plate_layers < layers) {  // behind whatever the stream still runs on the smaller stack
@@ -69,36 +59,14 @@ int plate_ws(Ctx* c, int rows, int cols, int layers, DenseWs** ws) {
         w->plate_layers = 0;
     }
     if (!w->d_plate) {
-        if (hipMalloc(reinterpret_cast<void**>(&w->d_plate), plate_ws_bytes(rows, cols, layers)) != hipSuccess) {
-            w->d_plate = nullptr;
-            return fail(c, RSDSFM_ERR_HIP, "plate: no memory for the reference planes and the stack of layers");
-        }
+        rc = ensure_plane(c, &w->d_plate, plate_ws_bytes(rows, cols, layers), "plate: no memory for the reference planes and the stack of layers");
+        if (rc != RSDSFM_OK) return rc;
         w->plate_layers = layers;
     }
     return RSDSFM_OK;
 }
 
-// one frame's host part for the clip call: the sources (the own frame first) and their poses
-struct PlatePlan {
-    int nsrc = 0;
-    int32_t src[kPlateSourcesMax];
-    double M[9 * kPlateSourcesMax], m[3 * kPlateSourcesMax];
-};
-
-bool plate_plan(const double* A, const double* c_, const double* A_path, const double* c_path, const double* scales, int nsources, int q, int radius, PlatePlan* plan) {
-    int32_t src2[2], nsrc = 0, wq = 0, ids[kPlateLayersMax], count = 0;
-    double M18[18], m6[6], At[9], ct[3];
-    if (rsdsfm_retime_poses(A, c_, A_path, c_path, scales, nsources, (double)q, src2, &nsrc, &wq, M18, m6, At, ct) != RSDSFM_OK || nsrc != 1) return false;
-    plan->src[0] = q;
-    for (int k = 0; k < 9; ++k) plan->M[k] = M18[k];
-    for (int k = 0; k < 3; ++k) plan->m[k] = m6[k];
-    if (nsources > 1 && rsdsfm_neighbour_poses(A, c_, A_path, c_path, scales, nsources, q, radius, plan->src + 1, ids, plan->M + 9, plan->m + 3, &count) != RSDSFM_OK)
-        return false;
-    plan->nsrc = 1 + count;
-    return plate_finite_all(plan->M, 9 * plan->nsrc) && plate_finite_all(plan->m, 3 * plan->nsrc);
-}
-
-const char* const kPlatePlanMessage = "plate video: the poses must be finite and every listed source's scale finite and positive";
+static_assert(kPlateSourcesMax == kClipSourcesMax, "a frame's sources are a ClipPlan's");
 
 }  // namespace
 }  // namespace rsdsfm
@@ -129,7 +97,7 @@ int rsdsfm_plate_median_dev(rsdsfm_ctx* ctx, const uint8_t* d_ref_image, const u
     if (!ctx) return RSDSFM_ERR_INVALID;
     Ctx* c = &ctx->c;
     DeviceGuard device_guard_(c);
-    if (!plate_size_ok(rows, cols)) return fail(c, RSDSFM_ERR_INVALID, "plate: rows and cols must be in [2, 16384]");
+    if (!frame_size_ok(rows, cols)) return fail(c, RSDSFM_ERR_INVALID, "plate: rows and cols must be in [2, 16384]");
     if (channels != 1 && channels != 3) return fail(c, RSDSFM_ERR_INVALID, "plate: channels must be 1 or 3");
     if (nlayers < 0 || nlayers > kPlateLayersMax) return fail(c, RSDSFM_ERR_INVALID, "plate median: nlayers must be in [0, 14]");
     if (min_overlap < 0 || (gain_mode != 0 && gain_mode != 1) || threshold < 0 || threshold > kPlateThresholdMax || min_votes < 0 || min_votes > kPlateMinVotesMax)
@@ -197,14 +165,13 @@ int rsdsfm_plate_frame_dev(rsdsfm_ctx* ctx, const uint8_t* const* d_images, int3
         if (!d_images[k] || !d_depths_colmajor[k] || !d_R_rows9[k] || !d_t_rows3[k] || d_images[k] == d_image_out || d_images[k] == d_mask_out ||
             (d_votes_or_null && d_images[k] == d_votes_or_null) || (d_moving_or_null && d_images[k] == d_moving_or_null) || ((uintptr_t)d_images[k] & 3u))
             return fail(c, RSDSFM_ERR_INVALID, "plate frame: null, misaligned or aliased source pointer");
-    if (!M || !m || !plate_finite_all(M, 9 * nsrc) || !plate_finite_all(m, 3 * nsrc))
+    if (!M || !m || !finite_all(M, 9 * nsrc) || !finite_all(m, 3 * nsrc))
         return fail(c, RSDSFM_ERR_INVALID, "plate frame: the poses (M, m) must be given and finite");
     rc = plate_outputs_check(c, d_image_out, d_mask_out, d_votes_or_null, d_moving_or_null, d_counts4_or_null);
     if (rc != RSDSFM_OK) return rc;
-    const int32_t full[4] = {0, 0, rows, cols};
-    const int32_t* window = window_or_null ? window_or_null : full;
-    if (window[2] < 1 || window[3] < 1 || window[0] < 0 || window[1] < 0 || (int64_t)window[0] + window[2] > rows || (int64_t)window[1] + window[3] > cols)
-        return fail(c, RSDSFM_ERR_INVALID, "plate frame: the window (r0, c0, h, w) needs h >= 1, w >= 1 and must lie inside the frame");
+    int32_t full[4];
+    const int32_t* window = window_or_full(window_or_null, rows, cols, full);
+    if (!window) return fail(c, RSDSFM_ERR_INVALID, "plate frame: the window (r0, c0, h, w) needs h >= 1, w >= 1 and must lie inside the frame");
     DenseWs* ws = nullptr;
     const int nl = nsrc - 1;
     rc = plate_ws(c, rows, cols, nl, &ws);
@@ -215,14 +182,9 @@ int rsdsfm_plate_frame_dev(rsdsfm_ctx* ctx, const uint8_t* const* d_images, int3
     uint8_t* rimage = ws->d_plate + 2 * P;
     uint64_t* records = reinterpret_cast<uint64_t*>(ws->d_plate + 5 * P);
     uint8_t* stack = ws->d_plate + 5 * P + plate_records_bytes();
-    if (hipMemsetAsync(rimage, 0, plane * (size_t)channels, c->stream) != hipSuccess || hipMemsetAsync(rmask, 0, plane, c->stream) != hipSuccess ||
-        hipMemsetAsync(rsource, 0, plane, c->stream) != hipSuccess)
-        return fail(c, RSDSFM_ERR_HIP, "plate frame: zeroing the reference failed");
-    // the public entry points themselves, so that they run the code they run alone.  The own frame never goes through the occlusion test
-    rc = rsdsfm_stabilize_window_frame_dev(ctx, d_images[0], channels, d_depths_colmajor[0], d_R_rows9[0], d_t_rows3[0], fx, fy, cx, cy, rows, cols, mode, q5_mode, iterations,
-                                           M, m, 1, window, rimage, rmask, rsource, nullptr);
+    rc = render_reference(ctx, "plate frame", d_images[0], channels, d_depths_colmajor[0], d_R_rows9[0], d_t_rows3[0], fx, fy, cx, cy, rows, cols, mode, q5_mode, iterations, M,
+                          m, window, rimage, rmask, rsource);
     if (rc != RSDSFM_OK) return rc;
-    const bool srch = pp.occlusion == 1 && c->occlusion_search == 1;
     const uint8_t *limages[kPlateLayersMax], *lmasks[kPlateLayersMax];
     for (int k = 1; k < nsrc; ++k) {
         uint8_t* lmask = stack + 4 * P * (size_t)(k - 1);  // every neighbour its own layer: the median sees them all at once
@@ -232,13 +194,8 @@ int rsdsfm_plate_frame_dev(rsdsfm_ctx* ctx, const uint8_t* const* d_images, int3
         if (hipMemsetAsync(limage, 0, plane * (size_t)channels, c->stream) != hipSuccess || hipMemsetAsync(lmask, 0, plane, c->stream) != hipSuccess)
             return fail(c, RSDSFM_ERR_HIP, "plate frame: zeroing a layer failed");
         const int id = 2;  // no source plane is passed: the id is not written anywhere
-        rc = srch ? rsdsfm_stabilize_search_frame_dev(ctx, d_images[k], channels, d_depths_colmajor[k], d_R_rows9[k], d_t_rows3[k], fx, fy, cx, cy, rows, cols, mode, q5_mode,
-                                                      iterations, M + 9 * k, m + 3 * k, id, window, limage, lmask, nullptr, pp.occlusion_tol_q16, nullptr)
-             : pp.occlusion == 1
-                 ? rsdsfm_stabilize_visible_frame_dev(ctx, d_images[k], channels, d_depths_colmajor[k], d_R_rows9[k], d_t_rows3[k], fx, fy, cx, cy, rows, cols, mode, q5_mode,
-                                                      iterations, M + 9 * k, m + 3 * k, id, window, limage, lmask, nullptr, pp.occlusion_tol_q16, nullptr)
-                 : rsdsfm_stabilize_window_frame_dev(ctx, d_images[k], channels, d_depths_colmajor[k], d_R_rows9[k], d_t_rows3[k], fx, fy, cx, cy, rows, cols, mode, q5_mode,
-                                                     iterations, M + 9 * k, m + 3 * k, id, window, limage, lmask, nullptr, nullptr);
+        rc = render_candidate(ctx, pp.occlusion == 1, pp.occlusion_tol_q16, d_images[k], channels, d_depths_colmajor[k], d_R_rows9[k], d_t_rows3[k], fx, fy, cx, cy, rows, cols,
+                              mode, q5_mode, iterations, M + 9 * k, m + 3 * k, id, window, limage, lmask, nullptr, nullptr);
         if (rc != RSDSFM_OK) return rc;
         rc = rsdsfm_seam_overlap_sums_dev(ctx, rimage, rsource, limage, lmask, channels, rows, cols, records + 8 * (size_t)(k - 1));
         if (rc != RSDSFM_OK) return rc;
@@ -255,48 +212,21 @@ int rsdsfm_plate_video_dev(rsdsfm_ctx* ctx, const uint8_t* const* d_frames, int3
     if (!ctx) return RSDSFM_ERR_INVALID;
     Ctx* c = &ctx->c;
     DeviceGuard device_guard_(c);
-    if (nsources < 1) return fail(c, RSDSFM_ERR_INVALID, "plate video: nsources must be >= 1");
-    if (!d_frames || !d_depth_maps || !d_R || !d_t || !A || !c_ || !A_path || !c_path || !scales) return fail(c, RSDSFM_ERR_INVALID, "plate video: null array");
-    if (!all_set(d_frames, nsources) || !all_set(d_depth_maps, nsources) || !all_set(d_R, nsources) || !all_set(d_t, nsources))
-        return fail(c, RSDSFM_ERR_INVALID, "plate video: every source needs its frame, depth map and pose table");
-    if (!d_out_images || !d_out_masks || !all_set(d_out_images, nsources) || !all_set(d_out_masks, nsources) ||
-        (d_out_votes_or_null && !all_set(d_out_votes_or_null, nsources)) || (d_out_moving_or_null && !all_set(d_out_moving_or_null, nsources)))
-        return fail(c, RSDSFM_ERR_INVALID, "plate video: every frame needs its image and its mask (and its votes and flag planes when their arrays are passed)");
+    ClipOutputs outs;
+    outs.planes[0] = d_out_images;
+    outs.planes[1] = d_out_masks;
+    outs.planes[2] = d_out_votes_or_null;
+    outs.planes[3] = d_out_moving_or_null;
+    const int rc = clip_arrays_check(c, "plate video", d_frames, nsources, d_depth_maps, d_R, d_t, A, c_, A_path, c_path, scales, outs,
+                                     "its votes and flag planes when their arrays are passed");
+    if (rc != RSDSFM_OK) return rc;
     rsdsfm_plate_params pp;
     if (!plate_params_resolve(params_or_null, &pp)) return fail(c, RSDSFM_ERR_INVALID, kPlateParamsMessage);
-    for (int q = 0; q < nsources; ++q)  // an output may not be a frame of the clip: a later frame call still reads it
-        for (int n = 0; n < nsources; ++n)
-            if (d_frames[n] == d_out_images[q] || d_frames[n] == d_out_masks[q] || (d_out_votes_or_null && d_frames[n] == d_out_votes_or_null[q]) ||
-                (d_out_moving_or_null && d_frames[n] == d_out_moving_or_null[q]))
-                return fail(c, RSDSFM_ERR_INVALID, "plate video: an output plane may not be a frame of the clip");
-    // every frame's sources and poses first: a refused pose enqueues nothing
-    std::vector<PlatePlan> plans(nsources);
-    for (int q = 0; q < nsources; ++q)
-        if (!plate_plan(A, c_, A_path, c_path, scales, nsources, q, pp.radius, &plans[q])) return fail(c, RSDSFM_ERR_INVALID, kPlatePlanMessage);
-    int64_t* d_cnt = nullptr;
-    if (counts_or_null) RSDSFM_HIP_CHECK(c, hipMalloc(reinterpret_cast<void**>(&d_cnt), 4 * sizeof(int64_t) * (size_t)nsources));
-    int rc = RSDSFM_OK;
-    for (int q = 0; q < nsources && rc == RSDSFM_OK; ++q) {  // the public entry point itself, so that it runs the code it runs alone
-        const PlatePlan& p = plans[q];
-        const uint8_t* img[kPlateSourcesMax];
-        const double *map[kPlateSourcesMax], *R[kPlateSourcesMax], *t[kPlateSourcesMax];
-        for (int k = 0; k < p.nsrc; ++k) {
-            img[k] = d_frames[p.src[k]];
-            map[k] = d_depth_maps[p.src[k]];
-            R[k] = d_R[p.src[k]];
-            t[k] = d_t[p.src[k]];
-        }
-        rc = rsdsfm_plate_frame_dev(ctx, img, channels, map, R, t, fx, fy, cx, cy, rows, cols, mode, q5_mode, iterations, p.nsrc, p.M, p.m, params_or_null, window_or_null,
-                                    d_out_images[q], d_out_masks[q], d_out_votes_or_null ? d_out_votes_or_null[q] : nullptr,
-                                    d_out_moving_or_null ? d_out_moving_or_null[q] : nullptr, d_cnt ? d_cnt + 4 * (size_t)q : nullptr);
-    }
-    if (d_cnt) {
-        hipError_t e = rc == RSDSFM_OK ? hipMemcpyAsync(counts_or_null, d_cnt, 4 * sizeof(int64_t) * (size_t)nsources, hipMemcpyDeviceToHost, c->stream) : hipSuccess;
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        (void)hipFree(d_cnt);
-        if (rc == RSDSFM_OK) RSDSFM_HIP_CHECK(c, e);
-    }
-    return rc;
+    // the public entry point itself, so that it runs the code it runs alone
+    return walk_clip(c, "plate video", d_frames, nsources, d_depth_maps, d_R, d_t, A, c_, A_path, c_path, scales, pp.radius, outs, 4, counts_or_null, [&](const ClipFrame& f) {
+        return rsdsfm_plate_frame_dev(ctx, f.img, channels, f.map, f.R, f.t, fx, fy, cx, cy, rows, cols, mode, q5_mode, iterations, f.plan->nsrc, f.plan->M, f.plan->m,
+                                      params_or_null, window_or_null, f.out[0], f.out[1], f.out[2], f.out[3], f.d_counts);
+    });
 }
 
 }  // extern "C"

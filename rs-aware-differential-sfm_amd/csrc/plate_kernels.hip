@@ -1,10 +1,9 @@
 // plate_kernels.hip -- the clean plate's median on MI355X (gfx950, wave64): include/rsdsfm_plate.h, defined by tests/plate_spec_numpy.py and
 // reproduced bit for bit.  Integer arithmetic only; every value goes to memory through ordinary stores and atomicAdd.  The project's first image
 // stage that is not a sum: of the accumulate kernels (denoise_kernels.hip) only the tile is borrowed.
-//   plate_median_kernel<CH, NL, FLAG>  the denoise's 2-D tile: a workgroup of kBP threads owns 16 rows x 64 columns, a thread 4 consecutive pixels
-//                               of one row.  The planes are dense (no pitch): every plane is read as ALIGNED dwords of the flat array about the
-//                               thread's bytes and shifted into place (one path for every cols; a dword that would reach past the plane's end is
-//                               read byte by byte).  NL: the layer count the instance is compiled for, one of kPlateSizes = 0, 2, 4, 7, 14; a call
+//   plate_median_kernel<CH, NL, FLAG>  on the 16 x 64 tile of image_tile_device.hpp (the plane reads, the LDS layout and its bank argument, the
+//                               output group and the counters are described there).
+//                               NL: the layer count the instance is compiled for, one of kPlateSizes = 0, 2, 4, 7, 14; a call
 //                               with L layers runs the smallest NL >= L and tests j < L (uniform) before it touches layer j.  The reference, the
 //                               layers and the records are pointers in the kernel argument (PlateArgs, 320 B): after unrolling every one is a
 //                               scalar load at a constant offset, there is no pointer table in memory.
@@ -19,18 +18,16 @@
 //                                 compiler.  The element at (n - 1) >> 1 is taken per halfword by a chain of selects over indices
 //                                 0 .. NL / 2, not by indexing.
 //                               FLAG (a flag plane or the counters were passed): e = sum_c |R_c - P_c| where mR is set and n >= min_votes, the
-//                                 packed dword (v << 16) | e to LDS, 18 rows x 66 dwords = 4 752 B, the tile's pixel (y, x) at [y + 1][x + 1]
-//                                 (the denoise's layout and bank argument).  The halo of 1 about the tile -- 2 * 66 + 2 * 16 = 164 pixels -- is
-//                                 formed by threads 0 .. 163, each its own median byte by byte (channels 0 and 1 share the packed network),
-//                                 never outside the frame.  The 3 x 3 sums from LDS as nine 8-byte reads; D > threshold * CH * count decides.
-//                                 The four counters: a sum per thread, shuffles, LDS, one 64-bit integer atomicAdd each per workgroup.
+//                                 packed dword (v << 16) | e to LDS.  A halo thread forms its own median byte by byte (channels 0 and 1 share
+//                                 the packed network), never outside the frame.  D > threshold * CH * count of the 3 x 3 sums decides.  The
+//                                 four counters [unset, static, moving, undecided].
 //                               Not FLAG: no LDS tile, no halo, one barrier (the gains; none at NL == 0).
-//                               Stores: whole dwords where the four pixels start on one, else byte by byte: every byte of the outputs given is
-//                                 written, no preset.
+//                               Every byte of the outputs given is written, no preset.
 //                               BGR, five sources: 5 (3 + 1) = 20 B read and 3 + 1 (+ 1 + 1) B written per pixel, plus the halo's 164 / 1024 of
 //                                 the reads with FLAG.
 #include <algorithm>
 
+#include "image_tile_device.hpp"
 #include "plate.hpp"
 #include "rectify_dense_device.hpp"
 #include "rsdsfm_internal.hpp"
@@ -39,52 +36,11 @@ namespace rsdsfm {
 
 namespace {
 
-constexpr int kTR = kDenoiseTileRows, kTC = kDenoiseTileCols;
-constexpr int kLdsStride = kTC + 2;                 // 66 dwords: the denoise's bank argument
-constexpr int kHalo = 2 * (kTC + 2) + 2 * kTR;      // 164
-static_assert(kTR * (kTC / 4) == kBP, "a thread owns 4 consecutive pixels of a row of the tile");
-static_assert(kHalo <= kBP && kLdsStride % 2 == 0, "one halo pixel per thread; 8-byte aligned rows");
 static_assert(kPlateSizes[kPlateNumSizes - 1] == kPlateLayersMax, "the largest instance holds every call");
 
 constexpr unsigned kUnset = 0xFFFFu;  // a candidate that is not there: above every byte, so it sorts last
 
-// 1 in every byte of w that is not 0
-__device__ __forceinline__ unsigned bytes_set(unsigned w) { return ((w | ((w & 0x7f7f7f7fu) + 0x7f7f7f7fu)) >> 7) & 0x01010101u; }
-
-// byte k of an array of dwords (k a compile-time constant after unrolling)
-__device__ __forceinline__ unsigned byte_of(const unsigned* w, int k) { return (w[k >> 2] >> (8 * (k & 3))) & 0xffu; }
-
-typedef unsigned Lds8 __attribute__((ext_vector_type(2), aligned(8)));  // one ds_read_b64
-typedef unsigned short Half2 __attribute__((ext_vector_type(2)));        // two candidates of one compare-exchange
-
-// the aligned dword at byte offset o (a multiple of 4) of a plane of nbytes bytes; bytes past the plane's end read as 0 and are not touched
-__device__ __forceinline__ unsigned aligned_dword(const unsigned char* __restrict__ base, int64_t o, int64_t nbytes) {
-    if (o + 4 <= nbytes) return *reinterpret_cast<const unsigned*>(base + o);
-    unsigned w = 0u;
-    for (int b = 0; b < 4; ++b)
-        if (o + b < nbytes) w |= (unsigned)base[o + b] << (8 * b);
-    return w;
-}
-
-// ND dwords of bytes from byte offset `off` (any alignment) of a plane, as ND + 1 aligned dwords shifted into place
-template <int ND>
-__device__ __forceinline__ void load_bytes(const unsigned char* __restrict__ base, int64_t off, int64_t nbytes, unsigned* out) {
-    const int64_t a = off & ~(int64_t)3;
-    const unsigned sh = 8u * (unsigned)(off & 3);
-    unsigned w[ND + 1];
-#pragma unroll
-    for (int d = 0; d < ND; ++d) w[d] = aligned_dword(base, a + 4 * d, nbytes);
-    w[ND] = sh ? aligned_dword(base, a + 4 * ND, nbytes) : 0u;
-#pragma unroll
-    for (int d = 0; d < ND; ++d) out[d] = sh ? (w[d] >> sh) | (w[d + 1] << (32u - sh)) : w[d];
-}
-
-__device__ __forceinline__ unsigned gained(unsigned G, unsigned l) {  // G <= 2^18, the byte < 2^8
-    const unsigned k = (G * l + 32768u) >> 16;
-    return k > 255u ? 255u : k;
-}
-
-__device__ __forceinline__ unsigned absdiff(unsigned a, unsigned b) { return a > b ? a - b : b - a; }
+typedef unsigned short Half2 __attribute__((ext_vector_type(2)));  // two candidates of one compare-exchange
 
 // Batcher's odd-even merge sort for N elements as a list of compare-exchanges (a[i] < b[i]), made at compile time
 template <int N>
@@ -142,16 +98,13 @@ __device__ __forceinline__ unsigned median2(unsigned (&v)[N], unsigned med_lo, u
 template <int CH, int NL, bool FLAG>
 __device__ __forceinline__ void plate_median_body(const PlateArgs& a) {
     constexpr int N = NL + 1;  // candidates
-    __shared__ __attribute__((aligned(16))) unsigned s_tile[FLAG ? (kTR + 2) * kLdsStride : 2];
+    __shared__ __attribute__((aligned(16))) unsigned s_tile[FLAG ? kTileLdsWords : 2];
     __shared__ unsigned s_gain[NL * CH + 1];
     const int rows = a.rows, cols = a.cols, nl = a.nlayers;
-    const int tid = (int)threadIdx.x, ty = tid / (kTC / 4), g = tid % (kTC / 4);
-    const int y0 = (int)blockIdx.y * kTR, x0 = (int)blockIdx.x * kTC;
-    const int y = y0 + ty, x = x0 + 4 * g;
-    const int64_t npix = (int64_t)rows * cols;
-    const int nin = (y < rows && x < cols) ? (cols - x < 4 ? cols - x : 4) : 0;  // the thread's pixels inside the frame: the first nin of its 4
-    const int64_t p0 = (int64_t)y * cols + x;
-    const unsigned inside = nin == 4 ? 0x01010101u : nin == 3 ? 0x00010101u : nin == 2 ? 0x00000101u : nin == 1 ? 0x00000001u : 0u;
+    const TileThread t = tile_thread(rows, cols);
+    const int tid = t.tid, nin = t.nin;
+    const int64_t p0 = t.p0, npix = (int64_t)rows * cols;
+    const unsigned inside = first_ones(nin);
 
     // the mask dwords first, then the images whose mask has a byte set
     unsigned mr = 0u, nw = 0u, ml[N], rw[CH], lw[N][CH];  // ml[NL], lw[NL] are never used: no array of length 0
@@ -224,7 +177,7 @@ __device__ __forceinline__ void plate_median_body(const PlateArgs& a) {
     unsigned fw = 0u, n4[4] = {0u, 0u, 0u, 0u};  // the flags, a byte per pixel; [unset, static, moving, undecided], at most 4 per thread
     if constexpr (FLAG) {
         // stage 1: the packed (v, e) of the thread's own four pixels
-        unsigned* row = s_tile + (ty + 1) * kLdsStride + 4 * g + 1;
+        unsigned* row = tile_own(s_tile, t);
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             unsigned e = 0u;
@@ -233,21 +186,12 @@ __device__ __forceinline__ void plate_median_body(const PlateArgs& a) {
             const bool v = ((mr >> (8 * j)) & 1u) && ((nw >> (8 * j)) & 0xffu) >= a.min_votes;
             row[j] = v ? (0x10000u | e) : 0u;
         }
-        // the halo: the rows above and below (66 each), the columns left and right (16 each), one pixel per thread, its own median
-        if (tid < kHalo) {
-            int ly, lx;
-            if (tid < 2 * kLdsStride) {
-                ly = tid < kLdsStride ? 0 : kTR + 1;
-                lx = tid < kLdsStride ? tid : tid - kLdsStride;
-            } else {
-                const int r = tid - 2 * kLdsStride;
-                ly = 1 + (r < kTR ? r : r - kTR);
-                lx = r < kTR ? 0 : kTC + 1;
-            }
-            const int hy = y0 + ly - 1, hx = x0 + lx - 1;
+        // the halo: one pixel per thread, its own median
+        if (tid < kTileHalo) {
+            const TileHalo h = tile_halo(t);
             unsigned ent = 0u;
-            if (hy >= 0 && hy < rows && hx >= 0 && hx < cols) {
-                const int64_t p = (int64_t)hy * cols + hx;
+            if (h.hy >= 0 && h.hy < rows && h.hx >= 0 && h.hx < cols) {
+                const int64_t p = (int64_t)h.hy * cols + h.hx;
                 if (a.rmask[p] != 0) {
                     unsigned seen = 0u, n = 1u;  // bit j: layer j saw the pixel
 #pragma unroll
@@ -282,22 +226,13 @@ __device__ __forceinline__ void plate_median_body(const PlateArgs& a) {
                     }
                 }
             }
-            s_tile[ly * kLdsStride + lx] = ent;
+            s_tile[h.ly * kTileLdsStride + h.lx] = ent;
         }
         __syncthreads();
-        // stage 2: the 3 x 3 sums of the packed dwords; three rows of six columns, 8-byte reads
+        // stage 2: the 3 x 3 sums of the packed dwords
         if (mr) {
-            unsigned col[6] = {0u, 0u, 0u, 0u, 0u, 0u};
-#pragma unroll
-            for (int r = 0; r < 3; ++r) {
-                const Lds8* q = static_cast<const Lds8*>(__builtin_assume_aligned(s_tile + (ty + r) * kLdsStride + 4 * g, 8));
-#pragma unroll
-                for (int i = 0; i < 3; ++i) {
-                    const Lds8 t = q[i];
-                    col[2 * i] += t[0];  // the high half is a count <= 9, the low half <= 9 * 765 = 6 885: no carry
-                    col[2 * i + 1] += t[1];
-                }
-            }
+            unsigned col[6];
+            tile_sum3x3(s_tile, t.ty, t.g, col);
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const unsigned s = col[j] + col[j + 1] + col[j + 2];
@@ -317,41 +252,11 @@ __device__ __forceinline__ void plate_median_body(const PlateArgs& a) {
             }
     }
 
-    if (nin == 4 && (p0 & 3) == 0) {  // p0 and CH * p0 bytes are 4-byte aligned
-#pragma unroll
-        for (int d = 0; d < CH; ++d) reinterpret_cast<unsigned*>(a.out + (int64_t)CH * p0)[d] = ow[d];
-        *reinterpret_cast<unsigned*>(a.mask_out + p0) = mw;
-        if (a.votes) *reinterpret_cast<unsigned*>(a.votes + p0) = nw;
-        if (FLAG && a.moving) *reinterpret_cast<unsigned*>(a.moving + p0) = fw;
-    } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-            if (j < nin) {
-#pragma unroll
-                for (int c = 0; c < CH; ++c) a.out[(int64_t)CH * (p0 + j) + c] = (unsigned char)byte_of(ow, CH * j + c);
-                a.mask_out[p0 + j] = (unsigned char)((mw >> (8 * j)) & 0xffu);
-                if (a.votes) a.votes[p0 + j] = (unsigned char)((nw >> (8 * j)) & 0xffu);
-                if (FLAG && a.moving) a.moving[p0 + j] = (unsigned char)((fw >> (8 * j)) & 0xffu);
-            }
-    }
+    unsigned char* const planes[3] = {a.mask_out, a.votes, FLAG ? a.moving : nullptr};
+    const unsigned words[3] = {mw, nw, fw};
+    store_group<CH>(a.out, ow, planes, words, p0, nin);
 
-    if constexpr (FLAG) {
-        __shared__ unsigned s_wave[4][kBP / 64];
-        if (!a.counts) return;  // (uniform)
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) n4[k] += __shfl_down(n4[k], off, 64);
-            if ((threadIdx.x & 63) == 0) s_wave[k][threadIdx.x / 64] = n4[k];
-        }
-        __syncthreads();
-        if (threadIdx.x < 4) {
-            unsigned total = 0;
-#pragma unroll
-            for (int i = 0; i < kBP / 64; ++i) total += s_wave[threadIdx.x][i];
-            if (total) atomicAdd(a.counts + threadIdx.x, (unsigned long long)total);
-        }
-    }
+    if constexpr (FLAG) block_counts_add<4>(n4, a.counts);
 }
 
 }  // namespace
@@ -368,7 +273,6 @@ __global__ __launch_bounds__(kBP) void plate_median_kernel(const PlateArgs a) {
 // ---------------------------------------------------------------------------------------------------
 int plate_median_launch(Ctx* c, const PlateArgs& args, int channels) {
     if (args.counts) RSDSFM_HIP_CHECK(c, hipMemsetAsync(args.counts, 0, 4 * sizeof(int64_t), c->stream));
-    const dim3 grid((unsigned)((args.cols + kTC - 1) / kTC), (unsigned)((args.rows + kTR - 1) / kTR));  // at most 256 x 1024
     using Kernel = void (*)(const PlateArgs);
 #define RSDSFM_PLATE_ROW(CH) \
     {{plate_median_kernel<CH, 0, false>, plate_median_kernel<CH, 0, true>}, {plate_median_kernel<CH, 2, false>, plate_median_kernel<CH, 2, true>}, \
@@ -380,7 +284,7 @@ int plate_median_launch(Ctx* c, const PlateArgs& args, int channels) {
     int size = 0;
     while (kPlateSizes[size] < args.nlayers) ++size;  // nlayers <= 14: checked by the caller
     const bool flag = args.moving != nullptr || args.counts != nullptr;
-    hipLaunchKernelGGL(kernels[channels == 3][size][flag], grid, dim3(kBP), 0, c->stream, args);
+    hipLaunchKernelGGL(kernels[channels == 3][size][flag], tile_grid(args.rows, args.cols), dim3(kBP), 0, c->stream, args);
     RSDSFM_HIP_CHECK(c, hipGetLastError());
     return RSDSFM_OK;
 }

@@ -6,6 +6,7 @@
 #include <cstring>
 #include <vector>
 
+#include "clip_stage_host.hpp"
 #include "link.hpp"
 #include "rectify_dense.hpp"
 #include "retime.hpp"
@@ -33,18 +34,10 @@ bool retime_params_resolve(const rsdsfm_retime_params* in, rsdsfm_retime_params*
 const char* const kRetimeParamsMessage =
     "rsdsfm_retime_params: threshold in [0, 255], occlusion 0 or 1, occlusion_tol_q16 in [0, 65536], struct_bytes 0 or sizeof (use rsdsfm_retime_params_init)";
 
-bool retime_size_ok(int rows, int cols) { return rows >= 2 && cols >= 2 && rows <= 16384 && cols <= 16384; }
-
-bool retime_finite_all(const double* a, int n) {
-    for (int i = 0; i < n; ++i)
-        if (!std::isfinite(a[i])) return false;
-    return true;
-}
-
 // the merge's argument checks, for the merge call and, before anything is enqueued, for the frame call (whose layers are the context's: NULL here)
 int retime_merge_check(Ctx* c, const uint8_t* d_image_a, const uint8_t* d_mask_a, const uint8_t* d_image_b, const uint8_t* d_mask_b, bool layers, int channels, int rows,
                        int cols, int weight_q16, int threshold, const uint8_t* d_image_out, const uint8_t* d_mask_out, const uint8_t* d_source, const int64_t* d_counts5) {
-    if (!retime_size_ok(rows, cols)) return fail(c, RSDSFM_ERR_INVALID, "retime merge: rows and cols must be in [2, 16384]");
+    if (!frame_size_ok(rows, cols)) return fail(c, RSDSFM_ERR_INVALID, "retime merge: rows and cols must be in [2, 16384]");
     if (channels != 1 && channels != 3) return fail(c, RSDSFM_ERR_INVALID, "retime merge: channels must be 1 or 3");
     if (weight_q16 < 0 || weight_q16 > kRetimeWeightMax) return fail(c, RSDSFM_ERR_INVALID, "retime merge: weight_q16 must be in [0, 65535]");
     if (threshold < 0 || threshold > kRetimeThresholdMax) return fail(c, RSDSFM_ERR_INVALID, "retime merge: threshold must be in [0, 255]");
@@ -170,41 +163,29 @@ int rsdsfm_retime_frame_dev(rsdsfm_ctx* ctx, const uint8_t* const* d_images, int
     for (int k = 0; k < nsrc; ++k)
         if (!d_images[k] || !d_depths_colmajor[k] || !d_R_rows9[k] || !d_t_rows3[k] || d_images[k] == d_image_out || ((uintptr_t)d_images[k] & 3u))
             return fail(c, RSDSFM_ERR_INVALID, "retime frame: null, misaligned or aliased source pointer");
-    if (!M18 || !m6 || !retime_finite_all(M18, 9 * nsrc) || !retime_finite_all(m6, 3 * nsrc))
+    if (!M18 || !m6 || !finite_all(M18, 9 * nsrc) || !finite_all(m6, 3 * nsrc))
         return fail(c, RSDSFM_ERR_INVALID, "retime frame: the poses (M, m) must be given and finite");
     rc = retime_merge_check(c, nullptr, nullptr, nullptr, nullptr, false, channels, rows, cols, weight_q16, rp.threshold, d_image_out, d_mask_out, d_source_or_null,
                             d_counts5_or_null);
     if (rc != RSDSFM_OK) return rc;
-    const int32_t full[4] = {0, 0, rows, cols};
-    const int32_t* window = window_or_null ? window_or_null : full;
-    if (window[2] < 1 || window[3] < 1 || window[0] < 0 || window[1] < 0 || (int64_t)window[0] + window[2] > rows || (int64_t)window[1] + window[3] > cols)
-        return fail(c, RSDSFM_ERR_INVALID, "retime frame: the window (r0, c0, h, w) needs h >= 1, w >= 1 and must lie inside the frame");
+    int32_t full[4];
+    const int32_t* window = window_or_full(window_or_null, rows, cols, full);
+    if (!window) return fail(c, RSDSFM_ERR_INVALID, "retime frame: the window (r0, c0, h, w) needs h >= 1, w >= 1 and must lie inside the frame");
     DenseWs* ws = nullptr;
     rc = rectify_dense_ws(c, rows, cols, &ws);  // a size change releases the layers with the rest
     if (rc != RSDSFM_OK) return rc;
-    if (!ws->d_layer && hipMalloc(reinterpret_cast<void**>(&ws->d_layer), blend_layer_bytes(rows, cols)) != hipSuccess) {
-        ws->d_layer = nullptr;
-        return fail(c, RSDSFM_ERR_HIP, "retime frame: no memory for layer A");
-    }
-    if (nsrc == 2 && !ws->d_layer2 && hipMalloc(reinterpret_cast<void**>(&ws->d_layer2), retime_layer2_bytes(rows, cols)) != hipSuccess) {
-        ws->d_layer2 = nullptr;
-        return fail(c, RSDSFM_ERR_HIP, "retime frame: no memory for layer B");
-    }
+    rc = ensure_plane(c, &ws->d_layer, blend_layer_bytes(rows, cols), "retime frame: no memory for layer A");
+    if (rc == RSDSFM_OK && nsrc == 2) rc = ensure_plane(c, &ws->d_layer2, retime_layer2_bytes(rows, cols), "retime frame: no memory for layer B");
+    if (rc != RSDSFM_OK) return rc;
     const size_t plane = (size_t)rows * (size_t)cols, P = blend_plane_bytes(rows, cols);
     uint8_t* lmask[2] = {ws->d_layer + P, nsrc == 2 ? ws->d_layer2 : nullptr};
     uint8_t* limage[2] = {ws->d_layer + 2 * P, nsrc == 2 ? ws->d_layer2 + P : nullptr};
-    const bool srch = rp.occlusion == 1 && c->occlusion_search == 1;
     for (int k = 0; k < nsrc; ++k) {
         if (hipMemsetAsync(limage[k], 0, plane * (size_t)channels, c->stream) != hipSuccess || hipMemsetAsync(lmask[k], 0, plane, c->stream) != hipSuccess)
             return fail(c, RSDSFM_ERR_HIP, "retime frame: zeroing a layer failed");
         const int id = k == 0 ? RSDSFM_RETIME_FROM_A : RSDSFM_RETIME_FROM_B;  // no source plane is passed: the id is not written anywhere
-        rc = srch ? rsdsfm_stabilize_search_frame_dev(ctx, d_images[k], channels, d_depths_colmajor[k], d_R_rows9[k], d_t_rows3[k], fx, fy, cx, cy, rows, cols, mode, q5_mode,
-                                                      iterations, M18 + 9 * k, m6 + 3 * k, id, window, limage[k], lmask[k], nullptr, rp.occlusion_tol_q16, nullptr)
-             : rp.occlusion == 1
-                 ? rsdsfm_stabilize_visible_frame_dev(ctx, d_images[k], channels, d_depths_colmajor[k], d_R_rows9[k], d_t_rows3[k], fx, fy, cx, cy, rows, cols, mode, q5_mode,
-                                                      iterations, M18 + 9 * k, m6 + 3 * k, id, window, limage[k], lmask[k], nullptr, rp.occlusion_tol_q16, nullptr)
-                 : rsdsfm_stabilize_window_frame_dev(ctx, d_images[k], channels, d_depths_colmajor[k], d_R_rows9[k], d_t_rows3[k], fx, fy, cx, cy, rows, cols, mode, q5_mode,
-                                                     iterations, M18 + 9 * k, m6 + 3 * k, id, window, limage[k], lmask[k], nullptr, nullptr);
+        rc = render_candidate(ctx, rp.occlusion == 1, rp.occlusion_tol_q16, d_images[k], channels, d_depths_colmajor[k], d_R_rows9[k], d_t_rows3[k], fx, fy, cx, cy, rows, cols,
+                              mode, q5_mode, iterations, M18 + 9 * k, m6 + 3 * k, id, window, limage[k], lmask[k], nullptr, nullptr);
         if (rc != RSDSFM_OK) return rc;
     }
     // the public entry point itself, so that it runs the code it runs alone
@@ -238,9 +219,8 @@ int rsdsfm_retime_video_dev(rsdsfm_ctx* ctx, const uint8_t* const* d_frames, int
             RSDSFM_OK)
             return fail(c, RSDSFM_ERR_INVALID, "retime video: a time must be finite and in [0, nsources - 1], and its sources' scales finite and positive");
     }
-    int64_t* d_cnt = nullptr;
-    if (counts_or_null) RSDSFM_HIP_CHECK(c, hipMalloc(reinterpret_cast<void**>(&d_cnt), 5 * sizeof(int64_t) * (size_t)ntimes));
-    int rc = RSDSFM_OK;
+    DeviceCounts counts;
+    int rc = counts.alloc(c, counts_or_null != nullptr, 5 * (size_t)ntimes);
     for (int i = 0; i < ntimes && rc == RSDSFM_OK; ++i) {
         const int n0 = src[2 * (size_t)i], n1 = nsrc[i] == 2 ? n0 + 1 : n0;
         const uint8_t* img[2] = {d_frames[n0], d_frames[n1]};
@@ -249,14 +229,9 @@ int rsdsfm_retime_video_dev(rsdsfm_ctx* ctx, const uint8_t* const* d_frames, int
         const double* t[2] = {d_t[n0], d_t[n1]};
         rc = rsdsfm_retime_frame_dev(ctx, img, channels, map, R, t, fx, fy, cx, cy, rows, cols, mode, q5_mode, iterations, nsrc[i], &M[18 * (size_t)i], &m[6 * (size_t)i],
                                      wq[i], params_or_null, window_or_null, d_out_images[i], d_out_masks[i], d_out_sources_or_null ? d_out_sources_or_null[i] : nullptr,
-                                     d_cnt ? d_cnt + 5 * (size_t)i : nullptr);
+                                     counts.at(5 * (size_t)i));
     }
-    if (d_cnt) {
-        hipError_t e = rc == RSDSFM_OK ? hipMemcpyAsync(counts_or_null, d_cnt, 5 * sizeof(int64_t) * (size_t)ntimes, hipMemcpyDeviceToHost, c->stream) : hipSuccess;
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        (void)hipFree(d_cnt);
-        if (rc == RSDSFM_OK) RSDSFM_HIP_CHECK(c, e);
-    }
+    rc = counts.fetch(c, counts_or_null, rc);
     if (rc != RSDSFM_OK) return rc;
     for (int i = 0; i < ntimes; ++i) {
         sources_out[2 * (size_t)i] = src[2 * (size_t)i];

@@ -7,10 +7,11 @@
 //                               plane's dword are written whole: every byte of the outputs is written, no preset.  BGR with the source plane:
 //                               8 B read and 5 B written per pixel where both layers are set.  The last rows cols % 4 pixels byte by byte (the
 //                               byte tail).  HAS_B = false: b absent everywhere (one source), its pointers are not touched.
-//                               The five counters as the blend's: a sum per thread, shuffles, LDS, one 64-bit integer atomicAdd each per
-//                               workgroup (5 120 at most in all), only when a counter pointer was passed: exact and independent of scheduling.
+//                               The five counters (block_counts_add, image_tile_device.hpp: 5 120 atomicAdd at most in all), only when a
+//                               counter pointer was passed.
 #include <algorithm>
 
+#include "image_tile_device.hpp"
 #include "rectify_dense_device.hpp"
 #include "retime.hpp"
 #include "rsdsfm_internal.hpp"
@@ -18,12 +19,6 @@
 namespace rsdsfm {
 
 namespace {
-
-// 1 in every byte of w that is not 0
-__device__ __forceinline__ unsigned bytes_set(unsigned w) { return ((w | ((w & 0x7f7f7f7fu) + 0x7f7f7f7fu)) >> 7) & 0x01010101u; }
-
-// byte k of an array of dwords (k a compile-time constant after unrolling)
-__device__ __forceinline__ unsigned byte_of(const unsigned* w, int k) { return (w[k >> 2] >> (8 * (k & 3))) & 0xffu; }
 
 // one pixel: the source byte (RSDSFM_RETIME_*) from the two mask bits and the two pixels' channels, and the output channels
 template <int CH>
@@ -51,7 +46,6 @@ __device__ __forceinline__ void retime_merge_body(const unsigned char* __restric
                                                   const unsigned char* __restrict__ image_b, const unsigned char* __restrict__ mask_b, int npix, unsigned w,
                                                   unsigned thr, unsigned char* __restrict__ out, unsigned char* __restrict__ mask, unsigned char* __restrict__ source,
                                                   unsigned long long* __restrict__ counts) {
-    __shared__ unsigned s_wave[5][kBP / 64];
     unsigned n[5] = {0u, 0u, 0u, 0u, 0u};  // at most 4 per step and 2^28 / 4 steps in all: no overflow
     const int64_t stride = (int64_t)gridDim.x * kBP * 4;
     for (int64_t q0 = ((int64_t)blockIdx.x * kBP + threadIdx.x) * 4; q0 < npix; q0 += stride) {
@@ -111,20 +105,7 @@ __device__ __forceinline__ void retime_merge_body(const unsigned char* __restric
             }
         }
     }
-    if (!counts) return;  // (uniform)
-#pragma unroll
-    for (int k = 0; k < 5; ++k) {
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) n[k] += __shfl_down(n[k], off, 64);
-        if ((threadIdx.x & 63) == 0) s_wave[k][threadIdx.x / 64] = n[k];
-    }
-    __syncthreads();
-    if (threadIdx.x < 5) {
-        unsigned total = 0;
-#pragma unroll
-        for (int i = 0; i < kBP / 64; ++i) total += s_wave[threadIdx.x][i];
-        if (total) atomicAdd(counts + threadIdx.x, (unsigned long long)total);
-    }
+    block_counts_add<5>(n, counts);
 }
 
 }  // namespace

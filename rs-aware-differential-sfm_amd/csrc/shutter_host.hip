@@ -4,6 +4,7 @@
 #include <cmath>
 #include <vector>
 
+#include "clip_stage_host.hpp"
 #include "rectify_dense.hpp"
 #include "rsdsfm_internal.hpp"
 #include "sequence_host.hpp"
@@ -27,7 +28,7 @@ const char* const kShutterParamsMessage =
     "rsdsfm_shutter_params: samples in [1, 64], min_samples in [1, samples], struct_bytes 0 or sizeof (use rsdsfm_shutter_params_init)";
 
 int shutter_shape_check(Ctx* c, int channels, int rows, int cols) {
-    if (rows < 2 || cols < 2 || rows > 16384 || cols > 16384) return fail(c, RSDSFM_ERR_INVALID, "shutter: rows and cols must be in [2, 16384]");
+    if (!frame_size_ok(rows, cols)) return fail(c, RSDSFM_ERR_INVALID, "shutter: rows and cols must be in [2, 16384]");
     if (channels != 1 && channels != 3) return fail(c, RSDSFM_ERR_INVALID, "shutter: channels must be 1 or 3");
     return RSDSFM_OK;
 }
@@ -59,10 +60,7 @@ bool shutter_plan(const double* A, const double* c_, const double* A_path, const
         if (rsdsfm_retime_poses(A, c_, A_path, c_path, scales, nsources, times[j], plan->src + 2 * j, plan->nsrc + j, plan->wq + j, plan->M + 18 * j, plan->m + 6 * j, At, ct) !=
             RSDSFM_OK)
             return false;
-        for (int k = 0; k < 9 * plan->nsrc[j]; ++k)
-            if (!std::isfinite(plan->M[18 * j + k])) return false;
-        for (int k = 0; k < 3 * plan->nsrc[j]; ++k)
-            if (!std::isfinite(plan->m[6 * j + k])) return false;
+        if (!finite_all(plan->M + 18 * j, 9 * plan->nsrc[j]) || !finite_all(plan->m + 6 * j, 3 * plan->nsrc[j])) return false;
     }
     plan->kept = kept;
     return true;
@@ -95,11 +93,7 @@ int shutter_alias_check(Ctx* c, const uint8_t* const* d_frames, int nsources, co
 int shutter_ws(Ctx* c, int rows, int cols, DenseWs** ws) {
     const int rc = rectify_dense_ws(c, rows, cols, ws);  // a size change releases them with the rest
     if (rc != RSDSFM_OK) return rc;
-    if (!(*ws)->d_shutter && hipMalloc(reinterpret_cast<void**>(&(*ws)->d_shutter), shutter_ws_bytes(rows, cols)) != hipSuccess) {
-        (*ws)->d_shutter = nullptr;
-        return fail(c, RSDSFM_ERR_HIP, "shutter: no memory for the sample planes and the cells");
-    }
-    return RSDSFM_OK;
+    return ensure_plane(c, &(*ws)->d_shutter, shutter_ws_bytes(rows, cols), "shutter: no memory for the sample planes and the cells");
 }
 
 // the enqueues of one exposed frame (everything checked by the caller): the public calls one after another
@@ -255,18 +249,13 @@ int rsdsfm_shutter_video_dev(rsdsfm_ctx* ctx, const uint8_t* const* d_frames, in
         if (!shutter_plan(A, c_, A_path, c_path, scales, nsources, times[i], sp, &plan)) return fail(c, RSDSFM_ERR_INVALID, kShutterPlanMessage);
         kept[i] = plan.kept;
     }
-    int64_t* d_cnt = nullptr;
-    if (counts_or_null) RSDSFM_HIP_CHECK(c, hipMalloc(reinterpret_cast<void**>(&d_cnt), 3 * sizeof(int64_t) * (size_t)ntimes));
+    DeviceCounts counts;
+    rc = counts.alloc(c, counts_or_null != nullptr, 3 * (size_t)ntimes);
     for (int i = 0; i < ntimes && rc == RSDSFM_OK; ++i)  // the public entry point itself, so that it runs the code it runs alone
         rc = rsdsfm_shutter_frame_dev(ctx, d_frames, nsources, rows, cols, channels, fx, fy, cx, cy, d_depth_maps, d_R, d_t, A, c_, A_path, c_path, scales, mode, q5_mode,
                                       iterations, times[i], shutter_or_null, retime_or_null, window_or_null, d_out_images[i], d_out_masks[i],
-                                      d_out_coverage_or_null ? d_out_coverage_or_null[i] : nullptr, d_cnt ? d_cnt + 3 * (size_t)i : nullptr, nullptr);
-    if (d_cnt) {
-        hipError_t e = rc == RSDSFM_OK ? hipMemcpyAsync(counts_or_null, d_cnt, 3 * sizeof(int64_t) * (size_t)ntimes, hipMemcpyDeviceToHost, c->stream) : hipSuccess;
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        (void)hipFree(d_cnt);
-        if (rc == RSDSFM_OK) RSDSFM_HIP_CHECK(c, e);
-    }
+                                      d_out_coverage_or_null ? d_out_coverage_or_null[i] : nullptr, counts.at(3 * (size_t)i), nullptr);
+    rc = counts.fetch(c, counts_or_null, rc);
     if (rc != RSDSFM_OK) return rc;
     for (int i = 0; i < ntimes; ++i) kept_out[i] = kept[i];
     return RSDSFM_OK;

@@ -9,10 +9,12 @@
 //                               n >= min_samples, else 0 / 0; the image's CH dwords, the mask's and the coverage plane's dword are written whole:
 //                               every byte of the outputs is written, no preset.  The last rows cols % 4 pixels byte by byte (the byte tail).
 //                               A mid sample of a BGR frame moves 1 + 3 + 8 + 8 = 20 B per pixel where its mask is set.
-//                               The three counters [unset, partial, full] as the merge's: a sum per thread, shuffles, LDS, one 64-bit integer
-//                               atomicAdd each per workgroup (3 072 at most in all), only in LAST and only when a counter pointer was passed.
+//                               The three counters [unset, partial, full] (block_counts_add, image_tile_device.hpp: 3 072 atomicAdd at most in
+//                               all), only in LAST and only when a counter pointer was passed.  The cells here always start on 16 bytes and the
+//                               tail goes halfword by halfword, so this kernel keeps its own cell access and output stores.
 #include <algorithm>
 
+#include "image_tile_device.hpp"
 #include "rectify_dense_device.hpp"
 #include "rsdsfm_internal.hpp"
 #include "shutter.hpp"
@@ -20,18 +22,6 @@
 namespace rsdsfm {
 
 namespace {
-
-// 1 in every byte of w that is not 0
-__device__ __forceinline__ unsigned bytes_set(unsigned w) { return ((w | ((w & 0x7f7f7f7fu) + 0x7f7f7f7fu)) >> 7) & 0x01010101u; }
-
-// byte k of an array of dwords (k a compile-time constant after unrolling)
-__device__ __forceinline__ unsigned byte_of(const unsigned* w, int k) { return (w[k >> 2] >> (8 * (k & 3))) & 0xffu; }
-
-// halfword k of an array of dwords
-__device__ __forceinline__ unsigned half_of(const unsigned* w, int k) { return (w[k >> 1] >> (16 * (k & 1))) & 0xffffu; }
-
-// 16 bytes of cells; the ABI promises 8-byte alignment
-typedef unsigned Cells16 __attribute__((ext_vector_type(4), aligned(8)));
 
 // one pixel resolved: n and its CH sums -> the CH output bytes (0 where n < min_samples); returns 1 where the pixel is set
 template <int CH>
@@ -132,23 +122,7 @@ __device__ __forceinline__ void shutter_accumulate_body(const unsigned char* __r
             }
         }
     }
-    if constexpr (LAST) {
-        __shared__ unsigned s_wave[3][kBP / 64];
-        if (!counts) return;  // (uniform)
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) n3[k] += __shfl_down(n3[k], off, 64);
-            if ((threadIdx.x & 63) == 0) s_wave[k][threadIdx.x / 64] = n3[k];
-        }
-        __syncthreads();
-        if (threadIdx.x < 3) {
-            unsigned total = 0;
-#pragma unroll
-            for (int i = 0; i < kBP / 64; ++i) total += s_wave[threadIdx.x][i];
-            if (total) atomicAdd(counts + threadIdx.x, (unsigned long long)total);
-        }
-    }
+    if constexpr (LAST) block_counts_add<3>(n3, counts);
 }
 
 }  // namespace

@@ -4,6 +4,7 @@
 #include <vector>
 
 #include "../../include/rsdsfm_stabilize_blend.h"
+#include "clip_stage_host.hpp"
 #include "rectify_dense.hpp"
 #include "rsdsfm_internal.hpp"
 #include "last_frame.hpp"
@@ -33,8 +34,6 @@ bool blend_params_resolve(const rsdsfm_stabilize_blend_params* in, rsdsfm_stabil
 const char* const kBlendParamsMessage =
     "rsdsfm_stabilize_blend_params: feather in [1, 64] or 0, gain_mode 0 or 1, min_overlap >= 0, struct_bytes 0 or sizeof (use rsdsfm_stabilize_blend_params_init)";
 
-bool blend_size_ok(int rows, int cols) { return rows >= 2 && cols >= 2 && rows <= 16384 && cols <= 16384; }
-
 }  // namespace
 }  // namespace rsdsfm
 
@@ -48,9 +47,9 @@ int rsdsfm_stabilize_blend_params_init(rsdsfm_stabilize_blend_params* params) {
     return RSDSFM_OK;
 }
 
-int rsdsfm_seam_distance_launches(int32_t rows, int32_t cols) { return blend_size_ok(rows, cols) ? 2 : RSDSFM_ERR_INVALID; }
+int rsdsfm_seam_distance_launches(int32_t rows, int32_t cols) { return frame_size_ok(rows, cols) ? 2 : RSDSFM_ERR_INVALID; }
 
-int rsdsfm_seam_blend_layer_launches(int32_t rows, int32_t cols) { return blend_size_ok(rows, cols) ? 2 : RSDSFM_ERR_INVALID; }
+int rsdsfm_seam_blend_layer_launches(int32_t rows, int32_t cols) { return frame_size_ok(rows, cols) ? 2 : RSDSFM_ERR_INVALID; }
 
 int rsdsfm_seam_gains(const uint64_t* sums8, int32_t channels, int64_t min_overlap, int32_t gain_mode, uint32_t gains_out[3]) {
     if (!sums8 || !gains_out || (channels != 1 && channels != 3) || min_overlap < 0 || (gain_mode != 0 && gain_mode != 1)) return RSDSFM_ERR_INVALID;
@@ -64,17 +63,15 @@ int rsdsfm_seam_distance_dev(rsdsfm_ctx* ctx, const uint8_t* d_mask, int32_t row
     if (!ctx) return RSDSFM_ERR_INVALID;
     Ctx* c = &ctx->c;
     DeviceGuard device_guard_(c);
-    if (!blend_size_ok(rows, cols)) return fail(c, RSDSFM_ERR_INVALID, "seam distance: rows and cols must be in [2, 16384]");
+    if (!frame_size_ok(rows, cols)) return fail(c, RSDSFM_ERR_INVALID, "seam distance: rows and cols must be in [2, 16384]");
     if (feather < 0 || feather > kFeatherMax) return fail(c, RSDSFM_ERR_INVALID, "seam distance: feather must be in [1, 64] (0: the default, 16)");
     if (!d_mask || !d_dist_out || d_mask == d_dist_out) return fail(c, RSDSFM_ERR_INVALID, "seam distance: null or aliased device pointer");
     if (((uintptr_t)d_mask | (uintptr_t)d_dist_out) & 3u) return fail(c, RSDSFM_ERR_INVALID, "seam distance: the mask and the distance plane must be 4-byte aligned");
     DenseWs* ws = nullptr;
     const int rc = rectify_dense_ws(c, rows, cols, &ws);
     if (rc != RSDSFM_OK) return rc;
-    if (!ws->d_seam && hipMalloc(reinterpret_cast<void**>(&ws->d_seam), (size_t)rows * (size_t)cols) != hipSuccess) {
-        ws->d_seam = nullptr;
-        return fail(c, RSDSFM_ERR_HIP, "seam distance: no memory for the row pass's plane");
-    }
+    const int rm = ensure_plane(c, &ws->d_seam, (size_t)rows * (size_t)cols, "seam distance: no memory for the row pass's plane");
+    if (rm != RSDSFM_OK) return rm;
     return seam_distance_launch(c, d_mask, rows, cols, feather ? feather : kFeatherDefault, ws->d_seam, d_dist_out);
 }
 
@@ -84,7 +81,7 @@ int rsdsfm_seam_blend_layer_dev(rsdsfm_ctx* ctx, const uint8_t* d_layer_image, c
     if (!ctx) return RSDSFM_ERR_INVALID;
     Ctx* c = &ctx->c;
     DeviceGuard device_guard_(c);
-    if (!blend_size_ok(rows, cols)) return fail(c, RSDSFM_ERR_INVALID, "seam blend: rows and cols must be in [2, 16384]");
+    if (!frame_size_ok(rows, cols)) return fail(c, RSDSFM_ERR_INVALID, "seam blend: rows and cols must be in [2, 16384]");
     if (channels != 1 && channels != 3) return fail(c, RSDSFM_ERR_INVALID, "seam blend: channels must be 1 or 3");
     if (!d_layer_image || !d_layer_mask || !d_dist || !d_image_inout || !d_mask_inout || !d_source_inout || !d_sums_out)
         return fail(c, RSDSFM_ERR_INVALID, "seam blend: null device pointer (the source plane and the sums record are required)");
@@ -123,7 +120,7 @@ int rsdsfm_stabilize_video_blended_dev(rsdsfm_ctx* ctx, const uint8_t* const* d_
     DeviceGuard device_guard_(c);
     if (nframes < 2) return fail(c, RSDSFM_ERR_INVALID, "stabilise video: nframes must be >= 2");
     const int np = stabilize_rendered_frames(stabilize_params_or_null, nframes);  // rendered frames: the pairs' first frames, and the last frame when asked for
-    if (!blend_size_ok(rows, cols)) return fail(c, RSDSFM_ERR_INVALID, "blend: rows and cols must be in [2, 16384]");
+    if (!frame_size_ok(rows, cols)) return fail(c, RSDSFM_ERR_INVALID, "blend: rows and cols must be in [2, 16384]");
     if (channels != 1 && channels != 3) return fail(c, RSDSFM_ERR_INVALID, "blend: channels must be 1 or 3");
     rsdsfm_stabilize_blend_params bp;
     if (!blend_params_resolve(blend_params_or_null, &bp)) return fail(c, RSDSFM_ERR_INVALID, kBlendParamsMessage);
@@ -144,17 +141,14 @@ int rsdsfm_stabilize_video_blended_dev(rsdsfm_ctx* ctx, const uint8_t* const* d_
     if (rc != RSDSFM_OK) return rc;
     const int radius = fill_params_or_null ? fill_params_or_null->radius : kBlendFillRadiusDefault;  // 0 .. 16: the inner call checked it
     const bool occ = visible_asked(fill_params_or_null);  // every layer is rendered through the occlusion test (the inner call checked the words)
-    const bool srch = search_asked(c, fill_params_or_null);  // ... and through the search for the visible pre-image
     const int offs = 2 * radius;
     const size_t plane = (size_t)rows * (size_t)cols, P = blend_plane_bytes(rows, cols);
     const bool have = window_out[2] >= 1, host = gains_or_null || blend_counts_or_null;
     DenseWs* ws = nullptr;
     rc = rectify_dense_ws(c, rows, cols, &ws);
     if (rc != RSDSFM_OK) return rc;
-    if (!ws->d_layer && hipMalloc(reinterpret_cast<void**>(&ws->d_layer), blend_layer_bytes(rows, cols)) != hipSuccess) {
-        ws->d_layer = nullptr;
-        return fail(c, RSDSFM_ERR_HIP, "blend: no memory for the distance plane and the layer");
-    }
+    rc = ensure_plane(c, &ws->d_layer, blend_layer_bytes(rows, cols), "blend: no memory for the distance plane and the layer");
+    if (rc != RSDSFM_OK) return rc;
     uint8_t* d_dist = ws->d_layer;
     uint8_t* d_lmask = ws->d_layer + P;
     uint8_t* d_limage = ws->d_layer + 2 * P;
@@ -193,14 +187,8 @@ int rsdsfm_stabilize_video_blended_dev(rsdsfm_ctx* ctx, const uint8_t* const* d_
                 break;
             }
             const double* nmap = d_fused_maps_or_null ? d_fused_maps_or_null[n] : d_depth_maps[n];
-            rc = srch ? rsdsfm_stabilize_search_frame_dev(ctx, d_frames[n], channels, nmap, d_R[n], d_t[n], fx, fy, cx, cy, rows, cols, mode, q5_mode, iterations,
-                                                          nM + 9 * (size_t)k, nm + 3 * (size_t)k, ids[k], window_out, d_limage, d_lmask, nullptr,
-                                                          fill_params_or_null->occlusion_tol_q16, nullptr)
-                 : occ ? rsdsfm_stabilize_visible_frame_dev(ctx, d_frames[n], channels, nmap, d_R[n], d_t[n], fx, fy, cx, cy, rows, cols, mode, q5_mode, iterations,
-                                                          nM + 9 * (size_t)k, nm + 3 * (size_t)k, ids[k], window_out, d_limage, d_lmask, nullptr,
-                                                          fill_params_or_null->occlusion_tol_q16, nullptr)
-                     : rsdsfm_stabilize_window_frame_dev(ctx, d_frames[n], channels, nmap, d_R[n], d_t[n], fx, fy, cx, cy, rows, cols, mode, q5_mode, iterations,
-                                                         nM + 9 * (size_t)k, nm + 3 * (size_t)k, ids[k], window_out, d_limage, d_lmask, nullptr, nullptr);
+            rc = render_candidate(ctx, occ, occ ? fill_params_or_null->occlusion_tol_q16 : 0, d_frames[n], channels, nmap, d_R[n], d_t[n], fx, fy, cx, cy, rows, cols, mode,
+                                  q5_mode, iterations, nM + 9 * (size_t)k, nm + 3 * (size_t)k, ids[k], window_out, d_limage, d_lmask, nullptr, nullptr);
             if (rc == RSDSFM_OK)
                 rc = rsdsfm_seam_blend_layer_dev(ctx, d_limage, d_lmask, channels, rows, cols, d_dist, &bp, ids[k], d_blend_images[p], d_blend_masks[p], d_blend_sources[p],
                                                  rec ? rec + (size_t)slot * 8 : d_one,

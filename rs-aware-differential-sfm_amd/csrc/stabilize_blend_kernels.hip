@@ -27,6 +27,7 @@
 //                               integer atomicAdd each per workgroup, only when a counter pointer was passed.
 #include <algorithm>
 
+#include "image_tile_device.hpp"  // bytes_set, bytes_zero, byte_of
 #include "rectify_dense_device.hpp"
 #include "rsdsfm_internal.hpp"
 #include "stabilize_blend.hpp"
@@ -36,13 +37,6 @@ namespace rsdsfm {
 namespace {
 
 constexpr int kSeg = kBP * 4;  // pixels of a row one workgroup of the row pass owns
-
-// 1 in every byte of w that is not 0 / that is 0
-__device__ __forceinline__ unsigned bytes_set(unsigned w) { return ((w | ((w & 0x7f7f7f7fu) + 0x7f7f7f7fu)) >> 7) & 0x01010101u; }
-__device__ __forceinline__ unsigned bytes_zero(unsigned w) { return bytes_set(w) ^ 0x01010101u; }
-
-// byte k of an array of dwords (k a compile-time constant after unrolling)
-__device__ __forceinline__ unsigned byte_of(const unsigned* w, int k) { return (w[k >> 2] >> (8 * (k & 3))) & 0xffu; }
 
 __device__ __forceinline__ unsigned long long shfl_down64(unsigned long long v, int off) {
     const unsigned lo = __shfl_down((unsigned)v, off, 64), hi = __shfl_down((unsigned)(v >> 32), off, 64);
@@ -163,8 +157,7 @@ __device__ __forceinline__ void seam_blend_body(const unsigned char* __restrict_
                 for (int c = 0; c < CH; ++c) {
                     const int b = CH * j + c;
                     const unsigned own = byte_of(iw, b);
-                    unsigned k = (G[c] * byte_of(lw, b) + 32768u) >> 16;  // G <= 2^18, the byte < 2^8
-                    k = k > 255u ? 255u : k;
+                    const unsigned k = gained(G[c], byte_of(lw, b));
                     const unsigned v = f ? k : m ? (dj * own + (T - dj) * k + half) / T : own;  // dj < T where m: <= 255
                     ow[b >> 2] |= v << (8 * (b & 3));
                 }
@@ -186,8 +179,7 @@ __device__ __forceinline__ void seam_blend_body(const unsigned char* __restrict_
                 if (!f && !m) continue;
 #pragma unroll
                 for (int c = 0; c < CH; ++c) {
-                    unsigned k = (G[c] * layer[(int64_t)CH * p + c] + 32768u) >> 16;
-                    k = k > 255u ? 255u : k;
+                    const unsigned k = gained(G[c], layer[(int64_t)CH * p + c]);
                     const unsigned own = image[(int64_t)CH * p + c];
                     image[(int64_t)CH * p + c] = (unsigned char)(f ? k : (dj * own + (T - dj) * k + half) / T);
                 }

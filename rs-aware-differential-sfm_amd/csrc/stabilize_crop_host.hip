@@ -5,6 +5,7 @@
 #include <vector>
 
 #include "../../include/rsdsfm_stabilize_crop.h"
+#include "clip_stage_host.hpp"
 #include "rectify_dense.hpp"
 #include "rsdsfm_internal.hpp"
 #include "last_frame.hpp"
@@ -26,18 +27,6 @@ rsdsfm_stabilize_crop_params crop_defaults() {
 bool crop_params_ok(const rsdsfm_stabilize_crop_params& p, int rows, int cols) {
     if (p.struct_bytes != 0 && p.struct_bytes != (int32_t)sizeof(rsdsfm_stabilize_crop_params)) return false;
     return p.margin >= 0 && p.margin <= kCropMarginMax && p.max_empty >= 0 && p.max_empty <= (int64_t)rows * cols;
-}
-
-bool crop_size_ok(int rows, int cols) { return rows >= 2 && cols >= 2 && rows <= 16384 && cols <= 16384; }
-
-bool crop_window_ok(const int32_t* w, int rows, int cols) {
-    return w && w[2] >= 1 && w[3] >= 1 && w[0] >= 0 && w[1] >= 0 && (int64_t)w[0] + w[2] <= rows && (int64_t)w[1] + w[3] <= cols;
-}
-
-bool crop_finite_all(const double* a, int n) {
-    for (int i = 0; i < n; ++i)
-        if (!std::isfinite(a[i])) return false;
-    return true;
 }
 
 }  // namespace
@@ -73,7 +62,7 @@ int rsdsfm_stabilize_crop_params_init(rsdsfm_stabilize_crop_params* params) {
 }
 
 int rsdsfm_crop_window_launches(int32_t rows, int32_t cols) {
-    if (!crop_size_ok(rows, cols)) return RSDSFM_ERR_INVALID;
+    if (!frame_size_ok(rows, cols)) return RSDSFM_ERR_INVALID;
     return 3;
 }
 
@@ -84,7 +73,7 @@ int rsdsfm_crop_window_dev(rsdsfm_ctx* ctx, const uint8_t* const* d_masks, int32
     if (!ctx) return RSDSFM_ERR_INVALID;
     Ctx* c = &ctx->c;
     DeviceGuard device_guard_(c);
-    if (!crop_size_ok(rows, cols)) return fail(c, RSDSFM_ERR_INVALID, "crop window: rows and cols must be in [2, 16384]");
+    if (!frame_size_ok(rows, cols)) return fail(c, RSDSFM_ERR_INVALID, "crop window: rows and cols must be in [2, 16384]");
     if (!window_out || nmasks < 1 || nmasks > kCropPlanesMax || !all_set(d_masks, nmasks))
         return fail(c, RSDSFM_ERR_INVALID, "crop window: 1 .. 4096 mask planes and window_out are required");
     for (int k = 0; k < nmasks; ++k)
@@ -96,10 +85,8 @@ int rsdsfm_crop_window_dev(rsdsfm_ctx* ctx, const uint8_t* const* d_masks, int32
     DenseWs* ws = nullptr;
     int rc = rectify_dense_ws(c, rows, cols, &ws);
     if (rc != RSDSFM_OK) return rc;
-    if (!ws->d_crop && hipMalloc(&ws->d_crop, crop_ws_bytes(rows, cols)) != hipSuccess) {
-        ws->d_crop = nullptr;
-        return fail(c, RSDSFM_ERR_HIP, "crop window: no memory for the summed-area table");
-    }
+    rc = ensure_plane(c, &ws->d_crop, crop_ws_bytes(rows, cols), "crop window: no memory for the summed-area table");
+    if (rc != RSDSFM_OK) return rc;
     const CropWs cw = crop_ws_layout(ws->d_crop);
     unsigned long long key = 0;
     // the planes' pointers go behind whatever the stream still runs on the table; this call waits below, so `d_masks` is read in time
@@ -132,8 +119,8 @@ int rsdsfm_stabilize_window_frame_dev(rsdsfm_ctx* ctx, const uint8_t* d_image_n,
         return fail(c, RSDSFM_ERR_INVALID, "window frame: images, mask and source plane must be 4-byte aligned");
     if ((uintptr_t)d_filled_or_null & 7u) return fail(c, RSDSFM_ERR_INVALID, "window frame: the filled counter must be 8-byte aligned");
     if (source_id < 1 || source_id > 255) return fail(c, RSDSFM_ERR_INVALID, "window frame: source_id must be in [1, 255] (1 is the own frame, 0 nobody)");
-    if (!M9 || !m3 || !crop_finite_all(M9, 9) || !crop_finite_all(m3, 3)) return fail(c, RSDSFM_ERR_INVALID, "window frame: the pose (M, m) must be given and finite");
-    if (!crop_window_ok(window, rows, cols))
+    if (!M9 || !m3 || !finite_all(M9, 9) || !finite_all(m3, 3)) return fail(c, RSDSFM_ERR_INVALID, "window frame: the pose (M, m) must be given and finite");
+    if (!window_ok(window, rows, cols))
         return fail(c, RSDSFM_ERR_INVALID, "window frame: the window (r0, c0, h, w) needs h >= 1, w >= 1 and must lie inside the frame");
     DenseWs* ws = nullptr;
     rc = rectify_dense_ws(c, rows, cols, &ws);
@@ -163,7 +150,7 @@ int rsdsfm_stabilize_video_cropped_dev(rsdsfm_ctx* ctx, const uint8_t* const* d_
     DeviceGuard device_guard_(c);
     if (nframes < 2) return fail(c, RSDSFM_ERR_INVALID, "stabilise video: nframes must be >= 2");
     const int np = stabilize_rendered_frames(stabilize_params_or_null, nframes);  // rendered frames: the pairs' first frames, and the last frame when asked for
-    if (!crop_size_ok(rows, cols)) return fail(c, RSDSFM_ERR_INVALID, "crop: rows and cols must be in [2, 16384]");
+    if (!frame_size_ok(rows, cols)) return fail(c, RSDSFM_ERR_INVALID, "crop: rows and cols must be in [2, 16384]");
     if (fill_params_or_null && ((fill_params_or_null->struct_bytes != 0 && fill_params_or_null->struct_bytes != (int32_t)sizeof(rsdsfm_stabilize_fill_params)) ||
                                 fill_params_or_null->radius < 0 || fill_params_or_null->radius > kCropFillRadiusMax || !visible_words_ok(fill_params_or_null)))
         return fail(c, RSDSFM_ERR_INVALID,
@@ -176,7 +163,7 @@ int rsdsfm_stabilize_video_cropped_dev(rsdsfm_ctx* ctx, const uint8_t* const* d_
     if (!crop_params_ok(cp, rows, cols))
         return fail(c, RSDSFM_ERR_INVALID,
                     "rsdsfm_stabilize_crop_params: margin in [0, 64], max_empty in [0, rows cols], struct_bytes 0 or sizeof (use rsdsfm_stabilize_crop_params_init)");
-    if (window_in_or_null && !crop_window_ok(window_in_or_null, rows, cols))
+    if (window_in_or_null && !window_ok(window_in_or_null, rows, cols))
         return fail(c, RSDSFM_ERR_INVALID, "crop: window_in (r0, c0, h, w) needs h >= 1, w >= 1 and must lie inside the frame");
     if (!window_out || !all_set(d_crop_images, np) || !all_set(d_crop_masks, np) || (d_crop_sources_or_null && !all_set(d_crop_sources_or_null, np)))
         return fail(c, RSDSFM_ERR_INVALID, "crop: window_out, d_crop_images and d_crop_masks are required");
@@ -221,15 +208,9 @@ int rsdsfm_stabilize_video_cropped_dev(rsdsfm_ctx* ctx, const uint8_t* const* d_
     const size_t plane = (size_t)rows * (size_t)cols;
     const int slots = 1 + 2 * radius;  // a counter per frame and source id, at id - 1; a skipped offset keeps its 0
     const bool have = window_out[2] >= 1;
-    int64_t* d_cnt = nullptr;
-    if (crop_counts_or_null && have) {
-        RSDSFM_HIP_CHECK(c, hipMalloc(reinterpret_cast<void**>(&d_cnt), sizeof(int64_t) * (size_t)np * slots * cw));
-        const hipError_t e = hipMemsetAsync(d_cnt, 0, sizeof(int64_t) * (size_t)np * slots * cw, c->stream);
-        if (e != hipSuccess) {
-            (void)hipFree(d_cnt);
-            RSDSFM_HIP_CHECK(c, e);
-        }
-    }
+    DeviceCounts counts;
+    rc = counts.alloc(c, crop_counts_or_null && have, (size_t)np * slots * cw, true);
+    if (rc != RSDSFM_OK) return rc;
     int32_t frames[2 * kCropFillRadiusMax], ids[2 * kCropFillRadiusMax], listed = 0;
     double nM[9 * 2 * kCropFillRadiusMax], nm[3 * 2 * kCropFillRadiusMax];
     for (int p = 0; p < np && rc == RSDSFM_OK; ++p) {
@@ -240,22 +221,16 @@ int rsdsfm_stabilize_video_cropped_dev(rsdsfm_ctx* ctx, const uint8_t* const* d_
         if (!have || rc != RSDSFM_OK) continue;
         const double* map = d_fused_maps_or_null ? d_fused_maps_or_null[p] : d_depth_maps[p];
         rc = rsdsfm_stabilize_window_frame_dev(ctx, d_frames[p], channels, map, d_R[p], d_t[p], fx, fy, cx, cy, rows, cols, mode, q5_mode, iterations, M + 9 * (size_t)p,
-                                               m + 3 * (size_t)p, 1, window_out, d_crop_images[p], d_crop_masks[p], src, d_cnt ? d_cnt + (size_t)p * slots * cw : nullptr);
+                                               m + 3 * (size_t)p, 1, window_out, d_crop_images[p], d_crop_masks[p], src, counts.at((size_t)p * slots * cw));
         listed = 0;
         if (rc == RSDSFM_OK && radius > 0 && rsdsfm_neighbour_poses(A, c_, A_s, c_s, scales, np, p, radius, frames, ids, nM, nm, &listed) != RSDSFM_OK)
             rc = fail(c, RSDSFM_ERR_INVALID, "crop: a neighbour's scale is not finite and positive");
         for (int k = 0; k < listed && rc == RSDSFM_OK; ++k) {
             const int n = frames[k];
             const double* nmap = d_fused_maps_or_null ? d_fused_maps_or_null[n] : d_depth_maps[n];
-            int64_t* cnt = d_cnt ? d_cnt + ((size_t)p * slots + (ids[k] - 1)) * cw : nullptr;
-            rc = srch ? rsdsfm_stabilize_search_frame_dev(ctx, d_frames[n], channels, nmap, d_R[n], d_t[n], fx, fy, cx, cy, rows, cols, mode, q5_mode, iterations,
-                                                          nM + 9 * (size_t)k, nm + 3 * (size_t)k, ids[k], window_out, d_crop_images[p], d_crop_masks[p], src,
-                                                          fill_params_or_null->occlusion_tol_q16, cnt)
-                 : occ ? rsdsfm_stabilize_visible_frame_dev(ctx, d_frames[n], channels, nmap, d_R[n], d_t[n], fx, fy, cx, cy, rows, cols, mode, q5_mode, iterations,
-                                                          nM + 9 * (size_t)k, nm + 3 * (size_t)k, ids[k], window_out, d_crop_images[p], d_crop_masks[p], src,
-                                                          fill_params_or_null->occlusion_tol_q16, cnt)
-                     : rsdsfm_stabilize_window_frame_dev(ctx, d_frames[n], channels, nmap, d_R[n], d_t[n], fx, fy, cx, cy, rows, cols, mode, q5_mode, iterations,
-                                                         nM + 9 * (size_t)k, nm + 3 * (size_t)k, ids[k], window_out, d_crop_images[p], d_crop_masks[p], src, cnt);
+            rc = render_candidate(ctx, occ, occ ? fill_params_or_null->occlusion_tol_q16 : 0, d_frames[n], channels, nmap, d_R[n], d_t[n], fx, fy, cx, cy, rows, cols, mode,
+                                  q5_mode, iterations, nM + 9 * (size_t)k, nm + 3 * (size_t)k, ids[k], window_out, d_crop_images[p], d_crop_masks[p], src,
+                                  counts.at(((size_t)p * slots + (ids[k] - 1)) * cw));
         }
     }
     if (crop_counts_or_null && !have && rc == RSDSFM_OK) {
@@ -266,12 +241,9 @@ int rsdsfm_stabilize_video_cropped_dev(rsdsfm_ctx* ctx, const uint8_t* const* d_
         }
         RSDSFM_HIP_CHECK(c, hipStreamSynchronize(c->stream));
     }
-    if (d_cnt) {
-        std::vector<int64_t> taken((size_t)np * slots * cw);
-        hipError_t e = rc == RSDSFM_OK ? hipMemcpyAsync(taken.data(), d_cnt, sizeof(int64_t) * taken.size(), hipMemcpyDeviceToHost, c->stream) : hipSuccess;
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        (void)hipFree(d_cnt);
-        if (rc == RSDSFM_OK) RSDSFM_HIP_CHECK(c, e);
+    if (counts) {
+        std::vector<int64_t> taken(counts.size());
+        rc = counts.fetch(c, taken.data(), rc);
         if (rc == RSDSFM_OK)
             for (int p = 0; p < np; ++p) {
                 int64_t* row = crop_counts_or_null + (size_t)p * (1 + slots);

@@ -17,6 +17,7 @@
 //                         window's scalars and the two scale factors are uniform kernel arguments.  Stages A and B are the existing launches.
 #include <algorithm>
 
+#include "image_tile_device.hpp"  // bytes_set
 #include "rectify_dense.hpp"
 #include "rectify_dense_device.hpp"
 #include "rsdsfm_internal.hpp"
@@ -28,9 +29,6 @@ namespace rsdsfm {
 namespace {
 
 constexpr int kSegs = 8;  // row segments of the column scan: kCB = 64 columns x 8
-
-// 1 in every byte of w that is not 0
-__device__ __forceinline__ unsigned bytes_set(unsigned w) { return ((w | ((w & 0x7f7f7f7fu) + 0x7f7f7f7fu)) >> 7) & 0x01010101u; }
 
 // warp_pixel_at, CropMap and window_target: stabilize_window_device.hpp (shared with the occlusion test's warp kernels)
 template <int CH>

@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "../../include/rsdsfm_stabilize_fill.h"
+#include "clip_stage_host.hpp"
 #include "rectify_dense.hpp"
 #include "rsdsfm_internal.hpp"
 #include "last_frame.hpp"
@@ -24,12 +25,6 @@ rsdsfm_stabilize_fill_params fill_defaults() { return rsdsfm_stabilize_fill_para
 bool fill_params_ok(const rsdsfm_stabilize_fill_params& p) {
     if (p.struct_bytes != 0 && p.struct_bytes != (int32_t)sizeof(rsdsfm_stabilize_fill_params)) return false;
     return p.radius >= 0 && p.radius <= kFillRadiusMax && visible_words_ok(&p);
-}
-
-bool fill_finite_all(const double* a, int n) {
-    for (int i = 0; i < n; ++i)
-        if (!std::isfinite(a[i])) return false;
-    return true;
 }
 
 }  // namespace
@@ -71,7 +66,7 @@ int rsdsfm_neighbour_poses(const double* A, const double* c, const double* A_s, 
 }
 
 int rsdsfm_stabilize_fill_launches(int32_t rows, int32_t cols) {
-    if (rows < 2 || cols < 2 || rows > 16384 || cols > 16384) return RSDSFM_ERR_INVALID;
+    if (!frame_size_ok(rows, cols)) return RSDSFM_ERR_INVALID;
     return rectify_dense_launch_count(rows, cols);
 }
 
@@ -91,7 +86,7 @@ int rsdsfm_stabilize_fill_frame_dev(rsdsfm_ctx* ctx, const uint8_t* d_image_n, i
         return fail(c, RSDSFM_ERR_INVALID, "border fill: images, mask and source plane must be 4-byte aligned");
     if ((uintptr_t)d_filled_or_null & 7u) return fail(c, RSDSFM_ERR_INVALID, "border fill: the filled counter must be 8-byte aligned");
     if (source_id < 2 || source_id > 255) return fail(c, RSDSFM_ERR_INVALID, "border fill: source_id must be in [2, 255] (1 is the own frame, 0 nobody)");
-    if (!M9 || !m3 || !fill_finite_all(M9, 9) || !fill_finite_all(m3, 3)) return fail(c, RSDSFM_ERR_INVALID, "border fill: the pose (M, m) must be given and finite");
+    if (!M9 || !m3 || !finite_all(M9, 9) || !finite_all(m3, 3)) return fail(c, RSDSFM_ERR_INVALID, "border fill: the pose (M, m) must be given and finite");
     DenseWs* ws = nullptr;
     rc = rectify_dense_ws(c, rows, cols, &ws);
     if (rc != RSDSFM_OK) return rc;
@@ -147,15 +142,9 @@ int rsdsfm_stabilize_video_filled_dev(rsdsfm_ctx* ctx, const uint8_t* const* d_f
     if (rc != RSDSFM_OK) return rc;
     const size_t plane = (size_t)rows * (size_t)cols;
     const int slots = 2 * radius;
-    int64_t* d_cnt = nullptr;  // a counter per frame and offset, at source id - 2; a skipped offset keeps its 0
-    if (counts_or_null) {
-        RSDSFM_HIP_CHECK(c, hipMalloc(reinterpret_cast<void**>(&d_cnt), sizeof(int64_t) * (size_t)np * slots * cw));
-        const hipError_t e = hipMemsetAsync(d_cnt, 0, sizeof(int64_t) * (size_t)np * slots * cw, c->stream);
-        if (e != hipSuccess) {
-            (void)hipFree(d_cnt);
-            RSDSFM_HIP_CHECK(c, e);
-        }
-    }
+    DeviceCounts counts;  // a counter per frame and offset, at source id - 2; a skipped offset keeps its 0
+    rc = counts.alloc(c, counts_or_null != nullptr, (size_t)np * slots * cw, true);
+    if (rc != RSDSFM_OK) return rc;
     int32_t frames[2 * kFillRadiusMax], ids[2 * kFillRadiusMax], listed = 0;
     double nM[9 * 2 * kFillRadiusMax], nm[3 * 2 * kFillRadiusMax];
     for (int p = 0; p < np && rc == RSDSFM_OK; ++p) {
@@ -167,7 +156,7 @@ int rsdsfm_stabilize_video_filled_dev(rsdsfm_ctx* ctx, const uint8_t* const* d_f
             const int n = frames[k];
             const double* map = d_fused_maps_or_null ? d_fused_maps_or_null[n] : d_depth_maps[n];
             uint8_t* src = d_sources_or_null ? d_sources_or_null[p] : nullptr;
-            int64_t* cnt = d_cnt ? d_cnt + ((size_t)p * slots + (ids[k] - 2)) * cw : nullptr;
+            int64_t* cnt = counts.at(((size_t)p * slots + (ids[k] - 2)) * cw);
             rc = srch ? rsdsfm_stabilize_search_frame_dev(ctx, d_frames[n], channels, map, d_R[n], d_t[n], fx, fy, cx, cy, rows, cols, mode, q5_mode, iterations,
                                                           nM + 9 * (size_t)k, nm + 3 * (size_t)k, ids[k], full, d_stab_images[p], d_masks_out[p], src,
                                                           fp.occlusion_tol_q16, cnt)
@@ -178,12 +167,9 @@ int rsdsfm_stabilize_video_filled_dev(rsdsfm_ctx* ctx, const uint8_t* const* d_f
                                                        nM + 9 * (size_t)k, nm + 3 * (size_t)k, ids[k], d_stab_images[p], d_masks_out[p], src, cnt);
         }
     }
-    if (d_cnt) {
-        std::vector<int64_t> filled((size_t)np * slots * cw);
-        hipError_t e = rc == RSDSFM_OK ? hipMemcpyAsync(filled.data(), d_cnt, sizeof(int64_t) * filled.size(), hipMemcpyDeviceToHost, c->stream) : hipSuccess;
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        (void)hipFree(d_cnt);
-        if (rc == RSDSFM_OK) RSDSFM_HIP_CHECK(c, e);
+    if (counts) {
+        std::vector<int64_t> filled(counts.size());
+        rc = counts.fetch(c, filled.data(), rc);
         if (rc == RSDSFM_OK)
             for (int p = 0; p < np; ++p) {
                 int64_t* row = counts_or_null + (size_t)p * (2 + slots);

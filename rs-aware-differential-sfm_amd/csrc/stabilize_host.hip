@@ -5,6 +5,7 @@
 #include <vector>
 
 #include "../../include/rsdsfm_stabilize.h"
+#include "clip_stage_host.hpp"
 #include "last_frame.hpp"
 #include "link.hpp"
 #include "rectify_dense.hpp"
@@ -22,13 +23,7 @@ bool stabilize_params_ok(const rsdsfm_stabilize_params& p) {
     return std::isfinite(p.sigma) && p.sigma > 0.0 && p.radius >= 0 && p.radius <= 1024 && (p.last_frame == 0 || p.last_frame == 1);
 }
 
-// mat3 and so3_log: stabilize.hpp (the retimer interpolates the path with them)
-
-bool finite_all(const double* a, int n) {
-    for (int i = 0; i < n; ++i)
-        if (!std::isfinite(a[i])) return false;
-    return true;
-}
+// mat3 and so3_log: stabilize.hpp (the retimer interpolates the path with them); finite_all: clip_stage_host.hpp
 
 }  // namespace
 }  // namespace rsdsfm

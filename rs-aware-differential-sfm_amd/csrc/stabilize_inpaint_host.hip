@@ -2,6 +2,7 @@
 // is the definition, stabilize_inpaint_kernels.hip the kernels): the frame call, which only enqueues, its launch count, and the clip call,
 // which CALLS the public entry points one after another.
 #include "../../include/rsdsfm_stabilize_inpaint.h"
+#include "clip_stage_host.hpp"
 #include "rectify_dense.hpp"
 #include "rsdsfm_internal.hpp"
 #include "last_frame.hpp"
@@ -13,8 +14,6 @@ namespace {
 
 static_assert(RSDSFM_SOURCE_INPAINTED == kSourceInpainted, "the header's id is the kernels'");
 
-bool inpaint_size_ok(int rows, int cols) { return rows >= 2 && cols >= 2 && rows <= 16384 && cols <= 16384; }
-
 }  // namespace
 }  // namespace rsdsfm
 
@@ -22,14 +21,14 @@ using namespace rsdsfm;
 
 extern "C" {
 
-int rsdsfm_inpaint_launches(int32_t rows, int32_t cols) { return inpaint_size_ok(rows, cols) ? inpaint_launch_count(rows, cols) : RSDSFM_ERR_INVALID; }
+int rsdsfm_inpaint_launches(int32_t rows, int32_t cols) { return frame_size_ok(rows, cols) ? inpaint_launch_count(rows, cols) : RSDSFM_ERR_INVALID; }
 
 int rsdsfm_inpaint_frame_dev(rsdsfm_ctx* ctx, uint8_t* d_image_inout, const uint8_t* d_mask, int32_t channels, int32_t rows, int32_t cols,
                              uint8_t* d_source_or_null, int64_t* d_count_or_null) {
     if (!ctx) return RSDSFM_ERR_INVALID;
     Ctx* c = &ctx->c;
     DeviceGuard device_guard_(c);
-    if (!inpaint_size_ok(rows, cols)) return fail(c, RSDSFM_ERR_INVALID, "inpaint: rows and cols must be in [2, 16384]");
+    if (!frame_size_ok(rows, cols)) return fail(c, RSDSFM_ERR_INVALID, "inpaint: rows and cols must be in [2, 16384]");
     if (channels != 1 && channels != 3) return fail(c, RSDSFM_ERR_INVALID, "inpaint: channels must be 1 or 3");
     if (!d_image_inout || !d_mask) return fail(c, RSDSFM_ERR_INVALID, "inpaint: null device pointer (the image and the mask are required)");
     if (d_image_inout == d_mask || (d_source_or_null && (d_source_or_null == d_mask || d_source_or_null == d_image_inout)))
@@ -38,12 +37,10 @@ int rsdsfm_inpaint_frame_dev(rsdsfm_ctx* ctx, uint8_t* d_image_inout, const uint
         return fail(c, RSDSFM_ERR_INVALID, "inpaint: every plane must be 4-byte aligned");
     if ((uintptr_t)d_count_or_null & 7u) return fail(c, RSDSFM_ERR_INVALID, "inpaint: the counter must be 8-byte aligned");
     DenseWs* ws = nullptr;
-    const int rc = rectify_dense_ws(c, rows, cols, &ws);
+    int rc = rectify_dense_ws(c, rows, cols, &ws);
     if (rc != RSDSFM_OK) return rc;
-    if (!ws->d_inpaint && hipMalloc(&ws->d_inpaint, inpaint_ws_bytes(rows, cols)) != hipSuccess) {
-        ws->d_inpaint = nullptr;
-        return fail(c, RSDSFM_ERR_HIP, "inpaint: no memory for the pyramid");
-    }
+    rc = ensure_plane(c, &ws->d_inpaint, inpaint_ws_bytes(rows, cols), "inpaint: no memory for the pyramid");
+    if (rc != RSDSFM_OK) return rc;
     return inpaint_launch(c, ws->d_inpaint, d_image_inout, d_mask, channels, rows, cols, d_source_or_null, d_count_or_null);
 }
 
@@ -88,8 +85,8 @@ int rsdsfm_stabilize_video_inpainted_dev(rsdsfm_ctx* ctx, const uint8_t* const* 
                                                 blend_params_or_null, d_blend_images, d_blend_masks, d_blend_sources, gains_or_null, blend_counts_or_null);
     if (rc != RSDSFM_OK) return rc;
     const size_t plane = (size_t)rows * (size_t)cols;
-    int64_t* d_cnt = nullptr;  // with the host array: one counter per frame (every frame call zeroes its own)
-    if (inpaint_counts_or_null) RSDSFM_HIP_CHECK(c, hipMalloc(reinterpret_cast<void**>(&d_cnt), sizeof(int64_t) * (size_t)np));
+    DeviceCounts counts;  // with the host array: one counter per frame (every frame call zeroes its own)
+    rc = counts.alloc(c, inpaint_counts_or_null != nullptr, (size_t)np);
     // without a window the blend planes are zero: the copies are, the mask has no set pixel and the frame call writes nothing
     for (int p = 0; p < np && rc == RSDSFM_OK; ++p) {
         if (hipMemcpyAsync(d_inpaint_images[p], d_blend_images[p], plane * (size_t)channels, hipMemcpyDeviceToDevice, c->stream) != hipSuccess ||
@@ -99,15 +96,9 @@ int rsdsfm_stabilize_video_inpainted_dev(rsdsfm_ctx* ctx, const uint8_t* const* 
             break;
         }
         rc = rsdsfm_inpaint_frame_dev(ctx, d_inpaint_images[p], d_blend_masks[p], channels, rows, cols, d_inpaint_sources_or_null ? d_inpaint_sources_or_null[p] : nullptr,
-                                      d_cnt ? d_cnt + p : nullptr);
+                                      counts.at((size_t)p));
     }
-    if (d_cnt) {
-        hipError_t e = rc == RSDSFM_OK ? hipMemcpyAsync(inpaint_counts_or_null, d_cnt, sizeof(int64_t) * (size_t)np, hipMemcpyDeviceToHost, c->stream) : hipSuccess;
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        (void)hipFree(d_cnt);
-        if (rc == RSDSFM_OK) RSDSFM_HIP_CHECK(c, e);
-    }
-    return rc;
+    return counts.fetch(c, inpaint_counts_or_null, rc);
 }
 
 }  // extern "C"

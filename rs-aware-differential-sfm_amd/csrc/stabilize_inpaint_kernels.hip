@@ -28,6 +28,7 @@
 //                              when a counter was passed.
 #include <algorithm>
 
+#include "image_tile_device.hpp"  // bytes_set, bytes_zero, byte_of
 #include "rectify_dense.hpp"
 #include "rectify_dense_device.hpp"  // kBP, kSB, kSmallCells
 #include "rsdsfm_internal.hpp"
@@ -36,13 +37,6 @@
 namespace rsdsfm {
 
 namespace {
-
-// 1 in every byte of w that is not 0 / that is 0
-__device__ __forceinline__ unsigned bytes_set(unsigned w) { return ((w | ((w & 0x7f7f7f7fu) + 0x7f7f7f7fu)) >> 7) & 0x01010101u; }
-__device__ __forceinline__ unsigned bytes_zero(unsigned w) { return bytes_set(w) ^ 0x01010101u; }
-
-// byte k of an array of dwords (k a compile-time constant after unrolling)
-__device__ __forceinline__ unsigned byte_of(const unsigned* w, int k) { return (w[k >> 2] >> (8 * (k & 3))) & 0xffu; }
 
 // the sums of a cell's children: s[c] <= 4 x 65280, n = the valid ones
 struct CellSum {

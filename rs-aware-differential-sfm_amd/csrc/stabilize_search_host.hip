@@ -4,6 +4,7 @@
 // (stabilize_fill_host.hip, stabilize_crop_host.hip, stabilize_blend_host.hip).
 #include <cmath>
 
+#include "clip_stage_host.hpp"
 #include "rectify_dense.hpp"
 #include "rsdsfm_internal.hpp"
 #include "stabilize_search.hpp"
@@ -39,19 +40,14 @@ int rsdsfm_stabilize_search_frame_dev(rsdsfm_ctx* ctx, const uint8_t* d_image_n,
     if ((uintptr_t)d_counts3_or_null & 7u) return fail(c, RSDSFM_ERR_INVALID, "search frame: the [taken, rejected, recovered] counters must be 8-byte aligned");
     if (source_id < 1 || source_id > 255) return fail(c, RSDSFM_ERR_INVALID, "search frame: source_id must be in [1, 255] (1 is the own frame, 0 nobody)");
     if (tol_q16 < 0 || tol_q16 > kVisibleTolQ16Max) return fail(c, RSDSFM_ERR_INVALID, "search frame: tol_q16 must be in [1, 65536], or 0 for the default");
-    bool finite = M9 && m3;
-    for (int i = 0; finite && i < 9; ++i) finite = std::isfinite(M9[i]);
-    for (int i = 0; finite && i < 3; ++i) finite = std::isfinite(m3[i]);
-    if (!finite) return fail(c, RSDSFM_ERR_INVALID, "search frame: the pose (M, m) must be given and finite");
-    if (!window || window[2] < 1 || window[3] < 1 || window[0] < 0 || window[1] < 0 || (int64_t)window[0] + window[2] > rows || (int64_t)window[1] + window[3] > cols)
+    if (!M9 || !m3 || !finite_all(M9, 9) || !finite_all(m3, 3)) return fail(c, RSDSFM_ERR_INVALID, "search frame: the pose (M, m) must be given and finite");
+    if (!window_ok(window, rows, cols))
         return fail(c, RSDSFM_ERR_INVALID, "search frame: the window (r0, c0, h, w) needs h >= 1, w >= 1 and must lie inside the frame");
     DenseWs* ws = nullptr;
     rc = rectify_dense_ws(c, rows, cols, &ws);  // a size change releases the two planes with the rest
     if (rc != RSDSFM_OK) return rc;
-    if (!ws->d_search && hipMalloc(&ws->d_search, search_ws_bytes(rows, cols)) != hipSuccess) {
-        ws->d_search = nullptr;
-        return fail(c, RSDSFM_ERR_HIP, "search frame: no memory for the key plane and the depth plane");
-    }
+    rc = ensure_plane(c, &ws->d_search, search_ws_bytes(rows, cols), "search frame: no memory for the key plane and the depth plane");
+    if (rc != RSDSFM_OK) return rc;
     StabPose vp;
     for (int i = 0; i < 9; ++i) vp.M[i] = M9[i];
     for (int i = 0; i < 3; ++i) vp.m[i] = m3[i];

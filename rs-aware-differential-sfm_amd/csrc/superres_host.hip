@@ -2,9 +2,7 @@
 // superres_kernels.hip the kernels): the render call, the accumulate call, the frame call, which CALLS the public render, record and
 // accumulate entry points one after another on planes of the context's dense workspace, and the clip call, which calls the frame call per
 // frame, walking the clip as rsdsfm_denoise_video_dev does.
-#include <cmath>
-#include <vector>
-
+#include "clip_stage_host.hpp"
 #include "rectify_dense.hpp"
 #include "rsdsfm_internal.hpp"
 #include "sequence_host.hpp"
@@ -37,24 +35,12 @@ const char* const kSuperresParamsMessage =
     "rsdsfm_superres_params: scale in [1, 4] or 0, radius in [1, 7] or 0, strength in [1, 255] or 0, gain_mode 0 or 1, min_overlap >= 0, reserved 0, struct_bytes 0 or "
     "sizeof (use rsdsfm_superres_params_init)";
 
-bool superres_size_ok(int rows, int cols) { return rows >= 2 && cols >= 2 && rows <= kSuperresSizeMax && cols <= kSuperresSizeMax; }
-
 // the source size and the scale: the fine size may not pass 16384 either
 bool superres_scale_ok(int rows, int cols, int scale) {
-    return superres_size_ok(rows, cols) && scale >= 1 && scale <= kSuperresScaleMax && (int64_t)scale * rows <= kSuperresSizeMax && (int64_t)scale * cols <= kSuperresSizeMax;
+    return frame_size_ok(rows, cols, kSuperresSizeMax) && scale >= 1 && scale <= kSuperresScaleMax && (int64_t)scale * rows <= kSuperresSizeMax && (int64_t)scale * cols <= kSuperresSizeMax;
 }
 
 const char* const kSuperresScaleMessage = "superres: scale must be in [1, 4] and scale * rows, scale * cols at most 16384";
-
-bool superres_finite_all(const double* a, int n) {
-    for (int i = 0; i < n; ++i)
-        if (!std::isfinite(a[i])) return false;
-    return true;
-}
-
-bool superres_window_ok(const int32_t* w, int rows, int cols) {
-    return w[2] >= 1 && w[3] >= 1 && w[0] >= 0 && w[1] >= 0 && (int64_t)w[0] + w[2] <= rows && (int64_t)w[1] + w[3] <= cols;
-}
 
 // the argument checks of the final outputs, for the accumulate call and, before anything is enqueued, for the frame call
 int superres_outputs_check(Ctx* c, const uint8_t* d_image_out, const uint8_t* d_mask_out, const uint8_t* d_weight, const int64_t* d_counts3) {
@@ -68,7 +54,7 @@ int superres_outputs_check(Ctx* c, const uint8_t* d_image_out, const uint8_t* d_
 
 // the workspace's fine planes, cells and record: made when first asked for and again when the scale changes (a size change releases them with the rest)
 int superres_ws(Ctx* c, int rows, int cols, int scale, DenseWs** ws) {
-    const int rc = rectify_dense_ws(c, rows, cols, ws);
+    int rc = rectify_dense_ws(c, rows, cols, ws);
     if (rc != RSDSFM_OK) return rc;
     DenseWs* w = *ws;
     if (w->d_superres && w->superres_scale != scale) {
@@ -78,34 +64,14 @@ int superres_ws(Ctx* c, int rows, int cols, int scale, DenseWs** ws) {
         w->superres_scale = 0;
     }
     if (!w->d_superres) {
-        if (hipMalloc(reinterpret_cast<void**>(&w->d_superres), superres_ws_bytes(scale * rows, scale * cols)) != hipSuccess) {
-            w->d_superres = nullptr;
-            return fail(c, RSDSFM_ERR_HIP, "superres: no memory for the fine planes and the cells");
-        }
+        rc = ensure_plane(c, &w->d_superres, superres_ws_bytes(scale * rows, scale * cols), "superres: no memory for the fine planes and the cells");
+        if (rc != RSDSFM_OK) return rc;
         w->superres_scale = scale;
     }
     return RSDSFM_OK;
 }
 
-// one frame's host part for the clip call: the sources (the own frame first) and their poses, as the denoise's clip call plans them
-struct SuperresPlan {
-    int nsrc = 0;
-    int32_t src[kSuperresSourcesMax];
-    double M[9 * kSuperresSourcesMax], m[3 * kSuperresSourcesMax];
-};
-
-bool superres_plan(const double* A, const double* c_, const double* A_path, const double* c_path, const double* scales, int nsources, int q, int radius, SuperresPlan* plan) {
-    int32_t src2[2], nsrc = 0, wq = 0, ids[kSuperresLayersMax], count = 0;
-    double M18[18], m6[6], At[9], ct[3];
-    if (rsdsfm_retime_poses(A, c_, A_path, c_path, scales, nsources, (double)q, src2, &nsrc, &wq, M18, m6, At, ct) != RSDSFM_OK || nsrc != 1) return false;
-    plan->src[0] = q;
-    for (int k = 0; k < 9; ++k) plan->M[k] = M18[k];
-    for (int k = 0; k < 3; ++k) plan->m[k] = m6[k];
-    if (nsources > 1 && rsdsfm_neighbour_poses(A, c_, A_path, c_path, scales, nsources, q, radius, plan->src + 1, ids, plan->M + 9, plan->m + 3, &count) != RSDSFM_OK)
-        return false;
-    plan->nsrc = 1 + count;
-    return superres_finite_all(plan->M, 9 * plan->nsrc) && superres_finite_all(plan->m, 3 * plan->nsrc);
-}
+static_assert(kSuperresSourcesMax == kClipSourcesMax, "a frame's sources are a ClipPlan's");
 
 }  // namespace
 }  // namespace rsdsfm
@@ -152,12 +118,11 @@ int rsdsfm_superres_render_dev(rsdsfm_ctx* ctx, const uint8_t* d_image_n, int32_
             if (io[j] && io[i] == io[j]) return fail(c, RSDSFM_ERR_INVALID, "superres render: the image and the output planes must be distinct");
     if (((uintptr_t)d_image_n | (uintptr_t)d_bil_out | (uintptr_t)d_near_out | (uintptr_t)d_prox_out | (uintptr_t)d_valid_or_null) & 3u)
         return fail(c, RSDSFM_ERR_INVALID, "superres render: the image and every output plane must be 4-byte aligned");
-    if (!M9 || !m3 || !superres_finite_all(M9, 9) || !superres_finite_all(m3, 3))
+    if (!M9 || !m3 || !finite_all(M9, 9) || !finite_all(m3, 3))
         return fail(c, RSDSFM_ERR_INVALID, "superres render: the pose (M, m) must be given and finite");
-    const int32_t full[4] = {0, 0, rows, cols};
-    const int32_t* window = window_or_null ? window_or_null : full;
-    if (!superres_window_ok(window, rows, cols))
-        return fail(c, RSDSFM_ERR_INVALID, "superres render: the window (r0, c0, h, w) needs h >= 1, w >= 1 and must lie inside the frame");
+    int32_t full[4];
+    const int32_t* window = window_or_full(window_or_null, rows, cols, full);
+    if (!window) return fail(c, RSDSFM_ERR_INVALID, "superres render: the window (r0, c0, h, w) needs h >= 1, w >= 1 and must lie inside the frame");
     DenseWs* ws = nullptr;
     rc = rectify_dense_ws(c, rows, cols, &ws);
     if (rc != RSDSFM_OK) return rc;
@@ -177,7 +142,7 @@ int rsdsfm_superres_accumulate_dev(rsdsfm_ctx* ctx, const uint8_t* d_ref_bil, co
     Ctx* c = &ctx->c;
     DeviceGuard device_guard_(c);
     if ((first != 0 && first != 1) || (last != 0 && last != 1)) return fail(c, RSDSFM_ERR_INVALID, "superres accumulate: first and last must be 0 or 1");
-    if (!superres_size_ok(rows, cols)) return fail(c, RSDSFM_ERR_INVALID, "superres: rows and cols must be in [2, 16384]");
+    if (!frame_size_ok(rows, cols, kSuperresSizeMax)) return fail(c, RSDSFM_ERR_INVALID, "superres: rows and cols must be in [2, 16384]");
     if (channels != 1 && channels != 3) return fail(c, RSDSFM_ERR_INVALID, "superres: channels must be 1 or 3");
     if (min_overlap < 0 || (gain_mode != 0 && gain_mode != 1) || strength < 0 || strength > kSuperresStrengthMax)
         return fail(c, RSDSFM_ERR_INVALID, "superres accumulate: min_overlap must be >= 0, gain_mode 0 or 1 and strength in [1, 255] (0: the default, 12)");
@@ -232,14 +197,13 @@ int rsdsfm_superres_frame_dev(rsdsfm_ctx* ctx, const uint8_t* const* d_images, i
         if (!d_images[k] || !d_depths_colmajor[k] || !d_R_rows9[k] || !d_t_rows3[k] || d_images[k] == d_image_out || d_images[k] == d_mask_out ||
             (d_weight_or_null && d_images[k] == d_weight_or_null) || ((uintptr_t)d_images[k] & 3u))
             return fail(c, RSDSFM_ERR_INVALID, "superres frame: null, misaligned or aliased source pointer");
-    if (!M || !m || !superres_finite_all(M, 9 * nsrc) || !superres_finite_all(m, 3 * nsrc))
+    if (!M || !m || !finite_all(M, 9 * nsrc) || !finite_all(m, 3 * nsrc))
         return fail(c, RSDSFM_ERR_INVALID, "superres frame: the poses (M, m) must be given and finite");
     rc = superres_outputs_check(c, d_image_out, d_mask_out, d_weight_or_null, d_counts3_or_null);
     if (rc != RSDSFM_OK) return rc;
-    const int32_t full[4] = {0, 0, rows, cols};
-    const int32_t* window = window_or_null ? window_or_null : full;
-    if (!superres_window_ok(window, rows, cols))
-        return fail(c, RSDSFM_ERR_INVALID, "superres frame: the window (r0, c0, h, w) needs h >= 1, w >= 1 and must lie inside the frame");
+    int32_t full[4];
+    const int32_t* window = window_or_full(window_or_null, rows, cols, full);
+    if (!window) return fail(c, RSDSFM_ERR_INVALID, "superres frame: the window (r0, c0, h, w) needs h >= 1, w >= 1 and must lie inside the frame");
     DenseWs* ws = nullptr;
     rc = superres_ws(c, rows, cols, sp.scale, &ws);
     if (rc != RSDSFM_OK) return rc;
@@ -277,47 +241,20 @@ int rsdsfm_superres_video_dev(rsdsfm_ctx* ctx, const uint8_t* const* d_frames, i
     if (!ctx) return RSDSFM_ERR_INVALID;
     Ctx* c = &ctx->c;
     DeviceGuard device_guard_(c);
-    if (nsources < 1) return fail(c, RSDSFM_ERR_INVALID, "superres video: nsources must be >= 1");
-    if (!d_frames || !d_depth_maps || !d_R || !d_t || !A || !c_ || !A_path || !c_path || !scales) return fail(c, RSDSFM_ERR_INVALID, "superres video: null array");
-    if (!all_set(d_frames, nsources) || !all_set(d_depth_maps, nsources) || !all_set(d_R, nsources) || !all_set(d_t, nsources))
-        return fail(c, RSDSFM_ERR_INVALID, "superres video: every source needs its frame, depth map and pose table");
-    if (!d_out_images || !d_out_masks || !all_set(d_out_images, nsources) || !all_set(d_out_masks, nsources) ||
-        (d_out_weights_or_null && !all_set(d_out_weights_or_null, nsources)))
-        return fail(c, RSDSFM_ERR_INVALID, "superres video: every frame needs its image and its mask (and its weight plane when the array is passed)");
+    ClipOutputs outs;
+    outs.planes[0] = d_out_images;
+    outs.planes[1] = d_out_masks;
+    outs.planes[2] = d_out_weights_or_null;
+    const int rc = clip_arrays_check(c, "superres video", d_frames, nsources, d_depth_maps, d_R, d_t, A, c_, A_path, c_path, scales, outs,
+                                     "its weight plane when the array is passed");
+    if (rc != RSDSFM_OK) return rc;
     rsdsfm_superres_params sp;
     if (!superres_params_resolve(params_or_null, &sp)) return fail(c, RSDSFM_ERR_INVALID, kSuperresParamsMessage);
-    for (int q = 0; q < nsources; ++q)  // an output may not be a frame of the clip: a later frame call still reads it
-        for (int n = 0; n < nsources; ++n)
-            if (d_frames[n] == d_out_images[q] || d_frames[n] == d_out_masks[q] || (d_out_weights_or_null && d_frames[n] == d_out_weights_or_null[q]))
-                return fail(c, RSDSFM_ERR_INVALID, "superres video: an output plane may not be a frame of the clip");
-    // every frame's sources and poses first: a refused pose enqueues nothing
-    std::vector<SuperresPlan> plans(nsources);
-    for (int q = 0; q < nsources; ++q)
-        if (!superres_plan(A, c_, A_path, c_path, scales, nsources, q, sp.radius, &plans[q]))
-            return fail(c, RSDSFM_ERR_INVALID, "superres video: the poses must be finite and every listed source's scale finite and positive");
-    int64_t* d_cnt = nullptr;
-    if (counts_or_null) RSDSFM_HIP_CHECK(c, hipMalloc(reinterpret_cast<void**>(&d_cnt), 3 * sizeof(int64_t) * (size_t)nsources));
-    int rc = RSDSFM_OK;
-    for (int q = 0; q < nsources && rc == RSDSFM_OK; ++q) {  // the public entry point itself, so that it runs the code it runs alone
-        const SuperresPlan& p = plans[q];
-        const uint8_t* img[kSuperresSourcesMax];
-        const double *map[kSuperresSourcesMax], *R[kSuperresSourcesMax], *t[kSuperresSourcesMax];
-        for (int k = 0; k < p.nsrc; ++k) {
-            img[k] = d_frames[p.src[k]];
-            map[k] = d_depth_maps[p.src[k]];
-            R[k] = d_R[p.src[k]];
-            t[k] = d_t[p.src[k]];
-        }
-        rc = rsdsfm_superres_frame_dev(ctx, img, channels, map, R, t, fx, fy, cx, cy, rows, cols, mode, q5_mode, iterations, p.nsrc, p.M, p.m, params_or_null, window_or_null,
-                                       d_out_images[q], d_out_masks[q], d_out_weights_or_null ? d_out_weights_or_null[q] : nullptr, d_cnt ? d_cnt + 3 * (size_t)q : nullptr);
-    }
-    if (d_cnt) {
-        hipError_t e = rc == RSDSFM_OK ? hipMemcpyAsync(counts_or_null, d_cnt, 3 * sizeof(int64_t) * (size_t)nsources, hipMemcpyDeviceToHost, c->stream) : hipSuccess;
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        (void)hipFree(d_cnt);
-        if (rc == RSDSFM_OK) RSDSFM_HIP_CHECK(c, e);
-    }
-    return rc;
+    // the public entry point itself, so that it runs the code it runs alone
+    return walk_clip(c, "superres video", d_frames, nsources, d_depth_maps, d_R, d_t, A, c_, A_path, c_path, scales, sp.radius, outs, 3, counts_or_null, [&](const ClipFrame& f) {
+        return rsdsfm_superres_frame_dev(ctx, f.img, channels, f.map, f.R, f.t, fx, fy, cx, cy, rows, cols, mode, q5_mode, iterations, f.plan->nsrc, f.plan->M, f.plan->m,
+                                         params_or_null, window_or_null, f.out[0], f.out[1], f.out[2], f.d_counts);
+    });
 }
 
 }  // extern "C"

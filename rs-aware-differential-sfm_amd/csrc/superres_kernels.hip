@@ -10,28 +10,23 @@
 //                               depth) gives all-zero planes.  Every byte of the outputs is written: no preset.  Stages A and B are the
 //                               existing launches on the source grid.
 //   superres_accumulate_kernel<CH, FIRST, LAST>
-//                               denoise_accumulate_kernel's 2-D tile (denoise_kernels.hip) on the fine grid: a workgroup of kBP threads owns
-//                               16 rows x 64 columns, a thread 4 consecutive pixels of one row; planes read as ALIGNED dwords of the flat
-//                               array shifted into place (one path for every cols).  Stage 1: the two proximity dwords first (a plane's
-//                               mask is prox != 0); R's CH dwords where some pixel has both set (LAST: where qR has a byte set), B's only
-//                               where some pixel has both; e = sum_c |R_c - k(B_c)| and the packed dword (v << 16) | e to LDS, 0 outside the
-//                               frame; the halo of 1 (164 pixels) by threads 0 .. 163, byte by byte.  LDS: 18 rows x 66 dwords = 4 752 B,
-//                               the denoise's layout and bank reasoning (8-byte reads at [row][4 g .. 4 g + 5]; rows 66 dwords apart lie 2
-//                               banks apart).  Stage 2: the 3 x 3 sum is D in the low half and the count in the high half;
-//                               w = 16 - min(16, 16 D / (h CH count)) where v; u = (w qL + 8) >> 4.  Only a thread with some u != 0 reads
-//                               the layer's NEAREST plane (CH dwords), only FIRST reads the reference's.  Cells as the shutter's: BGR cells
-//                               (8 B) move as 16-byte accesses (8-byte where the row's tail is shorter than 4), gray cells (4 B) as one
-//                               16-byte access where the pixel index is even and the four pixels are in the row, else 4-byte.  A mid step
+//                               on the 16 x 64 tile of image_tile_device.hpp, on the fine grid (the plane reads, the LDS layout and its bank
+//                               argument, the cells, the output group and the counters are described there).  Stage 1: the two proximity
+//                               dwords first (a plane's mask is prox != 0); R's CH dwords where some pixel has both set (LAST: where qR has a
+//                               byte set), B's only where some pixel has both; e = sum_c |R_c - k(B_c)| and the packed dword (v << 16) | e to
+//                               LDS, 0 outside the frame; the halo byte by byte.  Stage 2: the 3 x 3 sum is D in the low half and the count
+//                               in the high half; w = 16 - min(16, 16 D / (h CH count)) where v; u = (w qL + 8) >> 4.  Only a thread with
+//                               some u != 0 reads the layer's NEAREST plane (CH dwords), only FIRST reads the reference's.  A mid step
 //                               whose four u are 0 neither reads nor writes its cells.  FIRST: the cells are not read, cell =
 //                               [qR RN_c, qR].  LAST: the cells are not written; out_c = (2 s_c + n) / (2 n) where n > qR, R_c where
 //                               n == qR > 0, else 0; mask n > 0; the weight plane n.
 //                               A mid step of a BGR frame moves 1 + 1 + 3 + 3 + 3 + 8 + 8 = 27 B per fine pixel where both planes are set
 //                               and the weight is not 0.  Gains per workgroup from the 8-word record (seam_gain, threads 0 .. CH - 1,
-//                               through LDS): no host wait behind the sums kernel.  The three counters [unset, own only, merged]: a sum
-//                               per thread, shuffles, LDS, one 64-bit integer atomicAdd each per workgroup, only in LAST and only when a
-//                               counter pointer was passed.
+//                               through LDS): no host wait behind the sums kernel.  The three counters [unset, own only, merged] only in
+//                               LAST and only when a counter pointer was passed.
 #include <algorithm>
 
+#include "image_tile_device.hpp"
 #include "rectify_dense.hpp"
 #include "rectify_dense_device.hpp"
 #include "rsdsfm_internal.hpp"
@@ -43,55 +38,7 @@ namespace rsdsfm {
 
 namespace {
 
-constexpr int kTR = kDenoiseTileRows, kTC = kDenoiseTileCols;
-constexpr int kLdsStride = kTC + 2;             // 66 dwords: rows 2 banks apart, 8-byte aligned
-constexpr int kHalo = 2 * (kTC + 2) + 2 * kTR;  // 164
-static_assert(kTR * (kTC / 4) == kBP, "a thread owns 4 consecutive pixels of a row of the tile");
-static_assert(kHalo <= kBP && kLdsStride % 2 == 0, "one halo pixel per thread; 8-byte aligned rows");
 static_assert(kSuperresProxMax == kDenoiseW, "the own frame's nearest sample counts as the denoise's own frame does");
-
-// 1 in every byte of w that is not 0
-__device__ __forceinline__ unsigned bytes_set(unsigned w) { return ((w | ((w & 0x7f7f7f7fu) + 0x7f7f7f7fu)) >> 7) & 0x01010101u; }
-
-// byte k of an array of dwords (k a compile-time constant after unrolling)
-__device__ __forceinline__ unsigned byte_of(const unsigned* w, int k) { return (w[k >> 2] >> (8 * (k & 3))) & 0xffu; }
-
-// halfword k of an array of dwords
-__device__ __forceinline__ unsigned half_of(const unsigned* w, int k) { return (w[k >> 1] >> (16 * (k & 1))) & 0xffffu; }
-
-// 16 bytes of cells; the ABI promises 8-byte alignment
-typedef unsigned Cells16 __attribute__((ext_vector_type(4), aligned(8)));
-typedef unsigned Cells8 __attribute__((ext_vector_type(2), aligned(8)));
-typedef unsigned Lds8 __attribute__((ext_vector_type(2), aligned(8)));  // one ds_read_b64
-
-// the aligned dword at byte offset o (a multiple of 4) of a plane of nbytes bytes; bytes past the plane's end read as 0 and are not touched
-__device__ __forceinline__ unsigned aligned_dword(const unsigned char* __restrict__ base, int64_t o, int64_t nbytes) {
-    if (o + 4 <= nbytes) return *reinterpret_cast<const unsigned*>(base + o);
-    unsigned w = 0u;
-    for (int b = 0; b < 4; ++b)
-        if (o + b < nbytes) w |= (unsigned)base[o + b] << (8 * b);
-    return w;
-}
-
-// ND dwords of bytes from byte offset `off` (any alignment) of a plane, as ND + 1 aligned dwords shifted into place
-template <int ND>
-__device__ __forceinline__ void load_bytes(const unsigned char* __restrict__ base, int64_t off, int64_t nbytes, unsigned* out) {
-    const int64_t a = off & ~(int64_t)3;
-    const unsigned sh = 8u * (unsigned)(off & 3);
-    unsigned w[ND + 1];
-#pragma unroll
-    for (int d = 0; d < ND; ++d) w[d] = aligned_dword(base, a + 4 * d, nbytes);
-    w[ND] = sh ? aligned_dword(base, a + 4 * ND, nbytes) : 0u;
-#pragma unroll
-    for (int d = 0; d < ND; ++d) out[d] = sh ? (w[d] >> sh) | (w[d + 1] << (32u - sh)) : w[d];
-}
-
-__device__ __forceinline__ unsigned gained(unsigned G, unsigned l) {  // G <= 2^18, the byte < 2^8
-    const unsigned k = (G * l + 32768u) >> 16;
-    return k > 255u ? 255u : k;
-}
-
-__device__ __forceinline__ unsigned absdiff(unsigned a, unsigned b) { return a > b ? a - b : b - a; }
 
 // ---------------------------------------------------------------------------------------------------
 // the render's stage C
@@ -137,7 +84,7 @@ __device__ __forceinline__ void superres_warp_body(const unsigned char* __restri
             }
         }
         const int64_t p0 = (int64_t)Y * ocols + X0;
-        if (nin == 4 && (p0 & 3) == 0) {  // p0 and CH * p0 bytes are 4-byte aligned
+        if (group_whole(nin, p0)) {
             unsigned* db = reinterpret_cast<unsigned*>(bil + (int64_t)CH * p0);
             unsigned* dn = reinterpret_cast<unsigned*>(near + (int64_t)CH * p0);
 #pragma unroll
@@ -176,16 +123,13 @@ __device__ __forceinline__ void superres_accumulate_body(const unsigned char* __
                                                          unsigned char* __restrict__ weight, unsigned long long* __restrict__ counts) {
     constexpr int H = CH + 1;      // halfwords per cell
     constexpr int NW = 4 * H / 2;  // dwords of a thread's four cells: 8 (BGR) or 4 (gray)
-    __shared__ __attribute__((aligned(16))) unsigned s_tile[(kTR + 2) * kLdsStride];
+    __shared__ __attribute__((aligned(16))) unsigned s_tile[kTileLdsWords];
     __shared__ unsigned s_gain[CH];
     const bool has_layer = layer != nullptr;  // (uniform)
-    const int tid = (int)threadIdx.x, ty = tid / (kTC / 4), g = tid % (kTC / 4);
-    const int y0 = (int)blockIdx.y * kTR, x0 = (int)blockIdx.x * kTC;
-    const int y = y0 + ty, x = x0 + 4 * g;
-    const int64_t npix = (int64_t)rows * cols;
-    const int nin = (y < rows && x < cols) ? (cols - x < 4 ? cols - x : 4) : 0;  // the thread's pixels inside the frame: the first nin of its 4
-    const int64_t p0 = (int64_t)y * cols + x;
-    const unsigned inside = nin == 4 ? 0xffffffffu : nin == 3 ? 0x00ffffffu : nin == 2 ? 0x0000ffffu : nin == 1 ? 0x000000ffu : 0u;
+    const TileThread t = tile_thread(rows, cols);
+    const int nin = t.nin;
+    const int64_t p0 = t.p0, npix = (int64_t)rows * cols;
+    const unsigned inside = first_bytes(nin);
 
     unsigned qr = 0u, ql = 0u, v = 0u, rw[CH], u[4] = {0u, 0u, 0u, 0u};  // qr, ql: the four proximities; v: 1 in the bytes with both set
 #pragma unroll
@@ -207,7 +151,7 @@ __device__ __forceinline__ void superres_accumulate_body(const unsigned char* __
 #pragma unroll
     for (int c = 0; c < CH; ++c) G[c] = kGainOne;
     if (has_layer) {
-        if (tid < CH) s_gain[tid] = sums ? seam_gain(sums, CH, tid, min_overlap, gain_mode) : kGainOne;
+        if (t.tid < CH) s_gain[t.tid] = sums ? seam_gain(sums, CH, t.tid, min_overlap, gain_mode) : kGainOne;
         __syncthreads();
 #pragma unroll
         for (int c = 0; c < CH; ++c) G[c] = s_gain[c];
@@ -224,46 +168,27 @@ __device__ __forceinline__ void superres_accumulate_body(const unsigned char* __
                 ent[j] = ((v >> (8 * j)) & 1u) ? (0x10000u | e) : 0u;
             }
         }
-        unsigned* row = s_tile + (ty + 1) * kLdsStride + 4 * g + 1;
+        unsigned* row = tile_own(s_tile, t);
 #pragma unroll
         for (int j = 0; j < 4; ++j) row[j] = ent[j];
-        // the halo: the rows above and below (66 each), the columns left and right (16 each), one pixel per thread
-        if (tid < kHalo) {
-            int ly, lx;
-            if (tid < 2 * kLdsStride) {
-                ly = tid < kLdsStride ? 0 : kTR + 1;
-                lx = tid < kLdsStride ? tid : tid - kLdsStride;
-            } else {
-                const int r = tid - 2 * kLdsStride;
-                ly = 1 + (r < kTR ? r : r - kTR);
-                lx = r < kTR ? 0 : kTC + 1;
-            }
-            const int hy = y0 + ly - 1, hx = x0 + lx - 1;
+        if (t.tid < kTileHalo) {
+            const TileHalo h = tile_halo(t);
             unsigned e = 0u;
-            if (hy >= 0 && hy < rows && hx >= 0 && hx < cols) {
-                const int64_t p = (int64_t)hy * cols + hx;
+            if (h.hy >= 0 && h.hy < rows && h.hx >= 0 && h.hx < cols) {
+                const int64_t p = (int64_t)h.hy * cols + h.hx;
                 if (rprox[p] != 0 && lprox[p] != 0) {
                     e = 0x10000u;
 #pragma unroll
                     for (int c = 0; c < CH; ++c) e += absdiff(ref[CH * p + c], gained(G[c], layer[CH * p + c]));
                 }
             }
-            s_tile[ly * kLdsStride + lx] = e;
+            s_tile[h.ly * kTileLdsStride + h.lx] = e;
         }
         __syncthreads();
-        // stage 2: the 3 x 3 sums of the packed dwords; three rows of six columns, 8-byte reads
+        // stage 2: the 3 x 3 sums of the packed dwords
         if (v) {
-            unsigned col[6] = {0u, 0u, 0u, 0u, 0u, 0u};
-#pragma unroll
-            for (int r = 0; r < 3; ++r) {
-                const Lds8* q = static_cast<const Lds8*>(__builtin_assume_aligned(s_tile + (ty + r) * kLdsStride + 4 * g, 8));
-#pragma unroll
-                for (int i = 0; i < 3; ++i) {
-                    const Lds8 t = q[i];
-                    col[2 * i] += t[0];  // the high half is a count <= 9, the low half <= 6 885: no carry
-                    col[2 * i + 1] += t[1];
-                }
-            }
+            unsigned col[6];
+            tile_sum3x3(s_tile, t.ty, t.g, col);
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const unsigned s = col[j] + col[j + 1] + col[j + 2];
@@ -283,31 +208,9 @@ __device__ __forceinline__ void superres_accumulate_body(const unsigned char* __
         unsigned cw[NW];
 #pragma unroll
         for (int i = 0; i < NW; ++i) cw[i] = 0u;
-        // the thread's cells: BGR 8 B each (two 16-byte accesses when the four pixels are its own); gray 4 B each
-        const bool wide = nin == 4 && (CH == 3 || (p0 & 1) == 0);  // the 16 bytes start on the ABI's 8
+        const bool wide = cells_wide<CH>(nin, p0);
         unsigned short* cell0 = (FIRST && LAST) ? nullptr : cells + (int64_t)H * p0;
-        if (!FIRST) {
-            if (wide) {
-#pragma unroll
-                for (int k = 0; k < NW / 4; ++k) {
-                    const Cells16 t = reinterpret_cast<const Cells16*>(cell0)[k];
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) cw[4 * k + i] = t[i];
-                }
-            } else {
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    if (j < nin) {
-                        if constexpr (CH == 3) {
-                            const Cells8 t = reinterpret_cast<const Cells8*>(cell0)[j];
-                            cw[2 * j] = t[0];
-                            cw[2 * j + 1] = t[1];
-                        } else {
-                            cw[j] = reinterpret_cast<const unsigned*>(cell0)[j];
-                        }
-                    }
-            }
-        }
+        if (!FIRST) cells_load<CH>(cell0, nin, wide, cw);
         // the nearest samples: the reference's only in FIRST, the layer's only where something is added
         unsigned rn[CH], ln[CH];
 #pragma unroll
@@ -325,20 +228,7 @@ __device__ __forceinline__ void superres_accumulate_body(const unsigned char* __
             for (int h = 0; h < H; ++h) cw[(H * j + h) >> 1] += add[h] << (16 * ((H * j + h) & 1));  // no halfword overflows: n <= 240, sums <= 61 200
         }
         if (!LAST) {
-            if (wide) {
-#pragma unroll
-                for (int k = 0; k < NW / 4; ++k) reinterpret_cast<Cells16*>(cell0)[k] = Cells16{cw[4 * k], cw[4 * k + 1], cw[4 * k + 2], cw[4 * k + 3]};
-            } else {
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    if (j < nin) {
-                        if constexpr (CH == 3) {
-                            reinterpret_cast<Cells8*>(cell0)[j] = Cells8{cw[2 * j], cw[2 * j + 1]};
-                        } else {
-                            reinterpret_cast<unsigned*>(cell0)[j] = cw[j];
-                        }
-                    }
-            }
+            cells_store<CH>(cell0, nin, wide, cw);
         } else {
             unsigned ow[CH], mw = 0u, nw = 0u;
 #pragma unroll
@@ -360,40 +250,12 @@ __device__ __forceinline__ void superres_accumulate_body(const unsigned char* __
                     n3[2] += merged;
                 }
             }
-            if (nin == 4 && (p0 & 3) == 0) {  // p0 and CH * p0 bytes are 4-byte aligned
-#pragma unroll
-                for (int d = 0; d < CH; ++d) reinterpret_cast<unsigned*>(out + (int64_t)CH * p0)[d] = ow[d];
-                *reinterpret_cast<unsigned*>(mask_out + p0) = mw;
-                if (weight) *reinterpret_cast<unsigned*>(weight + p0) = nw;
-            } else {
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    if (j < nin) {
-#pragma unroll
-                        for (int c = 0; c < CH; ++c) out[(int64_t)CH * (p0 + j) + c] = (unsigned char)byte_of(ow, CH * j + c);
-                        mask_out[p0 + j] = (unsigned char)((mw >> (8 * j)) & 0xffu);
-                        if (weight) weight[p0 + j] = (unsigned char)((nw >> (8 * j)) & 0xffu);
-                    }
-            }
+            unsigned char* const planes[2] = {mask_out, weight};
+            const unsigned words[2] = {mw, nw};
+            store_group<CH>(out, ow, planes, words, p0, nin);
         }
     }
-    if constexpr (LAST) {
-        __shared__ unsigned s_wave[3][kBP / 64];
-        if (!counts) return;  // (uniform)
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) n3[k] += __shfl_down(n3[k], off, 64);
-            if ((threadIdx.x & 63) == 0) s_wave[k][threadIdx.x / 64] = n3[k];
-        }
-        __syncthreads();
-        if (threadIdx.x < 3) {
-            unsigned total = 0;
-#pragma unroll
-            for (int i = 0; i < kBP / 64; ++i) total += s_wave[threadIdx.x][i];
-            if (total) atomicAdd(counts + threadIdx.x, (unsigned long long)total);
-        }
-    }
+    if constexpr (LAST) block_counts_add<3>(n3, counts);
 }
 
 }  // namespace
@@ -452,7 +314,6 @@ int superres_accumulate_launch(Ctx* c, const unsigned char* d_ref, const unsigne
                                int64_t min_overlap, int gain_mode, int strength, uint16_t* d_cells, bool first, bool last, unsigned char* d_image_out,
                                unsigned char* d_mask_out, unsigned char* d_weight, int64_t* d_counts3) {
     if (last && d_counts3) RSDSFM_HIP_CHECK(c, hipMemsetAsync(d_counts3, 0, 3 * sizeof(int64_t), c->stream));
-    const dim3 grid((unsigned)((cols + kTC - 1) / kTC), (unsigned)((rows + kTR - 1) / kTR));  // at most 256 x 1024
     using Kernel = void (*)(const unsigned char*, const unsigned char*, const unsigned char*, const unsigned char*, const unsigned char*, const unsigned char*, int, int,
                             const unsigned long long*, long long, int, unsigned, unsigned short*, unsigned char*, unsigned char*, unsigned char*, unsigned long long*);
     static const Kernel kernels[2][2][2] = {
@@ -461,7 +322,7 @@ int superres_accumulate_launch(Ctx* c, const unsigned char* d_ref, const unsigne
         {{superres_accumulate_kernel<3, false, false>, superres_accumulate_kernel<3, false, true>},
          {superres_accumulate_kernel<3, true, false>, superres_accumulate_kernel<3, true, true>}}};
     // the outputs are passed only to the instances that write them
-    hipLaunchKernelGGL(kernels[channels == 3][first][last], grid, dim3(kBP), 0, c->stream, d_ref, d_rnear, d_rprox, d_layer, d_lnear, d_lprox, rows, cols, d_sums,
+    hipLaunchKernelGGL(kernels[channels == 3][first][last], tile_grid(rows, cols), dim3(kBP), 0, c->stream, d_ref, d_rnear, d_rprox, d_layer, d_lnear, d_lprox, rows, cols, d_sums,
                        (long long)min_overlap, gain_mode, (unsigned)strength, d_cells, last ? d_image_out : nullptr, last ? d_mask_out : nullptr,
                        last ? d_weight : nullptr, last ? reinterpret_cast<unsigned long long*>(d_counts3) : nullptr);
     RSDSFM_HIP_CHECK(c, hipGetLastError());
