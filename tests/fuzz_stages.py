@@ -15,9 +15,10 @@ or the seam distance of a fixed mask, in turn) runs at the OLD size, and behind 
 time a probe runs it must equal its definition, every later time the same bytes.
 
 Not covered: the second trip of the grid-stride loops whose grids are capped at 65536 blocks -- the warp kernels of the dense rectifier, the
-stabiliser, the fill and the window frame, seam_distance_cols_kernel, the seam blend's kernels and inpaint_write_kernel take it only above
-2^26 pixels, which no quick test reaches.  (tests/test_gpu_stage_fuzz.py takes the two smaller caps, stabilize_count_kernel's and
-crop_search_kernel's, past one grid.)  The clip calls are not driven either: they have their own "those calls one after another" tests.
+stabiliser, the fill and the window frame, seam_distance_cols_kernel, the seam blend's kernels, inpaint_write_kernel and the
+super-resolution's superres_warp_kernel (tests/fuzz_temporal.py draws that stage) take it only above 2^26 pixels, which no quick test
+reaches.  (tests/test_gpu_stage_fuzz.py takes the two smaller caps, stabilize_count_kernel's and crop_search_kernel's, past one grid;
+tests/test_gpu_temporal_fuzz.py retime_merge_kernel's and shutter_accumulate_kernel's.)  The clip calls are not driven either: they have their own "those calls one after another" tests.
 
 Prints one line  FAIL seed ... case ...  per failing case with everything needed to rebuild it, then one line per differing output, and a
 summary; returns 1 if anything failed.
