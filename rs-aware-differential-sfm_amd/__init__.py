@@ -136,11 +136,12 @@ class RansacOut(C.Structure):
 
 def declared_symbols():
     """Names of every function include/rsdsfm.h, include/rsdsfm_retime.h, include/rsdsfm_shutter.h, include/rsdsfm_denoise.h,
-    include/rsdsfm_superres.h and include/rsdsfm_plate.h declare (used by the CPU symbol-export test)."""
+    include/rsdsfm_superres.h, include/rsdsfm_plate.h and include/rsdsfm_erase.h declare (used by the CPU symbol-export test)."""
     import re
 
     txt = "".join(open(os.path.join(os.path.dirname(HEADER_PATH), name)).read()
-                  for name in (os.path.basename(HEADER_PATH), "rsdsfm_retime.h", "rsdsfm_shutter.h", "rsdsfm_denoise.h", "rsdsfm_superres.h", "rsdsfm_plate.h"))
+                  for name in (os.path.basename(HEADER_PATH), "rsdsfm_retime.h", "rsdsfm_shutter.h", "rsdsfm_denoise.h", "rsdsfm_superres.h", "rsdsfm_plate.h",
+                              "rsdsfm_erase.h"))
     txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
     return sorted(set(re.findall(r"\b(rsdsfm_[a-z0-9_]+)\s*\(", txt)))
 
@@ -3499,6 +3500,178 @@ class _PlateMixin:
 
 
 for _name, _fn in list(vars(_PlateMixin).items()):
+    if not _name.startswith("__"):
+        setattr(Solver, _name, _fn)
+
+
+# ---------------------------------------------------------------------------------------------------
+# the mover removal: the plate's flag as a cleaned, feathered matte and the plate under it (include/rsdsfm_erase.h)
+# ---------------------------------------------------------------------------------------------------
+ERASE_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "rsdsfm_erase.h")
+ERASE_OPEN_MAX, ERASE_GROW_MAX, ERASE_FEATHER_MAX = 3, 8, 16
+ERASE_COUNTS = ("unset", "kept", "replaced", "feathered", "unresolved")  # the counters' order
+
+
+class EraseParams(C.Structure):
+    _fields_ = [("radius", C.c_int32), ("threshold", C.c_int32), ("min_votes", C.c_int32), ("gain_mode", C.c_int32), ("occlusion", C.c_int32),
+                ("occlusion_tol_q16", C.c_int32), ("struct_bytes", C.c_int32), ("open", C.c_int32), ("min_overlap", C.c_int64), ("grow", C.c_int32),
+                ("feather", C.c_int32), ("include_undecided", C.c_int32), ("reserved", C.c_int32 * 5)]
+
+
+def erase_declared_symbols():
+    """Names of every function include/rsdsfm_erase.h declares"""
+    import re
+
+    txt = open(ERASE_HEADER_PATH).read()
+    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
+    return sorted(set(re.findall(r"\b(rsdsfm_[a-z0-9_]+)\s*\(", txt)))
+
+
+def _erase_params(radius=None, open=None, grow=None, feather=None, include_undecided=False, threshold=None, min_votes=None, gain=True, occlusion=False,
+                  occlusion_tol_q16=0, min_overlap=None):
+    """an EraseParams with the given values over the defaults (None: the default).  open and grow are literal here: 0 means none (the struct's -1)"""
+    p = EraseParams()
+    if load_library().rsdsfm_erase_params_init(C.byref(p)) != OK:
+        raise RsdsfmError("rsdsfm_erase_params_init failed")
+    if radius is not None:
+        p.radius = int(radius)
+    if threshold is not None:
+        p.threshold = int(threshold)
+    if min_votes is not None:
+        p.min_votes = int(min_votes)
+    if min_overlap is not None:
+        p.min_overlap = int(min_overlap)
+    if open is not None:
+        p.open = -1 if int(open) == 0 else int(open)
+    if grow is not None:
+        p.grow = -1 if int(grow) == 0 else int(grow)
+    if feather is not None:
+        p.feather = int(feather)
+    p.gain_mode, p.occlusion, p.occlusion_tol_q16, p.include_undecided = 0 if gain else 1, int(occlusion), int(occlusion_tol_q16), int(include_undecided)
+    return p
+
+
+def erase_default_params():
+    """the mover removal's defaults as a dict: the plate's and open = 2, grow = 2, feather = 4, include_undecided = 0 (rsdsfm_erase_params_init);
+    choices, not measurements"""
+    p = _erase_params()
+    return dict(radius=p.radius, threshold=p.threshold, min_votes=p.min_votes, min_overlap=p.min_overlap, gain_mode=p.gain_mode, occlusion=p.occlusion, open=p.open, grow=p.grow,
+                feather=p.feather, include_undecided=p.include_undecided)
+
+
+def mover_matte_launches(rows, cols):
+    """kernel launches of one mover_matte_dev call: 3 (rsdsfm_mover_matte_launches; host only)"""
+    n = load_library().rsdsfm_mover_matte_launches(C.c_int32(rows), C.c_int32(cols))
+    if n < 0:
+        raise RsdsfmError("rsdsfm_mover_matte_launches failed (%d): rows and cols in [2, 16384]" % n)
+    return n
+
+
+def erase_composite_launches():
+    """kernel launches of one erase_composite_dev call: 1 (rsdsfm_erase_composite_launches; host only)"""
+    return int(load_library().rsdsfm_erase_composite_launches())
+
+
+def erase_launches(rows, cols, nsrc):
+    """kernel launches of one erase_frame_dev call on nsrc sources: plate_launches + 3 + 1 (rsdsfm_erase_launches; host only)"""
+    n = load_library().rsdsfm_erase_launches(C.c_int32(rows), C.c_int32(cols), C.c_int32(nsrc))
+    if n < 0:
+        raise RsdsfmError("rsdsfm_erase_launches failed (%d): rows and cols in [2, 16384], nsrc in [1, 15]" % n)
+    return n
+
+
+class _EraseMixin:
+    def mover_matte_dev(self, d_flag, rows, cols, d_matte, open=2, grow=2, feather=4, include_undecided=False):
+        """the plate's flag plane as a matte (rsdsfm_mover_matte_dev; tests/erase_spec_numpy.py): the seeds (flag 2, with include_undecided 3 too)
+        eroded by the (2 open + 1)^2 window inside the frame, then feather within open + grow of what is left, one less per pixel beyond.
+        Literal values.  Three launches, enqueued on the context's stream."""
+        self._check(self.lib.rsdsfm_mover_matte_dev(self._ctx, _np0(d_flag), C.c_int32(rows), C.c_int32(cols), C.c_int32(open), C.c_int32(grow), C.c_int32(feather),
+                                                    C.c_int32(int(include_undecided)), _np0(d_matte)), "rsdsfm_mover_matte_dev")
+
+    def mover_matte(self, flag, open=2, grow=2, feather=4, include_undecided=False, device=0):
+        """host convenience around mover_matte_dev: flag (rows, cols) uint8 -> the matte (rows, cols) uint8"""
+        import torch
+
+        flag = np.ascontiguousarray(flag, dtype=np.uint8)
+        rows, cols = flag.shape
+        dev = torch.device("cuda", device)
+        with torch.cuda.device(dev):
+            d_f = torch.from_numpy(flag).to(dev)
+            d_a = torch.empty_like(d_f)
+            torch.cuda.synchronize()
+            self.mover_matte_dev(d_f.data_ptr(), rows, cols, d_a.data_ptr(), open, grow, feather, include_undecided)
+            self.synchronize()
+            return d_a.cpu().numpy()
+
+    def erase_composite_dev(self, d_ref, d_ref_mask, d_plate, d_plate_mask, d_matte, channels, rows, cols, d_image_out, d_mask_out, d_counts5=None, feather=4):
+        """the plate under the matte, the own frame's bytes everywhere else (rsdsfm_erase_composite_dev; tests/erase_spec_numpy.py); the counts
+        [unset, kept, replaced, feathered, unresolved] into d_counts5 (five device int64).  One launch, enqueued on the context's stream."""
+        self._check(self.lib.rsdsfm_erase_composite_dev(self._ctx, _np0(d_ref), _np0(d_ref_mask), _np0(d_plate), _np0(d_plate_mask), _np0(d_matte), C.c_int32(channels),
+                                                        C.c_int32(rows), C.c_int32(cols), C.c_int32(feather), _np0(d_image_out), _np0(d_mask_out), _np0(d_counts5)),
+                    "rsdsfm_erase_composite_dev")
+
+    def erase_composite(self, ref, ref_mask, plate, plate_mask, matte, feather=4, device=0):
+        """host convenience around erase_composite_dev -> (image, mask (rows, cols) uint8, counts (5,) int64)"""
+        import torch
+
+        ref = np.ascontiguousarray(ref, dtype=np.uint8)
+        rows, cols = ref.shape[:2]
+        ch = 1 if ref.ndim == 2 else ref.shape[2]
+        dev = torch.device("cuda", device)
+        with torch.cuda.device(dev):
+            up = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.uint8)).to(dev)
+            d_ref, d_rm, d_p, d_pm, d_a = up(ref), up(ref_mask), up(plate), up(plate_mask), up(matte)
+            d_out, d_mask, d_cnt = torch.empty_like(d_ref), torch.empty((rows, cols), dtype=torch.uint8, device=dev), torch.zeros(5, dtype=torch.int64, device=dev)
+            torch.cuda.synchronize()
+            self.erase_composite_dev(d_ref.data_ptr(), d_rm.data_ptr(), d_p.data_ptr(), d_pm.data_ptr(), d_a.data_ptr(), ch, rows, cols, d_out.data_ptr(), d_mask.data_ptr(),
+                                     d_cnt.data_ptr(), feather)
+            self.synchronize()
+            return d_out.cpu().numpy(), d_mask.cpu().numpy(), d_cnt.cpu().numpy()
+
+    def erase_frame_dev(self, d_images, channels, d_depth_maps, d_R, d_t, K, rows, cols, M, m, d_image, d_mask, d_matte=None, d_moving=None, d_counts5=None, open=None,
+                        grow=None, feather=None, include_undecided=False, threshold=None, min_votes=None, gain=True, min_overlap=None, window=None, occlusion=False,
+                        occlusion_tol_q16=0, mode=BACKPROJECT_RS, q5_mode=Q5_COMPAT, iterations=0, params=None):
+        """one frame without its movers (rsdsfm_erase_frame_dev): the sources and poses as plate_frame_dev takes them; plate_frame_dev into the
+        context's workspace, the matte of its flag (open, grow, feather literal; None: the defaults 2, 2, 4), the plate under the matte and the
+        own frame everywhere else into d_image, d_mask; the matte into d_matte, the plate's flag into d_moving, [unset, kept, replaced,
+        feathered, unresolved] into d_counts5.  params: an EraseParams passed as it is instead of the keywords.  Enqueued on the context's stream."""
+        ns = len(d_images)
+        _need_all(ns, d_depth_maps=d_depth_maps, d_R=d_R, d_t=d_t)
+        Mm, mm = _f64(M).reshape(-1, 9), _f64(m).reshape(-1, 3)
+        if Mm.shape[0] < ns or mm.shape[0] < ns:
+            raise RsdsfmError("erase_frame_dev: every source needs a pose (M, m)")
+        ep = params if params is not None else _erase_params(None, open, grow, feather, include_undecided, threshold, min_votes, gain, occlusion, occlusion_tol_q16, min_overlap)
+        d = C.c_double
+        arr = lambda x: _ptr_array(list(x)[:ns]) if ns else None
+        self._check(self.lib.rsdsfm_erase_frame_dev(self._ctx, arr(d_images), C.c_int32(channels), arr(d_depth_maps), arr(d_R), arr(d_t), d(K[0]), d(K[1]), d(K[2]), d(K[3]),
+                                                    C.c_int32(rows), C.c_int32(cols), int(mode), int(q5_mode), C.c_int32(iterations), C.c_int32(ns), _p(Mm), _p(mm),
+                                                    C.byref(ep), _window4(window), _dp(d_image), _dp(d_mask), _np0(d_matte), _np0(d_moving), _np0(d_counts5)),
+                    "rsdsfm_erase_frame_dev")
+
+    def erase_video_dev(self, d_frames, rows, cols, channels, K, d_depth_maps, d_R, d_t, A, c, A_path, c_path, scales, d_out, d_out_masks, d_out_mattes=None,
+                        d_out_moving=None, want_counts=True, radius=None, open=None, grow=None, feather=None, include_undecided=False, threshold=None, min_votes=None,
+                        gain=True, min_overlap=None, window=None, occlusion=False, occlusion_tol_q16=0, mode=BACKPROJECT_RS, q5_mode=Q5_COMPAT, iterations=0):
+        """a solved clip without its movers (rsdsfm_erase_video_dev): the clip as plate_video_dev takes it and walks it, erase_frame_dev into
+        d_out[q], d_out_masks[q], d_out_mattes[q], d_out_moving[q].  Returns dict(); with want_counts counts (nsources, 5) int64 [unset, kept,
+        replaced, feathered, unresolved] -- the call then waits."""
+        ns = len(d_depth_maps)
+        _need_all(ns, d_frames=d_frames, d_R=d_R, d_t=d_t, d_out=d_out, d_out_masks=d_out_masks, d_out_mattes=d_out_mattes, d_out_moving=d_out_moving)
+        a, cc, ap, cp = _f64(A).reshape(-1, 9), _f64(c).reshape(-1, 3), _f64(A_path).reshape(-1, 9), _f64(c_path).reshape(-1, 3)
+        sc = _f64(scales).reshape(-1)
+        if min(a.shape[0], cc.shape[0], ap.shape[0], cp.shape[0], sc.shape[0]) < ns:
+            raise RsdsfmError("erase_video_dev: every source needs a pose on both paths and a scale")
+        ep = _erase_params(radius, open, grow, feather, include_undecided, threshold, min_votes, gain, occlusion, occlusion_tol_q16, min_overlap)
+        counts = np.zeros((max(ns, 1), 5), dtype=np.int64) if want_counts else None
+        d = C.c_double
+        arr = lambda x: _ptr_array(list(x)[:ns]) if x is not None and ns else None
+        self._check(self.lib.rsdsfm_erase_video_dev(self._ctx, arr(d_frames), C.c_int32(ns), C.c_int32(rows), C.c_int32(cols), C.c_int32(channels), d(K[0]), d(K[1]),
+                                                    d(K[2]), d(K[3]), arr(d_depth_maps), arr(d_R), arr(d_t), _p(a), _p(cc), _p(ap), _p(cp), _p(sc), int(mode), int(q5_mode),
+                                                    C.c_int32(iterations), C.byref(ep), _window4(window), arr(d_out), arr(d_out_masks), arr(d_out_mattes), arr(d_out_moving),
+                                                    _p(counts)), "rsdsfm_erase_video_dev")
+        return dict(counts=counts[:ns]) if want_counts else dict()
+
+
+for _name, _fn in list(vars(_EraseMixin).items()):
     if not _name.startswith("__"):
         setattr(Solver, _name, _fn)
 

@@ -44,6 +44,11 @@ struct PlateArgs {
 inline size_t plate_records_bytes() { return (size_t)kPlateLayersMax * 8 * sizeof(uint64_t); }
 inline size_t plate_ws_bytes(int rows, int cols, int layers) { return (5 + 4 * (size_t)layers) * blend_plane_bytes(rows, cols) + plate_records_bytes(); }
 
+// the params with every 0 of radius, threshold, min_votes and min_overlap replaced by its default, or the defaults for NULL; false: refused with
+// kPlateParamsMessage (plate_host.hip; the mover removal resolves the plate's fields of its own params with it)
+bool plate_params_resolve(const rsdsfm_plate_params* in, rsdsfm_plate_params* out);
+extern const char* const kPlateParamsMessage;
+
 // the median on c->stream (arguments checked by the caller): the counters zeroed by a memset when passed, then one launch
 int plate_median_launch(Ctx* c, const PlateArgs& args, int channels);
 

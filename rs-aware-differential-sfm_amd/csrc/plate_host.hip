@@ -17,23 +17,6 @@ rsdsfm_plate_params plate_defaults() {
                                {0, 0, 0, 0}};
 }
 
-// the params with every 0 of radius, threshold, min_votes and min_overlap replaced by its default, or the defaults for NULL; false: refused
-bool plate_params_resolve(const rsdsfm_plate_params* in, rsdsfm_plate_params* out) {
-    *out = in ? *in : plate_defaults();
-    if (out->struct_bytes != 0 && out->struct_bytes != (int32_t)sizeof(rsdsfm_plate_params)) return false;
-    if (out->radius == 0) out->radius = RSDSFM_PLATE_RADIUS_DEFAULT;
-    if (out->threshold == 0) out->threshold = kPlateThresholdDefault;
-    if (out->min_votes == 0) out->min_votes = kPlateMinVotesDefault;
-    if (out->min_overlap == 0) out->min_overlap = kMinOverlapDefault;
-    return out->radius >= 1 && out->radius <= kPlateRadiusMax && out->threshold >= 1 && out->threshold <= kPlateThresholdMax && out->min_votes >= 1 &&
-           out->min_votes <= kPlateMinVotesMax && out->min_overlap >= 0 && (out->gain_mode == 0 || out->gain_mode == 1) && (out->occlusion == 0 || out->occlusion == 1) &&
-           out->occlusion_tol_q16 >= 0 && out->occlusion_tol_q16 <= kVisibleTolQ16Max;
-}
-
-const char* const kPlateParamsMessage =
-    "rsdsfm_plate_params: radius in [1, 7] or 0, threshold in [1, 255] or 0, min_votes in [1, 15] or 0, gain_mode 0 or 1, occlusion 0 or 1, occlusion_tol_q16 in [0, 65536], "
-    "min_overlap >= 0, struct_bytes 0 or sizeof (use rsdsfm_plate_params_init)";
-
 // the argument checks of the outputs, for the median call and, before anything is enqueued, for the frame call (whose input planes are the context's)
 int plate_outputs_check(Ctx* c, const uint8_t* d_image_out, const uint8_t* d_mask_out, const uint8_t* d_votes, const uint8_t* d_moving, const int64_t* d_counts4) {
     if (!d_image_out || !d_mask_out) return fail(c, RSDSFM_ERR_INVALID, "plate: null output plane");
@@ -69,6 +52,24 @@ int plate_ws(Ctx* c, int rows, int cols, int layers, DenseWs** ws) {
 static_assert(kPlateSourcesMax == kClipSourcesMax, "a frame's sources are a ClipPlan's");
 
 }  // namespace
+
+// the params with every 0 of radius, threshold, min_votes and min_overlap replaced by its default, or the defaults for NULL; false: refused
+bool plate_params_resolve(const rsdsfm_plate_params* in, rsdsfm_plate_params* out) {
+    *out = in ? *in : plate_defaults();
+    if (out->struct_bytes != 0 && out->struct_bytes != (int32_t)sizeof(rsdsfm_plate_params)) return false;
+    if (out->radius == 0) out->radius = RSDSFM_PLATE_RADIUS_DEFAULT;
+    if (out->threshold == 0) out->threshold = kPlateThresholdDefault;
+    if (out->min_votes == 0) out->min_votes = kPlateMinVotesDefault;
+    if (out->min_overlap == 0) out->min_overlap = kMinOverlapDefault;
+    return out->radius >= 1 && out->radius <= kPlateRadiusMax && out->threshold >= 1 && out->threshold <= kPlateThresholdMax && out->min_votes >= 1 &&
+           out->min_votes <= kPlateMinVotesMax && out->min_overlap >= 0 && (out->gain_mode == 0 || out->gain_mode == 1) && (out->occlusion == 0 || out->occlusion == 1) &&
+           out->occlusion_tol_q16 >= 0 && out->occlusion_tol_q16 <= kVisibleTolQ16Max;
+}
+
+const char* const kPlateParamsMessage =
+    "rsdsfm_plate_params: radius in [1, 7] or 0, threshold in [1, 255] or 0, min_votes in [1, 15] or 0, gain_mode 0 or 1, occlusion 0 or 1, occlusion_tol_q16 in [0, 65536], "
+    "min_overlap >= 0, struct_bytes 0 or sizeof (use rsdsfm_plate_params_init)";
+
 }  // namespace rsdsfm
 
 using namespace rsdsfm;

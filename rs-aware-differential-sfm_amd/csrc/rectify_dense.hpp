@@ -28,6 +28,8 @@ struct DenseWs {
     int superres_scale = 0;              // the scale d_superres was made for
     unsigned char* d_plate = nullptr;    // the clean plate's reference planes, records and stack of layers (plate.hpp; made when first asked for)
     int plate_layers = 0;                // the layers d_plate holds
+    unsigned char* d_matte = nullptr;    // the mover matte's two intermediate planes (erase.hpp; made when first asked for)
+    unsigned char* d_erase = nullptr;    // the mover removal's plate mask, flag, matte and plate image, 6 planes (erase.hpp; made when first asked for)
     int rows = 0, cols = 0;
 };
 

@@ -31,6 +31,10 @@ static void dense_ws_free(DenseWs* w) {
     if (w->d_plate) (void)hipFree(w->d_plate);
     w->d_plate = nullptr;
     w->plate_layers = 0;
+    if (w->d_matte) (void)hipFree(w->d_matte);
+    w->d_matte = nullptr;
+    if (w->d_erase) (void)hipFree(w->d_erase);
+    w->d_erase = nullptr;
     w->d_pyr = nullptr;
     w->d_disp = nullptr;
     w->d_mask = nullptr;

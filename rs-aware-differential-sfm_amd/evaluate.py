@@ -209,7 +209,7 @@ def evaluate_real_sequence(solver, frames, camera="galaxy", gamma=0.95, out_dir=
                            check_flow=False, trajectory=False, link_tol=None, min_links=None, fuse=False, fuse_tol=None, stabilize=False, smooth_sigma=None,
                            smooth_translation=True, fill=0, crop=False, crop_margin=None, crop_max_empty=0, blend=False, blend_feather=None,
                            blend_gain=True, inpaint=False, last_frame=False, occlusion=False, occlusion_tol=None, occlusion_search=False, retime=None,
-                           shutter=None, denoise=None, superres=None, plate=None):
+                           shutter=None, denoise=None, superres=None, plate=None, erase=None):
     """evaluate_real_run's real-world branch (main.cc:341-361, 364-531) for a clip: `frames` is <prefix>frame1.png ... frameN.png (the
     prefix, or a list of paths), or the frames themselves (an (N, rows, cols[, 3]) uint8 array or a list of arrays; 2-D frames are gray).
     By default ONE call does the clip (Solver.rectify_video_dev): the batched DeepFlow of every consecutive pair, the pipelined solve of every pair p
@@ -307,7 +307,22 @@ def evaluate_real_sequence(solver, frames, camera="galaxy", gamma=0.95, out_dir=
     the fused maps with fuse=True, the neighbours through the occlusion test with occlusion=True): the returned dict also has plate,
     plate_moving (lists of frames; the flag is 0 unset, 1 static, 2 moving, 3 undecided) and plate_counts ((frames, 4) int64: [unset, static,
     moving, undecided]); out_dir receives plate_<p>.png, moving_<p>.png (255 where the flag is 2) and plate.csv.  Without the keyword every key
-    and file is what it was."""
+    and file is what it was.
+    erase=True, K or (K, open, grow, feather) (needs stabilize=True: ValueError otherwise): behind everything else, every stabilised frame once
+    more WITHOUT what moved through it -- the plate of the frame and its up to K neighbours on each side (True: the default, 2) under the cleaned,
+    grown and feathered matte of the plate's flag, the frame's own bytes everywhere else (Solver.erase_video_dev, tests/erase_spec_numpy.py; open,
+    grow, feather literal, default 2, 2, 4; the fused maps with fuse=True, the neighbours through the occlusion test with occlusion=True): the
+    returned dict also has erased, erase_matte (lists of frames; the matte is 0 .. feather) and erase_counts ((frames, 5) int64: [unset, kept,
+    replaced, feathered, unresolved]); out_dir receives erased_<p>.png, matte_<p>.png (the matte scaled to 0 .. 255) and erase.csv.  Without the
+    keyword every key and file is what it was."""
+    if erase is not None and erase is not False and not stabilize:
+        raise ValueError("erase needs stabilize=True: it takes the movers out of the frames of the stabilised clip")
+    if erase is False:
+        erase = None
+    if erase is not None:
+        er_radius, er_open, er_grow, er_feather = (None, None, None, None) if erase is True else (int(erase), None, None, None) if np.ndim(erase) == 0 else \
+            tuple(int(x) for x in erase)
+        erase_feather = er_feather or 4  # the matte's largest byte (None or 0: the default), for matte_<p>.png
     if plate is not None and not stabilize:
         raise ValueError("plate needs stabilize=True: it takes the median of the frames of the stabilised clip")
     if superres is not None and not stabilize:
@@ -644,6 +659,15 @@ def evaluate_real_sequence(solver, frames, camera="galaxy", gamma=0.95, out_dir=
                                                 st_scales, ptrs(d_pl), ptrs(d_plmasks), None, ptrs(d_plmov), radius=pl_radius, threshold=pl_threshold, occlusion=occlusion,
                                                 occlusion_tol_q16=occ_q16 if occlusion else 0, mode=mode)
                     traj.update(plate=[t.cpu().numpy() for t in d_pl], plate_moving=[t.cpu().numpy() for t in d_plmov], plate_counts=pl["counts"])
+                if erase is not None:  # every stabilised frame once more, without what moved through it
+                    d_er = [torch.empty_like(d_imgs[0]) for _ in range(nst)]
+                    d_ermasks = [torch.empty((rows, cols), dtype=torch.uint8, device=dev) for _ in range(nst)]
+                    d_ermatte = [torch.empty((rows, cols), dtype=torch.uint8, device=dev) for _ in range(nst)]
+                    torch.cuda.synchronize()
+                    er = solver.erase_video_dev(ptrs(d_imgs), rows, cols, channels, K, ptrs(d_src[:nst]), ptrs(d_Rs[:nst]), ptrs(d_ts[:nst]), traj["A"], traj["c"], A_s, c_s,
+                                                st_scales, ptrs(d_er), ptrs(d_ermasks), ptrs(d_ermatte), None, radius=er_radius, open=er_open, grow=er_grow, feather=er_feather,
+                                                occlusion=occlusion, occlusion_tol_q16=occ_q16 if occlusion else 0, mode=mode)
+                    traj.update(erased=[t.cpu().numpy() for t in d_er], erase_matte=[t.cpu().numpy() for t in d_ermatte], erase_counts=er["counts"])
     if out_dir:
         os.makedirs(out_dir, exist_ok=True)
         lines = ["pair,v_x,v_y,v_z,w_x,w_y,w_z,k,inliers"]
@@ -754,6 +778,14 @@ def evaluate_real_sequence(solver, frames, camera="galaxy", gamma=0.95, out_dir=
                 formats.write_png(os.path.join(out_dir, "moving_%d.png" % p), np.where(traj["plate_moving"][p] == 2, 255, 0).astype(np.uint8))
                 rows_.append(",".join([str(p)] + [str(int(x)) for x in traj["plate_counts"][p]]))
             with open(os.path.join(out_dir, "plate.csv"), "w") as fh:
+                fh.write("\n".join(rows_) + "\n")
+        if erase is not None:
+            rows_ = ["pair,unset,kept,replaced,feathered,unresolved"]
+            for p in range(nst):
+                formats.write_png(os.path.join(out_dir, "erased_%d.png" % p), traj["erased"][p])
+                formats.write_png(os.path.join(out_dir, "matte_%d.png" % p), (traj["erase_matte"][p].astype(np.int64) * 255 // erase_feather).astype(np.uint8))
+                rows_.append(",".join([str(p)] + [str(int(x)) for x in traj["erase_counts"][p]]))
+            with open(os.path.join(out_dir, "erase.csv"), "w") as fh:
                 fh.write("\n".join(rows_) + "\n")
         if inpaint:
             rows_ = ["pair,stage,inpainted"]
