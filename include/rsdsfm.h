@@ -15,8 +15,9 @@
  *
  * Two families:
  *   host-pointer API  (rsdsfm_xxx)      caller-owned HOST buffers, synchronous -- the reference's semantics.
- *   device API        (rsdsfm_xxx_dev)  caller-owned DEVICE buffers (16-byte aligned), asynchronous on the
- *                                       context's stream -- what bench.py and the multi-GPU driver use.
+ *   device API        (rsdsfm_xxx_dev)  caller-owned DEVICE buffers (aligned as "alignment of device pointers" below
+ *                                       says, per pointer), asynchronous on the context's stream -- what bench.py and
+ *                                       the multi-GPU driver use.
  */
 #ifndef RSDSFM_H
 #define RSDSFM_H
@@ -278,16 +279,30 @@ int rsdsfm_pose_table(rsdsfm_ctx* ctx, const double v[3], const double w[3], dou
                       int32_t rows, double* R_rows9, double* t_rows3);
 
 /* ---------------------------------------------------------------------------------------------------- */
-/* device API (asynchronous on the context's stream; pointers are DEVICE memory, 16-byte aligned)          */
+/* device API (asynchronous on the context's stream; pointers are DEVICE memory)                          */
 /* ---------------------------------------------------------------------------------------------------- */
+/* Alignment of device pointers.  Every device pointer of the entry points below has ONE alignment need, the width of the widest access a
+ * kernel makes through it; it is stated next to each entry point ("align:") and tabulated with the kernel line it comes from in DESIGN.md
+ * ("Alignment of the core device API").  The rules:
+ *   16 bytes  arrays the kernels move as double2: the flow image, q (2xN), u / flow (2xN), the true-flow output, and all five arrays of
+ *             the dense depth solve (q, u, alpha, alpha_k, inv_depth: pairs of points per lane, 16-byte LDS-DMA loads in depth variant 1);
+ *    8 bytes  every other array of doubles or int64 (alpha, alpha_k, inliers 3xM, inlier_idx, depth maps, pose tables, world maps);
+ *    4 bytes  arrays of float or int32 (world points, xs / ys, best_row) and the 8-bit BGR / gray IMAGES, which the rectifier moves four
+ *             pixels = whole dwords at a time (as include/rsdsfm_rectify_video.h says of its own);
+ *    none     the 8-bit depth image, the error image and the RANSAC's inlier mask: written byte by byte, any address.
+ * A pointer below its need is refused with RSDSFM_ERR_INVALID before anything is launched, allocated or enqueued; an optional pointer
+ * that is NULL has no need.  Device pointers the library returns (rsdsfm_frame_result) are 256-byte aligned. */
 /* estimateInverseDepths on device-resident inputs.  Enqueues the fixed fast-path launch sequence (in
  * RSDSFM_DEPTH_CERES_LM mode: speculative LM launch 0, the decide kernel, launch 1 = apply / continue / no-op)
- * and returns without synchronising. */
+ * and returns without synchronising.
+ * align: d_q2n, d_u2n, d_alpha_n, d_alpha_k_n, d_inv_depth_n 16 (here and in every rsdsfm_depth_* / *_batch_dev call that takes them). */
 int rsdsfm_estimate_inverse_depths_dev(rsdsfm_ctx* ctx, const double* d_q2n, const double* d_u2n, int64_t n,
                                        const double v[3], const double w[3], double k, const double* d_alpha_n,
                                        const double* d_alpha_k_n, int depth_mode, double* d_inv_depth_n);
 /* flatten / depth map / pose table on device-resident buffers (same semantics as the host-pointer variants; the
- * scalar results *n_out, v_inout, *flipped are returned after one synchronisation) */
+ * scalar results *n_out, v_inout, *flipped are returned after one synchronisation)
+ * align: flatten (and rsdsfm_flatten_slab_dev): d_flow_img, d_q2n, d_u2n 16; d_alpha_n, d_alpha_k_n 8.
+ *        depth map: d_inliers_3m_inout, d_depth_map_colmajor 8; d_xs, d_ys 4.   pose table: d_R_rows9, d_t_rows3 8. */
 int rsdsfm_flatten_dev(rsdsfm_ctx* ctx, const double* d_flow_img, int32_t rows, int32_t cols, double fx, double fy,
                        double cx, double cy, double gamma, double flow_threshold, double* d_q2n, double* d_u2n,
                        double* d_alpha_n, double* d_alpha_k_n, int64_t* n_out);
@@ -326,7 +341,7 @@ typedef struct rsdsfm_frame_result {
     double ransac_w[3], ransac_v[3], ransac_k;
     double w[3], v[3], k;            /* after refinement and sign canonicalisation                       */
     rsdsfm_lm_summary refine_summary;
-    const double* d_inliers;         /* DEVICE, 3 x num_inliers (x, y, z), valid until the next call on the context */
+    const double* d_inliers;         /* DEVICE, 3 x num_inliers (x, y, z), valid until the next call on the context; 256-byte aligned, as the two below */
     const int64_t* d_inlier_idx;     /* DEVICE                                                            */
     const int32_t* d_scanline;       /* DEVICE, scanline (image row) index of each inlier                 */
 } rsdsfm_frame_result;
@@ -335,7 +350,9 @@ typedef struct rsdsfm_frame_result {
  * per-scanline pose table (DEVICE, may be NULL).  Runs flatten (+ the global-shutter override of alpha), ransac,
  * nonLinearRefinement (flow indexed as params->flow_index_mode says), the sign flip / depth scatter and
  * setRelativePose back to back on the context's stream.  A zero-initialised rsdsfm_frame_params with the trial count,
- * tolerances and use_refinement set reproduces evaluateSingleRun's call sequence (main.cc:398-522). */
+ * tolerances and use_refinement set reproduces evaluateSingleRun's call sequence (main.cc:398-522).
+ * align: d_flow_img 16; d_depth_map_colmajor, d_R_rows9_or_null, d_t_rows3_or_null 8 (the same for every rsdsfm_frame_job; rsdsfm_solve_frames_dev
+ * checks all jobs before it enqueues the first). */
 int rsdsfm_solve_frame_dev(rsdsfm_ctx* ctx, const double* d_flow_img, int32_t rows, int32_t cols, double fx, double fy,
                            double cx, double cy, double gamma, const rsdsfm_frame_params* params,
                            double* d_depth_map_colmajor, double* d_R_rows9_or_null, double* d_t_rows3_or_null,
@@ -409,13 +426,16 @@ int rsdsfm_lma_predict_stats(rsdsfm_ctx* ctx, int64_t* hypotheses, int64_t* ende
 int rsdsfm_set_lma_operands(rsdsfm_ctx* ctx, int mode);
 /* minimal::ransac on device-resident inputs.  The arrays of `out` (inlier_idx, inliers, alpha, alpha_k, mask,
  * inv_depth) are DEVICE pointers with capacity n (each may be NULL); its trial_* arrays are HOST pointers.
- * samples_9xT_or_null is a HOST pointer.  Synchronises once at the end to return the scalars of `out`. */
+ * samples_9xT_or_null is a HOST pointer.  Synchronises once at the end to return the scalars of `out`.  A NULL `out` is refused with
+ * RSDSFM_ERR_INVALID, as a NULL input array is.
+ * align: d_q2n, d_u2n 16; d_alpha_n, d_alpha_k_n and out->inlier_idx, inliers, alpha, alpha_k, inv_depth 8; out->mask none. */
 int rsdsfm_ransac_dev(rsdsfm_ctx* ctx, const double* d_q2n, const double* d_u2n, const double* d_alpha_n,
                       const double* d_alpha_k_n, int64_t n, int use_alpha_k, int32_t iterations, double tolerance,
                       const int32_t* samples_9xT_or_null, uint64_t seed, int depth_mode, int k_sign_mode,
                       rsdsfm_ransac_out* out);
 /* nonLinearRefinement on device-resident inputs (d_inlier_idx may be NULL in compat mode).  v/w/k and the
- * summary are HOST.  Polls the device-resident termination flag every few LM iterations. */
+ * summary are HOST.  Polls the device-resident termination flag every few LM iterations.
+ * align: d_flow2n 16; d_inliers_3m, d_alpha_m, d_alpha_k_m, d_inlier_idx_or_null, d_inliers_out_3m 8. */
 int rsdsfm_refine_dev(rsdsfm_ctx* ctx, const double* d_flow2n, int64_t n_flow, int64_t m, const double* d_inliers_3m,
                       const double* d_alpha_m, const double* d_alpha_k_m, const int64_t* d_inlier_idx_or_null,
                       const double v_in[3], const double w_in[3], double k_in, int const_acceleration,
@@ -634,6 +654,7 @@ int rsdsfm_estimate_inverse_depths_tiled_dev(rsdsfm_ctx* ctx, const double* d_q_
 int rsdsfm_back_project(rsdsfm_ctx* ctx, const uint8_t* image_bgr, const double* depth_map_colmajor, const double* R_rows9,
                         const double* t_rows3, double fx, double fy, double cx, double cy, int32_t rows, int32_t cols,
                         int mode, int q5_mode, uint8_t* gs_image_bgr, float* coords3d_or_null);
+/* align: d_image_bgr, d_gs_image_bgr, d_coords3d_or_null 4; d_depth_map_colmajor, d_R_rows9, d_t_rows3 8 */
 int rsdsfm_back_project_dev(rsdsfm_ctx* ctx, const uint8_t* d_image_bgr, const double* d_depth_map_colmajor,
                             const double* d_R_rows9, const double* d_t_rows3, double fx, double fy, double cx, double cy,
                             int32_t rows, int32_t cols, int mode, int q5_mode, uint8_t* d_gs_image_bgr,
@@ -641,19 +662,23 @@ int rsdsfm_back_project_dev(rsdsfm_ctx* ctx, const uint8_t* d_image_bgr, const d
 /* Camera::interpolateCrackyImage (camera.cc:753-774; main.cc:523 calls it with offset 1).  in and out must not alias. */
 int rsdsfm_interpolate_cracky(rsdsfm_ctx* ctx, const uint8_t* image_in_bgr, int32_t rows, int32_t cols, int32_t offset,
                               uint8_t* image_out_bgr);
+/* align: d_image_in_bgr, d_image_out_bgr 4 */
 int rsdsfm_interpolate_cracky_dev(rsdsfm_ctx* ctx, const uint8_t* d_image_in_bgr, int32_t rows, int32_t cols, int32_t offset,
                                   uint8_t* d_image_out_bgr);
 /* the 8-bit depth image of evaluateSingleRun (main.cc:480-509): depth_est(y, x) = 10 + int((z - z_min) * 244 /
  * (z_max - z_min)), row-major rows x cols, 0 where no inlier lands; inliers = 3 x m (x, y, z) AFTER the sign fix. */
 int rsdsfm_depth_preview(rsdsfm_ctx* ctx, const double* inliers3m, int64_t m, double fx, double fy, double cx, double cy,
                          int32_t rows, int32_t cols, uint8_t* depth_est);
+/* align: d_inliers3m 8; d_depth_est none */
 int rsdsfm_depth_preview_dev(rsdsfm_ctx* ctx, const double* d_inliers3m, int64_t m, double fx, double fy, double cx, double cy,
                              int32_t rows, int32_t cols, uint8_t* d_depth_est);
 /* main.cc:480-523 in ONE call on device buffers: the 8-bit depth image (rsdsfm_depth_preview_dev), the back projection
  * (rsdsfm_back_project_dev) and the crack interpolation of its result (rsdsfm_interpolate_cracky_dev) -- the same kernels' code and
  * the same bytes, in two launches instead of five: the two claim passes share a launch, and the write pass of the back projection forms
  * the interpolated image from its own tile + halo next to the depth image's write pass (offset <= 2 and cols % 4 == 0; three launches
- * otherwise) -- each of the five is short enough for the launch floor to show.  d_gs_image_bgr and d_fixed_image_bgr must not alias. */
+ * otherwise) -- each of the five is short enough for the launch floor to show.  d_gs_image_bgr and d_fixed_image_bgr must not alias.
+ * align: d_image_bgr, d_gs_image_bgr, d_fixed_image_bgr, d_coords3d_or_null 4; d_inliers3m, d_depth_map_colmajor, d_R_rows9, d_t_rows3 8;
+ * d_depth_est none. */
 int rsdsfm_rectify_frame_dev(rsdsfm_ctx* ctx, const double* d_inliers3m, int64_t m, const uint8_t* d_image_bgr,
                              const double* d_depth_map_colmajor, const double* d_R_rows9, const double* d_t_rows3, double fx, double fy,
                              double cx, double cy, int32_t rows, int32_t cols, int mode, int q5_mode, int32_t offset, uint8_t* d_depth_est,
@@ -668,7 +693,8 @@ int rsdsfm_rectify_frame_dev(rsdsfm_ctx* ctx, const double* d_inliers3m, int64_t
  * The search is exact: by default scanlines are visited in blocks of 32 and a block is skipped only when interval arithmetic over its
  * pose entries proves that none of its scanlines can reach the best |y - i| found so far (winners and flows bit-identical to
  * visiting every scanline).  rsdsfm_set_true_flow_search: 0 = automatic (pruned from 96 scanlines on; default), 1 = the exhaustive
- * loop (the reference's own), 2 = pruned at any size. */
+ * loop (the reference's own), 2 = pruned at any size.
+ * align (rsdsfm_true_flow_dev): d_flow 16; d_world_x / y / z, d_R2_rows9, d_t2_rows3 8; d_best_row_or_null 4. */
 int rsdsfm_set_true_flow_search(rsdsfm_ctx* ctx, int mode);
 int rsdsfm_true_flow(rsdsfm_ctx* ctx, const double* world_x, const double* world_y, const double* world_z, int32_t rows,
                      int32_t cols, const double* R2_rows9, const double* t2_rows3, int32_t rows2, double fx, double fy,
@@ -696,7 +722,9 @@ typedef struct rsdsfm_reprojection_stats {
  * (camera.cc:503-591; error_image(y, x) = (char)int(error * 255 / max_norm + 0.5), rows x cols bytes row-major).
  * est_coords: rows x cols x 3 floats (what rsdsfm_back_project writes); gt_depth / est_depth: column-major rows x cols
  * (a ground-truth depth of exactly 0 falls back to the estimated depth, the reference's planeToSpace default argument,
- * rsframe.cc:657); R_abs / t_abs: ABSOLUTE pose of every scanline after RsFrame::relocatePose.  Synchronises. */
+ * rsframe.cc:657); R_abs / t_abs: ABSOLUTE pose of every scanline after RsFrame::relocatePose.  Synchronises.
+ * align (rsdsfm_reprojection_error_dev): d_est_coords 4; d_gt_depth_colmajor, d_est_depth_colmajor, d_R_abs_rows9, d_t_abs_rows3 8;
+ * d_error_image_or_null none. */
 int rsdsfm_reprojection_error(rsdsfm_ctx* ctx, const float* est_coords, const double* gt_depth_colmajor,
                               const double* est_depth_colmajor, const double* R_abs_rows9, const double* t_abs_rows3, double fx,
                               double fy, double cx, double cy, int32_t rows, int32_t cols, double max_norm,

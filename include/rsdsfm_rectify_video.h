@@ -10,7 +10,8 @@
  * depend on the channel count.  DESIGN.md section 12 ("Sequences") has the measured times.
  *
  * Alignment: the kernels store four pixels as packed 32-bit words, so every image buffer (frames, global-shutter and interpolated
- * images, BGR or gray) must be 4-byte aligned, as rsdsfm_rectify_frame_dev's; depth images may have any alignment.
+ * images, BGR or gray) and the world points must be 4-byte aligned, as rsdsfm_rectify_frame_dev's; depth images may have any alignment.
+ * Less is refused with RSDSFM_ERR_INVALID before anything is enqueued (include/rsdsfm.h, "Alignment of device pointers").
  */
 #ifndef RSDSFM_RECTIFY_VIDEO_H
 #define RSDSFM_RECTIFY_VIDEO_H

@@ -437,6 +437,7 @@ int rsdsfm_estimate_inverse_depths_dev(rsdsfm_ctx* ctx, const double* d_q, const
     CTX_OR_FAIL(ctx);
     if (n < 0 || !v || !w) return fail(c, RSDSFM_ERR_INVALID, "bad arguments");
     if (n > 0 && (!d_q || !d_u || !d_alpha || !d_alpha_k || !d_rho)) return fail(c, RSDSFM_ERR_INVALID, "null device pointer");
+    if (!aligned_to(16, d_q, d_u, d_alpha, d_alpha_k, d_rho)) return fail(c, RSDSFM_ERR_INVALID, "device pointers must be 16-byte aligned");  // the depth kernels move all five as double2
     Pose pose;
     memcpy(pose.v, v, sizeof(pose.v));
     memcpy(pose.w, w, sizeof(pose.w));
@@ -496,6 +497,7 @@ static int depth_batch_common(rsdsfm_ctx* const* ctxs, int32_t count, const doub
         for (int j = 0; j < i; ++j)
             if (cs[j] == cs[i]) return fail(c, RSDSFM_ERR_INVALID, "a context may appear only once in a batch (it owns the solve's state)");
         if (n[i] < 0 || (n[i] > 0 && (!d_q[i] || !d_u[i] || !d_alpha[i] || !d_alpha_k[i] || !d_rho[i]))) return fail(c, RSDSFM_ERR_INVALID, "bad problem in the batch");
+        if (!aligned_to(16, d_q[i], d_u[i], d_alpha[i], d_alpha_k[i], d_rho[i])) return fail(c, RSDSFM_ERR_INVALID, "device pointers must be 16-byte aligned");
         memcpy(poses[i].v, v3 + 3 * i, sizeof(poses[i].v));
         memcpy(poses[i].w, w3 + 3 * i, sizeof(poses[i].w));
         poses[i].k = k[i];
@@ -530,6 +532,7 @@ int rsdsfm_depth_lm_launch_dev(rsdsfm_ctx* ctx, const double* d_q, const double*
     CTX_OR_FAIL(ctx);
     if (n < 0 || !v || !w || launch_id < 0) return fail(c, RSDSFM_ERR_INVALID, "bad arguments");
     if (n > 0 && (!d_q || !d_u || !d_alpha || !d_alpha_k || !d_rho)) return fail(c, RSDSFM_ERR_INVALID, "null device pointer");
+    if (!aligned_to(16, d_q, d_u, d_alpha, d_alpha_k, d_rho)) return fail(c, RSDSFM_ERR_INVALID, "device pointers must be 16-byte aligned");  // the depth kernels move all five as double2
     Pose pose;
     memcpy(pose.v, v, sizeof(pose.v));
     memcpy(pose.w, w, sizeof(pose.w));
@@ -570,6 +573,7 @@ int rsdsfm_depth_finish_dev(rsdsfm_ctx* ctx, const double* d_q, const double* d_
                             double* d_rho, rsdsfm_lm_summary* summary, int32_t* extra_launches) {
     CTX_OR_FAIL(ctx);
     if (!v || !w) return fail(c, RSDSFM_ERR_INVALID, "bad arguments");
+    if (!aligned_to(16, d_q, d_u, d_alpha, d_alpha_k, d_rho)) return fail(c, RSDSFM_ERR_INVALID, "device pointers must be 16-byte aligned");  // the depth kernels move all five as double2
     Pose pose;
     memcpy(pose.v, v, sizeof(pose.v));
     memcpy(pose.w, w, sizeof(pose.w));

@@ -750,12 +750,10 @@ static inline int depth_grid(int64_t n, int max_blocks) {
     return (int)blocks;
 }
 
-static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
 int depth_closed_form_launch(Ctx* c, const double* q, const double* u, const double* a, const double* ak,
                              int64_t n, const Pose& pose, double* rho) {
     if (n == 0) return RSDSFM_OK;
-    if (!aligned16(q) || !aligned16(u) || !aligned16(a) || !aligned16(ak) || !aligned16(rho))
+    if (!aligned_to(16, q, u, a, ak, rho))
         return fail(c, RSDSFM_ERR_INVALID, "device pointers must be 16-byte aligned");
     const int grid = depth_grid(n, 2048);
     hipLaunchKernelGGL(depth_closed_form_kernel, dim3(grid), dim3(kDepthBlock), 0, c->stream,
@@ -785,7 +783,7 @@ static inline bool depth_use_cores(const Ctx* c) { return !RSDSFM_FUSED && c->ra
 
 int depth_lm_launch(Ctx* c, const double* q, const double* u, const double* a, const double* ak, int64_t n,
                     const Pose& pose, double* rho, int launch_id, bool core) {
-    if (!aligned16(q) || !aligned16(u) || !aligned16(a) || !aligned16(ak) || !aligned16(rho))
+    if (!aligned_to(16, q, u, a, ak, rho))
         return fail(c, RSDSFM_ERR_INVALID, "device pointers must be 16-byte aligned");
     const int grid = depth_lm_grid(c, n);
     const double2 *q2 = reinterpret_cast<const double2*>(q), *u2 = reinterpret_cast<const double2*>(u),
@@ -871,7 +869,7 @@ int depth_lm_batch_launch(Ctx* const* cs, int count, const double* const* q, con
         for (int i = 0; i < count; ++i)
             if (cs[i]->depth_standard_math > 0) cs[i]->depth_standard_math -= 1;  // (one more solve on the standard functions behind a restart)
     for (int i = 0; i < count; ++i) {
-        if (!aligned16(q[i]) || !aligned16(u[i]) || !aligned16(a[i]) || !aligned16(ak[i]) || !aligned16(rho[i]))
+        if (!aligned_to(16, q[i], u[i], a[i], ak[i], rho[i]))
             return fail(c0, RSDSFM_ERR_INVALID, "device pointers must be 16-byte aligned");
         DepthBatchItem& it = args.item[i];
         it.q = reinterpret_cast<const double2*>(q[i]);
@@ -909,7 +907,7 @@ int depth_lm_batch_launch(Ctx* const* cs, int count, const double* const* q, con
 
 int depth_lm_fused_launch(Ctx* c, const double* q, const double* u, const double* a, const double* ak, int64_t n,
                           const Pose& pose, double* rho) {
-    if (!aligned16(q) || !aligned16(u) || !aligned16(a) || !aligned16(ak) || !aligned16(rho))
+    if (!aligned_to(16, q, u, a, ak, rho))
         return fail(c, RSDSFM_ERR_INVALID, "device pointers must be 16-byte aligned");
     const int grid = depth_lm_grid(c, n);
     hipLaunchKernelGGL(depth_lm_fused_kernel, dim3(grid), dim3(kDepthBlock), 0, c->stream, reinterpret_cast<const double2*>(q),

@@ -264,8 +264,6 @@ constexpr int kDepthLmaUnroll = 2;
 constexpr int kDepthLmaApplyGrid = 32;
 static_assert(kDepthLmaBlocks <= kDepthMaxBlocks && kLmaSlots <= NS, "partial rows fit the context's partial buffer");
 
-static inline bool aligned16p(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 // may this context's next dense depth solve take the analytic fast path?
 // (no hold behind a guard, unlike the RANSAC: there both arithmetics return the same bits in everything but diagnostics; here rho itself differs
 // in its last digits between them, and a result must not depend on what the context solved before -- every solve tries the analytic path and a
@@ -274,7 +272,7 @@ bool depth_lma_allowed(const Ctx* c, int64_t n) { return c->lm_arithmetic == 0 &
 
 static int depth_lma_item(Ctx* c0, Ctx* c, const double* q, const double* u, const double* a, const double* ak, int64_t n, const Pose& pose, double* rho,
                           bool new_solve, DepthLmaItem& it) {
-    if (!aligned16p(q) || !aligned16p(u) || !aligned16p(a) || !aligned16p(ak) || !aligned16p(rho)) return fail(c0, RSDSFM_ERR_INVALID, "device pointers must be 16-byte aligned");
+    if (!aligned_to(16, q, u, a, ak, rho)) return fail(c0, RSDSFM_ERR_INVALID, "device pointers must be 16-byte aligned");
     if (!c->d_lma_list) {
         const size_t bytes = sizeof(int) * (2 + 2 * (size_t)kLmaListCap);
         RSDSFM_HIP_CHECK(c0, hipMalloc(reinterpret_cast<void**>(&c->d_lma_list), bytes));

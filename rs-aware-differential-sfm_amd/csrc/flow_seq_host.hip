@@ -63,6 +63,12 @@ int solve_video_run(rsdsfm_ctx* ctx, const uint8_t* const* d_frames, int32_t nfr
     if (!all_set(d_frames, nframes) || !all_set(d_depth_maps, np) || (d_flows_or_null && !all_set(d_flows_or_null, np)) ||
         (d_R_or_null && !all_set(d_R_or_null, np)) || (d_t_or_null && !all_set(d_t_or_null, np)))
         return fail(c, RSDSFM_ERR_INVALID, "solve video: null device pointer");
+    // what becomes a pair's rsdsfm_frame_job (frame_host.hip: frame_begin holds every job to this) is checked for the whole clip before the
+    // first batch's flow is enqueued
+    for (int q = 0; q < np; ++q)
+        if (!aligned_to(16, d_flows_or_null ? d_flows_or_null[q] : nullptr) ||
+            !aligned_to(8, d_depth_maps[q], d_R_or_null ? d_R_or_null[q] : nullptr, d_t_or_null ? d_t_or_null[q] : nullptr))
+            return fail(c, RSDSFM_ERR_INVALID, "solve video: the flow fields must be 16-byte aligned, the depth maps and the pose tables 8-byte aligned");
     FlowWs* w = nullptr;
     rc = clip_ws(c, rows, cols, p, &w);
     if (rc == RSDSFM_OK && !d_flows_or_null) rc = ensure_ring(c, w);

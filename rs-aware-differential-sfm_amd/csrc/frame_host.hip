@@ -101,6 +101,13 @@ struct FrameInFlightEnd {
     ~FrameInFlightEnd() { frame_uncount(c, F); }
 };
 
+// the caller's pointers of a frame job: the flatten (in the minimal solver's launch or in front of it) reads the flow image as double2, the
+// depth map and the pose table are written as doubles
+static int frame_job_check_aligned(Ctx* c, const rsdsfm_frame_job& J) {
+    if (aligned_to(16, J.d_flow_img) && aligned_to(8, J.d_depth_map_colmajor, J.d_R_rows9_or_null, J.d_t_rows3_or_null)) return RSDSFM_OK;
+    return fail(c, RSDSFM_ERR_INVALID, "frame solve: the flow image must be 16-byte aligned, the depth map and the pose table 8-byte aligned");
+}
+
 int frame_begin(Ctx* c, FrameRun* F) {
     const rsdsfm_frame_job& J = F->job;
     const rsdsfm_frame_params* prm = &F->prm;
@@ -108,6 +115,7 @@ int frame_begin(Ctx* c, FrameRun* F) {
     F->open = false;
     F->rc_begin = RSDSFM_OK;
     if (J.rows <= 0 || J.cols <= 0 || !J.d_flow_img || !J.d_depth_map_colmajor) return fail(c, RSDSFM_ERR_INVALID, "bad arguments");
+    if (frame_job_check_aligned(c, J) != RSDSFM_OK) return RSDSFM_ERR_INVALID;
     if (prm->flow_index_mode != RSDSFM_FLOW_COMPAT_RANK && prm->flow_index_mode != RSDSFM_FLOW_GATHERED) return fail(c, RSDSFM_ERR_INVALID, "unknown flow_index_mode");
     if (prm->struct_bytes != 0 && prm->struct_bytes != (int32_t)sizeof(rsdsfm_frame_params))
         return fail(c, RSDSFM_ERR_INVALID, "rsdsfm_frame_params: struct_bytes is neither 0 nor sizeof(rsdsfm_frame_params) -- caller built against another header (use rsdsfm_frame_params_init)");
@@ -598,6 +606,8 @@ int rsdsfm_solve_frames_dev(rsdsfm_ctx* ctx, const rsdsfm_frame_job* jobs, int32
     DeviceGuard device_guard_(c);
     if (count < 0 || !prm || (count > 0 && (!jobs || !results))) return fail(c, RSDSFM_ERR_INVALID, "bad arguments");
     if (count == 0) return RSDSFM_OK;
+    for (int32_t i = 0; i < count; ++i)  // every job, before the first pair is enqueued (frame_begin would refuse pair i behind pairs 0 .. i - 1)
+        if (frame_job_check_aligned(c, jobs[i]) != RSDSFM_OK) return RSDSFM_ERR_INVALID;
     return solve_frames_run(c, jobs, count, prm, results, nullptr);
 }
 

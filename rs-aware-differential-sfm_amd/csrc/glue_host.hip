@@ -6,8 +6,16 @@
 
 using namespace rsdsfm;
 
-// flatten of a column slab: d_img is the row-major [rows][cols] slab whose first column is image column col0
 namespace rsdsfm {
+// the device pointers of both flatten drivers below: all set; flatten_tile_kernel moves the image, q and u as double2
+static int flatten_args_check(Ctx* c, const double* d_img, const double* d_q, const double* d_u, const double* d_alpha, const double* d_alpha_k) {
+    if (!d_img || !d_q || !d_u || !d_alpha || !d_alpha_k) return fail(c, RSDSFM_ERR_INVALID, "null device pointer");
+    if (!aligned_to(16, d_img, d_q, d_u) || !aligned_to(8, d_alpha, d_alpha_k))
+        return fail(c, RSDSFM_ERR_INVALID, "flatten: the flow image, q and u must be 16-byte aligned, alpha and alpha_k 8-byte aligned");
+    return RSDSFM_OK;
+}
+
+// flatten of a column slab: d_img is the row-major [rows][cols] slab whose first column is image column col0
 int flatten_device(Ctx* c, const double* d_img, int32_t rows, int32_t cols, int32_t col0, double fx, double fy, double cx,
                           double cy, double gamma, double thr, double* d_q, double* d_u, double* d_alpha, double* d_alpha_k,
                           int64_t* n_out) {
@@ -17,7 +25,8 @@ int flatten_device(Ctx* c, const double* d_img, int32_t rows, int32_t cols, int3
         *n_out = 0;
         return RSDSFM_OK;
     }
-    if (!d_img || !d_q || !d_u || !d_alpha || !d_alpha_k) return fail(c, RSDSFM_ERR_INVALID, "null device pointer");
+    const int rc_args = flatten_args_check(c, d_img, d_q, d_u, d_alpha, d_alpha_k);
+    if (rc_args != RSDSFM_OK) return rc_args;
     const size_t ncells = (size_t)flatten_cells(rows, cols);
     int rc = ensure_ws(c, 2 * Arena::need(sizeof(int64_t) * ncells) + Arena::need(64) + 1024);
     if (rc != RSDSFM_OK) return rc;
@@ -47,7 +56,8 @@ namespace rsdsfm {
 int flatten_enqueue(Ctx* c, const double* d_img, int32_t rows, int32_t cols, double fx, double fy, double cx, double cy, double gamma,
                     double thr, double* d_q, double* d_u, double* d_alpha, double* d_alpha_k, int64_t* h_total) {
     if (rows <= 0 || cols <= 0 || !h_total) return fail(c, RSDSFM_ERR_INVALID, "bad arguments");
-    if (!d_img || !d_q || !d_u || !d_alpha || !d_alpha_k) return fail(c, RSDSFM_ERR_INVALID, "null device pointer");
+    const int rc_args = flatten_args_check(c, d_img, d_q, d_u, d_alpha, d_alpha_k);
+    if (rc_args != RSDSFM_OK) return rc_args;
     const size_t ncells = (size_t)flatten_cells(rows, cols);
     int rc = ensure_ws(c, 2 * Arena::need(sizeof(int64_t) * ncells) + Arena::need(64) + 1024);
     if (rc != RSDSFM_OK) return rc;
@@ -130,6 +140,8 @@ int depth_map_device(Ctx* c, double* d_inl, int64_t m, double v_inout[3], double
     if (m < 0 || rows < 0 || cols < 0 || !v_inout) return fail(c, RSDSFM_ERR_INVALID, "bad arguments");
     const size_t npix = (size_t)rows * (size_t)cols;
     if ((m > 0 && !d_inl) || (npix > 0 && !d_depth_map)) return fail(c, RSDSFM_ERR_INVALID, "null device pointer");
+    if (!aligned_to(8, d_inl, d_depth_map, d_R_rows9, d_t_rows3) || !aligned_to(4, d_xs, d_ys))
+        return fail(c, RSDSFM_ERR_INVALID, "depth map: the inliers, the map and the pose table must be 8-byte aligned, xs and ys 4-byte aligned");
     int rc = ensure_ws(c, Arena::need(64) + Arena::need(8 * 1024) + 1024);
     if (rc != RSDSFM_OK) return rc;
     rc = ensure_pinned(c, 64);
@@ -190,6 +202,7 @@ int rsdsfm_pose_table_dev(rsdsfm_ctx* ctx, const double v[3], const double w[3],
     Ctx* c = &ctx->c;
     DeviceGuard device_guard_(c);
     if (rows < 0 || !v || !w || (rows > 0 && (!d_R || !d_t))) return fail(c, RSDSFM_ERR_INVALID, "bad arguments");
+    if (!aligned_to(8, d_R, d_t)) return fail(c, RSDSFM_ERR_INVALID, "pose table: R and t must be 8-byte aligned");
     Pose pose;
     memcpy(pose.v, v, sizeof(pose.v));
     memcpy(pose.w, w, sizeof(pose.w));

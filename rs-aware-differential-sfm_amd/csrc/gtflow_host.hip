@@ -23,6 +23,8 @@ int rsdsfm_true_flow_dev(rsdsfm_ctx* ctx, const double* d_world_x, const double*
     if ((int64_t)rows * cols == 0) return RSDSFM_OK;
     if (rows2 < 1) return fail(c, RSDSFM_ERR_INVALID, "frame 2 needs at least one scanline");
     if (!d_world_x || !d_world_y || !d_world_z || !d_flow || !d_R2_rows9 || !d_t2_rows3) return fail(c, RSDSFM_ERR_INVALID, "null device pointer");
+    if (!aligned_to(16, d_flow) || !aligned_to(8, d_world_x, d_world_y, d_world_z, d_R2_rows9, d_t2_rows3) || !aligned_to(4, d_best_row_or_null))  // the flow is stored as double2
+        return fail(c, RSDSFM_ERR_INVALID, "true flow: the flow must be 16-byte aligned, the world maps and the pose table 8-byte aligned, best_row 4-byte aligned");
     return true_flow_launch(c, d_world_x, d_world_y, d_world_z, rows, cols, d_R2_rows9, d_t2_rows3, rows2, fx, fy, cx, cy, q5_mode, d_flow,
                             d_best_row_or_null);
 }

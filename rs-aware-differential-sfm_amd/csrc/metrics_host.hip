@@ -50,6 +50,8 @@ int rsdsfm_reprojection_error_dev(rsdsfm_ctx* ctx, const float* d_est_coords, co
         return RSDSFM_OK;
     }
     if (!d_est_coords || !d_gt_depth || !d_est_depth || !d_R_abs_rows9 || !d_t_abs_rows3) return fail(c, RSDSFM_ERR_INVALID, "null device pointer");
+    if (!aligned_to(4, d_est_coords) || !aligned_to(8, d_gt_depth, d_est_depth, d_R_abs_rows9, d_t_abs_rows3))  // (the error image: any address)
+        return fail(c, RSDSFM_ERR_INVALID, "reprojection error: the points must be 4-byte aligned, the depth maps and the pose table 8-byte aligned");
     const size_t G = (size_t)metrics_blocks_max();
     int rc = ensure_ws(c, Arena::need(8 * 3 * G) + 1024);
     if (rc != RSDSFM_OK) return rc;

@@ -605,6 +605,10 @@ int rsdsfm_ransac_dev(rsdsfm_ctx* ctx, const double* d_q, const double* d_u, con
     Ctx* c = &ctx->c;
     DeviceGuard device_guard_(c);
     if (!d_q || !d_u || !d_alpha || !d_alpha_k) return fail(c, RSDSFM_ERR_INVALID, "null device pointer");
+    if (!out) return fail(c, RSDSFM_ERR_INVALID, "null out");
+    // every kernel of the RANSAC reads q and u as double2; its output arrays are plain doubles / int64 (the mask: bytes, any address)
+    if (!aligned_to(16, d_q, d_u) || !aligned_to(8, d_alpha, d_alpha_k, out->inlier_idx, out->inliers, out->alpha, out->alpha_k, out->inv_depth))
+        return fail(c, RSDSFM_ERR_INVALID, "ransac: q and u must be 16-byte aligned, alpha, alpha_k and the output arrays 8-byte aligned");
     return ransac_device(c, d_q, d_u, d_alpha, d_alpha_k, n, use_alpha_k, iterations, tolerance, samples, seed, depth_mode, k_sign_mode, out,
                          nullptr, nullptr);
 }

@@ -23,6 +23,9 @@ static int rectify_frame_checked(rsdsfm_ctx* ctx, bool gray, const double* d_inl
     if ((int64_t)rows * cols == 0) return RSDSFM_OK;
     if ((m > 0 && !d_inl) || !d_image || !d_depth_map || !d_R_rows9 || !d_t_rows3 || !d_depth_est || !d_gs_image || !d_fixed_image || d_gs_image == d_fixed_image)
         return fail(c, RSDSFM_ERR_INVALID, "null or aliased device pointer");
+    // the write and interpolation passes move the images as dwords (rectify_kernels.hip); the 8-bit depth image is written byte by byte
+    if (!aligned_to(4, d_image, d_gs_image, d_fixed_image, d_coords3d_or_null) || !aligned_to(8, d_inl, d_depth_map, d_R_rows9, d_t_rows3))
+        return fail(c, RSDSFM_ERR_INVALID, "rectify frame: the images and the world points must be 4-byte aligned, the inliers, the depth map and the pose table 8-byte aligned");
     int rc = ensure_ws(c, Arena::need(8 * 2048) + 1024);
     if (rc != RSDSFM_OK) return rc;
     return (gray ? rectify_gray_frame_launch : rectify_frame_launch)(c, d_inl, m, d_image, d_depth_map, d_R_rows9, d_t_rows3, fx, fy, cx, cy, rows, cols, mode, q5_mode,
@@ -43,6 +46,8 @@ int rsdsfm_back_project_dev(rsdsfm_ctx* ctx, const uint8_t* d_image_bgr, const d
     const size_t npix = (size_t)rows * (size_t)cols;
     if (npix == 0) return RSDSFM_OK;
     if (!d_image_bgr || !d_depth_map || !d_R_rows9 || !d_t_rows3 || !d_gs_image_bgr) return fail(c, RSDSFM_ERR_INVALID, "null device pointer");
+    if (!aligned_to(4, d_image_bgr, d_gs_image_bgr, d_coords3d_or_null) || !aligned_to(8, d_depth_map, d_R_rows9, d_t_rows3))
+        return fail(c, RSDSFM_ERR_INVALID, "back projection: the images and the world points must be 4-byte aligned, the depth map and the pose table 8-byte aligned");
     return back_project_launch(c, d_image_bgr, d_depth_map, d_R_rows9, d_t_rows3, fx, fy, cx, cy, rows, cols, mode, q5_mode,
                                d_gs_image_bgr, d_coords3d_or_null);
 }
@@ -87,6 +92,7 @@ int rsdsfm_interpolate_cracky_dev(rsdsfm_ctx* ctx, const uint8_t* d_image_in_bgr
     if (rows < 0 || cols < 0 || offset < 0) return fail(c, RSDSFM_ERR_INVALID, "bad arguments");
     if ((int64_t)rows * cols == 0) return RSDSFM_OK;
     if (!d_image_in_bgr || !d_image_out_bgr || d_image_in_bgr == d_image_out_bgr) return fail(c, RSDSFM_ERR_INVALID, "null or aliased device pointer");
+    if (!aligned_to(4, d_image_in_bgr, d_image_out_bgr)) return fail(c, RSDSFM_ERR_INVALID, "crack interpolation: both images must be 4-byte aligned");
     return interpolate_cracky_launch(c, d_image_in_bgr, rows, cols, offset, d_image_out_bgr);
 }
 
@@ -121,6 +127,7 @@ int rsdsfm_depth_preview_dev(rsdsfm_ctx* ctx, const double* d_inl, int64_t m, do
     const size_t npix = (size_t)rows * (size_t)cols;
     if (npix == 0) return RSDSFM_OK;
     if ((m > 0 && !d_inl) || !d_depth_est) return fail(c, RSDSFM_ERR_INVALID, "null device pointer");
+    if (!aligned_to(8, d_inl)) return fail(c, RSDSFM_ERR_INVALID, "depth image: the inliers must be 8-byte aligned");  // (the image itself: any address)
     int rc = ensure_ws(c, Arena::need(8 * 2048) + 1024);
     if (rc != RSDSFM_OK) return rc;
     return depth_preview_launch(c, d_inl, m, fx, fy, cx, cy, rows, cols, d_depth_est, static_cast<double*>(c->d_ws));

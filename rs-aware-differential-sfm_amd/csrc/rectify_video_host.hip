@@ -30,6 +30,9 @@ int rsdsfm_rectify_video_dev(rsdsfm_ctx* ctx, const uint8_t* const* d_frames, in
         return fail(c, RSDSFM_ERR_INVALID, "rectify video: null device pointer");
     for (int p = 0; p < np; ++p)
         if (d_gs_images[p] == d_fixed_images[p]) return fail(c, RSDSFM_ERR_INVALID, "rectify video: a pair's two output images are one buffer");
+    for (int p = 0; p < np; ++p)  // as rsdsfm_rectify_frame_dev (the depth images: any address; the solve's own buffers: solve_video_run)
+        if (!aligned_to(4, d_gs_images[p], d_fixed_images[p], d_coords3d_or_null ? d_coords3d_or_null[p] : nullptr) || (d_frames && !aligned_to(4, d_frames[p], d_frames[p + 1])))
+            return fail(c, RSDSFM_ERR_INVALID, "rectify video: every image buffer and the world points must be 4-byte aligned");
     const PairHook rectify = [&](Ctx* lane, int p, const rsdsfm_frame_job& job, const rsdsfm_frame_result& r) -> int {
         int rc = ensure_ws(lane, Arena::need(8 * 2048) + 1024);
         if (rc != RSDSFM_OK) return rc;

@@ -285,6 +285,9 @@ int rsdsfm_refine_dev(rsdsfm_ctx* ctx, const double* d_flow, int64_t n_flow, int
                       rsdsfm_lm_summary* summary) {
     if (!ctx) return RSDSFM_ERR_INVALID;
     DeviceGuard device_guard_(&ctx->c);
+    // refine_init_kernel and the radius-factorised first pass read the flow as double2; everything else is plain doubles / int64
+    if (!aligned_to(16, d_flow) || !aligned_to(8, d_inl, d_alpha, d_alpha_k, d_inlier_idx, d_inl_out))
+        return fail(&ctx->c, RSDSFM_ERR_INVALID, "refine: the flow must be 16-byte aligned, the inlier arrays 8-byte aligned");
     return refine_device(&ctx->c, d_flow, n_flow, m, d_inl, d_alpha, d_alpha_k, d_inlier_idx, v_in, w_in, k_in, const_acceleration,
                          flow_index_mode, d_inl_out, v_out, w_out, k_out, summary, nullptr, nullptr);
 }

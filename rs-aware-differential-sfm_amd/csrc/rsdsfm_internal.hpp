@@ -302,6 +302,13 @@ struct DeviceGuard {
 };
 
 int fail(Ctx* c, int code, const char* msg);
+// The alignment contract of the core device API (include/rsdsfm.h, "alignment of device pointers"; table in DESIGN.md): true iff
+// every pointer is a multiple of `bytes` (a power of two); NULL counts as aligned, the null checks are the callers'.  An entry point
+// refuses with RSDSFM_ERR_INVALID before any launch, workspace growth or stream operation.
+template <class... P>
+inline bool aligned_to(uintptr_t bytes, const P*... p) {
+    return ((reinterpret_cast<uintptr_t>(p) | ... | (uintptr_t)0) & (bytes - 1)) == 0;
+}
 int ensure_stage(Ctx* c, size_t bytes);
 // host_xfer.hip: the host-pointer boundary's transfers through a ring of pinned chunks filled / drained by a small thread pool, on the context's
 // stream.  xfer_h2d returns once the caller's array has been read, xfer_d2h once the caller's array holds the data.

@@ -180,8 +180,8 @@ def test_preview_equals_oracle_and_device_chain(oracle, rsdsfm):
             s.interpolate_cracky_dev(gs.data_ptr(), rows, cols, fixed.data_ptr(), offset=1)
             s.synchronize()
             # the same three stages in ONE call (rsdsfm_rectify_frame_dev: claims in one launch, writes in one launch): the same bytes
-            gs2, fixed2, c32, prev2 = torch.zeros_like(gs), torch.zeros_like(fixed), torch.zeros_like(c3), torch.zeros_like(prev)
-            for rep in range(2):  # (twice: the claim maps' epochs advance)
+            for rep in range(2):  # (twice: the claim maps' epochs advance; never preset to what a hole must contain)
+                gs2, fixed2, c32, prev2 = torch.full_like(gs, 77), torch.full_like(fixed, 77), torch.full_like(c3, float("nan")), torch.full_like(prev, 77)
                 s.rectify_frame_dev(r["d_inliers"], r["num_inliers"], t_img.data_ptr(), dm.data_ptr(), R.data_ptr(), t.data_ptr(), K, rows, cols,
                                     prev2.data_ptr(), gs2.data_ptr(), fixed2.data_ptr(), c32.data_ptr(), offset=1)
             s.synchronize()
@@ -222,10 +222,12 @@ def test_rectify_frame_one_call_equals_the_oracle(oracle, rsdsfm, rows, cols, m)
         R = R.reshape(rows, 9)
         tt = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
         d_img, d_dm, d_R, d_t, d_inl = tt(img), tt(depth.T), tt(R), tt(t), tt(inl if m else np.zeros((1, 3)))
-        prev = torch.zeros((rows, cols), dtype=torch.uint8, device=dev)
-        gs, fixed = torch.zeros((rows, cols, 3), dtype=torch.uint8, device=dev), torch.zeros((rows, cols, 3), dtype=torch.uint8, device=dev)
-        c3 = torch.zeros((rows, cols, 3), dtype=torch.float32, device=dev)
         for off in (1, 2):
+            # never preset to zero, which is what a hole, an empty depth pixel and a marker pixel's world point must contain
+            prev = torch.full((rows, cols), 77, dtype=torch.uint8, device=dev)
+            gs, fixed = torch.full((rows, cols, 3), 77, dtype=torch.uint8, device=dev), torch.full((rows, cols, 3), 77, dtype=torch.uint8, device=dev)
+            c3 = torch.full((rows, cols, 3), float("nan"), dtype=torch.float32, device=dev)
+            torch.cuda.synchronize()  # the fills run on torch's stream, the call on the context's own: a late fill would overwrite the result
             s.rectify_frame_dev(d_inl.data_ptr(), m, d_img.data_ptr(), d_dm.data_ptr(), d_R.data_ptr(), d_t.data_ptr(), K, rows, cols, prev.data_ptr(),
                                 gs.data_ptr(), fixed.data_ptr(), c3.data_ptr(), offset=off)
             s.synchronize()
