@@ -30,7 +30,8 @@
  * section 12 ("Clean plate") has the kernel, the bytes, the launches, the LDS layout and what the ISA shows for the selection.
  *
  * NOT here: the flag fed back into the denoise, the super-resolution or the fill; a vector (colour-consistent) median -- the channels are
- * selected independently --; weighted medians; temporal smoothing or morphology of the flag; inpainting where every source saw the mover (the
+ * selected independently -- (built since: rsdsfm_plate_medoid.h, the L1 medoid, and rsdsfm_set_plate_estimator, which puts it in step 4 of
+ * rsdsfm_plate_frame_dev); weighted medians; temporal smoothing or morphology of the flag; inpainting where every source saw the mover (the
  * median of movers is a mover); the C++ mirror.
  */
 #ifndef RSDSFM_PLATE_H

@@ -136,12 +136,13 @@ class RansacOut(C.Structure):
 
 def declared_symbols():
     """Names of every function include/rsdsfm.h, include/rsdsfm_retime.h, include/rsdsfm_shutter.h, include/rsdsfm_denoise.h,
-    include/rsdsfm_superres.h, include/rsdsfm_plate.h and include/rsdsfm_erase.h declare (used by the CPU symbol-export test)."""
+    include/rsdsfm_superres.h, include/rsdsfm_plate.h, include/rsdsfm_plate_medoid.h and include/rsdsfm_erase.h declare (used by the CPU
+    symbol-export test)."""
     import re
 
     txt = "".join(open(os.path.join(os.path.dirname(HEADER_PATH), name)).read()
                   for name in (os.path.basename(HEADER_PATH), "rsdsfm_retime.h", "rsdsfm_shutter.h", "rsdsfm_denoise.h", "rsdsfm_superres.h", "rsdsfm_plate.h",
-                              "rsdsfm_erase.h"))
+                              "rsdsfm_plate_medoid.h", "rsdsfm_erase.h"))
     txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
     return sorted(set(re.findall(r"\b(rsdsfm_[a-z0-9_]+)\s*\(", txt)))
 
@@ -3421,17 +3422,26 @@ class _PlateMixin:
         gain).  The plate into d_image_out, 1 into d_mask_out where anything voted, the number of candidates into d_votes, the flag 0 unset /
         1 static / 2 moving / 3 undecided into d_moving and the four counts into d_counts4 (four device int64).  One launch, enqueued on the
         context's stream."""
+        self._plate_estimator_dev("rsdsfm_plate_median_dev", d_ref, d_ref_mask, d_layers, d_layer_masks, channels, rows, cols, d_image_out, d_mask_out, d_votes, d_moving,
+                                  d_counts4, d_sums8, min_overlap, gain_mode, threshold, min_votes, nlayers)
+
+    def _plate_estimator_dev(self, name, d_ref, d_ref_mask, d_layers, d_layer_masks, channels, rows, cols, d_image_out, d_mask_out, d_votes, d_moving, d_counts4, d_sums8,
+                             min_overlap, gain_mode, threshold, min_votes, nlayers):
+        """rsdsfm_plate_median_dev or rsdsfm_plate_medoid_dev: one signature"""
         n = (len(d_layers) if d_layers is not None else 0) if nlayers is None else int(nlayers)
         arr = lambda x: _ptr_array(list(x)) if x is not None and len(x) else None
-        self._check(self.lib.rsdsfm_plate_median_dev(self._ctx, _dp(d_ref), _dp(d_ref_mask), arr(d_layers), arr(d_layer_masks), C.c_int32(n), C.c_int32(channels),
-                                                     C.c_int32(rows), C.c_int32(cols), _np0(d_sums8), C.c_int64(min_overlap), C.c_int32(gain_mode), C.c_int32(threshold),
-                                                     C.c_int32(min_votes), _np0(d_image_out), _np0(d_mask_out), _np0(d_votes), _np0(d_moving), _np0(d_counts4)),
-                    "rsdsfm_plate_median_dev")
+        self._check(getattr(self.lib, name)(self._ctx, _dp(d_ref), _dp(d_ref_mask), arr(d_layers), arr(d_layer_masks), C.c_int32(n), C.c_int32(channels), C.c_int32(rows),
+                                            C.c_int32(cols), _np0(d_sums8), C.c_int64(min_overlap), C.c_int32(gain_mode), C.c_int32(threshold), C.c_int32(min_votes),
+                                            _np0(d_image_out), _np0(d_mask_out), _np0(d_votes), _np0(d_moving), _np0(d_counts4)), name)
 
     def plate_median(self, ref, ref_mask, layers, records=None, min_overlap=0, gain_mode=0, threshold=0, min_votes=0, device=0):
         """host convenience around plate_median_dev: the reference (image, mask), layers a list of 0 .. 14 (image, mask) pairs of host arrays,
         records None or (nlayers, 8) uint64
         -> (image, mask, votes, moving (rows, cols) uint8, counts (4,) int64 [unset, static, moving, undecided])"""
+        return self._plate_estimator(self.plate_median_dev, ref, ref_mask, layers, records, min_overlap, gain_mode, threshold, min_votes, device)
+
+    def _plate_estimator(self, call_dev, ref, ref_mask, layers, records, min_overlap, gain_mode, threshold, min_votes, device):
+        """plate_median's and plate_medoid's upload, call and download"""
         import torch
 
         ref = np.ascontiguousarray(ref, dtype=np.uint8)
@@ -3448,9 +3458,8 @@ class _PlateMixin:
             d_out, d_mask = torch.empty_like(d_ref), torch.empty((rows, cols), dtype=torch.uint8, device=dev)
             d_v, d_f, d_cnt = torch.empty_like(d_mask), torch.empty_like(d_mask), torch.zeros(4, dtype=torch.int64, device=dev)
             torch.cuda.synchronize()
-            self.plate_median_dev(d_ref.data_ptr(), d_rm.data_ptr(), [i.data_ptr() for i, _ in d_l], [m.data_ptr() for _, m in d_l], ch, rows, cols, d_out.data_ptr(),
-                                  d_mask.data_ptr(), d_v.data_ptr(), d_f.data_ptr(), d_cnt.data_ptr(), d_rec.data_ptr() if d_rec is not None else None, min_overlap,
-                                  gain_mode, threshold, min_votes)
+            call_dev(d_ref.data_ptr(), d_rm.data_ptr(), [i.data_ptr() for i, _ in d_l], [m.data_ptr() for _, m in d_l], ch, rows, cols, d_out.data_ptr(), d_mask.data_ptr(),
+                     d_v.data_ptr(), d_f.data_ptr(), d_cnt.data_ptr(), d_rec.data_ptr() if d_rec is not None else None, min_overlap, gain_mode, threshold, min_votes)
             self.synchronize()
             return d_out.cpu().numpy(), d_mask.cpu().numpy(), d_v.cpu().numpy(), d_f.cpu().numpy(), d_cnt.cpu().numpy()
 
@@ -3500,6 +3509,63 @@ class _PlateMixin:
 
 
 for _name, _fn in list(vars(_PlateMixin).items()):
+    if not _name.startswith("__"):
+        setattr(Solver, _name, _fn)
+
+
+# ---------------------------------------------------------------------------------------------------
+# the colour-consistent plate: the L1 medoid in the median's place, and the context's knob between them (include/rsdsfm_plate_medoid.h)
+# ---------------------------------------------------------------------------------------------------
+PLATE_MEDOID_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "rsdsfm_plate_medoid.h")
+PLATE_MEDIAN, PLATE_MEDOID = 0, 1  # rsdsfm_set_plate_estimator
+_PLATE_ESTIMATORS = {"median": PLATE_MEDIAN, "medoid": PLATE_MEDOID}
+
+
+def plate_medoid_declared_symbols():
+    """Names of every function include/rsdsfm_plate_medoid.h declares"""
+    import re
+
+    txt = open(PLATE_MEDOID_HEADER_PATH).read()
+    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
+    return sorted(set(re.findall(r"\b(rsdsfm_[a-z0-9_]+)\s*\(", txt)))
+
+
+def plate_medoid_launches():
+    """kernel launches of one plate_medoid_dev call: 1 (rsdsfm_plate_medoid_launches; host only)"""
+    return int(load_library().rsdsfm_plate_medoid_launches())
+
+
+class _PlateMedoidMixin:
+    def plate_medoid_dev(self, d_ref, d_ref_mask, d_layers, d_layer_masks, channels, rows, cols, d_image_out, d_mask_out, d_votes=None, d_moving=None, d_counts4=None,
+                         d_sums8=None, min_overlap=0, gain_mode=0, threshold=0, min_votes=0, nlayers=None):
+        """the per-pixel L1 medoid of the reference and 0 .. 14 layers (rsdsfm_plate_medoid_dev; tests/plate_medoid_spec_numpy.py): a whole
+        candidate, the one whose summed L1 distance to the others is smallest, where plate_median_dev selects every channel on its own.  Every
+        argument and output is plate_median_dev's; with channels == 1 so is every byte.  One launch, enqueued on the context's stream."""
+        self._plate_estimator_dev("rsdsfm_plate_medoid_dev", d_ref, d_ref_mask, d_layers, d_layer_masks, channels, rows, cols, d_image_out, d_mask_out, d_votes, d_moving,
+                                  d_counts4, d_sums8, min_overlap, gain_mode, threshold, min_votes, nlayers)
+
+    def plate_medoid(self, ref, ref_mask, layers, records=None, min_overlap=0, gain_mode=0, threshold=0, min_votes=0, device=0):
+        """host convenience around plate_medoid_dev, as plate_median is around plate_median_dev
+        -> (image, mask, votes, moving (rows, cols) uint8, counts (4,) int64 [unset, static, moving, undecided])"""
+        return self._plate_estimator(self.plate_medoid_dev, ref, ref_mask, layers, records, min_overlap, gain_mode, threshold, min_votes, device)
+
+    def set_plate_estimator(self, estimator):
+        """the context's knob (rsdsfm_set_plate_estimator): "median" or 0 (the default) = plate_frame_dev ends with plate_median_dev, "medoid" or
+        1 = with plate_medoid_dev; plate_video_dev, erase_frame_dev and erase_video_dev follow it.  Anything else is refused.  Holds until set
+        again; Solver.plate_estimator is the value in force."""
+        value = _PLATE_ESTIMATORS.get(estimator, estimator) if isinstance(estimator, str) else estimator
+        if isinstance(value, str):
+            raise RsdsfmError("set_plate_estimator: 'median', 'medoid', 0 or 1, not %r" % (estimator,))
+        self._check(self.lib.rsdsfm_set_plate_estimator(self._ctx, C.c_int32(int(value))), "rsdsfm_set_plate_estimator")
+        self._plate_estimator_knob = int(value)
+
+    @property
+    def plate_estimator(self):
+        """the knob set_plate_estimator left: 0 (median) or 1 (medoid)"""
+        return getattr(self, "_plate_estimator_knob", PLATE_MEDIAN)
+
+
+for _name, _fn in list(vars(_PlateMedoidMixin).items()):
     if not _name.startswith("__"):
         setattr(Solver, _name, _fn)
 

@@ -4,7 +4,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
-#include "../../include/rsdsfm_plate.h"
+#include "../../include/rsdsfm_plate_medoid.h"
 #include "denoise.hpp"
 #include "rsdsfm_internal.hpp"
 #include "stabilize_blend.hpp"
@@ -51,5 +51,7 @@ extern const char* const kPlateParamsMessage;
 
 // the median on c->stream (arguments checked by the caller): the counters zeroed by a memset when passed, then one launch
 int plate_median_launch(Ctx* c, const PlateArgs& args, int channels);
+// the L1 medoid in its place (include/rsdsfm_plate_medoid.h; plate_medoid_kernels.hip): the same memset, one launch; channels == 1 IS the median's
+int plate_medoid_launch(Ctx* c, const PlateArgs& args, int channels);
 
 }  // namespace rsdsfm

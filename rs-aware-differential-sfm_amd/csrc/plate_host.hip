@@ -1,6 +1,8 @@
 // plate_host.hip -- C ABI of the clean plate (include/rsdsfm_plate.h; tests/plate_spec_numpy.py is the definition, plate_kernels.hip the
-// kernel): the median call, the frame call, which CALLS the public render entry points, the record call and the median one after another on
-// planes of the context's dense workspace, and the clip call, which calls the frame call per frame.
+// kernel) and of its colour-consistent estimator (include/rsdsfm_plate_medoid.h; tests/plate_medoid_spec_numpy.py, plate_medoid_kernels.hip):
+// the median call and the medoid call behind one argument check, the context's knob between them, the frame call, which CALLS the public
+// render entry points, the record call and the estimator one after another on planes of the context's dense workspace, and the clip call,
+// which calls the frame call per frame.
 #include "clip_stage_host.hpp"
 #include "plate.hpp"
 #include "rectify_dense.hpp"
@@ -46,6 +48,62 @@ int plate_ws(Ctx* c, int rows, int cols, int layers, DenseWs** ws) {
         if (rc != RSDSFM_OK) return rc;
         w->plate_layers = layers;
     }
+    return RSDSFM_OK;
+}
+
+// the argument checks of rsdsfm_plate_median_dev and rsdsfm_plate_medoid_dev, which take the same arguments and refuse the same ones, and the
+// kernel's argument with every default resolved
+int plate_call_args(Ctx* c, const uint8_t* d_ref_image, const uint8_t* d_ref_mask, const uint8_t* const* d_layer_images, const uint8_t* const* d_layer_masks, int32_t nlayers,
+                    int32_t channels, int32_t rows, int32_t cols, const uint64_t* d_sums8_or_null, int64_t min_overlap, int32_t gain_mode, int32_t threshold, int32_t min_votes,
+                    uint8_t* d_image_out, uint8_t* d_mask_out, uint8_t* d_votes_or_null, uint8_t* d_moving_or_null, int64_t* d_counts4_or_null, PlateArgs* out) {
+    if (!frame_size_ok(rows, cols)) return fail(c, RSDSFM_ERR_INVALID, "plate: rows and cols must be in [2, 16384]");
+    if (channels != 1 && channels != 3) return fail(c, RSDSFM_ERR_INVALID, "plate: channels must be 1 or 3");
+    if (nlayers < 0 || nlayers > kPlateLayersMax) return fail(c, RSDSFM_ERR_INVALID, "plate median: nlayers must be in [0, 14]");
+    if (min_overlap < 0 || (gain_mode != 0 && gain_mode != 1) || threshold < 0 || threshold > kPlateThresholdMax || min_votes < 0 || min_votes > kPlateMinVotesMax)
+        return fail(c, RSDSFM_ERR_INVALID,
+                    "plate median: min_overlap must be >= 0, gain_mode 0 or 1, threshold in [1, 255] (0: the default, 24) and min_votes in [1, 15] (0: the default, 3)");
+    int rc = plate_outputs_check(c, d_image_out, d_mask_out, d_votes_or_null, d_moving_or_null, d_counts4_or_null);
+    if (rc != RSDSFM_OK) return rc;
+    if (!d_ref_image || !d_ref_mask || d_ref_image == d_ref_mask) return fail(c, RSDSFM_ERR_INVALID, "plate median: the reference needs its image and its mask");
+    if (nlayers > 0 && (!d_layer_images || !d_layer_masks)) return fail(c, RSDSFM_ERR_INVALID, "plate median: the layers need their arrays of images and masks");
+    if (((uintptr_t)d_ref_image | (uintptr_t)d_ref_mask) & 3u) return fail(c, RSDSFM_ERR_INVALID, "plate: every plane must be 4-byte aligned");
+    if ((uintptr_t)d_sums8_or_null & 7u) return fail(c, RSDSFM_ERR_INVALID, "plate median: the records must be 8-byte aligned");
+    const void* in[3 + 2 * kPlateLayersMax] = {d_ref_image, d_ref_mask, d_sums8_or_null};
+    int nin = 3;
+    for (int j = 0; j < nlayers; ++j) {
+        const uint8_t *li = d_layer_images[j], *lm = d_layer_masks[j];
+        if (!li || !lm) return fail(c, RSDSFM_ERR_INVALID, "plate median: every layer needs its image and its mask");
+        if (((uintptr_t)li | (uintptr_t)lm) & 3u) return fail(c, RSDSFM_ERR_INVALID, "plate: every plane must be 4-byte aligned");
+        if (li == lm || li == d_ref_image || li == d_ref_mask || lm == d_ref_image || lm == d_ref_mask)
+            return fail(c, RSDSFM_ERR_INVALID, "plate median: the reference's and a layer's planes must be distinct");
+        in[nin++] = li;
+        in[nin++] = lm;
+    }
+    const void* io[5] = {d_image_out, d_mask_out, d_votes_or_null, d_moving_or_null, d_counts4_or_null};
+    for (int i = 0; i < 5; ++i)
+        for (int j = 0; j < nin && io[i]; ++j)
+            if (in[j] == io[i]) return fail(c, RSDSFM_ERR_INVALID, "plate median: an output may not be an input or the records");
+    PlateArgs& args = *out;
+    args = PlateArgs{};
+    args.ref = d_ref_image;
+    args.rmask = d_ref_mask;
+    for (int j = 0; j < nlayers; ++j) {
+        args.layer[j] = d_layer_images[j];
+        args.lmask[j] = d_layer_masks[j];
+    }
+    args.sums = nlayers > 0 ? reinterpret_cast<const unsigned long long*>(d_sums8_or_null) : nullptr;
+    args.out = d_image_out;
+    args.mask_out = d_mask_out;
+    args.votes = d_votes_or_null;
+    args.moving = d_moving_or_null;
+    args.counts = reinterpret_cast<unsigned long long*>(d_counts4_or_null);
+    args.min_overlap = min_overlap ? min_overlap : kMinOverlapDefault;
+    args.rows = rows;
+    args.cols = cols;
+    args.nlayers = nlayers;
+    args.gain_mode = gain_mode;
+    args.threshold = (unsigned)(threshold ? threshold : kPlateThresholdDefault);
+    args.min_votes = (unsigned)(min_votes ? min_votes : kPlateMinVotesDefault);
     return RSDSFM_OK;
 }
 
@@ -98,54 +156,36 @@ int rsdsfm_plate_median_dev(rsdsfm_ctx* ctx, const uint8_t* d_ref_image, const u
     if (!ctx) return RSDSFM_ERR_INVALID;
     Ctx* c = &ctx->c;
     DeviceGuard device_guard_(c);
-    if (!frame_size_ok(rows, cols)) return fail(c, RSDSFM_ERR_INVALID, "plate: rows and cols must be in [2, 16384]");
-    if (channels != 1 && channels != 3) return fail(c, RSDSFM_ERR_INVALID, "plate: channels must be 1 or 3");
-    if (nlayers < 0 || nlayers > kPlateLayersMax) return fail(c, RSDSFM_ERR_INVALID, "plate median: nlayers must be in [0, 14]");
-    if (min_overlap < 0 || (gain_mode != 0 && gain_mode != 1) || threshold < 0 || threshold > kPlateThresholdMax || min_votes < 0 || min_votes > kPlateMinVotesMax)
-        return fail(c, RSDSFM_ERR_INVALID,
-                    "plate median: min_overlap must be >= 0, gain_mode 0 or 1, threshold in [1, 255] (0: the default, 24) and min_votes in [1, 15] (0: the default, 3)");
-    int rc = plate_outputs_check(c, d_image_out, d_mask_out, d_votes_or_null, d_moving_or_null, d_counts4_or_null);
+    PlateArgs args;
+    const int rc = plate_call_args(c, d_ref_image, d_ref_mask, d_layer_images, d_layer_masks, nlayers, channels, rows, cols, d_sums8_or_null, min_overlap, gain_mode, threshold,
+                                   min_votes, d_image_out, d_mask_out, d_votes_or_null, d_moving_or_null, d_counts4_or_null, &args);
     if (rc != RSDSFM_OK) return rc;
-    if (!d_ref_image || !d_ref_mask || d_ref_image == d_ref_mask) return fail(c, RSDSFM_ERR_INVALID, "plate median: the reference needs its image and its mask");
-    if (nlayers > 0 && (!d_layer_images || !d_layer_masks)) return fail(c, RSDSFM_ERR_INVALID, "plate median: the layers need their arrays of images and masks");
-    if (((uintptr_t)d_ref_image | (uintptr_t)d_ref_mask) & 3u) return fail(c, RSDSFM_ERR_INVALID, "plate: every plane must be 4-byte aligned");
-    if ((uintptr_t)d_sums8_or_null & 7u) return fail(c, RSDSFM_ERR_INVALID, "plate median: the records must be 8-byte aligned");
-    const void* in[3 + 2 * kPlateLayersMax] = {d_ref_image, d_ref_mask, d_sums8_or_null};
-    int nin = 3;
-    for (int j = 0; j < nlayers; ++j) {
-        const uint8_t *li = d_layer_images[j], *lm = d_layer_masks[j];
-        if (!li || !lm) return fail(c, RSDSFM_ERR_INVALID, "plate median: every layer needs its image and its mask");
-        if (((uintptr_t)li | (uintptr_t)lm) & 3u) return fail(c, RSDSFM_ERR_INVALID, "plate: every plane must be 4-byte aligned");
-        if (li == lm || li == d_ref_image || li == d_ref_mask || lm == d_ref_image || lm == d_ref_mask)
-            return fail(c, RSDSFM_ERR_INVALID, "plate median: the reference's and a layer's planes must be distinct");
-        in[nin++] = li;
-        in[nin++] = lm;
-    }
-    const void* io[5] = {d_image_out, d_mask_out, d_votes_or_null, d_moving_or_null, d_counts4_or_null};
-    for (int i = 0; i < 5; ++i)
-        for (int j = 0; j < nin && io[i]; ++j)
-            if (in[j] == io[i]) return fail(c, RSDSFM_ERR_INVALID, "plate median: an output may not be an input or the records");
-    PlateArgs args{};
-    args.ref = d_ref_image;
-    args.rmask = d_ref_mask;
-    for (int j = 0; j < nlayers; ++j) {
-        args.layer[j] = d_layer_images[j];
-        args.lmask[j] = d_layer_masks[j];
-    }
-    args.sums = nlayers > 0 ? reinterpret_cast<const unsigned long long*>(d_sums8_or_null) : nullptr;
-    args.out = d_image_out;
-    args.mask_out = d_mask_out;
-    args.votes = d_votes_or_null;
-    args.moving = d_moving_or_null;
-    args.counts = reinterpret_cast<unsigned long long*>(d_counts4_or_null);
-    args.min_overlap = min_overlap ? min_overlap : kMinOverlapDefault;
-    args.rows = rows;
-    args.cols = cols;
-    args.nlayers = nlayers;
-    args.gain_mode = gain_mode;
-    args.threshold = (unsigned)(threshold ? threshold : kPlateThresholdDefault);
-    args.min_votes = (unsigned)(min_votes ? min_votes : kPlateMinVotesDefault);
     return plate_median_launch(c, args, channels);
+}
+
+int rsdsfm_plate_medoid_launches(void) { return 1; }
+
+int rsdsfm_plate_medoid_dev(rsdsfm_ctx* ctx, const uint8_t* d_ref_image, const uint8_t* d_ref_mask, const uint8_t* const* d_layer_images,
+                            const uint8_t* const* d_layer_masks, int32_t nlayers, int32_t channels, int32_t rows, int32_t cols, const uint64_t* d_sums8_or_null,
+                            int64_t min_overlap, int32_t gain_mode, int32_t threshold, int32_t min_votes, uint8_t* d_image_out, uint8_t* d_mask_out,
+                            uint8_t* d_votes_or_null, uint8_t* d_moving_or_null, int64_t* d_counts4_or_null) {
+    if (!ctx) return RSDSFM_ERR_INVALID;
+    Ctx* c = &ctx->c;
+    DeviceGuard device_guard_(c);
+    PlateArgs args;
+    const int rc = plate_call_args(c, d_ref_image, d_ref_mask, d_layer_images, d_layer_masks, nlayers, channels, rows, cols, d_sums8_or_null, min_overlap, gain_mode, threshold,
+                                   min_votes, d_image_out, d_mask_out, d_votes_or_null, d_moving_or_null, d_counts4_or_null, &args);
+    if (rc != RSDSFM_OK) return rc;
+    return plate_medoid_launch(c, args, channels);
+}
+
+int rsdsfm_set_plate_estimator(rsdsfm_ctx* ctx, int32_t estimator) {
+    if (!ctx) return RSDSFM_ERR_INVALID;
+    Ctx* c = &ctx->c;
+    if (estimator != RSDSFM_PLATE_MEDIAN && estimator != RSDSFM_PLATE_MEDOID)
+        return fail(c, RSDSFM_ERR_INVALID, "rsdsfm_set_plate_estimator: 0 (the per-channel median) or 1 (the L1 medoid)");
+    c->plate_estimator = estimator;
+    return RSDSFM_OK;
 }
 
 int rsdsfm_plate_frame_dev(rsdsfm_ctx* ctx, const uint8_t* const* d_images, int32_t channels, const double* const* d_depths_colmajor,
@@ -201,8 +241,10 @@ int rsdsfm_plate_frame_dev(rsdsfm_ctx* ctx, const uint8_t* const* d_images, int3
         rc = rsdsfm_seam_overlap_sums_dev(ctx, rimage, rsource, limage, lmask, channels, rows, cols, records + 8 * (size_t)(k - 1));
         if (rc != RSDSFM_OK) return rc;
     }
-    return rsdsfm_plate_median_dev(ctx, rimage, rmask, nl ? limages : nullptr, nl ? lmasks : nullptr, nl, channels, rows, cols, nl ? records : nullptr, pp.min_overlap,
-                                   pp.gain_mode, pp.threshold, pp.min_votes, d_image_out, d_mask_out, d_votes_or_null, d_moving_or_null, d_counts4_or_null);
+    // the public entry point of the context's estimator (rsdsfm_set_plate_estimator): the one place where the two part
+    const auto estimate = c->plate_estimator == RSDSFM_PLATE_MEDOID ? rsdsfm_plate_medoid_dev : rsdsfm_plate_median_dev;
+    return estimate(ctx, rimage, rmask, nl ? limages : nullptr, nl ? lmasks : nullptr, nl, channels, rows, cols, nl ? records : nullptr, pp.min_overlap, pp.gain_mode,
+                    pp.threshold, pp.min_votes, d_image_out, d_mask_out, d_votes_or_null, d_moving_or_null, d_counts4_or_null);
 }
 
 int rsdsfm_plate_video_dev(rsdsfm_ctx* ctx, const uint8_t* const* d_frames, int32_t nsources, int32_t rows, int32_t cols, int32_t channels, double fx, double fy,

@@ -2,7 +2,8 @@
 // reproduced bit for bit.  Integer arithmetic only; every value goes to memory through ordinary stores and atomicAdd.  The project's first image
 // stage that is not a sum: of the accumulate kernels (denoise_kernels.hip) only the tile is borrowed.
 //   plate_median_kernel<CH, NL, FLAG>  on the 16 x 64 tile of image_tile_device.hpp (the plane reads, the LDS layout and its bank argument, the
-//                               output group and the counters are described there).
+//                               output group and the counters are described there).  The loads, the gains and the flag's second stage are
+//                               plate_device.hpp's, shared with the L1 medoid (plate_medoid_kernels.hip): only the selection is this file's.
 //                               NL: the layer count the instance is compiled for, one of kPlateSizes = 0, 2, 4, 7, 14; a call
 //                               with L layers runs the smallest NL >= L and tests j < L (uniform) before it touches layer j.  The reference, the
 //                               layers and the records are pointers in the kernel argument (PlateArgs, 320 B): after unrolling every one is a
@@ -27,9 +28,7 @@
 //                                 the reads with FLAG.
 #include <algorithm>
 
-#include "image_tile_device.hpp"
-#include "plate.hpp"
-#include "rectify_dense_device.hpp"
+#include "plate_device.hpp"
 #include "rsdsfm_internal.hpp"
 
 namespace rsdsfm {
@@ -103,44 +102,14 @@ __device__ __forceinline__ void plate_median_body(const PlateArgs& a) {
     const int rows = a.rows, cols = a.cols, nl = a.nlayers;
     const TileThread t = tile_thread(rows, cols);
     const int tid = t.tid, nin = t.nin;
-    const int64_t p0 = t.p0, npix = (int64_t)rows * cols;
-    const unsigned inside = first_ones(nin);
+    const int64_t p0 = t.p0;
 
-    // the mask dwords first, then the images whose mask has a byte set
-    unsigned mr = 0u, nw = 0u, ml[N], rw[CH], lw[N][CH];  // ml[NL], lw[NL] are never used: no array of length 0
-#pragma unroll
-    for (int j = 0; j < NL; ++j) ml[j] = 0u;
-    if (nin) {
-        unsigned w1[1];
-        load_bytes<1>(a.rmask, p0, npix, w1);
-        mr = bytes_set(w1[0]) & inside;
-#pragma unroll
-        for (int j = 0; j < NL; ++j)
-            if (j < nl) {
-                load_bytes<1>(a.lmask[j], p0, npix, w1);
-                ml[j] = bytes_set(w1[0]) & inside;
-            }
-    }
-    nw = mr;
-#pragma unroll
-    for (int j = 0; j < NL; ++j) nw += ml[j];  // the votes, a byte per pixel: at most 15, no carry
-#pragma unroll
-    for (int d = 0; d < CH; ++d) rw[d] = 0u;
-    if (mr) load_bytes<CH>(a.ref, (int64_t)CH * p0, (int64_t)CH * npix, rw);  // image bytes under an empty mask are not read
-#pragma unroll
-    for (int j = 0; j < NL; ++j) {
-#pragma unroll
-        for (int d = 0; d < CH; ++d) lw[j][d] = 0u;
-        if (ml[j]) load_bytes<CH>(a.layer[j], (int64_t)CH * p0, (int64_t)CH * npix, lw[j]);
-    }
-
-    if constexpr (NL > 0) {
-        if (tid < NL * CH) {
-            const int j = tid / CH, c = tid % CH;
-            s_gain[tid] = (a.sums && j < nl) ? seam_gain(a.sums + 8 * j, CH, c, a.min_overlap, a.gain_mode) : kGainOne;
-        }
-        __syncthreads();
-    }
+    // the mask dwords first, then the images whose mask has a byte set; the gains (plate_device.hpp)
+    PlateLoads<CH, NL> l;
+    plate_load<CH, NL>(a, t, l);
+    plate_gains<CH, NL>(a, tid, s_gain);
+    const unsigned mr = l.mr, nw = l.nw;
+    const unsigned (&ml)[N] = l.ml, (&rw)[CH] = l.rw, (&lw)[N][CH] = l.lw;
 
     // the medians of the thread's own four pixels: per channel, pixels 0 and 2, then 1 and 3
     unsigned ow[CH], med[4];
@@ -230,26 +199,7 @@ __device__ __forceinline__ void plate_median_body(const PlateArgs& a) {
         }
         __syncthreads();
         // stage 2: the 3 x 3 sums of the packed dwords
-        if (mr) {
-            unsigned col[6];
-            tile_sum3x3(s_tile, t.ty, t.g, col);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const unsigned s = col[j] + col[j + 1] + col[j + 2];
-                const unsigned D = s & 0xffffu, cnt = s >> 16;
-                const unsigned f = cnt == 0u ? 3u : D > a.threshold * (unsigned)CH * cnt ? 2u : 1u;  // at most 255 * 27: products of integers, no division
-                fw |= (((mr >> (8 * j)) & 1u) ? f : 0u) << (8 * j);
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-            if (j < nin) {
-                const unsigned f = (fw >> (8 * j)) & 0xffu;
-                n4[0] += f == 0u ? 1u : 0u;
-                n4[1] += f == 1u ? 1u : 0u;
-                n4[2] += f == 2u ? 1u : 0u;
-                n4[3] += f == 3u ? 1u : 0u;
-            }
+        plate_flags<CH>(s_tile, t, mr, a.threshold, fw, n4);
     }
 
     unsigned char* const planes[3] = {a.mask_out, a.votes, FLAG ? a.moving : nullptr};

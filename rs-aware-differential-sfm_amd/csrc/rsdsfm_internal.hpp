@@ -259,6 +259,7 @@ struct Ctx {
     int64_t refine_cache_hits = 0;
     std::vector<rsdsfm_ctx*> lanes;
     int occlusion_search = 0;  // rsdsfm_set_occlusion_search: 1 = the clip calls' tested neighbour candidates go through rsdsfm_stabilize_search_frame_dev (stabilize_search_host.hip); last, so that every other member stays where it was
+    int plate_estimator = 0;  // rsdsfm_set_plate_estimator: 0 = rsdsfm_plate_frame_dev ends with the per-channel median, 1 = with the L1 medoid (plate_host.hip); behind the member above, which was the last
 };
 constexpr int kSequenceLanesDefault = 3;  // measured: 1 / 2 / 3 / 4 / 6 / 8 lanes = 0.91 / 1.19 / 1.31 / 1.21 / 1.31 / 1.27 Gpix/s at 1280x720, T = 50
 void dist_release(Ctx* c);

@@ -5,6 +5,7 @@ backProject -> interpolateCrackyImage -> point cloud, images and (synthetic data
 Host-side orchestration over the C-ABI wrappers (Solver); file formats in formats.py.  Image decoding / encoding and the
 CSV parsing are host work like in the reference; everything per-pixel runs in the HIP kernels.
 """
+import contextlib
 import os
 
 import numpy as np
@@ -204,12 +205,27 @@ def _write_real_outputs(out_dir, image, flow, depth_est, backprojection, coords)
     formats.write_ply(out_dir + "/point_cloud.ply", coords, image if image.ndim == 3 else np.repeat(image[:, :, None], 3, axis=2))
 
 
+@contextlib.contextmanager
+def _plate_estimator_for(solver, estimator):
+    """evaluate_real_sequence's plate_estimator keyword: the solver's knob (Solver.set_plate_estimator) at `estimator` inside the block and back
+    where it was behind it, whatever happens inside; None: the knob stays where the caller left it"""
+    if estimator is None:
+        yield
+        return
+    before = solver.plate_estimator
+    solver.set_plate_estimator(estimator)
+    try:
+        yield
+    finally:
+        solver.set_plate_estimator(before)
+
+
 def evaluate_real_sequence(solver, frames, camera="galaxy", gamma=0.95, out_dir=None, trials=5, seeds=None, tol=0.05, use_acceleration_mode=False,
                            use_refinement=True, use_global_shutter_mode=False, flow_threshold=1e-10, flow_index_mode=0, device=0, flow_params=None, dense=False,
                            check_flow=False, trajectory=False, link_tol=None, min_links=None, fuse=False, fuse_tol=None, stabilize=False, smooth_sigma=None,
                            smooth_translation=True, fill=0, crop=False, crop_margin=None, crop_max_empty=0, blend=False, blend_feather=None,
                            blend_gain=True, inpaint=False, last_frame=False, occlusion=False, occlusion_tol=None, occlusion_search=False, retime=None,
-                           shutter=None, denoise=None, superres=None, plate=None, erase=None):
+                           shutter=None, denoise=None, superres=None, plate=None, erase=None, plate_estimator=None):
     """evaluate_real_run's real-world branch (main.cc:341-361, 364-531) for a clip: `frames` is <prefix>frame1.png ... frameN.png (the
     prefix, or a list of paths), or the frames themselves (an (N, rows, cols[, 3]) uint8 array or a list of arrays; 2-D frames are gray).
     By default ONE call does the clip (Solver.rectify_video_dev): the batched DeepFlow of every consecutive pair, the pipelined solve of every pair p
@@ -314,7 +330,15 @@ def evaluate_real_sequence(solver, frames, camera="galaxy", gamma=0.95, out_dir=
     grow, feather literal, default 2, 2, 4; the fused maps with fuse=True, the neighbours through the occlusion test with occlusion=True): the
     returned dict also has erased, erase_matte (lists of frames; the matte is 0 .. feather) and erase_counts ((frames, 5) int64: [unset, kept,
     replaced, feathered, unresolved]); out_dir receives erased_<p>.png, matte_<p>.png (the matte scaled to 0 .. 255) and erase.csv.  Without the
-    keyword every key and file is what it was."""
+    keyword every key and file is what it was.
+    plate_estimator="median" or "medoid" (needs plate= or erase=: ValueError otherwise): the solver's knob (Solver.set_plate_estimator) is set to
+    it around the plate= and erase= stages and put back afterwards -- "medoid": every plate pixel is a whole candidate, the L1 medoid
+    (tests/plate_medoid_spec_numpy.py), not a per-channel median.  The keys and files are plate='s and erase='s.  None: the knob stays where the
+    caller left it, and every key and file is what it was."""
+    if plate_estimator is not None and plate_estimator not in ("median", "medoid"):
+        raise ValueError("plate_estimator is None, 'median' or 'medoid'")
+    if plate_estimator is not None and plate is None and erase in (None, False):
+        raise ValueError("plate_estimator needs plate= or erase=: it chooses what their plate is made with")
     if erase is not None and erase is not False and not stabilize:
         raise ValueError("erase needs stabilize=True: it takes the movers out of the frames of the stabilised clip")
     if erase is False:
@@ -655,18 +679,20 @@ def evaluate_real_sequence(solver, frames, camera="galaxy", gamma=0.95, out_dir=
                     d_plmasks = [torch.empty((rows, cols), dtype=torch.uint8, device=dev) for _ in range(nst)]
                     d_plmov = [torch.empty((rows, cols), dtype=torch.uint8, device=dev) for _ in range(nst)]
                     torch.cuda.synchronize()
-                    pl = solver.plate_video_dev(ptrs(d_imgs), rows, cols, channels, K, ptrs(d_src[:nst]), ptrs(d_Rs[:nst]), ptrs(d_ts[:nst]), traj["A"], traj["c"], A_s, c_s,
-                                                st_scales, ptrs(d_pl), ptrs(d_plmasks), None, ptrs(d_plmov), radius=pl_radius, threshold=pl_threshold, occlusion=occlusion,
-                                                occlusion_tol_q16=occ_q16 if occlusion else 0, mode=mode)
+                    with _plate_estimator_for(solver, plate_estimator):
+                        pl = solver.plate_video_dev(ptrs(d_imgs), rows, cols, channels, K, ptrs(d_src[:nst]), ptrs(d_Rs[:nst]), ptrs(d_ts[:nst]), traj["A"], traj["c"], A_s,
+                                                    c_s, st_scales, ptrs(d_pl), ptrs(d_plmasks), None, ptrs(d_plmov), radius=pl_radius, threshold=pl_threshold,
+                                                    occlusion=occlusion, occlusion_tol_q16=occ_q16 if occlusion else 0, mode=mode)
                     traj.update(plate=[t.cpu().numpy() for t in d_pl], plate_moving=[t.cpu().numpy() for t in d_plmov], plate_counts=pl["counts"])
                 if erase is not None:  # every stabilised frame once more, without what moved through it
                     d_er = [torch.empty_like(d_imgs[0]) for _ in range(nst)]
                     d_ermasks = [torch.empty((rows, cols), dtype=torch.uint8, device=dev) for _ in range(nst)]
                     d_ermatte = [torch.empty((rows, cols), dtype=torch.uint8, device=dev) for _ in range(nst)]
                     torch.cuda.synchronize()
-                    er = solver.erase_video_dev(ptrs(d_imgs), rows, cols, channels, K, ptrs(d_src[:nst]), ptrs(d_Rs[:nst]), ptrs(d_ts[:nst]), traj["A"], traj["c"], A_s, c_s,
-                                                st_scales, ptrs(d_er), ptrs(d_ermasks), ptrs(d_ermatte), None, radius=er_radius, open=er_open, grow=er_grow, feather=er_feather,
-                                                occlusion=occlusion, occlusion_tol_q16=occ_q16 if occlusion else 0, mode=mode)
+                    with _plate_estimator_for(solver, plate_estimator):
+                        er = solver.erase_video_dev(ptrs(d_imgs), rows, cols, channels, K, ptrs(d_src[:nst]), ptrs(d_Rs[:nst]), ptrs(d_ts[:nst]), traj["A"], traj["c"], A_s,
+                                                    c_s, st_scales, ptrs(d_er), ptrs(d_ermasks), ptrs(d_ermatte), None, radius=er_radius, open=er_open, grow=er_grow,
+                                                    feather=er_feather, occlusion=occlusion, occlusion_tol_q16=occ_q16 if occlusion else 0, mode=mode)
                     traj.update(erased=[t.cpu().numpy() for t in d_er], erase_matte=[t.cpu().numpy() for t in d_ermatte], erase_counts=er["counts"])
     if out_dir:
         os.makedirs(out_dir, exist_ok=True)
