@@ -1,0 +1,47 @@
+// deblur.hpp -- the sharpness transfer (include/rsdsfm_deblur.h): what deblur_kernels.hip and deblur_host.hip share.
+#pragma once
+
+#include <stddef.h>
+#include <stdint.h>
+
+#include "../../include/rsdsfm_deblur.h"
+#include "denoise.hpp"
+#include "rsdsfm_internal.hpp"
+
+namespace rsdsfm {
+
+constexpr int kDeblurRadiusMax = RSDSFM_DEBLUR_RADIUS_MAX;
+constexpr int kDeblurLayersMax = RSDSFM_DEBLUR_LAYERS_MAX;
+constexpr int kDeblurSourcesMax = 1 + kDeblurLayersMax;
+constexpr int kDeblurStrengthDefault = RSDSFM_DEBLUR_STRENGTH_DEFAULT, kDeblurStrengthMax = 255;
+constexpr int kDeblurMarginDefault = RSDSFM_DEBLUR_MARGIN_DEFAULT, kDeblurMarginMax = RSDSFM_DEBLUR_MARGIN_MAX;
+constexpr int64_t kDeblurMinPairsDefault = RSDSFM_DEBLUR_MIN_PAIRS_DEFAULT;
+constexpr unsigned kDeblurTauMax = RSDSFM_DEBLUR_TAU_MAX;
+constexpr unsigned kDeblurBias = 765u;  // Y_R - Y_L + bias lies in [0, 1530]
+// 16 (the own frame) + 7 * 32 = 240 = 16 (1 + 14): the cells' bounds are the denoise's
+static_assert(kDenoiseW + kDeblurLayersMax * kDeblurTauMax <= kDenoiseW * (1 + kDenoiseLayersMax), "a uint16 sum cannot overflow");
+
+// the ABI's margin word as its value: -1 none, 0 the default
+inline int deblur_margin_value(int word) { return word < 0 ? 0 : word == 0 ? kDeblurMarginDefault : word; }
+
+// tau of the record T = [pairs, A_R, A_L, 0]: the spec's tau(); host and device.  margin: the value, 0 .. 64; min_pairs >= 1.
+// A <= 2 * 16384^2 * 765^2 < 2^49, so 80 A < 2^56: nothing overflows
+__host__ __device__ inline unsigned deblur_tau_of(const unsigned long long* T, int margin, long long min_pairs) {
+    const unsigned long long ar = T[1], al = T[2];
+    if ((long long)T[0] < min_pairs || 16ull * al <= (16ull + (unsigned long long)margin) * ar) return 0u;
+    const unsigned long long q = (16ull * (al - ar)) / (ar ? ar : 1ull);
+    return q > kDeblurTauMax ? kDeblurTauMax : (unsigned)q;
+}
+
+// the record zeroed by a memset, then one launch, on c->stream (arguments checked by the caller; d_sums NULL: no gain)
+int deblur_sharpness_launch(Ctx* c, const unsigned char* d_ref, const unsigned char* d_rmask, const unsigned char* d_layer, const unsigned char* d_lmask, int channels,
+                            int rows, int cols, const unsigned long long* d_sums, int64_t min_overlap, int gain_mode, unsigned long long* d_sharp4);
+
+// one step on c->stream (arguments checked by the caller; d_layer, d_lmask and d_sharp all NULL: no layer; margin: the value): the counters
+// zeroed by a memset when passed and `last`, then one launch
+int deblur_accumulate_launch(Ctx* c, const unsigned char* d_ref, const unsigned char* d_rmask, const unsigned char* d_layer, const unsigned char* d_lmask, int channels,
+                             int rows, int cols, const unsigned long long* d_sums, int64_t min_overlap, int gain_mode, int strength, const unsigned long long* d_sharp4,
+                             int margin, int64_t min_pairs, int gate_mode, uint16_t* d_cells, bool first, bool last, unsigned char* d_image_out, unsigned char* d_mask_out,
+                             unsigned char* d_weight, int64_t* d_counts3);
+
+}  // namespace rsdsfm

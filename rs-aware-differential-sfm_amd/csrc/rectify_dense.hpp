@@ -30,6 +30,7 @@ struct DenseWs {
     int plate_layers = 0;                // the layers d_plate holds
     unsigned char* d_matte = nullptr;    // the mover matte's two intermediate planes (erase.hpp; made when first asked for)
     unsigned char* d_erase = nullptr;    // the mover removal's plate mask, flag, matte and plate image, 6 planes (erase.hpp; made when first asked for)
+    unsigned long long* d_deblur = nullptr; // the sharpness transfer's one record, 4 words; its planes are d_denoise's and d_layer's (deblur.hpp; made when first asked for)
     int rows = 0, cols = 0;
 };
 

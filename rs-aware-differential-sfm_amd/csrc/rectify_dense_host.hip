@@ -35,6 +35,8 @@ static void dense_ws_free(DenseWs* w) {
     w->d_matte = nullptr;
     if (w->d_erase) (void)hipFree(w->d_erase);
     w->d_erase = nullptr;
+    if (w->d_deblur) (void)hipFree(w->d_deblur);
+    w->d_deblur = nullptr;
     w->d_pyr = nullptr;
     w->d_disp = nullptr;
     w->d_mask = nullptr;

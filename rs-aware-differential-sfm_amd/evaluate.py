@@ -225,7 +225,7 @@ def evaluate_real_sequence(solver, frames, camera="galaxy", gamma=0.95, out_dir=
                            check_flow=False, trajectory=False, link_tol=None, min_links=None, fuse=False, fuse_tol=None, stabilize=False, smooth_sigma=None,
                            smooth_translation=True, fill=0, crop=False, crop_margin=None, crop_max_empty=0, blend=False, blend_feather=None,
                            blend_gain=True, inpaint=False, last_frame=False, occlusion=False, occlusion_tol=None, occlusion_search=False, retime=None,
-                           shutter=None, denoise=None, superres=None, plate=None, erase=None, plate_estimator=None):
+                           shutter=None, denoise=None, superres=None, plate=None, erase=None, plate_estimator=None, deblur=None):
     """evaluate_real_run's real-world branch (main.cc:341-361, 364-531) for a clip: `frames` is <prefix>frame1.png ... frameN.png (the
     prefix, or a list of paths), or the frames themselves (an (N, rows, cols[, 3]) uint8 array or a list of arrays; 2-D frames are gray).
     By default ONE call does the clip (Solver.rectify_video_dev): the batched DeepFlow of every consecutive pair, the pipelined solve of every pair p
@@ -334,7 +334,14 @@ def evaluate_real_sequence(solver, frames, camera="galaxy", gamma=0.95, out_dir=
     plate_estimator="median" or "medoid" (needs plate= or erase=: ValueError otherwise): the solver's knob (Solver.set_plate_estimator) is set to
     it around the plate= and erase= stages and put back afterwards -- "medoid": every plate pixel is a whole candidate, the L1 medoid
     (tests/plate_medoid_spec_numpy.py), not a per-channel median.  The keys and files are plate='s and erase='s.  None: the knob stays where the
-    caller left it, and every key and file is what it was."""
+    caller left it, and every key and file is what it was.
+    deblur=True, K or (K, strength) (needs stabilize=True: ValueError otherwise): behind everything else, every stabilised frame once more with the
+    pixels of its sharper neighbours -- the frame and its up to K neighbours on each side (1 .. 3; True: the default, 2), each rendered alone into
+    the frame's camera on the SMOOTHED path, a neighbour counting by how much sharper than the frame it is on their overlap
+    (Solver.deblur_video_dev, tests/deblur_spec_numpy.py; strength None: the default, 24; the fused maps with fuse=True, the neighbours through
+    the occlusion test with occlusion=True): the returned dict also has deblurred (a list of frames), deblur_counts ((frames, 3) int64: [unset,
+    own only, transferred]) and deblur_taus ((frames, 6) int32: the factor 0 .. 32 of every listed neighbour, -1 behind them); out_dir receives
+    deblurred_<p>.png and deblur.csv.  Without the keyword every key and file is what it was."""
     if plate_estimator is not None and plate_estimator not in ("median", "medoid"):
         raise ValueError("plate_estimator is None, 'median' or 'medoid'")
     if plate_estimator is not None and plate is None and erase in (None, False):
@@ -347,6 +354,12 @@ def evaluate_real_sequence(solver, frames, camera="galaxy", gamma=0.95, out_dir=
         er_radius, er_open, er_grow, er_feather = (None, None, None, None) if erase is True else (int(erase), None, None, None) if np.ndim(erase) == 0 else \
             tuple(int(x) for x in erase)
         erase_feather = er_feather or 4  # the matte's largest byte (None or 0: the default), for matte_<p>.png
+    if deblur is not None and deblur is not False and not stabilize:
+        raise ValueError("deblur needs stabilize=True: it transfers sharpness between the frames of the stabilised clip")
+    if deblur is False:
+        deblur = None
+    if deblur is not None:
+        db_radius, db_strength = (None, None) if deblur is True else (int(deblur), None) if np.ndim(deblur) == 0 else (int(deblur[0]), int(deblur[1]))
     if plate is not None and not stabilize:
         raise ValueError("plate needs stabilize=True: it takes the median of the frames of the stabilised clip")
     if superres is not None and not stabilize:
@@ -694,6 +707,14 @@ def evaluate_real_sequence(solver, frames, camera="galaxy", gamma=0.95, out_dir=
                                                     c_s, st_scales, ptrs(d_er), ptrs(d_ermasks), ptrs(d_ermatte), None, radius=er_radius, open=er_open, grow=er_grow,
                                                     feather=er_feather, occlusion=occlusion, occlusion_tol_q16=occ_q16 if occlusion else 0, mode=mode)
                     traj.update(erased=[t.cpu().numpy() for t in d_er], erase_matte=[t.cpu().numpy() for t in d_ermatte], erase_counts=er["counts"])
+                if deblur is not None:  # every stabilised frame once more, with what its sharper neighbours show
+                    d_db = [torch.empty_like(d_imgs[0]) for _ in range(nst)]
+                    d_dbmasks = [torch.empty((rows, cols), dtype=torch.uint8, device=dev) for _ in range(nst)]
+                    torch.cuda.synchronize()
+                    db = solver.deblur_video_dev(ptrs(d_imgs), rows, cols, channels, K, ptrs(d_src[:nst]), ptrs(d_Rs[:nst]), ptrs(d_ts[:nst]), traj["A"], traj["c"], A_s,
+                                                 c_s, st_scales, ptrs(d_db), ptrs(d_dbmasks), None, radius=db_radius, strength=db_strength, occlusion=occlusion,
+                                                 occlusion_tol_q16=occ_q16 if occlusion else 0, mode=mode)
+                    traj.update(deblurred=[t.cpu().numpy() for t in d_db], deblur_counts=db["counts"], deblur_taus=db["taus"])
     if out_dir:
         os.makedirs(out_dir, exist_ok=True)
         lines = ["pair,v_x,v_y,v_z,w_x,w_y,w_z,k,inliers"]
@@ -812,6 +833,13 @@ def evaluate_real_sequence(solver, frames, camera="galaxy", gamma=0.95, out_dir=
                 formats.write_png(os.path.join(out_dir, "matte_%d.png" % p), (traj["erase_matte"][p].astype(np.int64) * 255 // erase_feather).astype(np.uint8))
                 rows_.append(",".join([str(p)] + [str(int(x)) for x in traj["erase_counts"][p]]))
             with open(os.path.join(out_dir, "erase.csv"), "w") as fh:
+                fh.write("\n".join(rows_) + "\n")
+        if deblur is not None:
+            rows_ = ["pair,unset,own_only,transferred," + ",".join("tau_%d" % j for j in range(traj["deblur_taus"].shape[1]))]
+            for p in range(nst):
+                formats.write_png(os.path.join(out_dir, "deblurred_%d.png" % p), traj["deblurred"][p])
+                rows_.append(",".join([str(p)] + [str(int(x)) for x in traj["deblur_counts"][p]] + [str(int(x)) for x in traj["deblur_taus"][p]]))
+            with open(os.path.join(out_dir, "deblur.csv"), "w") as fh:
                 fh.write("\n".join(rows_) + "\n")
         if inpaint:
             rows_ = ["pair,stage,inpainted"]

@@ -278,7 +278,28 @@ def _with_mover(frames, mover, seed):
     return out
 
 
-def render_sequence(nframes, rows, cols, K, v, w, k=0.0, gamma=0.8, seed=0x5EED0000, speeds=None, gains=None, noise=None, noise_seed=0x5EED0001, mover=None):
+def _box_blurred(frames, blur):
+    """the frames with frame j replaced by its rounded box mean over blur[j] (odd) columns, edges replicated (a new array); None or all 1: the
+    frames themselves"""
+    if blur is None:
+        return frames
+    widths = [int(b) for b in blur]
+    if len(widths) != frames.shape[0] or any(b < 1 or b % 2 == 0 for b in widths):
+        raise ValueError("blur needs one odd box width >= 1 per frame (nframes)")
+    if all(b == 1 for b in widths):
+        return frames
+    out = frames.copy()
+    cols = frames.shape[2]
+    for j, b in enumerate(widths):
+        if b > 1:
+            idx = np.clip(np.arange(-(b // 2), cols + b // 2), 0, cols - 1)
+            padded = frames[j].astype(np.int64)[:, idx]
+            total = sum(padded[:, d:d + cols] for d in range(b))
+            out[j] = ((2 * total + b) // (2 * b)).astype(np.uint8)
+    return out
+
+
+def render_sequence(nframes, rows, cols, K, v, w, k=0.0, gamma=0.8, seed=0x5EED0000, speeds=None, gains=None, noise=None, noise_seed=0x5EED0001, mover=None, blur=None):
     """nframes 8-bit BGR frames of render_pair's texture under a constant motion: frame j at pixel q shows T(inv^j(q)), where inv is
     render_pair's fixed-point inverse of the model flow F (p + F(p) = q), applied j times from the pixel grid.  Every consecutive pair
     (j, j + 1) therefore has the true flow F and the true (v, w, k); render_pair's border mask.  nframes = 2 gives render_pair's two
@@ -294,14 +315,17 @@ def render_sequence(nframes, rows, cols, K, v, w, k=0.0, gamma=0.8, seed=0x5EED0
     mover: (y0, x0, h, w, dx, dy): a rectangle of h x w pixels with render_occluded_pair's block texture pasted onto frame j at
     (y0 + j dy, x0 + j dx), after the exposure gain and before the sensor noise -- something that moves through a static scene, what the clean
     plate is for; it must lie inside every frame and has no part in F or the mask (mover_planes gives its footprints).  None: byte for byte
-    what this function returns without the argument."""
+    what this function returns without the argument.
+    blur: one odd horizontal box width per frame (nframes of them): frame j becomes its rounded box mean over blur[j] columns with replicated
+    edges, after the mover and before the sensor noise -- the blur of a shaken exposure, what the sharpness transfer is for; the geometry is
+    unchanged.  None or all 1: byte for byte what this function returns without the argument."""
     if nframes < 2:
         raise ValueError("a sequence has at least two frames")
     if gains is not None and len(gains) != nframes:
         raise ValueError("gains needs one factor per frame (nframes)")
     if speeds is not None:
         frames, flows, mask = _render_sequence_speeds(nframes, rows, cols, K, v, w, k, gamma, seed, speeds, gains)
-        return _sensor_noise(_with_mover(frames, mover, seed), noise, noise_seed), flows, mask
+        return _sensor_noise(_box_blurred(_with_mover(frames, mover, seed), blur), noise, noise_seed), flows, mask
     flow, _ = make_flow(rows, cols, K, v, w, k, gamma, _model_only=True)
     yy, xx = np.mgrid[0:rows, 0:cols].astype(np.float64)
     frames = [_exposed(_texture(xx, yy, seed), None if gains is None else gains[0])]
@@ -320,7 +344,7 @@ def render_sequence(nframes, rows, cols, K, v, w, k=0.0, gamma=0.8, seed=0x5EED0
     band = int(np.ceil(np.abs(flow).max())) + 5
     mask = np.zeros((rows, cols), dtype=bool)
     mask[band:rows - band, band:cols - band] = True
-    return _sensor_noise(_with_mover(np.stack(frames), mover, seed), noise, noise_seed), np.ascontiguousarray(flow), mask
+    return _sensor_noise(_box_blurred(_with_mover(np.stack(frames), mover, seed), blur), noise, noise_seed), np.ascontiguousarray(flow), mask
 
 
 def _render_sequence_speeds(nframes, rows, cols, K, v, w, k, gamma, seed, speeds, gains=None):
