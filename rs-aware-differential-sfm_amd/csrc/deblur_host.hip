@@ -10,7 +10,6 @@
 #include "rsdsfm_internal.hpp"
 #include "sequence_host.hpp"
 #include "stabilize_blend.hpp"
-#include "stabilize_visible.hpp"
 
 namespace rsdsfm {
 namespace {
@@ -26,7 +25,7 @@ bool margin_word_ok(int margin) { return margin >= -1 && margin <= kDeblurMargin
 // is "none"), or the defaults for NULL; false: refused
 bool deblur_params_resolve(const rsdsfm_deblur_params* in, rsdsfm_deblur_params* out) {
     *out = in ? *in : deblur_defaults();
-    if (out->struct_bytes != 0 && out->struct_bytes != (int32_t)sizeof(rsdsfm_deblur_params)) return false;
+    if (!struct_bytes_ok(out->struct_bytes, sizeof(rsdsfm_deblur_params))) return false;
     if (out->radius == 0) out->radius = RSDSFM_DEBLUR_RADIUS_DEFAULT;
     if (out->strength == 0) out->strength = kDeblurStrengthDefault;
     if (out->margin == 0) out->margin = kDeblurMarginDefault;
@@ -34,22 +33,12 @@ bool deblur_params_resolve(const rsdsfm_deblur_params* in, rsdsfm_deblur_params*
     if (out->min_pairs == 0) out->min_pairs = kDeblurMinPairsDefault;
     return out->radius >= 1 && out->radius <= kDeblurRadiusMax && out->strength >= 1 && out->strength <= kDeblurStrengthMax && margin_word_ok(out->margin) &&
            (out->gate_mode == 0 || out->gate_mode == 1) && out->min_overlap >= 0 && out->min_pairs >= 0 && (out->gain_mode == 0 || out->gain_mode == 1) &&
-           (out->occlusion == 0 || out->occlusion == 1) && out->occlusion_tol_q16 >= 0 && out->occlusion_tol_q16 <= kVisibleTolQ16Max;
+           occlusion_words_ok(out->occlusion, out->occlusion_tol_q16);
 }
 
 const char* const kDeblurParamsMessage =
     "rsdsfm_deblur_params: radius in [1, 3] or 0, strength in [1, 255] or 0, margin in [-1, 64], gate_mode 0 or 1, gain_mode 0 or 1, occlusion 0 or 1, "
     "occlusion_tol_q16 in [0, 65536], min_overlap >= 0, min_pairs >= 0, struct_bytes 0 or sizeof (use rsdsfm_deblur_params_init)";
-
-// the argument checks of the outputs, for the accumulate call and, before anything is enqueued, for the frame call (whose planes and cells are the context's)
-int deblur_outputs_check(Ctx* c, const uint8_t* d_image_out, const uint8_t* d_mask_out, const uint8_t* d_weight, const int64_t* d_counts3) {
-    if (!d_image_out || !d_mask_out) return fail(c, RSDSFM_ERR_INVALID, "deblur: null output plane");
-    if (d_image_out == d_mask_out || (d_weight && (d_weight == d_image_out || d_weight == d_mask_out)))
-        return fail(c, RSDSFM_ERR_INVALID, "deblur: the output planes must be distinct");
-    if (((uintptr_t)d_image_out | (uintptr_t)d_mask_out | (uintptr_t)d_weight) & 3u) return fail(c, RSDSFM_ERR_INVALID, "deblur: every plane must be 4-byte aligned");
-    if ((uintptr_t)d_counts3 & 7u) return fail(c, RSDSFM_ERR_INVALID, "deblur: the counters must be 8-byte aligned");
-    return RSDSFM_OK;
-}
 
 // the denoise's reference planes and cells and the blend's layer, made when first asked for, and this stage's one record
 int deblur_ws(Ctx* c, int rows, int cols, DenseWs** ws) {
@@ -124,46 +113,21 @@ int rsdsfm_deblur_accumulate_dev(rsdsfm_ctx* ctx, const uint8_t* d_ref_image, co
     if (!ctx) return RSDSFM_ERR_INVALID;
     Ctx* c = &ctx->c;
     DeviceGuard device_guard_(c);
-    if ((first != 0 && first != 1) || (last != 0 && last != 1)) return fail(c, RSDSFM_ERR_INVALID, "deblur accumulate: first and last must be 0 or 1");
-    if (!frame_size_ok(rows, cols)) return fail(c, RSDSFM_ERR_INVALID, "deblur: rows and cols must be in [2, 16384]");
-    if (channels != 1 && channels != 3) return fail(c, RSDSFM_ERR_INVALID, "deblur: channels must be 1 or 3");
     if (min_overlap < 0 || (gain_mode != 0 && gain_mode != 1) || strength < 0 || strength > kDeblurStrengthMax)
         return fail(c, RSDSFM_ERR_INVALID, "deblur accumulate: min_overlap must be >= 0, gain_mode 0 or 1 and strength in [1, 255] (0: the default, 24)");
     if (!margin_word_ok(margin) || min_pairs < 0 || (gate_mode != 0 && gate_mode != 1))
         return fail(c, RSDSFM_ERR_INVALID, "deblur accumulate: margin must be in [-1, 64], min_pairs >= 0 and gate_mode 0 or 1");
-    if (last) {
-        const int rc = deblur_outputs_check(c, d_image_out, d_mask_out, d_weight_or_null, d_counts3_or_null);
-        if (rc != RSDSFM_OK) return rc;
-    } else {  // the outputs are not read
-        d_image_out = d_mask_out = d_weight_or_null = nullptr;
-        d_counts3_or_null = nullptr;
-    }
-    if (!d_ref_image || !d_ref_mask || d_ref_image == d_ref_mask) return fail(c, RSDSFM_ERR_INVALID, "deblur accumulate: the reference needs its image and its mask");
-    if ((d_layer_image_or_null == nullptr) != (d_layer_mask_or_null == nullptr))
-        return fail(c, RSDSFM_ERR_INVALID, "deblur accumulate: the layer needs its image and its mask, or neither");
-    if (!d_layer_image_or_null && !(first && last)) return fail(c, RSDSFM_ERR_INVALID, "deblur accumulate: without a layer first and last must both be 1");
     if (d_layer_image_or_null && !d_sharp4_or_null) return fail(c, RSDSFM_ERR_INVALID, "deblur accumulate: a layer needs its sharpness record");
     if (!d_layer_image_or_null) d_sharp4_or_null = nullptr, d_sums8_or_null = nullptr;  // not read
-    if (d_layer_image_or_null && (d_layer_image_or_null == d_layer_mask_or_null || d_layer_image_or_null == d_ref_image || d_layer_image_or_null == d_ref_mask ||
-                                  d_layer_mask_or_null == d_ref_image || d_layer_mask_or_null == d_ref_mask))
-        return fail(c, RSDSFM_ERR_INVALID, "deblur accumulate: the reference's and the layer's planes must be distinct");
-    if (!d_cells_or_null && !(first && last)) return fail(c, RSDSFM_ERR_INVALID, "deblur accumulate: the cells may be NULL only with first and last");
-    if (((uintptr_t)d_ref_image | (uintptr_t)d_ref_mask | (uintptr_t)d_layer_image_or_null | (uintptr_t)d_layer_mask_or_null) & 3u)
-        return fail(c, RSDSFM_ERR_INVALID, "deblur: every plane must be 4-byte aligned");
-    if (((uintptr_t)d_cells_or_null | (uintptr_t)d_sums8_or_null | (uintptr_t)d_sharp4_or_null) & 7u)
-        return fail(c, RSDSFM_ERR_INVALID, "deblur accumulate: the cells and the records must be 8-byte aligned");
-    const void* in[7] = {d_ref_image, d_ref_mask, d_layer_image_or_null, d_layer_mask_or_null, d_cells_or_null, d_sums8_or_null, d_sharp4_or_null};
-    const void* io[4] = {d_image_out, d_mask_out, d_weight_or_null, d_counts3_or_null};
-    for (int i = 0; i < 4; ++i)
-        for (int j = 0; j < 7 && io[i]; ++j)
-            if (in[j] == io[i]) return fail(c, RSDSFM_ERR_INVALID, "deblur accumulate: an output may not be an input, a record or the cells");
-    for (int j = 0; j < 7 && d_cells_or_null; ++j)
-        if (j != 4 && in[j] == (const void*)d_cells_or_null) return fail(c, RSDSFM_ERR_INVALID, "deblur accumulate: the cells may not be an input plane or a record");
+    AccumulateOutputs out{d_image_out, d_mask_out, d_weight_or_null, d_counts3_or_null};
+    const int rc = accumulate_check(c, "deblur", d_ref_image, d_ref_mask, d_layer_image_or_null, d_layer_mask_or_null, channels, rows, cols, d_cells_or_null,
+                                    {d_sums8_or_null, d_sharp4_or_null}, first, last, &out);
+    if (rc != RSDSFM_OK) return rc;
     return deblur_accumulate_launch(c, d_ref_image, d_ref_mask, d_layer_image_or_null, d_layer_mask_or_null, channels, rows, cols,
                                     reinterpret_cast<const unsigned long long*>(d_sums8_or_null), min_overlap ? min_overlap : kMinOverlapDefault, gain_mode,
                                     strength ? strength : kDeblurStrengthDefault, reinterpret_cast<const unsigned long long*>(d_sharp4_or_null), deblur_margin_value(margin),
-                                    min_pairs ? min_pairs : kDeblurMinPairsDefault, gate_mode, d_cells_or_null, first == 1, last == 1, d_image_out, d_mask_out,
-                                    d_weight_or_null, d_counts3_or_null);
+                                    min_pairs ? min_pairs : kDeblurMinPairsDefault, gate_mode, d_cells_or_null, first == 1, last == 1, out.image, out.mask,
+                                    out.weight, out.counts);
 }
 
 int rsdsfm_deblur_frame_dev(rsdsfm_ctx* ctx, const uint8_t* const* d_images, int32_t channels, const double* const* d_depths_colmajor,
@@ -179,52 +143,38 @@ int rsdsfm_deblur_frame_dev(rsdsfm_ctx* ctx, const uint8_t* const* d_images, int
     if (nsrc < 1 || nsrc > kDeblurSourcesMax) return fail(c, RSDSFM_ERR_INVALID, "deblur frame: nsrc must be in [1, 8]");
     rsdsfm_deblur_params dp;
     if (!deblur_params_resolve(params_or_null, &dp)) return fail(c, RSDSFM_ERR_INVALID, kDeblurParamsMessage);
-    if (!d_images || !d_depths_colmajor || !d_R_rows9 || !d_t_rows3) return fail(c, RSDSFM_ERR_INVALID, "deblur frame: null source array");
-    for (int k = 0; k < nsrc; ++k)
-        if (!d_images[k] || !d_depths_colmajor[k] || !d_R_rows9[k] || !d_t_rows3[k] || d_images[k] == d_image_out || d_images[k] == d_mask_out ||
-            (d_weight_or_null && d_images[k] == d_weight_or_null) || ((uintptr_t)d_images[k] & 3u))
-            return fail(c, RSDSFM_ERR_INVALID, "deblur frame: null, misaligned or aliased source pointer");
-    if (!M || !m || !finite_all(M, 9 * nsrc) || !finite_all(m, 3 * nsrc)) return fail(c, RSDSFM_ERR_INVALID, "deblur frame: the poses (M, m) must be given and finite");
-    rc = deblur_outputs_check(c, d_image_out, d_mask_out, d_weight_or_null, d_counts3_or_null);
+    rc = frame_sources_check(c, "deblur frame", d_images, d_depths_colmajor, d_R_rows9, d_t_rows3, nsrc, {d_image_out, d_mask_out, d_weight_or_null});
+    if (rc == RSDSFM_OK) rc = frame_poses_check(c, "deblur frame", M, m, nsrc);
+    if (rc == RSDSFM_OK) rc = output_planes_check(c, "deblur", {d_image_out, d_mask_out, d_weight_or_null}, d_counts3_or_null, false);
     if (rc != RSDSFM_OK) return rc;
     if (((uintptr_t)d_sharp_records_or_null & 7u) ||
         (d_sharp_records_or_null && ((const void*)d_sharp_records_or_null == d_image_out || (const void*)d_sharp_records_or_null == d_mask_out ||
                                      (const void*)d_sharp_records_or_null == d_weight_or_null || (const void*)d_sharp_records_or_null == d_counts3_or_null)))
         return fail(c, RSDSFM_ERR_INVALID, "deblur frame: the sharpness records must be 8-byte aligned and no output");
     int32_t full[4];
-    const int32_t* window = window_or_full(window_or_null, rows, cols, full);
-    if (!window) return fail(c, RSDSFM_ERR_INVALID, "deblur frame: the window (r0, c0, h, w) needs h >= 1, w >= 1 and must lie inside the frame");
+    const int32_t* window = nullptr;
+    rc = frame_window(c, "deblur frame", window_or_null, rows, cols, full, &window);
+    if (rc != RSDSFM_OK) return rc;
     DenseWs* ws = nullptr;
     rc = deblur_ws(c, rows, cols, &ws);
     if (rc != RSDSFM_OK) return rc;
-    const size_t plane = (size_t)rows * (size_t)cols, P = blend_plane_bytes(rows, cols);
-    uint8_t* rmask = ws->d_denoise;  // the denoise's layout (denoise.hpp)
-    uint8_t* rsource = ws->d_denoise + P;
-    uint8_t* rimage = ws->d_denoise + 2 * P;
-    uint16_t* cells = reinterpret_cast<uint16_t*>(ws->d_denoise + 5 * P);
-    uint8_t* lmask = ws->d_layer + P;  // the blend's layer A and its record (stabilize_blend.hpp)
-    uint8_t* limage = ws->d_layer + 2 * P;
-    uint64_t* record = reinterpret_cast<uint64_t*>(ws->d_layer + 5 * P);
-    rc = render_reference(ctx, "deblur frame", d_images[0], channels, d_depths_colmajor[0], d_R_rows9[0], d_t_rows3[0], fx, fy, cx, cy, rows, cols, mode, q5_mode, iterations,
-                          M, m, window, rimage, rmask, rsource);
+    const RenderGeom g{channels, fx, fy, cx, cy, rows, cols, mode, q5_mode, iterations};
+    const DenoisePlanes r = denoise_planes(ws->d_denoise, rows, cols);
+    const BlendLayer l = blend_layer(ws->d_layer, rows, cols);
+    rc = render_reference(ctx, "deblur frame", source_view(d_images, d_depths_colmajor, d_R_rows9, d_t_rows3, 0), g, M, m, window, r.rimage, r.rmask, r.rsource);
     if (rc != RSDSFM_OK) return rc;
     if (nsrc == 1)
-        return rsdsfm_deblur_accumulate_dev(ctx, rimage, rmask, nullptr, nullptr, channels, rows, cols, nullptr, dp.min_overlap, dp.gain_mode, dp.strength, nullptr, dp.margin,
+        return rsdsfm_deblur_accumulate_dev(ctx, r.rimage, r.rmask, nullptr, nullptr, channels, rows, cols, nullptr, dp.min_overlap, dp.gain_mode, dp.strength, nullptr, dp.margin,
                                             dp.min_pairs, dp.gate_mode, nullptr, 1, 1, d_image_out, d_mask_out, d_weight_or_null, d_counts3_or_null);
     for (int k = 1; k < nsrc; ++k) {
-        if (hipMemsetAsync(limage, 0, plane * (size_t)channels, c->stream) != hipSuccess || hipMemsetAsync(lmask, 0, plane, c->stream) != hipSuccess)
-            return fail(c, RSDSFM_ERR_HIP, "deblur frame: zeroing the layer failed");
-        const int id = 2;  // no source plane is passed: the id is not written anywhere
-        rc = render_candidate(ctx, dp.occlusion == 1, dp.occlusion_tol_q16, d_images[k], channels, d_depths_colmajor[k], d_R_rows9[k], d_t_rows3[k], fx, fy, cx, cy, rows, cols,
-                              mode, q5_mode, iterations, M + 9 * k, m + 3 * k, id, window, limage, lmask, nullptr, nullptr);
-        if (rc != RSDSFM_OK) return rc;
-        rc = rsdsfm_seam_overlap_sums_dev(ctx, rimage, rsource, limage, lmask, channels, rows, cols, record);
+        rc = neighbour_step(ctx, "deblur frame: zeroing the layer failed", dp.occlusion == 1, dp.occlusion_tol_q16, source_view(d_images, d_depths_colmajor, d_R_rows9, d_t_rows3, k),
+                            g, M + 9 * k, m + 3 * k, window, r.rimage, r.rsource, l.image, l.mask, l.record);
         if (rc != RSDSFM_OK) return rc;
         uint64_t* sharp = d_sharp_records_or_null ? d_sharp_records_or_null + 4 * (k - 1) : reinterpret_cast<uint64_t*>(ws->d_deblur);
-        rc = rsdsfm_deblur_sharpness_dev(ctx, rimage, rmask, limage, lmask, channels, rows, cols, record, dp.min_overlap, dp.gain_mode, sharp);
+        rc = rsdsfm_deblur_sharpness_dev(ctx, r.rimage, r.rmask, l.image, l.mask, channels, rows, cols, l.record, dp.min_overlap, dp.gain_mode, sharp);
         if (rc != RSDSFM_OK) return rc;
-        rc = rsdsfm_deblur_accumulate_dev(ctx, rimage, rmask, limage, lmask, channels, rows, cols, record, dp.min_overlap, dp.gain_mode, dp.strength, sharp, dp.margin,
-                                          dp.min_pairs, dp.gate_mode, cells, k == 1, k == nsrc - 1, d_image_out, d_mask_out, d_weight_or_null, d_counts3_or_null);
+        rc = rsdsfm_deblur_accumulate_dev(ctx, r.rimage, r.rmask, l.image, l.mask, channels, rows, cols, l.record, dp.min_overlap, dp.gain_mode, dp.strength, sharp, dp.margin,
+                                          dp.min_pairs, dp.gate_mode, r.cells, k == 1, k == nsrc - 1, d_image_out, d_mask_out, d_weight_or_null, d_counts3_or_null);
         if (rc != RSDSFM_OK) return rc;
     }
     return RSDSFM_OK;

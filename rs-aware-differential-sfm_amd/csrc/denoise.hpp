@@ -20,6 +20,14 @@ constexpr int kDenoiseTileRows = 16, kDenoiseTileCols = 64;  // one workgroup's 
 // DenseWs::d_denoise: [reference mask: P][reference source: P][reference image: 3 P][cells: 8 P], P = blend_plane_bytes (a multiple of 8, so
 // the cells are 8-byte aligned); apart from the blend's layer, which the neighbours are rendered onto while the cells hold the sums
 inline size_t denoise_ws_bytes(int rows, int cols) { return 13 * blend_plane_bytes(rows, cols); }
+struct DenoisePlanes {
+    unsigned char *rmask, *rsource, *rimage;
+    uint16_t* cells;
+};
+inline DenoisePlanes denoise_planes(unsigned char* d_denoise, int rows, int cols) {
+    const size_t P = blend_plane_bytes(rows, cols);
+    return DenoisePlanes{d_denoise, d_denoise + P, d_denoise + 2 * P, reinterpret_cast<uint16_t*>(d_denoise + 5 * P)};
+}
 
 // one step on c->stream (arguments checked by the caller; d_layer and d_lmask both NULL: no layer; d_sums NULL: no gain): the counters zeroed
 // by a memset when passed and `last`, then one launch

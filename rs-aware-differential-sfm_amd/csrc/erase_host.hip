@@ -27,7 +27,7 @@ bool erase_params_resolve(const rsdsfm_erase_params* in, EraseResolved* out) {
         out->open = kEraseOpenDefault, out->grow = kEraseGrowDefault, out->feather = kEraseFeatherDefault, out->include_undecided = 0;
         return plate_params_resolve(nullptr, &out->plate);
     }
-    if (in->struct_bytes != 0 && in->struct_bytes != (int32_t)sizeof(rsdsfm_erase_params)) return false;
+    if (!struct_bytes_ok(in->struct_bytes, sizeof(rsdsfm_erase_params))) return false;
     for (int i = 0; i < 5; ++i)
         if (in->reserved[i] != 0) return false;
     const rsdsfm_plate_params pp{in->radius, in->threshold, in->min_votes, in->gain_mode, in->occlusion, in->occlusion_tol_q16, 0, 0, in->min_overlap, {0, 0, 0, 0}};
@@ -39,19 +39,6 @@ bool erase_params_resolve(const rsdsfm_erase_params* in, EraseResolved* out) {
     out->include_undecided = in->include_undecided;
     return in->open >= -1 && in->open <= kEraseOpenMax && in->grow >= -1 && in->grow <= kEraseGrowMax && in->feather >= 0 && in->feather <= kEraseFeatherMax &&
            (in->include_undecided == 0 || in->include_undecided == 1);
-}
-
-// the argument checks of the frame call's outputs, before anything is enqueued
-int erase_outputs_check(Ctx* c, const uint8_t* d_image_out, const uint8_t* d_mask_out, const uint8_t* d_matte, const uint8_t* d_moving, const int64_t* d_counts5) {
-    if (!d_image_out || !d_mask_out) return fail(c, RSDSFM_ERR_INVALID, "erase: null output plane");
-    const void* o[5] = {d_image_out, d_mask_out, d_matte, d_moving, d_counts5};
-    for (int i = 0; i < 5; ++i)
-        for (int j = i + 1; j < 5; ++j)
-            if (o[i] && o[i] == o[j]) return fail(c, RSDSFM_ERR_INVALID, "erase: the output planes must be distinct");
-    if (((uintptr_t)d_image_out | (uintptr_t)d_mask_out | (uintptr_t)d_matte | (uintptr_t)d_moving) & 3u)
-        return fail(c, RSDSFM_ERR_INVALID, "erase: every plane must be 4-byte aligned");
-    if ((uintptr_t)d_counts5 & 7u) return fail(c, RSDSFM_ERR_INVALID, "erase: the counters must be 8-byte aligned");
-    return RSDSFM_OK;
 }
 
 }  // namespace
@@ -139,7 +126,7 @@ int rsdsfm_erase_frame_dev(rsdsfm_ctx* ctx, const uint8_t* const* d_images, int3
     if (nsrc < 1 || nsrc > kPlateSourcesMax) return fail(c, RSDSFM_ERR_INVALID, "erase frame: nsrc must be in [1, 15]");
     EraseResolved ep;
     if (!erase_params_resolve(params_or_null, &ep)) return fail(c, RSDSFM_ERR_INVALID, kEraseParamsMessage);
-    rc = erase_outputs_check(c, d_image_out, d_mask_out, d_matte_or_null, d_moving_or_null, d_counts5_or_null);
+    rc = output_planes_check(c, "erase", {d_image_out, d_mask_out, d_matte_or_null, d_moving_or_null}, d_counts5_or_null, true);
     if (rc != RSDSFM_OK) return rc;
     if (!d_images) return fail(c, RSDSFM_ERR_INVALID, "erase frame: null source array");
     for (int k = 0; k < nsrc; ++k)  // the plate call checks the sources against ITS outputs, which are the workspace's
@@ -159,13 +146,12 @@ int rsdsfm_erase_frame_dev(rsdsfm_ctx* ctx, const uint8_t* const* d_images, int3
     rc = rsdsfm_plate_frame_dev(ctx, d_images, channels, d_depths_colmajor, d_R_rows9, d_t_rows3, fx, fy, cx, cy, rows, cols, mode, q5_mode, iterations, nsrc, M, m, &ep.plate,
                                 window_or_null, pimage, pmask, nullptr, flag, nullptr);
     if (rc != RSDSFM_OK) return rc;
-    // 2. the own frame through the window with id 1 on zeroed planes: the plate call's reference planes, where it left them (plate.hpp's layout)
-    const uint8_t* rmask = ws->d_plate;
-    const uint8_t* rimage = ws->d_plate + 2 * P;
+    // 2. the own frame through the window with id 1 on zeroed planes: the plate call's reference planes, where it left them
+    const PlatePlanes r = plate_planes(ws->d_plate, rows, cols);
     // 3., 4.
     rc = rsdsfm_mover_matte_dev(ctx, flag, rows, cols, ep.open, ep.grow, ep.feather, ep.include_undecided, matte);
     if (rc != RSDSFM_OK) return rc;
-    return rsdsfm_erase_composite_dev(ctx, rimage, rmask, pimage, pmask, matte, channels, rows, cols, ep.feather, d_image_out, d_mask_out, d_counts5_or_null);
+    return rsdsfm_erase_composite_dev(ctx, r.rimage, r.rmask, pimage, pmask, matte, channels, rows, cols, ep.feather, d_image_out, d_mask_out, d_counts5_or_null);
 }
 
 int rsdsfm_erase_video_dev(rsdsfm_ctx* ctx, const uint8_t* const* d_frames, int32_t nsources, int32_t rows, int32_t cols, int32_t channels, double fx, double fy,

@@ -43,6 +43,15 @@ struct PlateArgs {
 // [layer 1 ...], P = blend_plane_bytes (a multiple of 8, so the records are 8-byte aligned and every plane 4)
 inline size_t plate_records_bytes() { return (size_t)kPlateLayersMax * 8 * sizeof(uint64_t); }
 inline size_t plate_ws_bytes(int rows, int cols, int layers) { return (5 + 4 * (size_t)layers) * blend_plane_bytes(rows, cols) + plate_records_bytes(); }
+struct PlatePlanes {
+    unsigned char *rmask, *rsource, *rimage;
+    uint64_t* records;
+    unsigned char* stack;  // layer j: its mask at stack + 4 P j, its image P behind
+};
+inline PlatePlanes plate_planes(unsigned char* d_plate, int rows, int cols) {
+    const size_t P = blend_plane_bytes(rows, cols);
+    return PlatePlanes{d_plate, d_plate + P, d_plate + 2 * P, reinterpret_cast<uint64_t*>(d_plate + 5 * P), d_plate + 5 * P + plate_records_bytes()};
+}
 
 // the params with every 0 of radius, threshold, min_votes and min_overlap replaced by its default, or the defaults for NULL; false: refused with
 // kPlateParamsMessage (plate_host.hip; the mover removal resolves the plate's fields of its own params with it)

@@ -9,7 +9,6 @@
 #include "rsdsfm_internal.hpp"
 #include "sequence_host.hpp"
 #include "stabilize_blend.hpp"
-#include "stabilize_visible.hpp"
 
 namespace rsdsfm {
 namespace {
@@ -17,19 +16,6 @@ namespace {
 rsdsfm_plate_params plate_defaults() {
     return rsdsfm_plate_params{RSDSFM_PLATE_RADIUS_DEFAULT, kPlateThresholdDefault, kPlateMinVotesDefault, 0, 0, 0, (int32_t)sizeof(rsdsfm_plate_params), 0, kMinOverlapDefault,
                                {0, 0, 0, 0}};
-}
-
-// the argument checks of the outputs, for the median call and, before anything is enqueued, for the frame call (whose input planes are the context's)
-int plate_outputs_check(Ctx* c, const uint8_t* d_image_out, const uint8_t* d_mask_out, const uint8_t* d_votes, const uint8_t* d_moving, const int64_t* d_counts4) {
-    if (!d_image_out || !d_mask_out) return fail(c, RSDSFM_ERR_INVALID, "plate: null output plane");
-    const void* o[5] = {d_image_out, d_mask_out, d_votes, d_moving, d_counts4};
-    for (int i = 0; i < 5; ++i)
-        for (int j = i + 1; j < 5; ++j)
-            if (o[i] && o[i] == o[j]) return fail(c, RSDSFM_ERR_INVALID, "plate: the output planes must be distinct");
-    if (((uintptr_t)d_image_out | (uintptr_t)d_mask_out | (uintptr_t)d_votes | (uintptr_t)d_moving) & 3u)
-        return fail(c, RSDSFM_ERR_INVALID, "plate: every plane must be 4-byte aligned");
-    if ((uintptr_t)d_counts4 & 7u) return fail(c, RSDSFM_ERR_INVALID, "plate: the counters must be 8-byte aligned");
-    return RSDSFM_OK;
 }
 
 // the workspace's reference planes, records and a stack of at least `layers` layers, made when first asked for and again when more layers are asked for
@@ -62,7 +48,7 @@ int plate_call_args(Ctx* c, const uint8_t* d_ref_image, const uint8_t* d_ref_mas
     if (min_overlap < 0 || (gain_mode != 0 && gain_mode != 1) || threshold < 0 || threshold > kPlateThresholdMax || min_votes < 0 || min_votes > kPlateMinVotesMax)
         return fail(c, RSDSFM_ERR_INVALID,
                     "plate median: min_overlap must be >= 0, gain_mode 0 or 1, threshold in [1, 255] (0: the default, 24) and min_votes in [1, 15] (0: the default, 3)");
-    int rc = plate_outputs_check(c, d_image_out, d_mask_out, d_votes_or_null, d_moving_or_null, d_counts4_or_null);
+    int rc = output_planes_check(c, "plate", {d_image_out, d_mask_out, d_votes_or_null, d_moving_or_null}, d_counts4_or_null, true);
     if (rc != RSDSFM_OK) return rc;
     if (!d_ref_image || !d_ref_mask || d_ref_image == d_ref_mask) return fail(c, RSDSFM_ERR_INVALID, "plate median: the reference needs its image and its mask");
     if (nlayers > 0 && (!d_layer_images || !d_layer_masks)) return fail(c, RSDSFM_ERR_INVALID, "plate median: the layers need their arrays of images and masks");
@@ -114,14 +100,14 @@ static_assert(kPlateSourcesMax == kClipSourcesMax, "a frame's sources are a Clip
 // the params with every 0 of radius, threshold, min_votes and min_overlap replaced by its default, or the defaults for NULL; false: refused
 bool plate_params_resolve(const rsdsfm_plate_params* in, rsdsfm_plate_params* out) {
     *out = in ? *in : plate_defaults();
-    if (out->struct_bytes != 0 && out->struct_bytes != (int32_t)sizeof(rsdsfm_plate_params)) return false;
+    if (!struct_bytes_ok(out->struct_bytes, sizeof(rsdsfm_plate_params))) return false;
     if (out->radius == 0) out->radius = RSDSFM_PLATE_RADIUS_DEFAULT;
     if (out->threshold == 0) out->threshold = kPlateThresholdDefault;
     if (out->min_votes == 0) out->min_votes = kPlateMinVotesDefault;
     if (out->min_overlap == 0) out->min_overlap = kMinOverlapDefault;
     return out->radius >= 1 && out->radius <= kPlateRadiusMax && out->threshold >= 1 && out->threshold <= kPlateThresholdMax && out->min_votes >= 1 &&
-           out->min_votes <= kPlateMinVotesMax && out->min_overlap >= 0 && (out->gain_mode == 0 || out->gain_mode == 1) && (out->occlusion == 0 || out->occlusion == 1) &&
-           out->occlusion_tol_q16 >= 0 && out->occlusion_tol_q16 <= kVisibleTolQ16Max;
+           out->min_votes <= kPlateMinVotesMax && out->min_overlap >= 0 && (out->gain_mode == 0 || out->gain_mode == 1) &&
+           occlusion_words_ok(out->occlusion, out->occlusion_tol_q16);
 }
 
 const char* const kPlateParamsMessage =
@@ -201,49 +187,35 @@ int rsdsfm_plate_frame_dev(rsdsfm_ctx* ctx, const uint8_t* const* d_images, int3
     if (nsrc < 1 || nsrc > kPlateSourcesMax) return fail(c, RSDSFM_ERR_INVALID, "plate frame: nsrc must be in [1, 15]");
     rsdsfm_plate_params pp;
     if (!plate_params_resolve(params_or_null, &pp)) return fail(c, RSDSFM_ERR_INVALID, kPlateParamsMessage);
-    if (!d_images || !d_depths_colmajor || !d_R_rows9 || !d_t_rows3) return fail(c, RSDSFM_ERR_INVALID, "plate frame: null source array");
-    for (int k = 0; k < nsrc; ++k)
-        if (!d_images[k] || !d_depths_colmajor[k] || !d_R_rows9[k] || !d_t_rows3[k] || d_images[k] == d_image_out || d_images[k] == d_mask_out ||
-            (d_votes_or_null && d_images[k] == d_votes_or_null) || (d_moving_or_null && d_images[k] == d_moving_or_null) || ((uintptr_t)d_images[k] & 3u))
-            return fail(c, RSDSFM_ERR_INVALID, "plate frame: null, misaligned or aliased source pointer");
-    if (!M || !m || !finite_all(M, 9 * nsrc) || !finite_all(m, 3 * nsrc))
-        return fail(c, RSDSFM_ERR_INVALID, "plate frame: the poses (M, m) must be given and finite");
-    rc = plate_outputs_check(c, d_image_out, d_mask_out, d_votes_or_null, d_moving_or_null, d_counts4_or_null);
-    if (rc != RSDSFM_OK) return rc;
+    rc = frame_sources_check(c, "plate frame", d_images, d_depths_colmajor, d_R_rows9, d_t_rows3, nsrc, {d_image_out, d_mask_out, d_votes_or_null, d_moving_or_null});
+    if (rc == RSDSFM_OK) rc = frame_poses_check(c, "plate frame", M, m, nsrc);
+    if (rc == RSDSFM_OK) rc = output_planes_check(c, "plate", {d_image_out, d_mask_out, d_votes_or_null, d_moving_or_null}, d_counts4_or_null, true);
     int32_t full[4];
-    const int32_t* window = window_or_full(window_or_null, rows, cols, full);
-    if (!window) return fail(c, RSDSFM_ERR_INVALID, "plate frame: the window (r0, c0, h, w) needs h >= 1, w >= 1 and must lie inside the frame");
+    const int32_t* window = nullptr;
+    if (rc == RSDSFM_OK) rc = frame_window(c, "plate frame", window_or_null, rows, cols, full, &window);
+    if (rc != RSDSFM_OK) return rc;
     DenseWs* ws = nullptr;
     const int nl = nsrc - 1;
     rc = plate_ws(c, rows, cols, nl, &ws);
     if (rc != RSDSFM_OK) return rc;
-    const size_t plane = (size_t)rows * (size_t)cols, P = blend_plane_bytes(rows, cols);
-    uint8_t* rmask = ws->d_plate;
-    uint8_t* rsource = ws->d_plate + P;
-    uint8_t* rimage = ws->d_plate + 2 * P;
-    uint64_t* records = reinterpret_cast<uint64_t*>(ws->d_plate + 5 * P);
-    uint8_t* stack = ws->d_plate + 5 * P + plate_records_bytes();
-    rc = render_reference(ctx, "plate frame", d_images[0], channels, d_depths_colmajor[0], d_R_rows9[0], d_t_rows3[0], fx, fy, cx, cy, rows, cols, mode, q5_mode, iterations, M,
-                          m, window, rimage, rmask, rsource);
+    const RenderGeom g{channels, fx, fy, cx, cy, rows, cols, mode, q5_mode, iterations};
+    const size_t P = blend_plane_bytes(rows, cols);
+    const PlatePlanes r = plate_planes(ws->d_plate, rows, cols);
+    rc = render_reference(ctx, "plate frame", source_view(d_images, d_depths_colmajor, d_R_rows9, d_t_rows3, 0), g, M, m, window, r.rimage, r.rmask, r.rsource);
     if (rc != RSDSFM_OK) return rc;
     const uint8_t *limages[kPlateLayersMax], *lmasks[kPlateLayersMax];
     for (int k = 1; k < nsrc; ++k) {
-        uint8_t* lmask = stack + 4 * P * (size_t)(k - 1);  // every neighbour its own layer: the median sees them all at once
+        uint8_t* lmask = r.stack + 4 * P * (size_t)(k - 1);  // every neighbour its own layer: the median sees them all at once
         uint8_t* limage = lmask + P;
         limages[k - 1] = limage;
         lmasks[k - 1] = lmask;
-        if (hipMemsetAsync(limage, 0, plane * (size_t)channels, c->stream) != hipSuccess || hipMemsetAsync(lmask, 0, plane, c->stream) != hipSuccess)
-            return fail(c, RSDSFM_ERR_HIP, "plate frame: zeroing a layer failed");
-        const int id = 2;  // no source plane is passed: the id is not written anywhere
-        rc = render_candidate(ctx, pp.occlusion == 1, pp.occlusion_tol_q16, d_images[k], channels, d_depths_colmajor[k], d_R_rows9[k], d_t_rows3[k], fx, fy, cx, cy, rows, cols,
-                              mode, q5_mode, iterations, M + 9 * k, m + 3 * k, id, window, limage, lmask, nullptr, nullptr);
-        if (rc != RSDSFM_OK) return rc;
-        rc = rsdsfm_seam_overlap_sums_dev(ctx, rimage, rsource, limage, lmask, channels, rows, cols, records + 8 * (size_t)(k - 1));
+        rc = neighbour_step(ctx, "plate frame: zeroing a layer failed", pp.occlusion == 1, pp.occlusion_tol_q16, source_view(d_images, d_depths_colmajor, d_R_rows9, d_t_rows3, k), g,
+                            M + 9 * k, m + 3 * k, window, r.rimage, r.rsource, limage, lmask, r.records + 8 * (size_t)(k - 1));
         if (rc != RSDSFM_OK) return rc;
     }
     // the public entry point of the context's estimator (rsdsfm_set_plate_estimator): the one place where the two part
     const auto estimate = c->plate_estimator == RSDSFM_PLATE_MEDOID ? rsdsfm_plate_medoid_dev : rsdsfm_plate_median_dev;
-    return estimate(ctx, rimage, rmask, nl ? limages : nullptr, nl ? lmasks : nullptr, nl, channels, rows, cols, nl ? records : nullptr, pp.min_overlap, pp.gain_mode,
+    return estimate(ctx, r.rimage, r.rmask, nl ? limages : nullptr, nl ? lmasks : nullptr, nl, channels, rows, cols, nl ? r.records : nullptr, pp.min_overlap, pp.gain_mode,
                     pp.threshold, pp.min_votes, d_image_out, d_mask_out, d_votes_or_null, d_moving_or_null, d_counts4_or_null);
 }
 

@@ -14,7 +14,6 @@
 #include "sequence_host.hpp"
 #include "stabilize.hpp"
 #include "stabilize_blend.hpp"
-#include "stabilize_visible.hpp"
 
 namespace rsdsfm {
 namespace {
@@ -26,9 +25,8 @@ rsdsfm_retime_params retime_defaults() {
 // the params, or the defaults for NULL; false: refused
 bool retime_params_resolve(const rsdsfm_retime_params* in, rsdsfm_retime_params* out) {
     *out = in ? *in : retime_defaults();
-    if (out->struct_bytes != 0 && out->struct_bytes != (int32_t)sizeof(rsdsfm_retime_params)) return false;
-    return out->threshold >= 0 && out->threshold <= kRetimeThresholdMax && (out->occlusion == 0 || out->occlusion == 1) && out->occlusion_tol_q16 >= 0 &&
-           out->occlusion_tol_q16 <= kVisibleTolQ16Max;
+    if (!struct_bytes_ok(out->struct_bytes, sizeof(rsdsfm_retime_params))) return false;
+    return out->threshold >= 0 && out->threshold <= kRetimeThresholdMax && occlusion_words_ok(out->occlusion, out->occlusion_tol_q16);
 }
 
 const char* const kRetimeParamsMessage =
@@ -159,33 +157,28 @@ int rsdsfm_retime_frame_dev(rsdsfm_ctx* ctx, const uint8_t* const* d_images, int
     if (nsrc == 1 && weight_q16 != 0) return fail(c, RSDSFM_ERR_INVALID, "retime frame: with one source the weight must be 0");
     rsdsfm_retime_params rp;
     if (!retime_params_resolve(params_or_null, &rp)) return fail(c, RSDSFM_ERR_INVALID, kRetimeParamsMessage);
-    if (!d_images || !d_depths_colmajor || !d_R_rows9 || !d_t_rows3) return fail(c, RSDSFM_ERR_INVALID, "retime frame: null source array");
-    for (int k = 0; k < nsrc; ++k)
-        if (!d_images[k] || !d_depths_colmajor[k] || !d_R_rows9[k] || !d_t_rows3[k] || d_images[k] == d_image_out || ((uintptr_t)d_images[k] & 3u))
-            return fail(c, RSDSFM_ERR_INVALID, "retime frame: null, misaligned or aliased source pointer");
-    if (!M18 || !m6 || !finite_all(M18, 9 * nsrc) || !finite_all(m6, 3 * nsrc))
-        return fail(c, RSDSFM_ERR_INVALID, "retime frame: the poses (M, m) must be given and finite");
-    rc = retime_merge_check(c, nullptr, nullptr, nullptr, nullptr, false, channels, rows, cols, weight_q16, rp.threshold, d_image_out, d_mask_out, d_source_or_null,
-                            d_counts5_or_null);
-    if (rc != RSDSFM_OK) return rc;
+    rc = frame_sources_check(c, "retime frame", d_images, d_depths_colmajor, d_R_rows9, d_t_rows3, nsrc, {d_image_out});  // the image output alone (DESIGN's known gaps)
+    if (rc == RSDSFM_OK) rc = frame_poses_check(c, "retime frame", M18, m6, nsrc);
+    if (rc == RSDSFM_OK)
+        rc = retime_merge_check(c, nullptr, nullptr, nullptr, nullptr, false, channels, rows, cols, weight_q16, rp.threshold, d_image_out, d_mask_out, d_source_or_null,
+                                d_counts5_or_null);
     int32_t full[4];
-    const int32_t* window = window_or_full(window_or_null, rows, cols, full);
-    if (!window) return fail(c, RSDSFM_ERR_INVALID, "retime frame: the window (r0, c0, h, w) needs h >= 1, w >= 1 and must lie inside the frame");
+    const int32_t* window = nullptr;
+    if (rc == RSDSFM_OK) rc = frame_window(c, "retime frame", window_or_null, rows, cols, full, &window);
+    if (rc != RSDSFM_OK) return rc;
     DenseWs* ws = nullptr;
     rc = rectify_dense_ws(c, rows, cols, &ws);  // a size change releases the layers with the rest
     if (rc != RSDSFM_OK) return rc;
     rc = ensure_plane(c, &ws->d_layer, blend_layer_bytes(rows, cols), "retime frame: no memory for layer A");
     if (rc == RSDSFM_OK && nsrc == 2) rc = ensure_plane(c, &ws->d_layer2, retime_layer2_bytes(rows, cols), "retime frame: no memory for layer B");
     if (rc != RSDSFM_OK) return rc;
-    const size_t plane = (size_t)rows * (size_t)cols, P = blend_plane_bytes(rows, cols);
-    uint8_t* lmask[2] = {ws->d_layer + P, nsrc == 2 ? ws->d_layer2 : nullptr};
-    uint8_t* limage[2] = {ws->d_layer + 2 * P, nsrc == 2 ? ws->d_layer2 + P : nullptr};
+    const RenderGeom g{channels, fx, fy, cx, cy, rows, cols, mode, q5_mode, iterations};
+    const BlendLayer a = blend_layer(ws->d_layer, rows, cols);
+    uint8_t* lmask[2] = {a.mask, nsrc == 2 ? ws->d_layer2 : nullptr};
+    uint8_t* limage[2] = {a.image, nsrc == 2 ? ws->d_layer2 + blend_plane_bytes(rows, cols) : nullptr};
     for (int k = 0; k < nsrc; ++k) {
-        if (hipMemsetAsync(limage[k], 0, plane * (size_t)channels, c->stream) != hipSuccess || hipMemsetAsync(lmask[k], 0, plane, c->stream) != hipSuccess)
-            return fail(c, RSDSFM_ERR_HIP, "retime frame: zeroing a layer failed");
-        const int id = k == 0 ? RSDSFM_RETIME_FROM_A : RSDSFM_RETIME_FROM_B;  // no source plane is passed: the id is not written anywhere
-        rc = render_candidate(ctx, rp.occlusion == 1, rp.occlusion_tol_q16, d_images[k], channels, d_depths_colmajor[k], d_R_rows9[k], d_t_rows3[k], fx, fy, cx, cy, rows, cols,
-                              mode, q5_mode, iterations, M18 + 9 * k, m6 + 3 * k, id, window, limage[k], lmask[k], nullptr, nullptr);
+        rc = render_layer(ctx, "retime frame: zeroing a layer failed", rp.occlusion == 1, rp.occlusion_tol_q16, source_view(d_images, d_depths_colmajor, d_R_rows9, d_t_rows3, k), g,
+                          M18 + 9 * k, m6 + 3 * k, k == 0 ? RSDSFM_RETIME_FROM_A : RSDSFM_RETIME_FROM_B, window, limage[k], lmask[k]);
         if (rc != RSDSFM_OK) return rc;
     }
     // the public entry point itself, so that it runs the code it runs alone

@@ -20,7 +20,7 @@ rsdsfm_shutter_params shutter_defaults() {
 // the params, or the defaults for NULL; false: refused (the shutter's range against the clip is rsdsfm_shutter_times')
 bool shutter_params_resolve(const rsdsfm_shutter_params* in, rsdsfm_shutter_params* out) {
     *out = in ? *in : shutter_defaults();
-    if (out->struct_bytes != 0 && out->struct_bytes != (int32_t)sizeof(rsdsfm_shutter_params)) return false;
+    if (!struct_bytes_ok(out->struct_bytes, sizeof(rsdsfm_shutter_params))) return false;
     return out->samples >= 1 && out->samples <= kShutterSamplesMax && out->min_samples >= 1 && out->min_samples <= out->samples;
 }
 
@@ -30,16 +30,6 @@ const char* const kShutterParamsMessage =
 int shutter_shape_check(Ctx* c, int channels, int rows, int cols) {
     if (!frame_size_ok(rows, cols)) return fail(c, RSDSFM_ERR_INVALID, "shutter: rows and cols must be in [2, 16384]");
     if (channels != 1 && channels != 3) return fail(c, RSDSFM_ERR_INVALID, "shutter: channels must be 1 or 3");
-    return RSDSFM_OK;
-}
-
-// the argument checks of the outputs, for the accumulate call and, before anything is enqueued, for the frame call (whose sample and cells are the context's)
-int shutter_outputs_check(Ctx* c, const uint8_t* d_image_out, const uint8_t* d_mask_out, const uint8_t* d_coverage, const int64_t* d_counts3) {
-    if (!d_image_out || !d_mask_out) return fail(c, RSDSFM_ERR_INVALID, "shutter: null output plane");
-    if (d_image_out == d_mask_out || (d_coverage && (d_coverage == d_image_out || d_coverage == d_mask_out)))
-        return fail(c, RSDSFM_ERR_INVALID, "shutter: the output planes must be distinct");
-    if (((uintptr_t)d_image_out | (uintptr_t)d_mask_out | (uintptr_t)d_coverage) & 3u) return fail(c, RSDSFM_ERR_INVALID, "shutter: every plane must be 4-byte aligned");
-    if ((uintptr_t)d_counts3 & 7u) return fail(c, RSDSFM_ERR_INVALID, "shutter: the counters must be 8-byte aligned");
     return RSDSFM_OK;
 }
 
@@ -176,7 +166,7 @@ int rsdsfm_shutter_accumulate_dev(rsdsfm_ctx* ctx, const uint8_t* d_image, const
     int rc = shutter_shape_check(c, channels, rows, cols);
     if (rc != RSDSFM_OK) return rc;
     if (last) {
-        rc = shutter_outputs_check(c, d_image_out, d_mask_out, d_coverage_or_null, d_counts3_or_null);
+        rc = output_planes_check(c, "shutter", {d_image_out, d_mask_out, d_coverage_or_null}, d_counts3_or_null, false);
         if (rc != RSDSFM_OK) return rc;
     } else {  // the outputs are not read
         d_image_out = d_mask_out = d_coverage_or_null = nullptr;
@@ -211,7 +201,7 @@ int rsdsfm_shutter_frame_dev(rsdsfm_ctx* ctx, const uint8_t* const* d_frames, in
     if (!shutter_params_resolve(shutter_or_null, &sp)) return fail(c, RSDSFM_ERR_INVALID, kShutterParamsMessage);
     rc = shutter_clip_check(c, d_frames, nsources, d_depth_maps, d_R, d_t, A, c_, A_path, c_path, scales);
     if (rc != RSDSFM_OK) return rc;
-    rc = shutter_outputs_check(c, d_image_out, d_mask_out, d_coverage_or_null, d_counts3_or_null);
+    rc = output_planes_check(c, "shutter", {d_image_out, d_mask_out, d_coverage_or_null}, d_counts3_or_null, false);
     if (rc != RSDSFM_OK) return rc;
     rc = shutter_alias_check(c, d_frames, nsources, d_image_out, d_mask_out, d_coverage_or_null);
     if (rc != RSDSFM_OK) return rc;

@@ -27,6 +27,14 @@ __host__ __device__ inline unsigned seam_gain(const unsigned long long* sums, in
 // layer A is this layer (retime_host.hip)
 inline size_t blend_plane_bytes(int rows, int cols) { return ((size_t)rows * (size_t)cols + 7u) & ~(size_t)7u; }
 inline size_t blend_layer_bytes(int rows, int cols) { return 5 * blend_plane_bytes(rows, cols) + 8 * sizeof(uint64_t); }
+struct BlendLayer {
+    unsigned char *dist, *mask, *image;
+    uint64_t* record;
+};
+inline BlendLayer blend_layer(unsigned char* d_layer, int rows, int cols) {
+    const size_t P = blend_plane_bytes(rows, cols);
+    return BlendLayer{d_layer, d_layer + P, d_layer + 2 * P, reinterpret_cast<uint64_t*>(d_layer + 5 * P)};
+}
 
 // the two launches of the seam distance on c->stream (arguments checked by the caller): rows, then columns; d_h is the row pass's plane
 int seam_distance_launch(Ctx* c, const unsigned char* d_mask, int rows, int cols, int feather, unsigned char* d_h, unsigned char* d_dist);

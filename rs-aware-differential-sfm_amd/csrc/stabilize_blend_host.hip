@@ -25,7 +25,7 @@ rsdsfm_stabilize_blend_params blend_defaults() {
 // the params with every 0 replaced by its default; false: refused
 bool blend_params_resolve(const rsdsfm_stabilize_blend_params* in, rsdsfm_stabilize_blend_params* out) {
     *out = in ? *in : blend_defaults();
-    if (out->struct_bytes != 0 && out->struct_bytes != (int32_t)sizeof(rsdsfm_stabilize_blend_params)) return false;
+    if (!struct_bytes_ok(out->struct_bytes, sizeof(rsdsfm_stabilize_blend_params))) return false;
     if (out->feather == 0) out->feather = kFeatherDefault;
     if (out->min_overlap == 0) out->min_overlap = kMinOverlapDefault;
     return out->feather >= 1 && out->feather <= kFeatherMax && out->min_overlap >= 0 && (out->gain_mode == 0 || out->gain_mode == 1);
@@ -142,17 +142,14 @@ int rsdsfm_stabilize_video_blended_dev(rsdsfm_ctx* ctx, const uint8_t* const* d_
     const int radius = fill_params_or_null ? fill_params_or_null->radius : kBlendFillRadiusDefault;  // 0 .. 16: the inner call checked it
     const bool occ = visible_asked(fill_params_or_null);  // every layer is rendered through the occlusion test (the inner call checked the words)
     const int offs = 2 * radius;
-    const size_t plane = (size_t)rows * (size_t)cols, P = blend_plane_bytes(rows, cols);
+    const size_t plane = (size_t)rows * (size_t)cols;
     const bool have = window_out[2] >= 1, host = gains_or_null || blend_counts_or_null;
     DenseWs* ws = nullptr;
     rc = rectify_dense_ws(c, rows, cols, &ws);
     if (rc != RSDSFM_OK) return rc;
     rc = ensure_plane(c, &ws->d_layer, blend_layer_bytes(rows, cols), "blend: no memory for the distance plane and the layer");
     if (rc != RSDSFM_OK) return rc;
-    uint8_t* d_dist = ws->d_layer;
-    uint8_t* d_lmask = ws->d_layer + P;
-    uint8_t* d_limage = ws->d_layer + 2 * P;
-    uint64_t* d_one = reinterpret_cast<uint64_t*>(ws->d_layer + 5 * P);  // the record of a call without host arrays: every layer's in turn
+    const BlendLayer l = blend_layer(ws->d_layer, rows, cols);  // l.record: the record of a call without host arrays, every layer's in turn
     // with a host array: per frame [sums: offs x 8][own: 1][(filled, blended): offs x 2], 8-byte words
     const size_t per = (size_t)offs * 8 + 1 + (size_t)offs * 2;
     uint64_t* d_rec = nullptr;
@@ -176,22 +173,22 @@ int rsdsfm_stabilize_video_blended_dev(rsdsfm_ctx* ctx, const uint8_t* const* d_
         rc = rsdsfm_stabilize_window_frame_dev(ctx, d_frames[p], channels, map, d_R[p], d_t[p], fx, fy, cx, cy, rows, cols, mode, q5_mode, iterations, M + 9 * (size_t)p,
                                                m + 3 * (size_t)p, 1, window_out, d_blend_images[p], d_blend_masks[p], d_blend_sources[p],
                                                rec ? reinterpret_cast<int64_t*>(rec + (size_t)offs * 8) : nullptr);
-        if (rc == RSDSFM_OK) rc = rsdsfm_seam_distance_dev(ctx, d_blend_masks[p], rows, cols, bp.feather, d_dist);
+        if (rc == RSDSFM_OK) rc = rsdsfm_seam_distance_dev(ctx, d_blend_masks[p], rows, cols, bp.feather, l.dist);
         listed = 0;
         if (rc == RSDSFM_OK && radius > 0 && rsdsfm_neighbour_poses(A, c_, A_s, c_s, scales, np, p, radius, frames, ids, nM, nm, &listed) != RSDSFM_OK)
             rc = fail(c, RSDSFM_ERR_INVALID, "blend: a neighbour's scale is not finite and positive");
         for (int k = 0; k < listed && rc == RSDSFM_OK; ++k) {
             const int n = frames[k], slot = ids[k] - 2;
-            if (hipMemsetAsync(d_limage, 0, plane * (size_t)channels, c->stream) != hipSuccess || hipMemsetAsync(d_lmask, 0, plane, c->stream) != hipSuccess) {
+            if (hipMemsetAsync(l.image, 0, plane * (size_t)channels, c->stream) != hipSuccess || hipMemsetAsync(l.mask, 0, plane, c->stream) != hipSuccess) {
                 rc = fail(c, RSDSFM_ERR_HIP, "blend: zeroing the layer failed");
                 break;
             }
             const double* nmap = d_fused_maps_or_null ? d_fused_maps_or_null[n] : d_depth_maps[n];
             rc = render_candidate(ctx, occ, occ ? fill_params_or_null->occlusion_tol_q16 : 0, d_frames[n], channels, nmap, d_R[n], d_t[n], fx, fy, cx, cy, rows, cols, mode,
-                                  q5_mode, iterations, nM + 9 * (size_t)k, nm + 3 * (size_t)k, ids[k], window_out, d_limage, d_lmask, nullptr, nullptr);
+                                  q5_mode, iterations, nM + 9 * (size_t)k, nm + 3 * (size_t)k, ids[k], window_out, l.image, l.mask, nullptr, nullptr);
             if (rc == RSDSFM_OK)
-                rc = rsdsfm_seam_blend_layer_dev(ctx, d_limage, d_lmask, channels, rows, cols, d_dist, &bp, ids[k], d_blend_images[p], d_blend_masks[p], d_blend_sources[p],
-                                                 rec ? rec + (size_t)slot * 8 : d_one,
+                rc = rsdsfm_seam_blend_layer_dev(ctx, l.image, l.mask, channels, rows, cols, l.dist, &bp, ids[k], d_blend_images[p], d_blend_masks[p], d_blend_sources[p],
+                                                 rec ? rec + (size_t)slot * 8 : l.record,
                                                  rec ? reinterpret_cast<int64_t*>(rec + (size_t)offs * 8 + 1 + (size_t)slot * 2) : nullptr);
         }
     }

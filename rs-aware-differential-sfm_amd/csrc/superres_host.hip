@@ -20,7 +20,7 @@ rsdsfm_superres_params superres_defaults() {
 // the params with every 0 of scale, radius, strength and min_overlap replaced by its default, or the defaults for NULL; false: refused
 bool superres_params_resolve(const rsdsfm_superres_params* in, rsdsfm_superres_params* out) {
     *out = in ? *in : superres_defaults();
-    if (out->struct_bytes != 0 && out->struct_bytes != (int32_t)sizeof(rsdsfm_superres_params)) return false;
+    if (!struct_bytes_ok(out->struct_bytes, sizeof(rsdsfm_superres_params))) return false;
     for (int i = 0; i < 5; ++i)
         if (out->reserved[i] != 0) return false;
     if (out->scale == 0) out->scale = kSuperresScaleDefault;
@@ -41,16 +41,6 @@ bool superres_scale_ok(int rows, int cols, int scale) {
 }
 
 const char* const kSuperresScaleMessage = "superres: scale must be in [1, 4] and scale * rows, scale * cols at most 16384";
-
-// the argument checks of the final outputs, for the accumulate call and, before anything is enqueued, for the frame call
-int superres_outputs_check(Ctx* c, const uint8_t* d_image_out, const uint8_t* d_mask_out, const uint8_t* d_weight, const int64_t* d_counts3) {
-    if (!d_image_out || !d_mask_out) return fail(c, RSDSFM_ERR_INVALID, "superres: null output plane");
-    if (d_image_out == d_mask_out || (d_weight && (d_weight == d_image_out || d_weight == d_mask_out)))
-        return fail(c, RSDSFM_ERR_INVALID, "superres: the output planes must be distinct");
-    if (((uintptr_t)d_image_out | (uintptr_t)d_mask_out | (uintptr_t)d_weight) & 3u) return fail(c, RSDSFM_ERR_INVALID, "superres: every plane must be 4-byte aligned");
-    if ((uintptr_t)d_counts3 & 7u) return fail(c, RSDSFM_ERR_INVALID, "superres: the counters must be 8-byte aligned");
-    return RSDSFM_OK;
-}
 
 // the workspace's fine planes, cells and record: made when first asked for and again when the scale changes (a size change releases them with the rest)
 int superres_ws(Ctx* c, int rows, int cols, int scale, DenseWs** ws) {
@@ -121,8 +111,9 @@ int rsdsfm_superres_render_dev(rsdsfm_ctx* ctx, const uint8_t* d_image_n, int32_
     if (!M9 || !m3 || !finite_all(M9, 9) || !finite_all(m3, 3))
         return fail(c, RSDSFM_ERR_INVALID, "superres render: the pose (M, m) must be given and finite");
     int32_t full[4];
-    const int32_t* window = window_or_full(window_or_null, rows, cols, full);
-    if (!window) return fail(c, RSDSFM_ERR_INVALID, "superres render: the window (r0, c0, h, w) needs h >= 1, w >= 1 and must lie inside the frame");
+    const int32_t* window = nullptr;
+    rc = frame_window(c, "superres render", window_or_null, rows, cols, full, &window);
+    if (rc != RSDSFM_OK) return rc;
     DenseWs* ws = nullptr;
     rc = rectify_dense_ws(c, rows, cols, &ws);
     if (rc != RSDSFM_OK) return rc;
@@ -147,7 +138,7 @@ int rsdsfm_superres_accumulate_dev(rsdsfm_ctx* ctx, const uint8_t* d_ref_bil, co
     if (min_overlap < 0 || (gain_mode != 0 && gain_mode != 1) || strength < 0 || strength > kSuperresStrengthMax)
         return fail(c, RSDSFM_ERR_INVALID, "superres accumulate: min_overlap must be >= 0, gain_mode 0 or 1 and strength in [1, 255] (0: the default, 12)");
     if (last) {
-        const int rc = superres_outputs_check(c, d_image_out, d_mask_out, d_weight_or_null, d_counts3_or_null);
+        const int rc = output_planes_check(c, "superres", {d_image_out, d_mask_out, d_weight_or_null}, d_counts3_or_null, false);
         if (rc != RSDSFM_OK) return rc;
     } else {  // the outputs are not read
         d_image_out = d_mask_out = d_weight_or_null = nullptr;
@@ -192,18 +183,13 @@ int rsdsfm_superres_frame_dev(rsdsfm_ctx* ctx, const uint8_t* const* d_images, i
     rsdsfm_superres_params sp;
     if (!superres_params_resolve(params_or_null, &sp)) return fail(c, RSDSFM_ERR_INVALID, kSuperresParamsMessage);
     if (!superres_scale_ok(rows, cols, sp.scale)) return fail(c, RSDSFM_ERR_INVALID, kSuperresScaleMessage);
-    if (!d_images || !d_depths_colmajor || !d_R_rows9 || !d_t_rows3) return fail(c, RSDSFM_ERR_INVALID, "superres frame: null source array");
-    for (int k = 0; k < nsrc; ++k)
-        if (!d_images[k] || !d_depths_colmajor[k] || !d_R_rows9[k] || !d_t_rows3[k] || d_images[k] == d_image_out || d_images[k] == d_mask_out ||
-            (d_weight_or_null && d_images[k] == d_weight_or_null) || ((uintptr_t)d_images[k] & 3u))
-            return fail(c, RSDSFM_ERR_INVALID, "superres frame: null, misaligned or aliased source pointer");
-    if (!M || !m || !finite_all(M, 9 * nsrc) || !finite_all(m, 3 * nsrc))
-        return fail(c, RSDSFM_ERR_INVALID, "superres frame: the poses (M, m) must be given and finite");
-    rc = superres_outputs_check(c, d_image_out, d_mask_out, d_weight_or_null, d_counts3_or_null);
-    if (rc != RSDSFM_OK) return rc;
+    rc = frame_sources_check(c, "superres frame", d_images, d_depths_colmajor, d_R_rows9, d_t_rows3, nsrc, {d_image_out, d_mask_out, d_weight_or_null});
+    if (rc == RSDSFM_OK) rc = frame_poses_check(c, "superres frame", M, m, nsrc);
+    if (rc == RSDSFM_OK) rc = output_planes_check(c, "superres", {d_image_out, d_mask_out, d_weight_or_null}, d_counts3_or_null, false);
     int32_t full[4];
-    const int32_t* window = window_or_full(window_or_null, rows, cols, full);
-    if (!window) return fail(c, RSDSFM_ERR_INVALID, "superres frame: the window (r0, c0, h, w) needs h >= 1, w >= 1 and must lie inside the frame");
+    const int32_t* window = nullptr;
+    if (rc == RSDSFM_OK) rc = frame_window(c, "superres frame", window_or_null, rows, cols, full, &window);
+    if (rc != RSDSFM_OK) return rc;
     DenseWs* ws = nullptr;
     rc = superres_ws(c, rows, cols, sp.scale, &ws);
     if (rc != RSDSFM_OK) return rc;
