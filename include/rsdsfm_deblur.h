@@ -31,9 +31,25 @@
  *
  * The defaults (margin 4, strength 24, the cap 32, radius 2) are choices, not measurements.
  *
- * NOT here: deconvolution or any single-frame sharpening; sharpness per scanline band (a rolling-shutter frame's blur varies down the frame,
- * tau is one number per layer); gates wider than 3 x 3 (a blur much wider than the window reads partly as disagreement); the mover flag fed
- * into the gate; the C++ mirror.
+ * Per scanline band (built since; tests/deblur_bands_spec_numpy.py is the definition, DESIGN.md section 12 "Sharpness per scanline band"): the
+ * rows of a rolling-shutter frame are exposed one after another, so shake blurs a frame differently down its rows, and one tau per layer is
+ * either 0 for the whole frame or a diluted value everywhere.  With band_rows = H, a multiple of 16 in [16, 16384]:
+ *   bands        band(y) = y / H, NB = ceil(rows / H) <= RSDSFM_DEBLUR_BANDS_MAX = 64; the last band may be short.
+ *   band records NB x 4 uint64, T_b = [pairs, A_R, A_L, 0]: the pairs of the sharpness record above, every pair (p, q) in the band of p, its
+ *                left or upper pixel (a vertical pair across a band border belongs to the upper band).  The sum of the T_b is T, exactly.
+ *   band tau     tau_b = tau(T_b) with the same margin and the same min_pairs, applied to the band.  No new knob.
+ *   row tau      centres c_b = b H + H / 2 (also for a short last band); tau(y) = tau_0 for y < c_0, tau_{NB-1} for y >= c_{NB-1}, else with
+ *                b = (y - H / 2) / H and f = (y - H / 2) - b H: tau(y) = (tau_b (H - f) + tau_{b+1} f + H / 2) / H, an integer in 0 .. 32.  The
+ *                interpolation keeps a band border from showing as a horizontal seam in sharpness.
+ *   step         the step above with u(p) = (w(p) tau(row of p) + 8) >> 4; u <= 32 per layer as before, so n <= 240, s_c <= 61 200 and the
+ *                limit of 7 layers per `first` hold unchanged.
+ * Consequences: NB = 1 gives the unbanded accumulate's bytes; every tau_b = 0 gives the own frame's bytes; no order of the layers changes a
+ * byte; a row both of whose surrounding bands have tau = 0 keeps its bytes.
+ *
+ * The band height's default (0: off) and the linear interpolation between band centres are choices, not measurements, too.
+ *
+ * NOT here: deconvolution or any single-frame sharpening; gates wider than 3 x 3 (a blur much wider than the window reads partly as
+ * disagreement); the mover flag fed into the gate; the C++ mirror.
  */
 #ifndef RSDSFM_DEBLUR_H
 #define RSDSFM_DEBLUR_H
@@ -48,6 +64,7 @@ extern "C" {
 #define RSDSFM_DEBLUR_LAYERS_MAX 7
 #define RSDSFM_DEBLUR_TAU_MAX 32
 #define RSDSFM_DEBLUR_MARGIN_MAX 64
+#define RSDSFM_DEBLUR_BANDS_MAX 64
 /* the defaults: choices, not measurements */
 #define RSDSFM_DEBLUR_RADIUS_DEFAULT 2
 #define RSDSFM_DEBLUR_STRENGTH_DEFAULT 24
@@ -65,11 +82,12 @@ typedef struct rsdsfm_deblur_params {
     int32_t struct_bytes;      /* 0 or sizeof(rsdsfm_deblur_params), as rsdsfm_deblur_params_init sets it; anything else is refused */
     int64_t min_overlap;       /* overlap pixels below which a neighbour gets no gain, >= 0; 0: the default, 1024 (the blend's) */
     int64_t min_pairs;         /* pixel pairs below which a neighbour's tau is 0, >= 0; 0: the default, 1024 */
-    int32_t reserved[4];       /* 0 */
+    int32_t band_rows;         /* rows per scanline band, a multiple of 16 in [16, 16384] with at most 64 bands; 0: off, one tau per neighbour */
+    int32_t reserved[3];       /* 0 */
 } rsdsfm_deblur_params;
 
 /* radius = 2, strength = 24, margin = 4, gate_mode = 0, gain_mode = 0, occlusion = 0, occlusion_tol_q16 = 0, min_overlap = 1024,
- * min_pairs = 1024, struct_bytes = sizeof.  A NULL params pointer means these values. */
+ * min_pairs = 1024, band_rows = 0, struct_bytes = sizeof.  A NULL params pointer means these values. */
 int rsdsfm_deblur_params_init(rsdsfm_deblur_params* params);
 
 /* The sharpness record of one layer against the reference, as defined above.  d_ref_image, d_layer_image: rows x cols x channels bytes,
@@ -112,13 +130,49 @@ int rsdsfm_deblur_accumulate_dev(rsdsfm_ctx* ctx, const uint8_t* d_ref_image, co
  * the workspace.  The reference planes, the cells and the layer are the denoise's planes of the context's dense workspace, the workspace's
  * sharpness record (32 B) joins it with the first call: a context that never asks keeps its footprint.  params->radius is not read here.
  * Returns without waiting.
- * RSDSFM_ERR_INVALID: nsrc outside [1, 8], a params field outside its range, bad struct_bytes, a misaligned record array or one that is an
- * output, and the list of rsdsfm_denoise_frame_dev. */
+ * With params->band_rows > 0 the two band calls stand where rsdsfm_deblur_sharpness_dev and rsdsfm_deblur_accumulate_dev stand (the launches are
+ * the same, rsdsfm_deblur_launches is unchanged), d_sharp_records_or_null is (nsrc - 1) x NB x 4 uint64 with neighbour j's band records at entry
+ * j NB, and without it the band records live in a 2 KB plane of the workspace (64 x 32 B), made with the first such call.
+ * RSDSFM_ERR_INVALID: nsrc outside [1, 8], a params field outside its range, bad struct_bytes, a band_rows that is neither 0 nor a multiple of
+ * 16 in [16, 16384] or gives more than 64 bands, a misaligned record array or one that is an output, and the list of rsdsfm_denoise_frame_dev. */
 int rsdsfm_deblur_frame_dev(rsdsfm_ctx* ctx, const uint8_t* const* d_images, int32_t channels, const double* const* d_depths_colmajor,
                             const double* const* d_R_rows9, const double* const* d_t_rows3, double fx, double fy, double cx, double cy, int32_t rows, int32_t cols,
                             int mode, int q5_mode, int32_t iterations, int32_t nsrc, const double* M, const double* m, const rsdsfm_deblur_params* params_or_null,
                             const int32_t* window_or_null, uint8_t* d_image_out, uint8_t* d_mask_out, uint8_t* d_weight_or_null, int64_t* d_counts3_or_null,
                             uint64_t* d_sharp_records_or_null);
+
+/* The band records of one layer against the reference, as defined above ("per scanline band"): rsdsfm_deblur_sharpness_dev's arguments, checks
+ * and refusals, with band_rows and d_band_records_out: NB x 4 uint64 on the DEVICE, NB = ceil(rows / band_rows), 8-byte aligned, distinct from every
+ * input.  One memset (NB x 32 B) and one launch (deblur_band_sharpness_kernel<CH>: the sharpness kernel with the workgroup's three sums added to
+ * record (16 blockIdx.y) / band_rows; the same three 64-bit integer atomics per workgroup: exact and independent of scheduling), enqueued on the
+ * context's stream; returns without waiting.  A refused call enqueues nothing.
+ * RSDSFM_ERR_INVALID: the list of rsdsfm_deblur_sharpness_dev, a band_rows that is no multiple of 16 in [16, 16384], more than 64 bands. */
+int rsdsfm_deblur_band_sharpness_dev(rsdsfm_ctx* ctx, const uint8_t* d_ref_image, const uint8_t* d_ref_mask, const uint8_t* d_layer_image, const uint8_t* d_layer_mask,
+                                     int32_t channels, int32_t rows, int32_t cols, const uint64_t* d_sums8_or_null, int64_t min_overlap, int32_t gain_mode,
+                                     int32_t band_rows, uint64_t* d_band_records_out);
+
+/* tau of each of nbands band records (records: HOST, nbands x 4; taus_out: HOST, nbands): rsdsfm_deblur_tau per record.  Host only, no context.
+ * RSDSFM_ERR_INVALID: a NULL pointer, nbands outside [1, 64], margin or min_pairs outside its range. */
+int rsdsfm_deblur_band_taus(const uint64_t* records, int32_t nbands, int32_t margin, int64_t min_pairs, int32_t* taus_out);
+
+/* tau of each of `rows` rows from the band taus, the interpolation defined above (taus: HOST, nbands, each 0 .. 32; row_taus_out: HOST, rows).
+ * Host only, no context.  RSDSFM_ERR_INVALID: a NULL pointer, a band_rows that is no multiple of 16 in [16, 16384], rows outside [2, 16384],
+ * nbands other than ceil(rows / band_rows) or above 64, a tau outside [0, 32]. */
+int rsdsfm_deblur_row_taus(const int32_t* taus, int32_t nbands, int32_t band_rows, int32_t rows, int32_t* row_taus_out);
+
+/* One step with a tau per row: rsdsfm_deblur_accumulate_dev's arguments, rules, checks and refusals (the same limit of 7 layers per `first`),
+ * with d_band_records_or_null, the layer's NB x 4 band records on the DEVICE (rsdsfm_deblur_band_sharpness_dev), in the record's place, and
+ * band_rows.  Three threads of every workgroup compute the taus of the tile's band and of the bands above and below it (one 64-bit integer
+ * division each), sixteen the tile's row taus; no read leaves the NB records.  A launch that is neither first nor last returns after reading the
+ * records where all three taus are 0: a blurred band of a sharp neighbour costs no image bytes.  With NB = 1 every byte, the cells included, is
+ * rsdsfm_deblur_accumulate_dev's.  One kernel launch (deblur_band_accumulate_kernel<CH, FIRST, LAST>), enqueued on the context's stream; returns
+ * without waiting.  A refused call enqueues nothing.
+ * RSDSFM_ERR_INVALID: the list of rsdsfm_deblur_accumulate_dev, a band_rows that is no multiple of 16 in [16, 16384], more than 64 bands. */
+int rsdsfm_deblur_band_accumulate_dev(rsdsfm_ctx* ctx, const uint8_t* d_ref_image, const uint8_t* d_ref_mask, const uint8_t* d_layer_image_or_null,
+                                      const uint8_t* d_layer_mask_or_null, int32_t channels, int32_t rows, int32_t cols, const uint64_t* d_sums8_or_null,
+                                      int64_t min_overlap, int32_t gain_mode, int32_t strength, const uint64_t* d_band_records_or_null, int32_t band_rows,
+                                      int32_t margin, int64_t min_pairs, int32_t gate_mode, uint16_t* d_cells_or_null, int32_t first, int32_t last,
+                                      uint8_t* d_image_out, uint8_t* d_mask_out, uint8_t* d_weight_or_null, int64_t* d_counts3_or_null);
 
 /* = nsrc rsdsfm_stabilize_window_launches(rows, cols) + 3 (nsrc - 1) (the sums, the sharpness and the accumulate per neighbour), or + 1 when
  * nsrc == 1.  RSDSFM_ERR_INVALID for a size outside [2, 16384] or nsrc outside [1, 8].  Host only. */
@@ -137,6 +191,19 @@ int rsdsfm_deblur_video_dev(rsdsfm_ctx* ctx, const uint8_t* const* d_frames, int
                             const double* c, const double* A_path, const double* c_path, const double* scales, int mode, int q5_mode, int32_t iterations,
                             const rsdsfm_deblur_params* params_or_null, const int32_t* window_or_null, uint8_t* const* d_out_images, uint8_t* const* d_out_masks,
                             uint8_t* const* d_out_weights_or_null, int64_t* counts_or_null, int32_t* taus_or_null);
+
+/* rsdsfm_deblur_video_dev with the band taus: band_taus_or_null: HOST, nsources x 6 x NB int32, NB = ceil(rows / params->band_rows): band b of the
+ * j-th listed neighbour of frame q at [(q 6 + j) NB + b], -1 behind the listed neighbours.  taus_or_null then gets the MAX over the bands of
+ * each listed neighbour's taus.  The per-frame device words are 3 + 4 * 6 * NB; with any of the three arrays the call ends with one copy and
+ * one wait.  rsdsfm_deblur_video_dev with band_rows > 0 is this call with NULL.  With band_rows = 0 both are the unbanded call and
+ * band_taus_or_null is filled as if NB = 1 (nsources x 6).
+ * RSDSFM_ERR_INVALID: the list of rsdsfm_deblur_video_dev. */
+int rsdsfm_deblur_video_banded_dev(rsdsfm_ctx* ctx, const uint8_t* const* d_frames, int32_t nsources, int32_t rows, int32_t cols, int32_t channels, double fx,
+                                   double fy, double cx, double cy, const double* const* d_depth_maps, const double* const* d_R, const double* const* d_t,
+                                   const double* A, const double* c, const double* A_path, const double* c_path, const double* scales, int mode, int q5_mode,
+                                   int32_t iterations, const rsdsfm_deblur_params* params_or_null, const int32_t* window_or_null, uint8_t* const* d_out_images,
+                                   uint8_t* const* d_out_masks, uint8_t* const* d_out_weights_or_null, int64_t* counts_or_null, int32_t* taus_or_null,
+                                   int32_t* band_taus_or_null);
 
 #ifdef __cplusplus
 }

@@ -3750,19 +3750,21 @@ DEBLUR_RADIUS_MAX = 3
 DEBLUR_LAYERS_MAX = 7
 DEBLUR_TAU_MAX = 32
 DEBLUR_TAUS_PER_FRAME = 2 * DEBLUR_RADIUS_MAX
+DEBLUR_BANDS_MAX = 64
 
 
 class DeblurParams(C.Structure):
     _fields_ = [("radius", C.c_int32), ("strength", C.c_int32), ("margin", C.c_int32), ("gate_mode", C.c_int32), ("gain_mode", C.c_int32), ("occlusion", C.c_int32),
-                ("occlusion_tol_q16", C.c_int32), ("struct_bytes", C.c_int32), ("min_overlap", C.c_int64), ("min_pairs", C.c_int64), ("reserved", C.c_int32 * 4)]
+                ("occlusion_tol_q16", C.c_int32), ("struct_bytes", C.c_int32), ("min_overlap", C.c_int64), ("min_pairs", C.c_int64), ("band_rows", C.c_int32), ("reserved3", C.c_int32 * 3)]
+    reserved = property(lambda self: [self.band_rows] + list(self.reserved3))  # the four words' name before the first meant anything
 
 
-def _deblur_params(radius=None, strength=None, margin=None, gate=True, gain=True, occlusion=False, occlusion_tol_q16=0, min_overlap=None, min_pairs=None):
-    """a DeblurParams with the given values over the defaults (None: the default; margin -1: none)"""
+def _deblur_params(radius=None, strength=None, margin=None, gate=True, gain=True, occlusion=False, occlusion_tol_q16=0, min_overlap=None, min_pairs=None, band_rows=None):
+    """a DeblurParams with the given values over the defaults (None: the default; margin -1: none; band_rows None or 0: one tau per neighbour)"""
     p = DeblurParams()
     if load_library().rsdsfm_deblur_params_init(C.byref(p)) != OK:
         raise RsdsfmError("rsdsfm_deblur_params_init failed")
-    for name, value in (("radius", radius), ("strength", strength), ("margin", margin), ("min_overlap", min_overlap), ("min_pairs", min_pairs)):
+    for name, value in (("radius", radius), ("strength", strength), ("margin", margin), ("min_overlap", min_overlap), ("min_pairs", min_pairs), ("band_rows", band_rows)):
         if value is not None:
             setattr(p, name, int(value))
     p.gate_mode, p.gain_mode, p.occlusion, p.occlusion_tol_q16 = 0 if gate else 1, 0 if gain else 1, int(occlusion), int(occlusion_tol_q16)
@@ -3770,11 +3772,11 @@ def _deblur_params(radius=None, strength=None, margin=None, gate=True, gain=True
 
 
 def deblur_default_params():
-    """the sharpness transfer's defaults as a dict: radius = 2, strength = 24, margin = 4, min_overlap = 1024, min_pairs = 1024
-    (rsdsfm_deblur_params_init); choices, not measurements"""
+    """the sharpness transfer's defaults as a dict: radius = 2, strength = 24, margin = 4, min_overlap = 1024, min_pairs = 1024, band_rows = 0
+    (off) (rsdsfm_deblur_params_init); choices, not measurements"""
     p = _deblur_params()
     return dict(radius=p.radius, strength=p.strength, margin=p.margin, gate_mode=p.gate_mode, gain_mode=p.gain_mode, occlusion=p.occlusion, min_overlap=p.min_overlap,
-                min_pairs=p.min_pairs)
+                min_pairs=p.min_pairs, band_rows=p.band_rows)
 
 
 def deblur_tau(sharp4, margin=0, min_pairs=0):
@@ -3786,6 +3788,29 @@ def deblur_tau(sharp4, margin=0, min_pairs=0):
     if rc != OK:
         raise RsdsfmError("rsdsfm_deblur_tau failed (%d): margin in [-1, 64], min_pairs >= 0" % rc)
     return int(out.value)
+
+
+def deblur_band_taus(records, margin=0, min_pairs=0):
+    """the factors 0 .. 32 of a layer's band records (NB, 4) [pairs, A_R, A_L, 0] (rsdsfm_deblur_band_taus; host only): deblur_tau per band
+    -> (NB,) int32"""
+    rec = np.ascontiguousarray(records, dtype=np.uint64).reshape(-1, 4)
+    out = np.full(max(rec.shape[0], 1), -1, dtype=np.int32)
+    rc = load_library().rsdsfm_deblur_band_taus(_p(rec), C.c_int32(rec.shape[0]), C.c_int32(margin), C.c_int64(min_pairs), _p(out))
+    if rc != OK:
+        raise RsdsfmError("rsdsfm_deblur_band_taus failed (%d): 1 .. 64 bands, margin in [-1, 64], min_pairs >= 0" % rc)
+    return out[:rec.shape[0]]
+
+
+def deblur_row_taus(taus, band_rows, rows):
+    """every row's factor from the band factors, interpolated between the band centres (rsdsfm_deblur_row_taus; host only;
+    tests/deblur_bands_spec_numpy.py's row_taus) -> (rows,) int32"""
+    t = np.ascontiguousarray(taus, dtype=np.int32).reshape(-1)
+    out = np.full(max(int(rows), 1), -1, dtype=np.int32)
+    rc = load_library().rsdsfm_deblur_row_taus(_p(t), C.c_int32(t.shape[0]), C.c_int32(band_rows), C.c_int32(rows), _p(out))
+    if rc != OK:
+        raise RsdsfmError("rsdsfm_deblur_row_taus failed (%d): band_rows a multiple of 16 in [16, 16384], rows in [2, 16384], ceil(rows / band_rows) <= 64 taus "
+                          "in [0, 32]" % rc)
+    return out[:int(rows)]
 
 
 def deblur_launches(rows, cols, nsrc):
@@ -3871,21 +3896,101 @@ class _DeblurMixin:
             self.synchronize()
             return d_out.cpu().numpy(), d_mask.cpu().numpy(), d_w.cpu().numpy(), d_cnt.cpu().numpy(), d_T.cpu().numpy().view(np.uint64)[:len(layers)]
 
+    def deblur_band_sharpness_dev(self, d_ref, d_ref_mask, d_layer, d_layer_mask, channels, rows, cols, band_rows, d_band_records, d_sums8=None, min_overlap=0,
+                                  gain_mode=0):
+        """a layer's sharpness records per band of band_rows rows (rsdsfm_deblur_band_sharpness_dev; tests/deblur_bands_spec_numpy.py's
+        band_sharpness): d_band_records (ceil(rows / band_rows) x 4 device uint64), a pair in the band of its left or upper pixel.  Enqueued on
+        the context's stream."""
+        self._check(self.lib.rsdsfm_deblur_band_sharpness_dev(self._ctx, _np0(d_ref), _np0(d_ref_mask), _np0(d_layer), _np0(d_layer_mask), C.c_int32(channels),
+                                                              C.c_int32(rows), C.c_int32(cols), _np0(d_sums8), C.c_int64(min_overlap), C.c_int32(gain_mode),
+                                                              C.c_int32(band_rows), _np0(d_band_records)), "rsdsfm_deblur_band_sharpness_dev")
+
+    def deblur_band_sharpness(self, ref, ref_mask, layer, layer_mask, band_rows, record=None, min_overlap=0, gain_mode=0, device=0):
+        """host convenience around deblur_band_sharpness_dev -> (NB, 4) uint64"""
+        import torch
+
+        ref = np.ascontiguousarray(ref, dtype=np.uint8)
+        rows, cols = ref.shape[:2]
+        nb = max(1, -(-rows // max(int(band_rows), 1)))
+        dev = torch.device("cuda", device)
+        with torch.cuda.device(dev):
+            up = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.uint8)).to(dev)
+            d = [up(ref), up(ref_mask), up(layer), up(layer_mask)]
+            d_rec = None if record is None else torch.from_numpy(np.ascontiguousarray(record, dtype=np.uint64).view(np.int64)).to(dev)
+            d_T = torch.full((nb, 4), -1, dtype=torch.int64, device=dev)
+            torch.cuda.synchronize()
+            self.deblur_band_sharpness_dev(d[0].data_ptr(), d[1].data_ptr(), d[2].data_ptr(), d[3].data_ptr(), 1 if ref.ndim == 2 else ref.shape[2], rows, cols, band_rows,
+                                           d_T.data_ptr(), d_rec.data_ptr() if d_rec is not None else None, min_overlap, gain_mode)
+            self.synchronize()
+            return d_T.cpu().numpy().view(np.uint64)
+
+    def deblur_band_accumulate_dev(self, d_ref, d_ref_mask, d_layer, d_layer_mask, channels, rows, cols, band_rows, d_cells, first, last, d_band_records=None, d_sums8=None,
+                                   min_overlap=0, gain_mode=0, strength=0, margin=0, min_pairs=0, gate_mode=0, d_image_out=None, d_mask_out=None, d_weight=None,
+                                   d_counts3=None):
+        """deblur_accumulate_dev with a factor per row (rsdsfm_deblur_band_accumulate_dev; tests/deblur_bands_spec_numpy.py): d_band_records the
+        layer's band records (deblur_band_sharpness_dev; required with a layer), every band's tau by the frame-wide rule, a row's tau
+        interpolated between the band centres.  Enqueued on the context's stream."""
+        self._check(self.lib.rsdsfm_deblur_band_accumulate_dev(self._ctx, _np0(d_ref), _np0(d_ref_mask), _np0(d_layer), _np0(d_layer_mask), C.c_int32(channels),
+                                                               C.c_int32(rows), C.c_int32(cols), _np0(d_sums8), C.c_int64(min_overlap), C.c_int32(gain_mode),
+                                                               C.c_int32(strength), _np0(d_band_records), C.c_int32(band_rows), C.c_int32(margin), C.c_int64(min_pairs),
+                                                               C.c_int32(gate_mode), _np0(d_cells), C.c_int32(int(first)), C.c_int32(int(last)), _np0(d_image_out),
+                                                               _np0(d_mask_out), _np0(d_weight), _np0(d_counts3)), "rsdsfm_deblur_band_accumulate_dev")
+
+    def deblur_band_accumulate(self, ref, ref_mask, layers, band_rows, records=None, band_records=None, min_overlap=0, gain_mode=0, strength=0, margin=0, min_pairs=0,
+                               gate_mode=0, device=0):
+        """host convenience around deblur_band_sharpness_dev and deblur_band_accumulate_dev, as deblur_accumulate: band_records None (computed
+        on the device) or one (NB, 4) array per layer
+        -> (image, mask, weight, counts (3,) int64, band records (n, NB, 4) uint64, cells (rows, cols, CH + 1) uint16 after the last step)"""
+        import torch
+
+        ref = np.ascontiguousarray(ref, dtype=np.uint8)
+        rows, cols = ref.shape[:2]
+        ch = 1 if ref.ndim == 2 else ref.shape[2]
+        nb = max(1, -(-rows // max(int(band_rows), 1)))
+        dev = torch.device("cuda", device)
+        with torch.cuda.device(dev):
+            up = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.uint8)).to(dev)
+            up64 = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.uint64).view(np.int64)).to(dev)
+            d_ref, d_rm = up(ref), up(ref_mask)
+            d_l = [(up(i), up(m)) for i, m in layers]
+            d_rec = [None if records is None or records[j] is None else up64(records[j]) for j in range(len(layers))]
+            d_T = (torch.full((max(len(layers), 1), nb, 4), -1, dtype=torch.int64, device=dev) if band_records is None
+                   else up64(np.asarray(band_records, dtype=np.uint64).reshape(-1, nb, 4)))
+            d_cells = torch.zeros((rows, cols, ch + 1), dtype=torch.int16, device=dev)
+            d_out, d_mask = torch.empty_like(d_ref), torch.empty((rows, cols), dtype=torch.uint8, device=dev)
+            d_w, d_cnt = torch.empty_like(d_mask), torch.zeros(3, dtype=torch.int64, device=dev)
+            torch.cuda.synchronize()
+            outs = dict(d_image_out=d_out.data_ptr(), d_mask_out=d_mask.data_ptr(), d_weight=d_w.data_ptr(), d_counts3=d_cnt.data_ptr())
+            knobs = dict(min_overlap=min_overlap, gain_mode=gain_mode, strength=strength, margin=margin, min_pairs=min_pairs, gate_mode=gate_mode)
+            if not d_l:
+                self.deblur_band_accumulate_dev(d_ref.data_ptr(), d_rm.data_ptr(), None, None, ch, rows, cols, band_rows, None, True, True, **knobs, **outs)
+            for j, (d_i, d_m) in enumerate(d_l):
+                rec = d_rec[j].data_ptr() if d_rec[j] is not None else None
+                if band_records is None:
+                    self.deblur_band_sharpness_dev(d_ref.data_ptr(), d_rm.data_ptr(), d_i.data_ptr(), d_m.data_ptr(), ch, rows, cols, band_rows, d_T[j].data_ptr(), rec,
+                                                   min_overlap, gain_mode)
+                self.deblur_band_accumulate_dev(d_ref.data_ptr(), d_rm.data_ptr(), d_i.data_ptr(), d_m.data_ptr(), ch, rows, cols, band_rows, d_cells.data_ptr(), j == 0,
+                                                j == len(d_l) - 1, d_T[j].data_ptr(), rec, **knobs, **outs)
+            self.synchronize()
+            return (d_out.cpu().numpy(), d_mask.cpu().numpy(), d_w.cpu().numpy(), d_cnt.cpu().numpy(), d_T.cpu().numpy().view(np.uint64)[:len(layers)],
+                    d_cells.cpu().numpy().view(np.uint16))
+
     def deblur_frame_dev(self, d_images, channels, d_depth_maps, d_R, d_t, K, rows, cols, M, m, d_image, d_mask, d_weight=None, d_counts3=None, d_sharp_records=None,
                          strength=None, margin=None, gate=True, gain=True, min_overlap=None, min_pairs=None, window=None, occlusion=False, occlusion_tol_q16=0,
-                         mode=BACKPROJECT_RS, q5_mode=Q5_COMPAT, iterations=0, params=None):
+                         mode=BACKPROJECT_RS, q5_mode=Q5_COMPAT, iterations=0, params=None, band_rows=None):
         """one frame (rsdsfm_deblur_frame_dev): d_images, d_depth_maps, d_R, d_t lists of 1 .. 8 device pointers, source 0 the own frame and the
         others its neighbours; M (nsrc, 3, 3), m (nsrc, 3) every source's pose in the target camera.  The own frame through
         stabilize_window_frame_dev, every neighbour alone on the context's layer, then seam_overlap_sums_dev, deblur_sharpness_dev and
         deblur_accumulate_dev per neighbour; the result into d_image, d_mask, d_weight, d_counts3, the neighbours' sharpness records into
-        d_sharp_records ((nsrc - 1) x 4 device uint64).  params: a DeblurParams passed as it is instead of the keywords.  Enqueued on the
-        context's stream."""
+        d_sharp_records ((nsrc - 1) x 4 device uint64).  band_rows (a multiple of 16; None or 0: off): a tau per band of rows through
+        deblur_band_sharpness_dev and deblur_band_accumulate_dev, d_sharp_records then (nsrc - 1) x NB x 4.  params: a DeblurParams passed as it
+        is instead of the keywords.  Enqueued on the context's stream."""
         ns = len(d_images)
         _need_all(ns, d_depth_maps=d_depth_maps, d_R=d_R, d_t=d_t)
         Mm, mm = _f64(M).reshape(-1, 9), _f64(m).reshape(-1, 3)
         if Mm.shape[0] < ns or mm.shape[0] < ns:
             raise RsdsfmError("deblur_frame_dev: every source needs a pose (M, m)")
-        dp = params if params is not None else _deblur_params(None, strength, margin, gate, gain, occlusion, occlusion_tol_q16, min_overlap, min_pairs)
+        dp = params if params is not None else _deblur_params(None, strength, margin, gate, gain, occlusion, occlusion_tol_q16, min_overlap, min_pairs, band_rows)
         d = C.c_double
         arr = lambda x: _ptr_array(list(x)[:ns]) if ns else None
         self._check(self.lib.rsdsfm_deblur_frame_dev(self._ctx, arr(d_images), C.c_int32(channels), arr(d_depth_maps), arr(d_R), arr(d_t), d(K[0]), d(K[1]), d(K[2]), d(K[3]),
@@ -3895,26 +4000,37 @@ class _DeblurMixin:
 
     def deblur_video_dev(self, d_frames, rows, cols, channels, K, d_depth_maps, d_R, d_t, A, c, A_path, c_path, scales, d_out, d_out_masks, d_out_weights=None,
                          want_counts=True, want_taus=True, radius=None, strength=None, margin=None, gate=True, gain=True, min_overlap=None, min_pairs=None, window=None,
-                         occlusion=False, occlusion_tol_q16=0, mode=BACKPROJECT_RS, q5_mode=Q5_COMPAT, iterations=0):
-        """a solved clip through the sharpness transfer (rsdsfm_deblur_video_dev): the clip as denoise_video_dev takes it and walks it, with
+                         occlusion=False, occlusion_tol_q16=0, mode=BACKPROJECT_RS, q5_mode=Q5_COMPAT, iterations=0, band_rows=None):
+        """a solved clip through the sharpness transfer (rsdsfm_deblur_video_dev; with band_rows rsdsfm_deblur_video_banded_dev): the clip as denoise_video_dev takes it and walks it, with
         `radius` 1 .. 3 (None: 2).  Returns dict(); with want_counts counts (nsources, 3) int64 [unset, own only, transferred], with want_taus
-        taus (nsources, 6) int32, entry j the factor of the j-th neighbour neighbour_poses lists, -1 behind them -- the call then waits."""
+        taus (nsources, 6) int32, entry j the factor of the j-th neighbour neighbour_poses lists, -1 behind them -- the call then waits.
+        band_rows (a multiple of 16; None: off): a tau per band of rows; taus is then the largest of a neighbour's band taus and, with
+        want_taus, band_taus (nsources, 6, NB) int32 rides along.  band_rows 0: rsdsfm_deblur_video_banded_dev with the bands off, band_taus
+        (nsources, 6, 1).  Without band_rows every key and byte is what it was."""
         ns = len(d_depth_maps)
         _need_all(ns, d_frames=d_frames, d_R=d_R, d_t=d_t, d_out=d_out, d_out_masks=d_out_masks, d_out_weights=d_out_weights)
         a, cc, ap, cp = _f64(A).reshape(-1, 9), _f64(c).reshape(-1, 3), _f64(A_path).reshape(-1, 9), _f64(c_path).reshape(-1, 3)
         sc = _f64(scales).reshape(-1)
         if min(a.shape[0], cc.shape[0], ap.shape[0], cp.shape[0], sc.shape[0]) < ns:
             raise RsdsfmError("deblur_video_dev: every source needs a pose on both paths and a scale")
-        dp = _deblur_params(radius, strength, margin, gate, gain, occlusion, occlusion_tol_q16, min_overlap, min_pairs)
+        dp = _deblur_params(radius, strength, margin, gate, gain, occlusion, occlusion_tol_q16, min_overlap, min_pairs, band_rows)
         counts = np.zeros((max(ns, 1), 3), dtype=np.int64) if want_counts else None
         taus = np.full((max(ns, 1), DEBLUR_TAUS_PER_FRAME), -1, dtype=np.int32) if want_taus else None
+        banded = band_rows is not None  # 0: the banded entry point with band_rows off, one band
+        nb = max(1, -(-int(rows) // int(band_rows))) if banded and int(band_rows) > 0 else 1
+        band_taus = np.full((max(ns, 1), DEBLUR_TAUS_PER_FRAME, min(nb, DEBLUR_BANDS_MAX)), -1, dtype=np.int32) if want_taus and banded else None
         d = C.c_double
         arr = lambda x: _ptr_array(list(x)[:ns]) if x is not None and ns else None
-        self._check(self.lib.rsdsfm_deblur_video_dev(self._ctx, arr(d_frames), C.c_int32(ns), C.c_int32(rows), C.c_int32(cols), C.c_int32(channels), d(K[0]), d(K[1]),
-                                                     d(K[2]), d(K[3]), arr(d_depth_maps), arr(d_R), arr(d_t), _p(a), _p(cc), _p(ap), _p(cp), _p(sc), int(mode), int(q5_mode),
-                                                     C.c_int32(iterations), C.byref(dp), _window4(window), arr(d_out), arr(d_out_masks), arr(d_out_weights), _p(counts),
-                                                     _p(taus)), "rsdsfm_deblur_video_dev")
+        args = (self._ctx, arr(d_frames), C.c_int32(ns), C.c_int32(rows), C.c_int32(cols), C.c_int32(channels), d(K[0]), d(K[1]), d(K[2]), d(K[3]), arr(d_depth_maps),
+                arr(d_R), arr(d_t), _p(a), _p(cc), _p(ap), _p(cp), _p(sc), int(mode), int(q5_mode), C.c_int32(iterations), C.byref(dp), _window4(window), arr(d_out),
+                arr(d_out_masks), arr(d_out_weights), _p(counts), _p(taus))
+        if banded:
+            self._check(self.lib.rsdsfm_deblur_video_banded_dev(*args, _p(band_taus)), "rsdsfm_deblur_video_banded_dev")
+        else:
+            self._check(self.lib.rsdsfm_deblur_video_dev(*args), "rsdsfm_deblur_video_dev")
         out = dict()
+        if band_taus is not None:
+            out["band_taus"] = band_taus[:ns]
         if want_counts:
             out["counts"] = counts[:ns]
         if want_taus:

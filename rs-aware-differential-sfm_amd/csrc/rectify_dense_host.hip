@@ -37,6 +37,8 @@ static void dense_ws_free(DenseWs* w) {
     w->d_erase = nullptr;
     if (w->d_deblur) (void)hipFree(w->d_deblur);
     w->d_deblur = nullptr;
+    if (w->d_deblur_bands) (void)hipFree(w->d_deblur_bands);
+    w->d_deblur_bands = nullptr;
     w->d_pyr = nullptr;
     w->d_disp = nullptr;
     w->d_mask = nullptr;

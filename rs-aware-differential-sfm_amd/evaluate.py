@@ -341,7 +341,10 @@ def evaluate_real_sequence(solver, frames, camera="galaxy", gamma=0.95, out_dir=
     (Solver.deblur_video_dev, tests/deblur_spec_numpy.py; strength None: the default, 24; the fused maps with fuse=True, the neighbours through
     the occlusion test with occlusion=True): the returned dict also has deblurred (a list of frames), deblur_counts ((frames, 3) int64: [unset,
     own only, transferred]) and deblur_taus ((frames, 6) int32: the factor 0 .. 32 of every listed neighbour, -1 behind them); out_dir receives
-    deblurred_<p>.png and deblur.csv.  Without the keyword every key and file is what it was."""
+    deblurred_<p>.png and deblur.csv.  deblur=(K, strength, band_rows): a factor per band of band_rows rows (a multiple of 16) and not per frame,
+    for frames whose blur varies down the rows (tests/deblur_bands_spec_numpy.py); deblur_taus is then the largest of a neighbour's band factors,
+    the dict also has deblur_band_taus ((frames, 6, NB) int32) and deblur.csv one column per neighbour and band behind the existing ones.  Without
+    the third element, and without the keyword, every key and file is what it was."""
     if plate_estimator is not None and plate_estimator not in ("median", "medoid"):
         raise ValueError("plate_estimator is None, 'median' or 'medoid'")
     if plate_estimator is not None and plate is None and erase in (None, False):
@@ -360,6 +363,7 @@ def evaluate_real_sequence(solver, frames, camera="galaxy", gamma=0.95, out_dir=
         deblur = None
     if deblur is not None:
         db_radius, db_strength = (None, None) if deblur is True else (int(deblur), None) if np.ndim(deblur) == 0 else (int(deblur[0]), int(deblur[1]))
+        db_band_rows = (int(deblur[2]) or None) if deblur is not True and np.ndim(deblur) != 0 and len(deblur) > 2 else None  # 0: off, as without it
     if plate is not None and not stabilize:
         raise ValueError("plate needs stabilize=True: it takes the median of the frames of the stabilised clip")
     if superres is not None and not stabilize:
@@ -713,8 +717,10 @@ def evaluate_real_sequence(solver, frames, camera="galaxy", gamma=0.95, out_dir=
                     torch.cuda.synchronize()
                     db = solver.deblur_video_dev(ptrs(d_imgs), rows, cols, channels, K, ptrs(d_src[:nst]), ptrs(d_Rs[:nst]), ptrs(d_ts[:nst]), traj["A"], traj["c"], A_s,
                                                  c_s, st_scales, ptrs(d_db), ptrs(d_dbmasks), None, radius=db_radius, strength=db_strength, occlusion=occlusion,
-                                                 occlusion_tol_q16=occ_q16 if occlusion else 0, mode=mode)
+                                                 occlusion_tol_q16=occ_q16 if occlusion else 0, mode=mode, band_rows=db_band_rows)
                     traj.update(deblurred=[t.cpu().numpy() for t in d_db], deblur_counts=db["counts"], deblur_taus=db["taus"])
+                    if db_band_rows:
+                        traj.update(deblur_band_taus=db["band_taus"])
     if out_dir:
         os.makedirs(out_dir, exist_ok=True)
         lines = ["pair,v_x,v_y,v_z,w_x,w_y,w_z,k,inliers"]
@@ -836,9 +842,13 @@ def evaluate_real_sequence(solver, frames, camera="galaxy", gamma=0.95, out_dir=
                 fh.write("\n".join(rows_) + "\n")
         if deblur is not None:
             rows_ = ["pair,unset,own_only,transferred," + ",".join("tau_%d" % j for j in range(traj["deblur_taus"].shape[1]))]
+            bt = traj.get("deblur_band_taus")  # (frames, 6, NB): one column per neighbour and band behind the existing ones
+            if bt is not None:
+                rows_[0] += "," + ",".join("tau_%d_band_%d" % (j, b) for j in range(bt.shape[1]) for b in range(bt.shape[2]))
             for p in range(nst):
                 formats.write_png(os.path.join(out_dir, "deblurred_%d.png" % p), traj["deblurred"][p])
-                rows_.append(",".join([str(p)] + [str(int(x)) for x in traj["deblur_counts"][p]] + [str(int(x)) for x in traj["deblur_taus"][p]]))
+                rows_.append(",".join([str(p)] + [str(int(x)) for x in traj["deblur_counts"][p]] + [str(int(x)) for x in traj["deblur_taus"][p]] +
+                                      ([str(int(x)) for x in bt[p].reshape(-1)] if bt is not None else [])))
             with open(os.path.join(out_dir, "deblur.csv"), "w") as fh:
                 fh.write("\n".join(rows_) + "\n")
         if inpaint:

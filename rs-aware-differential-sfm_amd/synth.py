@@ -278,24 +278,43 @@ def _with_mover(frames, mover, seed):
     return out
 
 
+def _box_mean(frame, b):
+    """a frame's rounded box mean over b (odd) columns, edges replicated"""
+    cols = frame.shape[1]
+    idx = np.clip(np.arange(-(b // 2), cols + b // 2), 0, cols - 1)
+    padded = frame.astype(np.int64)[:, idx]
+    total = sum(padded[:, d:d + cols] for d in range(b))
+    return ((2 * total + b) // (2 * b)).astype(np.uint8)
+
+
 def _box_blurred(frames, blur):
-    """the frames with frame j replaced by its rounded box mean over blur[j] (odd) columns, edges replicated (a new array); None or all 1: the
-    frames themselves"""
+    """the frames with frame j replaced by its rounded box mean over blur[j] (odd) columns, edges replicated (a new array); an entry that is a
+    sequence gives every ROW of the frame its own width (`rows` of them); None or all 1: the frames themselves"""
     if blur is None:
         return frames
-    widths = [int(b) for b in blur]
-    if len(widths) != frames.shape[0] or any(b < 1 or b % 2 == 0 for b in widths):
+    blur = list(blur)
+    if len(blur) != frames.shape[0]:
         raise ValueError("blur needs one odd box width >= 1 per frame (nframes)")
-    if all(b == 1 for b in widths):
+    widths = [int(b) if np.ndim(b) == 0 else None for b in blur]
+    if any(b is not None and (b < 1 or b % 2 == 0) for b in widths):
+        raise ValueError("blur needs one odd box width >= 1 per frame (nframes)")
+    per_row = {}
+    for j, b in enumerate(blur):
+        if widths[j] is None:
+            r = np.asarray(b, dtype=np.int64).reshape(-1)
+            if r.shape[0] != frames.shape[1] or (r < 1).any() or (r % 2 == 0).any():
+                raise ValueError("a per-row blur entry needs one odd box width >= 1 per row (rows)")
+            per_row[j] = r
+    if not per_row and all(b == 1 for b in widths):
         return frames
     out = frames.copy()
-    cols = frames.shape[2]
     for j, b in enumerate(widths):
-        if b > 1:
-            idx = np.clip(np.arange(-(b // 2), cols + b // 2), 0, cols - 1)
-            padded = frames[j].astype(np.int64)[:, idx]
-            total = sum(padded[:, d:d + cols] for d in range(b))
-            out[j] = ((2 * total + b) // (2 * b)).astype(np.uint8)
+        if b is not None and b > 1:
+            out[j] = _box_mean(frames[j], b)
+        elif b is None:
+            for w in np.unique(per_row[j]):
+                if w > 1:
+                    out[j][per_row[j] == w] = _box_mean(frames[j], int(w))[per_row[j] == w]
     return out
 
 
@@ -318,7 +337,8 @@ def render_sequence(nframes, rows, cols, K, v, w, k=0.0, gamma=0.8, seed=0x5EED0
     what this function returns without the argument.
     blur: one odd horizontal box width per frame (nframes of them): frame j becomes its rounded box mean over blur[j] columns with replicated
     edges, after the mover and before the sensor noise -- the blur of a shaken exposure, what the sharpness transfer is for; the geometry is
-    unchanged.  None or all 1: byte for byte what this function returns without the argument."""
+    unchanged.  An entry may be a sequence of `rows` odd widths, one per row: the smear of a rolling-shutter exposure, which varies down the
+    frame (what the sharpness transfer per scanline band is for).  None or all 1: byte for byte what this function returns without the argument."""
     if nframes < 2:
         raise ValueError("a sequence has at least two frames")
     if gains is not None and len(gains) != nframes:
