@@ -29,8 +29,11 @@
  * every call here reproduces it bit for bit.  DESIGN.md section 12 ("Temporal denoise") has the kernel, the bytes, the launches and the LDS
  * layout.
  *
- * NOT here: spatial (single-frame) denoising, patches other than 3 x 3, a noise-level estimate (the strength is the caller's), moving objects
- * (they only fall back to the own pixel), fill, blend or inpaint of the result (the generic frame calls rsdsfm_stabilize_window_frame_dev,
+ * The spatial top-up (rsdsfm_denoise_spatial.h, which this header includes at its end) is the single-frame denoiser beside it:
+ * it reads the weight plane n and tops every pixel up from its own frame in proportion to what time did not give.
+ *
+ * NOT here: spatial (single-frame) denoising (built since: rsdsfm_denoise_spatial.h), patches other than 3 x 3, a noise-level estimate (the
+ * strength is the caller's), moving objects (they only fall back to the own pixel; rsdsfm_denoise_spatial.h tops them up), fill, blend or inpaint of the result (the generic frame calls rsdsfm_stabilize_window_frame_dev,
  * rsdsfm_seam_blend_layer_dev and rsdsfm_inpaint_frame_dev accept this header's outputs), a fused render-and-accumulate kernel that skips the
  * layer, the C++ mirror.
  */
@@ -144,5 +147,8 @@ int rsdsfm_denoise_video_dev(rsdsfm_ctx* ctx, const uint8_t* const* d_frames, in
 #ifdef __cplusplus
 }
 #endif
+
+/* the spatial top-up's declarations come with this header */
+#include "rsdsfm_denoise_spatial.h"
 
 #endif /* RSDSFM_DENOISE_H */

@@ -136,13 +136,13 @@ class RansacOut(C.Structure):
 
 def declared_symbols():
     """Names of every function include/rsdsfm.h, include/rsdsfm_retime.h, include/rsdsfm_shutter.h, include/rsdsfm_denoise.h,
-    include/rsdsfm_superres.h, include/rsdsfm_plate.h, include/rsdsfm_plate_medoid.h, include/rsdsfm_erase.h and include/rsdsfm_deblur.h
-    declare (used by the CPU symbol-export test)."""
+    include/rsdsfm_denoise_spatial.h (which rsdsfm_denoise.h includes), include/rsdsfm_superres.h, include/rsdsfm_plate.h,
+    include/rsdsfm_plate_medoid.h, include/rsdsfm_erase.h and include/rsdsfm_deblur.h declare (used by the CPU symbol-export test)."""
     import re
 
     txt = "".join(open(os.path.join(os.path.dirname(HEADER_PATH), name)).read()
-                  for name in (os.path.basename(HEADER_PATH), "rsdsfm_retime.h", "rsdsfm_shutter.h", "rsdsfm_denoise.h", "rsdsfm_superres.h", "rsdsfm_plate.h",
-                              "rsdsfm_plate_medoid.h", "rsdsfm_erase.h", "rsdsfm_deblur.h"))
+                  for name in (os.path.basename(HEADER_PATH), "rsdsfm_retime.h", "rsdsfm_shutter.h", "rsdsfm_denoise.h", "rsdsfm_denoise_spatial.h", "rsdsfm_superres.h",
+                              "rsdsfm_plate.h", "rsdsfm_plate_medoid.h", "rsdsfm_erase.h", "rsdsfm_deblur.h"))
     txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
     return sorted(set(re.findall(r"\b(rsdsfm_[a-z0-9_]+)\s*\(", txt)))
 
@@ -3153,6 +3153,139 @@ class _DenoiseMixin:
 
 
 for _name, _fn in list(vars(_DenoiseMixin).items()):
+    if not _name.startswith("__"):
+        setattr(Solver, _name, _fn)
+
+
+# ---------------------------------------------------------------------------------------------------
+# the spatial top-up: a single-frame patch-weighted mean in proportion to what the temporal denoise did not give (include/rsdsfm_denoise_spatial.h)
+# ---------------------------------------------------------------------------------------------------
+DENOISE_SPATIAL_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "rsdsfm_denoise_spatial.h")
+DENOISE_SPATIAL_SEARCH_MAX = 3
+
+
+def denoise_spatial_declared_symbols():
+    """Names of every function include/rsdsfm_denoise_spatial.h declares"""
+    import re
+
+    txt = re.sub(r"/\*.*?\*/", "", open(DENOISE_SPATIAL_HEADER_PATH).read(), flags=re.S)
+    return sorted(set(re.findall(r"\b(rsdsfm_[a-z0-9_]+)\s*\(", txt)))
+
+
+class DenoiseSpatialParams(C.Structure):
+    _fields_ = [("strength", C.c_int32), ("target", C.c_int32), ("search", C.c_int32), ("struct_bytes", C.c_int32), ("reserved", C.c_int32 * 4)]
+
+
+def _denoise_spatial_params(strength=None, target=None, search=None):
+    """a DenoiseSpatialParams with the given values over the defaults (None: the default)"""
+    p = DenoiseSpatialParams()
+    if load_library().rsdsfm_denoise_spatial_params_init(C.byref(p)) != OK:
+        raise RsdsfmError("rsdsfm_denoise_spatial_params_init failed")
+    if strength is not None:
+        p.strength = int(strength)
+    if target is not None:
+        p.target = int(target)
+    if search is not None:
+        p.search = int(search)
+    return p
+
+
+def denoise_spatial_default_params():
+    """the top-up's defaults as a dict: strength = 12, target = 80, search = 2 (rsdsfm_denoise_spatial_params_init); choices, not measurements"""
+    p = _denoise_spatial_params()
+    return dict(strength=p.strength, target=p.target, search=p.search)
+
+
+def denoise_spatial_launches():
+    """kernel launches of one denoise_spatial_dev call: 1 (rsdsfm_denoise_spatial_launches; host only)"""
+    return int(load_library().rsdsfm_denoise_spatial_launches())
+
+
+def denoise_spatial_frame_launches(rows, cols, nsrc):
+    """kernel launches of one denoise_spatial_frame_dev call: denoise_launches + 1 (rsdsfm_denoise_spatial_frame_launches; host only)"""
+    n = load_library().rsdsfm_denoise_spatial_frame_launches(C.c_int32(rows), C.c_int32(cols), C.c_int32(nsrc))
+    if n < 0:
+        raise RsdsfmError("rsdsfm_denoise_spatial_frame_launches failed (%d): rows and cols in [2, 16384], nsrc in [1, 15]" % n)
+    return n
+
+
+class _DenoiseSpatialMixin:
+    def denoise_spatial_dev(self, d_image, d_mask, d_weight, channels, rows, cols, d_image_out, d_support=None, d_counts3=None, strength=0, target=0, search=0):
+        """the spatial top-up (rsdsfm_denoise_spatial_dev; tests/denoise_spatial_spec_numpy.py): every set pixel whose weight n (d_weight; None: 16)
+        is below `target` is mixed with the patch-weighted mean of its set neighbours within [-search, search]^2 of its own frame, in
+        proportion to target - n; a pixel at or above the target keeps its bytes.  The support to d_support, [unset, kept, smoothed] to d_counts3
+        (three device int64).  0: the default (strength 12, target 80, search 2).  Enqueued on the context's stream."""
+        self._check(self.lib.rsdsfm_denoise_spatial_dev(self._ctx, _dp(d_image), _dp(d_mask), _np0(d_weight), C.c_int32(channels), C.c_int32(rows), C.c_int32(cols),
+                                                        C.c_int32(strength), C.c_int32(target), C.c_int32(search), _dp(d_image_out), _np0(d_support), _np0(d_counts3)),
+                    "rsdsfm_denoise_spatial_dev")
+
+    def denoise_spatial(self, image, mask, weight=None, strength=0, target=0, search=0, device=0):
+        """host convenience around denoise_spatial_dev: image (rows, cols[, 3]) uint8, mask and weight (or None) (rows, cols) uint8
+        -> (image, support (rows, cols) uint8, counts (3,) int64 [unset, kept, smoothed])"""
+        import torch
+
+        image = np.ascontiguousarray(image, dtype=np.uint8)
+        rows, cols = image.shape[:2]
+        ch = 1 if image.ndim == 2 else image.shape[2]
+        dev = torch.device("cuda", device)
+        with torch.cuda.device(dev):
+            up = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.uint8)).to(dev)
+            d_i, d_m = up(image), up(mask)
+            d_w = up(weight) if weight is not None else None
+            d_out, d_sup = torch.empty_like(d_i), torch.empty((rows, cols), dtype=torch.uint8, device=dev)
+            d_cnt = torch.zeros(3, dtype=torch.int64, device=dev)
+            torch.cuda.synchronize()
+            self.denoise_spatial_dev(d_i.data_ptr(), d_m.data_ptr(), d_w.data_ptr() if d_w is not None else None, ch, rows, cols, d_out.data_ptr(), d_sup.data_ptr(),
+                                     d_cnt.data_ptr(), strength, target, search)
+            self.synchronize()
+            return d_out.cpu().numpy(), d_sup.cpu().numpy(), d_cnt.cpu().numpy()
+
+    def denoise_spatial_frame_dev(self, d_images, channels, d_depth_maps, d_R, d_t, K, rows, cols, M, m, d_image, d_mask, d_weight=None, d_support=None, d_counts6=None,
+                                  strength=None, gain=True, min_overlap=None, window=None, occlusion=False, occlusion_tol_q16=0, mode=BACKPROJECT_RS, q5_mode=Q5_COMPAT,
+                                  iterations=0, params=None, spatial_strength=None, target=None, search=None, spatial_params=None):
+        """one frame through the temporal denoise and the top-up (rsdsfm_denoise_spatial_frame_dev): denoise_frame_dev's arguments; the temporal
+        result stays in the context's workspace (its weight in d_weight when given, its mask in d_mask, its counters in d_counts6[0 .. 2]) and
+        denoise_spatial_dev reads it into d_image, d_support and d_counts6[3 .. 5].  params / spatial_params: a DenoiseParams / DenoiseSpatialParams
+        passed as it is instead of the keywords.  Enqueued on the context's stream."""
+        ns = len(d_images)
+        _need_all(ns, d_depth_maps=d_depth_maps, d_R=d_R, d_t=d_t)
+        Mm, mm = _f64(M).reshape(-1, 9), _f64(m).reshape(-1, 3)
+        if Mm.shape[0] < ns or mm.shape[0] < ns:
+            raise RsdsfmError("denoise_spatial_frame_dev: every source needs a pose (M, m)")
+        dp = params if params is not None else _denoise_params(None, strength, gain, occlusion, occlusion_tol_q16, min_overlap)
+        sp = spatial_params if spatial_params is not None else _denoise_spatial_params(spatial_strength, target, search)
+        d = C.c_double
+        arr = lambda x: _ptr_array(list(x)[:ns]) if ns else None
+        self._check(self.lib.rsdsfm_denoise_spatial_frame_dev(self._ctx, arr(d_images), C.c_int32(channels), arr(d_depth_maps), arr(d_R), arr(d_t), d(K[0]), d(K[1]), d(K[2]),
+                                                              d(K[3]), C.c_int32(rows), C.c_int32(cols), int(mode), int(q5_mode), C.c_int32(iterations), C.c_int32(ns), _p(Mm),
+                                                              _p(mm), C.byref(dp), C.byref(sp), _window4(window), _dp(d_image), _dp(d_mask), _np0(d_weight), _np0(d_support),
+                                                              _np0(d_counts6)), "rsdsfm_denoise_spatial_frame_dev")
+
+    def denoise_spatial_video_dev(self, d_frames, rows, cols, channels, K, d_depth_maps, d_R, d_t, A, c, A_path, c_path, scales, d_out, d_out_masks, d_out_weights=None,
+                                  d_out_supports=None, want_counts=True, radius=None, strength=None, gain=True, min_overlap=None, window=None, occlusion=False,
+                                  occlusion_tol_q16=0, mode=BACKPROJECT_RS, q5_mode=Q5_COMPAT, iterations=0, spatial_strength=None, target=None, search=None):
+        """a solved clip through the temporal denoise and the top-up (rsdsfm_denoise_spatial_video_dev): denoise_video_dev's clip and walk,
+        denoise_spatial_frame_dev per frame into d_out[q], d_out_masks[q], d_out_weights[q], d_out_supports[q].  Returns dict(); with want_counts
+        counts (nsources, 6) int64 [unset, own only, averaged, unset, kept, smoothed] -- the call then waits."""
+        ns = len(d_depth_maps)
+        _need_all(ns, d_frames=d_frames, d_R=d_R, d_t=d_t, d_out=d_out, d_out_masks=d_out_masks, d_out_weights=d_out_weights, d_out_supports=d_out_supports)
+        a, cc, ap, cp = _f64(A).reshape(-1, 9), _f64(c).reshape(-1, 3), _f64(A_path).reshape(-1, 9), _f64(c_path).reshape(-1, 3)
+        sc = _f64(scales).reshape(-1)
+        if min(a.shape[0], cc.shape[0], ap.shape[0], cp.shape[0], sc.shape[0]) < ns:
+            raise RsdsfmError("denoise_spatial_video_dev: every source needs a pose on both paths and a scale")
+        dp = _denoise_params(radius, strength, gain, occlusion, occlusion_tol_q16, min_overlap)
+        sp = _denoise_spatial_params(spatial_strength, target, search)
+        counts = np.zeros((max(ns, 1), 6), dtype=np.int64) if want_counts else None
+        d = C.c_double
+        arr = lambda x: _ptr_array(list(x)[:ns]) if x is not None and ns else None
+        self._check(self.lib.rsdsfm_denoise_spatial_video_dev(self._ctx, arr(d_frames), C.c_int32(ns), C.c_int32(rows), C.c_int32(cols), C.c_int32(channels), d(K[0]), d(K[1]),
+                                                              d(K[2]), d(K[3]), arr(d_depth_maps), arr(d_R), arr(d_t), _p(a), _p(cc), _p(ap), _p(cp), _p(sc), int(mode),
+                                                              int(q5_mode), C.c_int32(iterations), C.byref(dp), C.byref(sp), _window4(window), arr(d_out), arr(d_out_masks),
+                                                              arr(d_out_weights), arr(d_out_supports), _p(counts)), "rsdsfm_denoise_spatial_video_dev")
+        return dict(counts=counts[:ns]) if want_counts else dict()
+
+
+for _name, _fn in list(vars(_DenoiseSpatialMixin).items()):
     if not _name.startswith("__"):
         setattr(Solver, _name, _fn)
 

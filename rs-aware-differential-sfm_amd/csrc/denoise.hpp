@@ -35,4 +35,21 @@ int denoise_accumulate_launch(Ctx* c, const unsigned char* d_ref, const unsigned
                               int rows, int cols, const unsigned long long* d_sums, int64_t min_overlap, int gain_mode, int strength, uint16_t* d_cells, bool first,
                               bool last, unsigned char* d_image_out, unsigned char* d_mask_out, unsigned char* d_weight, int64_t* d_counts3);
 
+// the params with every 0 of radius, strength and min_overlap replaced by its default, or the defaults for NULL; false: refused, with
+// kDenoiseParamsMessage (denoise_host.hip; the top-up's frame and clip calls refuse the temporal stage's params in the same words)
+bool denoise_params_resolve(const rsdsfm_denoise_params* in, rsdsfm_denoise_params* out);
+extern const char* const kDenoiseParamsMessage;
+
+// the spatial top-up (rsdsfm_denoise_spatial_dev; denoise_spatial_kernels.hip, denoise_spatial_host.hip)
+constexpr int kDenoiseSpatialTargetDefault = RSDSFM_DENOISE_SPATIAL_TARGET_DEFAULT, kDenoiseSpatialTargetMax = 255;
+constexpr int kDenoiseSpatialSearchDefault = RSDSFM_DENOISE_SPATIAL_SEARCH_DEFAULT, kDenoiseSpatialSearchMax = RSDSFM_DENOISE_SPATIAL_SEARCH_MAX;
+
+// DenseWs::d_denoise_spatial: [weight: P][image: 3 P], P = blend_plane_bytes: what the temporal stage writes for the top-up to read
+inline size_t denoise_spatial_ws_bytes(int rows, int cols) { return 4 * blend_plane_bytes(rows, cols); }
+
+// the top-up on c->stream (arguments checked and defaults resolved by the caller; d_weight, d_support, d_counts3 may be NULL): the counters
+// zeroed by a memset when passed, then one launch
+int denoise_spatial_launch(Ctx* c, const unsigned char* d_image, const unsigned char* d_mask, const unsigned char* d_weight, int channels, int rows, int cols, int strength,
+                           int target, int search, unsigned char* d_image_out, unsigned char* d_support, int64_t* d_counts3);
+
 }  // namespace rsdsfm

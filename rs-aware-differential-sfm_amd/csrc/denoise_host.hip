@@ -16,6 +16,8 @@ rsdsfm_denoise_params denoise_defaults() {
     return rsdsfm_denoise_params{RSDSFM_DENOISE_RADIUS_DEFAULT, kDenoiseStrengthDefault, 0, 0, 0, (int32_t)sizeof(rsdsfm_denoise_params), kMinOverlapDefault, {0, 0, 0, 0}};
 }
 
+}  // namespace
+
 // the params with every 0 of radius, strength and min_overlap replaced by its default, or the defaults for NULL; false: refused
 bool denoise_params_resolve(const rsdsfm_denoise_params* in, rsdsfm_denoise_params* out) {
     *out = in ? *in : denoise_defaults();
@@ -30,6 +32,8 @@ bool denoise_params_resolve(const rsdsfm_denoise_params* in, rsdsfm_denoise_para
 const char* const kDenoiseParamsMessage =
     "rsdsfm_denoise_params: radius in [1, 7] or 0, strength in [1, 255] or 0, gain_mode 0 or 1, occlusion 0 or 1, occlusion_tol_q16 in [0, 65536], min_overlap >= 0, "
     "struct_bytes 0 or sizeof (use rsdsfm_denoise_params_init)";
+
+namespace {
 
 // the workspace's reference planes and cells, made when first asked for, and the blend's layer
 int denoise_ws(Ctx* c, int rows, int cols, DenseWs** ws) {

@@ -39,6 +39,8 @@ static void dense_ws_free(DenseWs* w) {
     w->d_deblur = nullptr;
     if (w->d_deblur_bands) (void)hipFree(w->d_deblur_bands);
     w->d_deblur_bands = nullptr;
+    if (w->d_denoise_spatial) (void)hipFree(w->d_denoise_spatial);
+    w->d_denoise_spatial = nullptr;
     w->d_pyr = nullptr;
     w->d_disp = nullptr;
     w->d_mask = nullptr;

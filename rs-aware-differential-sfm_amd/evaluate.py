@@ -312,6 +312,11 @@ def evaluate_real_sequence(solver, frames, camera="galaxy", gamma=0.95, out_dir=
     the occlusion test with occlusion=True): the returned dict also has stab_denoised, denoise_masks, denoise_weights (lists of frames; the weight
     is 16 for the own frame plus up to 16 per neighbour) and denoise_counts ((frames, 3) int64: [unset, own only, averaged]); out_dir receives
     stabilized_denoised_<p>.png and denoise.csv.  Without the keyword every key and file is what it was.
+    denoise=(K, strength, spatial) with spatial True or (target, search): the spatial top-up behind the temporal stage of every frame
+    (Solver.denoise_spatial_video_dev, tests/denoise_spatial_spec_numpy.py; the strength is both stages', True: target 80, search 2): stab_denoised is
+    then the topped-up clip, the returned dict also has denoise_support (a list of planes) and denoise_spatial_counts ((frames, 3) int64:
+    [unset, kept, smoothed]), and denoise.csv three more columns (kept, smoothed, mean_support).  Without the third element every key, file and
+    byte is what it was.
     superres=scale or (scale, K) (needs stabilize=True: ValueError otherwise): behind everything else, every stabilised frame once more on a grid
     `scale` times finer (1 .. 4), merged from itself and its K neighbours on either side (1 .. 7, default 2), each rendered alone into the frame's
     camera on the SMOOTHED path (Solver.superres_video_dev, tests/superres_spec_numpy.py; the fused maps with fuse=True): the returned dict also
@@ -671,16 +676,29 @@ def evaluate_real_sequence(solver, frames, camera="galaxy", gamma=0.95, out_dir=
                         traj.update(shuttered=[t.cpu().numpy() for t in d_sh], shutter_masks=[t.cpu().numpy() for t in d_shmasks],
                                     shutter_coverage=[t.cpu().numpy() for t in d_shcov], shutter_counts=sh["counts"], shutter_kept=sh["kept"])
                 if denoise is not None:  # every stabilised frame once more, averaged with its neighbours
-                    dn_radius, dn_strength = (int(denoise), None) if np.ndim(denoise) == 0 else (int(denoise[0]), int(denoise[1]))
+                    dn_one = not isinstance(denoise, (tuple, list, np.ndarray))  # K alone; (K, strength, (target, search)) is ragged: no np.ndim
+                    dn_radius, dn_strength = (int(denoise), None) if dn_one else (int(denoise[0]), None if denoise[1] is None else int(denoise[1]))
+                    dn_spatial = None if dn_one or len(denoise) < 3 or denoise[2] is None or denoise[2] is False else denoise[2]
                     d_dn = [torch.empty_like(d_imgs[0]) for _ in range(nst)]
                     d_dnmasks = [torch.empty((rows, cols), dtype=torch.uint8, device=dev) for _ in range(nst)]
                     d_dnw = [torch.empty((rows, cols), dtype=torch.uint8, device=dev) for _ in range(nst)]
-                    torch.cuda.synchronize()
-                    dn = solver.denoise_video_dev(ptrs(d_imgs), rows, cols, channels, K, ptrs(d_src[:nst]), ptrs(d_Rs[:nst]), ptrs(d_ts[:nst]), traj["A"], traj["c"], A_s,
-                                                  c_s, st_scales, ptrs(d_dn), ptrs(d_dnmasks), ptrs(d_dnw), radius=dn_radius, strength=dn_strength, occlusion=occlusion,
-                                                  occlusion_tol_q16=occ_q16 if occlusion else 0, mode=mode)
-                    traj.update(stab_denoised=[t.cpu().numpy() for t in d_dn], denoise_masks=[t.cpu().numpy() for t in d_dnmasks],
-                                denoise_weights=[t.cpu().numpy() for t in d_dnw], denoise_counts=dn["counts"])
+                    dn_kw = dict(radius=dn_radius, strength=dn_strength, occlusion=occlusion, occlusion_tol_q16=occ_q16 if occlusion else 0, mode=mode)
+                    if dn_spatial is None:
+                        torch.cuda.synchronize()
+                        dn = solver.denoise_video_dev(ptrs(d_imgs), rows, cols, channels, K, ptrs(d_src[:nst]), ptrs(d_Rs[:nst]), ptrs(d_ts[:nst]), traj["A"], traj["c"], A_s,
+                                                      c_s, st_scales, ptrs(d_dn), ptrs(d_dnmasks), ptrs(d_dnw), **dn_kw)
+                        traj.update(stab_denoised=[t.cpu().numpy() for t in d_dn], denoise_masks=[t.cpu().numpy() for t in d_dnmasks],
+                                    denoise_weights=[t.cpu().numpy() for t in d_dnw], denoise_counts=dn["counts"])
+                    else:  # the top-up behind the temporal stage of every frame: True, or (target, search)
+                        sp_target, sp_search = (None, None) if dn_spatial is True else (int(dn_spatial[0]), int(dn_spatial[1]))
+                        d_dns = [torch.empty((rows, cols), dtype=torch.uint8, device=dev) for _ in range(nst)]
+                        torch.cuda.synchronize()
+                        dn = solver.denoise_spatial_video_dev(ptrs(d_imgs), rows, cols, channels, K, ptrs(d_src[:nst]), ptrs(d_Rs[:nst]), ptrs(d_ts[:nst]), traj["A"], traj["c"],
+                                                              A_s, c_s, st_scales, ptrs(d_dn), ptrs(d_dnmasks), ptrs(d_dnw), ptrs(d_dns), spatial_strength=dn_strength,
+                                                              target=sp_target, search=sp_search, **dn_kw)
+                        traj.update(stab_denoised=[t.cpu().numpy() for t in d_dn], denoise_masks=[t.cpu().numpy() for t in d_dnmasks],
+                                    denoise_weights=[t.cpu().numpy() for t in d_dnw], denoise_counts=dn["counts"][:, :3].copy(),
+                                    denoise_support=[t.cpu().numpy() for t in d_dns], denoise_spatial_counts=dn["counts"][:, 3:].copy())
                 if superres is not None:  # every stabilised frame once more, on a finer grid, merged with its neighbours
                     sr_scale, sr_radius = (int(superres), None) if np.ndim(superres) == 0 else (int(superres[0]), int(superres[1]))
                     fine = (sr_scale * rows, sr_scale * cols)
@@ -811,10 +829,12 @@ def evaluate_real_sequence(solver, frames, camera="galaxy", gamma=0.95, out_dir=
             with open(os.path.join(out_dir, "shutter.csv"), "w") as fh:
                 fh.write("\n".join(rows_) + "\n")
         if denoise is not None:
-            rows_ = ["pair,unset,own_only,averaged,mean_weight"]
+            topped = "denoise_spatial_counts" in traj  # three more columns: kept, smoothed, mean_support
+            rows_ = ["pair,unset,own_only,averaged,mean_weight" + (",kept,smoothed,mean_support" if topped else "")]
             for p in range(nst):
                 formats.write_png(os.path.join(out_dir, "stabilized_denoised_%d.png" % p), traj["stab_denoised"][p])
-                rows_.append(",".join([str(p)] + [str(int(x)) for x in traj["denoise_counts"][p]] + ["%.4f" % float(traj["denoise_weights"][p].mean())]))
+                more = [str(int(x)) for x in traj["denoise_spatial_counts"][p][1:]] + ["%.4f" % float(traj["denoise_support"][p].mean())] if topped else []
+                rows_.append(",".join([str(p)] + [str(int(x)) for x in traj["denoise_counts"][p]] + ["%.4f" % float(traj["denoise_weights"][p].mean())] + more))
             with open(os.path.join(out_dir, "denoise.csv"), "w") as fh:
                 fh.write("\n".join(rows_) + "\n")
         if superres is not None:
