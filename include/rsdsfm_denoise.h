@@ -32,8 +32,8 @@
  * The spatial top-up (rsdsfm_denoise_spatial.h, which this header includes at its end) is the single-frame denoiser beside it:
  * it reads the weight plane n and tops every pixel up from its own frame in proportion to what time did not give.
  *
- * NOT here: spatial (single-frame) denoising (built since: rsdsfm_denoise_spatial.h), patches other than 3 x 3, a noise-level estimate (the
- * strength is the caller's), moving objects (they only fall back to the own pixel; rsdsfm_denoise_spatial.h tops them up), fill, blend or inpaint of the result (the generic frame calls rsdsfm_stabilize_window_frame_dev,
+ * NOT here: spatial (single-frame) denoising (built since: rsdsfm_denoise_spatial.h), patches other than 3 x 3, a noise-level estimate (built since:
+ * rsdsfm_noise.h measures it per frame and forms the strength from it on the device; in this header's calls the strength is the caller's), moving objects (they only fall back to the own pixel; rsdsfm_denoise_spatial.h tops them up), fill, blend or inpaint of the result (the generic frame calls rsdsfm_stabilize_window_frame_dev,
  * rsdsfm_seam_blend_layer_dev and rsdsfm_inpaint_frame_dev accept this header's outputs), a fused render-and-accumulate kernel that skips the
  * layer, the C++ mirror.
  */

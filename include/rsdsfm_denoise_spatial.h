@@ -18,7 +18,7 @@
  * The defaults (strength 12: the temporal default; target 80 = 16 (1 + 2 * 2): a fully supported pixel at the temporal default radius; search
  * 2) are choices, not measurements.  DESIGN.md section 12 ("Spatial top-up") has the kernel, the LDS layout and the bytes.
  *
- * NOT here: search windows beyond 7 x 7, patches other than 3 x 3, a noise-level estimate, the same top-up for super-resolution and sharpness
+ * NOT here: search windows beyond 7 x 7, patches other than 3 x 3, a noise-level estimate (built since: rsdsfm_noise.h), the same top-up for super-resolution and sharpness
  * transfer, the fuzz campaign entry, the C++ mirror.
  */
 #ifndef RSDSFM_DENOISE_SPATIAL_H

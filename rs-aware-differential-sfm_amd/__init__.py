@@ -137,12 +137,13 @@ class RansacOut(C.Structure):
 def declared_symbols():
     """Names of every function include/rsdsfm.h, include/rsdsfm_retime.h, include/rsdsfm_shutter.h, include/rsdsfm_denoise.h,
     include/rsdsfm_denoise_spatial.h (which rsdsfm_denoise.h includes), include/rsdsfm_superres.h, include/rsdsfm_plate.h,
-    include/rsdsfm_plate_medoid.h, include/rsdsfm_erase.h and include/rsdsfm_deblur.h declare (used by the CPU symbol-export test)."""
+    include/rsdsfm_plate_medoid.h, include/rsdsfm_erase.h, include/rsdsfm_deblur.h and include/rsdsfm_noise.h declare (used by the CPU symbol-export
+    test)."""
     import re
 
     txt = "".join(open(os.path.join(os.path.dirname(HEADER_PATH), name)).read()
                   for name in (os.path.basename(HEADER_PATH), "rsdsfm_retime.h", "rsdsfm_shutter.h", "rsdsfm_denoise.h", "rsdsfm_denoise_spatial.h", "rsdsfm_superres.h",
-                              "rsdsfm_plate.h", "rsdsfm_plate_medoid.h", "rsdsfm_erase.h", "rsdsfm_deblur.h"))
+                              "rsdsfm_plate.h", "rsdsfm_plate_medoid.h", "rsdsfm_erase.h", "rsdsfm_deblur.h", "rsdsfm_noise.h"))
     txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
     return sorted(set(re.findall(r"\b(rsdsfm_[a-z0-9_]+)\s*\(", txt)))
 
@@ -3286,6 +3287,225 @@ class _DenoiseSpatialMixin:
 
 
 for _name, _fn in list(vars(_DenoiseSpatialMixin).items()):
+    if not _name.startswith("__"):
+        setattr(Solver, _name, _fn)
+
+
+# ---------------------------------------------------------------------------------------------------
+# the noise level: a frame's noise measured from the frame, and the two denoisers at the strength it asks for (include/rsdsfm_noise.h)
+# ---------------------------------------------------------------------------------------------------
+NOISE_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "rsdsfm_noise.h")
+NOISE_BINS = 1024
+
+
+def noise_declared_symbols():
+    """Names of every function include/rsdsfm_noise.h declares"""
+    import re
+
+    txt = re.sub(r"/\*.*?\*/", "", open(NOISE_HEADER_PATH).read(), flags=re.S)
+    return sorted(set(re.findall(r"\b(rsdsfm_[a-z0-9_]+)\s*\(", txt)))
+
+
+class NoiseParams(C.Structure):
+    _fields_ = [("quantile_q8", C.c_int32), ("scale", C.c_int32), ("struct_bytes", C.c_int32), ("reserved0", C.c_int32), ("min_samples", C.c_int64),
+                ("reserved", C.c_int32 * 4)]
+
+
+def _noise_params(quantile_q8=None, scale=None, min_samples=None):
+    """a NoiseParams with the given values over the defaults (None: the default)"""
+    p = NoiseParams()
+    if load_library().rsdsfm_noise_params_init(C.byref(p)) != OK:
+        raise RsdsfmError("rsdsfm_noise_params_init failed")
+    if quantile_q8 is not None:
+        p.quantile_q8 = int(quantile_q8)
+    if scale is not None:
+        p.scale = int(scale)
+    if min_samples is not None:
+        p.min_samples = int(min_samples)
+    return p
+
+
+def noise_default_params():
+    """the noise level's defaults as a dict: quantile_q8 = 128 (the median; a choice, not a measurement), scale = 12, min_samples = 1024
+    (rsdsfm_noise_params_init)"""
+    p = _noise_params()
+    return dict(quantile_q8=p.quantile_q8, scale=p.scale, min_samples=p.min_samples)
+
+
+def noise_level_launches():
+    """kernel launches of one noise_level_dev call: 2 (rsdsfm_noise_level_launches; host only)"""
+    return int(load_library().rsdsfm_noise_level_launches())
+
+
+def noise_strength(n, m, scale=0, fallback=0, min_samples=0):
+    """the strength h a record [n, m, ...] asks for (rsdsfm_noise_strength; tests/noise_spec_numpy.py; host only): fallback (0: 12) where
+    n < min_samples (0: 1024), else clamp((scale m + 8) >> 4, 1, 255) (scale 0: 12)"""
+    h = load_library().rsdsfm_noise_strength(C.c_int64(int(n)), C.c_int64(int(m)), C.c_int32(scale), C.c_int32(fallback), C.c_int64(min_samples))
+    if h < 0:
+        raise RsdsfmError("rsdsfm_noise_strength failed (%d): n, m >= 0, scale in [0, 255], fallback in [0, 255], min_samples >= 0" % h)
+    return int(h)
+
+
+def denoise_auto_frame_launches(rows, cols, nsrc, with_spatial=False):
+    """kernel launches of one denoise_auto_frame_dev call: denoise_launches + 2, + 1 with the top-up (rsdsfm_denoise_auto_frame_launches; host only)"""
+    n = load_library().rsdsfm_denoise_auto_frame_launches(C.c_int32(rows), C.c_int32(cols), C.c_int32(nsrc), C.c_int32(1 if with_spatial else 0))
+    if n < 0:
+        raise RsdsfmError("rsdsfm_denoise_auto_frame_launches failed (%d): rows and cols in [2, 16384], nsrc in [1, 15]" % n)
+    return n
+
+
+class _NoiseMixin:
+    def noise_level_dev(self, d_image, d_mask, channels, rows, cols, d_hist1024, d_record4, quantile_q8=0):
+        """a frame's noise level (rsdsfm_noise_level_dev; tests/noise_spec_numpy.py): the histogram of |K * I| over the unclipped samples under
+        the mask into d_hist1024 (1024 device uint32) and [n, m, sigma_q8, 0] into d_record4 (four device uint64), m the quantile_q8 / 256
+        quantile (0: 128, the median).  Enqueued on the context's stream."""
+        self._check(self.lib.rsdsfm_noise_level_dev(self._ctx, _dp(d_image), _dp(d_mask), C.c_int32(channels), C.c_int32(rows), C.c_int32(cols), C.c_int32(quantile_q8),
+                                                    _dp(d_hist1024), _dp(d_record4)), "rsdsfm_noise_level_dev")
+
+    def noise_level(self, image, mask, quantile_q8=0, device=0):
+        """host convenience around noise_level_dev: image (rows, cols[, 3]) uint8, mask (rows, cols) uint8
+        -> dict(hist (1024,) uint32, record (4,) uint64 [n, m, sigma_q8, 0], sigma: the record's sigma in grey levels)"""
+        import torch
+
+        image = np.ascontiguousarray(image, dtype=np.uint8)
+        rows, cols = image.shape[:2]
+        ch = 1 if image.ndim == 2 else image.shape[2]
+        dev = torch.device("cuda", device)
+        with torch.cuda.device(dev):
+            d_i, d_m = torch.from_numpy(image).to(dev), torch.from_numpy(np.ascontiguousarray(mask, dtype=np.uint8)).to(dev)
+            d_h, d_r = torch.empty(NOISE_BINS, dtype=torch.int32, device=dev), torch.empty(4, dtype=torch.int64, device=dev)
+            torch.cuda.synchronize()
+            self.noise_level_dev(d_i.data_ptr(), d_m.data_ptr(), ch, rows, cols, d_h.data_ptr(), d_r.data_ptr(), quantile_q8)
+            self.synchronize()
+            record = d_r.cpu().numpy().view(np.uint64)
+            return dict(hist=d_h.cpu().numpy().view(np.uint32), record=record, sigma=int(record[2]) / 256.0)
+
+    def denoise_accumulate_auto_dev(self, d_ref, d_ref_mask, d_layer, d_layer_mask, channels, rows, cols, d_cells, first, last, d_noise4, d_sums8=None, min_overlap=0,
+                                    gain_mode=0, strength=0, scale=0, min_samples=0, d_image_out=None, d_mask_out=None, d_weight=None, d_counts3=None):
+        """denoise_accumulate_dev at the strength the record d_noise4 (four device uint64, noise_level_dev's) asks for, formed on the device
+        (rsdsfm_denoise_accumulate_auto_dev): `strength` is the fallback where the record has fewer than min_samples samples.  Enqueued on the
+        context's stream."""
+        self._check(self.lib.rsdsfm_denoise_accumulate_auto_dev(self._ctx, _dp(d_ref), _dp(d_ref_mask), _np0(d_layer), _np0(d_layer_mask), C.c_int32(channels), C.c_int32(rows),
+                                                                C.c_int32(cols), _np0(d_sums8), C.c_int64(min_overlap), C.c_int32(gain_mode), C.c_int32(strength), _np0(d_noise4),
+                                                                C.c_int32(scale), C.c_int64(min_samples), _np0(d_cells), C.c_int32(int(first)), C.c_int32(int(last)),
+                                                                _np0(d_image_out), _np0(d_mask_out), _np0(d_weight), _np0(d_counts3)), "rsdsfm_denoise_accumulate_auto_dev")
+
+    def denoise_accumulate_auto(self, ref, ref_mask, layers, record4, records=None, min_overlap=0, gain_mode=0, strength=0, scale=0, min_samples=0, device=0):
+        """host convenience around denoise_accumulate_auto_dev: denoise_accumulate's arguments with record4, a noise record (4,) uint64
+        -> (image, mask, weight (rows, cols) uint8, counts (3,) int64 [unset, own only, averaged])"""
+        import torch
+
+        ref = np.ascontiguousarray(ref, dtype=np.uint8)
+        rows, cols = ref.shape[:2]
+        ch = 1 if ref.ndim == 2 else ref.shape[2]
+        dev = torch.device("cuda", device)
+        with torch.cuda.device(dev):
+            up = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.uint8)).to(dev)
+            up64 = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.uint64).view(np.int64)).to(dev)
+            d_ref, d_rm, d_n = up(ref), up(ref_mask), up64(record4)
+            d_l = [(up(i), up(m)) for i, m in layers]
+            d_rec = [None if records is None or records[j] is None else up64(records[j]) for j in range(len(layers))]
+            d_cells = torch.empty((rows, cols, ch + 1), dtype=torch.int16, device=dev)
+            d_out, d_mask = torch.empty_like(d_ref), torch.empty((rows, cols), dtype=torch.uint8, device=dev)
+            d_w, d_cnt = torch.empty_like(d_mask), torch.zeros(3, dtype=torch.int64, device=dev)
+            torch.cuda.synchronize()
+            kw = dict(min_overlap=min_overlap, gain_mode=gain_mode, strength=strength, scale=scale, min_samples=min_samples, d_image_out=d_out.data_ptr(),
+                      d_mask_out=d_mask.data_ptr(), d_weight=d_w.data_ptr(), d_counts3=d_cnt.data_ptr())
+            if not d_l:
+                self.denoise_accumulate_auto_dev(d_ref.data_ptr(), d_rm.data_ptr(), None, None, ch, rows, cols, None, True, True, d_n.data_ptr(), None, **kw)
+            for j, (d_i, d_m) in enumerate(d_l):
+                self.denoise_accumulate_auto_dev(d_ref.data_ptr(), d_rm.data_ptr(), d_i.data_ptr(), d_m.data_ptr(), ch, rows, cols, d_cells.data_ptr(), j == 0, j == len(d_l) - 1,
+                                                 d_n.data_ptr(), d_rec[j].data_ptr() if d_rec[j] is not None else None, **kw)
+            self.synchronize()
+            return d_out.cpu().numpy(), d_mask.cpu().numpy(), d_w.cpu().numpy(), d_cnt.cpu().numpy()
+
+    def denoise_spatial_auto_dev(self, d_image, d_mask, d_weight, channels, rows, cols, d_noise4, d_image_out, d_support=None, d_counts3=None, strength=0, scale=0,
+                                 min_samples=0, target=0, search=0):
+        """denoise_spatial_dev at the strength the record d_noise4 asks for, formed on the device (rsdsfm_denoise_spatial_auto_dev): `strength` is
+        the fallback.  Enqueued on the context's stream."""
+        self._check(self.lib.rsdsfm_denoise_spatial_auto_dev(self._ctx, _dp(d_image), _dp(d_mask), _np0(d_weight), C.c_int32(channels), C.c_int32(rows), C.c_int32(cols),
+                                                             C.c_int32(strength), _np0(d_noise4), C.c_int32(scale), C.c_int64(min_samples), C.c_int32(target), C.c_int32(search),
+                                                             _dp(d_image_out), _np0(d_support), _np0(d_counts3)), "rsdsfm_denoise_spatial_auto_dev")
+
+    def denoise_spatial_auto(self, image, mask, record4, weight=None, strength=0, scale=0, min_samples=0, target=0, search=0, device=0):
+        """host convenience around denoise_spatial_auto_dev: denoise_spatial's arguments with record4, a noise record (4,) uint64
+        -> (image, support (rows, cols) uint8, counts (3,) int64 [unset, kept, smoothed])"""
+        import torch
+
+        image = np.ascontiguousarray(image, dtype=np.uint8)
+        rows, cols = image.shape[:2]
+        ch = 1 if image.ndim == 2 else image.shape[2]
+        dev = torch.device("cuda", device)
+        with torch.cuda.device(dev):
+            up = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.uint8)).to(dev)
+            d_i, d_m = up(image), up(mask)
+            d_w = up(weight) if weight is not None else None
+            d_n = torch.from_numpy(np.ascontiguousarray(record4, dtype=np.uint64).view(np.int64)).to(dev)
+            d_out, d_sup = torch.empty_like(d_i), torch.empty((rows, cols), dtype=torch.uint8, device=dev)
+            d_cnt = torch.zeros(3, dtype=torch.int64, device=dev)
+            torch.cuda.synchronize()
+            self.denoise_spatial_auto_dev(d_i.data_ptr(), d_m.data_ptr(), d_w.data_ptr() if d_w is not None else None, ch, rows, cols, d_n.data_ptr(), d_out.data_ptr(),
+                                          d_sup.data_ptr(), d_cnt.data_ptr(), strength, scale, min_samples, target, search)
+            self.synchronize()
+            return d_out.cpu().numpy(), d_sup.cpu().numpy(), d_cnt.cpu().numpy()
+
+    def denoise_auto_frame_dev(self, d_images, channels, d_depth_maps, d_R, d_t, K, rows, cols, M, m, d_image, d_mask, d_weight=None, d_support=None, d_counts6=None,
+                               d_noise4=None, strength=None, gain=True, min_overlap=None, window=None, occlusion=False, occlusion_tol_q16=0, mode=BACKPROJECT_RS,
+                               q5_mode=Q5_COMPAT, iterations=0, params=None, quantile_q8=None, scale=None, min_samples=None, noise_params=None, spatial=False,
+                               spatial_strength=None, target=None, search=None, spatial_params=None):
+        """one frame denoised at the strength its own noise asks for (rsdsfm_denoise_auto_frame_dev): denoise_frame_dev's arguments; the rendered
+        own frame is measured (noise_level_dev), every neighbour goes through denoise_accumulate_auto_dev, and with spatial (or spatial_params)
+        denoise_spatial_auto_dev follows on the same record.  `strength` and `spatial_strength` are the fallbacks.  d_counts6: six device int64
+        [unset, own only, averaged, unset, kept, smoothed]; d_noise4: four device uint64 for the record.  Enqueued on the context's stream."""
+        ns = len(d_images)
+        _need_all(ns, d_depth_maps=d_depth_maps, d_R=d_R, d_t=d_t)
+        Mm, mm = _f64(M).reshape(-1, 9), _f64(m).reshape(-1, 3)
+        if Mm.shape[0] < ns or mm.shape[0] < ns:
+            raise RsdsfmError("denoise_auto_frame_dev: every source needs a pose (M, m)")
+        dp = params if params is not None else _denoise_params(None, strength, gain, occlusion, occlusion_tol_q16, min_overlap)
+        npar = noise_params if noise_params is not None else _noise_params(quantile_q8, scale, min_samples)
+        sp = spatial_params if spatial_params is not None else (_denoise_spatial_params(spatial_strength, target, search) if spatial else None)
+        d = C.c_double
+        arr = lambda x: _ptr_array(list(x)[:ns]) if ns else None
+        self._check(self.lib.rsdsfm_denoise_auto_frame_dev(self._ctx, arr(d_images), C.c_int32(channels), arr(d_depth_maps), arr(d_R), arr(d_t), d(K[0]), d(K[1]), d(K[2]),
+                                                           d(K[3]), C.c_int32(rows), C.c_int32(cols), int(mode), int(q5_mode), C.c_int32(iterations), C.c_int32(ns), _p(Mm),
+                                                           _p(mm), C.byref(dp), C.byref(npar), C.byref(sp) if sp is not None else None, _window4(window), _dp(d_image),
+                                                           _dp(d_mask), _np0(d_weight), _np0(d_support), _np0(d_counts6), _np0(d_noise4)), "rsdsfm_denoise_auto_frame_dev")
+
+    def denoise_auto_video_dev(self, d_frames, rows, cols, channels, K, d_depth_maps, d_R, d_t, A, c, A_path, c_path, scales, d_out, d_out_masks, d_out_weights=None,
+                               d_out_supports=None, want_counts=True, want_noise=True, radius=None, strength=None, gain=True, min_overlap=None, window=None,
+                               occlusion=False, occlusion_tol_q16=0, mode=BACKPROJECT_RS, q5_mode=Q5_COMPAT, iterations=0, quantile_q8=None, scale=None, min_samples=None,
+                               spatial=False, spatial_strength=None, target=None, search=None):
+        """a solved clip denoised at every frame's own strength (rsdsfm_denoise_auto_video_dev): denoise_video_dev's clip and walk,
+        denoise_auto_frame_dev per frame.  Returns dict(); with want_counts counts (nsources, 6) int64, with want_noise noise (nsources, 4)
+        uint64 [n, m, sigma_q8, 0] -- with either the call waits."""
+        ns = len(d_depth_maps)
+        _need_all(ns, d_frames=d_frames, d_R=d_R, d_t=d_t, d_out=d_out, d_out_masks=d_out_masks, d_out_weights=d_out_weights, d_out_supports=d_out_supports)
+        a, cc, ap, cp = _f64(A).reshape(-1, 9), _f64(c).reshape(-1, 3), _f64(A_path).reshape(-1, 9), _f64(c_path).reshape(-1, 3)
+        sc = _f64(scales).reshape(-1)
+        if min(a.shape[0], cc.shape[0], ap.shape[0], cp.shape[0], sc.shape[0]) < ns:
+            raise RsdsfmError("denoise_auto_video_dev: every source needs a pose on both paths and a scale")
+        dp = _denoise_params(radius, strength, gain, occlusion, occlusion_tol_q16, min_overlap)
+        npar = _noise_params(quantile_q8, scale, min_samples)
+        sp = _denoise_spatial_params(spatial_strength, target, search) if spatial else None
+        counts = np.zeros((max(ns, 1), 6), dtype=np.int64) if want_counts else None
+        noise = np.zeros((max(ns, 1), 4), dtype=np.uint64) if want_noise else None
+        d = C.c_double
+        arr = lambda x: _ptr_array(list(x)[:ns]) if x is not None and ns else None
+        self._check(self.lib.rsdsfm_denoise_auto_video_dev(self._ctx, arr(d_frames), C.c_int32(ns), C.c_int32(rows), C.c_int32(cols), C.c_int32(channels), d(K[0]), d(K[1]),
+                                                           d(K[2]), d(K[3]), arr(d_depth_maps), arr(d_R), arr(d_t), _p(a), _p(cc), _p(ap), _p(cp), _p(sc), int(mode), int(q5_mode),
+                                                           C.c_int32(iterations), C.byref(dp), C.byref(npar), C.byref(sp) if sp is not None else None, _window4(window),
+                                                           arr(d_out), arr(d_out_masks), arr(d_out_weights), arr(d_out_supports), _p(counts), _p(noise)),
+                    "rsdsfm_denoise_auto_video_dev")
+        out = dict()
+        if want_counts:
+            out["counts"] = counts[:ns]
+        if want_noise:
+            out["noise"] = noise[:ns]
+        return out
+
+
+for _name, _fn in list(vars(_NoiseMixin).items()):
     if not _name.startswith("__"):
         setattr(Solver, _name, _fn)
 

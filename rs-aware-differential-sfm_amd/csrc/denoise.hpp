@@ -52,4 +52,15 @@ inline size_t denoise_spatial_ws_bytes(int rows, int cols) { return 4 * blend_pl
 int denoise_spatial_launch(Ctx* c, const unsigned char* d_image, const unsigned char* d_mask, const unsigned char* d_weight, int channels, int rows, int cols, int strength,
                            int target, int search, unsigned char* d_image_out, unsigned char* d_support, int64_t* d_counts3);
 
+// the top-up's argument checks (denoise_spatial_host.hip), shared with the calls that take the strength from a noise record (noise_host.hip):
+// every 0 replaced by its default, false: outside its range (kSpatialWordsMessage); the params likewise, or the defaults for NULL
+// (kSpatialParamsMessage); what the primitive refuses about its planes, or NULL; the refusal itself, "<stage>: <what>"
+bool spatial_words_resolve(int32_t* strength, int32_t* target, int32_t* search);
+bool spatial_params_resolve(const rsdsfm_denoise_spatial_params* in, rsdsfm_denoise_spatial_params* out);
+extern const char* const kSpatialWordsMessage;
+extern const char* const kSpatialParamsMessage;
+const char* spatial_planes_refusal(const uint8_t* d_image, const uint8_t* d_mask, const uint8_t* d_weight, int channels, int rows, int cols, const uint8_t* d_image_out,
+                                   const uint8_t* d_support, const int64_t* d_counts3);
+int spatial_fail(Ctx* c, const char* stage, const char* what);
+
 }  // namespace rsdsfm

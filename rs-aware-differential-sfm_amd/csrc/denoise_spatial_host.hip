@@ -16,7 +16,9 @@ rsdsfm_denoise_spatial_params spatial_defaults() {
                                          {0, 0, 0, 0}};
 }
 
-// every 0 replaced by its default; false: outside its range
+}  // namespace
+
+// every 0 replaced by its default; false: outside its range (declared in denoise.hpp: the auto calls of noise_host.hip refuse in the same words)
 bool spatial_words_resolve(int32_t* strength, int32_t* target, int32_t* search) {
     if (*strength == 0) *strength = kDenoiseStrengthDefault;
     if (*target == 0) *target = kDenoiseSpatialTargetDefault;
@@ -55,7 +57,6 @@ const char* spatial_planes_refusal(const uint8_t* d_image, const uint8_t* d_mask
 
 int spatial_fail(Ctx* c, const char* stage, const char* what) { return fail(c, RSDSFM_ERR_INVALID, (std::string(stage) + ": " + what).c_str()); }
 
-}  // namespace
 }  // namespace rsdsfm
 
 using namespace rsdsfm;

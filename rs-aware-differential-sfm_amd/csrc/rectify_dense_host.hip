@@ -41,6 +41,8 @@ static void dense_ws_free(DenseWs* w) {
     w->d_deblur_bands = nullptr;
     if (w->d_denoise_spatial) (void)hipFree(w->d_denoise_spatial);
     w->d_denoise_spatial = nullptr;
+    if (w->d_noise) (void)hipFree(w->d_noise);
+    w->d_noise = nullptr;
     w->d_pyr = nullptr;
     w->d_disp = nullptr;
     w->d_mask = nullptr;

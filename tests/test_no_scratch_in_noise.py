@@ -1,0 +1,55 @@
+"""CPU: the noise level's kernels (csrc/noise_kernels.hip) must not need SCRATCH memory (a private segment): noise_hist_kernel<CH> holds its 3 x 6
+window, the column terms and up to twelve (bin, valid) pairs in arrays that stay in registers only while every index is a compile-time constant,
+and the two auto kernels are the accumulate's and the top-up's bodies behind a few scalar operations, so they must stay what those are.  The
+compiler decides, so the build is checked: hipcc -S of the translation unit with each library build's flags, .private_segment_fixed_size and
+.vgpr_spill_count must be 0 and .vgpr_count at most 128 for every instantiation, and there are exactly seventeen of them: the histogram for one
+and three channels, the resolve, the accumulate for one and three channels x FIRST x LAST, the top-up for one and three channels at search 1, 2
+and 3.  (The pattern of tests/test_no_scratch_in_denoise_spatial.py; the same metadata keys only.)"""
+import os
+import re
+import shutil
+import subprocess
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+# mangled names: noise_hist_kernelILi<CH>EE, noise_resolve_kernelE, denoise_accumulate_auto_kernelILi<CH>ELb<F>ELb<L>EE, denoise_spatial_auto_kernelILi<CH>ELi<S>EE
+PATTERNS = {r"\S*noise_hist_kernelILi[13]EE\S*": 2, r"\S*noise_resolve_kernelE\S*": 1, r"\S*denoise_accumulate_auto_kernelILi[13]ELb[01]ELb[01]EE\S*": 8,
+            r"\S*denoise_spatial_auto_kernelILi[13]ELi[123]EE\S*": 6}
+INSTANCES = sum(PATTERNS.values())
+
+
+@pytest.fixture(scope="module")
+def assembly(tmp_path_factory):
+    cache = {}
+
+    def get(flags):
+        key = tuple(flags)
+        if key not in cache:
+            hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+            if not (os.path.exists(hipcc) or shutil.which(hipcc)):
+                pytest.skip("no hipcc")
+            out = tmp_path_factory.mktemp("noise") / ("noise_kernels%d.s" % len(cache))
+            src = os.path.join(ROOT, "rs-aware-differential-sfm_amd", "csrc", "noise_kernels.hip")
+            p = subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-S", "--cuda-device-only", "-I", os.path.join(ROOT, "include")] +
+                               list(flags) + [src, "-o", str(out)], capture_output=True, text=True, timeout=600)
+            assert p.returncode == 0, p.stderr[-3000:]
+            cache[key] = out.read_text()
+        return cache[key]
+
+    return get
+
+
+@pytest.mark.parametrize("flags", [[], ["-DRSDSFM_FUSED=1"]])
+def test_noise_kernels_have_no_private_segment(assembly, flags):
+    txt = assembly(flags)
+    every = []
+    for pattern, count in PATTERNS.items():
+        kernels = re.findall(r"\.name:\s+(%s)\n(?:.*\n)*?\s+\.private_segment_fixed_size:\s+(\d+)\n(?:.*\n)*?\s+\.vgpr_count:\s+(\d+)\n\s+\.vgpr_spill_count:\s+(\d+)" % pattern, txt)
+        assert len(kernels) == count and len({n for n, _, _, _ in kernels}) == count, (pattern, kernels)
+        every += kernels
+    bad = [(n, ps, sp) for n, ps, vg, sp in every if int(ps) != 0 or int(sp) != 0]
+    assert not bad, bad
+    assert all(int(vg) <= 128 for n, ps, vg, sp in every), every
+    assert len(re.findall(r"\.name:\s+\S*kernel\S*\n", txt)) == INSTANCES  # and no kernel beside them
