@@ -139,13 +139,8 @@ def declared_symbols():
     include/rsdsfm_denoise_spatial.h (which rsdsfm_denoise.h includes), include/rsdsfm_superres.h, include/rsdsfm_plate.h,
     include/rsdsfm_plate_medoid.h, include/rsdsfm_erase.h, include/rsdsfm_deblur.h and include/rsdsfm_noise.h declare (used by the CPU symbol-export
     test)."""
-    import re
-
-    txt = "".join(open(os.path.join(os.path.dirname(HEADER_PATH), name)).read()
-                  for name in (os.path.basename(HEADER_PATH), "rsdsfm_retime.h", "rsdsfm_shutter.h", "rsdsfm_denoise.h", "rsdsfm_denoise_spatial.h", "rsdsfm_superres.h",
-                              "rsdsfm_plate.h", "rsdsfm_plate_medoid.h", "rsdsfm_erase.h", "rsdsfm_deblur.h", "rsdsfm_noise.h"))
-    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    return sorted(set(re.findall(r"\b(rsdsfm_[a-z0-9_]+)\s*\(", txt)))
+    return _declared("rsdsfm.h", "rsdsfm_retime.h", "rsdsfm_shutter.h", "rsdsfm_denoise.h", "rsdsfm_denoise_spatial.h", "rsdsfm_superres.h", "rsdsfm_plate.h",
+                     "rsdsfm_plate_medoid.h", "rsdsfm_erase.h", "rsdsfm_deblur.h", "rsdsfm_noise.h")
 
 
 def load_library(build_if_missing=True, arith="reference"):
@@ -433,7 +428,8 @@ class Solver:
         q, u, a, ak = np.empty((n, 2)), np.empty((n, 2)), np.empty(n), np.empty(n)
         cnt = C.c_int64()
         d = C.c_double
-        self._check(self.lib.rsdsfm_flatten(self._ctx, _p(flow_img), C.c_int32(rows), C.c_int32(cols), d(K[0]), d(K[1]), d(K[2]), d(K[3]), d(gamma), d(thr), _p(q), _p(u), _p(a), _p(ak), C.byref(cnt)), "rsdsfm_flatten")
+        self._check(self.lib.rsdsfm_flatten(self._ctx, _p(flow_img), C.c_int32(rows), C.c_int32(cols), *_k4(K), d(gamma), d(thr), _p(q), _p(u), _p(a), _p(ak), C.byref(cnt)),
+                "rsdsfm_flatten")
         m = cnt.value
         return q[:m].copy(), u[:m].copy(), a[:m].copy(), ak[:m].copy()
 
@@ -444,8 +440,7 @@ class Solver:
         dm = np.zeros((cols, rows))
         xs, ys = np.empty(m, dtype=np.int32), np.empty(m, dtype=np.int32)
         flipped = C.c_int()
-        d = C.c_double
-        self._check(self.lib.rsdsfm_depth_map(self._ctx, _p(inl), C.c_int64(m), vv, d(K[0]), d(K[1]), d(K[2]), d(K[3]), C.c_int32(rows), C.c_int32(cols), _p(dm), _p(xs), _p(ys), C.byref(flipped)), "rsdsfm_depth_map")
+        self._check(self.lib.rsdsfm_depth_map(self._ctx, _p(inl), C.c_int64(m), vv, *_k4(K), C.c_int32(rows), C.c_int32(cols), _p(dm), _p(xs), _p(ys), C.byref(flipped)), "rsdsfm_depth_map")
         return dict(depth_map=dm.T.copy(), inliers=inl, v=np.array(vv[:]), xs=xs, ys=ys, flipped=bool(flipped.value))
 
     def pose_table(self, v, w, k, gamma, rows):
@@ -477,7 +472,8 @@ class Solver:
     def flatten_dev(self, d_img, rows, cols, K, gamma, d_q, d_u, d_alpha, d_alpha_k, thr=1e-10):
         cnt = C.c_int64()
         d = C.c_double
-        self._check(self.lib.rsdsfm_flatten_dev(self._ctx, _dp(d_img), C.c_int32(rows), C.c_int32(cols), d(K[0]), d(K[1]), d(K[2]), d(K[3]), d(gamma), d(thr), _dp(d_q), _dp(d_u), _dp(d_alpha), _dp(d_alpha_k), C.byref(cnt)), "rsdsfm_flatten_dev")
+        self._check(self.lib.rsdsfm_flatten_dev(self._ctx, _dp(d_img), C.c_int32(rows), C.c_int32(cols), *_k4(K), d(gamma), d(thr), _dp(d_q), _dp(d_u), _dp(d_alpha),
+                _dp(d_alpha_k), C.byref(cnt)), "rsdsfm_flatten_dev")
         return cnt.value
 
     def ransac_dev(self, d_q, d_u, d_alpha, d_alpha_k, n, use_alpha_k, iterations, tolerance, out_ptrs, samples=None, seed=0, depth_mode=DEPTH_CERES_LM, k_sign_mode=K_COMPAT):
@@ -503,8 +499,8 @@ class Solver:
     def depth_map_dev(self, d_inl, m, v, K, rows, cols, d_depth_map, d_xs=None, d_ys=None):
         vv = _v3(v)
         flipped = C.c_int()
-        d = C.c_double
-        self._check(self.lib.rsdsfm_depth_map_dev(self._ctx, _dp(d_inl), C.c_int64(m), vv, d(K[0]), d(K[1]), d(K[2]), d(K[3]), C.c_int32(rows), C.c_int32(cols), _dp(d_depth_map), _dp(d_xs) if d_xs else None, _dp(d_ys) if d_ys else None, C.byref(flipped)), "rsdsfm_depth_map_dev")
+        self._check(self.lib.rsdsfm_depth_map_dev(self._ctx, _dp(d_inl), C.c_int64(m), vv, *_k4(K), C.c_int32(rows), C.c_int32(cols), _dp(d_depth_map),
+                _dp(d_xs) if d_xs else None, _dp(d_ys) if d_ys else None, C.byref(flipped)), "rsdsfm_depth_map_dev")
         return np.array(vv[:]), bool(flipped.value)
 
     def pose_table_dev(self, v, w, k, gamma, rows, d_R, d_t):
@@ -520,7 +516,7 @@ class Solver:
                           int(flow_index_mode), int(use_global_shutter_mode), 0, float(tol), float(flow_threshold), int(seed))
         res = FrameResult()
         d = C.c_double
-        self._check(self.lib.rsdsfm_solve_frame_dev(self._ctx, _dp(d_flow_img), C.c_int32(rows), C.c_int32(cols), d(K[0]), d(K[1]), d(K[2]), d(K[3]),
+        self._check(self.lib.rsdsfm_solve_frame_dev(self._ctx, _dp(d_flow_img), C.c_int32(rows), C.c_int32(cols), *_k4(K),
                                                     d(gamma), C.byref(prm), _dp(d_depth_map), _dp(d_R) if d_R else None, _dp(d_t) if d_t else None,
                                                     C.byref(res)), "rsdsfm_solve_frame_dev")
         return dict(n=int(res.n_points), num_inliers=int(res.num_inliers), best_trial=int(res.best_trial), flipped=bool(res.flipped),
@@ -554,8 +550,8 @@ class Solver:
                           int(flow_index_mode), int(use_global_shutter_mode), 0, float(tol), float(flow_threshold), int(seed))
         res, info = FrameResult(), TiledInfo()
         d = C.c_double
-        self._check(self.lib.rsdsfm_solve_frame_tiled_dev(self._ctx, _dp(d_img_slab) if d_img_slab else None, C.c_int32(rows), C.c_int32(cols), d(K[0]), d(K[1]),
-                                                          d(K[2]), d(K[3]), d(gamma), C.byref(prm), _dp(d_depth_map), _dp(d_R) if d_R else None,
+        self._check(self.lib.rsdsfm_solve_frame_tiled_dev(self._ctx, _dp(d_img_slab) if d_img_slab else None, C.c_int32(rows), C.c_int32(cols), *_k4(K), d(gamma), C.byref(prm),
+                                                          _dp(d_depth_map), _dp(d_R) if d_R else None,
                                                           _dp(d_t) if d_t else None, C.byref(res), C.byref(info)), "rsdsfm_solve_frame_tiled_dev")
         return dict(n=int(res.n_points), num_inliers=int(res.num_inliers), best_trial=int(res.best_trial), flipped=bool(res.flipped),
                     ransac_w=np.array(res.ransac_w[:]), ransac_v=np.array(res.ransac_v[:]), ransac_k=float(res.ransac_k),
@@ -587,7 +583,7 @@ class Solver:
         res = FrameResult()
         d = C.c_double
         fn = self.lib.rsdsfm_solve_frame_dev
-        args = (self._ctx, _dp(d_flow_img), C.c_int32(rows), C.c_int32(cols), d(K[0]), d(K[1]), d(K[2]), d(K[3]), d(gamma), C.byref(prm),
+        args = (self._ctx, _dp(d_flow_img), C.c_int32(rows), C.c_int32(cols), *_k4(K), d(gamma), C.byref(prm),
                 _dp(d_depth_map), _dp(d_R) if d_R else None, _dp(d_t) if d_t else None, C.byref(res))
         check = self._check
 
@@ -684,6 +680,175 @@ class Solver:
 
 
 # ---------------------------------------------------------------------------------------------------
+# the marshalling kit: what the stage sections below build their calls from, each idiom once.  A helper returns the numpy and ctypes arrays
+# themselves, never a bare address: _p() stays in the call expression, so nothing a call reads can be collected before the call returns.
+# ---------------------------------------------------------------------------------------------------
+def _header_path(name):
+    return os.path.join(os.path.dirname(_HERE), "include", name)
+
+
+def _declared(*headers):
+    """the rsdsfm_* names the given headers of include/ declare"""
+    import re
+
+    txt = re.sub(r"/\*.*?\*/", "", "".join(open(_header_path(h)).read() for h in headers), flags=re.S)
+    return sorted(set(re.findall(r"\b(rsdsfm_[a-z0-9_]+)\s*\(", txt)))
+
+
+def _solver_methods(mixin):
+    """class decorator of a stage section's mixin: its functions become Solver's methods (a mixin is a namespace, not a base class)"""
+    for name, fn in list(vars(mixin).items()):
+        if not name.startswith("__"):
+            setattr(Solver, name, fn)
+    return mixin
+
+
+def _ref(struct):
+    """an optional parameter struct by reference; NULL (the library's defaults) for None"""
+    return None if struct is None else C.byref(struct)
+
+
+def _ptrs(ptrs, n=None):
+    """an optional list of device pointers -> a C array of the first n (None: all of them); NULL for None, and for no entries wanted"""
+    if ptrs is None or n == 0:
+        return None
+    return _ptr_array(list(ptrs) if n is None else list(ptrs)[:n])
+
+
+def _need_all(n, **lists):
+    for what, lst in lists.items():
+        _need_entries(what, lst, n)
+
+
+def _need_entries(what, lst, n):
+    """a clip wrapper's list must have an entry for every frame the call writes: the library reads exactly n pointers"""
+    if lst is not None and len(lst) < n:
+        raise RsdsfmError("%s has %d entries, the call needs %d (one per rendered frame; last_frame=True renders every frame of the clip)" % (what, len(lst), n))
+
+
+def _frame_front(what, d_images, M, m, **lists):
+    """the front of a frame call: ns sources, every list with an entry for each, every source with a pose -> (ns, M as (-1, 9), m as (-1, 3))"""
+    ns = len(d_images)
+    _need_all(ns, **lists)
+    Mm, mm = _f64(M).reshape(-1, 9), _f64(m).reshape(-1, 3)
+    if Mm.shape[0] < ns or mm.shape[0] < ns:
+        raise RsdsfmError("%s: every source needs a pose (M, m)" % what)
+    return ns, Mm, mm
+
+
+def _clip_front(what, d_depth_maps, A, c, A_path, c_path, scales, **lists):
+    """the front of a clip call: as many sources as depth maps, every list with an entry for each, every source with a pose on both paths and a
+    scale -> (ns, A, c, A_path, c_path as (-1, 9) / (-1, 3), scales as (-1))"""
+    ns = len(d_depth_maps)
+    _need_all(ns, **lists)
+    a, cc, ap, cp, sc = _f64(A).reshape(-1, 9), _f64(c).reshape(-1, 3), _f64(A_path).reshape(-1, 9), _f64(c_path).reshape(-1, 3), _f64(scales).reshape(-1)
+    if min(a.shape[0], cc.shape[0], ap.shape[0], cp.shape[0], sc.shape[0]) < ns:
+        raise RsdsfmError("%s: every source needs a pose on both paths and a scale" % what)
+    return ns, a, cc, ap, cp, sc
+
+
+def _counts(want, n, *shape, dtype=np.int64, fill=0):
+    """a per-frame result buffer the library fills, n (at least one) rows of `shape`; None when it is not wanted"""
+    return np.full((max(n, 1),) + shape, fill, dtype=dtype) if want else None
+
+
+def _wanted(n, **buffers):
+    """the first n rows of every buffer that was wanted, by name: what a clip call returns"""
+    return {name: buf[:n] for name, buf in buffers.items() if buf is not None}
+
+
+class _Staging:
+    """host arrays onto a device, library calls on them, the results back -- the one place (beside load_library) that imports torch and the one place
+    the order is written: up() (torch fills the plane on ITS stream) -> ready(), a device-wide wait: a plane is complete before its pointer is
+    handed out, because the library works on another stream -> the library calls -> down(): Solver.synchronize(), then the copies to the host.  A
+    convenience with two phases (stabilize_filled) calls wait() and ready() between them itself."""
+
+    def __init__(self, solver, device):
+        import torch
+
+        self.torch, self.solver, self.dev = torch, solver, torch.device("cuda", device)
+        self._on = torch.cuda.device(self.dev)
+
+    def __enter__(self):
+        self._on.__enter__()
+        return self
+
+    def __exit__(self, *exc):
+        return self._on.__exit__(*exc)
+
+    def up(self, a, dtype=None):
+        """a host array, made contiguous (and of dtype), on the device; None stays None"""
+        return None if a is None else self.torch.from_numpy(np.ascontiguousarray(a, dtype=dtype)).to(self.dev)
+
+    def up64(self, a):
+        """uint64 words, which torch does not have: they travel as int64"""
+        return self.up(np.ascontiguousarray(a, dtype=np.uint64).view(np.int64))
+
+    def up_frame(self, image, depth_map, R, t):
+        """a source as the frame calls take it: the uint8 image, the depth map column-major, the pose table as (rows, 9) and (rows, 3) doubles"""
+        img = np.ascontiguousarray(image, dtype=np.uint8)
+        return self.up(img), self.up(np.asarray(depth_map, dtype=np.float64).T), self.up(_f64(np.asarray(R).reshape(img.shape[0], 9))), self.up(_f64(t))
+
+    def empty(self, shape, dtype="uint8"):
+        return self.torch.empty(shape, dtype=getattr(self.torch, dtype), device=self.dev)
+
+    def zeros(self, shape, dtype="uint8"):
+        return self.torch.zeros(shape, dtype=getattr(self.torch, dtype), device=self.dev)
+
+    def full(self, shape, value, dtype):
+        return self.torch.full(shape if isinstance(shape, tuple) else (shape,), value, dtype=getattr(self.torch, dtype), device=self.dev)
+
+    def empty_like(self, t):
+        return self.torch.empty_like(t)
+
+    def zeros_like(self, t):
+        return self.torch.zeros_like(t)
+
+    @staticmethod
+    def ptrs(tensors):
+        return None if tensors is None else [t.data_ptr() for t in tensors]
+
+    def ready(self):
+        self.torch.cuda.synchronize()
+
+    def wait(self):
+        self.solver.synchronize()
+
+    @staticmethod
+    def host(t):
+        return t.cpu().numpy()
+
+    def down(self, *tensors):
+        self.wait()
+        return tuple(self.host(t) for t in tensors)
+
+
+def _params(struct, init, lib=None, **words):
+    """a parameter struct over the library's defaults: `init` fills it, then every word given a value other than None is set, as the int or the
+    float its field holds"""
+    p = struct()
+    if getattr(lib or load_library(), init)(C.byref(p)) != OK:
+        raise RsdsfmError("%s failed" % init)
+    for name, value in words.items():
+        if value is not None:
+            setattr(p, name, type(getattr(p, name))(value))
+    return p
+
+
+def _launches(entry, admits, *sizes):
+    """a *_launches entry point: int32 sizes in, the number of kernel launches out; a negative answer is a refusal and `admits` says what is taken"""
+    n = getattr(load_library(), entry)(*[C.c_int32(x) for x in sizes])
+    if n < 0:
+        raise RsdsfmError("%s failed (%d): %s" % (entry, n, admits))
+    return n
+
+
+def _k4(K):
+    """K = (fx, fy, cx, cy) as the four doubles every entry point takes: *_k4(K)"""
+    return C.c_double(K[0]), C.c_double(K[1]), C.c_double(K[2]), C.c_double(K[3])
+
+
+# ---------------------------------------------------------------------------------------------------
 # stage-level wrappers of the row-tiled whole-frame solve (include/rsdsfm.h "ROW-TILED WHOLE-FRAME"; driver: dist.py)
 # ---------------------------------------------------------------------------------------------------
 def _np0(ptr):
@@ -709,11 +874,13 @@ def sample_indices(n, iterations, seed):
     return out
 
 
+@_solver_methods
 class _TileMixin:
     def flatten_slab_dev(self, d_img_slab, rows, slab_cols, col0, K, gamma, d_q, d_u, d_alpha, d_alpha_k, thr=1e-10):
         cnt = C.c_int64()
         d = C.c_double
-        self._check(self.lib.rsdsfm_flatten_slab_dev(self._ctx, _np0(d_img_slab), C.c_int32(rows), C.c_int32(slab_cols), C.c_int32(col0), d(K[0]), d(K[1]), d(K[2]), d(K[3]), d(gamma), d(thr), _np0(d_q), _np0(d_u), _np0(d_alpha), _np0(d_alpha_k), C.byref(cnt)), "rsdsfm_flatten_slab_dev")
+        self._check(self.lib.rsdsfm_flatten_slab_dev(self._ctx, _np0(d_img_slab), C.c_int32(rows), C.c_int32(slab_cols), C.c_int32(col0), *_k4(K), d(gamma), d(thr), _np0(d_q),
+                _np0(d_u), _np0(d_alpha), _np0(d_alpha_k), C.byref(cnt)), "rsdsfm_flatten_slab_dev")
         return cnt.value
 
     def minimal9_probe_dev(self, d_q9, d_u9, d_a9, d_ak9, count, use_alpha_k, k_sign_mode, use_cores, d_hyp, d_probe4):
@@ -778,14 +945,9 @@ class _TileMixin:
     def tile_depth_map_dev(self, d_inl, m, d_zsums_all, nranks, m_total, v, K, rows, col0, slab_cols, d_depth_slab, d_xs=None, d_ys=None):
         vv = _v3(v)
         flipped = C.c_int()
-        d = C.c_double
-        self._check(self.lib.rsdsfm_tile_depth_map_dev(self._ctx, _np0(d_inl), C.c_int64(m), _dp(d_zsums_all), C.c_int32(nranks), C.c_int64(m_total), vv, d(K[0]), d(K[1]), d(K[2]), d(K[3]), C.c_int32(rows), C.c_int32(col0), C.c_int32(slab_cols), _np0(d_depth_slab), _np0(d_xs), _np0(d_ys), C.byref(flipped)), "rsdsfm_tile_depth_map_dev")
+        self._check(self.lib.rsdsfm_tile_depth_map_dev(self._ctx, _np0(d_inl), C.c_int64(m), _dp(d_zsums_all), C.c_int32(nranks), C.c_int64(m_total), vv, *_k4(K), C.c_int32(rows),
+                C.c_int32(col0), C.c_int32(slab_cols), _np0(d_depth_slab), _np0(d_xs), _np0(d_ys), C.byref(flipped)), "rsdsfm_tile_depth_map_dev")
         return np.array(vv[:]), bool(flipped.value)
-
-
-for _name, _fn in list(vars(_TileMixin).items()):
-    if not _name.startswith("__"):
-        setattr(Solver, _name, _fn)
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -795,6 +957,7 @@ BACKPROJECT_RS, BACKPROJECT_GS = 0, 1
 Q5_COMPAT, Q5_FIXED = 0, 1
 
 
+@_solver_methods
 class _RectifyMixin:
     def back_project(self, image_bgr, depth_map, R, t, K, mode=BACKPROJECT_RS, q5_mode=Q5_COMPAT, want_coords=True):
         """RsFrame::backProject / backProjectGs.  depth_map: (rows, cols) array; R: (rows, 3, 3) or (rows, 9); t: (rows, 3)."""
@@ -804,13 +967,13 @@ class _RectifyMixin:
         Rr, tt = _f64(np.asarray(R).reshape(rows, 9)), _f64(t)
         gs = np.zeros_like(img)
         c3 = np.zeros((rows, cols, 3), dtype=np.float32) if want_coords else None
-        d = C.c_double
-        self._check(self.lib.rsdsfm_back_project(self._ctx, _p(img), _p(dm), _p(Rr), _p(tt), d(K[0]), d(K[1]), d(K[2]), d(K[3]), C.c_int32(rows), C.c_int32(cols), int(mode), int(q5_mode), _p(gs), _p(c3)), "rsdsfm_back_project")
+        self._check(self.lib.rsdsfm_back_project(self._ctx, _p(img), _p(dm), _p(Rr), _p(tt), *_k4(K), C.c_int32(rows), C.c_int32(cols), int(mode), int(q5_mode), _p(gs), _p(c3)),
+                "rsdsfm_back_project")
         return gs, c3
 
     def back_project_dev(self, d_img, d_depth_map, d_R, d_t, K, rows, cols, d_gs, d_coords=None, mode=BACKPROJECT_RS, q5_mode=Q5_COMPAT):
-        d = C.c_double
-        self._check(self.lib.rsdsfm_back_project_dev(self._ctx, _dp(d_img), _dp(d_depth_map), _dp(d_R), _dp(d_t), d(K[0]), d(K[1]), d(K[2]), d(K[3]), C.c_int32(rows), C.c_int32(cols), int(mode), int(q5_mode), _dp(d_gs), _dp(d_coords) if d_coords else None), "rsdsfm_back_project_dev")
+        self._check(self.lib.rsdsfm_back_project_dev(self._ctx, _dp(d_img), _dp(d_depth_map), _dp(d_R), _dp(d_t), *_k4(K), C.c_int32(rows), C.c_int32(cols), int(mode),
+                int(q5_mode), _dp(d_gs), _dp(d_coords) if d_coords else None), "rsdsfm_back_project_dev")
 
     def interpolate_cracky(self, image_bgr, offset=1):
         img = np.ascontiguousarray(image_bgr, dtype=np.uint8)
@@ -825,32 +988,25 @@ class _RectifyMixin:
     def depth_preview(self, inliers, K, rows, cols):
         inl = _f64(inliers).reshape(-1, 3)
         out = np.zeros((rows, cols), dtype=np.uint8)
-        d = C.c_double
-        self._check(self.lib.rsdsfm_depth_preview(self._ctx, _p(inl), C.c_int64(inl.shape[0]), d(K[0]), d(K[1]), d(K[2]), d(K[3]), C.c_int32(rows), C.c_int32(cols), _p(out)), "rsdsfm_depth_preview")
+        self._check(self.lib.rsdsfm_depth_preview(self._ctx, _p(inl), C.c_int64(inl.shape[0]), *_k4(K), C.c_int32(rows), C.c_int32(cols), _p(out)), "rsdsfm_depth_preview")
         return out
 
     def depth_preview_dev(self, d_inl, m, K, rows, cols, d_out):
-        d = C.c_double
-        self._check(self.lib.rsdsfm_depth_preview_dev(self._ctx, _np0(d_inl), C.c_int64(m), d(K[0]), d(K[1]), d(K[2]), d(K[3]), C.c_int32(rows), C.c_int32(cols), _dp(d_out)), "rsdsfm_depth_preview_dev")
+        self._check(self.lib.rsdsfm_depth_preview_dev(self._ctx, _np0(d_inl), C.c_int64(m), *_k4(K), C.c_int32(rows), C.c_int32(cols), _dp(d_out)), "rsdsfm_depth_preview_dev")
 
     def rectify_frame_dev(self, d_inl, m, d_img, d_depth_map, d_R, d_t, K, rows, cols, d_preview, d_gs, d_fixed, d_coords=None, mode=BACKPROJECT_RS,
                           q5_mode=Q5_COMPAT, offset=1):
         """main.cc:480-523 in one call (rsdsfm_rectify_frame_dev): depth image + back projection + crack interpolation, two launches (three when
         the interpolation offset exceeds 2 or cols is not a multiple of 4)"""
-        d = C.c_double
-        self._check(self.lib.rsdsfm_rectify_frame_dev(self._ctx, _np0(d_inl), C.c_int64(m), _dp(d_img), _dp(d_depth_map), _dp(d_R), _dp(d_t), d(K[0]), d(K[1]),
-                                                      d(K[2]), d(K[3]), C.c_int32(rows), C.c_int32(cols), int(mode), int(q5_mode), C.c_int32(offset),
+        self._check(self.lib.rsdsfm_rectify_frame_dev(self._ctx, _np0(d_inl), C.c_int64(m), _dp(d_img), _dp(d_depth_map), _dp(d_R), _dp(d_t), *_k4(K), C.c_int32(rows),
+                                                      C.c_int32(cols), int(mode), int(q5_mode), C.c_int32(offset),
                                                       _dp(d_preview), _dp(d_gs), _np0(d_coords), _dp(d_fixed)), "rsdsfm_rectify_frame_dev")
-
-
-for _name, _fn in list(vars(_RectifyMixin).items()):
-    if not _name.startswith("__"):
-        setattr(Solver, _name, _fn)
 
 
 # ---------------------------------------------------------------------------------------------------
 # ground-truth flow between two rolling-shutter frames (SURVEY 8 f-2)
 # ---------------------------------------------------------------------------------------------------
+@_solver_methods
 class _TrueFlowMixin:
     def set_true_flow_search(self, mode):
         """0 / False (default): interval-pruned exact search from 96 scanlines on; 1 / True: every scanline for every pixel; 2: pruned
@@ -868,24 +1024,19 @@ class _TrueFlowMixin:
         Rr = _f64(np.asarray(R2).reshape(rows2, 9))
         flow = np.zeros((rows, cols, 2))
         best = np.zeros((rows, cols), dtype=np.int32) if want_best_row else None
-        d = C.c_double
-        self._check(self.lib.rsdsfm_true_flow(self._ctx, _p(maps[0]), _p(maps[1]), _p(maps[2]), C.c_int32(rows), C.c_int32(cols), _p(Rr), _p(tt), C.c_int32(rows2), d(K[0]), d(K[1]), d(K[2]), d(K[3]), int(q5_mode), _p(flow), _p(best)), "rsdsfm_true_flow")
+        self._check(self.lib.rsdsfm_true_flow(self._ctx, _p(maps[0]), _p(maps[1]), _p(maps[2]), C.c_int32(rows), C.c_int32(cols), _p(Rr), _p(tt), C.c_int32(rows2), *_k4(K),
+                int(q5_mode), _p(flow), _p(best)), "rsdsfm_true_flow")
         return flow, best
 
     def true_flow_dev(self, d_wx, d_wy, d_wz, rows, cols, d_R2, d_t2, rows2, K, d_flow, d_best_row=None, q5_mode=Q5_COMPAT):
-        d = C.c_double
-        self._check(self.lib.rsdsfm_true_flow_dev(self._ctx, _dp(d_wx), _dp(d_wy), _dp(d_wz), C.c_int32(rows), C.c_int32(cols), _dp(d_R2), _dp(d_t2), C.c_int32(rows2), d(K[0]), d(K[1]), d(K[2]), d(K[3]), int(q5_mode), _dp(d_flow), _dp(d_best_row) if d_best_row else None), "rsdsfm_true_flow_dev")
-
-
-for _name, _fn in list(vars(_TrueFlowMixin).items()):
-    if not _name.startswith("__"):
-        setattr(Solver, _name, _fn)
+        self._check(self.lib.rsdsfm_true_flow_dev(self._ctx, _dp(d_wx), _dp(d_wy), _dp(d_wz), C.c_int32(rows), C.c_int32(cols), _dp(d_R2), _dp(d_t2), C.c_int32(rows2), *_k4(K),
+                int(q5_mode), _dp(d_flow), _dp(d_best_row) if d_best_row else None), "rsdsfm_true_flow_dev")
 
 
 # ---------------------------------------------------------------------------------------------------
 # DeepFlow front end: two 8-bit frames -> dense flow (include/rsdsfm_flow.h; camera.cc:253-277)
 # ---------------------------------------------------------------------------------------------------
-FLOW_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "rsdsfm_flow.h")
+FLOW_HEADER_PATH = _header_path("rsdsfm_flow.h")
 
 
 class FlowParams(C.Structure):
@@ -898,11 +1049,7 @@ class FlowParams(C.Structure):
 
 def flow_declared_symbols():
     """Names of every function include/rsdsfm_flow.h declares"""
-    import re
-
-    txt = open(FLOW_HEADER_PATH).read()
-    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    return sorted(set(re.findall(r"\b(rsdsfm_[a-z0-9_]+)\s*\(", txt)))
+    return _declared("rsdsfm_flow.h")
 
 
 def flow_default_params():
@@ -932,7 +1079,7 @@ def flow_levels(rows, cols, params=None):
     lib = load_library()
     p = _flow_params(params)
     n = C.c_int32(0)
-    pp = C.byref(p) if p is not None else None
+    pp = _ref(p)
     if lib.rsdsfm_flow_levels(C.c_int32(rows), C.c_int32(cols), pp, C.byref(n), None, None) != OK:
         raise RsdsfmError("rsdsfm_flow_levels: bad arguments")
     lr, lc = (C.c_int32 * n.value)(), (C.c_int32 * n.value)()
@@ -941,6 +1088,7 @@ def flow_levels(rows, cols, params=None):
     return [(lr[i], lc[i]) for i in range(n.value)]
 
 
+@_solver_methods
 class _DeepFlowMixin:
     def deep_flow(self, img1, img2, params=None):
         """Camera::calculateDeepFlow: two uint8 images (rows, cols, 3) BGR or (rows, cols[, 1]) gray -> flow (rows, cols, 2) float64"""
@@ -952,34 +1100,25 @@ class _DeepFlowMixin:
         p = _flow_params(params)
         flow = np.empty((rows, cols, 2))
         self._check(self.lib.rsdsfm_deep_flow(self._ctx, _p(a), _p(b), C.c_int32(rows), C.c_int32(cols), C.c_int32(ch),
-                                              C.byref(p) if p is not None else None, _p(flow)), "rsdsfm_deep_flow")
+                                              _ref(p), _p(flow)), "rsdsfm_deep_flow")
         return flow
 
     def deep_flow_dev(self, d_img1, d_img2, rows, cols, channels, d_flow, params=None):
         """the same on device buffers, enqueued on the context's stream (no host wait)"""
         p = _flow_params(params)
         self._check(self.lib.rsdsfm_deep_flow_dev(self._ctx, _dp(d_img1), _dp(d_img2), C.c_int32(rows), C.c_int32(cols), C.c_int32(channels),
-                                                  C.byref(p) if p is not None else None, _dp(d_flow)), "rsdsfm_deep_flow_dev")
-
-
-for _name, _fn in list(vars(_DeepFlowMixin).items()):
-    if not _name.startswith("__"):
-        setattr(Solver, _name, _fn)
+                                                  _ref(p), _dp(d_flow)), "rsdsfm_deep_flow_dev")
 
 
 # ---------------------------------------------------------------------------------------------------
 # whole clips: frames in, the flow of every consecutive pair and its solve out (include/rsdsfm_video.h)
 # ---------------------------------------------------------------------------------------------------
-VIDEO_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "rsdsfm_video.h")
+VIDEO_HEADER_PATH = _header_path("rsdsfm_video.h")
 
 
 def video_declared_symbols():
     """Names of every function include/rsdsfm_video.h declares"""
-    import re
-
-    txt = open(VIDEO_HEADER_PATH).read()
-    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    return sorted(set(re.findall(r"\b(rsdsfm_[a-z0-9_]+)\s*\(", txt)))
+    return _declared("rsdsfm_video.h")
 
 
 def _ptr_array(ptrs):
@@ -994,6 +1133,7 @@ def _frame_result_dict(r):
                 d_inliers=r.d_inliers, d_inlier_idx=r.d_inlier_idx, d_scanline=r.d_scanline)
 
 
+@_solver_methods
 class _VideoMixin:
     def set_flow_batch(self, pairs):
         """pairs per batch of the clip calls (rsdsfm_set_flow_batch): 1..32, 0 = the default (8); scheduling only (it sizes the
@@ -1011,7 +1151,7 @@ class _VideoMixin:
         p = _flow_params(params)
         flows = np.empty((nf - 1, rows, cols, 2))
         self._check(self.lib.rsdsfm_deep_flow_seq(self._ctx, _ptr_array([f[i].ctypes.data for i in range(nf)]), C.c_int32(nf), C.c_int32(rows),
-                                                  C.c_int32(cols), C.c_int32(ch), C.byref(p) if p is not None else None,
+                                                  C.c_int32(cols), C.c_int32(ch), _ref(p),
                                                   _ptr_array([flows[i].ctypes.data for i in range(nf - 1)])), "rsdsfm_deep_flow_seq")
         return flows
 
@@ -1019,7 +1159,7 @@ class _VideoMixin:
         """the same on device buffers (lists of F frame and F - 1 field pointers), enqueued on the context's stream (no host wait)"""
         p = _flow_params(params)
         self._check(self.lib.rsdsfm_deep_flow_seq_dev(self._ctx, _ptr_array(d_frames), C.c_int32(len(d_frames)), C.c_int32(rows), C.c_int32(cols),
-                                                      C.c_int32(channels), C.byref(p) if p is not None else None, _ptr_array(d_flows)),
+                                                      C.c_int32(channels), _ref(p), _ptr_array(d_flows)),
                     "rsdsfm_deep_flow_seq_dev")
 
     def solve_video_dev(self, d_frames, rows, cols, channels, K, gamma, d_depth_maps, seeds=None, d_flows=None, d_R=None, d_t=None, flow_params=None,
@@ -1033,44 +1173,34 @@ class _VideoMixin:
                           int(flow_index_mode), int(use_global_shutter_mode), 0, float(tol), float(flow_threshold), 1)
         res = (FrameResult * max(n, 1))()
         sd = (C.c_uint64 * n)(*[int(s) for s in seeds]) if seeds is not None else None
-        arr = lambda a: _ptr_array(a) if a is not None else None
         p = _flow_params(flow_params)
         d = C.c_double
         self._check(self.lib.rsdsfm_solve_video_dev(self._ctx, _ptr_array(d_frames), C.c_int32(len(d_frames)), C.c_int32(rows), C.c_int32(cols),
-                                                    C.c_int32(channels), d(K[0]), d(K[1]), d(K[2]), d(K[3]), d(gamma), C.byref(p) if p is not None else None,
-                                                    C.byref(prm), sd, arr(d_flows), _ptr_array(d_depth_maps), arr(d_R), arr(d_t), res),
+                                                    C.c_int32(channels), *_k4(K), d(gamma), _ref(p),
+                                                    C.byref(prm), sd, _ptrs(d_flows), _ptr_array(d_depth_maps), _ptrs(d_R), _ptrs(d_t), res),
                     "rsdsfm_solve_video_dev")
         return [_frame_result_dict(r) for r in res[:n]]
-
-
-for _name, _fn in list(vars(_VideoMixin).items()):
-    if not _name.startswith("__"):
-        setattr(Solver, _name, _fn)
 
 
 # ---------------------------------------------------------------------------------------------------
 # rectified products of whole clips, gray frames included (include/rsdsfm_rectify_video.h)
 # ---------------------------------------------------------------------------------------------------
-RECTIFY_VIDEO_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "rsdsfm_rectify_video.h")
+RECTIFY_VIDEO_HEADER_PATH = _header_path("rsdsfm_rectify_video.h")
 
 
 def rectify_video_declared_symbols():
     """Names of every function include/rsdsfm_rectify_video.h declares"""
-    import re
-
-    txt = open(RECTIFY_VIDEO_HEADER_PATH).read()
-    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    return sorted(set(re.findall(r"\b(rsdsfm_[a-z0-9_]+)\s*\(", txt)))
+    return _declared("rsdsfm_rectify_video.h")
 
 
+@_solver_methods
 class _RectifyVideoMixin:
     def rectify_gray_frame_dev(self, d_inl, m, d_img, d_depth_map, d_R, d_t, K, rows, cols, d_preview, d_gs, d_fixed, d_coords=None, mode=BACKPROJECT_RS,
                                q5_mode=Q5_COMPAT, offset=1):
         """rectify_frame_dev on a one-channel image (rsdsfm_rectify_gray_frame_dev): d_img, d_gs, d_fixed are rows x cols bytes; the outputs are
         channel 0 of rectify_frame_dev's for the image (g, g, g), the depth image and the world points are its bit for bit"""
-        d = C.c_double
-        self._check(self.lib.rsdsfm_rectify_gray_frame_dev(self._ctx, _np0(d_inl), C.c_int64(m), _dp(d_img), _dp(d_depth_map), _dp(d_R), _dp(d_t), d(K[0]),
-                                                           d(K[1]), d(K[2]), d(K[3]), C.c_int32(rows), C.c_int32(cols), int(mode), int(q5_mode),
+        self._check(self.lib.rsdsfm_rectify_gray_frame_dev(self._ctx, _np0(d_inl), C.c_int64(m), _dp(d_img), _dp(d_depth_map), _dp(d_R), _dp(d_t), *_k4(K), C.c_int32(rows),
+                                                           C.c_int32(cols), int(mode), int(q5_mode),
                                                            C.c_int32(offset), _dp(d_preview), _dp(d_gs), _np0(d_coords), _dp(d_fixed)),
                     "rsdsfm_rectify_gray_frame_dev")
 
@@ -1087,45 +1217,33 @@ class _RectifyVideoMixin:
                           int(flow_index_mode), int(use_global_shutter_mode), 0, float(tol), float(flow_threshold), 1)
         res = (FrameResult * max(n, 1))()
         sd = (C.c_uint64 * n)(*[int(s) for s in seeds]) if seeds is not None else None
-        arr = lambda a: _ptr_array(a) if a is not None else None
         p = _flow_params(flow_params)
         d = C.c_double
         self._check(self.lib.rsdsfm_rectify_video_dev(self._ctx, _ptr_array(d_frames), C.c_int32(len(d_frames)), C.c_int32(rows), C.c_int32(cols),
-                                                      C.c_int32(channels), d(K[0]), d(K[1]), d(K[2]), d(K[3]), d(gamma),
-                                                      C.byref(p) if p is not None else None, C.byref(prm), sd, arr(d_flows), _ptr_array(d_depth_maps),
-                                                      arr(d_R), arr(d_t), res, int(mode), int(q5_mode), C.c_int32(offset), _ptr_array(d_depth_est),
-                                                      _ptr_array(d_gs), _ptr_array(d_fixed), arr(d_coords)), "rsdsfm_rectify_video_dev")
+                                                      C.c_int32(channels), *_k4(K), d(gamma),
+                                                      _ref(p), C.byref(prm), sd, _ptrs(d_flows), _ptr_array(d_depth_maps),
+                                                      _ptrs(d_R), _ptrs(d_t), res, int(mode), int(q5_mode), C.c_int32(offset), _ptr_array(d_depth_est),
+                                                      _ptr_array(d_gs), _ptr_array(d_fixed), _ptrs(d_coords)), "rsdsfm_rectify_video_dev")
         return [_frame_result_dict(r) for r in res[:n]]
-
-
-for _name, _fn in list(vars(_RectifyVideoMixin).items()):
-    if not _name.startswith("__"):
-        setattr(Solver, _name, _fn)
 
 
 # ---------------------------------------------------------------------------------------------------
 # the dense global-shutter frame: depth fill + backward warp (include/rsdsfm_rectify_dense.h)
 # ---------------------------------------------------------------------------------------------------
-RECTIFY_DENSE_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "rsdsfm_rectify_dense.h")
+RECTIFY_DENSE_HEADER_PATH = _header_path("rsdsfm_rectify_dense.h")
 
 
 def rectify_dense_declared_symbols():
     """Names of every function include/rsdsfm_rectify_dense.h declares"""
-    import re
-
-    txt = open(RECTIFY_DENSE_HEADER_PATH).read()
-    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    return sorted(set(re.findall(r"\b(rsdsfm_[a-z0-9_]+)\s*\(", txt)))
+    return _declared("rsdsfm_rectify_dense.h")
 
 
 def rectify_dense_launches(rows, cols):
     """kernel launches of one rectify_dense_frame_dev call at this size (rsdsfm_rectify_dense_launches; host only)"""
-    n = load_library().rsdsfm_rectify_dense_launches(C.c_int32(rows), C.c_int32(cols))
-    if n < 0:
-        raise RsdsfmError("rsdsfm_rectify_dense_launches failed (%d): rows and cols must be in [2, 16384]" % n)
-    return n
+    return _launches("rsdsfm_rectify_dense_launches", "rows and cols must be in [2, 16384]", rows, cols)
 
 
+@_solver_methods
 class _RectifyDenseMixin:
     def rectify_dense_frame_dev(self, d_img, channels, d_depth_map, d_R, d_t, K, rows, cols, d_dense, d_mask=None, d_filled=None, d_disp=None,
                                 mode=BACKPROJECT_RS, q5_mode=Q5_COMPAT, iterations=0):
@@ -1133,30 +1251,22 @@ class _RectifyDenseMixin:
         chain per pixel as a displacement plane, and its fixed-point inverse sampled bilinearly.  d_img / d_dense rows x cols x channels
         bytes; optional d_mask rows x cols bytes, d_filled rows x cols doubles (column-major, like d_depth_map), d_disp rows x cols x 2
         floats; iterations 1..16, 0 = the default (3).  Enqueued on the context's stream."""
-        d = C.c_double
-        self._check(self.lib.rsdsfm_rectify_dense_frame_dev(self._ctx, _dp(d_img), C.c_int32(channels), _dp(d_depth_map), _dp(d_R), _dp(d_t), d(K[0]), d(K[1]),
-                                                            d(K[2]), d(K[3]), C.c_int32(rows), C.c_int32(cols), int(mode), int(q5_mode), C.c_int32(iterations),
+        self._check(self.lib.rsdsfm_rectify_dense_frame_dev(self._ctx, _dp(d_img), C.c_int32(channels), _dp(d_depth_map), _dp(d_R), _dp(d_t), *_k4(K), C.c_int32(rows),
+                                                            C.c_int32(cols), int(mode), int(q5_mode), C.c_int32(iterations),
                                                             _dp(d_dense), _np0(d_mask), _np0(d_filled), _np0(d_disp)), "rsdsfm_rectify_dense_frame_dev")
 
     def rectify_dense(self, image, depth_map, R, t, K, mode=BACKPROJECT_RS, q5_mode=Q5_COMPAT, iterations=0, device=0):
         """host convenience around rectify_dense_frame_dev: image (rows, cols) or (rows, cols, 3) uint8, depth_map (rows, cols) (0 where
         unknown), R (rows, 3, 3) / (rows, 9), t (rows, 3).  Returns (dense image, mask)."""
-        import torch
-
         img = np.ascontiguousarray(image, dtype=np.uint8)
         rows, cols = img.shape[:2]
-        dev = torch.device("cuda", device)
-        with torch.cuda.device(dev):
-            up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-            d_img, d_dm = up(img), up(np.asarray(depth_map, dtype=np.float64).T)  # column-major rows x cols
-            d_R, d_t = up(_f64(np.asarray(R).reshape(rows, 9))), up(_f64(t))
-            d_out, d_mask = torch.empty_like(d_img), torch.empty((rows, cols), dtype=torch.uint8, device=dev)
-            torch.cuda.synchronize()
+        with _Staging(self, device) as st:
+            d_img, d_dm, d_R, d_t = st.up_frame(img, depth_map, R, t)
+            d_out, d_mask = st.empty_like(d_img), st.empty((rows, cols))
+            st.ready()
             self.rectify_dense_frame_dev(d_img.data_ptr(), 1 if img.ndim == 2 else img.shape[2], d_dm.data_ptr(), d_R.data_ptr(), d_t.data_ptr(), K, rows, cols,
                                          d_out.data_ptr(), d_mask.data_ptr(), mode=mode, q5_mode=q5_mode, iterations=iterations)
-            self.synchronize()
-            return d_out.cpu().numpy(), d_mask.cpu().numpy()
-
+            return st.down(d_out, d_mask)
     def rectify_dense_video_dev(self, d_frames, rows, cols, channels, K, gamma, d_depth_maps, d_dense, d_masks=None, d_filled=None, seeds=None,
                                 d_flows=None, d_R=None, d_t=None, flow_params=None, mode=BACKPROJECT_RS, q5_mode=Q5_COMPAT, iterations=0, trials=50,
                                 tol=0.05, use_acceleration_mode=False, use_refinement=True, depth_mode=DEPTH_CERES_LM, k_sign_mode=K_COMPAT,
@@ -1169,26 +1279,20 @@ class _RectifyDenseMixin:
                           int(flow_index_mode), int(use_global_shutter_mode), 0, float(tol), float(flow_threshold), 1)
         res = (FrameResult * max(n, 1))()
         sd = (C.c_uint64 * n)(*[int(s) for s in seeds]) if seeds is not None else None
-        arr = lambda a: _ptr_array(a) if a is not None else None
         p = _flow_params(flow_params)
         d = C.c_double
         self._check(self.lib.rsdsfm_rectify_dense_video_dev(self._ctx, _ptr_array(d_frames), C.c_int32(len(d_frames)), C.c_int32(rows), C.c_int32(cols),
-                                                            C.c_int32(channels), d(K[0]), d(K[1]), d(K[2]), d(K[3]), d(gamma),
-                                                            C.byref(p) if p is not None else None, C.byref(prm), sd, arr(d_flows), _ptr_array(d_depth_maps),
-                                                            arr(d_R), arr(d_t), res, int(mode), int(q5_mode), C.c_int32(iterations), _ptr_array(d_dense),
-                                                            arr(d_masks), arr(d_filled)), "rsdsfm_rectify_dense_video_dev")
+                                                            C.c_int32(channels), *_k4(K), d(gamma),
+                                                            _ref(p), C.byref(prm), sd, _ptrs(d_flows), _ptr_array(d_depth_maps),
+                                                            _ptrs(d_R), _ptrs(d_t), res, int(mode), int(q5_mode), C.c_int32(iterations), _ptr_array(d_dense),
+                                                            _ptrs(d_masks), _ptrs(d_filled)), "rsdsfm_rectify_dense_video_dev")
         return [_frame_result_dict(r) for r in res[:n]]
-
-
-for _name, _fn in list(vars(_RectifyDenseMixin).items()):
-    if not _name.startswith("__"):
-        setattr(Solver, _name, _fn)
 
 
 # ---------------------------------------------------------------------------------------------------
 # the forward-backward flow check: an occlusion mask that gates the solve (include/rsdsfm_flow_check.h)
 # ---------------------------------------------------------------------------------------------------
-FLOW_CHECK_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "rsdsfm_flow_check.h")
+FLOW_CHECK_HEADER_PATH = _header_path("rsdsfm_flow_check.h")
 
 
 class FlowCheckParams(C.Structure):
@@ -1197,11 +1301,7 @@ class FlowCheckParams(C.Structure):
 
 def flow_check_declared_symbols():
     """Names of every function include/rsdsfm_flow_check.h declares"""
-    import re
-
-    txt = open(FLOW_CHECK_HEADER_PATH).read()
-    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    return sorted(set(re.findall(r"\b(rsdsfm_[a-z0-9_]+)\s*\(", txt)))
+    return _declared("rsdsfm_flow_check.h")
 
 
 def flow_check_default_params():
@@ -1220,6 +1320,7 @@ def _flow_check_params(a1, a2):
     return FlowCheckParams(float(d["a1"] if a1 is None else a1), float(d["a2"] if a2 is None else a2))
 
 
+@_solver_methods
 class _FlowCheckMixin:
     def flow_consistency_dev(self, d_fwd, d_bwd, rows, cols, d_mask, d_masked=None, d_resid=None, d_count=None, a1=None, a2=None):
         """the forward-backward check on device fields (rsdsfm_flow_consistency_dev; tests/flow_check_spec_numpy.py): d_fwd / d_bwd
@@ -1227,58 +1328,48 @@ class _FlowCheckMixin:
         d_resid rows x cols doubles, d_count one int64.  One launch, enqueued on the context's stream."""
         k = _flow_check_params(a1, a2)
         self._check(self.lib.rsdsfm_flow_consistency_dev(self._ctx, _dp(d_fwd), _dp(d_bwd), C.c_int32(rows), C.c_int32(cols),
-                                                         C.byref(k) if k is not None else None, _dp(d_mask), _np0(d_masked), _np0(d_resid), _np0(d_count)),
+                                                         _ref(k), _dp(d_mask), _np0(d_masked), _np0(d_resid), _np0(d_count)),
                     "rsdsfm_flow_consistency_dev")
 
     def flow_consistency(self, fwd, bwd, a1=None, a2=None, device=0):
         """host convenience around flow_consistency_dev: two (rows, cols, 2) float64 fields in, dict(mask (rows, cols) uint8, masked
         (rows, cols, 2), resid (rows, cols), count) out"""
-        import torch
-
         f, b = _f64(fwd), _f64(bwd)
         if f.ndim != 3 or f.shape[2] != 2 or b.shape != f.shape:
             raise ValueError("the two fields must have the same (rows, cols, 2) shape")
         rows, cols = f.shape[:2]
-        dev = torch.device("cuda", device)
-        with torch.cuda.device(dev):
-            d_f, d_b = torch.from_numpy(f).to(dev), torch.from_numpy(b).to(dev)
-            d_mask = torch.empty((rows, cols), dtype=torch.uint8, device=dev)
-            d_masked, d_resid = torch.empty_like(d_f), torch.empty((rows, cols), dtype=torch.float64, device=dev)
-            d_count = torch.empty(1, dtype=torch.int64, device=dev)
-            torch.cuda.synchronize()
+        with _Staging(self, device) as st:
+            d_f, d_b = st.up(f), st.up(b)
+            d_mask, d_masked, d_resid, d_count = st.empty((rows, cols)), st.empty_like(d_f), st.empty((rows, cols), "float64"), st.empty(1, "int64")
+            st.ready()
             self.flow_consistency_dev(d_f.data_ptr(), d_b.data_ptr(), rows, cols, d_mask.data_ptr(), d_masked.data_ptr(), d_resid.data_ptr(),
                                       d_count.data_ptr(), a1=a1, a2=a2)
-            self.synchronize()
-            return dict(mask=d_mask.cpu().numpy(), masked=d_masked.cpu().numpy(), resid=d_resid.cpu().numpy(), count=int(d_count.cpu()[0]))
-
+            mask, masked, resid, count = st.down(d_mask, d_masked, d_resid, d_count)
+            return dict(mask=mask, masked=masked, resid=resid, count=int(count[0]))
     def deep_flow_checked_dev(self, d_img1, d_img2, rows, cols, channels, d_flow, d_mask, d_bwd=None, d_count=None, params=None, a1=None, a2=None):
         """DeepFlow both ways and the check (rsdsfm_deep_flow_checked_dev): d_flow receives the MASKED forward field (solve_frame_dev can
         follow on the same stream), d_mask the mask, optionally d_bwd the backward field and d_count the number of consistent pixels"""
         p, k = _flow_params(params), _flow_check_params(a1, a2)
         self._check(self.lib.rsdsfm_deep_flow_checked_dev(self._ctx, _dp(d_img1), _dp(d_img2), C.c_int32(rows), C.c_int32(cols), C.c_int32(channels),
-                                                          C.byref(p) if p is not None else None, C.byref(k) if k is not None else None, _dp(d_flow),
+                                                          _ref(p), _ref(k), _dp(d_flow),
                                                           _np0(d_bwd), _dp(d_mask), _np0(d_count)), "rsdsfm_deep_flow_checked_dev")
 
     def deep_flow_checked(self, img1, img2, params=None, a1=None, a2=None, device=0):
         """host convenience around deep_flow_checked_dev: two uint8 images as deep_flow takes them -> dict(flow (rows, cols, 2): the
         masked forward field, bwd (rows, cols, 2), mask (rows, cols) uint8, count)"""
-        import torch
-
         a, b = np.ascontiguousarray(img1, dtype=np.uint8), np.ascontiguousarray(img2, dtype=np.uint8)
         if a.shape != b.shape or a.ndim not in (2, 3):
             raise ValueError("the two images must have the same (rows, cols[, channels]) shape")
         rows, cols = a.shape[:2]
-        dev = torch.device("cuda", device)
-        with torch.cuda.device(dev):
-            d_a, d_b = torch.from_numpy(a).to(dev), torch.from_numpy(b).to(dev)
-            d_flow, d_bwd = (torch.empty((rows, cols, 2), dtype=torch.float64, device=dev) for _ in range(2))
-            d_mask, d_count = torch.empty((rows, cols), dtype=torch.uint8, device=dev), torch.empty(1, dtype=torch.int64, device=dev)
-            torch.cuda.synchronize()
+        with _Staging(self, device) as st:
+            d_a, d_b = st.up(a), st.up(b)
+            d_flow, d_bwd = (st.empty((rows, cols, 2), "float64") for _ in range(2))
+            d_mask, d_count = st.empty((rows, cols)), st.empty(1, "int64")
+            st.ready()
             self.deep_flow_checked_dev(d_a.data_ptr(), d_b.data_ptr(), rows, cols, 1 if a.ndim == 2 else a.shape[2], d_flow.data_ptr(), d_mask.data_ptr(),
                                        d_bwd=d_bwd.data_ptr(), d_count=d_count.data_ptr(), params=params, a1=a1, a2=a2)
-            self.synchronize()
-            return dict(flow=d_flow.cpu().numpy(), bwd=d_bwd.cpu().numpy(), mask=d_mask.cpu().numpy(), count=int(d_count.cpu()[0]))
-
+            flow, bwd, mask, count = st.down(d_flow, d_bwd, d_mask, d_count)
+            return dict(flow=flow, bwd=bwd, mask=mask, count=int(count[0]))
     def solve_video_checked_dev(self, d_frames, rows, cols, channels, K, gamma, d_depth_maps, d_masks, seeds=None, d_flows=None, d_bwd_flows=None,
                                 d_R=None, d_t=None, flow_params=None, a1=None, a2=None, trials=50, tol=0.05, use_acceleration_mode=False,
                                 use_refinement=True, depth_mode=DEPTH_CERES_LM, k_sign_mode=K_COMPAT, flow_threshold=1e-10,
@@ -1293,26 +1384,20 @@ class _FlowCheckMixin:
         res = (FrameResult * max(n, 1))()
         cnt = (C.c_int64 * max(n, 1))()
         sd = (C.c_uint64 * n)(*[int(s) for s in seeds]) if seeds is not None else None
-        arr = lambda a: _ptr_array(a) if a is not None else None
         p, k = _flow_params(flow_params), _flow_check_params(a1, a2)
         d = C.c_double
         self._check(self.lib.rsdsfm_solve_video_checked_dev(self._ctx, _ptr_array(d_frames), C.c_int32(len(d_frames)), C.c_int32(rows), C.c_int32(cols),
-                                                            C.c_int32(channels), d(K[0]), d(K[1]), d(K[2]), d(K[3]), d(gamma),
-                                                            C.byref(p) if p is not None else None, C.byref(prm), sd, arr(d_flows), _ptr_array(d_depth_maps),
-                                                            arr(d_R), arr(d_t), res, C.byref(k) if k is not None else None, _ptr_array(d_masks),
-                                                            arr(d_bwd_flows), cnt), "rsdsfm_solve_video_checked_dev")
+                                                            C.c_int32(channels), *_k4(K), d(gamma),
+                                                            _ref(p), C.byref(prm), sd, _ptrs(d_flows), _ptr_array(d_depth_maps),
+                                                            _ptrs(d_R), _ptrs(d_t), res, _ref(k), _ptr_array(d_masks),
+                                                            _ptrs(d_bwd_flows), cnt), "rsdsfm_solve_video_checked_dev")
         return [dict(_frame_result_dict(r), consistent=int(cnt[i])) for i, r in enumerate(res[:n])]
-
-
-for _name, _fn in list(vars(_FlowCheckMixin).items()):
-    if not _name.startswith("__"):
-        setattr(Solver, _name, _fn)
 
 
 # ---------------------------------------------------------------------------------------------------
 # a clip's trajectory: the links between consecutive pairs, the chain of scales and poses, the clip's points (include/rsdsfm_trajectory.h)
 # ---------------------------------------------------------------------------------------------------
-TRAJECTORY_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "rsdsfm_trajectory.h")
+TRAJECTORY_HEADER_PATH = _header_path("rsdsfm_trajectory.h")
 
 
 class LinkParams(C.Structure):
@@ -1328,18 +1413,12 @@ class LinkRecord(C.Structure):
 
 def trajectory_declared_symbols():
     """Names of every function include/rsdsfm_trajectory.h declares"""
-    import re
-
-    txt = open(TRAJECTORY_HEADER_PATH).read()
-    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    return sorted(set(re.findall(r"\b(rsdsfm_[a-z0-9_]+)\s*\(", txt)))
+    return _declared("rsdsfm_trajectory.h")
 
 
 def link_default_params():
     """the link's defaults as a dict: tol = 0.1, min_links = 16, radix_bits = 0 (rsdsfm_link_params_init)"""
-    p = LinkParams()
-    if load_library().rsdsfm_link_params_init(C.byref(p)) != OK:
-        raise RsdsfmError("rsdsfm_link_params_init failed")
+    p = _params(LinkParams, "rsdsfm_link_params_init")
     return dict(tol=p.tol, min_links=p.min_links, radix_bits=p.radix_bits)
 
 
@@ -1347,16 +1426,7 @@ def _link_params(tol, min_links, radix_bits):
     """(None, None, None) -> NULL (the defaults); otherwise a LinkParams with the given values over the defaults"""
     if tol is None and min_links is None and radix_bits is None:
         return None
-    p = LinkParams()
-    if load_library().rsdsfm_link_params_init(C.byref(p)) != OK:
-        raise RsdsfmError("rsdsfm_link_params_init failed")
-    if tol is not None:
-        p.tol = float(tol)
-    if min_links is not None:
-        p.min_links = int(min_links)
-    if radix_bits is not None:
-        p.radix_bits = int(radix_bits)
-    return p
+    return _params(LinkParams, "rsdsfm_link_params_init", tol=tol, min_links=min_links, radix_bits=radix_bits)
 
 
 def _records_in(records):
@@ -1383,6 +1453,7 @@ def chain_clip(records, vs, ws, gamma):
     return dict(scales=scales[:n], A=A, c=c, broken=broken[:max(n - 1, 0)])
 
 
+@_solver_methods
 class _TrajectoryMixin:
     def link_pairs_dev(self, d_fields, d_depth_maps, vs, ws, ks, rows, cols, K, gamma, global_shutter=False, d_planes=None, tol=None, min_links=None,
                        radix_bits=None):
@@ -1398,9 +1469,9 @@ class _TrajectoryMixin:
         rec = (LinkRecord * max(n - 1, 1))()
         d = C.c_double
         self._check(self.lib.rsdsfm_link_pairs_dev(self._ctx, _ptr_array(list(d_fields) + [0] * (n - len(d_fields))), _ptr_array(d_depth_maps), _p(v), _p(w),
-                                                   _p(k), C.c_int32(n), C.c_int32(rows), C.c_int32(cols), d(K[0]), d(K[1]), d(K[2]), d(K[3]), d(gamma),
-                                                   C.c_int32(int(bool(global_shutter))), C.byref(p) if p is not None else None,
-                                                   _ptr_array(d_planes) if d_planes is not None else None, rec), "rsdsfm_link_pairs_dev")
+                                                   _p(k), C.c_int32(n), C.c_int32(rows), C.c_int32(cols), *_k4(K), d(gamma),
+                                                   C.c_int32(int(bool(global_shutter))), _ref(p),
+                                                   _ptrs(d_planes), rec), "rsdsfm_link_pairs_dev")
         return [r.as_dict() for r in rec[:max(n - 1, 0)]]
 
     def link_pairs(self, fields, depth_maps, vs, ws, ks, K, gamma, global_shutter=False, tol=None, min_links=None, radix_bits=None, want_planes=False,
@@ -1408,23 +1479,18 @@ class _TrajectoryMixin:
         """host convenience around link_pairs_dev: fields (n or n - 1, rows, cols, 2) float64, depth_maps (n, rows, cols) float64 (row-major
         here; uploaded column-major, as the solve writes them) -> the n - 1 records, each with "plane" ((rows, cols) uint64) when
         want_planes"""
-        import torch
-
         maps = [_f64(m) for m in depth_maps]
         rows, cols = maps[0].shape
-        dev = torch.device("cuda", device)
-        with torch.cuda.device(dev):
-            d_f = [torch.from_numpy(_f64(f)).to(dev) for f in fields]
-            d_z = [torch.from_numpy(np.ascontiguousarray(m.T)).to(dev) for m in maps]
-            d_pl = [torch.zeros((rows, cols), dtype=torch.int64, device=dev) for _ in range(len(maps) - 1)] if want_planes else None
-            torch.cuda.synchronize()
-            rec = self.link_pairs_dev([t.data_ptr() for t in d_f], [t.data_ptr() for t in d_z], vs, ws, ks, rows, cols, K, gamma, global_shutter,
-                                      [t.data_ptr() for t in d_pl] if want_planes else None, tol, min_links, radix_bits)
-            if want_planes:
+        with _Staging(self, device) as st:
+            d_f = [st.up(_f64(f)) for f in fields]
+            d_z = [st.up(m.T) for m in maps]  # column-major, as the solve writes them
+            d_pl = [st.zeros((rows, cols), "int64") for _ in range(len(maps) - 1)] if want_planes else None
+            st.ready()
+            rec = self.link_pairs_dev(st.ptrs(d_f), st.ptrs(d_z), vs, ws, ks, rows, cols, K, gamma, global_shutter, st.ptrs(d_pl), tol, min_links, radix_bits)
+            if want_planes:  # (link_pairs_dev has waited for the records)
                 for r, t in zip(rec, d_pl):
-                    r["plane"] = t.cpu().numpy().view(np.uint64)
+                    r["plane"] = st.host(t).view(np.uint64)
         return rec
-
     def clip_points_dev(self, d_points_in, d_points_out, rows, cols, scales, A, c):
         """the clip's points (rsdsfm_clip_points_dev): pair q's world points (rows x cols x 3 floats, in frame q's coordinates) ->
         A_q (S_q X) + c_q, float64 rounded once to float; d_points_out[q] may be d_points_in[q]; (0, 0, 0) stays (0, 0, 0).  Enqueued on
@@ -1456,14 +1522,13 @@ class _TrajectoryMixin:
         scales, A, c = np.empty(max(n, 1)), np.empty((max(n, 1) + 1, 3, 3)), np.empty((max(n, 1) + 1, 3))
         broken = np.zeros(max(n - 1, 1), dtype=np.uint8)
         sd = (C.c_uint64 * n)(*[int(s) for s in seeds]) if seeds is not None else None
-        arr = lambda a: _ptr_array(a) if a is not None else None
         p, k, lp = _flow_params(flow_params), _flow_check_params(a1, a2), _link_params(link_tol, min_links, radix_bits)
         d = C.c_double
         self._check(self.lib.rsdsfm_solve_video_linked_dev(self._ctx, _ptr_array(d_frames), C.c_int32(len(d_frames)), C.c_int32(rows), C.c_int32(cols),
-                                                           C.c_int32(channels), d(K[0]), d(K[1]), d(K[2]), d(K[3]), d(gamma),
-                                                           C.byref(p) if p is not None else None, C.byref(prm), sd, arr(d_flows), _ptr_array(d_depth_maps),
-                                                           arr(d_R), arr(d_t), res, C.byref(k) if k is not None else None, arr(d_masks),
-                                                           C.byref(lp) if lp is not None else None, rec, _p(scales), _p(A), _p(c), _p(broken), arr(d_points)),
+                                                           C.c_int32(channels), *_k4(K), d(gamma),
+                                                           _ref(p), C.byref(prm), sd, _ptrs(d_flows), _ptr_array(d_depth_maps),
+                                                           _ptrs(d_R), _ptrs(d_t), res, _ref(k), _ptrs(d_masks),
+                                                           _ref(lp), rec, _p(scales), _p(A), _p(c), _p(broken), _ptrs(d_points)),
                     "rsdsfm_solve_video_linked_dev")
         out = dict(pairs=[_frame_result_dict(r) for r in res[:n]], links=[r.as_dict() for r in rec[:max(n - 1, 0)]], scales=scales[:n], A=A[:n + 1],
                    c=c[:n + 1], broken=broken[:max(n - 1, 0)])
@@ -1474,15 +1539,10 @@ class _TrajectoryMixin:
         return out
 
 
-for _name, _fn in list(vars(_TrajectoryMixin).items()):
-    if not _name.startswith("__"):
-        setattr(Solver, _name, _fn)
-
-
 # ---------------------------------------------------------------------------------------------------
 # the fusion of a clip's depth maps: every pair's holes filled from what its neighbours measured there (include/rsdsfm_fuse.h)
 # ---------------------------------------------------------------------------------------------------
-FUSE_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "rsdsfm_fuse.h")
+FUSE_HEADER_PATH = _header_path("rsdsfm_fuse.h")
 FUSE_OWN, FUSE_PREV, FUSE_NEXT, FUSE_PREV_AGREES, FUSE_NEXT_AGREES = 1, 2, 4, 8, 16
 
 
@@ -1500,19 +1560,12 @@ class FuseRecord(C.Structure):
 
 def fuse_declared_symbols():
     """Names of every function include/rsdsfm_fuse.h declares"""
-    import re
-
-    txt = open(FUSE_HEADER_PATH).read()
-    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    return sorted(set(re.findall(r"\b(rsdsfm_[a-z0-9_]+)\s*\(", txt)))
+    return _declared("rsdsfm_fuse.h")
 
 
 def fuse_default_params():
     """the fusion's defaults as a dict: tol = 0.1 (rsdsfm_fuse_params_init)"""
-    p = FuseParams()
-    if load_library().rsdsfm_fuse_params_init(C.byref(p)) != OK:
-        raise RsdsfmError("rsdsfm_fuse_params_init failed")
-    return dict(tol=p.tol)
+    return dict(tol=_params(FuseParams, "rsdsfm_fuse_params_init").tol)
 
 
 def _fuse_records_in(records):
@@ -1523,6 +1576,7 @@ def _fuse_records_in(records):
     return rec
 
 
+@_solver_methods
 class _FuseMixin:
     def fuse_depths_dev(self, d_fields, d_depth_maps, vs, ws, ks, rows, cols, K, gamma, records, d_fused, global_shutter=False, d_flags=None, d_planes=None,
                         tol=None, want_records=True):
@@ -1535,59 +1589,44 @@ class _FuseMixin:
         v, w, k = _f64(vs).reshape(-1, 3), _f64(ws).reshape(-1, 3), _f64(ks).reshape(-1)
         if not (v.shape[0] == w.shape[0] == k.shape[0] == n) or len(d_fields) not in (n - 1, n) or len(records) != max(n - 1, 0) or len(d_fused) != n:
             raise ValueError("n depth maps need n motions, n (or n - 1) fields, n - 1 link records and n outputs")
-        p = None
-        if tol is not None:
-            p = FuseParams()
-            if self.lib.rsdsfm_fuse_params_init(C.byref(p)) != OK:
-                raise RsdsfmError("rsdsfm_fuse_params_init failed")
-            p.tol = float(tol)
+        p = _params(FuseParams, "rsdsfm_fuse_params_init", self.lib, tol=tol) if tol is not None else None
         rec = (FuseRecord * max(n, 1))() if want_records else None
         d = C.c_double
         self._check(self.lib.rsdsfm_fuse_depths_dev(self._ctx, _ptr_array(list(d_fields) + [0] * (n - len(d_fields))), _ptr_array(d_depth_maps), _p(v), _p(w),
-                                                    _p(k), C.c_int32(n), C.c_int32(rows), C.c_int32(cols), d(K[0]), d(K[1]), d(K[2]), d(K[3]), d(gamma),
+                                                    _p(k), C.c_int32(n), C.c_int32(rows), C.c_int32(cols), *_k4(K), d(gamma),
                                                     C.c_int32(int(bool(global_shutter))), _fuse_records_in(records) if n > 1 else None,
-                                                    C.byref(p) if p is not None else None, _ptr_array(d_fused),
-                                                    _ptr_array(d_flags) if d_flags is not None else None,
-                                                    _ptr_array(d_planes) if d_planes is not None else None, rec), "rsdsfm_fuse_depths_dev")
+                                                    _ref(p), _ptr_array(d_fused),
+                                                    _ptrs(d_flags),
+                                                    _ptrs(d_planes), rec), "rsdsfm_fuse_depths_dev")
         return [r.as_dict() for r in rec[:n]] if want_records else None
 
     def fuse_depths(self, fields, depth_maps, vs, ws, ks, records, K, gamma, global_shutter=False, tol=None, want_flags=False, want_planes=False, device=0):
         """host convenience around fuse_depths_dev: fields (n or n - 1, rows, cols, 2) float64, depth_maps (n, rows, cols) float64
         (row-major here; uploaded column-major, as the solve writes them), records: the n - 1 link records -> dict(fused: n (rows, cols)
         float64, records: n dicts, flags: n (rows, cols) uint8 when want_flags, planes: n - 1 (rows, cols) uint64 when want_planes)"""
-        import torch
-
         maps = [_f64(m) for m in depth_maps]
         n = len(maps)
         rows, cols = maps[0].shape
-        dev = torch.device("cuda", device)
-        ptrs = lambda ts: [t.data_ptr() for t in ts]
-        with torch.cuda.device(dev):
-            d_f = [torch.from_numpy(_f64(f)).to(dev) for f in fields]
-            d_z = [torch.from_numpy(np.ascontiguousarray(m.T)).to(dev) for m in maps]
-            d_out = [torch.empty((cols, rows), dtype=torch.float64, device=dev) for _ in range(n)]
-            d_fl = [torch.empty((rows, cols), dtype=torch.uint8, device=dev) for _ in range(n)] if want_flags else None
-            d_pl = [torch.empty((rows, cols), dtype=torch.int64, device=dev) for _ in range(n - 1)] if want_planes else None
-            torch.cuda.synchronize()
-            rec = self.fuse_depths_dev(ptrs(d_f), ptrs(d_z), vs, ws, ks, rows, cols, K, gamma, records, ptrs(d_out), global_shutter,
-                                       ptrs(d_fl) if want_flags else None, ptrs(d_pl) if want_planes else None, tol)
-            out = dict(fused=[t.cpu().numpy().T.copy() for t in d_out], records=rec)
+        with _Staging(self, device) as st:
+            d_f = [st.up(_f64(f)) for f in fields]
+            d_z = [st.up(m.T) for m in maps]  # column-major, as the solve writes them
+            d_out = [st.empty((cols, rows), "float64") for _ in range(n)]
+            d_fl = [st.empty((rows, cols)) for _ in range(n)] if want_flags else None
+            d_pl = [st.empty((rows, cols), "int64") for _ in range(n - 1)] if want_planes else None
+            st.ready()
+            rec = self.fuse_depths_dev(st.ptrs(d_f), st.ptrs(d_z), vs, ws, ks, rows, cols, K, gamma, records, st.ptrs(d_out), global_shutter, st.ptrs(d_fl), st.ptrs(d_pl), tol)
+            out = dict(fused=[st.host(t).T.copy() for t in d_out], records=rec)  # (fuse_depths_dev has waited for the records)
             if want_flags:
-                out["flags"] = [t.cpu().numpy() for t in d_fl]
+                out["flags"] = [st.host(t) for t in d_fl]
             if want_planes:
-                out["planes"] = [t.cpu().numpy().view(np.uint64) for t in d_pl]
+                out["planes"] = [st.host(t).view(np.uint64) for t in d_pl]
         return out
-
-
-for _name, _fn in list(vars(_FuseMixin).items()):
-    if not _name.startswith("__"):
-        setattr(Solver, _name, _fn)
 
 
 # ---------------------------------------------------------------------------------------------------
 # the stabiliser: a smoothed camera path and every frame rendered from its virtual camera on it (include/rsdsfm_stabilize.h)
 # ---------------------------------------------------------------------------------------------------
-STABILIZE_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "rsdsfm_stabilize.h")
+STABILIZE_HEADER_PATH = _header_path("rsdsfm_stabilize.h")
 
 
 class StabilizeParams(C.Structure):
@@ -1597,41 +1636,18 @@ class StabilizeParams(C.Structure):
 
 def stabilize_declared_symbols():
     """Names of every function include/rsdsfm_stabilize.h declares"""
-    import re
-
-    txt = open(STABILIZE_HEADER_PATH).read()
-    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    return sorted(set(re.findall(r"\b(rsdsfm_[a-z0-9_]+)\s*\(", txt)))
+    return _declared("rsdsfm_stabilize.h")
 
 
 def stabilize_default_params():
     """the stabiliser's defaults as a dict: sigma = 4.0 frames, radius = 0 (ceil(3 sigma)), translation = 1 (rsdsfm_stabilize_params_init)"""
-    p = StabilizeParams()
-    if load_library().rsdsfm_stabilize_params_init(C.byref(p)) != OK:
-        raise RsdsfmError("rsdsfm_stabilize_params_init failed")
+    p = _params(StabilizeParams, "rsdsfm_stabilize_params_init")
     return dict(sigma=p.sigma, radius=p.radius, translation=p.translation)
 
 
 def _stabilize_params(sigma, radius, translation, last_frame=False):
     """a StabilizeParams with the given values over the defaults (sigma None: the default)"""
-    p = StabilizeParams()
-    if load_library().rsdsfm_stabilize_params_init(C.byref(p)) != OK:
-        raise RsdsfmError("rsdsfm_stabilize_params_init failed")
-    if sigma is not None:
-        p.sigma = float(sigma)
-    p.radius, p.translation, p.last_frame = int(radius), int(bool(translation)), int(last_frame)
-    return p
-
-
-def _need_all(n, **lists):
-    for what, lst in lists.items():
-        _need_entries(what, lst, n)
-
-
-def _need_entries(what, lst, n):
-    """a clip wrapper's list must have an entry for every frame the call writes: the library reads exactly n pointers"""
-    if lst is not None and len(lst) < n:
-        raise RsdsfmError("%s has %d entries, the call needs %d (one per rendered frame; last_frame=True renders every frame of the clip)" % (what, len(lst), n))
+    return _params(StabilizeParams, "rsdsfm_stabilize_params_init", sigma=sigma, radius=radius, translation=bool(translation), last_frame=last_frame)
 
 
 def smooth_path(A, c, sigma=None, radius=0, translation=True):
@@ -1674,45 +1690,35 @@ def virtual_poses(A, c, A_s, c_s, scales, translation=True, last_frame=False):
 def stabilize_launches(rows, cols, count=False):
     """kernel launches of one stabilize_frame_dev call at this size: rectify_dense_launches, plus one with a valid count
     (rsdsfm_stabilize_launches; host only)"""
-    n = load_library().rsdsfm_stabilize_launches(C.c_int32(rows), C.c_int32(cols), C.c_int32(int(bool(count))))
-    if n < 0:
-        raise RsdsfmError("rsdsfm_stabilize_launches failed (%d): rows and cols must be in [2, 16384]" % n)
-    return n
+    return _launches("rsdsfm_stabilize_launches", "rows and cols must be in [2, 16384]", rows, cols, int(bool(count)))
 
 
+@_solver_methods
 class _StabilizeMixin:
     def stabilize_frame_dev(self, d_img, channels, d_depth_map, d_R, d_t, K, rows, cols, M, m, d_out, d_mask=None, d_filled=None, d_disp=None, d_valid=None,
                             mode=BACKPROJECT_RS, q5_mode=Q5_COMPAT, iterations=0):
         """rectify_dense_frame_dev seen from the virtual camera (M (3, 3), m (3): host arrays; rsdsfm_stabilize_frame_dev): one more rigid
         transform inside the dense rectifier's stage B.  d_valid: a device int64 that receives the number of mask pixels that are 1.
         Enqueued on the context's stream."""
-        d = C.c_double
         Mh = None if M is None else _f64(M).reshape(9)
         mh = None if m is None else _f64(m).reshape(3)
-        self._check(self.lib.rsdsfm_stabilize_frame_dev(self._ctx, _dp(d_img), C.c_int32(channels), _dp(d_depth_map), _dp(d_R), _dp(d_t), d(K[0]), d(K[1]), d(K[2]),
-                                                        d(K[3]), C.c_int32(rows), C.c_int32(cols), int(mode), int(q5_mode), C.c_int32(iterations), _p(Mh), _p(mh),
+        self._check(self.lib.rsdsfm_stabilize_frame_dev(self._ctx, _dp(d_img), C.c_int32(channels), _dp(d_depth_map), _dp(d_R), _dp(d_t), *_k4(K), C.c_int32(rows),
+                                                        C.c_int32(cols), int(mode), int(q5_mode), C.c_int32(iterations), _p(Mh), _p(mh),
                                                         _dp(d_out), _np0(d_mask), _np0(d_filled), _np0(d_disp), _np0(d_valid)), "rsdsfm_stabilize_frame_dev")
 
     def stabilize(self, image, depth_map, R, t, K, M, m, mode=BACKPROJECT_RS, q5_mode=Q5_COMPAT, iterations=0, device=0):
         """host convenience around stabilize_frame_dev: image (rows, cols) or (rows, cols, 3) uint8, depth_map (rows, cols) (0 where unknown),
         R (rows, 3, 3) / (rows, 9), t (rows, 3), M (3, 3), m (3).  Returns (stabilised image, mask, valid)."""
-        import torch
-
         img = np.ascontiguousarray(image, dtype=np.uint8)
         rows, cols = img.shape[:2]
-        dev = torch.device("cuda", device)
-        with torch.cuda.device(dev):
-            up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-            d_img, d_dm = up(img), up(np.asarray(depth_map, dtype=np.float64).T)  # column-major rows x cols
-            d_R, d_t = up(_f64(np.asarray(R).reshape(rows, 9))), up(_f64(t))
-            d_out, d_mask = torch.empty_like(d_img), torch.empty((rows, cols), dtype=torch.uint8, device=dev)
-            d_valid = torch.zeros(1, dtype=torch.int64, device=dev)
-            torch.cuda.synchronize()
+        with _Staging(self, device) as st:
+            d_img, d_dm, d_R, d_t = st.up_frame(img, depth_map, R, t)
+            d_out, d_mask, d_valid = st.empty_like(d_img), st.empty((rows, cols)), st.zeros(1, "int64")
+            st.ready()
             self.stabilize_frame_dev(d_img.data_ptr(), 1 if img.ndim == 2 else img.shape[2], d_dm.data_ptr(), d_R.data_ptr(), d_t.data_ptr(), K, rows, cols, M, m,
                                      d_out.data_ptr(), d_mask.data_ptr(), d_valid=d_valid.data_ptr(), mode=mode, q5_mode=q5_mode, iterations=iterations)
-            self.synchronize()
-            return d_out.cpu().numpy(), d_mask.cpu().numpy(), int(d_valid.cpu().numpy()[0])
-
+            out, mask, valid = st.down(d_out, d_mask, d_valid)
+            return out, mask, int(valid[0])
     def stabilize_video_dev(self, d_frames, rows, cols, channels, K, gamma, d_depth_maps, d_flows, d_R, d_t, d_stab, d_masks_out=None, d_fused=None,
                             want_valid=True, sigma=None, radius=0, translation=True, fuse_tol=None, d_masks=None, seeds=None, flow_params=None, a1=None,
                             a2=None, link_tol=None, min_links=None, radix_bits=None, mode=BACKPROJECT_RS, q5_mode=Q5_COMPAT, iterations=0, trials=50, tol=0.05,
@@ -1723,8 +1729,7 @@ class _StabilizeMixin:
         d_stab (and d_masks_out).  Returns solve_video_linked_dev's dict plus A_s, c_s, M, m and, with want_valid, valid (F - 1 counts; the
         call then waits for the frames).  last_frame=True also renders frame F - 1, from the last pair's map moved onto it (last_frame_dev):
         d_depth_maps, d_R, d_t, d_stab, d_masks_out and d_fused then need F entries, and scales, M, m and valid have F."""
-        args = {k_: v_ for k_, v_ in locals().items() if k_ != "self"}
-        return self._stabilize_video("rsdsfm_stabilize_video_dev", (), **args)
+        return self._stabilize_video("rsdsfm_stabilize_video_dev", (), **_stabilize_video_args())
 
     def _stabilize_video(self, entry, tail, d_frames, rows, cols, channels, K, gamma, d_depth_maps, d_flows, d_R, d_t, d_stab, d_masks_out, d_fused, want_valid,
                          sigma, radius, translation, fuse_tol, d_masks, seeds, flow_params, a1, a2, link_tol, min_links, radix_bits, mode, q5_mode, iterations,
@@ -1744,41 +1749,36 @@ class _StabilizeMixin:
         nn = max(n, 1)
         scales, A, c = np.empty(nn + 1), np.empty((nn + 1, 3, 3)), np.empty((nn + 1, 3))
         A_s, c_s, M, m = np.empty((nn + 1, 3, 3)), np.empty((nn + 1, 3)), np.empty((nn + 1, 3, 3)), np.empty((nn + 1, 3))
-        valid = np.zeros(nn + 1, dtype=np.int64) if want_valid else None
+        valid = _counts(want_valid, nn + 1)
         broken = np.zeros(max(n - 1, 1), dtype=np.uint8)
         sd = (C.c_uint64 * n)(*[int(s) for s in seeds]) if seeds is not None else None
-        arr = lambda a: _ptr_array(a) if a is not None else None
         p, k, lp = _flow_params(flow_params), _flow_check_params(a1, a2), _link_params(link_tol, min_links, radix_bits)
         sp = _stabilize_params(sigma, radius, translation, last_frame)
-        fp = None
-        if fuse_tol is not None:
-            fp = FuseParams()
-            if self.lib.rsdsfm_fuse_params_init(C.byref(fp)) != OK:
-                raise RsdsfmError("rsdsfm_fuse_params_init failed")
-            fp.tol = float(fuse_tol)
+        fp = _params(FuseParams, "rsdsfm_fuse_params_init", self.lib, tol=fuse_tol) if fuse_tol is not None else None
         d = C.c_double
-        ref = lambda x: C.byref(x) if x is not None else None
         self._check(getattr(self.lib, entry)(self._ctx, _ptr_array(d_frames), C.c_int32(len(d_frames)), C.c_int32(rows), C.c_int32(cols),
-                                             C.c_int32(channels), d(K[0]), d(K[1]), d(K[2]), d(K[3]), d(gamma), ref(p), C.byref(prm), sd, arr(d_flows),
-                                             arr(d_depth_maps), arr(d_R), arr(d_t), res, ref(k), arr(d_masks), ref(lp), rec, _p(scales), _p(A), _p(c),
-                                             _p(broken), ref(fp), arr(d_fused), C.byref(sp), int(mode), int(q5_mode), C.c_int32(iterations), _p(A_s),
-                                             _p(c_s), _p(M), _p(m), arr(d_stab), arr(d_masks_out), _p(valid), *tail), entry)
+                                             C.c_int32(channels), *_k4(K), d(gamma), _ref(p), C.byref(prm), sd, _ptrs(d_flows),
+                                             _ptrs(d_depth_maps), _ptrs(d_R), _ptrs(d_t), res, _ref(k), _ptrs(d_masks), _ref(lp), rec, _p(scales), _p(A), _p(c),
+                                             _p(broken), _ref(fp), _ptrs(d_fused), C.byref(sp), int(mode), int(q5_mode), C.c_int32(iterations), _p(A_s),
+                                             _p(c_s), _p(M), _p(m), _ptrs(d_stab), _ptrs(d_masks_out), _p(valid), *tail), entry)
         out = dict(pairs=[_frame_result_dict(r) for r in res[:n]], links=[r.as_dict() for r in rec[:max(n - 1, 0)]], scales=scales[:nr], A=A[:n + 1], c=c[:n + 1],
                    broken=broken[:max(n - 1, 0)], A_s=A_s[:n + 1], c_s=c_s[:n + 1], M=M[:nr], m=m[:nr])
-        if want_valid:
-            out["valid"] = valid[:nr]
+        out.update(_wanted(nr, valid=valid))
         return out
 
 
-for _name, _fn in list(vars(_StabilizeMixin).items()):
-    if not _name.startswith("__"):
-        setattr(Solver, _name, _fn)
+def _stabilize_video_args():
+    """the arguments of the calling stabilize_video_* wrapper that _stabilize_video itself takes, selected by ITS parameter names (behind self, entry
+    and tail): a local or a keyword of the wrapper's own cannot leak into the call"""
+    code = Solver._stabilize_video.__code__
+    scope = sys._getframe(1).f_locals
+    return {name: scope[name] for name in code.co_varnames[3:code.co_argcount]}
 
 
 # ---------------------------------------------------------------------------------------------------
 # the stabiliser's border fill: the band its own frame leaves empty, from the neighbouring frames (include/rsdsfm_stabilize_fill.h)
 # ---------------------------------------------------------------------------------------------------
-STABILIZE_FILL_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "rsdsfm_stabilize_fill.h")
+STABILIZE_FILL_HEADER_PATH = _header_path("rsdsfm_stabilize_fill.h")
 
 
 class StabilizeFillParams(C.Structure):
@@ -1788,19 +1788,12 @@ class StabilizeFillParams(C.Structure):
 
 def stabilize_fill_declared_symbols():
     """Names of every function include/rsdsfm_stabilize_fill.h declares"""
-    import re
-
-    txt = open(STABILIZE_FILL_HEADER_PATH).read()
-    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    return sorted(set(re.findall(r"\b(rsdsfm_[a-z0-9_]+)\s*\(", txt)))
+    return _declared("rsdsfm_stabilize_fill.h")
 
 
 def stabilize_fill_default_params():
     """the border fill's defaults as a dict: radius = 2 neighbours on each side (rsdsfm_stabilize_fill_params_init)"""
-    p = StabilizeFillParams()
-    if load_library().rsdsfm_stabilize_fill_params_init(C.byref(p)) != OK:
-        raise RsdsfmError("rsdsfm_stabilize_fill_params_init failed")
-    return dict(radius=p.radius)
+    return dict(radius=_params(StabilizeFillParams, "rsdsfm_stabilize_fill_params_init").radius)
 
 
 def _occlusion_tol_q16(tol):
@@ -1812,14 +1805,8 @@ def _occlusion_tol_q16(tol):
 def _stabilize_fill_params(radius, occlusion=False, occlusion_tol=None):
     """a StabilizeFillParams with the given radius (0: the default); occlusion: the neighbour candidates go through the occlusion test
     (stabilize_visible_frame_dev), occlusion_tol its tolerance as a fraction of the depth in (0, 1] (None: the default, about 0.05)"""
-    p = StabilizeFillParams()
-    if load_library().rsdsfm_stabilize_fill_params_init(C.byref(p)) != OK:
-        raise RsdsfmError("rsdsfm_stabilize_fill_params_init failed")
-    if radius:
-        p.radius = int(radius)
-    p.occlusion = int(occlusion)  # (anything but 0 and 1 is refused by the library)
-    p.occlusion_tol_q16 = 0 if occlusion_tol is None else _occlusion_tol_q16(occlusion_tol)
-    return p
+    return _params(StabilizeFillParams, "rsdsfm_stabilize_fill_params_init", radius=radius or None, occlusion=occlusion,  # (occlusion: anything but 0 and 1 is refused by the library)
+                   occlusion_tol_q16=0 if occlusion_tol is None else _occlusion_tol_q16(occlusion_tol))
 
 
 def neighbour_poses(A, c, A_s, c_s, scales, q, radius=2):
@@ -1846,12 +1833,10 @@ def neighbour_poses(A, c, A_s, c_s, scales, q, radius=2):
 def stabilize_fill_launches(rows, cols):
     """kernel launches of one stabilize_fill_frame_dev call at this size: rectify_dense_launches -- the fill-warp kernel counts by itself
     (rsdsfm_stabilize_fill_launches; host only)"""
-    n = load_library().rsdsfm_stabilize_fill_launches(C.c_int32(rows), C.c_int32(cols))
-    if n < 0:
-        raise RsdsfmError("rsdsfm_stabilize_fill_launches failed (%d): rows and cols must be in [2, 16384]" % n)
-    return n
+    return _launches("rsdsfm_stabilize_fill_launches", "rows and cols must be in [2, 16384]", rows, cols)
 
 
+@_solver_methods
 class _StabilizeFillMixin:
     def stabilize_fill_frame_dev(self, d_img_n, channels, d_depth_map_n, d_R_n, d_t_n, K, rows, cols, M, m, source_id, d_image, d_mask, d_source=None,
                                  d_filled=None, mode=BACKPROJECT_RS, q5_mode=Q5_COMPAT, iterations=0):
@@ -1859,11 +1844,10 @@ class _StabilizeFillMixin:
         virtual camera (M (3, 3), m (3): host arrays, neighbour_poses') and taken where d_mask is 0 and the candidate is valid: d_image gets the
         pixel, d_mask 1, d_source (a device plane of bytes) source_id.  d_filled: a device int64 that receives the number of pixels taken.
         Enqueued on the context's stream."""
-        d = C.c_double
         Mh = None if M is None else _f64(M).reshape(9)
         mh = None if m is None else _f64(m).reshape(3)
-        self._check(self.lib.rsdsfm_stabilize_fill_frame_dev(self._ctx, _dp(d_img_n), C.c_int32(channels), _dp(d_depth_map_n), _dp(d_R_n), _dp(d_t_n), d(K[0]),
-                                                             d(K[1]), d(K[2]), d(K[3]), C.c_int32(rows), C.c_int32(cols), int(mode), int(q5_mode),
+        self._check(self.lib.rsdsfm_stabilize_fill_frame_dev(self._ctx, _dp(d_img_n), C.c_int32(channels), _dp(d_depth_map_n), _dp(d_R_n), _dp(d_t_n), *_k4(K), C.c_int32(rows),
+                                                             C.c_int32(cols), int(mode), int(q5_mode),
                                                              C.c_int32(iterations), _p(Mh), _p(mh), C.c_int32(source_id), _dp(d_image), _dp(d_mask), _np0(d_source),
                                                              _np0(d_filled)), "rsdsfm_stabilize_fill_frame_dev")
 
@@ -1873,38 +1857,27 @@ class _StabilizeFillMixin:
         its neighbours (neighbour_poses, then one stabilize_fill_frame_dev each).  images / depth_maps / Rs / ts are indexed by frame and entry
         q and its candidates' are read: images (rows, cols[, 3]) uint8, depth maps (rows, cols) (0 where unknown), R (rows, 3, 3) / (rows, 9),
         t (rows, 3).  Returns (image, mask, source (rows, cols) uint8, counts (2 + 2 radius,) int64: [none, own, -1, +1, -2, +2, ...])."""
-        import torch
-
         frames, ids, nM, nm = neighbour_poses(A, c, A_s, c_s, scales, q, radius)
         rows, cols = np.asarray(images[q]).shape[:2]
-        dev = torch.device("cuda", device)
-        with torch.cuda.device(dev):
-            up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-
-            def frame(n):  # image, column-major depth map, pose table
-                img = np.ascontiguousarray(images[n], dtype=np.uint8)
-                return up(img), up(np.asarray(depth_maps[n], dtype=np.float64).T), up(_f64(np.asarray(Rs[n]).reshape(rows, 9))), up(_f64(ts[n]))
-
+        with _Staging(self, device) as st:
+            frame = lambda n: st.up_frame(images[n], depth_maps[n], Rs[n], ts[n])
             d_img, d_dm, d_R, d_t = frame(q)
             channels = 1 if d_img.ndim == 2 else d_img.shape[2]
-            d_out, d_mask = torch.empty_like(d_img), torch.empty((rows, cols), dtype=torch.uint8, device=dev)
-            d_cnt = torch.zeros(2 + 2 * radius, dtype=torch.int64, device=dev)
+            d_out, d_mask, d_cnt = st.empty_like(d_img), st.empty((rows, cols)), st.zeros(2 + 2 * radius, "int64")
             cand = [frame(int(n)) for n in frames]
-            torch.cuda.synchronize()
+            st.ready()
             self.stabilize_frame_dev(d_img.data_ptr(), channels, d_dm.data_ptr(), d_R.data_ptr(), d_t.data_ptr(), K, rows, cols, M, m, d_out.data_ptr(),
                                      d_mask.data_ptr(), d_valid=d_cnt[1:].data_ptr(), mode=mode, q5_mode=q5_mode, iterations=iterations)
-            self.synchronize()
+            st.wait()  # two phases: the own frame's mask is complete before torch copies it, and the copy before the fill passes write it
             d_source = d_mask.clone()
-            torch.cuda.synchronize()
+            st.ready()
             for (n_img, n_dm, n_R, n_t), sid, Mn, mn in zip(cand, ids, nM, nm):
                 self.stabilize_fill_frame_dev(n_img.data_ptr(), channels, n_dm.data_ptr(), n_R.data_ptr(), n_t.data_ptr(), K, rows, cols, Mn, mn, int(sid),
                                               d_out.data_ptr(), d_mask.data_ptr(), d_source.data_ptr(), d_cnt[int(sid):].data_ptr(), mode=mode, q5_mode=q5_mode,
                                               iterations=iterations)
-            self.synchronize()
-            counts = d_cnt.cpu().numpy()
+            out, mask, source, counts = st.down(d_out, d_mask, d_source, d_cnt)
             counts[0] = rows * cols - int(counts[1:].sum())
-            return d_out.cpu().numpy(), d_mask.cpu().numpy(), d_source.cpu().numpy(), counts
-
+            return out, mask, source, counts
     def stabilize_video_filled_dev(self, d_frames, rows, cols, channels, K, gamma, d_depth_maps, d_flows, d_R, d_t, d_stab, d_masks_out, d_sources=None,
                                    fill_radius=0, want_counts=True, d_fused=None, want_valid=True, sigma=None, radius=0, translation=True, fuse_tol=None,
                                    d_masks=None, seeds=None, flow_params=None, a1=None, a2=None, link_tol=None, min_links=None, radix_bits=None,
@@ -1924,24 +1897,18 @@ class _StabilizeFillMixin:
         n = len(d_frames) - 1 + (1 if last_frame else 0)  # rendered frames
         _need_all(n, d_sources=d_sources)
         fp = _stabilize_fill_params(fill_radius, occlusion, occlusion_tol)
-        counts = np.zeros((max(n, 1), 2 + 2 * fp.radius), dtype=np.int64) if want_counts else None
-        args = {k_: v_ for k_, v_ in locals().items() if k_ not in ("self", "n", "fp", "counts", "d_sources", "fill_radius", "want_counts", "occlusion", "occlusion_tol", "occlusion_search")}
+        counts = _counts(want_counts, n, 2 + 2 * fp.radius)
+        args = _stabilize_video_args()
         with _occlusion_search_for(self, occlusion_search, occlusion):
-            out = self._stabilize_video("rsdsfm_stabilize_video_filled_dev", (C.byref(fp), _ptr_array(d_sources) if d_sources is not None else None, _p(counts)), **args)
-        if want_counts:
-            out["counts"] = counts[:n]
+            out = self._stabilize_video("rsdsfm_stabilize_video_filled_dev", (C.byref(fp), _ptrs(d_sources), _p(counts)), **args)
+        out.update(_wanted(n, counts=counts))
         return out
-
-
-for _name, _fn in list(vars(_StabilizeFillMixin).items()):
-    if not _name.startswith("__"):
-        setattr(Solver, _name, _fn)
 
 
 # ---------------------------------------------------------------------------------------------------
 # the stabiliser's crop and zoom: one window for the clip, every frame rendered through it (include/rsdsfm_stabilize_crop.h)
 # ---------------------------------------------------------------------------------------------------
-STABILIZE_CROP_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "rsdsfm_stabilize_crop.h")
+STABILIZE_CROP_HEADER_PATH = _header_path("rsdsfm_stabilize_crop.h")
 
 
 class StabilizeCropParams(C.Structure):
@@ -1950,53 +1917,36 @@ class StabilizeCropParams(C.Structure):
 
 def stabilize_crop_declared_symbols():
     """Names of every function include/rsdsfm_stabilize_crop.h declares"""
-    import re
-
-    txt = open(STABILIZE_CROP_HEADER_PATH).read()
-    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    return sorted(set(re.findall(r"\b(rsdsfm_[a-z0-9_]+)\s*\(", txt)))
+    return _declared("rsdsfm_stabilize_crop.h")
 
 
 def stabilize_crop_default_params():
     """the crop's defaults as a dict: max_empty = 0, margin = 1 (rsdsfm_stabilize_crop_params_init)"""
-    p = StabilizeCropParams()
-    if load_library().rsdsfm_stabilize_crop_params_init(C.byref(p)) != OK:
-        raise RsdsfmError("rsdsfm_stabilize_crop_params_init failed")
+    p = _params(StabilizeCropParams, "rsdsfm_stabilize_crop_params_init")
     return dict(max_empty=p.max_empty, margin=p.margin)
 
 
 def _stabilize_crop_params(max_empty, margin):
     """a StabilizeCropParams with the given values over the defaults (margin None: the default)"""
-    p = StabilizeCropParams()
-    if load_library().rsdsfm_stabilize_crop_params_init(C.byref(p)) != OK:
-        raise RsdsfmError("rsdsfm_stabilize_crop_params_init failed")
-    p.max_empty = int(max_empty)
-    if margin is not None:
-        p.margin = int(margin)
-    return p
+    return _params(StabilizeCropParams, "rsdsfm_stabilize_crop_params_init", max_empty=max_empty, margin=margin)
 
 
 def crop_window_launches(rows, cols):
     """kernel launches of one crop_window_dev call: 3 (rsdsfm_crop_window_launches; host only)"""
-    n = load_library().rsdsfm_crop_window_launches(C.c_int32(rows), C.c_int32(cols))
-    if n < 0:
-        raise RsdsfmError("rsdsfm_crop_window_launches failed (%d): rows and cols must be in [2, 16384]" % n)
-    return n
+    return _launches("rsdsfm_crop_window_launches", "rows and cols must be in [2, 16384]", rows, cols)
 
 
 def stabilize_window_launches(rows, cols):
     """kernel launches of one stabilize_window_frame_dev call at this size: stabilize_fill_launches (rsdsfm_stabilize_window_launches; host
     only)"""
-    n = load_library().rsdsfm_stabilize_window_launches(C.c_int32(rows), C.c_int32(cols))
-    if n < 0:
-        raise RsdsfmError("rsdsfm_stabilize_window_launches failed (%d): rows and cols must be in [2, 16384]" % n)
-    return n
+    return _launches("rsdsfm_stabilize_window_launches", "rows and cols must be in [2, 16384]", rows, cols)
 
 
 def _window4(window):
     return None if window is None else (C.c_int32 * 4)(*[int(x) for x in window])
 
 
+@_solver_methods
 class _StabilizeCropMixin:
     def crop_window_dev(self, d_masks, rows, cols, max_empty=0, margin=None):
         """the clip's window (rsdsfm_crop_window_dev; tests/stabilize_crop_spec_numpy.py): d_masks, a list of device planes of rows x cols bytes
@@ -2010,27 +1960,22 @@ class _StabilizeCropMixin:
 
     def crop_window(self, masks, max_empty=0, margin=None, device=0):
         """host convenience around crop_window_dev: masks (planes, rows, cols) or a list of (rows, cols) uint8 arrays"""
-        import torch
-
         m = np.ascontiguousarray(masks, dtype=np.uint8)
         if m.ndim == 2:
             m = m[None]
-        dev = torch.device("cuda", device)
-        with torch.cuda.device(dev):
-            planes = [torch.from_numpy(np.ascontiguousarray(x)).to(dev) for x in m]
-            torch.cuda.synchronize()
-            return self.crop_window_dev([t.data_ptr() for t in planes], m.shape[1], m.shape[2], max_empty, margin)
-
+        with _Staging(self, device) as st:
+            planes = [st.up(x) for x in m]
+            st.ready()
+            return self.crop_window_dev(st.ptrs(planes), m.shape[1], m.shape[2], max_empty, margin)
     def stabilize_window_frame_dev(self, d_img_n, channels, d_depth_map_n, d_R_n, d_t_n, K, rows, cols, M, m, source_id, window, d_image, d_mask, d_source=None,
                                    d_filled=None, mode=BACKPROJECT_RS, q5_mode=Q5_COMPAT, iterations=0):
         """one frame through a window (rsdsfm_stabilize_window_frame_dev): stabilize_fill_frame_dev with output pixel g mapped into
         window = (r0, c0, h, w) before stage C's fixed point, so that the full-size output shows the window, zoomed.  source_id 1 .. 255 (1: the
         own frame, onto a zeroed mask).  Enqueued on the context's stream."""
-        d = C.c_double
         Mh = None if M is None else _f64(M).reshape(9)
         mh = None if m is None else _f64(m).reshape(3)
-        self._check(self.lib.rsdsfm_stabilize_window_frame_dev(self._ctx, _dp(d_img_n), C.c_int32(channels), _dp(d_depth_map_n), _dp(d_R_n), _dp(d_t_n), d(K[0]),
-                                                               d(K[1]), d(K[2]), d(K[3]), C.c_int32(rows), C.c_int32(cols), int(mode), int(q5_mode),
+        self._check(self.lib.rsdsfm_stabilize_window_frame_dev(self._ctx, _dp(d_img_n), C.c_int32(channels), _dp(d_depth_map_n), _dp(d_R_n), _dp(d_t_n), *_k4(K), C.c_int32(rows),
+                                                               C.c_int32(cols), int(mode), int(q5_mode),
                                                                C.c_int32(iterations), _p(Mh), _p(mh), C.c_int32(source_id), _window4(window), _dp(d_image),
                                                                _dp(d_mask), _np0(d_source), _np0(d_filled)), "rsdsfm_stabilize_window_frame_dev")
 
@@ -2039,34 +1984,24 @@ class _StabilizeCropMixin:
         """host convenience: frame q of a clip rendered through `window` from its virtual camera (M, m: virtual_poses' entry q) onto zeroed
         planes, then its neighbours (neighbour_poses with `radius`; 0: none), one stabilize_window_frame_dev each.  Arguments as
         stabilize_filled.  Returns (image, mask, source (rows, cols) uint8, counts (2 + 2 radius,) int64: [none, own, -1, +1, -2, +2, ...])."""
-        import torch
-
         frames, ids, nM, nm = neighbour_poses(A, c, A_s, c_s, scales, q, radius) if radius else ((), (), (), ())
         rows, cols = np.asarray(images[q]).shape[:2]
-        dev = torch.device("cuda", device)
-        with torch.cuda.device(dev):
-            up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-
-            def frame(n):  # image, column-major depth map, pose table
-                img = np.ascontiguousarray(images[n], dtype=np.uint8)
-                return up(img), up(np.asarray(depth_maps[n], dtype=np.float64).T), up(_f64(np.asarray(Rs[n]).reshape(rows, 9))), up(_f64(ts[n]))
-
+        with _Staging(self, device) as st:
+            frame = lambda n: st.up_frame(images[n], depth_maps[n], Rs[n], ts[n])
             own = frame(q)
             channels = 1 if own[0].ndim == 2 else own[0].shape[2]
-            d_out = torch.zeros_like(own[0])
-            d_mask, d_source = (torch.zeros((rows, cols), dtype=torch.uint8, device=dev) for _ in range(2))
-            d_cnt = torch.zeros(2 + 2 * radius, dtype=torch.int64, device=dev)
+            d_out = st.zeros_like(own[0])
+            d_mask, d_source = (st.zeros((rows, cols)) for _ in range(2))
+            d_cnt = st.zeros(2 + 2 * radius, "int64")
             cand = [frame(int(n)) for n in frames]
-            torch.cuda.synchronize()
+            st.ready()
             for (n_img, n_dm, n_R, n_t), sid, Mn, mn in zip([own] + cand, [1] + list(ids), [M] + list(nM), [m] + list(nm)):
                 self.stabilize_window_frame_dev(n_img.data_ptr(), channels, n_dm.data_ptr(), n_R.data_ptr(), n_t.data_ptr(), K, rows, cols, Mn, mn, int(sid), window,
                                                 d_out.data_ptr(), d_mask.data_ptr(), d_source.data_ptr(), d_cnt[int(sid):].data_ptr(), mode=mode, q5_mode=q5_mode,
                                                 iterations=iterations)
-            self.synchronize()
-            counts = d_cnt.cpu().numpy()
+            out, mask, source, counts = st.down(d_out, d_mask, d_source, d_cnt)
             counts[0] = rows * cols - int(counts[1:].sum())
-            return d_out.cpu().numpy(), d_mask.cpu().numpy(), d_source.cpu().numpy(), counts
-
+            return out, mask, source, counts
     def stabilize_video_cropped_dev(self, d_frames, rows, cols, channels, K, gamma, d_depth_maps, d_flows, d_R, d_t, d_stab, d_masks_out, d_crop, d_crop_masks,
                                     d_crop_sources=None, window_in=None, max_empty=0, margin=None, want_crop_counts=True, d_sources=None, fill_radius=2,
                                     want_counts=True, d_fused=None, want_valid=True, sigma=None, radius=0, translation=True, fuse_tol=None, d_masks=None,
@@ -2091,55 +2026,38 @@ class _StabilizeCropMixin:
         fp.radius = int(fill_radius)  # 0 stays 0 here
         cp = _stabilize_crop_params(max_empty, margin)
         width = 2 + 2 * int(fill_radius)
-        counts = np.zeros((max(n, 1), width), dtype=np.int64) if want_counts else None
-        crop_counts = np.zeros((max(n, 1), width), dtype=np.int64) if want_crop_counts else None
+        counts = _counts(want_counts, n, width)
+        crop_counts = _counts(want_crop_counts, n, width)
         window = (C.c_int32 * 4)()
-        own = ("self", "n", "fp", "cp", "width", "counts", "crop_counts", "window", "d_sources", "fill_radius", "want_counts", "d_crop", "d_crop_masks",
-               "d_crop_sources", "window_in", "max_empty", "margin", "want_crop_counts")
-        args = {k_: v_ for k_, v_ in locals().items() if k_ not in own and k_ not in ("own", "occlusion", "occlusion_tol", "occlusion_search")}
-        arr = lambda a: _ptr_array(a) if a is not None else None
+        args = _stabilize_video_args()
         with _occlusion_search_for(self, occlusion_search, occlusion):
             out = self._stabilize_video("rsdsfm_stabilize_video_cropped_dev",
-                                        (C.byref(fp), arr(d_sources), _p(counts), C.byref(cp), _window4(window_in), arr(d_crop), arr(d_crop_masks), arr(d_crop_sources),
+                                        (C.byref(fp), _ptrs(d_sources), _p(counts), C.byref(cp), _window4(window_in), _ptrs(d_crop), _ptrs(d_crop_masks), _ptrs(d_crop_sources),
                                          window, _p(crop_counts)), **args)
         out["window"] = tuple(int(x) for x in window)
-        if want_counts:
-            out["counts"] = counts[:n]
-        if want_crop_counts:
-            out["crop_counts"] = crop_counts[:n]
+        out.update(_wanted(n, counts=counts, crop_counts=crop_counts))
         return out
-
-
-for _name, _fn in list(vars(_StabilizeCropMixin).items()):
-    if not _name.startswith("__"):
-        setattr(Solver, _name, _fn)
 
 
 # ---------------------------------------------------------------------------------------------------
 # the stabiliser's occlusion test: a neighbour offers a pixel only where it is the nearest surface there (include/rsdsfm_stabilize_visible.h)
 # ---------------------------------------------------------------------------------------------------
-STABILIZE_VISIBLE_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "rsdsfm_stabilize_visible.h")
+STABILIZE_VISIBLE_HEADER_PATH = _header_path("rsdsfm_stabilize_visible.h")
 OCCLUSION_TOL_Q16_DEFAULT = 3277  # RSDSFM_OCCLUSION_TOL_Q16_DEFAULT: about 0.05, a choice, not a measurement
 
 
 def stabilize_visible_declared_symbols():
     """Names of every function include/rsdsfm_stabilize_visible.h declares"""
-    import re
-
-    txt = open(STABILIZE_VISIBLE_HEADER_PATH).read()
-    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    return sorted(set(re.findall(r"\b(rsdsfm_[a-z0-9_]+)\s*\(", txt)))
+    return _declared("rsdsfm_stabilize_visible.h")
 
 
 def stabilize_visible_launches(rows, cols):
     """kernel launches of one stabilize_visible_frame_dev call at this size: stabilize_window_launches -- the map kernel splats and the warp
     kernel tests and counts by themselves (rsdsfm_stabilize_visible_launches; host only)"""
-    n = load_library().rsdsfm_stabilize_visible_launches(C.c_int32(rows), C.c_int32(cols))
-    if n < 0:
-        raise RsdsfmError("rsdsfm_stabilize_visible_launches failed (%d): rows and cols must be in [2, 16384]" % n)
-    return n
+    return _launches("rsdsfm_stabilize_visible_launches", "rows and cols must be in [2, 16384]", rows, cols)
 
 
+@_solver_methods
 class _StabilizeVisibleMixin:
     def stabilize_visible_frame_dev(self, d_img_n, channels, d_depth_map_n, d_R_n, d_t_n, K, rows, cols, M, m, source_id, window, d_image, d_mask, d_source=None,
                                     d_counts2=None, tol_q16=0, mode=BACKPROJECT_RS, q5_mode=Q5_COMPAT, iterations=0):
@@ -2147,11 +2065,10 @@ class _StabilizeVisibleMixin:
         stabilize_window_frame_dev, but a valid pixel whose source is not the nearest surface that lands there (within tol_q16 / 65536 of
         the depth; 0: the default, 3277) is rejected and not taken.  d_counts2: two device int64 that receive [taken, rejected].  Enqueued on
         the context's stream."""
-        d = C.c_double
         Mh = None if M is None else _f64(M).reshape(9)
         mh = None if m is None else _f64(m).reshape(3)
-        self._check(self.lib.rsdsfm_stabilize_visible_frame_dev(self._ctx, _dp(d_img_n), C.c_int32(channels), _dp(d_depth_map_n), _dp(d_R_n), _dp(d_t_n), d(K[0]),
-                                                                d(K[1]), d(K[2]), d(K[3]), C.c_int32(rows), C.c_int32(cols), int(mode), int(q5_mode),
+        self._check(self.lib.rsdsfm_stabilize_visible_frame_dev(self._ctx, _dp(d_img_n), C.c_int32(channels), _dp(d_depth_map_n), _dp(d_R_n), _dp(d_t_n), *_k4(K), C.c_int32(rows),
+                                                                C.c_int32(cols), int(mode), int(q5_mode),
                                                                 C.c_int32(iterations), _p(Mh), _p(mh), C.c_int32(source_id), _window4(window), _dp(d_image),
                                                                 _dp(d_mask), _np0(d_source), C.c_int32(tol_q16), _np0(d_counts2)),
                     "rsdsfm_stabilize_visible_frame_dev")
@@ -2161,57 +2078,39 @@ class _StabilizeVisibleMixin:
         """host convenience around stabilize_visible_frame_dev: one candidate -- image_n (rows, cols[, 3]) uint8, depth_map_n (rows, cols) (0
         where unknown), R_n (rows, 3, 3) / (rows, 9), t_n (rows, 3), seen with (M, m) -- onto the planes image / mask / source (None: zeroed;
         the arrays passed are not changed).  window None: the full frame.  Returns (image, mask, source (rows, cols) uint8, taken, rejected)."""
-        import torch
-
         img = np.ascontiguousarray(image_n, dtype=np.uint8)
         rows, cols = img.shape[:2]
         channels = 1 if img.ndim == 2 else img.shape[2]
-        dev = torch.device("cuda", device)
-        with torch.cuda.device(dev):
-            up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-            plane = lambda a, like: up(np.zeros_like(like) if a is None else np.asarray(a, dtype=np.uint8))
+        with _Staging(self, device) as st:
+            plane = lambda a, like: st.up(np.zeros_like(like) if a is None else np.asarray(a, dtype=np.uint8))
             zero = np.zeros((rows, cols), dtype=np.uint8)
-            d_n, d_dm = up(img), up(np.asarray(depth_map_n, dtype=np.float64).T)
-            d_R, d_t = up(_f64(np.asarray(R_n).reshape(rows, 9))), up(_f64(t_n))
+            d_n, d_dm, d_R, d_t = st.up_frame(img, depth_map_n, R_n, t_n)
             d_out, d_mask, d_source = plane(image, img), plane(mask, zero), plane(source, zero)
-            d_cnt = torch.zeros(2, dtype=torch.int64, device=dev)
-            torch.cuda.synchronize()
+            d_cnt = st.zeros(2, "int64")
+            st.ready()
             self.stabilize_visible_frame_dev(d_n.data_ptr(), channels, d_dm.data_ptr(), d_R.data_ptr(), d_t.data_ptr(), K, rows, cols, M, m, int(source_id),
-                                             (0, 0, rows, cols) if window is None else window, d_out.data_ptr(), d_mask.data_ptr(), d_source.data_ptr(),
-                                             d_cnt.data_ptr(), tol_q16=tol_q16, mode=mode, q5_mode=q5_mode, iterations=iterations)
-            self.synchronize()
-            cnt = d_cnt.cpu().numpy()
-            return d_out.cpu().numpy(), d_mask.cpu().numpy(), d_source.cpu().numpy(), int(cnt[0]), int(cnt[1])
-
-
-for _name, _fn in list(vars(_StabilizeVisibleMixin).items()):
-    if not _name.startswith("__"):
-        setattr(Solver, _name, _fn)
+                                         (0, 0, rows, cols) if window is None else window, d_out.data_ptr(), d_mask.data_ptr(), d_source.data_ptr(),
+                                         d_cnt.data_ptr(), tol_q16=tol_q16, mode=mode, q5_mode=q5_mode, iterations=iterations)
+            out, mask, source, cnt = st.down(d_out, d_mask, d_source, d_cnt)
+            return (out, mask, source) + tuple(int(x) for x in cnt)
 
 
 # ---------------------------------------------------------------------------------------------------
 # the search for the visible pre-image: a pixel the occlusion test rejects is looked for again from the source pixel that landed nearest the
 # camera (include/rsdsfm_stabilize_search.h)
 # ---------------------------------------------------------------------------------------------------
-STABILIZE_SEARCH_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "rsdsfm_stabilize_search.h")
+STABILIZE_SEARCH_HEADER_PATH = _header_path("rsdsfm_stabilize_search.h")
 
 
 def stabilize_search_declared_symbols():
     """Names of every function include/rsdsfm_stabilize_search.h declares"""
-    import re
-
-    txt = open(STABILIZE_SEARCH_HEADER_PATH).read()
-    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    return sorted(set(re.findall(r"\b(rsdsfm_[a-z0-9_]+)\s*\(", txt)))
+    return _declared("rsdsfm_stabilize_search.h")
 
 
 def stabilize_search_launches(rows, cols):
     """kernel launches of one stabilize_search_frame_dev call at this size: stabilize_window_launches -- the map kernel splats the keys and the
     warp kernel tests, searches and counts by themselves (rsdsfm_stabilize_search_launches; host only)"""
-    n = load_library().rsdsfm_stabilize_search_launches(C.c_int32(rows), C.c_int32(cols))
-    if n < 0:
-        raise RsdsfmError("rsdsfm_stabilize_search_launches failed (%d): rows and cols must be in [2, 16384]" % n)
-    return n
+    return _launches("rsdsfm_stabilize_search_launches", "rows and cols must be in [2, 16384]", rows, cols)
 
 
 @contextlib.contextmanager
@@ -2231,6 +2130,7 @@ def _occlusion_search_for(solver, search, occlusion):
         solver.set_occlusion_search(before)
 
 
+@_solver_methods
 class _StabilizeSearchMixin:
     def set_occlusion_search(self, on):
         """the clip calls' knob (rsdsfm_set_occlusion_search): 0 (the default) = a neighbour candidate that goes through the occlusion test goes
@@ -2245,11 +2145,10 @@ class _StabilizeSearchMixin:
         stabilize_visible_frame_dev, but a pixel the test rejects is looked for again from the source pixel that landed nearest the camera on
         its cell and, where that ends on the visible surface, recovered.  d_counts3: three device int64 that receive [taken, rejected,
         recovered].  Enqueued on the context's stream."""
-        d = C.c_double
         Mh = None if M is None else _f64(M).reshape(9)
         mh = None if m is None else _f64(m).reshape(3)
-        self._check(self.lib.rsdsfm_stabilize_search_frame_dev(self._ctx, _dp(d_img_n), C.c_int32(channels), _dp(d_depth_map_n), _dp(d_R_n), _dp(d_t_n), d(K[0]),
-                                                               d(K[1]), d(K[2]), d(K[3]), C.c_int32(rows), C.c_int32(cols), int(mode), int(q5_mode),
+        self._check(self.lib.rsdsfm_stabilize_search_frame_dev(self._ctx, _dp(d_img_n), C.c_int32(channels), _dp(d_depth_map_n), _dp(d_R_n), _dp(d_t_n), *_k4(K), C.c_int32(rows),
+                                                               C.c_int32(cols), int(mode), int(q5_mode),
                                                                C.c_int32(iterations), _p(Mh), _p(mh), C.c_int32(source_id), _window4(window), _dp(d_image),
                                                                _dp(d_mask), _np0(d_source), C.c_int32(tol_q16), _np0(d_counts3)),
                     "rsdsfm_stabilize_search_frame_dev")
@@ -2258,38 +2157,27 @@ class _StabilizeSearchMixin:
                          q5_mode=Q5_COMPAT, iterations=0, device=0):
         """host convenience around stabilize_search_frame_dev: stabilize_visible's arguments.  Returns (image, mask, source (rows, cols) uint8,
         taken, rejected, recovered)."""
-        import torch
-
         img = np.ascontiguousarray(image_n, dtype=np.uint8)
         rows, cols = img.shape[:2]
         channels = 1 if img.ndim == 2 else img.shape[2]
-        dev = torch.device("cuda", device)
-        with torch.cuda.device(dev):
-            up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-            plane = lambda a, like: up(np.zeros_like(like) if a is None else np.asarray(a, dtype=np.uint8))
+        with _Staging(self, device) as st:
+            plane = lambda a, like: st.up(np.zeros_like(like) if a is None else np.asarray(a, dtype=np.uint8))
             zero = np.zeros((rows, cols), dtype=np.uint8)
-            d_n, d_dm = up(img), up(np.asarray(depth_map_n, dtype=np.float64).T)
-            d_R, d_t = up(_f64(np.asarray(R_n).reshape(rows, 9))), up(_f64(t_n))
+            d_n, d_dm, d_R, d_t = st.up_frame(img, depth_map_n, R_n, t_n)
             d_out, d_mask, d_source = plane(image, img), plane(mask, zero), plane(source, zero)
-            d_cnt = torch.zeros(3, dtype=torch.int64, device=dev)
-            torch.cuda.synchronize()
+            d_cnt = st.zeros(3, "int64")
+            st.ready()
             self.stabilize_search_frame_dev(d_n.data_ptr(), channels, d_dm.data_ptr(), d_R.data_ptr(), d_t.data_ptr(), K, rows, cols, M, m, int(source_id),
-                                            (0, 0, rows, cols) if window is None else window, d_out.data_ptr(), d_mask.data_ptr(), d_source.data_ptr(),
-                                            d_cnt.data_ptr(), tol_q16=tol_q16, mode=mode, q5_mode=q5_mode, iterations=iterations)
-            self.synchronize()
-            cnt = d_cnt.cpu().numpy()
-            return d_out.cpu().numpy(), d_mask.cpu().numpy(), d_source.cpu().numpy(), int(cnt[0]), int(cnt[1]), int(cnt[2])
-
-
-for _name, _fn in list(vars(_StabilizeSearchMixin).items()):
-    if not _name.startswith("__"):
-        setattr(Solver, _name, _fn)
+                                        (0, 0, rows, cols) if window is None else window, d_out.data_ptr(), d_mask.data_ptr(), d_source.data_ptr(),
+                                        d_cnt.data_ptr(), tol_q16=tol_q16, mode=mode, q5_mode=q5_mode, iterations=iterations)
+            out, mask, source, cnt = st.down(d_out, d_mask, d_source, d_cnt)
+            return (out, mask, source) + tuple(int(x) for x in cnt)
 
 
 # ---------------------------------------------------------------------------------------------------
 # the stabiliser's seam blend: a gain per candidate and a feather next to the own frame's empty band (include/rsdsfm_stabilize_blend.h)
 # ---------------------------------------------------------------------------------------------------
-STABILIZE_BLEND_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "rsdsfm_stabilize_blend.h")
+STABILIZE_BLEND_HEADER_PATH = _header_path("rsdsfm_stabilize_blend.h")
 GAIN_ONE = 65536
 
 
@@ -2299,32 +2187,18 @@ class StabilizeBlendParams(C.Structure):
 
 def stabilize_blend_declared_symbols():
     """Names of every function include/rsdsfm_stabilize_blend.h declares"""
-    import re
-
-    txt = open(STABILIZE_BLEND_HEADER_PATH).read()
-    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    return sorted(set(re.findall(r"\b(rsdsfm_[a-z0-9_]+)\s*\(", txt)))
+    return _declared("rsdsfm_stabilize_blend.h")
 
 
 def stabilize_blend_default_params():
     """the blend's defaults as a dict: feather = 16, gain_mode = 0, min_overlap = 1024 (rsdsfm_stabilize_blend_params_init)"""
-    p = StabilizeBlendParams()
-    if load_library().rsdsfm_stabilize_blend_params_init(C.byref(p)) != OK:
-        raise RsdsfmError("rsdsfm_stabilize_blend_params_init failed")
+    p = _params(StabilizeBlendParams, "rsdsfm_stabilize_blend_params_init")
     return dict(feather=p.feather, gain_mode=p.gain_mode, min_overlap=p.min_overlap)
 
 
 def _stabilize_blend_params(feather, gain, min_overlap):
     """a StabilizeBlendParams with the given values over the defaults (feather / min_overlap None or 0: the default; gain False: off)"""
-    p = StabilizeBlendParams()
-    if load_library().rsdsfm_stabilize_blend_params_init(C.byref(p)) != OK:
-        raise RsdsfmError("rsdsfm_stabilize_blend_params_init failed")
-    if feather:
-        p.feather = int(feather)
-    if min_overlap:
-        p.min_overlap = int(min_overlap)
-    p.gain_mode = 0 if gain else 1
-    return p
+    return _params(StabilizeBlendParams, "rsdsfm_stabilize_blend_params_init", feather=feather or None, min_overlap=min_overlap or None, gain_mode=0 if gain else 1)
 
 
 def seam_gains(sums, channels, min_overlap=0, gain_mode=0):
@@ -2342,20 +2216,15 @@ def seam_gains(sums, channels, min_overlap=0, gain_mode=0):
 
 def seam_distance_launches(rows, cols):
     """kernel launches of one seam_distance_dev call: 2 (rsdsfm_seam_distance_launches; host only)"""
-    n = load_library().rsdsfm_seam_distance_launches(C.c_int32(rows), C.c_int32(cols))
-    if n < 0:
-        raise RsdsfmError("rsdsfm_seam_distance_launches failed (%d): rows and cols must be in [2, 16384]" % n)
-    return n
+    return _launches("rsdsfm_seam_distance_launches", "rows and cols must be in [2, 16384]", rows, cols)
 
 
 def seam_blend_layer_launches(rows, cols):
     """kernel launches of one seam_blend_layer_dev call: 2 (rsdsfm_seam_blend_layer_launches; host only)"""
-    n = load_library().rsdsfm_seam_blend_layer_launches(C.c_int32(rows), C.c_int32(cols))
-    if n < 0:
-        raise RsdsfmError("rsdsfm_seam_blend_layer_launches failed (%d): rows and cols must be in [2, 16384]" % n)
-    return n
+    return _launches("rsdsfm_seam_blend_layer_launches", "rows and cols must be in [2, 16384]", rows, cols)
 
 
+@_solver_methods
 class _StabilizeBlendMixin:
     def seam_distance_dev(self, d_mask, rows, cols, feather, d_dist):
         """the seam distance of a device mask into a device plane of bytes (rsdsfm_seam_distance_dev; tests/stabilize_blend_spec_numpy.py): 0 on
@@ -2366,18 +2235,13 @@ class _StabilizeBlendMixin:
 
     def seam_distance(self, mask, feather=0, device=0):
         """host convenience around seam_distance_dev: mask (rows, cols) uint8 -> the distance plane (rows, cols) uint8"""
-        import torch
-
         m = np.ascontiguousarray(mask, dtype=np.uint8)
-        dev = torch.device("cuda", device)
-        with torch.cuda.device(dev):
-            d_m = torch.from_numpy(m).to(dev)
-            d_d = torch.empty_like(d_m)
-            torch.cuda.synchronize()
+        with _Staging(self, device) as st:
+            d_m = st.up(m)
+            d_d = st.empty_like(d_m)
+            st.ready()
             self.seam_distance_dev(d_m.data_ptr(), m.shape[0], m.shape[1], feather, d_d.data_ptr())
-            self.synchronize()
-            return d_d.cpu().numpy()
-
+            return st.down(d_d)[0]
     def seam_blend_layer_dev(self, d_layer_image, d_layer_mask, channels, rows, cols, d_dist, source_id, d_image, d_mask, d_source, d_sums, d_counts=None, feather=None,
                              gain=True, min_overlap=None):
         """one candidate's layer onto the in-out planes (rsdsfm_seam_blend_layer_dev): the sums over the pixels the layer shares with the own
@@ -2416,62 +2280,42 @@ class _StabilizeBlendMixin:
         cp = _stabilize_crop_params(max_empty, margin)
         bp = _stabilize_blend_params(blend_feather, blend_gain, blend_min_overlap)
         width = 2 + 2 * int(fill_radius)
-        counts = np.zeros((max(n, 1), width), dtype=np.int64) if want_counts else None
-        crop_counts = np.zeros((max(n, 1), width), dtype=np.int64) if want_crop_counts else None
-        gains = np.zeros((max(n, 1), max(2 * int(fill_radius), 1), 3), dtype=np.uint32) if want_gains else None
-        blend_counts = np.zeros((max(n, 1), 2 + 4 * int(fill_radius)), dtype=np.int64) if want_blend_counts else None
+        counts = _counts(want_counts, n, width)
+        crop_counts = _counts(want_crop_counts, n, width)
+        gains = _counts(want_gains, n, max(2 * int(fill_radius), 1), 3, dtype=np.uint32)
+        blend_counts = _counts(want_blend_counts, n, 2 + 4 * int(fill_radius))
         window = (C.c_int32 * 4)()
-        own = ("self", "n", "fp", "cp", "bp", "width", "counts", "crop_counts", "gains", "blend_counts", "window", "d_sources", "fill_radius", "want_counts", "d_crop",
-               "d_crop_masks", "d_crop_sources", "window_in", "max_empty", "margin", "want_crop_counts", "d_blend", "d_blend_masks", "d_blend_sources",
-               "blend_feather", "blend_gain", "blend_min_overlap", "want_gains", "want_blend_counts")
-        args = {k_: v_ for k_, v_ in locals().items() if k_ not in own and k_ not in ("own", "occlusion", "occlusion_tol", "occlusion_search")}
-        arr = lambda a: _ptr_array(a) if a is not None else None
+        args = _stabilize_video_args()
         with _occlusion_search_for(self, occlusion_search, occlusion):
             out = self._stabilize_video("rsdsfm_stabilize_video_blended_dev",
-                                        (C.byref(fp), arr(d_sources), _p(counts), C.byref(cp), _window4(window_in), arr(d_crop), arr(d_crop_masks), arr(d_crop_sources),
-                                         window, _p(crop_counts), C.byref(bp), arr(d_blend), arr(d_blend_masks), arr(d_blend_sources), _p(gains), _p(blend_counts)),
+                                        (C.byref(fp), _ptrs(d_sources), _p(counts), C.byref(cp), _window4(window_in), _ptrs(d_crop), _ptrs(d_crop_masks), _ptrs(d_crop_sources),
+                                         window, _p(crop_counts), C.byref(bp), _ptrs(d_blend), _ptrs(d_blend_masks), _ptrs(d_blend_sources), _p(gains), _p(blend_counts)),
                                         **args)
         out["window"] = tuple(int(x) for x in window)
-        if want_counts:
-            out["counts"] = counts[:n]
-        if want_crop_counts:
-            out["crop_counts"] = crop_counts[:n]
+        out.update(_wanted(n, counts=counts, crop_counts=crop_counts, blend_counts=blend_counts))
         if want_gains:
             out["gains"] = gains[:n, :2 * int(fill_radius)]
-        if want_blend_counts:
-            out["blend_counts"] = blend_counts[:n]
         return out
-
-
-for _name, _fn in list(vars(_StabilizeBlendMixin).items()):
-    if not _name.startswith("__"):
-        setattr(Solver, _name, _fn)
 
 
 # ---------------------------------------------------------------------------------------------------
 # the stabiliser's inpainting: the pixels no frame saw, from an integer pull-push pyramid (include/rsdsfm_stabilize_inpaint.h)
 # ---------------------------------------------------------------------------------------------------
-STABILIZE_INPAINT_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "rsdsfm_stabilize_inpaint.h")
+STABILIZE_INPAINT_HEADER_PATH = _header_path("rsdsfm_stabilize_inpaint.h")
 INPAINT_SOURCE = 255  # RSDSFM_SOURCE_INPAINTED
 
 
 def stabilize_inpaint_declared_symbols():
     """Names of every function include/rsdsfm_stabilize_inpaint.h declares"""
-    import re
-
-    txt = open(STABILIZE_INPAINT_HEADER_PATH).read()
-    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    return sorted(set(re.findall(r"\b(rsdsfm_[a-z0-9_]+)\s*\(", txt)))
+    return _declared("rsdsfm_stabilize_inpaint.h")
 
 
 def inpaint_launches(rows, cols):
     """kernel launches of one inpaint_frame_dev call: 3 for a small frame, 8 at 1280 x 720 (rsdsfm_inpaint_launches; host only)"""
-    n = load_library().rsdsfm_inpaint_launches(C.c_int32(rows), C.c_int32(cols))
-    if n < 0:
-        raise RsdsfmError("rsdsfm_inpaint_launches failed (%d): rows and cols must be in [2, 16384]" % n)
-    return n
+    return _launches("rsdsfm_inpaint_launches", "rows and cols must be in [2, 16384]", rows, cols)
 
 
+@_solver_methods
 class _StabilizeInpaintMixin:
     def inpaint_frame_dev(self, d_image, d_mask, channels, rows, cols, d_source=None, d_count=None):
         """the empty pixels (d_mask byte 0; only read) of the device image filled from an integer pull-push pyramid of the set ones
@@ -2483,21 +2327,17 @@ class _StabilizeInpaintMixin:
     def inpaint(self, image, mask, device=0):
         """host convenience around inpaint_frame_dev: image (rows, cols) or (rows, cols, 3) uint8 and mask (rows, cols) uint8 (0 = empty) ->
         (image, source (rows, cols) uint8: INPAINT_SOURCE where a pixel was written and 0 elsewhere, count)"""
-        import torch
-
         img = np.ascontiguousarray(image, dtype=np.uint8)
         m = np.ascontiguousarray(mask, dtype=np.uint8)
         if img.shape[:2] != m.shape or m.ndim != 2:
             raise ValueError("image (rows, cols[, channels]) and mask (rows, cols)")
-        dev = torch.device("cuda", device)
-        with torch.cuda.device(dev):
-            d_img, d_m = torch.from_numpy(img).to(dev), torch.from_numpy(m).to(dev)
-            d_src, d_cnt = torch.zeros_like(d_m), torch.zeros(1, dtype=torch.int64, device=dev)
-            torch.cuda.synchronize()
+        with _Staging(self, device) as st:
+            d_img, d_m = st.up(img), st.up(m)
+            d_src, d_cnt = st.zeros_like(d_m), st.zeros(1, "int64")
+            st.ready()
             self.inpaint_frame_dev(d_img.data_ptr(), d_m.data_ptr(), 1 if img.ndim == 2 else img.shape[2], m.shape[0], m.shape[1], d_src.data_ptr(), d_cnt.data_ptr())
-            self.synchronize()
-            return d_img.cpu().numpy(), d_src.cpu().numpy(), int(d_cnt.cpu()[0])
-
+            out, src, cnt = st.down(d_img, d_src, d_cnt)
+            return out, src, int(cnt[0])
     def stabilize_video_inpainted_dev(self, d_frames, rows, cols, channels, K, gamma, d_depth_maps, d_flows, d_R, d_t, d_stab, d_masks_out, d_crop, d_crop_masks,
                                       d_blend, d_blend_masks, d_blend_sources, d_inpaint, d_inpaint_sources=None, want_inpaint_counts=True, blend_feather=None,
                                       blend_gain=True, blend_min_overlap=None, want_gains=True, want_blend_counts=True, d_crop_sources=None, window_in=None,
@@ -2523,55 +2363,34 @@ class _StabilizeInpaintMixin:
         cp = _stabilize_crop_params(max_empty, margin)
         bp = _stabilize_blend_params(blend_feather, blend_gain, blend_min_overlap)
         width = 2 + 2 * int(fill_radius)
-        counts = np.zeros((max(n, 1), width), dtype=np.int64) if want_counts else None
-        crop_counts = np.zeros((max(n, 1), width), dtype=np.int64) if want_crop_counts else None
-        gains = np.zeros((max(n, 1), max(2 * int(fill_radius), 1), 3), dtype=np.uint32) if want_gains else None
-        blend_counts = np.zeros((max(n, 1), 2 + 4 * int(fill_radius)), dtype=np.int64) if want_blend_counts else None
-        inpaint_counts = np.zeros(max(n, 1), dtype=np.int64) if want_inpaint_counts else None
+        counts = _counts(want_counts, n, width)
+        crop_counts = _counts(want_crop_counts, n, width)
+        gains = _counts(want_gains, n, max(2 * int(fill_radius), 1), 3, dtype=np.uint32)
+        blend_counts = _counts(want_blend_counts, n, 2 + 4 * int(fill_radius))
+        inpaint_counts = _counts(want_inpaint_counts, n)
         window = (C.c_int32 * 4)()
-        own = ("self", "n", "fp", "cp", "bp", "width", "counts", "crop_counts", "gains", "blend_counts", "inpaint_counts", "window", "d_sources", "fill_radius",
-               "want_counts", "d_crop", "d_crop_masks", "d_crop_sources", "window_in", "max_empty", "margin", "want_crop_counts", "d_blend", "d_blend_masks",
-               "d_blend_sources", "blend_feather", "blend_gain", "blend_min_overlap", "want_gains", "want_blend_counts", "d_inpaint", "d_inpaint_sources",
-               "want_inpaint_counts")
-        args = {k_: v_ for k_, v_ in locals().items() if k_ not in own and k_ not in ("own", "occlusion", "occlusion_tol", "occlusion_search")}
-        arr = lambda a: _ptr_array(a) if a is not None else None
+        args = _stabilize_video_args()
         with _occlusion_search_for(self, occlusion_search, occlusion):
             out = self._stabilize_video("rsdsfm_stabilize_video_inpainted_dev",
-                                        (C.byref(fp), arr(d_sources), _p(counts), C.byref(cp), _window4(window_in), arr(d_crop), arr(d_crop_masks), arr(d_crop_sources),
-                                         window, _p(crop_counts), C.byref(bp), arr(d_blend), arr(d_blend_masks), arr(d_blend_sources), _p(gains), _p(blend_counts),
-                                         arr(d_inpaint), arr(d_inpaint_sources), _p(inpaint_counts)), **args)
+                                        (C.byref(fp), _ptrs(d_sources), _p(counts), C.byref(cp), _window4(window_in), _ptrs(d_crop), _ptrs(d_crop_masks), _ptrs(d_crop_sources),
+                                         window, _p(crop_counts), C.byref(bp), _ptrs(d_blend), _ptrs(d_blend_masks), _ptrs(d_blend_sources), _p(gains), _p(blend_counts),
+                                         _ptrs(d_inpaint), _ptrs(d_inpaint_sources), _p(inpaint_counts)), **args)
         out["window"] = tuple(int(x) for x in window)
-        if want_counts:
-            out["counts"] = counts[:n]
-        if want_crop_counts:
-            out["crop_counts"] = crop_counts[:n]
+        out.update(_wanted(n, counts=counts, crop_counts=crop_counts, blend_counts=blend_counts, inpaint_counts=inpaint_counts))
         if want_gains:
             out["gains"] = gains[:n, :2 * int(fill_radius)]
-        if want_blend_counts:
-            out["blend_counts"] = blend_counts[:n]
-        if want_inpaint_counts:
-            out["inpaint_counts"] = inpaint_counts[:n]
         return out
-
-
-for _name, _fn in list(vars(_StabilizeInpaintMixin).items()):
-    if not _name.startswith("__"):
-        setattr(Solver, _name, _fn)
 
 
 # ---------------------------------------------------------------------------------------------------
 # the clip's last frame: the last pair's depth map moved onto it, and its pose table (include/rsdsfm_last_frame.h)
 # ---------------------------------------------------------------------------------------------------
-LAST_FRAME_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "rsdsfm_last_frame.h")
+LAST_FRAME_HEADER_PATH = _header_path("rsdsfm_last_frame.h")
 
 
 def last_frame_declared_symbols():
     """Names of every function include/rsdsfm_last_frame.h declares"""
-    import re
-
-    txt = open(LAST_FRAME_HEADER_PATH).read()
-    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    return sorted(set(re.findall(r"\b(rsdsfm_[a-z0-9_]+)\s*\(", txt)))
+    return _declared("rsdsfm_last_frame.h")
 
 
 def last_frame_motion(v, w, k):
@@ -2587,12 +2406,10 @@ def last_frame_motion(v, w, k):
 
 def advance_depth_launches(rows, cols):
     """kernel launches of one advance_depth_dev call: 3 (rsdsfm_advance_depth_launches; host only)"""
-    n = load_library().rsdsfm_advance_depth_launches(C.c_int32(rows), C.c_int32(cols))
-    if n < 0:
-        raise RsdsfmError("rsdsfm_advance_depth_launches failed (%d): rows and cols must be in [2, 16384]" % n)
-    return n
+    return _launches("rsdsfm_advance_depth_launches", "rows and cols must be in [2, 16384]", rows, cols)
 
 
+@_solver_methods
 class _LastFrameMixin:
     def advance_depth_dev(self, d_field, d_depth_map, v, w, k, rows, cols, K, gamma, d_out, global_shutter=False, d_plane=None, d_count=None):
         """a pair's depth map moved to its second capture, as a depth map of the second frame (rsdsfm_advance_depth_dev;
@@ -2600,50 +2417,41 @@ class _LastFrameMixin:
         the pair's final motion (host).  d_plane: a device plane of rows x cols uint64 that receives the winners' bit patterns; d_count: one
         device int64 that receives the number of pixels with a value.  Enqueued on the context's stream."""
         d = C.c_double
-        self._check(self.lib.rsdsfm_advance_depth_dev(self._ctx, _dp(d_field), _dp(d_depth_map), _v3(v), _v3(w), d(k), C.c_int32(rows), C.c_int32(cols), d(K[0]),
-                                                      d(K[1]), d(K[2]), d(K[3]), d(gamma), C.c_int32(int(bool(global_shutter))), _dp(d_out), _np0(d_plane),
+        self._check(self.lib.rsdsfm_advance_depth_dev(self._ctx, _dp(d_field), _dp(d_depth_map), _v3(v), _v3(w), d(k), C.c_int32(rows), C.c_int32(cols), *_k4(K), d(gamma),
+                                                      C.c_int32(int(bool(global_shutter))), _dp(d_out), _np0(d_plane),
                                                       _np0(d_count)), "rsdsfm_advance_depth_dev")
 
     def advance_depth(self, field, depth_map, v, w, k, K, gamma, global_shutter=False, want_plane=False, device=0):
         """host convenience around advance_depth_dev: field (rows, cols, 2), depth_map (rows, cols) (0 where unknown) -> (map (rows, cols),
         count[, plane (rows, cols) uint64])"""
-        import torch
-
         F, Z = _f64(field), _f64(depth_map)
         rows, cols = Z.shape
         if F.shape != (rows, cols, 2):
             raise ValueError("field (rows, cols, 2) and depth_map (rows, cols)")
-        dev = torch.device("cuda", device)
-        with torch.cuda.device(dev):
-            d_F, d_Z = torch.from_numpy(F).to(dev), torch.from_numpy(np.ascontiguousarray(Z.T)).to(dev)  # column-major rows x cols
-            d_out = torch.empty((cols, rows), dtype=torch.float64, device=dev)
-            d_plane = torch.empty((rows, cols), dtype=torch.int64, device=dev) if want_plane else None
-            d_cnt = torch.zeros(1, dtype=torch.int64, device=dev)
-            torch.cuda.synchronize()
+        with _Staging(self, device) as st:
+            d_F, d_Z = st.up(F), st.up(Z.T)  # column-major rows x cols
+            d_out = st.empty((cols, rows), "float64")
+            d_plane = st.empty((rows, cols), "int64") if want_plane else None
+            d_cnt = st.zeros(1, "int64")
+            st.ready()
             self.advance_depth_dev(d_F.data_ptr(), d_Z.data_ptr(), v, w, k, rows, cols, K, gamma, d_out.data_ptr(), global_shutter,
                                    d_plane.data_ptr() if want_plane else None, d_cnt.data_ptr())
-            self.synchronize()
-            out = (np.ascontiguousarray(d_out.cpu().numpy().T), int(d_cnt.cpu()[0]))
-            return out + (d_plane.cpu().numpy().view(np.uint64),) if want_plane else out
-
+            moved, cnt = st.down(d_out, d_cnt)
+            out = (np.ascontiguousarray(moved.T), int(cnt[0]))
+            return out + (st.host(d_plane).view(np.uint64),) if want_plane else out
     def last_frame_dev(self, d_field, d_depth_map, v, w, k, rows, cols, K, gamma, d_out, d_R, d_t, global_shutter=False, d_plane=None, d_count=None):
         """the last frame's depth map and pose table from the last pair (rsdsfm_last_frame_dev): advance_depth_dev, last_frame_motion and
         pose_table_dev of the moved motion into d_R (rows x 9) / d_t (rows x 3), one after another.  Enqueued on the context's stream."""
         d = C.c_double
-        self._check(self.lib.rsdsfm_last_frame_dev(self._ctx, _dp(d_field), _dp(d_depth_map), _v3(v), _v3(w), d(k), C.c_int32(rows), C.c_int32(cols), d(K[0]),
-                                                   d(K[1]), d(K[2]), d(K[3]), d(gamma), C.c_int32(int(bool(global_shutter))), _dp(d_out), _dp(d_R), _dp(d_t),
+        self._check(self.lib.rsdsfm_last_frame_dev(self._ctx, _dp(d_field), _dp(d_depth_map), _v3(v), _v3(w), d(k), C.c_int32(rows), C.c_int32(cols), *_k4(K), d(gamma),
+                                                   C.c_int32(int(bool(global_shutter))), _dp(d_out), _dp(d_R), _dp(d_t),
                                                    _np0(d_plane), _np0(d_count)), "rsdsfm_last_frame_dev")
-
-
-for _name, _fn in list(vars(_LastFrameMixin).items()):
-    if not _name.startswith("__"):
-        setattr(Solver, _name, _fn)
 
 
 # ---------------------------------------------------------------------------------------------------
 # the retimer: a frame at any instant along the camera path, from the two input frames next to it in time (include/rsdsfm_retime.h)
 # ---------------------------------------------------------------------------------------------------
-RETIME_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "rsdsfm_retime.h")
+RETIME_HEADER_PATH = _header_path("rsdsfm_retime.h")
 RETIME_NONE, RETIME_FROM_A, RETIME_FROM_B, RETIME_DISSOLVED, RETIME_CONFLICT_A, RETIME_CONFLICT_B = range(6)
 
 
@@ -2653,30 +2461,18 @@ class RetimeParams(C.Structure):
 
 def retime_declared_symbols():
     """Names of every function include/rsdsfm_retime.h declares"""
-    import re
-
-    txt = open(RETIME_HEADER_PATH).read()
-    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    return sorted(set(re.findall(r"\b(rsdsfm_[a-z0-9_]+)\s*\(", txt)))
+    return _declared("rsdsfm_retime.h")
 
 
 def retime_default_params():
     """the retimer's defaults as a dict: threshold = 24, occlusion = 0, occlusion_tol_q16 = 0 (rsdsfm_retime_params_init)"""
-    p = RetimeParams()
-    if load_library().rsdsfm_retime_params_init(C.byref(p)) != OK:
-        raise RsdsfmError("rsdsfm_retime_params_init failed")
+    p = _params(RetimeParams, "rsdsfm_retime_params_init")
     return dict(threshold=p.threshold, occlusion=p.occlusion, occlusion_tol_q16=p.occlusion_tol_q16)
 
 
 def _retime_params(threshold, occlusion, occlusion_tol_q16):
     """a RetimeParams with the given values over the defaults (threshold None: the default)"""
-    p = RetimeParams()
-    if load_library().rsdsfm_retime_params_init(C.byref(p)) != OK:
-        raise RsdsfmError("rsdsfm_retime_params_init failed")
-    if threshold is not None:
-        p.threshold = int(threshold)
-    p.occlusion, p.occlusion_tol_q16 = int(occlusion), int(occlusion_tol_q16)
-    return p
+    return _params(RetimeParams, "rsdsfm_retime_params_init", threshold=threshold, occlusion=occlusion, occlusion_tol_q16=occlusion_tol_q16)
 
 
 def path_at(A_path, c_path, t):
@@ -2722,10 +2518,7 @@ def retime_times(nsources, factor):
 
 def retime_launches(rows, cols, nsrc=2):
     """kernel launches of one retime_frame_dev call: nsrc stabilize_window_launches + 1 (rsdsfm_retime_launches; host only)"""
-    n = load_library().rsdsfm_retime_launches(C.c_int32(rows), C.c_int32(cols), C.c_int32(nsrc))
-    if n < 0:
-        raise RsdsfmError("rsdsfm_retime_launches failed (%d): rows and cols must be in [2, 16384], nsrc 1 or 2" % n)
-    return n
+    return _launches("rsdsfm_retime_launches", "rows and cols must be in [2, 16384], nsrc 1 or 2", rows, cols, nsrc)
 
 
 def retime_merge_launches():
@@ -2733,6 +2526,7 @@ def retime_merge_launches():
     return int(load_library().rsdsfm_retime_merge_launches())
 
 
+@_solver_methods
 class _RetimeMixin:
     def retime_merge_dev(self, d_image_a, d_mask_a, d_image_b, d_mask_b, channels, rows, cols, weight_q16, d_image, d_mask, d_source=None, d_counts5=None,
                          threshold=24):
@@ -2746,23 +2540,17 @@ class _RetimeMixin:
 
     def retime_merge(self, image_a, mask_a, image_b=None, mask_b=None, weight_q16=0, threshold=24, device=0):
         """host convenience around retime_merge_dev -> (image, mask, source (rows, cols) uint8, counts (5,) int64)"""
-        import torch
-
         ia, ma = np.ascontiguousarray(image_a, dtype=np.uint8), np.ascontiguousarray(mask_a, dtype=np.uint8)
         rows, cols = ma.shape
-        dev = torch.device("cuda", device)
-        with torch.cuda.device(dev):
-            up = lambda a: None if a is None else torch.from_numpy(np.ascontiguousarray(a, dtype=np.uint8)).to(dev)
-            d_ia, d_ma, d_ib, d_mb = up(ia), up(ma), up(image_b), up(mask_b)
-            d_out, d_mask, d_src = torch.empty_like(d_ia), torch.empty_like(d_ma), torch.empty_like(d_ma)
-            d_cnt = torch.zeros(5, dtype=torch.int64, device=dev)
-            torch.cuda.synchronize()
+        with _Staging(self, device) as st:
+            d_ia, d_ma, d_ib, d_mb = st.up(ia), st.up(ma), st.up(image_b, np.uint8), st.up(mask_b, np.uint8)
+            d_out, d_mask, d_src = st.empty_like(d_ia), st.empty_like(d_ma), st.empty_like(d_ma)
+            d_cnt = st.zeros(5, "int64")
+            st.ready()
             ptr = lambda x: None if x is None else x.data_ptr()
             self.retime_merge_dev(d_ia.data_ptr(), d_ma.data_ptr(), ptr(d_ib), ptr(d_mb), 1 if ia.ndim == 2 else ia.shape[2], rows, cols, int(weight_q16),
                                   d_out.data_ptr(), d_mask.data_ptr(), d_src.data_ptr(), d_cnt.data_ptr(), threshold=threshold)
-            self.synchronize()
-            return d_out.cpu().numpy(), d_mask.cpu().numpy(), d_src.cpu().numpy(), d_cnt.cpu().numpy()
-
+            return st.down(d_out, d_mask, d_src, d_cnt)
     def retime_frame_dev(self, d_images, channels, d_depth_maps, d_Rs, d_ts, K, rows, cols, M, m, weight_q16, d_image, d_mask, d_source=None, d_counts5=None,
                          window=None, threshold=None, occlusion=False, occlusion_tol_q16=0, mode=BACKPROJECT_RS, q5_mode=Q5_COMPAT, iterations=0, params=None):
         """one frame at one instant (rsdsfm_retime_frame_dev): d_images, d_depth_maps, d_Rs, d_ts are lists of one or two device pointers (the
@@ -2770,16 +2558,15 @@ class _RetimeMixin:
         context (stabilize_window_frame_dev; occlusion=True: stabilize_visible_frame_dev, or stabilize_search_frame_dev with
         set_occlusion_search(1)) and the layers are merged (retime_merge_dev) into d_image, d_mask, d_source, d_counts5.  window None: the full
         frame.  params: a RetimeParams passed as it is, instead of threshold / occlusion / occlusion_tol_q16.  Enqueued on the context's stream."""
-        d = C.c_double
         nsrc = len(d_images)
         Mh = None if M is None else _f64(M).reshape(-1)
         mh = None if m is None else _f64(m).reshape(-1)
         if (Mh is not None and Mh.size < 9 * min(nsrc, 2)) or (mh is not None and mh.size < 3 * min(nsrc, 2)) or min(len(d_depth_maps), len(d_Rs), len(d_ts)) < min(nsrc, 2):
             raise RsdsfmError("retime_frame_dev: every source needs an image, a depth map, a pose table and a pose (M, m)")
         p = params if params is not None else _retime_params(threshold, occlusion, occlusion_tol_q16)
-        arr = lambda a: _ptr_array(list(a)[:2]) if len(a) else None
-        self._check(self.lib.rsdsfm_retime_frame_dev(self._ctx, arr(d_images), C.c_int32(channels), arr(d_depth_maps), arr(d_Rs), arr(d_ts), d(K[0]), d(K[1]), d(K[2]),
-                                                     d(K[3]), C.c_int32(rows), C.c_int32(cols), int(mode), int(q5_mode), C.c_int32(iterations), C.c_int32(nsrc), _p(Mh),
+        self._check(self.lib.rsdsfm_retime_frame_dev(self._ctx, _ptrs(d_images, min(len(d_images), 2)), C.c_int32(channels), _ptrs(d_depth_maps, min(len(d_depth_maps), 2)),
+                                                     _ptrs(d_Rs, min(len(d_Rs), 2)), _ptrs(d_ts, min(len(d_ts),
+                                                     2)), *_k4(K), C.c_int32(rows), C.c_int32(cols), int(mode), int(q5_mode), C.c_int32(iterations), C.c_int32(nsrc), _p(Mh),
                                                      _p(mh), C.c_int32(weight_q16), C.byref(p), _window4(window), _dp(d_image), _dp(d_mask), _np0(d_source),
                                                      _np0(d_counts5)), "rsdsfm_retime_frame_dev")
 
@@ -2787,64 +2574,42 @@ class _RetimeMixin:
                q5_mode=Q5_COMPAT, iterations=0, device=0):
         """host convenience around retime_frame_dev: images, depth_maps (rows, cols), Rs, ts: lists of one or two sources' host arrays
         -> (image, mask, source (rows, cols) uint8, counts (5,) int64)"""
-        import torch
-
         imgs = [np.ascontiguousarray(i, dtype=np.uint8) for i in images]
         rows, cols = imgs[0].shape[:2]
-        dev = torch.device("cuda", device)
-        with torch.cuda.device(dev):
-            up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-            d_i = [up(i) for i in imgs]
-            d_dm = [up(np.asarray(z, dtype=np.float64).T) for z in depth_maps]
-            d_R, d_t = [up(_f64(np.asarray(R).reshape(rows, 9))) for R in Rs], [up(_f64(t)) for t in ts]
-            d_out, d_mask = torch.empty_like(d_i[0]), torch.empty((rows, cols), dtype=torch.uint8, device=dev)
-            d_src, d_cnt = torch.empty_like(d_mask), torch.zeros(5, dtype=torch.int64, device=dev)
-            torch.cuda.synchronize()
-            ptrs = lambda a: [x.data_ptr() for x in a]
-            self.retime_frame_dev(ptrs(d_i), 1 if imgs[0].ndim == 2 else imgs[0].shape[2], ptrs(d_dm), ptrs(d_R), ptrs(d_t), K, rows, cols, M, m, int(weight_q16),
+        with _Staging(self, device) as st:
+            d_i, d_dm, d_R, d_t = ([st.up(x) for x in xs] for xs in (imgs, [np.asarray(z, dtype=np.float64).T for z in depth_maps],
+                                                                     [_f64(np.asarray(R).reshape(rows, 9)) for R in Rs], [_f64(t) for t in ts]))
+            d_out, d_mask = st.empty_like(d_i[0]), st.empty((rows, cols))
+            d_src, d_cnt = st.empty_like(d_mask), st.zeros(5, "int64")
+            st.ready()
+            self.retime_frame_dev(st.ptrs(d_i), 1 if imgs[0].ndim == 2 else imgs[0].shape[2], st.ptrs(d_dm), st.ptrs(d_R), st.ptrs(d_t), K, rows, cols, M, m, int(weight_q16),
                                   d_out.data_ptr(), d_mask.data_ptr(), d_src.data_ptr(), d_cnt.data_ptr(), window=window, threshold=threshold, occlusion=occlusion,
                                   occlusion_tol_q16=occlusion_tol_q16, mode=mode, q5_mode=q5_mode, iterations=iterations)
-            self.synchronize()
-            return d_out.cpu().numpy(), d_mask.cpu().numpy(), d_src.cpu().numpy(), d_cnt.cpu().numpy()
-
+            return st.down(d_out, d_mask, d_src, d_cnt)
     def retime_video_dev(self, d_frames, rows, cols, channels, K, d_depth_maps, d_R, d_t, A, c, A_path, c_path, scales, times, d_out, d_out_masks, d_out_sources=None,
                          want_counts=True, window=None, threshold=None, occlusion=False, occlusion_tol_q16=0, mode=BACKPROJECT_RS, q5_mode=Q5_COMPAT, iterations=0):
         """a solved clip retimed (rsdsfm_retime_video_dev): d_depth_maps, d_R, d_t (their length is the number of sources; d_frames has at least
         as many) and the host arrays A, c, scales as a stabilise clip call left them, A_path, c_path the path to ride (its A_s, c_s, or A, c);
         for every t of `times` retime_poses and retime_frame_dev into d_out[i], d_out_masks[i], d_out_sources[i].  Returns dict(sources
         (ntimes, 2) int32, -1 for absent; weights (ntimes,) int32; with want_counts counts (ntimes, 5) int64 -- the call then waits)."""
-        ns, tm = len(d_depth_maps), _f64(times).reshape(-1)
+        ns, a, cc, ap, cp, sc = _clip_front("retime_video_dev", d_depth_maps, A, c, A_path, c_path, scales, d_frames=d_frames, d_R=d_R, d_t=d_t)
+        tm = _f64(times).reshape(-1)
         nt = tm.shape[0]
-        _need_all(ns, d_frames=d_frames, d_R=d_R, d_t=d_t)
         _need_all(nt, d_out=d_out, d_out_masks=d_out_masks, d_out_sources=d_out_sources)
-        a, cc, ap, cp = _f64(A).reshape(-1, 9), _f64(c).reshape(-1, 3), _f64(A_path).reshape(-1, 9), _f64(c_path).reshape(-1, 3)
-        sc = _f64(scales).reshape(-1)
-        if min(a.shape[0], cc.shape[0], ap.shape[0], cp.shape[0], sc.shape[0]) < ns:
-            raise RsdsfmError("retime_video_dev: every source needs a pose on both paths and a scale")
         p = _retime_params(threshold, occlusion, occlusion_tol_q16)
-        sources, weights = np.full((max(nt, 1), 2), -1, dtype=np.int32), np.zeros(max(nt, 1), dtype=np.int32)
-        counts = np.zeros((max(nt, 1), 5), dtype=np.int64) if want_counts else None
-        d = C.c_double
-        arr = lambda x, n: _ptr_array(list(x)[:n]) if x is not None and n else None
-        self._check(self.lib.rsdsfm_retime_video_dev(self._ctx, arr(d_frames, ns), C.c_int32(ns), C.c_int32(rows), C.c_int32(cols), C.c_int32(channels), d(K[0]), d(K[1]),
-                                                     d(K[2]), d(K[3]), arr(d_depth_maps, ns), arr(d_R, ns), arr(d_t, ns), _p(a), _p(cc), _p(ap), _p(cp), _p(sc), int(mode),
-                                                     int(q5_mode), C.c_int32(iterations), _p(tm), C.c_int32(nt), C.byref(p), _window4(window), arr(d_out, nt),
-                                                     arr(d_out_masks, nt), arr(d_out_sources, nt), _p(sources), _p(weights), _p(counts)), "rsdsfm_retime_video_dev")
-        out = dict(sources=sources[:nt], weights=weights[:nt])
-        if want_counts:
-            out["counts"] = counts[:nt]
-        return out
-
-
-for _name, _fn in list(vars(_RetimeMixin).items()):
-    if not _name.startswith("__"):
-        setattr(Solver, _name, _fn)
+        sources, weights = _counts(True, nt, 2, dtype=np.int32, fill=-1), _counts(True, nt, dtype=np.int32)
+        counts = _counts(want_counts, nt, 5)
+        self._check(self.lib.rsdsfm_retime_video_dev(self._ctx, _ptrs(d_frames, ns), C.c_int32(ns), C.c_int32(rows), C.c_int32(cols), C.c_int32(channels), *_k4(K),
+                                                     _ptrs(d_depth_maps, ns), _ptrs(d_R, ns), _ptrs(d_t, ns), _p(a), _p(cc), _p(ap), _p(cp), _p(sc), int(mode),
+                                                     int(q5_mode), C.c_int32(iterations), _p(tm), C.c_int32(nt), C.byref(p), _window4(window), _ptrs(d_out, nt),
+                                                     _ptrs(d_out_masks, nt), _ptrs(d_out_sources, nt), _p(sources), _p(weights), _p(counts)), "rsdsfm_retime_video_dev")
+        return _wanted(nt, sources=sources, weights=weights, counts=counts)
 
 
 # ---------------------------------------------------------------------------------------------------
 # the synthetic shutter: a frame exposed over a window of time, the mean of sub-instant renders (include/rsdsfm_shutter.h)
 # ---------------------------------------------------------------------------------------------------
-SHUTTER_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "rsdsfm_shutter.h")
+SHUTTER_HEADER_PATH = _header_path("rsdsfm_shutter.h")
 SHUTTER_SAMPLES_MAX = 64
 
 
@@ -2854,25 +2619,12 @@ class ShutterParams(C.Structure):
 
 def shutter_declared_symbols():
     """Names of every function include/rsdsfm_shutter.h declares"""
-    import re
-
-    txt = open(SHUTTER_HEADER_PATH).read()
-    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    return sorted(set(re.findall(r"\b(rsdsfm_[a-z0-9_]+)\s*\(", txt)))
+    return _declared("rsdsfm_shutter.h")
 
 
 def _shutter_params(shutter=None, samples=None, min_samples=None):
     """a ShutterParams with the given values over the defaults (None: the default)"""
-    p = ShutterParams()
-    if load_library().rsdsfm_shutter_params_init(C.byref(p)) != OK:
-        raise RsdsfmError("rsdsfm_shutter_params_init failed")
-    if shutter is not None:
-        p.shutter = float(shutter)
-    if samples is not None:
-        p.samples = int(samples)
-    if min_samples is not None:
-        p.min_samples = int(min_samples)
-    return p
+    return _params(ShutterParams, "rsdsfm_shutter_params_init", shutter=shutter, samples=samples, min_samples=min_samples)
 
 
 def shutter_default_params():
@@ -2901,10 +2653,7 @@ def shutter_from_angle(angle_deg, factor):
 def shutter_launches(rows, cols, n_one_source, n_two_sources):
     """kernel launches of one shutter_frame_dev call whose kept sub-instants are n_one_source integer instants and n_two_sources others: their
     retime_launches plus one accumulate each (rsdsfm_shutter_launches; host only)"""
-    n = load_library().rsdsfm_shutter_launches(C.c_int32(rows), C.c_int32(cols), C.c_int32(n_one_source), C.c_int32(n_two_sources))
-    if n < 0:
-        raise RsdsfmError("rsdsfm_shutter_launches failed (%d): rows and cols in [2, 16384], counts >= 0 with a sum in [1, 64]" % n)
-    return n
+    return _launches("rsdsfm_shutter_launches", "rows and cols in [2, 16384], counts >= 0 with a sum in [1, 64]", rows, cols, n_one_source, n_two_sources)
 
 
 def shutter_accumulate_launches():
@@ -2912,6 +2661,7 @@ def shutter_accumulate_launches():
     return int(load_library().rsdsfm_shutter_accumulate_launches())
 
 
+@_solver_methods
 class _ShutterMixin:
     def shutter_accumulate_dev(self, d_image, d_mask, channels, rows, cols, d_cells, first, last, nsamples, min_samples=1, d_image_out=None, d_mask_out=None,
                                d_coverage=None, d_counts3=None):
@@ -2926,35 +2676,20 @@ class _ShutterMixin:
     def shutter_accumulate(self, samples, min_samples=1, device=0):
         """host convenience around shutter_accumulate_dev: samples, a list of 1 .. 64 (image, mask) pairs of host arrays
         -> (image, mask, coverage (rows, cols) uint8, counts (3,) int64 [unset, partial, full])"""
-        import torch
-
         S = len(samples)
         first = np.ascontiguousarray(samples[0][0], dtype=np.uint8)
         rows, cols = first.shape[:2]
         ch = 1 if first.ndim == 2 else first.shape[2]
-        dev = torch.device("cuda", device)
-        with torch.cuda.device(dev):
-            up = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.uint8)).to(dev)
-            d_s = [(up(i), up(m)) for i, m in samples]
-            d_cells = torch.empty((rows, cols, ch + 1), dtype=torch.int16, device=dev)
-            d_out, d_mask = torch.empty_like(d_s[0][0]), torch.empty((rows, cols), dtype=torch.uint8, device=dev)
-            d_cov, d_cnt = torch.empty_like(d_mask), torch.zeros(3, dtype=torch.int64, device=dev)
-            torch.cuda.synchronize()
+        with _Staging(self, device) as st:
+            d_s = [(st.up(i, np.uint8), st.up(m, np.uint8)) for i, m in samples]
+            d_cells = st.empty((rows, cols, ch + 1), "int16")
+            d_out, d_mask = st.empty_like(d_s[0][0]), st.empty((rows, cols))
+            d_cov, d_cnt = st.empty_like(d_mask), st.zeros(3, "int64")
+            st.ready()
             for j, (d_i, d_m) in enumerate(d_s):
                 self.shutter_accumulate_dev(d_i.data_ptr(), d_m.data_ptr(), ch, rows, cols, d_cells.data_ptr(), j == 0, j == S - 1, S, min_samples, d_out.data_ptr(),
                                             d_mask.data_ptr(), d_cov.data_ptr(), d_cnt.data_ptr())
-            self.synchronize()
-            return d_out.cpu().numpy(), d_mask.cpu().numpy(), d_cov.cpu().numpy(), d_cnt.cpu().numpy()
-
-    def _shutter_clip(self, what, d_frames, d_depth_maps, d_R, d_t, A, c, A_path, c_path, scales):
-        ns = len(d_depth_maps)
-        _need_all(ns, d_frames=d_frames, d_R=d_R, d_t=d_t)
-        a, cc, ap, cp = _f64(A).reshape(-1, 9), _f64(c).reshape(-1, 3), _f64(A_path).reshape(-1, 9), _f64(c_path).reshape(-1, 3)
-        sc = _f64(scales).reshape(-1)
-        if min(a.shape[0], cc.shape[0], ap.shape[0], cp.shape[0], sc.shape[0]) < ns:
-            raise RsdsfmError("%s: every source needs a pose on both paths and a scale" % what)
-        return ns, a, cc, ap, cp, sc
-
+            return st.down(d_out, d_mask, d_cov, d_cnt)
     def shutter_frame_dev(self, d_frames, rows, cols, channels, K, d_depth_maps, d_R, d_t, A, c, A_path, c_path, scales, t, d_image, d_mask, d_coverage=None,
                           d_counts3=None, shutter=None, samples=None, min_samples=None, window=None, threshold=None, occlusion=False, occlusion_tol_q16=0,
                           mode=BACKPROJECT_RS, q5_mode=Q5_COMPAT, iterations=0, shutter_params=None, retime_params=None):
@@ -2962,14 +2697,13 @@ class _ShutterMixin:
         shutter_times(t, shutter, samples, len(d_depth_maps)) retime_poses, retime_frame_dev onto the context's sample planes and
         shutter_accumulate_dev, the mean into d_image, d_mask, d_coverage, d_counts3.  shutter, samples, min_samples None: the defaults (0.5, 8,
         1); shutter_params / retime_params: structs passed as they are instead.  Returns the kept count.  Enqueued on the context's stream."""
-        ns, a, cc, ap, cp, sc = self._shutter_clip("shutter_frame_dev", d_frames, d_depth_maps, d_R, d_t, A, c, A_path, c_path, scales)
+        ns, a, cc, ap, cp, sc = _clip_front("shutter_frame_dev", d_depth_maps, A, c, A_path, c_path, scales, d_frames=d_frames, d_R=d_R, d_t=d_t)
         sp = shutter_params if shutter_params is not None else _shutter_params(shutter, samples, min_samples)
         rp = retime_params if retime_params is not None else _retime_params(threshold, occlusion, occlusion_tol_q16)
         d = C.c_double
         kept = C.c_int32()
-        arr = lambda x: _ptr_array(list(x)[:ns]) if ns else None
-        self._check(self.lib.rsdsfm_shutter_frame_dev(self._ctx, arr(d_frames), C.c_int32(ns), C.c_int32(rows), C.c_int32(cols), C.c_int32(channels), d(K[0]), d(K[1]),
-                                                      d(K[2]), d(K[3]), arr(d_depth_maps), arr(d_R), arr(d_t), _p(a), _p(cc), _p(ap), _p(cp), _p(sc), int(mode),
+        self._check(self.lib.rsdsfm_shutter_frame_dev(self._ctx, _ptrs(d_frames, ns), C.c_int32(ns), C.c_int32(rows), C.c_int32(cols), C.c_int32(channels), *_k4(K),
+                                                      _ptrs(d_depth_maps, ns), _ptrs(d_R, ns), _ptrs(d_t, ns), _p(a), _p(cc), _p(ap), _p(cp), _p(sc), int(mode),
                                                       int(q5_mode), C.c_int32(iterations), d(t), C.byref(sp), C.byref(rp), _window4(window), _dp(d_image), _dp(d_mask),
                                                       _np0(d_coverage), _np0(d_counts3), C.byref(kept)), "rsdsfm_shutter_frame_dev")
         return int(kept.value)
@@ -2980,34 +2714,24 @@ class _ShutterMixin:
         """a solved clip exposed at every t of `times` (rsdsfm_shutter_video_dev): one shutter_frame_dev per instant into d_out[i],
         d_out_masks[i], d_out_coverage[i].  Returns dict(kept (ntimes,) int32; with want_counts counts (ntimes, 3) int64 [unset, partial, full]
         -- the call then waits)."""
-        ns, a, cc, ap, cp, sc = self._shutter_clip("shutter_video_dev", d_frames, d_depth_maps, d_R, d_t, A, c, A_path, c_path, scales)
+        ns, a, cc, ap, cp, sc = _clip_front("shutter_video_dev", d_depth_maps, A, c, A_path, c_path, scales, d_frames=d_frames, d_R=d_R, d_t=d_t)
         tm = _f64(times).reshape(-1)
         nt = tm.shape[0]
         _need_all(nt, d_out=d_out, d_out_masks=d_out_masks, d_out_coverage=d_out_coverage)
         sp, rp = _shutter_params(shutter, samples, min_samples), _retime_params(threshold, occlusion, occlusion_tol_q16)
-        kept = np.zeros(max(nt, 1), dtype=np.int32)
-        counts = np.zeros((max(nt, 1), 3), dtype=np.int64) if want_counts else None
-        d = C.c_double
-        arr = lambda x, n: _ptr_array(list(x)[:n]) if x is not None and n else None
-        self._check(self.lib.rsdsfm_shutter_video_dev(self._ctx, arr(d_frames, ns), C.c_int32(ns), C.c_int32(rows), C.c_int32(cols), C.c_int32(channels), d(K[0]), d(K[1]),
-                                                      d(K[2]), d(K[3]), arr(d_depth_maps, ns), arr(d_R, ns), arr(d_t, ns), _p(a), _p(cc), _p(ap), _p(cp), _p(sc), int(mode),
+        kept = _counts(True, nt, dtype=np.int32)
+        counts = _counts(want_counts, nt, 3)
+        self._check(self.lib.rsdsfm_shutter_video_dev(self._ctx, _ptrs(d_frames, ns), C.c_int32(ns), C.c_int32(rows), C.c_int32(cols), C.c_int32(channels), *_k4(K),
+                                                      _ptrs(d_depth_maps, ns), _ptrs(d_R, ns), _ptrs(d_t, ns), _p(a), _p(cc), _p(ap), _p(cp), _p(sc), int(mode),
                                                       int(q5_mode), C.c_int32(iterations), _p(tm), C.c_int32(nt), C.byref(sp), C.byref(rp), _window4(window),
-                                                      arr(d_out, nt), arr(d_out_masks, nt), arr(d_out_coverage, nt), _p(kept), _p(counts)), "rsdsfm_shutter_video_dev")
-        out = dict(kept=kept[:nt])
-        if want_counts:
-            out["counts"] = counts[:nt]
-        return out
-
-
-for _name, _fn in list(vars(_ShutterMixin).items()):
-    if not _name.startswith("__"):
-        setattr(Solver, _name, _fn)
+                                                      _ptrs(d_out, nt), _ptrs(d_out_masks, nt), _ptrs(d_out_coverage, nt), _p(kept), _p(counts)), "rsdsfm_shutter_video_dev")
+        return _wanted(nt, kept=kept, counts=counts)
 
 
 # ---------------------------------------------------------------------------------------------------
 # the temporal denoise: a frame averaged with its registered neighbours, patch-weighted (include/rsdsfm_denoise.h)
 # ---------------------------------------------------------------------------------------------------
-DENOISE_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "rsdsfm_denoise.h")
+DENOISE_HEADER_PATH = _header_path("rsdsfm_denoise.h")
 DENOISE_RADIUS_MAX = 7
 DENOISE_LAYERS_MAX = 14
 
@@ -3019,26 +2743,13 @@ class DenoiseParams(C.Structure):
 
 def denoise_declared_symbols():
     """Names of every function include/rsdsfm_denoise.h declares"""
-    import re
-
-    txt = open(DENOISE_HEADER_PATH).read()
-    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    return sorted(set(re.findall(r"\b(rsdsfm_[a-z0-9_]+)\s*\(", txt)))
+    return _declared("rsdsfm_denoise.h")
 
 
 def _denoise_params(radius=None, strength=None, gain=True, occlusion=False, occlusion_tol_q16=0, min_overlap=None):
     """a DenoiseParams with the given values over the defaults (None: the default)"""
-    p = DenoiseParams()
-    if load_library().rsdsfm_denoise_params_init(C.byref(p)) != OK:
-        raise RsdsfmError("rsdsfm_denoise_params_init failed")
-    if radius is not None:
-        p.radius = int(radius)
-    if strength is not None:
-        p.strength = int(strength)
-    if min_overlap is not None:
-        p.min_overlap = int(min_overlap)
-    p.gain_mode, p.occlusion, p.occlusion_tol_q16 = 0 if gain else 1, int(occlusion), int(occlusion_tol_q16)
-    return p
+    return _params(DenoiseParams, "rsdsfm_denoise_params_init", radius=radius, strength=strength, min_overlap=min_overlap, gain_mode=0 if gain else 1, occlusion=occlusion,
+                   occlusion_tol_q16=occlusion_tol_q16)
 
 
 def denoise_default_params():
@@ -3050,10 +2761,7 @@ def denoise_default_params():
 def denoise_launches(rows, cols, nsrc):
     """kernel launches of one denoise_frame_dev call on nsrc sources: nsrc stabilize_window_launches + 2 (nsrc - 1), or + 1 with one source
     (rsdsfm_denoise_launches; host only)"""
-    n = load_library().rsdsfm_denoise_launches(C.c_int32(rows), C.c_int32(cols), C.c_int32(nsrc))
-    if n < 0:
-        raise RsdsfmError("rsdsfm_denoise_launches failed (%d): rows and cols in [2, 16384], nsrc in [1, 15]" % n)
-    return n
+    return _launches("rsdsfm_denoise_launches", "rows and cols in [2, 16384], nsrc in [1, 15]", rows, cols, nsrc)
 
 
 def denoise_accumulate_launches():
@@ -3061,6 +2769,7 @@ def denoise_accumulate_launches():
     return int(load_library().rsdsfm_denoise_accumulate_launches())
 
 
+@_solver_methods
 class _DenoiseMixin:
     def seam_overlap_sums_dev(self, d_image, d_source, d_layer, d_layer_mask, channels, rows, cols, d_sums8):
         """the seam blend's record as a call of its own (rsdsfm_seam_overlap_sums_dev; tests/stabilize_blend_spec_numpy.py's overlap_sums):
@@ -3085,31 +2794,24 @@ class _DenoiseMixin:
         """host convenience around denoise_accumulate_dev: the reference (image, mask), layers a list of 0 .. 14 (image, mask) pairs of host
         arrays, records None or one 8-word record (or None) per layer
         -> (image, mask, weight (rows, cols) uint8, counts (3,) int64 [unset, own only, averaged])"""
-        import torch
-
         ref = np.ascontiguousarray(ref, dtype=np.uint8)
         rows, cols = ref.shape[:2]
         ch = 1 if ref.ndim == 2 else ref.shape[2]
-        dev = torch.device("cuda", device)
-        with torch.cuda.device(dev):
-            up = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.uint8)).to(dev)
-            d_ref, d_rm = up(ref), up(ref_mask)
-            d_l = [(up(i), up(m)) for i, m in layers]
-            d_rec = [None if records is None or records[j] is None else torch.from_numpy(np.ascontiguousarray(records[j], dtype=np.uint64).view(np.int64)).to(dev)
-                     for j in range(len(layers))]
-            d_cells = torch.empty((rows, cols, ch + 1), dtype=torch.int16, device=dev)
-            d_out, d_mask = torch.empty_like(d_ref), torch.empty((rows, cols), dtype=torch.uint8, device=dev)
-            d_w, d_cnt = torch.empty_like(d_mask), torch.zeros(3, dtype=torch.int64, device=dev)
-            torch.cuda.synchronize()
+        with _Staging(self, device) as st:
+            d_ref, d_rm = st.up(ref), st.up(ref_mask, np.uint8)
+            d_l = [(st.up(i, np.uint8), st.up(m, np.uint8)) for i, m in layers]
+            d_rec = [None if records is None or records[j] is None else st.up64(records[j]) for j in range(len(layers))]
+            d_cells = st.empty((rows, cols, ch + 1), "int16")
+            d_out, d_mask = st.empty_like(d_ref), st.empty((rows, cols))
+            d_w, d_cnt = st.empty_like(d_mask), st.zeros(3, "int64")
+            st.ready()
             outs = dict(d_image_out=d_out.data_ptr(), d_mask_out=d_mask.data_ptr(), d_weight=d_w.data_ptr(), d_counts3=d_cnt.data_ptr())
             if not d_l:
                 self.denoise_accumulate_dev(d_ref.data_ptr(), d_rm.data_ptr(), None, None, ch, rows, cols, None, True, True, None, min_overlap, gain_mode, strength, **outs)
             for j, (d_i, d_m) in enumerate(d_l):
                 self.denoise_accumulate_dev(d_ref.data_ptr(), d_rm.data_ptr(), d_i.data_ptr(), d_m.data_ptr(), ch, rows, cols, d_cells.data_ptr(), j == 0, j == len(d_l) - 1,
                                             d_rec[j].data_ptr() if d_rec[j] is not None else None, min_overlap, gain_mode, strength, **outs)
-            self.synchronize()
-            return d_out.cpu().numpy(), d_mask.cpu().numpy(), d_w.cpu().numpy(), d_cnt.cpu().numpy()
-
+            return st.down(d_out, d_mask, d_w, d_cnt)
     def denoise_frame_dev(self, d_images, channels, d_depth_maps, d_R, d_t, K, rows, cols, M, m, d_image, d_mask, d_weight=None, d_counts3=None, strength=None, gain=True,
                           min_overlap=None, window=None, occlusion=False, occlusion_tol_q16=0, mode=BACKPROJECT_RS, q5_mode=Q5_COMPAT, iterations=0, params=None):
         """one denoised frame (rsdsfm_denoise_frame_dev): d_images, d_depth_maps, d_R, d_t lists of 1 .. 15 device pointers, source 0 the own
@@ -3117,15 +2819,9 @@ class _DenoiseMixin:
         stabilize_window_frame_dev, every neighbour alone on the context's layer, seam_overlap_sums_dev and denoise_accumulate_dev per neighbour;
         the mean into d_image, d_mask, d_weight, d_counts3.  params: a DenoiseParams passed as it is instead of the keywords.  Enqueued on the
         context's stream."""
-        ns = len(d_images)
-        _need_all(ns, d_depth_maps=d_depth_maps, d_R=d_R, d_t=d_t)
-        Mm, mm = _f64(M).reshape(-1, 9), _f64(m).reshape(-1, 3)
-        if Mm.shape[0] < ns or mm.shape[0] < ns:
-            raise RsdsfmError("denoise_frame_dev: every source needs a pose (M, m)")
+        ns, Mm, mm = _frame_front("denoise_frame_dev", d_images, M, m, d_depth_maps=d_depth_maps, d_R=d_R, d_t=d_t)
         dp = params if params is not None else _denoise_params(None, strength, gain, occlusion, occlusion_tol_q16, min_overlap)
-        d = C.c_double
-        arr = lambda x: _ptr_array(list(x)[:ns]) if ns else None
-        self._check(self.lib.rsdsfm_denoise_frame_dev(self._ctx, arr(d_images), C.c_int32(channels), arr(d_depth_maps), arr(d_R), arr(d_t), d(K[0]), d(K[1]), d(K[2]), d(K[3]),
+        self._check(self.lib.rsdsfm_denoise_frame_dev(self._ctx, _ptrs(d_images, ns), C.c_int32(channels), _ptrs(d_depth_maps, ns), _ptrs(d_R, ns), _ptrs(d_t, ns), *_k4(K),
                                                       C.c_int32(rows), C.c_int32(cols), int(mode), int(q5_mode), C.c_int32(iterations), C.c_int32(ns), _p(Mm), _p(mm),
                                                       C.byref(dp), _window4(window), _dp(d_image), _dp(d_mask), _np0(d_weight), _np0(d_counts3)), "rsdsfm_denoise_frame_dev")
 
@@ -3136,41 +2832,27 @@ class _DenoiseMixin:
         retime_poses(t = q), the neighbours within `radius` (None: 2) by neighbour_poses on the same path, and denoise_frame_dev into d_out[q],
         d_out_masks[q], d_out_weights[q].  A_path = A, c_path = c denoises the rectified frames in place.  Returns dict(); with want_counts
         counts (nsources, 3) int64 [unset, own only, averaged] -- the call then waits."""
-        ns = len(d_depth_maps)
-        _need_all(ns, d_frames=d_frames, d_R=d_R, d_t=d_t, d_out=d_out, d_out_masks=d_out_masks, d_out_weights=d_out_weights)
-        a, cc, ap, cp = _f64(A).reshape(-1, 9), _f64(c).reshape(-1, 3), _f64(A_path).reshape(-1, 9), _f64(c_path).reshape(-1, 3)
-        sc = _f64(scales).reshape(-1)
-        if min(a.shape[0], cc.shape[0], ap.shape[0], cp.shape[0], sc.shape[0]) < ns:
-            raise RsdsfmError("denoise_video_dev: every source needs a pose on both paths and a scale")
+        ns, a, cc, ap, cp, sc = _clip_front("denoise_video_dev", d_depth_maps, A, c, A_path, c_path, scales, d_frames=d_frames, d_R=d_R, d_t=d_t, d_out=d_out,
+                d_out_masks=d_out_masks, d_out_weights=d_out_weights)
         dp = _denoise_params(radius, strength, gain, occlusion, occlusion_tol_q16, min_overlap)
-        counts = np.zeros((max(ns, 1), 3), dtype=np.int64) if want_counts else None
-        d = C.c_double
-        arr = lambda x: _ptr_array(list(x)[:ns]) if x is not None and ns else None
-        self._check(self.lib.rsdsfm_denoise_video_dev(self._ctx, arr(d_frames), C.c_int32(ns), C.c_int32(rows), C.c_int32(cols), C.c_int32(channels), d(K[0]), d(K[1]),
-                                                      d(K[2]), d(K[3]), arr(d_depth_maps), arr(d_R), arr(d_t), _p(a), _p(cc), _p(ap), _p(cp), _p(sc), int(mode), int(q5_mode),
-                                                      C.c_int32(iterations), C.byref(dp), _window4(window), arr(d_out), arr(d_out_masks), arr(d_out_weights), _p(counts)),
+        counts = _counts(want_counts, ns, 3)
+        self._check(self.lib.rsdsfm_denoise_video_dev(self._ctx, _ptrs(d_frames, ns), C.c_int32(ns), C.c_int32(rows), C.c_int32(cols), C.c_int32(channels), *_k4(K),
+                                                      _ptrs(d_depth_maps, ns), _ptrs(d_R, ns), _ptrs(d_t, ns), _p(a), _p(cc), _p(ap), _p(cp), _p(sc), int(mode), int(q5_mode),
+                                                      C.c_int32(iterations), C.byref(dp), _window4(window), _ptrs(d_out, ns), _ptrs(d_out_masks, ns), _ptrs(d_out_weights, ns), _p(counts)),
                     "rsdsfm_denoise_video_dev")
-        return dict(counts=counts[:ns]) if want_counts else dict()
-
-
-for _name, _fn in list(vars(_DenoiseMixin).items()):
-    if not _name.startswith("__"):
-        setattr(Solver, _name, _fn)
+        return _wanted(ns, counts=counts)
 
 
 # ---------------------------------------------------------------------------------------------------
 # the spatial top-up: a single-frame patch-weighted mean in proportion to what the temporal denoise did not give (include/rsdsfm_denoise_spatial.h)
 # ---------------------------------------------------------------------------------------------------
-DENOISE_SPATIAL_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "rsdsfm_denoise_spatial.h")
+DENOISE_SPATIAL_HEADER_PATH = _header_path("rsdsfm_denoise_spatial.h")
 DENOISE_SPATIAL_SEARCH_MAX = 3
 
 
 def denoise_spatial_declared_symbols():
     """Names of every function include/rsdsfm_denoise_spatial.h declares"""
-    import re
-
-    txt = re.sub(r"/\*.*?\*/", "", open(DENOISE_SPATIAL_HEADER_PATH).read(), flags=re.S)
-    return sorted(set(re.findall(r"\b(rsdsfm_[a-z0-9_]+)\s*\(", txt)))
+    return _declared("rsdsfm_denoise_spatial.h")
 
 
 class DenoiseSpatialParams(C.Structure):
@@ -3179,16 +2861,7 @@ class DenoiseSpatialParams(C.Structure):
 
 def _denoise_spatial_params(strength=None, target=None, search=None):
     """a DenoiseSpatialParams with the given values over the defaults (None: the default)"""
-    p = DenoiseSpatialParams()
-    if load_library().rsdsfm_denoise_spatial_params_init(C.byref(p)) != OK:
-        raise RsdsfmError("rsdsfm_denoise_spatial_params_init failed")
-    if strength is not None:
-        p.strength = int(strength)
-    if target is not None:
-        p.target = int(target)
-    if search is not None:
-        p.search = int(search)
-    return p
+    return _params(DenoiseSpatialParams, "rsdsfm_denoise_spatial_params_init", strength=strength, target=target, search=search)
 
 
 def denoise_spatial_default_params():
@@ -3204,12 +2877,10 @@ def denoise_spatial_launches():
 
 def denoise_spatial_frame_launches(rows, cols, nsrc):
     """kernel launches of one denoise_spatial_frame_dev call: denoise_launches + 1 (rsdsfm_denoise_spatial_frame_launches; host only)"""
-    n = load_library().rsdsfm_denoise_spatial_frame_launches(C.c_int32(rows), C.c_int32(cols), C.c_int32(nsrc))
-    if n < 0:
-        raise RsdsfmError("rsdsfm_denoise_spatial_frame_launches failed (%d): rows and cols in [2, 16384], nsrc in [1, 15]" % n)
-    return n
+    return _launches("rsdsfm_denoise_spatial_frame_launches", "rows and cols in [2, 16384], nsrc in [1, 15]", rows, cols, nsrc)
 
 
+@_solver_methods
 class _DenoiseSpatialMixin:
     def denoise_spatial_dev(self, d_image, d_mask, d_weight, channels, rows, cols, d_image_out, d_support=None, d_counts3=None, strength=0, target=0, search=0):
         """the spatial top-up (rsdsfm_denoise_spatial_dev; tests/denoise_spatial_spec_numpy.py): every set pixel whose weight n (d_weight; None: 16)
@@ -3223,24 +2894,16 @@ class _DenoiseSpatialMixin:
     def denoise_spatial(self, image, mask, weight=None, strength=0, target=0, search=0, device=0):
         """host convenience around denoise_spatial_dev: image (rows, cols[, 3]) uint8, mask and weight (or None) (rows, cols) uint8
         -> (image, support (rows, cols) uint8, counts (3,) int64 [unset, kept, smoothed])"""
-        import torch
-
         image = np.ascontiguousarray(image, dtype=np.uint8)
         rows, cols = image.shape[:2]
         ch = 1 if image.ndim == 2 else image.shape[2]
-        dev = torch.device("cuda", device)
-        with torch.cuda.device(dev):
-            up = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.uint8)).to(dev)
-            d_i, d_m = up(image), up(mask)
-            d_w = up(weight) if weight is not None else None
-            d_out, d_sup = torch.empty_like(d_i), torch.empty((rows, cols), dtype=torch.uint8, device=dev)
-            d_cnt = torch.zeros(3, dtype=torch.int64, device=dev)
-            torch.cuda.synchronize()
+        with _Staging(self, device) as st:
+            d_i, d_m, d_w = st.up(image), st.up(mask, np.uint8), st.up(weight, np.uint8)
+            d_out, d_sup, d_cnt = st.empty_like(d_i), st.empty((rows, cols)), st.zeros(3, "int64")
+            st.ready()
             self.denoise_spatial_dev(d_i.data_ptr(), d_m.data_ptr(), d_w.data_ptr() if d_w is not None else None, ch, rows, cols, d_out.data_ptr(), d_sup.data_ptr(),
                                      d_cnt.data_ptr(), strength, target, search)
-            self.synchronize()
-            return d_out.cpu().numpy(), d_sup.cpu().numpy(), d_cnt.cpu().numpy()
-
+            return st.down(d_out, d_sup, d_cnt)
     def denoise_spatial_frame_dev(self, d_images, channels, d_depth_maps, d_R, d_t, K, rows, cols, M, m, d_image, d_mask, d_weight=None, d_support=None, d_counts6=None,
                                   strength=None, gain=True, min_overlap=None, window=None, occlusion=False, occlusion_tol_q16=0, mode=BACKPROJECT_RS, q5_mode=Q5_COMPAT,
                                   iterations=0, params=None, spatial_strength=None, target=None, search=None, spatial_params=None):
@@ -3248,17 +2911,11 @@ class _DenoiseSpatialMixin:
         result stays in the context's workspace (its weight in d_weight when given, its mask in d_mask, its counters in d_counts6[0 .. 2]) and
         denoise_spatial_dev reads it into d_image, d_support and d_counts6[3 .. 5].  params / spatial_params: a DenoiseParams / DenoiseSpatialParams
         passed as it is instead of the keywords.  Enqueued on the context's stream."""
-        ns = len(d_images)
-        _need_all(ns, d_depth_maps=d_depth_maps, d_R=d_R, d_t=d_t)
-        Mm, mm = _f64(M).reshape(-1, 9), _f64(m).reshape(-1, 3)
-        if Mm.shape[0] < ns or mm.shape[0] < ns:
-            raise RsdsfmError("denoise_spatial_frame_dev: every source needs a pose (M, m)")
+        ns, Mm, mm = _frame_front("denoise_spatial_frame_dev", d_images, M, m, d_depth_maps=d_depth_maps, d_R=d_R, d_t=d_t)
         dp = params if params is not None else _denoise_params(None, strength, gain, occlusion, occlusion_tol_q16, min_overlap)
         sp = spatial_params if spatial_params is not None else _denoise_spatial_params(spatial_strength, target, search)
-        d = C.c_double
-        arr = lambda x: _ptr_array(list(x)[:ns]) if ns else None
-        self._check(self.lib.rsdsfm_denoise_spatial_frame_dev(self._ctx, arr(d_images), C.c_int32(channels), arr(d_depth_maps), arr(d_R), arr(d_t), d(K[0]), d(K[1]), d(K[2]),
-                                                              d(K[3]), C.c_int32(rows), C.c_int32(cols), int(mode), int(q5_mode), C.c_int32(iterations), C.c_int32(ns), _p(Mm),
+        self._check(self.lib.rsdsfm_denoise_spatial_frame_dev(self._ctx, _ptrs(d_images, ns), C.c_int32(channels), _ptrs(d_depth_maps, ns), _ptrs(d_R, ns), _ptrs(d_t, ns),
+                                                              *_k4(K), C.c_int32(rows), C.c_int32(cols), int(mode), int(q5_mode), C.c_int32(iterations), C.c_int32(ns), _p(Mm),
                                                               _p(mm), C.byref(dp), C.byref(sp), _window4(window), _dp(d_image), _dp(d_mask), _np0(d_weight), _np0(d_support),
                                                               _np0(d_counts6)), "rsdsfm_denoise_spatial_frame_dev")
 
@@ -3268,42 +2925,28 @@ class _DenoiseSpatialMixin:
         """a solved clip through the temporal denoise and the top-up (rsdsfm_denoise_spatial_video_dev): denoise_video_dev's clip and walk,
         denoise_spatial_frame_dev per frame into d_out[q], d_out_masks[q], d_out_weights[q], d_out_supports[q].  Returns dict(); with want_counts
         counts (nsources, 6) int64 [unset, own only, averaged, unset, kept, smoothed] -- the call then waits."""
-        ns = len(d_depth_maps)
-        _need_all(ns, d_frames=d_frames, d_R=d_R, d_t=d_t, d_out=d_out, d_out_masks=d_out_masks, d_out_weights=d_out_weights, d_out_supports=d_out_supports)
-        a, cc, ap, cp = _f64(A).reshape(-1, 9), _f64(c).reshape(-1, 3), _f64(A_path).reshape(-1, 9), _f64(c_path).reshape(-1, 3)
-        sc = _f64(scales).reshape(-1)
-        if min(a.shape[0], cc.shape[0], ap.shape[0], cp.shape[0], sc.shape[0]) < ns:
-            raise RsdsfmError("denoise_spatial_video_dev: every source needs a pose on both paths and a scale")
+        ns, a, cc, ap, cp, sc = _clip_front("denoise_spatial_video_dev", d_depth_maps, A, c, A_path, c_path, scales, d_frames=d_frames, d_R=d_R, d_t=d_t, d_out=d_out,
+                d_out_masks=d_out_masks, d_out_weights=d_out_weights, d_out_supports=d_out_supports)
         dp = _denoise_params(radius, strength, gain, occlusion, occlusion_tol_q16, min_overlap)
         sp = _denoise_spatial_params(spatial_strength, target, search)
-        counts = np.zeros((max(ns, 1), 6), dtype=np.int64) if want_counts else None
-        d = C.c_double
-        arr = lambda x: _ptr_array(list(x)[:ns]) if x is not None and ns else None
-        self._check(self.lib.rsdsfm_denoise_spatial_video_dev(self._ctx, arr(d_frames), C.c_int32(ns), C.c_int32(rows), C.c_int32(cols), C.c_int32(channels), d(K[0]), d(K[1]),
-                                                              d(K[2]), d(K[3]), arr(d_depth_maps), arr(d_R), arr(d_t), _p(a), _p(cc), _p(ap), _p(cp), _p(sc), int(mode),
-                                                              int(q5_mode), C.c_int32(iterations), C.byref(dp), C.byref(sp), _window4(window), arr(d_out), arr(d_out_masks),
-                                                              arr(d_out_weights), arr(d_out_supports), _p(counts)), "rsdsfm_denoise_spatial_video_dev")
-        return dict(counts=counts[:ns]) if want_counts else dict()
-
-
-for _name, _fn in list(vars(_DenoiseSpatialMixin).items()):
-    if not _name.startswith("__"):
-        setattr(Solver, _name, _fn)
+        counts = _counts(want_counts, ns, 6)
+        self._check(self.lib.rsdsfm_denoise_spatial_video_dev(self._ctx, _ptrs(d_frames, ns), C.c_int32(ns), C.c_int32(rows), C.c_int32(cols), C.c_int32(channels), *_k4(K),
+                                                              _ptrs(d_depth_maps, ns), _ptrs(d_R, ns), _ptrs(d_t, ns), _p(a), _p(cc), _p(ap), _p(cp), _p(sc), int(mode),
+                                                              int(q5_mode), C.c_int32(iterations), C.byref(dp), C.byref(sp), _window4(window), _ptrs(d_out, ns), _ptrs(d_out_masks, ns),
+                                                              _ptrs(d_out_weights, ns), _ptrs(d_out_supports, ns), _p(counts)), "rsdsfm_denoise_spatial_video_dev")
+        return _wanted(ns, counts=counts)
 
 
 # ---------------------------------------------------------------------------------------------------
 # the noise level: a frame's noise measured from the frame, and the two denoisers at the strength it asks for (include/rsdsfm_noise.h)
 # ---------------------------------------------------------------------------------------------------
-NOISE_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "rsdsfm_noise.h")
+NOISE_HEADER_PATH = _header_path("rsdsfm_noise.h")
 NOISE_BINS = 1024
 
 
 def noise_declared_symbols():
     """Names of every function include/rsdsfm_noise.h declares"""
-    import re
-
-    txt = re.sub(r"/\*.*?\*/", "", open(NOISE_HEADER_PATH).read(), flags=re.S)
-    return sorted(set(re.findall(r"\b(rsdsfm_[a-z0-9_]+)\s*\(", txt)))
+    return _declared("rsdsfm_noise.h")
 
 
 class NoiseParams(C.Structure):
@@ -3313,16 +2956,7 @@ class NoiseParams(C.Structure):
 
 def _noise_params(quantile_q8=None, scale=None, min_samples=None):
     """a NoiseParams with the given values over the defaults (None: the default)"""
-    p = NoiseParams()
-    if load_library().rsdsfm_noise_params_init(C.byref(p)) != OK:
-        raise RsdsfmError("rsdsfm_noise_params_init failed")
-    if quantile_q8 is not None:
-        p.quantile_q8 = int(quantile_q8)
-    if scale is not None:
-        p.scale = int(scale)
-    if min_samples is not None:
-        p.min_samples = int(min_samples)
-    return p
+    return _params(NoiseParams, "rsdsfm_noise_params_init", quantile_q8=quantile_q8, scale=scale, min_samples=min_samples)
 
 
 def noise_default_params():
@@ -3348,12 +2982,10 @@ def noise_strength(n, m, scale=0, fallback=0, min_samples=0):
 
 def denoise_auto_frame_launches(rows, cols, nsrc, with_spatial=False):
     """kernel launches of one denoise_auto_frame_dev call: denoise_launches + 2, + 1 with the top-up (rsdsfm_denoise_auto_frame_launches; host only)"""
-    n = load_library().rsdsfm_denoise_auto_frame_launches(C.c_int32(rows), C.c_int32(cols), C.c_int32(nsrc), C.c_int32(1 if with_spatial else 0))
-    if n < 0:
-        raise RsdsfmError("rsdsfm_denoise_auto_frame_launches failed (%d): rows and cols in [2, 16384], nsrc in [1, 15]" % n)
-    return n
+    return _launches("rsdsfm_denoise_auto_frame_launches", "rows and cols in [2, 16384], nsrc in [1, 15]", rows, cols, nsrc, 1 if with_spatial else 0)
 
 
+@_solver_methods
 class _NoiseMixin:
     def noise_level_dev(self, d_image, d_mask, channels, rows, cols, d_hist1024, d_record4, quantile_q8=0):
         """a frame's noise level (rsdsfm_noise_level_dev; tests/noise_spec_numpy.py): the histogram of |K * I| over the unclipped samples under
@@ -3365,21 +2997,17 @@ class _NoiseMixin:
     def noise_level(self, image, mask, quantile_q8=0, device=0):
         """host convenience around noise_level_dev: image (rows, cols[, 3]) uint8, mask (rows, cols) uint8
         -> dict(hist (1024,) uint32, record (4,) uint64 [n, m, sigma_q8, 0], sigma: the record's sigma in grey levels)"""
-        import torch
-
         image = np.ascontiguousarray(image, dtype=np.uint8)
         rows, cols = image.shape[:2]
         ch = 1 if image.ndim == 2 else image.shape[2]
-        dev = torch.device("cuda", device)
-        with torch.cuda.device(dev):
-            d_i, d_m = torch.from_numpy(image).to(dev), torch.from_numpy(np.ascontiguousarray(mask, dtype=np.uint8)).to(dev)
-            d_h, d_r = torch.empty(NOISE_BINS, dtype=torch.int32, device=dev), torch.empty(4, dtype=torch.int64, device=dev)
-            torch.cuda.synchronize()
+        with _Staging(self, device) as st:
+            d_i, d_m = st.up(image), st.up(mask, np.uint8)
+            d_h, d_r = st.empty(NOISE_BINS, "int32"), st.empty(4, "int64")
+            st.ready()
             self.noise_level_dev(d_i.data_ptr(), d_m.data_ptr(), ch, rows, cols, d_h.data_ptr(), d_r.data_ptr(), quantile_q8)
-            self.synchronize()
-            record = d_r.cpu().numpy().view(np.uint64)
-            return dict(hist=d_h.cpu().numpy().view(np.uint32), record=record, sigma=int(record[2]) / 256.0)
-
+            hist, record = st.down(d_h, d_r)
+            record = record.view(np.uint64)
+            return dict(hist=hist.view(np.uint32), record=record, sigma=int(record[2]) / 256.0)
     def denoise_accumulate_auto_dev(self, d_ref, d_ref_mask, d_layer, d_layer_mask, channels, rows, cols, d_cells, first, last, d_noise4, d_sums8=None, min_overlap=0,
                                     gain_mode=0, strength=0, scale=0, min_samples=0, d_image_out=None, d_mask_out=None, d_weight=None, d_counts3=None):
         """denoise_accumulate_dev at the strength the record d_noise4 (four device uint64, noise_level_dev's) asks for, formed on the device
@@ -3393,22 +3021,17 @@ class _NoiseMixin:
     def denoise_accumulate_auto(self, ref, ref_mask, layers, record4, records=None, min_overlap=0, gain_mode=0, strength=0, scale=0, min_samples=0, device=0):
         """host convenience around denoise_accumulate_auto_dev: denoise_accumulate's arguments with record4, a noise record (4,) uint64
         -> (image, mask, weight (rows, cols) uint8, counts (3,) int64 [unset, own only, averaged])"""
-        import torch
-
         ref = np.ascontiguousarray(ref, dtype=np.uint8)
         rows, cols = ref.shape[:2]
         ch = 1 if ref.ndim == 2 else ref.shape[2]
-        dev = torch.device("cuda", device)
-        with torch.cuda.device(dev):
-            up = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.uint8)).to(dev)
-            up64 = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.uint64).view(np.int64)).to(dev)
-            d_ref, d_rm, d_n = up(ref), up(ref_mask), up64(record4)
-            d_l = [(up(i), up(m)) for i, m in layers]
-            d_rec = [None if records is None or records[j] is None else up64(records[j]) for j in range(len(layers))]
-            d_cells = torch.empty((rows, cols, ch + 1), dtype=torch.int16, device=dev)
-            d_out, d_mask = torch.empty_like(d_ref), torch.empty((rows, cols), dtype=torch.uint8, device=dev)
-            d_w, d_cnt = torch.empty_like(d_mask), torch.zeros(3, dtype=torch.int64, device=dev)
-            torch.cuda.synchronize()
+        with _Staging(self, device) as st:
+            d_ref, d_rm, d_n = st.up(ref), st.up(ref_mask, np.uint8), st.up64(record4)
+            d_l = [(st.up(i, np.uint8), st.up(m, np.uint8)) for i, m in layers]
+            d_rec = [None if records is None or records[j] is None else st.up64(records[j]) for j in range(len(layers))]
+            d_cells = st.empty((rows, cols, ch + 1), "int16")
+            d_out, d_mask = st.empty_like(d_ref), st.empty((rows, cols))
+            d_w, d_cnt = st.empty_like(d_mask), st.zeros(3, "int64")
+            st.ready()
             kw = dict(min_overlap=min_overlap, gain_mode=gain_mode, strength=strength, scale=scale, min_samples=min_samples, d_image_out=d_out.data_ptr(),
                       d_mask_out=d_mask.data_ptr(), d_weight=d_w.data_ptr(), d_counts3=d_cnt.data_ptr())
             if not d_l:
@@ -3416,9 +3039,7 @@ class _NoiseMixin:
             for j, (d_i, d_m) in enumerate(d_l):
                 self.denoise_accumulate_auto_dev(d_ref.data_ptr(), d_rm.data_ptr(), d_i.data_ptr(), d_m.data_ptr(), ch, rows, cols, d_cells.data_ptr(), j == 0, j == len(d_l) - 1,
                                                  d_n.data_ptr(), d_rec[j].data_ptr() if d_rec[j] is not None else None, **kw)
-            self.synchronize()
-            return d_out.cpu().numpy(), d_mask.cpu().numpy(), d_w.cpu().numpy(), d_cnt.cpu().numpy()
-
+            return st.down(d_out, d_mask, d_w, d_cnt)
     def denoise_spatial_auto_dev(self, d_image, d_mask, d_weight, channels, rows, cols, d_noise4, d_image_out, d_support=None, d_counts3=None, strength=0, scale=0,
                                  min_samples=0, target=0, search=0):
         """denoise_spatial_dev at the strength the record d_noise4 asks for, formed on the device (rsdsfm_denoise_spatial_auto_dev): `strength` is
@@ -3430,25 +3051,16 @@ class _NoiseMixin:
     def denoise_spatial_auto(self, image, mask, record4, weight=None, strength=0, scale=0, min_samples=0, target=0, search=0, device=0):
         """host convenience around denoise_spatial_auto_dev: denoise_spatial's arguments with record4, a noise record (4,) uint64
         -> (image, support (rows, cols) uint8, counts (3,) int64 [unset, kept, smoothed])"""
-        import torch
-
         image = np.ascontiguousarray(image, dtype=np.uint8)
         rows, cols = image.shape[:2]
         ch = 1 if image.ndim == 2 else image.shape[2]
-        dev = torch.device("cuda", device)
-        with torch.cuda.device(dev):
-            up = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.uint8)).to(dev)
-            d_i, d_m = up(image), up(mask)
-            d_w = up(weight) if weight is not None else None
-            d_n = torch.from_numpy(np.ascontiguousarray(record4, dtype=np.uint64).view(np.int64)).to(dev)
-            d_out, d_sup = torch.empty_like(d_i), torch.empty((rows, cols), dtype=torch.uint8, device=dev)
-            d_cnt = torch.zeros(3, dtype=torch.int64, device=dev)
-            torch.cuda.synchronize()
+        with _Staging(self, device) as st:
+            d_i, d_m, d_w, d_n = st.up(image), st.up(mask, np.uint8), st.up(weight, np.uint8), st.up64(record4)
+            d_out, d_sup, d_cnt = st.empty_like(d_i), st.empty((rows, cols)), st.zeros(3, "int64")
+            st.ready()
             self.denoise_spatial_auto_dev(d_i.data_ptr(), d_m.data_ptr(), d_w.data_ptr() if d_w is not None else None, ch, rows, cols, d_n.data_ptr(), d_out.data_ptr(),
                                           d_sup.data_ptr(), d_cnt.data_ptr(), strength, scale, min_samples, target, search)
-            self.synchronize()
-            return d_out.cpu().numpy(), d_sup.cpu().numpy(), d_cnt.cpu().numpy()
-
+            return st.down(d_out, d_sup, d_cnt)
     def denoise_auto_frame_dev(self, d_images, channels, d_depth_maps, d_R, d_t, K, rows, cols, M, m, d_image, d_mask, d_weight=None, d_support=None, d_counts6=None,
                                d_noise4=None, strength=None, gain=True, min_overlap=None, window=None, occlusion=False, occlusion_tol_q16=0, mode=BACKPROJECT_RS,
                                q5_mode=Q5_COMPAT, iterations=0, params=None, quantile_q8=None, scale=None, min_samples=None, noise_params=None, spatial=False,
@@ -3457,19 +3069,13 @@ class _NoiseMixin:
         own frame is measured (noise_level_dev), every neighbour goes through denoise_accumulate_auto_dev, and with spatial (or spatial_params)
         denoise_spatial_auto_dev follows on the same record.  `strength` and `spatial_strength` are the fallbacks.  d_counts6: six device int64
         [unset, own only, averaged, unset, kept, smoothed]; d_noise4: four device uint64 for the record.  Enqueued on the context's stream."""
-        ns = len(d_images)
-        _need_all(ns, d_depth_maps=d_depth_maps, d_R=d_R, d_t=d_t)
-        Mm, mm = _f64(M).reshape(-1, 9), _f64(m).reshape(-1, 3)
-        if Mm.shape[0] < ns or mm.shape[0] < ns:
-            raise RsdsfmError("denoise_auto_frame_dev: every source needs a pose (M, m)")
+        ns, Mm, mm = _frame_front("denoise_auto_frame_dev", d_images, M, m, d_depth_maps=d_depth_maps, d_R=d_R, d_t=d_t)
         dp = params if params is not None else _denoise_params(None, strength, gain, occlusion, occlusion_tol_q16, min_overlap)
         npar = noise_params if noise_params is not None else _noise_params(quantile_q8, scale, min_samples)
         sp = spatial_params if spatial_params is not None else (_denoise_spatial_params(spatial_strength, target, search) if spatial else None)
-        d = C.c_double
-        arr = lambda x: _ptr_array(list(x)[:ns]) if ns else None
-        self._check(self.lib.rsdsfm_denoise_auto_frame_dev(self._ctx, arr(d_images), C.c_int32(channels), arr(d_depth_maps), arr(d_R), arr(d_t), d(K[0]), d(K[1]), d(K[2]),
-                                                           d(K[3]), C.c_int32(rows), C.c_int32(cols), int(mode), int(q5_mode), C.c_int32(iterations), C.c_int32(ns), _p(Mm),
-                                                           _p(mm), C.byref(dp), C.byref(npar), C.byref(sp) if sp is not None else None, _window4(window), _dp(d_image),
+        self._check(self.lib.rsdsfm_denoise_auto_frame_dev(self._ctx, _ptrs(d_images, ns), C.c_int32(channels), _ptrs(d_depth_maps, ns), _ptrs(d_R, ns), _ptrs(d_t, ns), *_k4(K),
+                                                           C.c_int32(rows), C.c_int32(cols), int(mode), int(q5_mode), C.c_int32(iterations), C.c_int32(ns), _p(Mm),
+                                                           _p(mm), C.byref(dp), C.byref(npar), _ref(sp), _window4(window), _dp(d_image),
                                                            _dp(d_mask), _np0(d_weight), _np0(d_support), _np0(d_counts6), _np0(d_noise4)), "rsdsfm_denoise_auto_frame_dev")
 
     def denoise_auto_video_dev(self, d_frames, rows, cols, channels, K, d_depth_maps, d_R, d_t, A, c, A_path, c_path, scales, d_out, d_out_masks, d_out_weights=None,
@@ -3479,41 +3085,25 @@ class _NoiseMixin:
         """a solved clip denoised at every frame's own strength (rsdsfm_denoise_auto_video_dev): denoise_video_dev's clip and walk,
         denoise_auto_frame_dev per frame.  Returns dict(); with want_counts counts (nsources, 6) int64, with want_noise noise (nsources, 4)
         uint64 [n, m, sigma_q8, 0] -- with either the call waits."""
-        ns = len(d_depth_maps)
-        _need_all(ns, d_frames=d_frames, d_R=d_R, d_t=d_t, d_out=d_out, d_out_masks=d_out_masks, d_out_weights=d_out_weights, d_out_supports=d_out_supports)
-        a, cc, ap, cp = _f64(A).reshape(-1, 9), _f64(c).reshape(-1, 3), _f64(A_path).reshape(-1, 9), _f64(c_path).reshape(-1, 3)
-        sc = _f64(scales).reshape(-1)
-        if min(a.shape[0], cc.shape[0], ap.shape[0], cp.shape[0], sc.shape[0]) < ns:
-            raise RsdsfmError("denoise_auto_video_dev: every source needs a pose on both paths and a scale")
+        ns, a, cc, ap, cp, sc = _clip_front("denoise_auto_video_dev", d_depth_maps, A, c, A_path, c_path, scales, d_frames=d_frames, d_R=d_R, d_t=d_t, d_out=d_out,
+                d_out_masks=d_out_masks, d_out_weights=d_out_weights, d_out_supports=d_out_supports)
         dp = _denoise_params(radius, strength, gain, occlusion, occlusion_tol_q16, min_overlap)
         npar = _noise_params(quantile_q8, scale, min_samples)
         sp = _denoise_spatial_params(spatial_strength, target, search) if spatial else None
-        counts = np.zeros((max(ns, 1), 6), dtype=np.int64) if want_counts else None
-        noise = np.zeros((max(ns, 1), 4), dtype=np.uint64) if want_noise else None
-        d = C.c_double
-        arr = lambda x: _ptr_array(list(x)[:ns]) if x is not None and ns else None
-        self._check(self.lib.rsdsfm_denoise_auto_video_dev(self._ctx, arr(d_frames), C.c_int32(ns), C.c_int32(rows), C.c_int32(cols), C.c_int32(channels), d(K[0]), d(K[1]),
-                                                           d(K[2]), d(K[3]), arr(d_depth_maps), arr(d_R), arr(d_t), _p(a), _p(cc), _p(ap), _p(cp), _p(sc), int(mode), int(q5_mode),
-                                                           C.c_int32(iterations), C.byref(dp), C.byref(npar), C.byref(sp) if sp is not None else None, _window4(window),
-                                                           arr(d_out), arr(d_out_masks), arr(d_out_weights), arr(d_out_supports), _p(counts), _p(noise)),
+        counts = _counts(want_counts, ns, 6)
+        noise = _counts(want_noise, ns, 4, dtype=np.uint64)
+        self._check(self.lib.rsdsfm_denoise_auto_video_dev(self._ctx, _ptrs(d_frames, ns), C.c_int32(ns), C.c_int32(rows), C.c_int32(cols), C.c_int32(channels), *_k4(K),
+                                                           _ptrs(d_depth_maps, ns), _ptrs(d_R, ns), _ptrs(d_t, ns), _p(a), _p(cc), _p(ap), _p(cp), _p(sc), int(mode), int(q5_mode),
+                                                           C.c_int32(iterations), C.byref(dp), C.byref(npar), _ref(sp), _window4(window),
+                                                           _ptrs(d_out, ns), _ptrs(d_out_masks, ns), _ptrs(d_out_weights, ns), _ptrs(d_out_supports, ns), _p(counts), _p(noise)),
                     "rsdsfm_denoise_auto_video_dev")
-        out = dict()
-        if want_counts:
-            out["counts"] = counts[:ns]
-        if want_noise:
-            out["noise"] = noise[:ns]
-        return out
-
-
-for _name, _fn in list(vars(_NoiseMixin).items()):
-    if not _name.startswith("__"):
-        setattr(Solver, _name, _fn)
+        return _wanted(ns, counts=counts, noise=noise)
 
 
 # ---------------------------------------------------------------------------------------------------
 # the multi-frame super-resolution: a frame on a grid S times finer, merged from its registered neighbours (include/rsdsfm_superres.h)
 # ---------------------------------------------------------------------------------------------------
-SUPERRES_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "rsdsfm_superres.h")
+SUPERRES_HEADER_PATH = _header_path("rsdsfm_superres.h")
 SUPERRES_SCALE_MAX = 4
 SUPERRES_RADIUS_MAX = 7
 SUPERRES_LAYERS_MAX = 14
@@ -3527,28 +3117,12 @@ class SuperresParams(C.Structure):
 
 def superres_declared_symbols():
     """Names of every function include/rsdsfm_superres.h declares"""
-    import re
-
-    txt = open(SUPERRES_HEADER_PATH).read()
-    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    return sorted(set(re.findall(r"\b(rsdsfm_[a-z0-9_]+)\s*\(", txt)))
+    return _declared("rsdsfm_superres.h")
 
 
 def _superres_params(scale=None, radius=None, strength=None, gain=True, min_overlap=None):
     """a SuperresParams with the given values over the defaults (None: the default)"""
-    p = SuperresParams()
-    if load_library().rsdsfm_superres_params_init(C.byref(p)) != OK:
-        raise RsdsfmError("rsdsfm_superres_params_init failed")
-    if scale is not None:
-        p.scale = int(scale)
-    if radius is not None:
-        p.radius = int(radius)
-    if strength is not None:
-        p.strength = int(strength)
-    if min_overlap is not None:
-        p.min_overlap = int(min_overlap)
-    p.gain_mode = 0 if gain else 1
-    return p
+    return _params(SuperresParams, "rsdsfm_superres_params_init", scale=scale, radius=radius, strength=strength, min_overlap=min_overlap, gain_mode=0 if gain else 1)
 
 
 def superres_default_params():
@@ -3560,10 +3134,7 @@ def superres_default_params():
 
 def superres_render_launches(rows, cols, scale):
     """kernel launches of one superres_render_dev call: stabilize_window_launches(rows, cols) (rsdsfm_superres_render_launches; host only)"""
-    n = load_library().rsdsfm_superres_render_launches(C.c_int32(rows), C.c_int32(cols), C.c_int32(scale))
-    if n < 0:
-        raise RsdsfmError("rsdsfm_superres_render_launches failed (%d): rows and cols in [2, 16384], scale in [1, 4], scale * size at most 16384" % n)
-    return n
+    return _launches("rsdsfm_superres_render_launches", "rows and cols in [2, 16384], scale in [1, 4], scale * size at most 16384", rows, cols, scale)
 
 
 def superres_accumulate_launches():
@@ -3574,12 +3145,10 @@ def superres_accumulate_launches():
 def superres_launches(rows, cols, scale, nsrc):
     """kernel launches of one superres_frame_dev call on nsrc sources of rows x cols: nsrc superres_render_launches + 2 (nsrc - 1), or + 1 with one
     source (rsdsfm_superres_launches; host only)"""
-    n = load_library().rsdsfm_superres_launches(C.c_int32(rows), C.c_int32(cols), C.c_int32(scale), C.c_int32(nsrc))
-    if n < 0:
-        raise RsdsfmError("rsdsfm_superres_launches failed (%d): rows and cols in [2, 16384], scale in [1, 4], scale * size at most 16384, nsrc in [1, 15]" % n)
-    return n
+    return _launches("rsdsfm_superres_launches", "rows and cols in [2, 16384], scale in [1, 4], scale * size at most 16384, nsrc in [1, 15]", rows, cols, scale, nsrc)
 
 
+@_solver_methods
 class _SuperresMixin:
     def superres_render_dev(self, d_image, channels, d_depth_map, d_R, d_t, K, rows, cols, M, m, scale, d_bil, d_near, d_prox, d_valid=None, window=None,
                             mode=BACKPROJECT_RS, q5_mode=Q5_COMPAT, iterations=0):
@@ -3587,34 +3156,26 @@ class _SuperresMixin:
         (scale rows x scale cols x channels) the bilinear and the nearest source sample of every fine pixel, d_prox (scale rows x scale cols) how
         near the nearest fell, 1 .. 16, 0 where the pixel is not valid; d_valid (optional) 1 where d_prox is not 0.  Every byte is written.
         Enqueued on the context's stream."""
-        d = C.c_double
-        self._check(self.lib.rsdsfm_superres_render_dev(self._ctx, _dp(d_image), C.c_int32(channels), _dp(d_depth_map), _dp(d_R), _dp(d_t), d(K[0]), d(K[1]), d(K[2]),
-                                                        d(K[3]), C.c_int32(rows), C.c_int32(cols), int(mode), int(q5_mode), C.c_int32(iterations), _p(_f64(M).reshape(-1)),
+        self._check(self.lib.rsdsfm_superres_render_dev(self._ctx, _dp(d_image), C.c_int32(channels), _dp(d_depth_map), _dp(d_R), _dp(d_t), *_k4(K), C.c_int32(rows),
+                                                        C.c_int32(cols), int(mode), int(q5_mode), C.c_int32(iterations), _p(_f64(M).reshape(-1)),
                                                         _p(_f64(m).reshape(-1)), C.c_int32(scale), _window4(window), _np0(d_bil), _np0(d_near), _np0(d_prox), _np0(d_valid)),
                     "rsdsfm_superres_render_dev")
 
     def superres_render(self, image, depth, R, t, K, M, m, scale=2, window=None, mode=BACKPROJECT_RS, q5_mode=Q5_COMPAT, iterations=0, device=0):
         """host convenience around superres_render_dev: image (rows, cols[, 3]) uint8, depth (rows, cols), R (rows, 9 or 3, 3), t (rows, 3)
         -> dict(bil, near, prox, valid) of host arrays on the fine grid"""
-        import torch
-
         image = np.ascontiguousarray(image, dtype=np.uint8)
         rows, cols = image.shape[:2]
         ch = 1 if image.ndim == 2 else image.shape[2]
-        dev = torch.device("cuda", device)
-        with torch.cuda.device(dev):
-            tt = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-            d_i, d_z = tt(image), tt(_f64(depth).T)
-            d_R, d_t = tt(_f64(R).reshape(-1, 9)), tt(_f64(t).reshape(-1, 3))
+        with _Staging(self, device) as st:
+            d_i, d_z, d_R, d_t = st.up_frame(image, depth, R, t)
             fine = (scale * rows, scale * cols)
-            d_b = torch.empty(fine + image.shape[2:], dtype=torch.uint8, device=dev)
-            d_n, d_q, d_v = torch.empty_like(d_b), torch.empty(fine, dtype=torch.uint8, device=dev), torch.empty(fine, dtype=torch.uint8, device=dev)
-            torch.cuda.synchronize()
+            d_b = st.empty(fine + image.shape[2:])
+            d_n, d_q, d_v = st.empty_like(d_b), st.empty(fine), st.empty(fine)
+            st.ready()
             self.superres_render_dev(d_i.data_ptr(), ch, d_z.data_ptr(), d_R.data_ptr(), d_t.data_ptr(), K, rows, cols, M, m, scale, d_b.data_ptr(), d_n.data_ptr(),
                                      d_q.data_ptr(), d_v.data_ptr(), window, mode, q5_mode, iterations)
-            self.synchronize()
-            return dict(bil=d_b.cpu().numpy(), near=d_n.cpu().numpy(), prox=d_q.cpu().numpy(), valid=d_v.cpu().numpy())
-
+            return dict(zip(("bil", "near", "prox", "valid"), st.down(d_b, d_n, d_q, d_v)))
     def superres_accumulate_dev(self, d_ref, d_ref_near, d_ref_prox, d_layer, d_layer_near, d_layer_prox, channels, rows, cols, d_cells, first, last, d_sums8=None,
                                 min_overlap=0, gain_mode=0, strength=0, d_image_out=None, d_mask_out=None, d_weight=None, d_counts3=None):
         """one layer accumulated onto the cells (rsdsfm_superres_accumulate_dev; tests/superres_spec_numpy.py) on FINE planes of rows x cols: the
@@ -3632,22 +3193,17 @@ class _SuperresMixin:
         """host convenience around superres_accumulate_dev: the reference's (bil, near, prox), layers a list of 0 .. 14 (bil, near, prox) triples of
         host arrays on the fine grid, records None or one 8-word record (or None) per layer
         -> (image, mask, weight (rows, cols) uint8, counts (3,) int64 [unset, own only, merged])"""
-        import torch
-
         ref = np.ascontiguousarray(ref, dtype=np.uint8)
         rows, cols = ref.shape[:2]
         ch = 1 if ref.ndim == 2 else ref.shape[2]
-        dev = torch.device("cuda", device)
-        with torch.cuda.device(dev):
-            up = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.uint8)).to(dev)
-            d_ref, d_rn, d_rq = up(ref), up(ref_near), up(ref_prox)
-            d_l = [(up(b), up(n), up(q)) for b, n, q in layers]
-            d_rec = [None if records is None or records[j] is None else torch.from_numpy(np.ascontiguousarray(records[j], dtype=np.uint64).view(np.int64)).to(dev)
-                     for j in range(len(layers))]
-            d_cells = torch.empty((rows, cols, ch + 1), dtype=torch.int16, device=dev)
-            d_out, d_mask = torch.empty_like(d_ref), torch.empty((rows, cols), dtype=torch.uint8, device=dev)
-            d_w, d_cnt = torch.empty_like(d_mask), torch.zeros(3, dtype=torch.int64, device=dev)
-            torch.cuda.synchronize()
+        with _Staging(self, device) as st:
+            d_ref, d_rn, d_rq = st.up(ref), st.up(ref_near, np.uint8), st.up(ref_prox, np.uint8)
+            d_l = [(st.up(b, np.uint8), st.up(n, np.uint8), st.up(q, np.uint8)) for b, n, q in layers]
+            d_rec = [None if records is None or records[j] is None else st.up64(records[j]) for j in range(len(layers))]
+            d_cells = st.empty((rows, cols, ch + 1), "int16")
+            d_out, d_mask = st.empty_like(d_ref), st.empty((rows, cols))
+            d_w, d_cnt = st.empty_like(d_mask), st.zeros(3, "int64")
+            st.ready()
             outs = dict(d_image_out=d_out.data_ptr(), d_mask_out=d_mask.data_ptr(), d_weight=d_w.data_ptr(), d_counts3=d_cnt.data_ptr())
             ref_ptrs = (d_ref.data_ptr(), d_rn.data_ptr(), d_rq.data_ptr())
             if not d_l:
@@ -3655,9 +3211,7 @@ class _SuperresMixin:
             for j, (d_b, d_n, d_q) in enumerate(d_l):
                 self.superres_accumulate_dev(*ref_ptrs, d_b.data_ptr(), d_n.data_ptr(), d_q.data_ptr(), ch, rows, cols, d_cells.data_ptr(), j == 0, j == len(d_l) - 1,
                                              d_rec[j].data_ptr() if d_rec[j] is not None else None, min_overlap, gain_mode, strength, **outs)
-            self.synchronize()
-            return d_out.cpu().numpy(), d_mask.cpu().numpy(), d_w.cpu().numpy(), d_cnt.cpu().numpy()
-
+            return st.down(d_out, d_mask, d_w, d_cnt)
     def superres_frame_dev(self, d_images, channels, d_depth_maps, d_R, d_t, K, rows, cols, M, m, d_image, d_mask, d_weight=None, d_counts3=None, scale=None, strength=None,
                            gain=True, min_overlap=None, window=None, mode=BACKPROJECT_RS, q5_mode=Q5_COMPAT, iterations=0, params=None):
         """one super-resolved frame (rsdsfm_superres_frame_dev): d_images, d_depth_maps, d_R, d_t lists of 1 .. 15 device pointers of rows x cols
@@ -3665,16 +3219,10 @@ class _SuperresMixin:
         Every source through superres_render_dev, per neighbour seam_overlap_sums_dev and superres_accumulate_dev; the merged frame into d_image
         (scale rows x scale cols x channels), d_mask, d_weight (scale rows x scale cols), d_counts3.  params: a SuperresParams passed as it is
         instead of the keywords.  Enqueued on the context's stream."""
-        ns = len(d_images)
-        _need_all(ns, d_depth_maps=d_depth_maps, d_R=d_R, d_t=d_t)
-        Mm, mm = _f64(M).reshape(-1, 9), _f64(m).reshape(-1, 3)
-        if Mm.shape[0] < ns or mm.shape[0] < ns:
-            raise RsdsfmError("superres_frame_dev: every source needs a pose (M, m)")
+        ns, Mm, mm = _frame_front("superres_frame_dev", d_images, M, m, d_depth_maps=d_depth_maps, d_R=d_R, d_t=d_t)
         sp = params if params is not None else _superres_params(scale, None, strength, gain, min_overlap)
-        d = C.c_double
-        arr = lambda x: _ptr_array(list(x)[:ns]) if ns else None
-        self._check(self.lib.rsdsfm_superres_frame_dev(self._ctx, arr(d_images), C.c_int32(channels), arr(d_depth_maps), arr(d_R), arr(d_t), d(K[0]), d(K[1]), d(K[2]),
-                                                       d(K[3]), C.c_int32(rows), C.c_int32(cols), int(mode), int(q5_mode), C.c_int32(iterations), C.c_int32(ns), _p(Mm), _p(mm),
+        self._check(self.lib.rsdsfm_superres_frame_dev(self._ctx, _ptrs(d_images, ns), C.c_int32(channels), _ptrs(d_depth_maps, ns), _ptrs(d_R, ns), _ptrs(d_t, ns), *_k4(K),
+                                                       C.c_int32(rows), C.c_int32(cols), int(mode), int(q5_mode), C.c_int32(iterations), C.c_int32(ns), _p(Mm), _p(mm),
                                                        C.byref(sp), _window4(window), _dp(d_image), _dp(d_mask), _np0(d_weight), _np0(d_counts3)), "rsdsfm_superres_frame_dev")
 
     def superres_video_dev(self, d_frames, rows, cols, channels, K, d_depth_maps, d_R, d_t, A, c, A_path, c_path, scales, d_out, d_out_masks, d_out_weights=None,
@@ -3684,32 +3232,21 @@ class _SuperresMixin:
         own pose by retime_poses(t = q), the neighbours within `radius` (None: 2) by neighbour_poses on the same path, and superres_frame_dev
         into d_out[q], d_out_masks[q], d_out_weights[q] (planes `scale` (None: 2) times finer than the frames).  Returns dict(); with want_counts
         counts (nsources, 3) int64 [unset, own only, merged] -- the call then waits."""
-        ns = len(d_depth_maps)
-        _need_all(ns, d_frames=d_frames, d_R=d_R, d_t=d_t, d_out=d_out, d_out_masks=d_out_masks, d_out_weights=d_out_weights)
-        a, cc, ap, cp = _f64(A).reshape(-1, 9), _f64(c).reshape(-1, 3), _f64(A_path).reshape(-1, 9), _f64(c_path).reshape(-1, 3)
-        sc = _f64(scales).reshape(-1)
-        if min(a.shape[0], cc.shape[0], ap.shape[0], cp.shape[0], sc.shape[0]) < ns:
-            raise RsdsfmError("superres_video_dev: every source needs a pose on both paths and a scale")
+        ns, a, cc, ap, cp, sc = _clip_front("superres_video_dev", d_depth_maps, A, c, A_path, c_path, scales, d_frames=d_frames, d_R=d_R, d_t=d_t, d_out=d_out,
+                d_out_masks=d_out_masks, d_out_weights=d_out_weights)
         sp = _superres_params(scale, radius, strength, gain, min_overlap)
-        counts = np.zeros((max(ns, 1), 3), dtype=np.int64) if want_counts else None
-        d = C.c_double
-        arr = lambda x: _ptr_array(list(x)[:ns]) if x is not None and ns else None
-        self._check(self.lib.rsdsfm_superres_video_dev(self._ctx, arr(d_frames), C.c_int32(ns), C.c_int32(rows), C.c_int32(cols), C.c_int32(channels), d(K[0]), d(K[1]),
-                                                       d(K[2]), d(K[3]), arr(d_depth_maps), arr(d_R), arr(d_t), _p(a), _p(cc), _p(ap), _p(cp), _p(sc), int(mode), int(q5_mode),
-                                                       C.c_int32(iterations), C.byref(sp), _window4(window), arr(d_out), arr(d_out_masks), arr(d_out_weights), _p(counts)),
+        counts = _counts(want_counts, ns, 3)
+        self._check(self.lib.rsdsfm_superres_video_dev(self._ctx, _ptrs(d_frames, ns), C.c_int32(ns), C.c_int32(rows), C.c_int32(cols), C.c_int32(channels), *_k4(K),
+                                                       _ptrs(d_depth_maps, ns), _ptrs(d_R, ns), _ptrs(d_t, ns), _p(a), _p(cc), _p(ap), _p(cp), _p(sc), int(mode), int(q5_mode),
+                                                       C.c_int32(iterations), C.byref(sp), _window4(window), _ptrs(d_out, ns), _ptrs(d_out_masks, ns), _ptrs(d_out_weights, ns), _p(counts)),
                     "rsdsfm_superres_video_dev")
-        return dict(counts=counts[:ns]) if want_counts else dict()
-
-
-for _name, _fn in list(vars(_SuperresMixin).items()):
-    if not _name.startswith("__"):
-        setattr(Solver, _name, _fn)
+        return _wanted(ns, counts=counts)
 
 
 # ---------------------------------------------------------------------------------------------------
 # the clean plate: the per-pixel median of a frame and its registered neighbours, and a moving flag (include/rsdsfm_plate.h)
 # ---------------------------------------------------------------------------------------------------
-PLATE_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "rsdsfm_plate.h")
+PLATE_HEADER_PATH = _header_path("rsdsfm_plate.h")
 PLATE_RADIUS_MAX = 7
 PLATE_LAYERS_MAX = 14
 PLATE_UNSET, PLATE_STATIC, PLATE_MOVING, PLATE_UNDECIDED = 0, 1, 2, 3  # the flag plane's bytes and the counters' order
@@ -3722,28 +3259,13 @@ class PlateParams(C.Structure):
 
 def plate_declared_symbols():
     """Names of every function include/rsdsfm_plate.h declares"""
-    import re
-
-    txt = open(PLATE_HEADER_PATH).read()
-    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    return sorted(set(re.findall(r"\b(rsdsfm_[a-z0-9_]+)\s*\(", txt)))
+    return _declared("rsdsfm_plate.h")
 
 
 def _plate_params(radius=None, threshold=None, min_votes=None, gain=True, occlusion=False, occlusion_tol_q16=0, min_overlap=None):
     """a PlateParams with the given values over the defaults (None: the default)"""
-    p = PlateParams()
-    if load_library().rsdsfm_plate_params_init(C.byref(p)) != OK:
-        raise RsdsfmError("rsdsfm_plate_params_init failed")
-    if radius is not None:
-        p.radius = int(radius)
-    if threshold is not None:
-        p.threshold = int(threshold)
-    if min_votes is not None:
-        p.min_votes = int(min_votes)
-    if min_overlap is not None:
-        p.min_overlap = int(min_overlap)
-    p.gain_mode, p.occlusion, p.occlusion_tol_q16 = 0 if gain else 1, int(occlusion), int(occlusion_tol_q16)
-    return p
+    return _params(PlateParams, "rsdsfm_plate_params_init", radius=radius, threshold=threshold, min_votes=min_votes, min_overlap=min_overlap, gain_mode=0 if gain else 1,
+                   occlusion=occlusion, occlusion_tol_q16=occlusion_tol_q16)
 
 
 def plate_default_params():
@@ -3756,10 +3278,7 @@ def plate_default_params():
 def plate_launches(rows, cols, nsrc):
     """kernel launches of one plate_frame_dev call on nsrc sources: nsrc stabilize_window_launches + (nsrc - 1) + 1 (rsdsfm_plate_launches; host
     only)"""
-    n = load_library().rsdsfm_plate_launches(C.c_int32(rows), C.c_int32(cols), C.c_int32(nsrc))
-    if n < 0:
-        raise RsdsfmError("rsdsfm_plate_launches failed (%d): rows and cols in [2, 16384], nsrc in [1, 15]" % n)
-    return n
+    return _launches("rsdsfm_plate_launches", "rows and cols in [2, 16384], nsrc in [1, 15]", rows, cols, nsrc)
 
 
 def plate_median_launches():
@@ -3767,6 +3286,7 @@ def plate_median_launches():
     return int(load_library().rsdsfm_plate_median_launches())
 
 
+@_solver_methods
 class _PlateMixin:
     def plate_median_dev(self, d_ref, d_ref_mask, d_layers, d_layer_masks, channels, rows, cols, d_image_out, d_mask_out, d_votes=None, d_moving=None, d_counts4=None,
                          d_sums8=None, min_overlap=0, gain_mode=0, threshold=0, min_votes=0, nlayers=None):
@@ -3782,8 +3302,7 @@ class _PlateMixin:
                              min_overlap, gain_mode, threshold, min_votes, nlayers):
         """rsdsfm_plate_median_dev or rsdsfm_plate_medoid_dev: one signature"""
         n = (len(d_layers) if d_layers is not None else 0) if nlayers is None else int(nlayers)
-        arr = lambda x: _ptr_array(list(x)) if x is not None and len(x) else None
-        self._check(getattr(self.lib, name)(self._ctx, _dp(d_ref), _dp(d_ref_mask), arr(d_layers), arr(d_layer_masks), C.c_int32(n), C.c_int32(channels), C.c_int32(rows),
+        self._check(getattr(self.lib, name)(self._ctx, _dp(d_ref), _dp(d_ref_mask), _ptrs(d_layers or None), _ptrs(d_layer_masks or None), C.c_int32(n), C.c_int32(channels), C.c_int32(rows),
                                             C.c_int32(cols), _np0(d_sums8), C.c_int64(min_overlap), C.c_int32(gain_mode), C.c_int32(threshold), C.c_int32(min_votes),
                                             _np0(d_image_out), _np0(d_mask_out), _np0(d_votes), _np0(d_moving), _np0(d_counts4)), name)
 
@@ -3795,27 +3314,21 @@ class _PlateMixin:
 
     def _plate_estimator(self, call_dev, ref, ref_mask, layers, records, min_overlap, gain_mode, threshold, min_votes, device):
         """plate_median's and plate_medoid's upload, call and download"""
-        import torch
-
         ref = np.ascontiguousarray(ref, dtype=np.uint8)
         rows, cols = ref.shape[:2]
         ch = 1 if ref.ndim == 2 else ref.shape[2]
-        dev = torch.device("cuda", device)
-        with torch.cuda.device(dev):
-            up = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.uint8)).to(dev)
-            d_ref, d_rm = up(ref), up(ref_mask)
-            d_l = [(up(i), up(m)) for i, m in layers]
+        with _Staging(self, device) as st:
+            d_ref, d_rm = st.up(ref), st.up(ref_mask, np.uint8)
+            d_l = [(st.up(i, np.uint8), st.up(m, np.uint8)) for i, m in layers]
             d_rec = None
             if records is not None and len(layers):
-                d_rec = torch.from_numpy(np.ascontiguousarray(records, dtype=np.uint64).reshape(len(layers), 8).view(np.int64)).to(dev)
-            d_out, d_mask = torch.empty_like(d_ref), torch.empty((rows, cols), dtype=torch.uint8, device=dev)
-            d_v, d_f, d_cnt = torch.empty_like(d_mask), torch.empty_like(d_mask), torch.zeros(4, dtype=torch.int64, device=dev)
-            torch.cuda.synchronize()
+                d_rec = st.up64(np.ascontiguousarray(records, dtype=np.uint64).reshape(len(layers), 8))
+            d_out, d_mask = st.empty_like(d_ref), st.empty((rows, cols))
+            d_v, d_f, d_cnt = st.empty_like(d_mask), st.empty_like(d_mask), st.zeros(4, "int64")
+            st.ready()
             call_dev(d_ref.data_ptr(), d_rm.data_ptr(), [i.data_ptr() for i, _ in d_l], [m.data_ptr() for _, m in d_l], ch, rows, cols, d_out.data_ptr(), d_mask.data_ptr(),
                      d_v.data_ptr(), d_f.data_ptr(), d_cnt.data_ptr(), d_rec.data_ptr() if d_rec is not None else None, min_overlap, gain_mode, threshold, min_votes)
-            self.synchronize()
-            return d_out.cpu().numpy(), d_mask.cpu().numpy(), d_v.cpu().numpy(), d_f.cpu().numpy(), d_cnt.cpu().numpy()
-
+            return st.down(d_out, d_mask, d_v, d_f, d_cnt)
     def plate_frame_dev(self, d_images, channels, d_depth_maps, d_R, d_t, K, rows, cols, M, m, d_image, d_mask, d_votes=None, d_moving=None, d_counts4=None, threshold=None,
                         min_votes=None, gain=True, min_overlap=None, window=None, occlusion=False, occlusion_tol_q16=0, mode=BACKPROJECT_RS, q5_mode=Q5_COMPAT, iterations=0,
                         params=None):
@@ -3824,15 +3337,9 @@ class _PlateMixin:
         stabilize_window_frame_dev, every neighbour alone on its own layer of the context's stack with its record by seam_overlap_sums_dev, one
         plate_median_dev into d_image, d_mask, d_votes, d_moving, d_counts4.  params: a PlateParams passed as it is instead of the keywords.
         Enqueued on the context's stream."""
-        ns = len(d_images)
-        _need_all(ns, d_depth_maps=d_depth_maps, d_R=d_R, d_t=d_t)
-        Mm, mm = _f64(M).reshape(-1, 9), _f64(m).reshape(-1, 3)
-        if Mm.shape[0] < ns or mm.shape[0] < ns:
-            raise RsdsfmError("plate_frame_dev: every source needs a pose (M, m)")
+        ns, Mm, mm = _frame_front("plate_frame_dev", d_images, M, m, d_depth_maps=d_depth_maps, d_R=d_R, d_t=d_t)
         pp = params if params is not None else _plate_params(None, threshold, min_votes, gain, occlusion, occlusion_tol_q16, min_overlap)
-        d = C.c_double
-        arr = lambda x: _ptr_array(list(x)[:ns]) if ns else None
-        self._check(self.lib.rsdsfm_plate_frame_dev(self._ctx, arr(d_images), C.c_int32(channels), arr(d_depth_maps), arr(d_R), arr(d_t), d(K[0]), d(K[1]), d(K[2]), d(K[3]),
+        self._check(self.lib.rsdsfm_plate_frame_dev(self._ctx, _ptrs(d_images, ns), C.c_int32(channels), _ptrs(d_depth_maps, ns), _ptrs(d_R, ns), _ptrs(d_t, ns), *_k4(K),
                                                     C.c_int32(rows), C.c_int32(cols), int(mode), int(q5_mode), C.c_int32(iterations), C.c_int32(ns), _p(Mm), _p(mm),
                                                     C.byref(pp), _window4(window), _dp(d_image), _dp(d_mask), _np0(d_votes), _np0(d_moving), _np0(d_counts4)),
                     "rsdsfm_plate_frame_dev")
@@ -3844,43 +3351,29 @@ class _PlateMixin:
         by retime_poses(t = q), the neighbours within `radius` (None: 2) by neighbour_poses on the same path, and plate_frame_dev into d_out[q],
         d_out_masks[q], d_out_votes[q], d_out_moving[q].  Returns dict(); with want_counts counts (nsources, 4) int64 [unset, static, moving,
         undecided] -- the call then waits."""
-        ns = len(d_depth_maps)
-        _need_all(ns, d_frames=d_frames, d_R=d_R, d_t=d_t, d_out=d_out, d_out_masks=d_out_masks, d_out_votes=d_out_votes, d_out_moving=d_out_moving)
-        a, cc, ap, cp = _f64(A).reshape(-1, 9), _f64(c).reshape(-1, 3), _f64(A_path).reshape(-1, 9), _f64(c_path).reshape(-1, 3)
-        sc = _f64(scales).reshape(-1)
-        if min(a.shape[0], cc.shape[0], ap.shape[0], cp.shape[0], sc.shape[0]) < ns:
-            raise RsdsfmError("plate_video_dev: every source needs a pose on both paths and a scale")
+        ns, a, cc, ap, cp, sc = _clip_front("plate_video_dev", d_depth_maps, A, c, A_path, c_path, scales, d_frames=d_frames, d_R=d_R, d_t=d_t, d_out=d_out,
+                d_out_masks=d_out_masks, d_out_votes=d_out_votes, d_out_moving=d_out_moving)
         pp = _plate_params(radius, threshold, min_votes, gain, occlusion, occlusion_tol_q16, min_overlap)
-        counts = np.zeros((max(ns, 1), 4), dtype=np.int64) if want_counts else None
-        d = C.c_double
-        arr = lambda x: _ptr_array(list(x)[:ns]) if x is not None and ns else None
-        self._check(self.lib.rsdsfm_plate_video_dev(self._ctx, arr(d_frames), C.c_int32(ns), C.c_int32(rows), C.c_int32(cols), C.c_int32(channels), d(K[0]), d(K[1]),
-                                                    d(K[2]), d(K[3]), arr(d_depth_maps), arr(d_R), arr(d_t), _p(a), _p(cc), _p(ap), _p(cp), _p(sc), int(mode), int(q5_mode),
-                                                    C.c_int32(iterations), C.byref(pp), _window4(window), arr(d_out), arr(d_out_masks), arr(d_out_votes), arr(d_out_moving),
+        counts = _counts(want_counts, ns, 4)
+        self._check(self.lib.rsdsfm_plate_video_dev(self._ctx, _ptrs(d_frames, ns), C.c_int32(ns), C.c_int32(rows), C.c_int32(cols), C.c_int32(channels), *_k4(K),
+                                                    _ptrs(d_depth_maps, ns), _ptrs(d_R, ns), _ptrs(d_t, ns), _p(a), _p(cc), _p(ap), _p(cp), _p(sc), int(mode), int(q5_mode),
+                                                    C.c_int32(iterations), C.byref(pp), _window4(window), _ptrs(d_out, ns), _ptrs(d_out_masks, ns), _ptrs(d_out_votes,
+                                                            ns), _ptrs(d_out_moving, ns),
                                                     _p(counts)), "rsdsfm_plate_video_dev")
-        return dict(counts=counts[:ns]) if want_counts else dict()
-
-
-for _name, _fn in list(vars(_PlateMixin).items()):
-    if not _name.startswith("__"):
-        setattr(Solver, _name, _fn)
+        return _wanted(ns, counts=counts)
 
 
 # ---------------------------------------------------------------------------------------------------
 # the colour-consistent plate: the L1 medoid in the median's place, and the context's knob between them (include/rsdsfm_plate_medoid.h)
 # ---------------------------------------------------------------------------------------------------
-PLATE_MEDOID_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "rsdsfm_plate_medoid.h")
+PLATE_MEDOID_HEADER_PATH = _header_path("rsdsfm_plate_medoid.h")
 PLATE_MEDIAN, PLATE_MEDOID = 0, 1  # rsdsfm_set_plate_estimator
 _PLATE_ESTIMATORS = {"median": PLATE_MEDIAN, "medoid": PLATE_MEDOID}
 
 
 def plate_medoid_declared_symbols():
     """Names of every function include/rsdsfm_plate_medoid.h declares"""
-    import re
-
-    txt = open(PLATE_MEDOID_HEADER_PATH).read()
-    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    return sorted(set(re.findall(r"\b(rsdsfm_[a-z0-9_]+)\s*\(", txt)))
+    return _declared("rsdsfm_plate_medoid.h")
 
 
 def plate_medoid_launches():
@@ -3888,6 +3381,7 @@ def plate_medoid_launches():
     return int(load_library().rsdsfm_plate_medoid_launches())
 
 
+@_solver_methods
 class _PlateMedoidMixin:
     def plate_medoid_dev(self, d_ref, d_ref_mask, d_layers, d_layer_masks, channels, rows, cols, d_image_out, d_mask_out, d_votes=None, d_moving=None, d_counts4=None,
                          d_sums8=None, min_overlap=0, gain_mode=0, threshold=0, min_votes=0, nlayers=None):
@@ -3918,15 +3412,10 @@ class _PlateMedoidMixin:
         return getattr(self, "_plate_estimator_knob", PLATE_MEDIAN)
 
 
-for _name, _fn in list(vars(_PlateMedoidMixin).items()):
-    if not _name.startswith("__"):
-        setattr(Solver, _name, _fn)
-
-
 # ---------------------------------------------------------------------------------------------------
 # the mover removal: the plate's flag as a cleaned, feathered matte and the plate under it (include/rsdsfm_erase.h)
 # ---------------------------------------------------------------------------------------------------
-ERASE_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "rsdsfm_erase.h")
+ERASE_HEADER_PATH = _header_path("rsdsfm_erase.h")
 ERASE_OPEN_MAX, ERASE_GROW_MAX, ERASE_FEATHER_MAX = 3, 8, 16
 ERASE_COUNTS = ("unset", "kept", "replaced", "feathered", "unresolved")  # the counters' order
 
@@ -3939,35 +3428,16 @@ class EraseParams(C.Structure):
 
 def erase_declared_symbols():
     """Names of every function include/rsdsfm_erase.h declares"""
-    import re
-
-    txt = open(ERASE_HEADER_PATH).read()
-    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    return sorted(set(re.findall(r"\b(rsdsfm_[a-z0-9_]+)\s*\(", txt)))
+    return _declared("rsdsfm_erase.h")
 
 
 def _erase_params(radius=None, open=None, grow=None, feather=None, include_undecided=False, threshold=None, min_votes=None, gain=True, occlusion=False,
                   occlusion_tol_q16=0, min_overlap=None):
     """an EraseParams with the given values over the defaults (None: the default).  open and grow are literal here: 0 means none (the struct's -1)"""
-    p = EraseParams()
-    if load_library().rsdsfm_erase_params_init(C.byref(p)) != OK:
-        raise RsdsfmError("rsdsfm_erase_params_init failed")
-    if radius is not None:
-        p.radius = int(radius)
-    if threshold is not None:
-        p.threshold = int(threshold)
-    if min_votes is not None:
-        p.min_votes = int(min_votes)
-    if min_overlap is not None:
-        p.min_overlap = int(min_overlap)
-    if open is not None:
-        p.open = -1 if int(open) == 0 else int(open)
-    if grow is not None:
-        p.grow = -1 if int(grow) == 0 else int(grow)
-    if feather is not None:
-        p.feather = int(feather)
-    p.gain_mode, p.occlusion, p.occlusion_tol_q16, p.include_undecided = 0 if gain else 1, int(occlusion), int(occlusion_tol_q16), int(include_undecided)
-    return p
+    literal = lambda x: None if x is None else (int(x) or -1)
+    return _params(EraseParams, "rsdsfm_erase_params_init", radius=radius, threshold=threshold, min_votes=min_votes, min_overlap=min_overlap, open=literal(open),
+                   grow=literal(grow), feather=feather, gain_mode=0 if gain else 1, occlusion=occlusion, occlusion_tol_q16=occlusion_tol_q16,
+                   include_undecided=include_undecided)
 
 
 def erase_default_params():
@@ -3980,10 +3450,7 @@ def erase_default_params():
 
 def mover_matte_launches(rows, cols):
     """kernel launches of one mover_matte_dev call: 3 (rsdsfm_mover_matte_launches; host only)"""
-    n = load_library().rsdsfm_mover_matte_launches(C.c_int32(rows), C.c_int32(cols))
-    if n < 0:
-        raise RsdsfmError("rsdsfm_mover_matte_launches failed (%d): rows and cols in [2, 16384]" % n)
-    return n
+    return _launches("rsdsfm_mover_matte_launches", "rows and cols in [2, 16384]", rows, cols)
 
 
 def erase_composite_launches():
@@ -3993,12 +3460,10 @@ def erase_composite_launches():
 
 def erase_launches(rows, cols, nsrc):
     """kernel launches of one erase_frame_dev call on nsrc sources: plate_launches + 3 + 1 (rsdsfm_erase_launches; host only)"""
-    n = load_library().rsdsfm_erase_launches(C.c_int32(rows), C.c_int32(cols), C.c_int32(nsrc))
-    if n < 0:
-        raise RsdsfmError("rsdsfm_erase_launches failed (%d): rows and cols in [2, 16384], nsrc in [1, 15]" % n)
-    return n
+    return _launches("rsdsfm_erase_launches", "rows and cols in [2, 16384], nsrc in [1, 15]", rows, cols, nsrc)
 
 
+@_solver_methods
 class _EraseMixin:
     def mover_matte_dev(self, d_flag, rows, cols, d_matte, open=2, grow=2, feather=4, include_undecided=False):
         """the plate's flag plane as a matte (rsdsfm_mover_matte_dev; tests/erase_spec_numpy.py): the seeds (flag 2, with include_undecided 3 too)
@@ -4009,19 +3474,14 @@ class _EraseMixin:
 
     def mover_matte(self, flag, open=2, grow=2, feather=4, include_undecided=False, device=0):
         """host convenience around mover_matte_dev: flag (rows, cols) uint8 -> the matte (rows, cols) uint8"""
-        import torch
-
         flag = np.ascontiguousarray(flag, dtype=np.uint8)
         rows, cols = flag.shape
-        dev = torch.device("cuda", device)
-        with torch.cuda.device(dev):
-            d_f = torch.from_numpy(flag).to(dev)
-            d_a = torch.empty_like(d_f)
-            torch.cuda.synchronize()
+        with _Staging(self, device) as st:
+            d_f = st.up(flag)
+            d_a = st.empty_like(d_f)
+            st.ready()
             self.mover_matte_dev(d_f.data_ptr(), rows, cols, d_a.data_ptr(), open, grow, feather, include_undecided)
-            self.synchronize()
-            return d_a.cpu().numpy()
-
+            return st.down(d_a)[0]
     def erase_composite_dev(self, d_ref, d_ref_mask, d_plate, d_plate_mask, d_matte, channels, rows, cols, d_image_out, d_mask_out, d_counts5=None, feather=4):
         """the plate under the matte, the own frame's bytes everywhere else (rsdsfm_erase_composite_dev; tests/erase_spec_numpy.py); the counts
         [unset, kept, replaced, feathered, unresolved] into d_counts5 (five device int64).  One launch, enqueued on the context's stream."""
@@ -4031,22 +3491,16 @@ class _EraseMixin:
 
     def erase_composite(self, ref, ref_mask, plate, plate_mask, matte, feather=4, device=0):
         """host convenience around erase_composite_dev -> (image, mask (rows, cols) uint8, counts (5,) int64)"""
-        import torch
-
         ref = np.ascontiguousarray(ref, dtype=np.uint8)
         rows, cols = ref.shape[:2]
         ch = 1 if ref.ndim == 2 else ref.shape[2]
-        dev = torch.device("cuda", device)
-        with torch.cuda.device(dev):
-            up = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.uint8)).to(dev)
-            d_ref, d_rm, d_p, d_pm, d_a = up(ref), up(ref_mask), up(plate), up(plate_mask), up(matte)
-            d_out, d_mask, d_cnt = torch.empty_like(d_ref), torch.empty((rows, cols), dtype=torch.uint8, device=dev), torch.zeros(5, dtype=torch.int64, device=dev)
-            torch.cuda.synchronize()
+        with _Staging(self, device) as st:
+            d_ref, d_rm, d_p, d_pm, d_a = (st.up(x, np.uint8) for x in (ref, ref_mask, plate, plate_mask, matte))
+            d_out, d_mask, d_cnt = st.empty_like(d_ref), st.empty((rows, cols)), st.zeros(5, "int64")
+            st.ready()
             self.erase_composite_dev(d_ref.data_ptr(), d_rm.data_ptr(), d_p.data_ptr(), d_pm.data_ptr(), d_a.data_ptr(), ch, rows, cols, d_out.data_ptr(), d_mask.data_ptr(),
                                      d_cnt.data_ptr(), feather)
-            self.synchronize()
-            return d_out.cpu().numpy(), d_mask.cpu().numpy(), d_cnt.cpu().numpy()
-
+            return st.down(d_out, d_mask, d_cnt)
     def erase_frame_dev(self, d_images, channels, d_depth_maps, d_R, d_t, K, rows, cols, M, m, d_image, d_mask, d_matte=None, d_moving=None, d_counts5=None, open=None,
                         grow=None, feather=None, include_undecided=False, threshold=None, min_votes=None, gain=True, min_overlap=None, window=None, occlusion=False,
                         occlusion_tol_q16=0, mode=BACKPROJECT_RS, q5_mode=Q5_COMPAT, iterations=0, params=None):
@@ -4054,15 +3508,9 @@ class _EraseMixin:
         context's workspace, the matte of its flag (open, grow, feather literal; None: the defaults 2, 2, 4), the plate under the matte and the
         own frame everywhere else into d_image, d_mask; the matte into d_matte, the plate's flag into d_moving, [unset, kept, replaced,
         feathered, unresolved] into d_counts5.  params: an EraseParams passed as it is instead of the keywords.  Enqueued on the context's stream."""
-        ns = len(d_images)
-        _need_all(ns, d_depth_maps=d_depth_maps, d_R=d_R, d_t=d_t)
-        Mm, mm = _f64(M).reshape(-1, 9), _f64(m).reshape(-1, 3)
-        if Mm.shape[0] < ns or mm.shape[0] < ns:
-            raise RsdsfmError("erase_frame_dev: every source needs a pose (M, m)")
+        ns, Mm, mm = _frame_front("erase_frame_dev", d_images, M, m, d_depth_maps=d_depth_maps, d_R=d_R, d_t=d_t)
         ep = params if params is not None else _erase_params(None, open, grow, feather, include_undecided, threshold, min_votes, gain, occlusion, occlusion_tol_q16, min_overlap)
-        d = C.c_double
-        arr = lambda x: _ptr_array(list(x)[:ns]) if ns else None
-        self._check(self.lib.rsdsfm_erase_frame_dev(self._ctx, arr(d_images), C.c_int32(channels), arr(d_depth_maps), arr(d_R), arr(d_t), d(K[0]), d(K[1]), d(K[2]), d(K[3]),
+        self._check(self.lib.rsdsfm_erase_frame_dev(self._ctx, _ptrs(d_images, ns), C.c_int32(channels), _ptrs(d_depth_maps, ns), _ptrs(d_R, ns), _ptrs(d_t, ns), *_k4(K),
                                                     C.c_int32(rows), C.c_int32(cols), int(mode), int(q5_mode), C.c_int32(iterations), C.c_int32(ns), _p(Mm), _p(mm),
                                                     C.byref(ep), _window4(window), _dp(d_image), _dp(d_mask), _np0(d_matte), _np0(d_moving), _np0(d_counts5)),
                     "rsdsfm_erase_frame_dev")
@@ -4073,32 +3521,22 @@ class _EraseMixin:
         """a solved clip without its movers (rsdsfm_erase_video_dev): the clip as plate_video_dev takes it and walks it, erase_frame_dev into
         d_out[q], d_out_masks[q], d_out_mattes[q], d_out_moving[q].  Returns dict(); with want_counts counts (nsources, 5) int64 [unset, kept,
         replaced, feathered, unresolved] -- the call then waits."""
-        ns = len(d_depth_maps)
-        _need_all(ns, d_frames=d_frames, d_R=d_R, d_t=d_t, d_out=d_out, d_out_masks=d_out_masks, d_out_mattes=d_out_mattes, d_out_moving=d_out_moving)
-        a, cc, ap, cp = _f64(A).reshape(-1, 9), _f64(c).reshape(-1, 3), _f64(A_path).reshape(-1, 9), _f64(c_path).reshape(-1, 3)
-        sc = _f64(scales).reshape(-1)
-        if min(a.shape[0], cc.shape[0], ap.shape[0], cp.shape[0], sc.shape[0]) < ns:
-            raise RsdsfmError("erase_video_dev: every source needs a pose on both paths and a scale")
+        ns, a, cc, ap, cp, sc = _clip_front("erase_video_dev", d_depth_maps, A, c, A_path, c_path, scales, d_frames=d_frames, d_R=d_R, d_t=d_t, d_out=d_out,
+                d_out_masks=d_out_masks, d_out_mattes=d_out_mattes, d_out_moving=d_out_moving)
         ep = _erase_params(radius, open, grow, feather, include_undecided, threshold, min_votes, gain, occlusion, occlusion_tol_q16, min_overlap)
-        counts = np.zeros((max(ns, 1), 5), dtype=np.int64) if want_counts else None
-        d = C.c_double
-        arr = lambda x: _ptr_array(list(x)[:ns]) if x is not None and ns else None
-        self._check(self.lib.rsdsfm_erase_video_dev(self._ctx, arr(d_frames), C.c_int32(ns), C.c_int32(rows), C.c_int32(cols), C.c_int32(channels), d(K[0]), d(K[1]),
-                                                    d(K[2]), d(K[3]), arr(d_depth_maps), arr(d_R), arr(d_t), _p(a), _p(cc), _p(ap), _p(cp), _p(sc), int(mode), int(q5_mode),
-                                                    C.c_int32(iterations), C.byref(ep), _window4(window), arr(d_out), arr(d_out_masks), arr(d_out_mattes), arr(d_out_moving),
+        counts = _counts(want_counts, ns, 5)
+        self._check(self.lib.rsdsfm_erase_video_dev(self._ctx, _ptrs(d_frames, ns), C.c_int32(ns), C.c_int32(rows), C.c_int32(cols), C.c_int32(channels), *_k4(K),
+                                                    _ptrs(d_depth_maps, ns), _ptrs(d_R, ns), _ptrs(d_t, ns), _p(a), _p(cc), _p(ap), _p(cp), _p(sc), int(mode), int(q5_mode),
+                                                    C.c_int32(iterations), C.byref(ep), _window4(window), _ptrs(d_out, ns), _ptrs(d_out_masks, ns), _ptrs(d_out_mattes,
+                                                            ns), _ptrs(d_out_moving, ns),
                                                     _p(counts)), "rsdsfm_erase_video_dev")
-        return dict(counts=counts[:ns]) if want_counts else dict()
-
-
-for _name, _fn in list(vars(_EraseMixin).items()):
-    if not _name.startswith("__"):
-        setattr(Solver, _name, _fn)
+        return _wanted(ns, counts=counts)
 
 
 # ---------------------------------------------------------------------------------------------------
 # the sharpness transfer: a blurred frame takes pixels from its sharper registered neighbours (include/rsdsfm_deblur.h)
 # ---------------------------------------------------------------------------------------------------
-DEBLUR_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "rsdsfm_deblur.h")
+DEBLUR_HEADER_PATH = _header_path("rsdsfm_deblur.h")
 DEBLUR_RADIUS_MAX = 3
 DEBLUR_LAYERS_MAX = 7
 DEBLUR_TAU_MAX = 32
@@ -4114,14 +3552,8 @@ class DeblurParams(C.Structure):
 
 def _deblur_params(radius=None, strength=None, margin=None, gate=True, gain=True, occlusion=False, occlusion_tol_q16=0, min_overlap=None, min_pairs=None, band_rows=None):
     """a DeblurParams with the given values over the defaults (None: the default; margin -1: none; band_rows None or 0: one tau per neighbour)"""
-    p = DeblurParams()
-    if load_library().rsdsfm_deblur_params_init(C.byref(p)) != OK:
-        raise RsdsfmError("rsdsfm_deblur_params_init failed")
-    for name, value in (("radius", radius), ("strength", strength), ("margin", margin), ("min_overlap", min_overlap), ("min_pairs", min_pairs), ("band_rows", band_rows)):
-        if value is not None:
-            setattr(p, name, int(value))
-    p.gate_mode, p.gain_mode, p.occlusion, p.occlusion_tol_q16 = 0 if gate else 1, 0 if gain else 1, int(occlusion), int(occlusion_tol_q16)
-    return p
+    return _params(DeblurParams, "rsdsfm_deblur_params_init", radius=radius, strength=strength, margin=margin, min_overlap=min_overlap, min_pairs=min_pairs,
+                   band_rows=band_rows, gate_mode=0 if gate else 1, gain_mode=0 if gain else 1, occlusion=occlusion, occlusion_tol_q16=occlusion_tol_q16)
 
 
 def deblur_default_params():
@@ -4169,12 +3601,10 @@ def deblur_row_taus(taus, band_rows, rows):
 def deblur_launches(rows, cols, nsrc):
     """kernel launches of one deblur_frame_dev call on nsrc sources: nsrc stabilize_window_launches + 3 (nsrc - 1), or + 1 with one source
     (rsdsfm_deblur_launches; host only)"""
-    n = load_library().rsdsfm_deblur_launches(C.c_int32(rows), C.c_int32(cols), C.c_int32(nsrc))
-    if n < 0:
-        raise RsdsfmError("rsdsfm_deblur_launches failed (%d): rows and cols in [2, 16384], nsrc in [1, 8]" % n)
-    return n
+    return _launches("rsdsfm_deblur_launches", "rows and cols in [2, 16384], nsrc in [1, 8]", rows, cols, nsrc)
 
 
+@_solver_methods
 class _DeblurMixin:
     def deblur_sharpness_dev(self, d_ref, d_ref_mask, d_layer, d_layer_mask, channels, rows, cols, d_sharp4, d_sums8=None, min_overlap=0, gain_mode=0):
         """a layer's sharpness record against the reference (rsdsfm_deblur_sharpness_dev; tests/deblur_spec_numpy.py's sharpness): d_sharp4
@@ -4186,22 +3616,16 @@ class _DeblurMixin:
 
     def deblur_sharpness(self, ref, ref_mask, layer, layer_mask, record=None, min_overlap=0, gain_mode=0, device=0):
         """host convenience around deblur_sharpness_dev -> (4,) uint64"""
-        import torch
-
         ref = np.ascontiguousarray(ref, dtype=np.uint8)
         rows, cols = ref.shape[:2]
-        dev = torch.device("cuda", device)
-        with torch.cuda.device(dev):
-            up = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.uint8)).to(dev)
-            d = [up(ref), up(ref_mask), up(layer), up(layer_mask)]
-            d_rec = None if record is None else torch.from_numpy(np.ascontiguousarray(record, dtype=np.uint64).view(np.int64)).to(dev)
-            d_T = torch.full((4,), -1, dtype=torch.int64, device=dev)
-            torch.cuda.synchronize()
+        with _Staging(self, device) as st:
+            d = [st.up(x, np.uint8) for x in (ref, ref_mask, layer, layer_mask)]
+            d_rec = None if record is None else st.up64(record)
+            d_T = st.full(4, -1, "int64")
+            st.ready()
             self.deblur_sharpness_dev(d[0].data_ptr(), d[1].data_ptr(), d[2].data_ptr(), d[3].data_ptr(), 1 if ref.ndim == 2 else ref.shape[2], rows, cols, d_T.data_ptr(),
                                       d_rec.data_ptr() if d_rec is not None else None, min_overlap, gain_mode)
-            self.synchronize()
-            return d_T.cpu().numpy().view(np.uint64)
-
+            return st.down(d_T)[0].view(np.uint64)
     def deblur_accumulate_dev(self, d_ref, d_ref_mask, d_layer, d_layer_mask, channels, rows, cols, d_cells, first, last, d_sharp4=None, d_sums8=None, min_overlap=0,
                               gain_mode=0, strength=0, margin=0, min_pairs=0, gate_mode=0, d_image_out=None, d_mask_out=None, d_weight=None, d_counts3=None):
         """one layer accumulated onto the cells (rsdsfm_deblur_accumulate_dev; tests/deblur_spec_numpy.py): the layer's pixel counts
@@ -4219,23 +3643,18 @@ class _DeblurMixin:
         mask) pairs of host arrays, records None or one 8-word overlap record (or None) per layer, sharps None (every layer's sharpness record
         is computed on the device) or one 4-word record per layer
         -> (image, mask, weight (rows, cols) uint8, counts (3,) int64 [unset, own only, transferred], sharps (n, 4) uint64)"""
-        import torch
-
         ref = np.ascontiguousarray(ref, dtype=np.uint8)
         rows, cols = ref.shape[:2]
         ch = 1 if ref.ndim == 2 else ref.shape[2]
-        dev = torch.device("cuda", device)
-        with torch.cuda.device(dev):
-            up = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.uint8)).to(dev)
-            up64 = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.uint64).view(np.int64)).to(dev)
-            d_ref, d_rm = up(ref), up(ref_mask)
-            d_l = [(up(i), up(m)) for i, m in layers]
-            d_rec = [None if records is None or records[j] is None else up64(records[j]) for j in range(len(layers))]
-            d_T = torch.full((max(len(layers), 1), 4), -1, dtype=torch.int64, device=dev) if sharps is None else up64(np.asarray(sharps, dtype=np.uint64).reshape(-1, 4))
-            d_cells = torch.empty((rows, cols, ch + 1), dtype=torch.int16, device=dev)
-            d_out, d_mask = torch.empty_like(d_ref), torch.empty((rows, cols), dtype=torch.uint8, device=dev)
-            d_w, d_cnt = torch.empty_like(d_mask), torch.zeros(3, dtype=torch.int64, device=dev)
-            torch.cuda.synchronize()
+        with _Staging(self, device) as st:
+            d_ref, d_rm = st.up(ref), st.up(ref_mask, np.uint8)
+            d_l = [(st.up(i, np.uint8), st.up(m, np.uint8)) for i, m in layers]
+            d_rec = [None if records is None or records[j] is None else st.up64(records[j]) for j in range(len(layers))]
+            d_T = st.full((max(len(layers), 1), 4), -1, "int64") if sharps is None else st.up64(np.asarray(sharps, dtype=np.uint64).reshape(-1, 4))
+            d_cells = st.empty((rows, cols, ch + 1), "int16")
+            d_out, d_mask = st.empty_like(d_ref), st.empty((rows, cols))
+            d_w, d_cnt = st.empty_like(d_mask), st.zeros(3, "int64")
+            st.ready()
             outs = dict(d_image_out=d_out.data_ptr(), d_mask_out=d_mask.data_ptr(), d_weight=d_w.data_ptr(), d_counts3=d_cnt.data_ptr())
             knobs = dict(min_overlap=min_overlap, gain_mode=gain_mode, strength=strength, margin=margin, min_pairs=min_pairs, gate_mode=gate_mode)
             if not d_l:
@@ -4246,9 +3665,8 @@ class _DeblurMixin:
                     self.deblur_sharpness_dev(d_ref.data_ptr(), d_rm.data_ptr(), d_i.data_ptr(), d_m.data_ptr(), ch, rows, cols, d_T[j].data_ptr(), rec, min_overlap, gain_mode)
                 self.deblur_accumulate_dev(d_ref.data_ptr(), d_rm.data_ptr(), d_i.data_ptr(), d_m.data_ptr(), ch, rows, cols, d_cells.data_ptr(), j == 0, j == len(d_l) - 1,
                                            d_T[j].data_ptr(), rec, **knobs, **outs)
-            self.synchronize()
-            return d_out.cpu().numpy(), d_mask.cpu().numpy(), d_w.cpu().numpy(), d_cnt.cpu().numpy(), d_T.cpu().numpy().view(np.uint64)[:len(layers)]
-
+            out, mask, weight, counts, T = st.down(d_out, d_mask, d_w, d_cnt, d_T)
+            return out, mask, weight, counts, T.view(np.uint64)[:len(layers)]
     def deblur_band_sharpness_dev(self, d_ref, d_ref_mask, d_layer, d_layer_mask, channels, rows, cols, band_rows, d_band_records, d_sums8=None, min_overlap=0,
                                   gain_mode=0):
         """a layer's sharpness records per band of band_rows rows (rsdsfm_deblur_band_sharpness_dev; tests/deblur_bands_spec_numpy.py's
@@ -4260,23 +3678,17 @@ class _DeblurMixin:
 
     def deblur_band_sharpness(self, ref, ref_mask, layer, layer_mask, band_rows, record=None, min_overlap=0, gain_mode=0, device=0):
         """host convenience around deblur_band_sharpness_dev -> (NB, 4) uint64"""
-        import torch
-
         ref = np.ascontiguousarray(ref, dtype=np.uint8)
         rows, cols = ref.shape[:2]
         nb = max(1, -(-rows // max(int(band_rows), 1)))
-        dev = torch.device("cuda", device)
-        with torch.cuda.device(dev):
-            up = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.uint8)).to(dev)
-            d = [up(ref), up(ref_mask), up(layer), up(layer_mask)]
-            d_rec = None if record is None else torch.from_numpy(np.ascontiguousarray(record, dtype=np.uint64).view(np.int64)).to(dev)
-            d_T = torch.full((nb, 4), -1, dtype=torch.int64, device=dev)
-            torch.cuda.synchronize()
+        with _Staging(self, device) as st:
+            d = [st.up(x, np.uint8) for x in (ref, ref_mask, layer, layer_mask)]
+            d_rec = None if record is None else st.up64(record)
+            d_T = st.full((nb, 4), -1, "int64")
+            st.ready()
             self.deblur_band_sharpness_dev(d[0].data_ptr(), d[1].data_ptr(), d[2].data_ptr(), d[3].data_ptr(), 1 if ref.ndim == 2 else ref.shape[2], rows, cols, band_rows,
                                            d_T.data_ptr(), d_rec.data_ptr() if d_rec is not None else None, min_overlap, gain_mode)
-            self.synchronize()
-            return d_T.cpu().numpy().view(np.uint64)
-
+            return st.down(d_T)[0].view(np.uint64)
     def deblur_band_accumulate_dev(self, d_ref, d_ref_mask, d_layer, d_layer_mask, channels, rows, cols, band_rows, d_cells, first, last, d_band_records=None, d_sums8=None,
                                    min_overlap=0, gain_mode=0, strength=0, margin=0, min_pairs=0, gate_mode=0, d_image_out=None, d_mask_out=None, d_weight=None,
                                    d_counts3=None):
@@ -4294,25 +3706,20 @@ class _DeblurMixin:
         """host convenience around deblur_band_sharpness_dev and deblur_band_accumulate_dev, as deblur_accumulate: band_records None (computed
         on the device) or one (NB, 4) array per layer
         -> (image, mask, weight, counts (3,) int64, band records (n, NB, 4) uint64, cells (rows, cols, CH + 1) uint16 after the last step)"""
-        import torch
-
         ref = np.ascontiguousarray(ref, dtype=np.uint8)
         rows, cols = ref.shape[:2]
         ch = 1 if ref.ndim == 2 else ref.shape[2]
         nb = max(1, -(-rows // max(int(band_rows), 1)))
-        dev = torch.device("cuda", device)
-        with torch.cuda.device(dev):
-            up = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.uint8)).to(dev)
-            up64 = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.uint64).view(np.int64)).to(dev)
-            d_ref, d_rm = up(ref), up(ref_mask)
-            d_l = [(up(i), up(m)) for i, m in layers]
-            d_rec = [None if records is None or records[j] is None else up64(records[j]) for j in range(len(layers))]
-            d_T = (torch.full((max(len(layers), 1), nb, 4), -1, dtype=torch.int64, device=dev) if band_records is None
-                   else up64(np.asarray(band_records, dtype=np.uint64).reshape(-1, nb, 4)))
-            d_cells = torch.zeros((rows, cols, ch + 1), dtype=torch.int16, device=dev)
-            d_out, d_mask = torch.empty_like(d_ref), torch.empty((rows, cols), dtype=torch.uint8, device=dev)
-            d_w, d_cnt = torch.empty_like(d_mask), torch.zeros(3, dtype=torch.int64, device=dev)
-            torch.cuda.synchronize()
+        with _Staging(self, device) as st:
+            d_ref, d_rm = st.up(ref), st.up(ref_mask, np.uint8)
+            d_l = [(st.up(i, np.uint8), st.up(m, np.uint8)) for i, m in layers]
+            d_rec = [None if records is None or records[j] is None else st.up64(records[j]) for j in range(len(layers))]
+            d_T = (st.full((max(len(layers), 1), nb, 4), -1, "int64") if band_records is None
+                   else st.up64(np.asarray(band_records, dtype=np.uint64).reshape(-1, nb, 4)))
+            d_cells = st.zeros((rows, cols, ch + 1), "int16")
+            d_out, d_mask = st.empty_like(d_ref), st.empty((rows, cols))
+            d_w, d_cnt = st.empty_like(d_mask), st.zeros(3, "int64")
+            st.ready()
             outs = dict(d_image_out=d_out.data_ptr(), d_mask_out=d_mask.data_ptr(), d_weight=d_w.data_ptr(), d_counts3=d_cnt.data_ptr())
             knobs = dict(min_overlap=min_overlap, gain_mode=gain_mode, strength=strength, margin=margin, min_pairs=min_pairs, gate_mode=gate_mode)
             if not d_l:
@@ -4324,10 +3731,8 @@ class _DeblurMixin:
                                                    min_overlap, gain_mode)
                 self.deblur_band_accumulate_dev(d_ref.data_ptr(), d_rm.data_ptr(), d_i.data_ptr(), d_m.data_ptr(), ch, rows, cols, band_rows, d_cells.data_ptr(), j == 0,
                                                 j == len(d_l) - 1, d_T[j].data_ptr(), rec, **knobs, **outs)
-            self.synchronize()
-            return (d_out.cpu().numpy(), d_mask.cpu().numpy(), d_w.cpu().numpy(), d_cnt.cpu().numpy(), d_T.cpu().numpy().view(np.uint64)[:len(layers)],
-                    d_cells.cpu().numpy().view(np.uint16))
-
+            out, mask, weight, counts, T, cells = st.down(d_out, d_mask, d_w, d_cnt, d_T, d_cells)
+            return out, mask, weight, counts, T.view(np.uint64)[:len(layers)], cells.view(np.uint16)
     def deblur_frame_dev(self, d_images, channels, d_depth_maps, d_R, d_t, K, rows, cols, M, m, d_image, d_mask, d_weight=None, d_counts3=None, d_sharp_records=None,
                          strength=None, margin=None, gate=True, gain=True, min_overlap=None, min_pairs=None, window=None, occlusion=False, occlusion_tol_q16=0,
                          mode=BACKPROJECT_RS, q5_mode=Q5_COMPAT, iterations=0, params=None, band_rows=None):
@@ -4338,15 +3743,9 @@ class _DeblurMixin:
         d_sharp_records ((nsrc - 1) x 4 device uint64).  band_rows (a multiple of 16; None or 0: off): a tau per band of rows through
         deblur_band_sharpness_dev and deblur_band_accumulate_dev, d_sharp_records then (nsrc - 1) x NB x 4.  params: a DeblurParams passed as it
         is instead of the keywords.  Enqueued on the context's stream."""
-        ns = len(d_images)
-        _need_all(ns, d_depth_maps=d_depth_maps, d_R=d_R, d_t=d_t)
-        Mm, mm = _f64(M).reshape(-1, 9), _f64(m).reshape(-1, 3)
-        if Mm.shape[0] < ns or mm.shape[0] < ns:
-            raise RsdsfmError("deblur_frame_dev: every source needs a pose (M, m)")
+        ns, Mm, mm = _frame_front("deblur_frame_dev", d_images, M, m, d_depth_maps=d_depth_maps, d_R=d_R, d_t=d_t)
         dp = params if params is not None else _deblur_params(None, strength, margin, gate, gain, occlusion, occlusion_tol_q16, min_overlap, min_pairs, band_rows)
-        d = C.c_double
-        arr = lambda x: _ptr_array(list(x)[:ns]) if ns else None
-        self._check(self.lib.rsdsfm_deblur_frame_dev(self._ctx, arr(d_images), C.c_int32(channels), arr(d_depth_maps), arr(d_R), arr(d_t), d(K[0]), d(K[1]), d(K[2]), d(K[3]),
+        self._check(self.lib.rsdsfm_deblur_frame_dev(self._ctx, _ptrs(d_images, ns), C.c_int32(channels), _ptrs(d_depth_maps, ns), _ptrs(d_R, ns), _ptrs(d_t, ns), *_k4(K),
                                                      C.c_int32(rows), C.c_int32(cols), int(mode), int(q5_mode), C.c_int32(iterations), C.c_int32(ns), _p(Mm), _p(mm),
                                                      C.byref(dp), _window4(window), _np0(d_image), _np0(d_mask), _np0(d_weight), _np0(d_counts3), _np0(d_sharp_records)),
                     "rsdsfm_deblur_frame_dev")
@@ -4360,40 +3759,22 @@ class _DeblurMixin:
         band_rows (a multiple of 16; None: off): a tau per band of rows; taus is then the largest of a neighbour's band taus and, with
         want_taus, band_taus (nsources, 6, NB) int32 rides along.  band_rows 0: rsdsfm_deblur_video_banded_dev with the bands off, band_taus
         (nsources, 6, 1).  Without band_rows every key and byte is what it was."""
-        ns = len(d_depth_maps)
-        _need_all(ns, d_frames=d_frames, d_R=d_R, d_t=d_t, d_out=d_out, d_out_masks=d_out_masks, d_out_weights=d_out_weights)
-        a, cc, ap, cp = _f64(A).reshape(-1, 9), _f64(c).reshape(-1, 3), _f64(A_path).reshape(-1, 9), _f64(c_path).reshape(-1, 3)
-        sc = _f64(scales).reshape(-1)
-        if min(a.shape[0], cc.shape[0], ap.shape[0], cp.shape[0], sc.shape[0]) < ns:
-            raise RsdsfmError("deblur_video_dev: every source needs a pose on both paths and a scale")
+        ns, a, cc, ap, cp, sc = _clip_front("deblur_video_dev", d_depth_maps, A, c, A_path, c_path, scales, d_frames=d_frames, d_R=d_R, d_t=d_t, d_out=d_out,
+                d_out_masks=d_out_masks, d_out_weights=d_out_weights)
         dp = _deblur_params(radius, strength, margin, gate, gain, occlusion, occlusion_tol_q16, min_overlap, min_pairs, band_rows)
-        counts = np.zeros((max(ns, 1), 3), dtype=np.int64) if want_counts else None
-        taus = np.full((max(ns, 1), DEBLUR_TAUS_PER_FRAME), -1, dtype=np.int32) if want_taus else None
+        counts = _counts(want_counts, ns, 3)
+        taus = _counts(want_taus, ns, DEBLUR_TAUS_PER_FRAME, dtype=np.int32, fill=-1)
         banded = band_rows is not None  # 0: the banded entry point with band_rows off, one band
         nb = max(1, -(-int(rows) // int(band_rows))) if banded and int(band_rows) > 0 else 1
-        band_taus = np.full((max(ns, 1), DEBLUR_TAUS_PER_FRAME, min(nb, DEBLUR_BANDS_MAX)), -1, dtype=np.int32) if want_taus and banded else None
-        d = C.c_double
-        arr = lambda x: _ptr_array(list(x)[:ns]) if x is not None and ns else None
-        args = (self._ctx, arr(d_frames), C.c_int32(ns), C.c_int32(rows), C.c_int32(cols), C.c_int32(channels), d(K[0]), d(K[1]), d(K[2]), d(K[3]), arr(d_depth_maps),
-                arr(d_R), arr(d_t), _p(a), _p(cc), _p(ap), _p(cp), _p(sc), int(mode), int(q5_mode), C.c_int32(iterations), C.byref(dp), _window4(window), arr(d_out),
-                arr(d_out_masks), arr(d_out_weights), _p(counts), _p(taus))
+        band_taus = _counts(want_taus and banded, ns, DEBLUR_TAUS_PER_FRAME, min(nb, DEBLUR_BANDS_MAX), dtype=np.int32, fill=-1)
+        args = (self._ctx, _ptrs(d_frames, ns), C.c_int32(ns), C.c_int32(rows), C.c_int32(cols), C.c_int32(channels), *_k4(K), _ptrs(d_depth_maps, ns),
+                _ptrs(d_R, ns), _ptrs(d_t, ns), _p(a), _p(cc), _p(ap), _p(cp), _p(sc), int(mode), int(q5_mode), C.c_int32(iterations), C.byref(dp), _window4(window), _ptrs(d_out, ns),
+                _ptrs(d_out_masks, ns), _ptrs(d_out_weights, ns), _p(counts), _p(taus))
         if banded:
             self._check(self.lib.rsdsfm_deblur_video_banded_dev(*args, _p(band_taus)), "rsdsfm_deblur_video_banded_dev")
         else:
             self._check(self.lib.rsdsfm_deblur_video_dev(*args), "rsdsfm_deblur_video_dev")
-        out = dict()
-        if band_taus is not None:
-            out["band_taus"] = band_taus[:ns]
-        if want_counts:
-            out["counts"] = counts[:ns]
-        if want_taus:
-            out["taus"] = taus[:ns]
-        return out
-
-
-for _name, _fn in list(vars(_DeblurMixin).items()):
-    if not _name.startswith("__"):
-        setattr(Solver, _name, _fn)
+        return _wanted(ns, band_taus=band_taus, counts=counts, taus=taus)
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -4417,6 +3798,7 @@ def velocity_errors(w_est, v_est, w_true, v_true):
     return we.value, ve.value
 
 
+@_solver_methods
 class _MetricsMixin:
     def reprojection_error(self, est_coords, gt_depth, est_depth, R_abs, t_abs, K, max_norm=10.0, want_image=True):
         """Camera::meanReprojectionError (+ createErrorImage).  est_coords: (rows, cols, 3) float32; depth maps (rows, cols)."""
@@ -4428,19 +3810,17 @@ class _MetricsMixin:
         st = ReprojectionStats()
         img = np.zeros((rows, cols), dtype=np.uint8) if want_image else None
         d = C.c_double
-        self._check(self.lib.rsdsfm_reprojection_error(self._ctx, _p(est), _p(gd), _p(ed), _p(Rr), _p(tt), d(K[0]), d(K[1]), d(K[2]), d(K[3]), C.c_int32(rows), C.c_int32(cols), d(max_norm), C.byref(st), _p(img)), "rsdsfm_reprojection_error")
+        self._check(self.lib.rsdsfm_reprojection_error(self._ctx, _p(est), _p(gd), _p(ed), _p(Rr), _p(tt), *_k4(K), C.c_int32(rows), C.c_int32(cols), d(max_norm), C.byref(st),
+                _p(img)), "rsdsfm_reprojection_error")
         return st.as_dict(), img
 
     def reprojection_error_dev(self, d_est, d_gt_depth, d_est_depth, d_R, d_t, K, rows, cols, max_norm=10.0, d_error_image=None):
         st = ReprojectionStats()
         d = C.c_double
-        self._check(self.lib.rsdsfm_reprojection_error_dev(self._ctx, _dp(d_est), _dp(d_gt_depth), _dp(d_est_depth), _dp(d_R), _dp(d_t), d(K[0]), d(K[1]), d(K[2]), d(K[3]), C.c_int32(rows), C.c_int32(cols), d(max_norm), C.byref(st), _dp(d_error_image) if d_error_image else None), "rsdsfm_reprojection_error_dev")
+        self._check(self.lib.rsdsfm_reprojection_error_dev(self._ctx, _dp(d_est), _dp(d_gt_depth), _dp(d_est_depth), _dp(d_R), _dp(d_t), *_k4(K), C.c_int32(rows), C.c_int32(cols),
+                d(max_norm), C.byref(st), _dp(d_error_image) if d_error_image else None), "rsdsfm_reprojection_error_dev")
         return st.as_dict()
 
-
-for _name, _fn in list(vars(_MetricsMixin).items()):
-    if not _name.startswith("__"):
-        setattr(Solver, _name, _fn)
 
 from . import evaluate, formats  # noqa: E402,F401  (on-disk formats + archive runner)
 
