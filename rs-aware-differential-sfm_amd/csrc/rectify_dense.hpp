@@ -34,6 +34,7 @@ struct DenseWs {
     unsigned long long* d_deblur_bands = nullptr; // its band records, 64 x 4 words whatever the size (deblur.hpp; made when a frame call with band_rows first asks for it)
     unsigned char* d_denoise_spatial = nullptr; // the spatial top-up's frame call: the temporal stage's weight and image, 4 planes (denoise.hpp; made when first asked for)
     unsigned char* d_noise = nullptr; // the noise level's histogram (1024 uint32) and a record (4 uint64) for the auto frame call (noise.hpp; made when first asked for)
+    unsigned char* d_noise_curve = nullptr; // the noise curve's histogram (8 x 1024 uint32) and a curve (36 uint64) for the curve frame call (noise_curve.hpp; made when first asked for)
     int rows = 0, cols = 0;
 };
 

@@ -43,6 +43,8 @@ static void dense_ws_free(DenseWs* w) {
     w->d_denoise_spatial = nullptr;
     if (w->d_noise) (void)hipFree(w->d_noise);
     w->d_noise = nullptr;
+    if (w->d_noise_curve) (void)hipFree(w->d_noise_curve);
+    w->d_noise_curve = nullptr;
     w->d_pyr = nullptr;
     w->d_disp = nullptr;
     w->d_mask = nullptr;

@@ -321,6 +321,11 @@ def evaluate_real_sequence(solver, frames, camera="galaxy", gamma=0.95, out_dir=
     frame's own render (Solver.denoise_auto_video_dev, tests/noise_spec_numpy.py): the returned dict also has denoise_noise ((frames, 4) int64:
     [n, m, sigma_q8, h]) and denoise.csv three more columns (noise_m, sigma, strength).  With an integer or None strength every key, file and
     byte is what it was.
+    denoise=(K, "curve") or (K, "curve", spatial): the strength of both stages PER PIXEL from every frame's own noise curve, measured per
+    brightness band on the device behind the frame's own render (rsdsfm_noise_curve.denoise_curve_video_dev, tests/noise_curve_spec_numpy.py): the
+    returned dict also has denoise_curve ((frames, 9, 4) int64: [n, m, sigma_q8, 0] of the eight bands, then of all samples), and
+    denoise.csv eleven more columns (noise_m0 .. noise_m7, noise_m, and strength_min, strength_max: the ends of the frame's strength table).  Any
+    other string is a ValueError.
     superres=scale or (scale, K) (needs stabilize=True: ValueError otherwise): behind everything else, every stabilised frame once more on a grid
     `scale` times finer (1 .. 4), merged from itself and its K neighbours on either side (1 .. 7, default 2), each rendered alone into the frame's
     camera on the SMOOTHED path (Solver.superres_video_dev, tests/superres_spec_numpy.py; the fused maps with fuse=True): the returned dict also
@@ -682,9 +687,11 @@ def evaluate_real_sequence(solver, frames, camera="galaxy", gamma=0.95, out_dir=
                 if denoise is not None:  # every stabilised frame once more, averaged with its neighbours
                     dn_one = not isinstance(denoise, (tuple, list, np.ndarray))  # K alone; (K, strength, (target, search)) is ragged: no np.ndim
                     dn_auto = not dn_one and isinstance(denoise[1], str)  # (K, "auto"[, spatial]): the strength from every frame's own noise
+                    dn_curve = dn_auto and denoise[1] == "curve"  # (K, "curve"[, spatial]): a strength per pixel from every frame's own noise curve
+                    dn_auto = dn_auto and not dn_curve
                     if dn_auto and denoise[1] != "auto":
                         raise ValueError("denoise: the strength is an integer, None or \"auto\"")
-                    dn_radius, dn_strength = (int(denoise), None) if dn_one else (int(denoise[0]), None if denoise[1] is None or dn_auto else int(denoise[1]))
+                    dn_radius, dn_strength = (int(denoise), None) if dn_one else (int(denoise[0]), None if denoise[1] is None or dn_auto or dn_curve else int(denoise[1]))
                     dn_spatial = None if dn_one or len(denoise) < 3 or denoise[2] is None or denoise[2] is False else denoise[2]
                     d_dn = [torch.empty_like(d_imgs[0]) for _ in range(nst)]
                     d_dnmasks = [torch.empty((rows, cols), dtype=torch.uint8, device=dev) for _ in range(nst)]
@@ -703,6 +710,20 @@ def evaluate_real_sequence(solver, frames, camera="galaxy", gamma=0.95, out_dir=
                         noise[:, 3] = [noise_strength(int(r[0]), int(r[1])) for r in noise]  # [n, m, sigma_q8, h]
                         traj.update(stab_denoised=[t.cpu().numpy() for t in d_dn], denoise_masks=[t.cpu().numpy() for t in d_dnmasks],
                                     denoise_weights=[t.cpu().numpy() for t in d_dnw], denoise_counts=dn["counts"][:, :3].copy(), denoise_noise=noise)
+                        if d_dns:
+                            traj.update(denoise_support=[t.cpu().numpy() for t in d_dns], denoise_spatial_counts=dn["counts"][:, 3:].copy())
+                    elif dn_curve:  # the frame's noise curve measured behind its own render, both stages at a strength per pixel
+                        import rsdsfm_noise_curve as nc  # a module beside the import shim: the package's surface is pinned
+
+                        sp_target, sp_search = (None, None) if dn_spatial is None or dn_spatial is True else (int(dn_spatial[0]), int(dn_spatial[1]))
+                        d_dns = [torch.empty((rows, cols), dtype=torch.uint8, device=dev) for _ in range(nst)] if dn_spatial is not None else None
+                        torch.cuda.synchronize()
+                        dn = nc.denoise_curve_video_dev(solver, ptrs(d_imgs), rows, cols, channels, K, ptrs(d_src[:nst]), ptrs(d_Rs[:nst]), ptrs(d_ts[:nst]), traj["A"], traj["c"],
+                                                        A_s, c_s, st_scales, ptrs(d_dn), ptrs(d_dnmasks), ptrs(d_dnw), ptrs(d_dns) if d_dns else None,
+                                                        spatial=dn_spatial is not None, target=sp_target, search=sp_search, **dn_kw)
+                        curves = dn["curves"].astype(np.int64)  # (frames, 9, 4): [n, m, sigma_q8, 0] per band, then of all samples
+                        traj.update(stab_denoised=[t.cpu().numpy() for t in d_dn], denoise_masks=[t.cpu().numpy() for t in d_dnmasks],
+                                    denoise_weights=[t.cpu().numpy() for t in d_dnw], denoise_counts=dn["counts"][:, :3].copy(), denoise_curve=curves)
                         if d_dns:
                             traj.update(denoise_support=[t.cpu().numpy() for t in d_dns], denoise_spatial_counts=dn["counts"][:, 3:].copy())
                     elif dn_spatial is None:
@@ -853,13 +874,20 @@ def evaluate_real_sequence(solver, frames, camera="galaxy", gamma=0.95, out_dir=
         if denoise is not None:
             topped = "denoise_spatial_counts" in traj  # three more columns: kept, smoothed, mean_support
             measured = "denoise_noise" in traj  # three more columns: noise_m, sigma, strength
-            rows_ = ["pair,unset,own_only,averaged,mean_weight" + (",kept,smoothed,mean_support" if topped else "") + (",noise_m,sigma,strength" if measured else "")]
+            curved = "denoise_curve" in traj  # eleven more columns: noise_m0 .. noise_m7, noise_m, strength_min, strength_max
+            rows_ = ["pair,unset,own_only,averaged,mean_weight" + (",kept,smoothed,mean_support" if topped else "") + (",noise_m,sigma,strength" if measured else "") +
+                     ("," + ",".join("noise_m%d" % b for b in range(8)) + ",noise_m,strength_min,strength_max" if curved else "")]
             for p in range(nst):
                 formats.write_png(os.path.join(out_dir, "stabilized_denoised_%d.png" % p), traj["stab_denoised"][p])
                 more = [str(int(x)) for x in traj["denoise_spatial_counts"][p][1:]] + ["%.4f" % float(traj["denoise_support"][p].mean())] if topped else []
                 if measured:
                     nz = traj["denoise_noise"][p]
                     more = more + [str(int(nz[1])), "%.4f" % (int(nz[2]) / 256.0), str(int(nz[3]))]
+                if curved:  # the band medians, the median of all samples, and the ends of the strength table the consumers formed (the defaults)
+                    import rsdsfm_noise_curve as nc
+
+                    lut = nc.noise_curve_strengths(traj["denoise_curve"][p].astype(np.uint64))
+                    more = more + [str(int(m_)) for m_ in traj["denoise_curve"][p][:, 1]] + [str(int(lut.min())), str(int(lut.max()))]
                 rows_.append(",".join([str(p)] + [str(int(x)) for x in traj["denoise_counts"][p]] + ["%.4f" % float(traj["denoise_weights"][p].mean())] + more))
             with open(os.path.join(out_dir, "denoise.csv"), "w") as fh:
                 fh.write("\n".join(rows_) + "\n")

@@ -234,6 +234,17 @@ def _sensor_noise(frames, noise, noise_seed):
     """seeded integer sensor noise on a stack of frames: every byte + an integer drawn uniformly from [-noise, noise], clipped to 0 .. 255, frame
     j from the generator seeded (noise_seed, j) -- so a frame's noise does not depend on how many frames follow it.  None or 0: the frames
     themselves"""
+    if isinstance(noise, (tuple, list, np.ndarray)):  # (a0, a255): signal-dependent noise, the amplitude per byte from the value before the noise
+        a0, a255 = (int(a) for a in noise)
+        if min(a0, a255) < 0 or max(a0, a255) > 255:
+            raise ValueError("noise is an amplitude in bytes, 0 .. 255, or a pair of them (at byte 0, at byte 255)")
+        out = np.empty_like(frames)
+        for j in range(frames.shape[0]):
+            rng = np.random.default_rng([int(noise_seed), j])
+            v = frames[j].astype(np.int64)
+            amp = a0 + ((a255 - a0) * v + 127) // 255
+            out[j] = np.clip(v + rng.integers(-amp, amp + 1), 0, 255).astype(np.uint8)
+        return out
     if not noise:
         return frames
     noise = int(noise)
@@ -330,7 +341,9 @@ def render_sequence(nframes, rows, cols, K, v, w, k=0.0, gamma=0.8, seed=0x5EED0
     for byte what this function returns without the argument.
     noise: an amplitude in bytes: after the exposure gain every byte of frame j gets an integer drawn uniformly from [-noise, noise] by the
     generator seeded (noise_seed, j), clipped to 0 .. 255 -- seeded integer sensor noise, what the temporal denoise is for.  None (or 0): byte
-    for byte what this function returns without the argument.
+    for byte what this function returns without the argument.  A pair (a0, a255): signal-dependent noise, what the noise curve is for -- the
+    amplitude of a byte of value v (before the noise) is a0 + ((a255 - a0) v + 127) // 255, the generators seeded in the same way; an integer
+    behaves exactly as before.
     mover: (y0, x0, h, w, dx, dy): a rectangle of h x w pixels with render_occluded_pair's block texture pasted onto frame j at
     (y0 + j dy, x0 + j dx), after the exposure gain and before the sensor noise -- something that moves through a static scene, what the clean
     plate is for; it must lie inside every frame and has no part in F or the mask (mover_planes gives its footprints).  None: byte for byte
