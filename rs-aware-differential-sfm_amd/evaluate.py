@@ -225,7 +225,7 @@ def evaluate_real_sequence(solver, frames, camera="galaxy", gamma=0.95, out_dir=
                            check_flow=False, trajectory=False, link_tol=None, min_links=None, fuse=False, fuse_tol=None, stabilize=False, smooth_sigma=None,
                            smooth_translation=True, fill=0, crop=False, crop_margin=None, crop_max_empty=0, blend=False, blend_feather=None,
                            blend_gain=True, inpaint=False, last_frame=False, occlusion=False, occlusion_tol=None, occlusion_search=False, retime=None,
-                           shutter=None, denoise=None, superres=None, plate=None, erase=None, plate_estimator=None, deblur=None):
+                           shutter=None, denoise=None, superres=None, plate=None, erase=None, plate_estimator=None, deblur=None, sharpen=None):
     """evaluate_real_run's real-world branch (main.cc:341-361, 364-531) for a clip: `frames` is <prefix>frame1.png ... frameN.png (the
     prefix, or a list of paths), or the frames themselves (an (N, rows, cols[, 3]) uint8 array or a list of arrays; 2-D frames are gray).
     By default ONE call does the clip (Solver.rectify_video_dev): the batched DeepFlow of every consecutive pair, the pipelined solve of every pair p
@@ -358,7 +358,22 @@ def evaluate_real_sequence(solver, frames, camera="galaxy", gamma=0.95, out_dir=
     deblurred_<p>.png and deblur.csv.  deblur=(K, strength, band_rows): a factor per band of band_rows rows (a multiple of 16) and not per frame,
     for frames whose blur varies down the rows (tests/deblur_bands_spec_numpy.py); deblur_taus is then the largest of a neighbour's band factors,
     the dict also has deblur_band_taus ((frames, 6, NB) int32) and deblur.csv one column per neighbour and band behind the existing ones.  Without
-    the third element, and without the keyword, every key and file is what it was."""
+    the third element, and without the keyword, every key and file is what it was.
+    sharpen=True, amount_q4 or (amount_q4, coring_q4[, overshoot]) (needs stabilize=True: ValueError otherwise): behind EVERYTHING else, one stream of
+    frames once more through the noise-gated unsharp mask (rsdsfm_sharpen.sharpen_video_dev, tests/sharpen_spec_numpy.py: every frame's own noise
+    curve measured, the detail cored below the strength it asks for per pixel, the result limited to the local range; True: amount 16, coring 8,
+    overshoot 0).  The stream is chosen by fixed priority: the super-resolved frames if superres was given, else the deblurred, else the denoised,
+    else the most complete stabilised frames the run produced (inpainted, blended, cropped, filled, stabilized), under that stream's masks.  The
+    returned dict also has sharpened (a list of frames), sharpen_counts ((frames, 4) int64: [unset, kept, sharpened, limited]), sharpen_curves
+    ((frames, 9, 4) int64) and sharpen_source (the key it read); out_dir receives sharpened_<p>.png and sharpen.csv (pair, the counts, noise_m,
+    strength_min, strength_max).  Without the keyword every key, file and byte is what it was."""
+    if sharpen is False:
+        sharpen = None
+    if sharpen is not None and not stabilize:
+        raise ValueError("sharpen needs stabilize=True: it sharpens the frames the stages behind the stabiliser produced")
+    if sharpen is not None:
+        sh_amount, sh_coring, sh_overshoot = (None, None, None) if sharpen is True else (int(sharpen), None, None) if np.ndim(sharpen) == 0 else \
+            (int(sharpen[0]), int(sharpen[1]), int(sharpen[2]) if len(sharpen) > 2 else None)
     if plate_estimator is not None and plate_estimator not in ("median", "medoid"):
         raise ValueError("plate_estimator is None, 'median' or 'medoid'")
     if plate_estimator is not None and plate is None and erase in (None, False):
@@ -782,6 +797,31 @@ def evaluate_real_sequence(solver, frames, camera="galaxy", gamma=0.95, out_dir=
                     traj.update(deblurred=[t.cpu().numpy() for t in d_db], deblur_counts=db["counts"], deblur_taus=db["taus"])
                     if db_band_rows:
                         traj.update(deblur_band_taus=db["band_taus"])
+                if sharpen is not None:  # one stream of frames once more, sharpened at every frame's own noise curve: behind everything else
+                    import rsdsfm_sharpen as shp  # a module beside the import shim: the package's surface is pinned
+
+                    if superres is not None:
+                        sh_source, d_shin, d_shmask = "superres", d_sr, d_srmasks
+                    elif deblur is not None:
+                        sh_source, d_shin, d_shmask = "deblurred", d_db, d_dbmasks
+                    elif denoise is not None:
+                        sh_source, d_shin, d_shmask = "stab_denoised", d_dn, d_dnmasks
+                    elif inpaint:
+                        sh_source, d_shin, d_shmask = "stab_inpainted", d_inps, d_isrcs  # a source id is 0 exactly where nothing is
+                    elif blend:
+                        sh_source, d_shin, d_shmask = "stab_blended", d_blends, d_bmasks
+                    elif crop:
+                        sh_source, d_shin, d_shmask = "stab_cropped", d_crops, d_cmasks
+                    elif fill:
+                        sh_source, d_shin, d_shmask = "stab_filled", d_fills, d_fmasks2
+                    else:
+                        sh_source, d_shin, d_shmask = "stabilized", d_stabs, d_smasks
+                    d_shout = [torch.empty_like(t) for t in d_shin]
+                    torch.cuda.synchronize()
+                    shr = shp.sharpen_video_dev(solver, ptrs(d_shin), ptrs(d_shmask), channels, int(d_shin[0].shape[0]), int(d_shin[0].shape[1]), ptrs(d_shout),
+                                                amount_q4=sh_amount, coring_q4=sh_coring, overshoot=sh_overshoot)
+                    traj.update(sharpened=[t.cpu().numpy() for t in d_shout], sharpen_counts=shr["counts"], sharpen_curves=shr["curves"].astype(np.int64),
+                                sharpen_source=sh_source)
     if out_dir:
         os.makedirs(out_dir, exist_ok=True)
         lines = ["pair,v_x,v_y,v_z,w_x,w_y,w_z,k,inliers"]
@@ -924,6 +964,17 @@ def evaluate_real_sequence(solver, frames, camera="galaxy", gamma=0.95, out_dir=
                 rows_.append(",".join([str(p)] + [str(int(x)) for x in traj["deblur_counts"][p]] + [str(int(x)) for x in traj["deblur_taus"][p]] +
                                       ([str(int(x)) for x in bt[p].reshape(-1)] if bt is not None else [])))
             with open(os.path.join(out_dir, "deblur.csv"), "w") as fh:
+                fh.write("\n".join(rows_) + "\n")
+        if sharpen is not None:
+            import rsdsfm_noise_curve as nc
+
+            rows_ = ["pair,unset,kept,sharpened,limited,noise_m,strength_min,strength_max"]
+            for p in range(len(traj["sharpened"])):
+                formats.write_png(os.path.join(out_dir, "sharpened_%d.png" % p), traj["sharpened"][p])
+                lut = nc.noise_curve_strengths(traj["sharpen_curves"][p].astype(np.uint64))  # the table the kernel formed (the defaults)
+                rows_.append(",".join([str(p)] + [str(int(x)) for x in traj["sharpen_counts"][p]] + [str(int(traj["sharpen_curves"][p][8, 1])), str(int(lut.min())),
+                                                                                                      str(int(lut.max()))]))
+            with open(os.path.join(out_dir, "sharpen.csv"), "w") as fh:
                 fh.write("\n".join(rows_) + "\n")
         if inpaint:
             rows_ = ["pair,stage,inpainted"]
