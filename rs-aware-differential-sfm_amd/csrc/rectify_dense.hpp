@@ -35,6 +35,8 @@ struct DenseWs {
     unsigned char* d_denoise_spatial = nullptr; // the spatial top-up's frame call: the temporal stage's weight and image, 4 planes (denoise.hpp; made when first asked for)
     unsigned char* d_noise = nullptr; // the noise level's histogram (1024 uint32) and a record (4 uint64) for the auto frame call (noise.hpp; made when first asked for)
     unsigned char* d_noise_curve = nullptr; // the noise curve's histogram (8 x 1024 uint32) and a curve (36 uint64) for the curve frame call (noise_curve.hpp; made when first asked for)
+    unsigned char* d_noise_temporal = nullptr; // the temporal noise curve's frame call: the neighbours' records and the stack of their layers (noise_temporal.hpp; made when first asked for)
+    size_t noise_temporal_bytes = 0;           // the bytes d_noise_temporal holds
     int rows = 0, cols = 0;
 };
 

@@ -45,6 +45,9 @@ static void dense_ws_free(DenseWs* w) {
     w->d_noise = nullptr;
     if (w->d_noise_curve) (void)hipFree(w->d_noise_curve);
     w->d_noise_curve = nullptr;
+    if (w->d_noise_temporal) (void)hipFree(w->d_noise_temporal);
+    w->d_noise_temporal = nullptr;
+    w->noise_temporal_bytes = 0;
     w->d_pyr = nullptr;
     w->d_disp = nullptr;
     w->d_mask = nullptr;

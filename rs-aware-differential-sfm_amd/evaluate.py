@@ -324,8 +324,11 @@ def evaluate_real_sequence(solver, frames, camera="galaxy", gamma=0.95, out_dir=
     denoise=(K, "curve") or (K, "curve", spatial): the strength of both stages PER PIXEL from every frame's own noise curve, measured per
     brightness band on the device behind the frame's own render (rsdsfm_noise_curve.denoise_curve_video_dev, tests/noise_curve_spec_numpy.py): the
     returned dict also has denoise_curve ((frames, 9, 4) int64: [n, m, sigma_q8, 0] of the eight bands, then of all samples), and
-    denoise.csv eleven more columns (noise_m0 .. noise_m7, noise_m, and strength_min, strength_max: the ends of the frame's strength table).  Any
-    other string is a ValueError.
+    denoise.csv eleven more columns (noise_m0 .. noise_m7, noise_m, and strength_min, strength_max: the ends of the frame's strength table).
+    denoise=(K, "temporal") or (K, "temporal", spatial): as "curve", with the curve measured from the differences to the frame's registered
+    neighbours in place of the frame's own render, so that a textured frame is not taken for a noisy one
+    (rsdsfm_noise_temporal.denoise_temporal_video_dev, tests/noise_temporal_spec_numpy.py): the same keys and the same columns.  Any other
+    string is a ValueError.
     superres=scale or (scale, K) (needs stabilize=True: ValueError otherwise): behind everything else, every stabilised frame once more on a grid
     `scale` times finer (1 .. 4), merged from itself and its K neighbours on either side (1 .. 7, default 2), each rendered alone into the frame's
     camera on the SMOOTHED path (Solver.superres_video_dev, tests/superres_spec_numpy.py; the fused maps with fuse=True): the returned dict also
@@ -702,7 +705,8 @@ def evaluate_real_sequence(solver, frames, camera="galaxy", gamma=0.95, out_dir=
                 if denoise is not None:  # every stabilised frame once more, averaged with its neighbours
                     dn_one = not isinstance(denoise, (tuple, list, np.ndarray))  # K alone; (K, strength, (target, search)) is ragged: no np.ndim
                     dn_auto = not dn_one and isinstance(denoise[1], str)  # (K, "auto"[, spatial]): the strength from every frame's own noise
-                    dn_curve = dn_auto and denoise[1] == "curve"  # (K, "curve"[, spatial]): a strength per pixel from every frame's own noise curve
+                    dn_temporal = dn_auto and denoise[1] == "temporal"  # (K, "temporal"[, spatial]): the curve measured from the registered neighbours
+                    dn_curve = dn_auto and (denoise[1] == "curve" or dn_temporal)  # (K, "curve"[, spatial]): a strength per pixel from every frame's own noise curve
                     dn_auto = dn_auto and not dn_curve
                     if dn_auto and denoise[1] != "auto":
                         raise ValueError("denoise: the strength is an integer, None or \"auto\"")
@@ -733,9 +737,14 @@ def evaluate_real_sequence(solver, frames, camera="galaxy", gamma=0.95, out_dir=
                         sp_target, sp_search = (None, None) if dn_spatial is None or dn_spatial is True else (int(dn_spatial[0]), int(dn_spatial[1]))
                         d_dns = [torch.empty((rows, cols), dtype=torch.uint8, device=dev) for _ in range(nst)] if dn_spatial is not None else None
                         torch.cuda.synchronize()
-                        dn = nc.denoise_curve_video_dev(solver, ptrs(d_imgs), rows, cols, channels, K, ptrs(d_src[:nst]), ptrs(d_Rs[:nst]), ptrs(d_ts[:nst]), traj["A"], traj["c"],
-                                                        A_s, c_s, st_scales, ptrs(d_dn), ptrs(d_dnmasks), ptrs(d_dnw), ptrs(d_dns) if d_dns else None,
-                                                        spatial=dn_spatial is not None, target=sp_target, search=sp_search, **dn_kw)
+                        dn_call = nc.denoise_curve_video_dev
+                        if dn_temporal:  # the same arguments, keys and files; the curve comes from the differences to the registered neighbours
+                            import rsdsfm_noise_temporal as nt
+
+                            dn_call = nt.denoise_temporal_video_dev
+                        dn = dn_call(solver, ptrs(d_imgs), rows, cols, channels, K, ptrs(d_src[:nst]), ptrs(d_Rs[:nst]), ptrs(d_ts[:nst]), traj["A"], traj["c"], A_s, c_s, st_scales,
+                                     ptrs(d_dn), ptrs(d_dnmasks), ptrs(d_dnw), ptrs(d_dns) if d_dns else None, spatial=dn_spatial is not None, target=sp_target, search=sp_search,
+                                     **dn_kw)
                         curves = dn["curves"].astype(np.int64)  # (frames, 9, 4): [n, m, sigma_q8, 0] per band, then of all samples
                         traj.update(stab_denoised=[t.cpu().numpy() for t in d_dn], denoise_masks=[t.cpu().numpy() for t in d_dnmasks],
                                     denoise_weights=[t.cpu().numpy() for t in d_dnw], denoise_counts=dn["counts"][:, :3].copy(), denoise_curve=curves)
