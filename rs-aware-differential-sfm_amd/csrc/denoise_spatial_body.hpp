@@ -1,10 +1,14 @@
 // denoise_spatial_body.hpp -- the body of the spatial top-up's kernels, included INSIDE the braces of denoise_spatial_kernel<CH, S>
-// (denoise_spatial_kernels.hip) and of denoise_spatial_auto_kernel<CH, S> (noise_kernels.hip); no include guard, no namespace.  A text and not a
-// __forceinline__ function, as deblur_sharpness_body.hpp is and for its reason: as a function the compiler orders the instructions of
-// denoise_spatial_kernel differently from the kernel that carried this code itself, and that kernel is to stay what it was.  Names it takes from
-// the kernel: CH, S; image, mask, weight, rows, cols, strength, target, out, support, counts.  out and support (may be NULL) are written whole;
-// counts[0 .. 2] (may be NULL) += [unset, kept, smoothed].  weight == NULL: n = 16 where the mask is set.  Described in
-// denoise_spatial_kernels.hip's header; SpatialLds, kSetBit and pair_entry are denoise_spatial_device.hpp's.
+// (denoise_spatial_kernels.hip), of denoise_spatial_auto_kernel<CH, S> (noise_kernels.hip) and of denoise_spatial_curve_kernel<CH, S>
+// (noise_curve_kernels.hip); no include guard, no namespace.  A text and not a __forceinline__ function, as deblur_sharpness_body.hpp is and for
+// its reason: as a function the compiler orders the instructions of denoise_spatial_kernel differently from the kernel that carried this code
+// itself, and that kernel is to stay what it was.  Names it takes from the kernel: CH, S; image, mask, weight, rows, cols, target, out, support,
+// counts, and the divisor's strength through two macros, which this text undefines at its end:
+//   RSDSFM_SPATIAL_HN_SETUP   statements behind the fill of the tile (pk[0 .. 3], the thread's packed centre pixels, are in scope) that declare hn
+//   RSDSFM_SPATIAL_HN(j)      the strength of the thread's pixel j, times CH
+// (the launch's one strength: `const unsigned hn = strength * (unsigned)CH;` and `hn`; a strength per pixel: hn[4] and `hn[j]`).  out and support
+// (may be NULL) are written whole; counts[0 .. 2] (may be NULL) += [unset, kept, smoothed].  weight == NULL: n = 16 where the mask is set.
+// Described in denoise_spatial_kernels.hip's header; SpatialLds, kSetBit and pair_entry are denoise_spatial_device.hpp's.
     using L = SpatialLds<S>;
     __shared__ __attribute__((aligned(16))) unsigned s_img[L::kWords];
     __shared__ __attribute__((aligned(16))) unsigned s_e[2][kTileLdsWords];
@@ -85,7 +89,7 @@
         const bool is_halo = t.tid < kTileHalo;
         const TileHalo h = tile_halo(t);
         const int halo_e = h.ly * kTileLdsStride + h.lx, halo_i = (h.ly + S) * L::kStride + h.lx + S + 1;
-        const unsigned hn = strength * (unsigned)CH;
+        RSDSFM_SPATIAL_HN_SETUP
         int buf = 0;
 #pragma unroll 1
         for (int dy = -S; dy <= S; ++dy) {
@@ -116,7 +120,7 @@
                     for (int j = 0; j < 4; ++j) {
                         if (ent[j]) {  // p and q both set: the patch counts at least o = 0
                             const unsigned s = col[j] + col[j + 1] + col[j + 2];
-                            const unsigned qd = (kDenoiseW * (s & 0xffffu)) / (hn * (s >> 16));
+                            const unsigned qd = (kDenoiseW * (s & 0xffffu)) / (RSDSFM_SPATIAL_HN(j) * (s >> 16));
                             const unsigned w = kDenoiseW - (qd > kDenoiseW ? kDenoiseW : qd);
                             const unsigned q = win[j + dx + S];
                             sw[j] += w;
@@ -165,3 +169,5 @@
         store_group<CH>(out, ow, planes, words, p0, nin);
     }
     block_counts_add<3>(n3, counts);
+#undef RSDSFM_SPATIAL_HN_SETUP
+#undef RSDSFM_SPATIAL_HN

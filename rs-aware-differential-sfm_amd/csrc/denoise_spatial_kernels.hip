@@ -40,6 +40,8 @@ __global__ __launch_bounds__(kBP) void denoise_spatial_kernel(const unsigned cha
                                                              const unsigned char* __restrict__ weight, int rows, int cols, unsigned strength, unsigned target,
                                                              unsigned char* __restrict__ out, unsigned char* __restrict__ support,
                                                              unsigned long long* __restrict__ counts) {
+#define RSDSFM_SPATIAL_HN_SETUP const unsigned hn = strength * (unsigned)CH;
+#define RSDSFM_SPATIAL_HN(j) hn
 #include "denoise_spatial_body.hpp"
 }
 

@@ -53,6 +53,12 @@ inline unsigned noise_curve_entry(const unsigned long long* curve, unsigned scal
     return h < 1ull ? 1u : h > 255ull ? 255u : (unsigned)h;
 }
 
+// the curve's words and its parameter struct (noise_curve_host.hip; the temporal noise curve's frame and clip calls take the same struct): every
+// 0 replaced by its default; false: outside its range, or a wrong struct_bytes (kCurveParamsMessage)
+bool curve_words_resolve(int32_t* scale, int64_t* min_samples, int64_t* band_min_samples);
+bool curve_params_resolve(const rsdsfm_noise_curve_params* in, rsdsfm_noise_curve_params* out);
+extern const char* const kCurveParamsMessage;
+
 // on c->stream (arguments checked and defaults resolved by the caller): the histogram zeroed by a memset, then the two launches
 int noise_curve_launch(Ctx* c, const unsigned char* d_image, const unsigned char* d_mask, int channels, int rows, int cols, int quantile, unsigned* d_hist,
                        unsigned long long* d_curve);

@@ -15,9 +15,10 @@
 //                                 each of the 256 threads forms one entry of the strength table in LDS (noise_curve_entry, noise_curve.hpp: the
 //                                 nine rows by uniform loads, validity and mfill in a loop over the eight bands, the interpolation); one
 //                                 barrier; then the accumulate's and the top-up's bodies with the divisor's strength replaced by the entry at
-//                                 the level of each of the thread's four pixels.  The bodies are texts of their OWN (below, and
-//                                 denoise_spatial_curve_body.hpp): denoise_device.hpp and denoise_spatial_body.hpp are not touched, so the
-//                                 existing kernels stay the code they are.
+//                                 the level of each of the thread's four pixels.  The bodies are the ONE text each that the fixed-strength and
+//                                 the auto kernels run, denoise_accumulate_body.hpp and denoise_spatial_body.hpp, included texts that take the
+//                                 strength through two macros each.  Every kernel compiles to the code it was
+//                                 (profiles/estimated_strength_isa.txt).
 #include "denoise.hpp"
 #include "denoise_spatial_device.hpp"
 #include "image_tile_device.hpp"
@@ -52,6 +53,14 @@ __device__ __forceinline__ unsigned curve_level(unsigned packed) {
 __device__ __forceinline__ void curve_table(unsigned char* s_lut, const unsigned long long* __restrict__ curve36, unsigned scale, unsigned fallback, long long min_samples,
                                             long long band_min_samples) {
     s_lut[threadIdx.x] = (unsigned char)noise_curve_entry(curve36, scale, fallback, min_samples, band_min_samples, (int)threadIdx.x);
+}
+
+// the table's entry at the level of the thread's reference pixel j (rw: its packed bytes); >= 1
+template <int CH>
+__device__ __forceinline__ unsigned curve_strength(const unsigned char* s_lut, const unsigned* rw, int j) {
+    unsigned lvl = byte_of(rw, CH * j);
+    if constexpr (CH == 3) lvl = third(lvl + byte_of(rw, CH * j + 1) + byte_of(rw, CH * j + 2) + 1u);
+    return s_lut[lvl];
 }
 
 }  // namespace
@@ -225,9 +234,8 @@ __global__ __launch_bounds__(kBP) void noise_curve_resolve_kernel(const unsigned
     }
 }
 
-// denoise_accumulate_auto_kernel's arguments (noise_kernels.hip) with the curve in the record's place and band_min_samples behind min_samples.
-// The body is denoise_accumulate_body's text (denoise_device.hpp) with ONE difference: stage 2's divisor takes the strength of pixel j from the
-// table at the level of the reference pixel, where that body has the launch's one strength.
+// denoise_accumulate_auto_kernel's arguments (noise_kernels.hip) with the curve in the record's place and band_min_samples behind min_samples:
+// denoise_accumulate_body.hpp's text with the strength of pixel j from the table, where the other two kernels have the launch's one
 template <int CH, bool FIRST, bool LAST>
 __global__ __launch_bounds__(kBP) void denoise_accumulate_curve_kernel(const unsigned char* __restrict__ ref, const unsigned char* __restrict__ rmask,
                                                                       const unsigned char* __restrict__ layer, const unsigned char* __restrict__ lmask, int rows,
@@ -236,143 +244,10 @@ __global__ __launch_bounds__(kBP) void denoise_accumulate_curve_kernel(const uns
                                                                       long long min_samples, long long band_min_samples, unsigned short* __restrict__ cells,
                                                                       unsigned char* __restrict__ out, unsigned char* __restrict__ mask_out,
                                                                       unsigned char* __restrict__ weight, unsigned long long* __restrict__ counts) {
-    constexpr int H = CH + 1;     // halfwords per cell
-    constexpr int NW = 4 * H / 2; // dwords of a thread's four cells: 8 (BGR) or 4 (gray)
-    __shared__ __attribute__((aligned(16))) unsigned s_tile[kTileLdsWords];
-    __shared__ unsigned s_gain[CH];
     __shared__ unsigned char s_lut[256];
-    const bool has_layer = layer != nullptr;  // (uniform)
-    const TileThread t = tile_thread(rows, cols);
-    const int nin = t.nin;
-    const int64_t p0 = t.p0, npix = (int64_t)rows * cols;
-    const unsigned inside = first_ones(nin);
-
-    unsigned mr = 0u, v = 0u, rw[CH], kk[4][CH], wgt[4] = {0u, 0u, 0u, 0u};
-#pragma unroll
-    for (int d = 0; d < CH; ++d) rw[d] = 0u;
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-        for (int c = 0; c < CH; ++c) kk[j][c] = 0u;
-
-    if (nin) {  // the mask dwords first
-        unsigned w1[1];
-        load_bytes<1>(rmask, p0, npix, w1);
-        mr = bytes_set(w1[0]) & inside;
-        if (has_layer && mr) {
-            load_bytes<1>(lmask, p0, npix, w1);
-            v = bytes_set(w1[0]) & mr;
-        }
-        if (FIRST ? mr != 0u : v != 0u) load_bytes<CH>(ref, (int64_t)CH * p0, (int64_t)CH * npix, rw);  // image bytes under an empty mask are not read
-    }
-
-    if (has_layer) {
-        curve_table(s_lut, curve36, scale, fallback, min_samples, band_min_samples);  // without a layer no weight is formed: no table
-        if (t.tid < CH) s_gain[t.tid] = sums ? seam_gain(sums, CH, t.tid, min_overlap, gain_mode) : kGainOne;
-        __syncthreads();
-        unsigned G[CH];
-#pragma unroll
-        for (int c = 0; c < CH; ++c) G[c] = s_gain[c];
-        // stage 1: the thread's own four pixels
-        unsigned ent[4] = {0u, 0u, 0u, 0u};
-        if (v) {
-            unsigned lw[CH];
-            load_bytes<CH>(layer, (int64_t)CH * p0, (int64_t)CH * npix, lw);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                unsigned e = 0u;
-#pragma unroll
-                for (int c = 0; c < CH; ++c) {
-                    kk[j][c] = gained(G[c], byte_of(lw, CH * j + c));
-                    e += absdiff(byte_of(rw, CH * j + c), kk[j][c]);
-                }
-                ent[j] = ((v >> (8 * j)) & 1u) ? (0x10000u | e) : 0u;
-            }
-        }
-        unsigned* row = tile_own(s_tile, t);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) row[j] = ent[j];
-        if (t.tid < kTileHalo) {
-            const TileHalo h = tile_halo(t);
-            unsigned e = 0u;
-            if (h.hy >= 0 && h.hy < rows && h.hx >= 0 && h.hx < cols) {
-                const int64_t p = (int64_t)h.hy * cols + h.hx;
-                if (rmask[p] != 0 && lmask[p] != 0) {
-                    e = 0x10000u;
-#pragma unroll
-                    for (int c = 0; c < CH; ++c) e += absdiff(ref[CH * p + c], gained(G[c], layer[CH * p + c]));
-                }
-            }
-            s_tile[h.ly * kTileLdsStride + h.lx] = e;
-        }
-        __syncthreads();
-        // stage 2: the 3 x 3 sums of the packed dwords; the strength of pixel j is the table's entry at the level of R(p_j)
-        if (v) {
-            unsigned col[6];
-            tile_sum3x3(s_tile, t.ty, t.g, col);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const unsigned s = col[j] + col[j + 1] + col[j + 2];
-                const unsigned D = s & 0xffffu, cnt = s >> 16;
-                if ((v >> (8 * j)) & 1u) {  // the pixel itself counts: cnt >= 1
-                    unsigned lvl = byte_of(rw, CH * j);
-                    if constexpr (CH == 3) lvl = third(lvl + byte_of(rw, CH * j + 1) + byte_of(rw, CH * j + 2) + 1u);
-                    const unsigned strength = s_lut[lvl];  // >= 1
-                    const unsigned qd = (kDenoiseW * D) / (strength * (unsigned)CH * cnt);
-                    wgt[j] = kDenoiseW - (qd > kDenoiseW ? kDenoiseW : qd);
-                }
-            }
-        }
-    }
-
-    unsigned n3[3] = {0u, 0u, 0u};  // [unset, own only, averaged]; at most 4 per thread
-    const bool any_w = (wgt[0] | wgt[1] | wgt[2] | wgt[3]) != 0u;
-    if (nin && (FIRST || LAST || any_w)) {  // a mid step that adds nothing neither reads nor writes its cells
-        unsigned cw[NW];
-#pragma unroll
-        for (int i = 0; i < NW; ++i) cw[i] = 0u;
-        const bool wide = cells_wide<CH>(nin, p0);
-        unsigned short* cell0 = (FIRST && LAST) ? nullptr : cells + (int64_t)H * p0;
-        if (!FIRST) cells_load<CH>(cell0, nin, wide, cw);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            unsigned add[H];
-            const unsigned own = FIRST ? ((mr >> (8 * j)) & 1u) * kDenoiseW : 0u;
-#pragma unroll
-            for (int c = 0; c < CH; ++c) add[c] = own * byte_of(rw, CH * j + c) + wgt[j] * kk[j][c];
-            add[CH] = own + wgt[j];
-#pragma unroll
-            for (int h = 0; h < H; ++h) cw[(H * j + h) >> 1] += add[h] << (16 * ((H * j + h) & 1));  // no halfword overflows: n <= 240, sums <= 61 200
-        }
-        if (!LAST) {
-            cells_store<CH>(cell0, nin, wide, cw);
-        } else {
-            unsigned ow[CH], mw = 0u, nw = 0u;
-#pragma unroll
-            for (int d = 0; d < CH; ++d) ow[d] = 0u;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const unsigned n = half_of(cw, H * j + CH);
-                const unsigned ok = n > 0u ? 1u : 0u, den = ok ? 2u * n : 1u;
-#pragma unroll
-                for (int c = 0; c < CH; ++c) {
-                    const unsigned val = ok ? (2u * half_of(cw, H * j + c) + n) / den : 0u;  // round half up; <= 255
-                    ow[(CH * j + c) >> 2] |= val << (8 * ((CH * j + c) & 3));
-                }
-                mw |= ok << (8 * j);
-                nw |= (n & 0xffu) << (8 * j);
-                if (j < nin) {
-                    n3[0] += 1u - ok;
-                    n3[1] += n == kDenoiseW ? 1u : 0u;
-                    n3[2] += n > kDenoiseW ? 1u : 0u;
-                }
-            }
-            unsigned char* const planes[2] = {mask_out, weight};
-            const unsigned words[2] = {mw, nw};
-            store_group<CH>(out, ow, planes, words, p0, nin);
-        }
-    }
-    if constexpr (LAST) block_counts_add<3>(n3, counts);
+#define RSDSFM_ACCUMULATE_TABLE curve_table(s_lut, curve36, scale, fallback, min_samples, band_min_samples);
+#define RSDSFM_ACCUMULATE_STRENGTH(j) curve_strength<CH>(s_lut, rw, j)
+#include "denoise_accumulate_body.hpp"
 }
 
 // denoise_spatial_auto_kernel's arguments (noise_kernels.hip) in the same way
@@ -385,7 +260,12 @@ __global__ __launch_bounds__(kBP) void denoise_spatial_curve_kernel(const unsign
     __shared__ unsigned char s_lut[256];
     curve_table(s_lut, curve36, scale, fallback, min_samples, band_min_samples);
     __syncthreads();
-#include "denoise_spatial_curve_body.hpp"
+// the strength at the level of each of the thread's four centre pixels, times CH
+#define RSDSFM_SPATIAL_HN_SETUP \
+    unsigned hn[4];             \
+    _Pragma("unroll") for (int j = 0; j < 4; ++j) hn[j] = (unsigned)s_lut[curve_level<CH>(pk[j])] * (unsigned)CH;
+#define RSDSFM_SPATIAL_HN(j) hn[j]
+#include "denoise_spatial_body.hpp"
 }
 
 // ---------------------------------------------------------------------------------------------------

@@ -1,12 +1,11 @@
 // noise_host.hip -- C ABI of the noise level (include/rsdsfm_noise.h; tests/noise_spec_numpy.py is the definition, noise_kernels.hip the
 // kernels): the primitive, the strength on the host, the accumulate and the top-up with the strength from a record, the frame call, which
 // CALLS the public entry points one after another on planes of the context's dense workspace as rsdsfm_denoise_frame_dev does, and the clip
-// call, which calls the frame call per frame (walk_clip, clip_stage_host.hpp).
-#include <string>
-#include <vector>
-
+// call, which calls the frame call per frame.
+// The frame call's front and tail and the clip call are denoise_estimated_host.hpp's; what stands here is the estimator's own.
 #include "clip_stage_host.hpp"
 #include "denoise.hpp"
+#include "denoise_estimated_host.hpp"
 #include "noise.hpp"
 #include "rectify_dense.hpp"
 #include "rsdsfm_internal.hpp"
@@ -40,29 +39,46 @@ const char* const kNoiseWordsMessage = "scale must be in [1, 255] (0: the defaul
 const char* const kNoiseParamsMessage =
     "rsdsfm_noise_params: quantile_q8 in [1, 256] or 0, scale in [1, 255] or 0, min_samples >= 0, struct_bytes 0 or sizeof (use rsdsfm_noise_params_init)";
 
-// what the primitive refuses about its planes, or NULL
-const char* noise_planes_refusal(const uint8_t* d_image, const uint8_t* d_mask, int channels, int rows, int cols, const uint32_t* d_hist, const uint64_t* d_record) {
-    if (!frame_size_ok(rows, cols)) return "rows and cols must be in [2, 16384]";
-    if (channels != 1 && channels != 3) return "channels must be 1 or 3";
-    if (!d_image || !d_mask || !d_hist || !d_record) return "null device pointer";
-    if (((uintptr_t)d_image | (uintptr_t)d_mask | (uintptr_t)d_hist) & 3u) return "the planes and the histogram must be 4-byte aligned";
-    if ((uintptr_t)d_record & 7u) return "the record must be 8-byte aligned";
-    const void *h = d_hist, *r = d_record;
-    if (h == (const void*)d_image || h == (const void*)d_mask || r == (const void*)d_image || r == (const void*)d_mask) return "an output may not be an input";
-    if (h == r) return "the outputs must be distinct";
-    return nullptr;
+// the auto frame call behind the public function's guard; the clip call runs it per frame
+int auto_frame(rsdsfm_ctx* ctx, const EstimatedFrame& a, const rsdsfm_noise_params* noise_or_null) {
+    Ctx* c = &ctx->c;
+    const char* const stage = "denoise auto frame";
+    rsdsfm_noise_params np;
+    // resolved here, reported by estimated_checks at its place in the order of checks: np is good only once that call has returned RSDSFM_OK
+    const char* const refusal = noise_params_resolve(noise_or_null, &np) ? nullptr : kNoiseParamsMessage;
+    NoisePlanes nz{nullptr, nullptr};
+    EstimatedFront f{};
+    int rc = estimated_checks(ctx, stage, "noise record", a, refusal, &f);
+    if (rc == RSDSFM_OK) rc = ensure_plane(c, &f.ws->d_layer, blend_layer_bytes(a.rows, a.cols), "denoise auto frame: no memory for the layer");
+    if (rc == RSDSFM_OK) rc = ensure_plane(c, &f.ws->d_denoise, denoise_ws_bytes(a.rows, a.cols), "denoise auto frame: no memory for the reference planes and the cells");
+    if (rc == RSDSFM_OK) rc = ensure_plane(c, &f.ws->d_noise, noise_ws_bytes(), "denoise auto frame: no memory for the histogram and the record");
+    if (rc == RSDSFM_OK) nz = noise_planes(f.ws->d_noise);
+    if (rc == RSDSFM_OK) rc = estimated_render(ctx, stage, a, nz.record, &f);
+    if (rc != RSDSFM_OK) return rc;
+    const DenoisePlanes& r = f.r;
+    const BlendLayer l = blend_layer(f.ws->d_layer, a.rows, a.cols);
+    // measure, then accumulate per neighbour
+    rc = rsdsfm_noise_level_dev(ctx, r.rimage, r.rmask, a.channels, a.rows, a.cols, np.quantile_q8, nz.hist, f.d_estimate);  // behind the render: the noise the weights compare
+    if (rc != RSDSFM_OK) return rc;
+    if (a.nsrc == 1) {
+        rc = rsdsfm_denoise_accumulate_auto_dev(ctx, r.rimage, r.rmask, nullptr, nullptr, a.channels, a.rows, a.cols, nullptr, f.dp.min_overlap, f.dp.gain_mode, f.dp.strength,
+                                                f.d_estimate, np.scale, np.min_samples, nullptr, 1, 1, f.d_image, a.d_mask_out, f.d_weight, a.d_counts6_or_null);
+        if (rc != RSDSFM_OK) return rc;
+    }
+    for (int k = 1; k < a.nsrc; ++k) {
+        rc = neighbour_step(ctx, "denoise auto frame: zeroing the layer failed", f.dp.occlusion == 1, f.dp.occlusion_tol_q16,
+                            source_view(a.d_images, a.d_depths_colmajor, a.d_R_rows9, a.d_t_rows3, k), f.g, a.M + 9 * k, a.m + 3 * k, f.window, r.rimage, r.rsource, l.image, l.mask,
+                            l.record);
+        if (rc != RSDSFM_OK) return rc;
+        rc = rsdsfm_denoise_accumulate_auto_dev(ctx, r.rimage, r.rmask, l.image, l.mask, a.channels, a.rows, a.cols, l.record, f.dp.min_overlap, f.dp.gain_mode, f.dp.strength,
+                                                f.d_estimate, np.scale, np.min_samples, r.cells, k == 1, k == a.nsrc - 1, f.d_image, a.d_mask_out, f.d_weight, a.d_counts6_or_null);
+        if (rc != RSDSFM_OK) return rc;
+    }
+    if (f.top_up)
+        return rsdsfm_denoise_spatial_auto_dev(ctx, f.d_image, a.d_mask_out, f.d_weight, a.channels, a.rows, a.cols, f.sp.strength, f.d_estimate, np.scale, np.min_samples, f.sp.target,
+                                               f.sp.search, a.d_image_out, a.d_support_or_null, f.d_counts3);
+    return estimated_tail(c, f);
 }
-
-// a record the auto calls read: given, 8-byte aligned, none of the outputs (NULL entries are skipped)
-const char* record_refusal(const uint64_t* d_noise4, std::initializer_list<const void*> outputs) {
-    if (!d_noise4) return "the noise record is NULL";
-    if ((uintptr_t)d_noise4 & 7u) return "the noise record must be 8-byte aligned";
-    for (const void* o : outputs)
-        if (o && o == (const void*)d_noise4) return "an output may not be the noise record";
-    return nullptr;
-}
-
-int noise_fail(Ctx* c, const char* stage, const char* what) { return fail(c, RSDSFM_ERR_INVALID, (std::string(stage) + ": " + what).c_str()); }
 
 }  // namespace
 }  // namespace rsdsfm
@@ -98,8 +114,9 @@ int rsdsfm_noise_level_dev(rsdsfm_ctx* ctx, const uint8_t* d_image, const uint8_
     if (!ctx) return RSDSFM_ERR_INVALID;
     Ctx* c = &ctx->c;
     DeviceGuard device_guard_(c);
-    if (!quantile_resolve(&quantile_q8)) return noise_fail(c, "noise level", "quantile_q8 must be in [1, 256] (0: the default, 128)");
-    if (const char* what = noise_planes_refusal(d_image, d_mask, channels, rows, cols, d_hist1024_out, d_record4_out)) return noise_fail(c, "noise level", what);
+    if (!quantile_resolve(&quantile_q8)) return stage_fail(c, "noise level", "quantile_q8 must be in [1, 256] (0: the default, 128)");
+    const int rc = measure_planes_check(c, "noise level", "record", d_image, d_mask, channels, rows, cols, d_hist1024_out, d_record4_out);
+    if (rc != RSDSFM_OK) return rc;
     return noise_level_launch(c, d_image, d_mask, channels, rows, cols, quantile_q8, d_hist1024_out, reinterpret_cast<unsigned long long*>(d_record4_out));
 }
 
@@ -113,9 +130,9 @@ int rsdsfm_denoise_accumulate_auto_dev(rsdsfm_ctx* ctx, const uint8_t* d_ref_ima
     DeviceGuard device_guard_(c);
     const char* const stage = "denoise auto accumulate";
     if (min_overlap < 0 || (gain_mode != 0 && gain_mode != 1) || strength < 0 || strength > kDenoiseStrengthMax)
-        return noise_fail(c, stage, "min_overlap must be >= 0, gain_mode 0 or 1 and strength in [1, 255] (0: the default, 12)");
-    if (!noise_words_resolve(&scale, &min_samples)) return noise_fail(c, stage, kNoiseWordsMessage);
-    if (!d_noise4) return noise_fail(c, stage, "the noise record is NULL");
+        return stage_fail(c, stage, "min_overlap must be >= 0, gain_mode 0 or 1 and strength in [1, 255] (0: the default, 12)");
+    if (!noise_words_resolve(&scale, &min_samples)) return stage_fail(c, stage, kNoiseWordsMessage);
+    if (!d_noise4) return stage_fail(c, stage, "the noise record is NULL");
     AccumulateOutputs out{d_image_out, d_mask_out, d_weight_or_null, d_counts3_or_null};
     const int rc = accumulate_check(c, "denoise auto", d_ref_image, d_ref_mask, d_layer_image_or_null, d_layer_mask_or_null, channels, rows, cols, d_cells_or_null,
                                     {d_sums8_or_null, d_noise4}, first, last, &out);
@@ -134,10 +151,11 @@ int rsdsfm_denoise_spatial_auto_dev(rsdsfm_ctx* ctx, const uint8_t* d_image, con
     DeviceGuard device_guard_(c);
     const char* const stage = "denoise spatial auto";
     if (!spatial_words_resolve(&strength, &target, &search)) return spatial_fail(c, stage, kSpatialWordsMessage);
-    if (!noise_words_resolve(&scale, &min_samples)) return noise_fail(c, stage, kNoiseWordsMessage);
+    if (!noise_words_resolve(&scale, &min_samples)) return stage_fail(c, stage, kNoiseWordsMessage);
     if (const char* what = spatial_planes_refusal(d_image, d_mask, d_weight_or_null, channels, rows, cols, d_image_out, d_support_or_null, d_counts3_or_null))
         return spatial_fail(c, stage, what);
-    if (const char* what = record_refusal(d_noise4, {d_image_out, d_support_or_null, d_counts3_or_null})) return noise_fail(c, stage, what);
+    const int rc = estimate_check(c, stage, "noise record", d_noise4, {d_image_out, d_support_or_null, d_counts3_or_null});
+    if (rc != RSDSFM_OK) return rc;
     return denoise_spatial_auto_launch(c, d_image, d_mask, d_weight_or_null, channels, rows, cols, strength, reinterpret_cast<const unsigned long long*>(d_noise4), scale,
                                        min_samples, target, search, d_image_out, d_support_or_null, d_counts3_or_null);
 }
@@ -149,80 +167,10 @@ int rsdsfm_denoise_auto_frame_dev(rsdsfm_ctx* ctx, const uint8_t* const* d_image
                                   uint8_t* d_image_out, uint8_t* d_mask_out, uint8_t* d_weight_or_null, uint8_t* d_support_or_null, int64_t* d_counts6_or_null,
                                   uint64_t* d_noise4_or_null) {
     if (!ctx) return RSDSFM_ERR_INVALID;
-    Ctx* c = &ctx->c;
-    DeviceGuard device_guard_(c);
-    const char* const stage = "denoise auto frame";
-    int rc = rectify_dense_check(c, channels, rows, cols, mode, q5_mode, iterations);
-    if (rc != RSDSFM_OK) return rc;
-    if (nsrc < 1 || nsrc > kDenoiseSourcesMax) return noise_fail(c, stage, "nsrc must be in [1, 15]");
-    rsdsfm_denoise_params dp;
-    if (!denoise_params_resolve(params_or_null, &dp)) return fail(c, RSDSFM_ERR_INVALID, kDenoiseParamsMessage);
-    rsdsfm_noise_params np;
-    if (!noise_params_resolve(noise_or_null, &np)) return fail(c, RSDSFM_ERR_INVALID, kNoiseParamsMessage);
-    const bool top_up = spatial_or_null != nullptr;
-    rsdsfm_denoise_spatial_params sp;
-    if (!spatial_params_resolve(spatial_or_null, &sp)) return fail(c, RSDSFM_ERR_INVALID, kSpatialParamsMessage);
-    if (d_support_or_null && !top_up) return noise_fail(c, stage, "a support plane needs the top-up's parameters");
-    rc = frame_sources_check(c, stage, d_images, d_depths_colmajor, d_R_rows9, d_t_rows3, nsrc, {d_image_out, d_mask_out, d_weight_or_null, d_support_or_null});
-    if (rc == RSDSFM_OK) rc = frame_poses_check(c, stage, M, m, nsrc);
-    if (rc == RSDSFM_OK) rc = output_planes_check(c, stage, {d_image_out, d_mask_out, d_weight_or_null, d_support_or_null}, d_counts6_or_null, true);
-    if (rc != RSDSFM_OK) return rc;
-    if (d_noise4_or_null) {
-        if (const char* what = record_refusal(d_noise4_or_null, {d_image_out, d_mask_out, d_weight_or_null, d_support_or_null, d_counts6_or_null})) return noise_fail(c, stage, what);
-        for (int k = 0; k < nsrc; ++k) {  // the record is written behind the own render: nothing a later step reads may be it
-            const void* const in[4] = {d_images[k], d_depths_colmajor[k], d_R_rows9[k], d_t_rows3[k]};
-            for (const void* p : in)
-                if (p == (const void*)d_noise4_or_null) return noise_fail(c, stage, "null, misaligned or aliased source pointer");
-        }
-    }
-    int32_t full[4];
-    const int32_t* window = nullptr;
-    rc = frame_window(c, stage, window_or_null, rows, cols, full, &window);
-    if (rc != RSDSFM_OK) return rc;
-    DenseWs* ws = nullptr;
-    rc = rectify_dense_ws(c, rows, cols, &ws);  // a size change releases the planes with the rest
-    if (rc == RSDSFM_OK) rc = ensure_plane(c, &ws->d_layer, blend_layer_bytes(rows, cols), "denoise auto frame: no memory for the layer");
-    if (rc == RSDSFM_OK) rc = ensure_plane(c, &ws->d_denoise, denoise_ws_bytes(rows, cols), "denoise auto frame: no memory for the reference planes and the cells");
-    if (rc == RSDSFM_OK) rc = ensure_plane(c, &ws->d_noise, noise_ws_bytes(), "denoise auto frame: no memory for the histogram and the record");
-    if (rc == RSDSFM_OK && top_up)
-        rc = ensure_plane(c, &ws->d_denoise_spatial, denoise_spatial_ws_bytes(rows, cols), "denoise auto frame: no memory for the temporal stage's planes");
-    if (rc != RSDSFM_OK) return rc;
-    const RenderGeom g{channels, fx, fy, cx, cy, rows, cols, mode, q5_mode, iterations};
-    const DenoisePlanes r = denoise_planes(ws->d_denoise, rows, cols);
-    const BlendLayer l = blend_layer(ws->d_layer, rows, cols);
-    const NoisePlanes nz = noise_planes(ws->d_noise);
-    uint64_t* const d_record = d_noise4_or_null ? d_noise4_or_null : nz.record;
-    // the temporal stage's outputs: with the top-up its image (and its weight, when the caller has no plane for it) stay in the workspace
-    uint8_t* const d_weight = !top_up || d_weight_or_null ? d_weight_or_null : ws->d_denoise_spatial;
-    uint8_t* const d_image = top_up ? ws->d_denoise_spatial + blend_plane_bytes(rows, cols) : d_image_out;
-    int64_t* const d_counts3 = d_counts6_or_null ? d_counts6_or_null + 3 : nullptr;
-    // what the top-up would refuse, in front of anything enqueued
-    if (top_up)
-        if (const char* what = spatial_planes_refusal(d_image, d_mask_out, d_weight, channels, rows, cols, d_image_out, d_support_or_null, d_counts3)) return spatial_fail(c, stage, what);
-
-    // the public entry points themselves, so that they run the code they run alone
-    rc = render_reference(ctx, stage, source_view(d_images, d_depths_colmajor, d_R_rows9, d_t_rows3, 0), g, M, m, window, r.rimage, r.rmask, r.rsource);
-    if (rc != RSDSFM_OK) return rc;
-    rc = rsdsfm_noise_level_dev(ctx, r.rimage, r.rmask, channels, rows, cols, np.quantile_q8, nz.hist, d_record);  // behind the render: the noise the weights compare
-    if (rc != RSDSFM_OK) return rc;
-    if (nsrc == 1) {
-        rc = rsdsfm_denoise_accumulate_auto_dev(ctx, r.rimage, r.rmask, nullptr, nullptr, channels, rows, cols, nullptr, dp.min_overlap, dp.gain_mode, dp.strength, d_record,
-                                                np.scale, np.min_samples, nullptr, 1, 1, d_image, d_mask_out, d_weight, d_counts6_or_null);
-        if (rc != RSDSFM_OK) return rc;
-    }
-    for (int k = 1; k < nsrc; ++k) {
-        rc = neighbour_step(ctx, "denoise auto frame: zeroing the layer failed", dp.occlusion == 1, dp.occlusion_tol_q16,
-                            source_view(d_images, d_depths_colmajor, d_R_rows9, d_t_rows3, k), g, M + 9 * k, m + 3 * k, window, r.rimage, r.rsource, l.image, l.mask, l.record);
-        if (rc != RSDSFM_OK) return rc;
-        rc = rsdsfm_denoise_accumulate_auto_dev(ctx, r.rimage, r.rmask, l.image, l.mask, channels, rows, cols, l.record, dp.min_overlap, dp.gain_mode, dp.strength, d_record,
-                                                np.scale, np.min_samples, r.cells, k == 1, k == nsrc - 1, d_image, d_mask_out, d_weight, d_counts6_or_null);
-        if (rc != RSDSFM_OK) return rc;
-    }
-    if (top_up)
-        return rsdsfm_denoise_spatial_auto_dev(ctx, d_image, d_mask_out, d_weight, channels, rows, cols, sp.strength, d_record, np.scale, np.min_samples, sp.target, sp.search,
-                                               d_image_out, d_support_or_null, d_counts3);
-    if (d_counts3) RSDSFM_HIP_CHECK(c, hipMemsetAsync(d_counts3, 0, 3 * sizeof(int64_t), c->stream));  // no top-up: its three counters are 0
-    return RSDSFM_OK;
+    DeviceGuard device_guard_(&ctx->c);
+    return auto_frame(ctx, EstimatedFrame{d_images, channels, d_depths_colmajor, d_R_rows9, d_t_rows3, fx, fy, cx, cy, rows, cols, mode, q5_mode, iterations, nsrc, M, m, params_or_null,
+                                          spatial_or_null, window_or_null, d_image_out, d_mask_out, d_weight_or_null, d_support_or_null, d_counts6_or_null, d_noise4_or_null},
+                      noise_or_null);
 }
 
 int rsdsfm_denoise_auto_video_dev(rsdsfm_ctx* ctx, const uint8_t* const* d_frames, int32_t nsources, int32_t rows, int32_t cols, int32_t channels, double fx, double fy,
@@ -233,40 +181,13 @@ int rsdsfm_denoise_auto_video_dev(rsdsfm_ctx* ctx, const uint8_t* const* d_frame
                                   uint8_t* const* d_out_masks, uint8_t* const* d_out_weights_or_null, uint8_t* const* d_out_supports_or_null, int64_t* counts_or_null,
                                   uint64_t* noise_records_or_null) {
     if (!ctx) return RSDSFM_ERR_INVALID;
-    Ctx* c = &ctx->c;
-    DeviceGuard device_guard_(c);
-    const char* const stage = "denoise auto video";
-    ClipOutputs outs;
-    outs.planes[0] = d_out_images;
-    outs.planes[1] = d_out_masks;
-    outs.planes[2] = d_out_weights_or_null;
-    outs.planes[3] = d_out_supports_or_null;
-    int rc = clip_arrays_check(c, stage, d_frames, nsources, d_depth_maps, d_R, d_t, A, c_, A_path, c_path, scales, outs, "its weight and support planes when the arrays are passed");
-    if (rc != RSDSFM_OK) return rc;
-    rsdsfm_denoise_params dp;  // the radius of the walk is the temporal stage's
-    if (!denoise_params_resolve(params_or_null, &dp)) return fail(c, RSDSFM_ERR_INVALID, kDenoiseParamsMessage);
+    DeviceGuard device_guard_(&ctx->c);
     rsdsfm_noise_params np;
-    if (!noise_params_resolve(noise_or_null, &np)) return fail(c, RSDSFM_ERR_INVALID, kNoiseParamsMessage);
-    rsdsfm_denoise_spatial_params sp;
-    if (!spatial_params_resolve(spatial_or_null, &sp)) return fail(c, RSDSFM_ERR_INVALID, kSpatialParamsMessage);
-    if (d_out_supports_or_null && !spatial_or_null) return noise_fail(c, stage, "the support planes need the top-up's parameters");
-    // a frame's ten device words, [counts: 6][record: 4], when the caller asks for either: one copy and one wait for both
-    constexpr int kWords = 10;
-    const bool wanted = counts_or_null || noise_records_or_null;
-    std::vector<int64_t> host(wanted ? (size_t)kWords * (size_t)nsources : 0);
-    rc = walk_clip(c, stage, d_frames, nsources, d_depth_maps, d_R, d_t, A, c_, A_path, c_path, scales, dp.radius, outs, kWords, wanted ? host.data() : nullptr,
-                   [&](const ClipFrame& f) {
-                       return rsdsfm_denoise_auto_frame_dev(ctx, f.img, channels, f.map, f.R, f.t, fx, fy, cx, cy, rows, cols, mode, q5_mode, iterations, f.plan->nsrc, f.plan->M,
-                                                            f.plan->m, params_or_null, noise_or_null, spatial_or_null, window_or_null, f.out[0], f.out[1], f.out[2], f.out[3],
-                                                            f.d_counts, f.d_counts ? reinterpret_cast<uint64_t*>(f.d_counts + 6) : nullptr);
-                   });
-    if (rc != RSDSFM_OK || !wanted) return rc;
-    for (int q = 0; q < nsources; ++q) {
-        const int64_t* w = host.data() + (size_t)kWords * (size_t)q;
-        for (int k = 0; k < 6 && counts_or_null; ++k) counts_or_null[6 * (size_t)q + k] = w[k];
-        for (int k = 0; k < 4 && noise_records_or_null; ++k) noise_records_or_null[4 * (size_t)q + k] = (uint64_t)w[6 + k];
-    }
-    return RSDSFM_OK;
+    return estimated_clip(ctx, "denoise auto video",
+                          EstimatedClip{d_frames, nsources, rows, cols, channels, fx, fy, cx, cy, d_depth_maps, d_R, d_t, A, c_, A_path, c_path, scales, mode, q5_mode, iterations,
+                                        params_or_null, spatial_or_null, window_or_null, d_out_images, d_out_masks, d_out_weights_or_null, d_out_supports_or_null, counts_or_null,
+                                        noise_records_or_null},
+                          noise_params_resolve(noise_or_null, &np) ? nullptr : kNoiseParamsMessage, 4, [&](const EstimatedFrame& f) { return auto_frame(ctx, f, noise_or_null); });
 }
 
 }  // extern "C"

@@ -216,6 +216,8 @@ __global__ __launch_bounds__(kBP) void denoise_spatial_auto_kernel(const unsigne
                                                                   unsigned target, unsigned char* __restrict__ out, unsigned char* __restrict__ support,
                                                                   unsigned long long* __restrict__ counts) {
     const unsigned strength = noise_strength_dev(noise4, scale, min_samples, fallback);  // (uniform)
+#define RSDSFM_SPATIAL_HN_SETUP const unsigned hn = strength * (unsigned)CH;
+#define RSDSFM_SPATIAL_HN(j) hn
 #include "denoise_spatial_body.hpp"
 }
 
